@@ -21,9 +21,21 @@ A "ray" is one traceBVH / traceBVHShadow call of the reference's shader for this
 (SURVEY.md 8d), counted by the library's work counters in a separate, untimed pass and checked
 against the oracle's count on the CPU sample.
 
-Self-check: the timed run submits frames in batches (rt_render_frames); afterwards the same frame
-indices are rendered again one rt_render_frame at a time and the COLOR0 targets of the last frame
-are compared (sha256).  A mismatch ends the run with a non-zero exit code.
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed
+steps, the work counters (over the first COUNT_FRAMES timed frames), `--dump-outputs DIR` if given,
+and the JSON line.  `--full` adds every side measurement and check below, as one line.
+
+Self-check (--full): the timed run submits frames in batches (rt_render_frames); afterwards the same
+frame indices are rendered again one rt_render_frame at a time and the COLOR0 targets of the last
+frame are compared (sha256).  A mismatch ends the run with a non-zero exit code.  Also under --full:
+work counters over every timed frame, stage spans and the roofline, the one-launch-set-in-flight and
+merged-access passes, parity of the last timed frame against the oracle, the reference's default
+camera, the CPU baseline and run B of BASELINE configs[2].
+
+--dump-outputs DIR: the four render targets of the last timed frame, as a caller of rt_render_frames
+receives them (half floats, written as float32 DIR/<target>.npy of shape [H, W, C]); frames whose
+targets exceed DUMP_BUDGET_BYTES are written as a fixed, seeded sample of pixels ([K, C] per target,
+flat pixel indices y * W + x in DIR/pixel_index.npy).  The inputs depend on the arguments only.
 """
 import argparse
 import hashlib
@@ -48,6 +60,9 @@ HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8
 CUS, PEAK_CLOCK_HZ = 256, 2.4e9
 L1_ACCESS_PEAK_G = CUS * PEAK_CLOCK_HZ / 1e9
 W, H, SPP = 1920, 1080, 4
+COUNT_FRAMES = 16                    # plain run: timed frames the work counters are taken over (--full: all of them)
+DUMP_BUDGET_BYTES = 60 * 2**20       # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240601
 
 
 TRAVERSAL_SOURCES = ("rt_wave.hip", "rt_wave.hpp", "rt_api.hip", "rt_frame.hpp", "rt_device_shade.hpp", "rt_device_math.hpp", "rt_device_analytic.hpp")
@@ -86,10 +101,15 @@ def parse_args(argv=None):
     ap.add_argument("--obj", action="append", default=[], help="render this .obj instead of the stand-in (repeat to merge several files into one "
                     "triangle soup): rt_load_obj -> rt_gather_triangles_checked with the reference's default transform -> rt_build_bvh")
     ap.add_argument("--pipeline", default="auto", choices=["auto", "mega", "wave"])
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of EACH oracle (CPU baseline) sample -- one thread, then all cores; 0 = skip")
+    ap.add_argument("--full", action="store_true", help="every side measurement and check beside the headline figure (see the module docstring); "
+                    "a plain run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the render targets of the last timed frame as DIR/<target>.npy "
+                    "(float32; a fixed, seeded pixel sample when the frame is larger than the budget)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="budget of EACH oracle (CPU baseline) sample -- one thread, then all cores; 0 = skip "
+                    "(default: 10 with --full, else 0)")
     ap.add_argument("--no-default-camera", action="store_true")
     ap.add_argument("--batch", type=int, default=8, help="frames per rt_render_frames call: consecutive frames of the static camera share one set of "
-                    "kernel launches (bit-identical to frame-by-frame rendering: checked in every run, see config.batched_equals_frame_by_frame); "
+                    "kernel launches (bit-identical to frame-by-frame rendering: checked in every --full run, see config.batched_equals_frame_by_frame); "
                     "1 = one rt_render_frame per step")
     ap.add_argument("--no-frame-by-frame", action="store_true", help="skip the frame-by-frame pass (and with it the self-check); used under rocprofv3 so "
                     "that the kernel statistics hold batched launches only")
@@ -114,12 +134,31 @@ def parse_args(argv=None):
     ap.add_argument("--hybrid", action="store_true", help="EXTENSION (not in the reference; SURVEY 8d config 3 run B): the analytic scene "
                     "(floor, glass / mirror / diffuse spheres) with the mesh added to it, reference default camera")
     ap.add_argument("--gi-bounces", type=int, default=1, help="EXTENSION: diffuse bounces of the analytic / hybrid GI path (configs[2]: 4)")
-    ap.add_argument("--parity-window", default="256x128", help="WxH of the oracle window around the frame centre that the last timed frame is compared "
-                    "with after the timed run (full history chain from frame 0, all host threads); 0 = skip the parity block")
+    ap.add_argument("--parity-window", default=None, help="WxH of the oracle window around the frame centre that the last timed frame is compared "
+                    "with after the timed run (full history chain from frame 0, all host threads); 0 = skip the parity block (default: 256x128 with "
+                    "--full, else 0)")
     ap.add_argument("--no-run-b", action="store_true", help="skip the short side measurement of BASELINE configs[2] as written (\"run B\": bunny + glass + mirror, "
                     "16 spp, 4 bounces -- the labelled hybrid EXTENSION) that the default line carries in `extension_run_b`")
     ap.add_argument("--n1-ms", type=float, default=None, help="N > 1: ms_per_step of the same workload on one GPU -> config.multi_gpu.efficiency_vs_n1")
     return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, targets, names):
+    """targets: [H, W, C] uint16 half bit patterns -> out_dir/<name>.npy as float32 (exact).  Above DUMP_BUDGET_BYTES: the same fixed, seeded
+    sample of pixels from every target ([K, C]), with their flat indices y * W + x in out_dir/pixel_index.npy (float64, exact)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrs = [np.ascontiguousarray(t).view(np.float16).astype(np.float32) for t in targets]
+    h, w = arrs[0].shape[:2]
+    px_bytes = sum(a.shape[2] for a in arrs) * 4
+    if h * w * px_bytes > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // (px_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=k, replace=False))
+        np.save(out_dir / "pixel_index.npy", idx.astype(np.float64))
+        arrs = [a.reshape(h * w, -1)[idx] for a in arrs]
+    for a, name in zip(arrs, names):
+        np.save(out_dir / ("%s.npy" % name), a)
 
 
 def free_port():
@@ -181,6 +220,13 @@ def main():
         raise SystemExit(self_launch(args, argv))
     if args.dry_launch:
         raise SystemExit("bench.py: --dry-launch needs --gpus N > 1 and no WORLD_SIZE in the environment")
+    # a plain run: no side measurements or checks unless asked for one by value (--cpu-seconds S, --parity-window WxH)
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 10.0 if args.full else 0.0
+    if args.parity_window is None:
+        args.parity_window = "256x128" if args.full else "0"
+    if not args.full:
+        args.no_default_camera = args.no_diagnostics = args.no_run_b = args.no_frame_by_frame = True
     global W, H, SPP
     W, H = (int(v) for v in args.size.lower().split("x"))
     SPP = args.spp
@@ -255,12 +301,14 @@ def main():
 
     def run_camera(cam, steps, warmup, timed_stage=True, check=False):
         """-> dict(seconds, counters summed over the timed frames, stage times, ...)"""
-        # untimed counting pass over the same frame indices (work counters slow the kernels down)
+        # untimed counting pass over the same frame indices (work counters slow the kernels down); a plain run counts the first
+        # COUNT_FRAMES timed frames, so that its cost does not grow with --steps
+        n_count = steps if args.full else min(steps, COUNT_FRAMES)
         rc = make_renderer(True)
         for f in range(warmup):
             rc.render_frame(uniforms(cam, f))
         rc.reset_counters()
-        for f in range(warmup, warmup + steps):
+        for f in range(warmup, warmup + n_count):
             rc.render_frame(uniforms(cam, f))
         cnt = rc.counters()
         rc.close()
@@ -352,13 +400,13 @@ def main():
         # what the parity block compares with the oracle: one GPU -- all four targets of the last timed frame; tile-parallel -- the COLOR0
         # frame rank 0 assembled from every rank's tiles in the last gather (so the exchange itself is inside the comparison)
         final_targets = None
-        if parity_wanted and timed_stage:
+        if (parity_wanted or args.dump_outputs) and timed_stage:
             if multi:
                 final_targets = [gatherer.frame_halfs()] if rank == 0 else None
             else:
                 final_targets = ren.read_all()
         stage_frames, stage_traced = steps, traced
-        if timed_stage and not events_in_timed_region:
+        if timed_stage and not events_in_timed_region and args.full:
             # the same batches once more, untimed, with the stage events on: spans of the stages while launch sets overlap (the targets have been read above)
             n_extra = min(2 * B, warmup + steps)
             ren.traced_rays(reset=True)
@@ -418,7 +466,7 @@ def main():
         traced_per_frame = int(tr[0].item()) // frames_all if traced.frames else 0
         return {"seconds": float(tt.item()), "seconds_own": dt_own, "memory": mem, "stage_frames": stage_frames, "stage_traced": stage_traced, "events_in_timed_region": bool(events_in_timed_region), "comm": comm, "gather_py": gather_py, "final_targets": final_targets, "frames_u": frames_u,
                 "counters": total, "local_counters": cnt, "stages": stages,
-                "traced_per_frame": traced_per_frame, "traced": traced, "scene_info": info, "counted_frames": steps,
+                "traced_per_frame": traced_per_frame, "traced": traced, "scene_info": info, "counted_frames": n_count,
                 "batched_hash": batched_hash, "fbf_hash": fbf_hash, "fbf_ms": fbf_ms, "same": bool(same.item()) if check else None,
                 "assembled_same": assembled_same}
 
@@ -433,6 +481,8 @@ def main():
     pw = [int(v) for v in args.parity_window.lower().split("x")] if args.parity_window not in ("0", "", "0x0") else None
     parity_wanted = pw is not None
     res = run_camera(scenes.camera(cam_kind), args.steps, args.warmup, check=check)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["final_targets"], ("color", "motion", "gpos", "gnrm")[:len(res["final_targets"])])
 
     # ---- diagnostics, untimed, single GPU: (1) one launch set in flight (RT_LANES=1) in the SAME batched mode as the timed run: what each
     # stage costs when it has the GPU to itself -- with 3-4 batches in flight an event span also contains the time a kernel shares the GPU
@@ -471,7 +521,7 @@ def main():
                 else:
                     os.environ[k] = v
 
-    rays = res["counters"].rays
+    rays = res["counters"].rays * args.steps / res["counted_frames"]      # reference rays of the timed frames
     mray = rays / res["seconds"] / 1e6
     ms_per_step = res["seconds"] / args.steps * 1e3
 
@@ -602,8 +652,10 @@ def main():
                    "self_check": ("COLOR0 of frame %d (last timed frame) after the batched run == after one rt_render_frame per frame over the same frame "
                                   "indices, sha256 of the RGBA16F bits%s" % (args.warmup + args.steps - 1, ", every rank its own tiles" if world > 1 else "")) if check else None,
                    "ms_per_step_frame_by_frame": res["fbf_ms"],
-                   "rays_per_frame": rays // args.steps, "msample_per_s": npix * SPP * args.steps / res["seconds"] / 1e6,
-                   "hit_pixels": res["counters"].hitPixels // args.steps,
+                   "rays_per_frame": res["counters"].rays // res["counted_frames"], "msample_per_s": npix * SPP * args.steps / res["seconds"] / 1e6,
+                   "hit_pixels": res["counters"].hitPixels // res["counted_frames"],
+                   "rays_counted_frames": res["counted_frames"],
+                   "full": bool(args.full),
                    "rays_traversed_per_frame": res["traced_per_frame"],
                    "ray_accounting": "value counts the reference shader's traceBVH/traceBVHShadow calls (SURVEY 8d); "
                                      "identical rays (SPP copies of the primary and AO rays) are traversed once and disk-light "
@@ -696,9 +748,9 @@ def main():
 
     if not args.no_default_camera and not args.hybrid:
         d = run_camera(scenes.camera("default"), args.steps, args.warmup, timed_stage=False)
-        out["default_camera"] = {"value": d["counters"].rays / d["seconds"] / 1e6, "unit": "Mray/s",
-                                 "ms_per_step": d["seconds"] / args.steps * 1e3, "rays_per_frame": d["counters"].rays // args.steps,
-                                 "hit_pixels": d["counters"].hitPixels // args.steps}
+        out["default_camera"] = {"value": d["counters"].rays * args.steps / d["counted_frames"] / d["seconds"] / 1e6, "unit": "Mray/s",
+                                 "ms_per_step": d["seconds"] / args.steps * 1e3, "rays_per_frame": d["counters"].rays // d["counted_frames"],
+                                 "hit_pixels": d["counters"].hitPixels // d["counted_frames"]}
 
     if rank == 0 and world == 1 and args.cpu_seconds > 0:
         import tempfile
@@ -737,10 +789,10 @@ def main():
                                        "frame times (frame_seconds_estimate vs ms_per_step), or value_traversed, not the two Mray/s figures"}
     # ---- BASELINE configs[2] AS WRITTEN ("bunny + glass + mirror materials ..., 16 spp, 4 bounces": run B).  The reference cannot express it (rt.frag:84-163: its BVH
     # mode has no analytic objects or materials, its analytic mode no mesh, both one bounce), so it exists here only as the labelled hybrid EXTENSION, with
-    # parity against this repository's own oracle.  The default line carries a short measurement of it so that the driver's record shows both runs; configs[2] / [3] are
+    # parity against this repository's own oracle.  The --full line carries a short measurement of it so that the record shows both runs; configs[2] / [3] are
     # still REPORTED as run A (`--spp 16`).  A child process of this command (the same bench.py with --hybrid); its failure does not fail the line.
     if rank == 0 and world == 1 and headline and not args.no_run_b:
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--hybrid", "--spp", "16", "--gi-bounces", "4", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0",
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--hybrid", "--spp", "16", "--gi-bounces", "4", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0",
                "--no-default-camera", "--no-frame-by-frame", "--no-diagnostics", "--no-run-b", "--parity-window", "32x16"]
         try:
             r_b = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=240)

@@ -1,12 +1,15 @@
 """bench.py's output contract, on a small variant of the workload (the driver runs the default line itself): ONE JSON line with the
 metric keys, a physical roofline (0 < frac <= 1 against the HBM peak AND against the L1 access ceiling beside it), the launch duration
 from real launches, the batched-vs-frame-by-frame self-check, the CPU baseline with one thread and all cores from the -O3 -march=native
-oracle build, and value / value_traversed consistent with ms_per_step.  Also: a supplied .obj drives the same line (--obj), and the
-self-launcher brings up the tile-parallel code path (process group, RCCL communicator, gather) with a world of one."""
+oracle build, and value / value_traversed consistent with ms_per_step -- all of it under --full.  Also: a supplied .obj drives the same
+line (--obj), the self-launcher brings up the tile-parallel code path (process group, RCCL communicator, gather) with a world of one, and a
+plain run (no --full) prints the headline keys only and writes the last timed frame's targets with --dump-outputs."""
+import hashlib
 import json
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import opengl_raytracing_amd as rt
@@ -25,8 +28,8 @@ def _bench(args, timeout=600):
     return json.loads(lines[0])
 
 
-def test_bench_line_contract():
-    d = _bench(SMALL + ["--cpu-seconds", "0.5"])
+def test_bench_line_contract(tmp_path):
+    d = _bench(SMALL + ["--full", "--cpu-seconds", "0.5", "--dump-outputs", str(tmp_path / "out")])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline", "value_traversed"):
         assert k in d, k
@@ -60,6 +63,11 @@ def test_bench_line_contract():
     b = d["cpu_baseline"]
     assert b["kind"] == "port" and b["cores"] >= 1 and b["value"] > 0 and b["single_thread"]["cores"] == 1 and b["single_thread"]["value"] > 0
     assert "-O3 -march=native" in b["sample"]
+    assert c["full"] is True and c["rays_counted_frames"] == 6
+    # the dumped COLOR0 is the frame the self-check hashed
+    color = np.load(tmp_path / "out" / "color.npy")
+    assert color.dtype == np.float32 and color.shape == (360, 640, 4)
+    assert hashlib.sha256(color.astype(np.float16).view(np.uint16).tobytes()).hexdigest() == c["color0_sha256"]
 
 
 def test_bench_obj_line_equals_the_standin_line(tmp_path):
@@ -68,7 +76,7 @@ def test_bench_obj_line_equals_the_standin_line(tmp_path):
     v, f = rt.meshgen.bunny_standin(4)
     obj = tmp_path / "standin.obj"
     rt.meshgen.write_obj(obj, v, f)
-    common = SMALL + ["--cpu-seconds", "0", "--no-default-camera", "--no-diagnostics"]
+    common = SMALL + ["--full", "--cpu-seconds", "0", "--no-default-camera", "--no-diagnostics"]
     a = _bench(common)
     b = _bench(common + ["--obj", str(obj)])
     for k in ("rays_per_frame", "hit_pixels", "rays_traversed_per_frame", "color0_sha256"):
@@ -80,7 +88,7 @@ def test_bench_obj_line_equals_the_standin_line(tmp_path):
 def test_bench_self_launch_rehearsal_world_of_one():
     """--launch --force-gather: bench.py starts torch.distributed.run itself (as it does for --gpus N > 1), the rank brings up the process group
     and the library's RCCL communicator and gathers after every batch."""
-    d = _bench(SMALL + ["--cpu-seconds", "0", "--no-default-camera", "--launch", "--force-gather", "--gpus", "1"])
+    d = _bench(SMALL + ["--full", "--cpu-seconds", "0", "--no-default-camera", "--launch", "--force-gather", "--gpus", "1"])
     assert d["n_gpus"] == 1 and d["config"]["gather"]["path"].startswith("library-owned RCCL")
     assert d["config"]["batched_equals_frame_by_frame"] is True
     # the self-diagnosing N-GPU block (VERDICT r03 item 3), here for a world of one over a real RCCL communicator
@@ -99,7 +107,8 @@ def test_bench_ranks_as_processes_on_one_gpu(ranks):
     the group is gloo and the gathers are staged through the host (RCCL refuses two ranks on one device).  What this covers that no
     one-process test can: the launch, RANK / WORLD_SIZE handling, barriers and max-over-ranks timing, counters summed over ranks, one gather
     per batch from N processes -- and rank 0 compares the assembled frame with the one a single context renders, bit for bit."""
-    d = _bench(SMALL + ["--cpu-seconds", "0", "--no-default-camera", "--no-diagnostics", "--gpus", str(ranks), "--rehearse-one-gpu", "--n1-ms", "1.0"], timeout=900)
+    d = _bench(SMALL + ["--full", "--cpu-seconds", "0", "--no-default-camera", "--no-diagnostics", "--gpus", str(ranks), "--rehearse-one-gpu", "--n1-ms", "1.0"],
+               timeout=900)
     assert d["n_gpus"] == ranks and d["scaling"] == "strong"
     c = d["config"]
     assert "gloo" in c["gather"]["path"] and "error" not in c["gather"]
@@ -116,3 +125,25 @@ def test_bench_ranks_as_processes_on_one_gpu(ranks):
     one = _bench(SMALL + ["--cpu-seconds", "0", "--no-default-camera", "--no-diagnostics"])
     assert c["rays_per_frame"] == one["config"]["rays_per_frame"]   # the ranks' reference-unit counters add up to the whole frame's
     assert c["hit_pixels"] == one["config"]["hit_pixels"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the headline keys, none of the side measurements or checks, the work counters over the first 16 timed frames, and
+    --dump-outputs writes the four targets of the last timed frame -- identical from run to run with the same arguments."""
+    args = ["--steps", "20", "--warmup", "2", "--size", "640x360", "--subdiv", "4"]
+    a = _bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in a, k
+    assert a["unit"] == "Mray/s" and a["higher_is_better"] is True and a["dtype"] == "f32" and a["steps"] == 20 and a["warmup"] == 2
+    c = a["config"]
+    assert c["full"] is False and c["rays_counted_frames"] == 16 and c["batched_equals_frame_by_frame"] is None
+    assert a["roofline"] is None and a["parity"] is None
+    for k in ("cpu_baseline", "default_camera", "extension_run_b", "stage_ms_per_frame"):
+        assert k not in a, k
+    assert abs(a["value"] - c["rays_per_frame"] / (a["ms_per_step"] * 1e-3) / 1e6) / a["value"] < 0.02
+    b = _bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    for name, ch in (("color", 4), ("motion", 2), ("gpos", 4), ("gnrm", 4)):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == (360, 640, ch), name
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), name
+    assert not (tmp_path / "a" / "pixel_index.npy").exists()

@@ -8,9 +8,9 @@ fi
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 bash tools/r03_profile.sh $TAG trace pmc_bunny pmc_1m > $OUT/profile.log 2>&1; tail -2 $OUT/profile.log
 python3 tools/r05_summarize.py $TAG > /dev/null 2>&1     # copies the traffic stamps into profiles/ (of this scratch copy) so that the bench lines below carry them
-timeout -k 10 400 python3 bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench rc $?"
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_like.json 2> $OUT/bench_driver_like.err; echo "bench (driver-like) rc $?"
-timeout -k 10 300 python3 bench.py --scene 1m --steps 20 --warmup 3 --cpu-seconds 0 --no-default-camera > $OUT/bench_line_1m.json 2>/dev/null; echo "bench 1m rc $?"
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench rc $?"
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_like.json 2> $OUT/bench_driver_like.err; echo "bench (driver-like) rc $?"
+timeout -k 10 300 python3 bench.py --full --scene 1m --steps 20 --warmup 3 --cpu-seconds 0 --no-default-camera > $OUT/bench_line_1m.json 2>/dev/null; echo "bench 1m rc $?"
 python3 - <<PY
 import json
 for f in ("bench_line", "bench_driver_like", "bench_line_1m"):

@@ -3,7 +3,7 @@
 # One small counter set per rocprofv3 pass over bench.py --hybrid; the program itself after "--"; no tracing options beside --pmc.
 TAG=${1:-r05hp}; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--hybrid --spp 16 --gi-bounces 4 --steps 3 --warmup 1 --cpu-seconds 0 --no-default-camera --no-frame-by-frame --parity-window 0 --no-diagnostics"
+ARGS="--full --hybrid --spp 16 --gi-bounces 4 --steps 3 --warmup 1 --cpu-seconds 0 --no-default-camera --no-frame-by-frame --parity-window 0 --no-diagnostics"
 SETS=(
  "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE"
  "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"

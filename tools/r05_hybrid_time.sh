@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 5: run B (1080p, 16 spp, 4 bounces) ms per step + stage split of the staged hybrid pipeline per environment setting:  tools/r05_hybrid_time.sh <tag> "VAR=val" ...
 TAG=$1; shift; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R
-ARGS="--hybrid --spp 16 --gi-bounces 4 --steps 6 --warmup 2 --cpu-seconds 0 --no-default-camera --no-frame-by-frame --no-diagnostics --parity-window 64x32"
+ARGS="--full --hybrid --spp 16 --gi-bounces 4 --steps 6 --warmup 2 --cpu-seconds 0 --no-default-camera --no-frame-by-frame --no-diagnostics --parity-window 64x32"
 for V in "$@"; do
   [ "$V" == "-" ] && V="A=0"
   echo "=== [$V]" | tee -a $OUT/hybrid.log

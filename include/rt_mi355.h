@@ -339,9 +339,29 @@ int rt_debug_eval(RtContext *ctx, int op, const float *a, const float *b, const 
 /* Trace n rays against the uploaded BVH with the device traversal: kind 0 = closest hit (out: t, then
  * hit point xyz, then normal xyz; t = inf on miss), kind 1 = any hit within tMax (out[0] = 1/0).
  * kinds 2 / 3: the same two questions put to the wavefront pipeline's own traversal kernels (persistent launch, refill scheduler, the
- * any-hit node form rt_upload_bvh chose) -- kind 2: out[0] = t (inf on miss), out[1] = index of the triangle hit; kind 3: out[0] = 1/0. */
+ * any-hit node form rt_upload_bvh chose, the kernel build the environment selects for frames) -- kind 2: out[0] = t (inf on miss), out[1] = index of the
+ * triangle hit; kind 3: out[0] = 1/0.
+ * kind 4: any-hit rays through the packet kernel of RT_PACKET_AO (k_trace_packets), out[0] = 1/0 as kind 3.  n must be a multiple of four: rays 4 p .. 4 p + 3
+ * form packet p, which leaves from the origin of its first ray (the caller guarantees that all four share it, as the AO rays of one hit do); a ray with
+ * tMax < 0 is an empty slot (out[0] = 0), so packets of one to three live rays can be expressed. */
 int rt_debug_trace(RtContext *ctx, int kind, const float *origins, const float *dirs, const float *tMax, float eps,
                    float inf, float *out7, int n);
+/* Which traversal kernel builds ran: the RT_BUILD_* bits of every k_trace / k_trace_packets launch of this context's wavefront frames and of
+ * rt_debug_trace kinds 2 - 4 since the last reset, ORed -- bits [0, 16) for the closest-hit launches, the same bits << RT_BUILD_ANY_SHIFT for the
+ * any-hit launches.  Host-side bookkeeping at launch time: no synchronisation, no device work. */
+#define RT_BUILD_LAUNCHED 0x001   /* a k_trace build ran */
+#define RT_BUILD_LEAFB4   0x002   /* four-triangle leaf groups (RT_LEAFB / RT_LEAFB_CLOSEST = 4) */
+#define RT_BUILD_STATS    0x004   /* counting build (RT_TRACE_STATS) */
+#define RT_BUILD_COOP     0x008   /* quad-cooperative node fetch (RT_COOP) */
+#define RT_BUILD_NEAR     0x010   /* near-first any-hit walk (RT_NEAR_FIRST) */
+#define RT_BUILD_QN1      0x020   /* quantised any-hit nodes, seven-wave build (RT_QNODES=1) */
+#define RT_BUILD_QN2      0x040   /* quantised any-hit nodes (RT_QNODES=2, or chosen by rt_upload_bvh) */
+#define RT_BUILD_FUSE     0x080   /* fused closest-hit records (RT_FUSED) */
+#define RT_BUILD_IMPL     0x100   /* implicit records (RT_IMPLICIT) */
+#define RT_BUILD_TIMING   0x200   /* time-stamped production build (RT_TRACE_TIMING) */
+#define RT_BUILD_PACKETS  0x400   /* (any-hit half) the packet kernel k_trace_packets ran (RT_PACKET_AO, rt_debug_trace kind 4) */
+#define RT_BUILD_ANY_SHIFT 16
+int rt_debug_builds(RtContext *ctx, uint32_t *out, int reset);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

@@ -154,6 +154,10 @@ class RtExtension(_Struct):
 
 RT_SCENE_HYBRID = 2   # RtUniforms.useBVH: the analytic scene + the BVH mesh (extension, not in the reference)
 RT_SCENE_QNODES_REJECTED, RT_SCENE_NOT_FUSED, RT_SCENE_IMPLICIT = 1, 2, 4   # RtSceneInfo.flags
+# rt_debug_builds: RT_BUILD_* bits of the traversal kernel builds launched (closest-hit half; the any-hit half << RT_BUILD_ANY_SHIFT)
+RT_BUILD_BITS = {"k_trace": 0x001, "LEAFB4": 0x002, "STATS": 0x004, "COOP": 0x008, "NEAR": 0x010, "QN1": 0x020, "QN2": 0x040, "FUSE": 0x080,
+                 "IMPL": 0x100, "TIMING": 0x200, "PACKETS": 0x400}
+RT_BUILD_ANY_SHIFT = 16
 
 
 class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
@@ -219,6 +223,7 @@ SIGNATURES = {
     "rt_stage_name": (C.c_char_p, [C.c_int]),
     "rt_debug_eval": (C.c_int, [C.c_void_p, C.c_int, _FP, _FP, _FP, _U32P, C.c_int]),
     "rt_debug_trace": (C.c_int, [C.c_void_p, C.c_int, _FP, _FP, _FP, C.c_float, C.c_float, _FP, C.c_int]),
+    "rt_debug_builds": (C.c_int, [C.c_void_p, _U32P, C.c_int]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
     "rt_default_camera": (None, [C.POINTER(RtCamera)]),
     "rt_default_bvh_transform": (None, [_FP]),
@@ -690,6 +695,14 @@ class Renderer:
         out = np.zeros((o.shape[0], 7), np.float32)
         self._check(lib().rt_debug_trace(self._h, kind, _fp(o), _fp(d), _fp(t), eps, inf, _fp(out), o.shape[0]))
         return out
+
+    def debug_builds(self, reset=True) -> dict:
+        """The traversal kernel builds launched since the last reset (frames and debug_trace kinds 2 - 4), as
+        {"closest": frozenset of RT_BUILD_BITS names, "any": ...}."""
+        v = C.c_uint32(0)
+        self._check(lib().rt_debug_builds(self._h, C.byref(v), 1 if reset else 0))
+        half = lambda b: frozenset(n for n, m in RT_BUILD_BITS.items() if b & m)
+        return {"closest": half(v.value & 0xFFFF), "any": half(v.value >> RT_BUILD_ANY_SHIFT)}
 
 
 def frame_uniforms(params, cam, w, h, frame_index, use_bvh, node_count=0, tri_count=0, prev_vp=None, env_loaded=True,

@@ -81,6 +81,7 @@ struct RtContext {
     RtArenaPool *arenaPool = nullptr;   // ray-queue arenas shared by the lanes' wavefront pipelines
     RtHybrid *hybrid[RT_MAX_LANES] = {};   // EXTENSION: staged hybrid pipeline, created on first use
     int cus = 256;
+    uint32_t debugBuilds = 0;   // RT_BUILD_* bits of the rt_debug_trace kind 2 - 4 launches since the last rt_debug_builds reset
     int giBounces = 1;   // EXTENSION, rt_set_extension
     int envFilter = 0;   // rt_set_extension: cube-map filter model (0 exact fp32 weights, 1 coordinates rounded to 1/256 texel)
     // tile-parallel exchange owned by the library (rt_comm.cpp): RCCL communicator + per-lane gather buffers on the gathering rank
@@ -1559,14 +1560,19 @@ int rt_debug_eval(RtContext *c, int op, const float *a, const float *b, const fl
     return RT_OK;
 }
 
-// kinds 2 / 3: the same rays through the wavefront pipeline's traversal kernels (k_trace, as the frames launch it)
-static int debug_trace_wave(RtContext *c, bool any, const float *origins, const float *dirs, const float *tMax, float eps, float inf, float *out7, int n) {
+// kinds 2 / 3: the same rays through the wavefront pipeline's traversal kernels (k_trace, as the frames launch it); kind 4: any-hit rays four at a time
+// through the packet kernel (k_trace_packets), ray r of packet p = input ray 4 p + r stored at [r * n / 4 + p] as PacketSrc reads it
+static int debug_trace_wave(RtContext *c, int kind, const float *origins, const float *dirs, const float *tMax, float eps, float inf, float *out7, int n) {
     if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_INVALID, "rt_debug_trace: no BVH uploaded");
+    const bool any = kind != 2, packets = kind == 4;
+    const size_t P = (size_t)n / 4;
+    auto at = [&](int i) { return packets ? (size_t)(i % 4) * P + (size_t)(i / 4) : (size_t)i; };   // device address of input ray i
     std::vector<float> o4((size_t)n * 4, 0.0f), d4((size_t)n * 4, 0.0f), tm((size_t)n, inf);
     for (int i = 0; i < n; ++i) {
-        std::memcpy(&o4[(size_t)i * 4], origins + (size_t)i * 3, 12);
-        std::memcpy(&d4[(size_t)i * 4], dirs + (size_t)i * 3, 12);
-        if (any) tm[(size_t)i] = tMax[i];
+        const size_t a = at(i);
+        std::memcpy(&o4[a * 4], origins + (size_t)i * 3, 12);
+        std::memcpy(&d4[a * 4], dirs + (size_t)i * 3, 12);
+        if (any) tm[a] = tMax[i];
     }
     std::vector<unsigned char> hostBytes(sizeof(DevFrame), 0);
     DevFrame *host = reinterpret_cast<DevFrame *>(hostBytes.data());
@@ -1583,13 +1589,14 @@ static int debug_trace_wave(RtContext *c, bool any, const float *origins, const 
     bool ok = hipMalloc(&dO, (size_t)n * 16) == hipSuccess && hipMalloc(&dD, (size_t)n * 16) == hipSuccess && hipMalloc(&dT, (size_t)n * 4) == hipSuccess &&
               hipMalloc(&dOutT, (size_t)n * 4) == hipSuccess && hipMalloc(&dTri, (size_t)n * 4) == hipSuccess && hipMalloc(&dOcc, (size_t)n) == hipSuccess &&
               hipMalloc(&dCnt, 4) == hipSuccess && hipMalloc(&dHeads, rt_wave_head_words() * 4) == hipSuccess && hipMalloc(&dF, sizeof(DevFrame)) == hipSuccess;
-    const uint32_t un = (uint32_t)n;
+    const uint32_t un = (uint32_t)n, live = packets ? (uint32_t)P : un;   // queue entries: rays, or packets
     ok = ok && hipMemcpy(dO, o4.data(), (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dD, d4.data(), (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dT, tm.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dCnt, &un, 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(dT, tm.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dCnt, &live, 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemset(dHeads, 0, rt_wave_head_words() * 4) == hipSuccess && hipMemset(dOcc, 0, (size_t)n) == hipSuccess && hipMemset(dTri, 0xff, (size_t)n * 4) == hipSuccess &&
          hipMemcpy(dF, host, sizeof(DevFrame), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { freeAll(); return fail(c, RT_ERR_HIP, "rt_debug_trace: allocation / upload failed"); }
-    rt_wave_debug_trace(c->stream, c->cus, c->treeDepth, dF, host->sc, any, dO, dD, dT, dCnt, un, dOutT, dTri, dOcc, dHeads);
+    c->debugBuilds |= packets ? rt_wave_debug_packets(c->stream, c->cus, c->treeDepth, dF, host->sc, dO, dD, dT, dCnt, (uint32_t)P, dOcc, dHeads)
+                              : rt_wave_debug_trace(c->stream, c->cus, c->treeDepth, dF, host->sc, any, dO, dD, dT, dCnt, un, dOutT, dTri, dOcc, dHeads);
     std::vector<float> t((size_t)n);
     std::vector<int> tri((size_t)n);
     std::vector<uint8_t> occ((size_t)n);
@@ -1600,16 +1607,16 @@ static int debug_trace_wave(RtContext *c, bool any, const float *origins, const 
     for (int i = 0; i < n; ++i) {
         float *out = out7 + (size_t)i * 7;
         for (int k = 0; k < 7; ++k) out[k] = 0.0f;
-        if (any) out[0] = occ[(size_t)i] ? 1.0f : 0.0f;
+        if (any) out[0] = occ[at(i)] ? 1.0f : 0.0f;
         else { out[0] = tri[(size_t)i] >= 0 ? t[(size_t)i] : inf; out[1] = (float)tri[(size_t)i]; }   // closest: t and the triangle's index in the reference order
     }
     return RT_OK;
 }
 
 int rt_debug_trace(RtContext *c, int kind, const float *origins, const float *dirs, const float *tMax, float eps, float inf, float *out7, int n) {
-    if (!c || !origins || !dirs || !out7 || n <= 0 || ((kind == 1 || kind == 3) && !tMax) || kind < 0 || kind > 3) return RT_ERR_INVALID;
+    if (!c || !origins || !dirs || !out7 || n <= 0 || ((kind == 1 || kind >= 3) && !tMax) || kind < 0 || kind > 4 || (kind == 4 && n % 4 != 0)) return RT_ERR_INVALID;
     (void)hipSetDevice(c->cfg.device);
-    if (kind >= 2) return guarded(c, "rt_debug_trace", [&]() -> int { return debug_trace_wave(c, kind == 3, origins, dirs, tMax, eps, inf, out7, n); });
+    if (kind >= 2) return guarded(c, "rt_debug_trace", [&]() -> int { return debug_trace_wave(c, kind, origins, dirs, tMax, eps, inf, out7, n); });
     float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dOut = nullptr;
     HIP_TRY(c, hipMalloc(&dO, (size_t)n * 12));
     HIP_TRY(c, hipMalloc(&dD, (size_t)n * 12));
@@ -1624,6 +1631,15 @@ int rt_debug_trace(RtContext *c, int kind, const float *origins, const float *di
     HIP_TRY(c, sync_all(c));
     HIP_TRY(c, hipMemcpy(out7, dOut, (size_t)n * 28, hipMemcpyDeviceToHost));
     (void)hipFree(dO); (void)hipFree(dD); (void)hipFree(dT); (void)hipFree(dOut);
+    return RT_OK;
+}
+
+int rt_debug_builds(RtContext *c, uint32_t *out, int reset) {
+    if (!c || !out) return RT_ERR_INVALID;
+    uint32_t b = c->debugBuilds;
+    for (int i = 0; i < RT_MAX_LANES; ++i) b |= rt_wave_builds(c->wave[i], reset != 0);
+    if (reset) c->debugBuilds = 0;
+    *out = b;
     return RT_OK;
 }
 

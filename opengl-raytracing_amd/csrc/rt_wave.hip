@@ -505,6 +505,25 @@ static TraceTune default_tune() {
     if (const char *e = getenv("RT_FUSED")) t.fused = atoi(e);
     return t;
 }
+// default_tune() with the scheduler and kernel-build options of the environment: what a context's frames launch (rt_wave_create) and what rt_debug_trace
+// kinds 2 - 4 launch (rt_wave_debug_trace / rt_wave_debug_packets), so that the per-ray tests walk the build a frame walks under the same environment.
+// RT_DEBUG_SKIP_TRAVERSAL is not read here: it skips the work, and only frames take it.
+static TraceTune tune_from_env() {
+    TraceTune t = default_tune();
+    if (const char *e = getenv("RT_REFILL_MIN")) t.refillMin = std::max(1, std::min(64, atoi(e)));
+    if (const char *e = getenv("RT_CHUNK")) { int v = atoi(e); t.chunk = v <= 0 ? 0 : std::max(8, std::min(1 << 20, v)); }   // 0 = from the queue size
+    if (const char *e = getenv("RT_LEAFB")) t.leafb = t.leafbClosest = atoi(e);
+    if (const char *e = getenv("RT_LEAFB_CLOSEST")) t.leafbClosest = atoi(e);
+    if (const char *e = getenv("RT_MIN_SEARCH")) t.minSearch = std::max(0, std::min(64, atoi(e)));
+    if (const char *e = getenv("RT_QUAD_REFILL")) t.quadRefill = atoi(e) != 0;
+    if (const char *e = getenv("RT_COOP")) t.coop = atoi(e);   // quad-cooperative node fetch of the closest-hit launches (measured option)
+    if (const char *e = getenv("RT_NEAR_FIRST")) t.nearFirst = atoi(e);
+    if (const char *e = getenv("RT_REVERSE")) t.reverse = atoi(e);      // 0: any-hit queues dealt from their beginning, as in rounds 1-3
+    if (const char *e = getenv("RT_GUIDED")) t.guided = atoi(e);
+    if (const char *e = getenv("RT_DENSE_TAKE")) t.denseTake = atoi(e);   // 0: every refill probes liveness first, as in rounds 2-3
+    if (const char *e = getenv("RT_QNODES")) t.qnodes = atoi(e);          // 0: never; 1 / 2: always (seven / six waves per SIMD); default: when rt_upload_bvh built them
+    return t;
+}
 
 // The slab test of rt_bvh.glsl:124-134 in two halves, so that the per-axis values of two child boxes can be merged into their parent's (k_trace, FUSE):
 // slab_parts + slab_eval are slab() operation for operation.
@@ -1119,6 +1138,15 @@ __global__ __launch_bounds__(256, (!STATS && !ANY) ? 5 : ((NEAR || QN == 2 || (I
     }
 }
 
+// A k_trace build with its RT_BUILD_* bits (include/rt_mi355.h): launch_trace reports which build it launched (rt_debug_builds).
+template <class Src, bool ANY, int LEAFB, bool STATS = false, bool COOP = false, bool NEAR = false, int QN = 0, bool FUSE = false, bool IMPL = false, bool TIMING = false>
+struct KTrace {
+    static constexpr auto fn = &k_trace<Src, ANY, LEAFB, STATS, COOP, NEAR, QN, FUSE, IMPL, TIMING>;
+    static constexpr uint32_t bits = (uint32_t)(RT_BUILD_LAUNCHED | (LEAFB >= 4 ? RT_BUILD_LEAFB4 : 0) | (STATS ? RT_BUILD_STATS : 0) | (COOP ? RT_BUILD_COOP : 0) |
+                                                (NEAR ? RT_BUILD_NEAR : 0) | (QN == 1 ? RT_BUILD_QN1 : 0) | (QN == 2 ? RT_BUILD_QN2 : 0) | (FUSE ? RT_BUILD_FUSE : 0) |
+                                                (IMPL ? RT_BUILD_IMPL : 0) | (TIMING ? RT_BUILD_TIMING : 0)) << (ANY ? RT_BUILD_ANY_SHIFT : 0);
+};
+
 // ---- packet traversal (round 4) ----------------------------------------------------------------------
 // The AO rays of one hit leave from ONE point (computeAO: org = hp + N * aoBias, rt_lighting.glsl:721-757) and are short (aoRadius 0.8): the
 // four of them visit nearly the same part of the tree -- traced one by one they fetch 39.8 four-wide node records and 8.8 leaves per hit on the
@@ -1658,7 +1686,7 @@ __global__ void k_accum_tally(const uint32_t *counts, unsigned long long *acc, i
 }
 
 template <class Src, bool ANY>
-void launch_trace(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, Src src, uint32_t *head, unsigned long long *tally,
+uint32_t launch_trace(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, Src src, uint32_t *head, unsigned long long *tally,
                   unsigned long long *gatherLoads, TraceTune tune, unsigned long long *stats = nullptr) {
     // Stack entries: closest-hit defers one sibling per binary level (8 B each); any-hit walks 4-wide nodes and can
     // defer three per two levels (4 B each).  Resident 256-thread workgroups per CU follow from the LDS footprint and the kernel's
@@ -1672,7 +1700,10 @@ void launch_trace(hipStream_t st, int cus, int gridPct, int depth, const DevFram
     const float4 *nodes = ANY ? (impl ? (qn ? hs.iQ4 : hs.iN4) : (qn ? hs.q4 : hs.w4)) : (fuse ? hs.wF : (impl ? hs.iN2 : hs.wnodesW));
     const float4 *pairRecords = impl ? hs.iPairs : hs.pairs;
     const float4 *leafBoxes = (ANY && impl) ? hs.iLeafBox : hs.leafBox;
-    auto go = [&](auto kernel) {
+    uint32_t built = 0;   // RT_BUILD_* bits of the build launched
+    auto go = [&](auto k) {
+        const auto kernel = decltype(k)::fn;
+        built = decltype(k)::bits;
         // the runtime's answer per (device, kernel, LDS bytes): a process may hold contexts on devices of different shapes
         thread_local std::map<std::tuple<int, const void *, size_t>, int> occ;
         int dev = 0;
@@ -1687,22 +1718,23 @@ void launch_trace(hipStream_t st, int cus, int gridPct, int depth, const DevFram
     };
     const int leafb = ANY ? tune.leafb : tune.leafbClosest;
     if (stats && tune.timing) {   // RT_TRACE_TIMING=1: the production kernel of this launch with scalar time stamps (exact / implicit records, default leaf groups only)
-        if (impl) go(k_trace<Src, ANY, 2, false, false, false, 0, false, true, true>); else go(k_trace<Src, ANY, 2, false, false, false, 0, false, false, true>);
-        return;
+        if (impl) go(KTrace<Src, ANY, 2, false, false, false, 0, false, true, true>{}); else go(KTrace<Src, ANY, 2, false, false, false, 0, false, false, true>{});
+        return built;
     }
-    if (impl && ANY) { if (qn) go(k_trace<Src, ANY, 2, false, false, false, ANY ? 2 : 0, false, true>); else go(k_trace<Src, ANY, 2, false, false, false, 0, false, true>); }
-    else if (impl) go(k_trace<Src, ANY, 2, false, false, false, 0, false, true>);
-    else if (stats && fuse) go(k_trace<Src, ANY, 2, true, false, false, 0, !ANY>);
-    else if (stats) { if (leafb >= 4) go(k_trace<Src, ANY, 4, true>); else go(k_trace<Src, ANY, 2, true>); }
-    else if (fuse) go(k_trace<Src, ANY, 2, false, false, false, 0, !ANY>);
-    else if (!ANY && tune.coop) go(k_trace<Src, ANY, 2, false, !ANY>);
-    else if (ANY && tune.nearFirst) go(k_trace<Src, ANY, 2, false, false, ANY>);
-    else if (qn && tune.qnodes == 1) go(k_trace<Src, ANY, 2, false, false, false, ANY ? 1 : 0>);   // seven waves per SIMD, 44 B of scratch: slower (measured)
-    else if (qn) go(k_trace<Src, ANY, 2, false, false, false, ANY ? 2 : 0>);
-    else       { if (leafb >= 4) go(k_trace<Src, ANY, 4, false>); else go(k_trace<Src, ANY, 2, false>); }
+    if (impl && ANY) { if (qn) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 2 : 0, false, true>{}); else go(KTrace<Src, ANY, 2, false, false, false, 0, false, true>{}); }
+    else if (impl) go(KTrace<Src, ANY, 2, false, false, false, 0, false, true>{});
+    else if (stats && fuse) go(KTrace<Src, ANY, 2, true, false, false, 0, !ANY>{});
+    else if (stats) { if (leafb >= 4) go(KTrace<Src, ANY, 4, true>{}); else go(KTrace<Src, ANY, 2, true>{}); }
+    else if (fuse) go(KTrace<Src, ANY, 2, false, false, false, 0, !ANY>{});
+    else if (!ANY && tune.coop) go(KTrace<Src, ANY, 2, false, !ANY>{});
+    else if (ANY && tune.nearFirst) go(KTrace<Src, ANY, 2, false, false, ANY>{});
+    else if (qn && tune.qnodes == 1) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 1 : 0>{});   // seven waves per SIMD, 44 B of scratch: slower (measured)
+    else if (qn) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 2 : 0>{});
+    else       { if (leafb >= 4) go(KTrace<Src, ANY, 4, false>{}); else go(KTrace<Src, ANY, 2, false>{}); }
+    return built;
 }
 
-void launch_packets(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, PacketSrc src, uint32_t *head, unsigned long long *tally,
+uint32_t launch_packets(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, PacketSrc src, uint32_t *head, unsigned long long *tally,
                     unsigned long long *gatherLoads, TraceTune tune) {
     const int stack = std::max(4, hs.anyStack > 0 ? hs.anyStack : 3 * ((depth + 1) / 2));
     const size_t ldsBytes = (size_t)256 * stack * 4;
@@ -1716,6 +1748,7 @@ void launch_packets(hipStream_t st, int cus, int gridPct, int depth, const DevFr
     }
     const unsigned blocks = (unsigned)std::max(8, cus * perCU * gridPct / 100);
     hipLaunchKernelGGL(k_trace_packets, dim3(blocks), dim3(256), ldsBytes, st, fr, hs.w4, hs.pairs, src, head, tally, gatherLoads, tune, stack);
+    return (uint32_t)RT_BUILD_PACKETS << RT_BUILD_ANY_SHIFT;
 }
 
 }  // namespace
@@ -1759,7 +1792,7 @@ struct RtWave {
     // ray-queue budget per frame lane; 288 GB of HBM make this cheap.  16 GB hold the queues of a whole batch of eight 1080p / 4 spp frames (7.4 M hits x
     // 2.1 KB) in ONE chunk: no hit-count read-back, half the launches (1.76-1.80 -> 1.68-1.72 ms per frame against 8 GB; profiles/r03_experiments.txt)
     size_t budgetBytes = (size_t)16 << 30;
-    TraceTune tune = default_tune();   // chunk 0 = run length chosen in the kernel from the queue size
+    TraceTune tune = tune_from_env();   // chunk 0 = run length chosen in the kernel from the queue size
     // allocations
     size_t slotsCap = 0;      // per-frame arrays sized for this many pixel slots
     size_t chunkBytes = 0;    // bytes of the per-chunk arena
@@ -1777,6 +1810,7 @@ struct RtWave {
     hipEvent_t hopEv = nullptr;
     bool binGi = false;                  // RT_BIN_GI=1: bounce rays sorted by direction inside each workgroup of k_gen_direct (experiment)
     bool chunksFromSlots = false;        // RT_CHUNKS_FROM_SLOTS=1 (tests): launch the chunk loop for every pixel slot, as rounds 1-2 did
+    uint32_t builds = 0;                 // RT_BUILD_* bits of the traversal builds launched since the last rt_wave_builds reset
 };
 
 RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
@@ -1786,29 +1820,17 @@ RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
     w->lane = lane;
     w->arena = pool ? lane % pool->n : 0;
     if (const char *e = getenv("RT_QUEUE_BUDGET_MB")) w->budgetBytes = (size_t)atoll(e) << 20;
-    if (const char *e = getenv("RT_REFILL_MIN")) w->tune.refillMin = std::max(1, std::min(64, atoi(e)));
-    if (const char *e = getenv("RT_CHUNK")) { int v = atoi(e); w->tune.chunk = v <= 0 ? 0 : std::max(8, std::min(1 << 20, v)); }   // 0 = from the queue size
     if (const char *e = getenv("RT_DEBUG_SKIP_TRAVERSAL")) w->tune.skipTraversal = atoi(e);
-    if (const char *e = getenv("RT_LEAFB")) w->tune.leafb = w->tune.leafbClosest = atoi(e);
-    if (const char *e = getenv("RT_LEAFB_CLOSEST")) w->tune.leafbClosest = atoi(e);
-    if (const char *e = getenv("RT_MIN_SEARCH")) w->tune.minSearch = std::max(0, std::min(64, atoi(e)));
     if (const char *e = getenv("RT_CHUNKS_FROM_SLOTS")) w->chunksFromSlots = atoi(e) != 0;
-    if (const char *e = getenv("RT_QUAD_REFILL")) w->tune.quadRefill = atoi(e) != 0;
-    if (const char *e = getenv("RT_COOP")) w->tune.coop = atoi(e);
     if (const char *e = getenv("RT_BIN_GI")) w->binGi = atoi(e) != 0;
-    if (const char *e = getenv("RT_NEAR_FIRST")) w->tune.nearFirst = atoi(e);
-    if (const char *e = getenv("RT_REVERSE")) w->tune.reverse = atoi(e);
-    if (const char *e = getenv("RT_GUIDED")) w->tune.guided = atoi(e);
-    if (const char *e = getenv("RT_DENSE_TAKE")) w->tune.denseTake = atoi(e);   // 0: every refill probes liveness first, as in rounds 2-3     // 0: runs of one length, as in rounds 1-3   // 0: any-hit queues dealt from their beginning, as in rounds 1-3
     if (const char *e = getenv("RT_PACKET_AO")) w->packetAO = atoi(e) != 0;
-    if (const char *e = getenv("RT_QNODES")) w->tune.qnodes = atoi(e);        // 0: never; 1 / 2: always (seven / six waves per SIMD); default: when rt_upload_bvh built them
     (void)hipEventCreateWithFlags(&w->hopEv, hipEventDisableTiming);
     if (const char *e = getenv("RT_CU_SPLIT")) {
         const int k = std::max(1, std::min(7, atoi(e)));
         uint32_t mask[8];
         for (int i = 0; i < 8; ++i) { uint32_t m = 0; for (int b = 0; b < 32; ++b) if (((i * 32 + b) & 7) < k) m |= 1u << b; mask[i] = m; }
         if (hipExtStreamCreateWithCUMask(&w->shadeStream, 8, mask) != hipSuccess) w->shadeStream = nullptr;
-    }   // quad-cooperative node fetch of the closest-hit launches (measured option)
+    }
     // EXPERIMENT RT_SHADE_PRIORITY=p: the shading kernels on a second stream of queue priority p (-1 high, 1 low; no CU mask), the traversal launches on the lane's own
     else if (const char *e = getenv("RT_SHADE_PRIORITY")) {
         int least = 0, greatest = 0;
@@ -2042,7 +2064,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
     TraceTune tuneP = tune;   // primary rays: their cost varies strongly across the screen, so shorter runs than the queue launches (128 - 256, see k_trace)
     tuneP.chunkMax = 256;
     if (const char *e = getenv("RT_CHUNK_PRIMARY")) tuneP.chunk = atoi(e);
-    launch_trace<PrimarySrc, false>(st, w->cus, gridPctPrimary, treeDepth, dFrame, host.sc, ps, &wb.heads[0], w->acc + 2, w->acc + 8, tuneP, S ? S + 0 : nullptr);
+    w->builds |= launch_trace<PrimarySrc, false>(st, w->cus, gridPctPrimary, treeDepth, dFrame, host.sc, ps, &wb.heads[0], w->acc + 2, w->acc + 8, tuneP, S ? S + 0 : nullptr);
     rt_stage_end(ctx, ST_TRACE_PRIMARY, 1, st);
 
     W_TRY(hop(st, ss));
@@ -2099,7 +2121,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
             PacketSrc pk;
             pk.o = wb.shO; pk.d = wb.shD; pk.tm = wb.shT; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = A; pk.nLive = 0;
             rt_stage_begin(ctx, ST_TRACE_AO, st);
-            launch_packets(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pk, &wb.heads[(size_t)(1 + c * 4 + 3) * kHeadWords], w->acc + 7, w->acc + 14, tune);
+            w->builds |= launch_packets(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pk, &wb.heads[(size_t)(1 + c * 4 + 3) * kHeadWords], w->acc + 7, w->acc + 14, tune);
             rt_stage_end(ctx, ST_TRACE_AO, 1, st);
         }
         const size_t skip = pkAO ? (size_t)A * CH : 0;
@@ -2114,7 +2136,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
             qg.o = wb.giO; qg.d = wb.giD; qg.tm = wb.giL; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
             qg.outT = wb.giT; qg.outTri = wb.giTri; qg.outOcc = nullptr;
             rt_stage_begin(ctx, ST_TRACE_GI, st);
-            launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
+            w->builds |= launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
             rt_stage_end(ctx, ST_TRACE_GI, 1, st);
 
             W_TRY(hop(st, ss));
@@ -2131,11 +2153,11 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
             qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.denseSlots = 0u;
             qq.b.outT = nullptr; qq.b.outTri = nullptr; qq.b.outOcc = wb.occ2;
             rt_stage_begin(ctx, ST_TRACE_SHADOW, st);
-            launch_trace<DualQueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qq, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
+            w->builds |= launch_trace<DualQueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qq, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
             rt_stage_end(ctx, ST_TRACE_SHADOW, 1, st);
         } else {
             rt_stage_begin(ctx, ST_TRACE_SHADOW, st);
-            launch_trace<QueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, q1, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
+            w->builds |= launch_trace<QueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, q1, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
             rt_stage_end(ctx, ST_TRACE_SHADOW, 1, st);
         }
         // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
@@ -2175,16 +2197,30 @@ void rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const
     launch_trace<CompactSrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
 }
 // Diagnostics (rt_debug_trace kinds 2 / 3): n arbitrary rays through the PRODUCTION traversal kernels -- a one-slot queue of n entries, closest-hit or any-hit
-// launch as the frames use it (persistent grid, refill scheduler, the any-hit node form rt_upload_bvh chose) -- so that the kernels can be tested ray by ray.
-void rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, bool any, const float4 *o, const float4 *d,
-                         const float *tm, const uint32_t *liveCount, uint32_t n, float *outT, int *outTri, uint8_t *outOcc, uint32_t *heads) {
+// launch as the frames use it (persistent grid, refill scheduler, the any-hit node form rt_upload_bvh chose, the build the environment selects: tune_from_env)
+// -- so that the kernels can be tested ray by ray.  Returns the RT_BUILD_* bits of the build launched.
+uint32_t rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, bool any, const float4 *o, const float4 *d,
+                             const float *tm, const uint32_t *liveCount, uint32_t n, float *outT, int *outTri, uint8_t *outOcc, uint32_t *heads) {
     QueueSrc q;
     q.o = o; q.d = d; q.tm = tm; q.liveCount = liveCount; q.c0 = 0; q.cap = n; q.stride = n; q.slots = 1; q.denseSlots = 0;
     q.outT = outT; q.outTri = outTri; q.outOcc = outOcc; q.nLive = 0;
-    TraceTune tune = default_tune();
-    if (const char *e = getenv("RT_QNODES")) tune.qnodes = atoi(e);
-    if (any) launch_trace<QueueSrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
-    else launch_trace<QueueSrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
+    const TraceTune tune = tune_from_env();
+    if (any) return launch_trace<QueueSrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
+    return launch_trace<QueueSrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
+}
+// rt_debug_trace kind 4: nPackets packets of four any-hit rays through k_trace_packets, in the layout of PacketSrc with A = 4 AO slots: ray r of packet p at
+// [r * nPackets + p] (*liveCount = nPackets).  A packet leaves from the origin of its ray 0; tm < 0 marks an empty slot (its occ entry is not written).
+uint32_t rt_wave_debug_packets(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const float4 *o, const float4 *d,
+                               const float *tm, const uint32_t *liveCount, uint32_t nPackets, uint8_t *outOcc, uint32_t *heads) {
+    PacketSrc pk;
+    pk.o = o; pk.d = d; pk.tm = tm; pk.occ = outOcc; pk.liveCount = liveCount; pk.c0 = 0; pk.cap = nPackets; pk.stride = nPackets; pk.A = 4; pk.nLive = 0;
+    return launch_packets(st, cus, 100, treeDepth, dFrame, hostScene, pk, heads, nullptr, nullptr, tune_from_env());
+}
+uint32_t rt_wave_builds(RtWave *w, bool reset) {
+    if (!w) return 0;
+    const uint32_t b = w->builds;
+    if (reset) w->builds = 0;
+    return b;
 }
 size_t rt_wave_head_words() { return kHeadWords; }
 

@@ -42,8 +42,14 @@ void rt_wave_trace_closest_indexed(hipStream_t st, int cus, int treeDepth, const
 void rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const float4 *o, const float4 *d,
                                    const uint32_t *dst, const uint32_t *count, const uint32_t *flags, uint32_t cap, float *outT, int *outTri, uint32_t *heads,
                                    uint32_t capOut = 0);   // capOut != 0 (RT_HYBRID_CHECK): entries of outT / outTri, checked before every store
-void rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, bool any, const float4 *o, const float4 *d,
-                         const float *tm, const uint32_t *liveCount, uint32_t n, float *outT, int *outTri, uint8_t *outOcc, uint32_t *heads);
+// rt_debug_trace kinds 2 - 4 (diagnostics): rays through the production traversal kernels with the build the environment selects; the RT_BUILD_* bits of
+// the build launched are returned.
+uint32_t rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, bool any, const float4 *o, const float4 *d,
+                             const float *tm, const uint32_t *liveCount, uint32_t n, float *outT, int *outTri, uint8_t *outOcc, uint32_t *heads);
+uint32_t rt_wave_debug_packets(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const float4 *o, const float4 *d,
+                               const float *tm, const uint32_t *liveCount, uint32_t nPackets, uint8_t *outOcc, uint32_t *heads);
+// RT_BUILD_* bits (include/rt_mi355.h) of the traversal builds this lane's frames launched since the last reset
+uint32_t rt_wave_builds(RtWave *w, bool reset);
 size_t rt_wave_head_words();
 
 // rt_hybrid.hip -- EXTENSION: the hybrid scene (analytic objects + mesh, N diffuse bounces) in stages: shading passes that replay answered mesh

@@ -363,6 +363,40 @@ int rt_debug_trace(RtContext *ctx, int kind, const float *origins, const float *
 #define RT_BUILD_ANY_SHIFT 16
 int rt_debug_builds(RtContext *ctx, uint32_t *out, int reset);
 
+/* ---- raster preview: renderRaster (src/render/render.cpp:244-295, shaders/basic.vert / basic.frag), the reference's other frame
+ * mode.  Flat-coloured meshes, MVP transform, GL_LESS depth test on a D24 buffer, no MSAA, no culling; the rules a GL 4.1 driver
+ * follows in that state are restated bit for bit in DESIGN.md 11 (tests/raster_ref.py mirrors them).  Single-rank contexts only. */
+#define RT_MAX_RASTER_MESHES 8
+/* Mesh::setupMesh (include/scene/mesh.h:170-214): positions (3 floats per vertex) + triangle index list, checked once on the host
+ * (nIdx % 3 == 0, every index < nVerts).  nVerts == 0 frees the slot. */
+int rt_raster_mesh(RtContext *ctx, int slot, const float *positions, int nVerts, const uint32_t *indices, int nIdx);
+/* one glDrawElements of renderRaster: mesh slot, model matrix (column-major), uColor */
+typedef struct RtRasterDraw { int32_t mesh; float model[16]; float color[3]; } RtRasterDraw;
+/* The draw list of renderRaster (ground, bunny, sphere, point-light marker when params->pointLightEnabled): returns the number of
+ * draws written to out[4] (0..4).  A negative slot skips its draw (a model the reference did not load draws nothing). */
+int rt_raster_scene_draws(const RtRenderParams *params, int groundSlot, int bunnySlot, int sphereSlot, RtRasterDraw out[4]);
+/* Clear + the draws into the context's raster buffers (RGBA8, primitive id, depth; allocated on the first call, sized by
+ * rt_resize).  Enqueued on rt_stream()'s stream; it does not wait for the device, except that growing a buffer (first call, a new
+ * framebuffer size, more triangles, more bin pairs than before) frees and allocates device memory, which synchronises.  view16 /
+ * proj16: currView / currProj (column-major).  Touches no ray target, no accumulation history and no frame index. */
+int rt_render_raster(RtContext *ctx, const RtRasterDraw *draws, int nDraws, const float *view16, const float *proj16);
+/* Synchronises; copies width x height pixels (row 0 = bottom) of the last rt_render_raster.  Any pointer may be NULL.  RT_ERR_STATE
+ * when rt_resize changed the framebuffer size since that call (the buffers are sized by the framebuffer: render again first).  primId: the
+ * global primitive index (draw's offset in the draw list + triangle's position in its index buffer), 0xFFFFFFFF on the background;
+ * depth24: the D24 value (0xFFFFFF on the background). */
+int rt_read_raster(RtContext *ctx, uint8_t *rgba8, uint32_t *primId, uint32_t *depth24);
+/* What the last rt_render_raster did (synchronises).  trianglesIn = trianglesSetUp + trianglesDropped (dropped: non-finite, clipped
+ * away or of zero area); trianglesClipped: went through the clipper; binEntries: (tile, triangle) pairs; binCapacity: pairs the bin
+ * arrays held (entries beyond it were rasterised from the triangle list instead); deviceMs: HIP events around the call's launches. */
+typedef struct RtRasterStats {
+    uint64_t trianglesIn, trianglesDropped, trianglesClipped, trianglesSetUp, binEntries, binCapacity, rasterBytes;
+    double deviceMs;
+} RtRasterStats;
+int rt_get_raster_stats(RtContext *ctx, RtRasterStats *out);
+/* Diagnostics used by the tests: the bin arrays of the following rt_render_raster calls hold exactly `pairs` (tile, triangle) pairs,
+ * so that the path past the capacity runs; 0 returns to automatic sizing. */
+int rt_debug_raster_bin_capacity(RtContext *ctx, uint64_t pairs);
+
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 
 void rt_default_render_params(RtRenderParams *p);      /* include/render/RenderParams.h:20-238 */

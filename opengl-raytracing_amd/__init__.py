@@ -165,6 +165,19 @@ class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
                         ("kColor", f32), ("kVarMotion", f32), ("kColorMotion", f32), ("svgfStrength", f32), ("enableSVGF", i32)])
 
 
+RT_MAX_RASTER_MESHES = 8
+RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
+
+
+class RtRasterDraw(_Struct):   # one glDrawElements of renderRaster (src/render/render.cpp:244-295)
+    _fields_ = _fields([("mesh", i32), ("model", (f32, 16)), ("color", (f32, 3))])
+
+
+class RtRasterStats(_Struct):
+    _fields_ = [(n, C.c_uint64) for n in ("trianglesIn", "trianglesDropped", "trianglesClipped", "trianglesSetUp", "binEntries", "binCapacity",
+                                           "rasterBytes")] + [("deviceMs", C.c_double)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rt_mi355 error {code}: {msg}")
@@ -204,6 +217,12 @@ SIGNATURES = {
     "rt_gather_block_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "rt_assemble_gathered": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rt_raster_mesh": (C.c_int, [C.c_void_p, C.c_int, _FP, C.c_int, _U32P, C.c_int]),
+    "rt_raster_scene_draws": (C.c_int, [C.POINTER(RtRenderParams), C.c_int, C.c_int, C.c_int, C.POINTER(RtRasterDraw)]),
+    "rt_render_raster": (C.c_int, [C.c_void_p, C.POINTER(RtRasterDraw), C.c_int, _FP, _FP]),
+    "rt_read_raster": (C.c_int, [C.c_void_p, _U8P, _U32P, _U32P]),
+    "rt_get_raster_stats": (C.c_int, [C.c_void_p, C.POINTER(RtRasterStats)]),
+    "rt_debug_raster_bin_capacity": (C.c_int, [C.c_void_p, C.c_uint64]),
     "rt_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),
     "rt_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rt_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -351,6 +370,25 @@ def mat4_mul(a, b) -> np.ndarray:
     m = np.zeros(16, np.float32)
     lib().rt_mat4_mul(_fp(a), _fp(b), _fp(m))
     return m
+
+
+def raster_scene_draws(params, ground=0, bunny=1, sphere=2) -> list:
+    """renderRaster's draw list (ground, bunny, sphere, point-light marker) for the given mesh slots; a negative slot skips its draw."""
+    out = (RtRasterDraw * 4)()
+    n = lib().rt_raster_scene_draws(C.byref(params), ground, bunny, sphere, out)
+    if n < 0:
+        raise RtError(n, "rt_raster_scene_draws: bad arguments")
+    return [out[i].copy() for i in range(n)]
+
+
+def raster_draw(mesh, model=None, color=(1.0, 1.0, 1.0)) -> RtRasterDraw:
+    d = RtRasterDraw(mesh=mesh)
+    m = np.eye(4, dtype=np.float32).reshape(-1) if model is None else _f32(model).reshape(-1)
+    for i in range(16):
+        d.model[i] = float(m[i])
+    for i in range(3):
+        d.color[i] = float(color[i])
+    return d
 
 
 def generate_jitter(frame_index: int) -> np.ndarray:
@@ -695,6 +733,42 @@ class Renderer:
         out = np.zeros((o.shape[0], 7), np.float32)
         self._check(lib().rt_debug_trace(self._h, kind, _fp(o), _fp(d), _fp(t), eps, inf, _fp(out), o.shape[0]))
         return out
+
+    def raster_mesh(self, slot, positions, indices=None):
+        """Upload one mesh for the raster preview (Mesh::setupMesh); positions [N,3] float32, indices uint32 triples.  None frees the slot."""
+        if positions is None:
+            self._check(lib().rt_raster_mesh(self._h, slot, None, 0, None, 0))
+            return
+        p = _f32(positions).reshape(-1, 3)
+        i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        self._check(lib().rt_raster_mesh(self._h, slot, _fp(p), p.shape[0], i.ctypes.data_as(_U32P), i.size))
+
+    def render_raster_async(self, draws, view, proj):
+        arr = (RtRasterDraw * max(len(draws), 1))(*draws)
+        v, p = _f32(view).reshape(-1), _f32(proj).reshape(-1)
+        self._check(lib().rt_render_raster(self._h, arr, len(draws), _fp(v), _fp(p)))
+
+    def read_raster(self):
+        """(rgba8 [H,W,4] uint8, prim_id [H,W] uint32, depth24 [H,W] uint32) of the last raster frame, row 0 = bottom."""
+        rgba = np.zeros((self.height, self.width, 4), np.uint8)
+        prim = np.zeros((self.height, self.width), np.uint32)
+        depth = np.zeros((self.height, self.width), np.uint32)
+        self._check(lib().rt_read_raster(self._h, rgba.ctypes.data_as(_U8P), prim.ctypes.data_as(_U32P), depth.ctypes.data_as(_U32P)))
+        return rgba, prim, depth
+
+    def render_raster(self, draws, view, proj):
+        """renderRaster: clear + draws (RtRasterDraw list) with currView / currProj -> read_raster()."""
+        self.render_raster_async(draws, view, proj)
+        return self.read_raster()
+
+    def debug_raster_bin_capacity(self, pairs):
+        """Diagnostics: bin arrays of exactly `pairs` pairs for the following raster calls (0: automatic)."""
+        self._check(lib().rt_debug_raster_bin_capacity(self._h, int(pairs)))
+
+    def raster_stats(self) -> RtRasterStats:
+        s = RtRasterStats()
+        self._check(lib().rt_get_raster_stats(self._h, C.byref(s)))
+        return s
 
     def debug_builds(self, reset=True) -> dict:
         """The traversal kernel builds launched since the last reset (frames and debug_trace kinds 2 - 4), as

@@ -80,6 +80,7 @@ struct RtContext {
     RtWave *wave[RT_MAX_LANES] = {};
     RtArenaPool *arenaPool = nullptr;   // ray-queue arenas shared by the lanes' wavefront pipelines
     RtHybrid *hybrid[RT_MAX_LANES] = {};   // EXTENSION: staged hybrid pipeline, created on first use
+    RtRaster *raster = nullptr;            // raster preview (rt_raster.hip): mesh slots + its own buffers, created on first use
     int cus = 256;
     uint32_t debugBuilds = 0;   // RT_BUILD_* bits of the rt_debug_trace kind 2 - 4 launches since the last rt_debug_builds reset
     int giBounces = 1;   // EXTENSION, rt_set_extension
@@ -404,6 +405,7 @@ void rt_destroy(RtContext *c) {
     (void)rt_comm_destroy(c);
     free_targets(c);
     for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->hybrid[i]) rt_hybrid_destroy(c->hybrid[i]); if (c->wave[i]) rt_wave_destroy(c->wave[i]); if (c->dFrame[i]) (void)hipFree(c->dFrame[i]); if (c->evDone[i]) (void)hipEventDestroy(c->evDone[i]); }
+    rt_raster_destroy(c->raster);
     rt_arena_pool_destroy(c->arenaPool);
     for (int i = 0; i < RT_MAX_LANES; ++i) if (c->lanes[i]) (void)hipStreamDestroy(c->lanes[i]);   // c->stream is lanes[0]
     if (c->dWNodes) (void)hipFree(c->dWNodes);
@@ -1443,6 +1445,51 @@ int rt_assemble_gathered(RtContext *c, int which, const void *gatheredDev, void 
     HIP_TRY(c, hipGetLastError());
     return RT_OK;
 }
+// ---- raster preview (renderRaster): the work is in rt_raster.hip; its buffers are its own, no ray target or frame state is touched
+int rt_raster_mesh(RtContext *c, int slot, const float *positions, int nVerts, const uint32_t *indices, int nIdx) {
+    if (!c) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    if (!c->raster) c->raster = rt_raster_create();
+    const int rc = rt_raster_set_mesh(c->raster, slot, positions, nVerts, indices, nIdx);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_render_raster(RtContext *c, const RtRasterDraw *draws, int nDraws, const float *view16, const float *proj16) {
+    if (!c) return RT_ERR_INVALID;
+    if (nDraws < 0 || (nDraws > 0 && !draws) || !view16 || !proj16) return fail(c, RT_ERR_INVALID, "rt_render_raster: bad arguments");
+    if (!c->sized) return fail(c, RT_ERR_STATE, "rt_render_raster before rt_resize");
+    if (c->g.world > 1) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_raster: tile-parallel contexts (worldSize %d) do not rasterise; use a single-rank context", c->g.world);
+    (void)hipSetDevice(c->cfg.device);
+    if (!c->raster) c->raster = rt_raster_create();
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    const int rc = rt_raster_render(c->raster, st, c->g.W, c->g.H, draws, nDraws, view16, proj16);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_read_raster(RtContext *c, uint8_t *rgba8, uint32_t *primId, uint32_t *depth24) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->raster) return fail(c, RT_ERR_STATE, "rt_read_raster before rt_render_raster");
+    (void)hipSetDevice(c->cfg.device);
+    if (!c->sized) return fail(c, RT_ERR_STATE, "rt_read_raster before rt_resize");
+    const int rc = rt_raster_read(c->raster, c->g.W, c->g.H, rgba8, primId, depth24);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_debug_raster_bin_capacity(RtContext *c, uint64_t pairs) {
+    if (!c) return RT_ERR_INVALID;
+    if (pairs > ((uint64_t)1 << 31)) return fail(c, RT_ERR_INVALID, "rt_debug_raster_bin_capacity: %llu pairs (at most 2^31)", (unsigned long long)pairs);
+    if (!c->raster) c->raster = rt_raster_create();
+    rt_raster_force_bin_capacity(c->raster, (size_t)pairs);
+    return RT_OK;
+}
+
+int rt_get_raster_stats(RtContext *c, RtRasterStats *out) {
+    if (!c || !out) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    const int rc = rt_raster_stats(c->raster, out);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
 int rt_stream(RtContext *c, void **s) {
     if (!c || !s) return RT_ERR_INVALID;
     *s = (void *)(c->lastStream ? c->lastStream : c->stream);   // the stream the most recent frame was enqueued on

@@ -120,6 +120,8 @@ static void die(RtContext *c, const char *what, int rc) {
 int main(int argc, char **argv) {
     std::vector<std::string> objs;
     std::string env, out = "frame";
+    bool raster = false;                     // --raster: renderRaster's draw list instead of ray frames (ground / --obj / sphere meshes)
+    std::string groundObj, sphereObj;
     bool dumpTargets = false;
     float dt = 1.0f / 60.0f;   // seconds per frame for the point-light orbit
     int W = 1920, H = 1080, frames = 1, device = 0, useBVH = 0, showMotion = 0;
@@ -149,6 +151,9 @@ int main(int argc, char **argv) {
                 bool ok = true;
                 if (k == "obj") { if (useBVH == 0) useBVH = 1; if (v.kind == scenefile::Value::Str) objs.push_back(v.str); else if (v.kind == scenefile::Value::Arr) for (const auto &e : v.arr) { ok = ok && e.kind == scenefile::Value::Str; objs.push_back(e.str); } else ok = false; }
                 else if (k == "env") { ok = v.kind == scenefile::Value::Str; env = v.str; }
+                else if (k == "raster") raster = v.num != 0;
+                else if (k == "ground") { ok = v.kind == scenefile::Value::Str; groundObj = v.str; }
+                else if (k == "sphere") { ok = v.kind == scenefile::Value::Str; sphereObj = v.str; }
                 else if (k == "out") { ok = v.kind == scenefile::Value::Str; out = v.str; }
                 else if (k == "size") { ok = v.kind == scenefile::Value::Arr && v.arr.size() == 2; if (ok) { W = (int)v.arr[0].num; H = (int)v.arr[1].num; } }
                 else if (k == "frames") frames = (int)v.num;
@@ -174,6 +179,9 @@ int main(int argc, char **argv) {
         }
         else if (a == "--obj") { objs.push_back(next()); if (useBVH == 0) useBVH = 1; }
         else if (a == "--dump-targets") dumpTargets = true;
+        else if (a == "--raster") raster = true;
+        else if (a == "--ground") groundObj = next();
+        else if (a == "--sphere") sphereObj = next();
         else if (a == "--dt") dt = (float)std::atof(next());
         else if (a == "--env") env = next();
         else if (a == "--out") out = next();
@@ -202,6 +210,7 @@ int main(int argc, char **argv) {
         else if (a == "--aspect") { cam.aspect = (float)std::atof(next()); aspectSet = true; }
         else { std::fprintf(stderr, "usage: rt_cli [--obj f.obj] [--env cross.png] [--size WxH] [--spp n] [--frames n] [--bvh|--analytic] [--motion]\n"
                                     "              [--cam x,y,z,yaw,pitch] [--fov deg] [--aspect a] [--exposure e] [--no-gi --no-ao --no-taa --no-svgf --no-env] [--out prefix]\n"
+                                    "              [--raster [--ground f.obj] [--sphere f.obj]]  (renderRaster's flat-colour preview of ground / --obj / sphere)\n"
                                     "              [--hybrid [--gi-bounces n]]   EXTENSION: the analytic scene with the .obj mesh added to it, n diffuse GI bounces\n"
                                     "              [--env-filter 0|1]   cube-map filter model: exact fp32 weights (default) / texel coordinates rounded to 1/256 texel\n"
                                     "              [--ranks N [--devices d0,d1,..] [--gather-every k] [--dry-run]]   tile-parallel over N GPUs, one process each, RCCL gather to rank 0\n"
@@ -291,6 +300,47 @@ int main(int argc, char **argv) {
         if (root) std::printf("[RCCL] %d ranks, communicator up\n", world);
     }
 #define RT_SAY(...) do { if (root) std::printf(__VA_ARGS__); } while (0)
+
+    if (raster) {
+        // renderRaster (src/render/render.cpp:244-295): slot 0 ground, 1 the --obj mesh(es) merged, 2 sphere; a missing one is skipped
+        if (ranks > 0) { std::fprintf(stderr, "rt_cli: --raster runs on one GPU (no --ranks)\n"); return 2; }
+        const std::vector<std::string> ground = groundObj.empty() ? std::vector<std::string>() : std::vector<std::string>{groundObj};
+        const std::vector<std::string> sphere = sphereObj.empty() ? std::vector<std::string>() : std::vector<std::string>{sphereObj};
+        const std::vector<std::string> *files[3] = {&ground, &objs, &sphere};
+        int slots[3] = {-1, -1, -1};
+        for (int s = 0; s < 3; ++s) {
+            std::vector<float> P; std::vector<uint32_t> I;
+            for (const std::string &obj : *files[s]) {
+                float *pos = nullptr; uint32_t *idx = nullptr; int nv = 0, ni = 0;
+                if ((rc = rt_load_obj(obj.c_str(), &pos, &nv, &idx, &ni)) != RT_OK) die(ctx, obj.c_str(), rc);
+                const uint32_t base = (uint32_t)(P.size() / 3);
+                P.insert(P.end(), pos, pos + (size_t)nv * 3);
+                for (int q = 0; q < ni; ++q) I.push_back(idx[q] + base);
+                rt_free(pos); rt_free(idx);
+            }
+            if (P.empty()) continue;
+            if ((rc = rt_raster_mesh(ctx, s, P.data(), (int)(P.size() / 3), I.data(), (int)I.size())) != RT_OK) die(ctx, "rt_raster_mesh", rc);
+            slots[s] = s;
+        }
+        if ((rc = rt_resize(ctx, W, H)) != RT_OK) die(ctx, "rt_resize", rc);
+        RtRasterDraw draws[4];
+        const int nd = rt_raster_scene_draws(&params, slots[0], slots[1], slots[2], draws);
+        float V[16], Pm[16];
+        rt_camera_view(&cam, V);
+        rt_camera_proj(&cam, Pm);
+        if ((rc = rt_render_raster(ctx, draws, nd, V, Pm)) != RT_OK) die(ctx, "rt_render_raster", rc);
+        std::vector<uint8_t> rgba((size_t)W * H * 4);
+        if ((rc = rt_read_raster(ctx, rgba.data(), nullptr, nullptr)) != RT_OK) die(ctx, "rt_read_raster", rc);
+        RtRasterStats st;
+        rt_get_raster_stats(ctx, &st);
+        std::printf("[RASTER] %d draw(s), %llu triangles (%llu set up), %dx%d in %.3f ms (device)\n", nd, (unsigned long long)st.trianglesIn,
+                    (unsigned long long)st.trianglesSetUp, W, H, st.deviceMs);
+        const std::string png = out + ".png";
+        if ((rc = rt_save_png(png.c_str(), rgba.data(), W, H, 4, /*flipY=*/1)) != RT_OK) die(ctx, "rt_save_png", rc);
+        std::printf("[RASTER] wrote %s\n", png.c_str());
+        rt_destroy(ctx);
+        return 0;
+    }
 
     if (!objs.empty()) {
         float M[16];

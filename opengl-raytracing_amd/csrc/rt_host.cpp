@@ -303,6 +303,17 @@ int rt_camera_moved(const float *currVP, const float *prevVP) {
     return worst > 1e-5f;
 }
 
+// computePointLightWorldPos, render.cpp:8-31
+static F3 point_light_world_pos(const RtRenderParams *p) {
+    F3 lp = f3(p->pointLightPos[0], p->pointLightPos[1], p->pointLightPos[2]);
+    if (p->pointLightOrbitEnabled && p->pointLightOrbitRadius > 0.0f) {
+        const float yr = deg2rad(p->pointLightYaw), pr = deg2rad(p->pointLightPitch);
+        const float cy = cosf(yr), sy = sinf(yr), cp = cosf(pr), sp = sinf(pr);
+        lp = add(lp, mul(f3(cp * sy, sp, cp * cy), p->pointLightOrbitRadius));
+    }
+    return lp;
+}
+
 void rt_make_uniforms(const RtRenderParams *p, const RtCamera *cam, const float *V, const float *currVP, const float *prevVP,
                       int fbw, int fbh, int frameIndex, int cameraMoved, int useBVH, int showMotion, int nodeCount,
                       int triCount, int envLoaded, RtUniforms *u) {
@@ -344,13 +355,7 @@ void rt_make_uniforms(const RtRenderParams *p, const RtCamera *cam, const float 
     put3(u->sunDir, dir_from_yaw_pitch(p->sunYaw, p->sunPitch));
     u->skyEnabled = p->skyEnabled; std::memcpy(u->skyColor, p->skyColor, 12); u->skyIntensity = p->skyIntensity;
     put3(u->skyUpDir, dir_from_yaw_pitch(p->skyYaw, p->skyPitch));
-    // computePointLightWorldPos, render.cpp:8-31
-    F3 lp = f3(p->pointLightPos[0], p->pointLightPos[1], p->pointLightPos[2]);
-    if (p->pointLightOrbitEnabled && p->pointLightOrbitRadius > 0.0f) {
-        const float yr = deg2rad(p->pointLightYaw), pr = deg2rad(p->pointLightPitch);
-        const float cy = cosf(yr), sy = sinf(yr), cp = cosf(pr), sp = sinf(pr);
-        lp = add(lp, mul(f3(cp * sy, sp, cp * cy), p->pointLightOrbitRadius));
-    }
+    const F3 lp = point_light_world_pos(p);
     u->pointLightEnabled = p->pointLightEnabled; put3(u->pointLightPos, lp);
     std::memcpy(u->pointLightColor, p->pointLightColor, 12); u->pointLightIntensity = p->pointLightIntensity;
     std::memcpy(u->matAlbedoColor, p->matAlbedoColor, 12);
@@ -566,6 +571,28 @@ int rt_cubemap_from_cross(const uint8_t *img, int width, int height, int channel
         const uint8_t *src = img + (size_t)cell[f][1] * n * stride + (size_t)cell[f][0] * rowBytes;
         uint8_t *dst = faces + (size_t)f * n * rowBytes;
         for (int y = 0; y < n; ++y) std::memcpy(dst + (size_t)y * rowBytes, src + (size_t)y * stride, rowBytes);
+    }
+    return n;
+}
+
+
+// renderRaster's draw list (src/render/render.cpp:244-295): translate(t) * scale(s) is exact (column 3 = t, diagonal = s)
+static void raster_draw(RtRasterDraw &d, int slot, float tx, float ty, float tz, float sc, float r, float g, float b) {
+    d.mesh = slot;
+    mat_identity(d.model);
+    d.model[0] = d.model[5] = d.model[10] = sc;
+    d.model[12] = tx; d.model[13] = ty; d.model[14] = tz;
+    d.color[0] = r; d.color[1] = g; d.color[2] = b;
+}
+int rt_raster_scene_draws(const RtRenderParams *p, int groundSlot, int bunnySlot, int sphereSlot, RtRasterDraw *out) {
+    if (!p || !out) return RT_ERR_INVALID;
+    int n = 0;
+    if (groundSlot >= 0) raster_draw(out[n++], groundSlot, 0.0f, 0.0f, 0.0f, 1.0f, 0.1f, 0.4f, 0.1f);
+    if (bunnySlot >= 0) raster_draw(out[n++], bunnySlot, -2.0f, 1.5f, 0.0f, 0.5f, 0.9f, 0.9f, 0.9f);
+    if (sphereSlot >= 0) raster_draw(out[n++], sphereSlot, 2.0f, 1.0f, 0.0f, 0.5f, 0.3f, 0.6f, 1.0f);
+    if (sphereSlot >= 0 && p->pointLightEnabled) {
+        const F3 lp = point_light_world_pos(p);
+        raster_draw(out[n++], sphereSlot, lp[0], lp[1], lp[2], 0.15f, p->pointLightColor[0] * 3.0f, p->pointLightColor[1] * 3.0f, p->pointLightColor[2] * 3.0f);
     }
     return n;
 }

@@ -64,3 +64,15 @@ int rt_hybrid_render(RtHybrid *h, RtContext *ctx, hipStream_t stream, const rtd:
 // stage timing hooks (rt_api.hip); stage ids index rt_stage_name()
 void rt_stage_begin(RtContext *c, int stage, hipStream_t on = nullptr);   // on == nullptr: the context's stream
 void rt_stage_end(RtContext *c, int stage, int launches, hipStream_t on = nullptr);
+
+// rt_raster.hip -- the raster preview (renderRaster): mesh slots, the binned rasteriser, its outputs and tallies.  Errors: rt_raster_error.
+struct RtRaster;
+RtRaster *rt_raster_create();
+void rt_raster_destroy(RtRaster *r);
+const char *rt_raster_error(const RtRaster *r);
+void rt_raster_force_bin_capacity(RtRaster *r, size_t pairs);   // 0: automatic
+int rt_raster_set_mesh(RtRaster *r, int slot, const float *positions, int nVerts, const uint32_t *indices, int nIdx);
+int rt_raster_render(RtRaster *r, hipStream_t stream, int W, int H, const RtRasterDraw *draws, int nDraws, const float *view16, const float *proj16);
+// W x H: the context's framebuffer; RT_ERR_STATE when the last raster frame has another size
+int rt_raster_read(RtRaster *r, int W, int H, uint8_t *rgba8, uint32_t *primId, uint32_t *depth24);
+int rt_raster_stats(RtRaster *r, RtRasterStats *out);

@@ -418,6 +418,49 @@ int rt_trace_rays(RtContext *ctx, int kind, const float *origins, int originStri
 int rt_trace_rays_host(RtContext *ctx, int kind, const float *origins, int originStride, const float *dirs, int dirStride,
                        const float *tMax, float eps, float inf, int n, RtHit *hits, float *normals, uint8_t *occluded);
 
+/* ---------------------------------------------------------------- scene queries and pixel picking
+ * The scene a frame rendered with *u shows, in every mode of u->useBVH: 0 the analytic scene (traceAnalyticCore, rt_scene_analytic.glsl:132-167),
+ * 1 the uploaded BVH (traceBVH: the bytes of rt_trace_rays), RT_SCENE_HYBRID the analytic scene plus the mesh as one more object.  u->eps / u->inf are
+ * uEPS / uINF, u->pointLightEnabled / u->pointLightPos place the marker sphere.  u->nodeCount / u->triCount are checked as rt_render_frame checks them
+ * (RT_ERR_STATE when they name more than was uploaded); either 0: the scene has no mesh.  Analytic-mode queries need no BVH.
+ * kind RT_QUERY_CLOSEST: one RtHit per ray.  A mesh hit: prim and u, v as rt_trace_rays.  An analytic hit: prim -1, u = v = 0.  A miss: {inf, -1, 0, 0}.
+ *   Objects are tested in list order (floor, albedo, glass, mirror sphere, marker, mesh); a later object wins only at a strictly smaller t.
+ *   objects (may be NULL): RT_OBJECT_* per ray.  normals (may be NULL): 3 floats, the hit's normal as the scene query stores it (plane normal,
+ *   normalize(p - c) on a sphere, normalize(cross(e1, e2)) on the mesh).  points (may be NULL): 3 floats, ro + rd * t.  Both zero on a miss.
+ *   tMax (optional): ray i is a hit exactly when the unbounded answer has t <= tMax[i], and then it is that answer (BVH mode: the bytes of
+ *   rt_trace_rays with the same tMax); tMax[i] < 0 marks an empty slot.
+ * kind RT_QUERY_ANY: occluded[i] = 1 when the analytic scene's closest t <= tMax[i], or (BVH / hybrid) traceBVHShadow finds a triangle within
+ *   [eps, tMax[i]] -- the closest answer's t <= tMax[i], except for a triangle flush with a face of its BVH box at a tMax within rounding of its t
+ *   (DESIGN.md 13.2).  tMax is required.
+ *   occludedToward (rt_lighting.glsl:49-60) tests h.t < maxT - eps: pass tMax = nextafterf(maxT - eps, 0) for that test.
+ * flags: RT_QUERY_SKIP_GLASS / RT_QUERY_SKIP_MARKER leave the glass sphere / the marker out (traceAnalyticIgnoreGlass / traceAnalyticIgnorePointLight,
+ *   rt_scene_analytic.glsl:175-196); analytic objects only.
+ * Rays, strides and alignment as rt_trace_rays; n == 0 is a no-op.  Device pointers; enqueued on rt_stream()'s stream; no host synchronisation and,
+ * after the first call, no allocation.  No target, history, frame index, counter, traced-ray tally or rt_debug_builds bit changes. */
+#define RT_QUERY_SKIP_GLASS 1
+#define RT_QUERY_SKIP_MARKER 2
+#define RT_OBJECT_NONE (-1)
+#define RT_OBJECT_FLOOR 0
+#define RT_OBJECT_ALBEDO_SPHERE 1
+#define RT_OBJECT_GLASS_SPHERE 2
+#define RT_OBJECT_MIRROR_SPHERE 3
+#define RT_OBJECT_POINT_LIGHT 4
+#define RT_OBJECT_MESH 5
+int rt_trace_scene_rays(RtContext *ctx, const RtUniforms *u, int kind, int flags, const float *origins, int originStride,
+                        const float *dirs, int dirStride, const float *tMax, int n,
+                        RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded);
+/* Pixel (xy[2i], xy[2i + 1]) (row 0 = bottom, as rt_read_target) along the frame's primary ray: origin u->camPos, direction
+ * primaryDirJ(u, x + 0.5, y + 0.5, u->jitter) (rt.frag:58-68, honouring enableJitter), answered as RT_QUERY_CLOSEST.  Any integer pair is a ray.
+ * For every pixel of a frame rendered with *u: RT_TARGET_GPOS == (f16(points), 1) on a hit, zero on a miss, RT_TARGET_GNRM == (f16(normalize(normals)), 0). */
+int rt_pick_pixels(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n,
+                   RtHit *hits, int32_t *objects, float *normals, float *points);
+/* The same with host pointers: staged through the context's buffer, synchronises. */
+int rt_trace_scene_rays_host(RtContext *ctx, const RtUniforms *u, int kind, int flags, const float *origins, int originStride,
+                             const float *dirs, int dirStride, const float *tMax, int n,
+                             RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded);
+int rt_pick_pixels_host(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n,
+                        RtHit *hits, int32_t *objects, float *normals, float *points);
+
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 
 void rt_default_render_params(RtRenderParams *p);      /* include/render/RenderParams.h:20-238 */

@@ -179,6 +179,9 @@ class RtRasterStats(_Struct):
 
 
 RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1   # rt_trace_rays kinds
+RT_QUERY_SKIP_GLASS, RT_QUERY_SKIP_MARKER = 1, 2   # rt_trace_scene_rays flags
+# rt_trace_scene_rays / rt_pick_pixels objects: the device's material ids
+RT_OBJECT_NONE, RT_OBJECT_FLOOR, RT_OBJECT_ALBEDO_SPHERE, RT_OBJECT_GLASS_SPHERE, RT_OBJECT_MIRROR_SPHERE, RT_OBJECT_POINT_LIGHT, RT_OBJECT_MESH = -1, 0, 1, 2, 3, 4, 5
 
 
 class RtHit(_Struct):   # one closest-hit answer of rt_trace_rays: t, prim (row of tris12, -1 on a miss), barycentrics u, v
@@ -254,6 +257,12 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p]),
     "rt_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_trace_scene_rays": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_trace_scene_rays_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_pick_pixels": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_pick_pixels_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
     "rt_default_camera": (None, [C.POINTER(RtCamera)]),
     "rt_default_bvh_transform": (None, [_FP]),
@@ -541,6 +550,20 @@ class RayHits:
 
     def __len__(self):
         return self.record.shape[0]
+
+
+class SceneHits(RayHits):
+    """Closest-hit answers of Renderer.trace_scene_rays / Renderer.pick: RayHits (prim -1 on an analytic hit) plus object [N] int32
+    (RT_OBJECT_*, RT_OBJECT_NONE on a miss) and, when asked for, normal [N,3] and point [N,3]."""
+
+    def __init__(self, record, obj, normal=None, point=None):
+        super().__init__(record, normal)
+        self.object = obj
+        self.point = point
+
+    @property
+    def hit(self):
+        return self.object >= 0
 
 
 def _query_invalid(msg):
@@ -875,6 +898,112 @@ class Renderer:
         if kind == RT_QUERY_ANY:
             return out.view(torch.bool)
         return RayHits(out, nrm)
+
+    def trace_scene_rays(self, u, origins, dirs, tmax=None, any_hit=False, skip_glass=False, skip_marker=False, normals=False, points=False):
+        """Ray queries against the scene a frame rendered with uniforms `u` shows (rt_trace_scene_rays): u.useBVH picks the analytic
+        scene, the uploaded BVH or the hybrid scene; u.eps / u.inf, the marker and u.nodeCount / u.triCount come from u.  Rays and tmax as trace_rays.
+        Closest hit -> SceneHits; any hit (tmax required) -> occluded [N] bool.  numpy arrays go through rt_trace_scene_rays_host, torch tensors
+        on this context's device take the zero-copy path of trace_rays."""
+        kind = RT_QUERY_ANY if any_hit else RT_QUERY_CLOSEST
+        flags = (RT_QUERY_SKIP_GLASS if skip_glass else 0) | (RT_QUERY_SKIP_MARKER if skip_marker else 0)
+        if any_hit and tmax is None:
+            raise _query_invalid("any-hit queries need tmax")
+        arrays = [a for a in (origins, dirs, tmax) if a is not None]
+        if all(isinstance(a, np.ndarray) for a in arrays):
+            for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
+                if a is not None and a.dtype != np.float32:
+                    raise _query_invalid(f"{name} must be float32, got {a.dtype}")
+            n = origins.shape[0] if origins.ndim == 2 else -1
+            os_ = self._ray_rows("origins", origins, 4, origins.strides)
+            ds = self._ray_rows("dirs", dirs, 4, dirs.strides, n)
+            if tmax is not None:
+                if tmax.shape != (n,):
+                    raise _query_invalid(f"tmax must be [{n}], got shape {tmax.shape}")
+                tmax = np.ascontiguousarray(tmax)
+            return self._scene_query_numpy(u, kind, flags, (origins, os_, dirs, ds), None, tmax, n, normals, points)
+        import torch
+        if not all(isinstance(a, torch.Tensor) for a in arrays):
+            raise _query_invalid("origins, dirs and tmax must all be numpy arrays or all torch tensors")
+        dev = self._query_device(origins, dirs, tmax, dtype=torch.float32)
+        n = origins.shape[0] if origins.dim() == 2 else -1
+        os_ = self._ray_rows("origins", origins, 1, origins.stride())
+        ds = self._ray_rows("dirs", dirs, 1, dirs.stride(), n)
+        if tmax is not None and (tuple(tmax.shape) != (n,) or (n > 1 and tmax.stride(0) != 1)):
+            raise _query_invalid(f"tmax must be a contiguous [{n}] tensor, got shape {tuple(tmax.shape)}")
+        return self._scene_query_torch(dev, u, kind, flags, (origins, os_, dirs, ds), None, tmax, n, normals, points)
+
+    def pick(self, u, xy, normals=True, points=True):
+        """What pixels (x, y) (int32 [N,2], row 0 = bottom) of a frame rendered with uniforms `u` show (rt_pick_pixels): each is traced
+        along the frame's own primary ray (jitter included) through the frame's scene -> SceneHits.  numpy or torch, as trace_scene_rays."""
+        if isinstance(xy, np.ndarray):
+            if xy.dtype != np.int32 or xy.ndim != 2 or xy.shape[1] != 2:
+                raise _query_invalid(f"xy must be int32 [N,2], got {xy.dtype} {xy.shape}")
+            return self._scene_query_numpy(u, RT_QUERY_CLOSEST, 0, None, np.ascontiguousarray(xy), None, xy.shape[0], normals, points)
+        import torch
+        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+            raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
+        dev = self._query_device(xy, dtype=torch.int32)
+        return self._scene_query_torch(dev, u, RT_QUERY_CLOSEST, 0, None, xy, None, xy.shape[0], normals, points)
+
+    def _query_device(self, *arrays, dtype):
+        import torch
+        dev = torch.device("cuda", self.device)
+        for a in arrays:
+            if a is None:
+                continue
+            if a.dtype != dtype:
+                raise _query_invalid(f"expected {dtype}, got {a.dtype}")
+            if a.device != dev:
+                raise _query_invalid(f"a tensor is on {a.device}, the context on {dev}")
+        return dev
+
+    def _scene_query_numpy(self, u, kind, flags, rays, xy, tmax, n, normals, points):
+        p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        if kind == RT_QUERY_ANY:
+            o, os_, d, ds = rays
+            occ = np.zeros(n, np.uint8)
+            self._check(lib().rt_trace_scene_rays_host(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n, None, None, None, None, p(occ)))
+            return occ.view(bool)
+        rec, obj = np.zeros((n, 4), np.float32), np.zeros(n, np.int32)
+        nrm = np.zeros((n, 3), np.float32) if normals else None
+        pts = np.zeros((n, 3), np.float32) if points else None
+        if xy is not None:
+            self._check(lib().rt_pick_pixels_host(self._h, C.byref(u), p(xy), n, p(rec), p(obj), p(nrm), p(pts)))
+        else:
+            o, os_, d, ds = rays
+            self._check(lib().rt_trace_scene_rays_host(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n, p(rec), p(obj), p(nrm), p(pts), None))
+        return SceneHits(rec, obj, nrm, pts)
+
+    def _scene_query_torch(self, dev, u, kind, flags, rays, xy, tmax, n, normals, points):
+        """The zero-copy path: stream ordering and lifetimes exactly as _trace_rays_torch."""
+        import torch
+        if kind == RT_QUERY_ANY:
+            out, obj, nrm, pts = torch.zeros(n, dtype=torch.uint8, device=dev), None, None, None
+        else:
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            obj = torch.empty(n, dtype=torch.int32, device=dev)
+            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
+            pts = torch.empty((n, 3), dtype=torch.float32, device=dev) if points else None
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the rays (and the outputs' allocation) are ready before the query starts
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        if xy is not None:
+            self._check(lib().rt_pick_pixels(self._h, C.byref(u), p(xy), n, p(out), p(obj), p(nrm), p(pts)))
+            inputs = (xy,)
+        else:
+            o, os_, d, ds = rays
+            self._check(lib().rt_trace_scene_rays(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n,
+                                                  p(out) if kind == RT_QUERY_CLOSEST else None, p(obj), p(nrm), p(pts),
+                                                  p(out) if kind == RT_QUERY_ANY else None))
+            inputs = (o, d, tmax)
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers
+        for a in inputs:                     # (never tied to the library stream: it dies with the context)
+            if a is not None:
+                a.record_stream(cur)
+        if kind == RT_QUERY_ANY:
+            return out.view(torch.bool)
+        return SceneHits(out, obj, nrm, pts)
 
     def raster_mesh(self, slot, positions, indices=None):
         """Upload one mesh for the raster preview (Mesh::setupMesh); positions [N,3] float32, indices uint32 triples.  None frees the slot."""

@@ -1706,13 +1706,8 @@ static int query_args(RtContext *c, const char *what, int kind, const float *ori
     return RT_OK;
 }
 
-int rt_trace_rays(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
-                  RtHit *hits, float *normals, uint8_t *occluded) {
-    if (!c) return RT_ERR_INVALID;
-    const int rc = query_args(c, "rt_trace_rays", kind, origins, originStride, dirs, dirStride, tMax, n, hits, occluded);
-    if (rc != RT_OK || n == 0) return rc;
-    if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)tMax | (uintptr_t)normals) & 3u) return fail(c, RT_ERR_INVALID, "rt_trace_rays: float arrays must be 4-byte aligned");
-    if (kind == RT_QUERY_CLOSEST && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "rt_trace_rays: hits must be 16-byte aligned (one 16-byte store per ray)");
+// The query scratch (allocated on the first query) and rt_stream()'s stream, which first waits for the previous query if that ran on another stream
+static int query_begin(RtContext *c, hipStream_t &st) {
     (void)hipSetDevice(c->cfg.device);
     if (!c->dQueryFrame) {
         HIP_TRY(c, hipMalloc(&c->dQueryFrame, sizeof(DevFrame)));
@@ -1720,15 +1715,31 @@ int rt_trace_rays(RtContext *c, int kind, const float *origins, int originStride
         HIP_TRY(c, hipMemset(c->dQueryFrame, 0, sizeof(DevFrame)));
         HIP_TRY(c, hipEventCreateWithFlags(&c->queryDone, hipEventDisableTiming));
     }
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
     if (c->queryStream && c->queryStream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->queryDone, 0));   // the scratch is free again
-    const DevScene sc = make_dev_scene(c);
-    (void)rt_wave_trace_query(st, c->cus, c->treeDepth, c->dQueryFrame, sc, kind == RT_QUERY_ANY, origins, originStride, dirs, dirStride, tMax, eps, inf, (uint32_t)n,
-                              hits, normals, occluded, c->dQueryHeads);
+    return RT_OK;
+}
+static int query_end(RtContext *c, hipStream_t st) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->queryDone, st));
     c->queryStream = st;
     return RT_OK;
+}
+
+int rt_trace_rays(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
+                  RtHit *hits, float *normals, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = query_args(c, "rt_trace_rays", kind, origins, originStride, dirs, dirStride, tMax, n, hits, occluded);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)tMax | (uintptr_t)normals) & 3u) return fail(c, RT_ERR_INVALID, "rt_trace_rays: float arrays must be 4-byte aligned");
+    if (kind == RT_QUERY_CLOSEST && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "rt_trace_rays: hits must be 16-byte aligned (one 16-byte store per ray)");
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    const DevScene sc = make_dev_scene(c);
+    (void)rt_wave_trace_query(st, c->cus, c->treeDepth, c->dQueryFrame, sc, kind == RT_QUERY_ANY, origins, originStride, dirs, dirStride, tMax, eps, inf, (uint32_t)n,
+                              hits, normals, occluded, c->dQueryHeads);
+    return query_end(c, st);
 }
 
 int rt_trace_rays_host(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
@@ -1761,6 +1772,121 @@ int rt_trace_rays_host(RtContext *c, int kind, const float *origins, int originS
     HIP_TRY(c, hipStreamSynchronize(st));
     return RT_OK;
     });
+}
+
+// ---- scene queries and pixel picking: the analytic leg (rt_scene_query.hip) into the caller's outputs, then the mesh leg through the frames'
+// persistent traversal launch (SceneSrc).  Shares rt_trace_rays' scratch; touches no frame state.
+// xy != null: pixel rays (rt_pick_pixels), else origins / dirs.  Checks everything before any device work; `mesh` = the scene has a mesh leg.
+static int scene_query_args(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs,
+                            int dirStride, const int32_t *xy, const float *tMax, int n, const RtHit *hits, const uint8_t *occluded, bool &mesh) {
+    if (!u) return fail(c, RT_ERR_INVALID, "%s: null uniforms", what);
+    if (kind != RT_QUERY_CLOSEST && kind != RT_QUERY_ANY) return fail(c, RT_ERR_INVALID, "%s: kind %d (RT_QUERY_CLOSEST or RT_QUERY_ANY)", what, kind);
+    if (flags & ~(RT_QUERY_SKIP_GLASS | RT_QUERY_SKIP_MARKER)) return fail(c, RT_ERR_INVALID, "%s: flags 0x%x (RT_QUERY_SKIP_*)", what, flags);
+    if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
+    if (xy) {
+        if ((size_t)n * 2 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the pixel array exceeds 2^32 entries", what);
+    } else {
+        if (originStride < 3 || dirStride < 3) return fail(c, RT_ERR_INVALID, "%s: strides %d / %d floats (at least 3)", what, originStride, dirStride);
+        if (n > 0 && (!origins || !dirs)) return fail(c, RT_ERR_INVALID, "%s: null ray arrays", what);
+        if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)std::max(originStride, dirStride) + 3 > ((size_t)1 << 32))
+            return fail(c, RT_ERR_INVALID, "%s: the ray arrays exceed 2^32 floats", what);
+    }
+    if (kind == RT_QUERY_ANY && !tMax) return fail(c, RT_ERR_INVALID, "%s: any-hit queries need tMax", what);
+    if (n > 0 && kind == RT_QUERY_CLOSEST && !hits) return fail(c, RT_ERR_INVALID, "%s: closest-hit queries need hits", what);
+    if (n > 0 && kind == RT_QUERY_ANY && !occluded) return fail(c, RT_ERR_INVALID, "%s: any-hit queries need occluded", what);
+    // the mesh as render_frames_impl sees it
+    const bool meshMode = u->useBVH == 1 || u->useBVH == RT_SCENE_HYBRID;
+    mesh = meshMode && u->nodeCount > 0 && u->triCount > 0;
+    if (mesh && (c->nNodes == 0 || u->nodeCount > c->nNodes || u->triCount > c->nTris))
+        return fail(c, RT_ERR_STATE, "%s: uniforms name %d nodes / %d tris, uploaded %d / %d", what, u->nodeCount, u->triCount, c->nNodes, c->nTris);
+    return RT_OK;
+}
+
+static int scene_query(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                       const int32_t *xy, const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    bool mesh = false;
+    const int rc = scene_query_args(c, what, u, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)xy | (uintptr_t)tMax | (uintptr_t)objects | (uintptr_t)normals | (uintptr_t)points) & 3u)
+        return fail(c, RT_ERR_INVALID, "%s: float and int32 arrays must be 4-byte aligned", what);
+    if (kind == RT_QUERY_CLOSEST && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "%s: hits must be 16-byte aligned (one 16-byte store per ray)", what);
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    DevScene sc = make_dev_scene(c);
+    if (!mesh) sc.hasBVH = 0;
+    const bool any = kind == RT_QUERY_ANY;
+    SceneRays r;
+    r.o = xy ? nullptr : origins; r.d = xy ? nullptr : dirs; r.os = originStride; r.ds = dirStride; r.xy = xy; r.tm = tMax; r.n = (uint32_t)n;
+    r.hits = any ? nullptr : reinterpret_cast<float4 *>(hits);
+    r.objects = any ? nullptr : objects; r.normals = any ? nullptr : normals; r.points = any ? nullptr : points; r.occ = any ? occluded : nullptr;
+    rt_scene_query_analytic(st, *u, sc, flags, r, c->dQueryFrame, c->dQueryHeads);
+    if (mesh) (void)rt_wave_trace_scene(st, c->cus, c->treeDepth, c->dQueryFrame, sc, u->useBVH == RT_SCENE_HYBRID, r, u->inf, c->dQueryHeads);
+    return query_end(c, st);
+}
+
+int rt_trace_scene_rays(RtContext *c, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                        const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    return scene_query(c, "rt_trace_scene_rays", u, kind, flags, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, objects, normals, points, occluded);
+}
+
+int rt_pick_pixels(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, RtHit *hits, int32_t *objects, float *normals, float *points) {
+    if (!c) return RT_ERR_INVALID;
+    if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels: null pixel array");
+    return scene_query(c, "rt_pick_pixels", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals, points, nullptr);
+}
+
+// host arrays: staged through the context's buffer (inputs | outputs, each 16-byte aligned; the ray arrays keep their strides), then synchronised
+static int scene_query_host(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs,
+                            int dirStride, const int32_t *xy, const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    bool mesh = false;
+    const int rc = scene_query_args(c, what, u, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    return guarded(c, what, [&]() -> int {
+    (void)hipSetDevice(c->cfg.device);
+    const bool any = kind == RT_QUERY_ANY;
+    const size_t N = (size_t)n;
+    const size_t oB = xy ? 0 : ((N - 1) * originStride + 3) * 4, dB = xy ? 0 : ((N - 1) * dirStride + 3) * 4, xB = xy ? N * 8 : 0, tB = tMax ? N * 4 : 0;
+    const size_t hB = any ? N : N * sizeof(RtHit), bB = (!any && objects) ? N * 4 : 0, nB = (!any && normals) ? N * 12 : 0, pB = (!any && points) ? N * 12 : 0;
+    auto al = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t offD = al(oB), offX = offD + al(dB), offT = offX + al(xB), offH = offT + al(tB), offB = offH + al(hB), offN = offB + al(bB), offP = offN + al(nB),
+                 total = offP + al(pB);
+    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
+    const int sr = ensure_staging(c, total);
+    if (sr != RT_OK) return sr;
+    char *base = (char *)c->dStaging;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    if (oB) HIP_TRY(c, hipMemcpyAsync(base, origins, oB, hipMemcpyHostToDevice, st));
+    if (dB) HIP_TRY(c, hipMemcpyAsync(base + offD, dirs, dB, hipMemcpyHostToDevice, st));
+    if (xB) HIP_TRY(c, hipMemcpyAsync(base + offX, xy, xB, hipMemcpyHostToDevice, st));
+    if (tB) HIP_TRY(c, hipMemcpyAsync(base + offT, tMax, tB, hipMemcpyHostToDevice, st));
+    const int qr = scene_query(c, what, u, kind, flags, oB ? (const float *)base : nullptr, originStride, dB ? (const float *)(base + offD) : nullptr, dirStride,
+                               xB ? (const int32_t *)(base + offX) : nullptr, tB ? (const float *)(base + offT) : nullptr, n, any ? nullptr : (RtHit *)(base + offH),
+                               bB ? (int32_t *)(base + offB) : nullptr, nB ? (float *)(base + offN) : nullptr, pB ? (float *)(base + offP) : nullptr,
+                               any ? (uint8_t *)(base + offH) : nullptr);
+    if (qr != RT_OK) { (void)sync_all(c); return qr; }
+    HIP_TRY(c, hipMemcpyAsync(any ? (void *)occluded : (void *)hits, base + offH, hB, hipMemcpyDeviceToHost, st));
+    if (bB) HIP_TRY(c, hipMemcpyAsync(objects, base + offB, bB, hipMemcpyDeviceToHost, st));
+    if (nB) HIP_TRY(c, hipMemcpyAsync(normals, base + offN, nB, hipMemcpyDeviceToHost, st));
+    if (pB) HIP_TRY(c, hipMemcpyAsync(points, base + offP, pB, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return RT_OK;
+    });
+}
+
+int rt_trace_scene_rays_host(RtContext *c, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                             const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    return scene_query_host(c, "rt_trace_scene_rays_host", u, kind, flags, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, objects, normals, points,
+                            occluded);
+}
+
+int rt_pick_pixels_host(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, RtHit *hits, int32_t *objects, float *normals, float *points) {
+    if (!c) return RT_ERR_INVALID;
+    if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels_host: null pixel array");
+    return scene_query_host(c, "rt_pick_pixels_host", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals,
+                            points, nullptr);
 }
 
 int rt_debug_builds(RtContext *c, uint32_t *out, int reset) {

@@ -456,10 +456,79 @@ struct QuerySrc {
     RT_DEV bool dense(uint32_t, uint32_t) const { return tm == nullptr; }
     RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const { token = r; ro = origin(r); rd = dir(r); return inf; }
 };
+// The mesh leg of rt_trace_scene_rays / rt_pick_pixels.  The analytic leg (rt_scene_query.hip) has already written every ray's answer into
+// the caller's outputs: the analytic scene's, bounded by tMax (hybrid mode), or a miss / "not occluded" (BVH mode), so this source never stores an empty
+// slot.  Rays are the caller's strided arrays, or pixel rays built here from the uniform block of the query's frame descriptor (primaryDirJ, as the frame
+// builds them) -- whenever a ray is taken and again when its answer is stored.
+//   BVH mode: the probe returns tMax (uINF without), every walked ray stores its answer: the bytes of QuerySrc.
+//   hybrid, closest: the walk is the frame's, unbounded (best = uINF, as traceScene's bvh_closest); the mesh answer t_m replaces the stored one only at
+//   t_m < t_a -- traceScene's rule, the earlier object wins a tie -- and t_m <= tMax.  t_a is the t the analytic leg stored (uINF: none, or beyond tMax).
+//   (Not a walk bounded by min(t_a, tMax): a triangle flush with a face of its box can lie a few ulps before that box's slab entry, so a bound
+//   equal to its t culls it -- a mesh resting on the floor would then lose to the floor although the frame shows it)
+//   hybrid, any: rays the analytic scene occludes are not walked (empty slots); the others take traceBVHShadow's answer.
+struct SceneSrc {
+    const float *o, *d;
+    const int32_t *xy;           // pixel rays (null: o / d)
+    const RtUniforms *cam;       // pixel rays: the query's uniform block (in its frame descriptor)
+    const float *tm;             // null: no tMax
+    uint32_t os, ds, n;
+    float inf;
+    bool hybrid;
+    const float4 *tris;
+    float4 *hits;                // closest-hit (null for any-hit)
+    int32_t *objects;
+    float *normals, *points;
+    uint8_t *occ;                // any-hit
+    RT_DEV void prepare() {}
+    RT_DEV uint32_t size() const { return n; }
+    RT_DEV V3 origin(uint32_t i) const { return xy ? ld3(cam->camPos) : ld3(o + (size_t)i * os); }
+    RT_DEV V3 dir(uint32_t i) const {
+        if (!xy) return ld3(d + (size_t)i * ds);
+        return primaryDirJ(*cam, (float)xy[(size_t)i * 2] + 0.5f, (float)xy[(size_t)i * 2 + 1] + 0.5f, cam->jitter[0], cam->jitter[1]);
+    }
+    struct Payload { uint32_t a; };
+    RT_DEV float probe(uint32_t i, Payload &p) const {
+        p.a = i;
+        if (!hits) {
+            if (hybrid && occ[i]) return -1.0f;   // occluded by the analytic scene
+            return tm[i];
+        }
+        const float b = tm ? tm[i] : inf;
+        return (hybrid && !(b < 0.0f)) ? inf : b;
+    }
+    RT_DEV static Payload route(const Payload &p, int e) { Payload q; q.a = (uint32_t)__shfl((int)p.a, e, 64); return q; }
+    RT_DEV void take(uint32_t, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const { token = p.a; ro = origin(p.a); rd = dir(p.a); }
+    RT_DEV void store_closest(uint32_t i, float t, int tri) const {
+        if (hybrid && !(tri >= 0 && t < hits[i].x && (!tm || t <= tm[i]))) return;   // the analytic answer stands
+        float u = 0.0f, v = 0.0f;
+        V3 nrm = mk3(0.0f), pt = mk3(0.0f);
+        if (tri >= 0) {
+            const V3 ro = origin(i), rd = dir(i);
+            const float4 *T = tris + (size_t)tri * 3;
+            const V3 v0 = f4xyz(T[0]), e1 = f4xyz(T[1]), e2 = f4xyz(T[2]);
+            const V3 pvec = cross(rd, e2);                 // tri_hit's operations, in its order (QuerySrc::store_closest)
+            const float invDet = 1.0f / dot(e1, pvec);
+            const V3 tvec = ro - v0;
+            u = dot(tvec, pvec) * invDet;
+            v = dot(rd, cross(tvec, e1)) * invDet;
+            if (normals) nrm = normalize(cross(e1, e2));   // hit.n of traceScene / traceBVH
+            pt = ro + rd * t;                              // hit.p
+        }
+        hits[i] = make_float4(t, __int_as_float(tri), u, v);
+        if (objects) objects[i] = tri >= 0 ? RT_OBJECT_MESH : RT_OBJECT_NONE;
+        if (normals) { normals[(size_t)i * 3] = nrm.x; normals[(size_t)i * 3 + 1] = nrm.y; normals[(size_t)i * 3 + 2] = nrm.z; }
+        if (points) { points[(size_t)i * 3] = pt.x; points[(size_t)i * 3 + 1] = pt.y; points[(size_t)i * 3 + 2] = pt.z; }
+    }
+    RT_DEV void store_any(uint32_t i, bool hit) const { occ[i] = hit ? 1 : 0; }
+    RT_DEV bool dense(uint32_t, uint32_t) const { return tm == nullptr; }
+    RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const { token = r; ro = origin(r); rd = dir(r); return inf; }
+};
+
 // Closest-hit rays of a source with this trait start their walk with best = the tMax the source hands out (QuerySrc) instead of uINF; the frame
 // sources keep uINF (a compile-time choice: their kernels are the same instructions as without it).
 template <class Src> struct QueryTMax { static constexpr bool value = false; };
 template <> struct QueryTMax<QuerySrc> { static constexpr bool value = true; };
+template <> struct QueryTMax<SceneSrc> { static constexpr bool value = true; };
 
 // hipcc sinks loads into the branches that first use them (e.g. a triangle's v0 behind the determinant test), which turns
 // one gather round trip into two or three dependent ones.  pin() makes a loaded record "used" right after the loads were
@@ -2293,6 +2362,17 @@ uint32_t rt_wave_trace_query(hipStream_t st, int cus, int treeDepth, DevFrame *d
     const TraceTune tune = tune_from_env();
     if (any) return launch_trace<QuerySrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr, maxBlocks);
     return launch_trace<QuerySrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr, maxBlocks);
+}
+// rt_trace_scene_rays / rt_pick_pixels: the mesh leg, after rt_scene_query_analytic wrote dFrame, heads and every ray's first answer
+uint32_t rt_wave_trace_scene(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, bool hybrid, const SceneRays &r, float inf,
+                             uint32_t *heads) {
+    SceneSrc q;
+    q.o = r.o; q.d = r.d; q.xy = r.xy; q.cam = &dFrame->u; q.tm = r.tm; q.os = (uint32_t)r.os; q.ds = (uint32_t)r.ds; q.n = r.n; q.inf = inf; q.hybrid = hybrid;
+    q.tris = hostScene.tris; q.hits = r.hits; q.objects = r.objects; q.normals = r.normals; q.points = r.points; q.occ = r.occ;
+    const unsigned maxBlocks = (unsigned)((r.n + 255u) / 256u);
+    const TraceTune tune = tune_from_env();
+    if (!r.hits) return launch_trace<SceneSrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr, maxBlocks);
+    return launch_trace<SceneSrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr, maxBlocks);
 }
 uint32_t rt_wave_builds(RtWave *w, bool reset) {
     if (!w) return 0;

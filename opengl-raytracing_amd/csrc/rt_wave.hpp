@@ -52,6 +52,28 @@ uint32_t rt_wave_debug_packets(hipStream_t st, int cus, int treeDepth, const rtd
 // `st` first.  Closest-hit answers to hits (RtHit) and normals (may be null), any-hit answers to occ.  Returns the RT_BUILD_* bits of the build.
 uint32_t rt_wave_trace_query(hipStream_t st, int cus, int treeDepth, rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, bool any, const float *o, int os,
                              const float *d, int ds, const float *tm, float eps, float inf, uint32_t n, void *hits, float *normals, uint8_t *occ, uint32_t *heads);
+// rt_trace_scene_rays / rt_pick_pixels: the rays and outputs of one scene query.  Ray i is o[i * os] / d[i * ds] (strides in floats), or --
+// when xy is set -- the primary ray of pixel (xy[2i], xy[2i + 1]) of the uniform block in the query's frame descriptor.  Outputs other than hits / occ
+// may be null.  hits: one RtHit (float4) per ray for closest hit, null for any hit.
+struct SceneRays {
+    const float *o, *d;
+    int os, ds;
+    const int32_t *xy;
+    const float *tm;
+    uint32_t n;
+    float4 *hits;
+    int32_t *objects;
+    float *normals, *points;
+    uint8_t *occ;
+};
+// rt_scene_query.hip: the analytic leg, one lane per ray -- traceAnalyticCore (analytic and hybrid modes; BVH mode: every answer a miss), bounded by tm, into
+// the caller's outputs -- and the query scratch (dFrame = u and the scene, heads zeroed) for the mesh leg that follows on `st`.  flags: RT_QUERY_SKIP_*.
+void rt_scene_query_analytic(hipStream_t st, const RtUniforms &u, const rtd::DevScene &sc, int flags, const SceneRays &r, rtd::DevFrame *dFrame, uint32_t *heads);
+// rt_wave.hip: the mesh leg through the production traversal launch (SceneSrc).  hybrid: merged into the analytic answers the outputs hold (mesh wins at a
+// strictly smaller t; any hit: rays already occluded are not walked); else BVH mode, the bytes of rt_wave_trace_query plus objects / points.  dFrame and heads
+// were written by rt_scene_query_analytic.  Returns the RT_BUILD_* bits of the build.
+uint32_t rt_wave_trace_scene(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, bool hybrid, const SceneRays &r,
+                             float inf, uint32_t *heads);
 // RT_BUILD_* bits (include/rt_mi355.h) of the traversal builds this lane's frames launched since the last reset
 uint32_t rt_wave_builds(RtWave *w, bool reset);
 size_t rt_wave_head_words();

@@ -13,11 +13,16 @@ What is changed in the shader text at load time, and nothing else:
   * GLES 3.0 has no samplerBuffer: the two texture buffers (uBvhNodes / uBvhTris, rt_uniforms.glsl:73-74,
     RGBA32F texels, src/scene/bvh.cpp:181,217) are bound as 2048-texel-wide RGBA32F 2D textures and
     `texelFetch(buf, i)` is macro-mapped to `texelFetch(tex, ivec2(i & 2047, i >> 11), 0)` (index clamped to
-    the texture) -- the same texel values reach the shader.
+    the texture) -- the same texel values reach the shader.  Each texture is as tall as its data needs plus at
+    least one zero texel (rows = texels // 2048 + 1, up to GL_MAX_TEXTURE_SIZE: 1M-triangle trees fit), and the
+    clamp reads the bound texture's own size (textureSize), so an index past the data reads zeros as before.
   * the vertex stage: SwiftShader 4.1 evaluates gl_VertexID as 0 for every vertex, so rt_fullscreen.vert
     (which derives the three clip-space corners (-1,-1) (3,-1) (-1,3) from gl_VertexID, :30-45) collapses to
     a degenerate triangle.  The same three corners are fed through a vertex attribute instead and
     vUV = 0.5 * (p + 1.0) is computed as at :44.  The fragment stage -- the hot path -- is untouched.
+  * windows of large frames: render() and present() take an optional pixel window.  The viewport, uResolution,
+    gl_FragCoord and vUV stay those of the full frame and every texture has the full-frame size; a scissor
+    rectangle limits shading to the window and only the window is read back.  No shader text changes.
   * SwiftShader 4.1 mis-executes `continue` inside a `while` loop (minimal reproducer without any reference text:
     tests/golden/swiftshader_continue_defect.py, log beside it), which is what broke traceBVH / traceBVHShadow
     (rt_bvh.glsl:208,272) in round 1.  With rewrite_continue=True the two `if (C) continue;` statements become
@@ -42,8 +47,7 @@ import tempfile
 import numpy as np
 
 REF_SHADERS = "/root/reference/shaders/rt"
-TBO_W_LOG2 = 11
-TBO_H = 64       # every stand-in texture is 2048 x 64 texels, so the index clamp is a constant
+TBO_W_LOG2 = 11   # every stand-in texture is 2048 texels wide; its height follows the data (_tbo)
 
 GL_FRAGMENT_SHADER, GL_VERTEX_SHADER = 0x8B30, 0x8B31
 GL_TEXTURE_2D, GL_TEXTURE_CUBE_MAP, GL_TEXTURE_CUBE_MAP_POSITIVE_X = 0x0DE1, 0x8513, 0x8515
@@ -65,9 +69,9 @@ precision highp int;
 precision highp sampler2D;
 precision highp samplerCube;
 #define samplerBuffer sampler2D
-#define RT_TBO_CLAMP(i) clamp((i), 0, %d)
-#define texelFetch(s, i) texelFetch(s, ivec2(RT_TBO_CLAMP(i) & %d, RT_TBO_CLAMP(i) >> %d), 0)
-""" % ((1 << TBO_W_LOG2) * TBO_H - 1, (1 << TBO_W_LOG2) - 1, TBO_W_LOG2)
+#define RT_TBO_CLAMP(s, i) clamp((i), 0, textureSize(s, 0).x * textureSize(s, 0).y - 1)
+#define texelFetch(s, i) texelFetch(s, ivec2(RT_TBO_CLAMP(s, i) & %d, RT_TBO_CLAMP(s, i) >> %d), 0)
+""" % ((1 << TBO_W_LOG2) - 1, TBO_W_LOG2)
 
 # RtUniforms field -> GLSL uniform name (rt_uniforms.glsl:25-177, same order as the struct)
 UNIFORM_NAMES = {
@@ -204,6 +208,9 @@ class GlslReference:
             raise RuntimeError("eglMakeCurrent failed")
         gl.glGetString.restype = C.c_char_p
         self.version = gl.glGetString(0x1F02).decode()
+        mts = C.c_int()
+        gl.glGetIntegerv(0x0D33, C.byref(mts))   # GL_MAX_TEXTURE_SIZE
+        self.max_texture_size = mts.value
         gl.glCreateShader.restype = C.c_uint
         gl.glCreateProgram.restype = C.c_uint
         gl.glGetUniformLocation.restype = C.c_int
@@ -277,11 +284,13 @@ class GlslReference:
         return t
 
     def _tbo(self, arr12):
-        """N x 12 floats -> 3N RGBA32F texels in a 2048-wide 2D texture (stand-in binding for the reference's TBO)."""
+        """N x 12 floats -> 3N RGBA32F texels in a 2048-wide 2D texture (stand-in binding for the reference's TBO), followed by
+        at least one zero texel: the clamped index of a fetch past the data reads zeros."""
         texels = np.ascontiguousarray(arr12, np.float32).reshape(-1, 4)
         w = 1 << TBO_W_LOG2
-        h = TBO_H
-        assert texels.shape[0] <= w * h
+        h = texels.shape[0] // w + 1
+        if h > self.max_texture_size:
+            raise RuntimeError(f"{texels.shape[0]} texels need {h} rows, GL_MAX_TEXTURE_SIZE is {self.max_texture_size}")
         buf = np.zeros((h * w, 4), np.float32)
         buf[:texels.shape[0]] = texels
         return self._tex2d(GL_RGBA32F, w, h, GL_RGBA, GL_FLOAT, buf)
@@ -344,15 +353,19 @@ class GlslReference:
             self.gl.glDeleteTextures(1, C.byref(t))
 
     # ---- the ray pass: src/render/render.cpp:120-195 (bind MRT, uniforms, textures, draw 3 vertices)
-    def render(self, u, nodes12=None, tris12=None, env_faces=None, prev=None):
-        """-> [color HxWx4, motion HxWx2, gpos HxWx4, gnrm HxWx4] as float16 bit patterns (uint16), row 0 = bottom."""
+    def render(self, u, nodes12=None, tris12=None, env_faces=None, prev=None, window=None):
+        """-> [color, motion, gpos, gnrm] as float16 bit patterns (uint16), row 0 = bottom.  prev: the full-frame history (H x W x 4).
+        window (x0, y0, x1, y1): shade and read back only that pixel rectangle of the full frame (scissor; the viewport, uResolution,
+        gl_FragCoord and vUV stay the full frame's) -> arrays of (y1 - y0) x (x1 - x0) pixels.  Default: the whole frame."""
         gl = self.gl
         W, H = int(u.resolution[0]), int(u.resolution[1])
+        x0, y0, x1, y1 = self._window(window, W, H)
         one = np.zeros((1, 12), np.float32)
         tn = self._tbo(one if nodes12 is None else nodes12)
         tt = self._tbo(one if tris12 is None else tris12)
         te = self._cube(np.zeros((6, 1, 1, 3), np.uint8) if env_faces is None else env_faces)
         pv = np.zeros((H, W, 4), np.uint16) if prev is None else np.ascontiguousarray(prev, np.uint16)
+        assert pv.shape == (H, W, 4), pv.shape
         tp = self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, pv)
         outs = [self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, None), self._tex2d(GL_RG16F, W, H, GL_RG, GL_HALF_FLOAT, None),
                 self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, None), self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, None)]
@@ -367,7 +380,7 @@ class GlslReference:
         if st != GL_FRAMEBUFFER_COMPLETE:
             raise RuntimeError(f"FBO incomplete 0x{st:x}")
         gl.glViewport(0, 0, W, H)
-        gl.glDisable(0x0C11)   # scissor
+        self._scissor(x0, y0, x1, y1, W, H)
         gl.glDisable(0x0B71)   # depth
         gl.glDisable(0x0BE2)   # blend
         gl.glUseProgram(self.prog_rt)
@@ -382,26 +395,44 @@ class GlslReference:
         res = []
         for i, c in enumerate((4, 2, 4, 4)):
             gl.glReadBuffer(GL_COLOR_ATTACHMENT0 + i)
-            buf = np.zeros((H, W, 4), np.float32)
+            buf = np.zeros((y1 - y0, x1 - x0, 4), np.float32)
             gl.glPixelStorei(0x0D05, 1)   # PACK_ALIGNMENT
-            gl.glReadPixels(0, 0, W, H, GL_RGBA, GL_FLOAT, buf.ctypes.data_as(C.c_void_p))
+            gl.glReadPixels(x0, y0, x1 - x0, y1 - y0, GL_RGBA, GL_FLOAT, buf.ctypes.data_as(C.c_void_p))
             self._check("read")
             res.append(np.ascontiguousarray(buf[:, :, :c]).astype(np.float16).view(np.uint16))   # exact: values are halves
+        gl.glDisable(0x0C11)
         gl.glBindFramebuffer(GL_FRAMEBUFFER, 0)
         gl.glDeleteFramebuffers(1, C.byref(fbo))
         self._delete([tn, tt, te, tp] + outs)
         return res
+
+    @staticmethod
+    def _window(window, W, H):
+        x0, y0, x1, y1 = (0, 0, W, H) if window is None else (int(v) for v in window)
+        if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+            raise ValueError(f"window {window} outside the {W}x{H} frame")
+        return x0, y0, x1, y1
+
+    def _scissor(self, x0, y0, x1, y1, W, H):
+        gl = self.gl
+        if (x0, y0, x1, y1) == (0, 0, W, H):
+            gl.glDisable(0x0C11)   # scissor
+        else:
+            gl.glEnable(0x0C11)
+            gl.glScissor(x0, y0, x1 - x0, y1 - y0)
 
     # ---- the present pass: src/render/render.cpp:200-239 (default framebuffer = RGBA8 here)
     PRESENT_NAMES = {"exposure": "uExposure", "showMotion": "uShowMotion", "motionScale": "uMotionScale", "resolution": "uResolution",
                      "varMax": "uVarMax", "kVar": "uKVar", "kColor": "uKColor", "kVarMotion": "uKVarMotion",
                      "kColorMotion": "uKColorMotion", "svgfStrength": "uSvgfStrength", "enableSVGF": "uEnableSVGF"}
 
-    def present(self, pp, targets):
-        """rt_present.frag over [color, motion, gpos, gnrm] half images -> HxWx4 uint8."""
+    def present(self, pp, targets, window=None):
+        """rt_present.frag over full-frame [color, motion, gpos, gnrm] half images -> uint8 RGBA of the window (x0, y0, x1, y1)
+        (default: the whole frame), shaded under a scissor as in render()."""
         gl = self.gl
         color, motion, gpos, gnrm = [np.ascontiguousarray(a, np.uint16) for a in targets]
         H, W = color.shape[:2]
+        x0, y0, x1, y1 = self._window(window, W, H)
         tin = [self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, color), self._tex2d(GL_RG16F, W, H, GL_RG, GL_HALF_FLOAT, motion),
                self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, gpos), self._tex2d(GL_RGBA16F, W, H, GL_RGBA, GL_HALF_FLOAT, gnrm)]
         out = self._tex2d(GL_RGBA8, W, H, GL_RGBA, GL_UNSIGNED_BYTE, None)
@@ -415,6 +446,7 @@ class GlslReference:
         if st != GL_FRAMEBUFFER_COMPLETE:
             raise RuntimeError(f"FBO incomplete 0x{st:x}")
         gl.glViewport(0, 0, W, H)
+        self._scissor(x0, y0, x1, y1, W, H)
         gl.glUseProgram(self.prog_present)
         for field, name in self.PRESENT_NAMES.items():
             loc = gl.glGetUniformLocation(self.prog_present, name.encode())
@@ -433,10 +465,11 @@ class GlslReference:
         gl.glFinish()
         self._check("present draw")
         gl.glReadBuffer(GL_COLOR_ATTACHMENT0)
-        buf = np.zeros((H, W, 4), np.uint8)
+        buf = np.zeros((y1 - y0, x1 - x0, 4), np.uint8)
         gl.glPixelStorei(0x0D05, 1)
-        gl.glReadPixels(0, 0, W, H, GL_RGBA, GL_UNSIGNED_BYTE, buf.ctypes.data_as(C.c_void_p))
+        gl.glReadPixels(x0, y0, x1 - x0, y1 - y0, GL_RGBA, GL_UNSIGNED_BYTE, buf.ctypes.data_as(C.c_void_p))
         self._check("present read")
+        gl.glDisable(0x0C11)
         gl.glBindFramebuffer(GL_FRAMEBUFFER, 0)
         gl.glDeleteFramebuffers(1, C.byref(fbo))
         self._delete(tin + [out])

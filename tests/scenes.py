@@ -25,6 +25,20 @@ def bunny_bvh(subdiv=6):
     return rt.build_bvh(tris9)
 
 
+@functools.lru_cache(maxsize=1)
+def million_bvh():
+    """(nodes12, tris12) of BASELINE configs[4]'s 1 M-triangle scene (meshgen.million_triangle_scene, identity model), built by the PRODUCT host code."""
+    v, f = rt.meshgen.million_triangle_scene()
+    return rt.build_bvh(rt.gather_triangles(v, f, np.eye(4, dtype=np.float32).reshape(-1)))
+
+
+def reference_window_inputs(mesh, env):
+    """(nodes12, tris12, faces) named by a windowed reference fixture (tests/golden/glsl_k_*.npz): mesh "bench" (bunny_bvh(6), the bench
+    mesh), "million" (million_bvh()) or "" (analytic scene); env a cube map under assets/cubemaps or "" (gradient sky)."""
+    nodes, tris = {"bench": bunny_bvh, "million": million_bvh}[mesh]() if mesh else (None, None)
+    return nodes, tris, env_faces(env) if env else None
+
+
 def tiny_env(n=8, seed=3):
     """Small random RGB cube map (exercises face seams and bilinear weights)."""
     rng = np.random.default_rng(seed)

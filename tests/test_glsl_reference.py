@@ -6,12 +6,14 @@ sin/cos/pow/normalize/dot differ from the oracle's float model in the last bits 
 agreement is to a tolerance: RMSE < 1e-4 per target (north_star's float tolerance) AND at least 99 % of all values
 bit-identical -- i.e. what differs are isolated pixels next to discontinuities, not a systematic error.
 """
+import hashlib
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 import opengl_raytracing_amd as rt
+import scenes
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 FRAME_FIXTURES = ["glsl_analytic_gradient_64x48", "glsl_analytic_materials_env_48x36", "glsl_analytic_moving_48x36",
@@ -19,6 +21,11 @@ FRAME_FIXTURES = ["glsl_analytic_gradient_64x48", "glsl_analytic_materials_env_4
                   # rt.frag in BVH mode -- traceBVH / traceBVHShadow executed by the reference GLSL for every primary, shadow,
                   # bounce and AO ray of the frame (round 2: oracle/glsl_ref.py structured_continue)
                   "glsl_bvh_closeup_64x48", "glsl_bvh_moving_64x48", "glsl_bvh_5k_gradient_64x48"]
+# Windows of the BASELINE configurations at their own resolution, spp and frame depth (make_glsl_golden.py section K): the shader shaded
+# window + margin of the full frame (full-frame gl_FragCoord, vUV, uResolution), checkers compare the inner window.
+WINDOW_FIXTURES = ["glsl_k_bench_1080p_f0-2", "glsl_k_bench_1080p_f210",                      # configs[1]: 81 920 triangles, 1080p, 4 spp, Sky_01
+                   "glsl_k_bench_4k_16spp",                                                   # configs[2]/[3] run A: 4K, 16 spp, x across 2048
+                   "glsl_k_million_1080p_64spp"]                                              # configs[4]: 1 M triangles, 64 spp, frames 0 and 31
 RMSE_TOL = 1e-4
 EXACT_MIN = 0.99
 
@@ -36,6 +43,80 @@ def check_targets(name, f, got, d):
         rmse = float(np.sqrt(np.mean(diff * diff)))
         exact = float(np.mean(a == b))
         assert rmse < RMSE_TOL and exact >= EXACT_MIN, (name, f, k, rmse, exact)
+
+
+def load_window_fixture(name):
+    """-> (fixture, nodes12, tris12, faces).  The scene is rebuilt from the names the fixture records; its SHA-256 is checked first,
+    so a change to meshgen, the host BVH builder or the PNG loader fails here instead of comparing against another scene."""
+    d = np.load(GOLDEN / f"{name}.npz")
+    nodes, tris, faces = scenes.reference_window_inputs(str(d["mesh"]), str(d["env"]))
+    for key, a in (("sha_nodes12", nodes), ("sha_tris12", tris), ("sha_env", faces)):
+        assert (key in d) == (a is not None), (name, key)
+        if a is not None:
+            assert hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() == str(d[key]), (name, key, "the scene is not the one the fixture was made from")
+    return d, nodes, tris, faces
+
+
+def window_history(d, f):
+    """The history frame f of a window fixture read, over window + margin (None for frame 0): prev{f}, else the shader's own COLOR0 of
+    frame f-1 from this fixture or from the one `chain_from` names."""
+    if f == 0:
+        return None
+    if f"prev{f}" in d:
+        return d[f"prev{f}"]
+    if f"color{f - 1}" in d:
+        return d[f"color{f - 1}"]
+    return np.load(GOLDEN / f"{d['chain_from']}.npz")[f"color{f - 1}"]
+
+
+def embed_outer(d, a, shape):
+    """A window + margin array placed into a zero full-frame array of `shape` (H, W)."""
+    x0, y0, x1, y1 = (int(v) for v in d["outer"])
+    full = np.zeros(tuple(shape) + a.shape[2:], a.dtype)
+    full[y0:y1, x0:x1] = a
+    return full
+
+
+def check_window(name, f, got, d):
+    """got: four full-frame targets; compares the inner window with the fixture's frame f at the thresholds of check_targets."""
+    x0, y0, x1, y1 = (int(v) for v in d["window"])
+    ox0, oy0 = int(d["outer"][0]), int(d["outer"][1])
+    want = {f"{k}{f}": d[f"{k}{f}"][y0 - oy0:y1 - oy0, x0 - ox0:x1 - ox0] for k in ("color", "motion", "gpos", "gnrm")}
+    check_targets(name, f, [np.ascontiguousarray(a[y0:y1, x0:x1]) for a in got], want)
+
+
+@pytest.mark.parametrize("name", WINDOW_FIXTURES)
+def test_oracle_matches_reference_glsl_baseline_windows(orc, name):
+    d, nodes, tris, faces = load_window_fixture(name)
+    outer = tuple(int(v) for v in d["outer"])
+    for i, f in enumerate(int(v) for v in d["frames"]):
+        u = rt.RtUniforms.from_buffer_copy(d["uniforms"][i].tobytes())
+        assert u.frameIndex == f and u.cameraMoved == 0
+        W, H = int(u.resolution[0]), int(u.resolution[1])
+        hist = window_history(d, f)
+        got, _ = orc.render(u, nodes, tris, faces, None if hist is None else embed_outer(d, hist, (H, W)), region=outer)
+        check_window(name, f, got, d)
+
+
+def test_baseline_windows_reach():
+    """What the window fixtures cover that the small ones do not: the BASELINE resolutions, spp and depths, pixel coordinates past 64 and
+    2048, a depth-15 tree, frames past the last switch of the TAA weights, a real cube map and the million-triangle scene."""
+    seen = {}
+    for name in WINDOW_FIXTURES:
+        d = np.load(GOLDEN / f"{name}.npz")
+        for i in range(d["uniforms"].shape[0]):
+            u = rt.RtUniforms.from_buffer_copy(d["uniforms"][i].tobytes())
+            seen.setdefault(name, []).append((int(u.resolution[0]), int(u.resolution[1]), u.spp, u.frameIndex, int(d["window"][2])))
+    assert [s[:4] for s in seen["glsl_k_bench_1080p_f0-2"]] == [(1920, 1080, 4, f) for f in range(3)]
+    assert seen["glsl_k_bench_1080p_f210"][0][3] >= 64
+    assert seen["glsl_k_bench_4k_16spp"][0][:3] == (3840, 2160, 16) and seen["glsl_k_bench_4k_16spp"][0][4] > 2048
+    assert [s[2:4] for s in seen["glsl_k_million_1080p_64spp"]] == [(64, 0), (64, 31)]
+    nodes, tris = scenes.bunny_bvh(6)
+    assert tris.shape[0] == 81920
+    d = np.load(GOLDEN / "glsl_k_million_1080p_64spp.npz")
+    assert str(d["env"]) == "Sky_01" and (d["color0"].view(np.float16)[..., :3] > 0).all()
+    gpos = d["gpos0"].view(np.float16)[..., 3]
+    assert 0.2 < np.mean(gpos != 0) < 0.9            # the window crosses a silhouette: mesh hits and sky
 
 
 @pytest.mark.parametrize("name", FRAME_FIXTURES)
@@ -68,6 +149,34 @@ def test_oracle_matches_reference_glsl_present(orc, tag):
     want = d[f"rgba_{tag}"]
     diff = np.abs(got.astype(np.int32) - want.astype(np.int32))
     assert diff.max() <= 1 and np.mean(got == want) >= 0.995, (tag, diff.max(), np.mean(got == want))
+
+
+def check_present_window(tag, got, d):
+    """got: the full-frame present output; compares the inner window with the fixture (<= 1 LSB, >= 99.5 % identical)."""
+    x0, y0, x1, y1 = (int(v) for v in d["window"])
+    ox0, oy0 = int(d["outer"][0]), int(d["outer"][1])
+    g = got[y0:y1, x0:x1].astype(np.int32)
+    w = d[f"rgba_{tag}"][y0 - oy0:y1 - oy0, x0 - ox0:x1 - ox0].astype(np.int32)
+    diff = np.abs(g - w)
+    assert diff.max() <= 1 and np.mean(g == w) >= 0.995, (tag, diff.max(), np.mean(g == w))
+
+
+def present_window_inputs():
+    """(fixture, [color, motion, gpos, gnrm] full 1080p frames): the present fixture's inputs are frame 2 of the configs[1] window fixture
+    over window + margin, zero elsewhere."""
+    d = np.load(GOLDEN / "glsl_k_present_1080p.npz")
+    src = np.load(GOLDEN / f"{d['source']}.npz")
+    f = int(d["frame"])
+    assert np.array_equal(src["outer"], d["outer"])
+    return d, [embed_outer(d, src[f"{k}{f}"], (1080, 1920)) for k in ("color", "motion", "gpos", "gnrm")]
+
+
+@pytest.mark.parametrize("tag", ["svgf", "plain", "motion"])
+def test_oracle_matches_reference_glsl_present_1080p_window(orc, tag):
+    d, targets = present_window_inputs()
+    pp = rt.RtPresentParams.from_buffer_copy(d[f"pp_{tag}"].tobytes())
+    assert tuple(pp.resolution) == (1920.0, 1080.0) and int(d["margin"]) >= 4
+    check_present_window(tag, orc.present(pp, targets), d)
 
 
 def test_oracle_matches_reference_glsl_bvh_primitives(orc):

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import opengl_raytracing_amd as rt
-from test_glsl_reference import FRAME_FIXTURES, check_targets, check_taa_regimes, check_trace_kat
+from test_glsl_reference import (FRAME_FIXTURES, WINDOW_FIXTURES, check_present_window, check_targets, check_taa_regimes, check_trace_kat,
+                                 check_window, embed_outer, load_window_fixture, present_window_inputs, window_history)
 
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -76,6 +77,51 @@ def test_hip_matches_reference_glsl_taa_weight_regimes(pipeline):
             return r.read_all()
 
         check_taa_regimes(d, render)
+
+
+# the 1 M-triangle scene on the wavefront pipeline with defaults
+WINDOW_CASES = [(n, p) for n in WINDOW_FIXTURES if "_bench_" in n for p in (rt.RT_PIPELINE_WAVEFRONT, rt.RT_PIPELINE_MEGAKERNEL)] + \
+               [(n, rt.RT_PIPELINE_WAVEFRONT) for n in WINDOW_FIXTURES if "_million_" in n]
+
+
+@pytest.mark.parametrize("name,pipeline", WINDOW_CASES)
+def test_hip_matches_reference_glsl_baseline_windows(name, pipeline):
+    """Whole frames at the BASELINE configurations' own size, spp and depth against the reference GLSL's window (section K of
+    make_glsl_golden.py).  uFrameIndex comes from the library's counter: frames before a fixture's first frame are rendered (their output
+    is irrelevant), then each checked frame gets the fixture's history over window + margin, zeros elsewhere, through rt_write_target."""
+    d, nodes, tris, faces = load_window_fixture(name)
+    u0 = rt.RtUniforms.from_buffer_copy(d["uniforms"][0].tobytes())
+    W, H = int(u0.resolution[0]), int(u0.resolution[1])
+    with rt.Renderer(pipeline=pipeline) as r:
+        r.resize(W, H)
+        r.upload_env(faces)
+        if nodes is not None:
+            r.upload_bvh(nodes, tris)
+        r.debug_builds(reset=True)
+        for i, f in enumerate(int(v) for v in d["frames"]):
+            u = rt.RtUniforms.from_buffer_copy(d["uniforms"][i].tobytes())
+            while r.frame_index < f:
+                r.render_frame(u)
+            assert r.frame_index == f
+            hist = window_history(d, f)
+            if hist is not None:
+                r.write_target(rt.RT_TARGET_COLOR, embed_outer(d, hist, (H, W)))
+            r.render_frame(u)
+            check_window(name, f, r.read_all(), d)
+        if "_million_" in name:
+            # the default any-hit walk of this scene is the quantised 64-byte node form, which no smaller fixture reaches
+            assert "QN2" in r.debug_builds()["any"]
+            assert not (r.scene_info().flags & rt.RT_SCENE_QNODES_REJECTED)
+
+
+@pytest.mark.parametrize("tag", ["svgf", "plain", "motion"])
+def test_hip_matches_reference_glsl_present_1080p_window(ren, tag):
+    d, targets = present_window_inputs()
+    pp = rt.RtPresentParams.from_buffer_copy(d[f"pp_{tag}"].tobytes())
+    ren.resize(1920, 1080)
+    for which, a in zip((rt.RT_TARGET_COLOR, rt.RT_TARGET_MOTION, rt.RT_TARGET_GPOS, rt.RT_TARGET_GNRM), targets):
+        ren.write_target(which, a)
+    check_present_window(tag, ren.present_with(pp), d)
 
 
 @pytest.mark.parametrize("tag", ["crate", "bunny"])

@@ -360,8 +360,17 @@ int rt_debug_trace(RtContext *ctx, int kind, const float *origins, const float *
 #define RT_BUILD_IMPL     0x100   /* implicit records (RT_IMPLICIT) */
 #define RT_BUILD_TIMING   0x200   /* time-stamped production build (RT_TRACE_TIMING) */
 #define RT_BUILD_PACKETS  0x400   /* (any-hit half) the packet kernel k_trace_packets ran (RT_PACKET_AO, rt_debug_trace kind 4) */
+#define RT_BUILD_BOUNCE_PROBE 0x800   /* (any-hit half) bounce rays were walked any-hit first, the hits re-traced closest-hit (RT_BOUNCE_PROBE) */
 #define RT_BUILD_ANY_SHIFT 16
 int rt_debug_builds(RtContext *ctx, uint32_t *out, int reset);
+/* The bounce probe of the wavefront frames.  Environment RT_BOUNCE_PROBE=0|1|auto (default auto): 0 traces the bounce rays with the
+ * closest-hit launch alone; 1 walks them any-hit first with tMax = uINF -- a ray that misses is answered there, the few that hit are traced again by the
+ * closest-hit launch -- in every launch set; auto does so while the share of bounce rays that hit, measured on earlier launch sets of the scene, is small.
+ * Never under RT_ANYHIT_TREE=sah.  Frames are bit-identical either way.  Counts since the last reset, summed over the frame lanes (synchronises):
+ * probed = bounce rays walked any-hit first, retraced = those of them traced again (the probe found a triangle), probeLaunches / closestLaunches = bounce
+ * launches (one per chunk of a launch set) with / without the probe.  rt_get_traced_rays counts every bounce ray once either way. */
+typedef struct RtBounceProbe { uint64_t probed, retraced, probeLaunches, closestLaunches; } RtBounceProbe;
+int rt_debug_bounce_probe(RtContext *ctx, RtBounceProbe *out, int reset);
 
 /* ---- raster preview: renderRaster (src/render/render.cpp:244-295, shaders/basic.vert / basic.frag), the reference's other frame
  * mode.  Flat-coloured meshes, MVP transform, GL_LESS depth test on a D24 buffer, no MSAA, no culling; the rules a GL 4.1 driver

@@ -137,6 +137,10 @@ class RtTracedRays(_Struct):
         return self.primary + self.shadow + self.bounce + self.bounceShadow + self.ao
 
 
+class RtBounceProbe(_Struct):   # rt_debug_bounce_probe: the bounce probe's counts (RT_BOUNCE_PROBE)
+    _fields_ = [(n, C.c_uint64) for n in ("probed", "retraced", "probeLaunches", "closestLaunches")]
+
+
 class RtSceneInfo(_Struct):
     _fields_ = [(n, i32) for n in ("nNodes", "nTris", "nInner", "treeDepth", "nWide4", "nPairs")] + \
                [(n, C.c_uint64) for n in ("bytesNodes2", "bytesNodes4", "bytesPairs", "bytesTris")] + \
@@ -157,6 +161,7 @@ RT_SCENE_QNODES_REJECTED, RT_SCENE_NOT_FUSED, RT_SCENE_IMPLICIT = 1, 2, 4   # Rt
 # rt_debug_builds: RT_BUILD_* bits of the traversal kernel builds launched (closest-hit half; the any-hit half << RT_BUILD_ANY_SHIFT)
 RT_BUILD_BITS = {"k_trace": 0x001, "LEAFB4": 0x002, "STATS": 0x004, "COOP": 0x008, "NEAR": 0x010, "QN1": 0x020, "QN2": 0x040, "FUSE": 0x080,
                  "IMPL": 0x100, "TIMING": 0x200, "PACKETS": 0x400}
+RT_BUILD_BOUNCE_PROBE = 0x800   # (any-hit half) not a k_trace build but a path of the frame: the bounce rays were walked any-hit first (Renderer.bounce_probe)
 RT_BUILD_ANY_SHIFT = 16
 
 
@@ -253,6 +258,7 @@ SIGNATURES = {
     "rt_debug_eval": (C.c_int, [C.c_void_p, C.c_int, _FP, _FP, _FP, _U32P, C.c_int]),
     "rt_debug_trace": (C.c_int, [C.c_void_p, C.c_int, _FP, _FP, _FP, C.c_float, C.c_float, _FP, C.c_int]),
     "rt_debug_builds": (C.c_int, [C.c_void_p, _U32P, C.c_int]),
+    "rt_debug_bounce_probe": (C.c_int, [C.c_void_p, C.POINTER(RtBounceProbe), C.c_int]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     "rt_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
@@ -1040,6 +1046,19 @@ class Renderer:
         s = RtRasterStats()
         self._check(lib().rt_get_raster_stats(self._h, C.byref(s)))
         return s
+
+    def bounce_probe(self, reset=False) -> RtBounceProbe:
+        """Counts of the bounce probe (RT_BOUNCE_PROBE) since the last reset: rays walked any-hit first, rays re-traced closest-hit, bounce
+        launches with / without the probe (rt_debug_bounce_probe)."""
+        b = RtBounceProbe()
+        self._check(lib().rt_debug_bounce_probe(self._h, C.byref(b), int(reset)))
+        return b
+
+    def debug_build_bits(self, reset=False) -> int:
+        """rt_debug_builds as the raw RT_BUILD_* word (closest-hit half, any-hit half << RT_BUILD_ANY_SHIFT)."""
+        v = C.c_uint32(0)
+        self._check(lib().rt_debug_builds(self._h, C.byref(v), 1 if reset else 0))
+        return v.value
 
     def debug_builds(self, reset=True) -> dict:
         """The traversal kernel builds launched since the last reset (frames and debug_trace kinds 2 - 4), as

@@ -464,6 +464,7 @@ int rt_upload_bvh(RtContext *c, const float *nodes12, int nNodes, const float *t
     c->nWide4 = c->nPairs = c->nFused = 0;
     c->sceneFlags = 0;
     c->anyStack = 0;
+    for (int i = 0; i < RT_MAX_LANES; ++i) { rt_wave_forget_share(c->wave[i]); rt_wave_set_probe_tree(c->wave[i], true); }   // a new scene: its share of bounce hits is not known
     if (nNodes == 0 || nTris == 0) return RT_OK;
     if (nTris >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "rt_upload_bvh: %d triangles exceed the 2^28 leaf encoding", nTris);
 
@@ -712,7 +713,10 @@ int rt_upload_bvh(RtContext *c, const float *nodes12, int nNodes, const float *t
                 std::memcpy(&s4[jb.at * 32 + 24 + (size_t)i], &ref, 4);
             }
         }
-        if (3 * depth4 <= 60) { w4.swap(s4); rootRef4 = 0; anyStack = 3 * depth4; }
+        if (3 * depth4 <= 60) {
+            w4.swap(s4); rootRef4 = 0; anyStack = 3 * depth4;
+            for (int i = 0; i < RT_MAX_LANES; ++i) rt_wave_set_probe_tree(c->wave[i], false);   // not the binary tree collapsed: no bounce probe
+        }
     }
     // Exact stack need of the any-hit walk (round 4): a visit of a node with nc children pushes at most nc - 1 entries (one child is gone on with),
     // so S(node) = nc - 1 + max over its inner children S(child).  Round 3 sized the stack as 3 per two binary levels INCLUDING the leaf level: 24 entries
@@ -1133,6 +1137,7 @@ int rt_resize(RtContext *c, int w, int h) {
     }
     c->sized = true;
     c->haveFrameState = false;
+    for (int i = 0; i < RT_MAX_LANES; ++i) rt_wave_forget_share(c->wave[i]);   // the share of bounce hits belongs to the old frame
     return rt_reset_accum(c);
 }
 
@@ -1887,6 +1892,20 @@ int rt_pick_pixels_host(RtContext *c, const RtUniforms *u, const int32_t *xy, in
     if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels_host: null pixel array");
     return scene_query_host(c, "rt_pick_pixels_host", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals,
                             points, nullptr);
+}
+
+int rt_debug_bounce_probe(RtContext *c, RtBounceProbe *out, int reset) {
+    if (!c || !out) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    unsigned long long v[4] = {0, 0, 0, 0};
+    for (int i = 0; i < c->nLanes; ++i) {
+        unsigned long long t[4];
+        int rc = rt_wave_bounce_probe(c->wave[i], c->lanes[i], t, reset != 0);
+        if (rc != RT_OK) return fail(c, rc, "rt_debug_bounce_probe: %s", rt_wave_error(c->wave[i]));
+        for (int k = 0; k < 4; ++k) v[k] += t[k];
+    }
+    out->probed = v[0]; out->retraced = v[1]; out->probeLaunches = v[2]; out->closestLaunches = v[3];
+    return RT_OK;
 }
 
 int rt_debug_builds(RtContext *c, uint32_t *out, int reset) {

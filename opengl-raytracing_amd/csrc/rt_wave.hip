@@ -69,6 +69,7 @@ struct WaveBuf {
     uint8_t *occ2;
     int *giPos;              // per (sample, hit): entry in queue 2, -1 when the bounce ray missed or was not cast
     int *giPerm;             // RT_BIN_GI=1 (experiment, round 4): per (sample, hit) the bounce queue entry its ray was sorted to; null = entry (sample, hit) itself
+    uint32_t *giHit;         // RT_BOUNCE_PROBE: bounce queue addresses whose any-hit probe found a triangle (dense, CH * SPP entries at most; per lane, like giT)
     // per frame, per pixel slot: everything the frame produced BEFORE the temporal resolve (the only history-dependent step)
     float4 *pendC;           // curr.rgb (frame average, fp32), motion.x
     float *pendMy;           // motion.y
@@ -347,6 +348,37 @@ struct DualQueueSrc {
     }
     RT_DEV bool dense(uint32_t r0, uint32_t r1) const { return r1 <= na && a.dense(r0, r1); }
     RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const { return a.probe_take(r, ro, rd, token); }
+};
+
+// The bounce queue walked ANY-hit first (RT_BOUNCE_PROBE): almost every bounce ray misses, and a miss does not depend on the
+// order the walk visits the leaves in.  A ray whose any-hit walk with tMax = uINF (the closest-hit launch's own start value) finds no triangle
+// gets the closest-hit launch's miss answer (uINF, -1) here; the few that hit are listed in `hitters` and walked again by the closest-hit
+// kernel (IndexedSrc), unchanged.  Bit-identical because both walks test the same leaves against the same exact boxes with the same tri_hit,
+// whose acceptance is monotone in tBest -- true of the 4-wide tree rt_upload_bvh collapses from the binary one (exact or quantised nodes),
+// not of RT_ANYHIT_TREE=sah, where the probe is never launched.
+struct BounceProbeSrc {
+    QueueSrc q;                  // the bounce queue: its tm word is the liveness value giL (1.0), NOT a distance
+    uint32_t *hitters, *hitCount;
+    float inf;                   // uINF of the frame (the host copy of its descriptor): the closest-hit walk's start value and its answer for a miss
+    RT_DEV void prepare() { q.prepare(); }
+    RT_DEV uint32_t size() const { return q.size(); }
+    typedef QueueSrc::Payload Payload;
+    RT_DEV float probe(uint32_t r, Payload &p) const { const float t = q.probe(r, p); return t < 0.0f ? t : inf; }
+    RT_DEV static Payload route(const Payload &p, int e) { return QueueSrc::route(p, e); }
+    RT_DEV void take(uint32_t r, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const { q.take(r, p, ro, rd, token); }
+    RT_DEV void store_closest(uint32_t, float, int) const {}
+    RT_DEV void store_any(uint32_t a, bool hit) const {
+        const unsigned long long m = __ballot(hit);   // the lanes that retire a hit in this step append together: one atomic per wave
+        if (!hit) { q.outT[a] = inf; q.outTri[a] = -1; return; }
+        const uint32_t lane = threadIdx.x & 63u;
+        const int leader = __ffsll((long long)m) - 1;
+        uint32_t base = 0;
+        if ((int)lane == leader) base = atomicAdd(hitCount, (uint32_t)__popcll(m));
+        base = (uint32_t)__shfl((int)base, leader, 64);
+        hitters[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = a;
+    }
+    RT_DEV bool dense(uint32_t r0, uint32_t r1) const { return q.dense(r0, r1); }
+    RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const { const float t = q.probe_take(r, ro, rd, token); return t < 0.0f ? t : inf; }
 };
 
 // A dense list of queue addresses (rt_hybrid.hip): ray r is the record at idx[r]; every listed record is a ray.
@@ -1898,7 +1930,8 @@ struct RtArenaPool {
     void *mem[RT_MAX_LANES] = {};
     size_t bytes[RT_MAX_LANES] = {};
     double q2Frac = 0.0;                       // largest share of (hit, sample) pairs whose bounce ray hit, over the launch sets of all lanes so far (read back with the NEXT
-                                               // launch set's hit count: no extra synchronisation); 0: nothing known yet
+                                               // launch set's hit count: no extra synchronisation); 0: nothing known yet.  Forgotten by rt_upload_bvh, rt_resize and an spp change
+    int q2SPP = 0;                             // samples per pixel q2Frac was measured at
     size_t maxCh[RT_MAX_LANES] = {};           // most hits an arena has been sized for
     hipEvent_t freeEv[RT_MAX_LANES] = {};      // recorded behind the last kernel of the batch that used the arena last
     hipStream_t lastUser[RT_MAX_LANES] = {};   // (a later batch on the same stream is ordered behind it anyway)
@@ -1932,6 +1965,7 @@ struct RtWave {
     size_t chunkBytes = 0;    // bytes of the per-chunk arena
     int prevChunks = 0, prevSPP = 1;   // chunks / spp of this lane's previous launch set: its hit count and bounce-hit counts are copied to hostHits[1], [2..] before the counters are cleared
     double q2FracOwn = 0.0;   // (no pool)
+    int q2SPPOwn = 0;
     void *frameArena = nullptr, *chunkArena = nullptr, *resultArena = nullptr;
     size_t resultBytes = 0;   // per-lane traversal results (what k_combine reads)
     uint32_t *counts = nullptr, *heads = nullptr;
@@ -1945,6 +1979,13 @@ struct RtWave {
     bool binGi = false;                  // RT_BIN_GI=1: bounce rays sorted by direction inside each workgroup of k_gen_direct (experiment)
     bool chunksFromSlots = false;        // RT_CHUNKS_FROM_SLOTS=1 (tests): launch the chunk loop for every pixel slot, as rounds 1-2 did
     uint32_t builds = 0;                 // RT_BUILD_* bits of the traversal builds launched since the last rt_wave_builds reset
+    // RT_BOUNCE_PROBE: 0 never, 1 always, -1 (auto) while the bounce-hit share of earlier launch sets is below kProbeShareMax
+    int probeMode = -1;
+    bool probeTree = true;               // the any-hit tree is the collapse of the binary one (rt_upload_bvh): false under RT_ANYHIT_TREE=sah
+    unsigned long long *probeAcc = nullptr;   // device, monotonic: [0] bounce rays the probe walked [1] rays it re-traced closest-hit
+    unsigned long long probeLaunches = 0, closestLaunches = 0;   // bounce launches (chunks) with / without the probe
+    unsigned long long probeBase[4] = {};     // rt_wave_bounce_probe's reset: the values above at that time
+    unsigned long long tracedProbeBase = 0;   // rt_wave_traced's reset: probeAcc[0] at that time (probed rays count as bounce rays there)
 };
 
 RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
@@ -1958,6 +1999,7 @@ RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
     if (const char *e = getenv("RT_CHUNKS_FROM_SLOTS")) w->chunksFromSlots = atoi(e) != 0;
     if (const char *e = getenv("RT_BIN_GI")) w->binGi = atoi(e) != 0;
     if (const char *e = getenv("RT_PACKET_AO")) w->packetAO = atoi(e) != 0;
+    if (const char *e = getenv("RT_BOUNCE_PROBE")) w->probeMode = std::string(e) == "auto" ? -1 : (atoi(e) != 0 ? 1 : 0);
     (void)hipEventCreateWithFlags(&w->hopEv, hipEventDisableTiming);
     if (const char *e = getenv("RT_CU_SPLIT")) {
         const int k = std::max(1, std::min(7, atoi(e)));
@@ -1984,6 +2026,7 @@ void rt_wave_destroy(RtWave *w) {
     if (w->counts) (void)hipFree(w->counts);
     if (w->heads) (void)hipFree(w->heads);
     if (w->acc) (void)hipFree(w->acc);
+    if (w->probeAcc) (void)hipFree(w->probeAcc);
     if (w->stats) (void)hipFree(w->stats);
     if (w->hostHits) (void)hipHostFree(w->hostHits);
     delete w;
@@ -2010,6 +2053,13 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
     const int S1 = A + 4 * SPP + 2, S2 = 6 * SPP;   // WaveBuf::sh1_slot
 
     if (!w->acc) { W_TRY(hipMalloc(&w->acc, 16 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->acc, 0, 16 * sizeof(unsigned long long), st)); }
+    if (!w->probeAcc) { W_TRY(hipMalloc(&w->probeAcc, 2 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->probeAcc, 0, 2 * sizeof(unsigned long long), st)); }
+    {   // the share of bounce hits belongs to one spp (rt_upload_bvh / rt_resize forget it too)
+        double &share = w->pool ? w->pool->q2Frac : w->q2FracOwn;
+        int &shareSPP = w->pool ? w->pool->q2SPP : w->q2SPPOwn;
+        if (shareSPP != SPP) { share = 0.0; shareSPP = SPP; }
+        if (w->prevSPP != SPP) w->prevChunks = 0;   // this lane's previous launch set ran at another spp: its bounce counts are not read
+    }
     // per-frame arena: cand, primT, primTri, hits
     if (w->slotsCap < nSlots) {
         if (w->frameArena) (void)hipFree(w->frameArena);
@@ -2027,9 +2077,9 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
                align_up(ch * (size_t)S1 * 4, 256) + align_up(ch * (size_t)SPP * 4, 256) + 4096;
     };
     auto q2_bytes = [&](size_t n) { return align_up(n * 6 * 16, 256) * 2 + align_up(n * 6 * 4, 256) + 4096; };
-    // ... and the results k_combine reads (1 byte per any-hit ray, 8 per bounce ray, 4 per (hit, sample)): the lane's own
+    // ... and the results k_combine reads (1 byte per any-hit ray, 8 per bounce ray, 4 per (hit, sample)) + the bounce probe's hit list (4 per bounce ray): the lane's own
     auto result_bytes = [&](size_t ch) {
-        return align_up(ch * (size_t)S1, 256) + align_up(ch * (size_t)SPP * 8, 256) + align_up(ch * (size_t)S2, 256) * 2 + align_up(ch * (size_t)SPP * 4, 256) * 2 + 4096;
+        return align_up(ch * (size_t)S1, 256) + align_up(ch * (size_t)SPP * 8, 256) + align_up(ch * (size_t)S2, 256) * 2 + align_up(ch * (size_t)SPP * 4, 256) * 3 + 4096;
     };
     // arrays that hold `ch` hits (grown, never shrunk; `room`: allocate for that many when growing, so that a batch with a few more hits fits too)
     // Shadow queue 2 (round 5): six ray records per bounce HIT, behind queue 1 in the same allocation.  Sized for the worst case -- every bounce ray
@@ -2108,6 +2158,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         wb.occOvf = (uint8_t *)take(ch * (size_t)S2);
         wb.giPos = (int *)take(ch * (size_t)SPP * 4);
         wb.giPerm = w->binGi ? (int *)take(ch * (size_t)SPP * 4) : nullptr;
+        wb.giHit = (uint32_t *)take(ch * (size_t)SPP * 4);
         wb.CH = (uint32_t)ch;
     };
     if (CHbudget * (size_t)std::max(S1, S2) >= ((size_t)1 << 31)) { w->err = "ray queue chunk exceeds 2^31 entries; lower RT_QUEUE_BUDGET_MB"; return RT_ERR_UNSUPPORTED; }
@@ -2123,7 +2174,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         wb.pendMy = (float *)p;
     }
     wb.shO = wb.shD = wb.giO = wb.giD = wb.sh2O = wb.sh2D = nullptr; wb.shT = wb.giL = wb.sh2T = nullptr;   // (deferred: carved behind k_post_primary)
-    wb.occ1 = wb.occ2 = wb.occOvf = nullptr; wb.giT = nullptr; wb.giTri = wb.giPos = wb.giPerm = nullptr;
+    wb.occ1 = wb.occ2 = wb.occOvf = nullptr; wb.giT = nullptr; wb.giTri = wb.giPos = wb.giPerm = nullptr; wb.giHit = nullptr;
     wb.q2Stride = 0;
     if (!deferred) {
         if (w->pool) w->arena = (nSlots + CH - 1) / CH > 1 ? w->lane : w->lane % w->pool->n;
@@ -2144,7 +2195,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         w->launchCap = w->chunkCap = 0;
         w->prevChunks = 0;
         const int lc = std::max(kMinLaunches, 1 + nChunks * 4), cc = std::max(4096, nChunks);
-        W_TRY(hipMalloc(&w->counts, (size_t)(64 + cc) * sizeof(uint32_t)));
+        W_TRY(hipMalloc(&w->counts, (size_t)(64 + 2 * cc) * sizeof(uint32_t)));   // [64 + c]: bounce hits of chunk c, [64 + cc + c]: its probe's hit list length
         W_TRY(hipMalloc(&w->heads, (size_t)lc * kHeadWords * sizeof(uint32_t)));
         w->launchCap = lc; w->chunkCap = cc;
     }
@@ -2158,7 +2209,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         W_TRY(hipMemcpyAsync(w->hostHits + 1, w->counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         W_TRY(hipMemcpyAsync(w->hostHits + 2, w->counts + 64, (size_t)giCopied * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
-    W_TRY(hipMemsetAsync(w->counts, 0, (size_t)(64 + nChunks) * sizeof(uint32_t), st));
+    W_TRY(hipMemsetAsync(w->counts, 0, (size_t)(64 + w->chunkCap + nChunks) * sizeof(uint32_t), st));
     W_TRY(hipMemsetAsync(w->heads, 0, (size_t)(1 + nChunks * 4) * kHeadWords * sizeof(uint32_t), st));
     // Persistent grids smaller than what fits, for the two queue launches of a cache-resident scene: they run near the vector L1's access
     // rate (0.81 accesses per clock and CU, PMC), which four and a half workgroups per CU sustain as well as six, and the
@@ -2238,6 +2289,14 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         }
         if (nChunks > 0) carve(CH);
     }
+    // RT_BOUNCE_PROBE (auto): the bounce rays are walked any-hit first while the share of them that hit, in earlier launch sets, is below kProbeShareMax.  The
+    // any-hit walk proves a miss at 0.72 of the closest-hit walk's cost on the bench view (profiles/r06_bounce_probe.txt); a hit pays both walks, so the probe
+    // pays while share < 1 - 0.72, less the second launch -- kProbeShareMax keeps a margin.  Nothing known (share 0): the closest-hit launch alone.  Both
+    // paths are exact, so a wrong guess costs time, never bits.
+    constexpr double kProbeShareMax = 0.15;
+    const bool probe = u.enableGI == 1 && w->probeTree && (w->probeMode == 1 || (w->probeMode < 0 && q2Share > 0.0 && q2Share < kProbeShareMax));
+    // the re-trace launch: a grid for about twice the expected hits (a persistent grid for ~1 % of the rays would mostly ramp up and drain)
+    const unsigned retraceBlocks = q2Share > 0.0 ? (unsigned)std::max(32.0, std::min(1e6, 2.0 * q2Share * (double)CH * SPP / 2048.0)) : 0u;
     // shared arena: everything from here to the last combine reads or writes it
     if (w->pool && nChunks > 0 && w->pool->lastUser[w->arena] && w->pool->lastUser[w->arena] != st) W_TRY(hipStreamWaitEvent(st, w->pool->freeEv[w->arena], 0));
     for (int c = 0; c < nChunks; ++c) {
@@ -2270,7 +2329,20 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
             qg.o = wb.giO; qg.d = wb.giD; qg.tm = wb.giL; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
             qg.outT = wb.giT; qg.outTri = wb.giTri; qg.outOcc = nullptr;
             rt_stage_begin(ctx, ST_TRACE_GI, st);
-            w->builds |= launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
+            if (probe) {
+                // any-hit walk of every bounce ray (misses answered in place, hits listed), then the closest-hit walk of the listed ones
+                BounceProbeSrc pb;
+                pb.q = qg; pb.hitters = wb.giHit; pb.hitCount = &wb.counts[64 + w->chunkCap + c]; pb.inf = u.inf;
+                w->builds |= launch_trace<BounceProbeSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pb, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->probeAcc + 0, w->acc + 10, tune, S ? S + 32 : nullptr)
+                             | ((uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT);
+                IndexedSrc rq;
+                rq.idx = wb.giHit; rq.count = pb.hitCount; rq.o = wb.giO; rq.d = wb.giD; rq.outT = wb.giT; rq.outTri = wb.giTri; rq.n = 0;
+                w->builds |= launch_trace<IndexedSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, rq, &wb.heads[(size_t)(1 + c * 4 + 2) * kHeadWords], w->probeAcc + 1, w->acc + 10, tune, nullptr, retraceBlocks);
+                w->probeLaunches++;
+            } else {
+                w->builds |= launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
+                w->closestLaunches++;
+            }
             rt_stage_end(ctx, ST_TRACE_GI, 1, st);
 
             W_TRY(hop(st, ss));
@@ -2387,6 +2459,12 @@ int rt_wave_traced(RtWave *w, hipStream_t st, unsigned long long *out8, bool res
     if (!w->acc) return RT_OK;
     W_TRY(hipStreamSynchronize(st));
     W_TRY(hipMemcpy(out8, w->acc, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (w->probeAcc) {   // bounce rays the probe walked count as bounce rays, once (their re-traced hits do not count again)
+        unsigned long long pa[2];
+        W_TRY(hipMemcpy(pa, w->probeAcc, sizeof pa, hipMemcpyDeviceToHost));
+        out8[4] += pa[0] - w->tracedProbeBase;
+        if (reset) w->tracedProbeBase = pa[0];
+    }
     if (w->stats) {
         unsigned long long v[64];
         W_TRY(hipMemcpy(v, w->stats, sizeof v, hipMemcpyDeviceToHost));
@@ -2424,3 +2502,23 @@ int rt_wave_traced(RtWave *w, hipStream_t st, unsigned long long *out8, bool res
     if (reset) W_TRY(hipMemset(w->acc, 0, 16 * sizeof(unsigned long long)));
     return RT_OK;
 }
+
+int rt_wave_bounce_probe(RtWave *w, hipStream_t st, unsigned long long *out4, bool reset) {
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (!w) return RT_OK;
+    unsigned long long v[4] = {0, 0, w->probeLaunches, w->closestLaunches};
+    if (w->probeAcc) {
+        W_TRY(hipStreamSynchronize(st));
+        W_TRY(hipMemcpy(v, w->probeAcc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < 4; ++i) { out4[i] = v[i] - w->probeBase[i]; if (reset) w->probeBase[i] = v[i]; }
+    return RT_OK;
+}
+
+void rt_wave_forget_share(RtWave *w) {
+    if (!w) return;
+    if (w->pool) w->pool->q2Frac = 0.0; else w->q2FracOwn = 0.0;
+    w->prevChunks = 0;   // the bounce counts of the launch set in flight belong to the old scene / frame size: not read
+}
+
+void rt_wave_set_probe_tree(RtWave *w, bool collapsed) { if (w) w->probeTree = collapsed; }

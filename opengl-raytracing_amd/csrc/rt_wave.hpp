@@ -32,6 +32,14 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t stream, const rtd::Dev
 // any-hit / bounce traversal launches, [11..13] the same after merging the lanes of a wave that read the same record (only
 // counted by the diagnostic kernels, RT_TRACE_STATS=1; 0 otherwise)
 int rt_wave_traced(RtWave *w, hipStream_t stream, unsigned long long *out16, bool reset);
+// RT_BOUNCE_PROBE since the last reset, 4 words: [0] bounce rays walked any-hit first [1] of them re-traced closest-hit (the probe found a triangle)
+// [2] bounce launches (chunks) with the probe [3] without it
+int rt_wave_bounce_probe(RtWave *w, hipStream_t stream, unsigned long long *out4, bool reset);
+// The share of bounce hits of earlier launch sets (what shadow queue 2 is sized from and the bounce probe is chosen by) belongs to a scene and a frame size:
+// rt_upload_bvh and rt_resize forget it (an spp change does so in rt_wave_render)
+void rt_wave_forget_share(RtWave *w);
+// rt_upload_bvh: whether the any-hit tree is the collapse of the binary tree -- the bounce probe's exactness needs it (false: RT_ANYHIT_TREE=sah)
+void rt_wave_set_probe_tree(RtWave *w, bool collapsed);
 
 // Closest-hit traversal of the rays listed in idx[0 .. *count) (queue addresses into o / d) with the persistent kernel of the wavefront
 // pipeline; results to outT / outTri at the same address.  heads: rt_wave_head_words() zeroed uint32 cursor words.

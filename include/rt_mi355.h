@@ -470,6 +470,55 @@ int rt_trace_scene_rays_host(RtContext *ctx, const RtUniforms *u, int kind, int 
 int rt_pick_pixels_host(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n,
                         RtHit *hits, int32_t *objects, float *normals, float *points);
 
+/* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
+ * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
+ * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what
+ * rt_gather_triangles_checked(positions, indices, M) -> rt_build_bvh_gpu -> rt_upload_bvh would have installed -- reached without copying geometry or
+ * records to or from the host, without allocating and without blocking the host.  Frames, the hybrid extension, ray / scene queries and picking work
+ * unchanged on it.
+ *  - rt_upload_bvh after rt_mesh_upload installs its scene as always and releases the dynamic mesh; a later rt_mesh_rebuild is RT_ERR_INVALID.
+ *    rt_mesh_rebuild before rt_mesh_upload: RT_ERR_INVALID as well.
+ *  - rt_mesh_upload removes whatever scene the context had (as rt_upload_bvh does) and installs none: the context has no BVH until the first rebuild.
+ *  - A rebuild does not reset the accumulation (neither does rt_upload_bvh): call rt_reset_accum or render with cameraMoved, as the application does.
+ *  - The quantised any-hit form is built under rt_upload_bvh's rule (tree size, RT_QNODES).  Whether it could be built is known on the device only and the
+ *    host chooses the kernel, so when -- and only when -- that form is in use, rt_mesh_rebuild reads one status word back and waits for the rebuild: the
+ *    one host wait of the path (RtMeshInfo.hostSyncs).  On failure the scene carries RT_SCENE_QNODES_REJECTED and the exact nodes are walked.
+ *  - RT_FUSED, RT_IMPLICIT and RT_ANYHIT_TREE=sah (measured and rejected record forms) are not rebuilt on the device: rt_mesh_upload returns
+ *    RT_ERR_UNSUPPORTED under any of them and says which.
+ *  - The bounce-share prediction of the wavefront frames survives the rebuilds of one mesh (same topology; frames do not depend on it);
+ *    rt_mesh_upload forgets it, as rt_upload_bvh does.
+ *  - Tile-parallel ranks each rebuild their own copy; nothing is exchanged. */
+/* What the triangle count alone determines: the builder splits every range at its middle and stops at <= 8 triangles, so numbering, links, leaf ranges,
+ * record counts, stack need and array sizes of every device record form follow from nTris.  quantised / bytesNodes4: under rt_upload_bvh's rule for the
+ * quantised any-hit form (RT_QNODES in this process's environment), assuming it can be built.  Host only.  nTris <= 0: RT_ERR_INVALID; nTris >= 2^28 or a
+ * depth beyond 32: RT_ERR_UNSUPPORTED, as rt_upload_bvh refuses them. */
+typedef struct RtBvhLayout {
+    int32_t nTris, nNodes, nInner, treeDepth, nWide4, nPairs, anyStack, quantised;
+    uint64_t bytesNodes2, bytesNodes4, bytesPairs, bytesTris;   /* as RtSceneInfo reports them */
+} RtBvhLayout;
+int rt_bvh_layout(int nTris, RtBvhLayout *out);
+/* Mesh::setupMesh's arrays (3 floats per vertex, index triples), checked as rt_gather_triangles_checked checks them (every index < nVerts) and
+ * nIdx % 3 == 0.  Keeps both on the device, lays the topology out on the host, uploads the index tables and allocates, once, every scene array and all
+ * build scratch.  May synchronise and allocate; the only call of the group that may.  nIdx == 0 releases the mesh (and the scene it installed). */
+int rt_mesh_upload(RtContext *ctx, const float *positions, int nVerts, const uint32_t *indices, int nIdx);
+/* The device array of object-space positions (nVerts x 3 floats) for a caller that deforms the mesh on the device; writes must be ordered on
+ * rt_stream()'s stream, as the rays of rt_trace_rays.  rt_mesh_set_positions: the same from host memory (nVerts x 3 floats), copied on that stream. */
+int rt_mesh_positions(RtContext *ctx, void **devPtr, size_t *bytes);
+int rt_mesh_set_positions(RtContext *ctx, const float *positions);
+/* Gather with the model matrix M16 (column-major; NULL: identity), build, emit every record form, install.  Enqueued on rt_stream()'s stream, ordered
+ * after the frames and queries already enqueued on every frame lane and before whatever is enqueued next, by events.  No allocation; no host wait
+ * except the one named above. */
+int rt_mesh_rebuild(RtContext *ctx, const float *M16);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild. */
+typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
+int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
+/* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
+ * alike; it is what makes the contract above checkable.  *bytes = size of the array (0: absent); dst == NULL only asks for the size; a capacity below
+ * it: RT_ERR_INVALID. */
+enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 = 2, RT_SCENE_ARRAY_NODES2W = 3, RT_SCENE_ARRAY_NODES4 = 4,
+       RT_SCENE_ARRAY_QNODES4 = 5, RT_SCENE_ARRAY_LEAFBOX = 6 };
+int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
+
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 
 void rt_default_render_params(RtRenderParams *p);      /* include/render/RenderParams.h:20-238 */

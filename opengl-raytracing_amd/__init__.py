@@ -147,6 +147,20 @@ class RtSceneInfo(_Struct):
                [("nFused", i32), ("flags", i32), ("implicitDepth", i32), ("reserved", i32)]
 
 
+class RtBvhLayout(_Struct):   # rt_bvh_layout: what the triangle count alone determines
+    _fields_ = [(n, i32) for n in ("nTris", "nNodes", "nInner", "treeDepth", "nWide4", "nPairs", "anyStack", "quantised")] + \
+               [(n, C.c_uint64) for n in ("bytesNodes2", "bytesNodes4", "bytesPairs", "bytesTris")]
+
+
+class RtMeshInfo(_Struct):   # rt_get_mesh_info: the dynamic mesh and what its rebuilds cost the host
+    _fields_ = [("nVerts", i32), ("nTris", i32)] + [(n, C.c_uint64) for n in ("rebuilds", "allocations", "hostSyncs", "scratchBytes", "sceneBytes")]
+
+
+# rt_debug_read_scene: the device scene arrays
+RT_SCENE_ARRAY_TRIS, RT_SCENE_ARRAY_PAIRS, RT_SCENE_ARRAY_NODES2, RT_SCENE_ARRAY_NODES2W, RT_SCENE_ARRAY_NODES4, RT_SCENE_ARRAY_QNODES4, RT_SCENE_ARRAY_LEAFBOX = range(7)
+SCENE_ARRAYS = {"tris": 0, "pairs": 1, "nodes2": 2, "nodes2w": 3, "nodes4": 4, "qnodes4": 5, "leafbox": 6}
+
+
 class RtMemoryInfo(_Struct):
     _fields_ = [(n, C.c_uint64) for n in ("queueArenaBytes", "frameArrayBytes", "hybridArenaBytes", "deviceFreeBytes", "deviceTotalBytes")] + \
                [(n, i32) for n in ("queueArenas", "lanes")]
@@ -269,6 +283,13 @@ SIGNATURES = {
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_pick_pixels": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_pick_pixels_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
+    "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
+    "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_positions": (C.c_int, [C.c_void_p, _FP]),
+    "rt_mesh_rebuild": (C.c_int, [C.c_void_p, _FP]),
+    "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
+    "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
     "rt_default_camera": (None, [C.POINTER(RtCamera)]),
     "rt_default_bvh_transform": (None, [_FP]),
@@ -456,6 +477,15 @@ def gather_triangles(positions, indices, model=None) -> np.ndarray:
     return out[:n]
 
 
+def bvh_layout(n_tris: int) -> RtBvhLayout:
+    """What the triangle count alone determines of the BVH scene (rt_bvh_layout): node / record counts, stack need, array sizes."""
+    out = RtBvhLayout()
+    rc = lib().rt_bvh_layout(int(n_tris), C.byref(out))
+    if rc != RT_OK:
+        raise RtError(rc, (lib().rt_last_error(None) or b"").decode())
+    return out
+
+
 def build_bvh(tris9):
     """-> (nodes12 [nNodes,12], tris12 [nTris,12]) in the reference's texture-buffer layout."""
     t = _f32(tris9).reshape(-1, 9)
@@ -611,6 +641,67 @@ class Renderer:
         n, t = _f32(nodes12).reshape(-1, 12), _f32(tris12).reshape(-1, 12)
         self._check(lib().rt_upload_bvh(self._h, _fp(n), n.shape[0], _fp(t), t.shape[0]))
         self.n_nodes, self.n_tris = n.shape[0], t.shape[0]
+
+    # ---- dynamic mesh: the BVH scene rebuilt on the device
+    def mesh_upload(self, positions, indices):
+        """Positions [V,3] float32 and triangle indices to the device, topology tables and every scene array allocated (rt_mesh_upload).  Installs no
+        scene: mesh_rebuild does.  indices=None or empty releases the mesh."""
+        idx = np.zeros(0, np.uint32) if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        v = _f32(positions).reshape(-1, 3)
+        self._check(lib().rt_mesh_upload(self._h, _fp(v), v.shape[0], idx.ctypes.data_as(_U32P), idx.size))
+        self.n_nodes = self.n_tris = 0
+        self._mesh_verts = v.shape[0] if idx.size else 0
+
+    def mesh_positions(self, as_torch=None):
+        """The device array of object-space positions.  With torch (as_torch=None: when it imports) a float32 [V,3] tensor that aliases it, zero-copy;
+        writes to it must be ordered on stream() (run them under torch.cuda.stream(torch.cuda.ExternalStream(ren.stream()))).  Else (pointer, bytes)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_positions(self._h, C.byref(ptr), C.byref(n)))
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        if not as_torch:
+            return ptr.value, n.value
+        import torch
+        nv = n.value // 12
+
+        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+            __cuda_array_interface__ = {"shape": (nv, 3), "typestr": "<f4", "data": (ptr.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    def mesh_set_positions(self, positions):
+        v = _f32(positions).reshape(-1, 3)
+        if v.shape[0] != getattr(self, "_mesh_verts", 0):
+            raise RtError(RT_ERR_INVALID, f"mesh_set_positions: {v.shape[0]} vertices, the mesh has {getattr(self, '_mesh_verts', 0)}")
+        self._check(lib().rt_mesh_set_positions(self._h, _fp(v)))   # pageable memory: staged before the call returns, as a frame's uniforms are
+
+    def mesh_rebuild(self, model=None):
+        """Gather with the model matrix (column-major 16 floats or a 4x4 array as default_bvh_transform returns it; None: identity), build the BVH and
+        every device record form on the device, install (rt_mesh_rebuild).  Asynchronous; no host wait unless the quantised any-hit form is in use."""
+        m = None if model is None else _f32(model).reshape(-1)
+        if m is not None and m.size != 16:
+            raise RtError(RT_ERR_INVALID, "mesh_rebuild: model must have 16 floats")
+        self._check(lib().rt_mesh_rebuild(self._h, None if m is None else _fp(m)))
+        i = self.scene_info()
+        self.n_nodes, self.n_tris = i.nNodes, i.nTris
+
+    def mesh_info(self) -> RtMeshInfo:
+        i = RtMeshInfo()
+        self._check(lib().rt_get_mesh_info(self._h, C.byref(i)))
+        return i
+
+    def debug_read_scene(self, which) -> np.ndarray:
+        """One device scene array as bytes (uint8), padding included; empty when the scene has no such array.  which: RT_SCENE_ARRAY_* or its name."""
+        which = SCENE_ARRAYS[which] if isinstance(which, str) else int(which)
+        n = C.c_size_t()
+        self._check(lib().rt_debug_read_scene(self._h, which, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            self._check(lib().rt_debug_read_scene(self._h, which, C.c_void_p(out.ctypes.data), out.size, C.byref(n)))
+        return out
 
     def build_bvh_gpu(self, tris9):
         """Median-split BVH built on this context's GPU -> (nodes12, tris12); same tree as build_bvh, leaf-internal order may differ."""

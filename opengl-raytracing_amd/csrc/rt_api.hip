@@ -18,6 +18,7 @@
 
 #include "../../include/rt_mi355.h"
 #include "rt_frame.hpp"
+#include "rt_mesh.hpp"
 #include "rt_wave.hpp"
 
 using namespace rtd;
@@ -61,6 +62,13 @@ struct RtContext {
     uint32_t leafBoxMagic = 0;       // dLeafBox index of a leaf = (first pair record * magic) >> 32 (0: = first)
     int anyStack = 0;                // stack entries of the any-hit walk (0: from the binary depth)
     float rootMin[3] = {0, 0, 0}, rootMax[3] = {0, 0, 0};
+    size_t leafBoxBytes = 0;         // bytes of dLeafBox
+    // dynamic mesh: its arrays belong to `mesh`; once a rebuild has installed them the scene pointers above alias them (sceneFromMesh)
+    rtl::Mesh *mesh = nullptr;
+    bool sceneFromMesh = false;
+    float *dRootBox = nullptr;       // sceneFromMesh: node 0's box on the device -- the host does not know it (rootMin / rootMax above are not used then)
+    hipEvent_t evMeshLane[RT_MAX_LANES] = {}, evMeshDone = nullptr;   // a rebuild waits for every lane / every lane waits for the rebuild
+    uint64_t meshRebuilds = 0, meshHostSyncs = 0;
     // frame state
     FrameGeom g{};
     bool sized = false;
@@ -202,12 +210,18 @@ __global__ void k_debug_eval(int op, const float *a, const float *b, const float
     out[i] = r;
 }
 
+// A scene a device rebuild installed: the frame descriptor the host copied carries no root box; take it from the device.
+__global__ void k_frame_root_box(DevFrame *fr) {
+    if (threadIdx.x == 0) scene_take_root_box(fr->sc);
+}
+
 __global__ __launch_bounds__(256) void k_debug_trace(DevScene sc, int kind, const float *o, const float *d, const float *tMax, float eps,
                                                      float inf, float *out7, int n) {
     __shared__ StackEntry stack[4 * 32 * 64];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     StackEntry *stk = &stack[(threadIdx.x >> 6) * 32 * 64 + (threadIdx.x & 63)];
     if (i >= n) return;
+    scene_take_root_box(sc);
     Work w;
     work_zero(w);
     V3 ro = ld3(o + (size_t)i * 3), rd = ld3(d + (size_t)i * 3);
@@ -252,6 +266,7 @@ DevScene make_dev_scene(const RtContext *c) {
     s.anyStack = c->anyStack;
     std::memcpy(s.rootMin, c->rootMin, 12);
     std::memcpy(s.rootMax, c->rootMax, 12);
+    s.rootBox = c->sceneFromMesh ? c->dRootBox : nullptr;
     return s;
 }
 
@@ -285,6 +300,21 @@ int ensure_staging(RtContext *c, size_t bytes) {
     HIP_TRY(c, hipMalloc(&c->dStaging, bytes));
     c->stagingBytes = bytes;
     return RT_OK;
+}
+
+// Lets go of the dynamic mesh; a scene its rebuild installed goes with it (the scene pointers alias the mesh's arrays).  Callers have synchronised.
+void release_mesh(RtContext *c) {
+    if (c->sceneFromMesh) {
+        c->dWNodes = c->dW4 = c->dTris = c->dWNodesW = c->dPairs = c->dQ4 = c->dLeafBox = nullptr;
+        c->nNodes = c->nTris = c->nInner = 0;
+        c->sceneFromMesh = false;
+        c->dRootBox = nullptr;
+    }
+    rtl::mesh_destroy(c->mesh);
+    c->mesh = nullptr;
+    for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->evMeshLane[i]) (void)hipEventDestroy(c->evMeshLane[i]); c->evMeshLane[i] = nullptr; }
+    if (c->evMeshDone) (void)hipEventDestroy(c->evMeshDone);
+    c->evMeshDone = nullptr;
 }
 
 int last_lane(const RtContext *c) { return (c->writeIdx + c->nLanes - 1) % c->nLanes; }   // lane of the frame rendered last
@@ -409,6 +439,7 @@ void rt_destroy(RtContext *c) {
     (void)hipSetDevice(c->cfg.device);
     (void)sync_all(c);
     (void)rt_comm_destroy(c);
+    release_mesh(c);
     free_targets(c);
     for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->hybrid[i]) rt_hybrid_destroy(c->hybrid[i]); if (c->wave[i]) rt_wave_destroy(c->wave[i]); if (c->dFrame[i]) (void)hipFree(c->dFrame[i]); if (c->evDone[i]) (void)hipEventDestroy(c->evDone[i]); }
     rt_raster_destroy(c->raster);
@@ -444,6 +475,7 @@ int rt_upload_bvh(RtContext *c, const float *nodes12, int nNodes, const float *t
     return guarded(c, "rt_upload_bvh", [&]() -> int {
     (void)hipSetDevice(c->cfg.device);
     HIP_TRY(c, sync_all(c));
+    release_mesh(c);   // an upload takes the scene over from the dynamic mesh
     if (c->dWNodes) (void)hipFree(c->dWNodes);
     if (c->dW4) (void)hipFree(c->dW4);
     if (c->dQ4) (void)hipFree(c->dQ4);
@@ -1031,6 +1063,7 @@ int rt_upload_bvh(RtContext *c, const float *nodes12, int nNodes, const float *t
         HIP_TRY(c, hipMemcpy(c->dQ4, q4.data(), q4.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(c, hipMalloc(&c->dLeafBox, leafBox.size() * 4));
         HIP_TRY(c, hipMemcpy(c->dLeafBox, leafBox.data(), leafBox.size() * 4, hipMemcpyHostToDevice));
+        c->leafBoxBytes = leafBox.size() * 4;
     }
     if (!iN2.empty()) {
         HIP_TRY(c, hipMalloc(&c->dIN2, iN2.size() * sizeof(float)));
@@ -1082,6 +1115,154 @@ int rt_build_bvh_gpu(RtContext *c, const float *tris9, int nTris, float *nodes12
     const int rc = rtl::build_bvh_gpu(c->cfg.device, tris9, nTris, nodes12, tris12, &err);
     if (rc < 0) return fail(c, rc, "rt_build_bvh_gpu: %s", err ? err : "bad arguments");
     return rc;
+}
+
+// ---- dynamic mesh: rt_mesh.hip builds, this file orders the rebuild against the lanes and installs its arrays
+static bool want_quantised(size_t nWide4, int rootRef4) {   // rt_upload_bvh's rule
+    const int qmode = getenv("RT_QNODES") ? atoi(getenv("RT_QNODES")) : -1;
+    return rootRef4 == 0 && (qmode > 0 || (qmode < 0 && nWide4 * 112 > kQNodesAbove));
+}
+
+int rt_bvh_layout(int nTris, RtBvhLayout *out) {
+    if (!out) return RT_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    return guarded(nullptr, "rt_bvh_layout", [&]() -> int {
+        rtl::BvhLayout L;
+        const int rc = rtl::bvh_layout(nTris, L);
+        if (rc == RT_ERR_INVALID) return fail(nullptr, rc, "rt_bvh_layout: nTris = %d", nTris);
+        if (rc != RT_OK) return fail(nullptr, rc, "rt_bvh_layout: %d triangles exceed the 2^28 leaf encoding or the 32-entry traversal stack", nTris);
+        out->nTris = L.nTris; out->nNodes = L.nNodes; out->nInner = L.nInner; out->treeDepth = L.treeDepth;
+        out->nWide4 = (int32_t)L.nWide4; out->nPairs = (int32_t)L.nPairs; out->anyStack = L.anyStack;
+        out->quantised = want_quantised(L.nWide4, L.rootRef4) ? 1 : 0;
+        out->bytesNodes2 = (uint64_t)std::max(L.nInner, 1) * 64;
+        out->bytesNodes4 = out->quantised ? (uint64_t)L.nWide4 * 64 + (uint64_t)L.nLeaves * 32 : (uint64_t)L.nWide4 * 128;
+        out->bytesPairs = (uint64_t)L.nPairs * 80;
+        out->bytesTris = (uint64_t)L.nTris * 48;
+        return RT_OK;
+    });
+}
+
+int rt_mesh_upload(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx) {
+    if (!c) return RT_ERR_INVALID;
+    if (nIdx < 0 || nVerts < 0 || (nIdx > 0 && (!positions || !indices || nVerts == 0))) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: bad arguments");
+    if (nIdx % 3 != 0) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: %d indices are not a list of triangles", nIdx);
+    for (int k = 0; k < nIdx; ++k)
+        if (indices[k] >= (uint32_t)nVerts) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: index %d names vertex %u of %d", k, indices[k], nVerts);
+    if (nIdx > 0) {
+        if (getenv("RT_FUSED") && atoi(getenv("RT_FUSED")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: RT_FUSED records are not rebuilt on the device");
+        if (getenv("RT_IMPLICIT") && atoi(getenv("RT_IMPLICIT")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: RT_IMPLICIT records are not rebuilt on the device");
+        if (getenv("RT_ANYHIT_TREE") && std::string(getenv("RT_ANYHIT_TREE")) == "sah") return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device");
+        if (nIdx / 3 >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: %d triangles exceed the 2^28 leaf encoding", nIdx / 3);
+    }
+    const int rc = rt_upload_bvh(c, nullptr, 0, nullptr, 0);   // waits for the lanes, removes the scene and the previous mesh, forgets the bounce share
+    if (rc != RT_OK || nIdx == 0) return rc;
+    return guarded(c, "rt_mesh_upload", [&]() -> int {
+        rtl::BvhLayout L;
+        const int lr = rtl::bvh_layout(nIdx / 3, L);
+        if (lr != RT_OK) return fail(c, lr, "rt_mesh_upload: %d triangles cannot be laid out", nIdx / 3);
+        const char *err = nullptr;
+        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, want_quantised(L.nWide4, L.rootRef4), &c->mesh, &err);
+        if (mr != RT_OK) { c->mesh = nullptr; return fail(c, mr, "rt_mesh_upload: %s", err ? err : "layout failed"); }
+        bool ok = hipEventCreateWithFlags(&c->evMeshDone, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; ok && i < c->nLanes; ++i) ok = hipEventCreateWithFlags(&c->evMeshLane[i], hipEventDisableTiming) == hipSuccess;
+        if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "rt_mesh_upload: event creation failed"); }
+        c->meshRebuilds = c->meshHostSyncs = 0;
+        return RT_OK;
+    });
+}
+
+int rt_mesh_positions(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_positions: no mesh (rt_mesh_upload first)");
+    *devPtr = rtl::mesh_positions(c->mesh);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
+    return RT_OK;
+}
+
+int rt_mesh_set_positions(RtContext *c, const float *positions) {
+    if (!c || !positions) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_set_positions: no mesh (rt_mesh_upload first)");
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_positions(c->mesh), positions, (size_t)rtl::mesh_verts(c->mesh) * 12, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
+    return RT_OK;
+}
+
+int rt_mesh_rebuild(RtContext *c, const float *M16) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_rebuild: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    // every lane's frames and queries read the arrays that are about to be rewritten: the rebuild waits for them ...
+    for (int i = 0; i < c->nLanes; ++i) {
+        if (c->lanes[i] == st) continue;
+        HIP_TRY(c, hipEventRecord(c->evMeshLane[i], c->lanes[i]));
+        HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
+    }
+    const char *err = nullptr;
+    int rc = rtl::mesh_rebuild(c->mesh, st, M16 ? M16 : kIdentity, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_rebuild: %s", err ? err : "launch failed");
+    // ... and whatever a lane is given next waits for the rebuild
+    HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
+    for (int i = 0; i < c->nLanes; ++i)
+        if (c->lanes[i] != st) HIP_TRY(c, hipStreamWaitEvent(c->lanes[i], c->evMeshDone, 0));
+    const rtl::BvhLayout &L = rtl::mesh_layout(c->mesh);
+    const rtl::MeshScene &sc = rtl::mesh_scene(c->mesh);
+    bool okQ = sc.q4 != nullptr;
+    if (sc.q4) {   // the host picks the any-hit kernel by whether the quantised nodes exist: the one allowed wait
+        rc = rtl::mesh_quantised_ok(c->mesh, st, okQ, &err);
+        ++c->meshHostSyncs;
+        if (rc != RT_OK) return fail(c, rc, "rt_mesh_rebuild: %s", err ? err : "status read failed");
+    }
+    // install: pointers and counts are those of the mesh, the same at every rebuild
+    c->dWNodes = sc.wnodes; c->dWNodesW = sc.wnodesW; c->dW4 = sc.w4; c->dPairs = sc.pairs; c->dTris = sc.tris;
+    c->dQ4 = okQ ? sc.q4 : nullptr; c->dLeafBox = okQ ? sc.leafBox : nullptr;
+    c->leafBoxBytes = sc.leafBoxBytes; c->leafBoxMagic = sc.leafBoxMagic; c->nLeafBoxes = L.nLeaves;
+    c->sceneFlags = (sc.q4 && !okQ) ? RT_SCENE_QNODES_REJECTED : 0;
+    if (sc.q4 && !okQ && getenv("RT_VERBOSE")) fprintf(stderr, "[rt_mesh_rebuild] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n");
+    c->nNodes = L.nNodes; c->nTris = L.nTris; c->nInner = L.nInner; c->treeDepth = L.treeDepth;
+    c->nWide4 = L.nWide4; c->nPairs = L.nPairs; c->nFused = 0;
+    c->rootRef = L.rootRef; c->rootRefW = L.rootRefW; c->rootRef4 = L.rootRef4; c->anyStack = L.anyStack;
+    c->dRootBox = sc.rootBox;
+    c->sceneFromMesh = true;
+    ++c->meshRebuilds;
+    return RT_OK;
+}
+
+int rt_get_mesh_info(RtContext *c, RtMeshInfo *out) {
+    if (!c || !out) return RT_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!c->mesh) return RT_OK;
+    out->nVerts = rtl::mesh_verts(c->mesh); out->nTris = rtl::mesh_layout(c->mesh).nTris;
+    out->rebuilds = c->meshRebuilds; out->allocations = rtl::mesh_allocations(c->mesh); out->hostSyncs = c->meshHostSyncs;
+    out->scratchBytes = rtl::mesh_scratch_bytes(c->mesh); out->sceneBytes = rtl::mesh_scene_bytes(c->mesh);
+    return RT_OK;
+}
+
+int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, size_t *bytes) {
+    if (!c || !bytes) return RT_ERR_INVALID;
+    *bytes = 0;
+    const void *src = nullptr;
+    size_t n = 0;
+    const bool have = c->nNodes > 0 && c->nTris > 0;
+    switch (which) {
+        case RT_SCENE_ARRAY_TRIS: src = c->dTris; n = (size_t)(c->nTris + 8) * 48; break;
+        case RT_SCENE_ARRAY_PAIRS: src = c->dPairs; n = (c->nPairs + 8) * 80; break;
+        case RT_SCENE_ARRAY_NODES2: src = c->dWNodes; n = (size_t)std::max(c->nInner, 1) * 64; break;
+        case RT_SCENE_ARRAY_NODES2W: src = c->dWNodesW; n = (size_t)std::max(c->nInner, 1) * 64; break;
+        case RT_SCENE_ARRAY_NODES4: src = c->dW4; n = c->nWide4 * 128; break;
+        case RT_SCENE_ARRAY_QNODES4: src = c->dQ4; n = c->nWide4 * 64; break;
+        case RT_SCENE_ARRAY_LEAFBOX: src = c->dLeafBox; n = c->leafBoxBytes; break;
+        default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
+    }
+    if (!have || !src) return RT_OK;
+    *bytes = n;
+    if (!dst) return RT_OK;
+    if (capacity < n) return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d has %zu bytes, room for %zu", which, n, capacity);
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, sync_all(c));
+    HIP_TRY(c, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 int rt_upload_env(RtContext *c, const uint8_t *faces, int faceSize, int channels) {
@@ -1193,6 +1374,7 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     hipStream_t st = c->lanes[lane];
     if (c->serialFrames) HIP_TRY(c, hipStreamWaitEvent(st, c->evDone[prevLane], 0));
     HIP_TRY(c, hipMemcpyAsync(c->dFrame[lane], &fr, sizeof(fr), hipMemcpyHostToDevice, st));
+    if (fr.sc.rootBox) hipLaunchKernelGGL(k_frame_root_box, dim3(1), dim3(64), 0, st, c->dFrame[lane]);
     Targets tg;
     tg.color = c->dColor[c->writeIdx];
     tg.prev = c->dColor[prevLane];
@@ -1656,6 +1838,7 @@ static int debug_trace_wave(RtContext *c, int kind, const float *origins, const 
          hipMemset(dHeads, 0, rt_wave_head_words() * 4) == hipSuccess && hipMemset(dOcc, 0, (size_t)n) == hipSuccess && hipMemset(dTri, 0xff, (size_t)n * 4) == hipSuccess &&
          hipMemcpy(dF, host, sizeof(DevFrame), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { freeAll(); return fail(c, RT_ERR_HIP, "rt_debug_trace: allocation / upload failed"); }
+    if (host->sc.rootBox) hipLaunchKernelGGL(k_frame_root_box, dim3(1), dim3(64), 0, c->stream, dF);
     c->debugBuilds |= packets ? rt_wave_debug_packets(c->stream, c->cus, c->treeDepth, dF, host->sc, dO, dD, dT, dCnt, (uint32_t)P, dOcc, dHeads)
                               : rt_wave_debug_trace(c->stream, c->cus, c->treeDepth, dF, host->sc, any, dO, dD, dT, dCnt, un, dOutT, dTri, dOcc, dHeads);
     std::vector<float> t((size_t)n);

@@ -51,7 +51,13 @@ struct DevScene {
     int hasBVH;
     float rootMin[3], rootMax[3];
     int anyStack;   // per-lane stack entries the any-hit walk of w4 can need (3 per level of the 4-wide tree)
+    const float *rootBox;   // a scene rt_mesh_rebuild installed: node 0's box on the device (min.xyz, max.xyz), which the host does not know; whoever
+                            // writes a scene block to the device copies it into rootMin / rootMax (scene_take_root_box).  null: they hold it already
 };
+RT_DEV void scene_take_root_box(DevScene &sc) {
+    if (!sc.rootBox) return;
+    for (int k = 0; k < 3; ++k) { sc.rootMin[k] = sc.rootBox[k]; sc.rootMax[k] = sc.rootBox[3 + k]; }
+}
 
 struct Work {   // RtCounters, per lane
     uint32_t raysClosest, raysShadow, raysAnalytic, nodeFetch, triFetch, envLookup, hitPixels;

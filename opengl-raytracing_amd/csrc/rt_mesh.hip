@@ -1,0 +1,498 @@
+// rt_mesh.hip -- the dynamic mesh: rt_gather_triangles -> rt_build_bvh_gpu -> rt_upload_bvh as one fixed sequence of kernels on one
+// stream, with no copy of geometry or records to or from the host, no allocation and no host wait.
+//
+// The reference's builder splits every range at its middle and stops at <= 8 triangles (bvh.cpp:62-76), so node numbering, links, leaf ranges and with
+// them every reference, record slot, stack need and array size of every device record form depend on the triangle count alone.  mesh_create lays that
+// out once on the host (the derivations of rt_upload_bvh, applied to the skeleton instead of to decoded nodes) and keeps it on the device as index
+// tables; what depends on the geometry -- node boxes and the order of the triangles -- is computed by the level kernels of rt_bvh_build.hpp, and one
+// emission kernel per record form then writes whole records through the tables.  Every array ends up byte for byte as rt_upload_bvh would have left it.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <new>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "../../include/rt_mi355.h"
+#include "rt_bvh_build.hpp"
+#include "rt_mesh.hpp"
+
+#pragma clang fp contract(off)
+
+#define RT_NO_CHILD 0x7fffffff   // rt_device_shade.hpp
+
+namespace {
+
+struct Mat16 { float m[16]; };
+struct Wn2Tab { int slotL, slotR, refL, refR, refLW, refRW; };   // one two-child record: bounds slots of the children, their references in both encodings
+struct W4Tab { int slot[4]; int ref[4]; };                       // one four-child record: bounds slot (-1: absent) and reference per child
+struct LeafTab { int slot; uint32_t at; };                       // one leaf box: bounds slot -> index in leafBox
+
+// rt_gather_triangles (rt_host.cpp): glm's mat4 * vec4 order per vertex, then e1 = b - a, e2 = c - a
+__global__ void k_mesh_gather(const float *__restrict__ pos, const uint32_t *__restrict__ idx, int nTris, Mat16 M, float *__restrict__ t9) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nTris) return;
+    float v[3][3];
+    for (int c = 0; c < 3; ++c) {
+        const float *p = pos + (size_t)idx[(size_t)i * 3 + c] * 3;
+        const float x = p[0], y = p[1], z = p[2];
+        for (int k = 0; k < 3; ++k) v[c][k] = (M.m[k] * x + M.m[4 + k] * y) + (M.m[8 + k] * z + M.m[12 + k] * 1.0f);
+    }
+    float *o = t9 + (size_t)i * 9;
+    for (int j = 0; j < 3; ++j) { o[j] = v[0][j]; o[3 + j] = v[1][j] - v[0][j]; o[6 + j] = v[2][j] - v[0][j]; }
+}
+
+// identity of min over sortable uints = 0xffffffff, of max = 0: [min, min, min, max, max, max] per node; the status word of the quantiser cleared
+__global__ void k_mesh_init(uint32_t *__restrict__ bounds, int nWords, uint32_t *__restrict__ status) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *status = 0u;
+    if (i < nWords) bounds[i] = (i % 6) < 3 ? 0xffffffffu : 0u;
+}
+
+__device__ __forceinline__ float bnd(const uint32_t *__restrict__ bounds, int slot, int c) { return sortable2f(bounds[(size_t)slot * 6 + c]); }
+
+__global__ void k_mesh_root(const uint32_t *__restrict__ bounds, float *__restrict__ rootBox) {
+    if (threadIdx.x < 6) rootBox[threadIdx.x] = sortable2f(bounds[threadIdx.x]);
+}
+
+// 80-byte triangle-pair records (rt_upload_bvh): [v0 e1 e2][v0 e1 e2][index of the first][-]; a record with one triangle repeats the index in its tenth float
+__global__ void k_mesh_pairs(const float4 *__restrict__ tris, const uint32_t *__restrict__ tab, int nPairs, float4 *__restrict__ pairs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nPairs) return;
+    const uint32_t e = tab[r], orig = e & 0x7fffffffu;
+    const bool single = (e >> 31) != 0u;
+    const float fo = __uint_as_float(orig);
+    const float4 a0 = tris[(size_t)orig * 3], a1 = tris[(size_t)orig * 3 + 1], a2 = tris[(size_t)orig * 3 + 2];
+    float4 *o = pairs + (size_t)r * 5;
+    o[0] = make_float4(a0.x, a0.y, a0.z, a1.x);
+    o[1] = make_float4(a1.y, a1.z, a2.x, a2.y);
+    if (single) {
+        o[2] = make_float4(a2.z, fo, 0.0f, 0.0f);
+        o[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        o[4] = make_float4(0.0f, 0.0f, fo, 0.0f);
+    } else {
+        const float4 b0 = tris[(size_t)orig * 3 + 3], b1 = tris[(size_t)orig * 3 + 4], b2 = tris[(size_t)orig * 3 + 5];
+        o[2] = make_float4(a2.z, b0.x, b0.y, b0.z);
+        o[3] = make_float4(b1.x, b1.y, b1.z, b2.x);
+        o[4] = make_float4(b2.y, b2.z, fo, 0.0f);
+    }
+}
+
+// 64-byte two-child records in both reference encodings: [L.min, ref L][L.max, ref R][R.min, 0][R.max, 0]
+__global__ void k_mesh_nodes2(const uint32_t *__restrict__ bounds, const Wn2Tab *__restrict__ tab, int nInner, float4 *__restrict__ wn, float4 *__restrict__ wnW) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nInner) return;
+    const Wn2Tab t = tab[k];
+    const float lx = bnd(bounds, t.slotL, 0), ly = bnd(bounds, t.slotL, 1), lz = bnd(bounds, t.slotL, 2);
+    const float Lx = bnd(bounds, t.slotL, 3), Ly = bnd(bounds, t.slotL, 4), Lz = bnd(bounds, t.slotL, 5);
+    const float4 q2 = make_float4(bnd(bounds, t.slotR, 0), bnd(bounds, t.slotR, 1), bnd(bounds, t.slotR, 2), 0.0f);
+    const float4 q3 = make_float4(bnd(bounds, t.slotR, 3), bnd(bounds, t.slotR, 4), bnd(bounds, t.slotR, 5), 0.0f);
+    float4 *o = wn + (size_t)k * 4, *w = wnW + (size_t)k * 4;
+    o[0] = make_float4(lx, ly, lz, __int_as_float(t.refL)); o[1] = make_float4(Lx, Ly, Lz, __int_as_float(t.refR)); o[2] = q2; o[3] = q3;
+    w[0] = make_float4(lx, ly, lz, __int_as_float(t.refLW)); w[1] = make_float4(Lx, Ly, Lz, __int_as_float(t.refRW)); w[2] = q2; w[3] = q3;
+}
+
+// 128-byte four-child any-hit records, component-wise with NaN boxes for absent children, and (q4 != null) the same node quantised exactly as
+// rt_upload_bvh quantises it: the same double-precision start values and the same fmaf(q, 2^e, origin) correction loops.  A node that cannot be
+// quantised sets *status; the host then walks the exact records, as after an upload.
+__global__ void k_mesh_nodes4(const uint32_t *__restrict__ bounds, const W4Tab *__restrict__ tab, int n4, float4 *__restrict__ w4, uint4 *__restrict__ q4,
+                              uint32_t *__restrict__ status) {
+    const int nn = blockIdx.x * blockDim.x + threadIdx.x;
+    if (nn >= n4) return;
+    const W4Tab t = tab[nn];
+    const float qnan = __uint_as_float(0x7fc00000u);
+    float o[24];
+    for (int i = 0; i < 4; ++i)
+        for (int c = 0; c < 6; ++c) o[4 * c + i] = t.slot[i] >= 0 ? bnd(bounds, t.slot[i], c) : qnan;
+    float4 *w = w4 + (size_t)nn * 8;
+    for (int c = 0; c < 6; ++c) w[c] = make_float4(o[4 * c], o[4 * c + 1], o[4 * c + 2], o[4 * c + 3]);
+    w[6] = make_float4(__int_as_float(t.ref[0]), __int_as_float(t.ref[1]), __int_as_float(t.ref[2]), __int_as_float(t.ref[3]));
+    w[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!q4) return;
+    uint32_t q[16];
+    for (int k = 0; k < 16; ++k) q[k] = 0u;
+    float org[3], scale[3];
+    uint32_t exps = 0;
+    bool okQ = true;
+    for (int a = 0; a < 3; ++a) {
+        float lo = INFINITY, hi = -INFINITY;
+        for (int i = 0; i < 4; ++i)
+            if (t.ref[i] != RT_NO_CHILD) { const float l = o[4 * a + i], h = o[12 + 4 * a + i]; lo = l < lo ? l : lo; hi = hi < h ? h : hi; }   // std::min / std::max
+        if (!(lo <= hi)) { lo = hi = 0.0f; }
+        int eb = 1;
+        const double ext = ((double)hi - (double)lo) / 255.0;
+        if (ext > 0.0) { const int e2 = (int)((__double_as_longlong(ext) >> 52) & 0x7ff) - 1022; eb = e2 - 1 + 127 > 1 ? e2 - 1 + 127 : 1; }   // frexp's exponent of a normal double
+        while (eb <= 254 && __builtin_fmaf(255.0f, __uint_as_float((uint32_t)eb << 23), lo) < hi) ++eb;
+        if (eb > 254) { okQ = false; break; }
+        org[a] = lo; scale[a] = __uint_as_float((uint32_t)eb << 23);
+        exps |= (uint32_t)eb << (8 * a);
+        q[a] = __float_as_uint(lo);
+    }
+    if (okQ) {
+        q[3] = exps;
+        for (int i = 0; i < 4; ++i) {
+            q[12 + i] = (uint32_t)t.ref[i];
+            if (t.ref[i] == RT_NO_CHILD) continue;
+            for (int a = 0; a < 3; ++a) {
+                const float lo = o[4 * a + i], hi = o[12 + 4 * a + i];
+                int ql = (int)floor(((double)lo - (double)org[a]) / (double)scale[a]);
+                ql = ql < 255 ? ql : 255; ql = ql > 0 ? ql : 0;
+                while (ql > 0 && __builtin_fmaf((float)ql, scale[a], org[a]) > lo) --ql;
+                int qh = (int)ceil(((double)hi - (double)org[a]) / (double)scale[a]);
+                qh = qh < 255 ? qh : 255; qh = qh > 0 ? qh : 0;
+                while (qh < 255 && __builtin_fmaf((float)qh, scale[a], org[a]) < hi) ++qh;
+                if (__builtin_fmaf((float)ql, scale[a], org[a]) > lo || __builtin_fmaf((float)qh, scale[a], org[a]) < hi) okQ = false;
+                const int wl = 4 + a, wh = a == 0 ? 7 : 7 + a;      // words: lo.x lo.y lo.z hi.x | hi.y hi.z
+                q[wl] |= (uint32_t)ql << (8 * i);
+                q[wh] |= (uint32_t)qh << (8 * i);
+            }
+        }
+    }
+    if (!okQ) atomicOr(status, 1u);
+    uint4 *d = q4 + (size_t)nn * 4;
+    for (int k = 0; k < 4; ++k) d[k] = make_uint4(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]);
+}
+
+// the leaves' exact boxes for the quantised walk: [lo.xyz hi.x][hi.yz 0 0]
+__global__ void k_mesh_leafbox(const uint32_t *__restrict__ bounds, const LeafTab *__restrict__ tab, int nLeaves, float4 *__restrict__ leafBox) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nLeaves) return;
+    const LeafTab t = tab[j];
+    float4 *o = leafBox + (size_t)t.at * 2;
+    o[0] = make_float4(bnd(bounds, t.slot, 0), bnd(bounds, t.slot, 1), bnd(bounds, t.slot, 2), bnd(bounds, t.slot, 3));
+    o[1] = make_float4(bnd(bounds, t.slot, 4), bnd(bounds, t.slot, 5), 0.0f, 0.0f);
+}
+
+inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }
+
+}  // namespace
+
+namespace rtl {
+
+int bvh_layout(int nTris, BvhLayout &out) {
+    out = BvhLayout{};
+    if (nTris <= 0) return RT_ERR_INVALID;
+    if (nTris >= (1 << 28)) return RT_ERR_UNSUPPORTED;
+    // a subtree's shape depends on its triangle count alone, and a level holds at most two distinct counts
+    struct Sub { long long nodes, inner, pairs, leaves; int depth, minRec; };
+    struct Wide { long long n4; int stack; };
+    std::map<int, Sub> sub;
+    std::map<int, Wide> wide;
+    auto subOf = [&](auto &&self, int s) -> Sub {
+        auto it = sub.find(s);
+        if (it != sub.end()) return it->second;
+        Sub r;
+        if (s <= 8) r = {1, 0, (s + 1) / 2, 1, 1, (s + 1) / 2};
+        else {
+            const Sub a = self(self, s / 2), b = self(self, s - s / 2);
+            r = {1 + a.nodes + b.nodes, 1 + a.inner + b.inner, a.pairs + b.pairs, a.leaves + b.leaves, 1 + std::max(a.depth, b.depth), std::min(a.minRec, b.minRec)};
+        }
+        sub[s] = r;
+        return r;
+    };
+    // four-child record of an inner node of s triangles: it absorbs its inner children (rt_upload_bvh); stack need = children - 1 + the deepest inner child's
+    auto wideOf = [&](auto &&self, int s) -> Wide {
+        auto it = wide.find(s);
+        if (it != wide.end()) return it->second;
+        int kids[4], nk = 0;
+        for (int ch : {s / 2, s - s / 2}) {
+            if (ch <= 8) kids[nk++] = ch;
+            else { kids[nk++] = ch / 2; kids[nk++] = ch - ch / 2; }
+        }
+        Wide r{1, 0};
+        int deepest = 0;
+        for (int i = 0; i < nk; ++i)
+            if (kids[i] > 8) { const Wide k = self(self, kids[i]); r.n4 += k.n4; deepest = std::max(deepest, k.stack); }
+        r.stack = std::max(nk - 1, 0) + deepest;
+        wide[s] = r;
+        return r;
+    };
+    const Sub root = subOf(subOf, nTris);
+    if (root.depth > 32) return RT_ERR_UNSUPPORTED;
+    out.nTris = nTris; out.nNodes = (int)root.nodes; out.nInner = (int)root.inner; out.treeDepth = root.depth;
+    out.nPairs = (size_t)root.pairs; out.nLeaves = (size_t)root.leaves; out.minLeafRecords = root.minRec;
+    if (out.nPairs + 8 >= ((size_t)1 << 28)) return RT_ERR_UNSUPPORTED;
+    const int leafRef = -(((0 << 3) | (nTris - 1)) + 1);   // the root as a leaf: first = 0 in both encodings
+    if (nTris <= 8) { out.nWide4 = 1; out.anyStack = 0; out.rootRef = out.rootRefW = out.rootRef4 = leafRef; }
+    else { const Wide w = wideOf(wideOf, nTris); out.nWide4 = (size_t)w.n4; out.anyStack = std::max(w.stack, 1); out.rootRef = out.rootRefW = out.rootRef4 = 0; }
+    return RT_OK;
+}
+
+struct Mesh {
+    BvhLayout lay;
+    MeshScene sc;
+    int nVerts = 0, nLevels = 0;
+    bool quantised = false;
+    std::vector<int> levelOff, levelSegs;   // per level: first bounds slot / segment, number of nodes
+    std::vector<char> levelInner;           // per level: some node of it is split
+    // geometry and build scratch
+    float *dPos = nullptr, *dT9 = nullptr, *dMn = nullptr, *dMx = nullptr, *dCen = nullptr;
+    uint32_t *dIdx = nullptr, *dBounds = nullptr, *dStatus = nullptr;
+    int *dPerm[2] = {nullptr, nullptr}, *dSegB = nullptr, *dSegE = nullptr, *dSegI = nullptr, *dOut = nullptr;
+    unsigned long long *dKeys[2] = {nullptr, nullptr};
+    void *dTemp = nullptr;
+    size_t tempBytes = 0;
+    // index tables
+    uint32_t *dPairTab = nullptr;
+    Wn2Tab *dWn2Tab = nullptr;
+    W4Tab *dW4Tab = nullptr;
+    LeafTab *dLeafTab = nullptr;
+    uint32_t *hStatus = nullptr;   // pinned
+    std::vector<void *> owned;
+    uint64_t allocations = 0;
+    size_t scratchBytes = 0, sceneBytes = 0;
+};
+
+namespace {
+template <class T> hipError_t dev_alloc(Mesh *m, T **p, size_t bytes, bool scene, bool zero) {
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) return e;
+    m->owned.push_back(q);
+    ++m->allocations;
+    (scene ? m->sceneBytes : m->scratchBytes) += bytes;
+    *p = reinterpret_cast<T *>(q);
+    return zero ? hipMemset(q, 0, std::max<size_t>(bytes, 16)) : hipSuccess;
+}
+template <class T> hipError_t dev_upload(Mesh *m, T **p, const std::vector<T> &v) {
+    hipError_t e = dev_alloc(m, p, v.size() * sizeof(T), false, false);
+    if (e != hipSuccess || v.empty()) return e;
+    return hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+}  // namespace
+
+#define MESH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); mesh_destroy(m); return RT_ERR_HIP; } } while (0)
+
+int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, bool quantised, Mesh **out, const char **err) {
+    *out = nullptr;
+    const int n = nIdx / 3;
+    Mesh *m = new Mesh();
+    m->nVerts = nVerts; m->quantised = quantised;
+    int rc = bvh_layout(n, m->lay);
+    if (rc != RT_OK) { delete m; return rc; }
+    // ---- the topology, node by node: rt_upload_bvh's derivations on the skeleton
+    std::vector<SkNode> sk;
+    skeleton(n, sk);
+    const int nNodes = (int)sk.size();
+    auto countOf = [&](int i) { return sk[(size_t)i].left < 0 ? sk[(size_t)i].end - sk[(size_t)i].begin : 0; };
+    int maxDepth = 0;
+    for (const SkNode &nd : sk) maxDepth = std::max(maxDepth, nd.depth);
+    m->nLevels = maxDepth + 1;
+    std::vector<std::vector<int>> byDepth((size_t)maxDepth + 1);
+    for (int i = 0; i < nNodes; ++i) byDepth[(size_t)sk[(size_t)i].depth].push_back(i);
+    for (auto &v : byDepth) std::sort(v.begin(), v.end(), [&](int a, int b) { return sk[(size_t)a].begin < sk[(size_t)b].begin; });
+    std::vector<int> slotOf((size_t)nNodes), segB, segE, segI;
+    for (int d = 0; d <= maxDepth; ++d) {
+        m->levelOff.push_back((int)segB.size());
+        m->levelSegs.push_back((int)byDepth[(size_t)d].size());
+        bool anyInner = false;
+        for (int id : byDepth[(size_t)d]) {
+            const SkNode &nd = sk[(size_t)id];
+            slotOf[(size_t)id] = (int)segB.size();
+            segB.push_back(nd.begin); segE.push_back(nd.end); segI.push_back(nd.left >= 0);
+            anyInner = anyInner || nd.left >= 0;
+        }
+        m->levelInner.push_back(anyInner ? 1 : 0);
+    }
+    std::vector<int> outOfPos((size_t)n);
+    for (const SkNode &nd : sk)
+        if (nd.left < 0) for (int k = 0; k < nd.end - nd.begin; ++k) outOfPos[(size_t)(nd.begin + k)] = nd.firstOut + k;
+    std::vector<int> innerIdx((size_t)nNodes, -1), pairRefOf((size_t)nNodes, 0);
+    int nInner = 0;
+    std::vector<uint32_t> pairTab;
+    int rmin = 8;
+    size_t nLeaves = 0;
+    for (int i = 0; i < nNodes; ++i) {
+        const int cnt = countOf(i);
+        if (cnt <= 0) { innerIdx[(size_t)i] = nInner++; continue; }
+        ++nLeaves;
+        rmin = std::min(rmin, (cnt + 1) / 2);
+        const size_t rec = pairTab.size();
+        pairRefOf[(size_t)i] = -((int)((rec << 3) | (size_t)(cnt - 1)) + 1);
+        for (int t = 0; t < cnt; t += 2) pairTab.push_back((uint32_t)(sk[(size_t)i].firstOut + t) | (t + 1 >= cnt ? 0x80000000u : 0u));
+    }
+    auto refOf = [&](int node) { const int cnt = countOf(node); return cnt > 0 ? -(((sk[(size_t)node].firstOut << 3) | (cnt - 1)) + 1) : innerIdx[(size_t)node]; };
+    auto refOfW = [&](int node) { return countOf(node) > 0 ? pairRefOf[(size_t)node] : innerIdx[(size_t)node]; };
+    std::vector<Wn2Tab> wn2((size_t)nInner);
+    for (int i = 0; i < nNodes; ++i) {
+        if (innerIdx[(size_t)i] < 0) continue;
+        const int L = sk[(size_t)i].left, R = sk[(size_t)i].right;
+        wn2[(size_t)innerIdx[(size_t)i]] = {slotOf[(size_t)L], slotOf[(size_t)R], refOf(L), refOf(R), refOfW(L), refOfW(R)};
+    }
+    std::vector<W4Tab> w4;
+    int anyStack = 0;
+    if (countOf(0) <= 0) {
+        struct Job { int bin; size_t at; };
+        std::vector<Job> jobs{{0, 0}};
+        w4.push_back(W4Tab{});
+        while (!jobs.empty()) {
+            const Job jb = jobs.back();
+            jobs.pop_back();
+            int kids[4], nk = 0;
+            for (int ch : {sk[(size_t)jb.bin].left, sk[(size_t)jb.bin].right}) {
+                if (countOf(ch) > 0) kids[nk++] = ch;
+                else { kids[nk++] = sk[(size_t)ch].left; kids[nk++] = sk[(size_t)ch].right; }
+            }
+            for (int i = 0; i < 4; ++i) {
+                int ref = RT_NO_CHILD, slot = -1;
+                if (i < nk) {
+                    slot = slotOf[(size_t)kids[i]];
+                    if (countOf(kids[i]) > 0) ref = refOfW(kids[i]);
+                    else { ref = (int)w4.size(); w4.push_back(W4Tab{}); jobs.push_back({kids[i], (size_t)ref}); }
+                }
+                w4[jb.at].slot[i] = slot; w4[jb.at].ref[i] = ref;
+            }
+        }
+        // exact stack need of the any-hit walk (rt_upload_bvh): S(node) = children - 1 + max over its inner children
+        const size_t n4 = w4.size();
+        std::vector<int> need(n4, -1);
+        std::vector<std::pair<size_t, int>> st{{0, 0}};
+        while (!st.empty()) {
+            auto &[nn, ci] = st.back();
+            if (ci < 4) {
+                const int ref = w4[nn].ref[ci];
+                ++ci;
+                if (ref >= 0 && ref != RT_NO_CHILD && (size_t)ref < n4 && need[(size_t)ref] < 0) st.push_back({(size_t)ref, 0});
+                continue;
+            }
+            int nc = 0, deepest = 0;
+            for (int i = 0; i < 4; ++i) {
+                const int ref = w4[nn].ref[i];
+                if (ref == RT_NO_CHILD) continue;
+                ++nc;
+                if (ref >= 0 && (size_t)ref < n4) deepest = std::max(deepest, need[(size_t)ref]);
+            }
+            need[nn] = std::max(nc - 1, 0) + deepest;
+            st.pop_back();
+        }
+        anyStack = std::max(need[0], 1);
+    }
+    const BvhLayout &L = m->lay;
+    if (nNodes != L.nNodes || nInner != L.nInner || maxDepth + 1 != L.treeDepth || pairTab.size() != L.nPairs || std::max<size_t>(w4.size(), 1) != L.nWide4 ||
+        anyStack != L.anyStack || nLeaves != L.nLeaves || rmin != L.minLeafRecords || refOf(0) != L.rootRef || refOfW(0) != L.rootRefW) {
+        if (err) *err = "internal: the layout of the count and the layout of the skeleton disagree";
+        delete m;
+        return RT_ERR_STATE;
+    }
+    std::vector<LeafTab> leafTab;
+    size_t leafBoxFloats = 0;
+    if (quantised) {
+        if (getenv("RT_QNODES_SPARSE_BOXES")) rmin = 1;
+        m->sc.leafBoxMagic = rmin <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + (uint64_t)rmin - 1) / (uint64_t)rmin);
+        leafBoxFloats = ((L.nPairs + 8) / (size_t)std::max(rmin, 1) + 1) * 8;
+        for (int i = 0; i < nNodes; ++i) {
+            if (countOf(i) <= 0) continue;
+            const size_t first = (size_t)(-pairRefOf[(size_t)i] - 1) >> 3;
+            const size_t at = m->sc.leafBoxMagic ? (size_t)(((uint64_t)first * m->sc.leafBoxMagic) >> 32) : first;
+            if (at * 8 + 8 > leafBoxFloats) { if (err) *err = "internal: leaf-box index out of range"; delete m; return RT_ERR_STATE; }
+            leafTab.push_back({slotOf[(size_t)i], (uint32_t)at});
+        }
+        m->sc.leafBoxBytes = leafBoxFloats * 4;
+    }
+    // ---- device memory: geometry, tables, build scratch, scene arrays (padding zeroed here, once)
+    const size_t N = (size_t)n;
+    MESH_TRY(dev_alloc(m, &m->dPos, (size_t)nVerts * 12, false, false));
+    MESH_TRY(hipMemcpy(m->dPos, positions, (size_t)nVerts * 12, hipMemcpyHostToDevice));
+    MESH_TRY(dev_alloc(m, &m->dIdx, N * 12, false, false));
+    MESH_TRY(hipMemcpy(m->dIdx, indices, N * 12, hipMemcpyHostToDevice));
+    MESH_TRY(dev_upload(m, &m->dSegB, segB)); MESH_TRY(dev_upload(m, &m->dSegE, segE)); MESH_TRY(dev_upload(m, &m->dSegI, segI));
+    MESH_TRY(dev_upload(m, &m->dOut, outOfPos));
+    MESH_TRY(dev_upload(m, &m->dPairTab, pairTab)); MESH_TRY(dev_upload(m, &m->dWn2Tab, wn2)); MESH_TRY(dev_upload(m, &m->dW4Tab, w4));
+    if (quantised) MESH_TRY(dev_upload(m, &m->dLeafTab, leafTab));
+    MESH_TRY(dev_alloc(m, &m->dT9, N * 36, false, false));
+    MESH_TRY(dev_alloc(m, &m->dMn, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dMx, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dCen, N * 12, false, false));
+    MESH_TRY(dev_alloc(m, &m->dPerm[0], N * 4, false, false)); MESH_TRY(dev_alloc(m, &m->dPerm[1], N * 4, false, false));
+    MESH_TRY(dev_alloc(m, &m->dKeys[0], N * 8, false, false)); MESH_TRY(dev_alloc(m, &m->dKeys[1], N * 8, false, false));
+    MESH_TRY(dev_alloc(m, &m->dBounds, (size_t)nNodes * 24, false, false));
+    MESH_TRY(dev_alloc(m, &m->dStatus, 16, false, true));
+    {
+        rocprim::double_buffer<unsigned long long> kb(m->dKeys[0], m->dKeys[1]);
+        rocprim::double_buffer<int> vb(m->dPerm[0], m->dPerm[1]);
+        MESH_TRY(rocprim::radix_sort_pairs(nullptr, m->tempBytes, kb, vb, N, 0, 64, (hipStream_t) nullptr));
+        MESH_TRY(dev_alloc(m, reinterpret_cast<char **>(&m->dTemp), std::max<size_t>(m->tempBytes, 16), false, false));
+    }
+    MESH_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->hStatus), 16, hipHostMallocDefault));
+    ++m->allocations;
+    *m->hStatus = 0u;
+    MESH_TRY(dev_alloc(m, &m->sc.wnodes, (size_t)std::max(nInner, 1) * 64, true, true));
+    MESH_TRY(dev_alloc(m, &m->sc.wnodesW, (size_t)std::max(nInner, 1) * 64, true, true));
+    MESH_TRY(dev_alloc(m, &m->sc.w4, L.nWide4 * 128, true, true));
+    MESH_TRY(dev_alloc(m, &m->sc.pairs, (L.nPairs + 8) * 80, true, true));
+    MESH_TRY(dev_alloc(m, &m->sc.tris, (N + 8) * 48, true, true));
+    MESH_TRY(dev_alloc(m, &m->sc.rootBox, 32, true, true));
+    if (quantised) {
+        MESH_TRY(dev_alloc(m, &m->sc.q4, L.nWide4 * 64, true, true));
+        MESH_TRY(dev_alloc(m, &m->sc.leafBox, leafBoxFloats * 4, true, true));
+    }
+    MESH_TRY(hipDeviceSynchronize());
+    *out = m;
+    return RT_OK;
+}
+
+void mesh_destroy(Mesh *m) {
+    if (!m) return;
+    for (void *p : m->owned) (void)hipFree(p);
+    if (m->hStatus) (void)hipHostFree(m->hStatus);
+    delete m;
+}
+
+const BvhLayout &mesh_layout(const Mesh *m) { return m->lay; }
+const MeshScene &mesh_scene(const Mesh *m) { return m->sc; }
+float *mesh_positions(Mesh *m) { return m->dPos; }
+int mesh_verts(const Mesh *m) { return m->nVerts; }
+uint64_t mesh_allocations(const Mesh *m) { return m->allocations; }
+size_t mesh_scratch_bytes(const Mesh *m) { return m->scratchBytes; }
+size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }
+
+#define REB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); return RT_ERR_HIP; } } while (0)
+
+int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
+    const BvhLayout &L = m->lay;
+    const int n = L.nTris;
+    const unsigned gN = blocks_for((size_t)n);
+    Mat16 M;
+    std::memcpy(M.m, M16, sizeof M.m);
+    hipLaunchKernelGGL(k_mesh_gather, dim3(gN), dim3(256), 0, st, m->dPos, m->dIdx, n, M, m->dT9);
+    hipLaunchKernelGGL(k_mesh_init, dim3(blocks_for((size_t)L.nNodes * 6)), dim3(256), 0, st, m->dBounds, L.nNodes * 6, m->dStatus);
+    hipLaunchKernelGGL(k_tri_prep, dim3(gN), dim3(256), 0, st, m->dT9, n, m->dMn, m->dMx, m->dCen);
+    hipLaunchKernelGGL(k_iota, dim3(gN), dim3(256), 0, st, m->dPerm[0], n);
+    int cur = 0;
+    for (int d = 0; d < m->nLevels; ++d) {   // the level loop of build_bvh_gpu (rt_bvh_gpu.hip) with its segment tables and bounds resident
+        const int off = m->levelOff[(size_t)d], nSeg = m->levelSegs[(size_t)d];
+        uint32_t *bounds = m->dBounds + (size_t)off * 6;
+        hipLaunchKernelGGL(k_level_bounds, dim3(gN), dim3(256), 0, st, m->dPerm[cur], n, m->dMn, m->dMx, m->dSegB + off, m->dSegE + off, nSeg, bounds);
+        if (!m->levelInner[(size_t)d]) continue;
+        hipLaunchKernelGGL(k_level_keys, dim3(gN), dim3(256), 0, st, m->dPerm[cur], n, m->dCen, m->dSegB + off, m->dSegE + off, m->dSegI + off, nSeg, bounds,
+                           m->dKeys[cur]);
+        rocprim::double_buffer<unsigned long long> kb(m->dKeys[cur], m->dKeys[cur ^ 1]);
+        rocprim::double_buffer<int> vb(m->dPerm[cur], m->dPerm[cur ^ 1]);
+        REB_TRY(rocprim::radix_sort_pairs(m->dTemp, m->tempBytes, kb, vb, (size_t)n, 0, 64, st));
+        cur = (vb.current() == m->dPerm[0]) ? 0 : 1;
+    }
+    hipLaunchKernelGGL(k_emit_tris, dim3(gN), dim3(256), 0, st, m->dT9, m->dPerm[cur], m->dOut, n, reinterpret_cast<float *>(m->sc.tris));
+    hipLaunchKernelGGL(k_mesh_root, dim3(1), dim3(64), 0, st, m->dBounds, m->sc.rootBox);
+    hipLaunchKernelGGL(k_mesh_pairs, dim3(blocks_for(L.nPairs)), dim3(256), 0, st, m->sc.tris, m->dPairTab, (int)L.nPairs, m->sc.pairs);
+    if (L.nInner > 0) {
+        hipLaunchKernelGGL(k_mesh_nodes2, dim3(blocks_for((size_t)L.nInner)), dim3(256), 0, st, m->dBounds, m->dWn2Tab, L.nInner, m->sc.wnodes, m->sc.wnodesW);
+        hipLaunchKernelGGL(k_mesh_nodes4, dim3(blocks_for(L.nWide4)), dim3(256), 0, st, m->dBounds, m->dW4Tab, (int)L.nWide4, m->sc.w4,
+                           reinterpret_cast<uint4 *>(m->sc.q4), m->dStatus);
+        if (m->quantised)
+            hipLaunchKernelGGL(k_mesh_leafbox, dim3(blocks_for(L.nLeaves)), dim3(256), 0, st, m->dBounds, m->dLeafTab, (int)L.nLeaves, m->sc.leafBox);
+    }
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err) {
+    REB_TRY(hipMemcpyAsync(m->hStatus, m->dStatus, 4, hipMemcpyDeviceToHost, st));
+    REB_TRY(hipStreamSynchronize(st));
+    ok = *m->hStatus == 0u;
+    return RT_OK;
+}
+
+}  // namespace rtl

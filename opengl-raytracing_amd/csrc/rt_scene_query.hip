@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k_scene_analytic(const RtUniforms u, DevS
         const uint32_t *src = reinterpret_cast<const uint32_t *>(&u);
         uint32_t *dst = reinterpret_cast<uint32_t *>(&fr->u);
         for (uint32_t k = threadIdx.x; k < sizeof(RtUniforms) / 4; k += blockDim.x) dst[k] = src[k];
-        if (threadIdx.x == 0) fr->sc = sc;
+        if (threadIdx.x == 0) { fr->sc = sc; scene_take_root_box(fr->sc); }
     }
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= r.n) return;

@@ -1897,7 +1897,7 @@ uint32_t launch_trace(hipStream_t st, int cus, int gridPct, int depth, const Dev
 // stream of queries needs no host copy and no synchronisation
 __global__ __launch_bounds__(256) void k_query_prep(DevFrame *fr, DevScene sc, float eps, float inf, uint32_t *head) {
     for (uint32_t i = threadIdx.x; i < kHeadWords; i += blockDim.x) head[i] = 0u;
-    if (threadIdx.x == 0) { fr->sc = sc; fr->u.eps = eps; fr->u.inf = inf; }
+    if (threadIdx.x == 0) { fr->sc = sc; scene_take_root_box(fr->sc); fr->u.eps = eps; fr->u.inf = inf; }
 }
 
 uint32_t launch_packets(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, PacketSrc src, uint32_t *head, unsigned long long *tally,

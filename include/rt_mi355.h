@@ -371,6 +371,15 @@ int rt_debug_builds(RtContext *ctx, uint32_t *out, int reset);
  * launches (one per chunk of a launch set) with / without the probe.  rt_get_traced_rays counts every bounce ray once either way. */
 typedef struct RtBounceProbe { uint64_t probed, retraced, probeLaunches, closestLaunches; } RtBounceProbe;
 int rt_debug_bounce_probe(RtContext *ctx, RtBounceProbe *out, int reset);
+/* The disk-light skip of the wavefront frames' shading stages: a wave whose hits all face away from the whole disk light does not evaluate
+ * the four disk samples, which add exactly zero there.  Counts since the last reset, summed over the frame lanes (synchronises), for the two ray generators:
+ * pairs = (hit, sample) pairs shaded, unlit = pairs the per-hit test proved unlit, skipped = pairs whose wave skipped the loop, waves / wavesSkipped = the
+ * waves they ran in.  The kernels count only from the first call of this entry on (a kernel argument that is null before): call it once, with reset, first. */
+typedef struct RtDiskSkip { uint64_t directPairs, directUnlit, directSkipped, directWaves, directWavesSkipped, giPairs, giUnlit, giSkipped, giWaves, giWavesSkipped; } RtDiskSkip;
+int rt_debug_disk_skip(RtContext *ctx, RtDiskSkip *out, int reset);
+/* Diagnostics: the per-hit test beside the code it stands for.  For n pairs (hp, normal; 3 floats each) flags[i] bit 0 = the test holds, bit 1 = one of the
+ * four disk samples of `seeds` (pixel, frame) seeds had geom != 0; maxDot[i] = the largest dot(N, L) those samples computed.  u supplies uPI. */
+int rt_debug_disk_unlit(RtContext *ctx, const RtUniforms *u, const float *hp, const float *normals, int n, int seeds, uint8_t *flags, float *maxDot);
 
 /* ---- raster preview: renderRaster (src/render/render.cpp:244-295, shaders/basic.vert / basic.frag), the reference's other frame
  * mode.  Flat-coloured meshes, MVP transform, GL_LESS depth test on a D24 buffer, no MSAA, no culling; the rules a GL 4.1 driver

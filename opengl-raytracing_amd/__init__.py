@@ -141,6 +141,11 @@ class RtBounceProbe(_Struct):   # rt_debug_bounce_probe: the bounce probe's coun
     _fields_ = [(n, C.c_uint64) for n in ("probed", "retraced", "probeLaunches", "closestLaunches")]
 
 
+class RtDiskSkip(_Struct):   # rt_debug_disk_skip: the disk-light skip of the shading stages
+    _fields_ = [(n, C.c_uint64) for n in ("directPairs", "directUnlit", "directSkipped", "directWaves", "directWavesSkipped",
+                                             "giPairs", "giUnlit", "giSkipped", "giWaves", "giWavesSkipped")]
+
+
 class RtSceneInfo(_Struct):
     _fields_ = [(n, i32) for n in ("nNodes", "nTris", "nInner", "treeDepth", "nWide4", "nPairs")] + \
                [(n, C.c_uint64) for n in ("bytesNodes2", "bytesNodes4", "bytesPairs", "bytesTris")] + \
@@ -273,6 +278,9 @@ SIGNATURES = {
     "rt_debug_trace": (C.c_int, [C.c_void_p, C.c_int, _FP, _FP, _FP, C.c_float, C.c_float, _FP, C.c_int]),
     "rt_debug_builds": (C.c_int, [C.c_void_p, _U32P, C.c_int]),
     "rt_debug_bounce_probe": (C.c_int, [C.c_void_p, C.POINTER(RtBounceProbe), C.c_int]),
+    "rt_debug_disk_skip": (C.c_int, [C.c_void_p, C.POINTER(RtDiskSkip), C.c_int]),
+    "rt_debug_disk_unlit": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     "rt_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
@@ -1144,6 +1152,27 @@ class Renderer:
         b = RtBounceProbe()
         self._check(lib().rt_debug_bounce_probe(self._h, C.byref(b), int(reset)))
         return b
+
+    def disk_skip(self, reset=False) -> RtDiskSkip:
+        """Counts of the disk-light skip since the last reset, for k_gen_direct and k_gen_gi: (hit, sample) pairs shaded, pairs proved unlit, pairs whose
+        wave skipped the disk loop, waves, waves that skipped (rt_debug_disk_skip).  The kernels count from the first call on: call once with reset first."""
+        b = RtDiskSkip()
+        self._check(lib().rt_debug_disk_skip(self._h, C.byref(b), int(reset)))
+        return b
+
+    def debug_disk_unlit(self, u, hp, normals, seeds=64):
+        """rt_debug_disk_unlit: (unlit, lit, maxDot) arrays for n (hp, normal) pairs -- the per-hit test, whether any of the four disk samples of `seeds`
+        seeds had geom != 0, and the largest dot(N, L) they computed."""
+        hp = np.ascontiguousarray(hp, dtype=np.float32).reshape(-1, 3)
+        nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        n = hp.shape[0]
+        if nr.shape[0] != n:
+            raise ValueError("hp and normals differ in length")
+        flags = np.zeros(n, dtype=np.uint8)
+        md = np.zeros(n, dtype=np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(lib().rt_debug_disk_unlit(self._h, C.byref(u), fp(hp), fp(nr), n, int(seeds), flags.ctypes.data_as(C.POINTER(C.c_uint8)), fp(md)))
+        return (flags & 1) != 0, (flags & 2) != 0, md
 
     def debug_build_bits(self, reset=False) -> int:
         """rt_debug_builds as the raw RT_BUILD_* word (closest-hit half, any-hit half << RT_BUILD_ANY_SHIFT)."""

@@ -210,6 +210,32 @@ __global__ void k_debug_eval(int op, const float *a, const float *b, const float
     out[i] = r;
 }
 
+// rt_debug_disk_unlit: diskUnlit(hp, N) beside what it stands for -- diskSample, the production code, for the four samples of `seeds` (pixel, frame) seeds.
+// flags bit 0: diskUnlit; bit 1: some sample had geom != 0 (NaN counts).  maxDot: the largest dot(N, s.L) as diskSample / shadeLambertPhong compute it.
+__global__ __launch_bounds__(256) void k_debug_disk_unlit(RtUniforms u, const float *hp, const float *nrm, int n, int seeds, uint8_t *flags, float *maxDot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 p = ld3(hp + (size_t)i * 3), N = ld3(nrm + (size_t)i * 3);
+    Frag F;
+    F.u = &u; F.sc = nullptr;
+    V3 lt, lb;
+    lightFrame(lt, lb);
+    bool lit = false;
+    float md = -__builtin_inff();
+    for (int k = 0; k < seeds; ++k) {
+        F.fcx = (float)((k * 73 + i) % 1920) + 0.5f; F.fcy = (float)((k * 151 + i * 7) % 1080) + 0.5f;
+        F.frameIndex = k;
+        const V2 rot = cpOffset(F.fcx, F.fcy, F.frameIndex);
+        for (int j = 0; j < 4; ++j) {
+            const DiskSample s = diskSample(F, p, N, k * 4 + (i & 3), j, rot, lt, lb);
+            lit = lit || !(s.geom == 0.0f);
+            md = fmaxr(md, dot(N, s.L));
+        }
+    }
+    flags[i] = (uint8_t)((diskUnlit(p, N) ? 1 : 0) | (lit ? 2 : 0));
+    maxDot[i] = md;
+}
+
 // A scene a device rebuild installed: the frame descriptor the host copied carries no root box; take it from the device.
 __global__ void k_frame_root_box(DevFrame *fr) {
     if (threadIdx.x == 0) scene_take_root_box(fr->sc);
@@ -2088,6 +2114,39 @@ int rt_debug_bounce_probe(RtContext *c, RtBounceProbe *out, int reset) {
         for (int k = 0; k < 4; ++k) v[k] += t[k];
     }
     out->probed = v[0]; out->retraced = v[1]; out->probeLaunches = v[2]; out->closestLaunches = v[3];
+    return RT_OK;
+}
+
+int rt_debug_disk_skip(RtContext *c, RtDiskSkip *out, int reset) {
+    if (!c || !out) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    unsigned long long v[10] = {};
+    for (int i = 0; i < c->nLanes; ++i) {
+        unsigned long long t[10];
+        int rc = rt_wave_disk_skip(c->wave[i], c->lanes[i], t, reset != 0);
+        if (rc != RT_OK) return fail(c, rc, "rt_debug_disk_skip: %s", rt_wave_error(c->wave[i]));
+        for (int k = 0; k < 10; ++k) v[k] += t[k];
+    }
+    out->directPairs = v[0]; out->directUnlit = v[1]; out->directSkipped = v[2]; out->directWaves = v[3]; out->directWavesSkipped = v[4];
+    out->giPairs = v[5]; out->giUnlit = v[6]; out->giSkipped = v[7]; out->giWaves = v[8]; out->giWavesSkipped = v[9];
+    return RT_OK;
+}
+
+int rt_debug_disk_unlit(RtContext *c, const RtUniforms *u, const float *hp, const float *normals, int n, int seeds, uint8_t *flags, float *maxDot) {
+    if (!c || !u || !hp || !normals || !flags || !maxDot || n <= 0 || seeds <= 0) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    float *dP = nullptr, *dN = nullptr, *dM = nullptr;
+    uint8_t *dF = nullptr;
+    auto freeAll = [&]() { for (void *p : {(void *)dP, (void *)dN, (void *)dM, (void *)dF}) if (p) (void)hipFree(p); };
+    const size_t b3 = (size_t)n * 12;
+    bool ok = hipMalloc(&dP, b3) == hipSuccess && hipMalloc(&dN, b3) == hipSuccess && hipMalloc(&dM, (size_t)n * 4) == hipSuccess && hipMalloc(&dF, (size_t)n) == hipSuccess &&
+              hipMemcpy(dP, hp, b3, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dN, normals, b3, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { freeAll(); return fail(c, RT_ERR_HIP, "rt_debug_disk_unlit: allocation / upload failed"); }
+    hipLaunchKernelGGL(k_debug_disk_unlit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *u, dP, dN, n, seeds, dF, dM);
+    ok = hipGetLastError() == hipSuccess && sync_all(c) == hipSuccess && hipMemcpy(flags, dF, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(maxDot, dM, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    freeAll();
+    if (!ok) return fail(c, RT_ERR_HIP, "rt_debug_disk_unlit: launch failed");
     return RT_OK;
 }
 

@@ -414,9 +414,10 @@ RT_DEV void lightFrame(V3 &t, V3 &b) {   // :355-357
 // One disk-light sample i of directLight / directLightBVH (:363-385 / :422-443) up to the visibility
 // ray: returns the light point xL and the shadow ray occludedToward(p, xL) would cast (:49-54).
 struct DiskSample { V3 xL; V3 L; float geom; V3 ro; V3 rd; float tMax; };
+RT_DEV V3 kDiskLightCenter() { return mk3(0.0f, 5.0f, -3.0f); }   // :29
 RT_DEV DiskSample diskSample(const Frag &F, V3 hp, V3 N, int frame, int i, V2 rot, V3 lt, V3 lb) {
     const float kLightRadius = 1.2f;
-    const V3 kLightCenter = mk3(0.0f, 5.0f, -3.0f);
+    const V3 kLightCenter = kDiskLightCenter();
     float fi = (float)i, fk = (float)(31 * i + 7);
     V2 uu = mk2(randr(F.fcx + fi, F.fcy + fi, frame), randr(F.fcy + fk, F.fcx + fk, frame));
     uu = mk2(fractr(uu.x + rot.x), fractr(uu.y + rot.y));
@@ -438,6 +439,20 @@ RT_DEV DiskSample diskSample(const Frag &F, V3 hp, V3 N, int frame, int i, V2 ro
     return s;
 }
 
+// "The surface at hp faces away from the whole disk light": true only when the dot(N, s.L) that diskSample and shadeLambertPhong
+// COMPUTE is <= 0 for every sample diskSample can draw, so that ndl == 0, geom == +-0 and the sample adds exactly mk3(0.0f)
+// (proof: DESIGN.md 4.2).  With c the disk's centre and every light point within kR of it,
+//     dot(N, c - hp) + kR |N|  <  -kTau |N| (|c - hp| + kR)
+// bounds the cosine between N and any xL - hp below -kTau; kR = 1.21 covers the radius 1.2 and the rounding of xL (< 3e-5),
+// kTau = 1e-4 the rounding of normalize, of the dot product and of this test (< 2e-6 together).  N is a normalised vector in
+// every caller; anything else -- zero, denormal, huge, NaN, and a NaN or infinite hp -- compares false and takes the loop.
+RT_DEV bool diskUnlit(V3 hp, V3 N) {
+    const float kR = 1.21f, kTau = 1e-4f;
+    const V3 v = kDiskLightCenter() - hp;
+    const float n = length(N), lv = length(v);
+    return (n > 0.5f && n < 2.0f) && (dot(N, v) + kR * n < (-kTau * n) * (lv + kR));
+}
+
 // Segments of one BVH-mode sample; a tracer policy maps (segment, k) to a queue slot.
 enum { SEG_DIRECT = 0, SEG_GI_DIRECT = 1 };
 
@@ -446,6 +461,9 @@ enum { SEG_DIRECT = 0, SEG_GI_DIRECT = 1 };
 // `matters` is false when the visibility cannot reach the output: the reference casts the disk-sample
 // ray even when geom == 0 (rt_lighting.glsl:437-438), but then Li = kLightCol*0*vis = 0 for either
 // answer.  A tracer may skip such a ray and return anything.
+//   static constexpr bool T::kSkipUnlitDisk: a wave all of whose lanes satisfy diskUnlit does not evaluate the disk loop: it reports
+// the four samples as dead rays (matters == false) and leaves sum at mk3(0.0f) -- what the loop computes for such a hit, bit for bit.
+// The tracer is then told through T::disk_stat(seg, unlit, skipped).  Tracers that count the rays the REFERENCE casts do not opt in.
 template <class T>
 RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame, V3 Vdir) {
     const RtUniforms &u = *F.u;
@@ -453,15 +471,25 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
     V3 sum = mk3(0.0f);
     const V3 albedo = mk3(0.85f);
     const float specStrength = 0.25f, gloss = 32.0f;
-    V3 lt, lb;
-    lightFrame(lt, lb);
-    V2 rot = cpOffset(F.fcx, F.fcy, F.frameIndex);
     V3 V = normalize(Vdir);
-    for (int i = 0; i < 4; ++i) {   // SOFT_SHADOW_SAMPLES
-        DiskSample s = diskSample(F, hp, N, frame, i, rot, lt, lb);
-        float vis = tr.shadow(seg, i, s.ro, s.rd, s.tMax, s.geom != 0.0f) ? 0.0f : 1.0f;
-        V3 Li = mk3(18.0f) * s.geom * vis;
-        sum = sum + shadeLambertPhong(u.pi, N, V, s.L, Li, albedo, specStrength, gloss);
+    bool skip = false;
+    if constexpr (T::kSkipUnlitDisk) {
+        const bool unlit = diskUnlit(hp, N);
+        skip = __ballot(!unlit) == 0ull;   // (lanes that are not here vote 0: all ACTIVE lanes are unlit)
+        tr.disk_stat(seg, unlit, skip);
+    }
+    if (skip) {
+        for (int i = 0; i < 4; ++i) (void)tr.shadow(seg, i, mk3(0.0f), mk3(0.0f), 0.0f, false);
+    } else {
+        V3 lt, lb;
+        lightFrame(lt, lb);
+        V2 rot = cpOffset(F.fcx, F.fcy, F.frameIndex);
+        for (int i = 0; i < 4; ++i) {   // SOFT_SHADOW_SAMPLES
+            DiskSample s = diskSample(F, hp, N, frame, i, rot, lt, lb);
+            float vis = tr.shadow(seg, i, s.ro, s.rd, s.tMax, s.geom != 0.0f) ? 0.0f : 1.0f;
+            V3 Li = mk3(18.0f) * s.geom * vis;
+            sum = sum + shadeLambertPhong(u.pi, N, V, s.L, Li, albedo, specStrength, gloss);
+        }
     }
     sum = sum / 4.0f;
     MaterialProps fakeMat;

@@ -20,6 +20,7 @@ struct InlineTracer {
     StackEntry *stk;
     Work *w;
     // the megakernel is the reference-shaped baseline: it traces every ray the reference casts, needed or not
+    static constexpr bool kSkipUnlitDisk = false;
     __device__ __noinline__ bool shadow(int, int, V3 ro, V3 rd, float tMax, bool) {
         uint32_t f0 = w->fetches();
         bool r = bvh_anyhit<COUNT>(*sc, ro, rd, eps, tMax, stk, *w);

@@ -1575,7 +1575,21 @@ __global__ __launch_bounds__(256) void k_post_primary(const DevFrame *__restrict
 RT_DEV float4 mkf4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 RT_DEV float below(float r) { return (r > 0.0f) ? u2f(f2u(r) - 1u) : -1.0f; }   // largest float < r (r > 0), else "no ray"
 
+// rt_debug_disk_skip: five sums per generator kernel -- (hit, sample) pairs through directLightBVH, pairs with diskUnlit, pairs whose wave skipped the disk
+// loop, waves, waves that skipped it.  One lane per wave adds; only when the entry has switched counting on (stat != null).
+RT_DEV void disk_stat_add(unsigned long long *stat, bool unlit, bool skipped) {
+    const unsigned long long act = __ballot(1), un = __ballot(unlit);
+    if ((int)(threadIdx.x & 63) != __ffsll((long long)act) - 1) return;
+    atomicAdd(&stat[0], (unsigned long long)__popcll(act));
+    atomicAdd(&stat[1], (unsigned long long)__popcll(un));
+    atomicAdd(&stat[3], 1ull);
+    if (skipped) { atomicAdd(&stat[2], (unsigned long long)__popcll(act)); atomicAdd(&stat[4], 1ull); }
+}
+
 struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
+    static constexpr bool kSkipUnlitDisk = true;
+    unsigned long long *stat;
+    RT_DEV void disk_stat(int, bool unlit, bool skipped) { if (stat) disk_stat_add(stat, unlit, skipped); }
     WaveBuf wb;
     uint32_t j;
     int s;
@@ -1612,6 +1626,9 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
     }
 };
 struct GenGiTracer {       // reads the bounce result, records the shadow rays at the bounce hit
+    static constexpr bool kSkipUnlitDisk = true;
+    unsigned long long *stat;
+    RT_DEV void disk_stat(int, bool unlit, bool skipped) { if (stat) disk_stat_add(stat + 5, unlit, skipped); }
     WaveBuf wb;
     const DevScene *sc;
     float inf;
@@ -1641,6 +1658,8 @@ struct GenGiTracer {       // reads the bounce result, records the shadow rays a
     RT_DEV bool ao(int, V3, V3, float) { return false; }
 };
 struct CombineTracer {     // reads everything
+    static constexpr bool kSkipUnlitDisk = true;
+    RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
     uint32_t j;
@@ -1680,7 +1699,7 @@ RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
 RT_DEV uint32_t chunk_live(const WaveBuf &wb, uint32_t c0) { uint32_t h = wb.counts[1]; return min(h, c0 + wb.CH) - min(h, c0); }
 
 // ---- stage: gen_direct  (thread = (hit j, sample s), s-major so a wave shares s) -----------------
-__global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0) {
+__global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, unsigned long long *diskStat) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
@@ -1689,7 +1708,7 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
     const int s = mine ? (int)(tid / live) : 0;
     const uint32_t j = mine ? tid % live : 0;
     GenDirectTracer tr;
-    tr.wb = wb; tr.j = j; tr.s = s; tr.shadowMask = 0; tr.giCast = false;
+    tr.wb = wb; tr.j = j; tr.s = s; tr.shadowMask = 0; tr.giCast = false; tr.stat = diskStat;
     tr.giRo = mk3(0.0f); tr.giRd = mk3(0.0f);
     if (mine) {
         HitCtx c = load_hit(fr, wb.hits[c0 + j]);
@@ -1733,7 +1752,7 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
 }
 
 // ---- stage: gen_gi -------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount) {
+__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
@@ -1748,7 +1767,7 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
     wb.giPos[a] = bounced ? (int)pos : -1;
     if (!bounced) return;
     GenGiTracer tr;
-    tr.wb = wb; tr.sc = &fr->sc; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0;
+    tr.wb = wb; tr.sc = &fr->sc; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
     HitCtx c = load_hit(fr, wb.hits[c0 + j]);
     const int SPP = max(u.spp, 1);
     const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
@@ -1764,6 +1783,8 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
 // walk (bvh_anyhit: the same answers as the any-hit launch, tests/test_gpu_parity.py), into occOvf.  Launched behind every k_gen_gi of such a set; returns at once when
 // nothing overflowed.
 struct GenGiOverflowTracer {
+    static constexpr bool kSkipUnlitDisk = true;
+    RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
     float eps;
@@ -1985,6 +2006,8 @@ struct RtWave {
     unsigned long long *probeAcc = nullptr;   // device, monotonic: [0] bounce rays the probe walked [1] rays it re-traced closest-hit
     unsigned long long probeLaunches = 0, closestLaunches = 0;   // bounce launches (chunks) with / without the probe
     unsigned long long probeBase[4] = {};     // rt_wave_bounce_probe's reset: the values above at that time
+    unsigned long long *diskAcc = nullptr;    // device: rt_wave_disk_skip's ten sums (disk_stat_add); the generators count only once the entry was called
+    bool diskStatOn = false;
     unsigned long long tracedProbeBase = 0;   // rt_wave_traced's reset: probeAcc[0] at that time (probed rays count as bounce rays there)
 };
 
@@ -2027,6 +2050,7 @@ void rt_wave_destroy(RtWave *w) {
     if (w->heads) (void)hipFree(w->heads);
     if (w->acc) (void)hipFree(w->acc);
     if (w->probeAcc) (void)hipFree(w->probeAcc);
+    if (w->diskAcc) (void)hipFree(w->diskAcc);
     if (w->stats) (void)hipFree(w->stats);
     if (w->hostHits) (void)hipHostFree(w->hostHits);
     delete w;
@@ -2304,7 +2328,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         const unsigned gridHS = (unsigned)((CH * (size_t)SPP + 255) / 256), gridH = (unsigned)((CH + 255) / 256);
         W_TRY(hop(st, ss));
         rt_stage_begin(ctx, ST_GEN_DIRECT, ss);
-        hipLaunchKernelGGL(k_gen_direct, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0);
+        hipLaunchKernelGGL(k_gen_direct, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr);
         rt_stage_end(ctx, ST_GEN_DIRECT, 1, ss);
         W_TRY(hop(ss, st));
 
@@ -2347,7 +2371,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
 
             W_TRY(hop(st, ss));
             rt_stage_begin(ctx, ST_GEN_GI, ss);
-            hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, &wb.counts[64 + c]);
+            hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr);
             if (wb.q2Stride < wb.CH * (uint32_t)SPP)   // a predicted capacity: the pairs beyond it (normally none) trace their rays in place
                 hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(treeDepth, 4) * 8, ss, dFrame, wb, c0, &wb.counts[64 + c], std::max(treeDepth, 4));
             rt_stage_end(ctx, ST_GEN_GI, 1, ss);
@@ -2512,6 +2536,17 @@ int rt_wave_bounce_probe(RtWave *w, hipStream_t st, unsigned long long *out4, bo
         W_TRY(hipMemcpy(v, w->probeAcc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
     for (int i = 0; i < 4; ++i) { out4[i] = v[i] - w->probeBase[i]; if (reset) w->probeBase[i] = v[i]; }
+    return RT_OK;
+}
+
+int rt_wave_disk_skip(RtWave *w, hipStream_t st, unsigned long long *out10, bool reset) {
+    for (int i = 0; i < 10; ++i) out10[i] = 0;
+    if (!w) return RT_OK;
+    W_TRY(hipStreamSynchronize(st));
+    if (!w->diskAcc) { W_TRY(hipMalloc(&w->diskAcc, 10 * sizeof(unsigned long long))); W_TRY(hipMemset(w->diskAcc, 0, 10 * sizeof(unsigned long long))); }
+    W_TRY(hipMemcpy(out10, w->diskAcc, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) W_TRY(hipMemset(w->diskAcc, 0, 10 * sizeof(unsigned long long)));
+    w->diskStatOn = true;
     return RT_OK;
 }
 

@@ -35,6 +35,9 @@ int rt_wave_traced(RtWave *w, hipStream_t stream, unsigned long long *out16, boo
 // RT_BOUNCE_PROBE since the last reset, 4 words: [0] bounce rays walked any-hit first [1] of them re-traced closest-hit (the probe found a triangle)
 // [2] bounce launches (chunks) with the probe [3] without it
 int rt_wave_bounce_probe(RtWave *w, hipStream_t stream, unsigned long long *out4, bool reset);
+// The disk-light skip of the shading stages since the last reset, 10 words: for k_gen_direct [0] (hit, sample) pairs shaded [1] pairs with diskUnlit
+// [2] pairs whose wave skipped the disk loop [3] waves [4] waves that skipped; [5..9] the same for k_gen_gi.  The generators count from the first call on.
+int rt_wave_disk_skip(RtWave *w, hipStream_t stream, unsigned long long *out10, bool reset);
 // The share of bounce hits of earlier launch sets (what shadow queue 2 is sized from and the bounce probe is chosen by) belongs to a scene and a frame size:
 // rt_upload_bvh and rt_resize forget it (an spp change does so in rt_wave_render)
 void rt_wave_forget_share(RtWave *w);

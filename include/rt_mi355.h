@@ -518,7 +518,27 @@ int rt_mesh_set_positions(RtContext *ctx, const float *positions);
  * after the frames and queries already enqueued on every frame lane and before whatever is enqueued next, by events.  No allocation; no host wait
  * except the one named above. */
 int rt_mesh_rebuild(RtContext *ctx, const float *M16);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild. */
+/* Refit: the second build mode.  Keeps the tree of the most recent rt_mesh_rebuild -- node numbering, links, leaf ranges and which input triangle sits
+ * in which row of the triangle array -- and recomputes, on the device, everything that depends on coordinates from the current device positions and M16
+ * (NULL: identity): the triangles, every node's box bottom-up, the root box and every record form a rebuild emits.  No sort, so a fraction of a rebuild's
+ * cost.  Contract: afterwards the scene is, byte for byte in every device array and in RtSceneInfo, what rt_upload_bvh installs from
+ * rt_refit_bvh(rt_gather_triangles_checked(positions, indices, M16), order, nodes12, tris12) with route A's arrays of the last rebuild and rt_mesh_order's
+ * order.  Enqueued, ordered and installed exactly as rt_mesh_rebuild: no allocation, no host wait but the one status-word read of the quantised form
+ * (RtMeshInfo.hostSyncs counts it; on failure RT_SCENE_QNODES_REJECTED), accumulation and bounce-share prediction kept.  RT_ERR_INVALID without a mesh
+ * and before the first rt_mesh_rebuild of the current mesh; rt_mesh_upload / rt_upload_bvh forget the tree as they forget the mesh.
+ * Tree quality is the caller's business: a refitted tree is exact for any deformation, but the further triangles move apart from where the last rebuild
+ * found them, the more its boxes overlap and the slower it is to walk.  Rebuild from time to time. */
+int rt_mesh_refit(RtContext *ctx, const float *M16);
+/* Refits since rt_mesh_upload and since the last rt_mesh_rebuild (either pointer may be NULL, not both).  RtMeshInfo.rebuilds counts rebuilds only. */
+int rt_mesh_refit_count(RtContext *ctx, uint64_t *total, uint64_t *sinceRebuild);
+/* order[i] = the input triangle (index triple i of rt_mesh_upload's indices) that is row i of the device triangle array since the last rebuild --
+ * rt_build_bvh_order's meaning, so order[prim] ties a query's or a pick's answer to the caller's index buffer.  A refit does not change it.
+ * rt_mesh_order copies nTris entries out and synchronises; rt_mesh_order_device hands out a device array (nTris x int32) that is valid until the next
+ * rt_mesh_rebuild and is written, at the first call after a rebuild, on rt_stream()'s stream: order reads of it there.  RT_ERR_INVALID before the first
+ * rebuild. */
+int rt_mesh_order(RtContext *ctx, int32_t *order);
+int rt_mesh_order_device(RtContext *ctx, void **devPtr, size_t *bytes);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -557,6 +577,14 @@ int rt_build_bvh(const float *tris9, int nTris, float *nodes12, float *tris12);
 /* rt_build_bvh (bit for bit the same nodes12 / tris12) plus order[i] = the input triangle that became row i of tris12: maps a query's
  * prim back to the mesh.  order needs room for nTris entries. */
 int rt_build_bvh_order(const float *tris9, int nTris, float *nodes12, float *tris12, int32_t *order);
+/* Refit on host arrays, and the definition rt_mesh_refit is tested against.  nodes12 (nNodes rows) / tris12 / order as rt_build_bvh_order produced them
+ * (or rt_build_bvh_gpu plus rt_mesh_order); tris9 the new triangles in input order.  Rewrites row i of tris12 from triangle order[i] and the six bounds
+ * floats of every node: min / max over the triangles of its range of the corners v0, v0 + e1, v0 + e2.  Links, first and count stay untouched.
+ * The reduction orders floats as the device builder's sortable keys do: -0 lies below +0 (std::min / std::max would keep whichever came first).
+ * Coordinates are finite and below 1e30 in magnitude, as for the builders.  RT_ERR_INVALID: a null array, counts <= 0, order not a permutation of
+ * 0 .. nTris-1, or nodes that are not a tree in pre-order whose leaf ranges cover every row once.  With rt_upload_bvh it is a refit for hosts that
+ * build on the CPU.  Returns RT_OK. */
+int rt_refit_bvh(const float *tris9, int nTris, const int32_t *order, float *nodes12, int nNodes, float *tris12);
 
 /* Stand-in for Model/Mesh + Assimp (include/scene/model.h:105-228) for plain .obj files: v / f records,
  * fan triangulation, negative indices.  Buffers are malloc'ed; release with rt_free. */

@@ -296,6 +296,10 @@ SIGNATURES = {
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_mesh_set_positions": (C.c_int, [C.c_void_p, _FP]),
     "rt_mesh_rebuild": (C.c_int, [C.c_void_p, _FP]),
+    "rt_mesh_refit": (C.c_int, [C.c_void_p, _FP]),
+    "rt_mesh_refit_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rt_mesh_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rt_mesh_order_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
     "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
@@ -311,6 +315,7 @@ SIGNATURES = {
     "rt_gather_triangles_checked": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, _FP, _FP]),
     "rt_build_bvh": (C.c_int, [_FP, C.c_int, _FP, _FP]),
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
+    "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -520,6 +525,22 @@ def build_bvh_order(tris9):
     return nodes[:k].copy(), tris[:n].copy(), order[:n].copy()
 
 
+def refit_bvh(nodes12, tris12, order, tris9):
+    """-> (nodes12, tris12) of the same tree over new triangles (rt_refit_bvh): tris9 in input order, order as build_bvh_order or Renderer.mesh_order
+    gave it.  Row i of tris12 comes from triangle order[i]; every node's box is recomputed from its range; links, first and count stay.  The inputs
+    are not modified."""
+    n = np.array(_f32(nodes12).reshape(-1, 12), copy=True)
+    t = np.array(_f32(tris12).reshape(-1, 12), copy=True)
+    o = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+    t9 = _f32(tris9).reshape(-1, 9)
+    if o.size != t.shape[0] or t9.shape[0] != t.shape[0]:
+        raise RtError(RT_ERR_INVALID, f"refit_bvh: {t.shape[0]} rows of tris12, {o.size} entries of order, {t9.shape[0]} triangles")
+    rc = lib().rt_refit_bvh(_fp(t9), t9.shape[0], o.ctypes.data_as(C.POINTER(C.c_int32)), _fp(n), n.shape[0], _fp(t))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_refit_bvh: order is not a permutation or the nodes are not a tree over the rows" if rc == RT_ERR_INVALID else "rt_refit_bvh")
+    return n, t
+
+
 def load_obj(path):
     pos, idx = _FP(), _U32P()
     nv, ni = C.c_int(), C.c_int()
@@ -695,6 +716,44 @@ class Renderer:
         self._check(lib().rt_mesh_rebuild(self._h, None if m is None else _fp(m)))
         i = self.scene_info()
         self.n_nodes, self.n_tris = i.nNodes, i.nTris
+
+    def mesh_refit(self, model=None):
+        """Keep the tree of the last mesh_rebuild and recompute what depends on coordinates -- triangles, every box, every record form -- from the
+        current device positions and the model matrix (None: identity) (rt_mesh_refit).  Asynchronous like mesh_rebuild, at a fraction of its cost.
+        Exact for any deformation; the tree gets slower to walk as triangles move apart, so rebuild from time to time."""
+        m = None if model is None else _f32(model).reshape(-1)
+        if m is not None and m.size != 16:
+            raise RtError(RT_ERR_INVALID, "mesh_refit: model must have 16 floats")
+        self._check(lib().rt_mesh_refit(self._h, None if m is None else _fp(m)))
+
+    def mesh_refit_count(self):
+        """-> (refits since mesh_upload, refits since the last mesh_rebuild)"""
+        total, since = C.c_uint64(), C.c_uint64()
+        self._check(lib().rt_mesh_refit_count(self._h, C.byref(total), C.byref(since)))
+        return total.value, since.value
+
+    def mesh_order(self, as_torch=None):
+        """order[i] = the input triangle that is row i of the device triangle array since the last mesh_rebuild, so order[prim] maps a hit back to the
+        index buffer.  With torch (as_torch=None: when it imports) an int32 [nTris] tensor that aliases the device array, zero-copy, valid until the
+        next mesh_rebuild and written on stream(): read it there.  Else a numpy array (rt_mesh_order: copies and synchronises)."""
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        if not as_torch:
+            out = np.zeros(max(self.mesh_info().nTris, 1), np.int32)
+            self._check(lib().rt_mesh_order(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+            return out[:self.mesh_info().nTris]
+        import torch
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_order_device(self._h, C.byref(ptr), C.byref(n)))
+        nt = n.value // 4
+
+        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+            __cuda_array_interface__ = {"shape": (nt,), "typestr": "<i4", "data": (ptr.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
 
     def mesh_info(self) -> RtMeshInfo:
         i = RtMeshInfo()

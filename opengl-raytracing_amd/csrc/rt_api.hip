@@ -68,7 +68,7 @@ struct RtContext {
     bool sceneFromMesh = false;
     float *dRootBox = nullptr;       // sceneFromMesh: node 0's box on the device -- the host does not know it (rootMin / rootMax above are not used then)
     hipEvent_t evMeshLane[RT_MAX_LANES] = {}, evMeshDone = nullptr;   // a rebuild waits for every lane / every lane waits for the rebuild
-    uint64_t meshRebuilds = 0, meshHostSyncs = 0;
+    uint64_t meshRebuilds = 0, meshHostSyncs = 0, meshRefits = 0, meshRefitsSinceRebuild = 0;
     // frame state
     FrameGeom g{};
     bool sized = false;
@@ -1192,7 +1192,7 @@ int rt_mesh_upload(RtContext *c, const float *positions, int nVerts, const uint3
         bool ok = hipEventCreateWithFlags(&c->evMeshDone, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; ok && i < c->nLanes; ++i) ok = hipEventCreateWithFlags(&c->evMeshLane[i], hipEventDisableTiming) == hipSuccess;
         if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "rt_mesh_upload: event creation failed"); }
-        c->meshRebuilds = c->meshHostSyncs = 0;
+        c->meshRebuilds = c->meshHostSyncs = c->meshRefits = c->meshRefitsSinceRebuild = 0;
         return RT_OK;
     });
 }
@@ -1213,22 +1213,26 @@ int rt_mesh_set_positions(RtContext *c, const float *positions) {
     return RT_OK;
 }
 
-int rt_mesh_rebuild(RtContext *c, const float *M16) {
+// A rebuild or a refit: the device work of rt_mesh.hip between the two halves of the event scheme, then the scene installed (the same pointers and
+// counts every time; what a refit can change is whether the quantised nodes could be built).
+static int mesh_update(RtContext *c, const float *M16, bool refit) {
+    const char *who = refit ? "rt_mesh_refit" : "rt_mesh_rebuild";
     if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_rebuild: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", who);
+    if (refit && !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_refit: no tree to keep (rt_mesh_rebuild first)");
     (void)hipSetDevice(c->cfg.device);
     static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    // every lane's frames and queries read the arrays that are about to be rewritten: the rebuild waits for them ...
+    // every lane's frames and queries read the arrays that are about to be rewritten: the update waits for them ...
     for (int i = 0; i < c->nLanes; ++i) {
         if (c->lanes[i] == st) continue;
         HIP_TRY(c, hipEventRecord(c->evMeshLane[i], c->lanes[i]));
         HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
     }
     const char *err = nullptr;
-    int rc = rtl::mesh_rebuild(c->mesh, st, M16 ? M16 : kIdentity, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_rebuild: %s", err ? err : "launch failed");
-    // ... and whatever a lane is given next waits for the rebuild
+    int rc = refit ? rtl::mesh_refit(c->mesh, st, M16 ? M16 : kIdentity, &err) : rtl::mesh_rebuild(c->mesh, st, M16 ? M16 : kIdentity, &err);
+    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
+    // ... and whatever a lane is given next waits for it
     HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
     for (int i = 0; i < c->nLanes; ++i)
         if (c->lanes[i] != st) HIP_TRY(c, hipStreamWaitEvent(c->lanes[i], c->evMeshDone, 0));
@@ -1238,20 +1242,57 @@ int rt_mesh_rebuild(RtContext *c, const float *M16) {
     if (sc.q4) {   // the host picks the any-hit kernel by whether the quantised nodes exist: the one allowed wait
         rc = rtl::mesh_quantised_ok(c->mesh, st, okQ, &err);
         ++c->meshHostSyncs;
-        if (rc != RT_OK) return fail(c, rc, "rt_mesh_rebuild: %s", err ? err : "status read failed");
+        if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "status read failed");
     }
     // install: pointers and counts are those of the mesh, the same at every rebuild
     c->dWNodes = sc.wnodes; c->dWNodesW = sc.wnodesW; c->dW4 = sc.w4; c->dPairs = sc.pairs; c->dTris = sc.tris;
     c->dQ4 = okQ ? sc.q4 : nullptr; c->dLeafBox = okQ ? sc.leafBox : nullptr;
     c->leafBoxBytes = sc.leafBoxBytes; c->leafBoxMagic = sc.leafBoxMagic; c->nLeafBoxes = L.nLeaves;
     c->sceneFlags = (sc.q4 && !okQ) ? RT_SCENE_QNODES_REJECTED : 0;
-    if (sc.q4 && !okQ && getenv("RT_VERBOSE")) fprintf(stderr, "[rt_mesh_rebuild] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n");
+    if (sc.q4 && !okQ && getenv("RT_VERBOSE")) fprintf(stderr, "[%s] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n", who);
     c->nNodes = L.nNodes; c->nTris = L.nTris; c->nInner = L.nInner; c->treeDepth = L.treeDepth;
     c->nWide4 = L.nWide4; c->nPairs = L.nPairs; c->nFused = 0;
     c->rootRef = L.rootRef; c->rootRefW = L.rootRefW; c->rootRef4 = L.rootRef4; c->anyStack = L.anyStack;
     c->dRootBox = sc.rootBox;
     c->sceneFromMesh = true;
-    ++c->meshRebuilds;
+    if (refit) { ++c->meshRefits; ++c->meshRefitsSinceRebuild; }
+    else { ++c->meshRebuilds; c->meshRefitsSinceRebuild = 0; }
+    return RT_OK;
+}
+
+int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16, false); }
+int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
+
+int rt_mesh_refit_count(RtContext *c, uint64_t *total, uint64_t *sinceRebuild) {
+    if (!c || (!total && !sinceRebuild)) return RT_ERR_INVALID;
+    if (total) *total = c->mesh ? c->meshRefits : 0;
+    if (sinceRebuild) *sinceRebuild = c->mesh ? c->meshRefitsSinceRebuild : 0;
+    return RT_OK;
+}
+
+int rt_mesh_order_device(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_order: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
+    (void)hipSetDevice(c->cfg.device);
+    const char *err = nullptr;
+    const int *order = nullptr;
+    const int rc = rtl::mesh_order(c->mesh, c->lastStream ? c->lastStream : c->stream, &order, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_order: %s", err ? err : "launch failed");
+    *devPtr = const_cast<int *>(order);
+    *bytes = (size_t)rtl::mesh_layout(c->mesh).nTris * 4;
+    return RT_OK;
+}
+
+int rt_mesh_order(RtContext *c, int32_t *order) {
+    if (!c || !order) return RT_ERR_INVALID;
+    void *d = nullptr;
+    size_t bytes = 0;
+    const int rc = rt_mesh_order_device(c, &d, &bytes);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    HIP_TRY(c, hipMemcpyAsync(order, d, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     return RT_OK;
 }
 
@@ -1923,13 +1964,15 @@ static int query_args(RtContext *c, const char *what, int kind, const float *ori
 // The query scratch (allocated on the first query) and rt_stream()'s stream, which first waits for the previous query if that ran on another stream
 static int query_begin(RtContext *c, hipStream_t &st) {
     (void)hipSetDevice(c->cfg.device);
+    st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
     if (!c->dQueryFrame) {
         HIP_TRY(c, hipMalloc(&c->dQueryFrame, sizeof(DevFrame)));
         HIP_TRY(c, hipMalloc(&c->dQueryHeads, rt_wave_head_words() * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemset(c->dQueryFrame, 0, sizeof(DevFrame)));
+        // on the query's own stream: the lanes do not synchronise with the null stream, and a memset there can land after the first query's kernels
+        // have written their uniforms into the scratch
+        HIP_TRY(c, hipMemsetAsync(c->dQueryFrame, 0, sizeof(DevFrame), st));
         HIP_TRY(c, hipEventCreateWithFlags(&c->queryDone, hipEventDisableTiming));
     }
-    st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
     if (c->queryStream && c->queryStream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->queryDone, 0));   // the scratch is free again
     return RT_OK;
 }

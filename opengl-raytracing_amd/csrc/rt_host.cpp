@@ -447,6 +447,72 @@ int rt_build_bvh_order(const float *tris9, int nTris, float *nodes12, float *tri
     });
 }
 
+// The device builder reduces bounds as sortable unsigned keys (rt_bvh_build.hpp): a total order in which -0 lies below +0.
+static inline uint32_t f2sortable(float f) { uint32_t u; std::memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+static inline float sortable2f(uint32_t s) { const uint32_t u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s; float f; std::memcpy(&f, &u, 4); return f; }
+
+int rt_refit_bvh(const float *tris9, int nTris, const int32_t *order, float *nodes12, int nNodes, float *tris12) {
+    if (!tris9 || !order || !nodes12 || !tris12 || nTris <= 0 || nNodes <= 0) return RT_ERR_INVALID;
+    return guarded([&]() -> int {
+    const size_t N = (size_t)nTris, K = (size_t)nNodes;
+    std::vector<char> seen(N, 0);
+    for (size_t i = 0; i < N; ++i) {
+        if (order[i] < 0 || order[i] >= nTris || seen[(size_t)order[i]]) return RT_ERR_INVALID;
+        seen[(size_t)order[i]] = 1;
+    }
+    // the links: integers, a leaf's range inside the array, an inner node's children behind it (pre-order), every node but the root the child of
+    // exactly one node, every row in exactly one leaf
+    struct Link { int left, right, first, count; };
+    std::vector<Link> links(K);
+    std::vector<char> hasParent(K, 0), covered(N, 0);
+    auto asInt = [](float f, int &out) { if (!(f >= -1.0f && f < 2147483648.0f) || f != std::floor(f)) return false; out = (int)f; return true; };
+    for (size_t i = 0; i < K; ++i) {
+        const float *o = nodes12 + i * 12;
+        Link &l = links[i];
+        if (!asInt(o[3], l.left) || !asInt(o[7], l.right) || !asInt(o[8], l.first) || !asInt(o[9], l.count) || l.count < 0) return RT_ERR_INVALID;
+        if (l.count > 0) {
+            if (l.first < 0 || l.first > nTris - l.count) return RT_ERR_INVALID;
+            for (int k = 0; k < l.count; ++k) { if (covered[(size_t)(l.first + k)]) return RT_ERR_INVALID; covered[(size_t)(l.first + k)] = 1; }
+        } else {
+            for (int ch : {l.left, l.right}) {
+                if (ch <= (int)i || ch >= nNodes || hasParent[(size_t)ch]) return RT_ERR_INVALID;
+                hasParent[(size_t)ch] = 1;
+            }
+        }
+    }
+    for (size_t i = 1; i < K; ++i) if (!hasParent[i]) return RT_ERR_INVALID;
+    for (size_t i = 0; i < N; ++i) if (!covered[i]) return RT_ERR_INVALID;
+    for (size_t i = 0; i < N; ++i) {   // triangle texels, as rt_build_bvh_order writes them
+        const float *t = tris9 + (size_t)order[i] * 9;
+        float *o = tris12 + i * 12;
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = 0.0f;
+        o[4] = t[3]; o[5] = t[4]; o[6] = t[5]; o[7] = 0.0f;
+        o[8] = t[6]; o[9] = t[7]; o[10] = t[8]; o[11] = 0.0f;
+    }
+    std::vector<uint32_t> keys(K * 6);
+    for (size_t i = K; i-- > 0;) {     // children come behind their parent: backwards is bottom-up
+        const Link &l = links[i];
+        uint32_t *b = &keys[i * 6];
+        for (int a = 0; a < 3; ++a) { b[a] = 0xffffffffu; b[3 + a] = 0u; }
+        if (l.count > 0) {
+            for (int k = 0; k < l.count; ++k) {
+                const float *t = tris12 + (size_t)(l.first + k) * 12;
+                for (int a = 0; a < 3; ++a) {
+                    const float v0 = t[a], v1 = v0 + t[4 + a], v2 = v0 + t[8 + a];   // bvh.cpp:10-20
+                    for (float v : {v0, v1, v2}) { const uint32_t s = f2sortable(v); b[a] = std::min(b[a], s); b[3 + a] = std::max(b[3 + a], s); }
+                }
+            }
+        } else {
+            const uint32_t *x = &keys[(size_t)l.left * 6], *y = &keys[(size_t)l.right * 6];
+            for (int a = 0; a < 3; ++a) { b[a] = std::min(x[a], y[a]); b[3 + a] = std::max(x[3 + a], y[3 + a]); }
+        }
+        float *o = nodes12 + i * 12;
+        for (int a = 0; a < 3; ++a) { o[a] = sortable2f(b[a]); o[4 + a] = sortable2f(b[3 + a]); }
+    }
+    return RT_OK;
+    });
+}
+
 int rt_build_bvh(const float *tris9, int nTris, float *nodes12, float *tris12) { return rt_build_bvh_order(tris9, nTris, nodes12, tris12, nullptr); }
 
 int rt_load_obj(const char *path, float **positions, int *nVerts, uint32_t **indices, int *nIdx) {

@@ -242,6 +242,12 @@ struct Mesh {
     Wn2Tab *dWn2Tab = nullptr;
     W4Tab *dW4Tab = nullptr;
     LeafTab *dLeafTab = nullptr;
+    RefitLeaf *dRefitLeaf = nullptr;
+    RefitKids *dRefitKids = nullptr;
+    // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
+    // and holds, once asked for, the row -> input triangle map
+    int permCur = -1;
+    bool orderValid = false;
     uint32_t *hStatus = nullptr;   // pinned
     std::vector<void *> owned;
     uint64_t allocations = 0;
@@ -324,6 +330,12 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
         const int L = sk[(size_t)i].left, R = sk[(size_t)i].right;
         wn2[(size_t)innerIdx[(size_t)i]] = {slotOf[(size_t)L], slotOf[(size_t)R], refOf(L), refOf(R), refOfW(L), refOfW(R)};
     }
+    std::vector<RefitLeaf> refitLeaf;
+    std::vector<RefitKids> refitKids((size_t)nNodes);
+    for (int i = 0; i < nNodes; ++i) {
+        if (countOf(i) > 0) { refitLeaf.push_back({slotOf[(size_t)i], sk[(size_t)i].firstOut, countOf(i)}); refitKids[(size_t)slotOf[(size_t)i]] = {-1, -1}; }
+        else refitKids[(size_t)slotOf[(size_t)i]] = {slotOf[(size_t)sk[(size_t)i].left], slotOf[(size_t)sk[(size_t)i].right]};
+    }
     std::vector<W4Tab> w4;
     int anyStack = 0;
     if (countOf(0) <= 0) {
@@ -404,6 +416,7 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
     MESH_TRY(dev_upload(m, &m->dOut, outOfPos));
     MESH_TRY(dev_upload(m, &m->dPairTab, pairTab)); MESH_TRY(dev_upload(m, &m->dWn2Tab, wn2)); MESH_TRY(dev_upload(m, &m->dW4Tab, w4));
     if (quantised) MESH_TRY(dev_upload(m, &m->dLeafTab, leafTab));
+    MESH_TRY(dev_upload(m, &m->dRefitLeaf, refitLeaf)); MESH_TRY(dev_upload(m, &m->dRefitKids, refitKids));
     MESH_TRY(dev_alloc(m, &m->dT9, N * 36, false, false));
     MESH_TRY(dev_alloc(m, &m->dMn, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dMx, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dCen, N * 12, false, false));
     MESH_TRY(dev_alloc(m, &m->dPerm[0], N * 4, false, false)); MESH_TRY(dev_alloc(m, &m->dPerm[1], N * 4, false, false));
@@ -451,10 +464,27 @@ size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }
 
 #define REB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); return RT_ERR_HIP; } } while (0)
 
+namespace {
+// every record form from the bounds and the triangle array, through the tables: the tail of a rebuild and of a refit
+void emit_records(Mesh *m, hipStream_t st) {
+    const BvhLayout &L = m->lay;
+    hipLaunchKernelGGL(k_mesh_root, dim3(1), dim3(64), 0, st, m->dBounds, m->sc.rootBox);
+    hipLaunchKernelGGL(k_mesh_pairs, dim3(blocks_for(L.nPairs)), dim3(256), 0, st, m->sc.tris, m->dPairTab, (int)L.nPairs, m->sc.pairs);
+    if (L.nInner > 0) {
+        hipLaunchKernelGGL(k_mesh_nodes2, dim3(blocks_for((size_t)L.nInner)), dim3(256), 0, st, m->dBounds, m->dWn2Tab, L.nInner, m->sc.wnodes, m->sc.wnodesW);
+        hipLaunchKernelGGL(k_mesh_nodes4, dim3(blocks_for(L.nWide4)), dim3(256), 0, st, m->dBounds, m->dW4Tab, (int)L.nWide4, m->sc.w4,
+                           reinterpret_cast<uint4 *>(m->sc.q4), m->dStatus);
+        if (m->quantised)
+            hipLaunchKernelGGL(k_mesh_leafbox, dim3(blocks_for(L.nLeaves)), dim3(256), 0, st, m->dBounds, m->dLeafTab, (int)L.nLeaves, m->sc.leafBox);
+    }
+}
+}  // namespace
+
 int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     const BvhLayout &L = m->lay;
     const int n = L.nTris;
     const unsigned gN = blocks_for((size_t)n);
+    m->permCur = -1; m->orderValid = false;   // the sorts below use both permutation buffers
     Mat16 M;
     std::memcpy(M.m, M16, sizeof M.m);
     hipLaunchKernelGGL(k_mesh_gather, dim3(gN), dim3(256), 0, st, m->dPos, m->dIdx, n, M, m->dT9);
@@ -475,16 +505,39 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
         cur = (vb.current() == m->dPerm[0]) ? 0 : 1;
     }
     hipLaunchKernelGGL(k_emit_tris, dim3(gN), dim3(256), 0, st, m->dT9, m->dPerm[cur], m->dOut, n, reinterpret_cast<float *>(m->sc.tris));
-    hipLaunchKernelGGL(k_mesh_root, dim3(1), dim3(64), 0, st, m->dBounds, m->sc.rootBox);
-    hipLaunchKernelGGL(k_mesh_pairs, dim3(blocks_for(L.nPairs)), dim3(256), 0, st, m->sc.tris, m->dPairTab, (int)L.nPairs, m->sc.pairs);
-    if (L.nInner > 0) {
-        hipLaunchKernelGGL(k_mesh_nodes2, dim3(blocks_for((size_t)L.nInner)), dim3(256), 0, st, m->dBounds, m->dWn2Tab, L.nInner, m->sc.wnodes, m->sc.wnodesW);
-        hipLaunchKernelGGL(k_mesh_nodes4, dim3(blocks_for(L.nWide4)), dim3(256), 0, st, m->dBounds, m->dW4Tab, (int)L.nWide4, m->sc.w4,
-                           reinterpret_cast<uint4 *>(m->sc.q4), m->dStatus);
-        if (m->quantised)
-            hipLaunchKernelGGL(k_mesh_leafbox, dim3(blocks_for(L.nLeaves)), dim3(256), 0, st, m->dBounds, m->dLeafTab, (int)L.nLeaves, m->sc.leafBox);
-    }
+    emit_records(m, st);
     REB_TRY(hipGetLastError());
+    m->permCur = cur;
+    return RT_OK;
+}
+
+bool mesh_has_tree(const Mesh *m) { return m->permCur >= 0; }
+
+int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err) {
+    if (m->permCur < 0) return RT_ERR_INVALID;
+    const BvhLayout &L = m->lay;
+    const int n = L.nTris;
+    refit_launch_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, n, M16, m->sc.tris);
+    refit_launch_leaves(st, m->sc.tris, m->dRefitLeaf, (int)L.nLeaves, m->dBounds, m->dStatus);
+    for (int d = m->nLevels - 2; d >= 0; --d) {   // bottom-up, one launch per level: a kernel boundary makes the children's boxes visible
+        if (!m->levelInner[(size_t)d]) continue;
+        const int nSeg = m->levelSegs[(size_t)d];
+        refit_launch_inner(st, m->dRefitKids, m->levelOff[(size_t)d], nSeg, m->dBounds);
+    }
+    emit_records(m, st);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int mesh_order(Mesh *m, hipStream_t st, const int **order, const char **err) {
+    if (m->permCur < 0) return RT_ERR_INVALID;
+    int *dst = m->dPerm[m->permCur ^ 1];
+    if (!m->orderValid) {
+        refit_launch_order(st, m->dPerm[m->permCur], m->dOut, m->lay.nTris, dst);
+        REB_TRY(hipGetLastError());
+        m->orderValid = true;
+    }
+    *order = dst;
     return RT_OK;
 }
 

@@ -40,6 +40,23 @@ size_t mesh_scratch_bytes(const Mesh *m);
 size_t mesh_scene_bytes(const Mesh *m);
 // Enqueues gather (model matrix M16, column-major), build and record emission on `st`: no allocation, no host wait.
 int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err);
+// A rebuild of this mesh has run: there is a tree to refit and an order to hand out.
+bool mesh_has_tree(const Mesh *m);
+// Enqueues the refit on `st`: the tree of the last rebuild (numbering, links, leaf ranges, which input triangle sits in which row) kept, triangles
+// re-gathered under M16 into their rows, boxes bottom-up, every record form re-emitted.  No allocation, no host wait.  RT_ERR_INVALID without a tree.
+int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err);
+// *order: device array, order[row of the triangle array] = input triangle, derived on `st` at the first call after a rebuild into the permutation
+// buffer that is idle between rebuilds; valid until the next rebuild.  RT_ERR_INVALID without a tree.
+int mesh_order(Mesh *m, hipStream_t st, const int **order, const char **err);
+
+// rt_mesh_refit.hip: the refit's kernels behind plain launch functions (raw device pointers; bounds are the builder's sortable uints, six per slot)
+struct RefitLeaf { int slot, first, count; };   // one leaf: bounds slot, its rows of the triangle array
+struct RefitKids { int l, r; };                 // per bounds slot: the children's slots (-1, -1: a leaf)
+void refit_launch_tris(hipStream_t st, const float *pos, const uint32_t *idx, const int *perm, const int *outOfPos, int nTris, const float *M16, float4 *t12);
+void refit_launch_leaves(hipStream_t st, const float4 *t12, const RefitLeaf *leaves, int nLeaves, uint32_t *bounds, uint32_t *status);   // clears *status
+void refit_launch_inner(hipStream_t st, const RefitKids *kids, int firstSlot, int nSlots, uint32_t *bounds);                             // one level
+void refit_launch_order(hipStream_t st, const int *perm, const int *outOfPos, int nTris, int *order);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

@@ -1,0 +1,178 @@
+"""Times rt_mesh_refit against rt_mesh_rebuild on the same animation step, and what frames cost on a tree that is refitted
+instead of rebuilt.
+
+    python tools/mesh_refit_time.py [--reps N] [--out profiles/r09_mesh_refit.txt] [--sizes bunny,1m | none] [--no-frames]
+
+Per size (the bench mesh -- bunny stand-in, 81 920 triangles -- and the 1 M-triangle scene, where the quantised any-hit form is in use and both
+calls pay their one host wait), in one process and on one context: every step displaces the positions on the device, then runs rt_mesh_rebuild
+and rt_mesh_refit over those positions, alternated, `--reps` repetitions each after warm-up.  Device time between torch events recorded on the
+library stream around the call; wall time from the call to the return of rt_synchronize.  Medians with min .. max.
+Condition of the issue: the refit's median device time is below the rebuild's and its whole range lies below the rebuild's minimum.
+
+Informational (bench mesh only): ms per frame of the bench view (1920x1080, 4 spp, close-up camera, wavefront pipeline) on the tree after 1, 8
+and 32 refit steps of the animation, and after random per-vertex displacements, against a tree rebuilt over the same positions on a second
+context -- the price of not rebuilding.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import opengl_raytracing_amd as rt  # noqa: E402
+import scenes  # noqa: E402
+
+
+def step_delta(pos, ext, k):
+    """One step of the test animation: a smooth displacement of 3 % of the mesh's extent (tests/test_gpu_mesh_refit.py::_sinus)."""
+    return (np.float32(0.03) * ext * np.sin(np.float32(3.0) * pos / ext + np.float32(0.7 + k))).astype(np.float32)
+
+
+def fmt(name, ms):
+    return f"  {name:<52s} median {statistics.median(ms):9.3f} ms   min {min(ms):9.3f}   max {max(ms):9.3f}   (n = {len(ms)})"
+
+
+def measure(name, v, f, reps, lines):
+    import torch
+    dev = torch.device("cuda", 0)
+    v = np.ascontiguousarray(v, np.float32)
+    ext = np.float32((v.max(0) - v.min(0)).max())
+    M = rt.default_bvh_transform()
+    t = {k: [] for k in ("dev_rebuild", "wall_rebuild", "dev_refit", "wall_refit")}
+    with rt.Renderer() as b:
+        b.mesh_upload(v, f)
+        stream = torch.cuda.ExternalStream(b.stream(), device=dev)
+        delta = torch.from_numpy(step_delta(v, ext, 0) * np.float32(0.1)).to(dev)
+        torch.cuda.synchronize()
+
+        def timed(call, what, keep):
+            b.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record(stream)
+            call(M)
+            e1.record(stream)
+            b.synchronize()
+            t1 = time.perf_counter()
+            if keep:
+                t["wall_" + what].append((t1 - t0) * 1e3); t["dev_" + what].append(e0.elapsed_time(e1))
+
+        for k in range(-3, reps):       # k < 0: warm-up (code objects, rocPRIM's kernels)
+            with torch.cuda.stream(stream):
+                b.mesh_positions().add_(delta if k % 2 else -delta)
+            timed(b.mesh_rebuild, "rebuild", k >= 0)
+            timed(b.mesh_refit, "refit", k >= 0)
+        mi, si = b.mesh_info(), b.scene_info()
+        total, _ = b.mesh_refit_count()
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    lines.append(f"{name}: {np.asarray(f).size // 3} triangles, {si.nNodes} nodes, {si.treeDepth} levels; quantised any-hit form "
+                 f"{'in use (one host wait per call)' if mi.hostSyncs else 'not in use (no host wait)'}")
+    lines.append(fmt("rt_mesh_rebuild, device (events on the library stream)", t["dev_rebuild"]))
+    lines.append(fmt("rt_mesh_refit,   device (events on the library stream)", t["dev_refit"]))
+    lines.append(fmt("rt_mesh_rebuild, wall (call .. rt_synchronize)", t["wall_rebuild"]))
+    lines.append(fmt("rt_mesh_refit,   wall (call .. rt_synchronize)", t["wall_refit"]))
+    dr, df = statistics.median(t["dev_rebuild"]), statistics.median(t["dev_refit"])
+    wr, wf = statistics.median(t["wall_rebuild"]), statistics.median(t["wall_refit"])
+    ok = df < dr and max(t["dev_refit"]) < min(t["dev_rebuild"])
+    lines.append(f"  rebuild / refit: device {dr / df:.1f}x   wall {wr / wf:.1f}x      RtMeshInfo: rebuilds {mi.rebuilds}, refits {total}, allocations "
+                 f"{mi.allocations} (all in rt_mesh_upload), hostSyncs {mi.hostSyncs}")
+    lines.append(f"  condition (refit median < rebuild median, refit max {max(t['dev_refit']):.3f} < rebuild min {min(t['dev_rebuild']):.3f}, device): "
+                 f"{'MET' if ok else 'MISSED'}")
+    lines.append("")
+    return ok
+
+
+def frame_cost(lines, steps=(1, 8, 32), frames=48, batch=8):
+    """ms per frame of the bench view on a refitted tree against a rebuilt one over the same positions."""
+    import torch
+    dev = torch.device("cuda", 0)
+    v, f = rt.meshgen.bunny_standin(6)
+    v = np.ascontiguousarray(v, np.float32)
+    ext = np.float32((v.max(0) - v.min(0)).max())
+    M = rt.default_bvh_transform()
+    W, H = 1920, 1080
+    p = rt.default_render_params()
+    p.sppPerFrame = 4
+    cam = scenes.camera("closeup", aspect=W / H)
+    L = rt.bvh_layout(np.asarray(f).size // 3)
+    us = [rt.frame_uniforms(p, cam, W, H, k, True, L.nNodes, L.nTris) for k in range(frames + batch)]
+
+    def ms_per_frame(r):
+        # warm-up: after a change of scene the frames re-learn their share of bounce hits and re-size their ray arenas (device-wide waits and
+        # allocations of gigabytes, tens of ms per frame while it lasts); four batches let that finish.  Then the better of two timed passes.
+        for _ in range(4):
+            r.render_frames(us[:batch])
+        r.synchronize()
+        best = None
+        for _ in range(2):
+            t0 = time.perf_counter()
+            for k in range(batch, batch + frames, batch):
+                r.render_frames(us[k:k + batch])
+            r.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / frames
+            best = ms if best is None else min(best, ms)
+        return best
+
+    lines.append(f"frames on a refitted tree (informational): bench view {W}x{H}, {p.sppPerFrame} spp, {frames} frames in batches of {batch} after 32 of warm-up, wall / frame, better of two passes")
+    with rt.Renderer() as b, rt.Renderer() as c:     # b is refitted step by step, c is rebuilt over the same positions; both made and warmed up first
+        for r in (b, c):
+            r.upload_env(scenes.env_faces("Sky_01"))
+            r.resize(W, H)
+            r.mesh_upload(v, f)
+            r.mesh_rebuild(M)
+        stream = torch.cuda.ExternalStream(b.stream(), device=dev)
+        lines.append(f"  undeformed mesh, rebuilt: context b {ms_per_frame(b):8.3f} ms   context c {ms_per_frame(c):8.3f} ms")
+        pos, done = v, 0
+        for n in steps:
+            for k in range(done, n):     # refit steps on top of the first rebuild's tree
+                d = step_delta(pos, ext, k)
+                pos = (pos + d).astype(np.float32)
+                dd = torch.from_numpy(d).to(dev)
+                torch.cuda.current_stream(dev).synchronize()
+                with torch.cuda.stream(stream):
+                    b.mesh_positions().add_(dd)
+                torch.cuda.current_stream(dev).wait_stream(stream)
+                b.mesh_refit(M)
+            done = n
+            c.mesh_set_positions(pos)
+            c.mesh_rebuild(M)
+            refitted, rebuilt = ms_per_frame(b), ms_per_frame(c)
+            lines.append(f"  after {n:2d} refit steps: refitted tree {refitted:8.3f} ms   rebuilt {rebuilt:8.3f} ms   ratio {refitted / rebuilt:.3f}")
+        for frac in (0.02, 0.1):         # and where a refit does cost: every vertex displaced at random, neighbours torn apart
+            noisy = (pos + np.random.default_rng(1).normal(0, frac * ext, pos.shape)).astype(np.float32)
+            for r, update in ((b, b.mesh_refit), (c, c.mesh_rebuild)):
+                r.mesh_set_positions(noisy)
+                update(M)
+            refitted, rebuilt = ms_per_frame(b), ms_per_frame(c)
+            lines.append(f"  random displacement, sigma {frac:4.2f} of the extent: refitted tree {refitted:8.3f} ms   rebuilt {rebuilt:8.3f} ms   ratio {refitted / rebuilt:.3f}")
+    lines.append("")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=12)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", default="bunny,1m")
+    ap.add_argument("--no-frames", action="store_true")
+    args = ap.parse_args()
+    lines = [f"mesh_refit_time.py --reps {args.reps}: rebuild and refit alternated on one context, one process", ""]
+    ok = True
+    for s in [x for x in args.sizes.split(",") if x and x != "none"]:
+        v, f = rt.meshgen.bunny_standin(6) if s == "bunny" else rt.meshgen.million_triangle_scene()
+        ok = measure("bench mesh" if s == "bunny" else "1 M scene", v, f, max(args.reps, 1), lines) and ok
+    if not args.no_frames:
+        frame_cost(lines)
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write(text + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

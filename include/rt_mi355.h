@@ -144,8 +144,12 @@ int rt_upload_bvh(RtContext *ctx, const float *nodes12, int nNodes, const float 
  * `channels` (3 or 4) bytes, rows in upload order.  faces == NULL installs the 1x1 dummy
  * (128,128,255) of cubemap.cpp:13. */
 /* The same builder as rt_build_bvh (below), run on the context's GPU: identical node numbering, ranges and boxes and the same
- * set of triangles in every leaf whenever no two triangles tie at a median; the order of triangles INSIDE a leaf differs
- * (the reference's std::nth_element leaves it unspecified), so rt_build_bvh remains the bit-parity path and this the fast one.
+ * set of triangles in every leaf whenever no two triangles tie at a median.  Unlike rt_build_bvh, whose std::nth_element leaves
+ * tied ranges and the order inside a leaf to the library, this builder is fully specified ("the tie rule"): level
+ * by level, from input order, every inner range is sorted STABLY by the sortable key of the centroid along its axis, so triangles
+ * with bit-equal keys keep the order they had and the order of the rows inside every leaf is defined; boxes are reduced in the
+ * keys' order, in which -0 lies below +0.  tests/bvh_build_ref.py restates it in numpy and the device is compared with it bit
+ * for bit.  rt_build_bvh remains the path that is bit-equal to the reference's own build; this is the fast one.
  * Returns the number of nodes (or a negative RtStatus); nodes12 needs room for 2*nTris nodes. */
 int rt_build_bvh_gpu(RtContext *ctx, const float *tris9, int nTris, float *nodes12, float *tris12);
 

@@ -771,7 +771,8 @@ class Renderer:
         return out
 
     def build_bvh_gpu(self, tris9):
-        """Median-split BVH built on this context's GPU -> (nodes12, tris12); same tree as build_bvh, leaf-internal order may differ."""
+        """Median-split BVH built on this context's GPU -> (nodes12, tris12); build_bvh's tree wherever no median ties, and fully specified where
+        one does: a stable sort per level from input order, which also fixes the order of the rows inside a leaf."""
         t = _f32(tris9).reshape(-1, 9)
         n = t.shape[0]
         nodes = np.zeros((max(2 * n, 1), 12), np.float32)

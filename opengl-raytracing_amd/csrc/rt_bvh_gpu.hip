@@ -10,9 +10,14 @@
 //   * the partition about the median centroid (:75-80).  The reference uses std::nth_element; here every range is SORTED by
 //     the same key (one global radix sort per level on (node rank, centroid[axis]) pairs).  The lower half holds the same
 //     triangles whenever the median key is unique, so nodes, boxes and the set of triangles of every leaf are then identical
-//     to the CPU build's; only the order of triangles inside a leaf differs (nth_element's arrangement is unspecified), which
+//     to the CPU build's; the order of triangles inside a leaf differs from it (nth_element's arrangement is unspecified), which
 //     can change the winner of an exact-t tie between two triangles of one leaf, nothing else.  rt_build_bvh stays the
 //     parity path; this is the fast one (1 M triangles: ~0.9 s on the host).
+// THE TIE RULE (restated in tests/bvh_build_ref.py and compared bit for bit).  This builder is deterministic, ties
+// included: level 0 starts from input order (k_iota); each level is ONE STABLE radix sort on (start of the item's range, sortable key
+// of its centroid along the range's axis), applied to the permutation the level above left; items of leaves keep their place.  Items
+// with bit-equal keys therefore keep their order, the lower half of a tied median takes the earlier ones, and the order of the rows
+// inside a leaf is specified.  Boxes are min / max in the keys' order, in which -0 lies below +0; equal extents fall to the later axis.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>

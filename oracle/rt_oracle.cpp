@@ -55,7 +55,7 @@ static std::atomic<int> g_envFilter{0};
 static const int MAT_MESH = 5;      // no material of rt_materials.glsl:20-24 -> getMaterial's default branch (:123-124): 0.8 grey, spec 0.2, gloss 16, diffuse
 
 // ---------------------------------------------------------------- rt_common.glsl
-struct Hit { float t; vec3 p; vec3 n; int mat; };                       // :39-44
+struct Hit { float t; vec3 p; vec3 n; int mat; int prim; };             // :39-44; prim (not in the shader): the row of the winning triangle, traceBVH only
 
 static inline uint32_t hash2(uint32_t vx, uint32_t vy) {                // :57-63
     vx = vx * 1664525u + 1013904223u;
@@ -307,6 +307,7 @@ static bool traceBVH(const Scene &S, Counters &C, vec3 ro, vec3 rd, Hit &hitOut)
                     hitOut.p = ro + rd * t;
                     hitOut.n = n;
                     hitOut.mat = 1;
+                    hitOut.prim = N.first + i;
                 }
             }
         } else {
@@ -830,6 +831,14 @@ int orc_trace_bvh(const OrcUniforms *u, const float *nodes, const float *tris, c
     if (hit) { *tOut = h.t; pOut[0] = h.p.x; pOut[1] = h.p.y; pOut[2] = h.p.z; nOut[0] = h.n.x; nOut[1] = h.n.y; nOut[2] = h.n.z; }
     if (c) { c->nodeFetch = C.nodeFetch; c->triFetch = C.triFetch; c->raysClosest = C.raysClosest; }
     return hit ? 1 : 0;
+}
+// traceBVH with the row of the triangle that won (ties at equal t overwrite, so it is the last such triangle in visit order); -1 on a miss
+int orc_trace_bvh_prim(const OrcUniforms *u, const float *nodes, const float *tris, const float *ro, const float *rd, float *tOut) {
+    Scene S; S.u = *u; S.nodes = nodes; S.tris = tris;
+    Counters C; Hit h; h.p = v3(0.0f); h.prim = -1;
+    if (!traceBVH(S, C, ld3(ro), ld3(rd), h)) return -1;
+    *tOut = h.t;
+    return h.prim;
 }
 // aabbHit (rt_bvh.glsl:124-134) and triHit (:154-170) on their own, for the per-function vectors in tests/golden/glsl_bvh_kat.npz.
 // out4 = {hit, tmin, tmax, 0};  out8 = {hit, t, n.x, n.y, n.z} (t, n only written on a hit, as in the shader).

@@ -270,6 +270,16 @@ def trace_bvh(u, nodes12, tris12, ro, rd):
     return bool(hit), tt.value, p, nn, cnt
 
 
+def trace_bvh_prim(u, nodes12, tris12, ro, rd):
+    """traceBVH -> (prim, t): the row of tris12 that won (the last triangle at the closest t in visit order), -1 and uINF on a miss."""
+    f = lib().orc_trace_bvh_prim
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(rt.RtUniforms), _FP, _FP, _FP, _FP, C.POINTER(C.c_float)]
+    tt = C.c_float(u.inf)
+    prim = f(C.byref(u), _fp(_f32(nodes12)), _fp(_f32(tris12)), _fp(_f32(ro)), _fp(_f32(rd)), C.byref(tt))
+    return prim, np.float32(tt.value)
+
+
 def trace_bvh_shadow(u, nodes12, tris12, ro, rd, tmax):
     n, t = _f32(nodes12), _f32(tris12)
     ro, rd = _f32(ro), _f32(rd)

@@ -542,6 +542,41 @@ int rt_mesh_refit_count(RtContext *ctx, uint64_t *total, uint64_t *sinceRebuild)
  * rebuild. */
 int rt_mesh_order(RtContext *ctx, int32_t *order);
 int rt_mesh_order_device(RtContext *ctx, void **devPtr, size_t *bytes);
+/* ---- parts: a mesh is a list of parts, each with its own model matrix on the device; a hit maps back to (part, triangle of the part).
+ * A part is a contiguous run of index triples: partFirst has nParts + 1 entries in triangle units, partFirst[0] == 0, partFirst[nParts] == nIdx / 3,
+ * non-decreasing.  Empty parts are legal anywhere and their matrices are ignored.  Parts share the one position pool: a vertex used by several parts is
+ * transformed once per use, under each part's matrix.  1 <= nParts <= RT_MAX_MESH_PARTS.  rt_mesh_upload makes a mesh of one part, and
+ * rt_mesh_rebuild(ctx, M) / rt_mesh_refit(ctx, M) keep their meaning -- one M for every triangle -- on any mesh; they neither read nor write the table. */
+#define RT_MAX_MESH_PARTS 65535
+/* rt_mesh_upload with a part table: RT_ERR_INVALID, with a message, for a broken partFirst, a part count out of range or a null table, besides
+ * rt_mesh_upload's own causes (and its RT_ERR_UNSUPPORTED ones).  Allocates, besides what rt_mesh_upload allocates, the parts table, the per-triangle
+ * part lookup and the matrix table (RtMeshInfo.allocations counts them), and sets every matrix to the identity.  nIdx == 0 releases the mesh. */
+int rt_mesh_upload_parts(RtContext *ctx, const float *positions, int nVerts, const uint32_t *indices, int nIdx,
+                         const int32_t *partFirst, int nParts);
+/* *nParts = the part count of the current mesh; the nParts + 1 boundaries are copied when partFirst != NULL and capacity >= nParts + 1 (partFirst ==
+ * NULL asks for the count only; a smaller capacity: RT_ERR_INVALID).  RT_ERR_INVALID without a mesh. */
+int rt_mesh_parts(RtContext *ctx, int32_t *partFirst, int capacity, int *nParts);
+/* The matrix table: nParts x 16 float32 on the device, column-major, for a caller that writes matrices on the device; writes must be ordered on
+ * rt_stream()'s stream, exactly as for rt_mesh_positions.  rt_mesh_set_part_matrices: `count` matrices from host memory into entries first .., copied on
+ * that stream as rt_mesh_set_positions copies positions; a range outside the table: RT_ERR_INVALID. */
+int rt_mesh_part_matrices(RtContext *ctx, void **devPtr, size_t *bytes);
+int rt_mesh_set_part_matrices(RtContext *ctx, int first, int count, const float *M16s);
+/* rt_mesh_rebuild / rt_mesh_refit with the gather of rt_gather_triangles_parts under the matrices that are in the table when the call's work runs on
+ * the stream.  Contracts: after the rebuild the scene is, byte for byte in every device array and in RtSceneInfo, what rt_gather_triangles_parts ->
+ * rt_build_bvh_gpu -> rt_upload_bvh installs in a fresh context; after the refit, what rt_upload_bvh installs from
+ * rt_refit_bvh(rt_gather_triangles_parts(...), order, nodes12, tris12) with route A's arrays of the last rebuild and rt_mesh_order's order.  Everything
+ * else is the single-matrix calls': the same ordering by events, no allocation, no host wait but the status-word read of the quantised form
+ * (RtMeshInfo.hostSyncs), accumulation and bounce-share prediction kept, RtMeshInfo.rebuilds and rt_mesh_refit_count count them, the same RT_ERR_INVALID
+ * cases.  The four update calls may be mixed freely; a refit keeps the tree of the most recent rebuild of either kind. */
+int rt_mesh_rebuild_parts(RtContext *ctx);
+int rt_mesh_refit_parts(RtContext *ctx);
+/* Hit -> part, on the device: for hit i of n RtHit records (rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels), parts[i] = the part whose range holds
+ * t = order[prim] (rt_mesh_order's order) and tris[i] = t - partFirst[parts[i]]; a prim outside [0, nTris) -- a miss, an analytic hit, a stale value --
+ * gives parts[i] = tris[i] = -1 and reads nothing out of bounds.  Device pointers; either output may be NULL, not both.  Enqueued on rt_stream()'s
+ * stream: no host wait, no allocation; the order array is derived on first use after a rebuild, as by rt_mesh_order_device.  RT_ERR_INVALID before the
+ * first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
+int rt_mesh_hit_parts(RtContext *ctx, const RtHit *hits, int n, int32_t *parts, int32_t *tris);
+int rt_mesh_hit_parts_host(RtContext *ctx, const RtHit *hits, int n, int32_t *parts, int32_t *tris);
 /* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
@@ -574,6 +609,13 @@ void rt_make_uniforms(const RtRenderParams *p, const RtCamera *cam, const float 
 int rt_gather_triangles(const float *positions, const uint32_t *indices, int nIdx, const float *M16, float *outTris9);
 /* the same with the vertex count: RT_ERR_INVALID if any index is out of range (use this one for data read from files) */
 int rt_gather_triangles_checked(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const float *M16, float *outTris9);
+
+/* The gather of a mesh of parts (see rt_mesh_upload_parts for partFirst), and the definition rt_mesh_rebuild_parts / rt_mesh_refit_parts are tested
+ * against: triangle i of part p is what rt_gather_triangles_checked computes under M16s + 16 * p, so the output is the concatenation of per-part
+ * rt_gather_triangles_checked calls, bit for bit.  M16s == NULL: the identity for every part.  RT_ERR_INVALID for rt_gather_triangles_checked's
+ * causes, nIdx % 3 != 0, a null or broken partFirst or nParts outside 1 .. RT_MAX_MESH_PARTS.  Returns the triangle count. */
+int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, const float *M16s,
+                              float *outTris9);
 
 /* build_bvh (include/scene/bvh.h:102, src/scene/bvh.cpp:94-137) + the packing half of upload_bvh_tbo
  * (:147-204).  nodes12 needs room for 2*nTris*12 floats, tris12 for nTris*12.  Returns the node count. */

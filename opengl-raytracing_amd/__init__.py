@@ -190,6 +190,7 @@ class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
 
 
 RT_MAX_RASTER_MESHES = 8
+RT_MAX_MESH_PARTS = 65535   # rt_mesh_upload_parts
 RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
 
 
@@ -300,6 +301,14 @@ SIGNATURES = {
     "rt_mesh_refit_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rt_mesh_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_mesh_order_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_upload_parts": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "rt_mesh_parts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "rt_mesh_part_matrices": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_part_matrices": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _FP]),
+    "rt_mesh_rebuild_parts": (C.c_int, [C.c_void_p]),
+    "rt_mesh_refit_parts": (C.c_int, [C.c_void_p]),
+    "rt_mesh_hit_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_mesh_hit_parts_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
     "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
@@ -313,6 +322,7 @@ SIGNATURES = {
     "rt_make_uniforms": (None, [C.POINTER(RtRenderParams), C.POINTER(RtCamera), _FP, _FP, _FP] + [C.c_int] * 9 + [C.POINTER(RtUniforms)]),
     "rt_gather_triangles": (C.c_int, [_FP, _U32P, C.c_int, _FP, _FP]),
     "rt_gather_triangles_checked": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, _FP, _FP]),
+    "rt_gather_triangles_parts": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, C.POINTER(C.c_int32), C.c_int, _FP, _FP]),
     "rt_build_bvh": (C.c_int, [_FP, C.c_int, _FP, _FP]),
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
@@ -487,6 +497,23 @@ def gather_triangles(positions, indices, model=None) -> np.ndarray:
     n = lib().rt_gather_triangles_checked(_fp(pos), pos.size // 3, idx.ctypes.data_as(_U32P), idx.size, _fp(m), _fp(out))
     if n < 0:
         raise RtError(n, "rt_gather_triangles: index out of range" if n == RT_ERR_INVALID else "rt_gather_triangles")
+    return out[:n]
+
+
+def gather_triangles_parts(positions, indices, part_first, models=None) -> np.ndarray:
+    """The gather of a mesh of parts (rt_gather_triangles_parts): triangle i of part p under models[p] ([nParts,16] column-major; None: the identity
+    for every part) -> [nTris,9].  The host definition mesh_rebuild_parts / mesh_refit_parts are tested against."""
+    pos = _f32(positions).reshape(-1)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    pf = np.ascontiguousarray(part_first, dtype=np.int32).reshape(-1)
+    m = None if models is None else _f32(models).reshape(-1)
+    if m is not None and m.size != 16 * (pf.size - 1):
+        raise RtError(RT_ERR_INVALID, f"gather_triangles_parts: {m.size} floats for {pf.size - 1} matrices")
+    out = np.zeros((max(idx.size // 3, 1), 9), np.float32)
+    n = lib().rt_gather_triangles_parts(_fp(pos), pos.size // 3, idx.ctypes.data_as(_U32P), idx.size, pf.ctypes.data_as(C.POINTER(C.c_int32)), pf.size - 1,
+                                        None if m is None else _fp(m), _fp(out))
+    if n < 0:
+        raise RtError(n, "rt_gather_triangles_parts: an index out of range, indices that are no triangle list or a broken part table")
     return out[:n]
 
 
@@ -754,6 +781,94 @@ class Renderer:
         class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
             __cuda_array_interface__ = {"shape": (nt,), "typestr": "<i4", "data": (ptr.value, False), "version": 2, "strides": None}
         return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    # ---- parts: one model matrix per part, on the device, and hit -> (part, triangle of the part)
+    def mesh_upload_parts(self, positions, indices, part_first):
+        """mesh_upload for a mesh of parts (rt_mesh_upload_parts): part_first holds nParts + 1 boundaries in triangle units, from 0 to the triangle
+        count, non-decreasing; empty parts are legal.  Every part's matrix starts as the identity."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        v = _f32(positions).reshape(-1, 3)
+        pf = np.ascontiguousarray(part_first, dtype=np.int32).reshape(-1)
+        self._check(lib().rt_mesh_upload_parts(self._h, _fp(v), v.shape[0], idx.ctypes.data_as(_U32P), idx.size, pf.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               pf.size - 1))
+        self.n_nodes = self.n_tris = 0
+        self._mesh_verts = v.shape[0] if idx.size else 0
+
+    def mesh_parts(self) -> np.ndarray:
+        """The part_first array of the current mesh (int32, nParts + 1 entries); [0, nTris] after mesh_upload."""
+        n = C.c_int()
+        self._check(lib().rt_mesh_parts(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value + 1, np.int32)
+        self._check(lib().rt_mesh_parts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size, C.byref(n)))
+        return out
+
+    def mesh_part_matrices(self, as_torch=None):
+        """The device table of model matrices, one per part, column-major.  With torch (as_torch=None: when it imports) a float32 [nParts,16] tensor
+        that aliases it, zero-copy; writes to it must be ordered on stream(), as for mesh_positions.  Else (pointer, bytes)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_part_matrices(self._h, C.byref(ptr), C.byref(n)))
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        if not as_torch:
+            return ptr.value, n.value
+        import torch
+        nparts = n.value // 64
+
+        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+            __cuda_array_interface__ = {"shape": (nparts, 16), "typestr": "<f4", "data": (ptr.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    def mesh_set_part_matrices(self, models, first=0):
+        """Matrices [count,16] (or [count,4,4] as default_bvh_transform lays one out: column-major) from host memory into entries first .. of the
+        table, copied on stream() (rt_mesh_set_part_matrices)."""
+        m = _f32(models)
+        if m.size % 16:
+            raise RtError(RT_ERR_INVALID, "mesh_set_part_matrices: models must hold 16 floats per matrix")
+        m = m.reshape(-1, 16)
+        self._check(lib().rt_mesh_set_part_matrices(self._h, int(first), m.shape[0], _fp(m)))   # pageable memory: staged before the call returns
+
+    def mesh_rebuild_parts(self):
+        """mesh_rebuild with every part gathered under its own matrix of the device table (rt_mesh_rebuild_parts)."""
+        self._check(lib().rt_mesh_rebuild_parts(self._h))
+        i = self.scene_info()
+        self.n_nodes, self.n_tris = i.nNodes, i.nTris
+
+    def mesh_refit_parts(self):
+        """mesh_refit with every part gathered under its own matrix of the device table (rt_mesh_refit_parts)."""
+        self._check(lib().rt_mesh_refit_parts(self._h))
+
+    def mesh_hit_parts(self, hits):
+        """Closest-hit answers -> (parts, tris): int32 [N] each, the part a hit's triangle belongs to and the triangle's index within the part;
+        (-1, -1) for a miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in,
+        numpy out (rt_mesh_hit_parts_host: synchronises); a torch tensor on this context's device takes the zero-copy path of trace_rays: enqueued
+        on the library stream, ordered against torch's current stream, no host wait."""
+        rec = hits.record if isinstance(hits, RayHits) else hits
+        if isinstance(rec, np.ndarray):
+            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+                raise RtError(RT_ERR_INVALID, f"mesh_hit_parts: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+            rec = np.ascontiguousarray(rec)
+            n = rec.shape[0]
+            parts, tris = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            self._check(lib().rt_mesh_hit_parts_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(parts.ctypes.data), C.c_void_p(tris.ctypes.data)))
+            return parts, tris
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+            raise RtError(RT_ERR_INVALID, f"mesh_hit_parts: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+        rec = rec.contiguous()
+        n = rec.shape[0]
+        parts = torch.empty(n, dtype=torch.int32, device=dev)
+        tris = torch.empty(n, dtype=torch.int32, device=dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the records (and the outputs' allocation) are ready before the map starts
+        self._check(lib().rt_mesh_hit_parts(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(parts.data_ptr()), C.c_void_p(tris.data_ptr())))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        return parts, tris
 
     def mesh_info(self) -> RtMeshInfo:
         i = RtMeshInfo()

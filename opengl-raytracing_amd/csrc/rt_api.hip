@@ -68,6 +68,8 @@ struct RtContext {
     bool sceneFromMesh = false;
     float *dRootBox = nullptr;       // sceneFromMesh: node 0's box on the device -- the host does not know it (rootMin / rootMax above are not used then)
     hipEvent_t evMeshLane[RT_MAX_LANES] = {}, evMeshDone = nullptr;   // a rebuild waits for every lane / every lane waits for the rebuild
+    hipEvent_t evMeshOrder = nullptr;      // the order array of the current tree has been written, on meshOrderStream
+    hipStream_t meshOrderStream = nullptr;
     uint64_t meshRebuilds = 0, meshHostSyncs = 0, meshRefits = 0, meshRefitsSinceRebuild = 0;
     // frame state
     FrameGeom g{};
@@ -341,6 +343,8 @@ void release_mesh(RtContext *c) {
     for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->evMeshLane[i]) (void)hipEventDestroy(c->evMeshLane[i]); c->evMeshLane[i] = nullptr; }
     if (c->evMeshDone) (void)hipEventDestroy(c->evMeshDone);
     c->evMeshDone = nullptr;
+    if (c->evMeshOrder) (void)hipEventDestroy(c->evMeshOrder);
+    c->evMeshOrder = nullptr; c->meshOrderStream = nullptr;
 }
 
 int last_lane(const RtContext *c) { return (c->writeIdx + c->nLanes - 1) % c->nLanes; }   // lane of the frame rendered last
@@ -1168,33 +1172,85 @@ int rt_bvh_layout(int nTris, RtBvhLayout *out) {
     });
 }
 
-int rt_mesh_upload(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx) {
+// rt_mesh_upload (partFirst == null: one part holding everything) and rt_mesh_upload_parts
+static int mesh_upload(RtContext *c, const char *who, const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts) {
     if (!c) return RT_ERR_INVALID;
-    if (nIdx < 0 || nVerts < 0 || (nIdx > 0 && (!positions || !indices || nVerts == 0))) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: bad arguments");
-    if (nIdx % 3 != 0) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: %d indices are not a list of triangles", nIdx);
+    if (nIdx < 0 || nVerts < 0 || (nIdx > 0 && (!positions || !indices || nVerts == 0))) return fail(c, RT_ERR_INVALID, "%s: bad arguments", who);
+    if (nIdx % 3 != 0) return fail(c, RT_ERR_INVALID, "%s: %d indices are not a list of triangles", who, nIdx);
     for (int k = 0; k < nIdx; ++k)
-        if (indices[k] >= (uint32_t)nVerts) return fail(c, RT_ERR_INVALID, "rt_mesh_upload: index %d names vertex %u of %d", k, indices[k], nVerts);
+        if (indices[k] >= (uint32_t)nVerts) return fail(c, RT_ERR_INVALID, "%s: index %d names vertex %u of %d", who, k, indices[k], nVerts);
+    const int32_t one[2] = {0, nIdx / 3};
+    if (!partFirst) { partFirst = one; nParts = 1; }
+    if (nParts < 1 || nParts > RT_MAX_MESH_PARTS) return fail(c, RT_ERR_INVALID, "%s: %d parts (1 .. %d)", who, nParts, RT_MAX_MESH_PARTS);
+    if (partFirst[0] != 0 || partFirst[nParts] != nIdx / 3)
+        return fail(c, RT_ERR_INVALID, "%s: partFirst runs from %d to %d, the mesh from 0 to %d triangles", who, partFirst[0], partFirst[nParts], nIdx / 3);
+    for (int p = 0; p < nParts; ++p)
+        if (partFirst[p + 1] < partFirst[p]) return fail(c, RT_ERR_INVALID, "%s: partFirst decreases at part %d (%d after %d)", who, p, partFirst[p + 1], partFirst[p]);
     if (nIdx > 0) {
-        if (getenv("RT_FUSED") && atoi(getenv("RT_FUSED")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: RT_FUSED records are not rebuilt on the device");
-        if (getenv("RT_IMPLICIT") && atoi(getenv("RT_IMPLICIT")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: RT_IMPLICIT records are not rebuilt on the device");
-        if (getenv("RT_ANYHIT_TREE") && std::string(getenv("RT_ANYHIT_TREE")) == "sah") return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device");
-        if (nIdx / 3 >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "rt_mesh_upload: %d triangles exceed the 2^28 leaf encoding", nIdx / 3);
+        if (getenv("RT_FUSED") && atoi(getenv("RT_FUSED")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_FUSED records are not rebuilt on the device", who);
+        if (getenv("RT_IMPLICIT") && atoi(getenv("RT_IMPLICIT")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_IMPLICIT records are not rebuilt on the device", who);
+        if (getenv("RT_ANYHIT_TREE") && std::string(getenv("RT_ANYHIT_TREE")) == "sah") return fail(c, RT_ERR_UNSUPPORTED, "%s: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device", who);
+        if (nIdx / 3 >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "%s: %d triangles exceed the 2^28 leaf encoding", who, nIdx / 3);
     }
     const int rc = rt_upload_bvh(c, nullptr, 0, nullptr, 0);   // waits for the lanes, removes the scene and the previous mesh, forgets the bounce share
     if (rc != RT_OK || nIdx == 0) return rc;
-    return guarded(c, "rt_mesh_upload", [&]() -> int {
+    return guarded(c, who, [&]() -> int {
         rtl::BvhLayout L;
         const int lr = rtl::bvh_layout(nIdx / 3, L);
-        if (lr != RT_OK) return fail(c, lr, "rt_mesh_upload: %d triangles cannot be laid out", nIdx / 3);
+        if (lr != RT_OK) return fail(c, lr, "%s: %d triangles cannot be laid out", who, nIdx / 3);
         const char *err = nullptr;
-        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, want_quantised(L.nWide4, L.rootRef4), &c->mesh, &err);
-        if (mr != RT_OK) { c->mesh = nullptr; return fail(c, mr, "rt_mesh_upload: %s", err ? err : "layout failed"); }
+        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, partFirst, nParts, want_quantised(L.nWide4, L.rootRef4), &c->mesh, &err);
+        if (mr != RT_OK) { c->mesh = nullptr; return fail(c, mr, "%s: %s", who, err ? err : "layout failed"); }
         bool ok = hipEventCreateWithFlags(&c->evMeshDone, hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&c->evMeshOrder, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; ok && i < c->nLanes; ++i) ok = hipEventCreateWithFlags(&c->evMeshLane[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "rt_mesh_upload: event creation failed"); }
+        if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "%s: event creation failed", who); }
         c->meshRebuilds = c->meshHostSyncs = c->meshRefits = c->meshRefitsSinceRebuild = 0;
         return RT_OK;
     });
+}
+
+int rt_mesh_upload(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx) {
+    return mesh_upload(c, "rt_mesh_upload", positions, nVerts, indices, nIdx, nullptr, 1);
+}
+
+int rt_mesh_upload_parts(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts) {
+    if (!c) return RT_ERR_INVALID;
+    if (!partFirst) return fail(c, RT_ERR_INVALID, "rt_mesh_upload_parts: null partFirst");
+    return mesh_upload(c, "rt_mesh_upload_parts", positions, nVerts, indices, nIdx, partFirst, nParts);
+}
+
+int rt_mesh_parts(RtContext *c, int32_t *partFirst, int capacity, int *nParts) {
+    if (!c || !nParts) return RT_ERR_INVALID;
+    *nParts = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_parts: no mesh (rt_mesh_upload first)");
+    const int n = rtl::mesh_part_count(c->mesh);
+    *nParts = n;
+    if (!partFirst) return RT_OK;
+    if (capacity < n + 1) return fail(c, RT_ERR_INVALID, "rt_mesh_parts: room for %d entries, the table has %d", capacity, n + 1);
+    std::memcpy(partFirst, rtl::mesh_part_first(c->mesh), (size_t)(n + 1) * sizeof(int32_t));
+    return RT_OK;
+}
+
+int rt_mesh_part_matrices(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_part_matrices: no mesh (rt_mesh_upload first)");
+    *devPtr = rtl::mesh_part_matrices(c->mesh);
+    *bytes = (size_t)rtl::mesh_part_count(c->mesh) * 64;
+    return RT_OK;
+}
+
+int rt_mesh_set_part_matrices(RtContext *c, int first, int count, const float *M16s) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: no mesh (rt_mesh_upload first)");
+    const int n = rtl::mesh_part_count(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: entries %d .. %d of a table of %d", first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!M16s) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: null matrices");
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_part_matrices(c->mesh) + (size_t)first * 16, M16s, (size_t)count * 64, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
+    return RT_OK;
 }
 
 int rt_mesh_positions(RtContext *c, void **devPtr, size_t *bytes) {
@@ -1215,11 +1271,12 @@ int rt_mesh_set_positions(RtContext *c, const float *positions) {
 
 // A rebuild or a refit: the device work of rt_mesh.hip between the two halves of the event scheme, then the scene installed (the same pointers and
 // counts every time; what a refit can change is whether the quantised nodes could be built).
-static int mesh_update(RtContext *c, const float *M16, bool refit) {
-    const char *who = refit ? "rt_mesh_refit" : "rt_mesh_rebuild";
+// parts: gather under the device matrix table instead of under M16.
+static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = false) {
+    const char *who = parts ? (refit ? "rt_mesh_refit_parts" : "rt_mesh_rebuild_parts") : (refit ? "rt_mesh_refit" : "rt_mesh_rebuild");
     if (!c) return RT_ERR_INVALID;
     if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", who);
-    if (refit && !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_refit: no tree to keep (rt_mesh_rebuild first)");
+    if (refit && !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree to keep (rt_mesh_rebuild first)", who);
     (void)hipSetDevice(c->cfg.device);
     static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
@@ -1230,7 +1287,8 @@ static int mesh_update(RtContext *c, const float *M16, bool refit) {
         HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
     }
     const char *err = nullptr;
-    int rc = refit ? rtl::mesh_refit(c->mesh, st, M16 ? M16 : kIdentity, &err) : rtl::mesh_rebuild(c->mesh, st, M16 ? M16 : kIdentity, &err);
+    const float *gatherM = parts ? nullptr : (M16 ? M16 : kIdentity);   // null: the part-aware gather
+    int rc = refit ? rtl::mesh_refit(c->mesh, st, gatherM, &err) : rtl::mesh_rebuild(c->mesh, st, gatherM, &err);
     if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
     // ... and whatever a lane is given next waits for it
     HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
@@ -1262,6 +1320,8 @@ static int mesh_update(RtContext *c, const float *M16, bool refit) {
 
 int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16, false); }
 int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
+int rt_mesh_rebuild_parts(RtContext *c) { return mesh_update(c, nullptr, false, true); }
+int rt_mesh_refit_parts(RtContext *c) { return mesh_update(c, nullptr, true, true); }
 
 int rt_mesh_refit_count(RtContext *c, uint64_t *total, uint64_t *sinceRebuild) {
     if (!c || (!total && !sinceRebuild)) return RT_ERR_INVALID;
@@ -1270,18 +1330,69 @@ int rt_mesh_refit_count(RtContext *c, uint64_t *total, uint64_t *sinceRebuild) {
     return RT_OK;
 }
 
+// The order array of the current tree, readable on `st`: derived there at the first call after a rebuild; a later reader on another stream (frames rotate
+// rt_stream() through the lanes) waits for that launch by an event.
+static int mesh_order_on(RtContext *c, hipStream_t st, const char *who, const int **order) {
+    const char *err = nullptr;
+    const bool written = rtl::mesh_order_written(c->mesh);
+    const int rc = rtl::mesh_order(c->mesh, st, order, &err);
+    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
+    if (!written) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
+    else if (c->meshOrderStream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshOrder, 0));
+    return RT_OK;
+}
+
 int rt_mesh_order_device(RtContext *c, void **devPtr, size_t *bytes) {
     if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
     *devPtr = nullptr; *bytes = 0;
     if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_order: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
     (void)hipSetDevice(c->cfg.device);
-    const char *err = nullptr;
     const int *order = nullptr;
-    const int rc = rtl::mesh_order(c->mesh, c->lastStream ? c->lastStream : c->stream, &order, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_order: %s", err ? err : "launch failed");
+    const int rc = mesh_order_on(c, c->lastStream ? c->lastStream : c->stream, "rt_mesh_order", &order);
+    if (rc != RT_OK) return rc;
     *devPtr = const_cast<int *>(order);
     *bytes = (size_t)rtl::mesh_layout(c->mesh).nTris * 4;
     return RT_OK;
+}
+
+int rt_mesh_hit_parts(RtContext *c, const RtHit *hits, int n, int32_t *parts, int32_t *tris) {
+    if (!c) return RT_ERR_INVALID;
+    if (n < 0 || (n > 0 && !hits) || (!parts && !tris)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: bad arguments (n = %d; hits and one of parts / tris are needed)", n);
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
+    if (((uintptr_t)hits | (uintptr_t)parts | (uintptr_t)tris) & 3u) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: arrays must be 4-byte aligned");
+    if (n == 0) return RT_OK;
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    const int *order = nullptr;
+    int rc = mesh_order_on(c, st, "rt_mesh_hit_parts", &order);
+    if (rc != RT_OK) return rc;
+    const char *err = nullptr;
+    rc = rtl::mesh_hit_parts(c->mesh, st, order, hits, n, parts, tris, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_parts: %s", err ? err : "launch failed");
+    return RT_OK;
+}
+
+int rt_mesh_hit_parts_host(RtContext *c, const RtHit *hits, int n, int32_t *parts, int32_t *tris) {
+    if (!c) return RT_ERR_INVALID;
+    if (n < 0 || (n > 0 && !hits) || (!parts && !tris)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts_host: bad arguments (n = %d; hits and one of parts / tris are needed)", n);
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts_host: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
+    if (n == 0) return RT_OK;
+    return guarded(c, "rt_mesh_hit_parts_host", [&]() -> int {
+    (void)hipSetDevice(c->cfg.device);
+    const size_t N = (size_t)n, hB = N * sizeof(RtHit), offP = hB, offT = offP + (N * 4 + 15) / 16 * 16, total = offT + N * 4;   // hits | parts | tris
+    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
+    const int sr = ensure_staging(c, total);
+    if (sr != RT_OK) return sr;
+    char *base = (char *)c->dStaging;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
+    const int qr = rt_mesh_hit_parts(c, (const RtHit *)base, n, (int32_t *)(base + offP), (int32_t *)(base + offT));
+    if (qr != RT_OK) { (void)sync_all(c); return qr; }
+    if (parts) HIP_TRY(c, hipMemcpyAsync(parts, base + offP, N * 4, hipMemcpyDeviceToHost, st));
+    if (tris) HIP_TRY(c, hipMemcpyAsync(tris, base + offT, N * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return RT_OK;
+    });
 }
 
 int rt_mesh_order(RtContext *c, int32_t *order) {

@@ -398,6 +398,22 @@ int rt_gather_triangles_checked(const float *positions, int nVerts, const uint32
     return rt_gather_triangles(positions, indices, nIdx, M, out);
 }
 
+int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, const float *M16s,
+                              float *out) {
+    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (!positions || !indices || !out || !partFirst || nIdx < 0 || nVerts < 0 || nIdx % 3 != 0) return RT_ERR_INVALID;
+    if (nParts < 1 || nParts > RT_MAX_MESH_PARTS || partFirst[0] != 0 || partFirst[nParts] != nIdx / 3) return RT_ERR_INVALID;
+    for (int p = 0; p < nParts; ++p)
+        if (partFirst[p + 1] < partFirst[p]) return RT_ERR_INVALID;
+    for (int k = 0; k < nIdx; ++k)
+        if (indices[k] >= (uint32_t)nVerts) return RT_ERR_INVALID;
+    for (int p = 0; p < nParts; ++p) {   // part p = rt_gather_triangles over its run of index triples, under its own matrix
+        const int first = partFirst[p], count = partFirst[p + 1] - first;
+        if (count > 0) rt_gather_triangles(positions, indices + (size_t)first * 3, count * 3, M16s ? M16s + (size_t)p * 16 : kIdentity, out + (size_t)first * 9);
+    }
+    return nIdx / 3;
+}
+
 int rt_build_bvh_order(const float *tris9, int nTris, float *nodes12, float *tris12, int32_t *orderOut) {
     if (nTris < 0 || (nTris > 0 && (!tris9 || !nodes12 || !tris12))) return RT_ERR_INVALID;
     if (nTris == 0) return 0;

@@ -244,6 +244,11 @@ struct Mesh {
     LeafTab *dLeafTab = nullptr;
     RefitLeaf *dRefitLeaf = nullptr;
     RefitKids *dRefitKids = nullptr;
+    // parts: boundaries in triangle units (host copy and device), the part of every input triangle, one model matrix per part
+    std::vector<int32_t> partFirst;
+    int32_t *dPartFirst = nullptr;
+    uint16_t *dPartOf = nullptr;
+    float *dPartM = nullptr;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -274,7 +279,8 @@ template <class T> hipError_t dev_upload(Mesh *m, T **p, const std::vector<T> &v
 
 #define MESH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); mesh_destroy(m); return RT_ERR_HIP; } } while (0)
 
-int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, bool quantised, Mesh **out, const char **err) {
+int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, Mesh **out,
+                const char **err) {
     *out = nullptr;
     const int n = nIdx / 3;
     Mesh *m = new Mesh();
@@ -417,6 +423,16 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
     MESH_TRY(dev_upload(m, &m->dPairTab, pairTab)); MESH_TRY(dev_upload(m, &m->dWn2Tab, wn2)); MESH_TRY(dev_upload(m, &m->dW4Tab, w4));
     if (quantised) MESH_TRY(dev_upload(m, &m->dLeafTab, leafTab));
     MESH_TRY(dev_upload(m, &m->dRefitLeaf, refitLeaf)); MESH_TRY(dev_upload(m, &m->dRefitKids, refitKids));
+    {   // parts: an empty part owns no triangle, so the lookup never names one
+        m->partFirst.assign(partFirst, partFirst + nParts + 1);
+        std::vector<uint16_t> partOf(N);
+        std::vector<float> ident((size_t)nParts * 16, 0.0f);
+        for (int p = 0; p < nParts; ++p) {
+            for (int t = partFirst[p]; t < partFirst[p + 1]; ++t) partOf[(size_t)t] = (uint16_t)p;
+            for (int k = 0; k < 4; ++k) ident[(size_t)p * 16 + 5 * k] = 1.0f;
+        }
+        MESH_TRY(dev_upload(m, &m->dPartFirst, m->partFirst)); MESH_TRY(dev_upload(m, &m->dPartOf, partOf)); MESH_TRY(dev_upload(m, &m->dPartM, ident));
+    }
     MESH_TRY(dev_alloc(m, &m->dT9, N * 36, false, false));
     MESH_TRY(dev_alloc(m, &m->dMn, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dMx, N * 12, false, false)); MESH_TRY(dev_alloc(m, &m->dCen, N * 12, false, false));
     MESH_TRY(dev_alloc(m, &m->dPerm[0], N * 4, false, false)); MESH_TRY(dev_alloc(m, &m->dPerm[1], N * 4, false, false));
@@ -458,6 +474,9 @@ const BvhLayout &mesh_layout(const Mesh *m) { return m->lay; }
 const MeshScene &mesh_scene(const Mesh *m) { return m->sc; }
 float *mesh_positions(Mesh *m) { return m->dPos; }
 int mesh_verts(const Mesh *m) { return m->nVerts; }
+int mesh_part_count(const Mesh *m) { return (int)m->partFirst.size() - 1; }
+const int32_t *mesh_part_first(const Mesh *m) { return m->partFirst.data(); }
+float *mesh_part_matrices(Mesh *m) { return m->dPartM; }
 uint64_t mesh_allocations(const Mesh *m) { return m->allocations; }
 size_t mesh_scratch_bytes(const Mesh *m) { return m->scratchBytes; }
 size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }
@@ -485,9 +504,11 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     const int n = L.nTris;
     const unsigned gN = blocks_for((size_t)n);
     m->permCur = -1; m->orderValid = false;   // the sorts below use both permutation buffers
-    Mat16 M;
-    std::memcpy(M.m, M16, sizeof M.m);
-    hipLaunchKernelGGL(k_mesh_gather, dim3(gN), dim3(256), 0, st, m->dPos, m->dIdx, n, M, m->dT9);
+    if (M16) {
+        Mat16 M;
+        std::memcpy(M.m, M16, sizeof M.m);
+        hipLaunchKernelGGL(k_mesh_gather, dim3(gN), dim3(256), 0, st, m->dPos, m->dIdx, n, M, m->dT9);
+    } else parts_launch_gather(st, m->dPos, m->dIdx, m->dPartOf, m->dPartM, n, m->dT9);
     hipLaunchKernelGGL(k_mesh_init, dim3(blocks_for((size_t)L.nNodes * 6)), dim3(256), 0, st, m->dBounds, L.nNodes * 6, m->dStatus);
     hipLaunchKernelGGL(k_tri_prep, dim3(gN), dim3(256), 0, st, m->dT9, n, m->dMn, m->dMx, m->dCen);
     hipLaunchKernelGGL(k_iota, dim3(gN), dim3(256), 0, st, m->dPerm[0], n);
@@ -517,7 +538,8 @@ int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     if (m->permCur < 0) return RT_ERR_INVALID;
     const BvhLayout &L = m->lay;
     const int n = L.nTris;
-    refit_launch_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, n, M16, m->sc.tris);
+    if (M16) refit_launch_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, n, M16, m->sc.tris);
+    else parts_launch_refit_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, m->dPartOf, m->dPartM, n, m->sc.tris);
     refit_launch_leaves(st, m->sc.tris, m->dRefitLeaf, (int)L.nLeaves, m->dBounds, m->dStatus);
     for (int d = m->nLevels - 2; d >= 0; --d) {   // bottom-up, one launch per level: a kernel boundary makes the children's boxes visible
         if (!m->levelInner[(size_t)d]) continue;
@@ -538,6 +560,15 @@ int mesh_order(Mesh *m, hipStream_t st, const int **order, const char **err) {
         m->orderValid = true;
     }
     *order = dst;
+    return RT_OK;
+}
+
+bool mesh_order_written(const Mesh *m) { return m->permCur >= 0 && m->orderValid; }
+
+int mesh_hit_parts(Mesh *m, hipStream_t st, const int *order, const void *hits, int n, int32_t *parts, int32_t *tris, const char **err) {
+    if (m->permCur < 0) return RT_ERR_INVALID;
+    parts_launch_hit_parts(st, hits, n, order, m->lay.nTris, m->dPartOf, m->dPartFirst, parts, tris);
+    REB_TRY(hipGetLastError());
     return RT_OK;
 }
 

@@ -28,8 +28,11 @@ struct MeshScene {
 };
 
 struct Mesh;
-// positions / indices: validated host arrays.  quantised: build the quantised any-hit form as well.  May allocate and synchronise.
-int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, bool quantised, Mesh **out, const char **err);
+// positions / indices: validated host arrays.  partFirst: nParts + 1 validated part boundaries in triangle units; the parts table, the
+// per-triangle part lookup and the matrix table (identities) go to the device here.  quantised: build the quantised any-hit form as well.  May allocate
+// and synchronise.
+int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, Mesh **out,
+                const char **err);
 void mesh_destroy(Mesh *m);
 const BvhLayout &mesh_layout(const Mesh *m);
 const MeshScene &mesh_scene(const Mesh *m);
@@ -38,7 +41,11 @@ int mesh_verts(const Mesh *m);
 uint64_t mesh_allocations(const Mesh *m);
 size_t mesh_scratch_bytes(const Mesh *m);
 size_t mesh_scene_bytes(const Mesh *m);
-// Enqueues gather (model matrix M16, column-major), build and record emission on `st`: no allocation, no host wait.
+int mesh_part_count(const Mesh *m);
+const int32_t *mesh_part_first(const Mesh *m);   // host copy, nParts + 1 entries
+float *mesh_part_matrices(Mesh *m);               // device, nParts x 16 floats, column-major
+// Enqueues gather, build and record emission on `st`: no allocation, no host wait.  The gather is the single-matrix one under M16 (column-major), or,
+// with M16 == nullptr, the part-aware one under the matrix table as it stands when the kernel runs.  mesh_refit takes the same argument.
 int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err);
 // A rebuild of this mesh has run: there is a tree to refit and an order to hand out.
 bool mesh_has_tree(const Mesh *m);
@@ -48,6 +55,10 @@ int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err);
 // *order: device array, order[row of the triangle array] = input triangle, derived on `st` at the first call after a rebuild into the permutation
 // buffer that is idle between rebuilds; valid until the next rebuild.  RT_ERR_INVALID without a tree.
 int mesh_order(Mesh *m, hipStream_t st, const int **order, const char **err);
+bool mesh_order_written(const Mesh *m);   // the order array of the current tree has been derived (by whichever call asked first)
+// Enqueues the hit -> (part, triangle of the part) map on `st` for n RtHit records (device pointers; either output may be null): order[prim] through the
+// part lookup, (-1, -1) for a prim outside [0, nTris).  The caller has made the order array visible on `st` (mesh_order).
+int mesh_hit_parts(Mesh *m, hipStream_t st, const int *order, const void *hits, int n, int32_t *parts, int32_t *tris, const char **err);
 
 // rt_mesh_refit.hip: the refit's kernels behind plain launch functions (raw device pointers; bounds are the builder's sortable uints, six per slot)
 struct RefitLeaf { int slot, first, count; };   // one leaf: bounds slot, its rows of the triangle array
@@ -56,6 +67,13 @@ void refit_launch_tris(hipStream_t st, const float *pos, const uint32_t *idx, co
 void refit_launch_leaves(hipStream_t st, const float4 *t12, const RefitLeaf *leaves, int nLeaves, uint32_t *bounds, uint32_t *status);   // clears *status
 void refit_launch_inner(hipStream_t st, const RefitKids *kids, int firstSlot, int nSlots, uint32_t *bounds);                             // one level
 void refit_launch_order(hipStream_t st, const int *perm, const int *outOfPos, int nTris, int *order);
+
+// rt_mesh_parts.hip: the part-aware kernels behind plain launch functions.  partOf[input triangle] = its part; mats = the matrix table
+void parts_launch_gather(hipStream_t st, const float *pos, const uint32_t *idx, const uint16_t *partOf, const float *mats, int nTris, float *t9);
+void parts_launch_refit_tris(hipStream_t st, const float *pos, const uint32_t *idx, const int *perm, const int *outOfPos, const uint16_t *partOf, const float *mats,
+                             int nTris, float4 *t12);
+void parts_launch_hit_parts(hipStream_t st, const void *hits, int n, const int *order, int nTris, const uint16_t *partOf, const int32_t *partFirst, int32_t *parts,
+                            int32_t *tris);
 
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);

@@ -2,6 +2,7 @@
 instead of rebuilt.
 
     python tools/mesh_refit_time.py [--reps N] [--out profiles/r09_mesh_refit.txt] [--sizes bunny,1m | none] [--no-frames]
+    python tools/mesh_refit_time.py --parts 1,64,4096 [--reps N] [--out profiles/r10_mesh_parts.txt] [--sizes bunny,1m]
 
 Per size (the bench mesh -- bunny stand-in, 81 920 triangles -- and the 1 M-triangle scene, where the quantised any-hit form is in use and both
 calls pay their one host wait), in one process and on one context: every step displaces the positions on the device, then runs rt_mesh_rebuild
@@ -12,6 +13,12 @@ Condition of the issue: the refit's median device time is below the rebuild's an
 Informational (bench mesh only): ms per frame of the bench view (1920x1080, 4 spp, close-up camera, wavefront pipeline) on the tree after 1, 8
 and 32 refit steps of the animation, and after random per-vertex displacements, against a tree rebuilt over the same positions on a second
 context -- the price of not rebuilding.
+
+--parts N[,N ...] measures the part-aware calls instead: per size and N, the mesh split into N equal parts with a distinct rigid
+matrix per part that changes every step (written into the device table on the library stream), and rt_mesh_refit / rt_mesh_refit_parts /
+rt_mesh_rebuild / rt_mesh_rebuild_parts alternated on one context.  Conditions: the refit_parts median is below the rebuild median and its whole
+range below the rebuild minimum; the rebuild_parts median is at most the rebuild median plus that rebuild's own (max - min) spread of the run.
+refit_parts / refit is recorded without a bound.
 """
 import argparse
 import os
@@ -86,6 +93,68 @@ def measure(name, v, f, reps, lines):
     return ok
 
 
+def rigid_models(n_parts, k):
+    """[n_parts,16] column-major: the default BVH transform after a rotation about y and a small translation, distinct per part, another at every step k."""
+    p = np.arange(n_parts, dtype=np.float64)
+    ang = 0.02 * (k + 1) * (1.0 + p % 7) + 0.001 * p
+    c, s = np.cos(ang), np.sin(ang)
+    R = np.zeros((n_parts, 4, 4))
+    R[:, 0, 0], R[:, 0, 2], R[:, 2, 0], R[:, 2, 2], R[:, 1, 1], R[:, 3, 3] = c, s, -s, c, 1.0, 1.0
+    R[:, 0, 3], R[:, 1, 3] = 0.01 * (p % 5), 0.005 * ((p + k) % 3)
+    D = np.asarray(rt.default_bvh_transform(), np.float64).reshape(4, 4).T
+    return np.ascontiguousarray(np.transpose(D @ R, (0, 2, 1)), np.float32).reshape(n_parts, 16)
+
+
+def measure_parts(name, v, f, n_parts, reps, lines):
+    import torch
+    dev = torch.device("cuda", 0)
+    v = np.ascontiguousarray(v, np.float32)
+    n = np.asarray(f).size // 3
+    pf = np.linspace(0, n, n_parts + 1).astype(np.int32)
+    M = rt.default_bvh_transform()
+    calls = ("refit", "refit_parts", "rebuild", "rebuild_parts")
+    t = {c: [] for c in calls}
+    with rt.Renderer() as b:
+        b.mesh_upload_parts(v, f, pf)
+        stream = torch.cuda.ExternalStream(b.stream(), device=dev)
+        tables = [torch.from_numpy(rigid_models(n_parts, k)).to(dev) for k in range(4)]
+        torch.cuda.synchronize()
+        run = {"refit": lambda: b.mesh_refit(M), "refit_parts": b.mesh_refit_parts, "rebuild": lambda: b.mesh_rebuild(M), "rebuild_parts": b.mesh_rebuild_parts}
+        b.mesh_rebuild(M)
+        for k in range(-3, reps):       # k < 0: warm-up
+            with torch.cuda.stream(stream):
+                b.mesh_part_matrices().copy_(tables[k % 4])
+            for c in calls:
+                b.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                run[c]()
+                e1.record(stream)
+                b.synchronize()
+                if k >= 0:
+                    t[c].append(e0.elapsed_time(e1))
+        mi = b.mesh_info()
+        total, _ = b.mesh_refit_count()
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    lines.append(f"{name}, {n_parts} parts: {n} triangles; device time between events on the library stream; quantised any-hit form "
+                 f"{'in use (one host wait per call)' if mi.hostSyncs else 'not in use (no host wait)'}")
+    for c in calls:
+        lines.append(fmt("rt_mesh_" + c, t[c]))
+    med = {c: statistics.median(t[c]) for c in calls}
+    spread = max(t["rebuild"]) - min(t["rebuild"])
+    ok_refit = med["refit_parts"] < med["rebuild"] and max(t["refit_parts"]) < min(t["rebuild"])
+    ok_rebuild = med["rebuild_parts"] <= med["rebuild"] + spread
+    lines.append(f"  refit_parts / refit {med['refit_parts'] / med['refit']:.3f}   rebuild_parts / rebuild {med['rebuild_parts'] / med['rebuild']:.3f}   "
+                 f"rebuild / refit_parts {med['rebuild'] / med['refit_parts']:.1f}x      RtMeshInfo: rebuilds {mi.rebuilds}, refits {total}, allocations "
+                 f"{mi.allocations} (all in the upload), hostSyncs {mi.hostSyncs}")
+    lines.append(f"  condition (refit_parts median < rebuild median, refit_parts max {max(t['refit_parts']):.3f} < rebuild min {min(t['rebuild']):.3f}): "
+                 f"{'MET' if ok_refit else 'MISSED'}")
+    lines.append(f"  condition (rebuild_parts median {med['rebuild_parts']:.3f} <= rebuild median {med['rebuild']:.3f} + its spread {spread:.3f}): "
+                 f"{'MET' if ok_rebuild else 'MISSED'}")
+    lines.append("")
+    return ok_refit and ok_rebuild
+
+
 def frame_cost(lines, steps=(1, 8, 32), frames=48, batch=8):
     """ms per frame of the bench view on a refitted tree against a rebuilt one over the same positions."""
     import torch
@@ -158,7 +227,21 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="bunny,1m")
     ap.add_argument("--no-frames", action="store_true")
+    ap.add_argument("--parts", default=None, help="comma-separated part counts: time the part-aware calls against the single-matrix ones instead")
     args = ap.parse_args()
+    if args.parts:
+        lines = [f"mesh_refit_time.py --parts {args.parts} --reps {args.reps}: refit, refit_parts, rebuild and rebuild_parts alternated on one context, one process", ""]
+        ok = True
+        for s in [x for x in args.sizes.split(",") if x and x != "none"]:
+            v, f = rt.meshgen.bunny_standin(6) if s == "bunny" else rt.meshgen.million_triangle_scene()
+            for n_parts in [int(x) for x in args.parts.split(",")]:
+                ok = measure_parts("bench mesh" if s == "bunny" else "1 M scene", v, f, n_parts, max(args.reps, 1), lines) and ok
+        text = "\n".join(lines)
+        print(text)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(text + "\n")
+        return 0 if ok else 1
     lines = [f"mesh_refit_time.py --reps {args.reps}: rebuild and refit alternated on one context, one process", ""]
     ok = True
     for s in [x for x in args.sizes.split(",") if x and x != "none"]:

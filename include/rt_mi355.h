@@ -381,6 +381,13 @@ int rt_debug_bounce_probe(RtContext *ctx, RtBounceProbe *out, int reset);
  * waves they ran in.  The kernels count only from the first call of this entry on (a kernel argument that is null before): call it once, with reset, first. */
 typedef struct RtDiskSkip { uint64_t directPairs, directUnlit, directSkipped, directWaves, directWavesSkipped, giPairs, giUnlit, giSkipped, giWaves, giWavesSkipped; } RtDiskSkip;
 int rt_debug_disk_skip(RtContext *ctx, RtDiskSkip *out, int reset);
+/* The bounce-hit generator of the wavefront frames, the stage that records the shadow rays at the bounce hits.  Behind a bounce probe it walks
+ * the probe's list of hits (k_gen_gi_listed); otherwise -- no probe, RT_BIN_GI=1 -- it visits every (hit, sample) pair (k_gen_gi).  Counts since the last reset,
+ * summed over the frame lanes (synchronises): visited = pairs the generator looked at, shaded = pairs whose bounce ray hit, listedLaunches / pairLaunches =
+ * launches (one per chunk of a launch set) over the list / over every pair.  visited and shaded count only from the first call of this entry on (a kernel
+ * argument that is null before): call it once, with reset, first. */
+typedef struct RtGiList { uint64_t visited, shaded, listedLaunches, pairLaunches; } RtGiList;
+int rt_debug_gi_list(RtContext *ctx, RtGiList *out, int reset);
 /* Diagnostics: the per-hit test beside the code it stands for.  For n pairs (hp, normal; 3 floats each) flags[i] bit 0 = the test holds, bit 1 = one of the
  * four disk samples of `seeds` (pixel, frame) seeds had geom != 0; maxDot[i] = the largest dot(N, L) those samples computed.  u supplies uPI. */
 int rt_debug_disk_unlit(RtContext *ctx, const RtUniforms *u, const float *hp, const float *normals, int n, int seeds, uint8_t *flags, float *maxDot);

@@ -146,6 +146,10 @@ class RtDiskSkip(_Struct):   # rt_debug_disk_skip: the disk-light skip of the sh
                                              "giPairs", "giUnlit", "giSkipped", "giWaves", "giWavesSkipped")]
 
 
+class RtGiList(_Struct):   # rt_debug_gi_list: what the bounce-hit generator visited and shaded, and which kernel ran
+    _fields_ = [(n, C.c_uint64) for n in ("visited", "shaded", "listedLaunches", "pairLaunches")]
+
+
 class RtSceneInfo(_Struct):
     _fields_ = [(n, i32) for n in ("nNodes", "nTris", "nInner", "treeDepth", "nWide4", "nPairs")] + \
                [(n, C.c_uint64) for n in ("bytesNodes2", "bytesNodes4", "bytesPairs", "bytesTris")] + \
@@ -280,6 +284,7 @@ SIGNATURES = {
     "rt_debug_builds": (C.c_int, [C.c_void_p, _U32P, C.c_int]),
     "rt_debug_bounce_probe": (C.c_int, [C.c_void_p, C.POINTER(RtBounceProbe), C.c_int]),
     "rt_debug_disk_skip": (C.c_int, [C.c_void_p, C.POINTER(RtDiskSkip), C.c_int]),
+    "rt_debug_gi_list": (C.c_int, [C.c_void_p, C.POINTER(RtGiList), C.c_int]),
     "rt_debug_disk_unlit": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                       C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,
@@ -1333,6 +1338,13 @@ class Renderer:
         wave skipped the disk loop, waves, waves that skipped (rt_debug_disk_skip).  The kernels count from the first call on: call once with reset first."""
         b = RtDiskSkip()
         self._check(lib().rt_debug_disk_skip(self._h, C.byref(b), int(reset)))
+        return b
+
+    def gi_list(self, reset=False) -> RtGiList:
+        """Counts of the bounce-hit generator since the last reset: (hit, sample) pairs visited, pairs shaded, launches over the bounce probe's hit list /
+        over every pair (rt_debug_gi_list).  The kernels count from the first call on: call once with reset first."""
+        b = RtGiList()
+        self._check(lib().rt_debug_gi_list(self._h, C.byref(b), int(reset)))
         return b
 
     def debug_disk_unlit(self, u, hp, normals, seeds=64):

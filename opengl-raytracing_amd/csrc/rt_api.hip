@@ -2286,6 +2286,20 @@ int rt_debug_disk_skip(RtContext *c, RtDiskSkip *out, int reset) {
     return RT_OK;
 }
 
+int rt_debug_gi_list(RtContext *c, RtGiList *out, int reset) {
+    if (!c || !out) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    unsigned long long v[4] = {0, 0, 0, 0};
+    for (int i = 0; i < c->nLanes; ++i) {
+        unsigned long long t[4];
+        int rc = rt_wave_gi_list(c->wave[i], c->lanes[i], t, reset != 0);
+        if (rc != RT_OK) return fail(c, rc, "rt_debug_gi_list: %s", rt_wave_error(c->wave[i]));
+        for (int k = 0; k < 4; ++k) v[k] += t[k];
+    }
+    out->visited = v[0]; out->shaded = v[1]; out->listedLaunches = v[2]; out->pairLaunches = v[3];
+    return RT_OK;
+}
+
 int rt_debug_disk_unlit(RtContext *c, const RtUniforms *u, const float *hp, const float *normals, int n, int seeds, uint8_t *flags, float *maxDot) {
     if (!c || !u || !hp || !normals || !flags || !maxDot || n <= 0 || seeds <= 0) return RT_ERR_INVALID;
     (void)hipSetDevice(c->cfg.device);

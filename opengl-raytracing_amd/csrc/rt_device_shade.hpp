@@ -535,6 +535,8 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
     return sum;
 }
 
+// where the bounce ray of a hit starts (:531): the same point for every sample of the hit.  N0 = normalize(hn0).
+RT_DEV V3 bounce_origin(V3 hp0, V3 N0, float eps) { return hp0 + N0 * eps; }
 // oneBounceGIBVH (:515-561):  int T::gi(V3 ro, V3 rd, V3 &hp, V3 &hn)  -> 1 hit, 0 miss, -1 "not known yet"
 template <class T, bool COUNT>
 RT_DEV V3 oneBounceGIBVH(T &tr, const Frag &F, V3 hp0, V3 hn0, int frame, int seed, Work &w) {
@@ -547,7 +549,7 @@ RT_DEV V3 oneBounceGIBVH(T &tr, const Frag &F, V3 hp0, V3 hn0, int frame, int se
     V3 wi = sampleHemisphereCosine(u.pi, N0, uu);
     float cosTheta = fmaxr(dot(N0, wi), 0.0f);
     if (cosTheta <= MIN_COS_THETA) return mk3(0.0f);
-    V3 origin = hp0 + N0 * u.eps;
+    V3 origin = bounce_origin(hp0, N0, u.eps);
     V3 hp1, hn1;
     int hit1 = tr.gi(origin, wi, hp1, hn1);
     if (hit1 < 0) return mk3(0.0f);

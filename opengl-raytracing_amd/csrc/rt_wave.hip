@@ -56,10 +56,16 @@ struct WaveBuf {
     int *primTri;
     HitRec *hits;
     // per chunk of CH hits
-    float4 *shO, *shD;       // shadow queue 1: (A + 6*SPP) slots x CH
-    float *shT, *giL, *sh2T; // per-slot tMax (any-hit) / liveness (bounce); < 0 = no ray in this slot (4 B instead of a 32-B record)
+    // Shadow queue 1: (A + 4*SPP + 2) slots x CH.  Every slot has a direction record in shD.  The A AO slots are DENSE slots: the record is {dir, limit} -- limit =
+    // tMax, < 0 = no ray -- and the origin, one for all AO rays of the hit (computeAO_BVH), is aoOrg[j].  The light slots behind them keep an origin record and a
+    // tMax / liveness word of their own (hp + L*e differs from ray to ray): shO / shT, indexed by the slot's address LESS the A * CH dense ones.
+    float4 *shO, *shD;
+    float *shT, *sh2T;       // per-slot tMax (any-hit); < 0 = no ray in this slot (4 B instead of a 32-B record)
+    float4 *aoOrg;           // per hit: hp + N * aoBias, written once (AO ray 0)
     uint8_t *occ1;
-    float4 *giO, *giD;       // bounce queue: SPP slots x CH
+    // Bounce queue: SPP dense slots x CH, record {dir, 1.0 = a ray was cast | < 0 = none}; the origin hp + N * eps (bounce_origin) belongs to the hit: giOrg[j],
+    // written once by sample 0 whether or not that sample casts.  (RT_BIN_GI permutes the records of a workgroup: there giOrg holds one origin per RECORD.)
+    float4 *giD, *giOrg;
     float *giT;
     int *giTri;
     float4 *sh2O, *sh2D;     // shadow queue 2: 6 slots x q2Stride, entries compacted over the (hit, sample) pairs whose bounce hit
@@ -81,6 +87,7 @@ struct WaveBuf {
     // slot per hit -- those two rays do not depend on the sample (rt_lighting.glsl:114-214), sample 0 traces them and the others reuse its answer,
     // so samples > 0 own no slot for them (round 4: 22 instead of 28 slots per hit at 4 spp)
     __device__ __forceinline__ uint32_t gi_entry(int s, uint32_t j) const { const uint32_t a = (uint32_t)s * CH + j; return giPerm ? (uint32_t)giPerm[a] : a; }
+    __device__ __forceinline__ uint32_t sh1_light(uint32_t a) const { return a - (uint32_t)A * CH; }   // address of a light slot -> entry of shO / shT
     __device__ __forceinline__ uint32_t sh1_slot(int s, int k) const { return (uint32_t)(k < 4 ? A + s * 4 + k : A + 4 * SPP + (k - 4)); }
 };
 
@@ -279,11 +286,15 @@ struct PrimarySrc {   // ray i = primary ray of candidate i
     RT_DEV float probe_take(uint32_t, V3 &, V3 &, uint32_t &) const { return -1.0f; }
 };
 struct QueueSrc {     // slot-major queue: ray r -> (slot = r / n, j = r % n) at [slot*stride + j], n = live entries
-    const float4 *o, *d;
+    const float4 *o, *d;         // d: every slot; o / tm: the slots behind the dense ones, entry [address - denseSlots * stride]
     const float *tm;             // per-slot tMax / liveness
     const uint32_t *liveCount;   // device counter the live entry count derives from
     uint32_t c0, cap, stride, slots;
-    uint32_t denseSlots;         // the first `denseSlots` slots hold a ray for (nearly) every entry (AO slots, the bounce queue): see dense() below
+    uint32_t denseSlots;         // the first `denseSlots` slots hold a ray for (nearly) every entry (AO slots, the bounce queue): see dense() below.  Their record is
+                                 // ONE float4 {dir, tMax / liveness}; the origin belongs to the entry, not the slot: org[j] (orgStride = 0), or to the record: org[address]
+    const float4 *org;
+    uint32_t orgStride;          // 0, or `stride`
+    RT_DEV uint32_t nDense() const { return denseSlots * stride; }
     float *outT;
     int *outTri;
     uint8_t *outOcc;
@@ -298,11 +309,11 @@ struct QueueSrc {     // slot-major queue: ray r -> (slot = r / n, j = r % n) at
     // (Reading the records together with the liveness words -- one round trip per refill instead of two -- was measured slower for
     // the shadow queue, where 55 % of the slots are dead: 1.07 vs 1.01 ms.)
     struct Payload { uint32_t a; };
-    RT_DEV float probe(uint32_t r, Payload &p) const { p.a = addr(r); return tm[p.a]; }
+    RT_DEV float probe(uint32_t r, Payload &p) const { p.a = addr(r); return p.a < nDense() ? d[p.a].w : tm[p.a - nDense()]; }   // (dense slots here: RT_DENSE_TAKE=0, or a run across the last dense slot's end)
     RT_DEV static Payload route(const Payload &p, int e) { Payload q; q.a = (uint32_t)__shfl((int)p.a, e, 64); return q; }
     RT_DEV void take(uint32_t, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const {
         token = p.a;                     // results go to the same queue address: no second div/mod at retirement
-        const float4 oo = o[p.a], dd = d[p.a];
+        const float4 oo = p.a < nDense() ? org[orgStride ? p.a : p.a % stride] : o[p.a - nDense()], dd = d[p.a];
         ro = f4xyz(oo); rd = f4xyz(dd);
     }
     RT_DEV void store_closest(uint32_t a, float t, int tri) const { outT[a] = t; outTri[a] = tri; }
@@ -311,12 +322,11 @@ struct QueueSrc {     // slot-major queue: ray r -> (slot = r / n, j = r % n) at
     // left and reads liveness word and record together; an entry that is dead after all (AO radius 0, GI switched off) just leaves its lane idle.
     RT_DEV bool dense(uint32_t r0, uint32_t r1) const { return r1 > r0 && (r1 - 1u) / nLive < denseSlots; }
     RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const {
-        const uint32_t a = addr(r);
-        const float t = tm[a];
-        const float4 oo = o[a], dd = d[a];
+        const uint32_t sl = r / nLive, j = r % nLive, a = sl * stride + j;
+        const float4 oo = org[sl * orgStride + j], dd = d[a];
         token = a;
         ro = f4xyz(oo); rd = f4xyz(dd);
-        return t;
+        return dd.w;
     }
 };
 
@@ -352,12 +362,12 @@ struct DualQueueSrc {
 
 // The bounce queue walked ANY-hit first (RT_BOUNCE_PROBE): almost every bounce ray misses, and a miss does not depend on the
 // order the walk visits the leaves in.  A ray whose any-hit walk with tMax = uINF (the closest-hit launch's own start value) finds no triangle
-// gets the closest-hit launch's miss answer (uINF, -1) here; the few that hit are listed in `hitters` and walked again by the closest-hit
+// gets the closest-hit launch's miss answer here -- its triangle, -1; the distance uINF is not stored, nothing reads giT of a ray without a triangle --; the few that hit are listed in `hitters` and walked again by the closest-hit
 // kernel (IndexedSrc), unchanged.  Bit-identical because both walks test the same leaves against the same exact boxes with the same tri_hit,
 // whose acceptance is monotone in tBest -- true of the 4-wide tree rt_upload_bvh collapses from the binary one (exact or quantised nodes),
 // not of RT_ANYHIT_TREE=sah, where the probe is never launched.
 struct BounceProbeSrc {
-    QueueSrc q;                  // the bounce queue: its tm word is the liveness value giL (1.0), NOT a distance
+    QueueSrc q;                  // the bounce queue: the .w of its records is a liveness value (1.0), NOT a distance
     uint32_t *hitters, *hitCount;
     float inf;                   // uINF of the frame (the host copy of its descriptor): the closest-hit walk's start value and its answer for a miss
     RT_DEV void prepare() { q.prepare(); }
@@ -369,7 +379,7 @@ struct BounceProbeSrc {
     RT_DEV void store_closest(uint32_t, float, int) const {}
     RT_DEV void store_any(uint32_t a, bool hit) const {
         const unsigned long long m = __ballot(hit);   // the lanes that retire a hit in this step append together: one atomic per wave
-        if (!hit) { q.outT[a] = inf; q.outTri[a] = -1; return; }
+        if (!hit) { q.outTri[a] = -1; return; }   // (no t for a miss: every reader of giT looks at giTri first)
         const uint32_t lane = threadIdx.x & 63u;
         const int leader = __ffsll((long long)m) - 1;
         uint32_t base = 0;
@@ -397,6 +407,31 @@ struct IndexedSrc {
     RT_DEV void take(uint32_t, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const {
         token = p.a;
         const float4 oo = o[p.a], dd = d[p.a];
+        ro = f4xyz(oo); rd = f4xyz(dd);
+    }
+    RT_DEV void store_closest(uint32_t a, float t, int tri) const { outT[a] = t; outTri[a] = tri; }
+    RT_DEV void store_any(uint32_t, bool) const {}
+    RT_DEV bool dense(uint32_t, uint32_t) const { return false; }
+    RT_DEV float probe_take(uint32_t, V3 &, V3 &, uint32_t &) const { return -1.0f; }
+};
+
+// The same list over the DENSE slots of a queue (the re-trace of the bounce probe's hits): record d[a] = {dir, .}, origin org[a % stride] (orgStride = 0) or org[a].
+struct IndexedDenseSrc {
+    const uint32_t *idx;
+    const uint32_t *count;
+    const float4 *org, *d;
+    uint32_t stride, orgStride;
+    float *outT;
+    int *outTri;
+    uint32_t n;
+    RT_DEV void prepare() { n = *count; }
+    RT_DEV uint32_t size() const { return n; }
+    struct Payload { uint32_t a; };
+    RT_DEV float probe(uint32_t r, Payload &p) const { p.a = idx[r]; return 1.0f; }
+    RT_DEV static Payload route(const Payload &p, int e) { Payload q; q.a = (uint32_t)__shfl((int)p.a, e, 64); return q; }
+    RT_DEV void take(uint32_t, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const {
+        token = p.a;
+        const float4 oo = org[orgStride ? p.a : p.a % stride], dd = d[p.a];
         ro = f4xyz(oo); rd = f4xyz(dd);
     }
     RT_DEV void store_closest(uint32_t a, float t, int tri) const { outT[a] = t; outTri[a] = tri; }
@@ -1315,8 +1350,9 @@ struct KTrace {
 // ray's answer is the OR over the reference's leaves whose own box the ray passes ("any-hit rays walk 4-wide nodes") -- which is
 // what this computes, in another order -- so the answers are the same bits.
 struct PacketSrc {       // packet p -> hit j = p % nLive, ray group g = p / nLive: rays i = 4 g .. 4 g + 3 (< A) at [i * stride + j]
-    const float4 *o, *d;
+    const float4 *o, *d;     // org == null (rt_debug_trace kind 4): a packet leaves from the origin record of its first ray, o[.], tMax words in tm
     const float *tm;
+    const float4 *org;       // the frames' dense AO slots: one origin per hit, org[j]; tMax is the .w of the direction record
     uint8_t *occ;
     const uint32_t *liveCount;
     uint32_t c0, cap, stride;
@@ -1414,16 +1450,17 @@ __global__ __launch_bounds__(256, 4) void k_trace_packets(const DevFrame *__rest
                 const uint32_t g = p / src.nLive, j = p % src.nLive;
                 token = (4u * g) * src.stride + j;
                 nRays = min(4u, (uint32_t)src.A - 4u * g);
-                ro = f4xyz(src.o[token]);        // one origin for the packet
+                ro = f4xyz(src.org ? src.org[j] : src.o[token]);        // one origin for the packet
                 alive = 0; occl = 0; sp = 0; cur = 0; leafE = 0;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     tMax[r] = -1.0f;
                     if ((uint32_t)r < nRays) {
                         const uint32_t a = token + (uint32_t)r * src.stride;
-                        tMax[r] = src.tm[a];
+                        float4 dd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        if (src.org) { dd = src.d[a]; tMax[r] = dd.w; } else tMax[r] = src.tm[a];
                         if (!(tMax[r] < 0.0f)) {
-                            rd[r] = f4xyz(src.d[a]);
+                            rd[r] = f4xyz(src.org ? dd : src.d[a]);
                             rdInv[r] = mk3(1.0f / rd[r].x, 1.0f / rd[r].y, 1.0f / rd[r].z);
                             traced++;
                             float tmin;
@@ -1601,9 +1638,10 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         // sample of the pixel (rt_lighting.glsl:114-214 never look at the seed) -- sample 0 traces it, the others reuse its answer
         if (k >= 4 && s > 0) return false;
         uint32_t a = wb.sh1_slot(s, k) * wb.CH + j;
-        if (!matters) { wb.shT[a] = -1.0f; return false; }   // dead ray: its answer is multiplied by zero
-        wb.shT[a] = fmaxr(tMax, 0.0f);
-        wb.shO[a] = mkf4(ro, 0.0f);
+        const uint32_t al = wb.sh1_light(a);
+        if (!matters) { wb.shT[al] = -1.0f; return false; }   // dead ray: its answer is multiplied by zero
+        wb.shT[al] = fmaxr(tMax, 0.0f);
+        wb.shO[al] = mkf4(ro, 0.0f);
         wb.shD[a] = mkf4(rd, 0.0f);
         return false;
     }
@@ -1612,16 +1650,13 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         giCast = true;
         if (wb.giPerm) { giRo = ro; giRd = rd; return -1; }
         uint32_t a = (uint32_t)s * wb.CH + j;
-        wb.giL[a] = 1.0f;
-        wb.giO[a] = mkf4(ro, 0.0f);
-        wb.giD[a] = mkf4(rd, 0.0f);
+        wb.giD[a] = mkf4(rd, 1.0f);      // the origin is the hit's: giOrg[j], written by sample 0 (k_gen_direct)
         return -1;
     }
     RT_DEV bool ao(int i, V3 org, V3 dir, float radius) {
         uint32_t a = (uint32_t)i * wb.CH + j;
-        wb.shT[a] = below(radius);   // closest t < radius  <=>  any hit with t <= pred(radius)
-        wb.shO[a] = mkf4(org, 0.0f);
-        wb.shD[a] = mkf4(dir, 0.0f);
+        if (i == 0) wb.aoOrg[j] = mkf4(org, 0.0f);   // one origin for the hit's AO rays (only sample 0's thread gets here)
+        wb.shD[a] = mkf4(dir, below(radius));         // closest t < radius  <=>  any hit with t <= pred(radius)
         return false;
     }
 };
@@ -1717,10 +1752,14 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
         (void)directLightBVH(tr, c.F, SEG_DIRECT, c.hp, c.hn, seed, -c.dir);
         if (s == 0)
             for (int k = 4; k < 6; ++k)   // sun / point rays are conditional (rt_lighting.glsl:123,194)
-                if (!(tr.shadowMask & (1u << k))) wb.shT[wb.sh1_slot(0, k) * wb.CH + j] = -1.0f;
+                if (!(tr.shadowMask & (1u << k))) wb.shT[wb.sh1_light(wb.sh1_slot(0, k) * wb.CH + j)] = -1.0f;
         Work w;
         if (u.enableGI == 1) (void)oneBounceGIBVH<GenDirectTracer, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
-        if (!tr.giCast && !wb.giPerm) wb.giL[(uint32_t)s * wb.CH + j] = -1.0f;
+        if (u.enableGI == 1 && !wb.giPerm) {
+            if (!tr.giCast) wb.giD[(uint32_t)s * wb.CH + j].w = -1.0f;
+            // the bounce origin of the hit's samples, once: from sample 0 even when its own direction declines (cosTheta), another sample's may not
+            if (s == 0) wb.giOrg[j] = mkf4(bounce_origin(c.hp, normalize(c.hn), u.eps), 0.0f);
+        }
         if (s == 0 && wb.A > 0) (void)computeAO_BVH(tr, c.F, c.hp, c.hn, c.F.frameIndex);
     }
     if (wb.giPerm) {
@@ -1745,14 +1784,21 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
         const uint32_t target = sAddr[rank];
         if (mine) {
             wb.giPerm[(uint32_t)s * wb.CH + j] = (int)target;
-            if (tr.giCast) { wb.giL[target] = 1.0f; wb.giO[target] = mkf4(tr.giRo, 0.0f); wb.giD[target] = mkf4(tr.giRd, 0.0f); }
-            else wb.giL[target] = -1.0f;
+            if (tr.giCast) { wb.giOrg[target] = mkf4(tr.giRo, 0.0f); wb.giD[target] = mkf4(tr.giRd, 1.0f); }   // (one origin per record here: the sort moves records between hits)
+            else wb.giD[target].w = -1.0f;
         }
     }
 }
 
 // ---- stage: gen_gi -------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat) {
+// rt_debug_gi_list: two sums over the bounce-hit generators -- (hit, sample) pairs visited, pairs shaded.  One lane per wave adds, once the entry switched counting on.
+RT_DEV void gi_list_stat_add(unsigned long long *stat, bool visited, bool shaded) {
+    const unsigned long long act = __ballot(1), vi = __ballot(visited), sh = __ballot(shaded);
+    if ((int)(threadIdx.x & 63) != __ffsll((long long)act) - 1) return;
+    if (vi) atomicAdd(&stat[0], (unsigned long long)__popcll(vi));
+    if (sh) atomicAdd(&stat[1], (unsigned long long)__popcll(sh));
+}
+__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
@@ -1761,8 +1807,9 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
     const uint32_t j = mine ? tid % live : 0;
     const uint32_t a = (uint32_t)s * wb.CH + j;
     const uint32_t ae = mine ? wb.gi_entry(s, j) : 0u;   // where this (hit, sample)'s bounce ray and its answer are
-    const bool bounced = mine && wb.giL[ae] >= 0.0f && wb.giTri[ae] >= 0;
+    const bool bounced = mine && wb.giD[ae].w >= 0.0f && wb.giTri[ae] >= 0;
     const uint32_t pos = block_append(bounced, giCount);   // compact the (hit, sample) pairs that need second-generation rays
+    if (listStat) gi_list_stat_add(listStat, mine, bounced);
     if (!mine) return;
     wb.giPos[a] = bounced ? (int)pos : -1;
     if (!bounced) return;
@@ -1778,10 +1825,44 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
             if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
 }
 
+// The same stage behind a bounce probe (RT_BOUNCE_PROBE, giPerm == null): the probe left the queue addresses of the bounce rays that hit in a dense list
+// (BounceProbeSrc::hitters, re-traced closest-hit since), so only those are visited -- on the bench view 54 419 of 29.6 M (hit, sample) pairs per launch set --
+// instead of every pair.  A fixed grid strides over the list, whose length only the device knows.  giPos is written for the pairs that bounced and for no other:
+// CombineTracer reads it behind gi() == 1 alone, k_gen_gi_overflow walks the same list.  Queue 2 positions are dealt in list order instead of pair order; an
+// entry's position is only ever reached through giPos, so frames do not change.
+__global__ __launch_bounds__(256) void k_gen_gi_listed(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *hitList, const uint32_t *hitCount,
+                                                       uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
+    const RtUniforms &u = fr->u;
+    const uint32_t n = min(*hitCount, wb.CH * (uint32_t)wb.SPP);
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {   // whole workgroups: block_append
+        const uint32_t i = base + threadIdx.x;
+        const bool mine = i < n;
+        const uint32_t a = mine ? hitList[i] : 0u;
+        const bool bounced = mine && wb.giTri[a] >= 0;
+        const uint32_t pos = block_append(bounced, giCount);
+        if (listStat) gi_list_stat_add(listStat, mine, bounced);
+        if (!bounced) continue;
+        const int s = (int)(a / wb.CH);
+        const uint32_t j = a % wb.CH;
+        wb.giPos[a] = (int)pos;
+        GenGiTracer tr;
+        tr.wb = wb; tr.sc = &fr->sc; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
+        HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+        const int SPP = max(u.spp, 1);
+        const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
+        Work w;
+        (void)oneBounceGIBVH<GenGiTracer, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
+        if (pos < wb.q2Stride)
+            for (int k = 0; k < 6; ++k)
+                if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
+    }
+}
+
 // Shadow queue 2 of a large launch set holds a PREDICTED number of bounce hits (rt_wave_render).  The (hit, sample) pairs beyond it -- none, unless the view changed so
 // that more than twice as many bounce rays hit as in any batch before -- get their six shadow rays traced right here, one thread per pair, with the megakernel's any-hit
 // walk (bvh_anyhit: the same answers as the any-hit launch, tests/test_gpu_parity.py), into occOvf.  Launched behind every k_gen_gi of such a set; returns at once when
-// nothing overflowed.
+// nothing overflowed.  Behind k_gen_gi_listed it walks the probe's hit list (hitList != null) as that kernel did: giPos of a pair outside the list is not written
+// there and may hold an earlier launch set's value.
 struct GenGiOverflowTracer {
     static constexpr bool kSkipUnlitDisk = true;
     RT_DEV void disk_stat(int, bool, bool) {}
@@ -1809,15 +1890,21 @@ struct GenGiOverflowTracer {
     }
     RT_DEV bool ao(int, V3, V3, float) { return false; }
 };
-__global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries) {
+__global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries,
+                                                         const uint32_t *hitList, const uint32_t *hitCount) {
     if (*giCount <= wb.q2Stride) return;      // the normal case: a small fixed grid that leaves at once (a grid of one thread per pair -- 29 000 workgroups for a batch of eight
                                               // 1080p frames -- cost 2 % of a frame just to be dispatched and return)
     const uint32_t live = chunk_live(wb, c0);
     if (live == 0) return;
-    const uint32_t n = live * (uint32_t)wb.SPP;
+    const uint32_t n = hitList ? min(*hitCount, wb.CH * (uint32_t)wb.SPP) : live * (uint32_t)wb.SPP;
     for (uint32_t tid = blockIdx.x * 256 + threadIdx.x; tid < n; tid += gridDim.x * 256) {
-        const int s = (int)(tid / live);
-        const uint32_t j = tid % live;
+        int s = (int)(tid / live);
+        uint32_t j = tid % live;
+        if (hitList) {
+            const uint32_t a = hitList[tid];
+            if (wb.giTri[a] < 0) continue;    // listed, but k_gen_gi_listed did not shade it: no giPos
+            s = (int)(a / wb.CH); j = a % wb.CH;
+        }
         const int gp = wb.giPos[(uint32_t)s * wb.CH + j];
         if (gp < 0 || (uint32_t)gp < wb.q2Stride) continue;
         GenGiOverflowTracer tr;
@@ -2008,6 +2095,9 @@ struct RtWave {
     unsigned long long probeBase[4] = {};     // rt_wave_bounce_probe's reset: the values above at that time
     unsigned long long *diskAcc = nullptr;    // device: rt_wave_disk_skip's ten sums (disk_stat_add); the generators count only once the entry was called
     bool diskStatOn = false;
+    unsigned long long *giListAcc = nullptr;  // device: rt_wave_gi_list's two sums (gi_list_stat_add); counted only once the entry was called
+    bool giListOn = false;
+    unsigned long long listedLaunches = 0, pairLaunches = 0, giListBase[2] = {0, 0};   // host: bounce-hit generator launches over the hit list / over every pair
     unsigned long long tracedProbeBase = 0;   // rt_wave_traced's reset: probeAcc[0] at that time (probed rays count as bounce rays there)
 };
 
@@ -2051,6 +2141,7 @@ void rt_wave_destroy(RtWave *w) {
     if (w->acc) (void)hipFree(w->acc);
     if (w->probeAcc) (void)hipFree(w->probeAcc);
     if (w->diskAcc) (void)hipFree(w->diskAcc);
+    if (w->giListAcc) (void)hipFree(w->giListAcc);
     if (w->stats) (void)hipFree(w->stats);
     if (w->hostHits) (void)hipHostFree(w->hostHits);
     delete w;
@@ -2092,13 +2183,16 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         w->slotsCap = nSlots;
     }
     // chunk capacity from the budget
-    const size_t perHit = (size_t)(S1 + SPP + S2) * 36 + (size_t)S1 + (size_t)SPP * 12 + (size_t)S2;
+    // bytes per hit: 36 per light ray (origin, direction, tMax word), 16 per dense ray (AO, bounce) + 16 per hit and dense group for its origin; results as before
+    const int L1 = S1 - A;                                     // light slots of shadow queue 1
+    const size_t giOrgs = w->binGi ? (size_t)SPP : 1;          // bounce origins per hit (RT_BIN_GI: one per record)
+    const size_t perHit = (size_t)(L1 + S2) * 36 + (size_t)(A + SPP) * 16 + (size_t)((A > 0 ? 1 : 0) + giOrgs) * 16 + (size_t)S1 + (size_t)SPP * 12 + (size_t)S2;
     const size_t CHbudget = align_up(std::min(nSlots, std::max<size_t>(w->budgetBytes / perHit, 4096)), 256);
     // ray records + liveness words (read by the traversal launches only: a SHARED arena can be handed on as soon as the last of them is done) ...
     // (shadow queue 2 -- six slots per bounce HIT -- is an allocation of its own since round 5: q2_bytes(entries per slot))
     auto rays_bytes = [&](size_t ch) {
-        return align_up(ch * (size_t)S1 * 32, 256) + align_up(ch * (size_t)SPP * 32, 256) +
-               align_up(ch * (size_t)S1 * 4, 256) + align_up(ch * (size_t)SPP * 4, 256) + 4096;
+        return align_up(ch * (size_t)L1 * 16, 256) + align_up(ch * (size_t)S1 * 16, 256) + align_up(ch * (size_t)L1 * 4, 256) + align_up(ch * 16, 256) +
+               align_up(ch * (size_t)SPP * 16, 256) + align_up(ch * giOrgs * 16, 256) + 4096;
     };
     auto q2_bytes = [&](size_t n) { return align_up(n * 6 * 16, 256) * 2 + align_up(n * 6 * 4, 256) + 4096; };
     // ... and the results k_combine reads (1 byte per any-hit ray, 8 per bounce ray, 4 per (hit, sample)) + the bounce probe's hit list (4 per bounce ray): the lane's own
@@ -2169,9 +2263,9 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
     auto carve = [&](size_t ch) {
         char *q = (char *)w->chunkArena;
         auto take = [&](size_t bytes) { char *r = q; q += align_up(bytes, 256); return r; };
-        wb.shO = (float4 *)take(ch * (size_t)S1 * 16); wb.shD = (float4 *)take(ch * (size_t)S1 * 16);
-        wb.giO = (float4 *)take(ch * (size_t)SPP * 16); wb.giD = (float4 *)take(ch * (size_t)SPP * 16);
-        wb.shT = (float *)take(ch * (size_t)S1 * 4); wb.giL = (float *)take(ch * (size_t)SPP * 4);
+        wb.shO = (float4 *)take(ch * (size_t)L1 * 16); wb.shD = (float4 *)take(ch * (size_t)S1 * 16);
+        wb.shT = (float *)take(ch * (size_t)L1 * 4); wb.aoOrg = (float4 *)take(ch * 16);
+        wb.giD = (float4 *)take(ch * (size_t)SPP * 16); wb.giOrg = (float4 *)take(ch * giOrgs * 16);
         const size_t n2 = n2_of(ch);
         wb.sh2O = (float4 *)take(n2 * 6 * 16); wb.sh2D = (float4 *)take(n2 * 6 * 16); wb.sh2T = (float *)take(n2 * 6 * 4);
         wb.q2Stride = (uint32_t)n2;
@@ -2197,7 +2291,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         wb.pendNrm = (uint2 *)p; p += nSlots * 8;
         wb.pendMy = (float *)p;
     }
-    wb.shO = wb.shD = wb.giO = wb.giD = wb.sh2O = wb.sh2D = nullptr; wb.shT = wb.giL = wb.sh2T = nullptr;   // (deferred: carved behind k_post_primary)
+    wb.shO = wb.shD = wb.aoOrg = wb.giD = wb.giOrg = wb.sh2O = wb.sh2D = nullptr; wb.shT = wb.sh2T = nullptr;   // (deferred: carved behind k_post_primary)
     wb.occ1 = wb.occ2 = wb.occOvf = nullptr; wb.giT = nullptr; wb.giTri = wb.giPos = wb.giPerm = nullptr; wb.giHit = nullptr;
     wb.q2Stride = 0;
     if (!deferred) {
@@ -2321,6 +2415,8 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
     const bool probe = u.enableGI == 1 && w->probeTree && (w->probeMode == 1 || (w->probeMode < 0 && q2Share > 0.0 && q2Share < kProbeShareMax));
     // the re-trace launch: a grid for about twice the expected hits (a persistent grid for ~1 % of the rays would mostly ramp up and drain)
     const unsigned retraceBlocks = q2Share > 0.0 ? (unsigned)std::max(32.0, std::min(1e6, 2.0 * q2Share * (double)CH * SPP / 2048.0)) : 0u;
+    // k_gen_gi_listed: one thread per listed hit for about twice the expected hits, between 32 workgroups and eight per CU; the grid strides over whatever the list holds
+    const unsigned listedBlocks = (unsigned)std::max(32.0, std::min((double)w->cus * 8.0, q2Share > 0.0 ? 2.0 * q2Share * (double)CH * SPP / 256.0 : (double)w->cus * 4.0));
     // shared arena: everything from here to the last combine reads or writes it
     if (w->pool && nChunks > 0 && w->pool->lastUser[w->arena] && w->pool->lastUser[w->arena] != st) W_TRY(hipStreamWaitEvent(st, w->pool->freeEv[w->arena], 0));
     for (int c = 0; c < nChunks; ++c) {
@@ -2336,21 +2432,21 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         const bool pkAO = w->packetAO && A > 0;
         if (pkAO) {
             PacketSrc pk;
-            pk.o = wb.shO; pk.d = wb.shD; pk.tm = wb.shT; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = A; pk.nLive = 0;
+            pk.o = nullptr; pk.d = wb.shD; pk.tm = nullptr; pk.org = wb.aoOrg; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = A; pk.nLive = 0;
             rt_stage_begin(ctx, ST_TRACE_AO, st);
             w->builds |= launch_packets(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pk, &wb.heads[(size_t)(1 + c * 4 + 3) * kHeadWords], w->acc + 7, w->acc + 14, tune);
             rt_stage_end(ctx, ST_TRACE_AO, 1, st);
         }
         const size_t skip = pkAO ? (size_t)A * CH : 0;
         QueueSrc q1;
-        q1.o = wb.shO + skip; q1.d = wb.shD + skip; q1.tm = wb.shT + skip; q1.liveCount = &wb.counts[1]; q1.c0 = c0; q1.cap = wb.CH; q1.stride = wb.CH;
+        q1.o = wb.shO; q1.d = wb.shD + skip; q1.tm = wb.shT; q1.org = wb.aoOrg; q1.orgStride = 0; q1.liveCount = &wb.counts[1]; q1.c0 = c0; q1.cap = wb.CH; q1.stride = wb.CH;
         q1.slots = (uint32_t)(S1 - (pkAO ? A : 0));
         q1.denseSlots = pkAO ? 0u : (uint32_t)A;
         q1.outT = nullptr; q1.outTri = nullptr; q1.outOcc = wb.occ1 + skip;
         if (u.enableGI == 1) {
             // bounce rays first, then ONE any-hit launch over both shadow queues
             QueueSrc qg;
-            qg.o = wb.giO; qg.d = wb.giD; qg.tm = wb.giL; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
+            qg.o = nullptr; qg.d = wb.giD; qg.tm = nullptr; qg.org = wb.giOrg; qg.orgStride = wb.giPerm ? wb.CH : 0u; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
             qg.outT = wb.giT; qg.outTri = wb.giTri; qg.outOcc = nullptr;
             rt_stage_begin(ctx, ST_TRACE_GI, st);
             if (probe) {
@@ -2359,9 +2455,9 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
                 pb.q = qg; pb.hitters = wb.giHit; pb.hitCount = &wb.counts[64 + w->chunkCap + c]; pb.inf = u.inf;
                 w->builds |= launch_trace<BounceProbeSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pb, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->probeAcc + 0, w->acc + 10, tune, S ? S + 32 : nullptr)
                              | ((uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT);
-                IndexedSrc rq;
-                rq.idx = wb.giHit; rq.count = pb.hitCount; rq.o = wb.giO; rq.d = wb.giD; rq.outT = wb.giT; rq.outTri = wb.giTri; rq.n = 0;
-                w->builds |= launch_trace<IndexedSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, rq, &wb.heads[(size_t)(1 + c * 4 + 2) * kHeadWords], w->probeAcc + 1, w->acc + 10, tune, nullptr, retraceBlocks);
+                IndexedDenseSrc rq;
+                rq.idx = wb.giHit; rq.count = pb.hitCount; rq.org = wb.giOrg; rq.d = wb.giD; rq.stride = wb.CH; rq.orgStride = qg.orgStride; rq.outT = wb.giT; rq.outTri = wb.giTri; rq.n = 0;
+                w->builds |= launch_trace<IndexedDenseSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, rq, &wb.heads[(size_t)(1 + c * 4 + 2) * kHeadWords], w->probeAcc + 1, w->acc + 10, tune, nullptr, retraceBlocks);
                 w->probeLaunches++;
             } else {
                 w->builds |= launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
@@ -2371,16 +2467,26 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
 
             W_TRY(hop(st, ss));
             rt_stage_begin(ctx, ST_GEN_GI, ss);
-            hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr);
+            // behind a probe the generator walks the probe's hit list (k_gen_gi_listed); RT_BIN_GI's permuted queue and sets without a probe visit every pair
+            const bool listed = probe && !wb.giPerm;
+            const uint32_t *hitList = listed ? wb.giHit : nullptr, *hitCount = listed ? &wb.counts[64 + w->chunkCap + c] : nullptr;
+            unsigned long long *listStat = w->giListOn ? w->giListAcc : nullptr;
+            if (listed) {
+                hipLaunchKernelGGL(k_gen_gi_listed, dim3(listedBlocks), dim3(256), 0, ss, dFrame, wb, c0, hitList, hitCount, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+                w->listedLaunches++;
+            } else {
+                hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+                w->pairLaunches++;
+            }
             if (wb.q2Stride < wb.CH * (uint32_t)SPP)   // a predicted capacity: the pairs beyond it (normally none) trace their rays in place
-                hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(treeDepth, 4) * 8, ss, dFrame, wb, c0, &wb.counts[64 + c], std::max(treeDepth, 4));
+                hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(treeDepth, 4) * 8, ss, dFrame, wb, c0, &wb.counts[64 + c], std::max(treeDepth, 4), hitList, hitCount);
             rt_stage_end(ctx, ST_GEN_GI, 1, ss);
             W_TRY(hop(ss, st));
 
             DualQueueSrc qq;
             qq.a = q1;
             qq.b.o = wb.sh2O; qq.b.d = wb.sh2D; qq.b.tm = wb.sh2T; qq.b.liveCount = &wb.counts[64 + c]; qq.b.c0 = 0; qq.b.cap = wb.q2Stride;
-            qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.denseSlots = 0u;
+            qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.denseSlots = 0u; qq.b.org = nullptr; qq.b.orgStride = 0;
             qq.b.outT = nullptr; qq.b.outTri = nullptr; qq.b.outOcc = wb.occ2;
             rt_stage_begin(ctx, ST_TRACE_SHADOW, st);
             w->builds |= launch_trace<DualQueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qq, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
@@ -2432,7 +2538,7 @@ void rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const
 uint32_t rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, bool any, const float4 *o, const float4 *d,
                              const float *tm, const uint32_t *liveCount, uint32_t n, float *outT, int *outTri, uint8_t *outOcc, uint32_t *heads) {
     QueueSrc q;
-    q.o = o; q.d = d; q.tm = tm; q.liveCount = liveCount; q.c0 = 0; q.cap = n; q.stride = n; q.slots = 1; q.denseSlots = 0;
+    q.o = o; q.d = d; q.tm = tm; q.liveCount = liveCount; q.c0 = 0; q.cap = n; q.stride = n; q.slots = 1; q.denseSlots = 0; q.org = nullptr; q.orgStride = 0;
     q.outT = outT; q.outTri = outTri; q.outOcc = outOcc; q.nLive = 0;
     const TraceTune tune = tune_from_env();
     if (any) return launch_trace<QueueSrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
@@ -2443,7 +2549,7 @@ uint32_t rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const DevFr
 uint32_t rt_wave_debug_packets(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const float4 *o, const float4 *d,
                                const float *tm, const uint32_t *liveCount, uint32_t nPackets, uint8_t *outOcc, uint32_t *heads) {
     PacketSrc pk;
-    pk.o = o; pk.d = d; pk.tm = tm; pk.occ = outOcc; pk.liveCount = liveCount; pk.c0 = 0; pk.cap = nPackets; pk.stride = nPackets; pk.A = 4; pk.nLive = 0;
+    pk.o = o; pk.d = d; pk.tm = tm; pk.org = nullptr; pk.occ = outOcc; pk.liveCount = liveCount; pk.c0 = 0; pk.cap = nPackets; pk.stride = nPackets; pk.A = 4; pk.nLive = 0;
     return launch_packets(st, cus, 100, treeDepth, dFrame, hostScene, pk, heads, nullptr, nullptr, tune_from_env());
 }
 // rt_trace_rays: n user rays through the production traversal launch of the environment's build (tune_from_env), the node form
@@ -2547,6 +2653,19 @@ int rt_wave_disk_skip(RtWave *w, hipStream_t st, unsigned long long *out10, bool
     W_TRY(hipMemcpy(out10, w->diskAcc, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (reset) W_TRY(hipMemset(w->diskAcc, 0, 10 * sizeof(unsigned long long)));
     w->diskStatOn = true;
+    return RT_OK;
+}
+
+int rt_wave_gi_list(RtWave *w, hipStream_t st, unsigned long long *out4, bool reset) {
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (!w) return RT_OK;
+    W_TRY(hipStreamSynchronize(st));
+    if (!w->giListAcc) { W_TRY(hipMalloc(&w->giListAcc, 2 * sizeof(unsigned long long))); W_TRY(hipMemset(w->giListAcc, 0, 2 * sizeof(unsigned long long))); }
+    W_TRY(hipMemcpy(out4, w->giListAcc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) W_TRY(hipMemset(w->giListAcc, 0, 2 * sizeof(unsigned long long)));
+    const unsigned long long l[2] = {w->listedLaunches, w->pairLaunches};
+    for (int i = 0; i < 2; ++i) { out4[2 + i] = l[i] - w->giListBase[i]; if (reset) w->giListBase[i] = l[i]; }
+    w->giListOn = true;
     return RT_OK;
 }
 

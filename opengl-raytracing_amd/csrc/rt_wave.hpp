@@ -38,6 +38,9 @@ int rt_wave_bounce_probe(RtWave *w, hipStream_t stream, unsigned long long *out4
 // The disk-light skip of the shading stages since the last reset, 10 words: for k_gen_direct [0] (hit, sample) pairs shaded [1] pairs with diskUnlit
 // [2] pairs whose wave skipped the disk loop [3] waves [4] waves that skipped; [5..9] the same for k_gen_gi.  The generators count from the first call on.
 int rt_wave_disk_skip(RtWave *w, hipStream_t stream, unsigned long long *out10, bool reset);
+// The bounce-hit generator (k_gen_gi / k_gen_gi_listed) since the last reset, 4 words: [0] (hit, sample) pairs it visited [1] pairs it shaded (their bounce ray hit)
+// [2] launches over the bounce probe's hit list [3] launches over every pair.  [0] and [1] count from the first call on.
+int rt_wave_gi_list(RtWave *w, hipStream_t stream, unsigned long long *out4, bool reset);
 // The share of bounce hits of earlier launch sets (what shadow queue 2 is sized from and the bounce probe is chosen by) belongs to a scene and a frame size:
 // rt_upload_bvh and rt_resize forget it (an spp change does so in rt_wave_render)
 void rt_wave_forget_share(RtWave *w);

@@ -537,8 +537,8 @@ int rt_mesh_rebuild(RtContext *ctx, const float *M16);
  * order.  Enqueued, ordered and installed exactly as rt_mesh_rebuild: no allocation, no host wait but the one status-word read of the quantised form
  * (RtMeshInfo.hostSyncs counts it; on failure RT_SCENE_QNODES_REJECTED), accumulation and bounce-share prediction kept.  RT_ERR_INVALID without a mesh
  * and before the first rt_mesh_rebuild of the current mesh; rt_mesh_upload / rt_upload_bvh forget the tree as they forget the mesh.
- * Tree quality is the caller's business: a refitted tree is exact for any deformation, but the further triangles move apart from where the last rebuild
- * found them, the more its boxes overlap and the slower it is to walk.  Rebuild from time to time. */
+ * A refitted tree is exact for any deformation, but the further triangles move apart from where the last rebuild found them, the more its boxes overlap
+ * and the slower it is to walk.  rt_mesh_measure / rt_mesh_quality measure that on the device and rt_mesh_update refits or rebuilds by it (below). */
 int rt_mesh_refit(RtContext *ctx, const float *M16);
 /* Refits since rt_mesh_upload and since the last rt_mesh_rebuild (either pointer may be NULL, not both).  RtMeshInfo.rebuilds counts rebuilds only. */
 int rt_mesh_refit_count(RtContext *ctx, uint64_t *total, uint64_t *sinceRebuild);
@@ -584,6 +584,49 @@ int rt_mesh_refit_parts(RtContext *ctx);
  * first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
 int rt_mesh_hit_parts(RtContext *ctx, const RtHit *hits, int n, int32_t *parts, int32_t *tris);
 int rt_mesh_hit_parts_host(RtContext *ctx, const RtHit *hits, int n, int32_t *parts, int32_t *tris);
+/* ---- tree quality: what refitting has cost the tree, measured on the device, and the refit-or-rebuild policy on top of it.
+ * The metric is rt_bvh_cost's (host side, below): the surface-area heuristic with both unit costs 1, in units of the root's area, summed as integers so
+ * that the device reproduces the host's bits.  It is a measurement: what ratio is worth a rebuild depends on the scene, and is the caller's argument. */
+typedef struct RtBvhCost {
+    uint64_t innerQ, leafQ;        /* sum of q over inner nodes / of q * count over leaves; q = floor(half-area * 2^(32 - rootExp)) */
+    double rootArea;               /* node 0's half-area dx*dy + dy*dz + dz*dx, in double */
+    double inner, leaf, cost;      /* innerQ, leafQ back in units of rootArea; cost = inner + leaf */
+    int32_t rootExp;               /* frexp's exponent of rootArea */
+    int32_t degenerate;            /* rootArea == 0: every sum is zero and means nothing */
+    int32_t nInner, nLeaves;
+} RtBvhCost;
+typedef struct RtMeshQuality {
+    RtBvhCost cost;
+    uint64_t update;               /* serial of the update that was measured: rebuilds + refits of the current mesh up to and including it */
+    int32_t refitsSinceRebuild;    /* of that update: 0 = the tree as its rebuild left it */
+    int32_t skipped;               /* rt_mesh_measure calls of the current mesh that found every result slot in flight */
+} RtMeshQuality;
+/* Enqueues the measurement of the current tree on rt_stream()'s stream: behind the update that wrote the boxes, before the next update (which waits for
+ * every lane).  No host wait (RtMeshInfo.hostSyncs does not move), no allocation: accumulators, a ring of RT_MESH_QUALITY_SLOTS pinned result slots and
+ * their events belong to the upload (RtMeshInfo.allocations).  When every slot is still in flight the call measures nothing, counts that
+ * (RtMeshQuality.skipped) and returns RT_OK.  RT_ERR_INVALID without a mesh (rt_upload_bvh releases it) or before the mesh's first rebuild. */
+#define RT_MESH_QUALITY_SLOTS 8
+int rt_mesh_measure(RtContext *ctx);
+/* which = RT_MESH_QUALITY_LATEST: the newest result that has arrived; RT_MESH_QUALITY_BASELINE: the result for the current tree as its last rebuild left
+ * it (refitsSinceRebuild == 0).  wait == 0 never blocks (it polls events) and returns RT_ERR_STATE when no such result has arrived; wait != 0 first
+ * waits for the newest enqueued measurement.  The doubles are computed on the host from the device's integer sums with rt_bvh_cost's expressions, so
+ * the record equals rt_bvh_cost of the host route's nodes12 bit for bit. */
+enum { RT_MESH_QUALITY_LATEST = 0, RT_MESH_QUALITY_BASELINE = 1 };
+int rt_mesh_quality(RtContext *ctx, int which, int wait, RtMeshQuality *out);
+/* One animation step: refit or rebuild, decided on the host from results that have already arrived, then a measurement of the new tree enqueued.
+ * mode = RT_MESH_UPDATE_SINGLE: gather under M16 (NULL: identity), as rt_mesh_rebuild / rt_mesh_refit; RT_MESH_UPDATE_PARTS: under the matrix table,
+ * as rt_mesh_rebuild_parts / rt_mesh_refit_parts (M16 must be NULL).  The update itself is the one of those four calls: ordering, install, counters and
+ * the quantised form's status read are theirs.  rebuildAbove has no default: NaN or a value below 1 is RT_ERR_INVALID.  The rule:
+ *   1. no tree: rebuild;
+ *   2. no arrived baseline for the current tree and none in flight: rebuild (so a tree built by the plain calls and never measured is replaced once);
+ *   3. the baseline in flight, or the baseline or the latest record degenerate: refit;
+ *   4. otherwise rebuild exactly when latest.cost > (double)rebuildAbove * baseline.cost, latest = the newest arrived result of the current tree.
+ * The call never waits, so the decision at step k rests on the tree of step k - 1 at the latest, and on an older one when the device lags; a caller who
+ * synchronises between steps gets a deterministic sequence.  *action (may be NULL) receives RT_MESH_DID_REFIT or RT_MESH_DID_REBUILD.
+ * The four plain update calls neither measure nor decide. */
+enum { RT_MESH_UPDATE_SINGLE = 0, RT_MESH_UPDATE_PARTS = 1 };
+enum { RT_MESH_DID_REFIT = 0, RT_MESH_DID_REBUILD = 1 };
+int rt_mesh_update(RtContext *ctx, int mode, const float *M16, float rebuildAbove, int *action);
 /* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
@@ -638,6 +681,14 @@ int rt_build_bvh_order(const float *tris9, int nTris, float *nodes12, float *tri
  * 0 .. nTris-1, or nodes that are not a tree in pre-order whose leaf ranges cover every row once.  With rt_upload_bvh it is a refit for hosts that
  * build on the CPU.  Returns RT_OK. */
 int rt_refit_bvh(const float *tris9, int nTris, const int32_t *order, float *nodes12, int nNodes, float *tris12);
+/* The quality metric of a tree, and the definition rt_mesh_quality is tested against.  nodes12 as rt_build_bvh, rt_build_bvh_gpu and rt_refit_bvh produce
+ * them: min in floats 0-2, max in floats 4-6, count in float 9 (> 0: a leaf).  Per node d = max - min in fp32, widened to double, half-area
+ * a = (dx*dy + dy*dz) + dz*dx (exact products; fp32 would overflow).  With A = node 0's half-area = m * 2^e (frexp), q = (uint64) floor(ldexp(a, 32 - e))
+ * <= 2^32; innerQ = sum of q over inner nodes, leafQ = sum of q * count over leaves, inner = ldexp((double)innerQ, e - 32) / A, leaf likewise,
+ * cost = inner + leaf.  Only integers are summed over nodes, so the result depends on the set of nodes, not on their order.  Below 2^28 triangles in
+ * leaves of at most 8 neither sum can reach 2^64.  A == 0: degenerate = 1, every sum zero.  RT_ERR_INVALID: a null pointer,
+ * nNodes <= 0, a negative count, a non-finite bound, a max below its min.  Needs no GPU.  Returns RT_OK. */
+int rt_bvh_cost(const float *nodes12, int nNodes, RtBvhCost *out);
 
 /* Stand-in for Model/Mesh + Assimp (include/scene/model.h:105-228) for plain .obj files: v / f records,
  * fan triangulation, negative indices.  Buffers are malloc'ed; release with rt_free. */

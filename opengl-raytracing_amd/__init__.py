@@ -165,6 +165,21 @@ class RtMeshInfo(_Struct):   # rt_get_mesh_info: the dynamic mesh and what its r
     _fields_ = [("nVerts", i32), ("nTris", i32)] + [(n, C.c_uint64) for n in ("rebuilds", "allocations", "hostSyncs", "scratchBytes", "sceneBytes")]
 
 
+class RtBvhCost(_Struct):   # rt_bvh_cost: the quality metric of a tree
+    _fields_ = [("innerQ", C.c_uint64), ("leafQ", C.c_uint64)] + [(n, C.c_double) for n in ("rootArea", "inner", "leaf", "cost")] + \
+               [(n, i32) for n in ("rootExp", "degenerate", "nInner", "nLeaves")]
+
+
+class RtMeshQuality(_Struct):   # rt_mesh_quality: one device measurement and the update it measured
+    _fields_ = [("cost", RtBvhCost), ("update", C.c_uint64), ("refitsSinceRebuild", i32), ("skipped", i32)]
+
+
+RT_MESH_QUALITY_SLOTS = 8
+RT_MESH_QUALITY_LATEST, RT_MESH_QUALITY_BASELINE = 0, 1
+RT_MESH_UPDATE_SINGLE, RT_MESH_UPDATE_PARTS = 0, 1
+RT_MESH_DID_REFIT, RT_MESH_DID_REBUILD = 0, 1
+
+
 # rt_debug_read_scene: the device scene arrays
 RT_SCENE_ARRAY_TRIS, RT_SCENE_ARRAY_PAIRS, RT_SCENE_ARRAY_NODES2, RT_SCENE_ARRAY_NODES2W, RT_SCENE_ARRAY_NODES4, RT_SCENE_ARRAY_QNODES4, RT_SCENE_ARRAY_LEAFBOX = range(7)
 SCENE_ARRAYS = {"tris": 0, "pairs": 1, "nodes2": 2, "nodes2w": 3, "nodes4": 4, "qnodes4": 5, "leafbox": 6}
@@ -314,6 +329,9 @@ SIGNATURES = {
     "rt_mesh_refit_parts": (C.c_int, [C.c_void_p]),
     "rt_mesh_hit_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_mesh_hit_parts_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_mesh_measure": (C.c_int, [C.c_void_p]),
+    "rt_mesh_quality": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(RtMeshQuality)]),
+    "rt_mesh_update": (C.c_int, [C.c_void_p, C.c_int, _FP, C.c_float, C.POINTER(C.c_int)]),
     "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
     "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
@@ -331,6 +349,7 @@ SIGNATURES = {
     "rt_build_bvh": (C.c_int, [_FP, C.c_int, _FP, _FP]),
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
+    "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -573,6 +592,17 @@ def refit_bvh(nodes12, tris12, order, tris9):
     return n, t
 
 
+def bvh_cost(nodes12) -> RtBvhCost:
+    """The quality metric of a tree (rt_bvh_cost): the surface-area heuristic with both unit costs 1, in units of the root's area, summed as integers
+    (innerQ, leafQ) so that Renderer.mesh_quality reproduces it bit for bit.  nodes12 as build_bvh / build_bvh_gpu / refit_bvh return them."""
+    n = _f32(nodes12).reshape(-1, 12)
+    out = RtBvhCost()
+    rc = lib().rt_bvh_cost(_fp(n) if n.shape[0] else None, n.shape[0], C.byref(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_bvh_cost: no nodes, a negative count, a non-finite bound or a max below its min")
+    return out
+
+
 def load_obj(path):
     pos, idx = _FP(), _U32P()
     nv, ni = C.c_int(), C.c_int()
@@ -752,11 +782,44 @@ class Renderer:
     def mesh_refit(self, model=None):
         """Keep the tree of the last mesh_rebuild and recompute what depends on coordinates -- triangles, every box, every record form -- from the
         current device positions and the model matrix (None: identity) (rt_mesh_refit).  Asynchronous like mesh_rebuild, at a fraction of its cost.
-        Exact for any deformation; the tree gets slower to walk as triangles move apart, so rebuild from time to time."""
+        Exact for any deformation; the tree gets slower to walk as triangles move apart: mesh_measure / mesh_quality measure that, and mesh_update
+        refits or rebuilds by it."""
         m = None if model is None else _f32(model).reshape(-1)
         if m is not None and m.size != 16:
             raise RtError(RT_ERR_INVALID, "mesh_refit: model must have 16 floats")
         self._check(lib().rt_mesh_refit(self._h, None if m is None else _fp(m)))
+
+    def mesh_measure(self):
+        """Enqueue the measurement of the current tree's quality on stream() (rt_mesh_measure): no host wait, no allocation.  When every result slot is
+        still in flight nothing is measured and mesh_quality().skipped counts it."""
+        self._check(lib().rt_mesh_measure(self._h))
+
+    def mesh_quality(self, which="latest", wait=True) -> RtMeshQuality:
+        """which="latest": the newest measurement that has arrived; "baseline": the one of the current tree as its last rebuild left it.  wait=False
+        never blocks and raises RtError(RT_ERR_STATE) when no such result has arrived; wait=True waits for the newest enqueued measurement first.
+        .cost equals bvh_cost of the host route's nodes bit for bit (rt_mesh_quality)."""
+        w = {"latest": RT_MESH_QUALITY_LATEST, "baseline": RT_MESH_QUALITY_BASELINE}.get(which)
+        if w is None:
+            raise RtError(RT_ERR_INVALID, f"mesh_quality: which must be 'latest' or 'baseline', got {which!r}")
+        out = RtMeshQuality()
+        self._check(lib().rt_mesh_quality(self._h, w, int(bool(wait)), C.byref(out)))
+        return out
+
+    def mesh_update(self, model=None, parts=False, *, rebuild_above):
+        """One animation step (rt_mesh_update): refit, or rebuild when the newest arrived measurement of the current tree costs more than rebuild_above
+        times what the tree cost as its rebuild left it; then enqueue a measurement of the result.  parts=True gathers under the device matrix table
+        (model must be None).  Never waits, so the decision rests on the previous step's tree at the latest.  rebuild_above has no default: what ratio
+        is worth a rebuild depends on the scene.  -> "refit" or "rebuild"."""
+        m = None if model is None else _f32(model).reshape(-1)
+        if m is not None and m.size != 16:
+            raise RtError(RT_ERR_INVALID, "mesh_update: model must have 16 floats")
+        action = C.c_int(-1)
+        self._check(lib().rt_mesh_update(self._h, RT_MESH_UPDATE_PARTS if parts else RT_MESH_UPDATE_SINGLE, None if m is None else _fp(m), float(rebuild_above),
+                                         C.byref(action)))
+        if action.value == RT_MESH_DID_REBUILD:
+            i = self.scene_info()
+            self.n_nodes, self.n_tris = i.nNodes, i.nTris
+        return "rebuild" if action.value == RT_MESH_DID_REBUILD else "refit"
 
     def mesh_refit_count(self):
         """-> (refits since mesh_upload, refits since the last mesh_rebuild)"""

@@ -18,6 +18,7 @@
 
 #include "../../include/rt_mi355.h"
 #include "rt_frame.hpp"
+#include "rt_bvh_cost.hpp"
 #include "rt_mesh.hpp"
 #include "rt_wave.hpp"
 
@@ -71,6 +72,13 @@ struct RtContext {
     hipEvent_t evMeshOrder = nullptr;      // the order array of the current tree has been written, on meshOrderStream
     hipStream_t meshOrderStream = nullptr;
     uint64_t meshRebuilds = 0, meshHostSyncs = 0, meshRefits = 0, meshRefitsSinceRebuild = 0;
+    // tree quality: which result slots of the mesh are in flight and what they measure; the arrived records the policy reads
+    struct MeshQSlot { bool inFlight = false; uint64_t update = 0, tree = 0; int32_t refits = 0; } meshQSlot[rtl::kQualityRing];
+    RtMeshQuality meshQLatest = {}, meshQBaseline = {};
+    bool meshQHaveLatest = false, meshQHaveBaseline = false;
+    uint64_t meshQLatestTree = 0, meshQBaselineTree = 0;   // RtMeshInfo.rebuilds when the measured tree was built
+    uint64_t meshQSkipped = 0, meshQEnqueued = 0;
+    int meshQNewest = -1;                                  // slot of the newest enqueued measurement
     // frame state
     FrameGeom g{};
     bool sized = false;
@@ -1172,6 +1180,15 @@ int rt_bvh_layout(int nTris, RtBvhLayout *out) {
     });
 }
 
+static void mesh_quality_reset(RtContext *c) {
+    for (auto &sl : c->meshQSlot) sl = RtContext::MeshQSlot{};
+    c->meshQLatest = c->meshQBaseline = RtMeshQuality{};
+    c->meshQHaveLatest = c->meshQHaveBaseline = false;
+    c->meshQLatestTree = c->meshQBaselineTree = 0;
+    c->meshQSkipped = c->meshQEnqueued = 0;
+    c->meshQNewest = -1;
+}
+
 // rt_mesh_upload (partFirst == null: one part holding everything) and rt_mesh_upload_parts
 static int mesh_upload(RtContext *c, const char *who, const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts) {
     if (!c) return RT_ERR_INVALID;
@@ -1206,6 +1223,7 @@ static int mesh_upload(RtContext *c, const char *who, const float *positions, in
         for (int i = 0; ok && i < c->nLanes; ++i) ok = hipEventCreateWithFlags(&c->evMeshLane[i], hipEventDisableTiming) == hipSuccess;
         if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "%s: event creation failed", who); }
         c->meshRebuilds = c->meshHostSyncs = c->meshRefits = c->meshRefitsSinceRebuild = 0;
+        mesh_quality_reset(c);
         return RT_OK;
     });
 }
@@ -1272,8 +1290,8 @@ int rt_mesh_set_positions(RtContext *c, const float *positions) {
 // A rebuild or a refit: the device work of rt_mesh.hip between the two halves of the event scheme, then the scene installed (the same pointers and
 // counts every time; what a refit can change is whether the quantised nodes could be built).
 // parts: gather under the device matrix table instead of under M16.
-static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = false) {
-    const char *who = parts ? (refit ? "rt_mesh_refit_parts" : "rt_mesh_rebuild_parts") : (refit ? "rt_mesh_refit" : "rt_mesh_rebuild");
+static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = false, const char *caller = nullptr) {
+    const char *who = caller ? caller : parts ? (refit ? "rt_mesh_refit_parts" : "rt_mesh_rebuild_parts") : (refit ? "rt_mesh_refit" : "rt_mesh_rebuild");
     if (!c) return RT_ERR_INVALID;
     if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", who);
     if (refit && !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree to keep (rt_mesh_rebuild first)", who);
@@ -1322,6 +1340,105 @@ int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16,
 int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
 int rt_mesh_rebuild_parts(RtContext *c) { return mesh_update(c, nullptr, false, true); }
 int rt_mesh_refit_parts(RtContext *c) { return mesh_update(c, nullptr, true, true); }
+
+// ---- tree quality
+static inline float key2f(uint32_t s) { const uint32_t u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s; float f; std::memcpy(&f, &u, 4); return f; }
+
+// Collects what has arrived, without waiting: an arrived slot's integers become a record (rt_bvh_cost's own expressions) and the slot is free again.
+static void mesh_quality_harvest(RtContext *c) {
+    const rtl::BvhLayout &L = rtl::mesh_layout(c->mesh);
+    for (int i = 0; i < rtl::kQualityRing; ++i) {
+        RtContext::MeshQSlot &sl = c->meshQSlot[i];
+        if (!sl.inFlight || hipEventQuery(rtl::mesh_quality_event(c->mesh, i)) != hipSuccess) continue;
+        sl.inFlight = false;
+        const rtl::QualityRecord r = *rtl::mesh_quality_record(c->mesh, i);
+        RtMeshQuality q = {};
+        RtBvhCost &k = q.cost;
+        k.nInner = L.nInner; k.nLeaves = (int32_t)L.nLeaves;
+        const double A = rtcost::half_area(key2f(r.rootKeys[3]) - key2f(r.rootKeys[0]), key2f(r.rootKeys[4]) - key2f(r.rootKeys[1]), key2f(r.rootKeys[5]) - key2f(r.rootKeys[2]));
+        k.rootArea = A;
+        if (A == 0.0) k.degenerate = 1;
+        else {
+            k.rootExp = rtcost::root_exp(A);
+            k.innerQ = r.innerQ; k.leafQ = r.leafQ;
+            k.inner = rtcost::from_sum(k.innerQ, k.rootExp, A);
+            k.leaf = rtcost::from_sum(k.leafQ, k.rootExp, A);
+            k.cost = k.inner + k.leaf;
+        }
+        q.update = sl.update; q.refitsSinceRebuild = sl.refits;
+        if (!c->meshQHaveLatest || q.update >= c->meshQLatest.update) { c->meshQLatest = q; c->meshQLatestTree = sl.tree; c->meshQHaveLatest = true; }
+        if (sl.refits == 0 && (!c->meshQHaveBaseline || sl.tree >= c->meshQBaselineTree)) { c->meshQBaseline = q; c->meshQBaselineTree = sl.tree; c->meshQHaveBaseline = true; }
+    }
+}
+
+static int mesh_measure(RtContext *c, const char *who) {
+    (void)hipSetDevice(c->cfg.device);
+    mesh_quality_harvest(c);
+    int slot = -1;
+    for (int i = 0; i < rtl::kQualityRing && slot < 0; ++i) if (!c->meshQSlot[i].inFlight) slot = i;
+    if (slot < 0) { ++c->meshQSkipped; return RT_OK; }
+    const char *err = nullptr;
+    const int rc = rtl::mesh_measure(c->mesh, c->lastStream ? c->lastStream : c->stream, slot, &err);
+    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
+    RtContext::MeshQSlot &sl = c->meshQSlot[slot];
+    sl.inFlight = true; sl.update = c->meshRebuilds + c->meshRefits; sl.tree = c->meshRebuilds; sl.refits = (int32_t)c->meshRefitsSinceRebuild;
+    c->meshQNewest = slot;
+    ++c->meshQEnqueued;
+    return RT_OK;
+}
+
+int rt_mesh_measure(RtContext *c) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_measure: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_measure: no tree to measure (rt_mesh_rebuild first)");
+    return mesh_measure(c, "rt_mesh_measure");
+}
+
+int rt_mesh_quality(RtContext *c, int which, int wait, RtMeshQuality *out) {
+    if (!c || !out) return RT_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (which != RT_MESH_QUALITY_LATEST && which != RT_MESH_QUALITY_BASELINE) return fail(c, RT_ERR_INVALID, "rt_mesh_quality: which = %d", which);
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_quality: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    if (wait && c->meshQNewest >= 0 && c->meshQSlot[c->meshQNewest].inFlight) HIP_TRY(c, hipEventSynchronize(rtl::mesh_quality_event(c->mesh, c->meshQNewest)));
+    mesh_quality_harvest(c);
+    if (which == RT_MESH_QUALITY_LATEST) {
+        if (!c->meshQHaveLatest) return fail(c, RT_ERR_STATE, "rt_mesh_quality: no measurement has arrived yet");
+        *out = c->meshQLatest;
+    } else {
+        if (!c->meshQHaveBaseline || c->meshQBaselineTree != c->meshRebuilds)
+            return fail(c, RT_ERR_STATE, "rt_mesh_quality: no measurement of the current tree as its rebuild left it has arrived");
+        *out = c->meshQBaseline;
+    }
+    out->skipped = (int32_t)c->meshQSkipped;
+    return RT_OK;
+}
+
+int rt_mesh_update(RtContext *c, int mode, const float *M16, float rebuildAbove, int *action) {
+    if (!c) return RT_ERR_INVALID;
+    if (mode != RT_MESH_UPDATE_SINGLE && mode != RT_MESH_UPDATE_PARTS) return fail(c, RT_ERR_INVALID, "rt_mesh_update: mode = %d", mode);
+    if (mode == RT_MESH_UPDATE_PARTS && M16) return fail(c, RT_ERR_INVALID, "rt_mesh_update: RT_MESH_UPDATE_PARTS gathers under the matrix table, M16 must be NULL");
+    if (!(rebuildAbove >= 1.0f)) return fail(c, RT_ERR_INVALID, "rt_mesh_update: rebuildAbove = %g (a ratio of costs, at least 1)", (double)rebuildAbove);
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_update: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    bool rebuild = true;
+    if (rtl::mesh_has_tree(c->mesh)) {
+        mesh_quality_harvest(c);
+        const bool haveBase = c->meshQHaveBaseline && c->meshQBaselineTree == c->meshRebuilds;
+        bool baseInFlight = false;
+        for (const auto &sl : c->meshQSlot) baseInFlight = baseInFlight || (sl.inFlight && sl.tree == c->meshRebuilds && sl.refits == 0);
+        if (haveBase) {
+            // a record of the current tree is at least as new as its baseline; one of an older tree cannot be newer
+            const RtMeshQuality &latest = (c->meshQHaveLatest && c->meshQLatestTree == c->meshRebuilds) ? c->meshQLatest : c->meshQBaseline;
+            if (c->meshQBaseline.cost.degenerate || latest.cost.degenerate) rebuild = false;
+            else rebuild = latest.cost.cost > (double)rebuildAbove * c->meshQBaseline.cost.cost;
+        } else rebuild = !baseInFlight;
+    }
+    const int rc = mesh_update(c, M16, !rebuild, mode == RT_MESH_UPDATE_PARTS, "rt_mesh_update");
+    if (rc != RT_OK) return rc;
+    if (action) *action = rebuild ? RT_MESH_DID_REBUILD : RT_MESH_DID_REFIT;
+    return mesh_measure(c, "rt_mesh_update");
+}
 
 int rt_mesh_refit_count(RtContext *c, uint64_t *total, uint64_t *sinceRebuild) {
     if (!c || (!total && !sinceRebuild)) return RT_ERR_INVALID;

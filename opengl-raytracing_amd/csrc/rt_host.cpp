@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_mi355.h"
+#include "rt_bvh_cost.hpp"
 
 namespace rthost {
 
@@ -527,6 +528,36 @@ int rt_refit_bvh(const float *tris9, int nTris, const int32_t *order, float *nod
     }
     return RT_OK;
     });
+}
+
+// The BVH quality metric: rt_bvh_cost.hpp's expressions over the reference's nodes.  A function of the set of nodes: integer sums only.
+int rt_bvh_cost(const float *nodes12, int nNodes, RtBvhCost *out) {
+    if (!out) return RT_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!nodes12 || nNodes <= 0) return RT_ERR_INVALID;
+    for (int i = 0; i < nNodes; ++i) {
+        const float *o = nodes12 + (size_t)i * 12;
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(o[a]) || !std::isfinite(o[4 + a]) || o[4 + a] < o[a]) return RT_ERR_INVALID;
+        if (!(o[9] >= 0.0f) || !std::isfinite(o[9])) return RT_ERR_INVALID;
+    }
+    auto area = [&](int i) { const float *o = nodes12 + (size_t)i * 12; return rtcost::half_area(o[4] - o[0], o[5] - o[1], o[6] - o[2]); };
+    for (int i = 0; i < nNodes; ++i) ++(nodes12[(size_t)i * 12 + 9] > 0.0f ? out->nLeaves : out->nInner);
+    const double A = area(0);
+    out->rootArea = A;
+    if (A == 0.0) { out->degenerate = 1; return RT_OK; }
+    const int e = rtcost::root_exp(A);
+    out->rootExp = e;
+    for (int i = 0; i < nNodes; ++i) {
+        const float count = nodes12[(size_t)i * 12 + 9];
+        const uint64_t q = rtcost::quantise(area(i), e);
+        if (count > 0.0f) out->leafQ += q * (uint64_t)count;
+        else out->innerQ += q;
+    }
+    out->inner = rtcost::from_sum(out->innerQ, e, A);
+    out->leaf = rtcost::from_sum(out->leafQ, e, A);
+    out->cost = out->inner + out->leaf;
+    return RT_OK;
 }
 
 int rt_build_bvh(const float *tris9, int nTris, float *nodes12, float *tris12) { return rt_build_bvh_order(tris9, nTris, nodes12, tris12, nullptr); }

@@ -254,6 +254,10 @@ struct Mesh {
     int permCur = -1;
     bool orderValid = false;
     uint32_t *hStatus = nullptr;   // pinned
+    // quality measurements: per result slot its accumulators on the device, its pinned record and the event behind the copy
+    unsigned long long *dQAcc = nullptr;
+    char *hQRec = nullptr;         // pinned
+    hipEvent_t evQ[kQualityRing] = {};
     std::vector<void *> owned;
     uint64_t allocations = 0;
     size_t scratchBytes = 0, sceneBytes = 0;
@@ -448,6 +452,11 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
     MESH_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->hStatus), 16, hipHostMallocDefault));
     ++m->allocations;
     *m->hStatus = 0u;
+    MESH_TRY(dev_alloc(m, &m->dQAcc, kQualityRing * kQualityRecordBytes, false, true));
+    MESH_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->hQRec), kQualityRing * kQualityRecordBytes, hipHostMallocDefault));
+    ++m->allocations;
+    std::memset(m->hQRec, 0, kQualityRing * kQualityRecordBytes);
+    for (int i = 0; i < kQualityRing; ++i) { MESH_TRY(hipEventCreateWithFlags(&m->evQ[i], hipEventDisableTiming)); ++m->allocations; }
     MESH_TRY(dev_alloc(m, &m->sc.wnodes, (size_t)std::max(nInner, 1) * 64, true, true));
     MESH_TRY(dev_alloc(m, &m->sc.wnodesW, (size_t)std::max(nInner, 1) * 64, true, true));
     MESH_TRY(dev_alloc(m, &m->sc.w4, L.nWide4 * 128, true, true));
@@ -467,6 +476,8 @@ void mesh_destroy(Mesh *m) {
     if (!m) return;
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
+    if (m->hQRec) (void)hipHostFree(m->hQRec);
+    for (hipEvent_t e : m->evQ) if (e) (void)hipEventDestroy(e);
     delete m;
 }
 
@@ -571,6 +582,18 @@ int mesh_hit_parts(Mesh *m, hipStream_t st, const int *order, const void *hits, 
     REB_TRY(hipGetLastError());
     return RT_OK;
 }
+
+int mesh_measure(Mesh *m, hipStream_t st, int slot, const char **err) {
+    if (m->permCur < 0 || slot < 0 || slot >= kQualityRing) return RT_ERR_INVALID;
+    const BvhLayout &L = m->lay;
+    REB_TRY(quality_launch(st, m->dBounds, m->dRefitKids, L.nNodes, m->dRefitLeaf, (int)L.nLeaves, m->dQAcc + (size_t)slot * (kQualityRecordBytes / 8),
+                           m->hQRec + (size_t)slot * kQualityRecordBytes));
+    REB_TRY(hipEventRecord(m->evQ[slot], st));
+    return RT_OK;
+}
+
+hipEvent_t mesh_quality_event(const Mesh *m, int slot) { return m->evQ[slot]; }
+const QualityRecord *mesh_quality_record(const Mesh *m, int slot) { return reinterpret_cast<const QualityRecord *>(m->hQRec + (size_t)slot * kQualityRecordBytes); }
 
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err) {
     REB_TRY(hipMemcpyAsync(m->hStatus, m->dStatus, 4, hipMemcpyDeviceToHost, st));

@@ -75,6 +75,19 @@ void parts_launch_refit_tris(hipStream_t st, const float *pos, const uint32_t *i
 void parts_launch_hit_parts(hipStream_t st, const void *hits, int n, const int *order, int nTris, const uint16_t *partOf, const int32_t *partFirst, int32_t *parts,
                             int32_t *tris);
 
+// rt_mesh_quality.hip: the quality metric of the tree in the bounds array.  One record = the two integer sums of rt_bvh_cost and the
+// root's six sortable keys, from which the host derives everything else.
+constexpr int kQualityRing = 8;                 // result slots: measurements that may be in flight at once
+constexpr size_t kQualityRecordBytes = 64;
+struct QualityRecord { uint64_t innerQ, leafQ; uint32_t rootKeys[6]; };
+hipError_t quality_launch(hipStream_t st, const uint32_t *bounds, const RefitKids *kids, int nNodes, const RefitLeaf *leaves, int nLeaves, unsigned long long *acc,
+                          void *pinned);
+// Enqueues the measurement of the current tree on `st` into result slot `slot` (its own accumulators, its own pinned record) and records the slot's
+// event behind it: no allocation, no host wait.  RT_ERR_INVALID without a tree.  mesh_quality_event / mesh_quality_record: what the host polls and reads.
+int mesh_measure(Mesh *m, hipStream_t st, int slot, const char **err);
+hipEvent_t mesh_quality_event(const Mesh *m, int slot);
+const QualityRecord *mesh_quality_record(const Mesh *m, int slot);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

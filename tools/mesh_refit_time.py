@@ -3,6 +3,7 @@ instead of rebuilt.
 
     python tools/mesh_refit_time.py [--reps N] [--out profiles/r09_mesh_refit.txt] [--sizes bunny,1m | none] [--no-frames]
     python tools/mesh_refit_time.py --parts 1,64,4096 [--reps N] [--out profiles/r10_mesh_parts.txt] [--sizes bunny,1m]
+    python tools/mesh_refit_time.py --quality [--reps N] [--out profiles/r12_mesh_quality.txt] [--sizes bunny,1m] [--no-frames]
 
 Per size (the bench mesh -- bunny stand-in, 81 920 triangles -- and the 1 M-triangle scene, where the quantised any-hit form is in use and both
 calls pay their one host wait), in one process and on one context: every step displaces the positions on the device, then runs rt_mesh_rebuild
@@ -19,6 +20,12 @@ matrix per part that changes every step (written into the device table on the li
 rt_mesh_rebuild / rt_mesh_rebuild_parts alternated on one context.  Conditions: the refit_parts median is below the rebuild median and its whole
 range below the rebuild minimum; the rebuild_parts median is at most the rebuild median plus that rebuild's own (max - min) spread of the run.
 refit_parts / refit is recorded without a bound.
+
+--quality measures the tree-quality path: per size, rt_mesh_rebuild, rt_mesh_refit, rt_mesh_refit + rt_mesh_measure and
+rt_mesh_measure alone, alternated on one context.  Condition: the refit + measure median is below the rebuild median and its whole range below the
+rebuild minimum.  Then (bench mesh only, unless --no-frames) the table of cost ratio against ms per frame: for the deformations of the frames table
+above plus four interleaved parts drifting apart, the refitted and the rebuilt tree's cost over the cost of the first build (rt_mesh_quality) beside
+their ms per frame.
 """
 import argparse
 import os
@@ -221,6 +228,144 @@ def frame_cost(lines, steps=(1, 8, 32), frames=48, batch=8):
     lines.append("")
 
 
+def measure_quality(name, v, f, reps, lines):
+    """Device time of rebuild, refit, refit + measure and measure alone, alternated on one context."""
+    import torch
+    dev = torch.device("cuda", 0)
+    v = np.ascontiguousarray(v, np.float32)
+    ext = np.float32((v.max(0) - v.min(0)).max())
+    M = rt.default_bvh_transform()
+    calls = ("rebuild", "refit", "refit_measure", "measure")
+    t = {c: [] for c in calls}
+    with rt.Renderer() as b:
+        b.mesh_upload(v, f)
+        stream = torch.cuda.ExternalStream(b.stream(), device=dev)
+        delta = torch.from_numpy(step_delta(v, ext, 0) * np.float32(0.1)).to(dev)
+        torch.cuda.synchronize()
+
+        def refit_measure():
+            b.mesh_refit(M)
+            b.mesh_measure()
+
+        run = {"rebuild": lambda: b.mesh_rebuild(M), "refit": lambda: b.mesh_refit(M), "refit_measure": refit_measure, "measure": b.mesh_measure}
+        for k in range(-3, reps):       # k < 0: warm-up
+            with torch.cuda.stream(stream):
+                b.mesh_positions().add_(delta if k % 2 else -delta)
+            for c in calls:
+                b.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                run[c]()
+                e1.record(stream)
+                b.synchronize()
+                if k >= 0:
+                    t[c].append(e0.elapsed_time(e1))
+        q = b.mesh_quality(wait=True)
+        mi, si = b.mesh_info(), b.scene_info()
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    lines.append(f"{name}: {np.asarray(f).size // 3} triangles, {si.nNodes} nodes; device time between events on the library stream; quantised any-hit form "
+                 f"{'in use (one host wait per update)' if mi.hostSyncs else 'not in use (no host wait)'}")
+    for c, label in zip(calls, ("rt_mesh_rebuild", "rt_mesh_refit", "rt_mesh_refit + rt_mesh_measure", "rt_mesh_measure alone")):
+        lines.append(fmt(label, t[c]))
+    med = {c: statistics.median(t[c]) for c in calls}
+    ok = med["refit_measure"] < med["rebuild"] and max(t["refit_measure"]) < min(t["rebuild"])
+    lines.append(f"  rebuild / (refit + measure) {med['rebuild'] / med['refit_measure']:.1f}x   (refit + measure) - refit {med['refit_measure'] - med['refit']:.3f} ms      "
+                 f"measurements skipped {q.skipped}, allocations {mi.allocations} (all in rt_mesh_upload), hostSyncs {mi.hostSyncs} (the updates' own)")
+    lines.append(f"  condition (refit + measure median < rebuild median, refit + measure max {max(t['refit_measure']):.3f} < rebuild min {min(t['rebuild']):.3f}): "
+                 f"{'MET' if ok else 'MISSED'}")
+    lines.append("")
+    return ok
+
+
+def quality_frames(lines, steps=(1, 8, 32), frames=48, batch=8):
+    """Cost ratio (rt_mesh_quality) beside ms per frame of the bench view: a refitted tree against one rebuilt over the same positions."""
+    v, f = rt.meshgen.bunny_standin(6)
+    v = np.ascontiguousarray(v, np.float32)
+    tri = np.asarray(f, np.uint32).reshape(-1, 3)
+    nparts = 4
+    runs = [tri[p::nparts] for p in range(nparts)]          # four parts interleaved in space: triangle i in part i % 4
+    f = np.concatenate(runs).reshape(-1)
+    pf = np.concatenate([[0], np.cumsum([r.shape[0] for r in runs])]).astype(np.int32)
+    ext = np.float32((v.max(0) - v.min(0)).max())
+    D = np.asarray(rt.default_bvh_transform(), np.float64).reshape(4, 4).T
+    W, H = 1920, 1080
+    p = rt.default_render_params()
+    p.sppPerFrame = 4
+    cam = scenes.camera("closeup", aspect=W / H)
+    L = rt.bvh_layout(tri.shape[0])
+    us = [rt.frame_uniforms(p, cam, W, H, k, True, L.nNodes, L.nTris) for k in range(frames + batch)]
+
+    def table(drift):
+        """The matrix table: the default transform, part p moved by p * drift * extent along x in object space."""
+        T = np.tile(np.eye(4), (nparts, 1, 1))
+        T[:, 0, 3] = np.arange(nparts) * drift * float(ext)
+        return np.ascontiguousarray(np.transpose(D @ T, (0, 2, 1)), np.float32).reshape(nparts, 16)
+
+    def ms_per_frame(r):
+        for _ in range(4):               # 32 frames of warm-up: the frames re-learn their bounce share and re-size their arenas after a change of scene
+            r.render_frames(us[:batch])
+        r.synchronize()
+        best = None
+        for _ in range(2):
+            t0 = time.perf_counter()
+            for k in range(batch, batch + frames, batch):
+                r.render_frames(us[k:k + batch])
+            r.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / frames
+            best = ms if best is None else min(best, ms)
+        return best
+
+    lines.append(f"cost ratio against frame time: bench mesh in {nparts} interleaved parts, bench view {W}x{H}, {p.sppPerFrame} spp, {frames} frames in batches of "
+                 f"{batch} after 32 of warm-up, wall / frame, better of two passes; cost = rt_mesh_quality's, over the cost of the first build")
+    rows = []
+    with rt.Renderer() as b, rt.Renderer() as c:     # b is refitted, c is rebuilt over the same positions and matrices
+        for r in (b, c):
+            r.upload_env(scenes.env_faces("Sky_01"))
+            r.resize(W, H)
+            r.mesh_upload_parts(v, f, pf)
+            r.mesh_set_part_matrices(table(0.0))
+            r.mesh_rebuild_parts()
+            r.mesh_measure()
+        base = b.mesh_quality(wait=True).cost.cost
+        lines.append(f"  first build: cost {base:.3f} (inner {b.mesh_quality().cost.inner:.3f}, leaf {b.mesh_quality().cost.leaf:.3f})   "
+                     f"context b {ms_per_frame(b):8.3f} ms   context c {ms_per_frame(c):8.3f} ms")
+
+        def row(label):
+            b.mesh_refit_parts(); b.mesh_measure()
+            c.mesh_rebuild_parts(); c.mesh_measure()
+            qb, qc = b.mesh_quality(wait=True).cost.cost / base, c.mesh_quality(wait=True).cost.cost / base
+            mb, mc = ms_per_frame(b), ms_per_frame(c)
+            agree = (qb > qc) == (mb > mc)
+            rows.append((qb / qc, mb / mc))
+            lines.append(f"  {label:<44s} refitted: cost {qb:7.3f}  {mb:8.3f} ms   rebuilt: cost {qc:7.3f}  {mc:8.3f} ms   cost ratio {qb / qc:6.3f}  "
+                         f"time ratio {mb / mc:6.3f}  {'same side of 1' if agree else 'OPPOSITE sides of 1'}")
+
+        pos, done = v, 0
+        for n in steps:
+            for k in range(done, n):
+                pos = (pos + step_delta(pos, ext, k)).astype(np.float32)
+            done = n
+            for r in (b, c):
+                r.mesh_set_positions(pos)
+            row(f"smooth animation, {n} steps of 3 % of the extent")
+        for frac in (0.02, 0.1):
+            noisy = (pos + np.random.default_rng(1).normal(0, frac * ext, pos.shape)).astype(np.float32)
+            for r in (b, c):
+                r.mesh_set_positions(noisy)
+            row(f"random displacement, sigma {frac:4.2f} of the extent")
+        for r in (b, c):                 # back to the rest pose and a fresh tree, then the parts drift apart
+            r.mesh_set_positions(v)
+            r.mesh_rebuild_parts()
+        for drift in (0.05, 0.25, 1.0):
+            for r in (b, c):
+                r.mesh_set_part_matrices(table(drift))
+            row(f"parts {drift:4.2f} of the extent apart")
+    order = sorted(rows)
+    monotone = all(order[i][1] <= order[i + 1][1] for i in range(len(order) - 1))
+    lines.append(f"  rows ordered by cost ratio: time ratios {' '.join(f'{t:.3f}' for _, t in order)} -- {'ascending too' if monotone else 'NOT ascending'}")
+    lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=12)
@@ -228,7 +373,22 @@ def main():
     ap.add_argument("--sizes", default="bunny,1m")
     ap.add_argument("--no-frames", action="store_true")
     ap.add_argument("--parts", default=None, help="comma-separated part counts: time the part-aware calls against the single-matrix ones instead")
+    ap.add_argument("--quality", action="store_true", help="time rt_mesh_measure and print the table of cost ratio against frame time")
     args = ap.parse_args()
+    if args.quality:
+        lines = [f"mesh_refit_time.py --quality --reps {args.reps}: rebuild, refit, refit + measure and measure alternated on one context, one process", ""]
+        ok = True
+        for s in [x for x in args.sizes.split(",") if x and x != "none"]:
+            v, f = rt.meshgen.bunny_standin(6) if s == "bunny" else rt.meshgen.million_triangle_scene()
+            ok = measure_quality("bench mesh" if s == "bunny" else "1 M scene", v, f, max(args.reps, 1), lines) and ok
+        if not args.no_frames:
+            quality_frames(lines)
+        text = "\n".join(lines)
+        print(text)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(text + "\n")
+        return 0 if ok else 1
     if args.parts:
         lines = [f"mesh_refit_time.py --parts {args.parts} --reps {args.reps}: refit, refit_parts, rebuild and rebuild_parts alternated on one context, one process", ""]
         ok = True

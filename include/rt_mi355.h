@@ -425,6 +425,36 @@ int rt_get_raster_stats(RtContext *ctx, RtRasterStats *out);
 /* Diagnostics used by the tests: the bin arrays of the following rt_render_raster calls hold exactly `pairs` (tile, triangle) pairs,
  * so that the path past the capacity runs; 0 returns to automatic sizing. */
 int rt_debug_raster_bin_capacity(RtContext *ctx, uint64_t pairs);
+/* ---- raster draws of the dynamic mesh.  Bind a raster mesh slot to the context's dynamic mesh (rt_mesh_upload /
+ * rt_mesh_upload_parts): draws naming the slot read the mesh's device positions and indices where they lie -- no copy, no index validation
+ * (the upload did it), no allocation, no host wait.  A bound draw d is, by definition, the run of draws, one per non-empty part p in part
+ * order, that rt_render_raster would execute from static slots holding the mesh's device positions as they stand when the call's setup work
+ * runs on the stream, the index triples [partFirst[p], partFirst[p+1]), model = rt_mat4_mul(d.model, table[p]) with the table
+ * (rt_mesh_part_matrices) as it stands at that moment, and the part's colour if a colour table is set, else d.color: every buffer and every
+ * RtRasterStats count equal that list's bit for bit.  Input triangle t of the draw is global primitive base + t (base: the triangles of the
+ * draws before d), so primId - base indexes the caller's index buffer and its part is rt_mesh_hit_parts' (the part whose range holds it).
+ *   The binding is to "the context's dynamic mesh", resolved at each rt_render_raster: it follows a later rt_mesh_upload / rt_mesh_upload_parts
+ * without rebinding, and a draw naming a bound slot while there is no mesh (never uploaded, released, or released by rt_upload_bvh) is
+ * RT_ERR_STATE with nothing enqueued, as for an empty slot.  No tree is needed: positions, indices, the part lookup and the matrix table are
+ * read, never the BVH, so a bound draw works before the first rt_mesh_rebuild.  rt_raster_mesh on a bound slot replaces the binding (nVerts == 0
+ * unbinds); binding a slot that holds an uploaded mesh frees that mesh (after the wait rt_raster_mesh makes).  Several slots may be bound, in
+ * either mode; RT_RASTER_BIND_PARTS on a mesh from plain rt_mesh_upload is its one part; a bound slot may be passed to rt_raster_scene_draws.
+ *   Ordering: a raster call that names a bound slot sees every rt_mesh_set_positions / rt_mesh_set_part_matrices and every write of the caller
+ * ordered on rt_stream()'s stream -- as it was when they were enqueued -- before the call, and is finished with positions and matrices before
+ * any such write or mesh update enqueued after it; both by events, with no host wait.  Calls that name no bound slot gain no wait.
+ *   RT_ERR_INVALID: a slot outside 0..RT_MAX_RASTER_MESHES-1, a mode other than the two. */
+#define RT_RASTER_BIND_SINGLE 0   /* the draw's model matrix for every triangle, as rt_mesh_rebuild(ctx, M) gathers; the matrix table is not touched */
+#define RT_RASTER_BIND_PARTS  1   /* per part p: model_p = rt_mat4_mul(draw.model, table[p]), table = rt_mesh_part_matrices() */
+int rt_raster_mesh_dynamic(RtContext *ctx, int slot, int mode);
+/* Optional flat colour per part for a slot bound with RT_RASTER_BIND_PARTS: nParts x 3 floats (host), packed as the draw colour is (unorm8 of
+ * clamp) and kept on the device; rgb == NULL or nParts == 0 returns to the draw's own colour.  May wait for a raster call in flight and
+ * allocate.  RT_ERR_INVALID: a slot not bound in parts mode, a negative count.  A table whose count differs from the mesh's part count when a
+ * draw uses it makes that rt_render_raster RT_ERR_STATE (nothing enqueued; the previous raster frame stays readable). */
+int rt_raster_part_colors(RtContext *ctx, int slot, const float *rgb, int nParts);
+/* Device pointers of the last raster frame (RGBA8, primitive id, depth24; width x height uint32 each, row 0 = bottom), valid until the next
+ * rt_render_raster that grows them or rt_resize; reads must be ordered on rt_stream()'s stream.  Any pointer may be NULL.  RT_ERR_STATE as
+ * rt_read_raster.  No host wait. */
+int rt_raster_targets(RtContext *ctx, void **rgba8, void **primId, void **depth24, size_t *bytesEach);
 
 /* ---------------------------------------------------------------- ray queries against the uploaded BVH
  * "Here are N rays; what does each one hit?" through the persistent traversal kernels the frames use (same node form and build).

@@ -211,6 +211,7 @@ class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
 RT_MAX_RASTER_MESHES = 8
 RT_MAX_MESH_PARTS = 65535   # rt_mesh_upload_parts
 RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
+RT_RASTER_BIND_SINGLE, RT_RASTER_BIND_PARTS = 0, 1   # rt_raster_mesh_dynamic
 
 
 class RtRasterDraw(_Struct):   # one glDrawElements of renderRaster (src/render/render.cpp:244-295)
@@ -277,6 +278,9 @@ SIGNATURES = {
     "rt_read_raster": (C.c_int, [C.c_void_p, _U8P, _U32P, _U32P]),
     "rt_get_raster_stats": (C.c_int, [C.c_void_p, C.POINTER(RtRasterStats)]),
     "rt_debug_raster_bin_capacity": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "rt_raster_mesh_dynamic": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rt_raster_part_colors": (C.c_int, [C.c_void_p, C.c_int, _FP, C.c_int]),
+    "rt_raster_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),
     "rt_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rt_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -484,6 +488,19 @@ def raster_draw(mesh, model=None, color=(1.0, 1.0, 1.0)) -> RtRasterDraw:
     for i in range(3):
         d.color[i] = float(color[i])
     return d
+
+
+def raster_prim_parts(prim_id, base, part_first):
+    """Primitive ids of a raster frame -> (part, tri), int32 arrays of prim_id's shape, for a draw of a slot bound to the dynamic mesh
+    (Renderer.raster_mesh_dynamic): base is the number of triangles of the draws before it, part_first the mesh's boundaries (mesh_parts()).  The
+    draw's input triangle is prim_id - base; part is the part whose range holds it and tri its index within that part, mesh_hit_parts' meaning
+    (part_first[part] + tri indexes the caller's index buffer).  (-1, -1) outside the draw's range and on the background.  Pure numpy."""
+    pf = np.asarray(part_first, np.int64).reshape(-1)
+    prim = np.asarray(prim_id)
+    t = prim.astype(np.int64) - int(base)
+    ok = (prim != RASTER_BACKGROUND) & (t >= 0) & (t < pf[-1])
+    part = np.searchsorted(pf, np.where(ok, t, 0), "right") - 1
+    return np.where(ok, part, -1).astype(np.int32), np.where(ok, t - pf[part], -1).astype(np.int32)
 
 
 def generate_jitter(frame_index: int) -> np.ndarray:
@@ -1361,6 +1378,55 @@ class Renderer:
         p = _f32(positions).reshape(-1, 3)
         i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
         self._check(lib().rt_raster_mesh(self._h, slot, _fp(p), p.shape[0], i.ctypes.data_as(_U32P), i.size))
+
+    def raster_mesh_dynamic(self, slot, parts=False, colors=None):
+        """Bind a raster mesh slot to the dynamic mesh (rt_raster_mesh_dynamic): draws naming it read mesh_positions() and the
+        uploaded indices where they lie.  parts=False: the draw's model for every triangle; parts=True: draw.model times each part's matrix of
+        mesh_part_matrices().  colors ([nParts,3], parts=True only): a flat colour per part instead of the draw's.  The binding follows later
+        mesh_upload / mesh_upload_parts calls; raster_mesh(slot, None) unbinds."""
+        self._check(lib().rt_raster_mesh_dynamic(self._h, int(slot), RT_RASTER_BIND_PARTS if parts else RT_RASTER_BIND_SINGLE))
+        if colors is not None:
+            self.raster_part_colors(slot, colors)
+
+    def raster_part_colors(self, slot, colors):
+        """A flat colour per part ([nParts,3] floats, packed as a draw's colour is) for a slot bound with parts=True; None returns to the draw's
+        colour (rt_raster_part_colors).  The count must equal the mesh's part count when a draw uses the table."""
+        if colors is None:
+            self._check(lib().rt_raster_part_colors(self._h, int(slot), None, 0))
+            return
+        c = _f32(colors)
+        if c.size % 3:
+            raise RtError(RT_ERR_INVALID, "raster_part_colors: colors must hold 3 floats per part")
+        c = c.reshape(-1, 3)
+        self._check(lib().rt_raster_part_colors(self._h, int(slot), _fp(c), c.shape[0]))
+
+    def raster_targets(self, as_torch=None):
+        """(rgba8 [H,W,4] uint8, prim_id [H,W], depth24 [H,W]) of the last raster frame, row 0 = bottom (rt_raster_targets).  With torch
+        (as_torch=None: when it imports) tensors that alias the device buffers, zero-copy and without a host wait: torch's current stream is made to
+        wait for the library stream, as trace_rays does it; prim_id and depth24 are int32 views of the uint32 words (the background id reads -1).
+        They are valid until a raster call grows the buffers or resize().  Else numpy copies (read_raster)."""
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_raster_targets(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        if not as_torch:
+            return self.read_raster()
+        import torch
+        dev = torch.device("cuda", self.device)
+        h, w = self.height, self.width
+
+        def view(ptr, shape, typestr):
+            class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+                __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+            return torch.as_tensor(_View(), device=dev)
+
+        out = view(a.value, (h, w, 4), "|u1"), view(b.value, (h, w), "<i4"), view(c.value, (h, w), "<i4")
+        torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(self.stream(), device=dev))   # torch's reads see the raster frame
+        return out
 
     def render_raster_async(self, draws, view, proj):
         arr = (RtRasterDraw * max(len(draws), 1))(*draws)

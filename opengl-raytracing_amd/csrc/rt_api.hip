@@ -1267,6 +1267,7 @@ int rt_mesh_set_part_matrices(RtContext *c, int first, int count, const float *M
     if (count == 0) return RT_OK;
     if (!M16s) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: null matrices");
     (void)hipSetDevice(c->cfg.device);
+    if (c->raster && rt_raster_order_after(c->raster, c->lastStream ? c->lastStream : c->stream) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_set_part_matrices: %s", rt_raster_error(c->raster));
     HIP_TRY(c, hipMemcpyAsync(rtl::mesh_part_matrices(c->mesh) + (size_t)first * 16, M16s, (size_t)count * 64, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
     return RT_OK;
 }
@@ -1283,6 +1284,7 @@ int rt_mesh_set_positions(RtContext *c, const float *positions) {
     if (!c || !positions) return RT_ERR_INVALID;
     if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_set_positions: no mesh (rt_mesh_upload first)");
     (void)hipSetDevice(c->cfg.device);
+    if (c->raster && rt_raster_order_after(c->raster, c->lastStream ? c->lastStream : c->stream) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_set_positions: %s", rt_raster_error(c->raster));
     HIP_TRY(c, hipMemcpyAsync(rtl::mesh_positions(c->mesh), positions, (size_t)rtl::mesh_verts(c->mesh) * 12, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
     return RT_OK;
 }
@@ -1703,6 +1705,9 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     if (c->timing) c->timedFrames += batch;
     c->frameIndex += batch;          // Accum::swapAfterFrame, include/render/accum.h:125-128
     c->writeIdx = (c->writeIdx + 1) % c->nLanes;
+    // rt_stream() is this lane from here on: device writes to the dynamic mesh that the caller orders on it must find a raster call that read the
+    // mesh on another lane finished.  Nothing is enqueued unless such a call is in flight; the frame itself does not wait.
+    if (c->raster && rt_raster_order_after(c->raster, st) != RT_OK) return fail(c, RT_ERR_HIP, "%s", rt_raster_error(c->raster));
     return RT_OK;
 }
 
@@ -1953,7 +1958,44 @@ int rt_render_raster(RtContext *c, const RtRasterDraw *draws, int nDraws, const 
     (void)hipSetDevice(c->cfg.device);
     if (!c->raster) c->raster = rt_raster_create();
     hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    const int rc = rt_raster_render(c->raster, st, c->g.W, c->g.H, draws, nDraws, view16, proj16);
+    // the dynamic mesh as it is now (a binding follows a later rt_mesh_upload): its arrays, and mesh_update's per-lane events for the other lanes.  Whoever
+    // releases the mesh has waited for every lane, and this call runs on one, so no array is freed under it.
+    RtRasterDynamic dyn = {};
+    if (c->mesh) {
+        dyn.pos = rtl::mesh_positions(c->mesh); dyn.idx = rtl::mesh_indices(c->mesh); dyn.partOf = rtl::mesh_part_of(c->mesh); dyn.partM = rtl::mesh_part_matrices(c->mesh);
+        dyn.nTris = rtl::mesh_layout(c->mesh).nTris; dyn.nParts = rtl::mesh_part_count(c->mesh);
+        for (int i = 0; i < c->nLanes; ++i)
+            if (c->lanes[i] != st) { dyn.others[dyn.nOthers] = c->lanes[i]; dyn.evOther[dyn.nOthers] = c->evMeshLane[i]; ++dyn.nOthers; }
+    }
+    const int rc = rt_raster_render(c->raster, st, c->g.W, c->g.H, draws, nDraws, view16, proj16, c->mesh ? &dyn : nullptr);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_raster_mesh_dynamic(RtContext *c, int slot, int mode) {
+    if (!c) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    if (!c->raster) c->raster = rt_raster_create();
+    const int rc = rt_raster_bind_dynamic(c->raster, slot, mode);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_raster_part_colors(RtContext *c, int slot, const float *rgb, int nParts) {
+    if (!c) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    if (!c->raster) c->raster = rt_raster_create();
+    const int rc = rt_raster_set_part_colors(c->raster, slot, rgb, nParts);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
+}
+
+int rt_raster_targets(RtContext *c, void **rgba8, void **primId, void **depth24, size_t *bytesEach) {
+    if (!c) return RT_ERR_INVALID;
+    if (rgba8) *rgba8 = nullptr;
+    if (primId) *primId = nullptr;
+    if (depth24) *depth24 = nullptr;
+    if (bytesEach) *bytesEach = 0;
+    if (!c->raster) return fail(c, RT_ERR_STATE, "rt_raster_targets before rt_render_raster");
+    if (!c->sized) return fail(c, RT_ERR_STATE, "rt_raster_targets before rt_resize");
+    const int rc = rt_raster_buffers(c->raster, c->g.W, c->g.H, rgba8, primId, depth24, bytesEach);
     return rc == RT_OK ? RT_OK : fail(c, rc, "%s", rt_raster_error(c->raster));
 }
 

@@ -488,6 +488,8 @@ int mesh_verts(const Mesh *m) { return m->nVerts; }
 int mesh_part_count(const Mesh *m) { return (int)m->partFirst.size() - 1; }
 const int32_t *mesh_part_first(const Mesh *m) { return m->partFirst.data(); }
 float *mesh_part_matrices(Mesh *m) { return m->dPartM; }
+const uint32_t *mesh_indices(const Mesh *m) { return m->dIdx; }
+const uint16_t *mesh_part_of(const Mesh *m) { return m->dPartOf; }
 uint64_t mesh_allocations(const Mesh *m) { return m->allocations; }
 size_t mesh_scratch_bytes(const Mesh *m) { return m->scratchBytes; }
 size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }

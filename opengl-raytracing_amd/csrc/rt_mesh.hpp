@@ -44,6 +44,8 @@ size_t mesh_scene_bytes(const Mesh *m);
 int mesh_part_count(const Mesh *m);
 const int32_t *mesh_part_first(const Mesh *m);   // host copy, nParts + 1 entries
 float *mesh_part_matrices(Mesh *m);               // device, nParts x 16 floats, column-major
+const uint32_t *mesh_indices(const Mesh *m);      // device, the uploaded index triples (validated on upload)
+const uint16_t *mesh_part_of(const Mesh *m);      // device, [input triangle] -> part
 // Enqueues gather, build and record emission on `st`: no allocation, no host wait.  The gather is the single-matrix one under M16 (column-major), or,
 // with M16 == nullptr, the part-aware one under the matrix table as it stands when the kernel runs.  mesh_refit takes the same argument.
 int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err);

@@ -2,7 +2,9 @@
 // basic.vert / basic.frag with GL_LESS on a D24 buffer.  The rules (mirrored by tests/raster_ref.py) are exact integer /
 // fixed-order fp32 arithmetic, so every triangle's contribution to a pixel is a 64-bit key (d24 << 32 | global primitive index) and a
 // pixel keeps the smallest: the kernels may visit triangles in any order and the frame is still GL's in-order result.
-//   k_rs_setup   one lane per triangle of one draw: index fetch, MVP, clip (near + guard band), snap, tile rectangle, record
+//   k_rs_part_mvp  (draws of a slot bound to the dynamic mesh in parts mode) one lane per part: the part's MVP from the device matrix table
+//   k_rs_setup   one lane per triangle of one draw: index fetch, MVP, clip (near + guard band), snap, tile rectangle, record; a template over where
+//                the MVP and the colour come from (StaticDraw: the kernel arguments; PartsDraw: the triangle's part)
 //   scan         rocprim exclusive scan of the per-triangle tile counts
 //   k_rs_scatter (tile, triangle) pairs at the scanned offsets; a triangle whose pairs would pass the capacity writes none
 //   sort         rocprim radix sort of the pairs by tile (stable: triangle order inside a tile)
@@ -35,13 +37,59 @@ constexpr int kVertInts = kMaxPoly * 3;   // record vertices: (x, y) in 1/256 pi
 constexpr float kGuardPixels2 = 2097152.0f;   // 2 x the guard band (2^20 pixels beyond each side of the viewport), see DESIGN.md 11
 constexpr uint32_t kBg = 0xFFFFFFFFu;
 
-struct DrawArgs {
+// Where a draw's triangles, MVP and colour come from: the source policy of k_rs_setup (QuerySrc / SceneSrc in rt_wave.hip are the pattern).
+// StaticDraw: one MVP and one colour for the whole draw, in the kernel arguments -- a static slot, or the dynamic mesh's own arrays bound with
+// RT_RASTER_BIND_SINGLE.  `m` is read through a pointer into the kernel arguments, so it stays in scalar registers.
+struct StaticDraw {
     float m[16];               // MVP = P * V * M, column-major
     const float *pos;          // 3 floats per vertex
     const uint32_t *idx;       // validated < nVerts on upload
     uint32_t triBase, nTris;   // global index of the draw's first triangle, triangles in the draw
     uint32_t rgba;
+    __device__ __forceinline__ const float *mvp(uint32_t, float *) const { return m; }
+    __device__ __forceinline__ uint32_t color(uint32_t) const { return rgba; }
 };
+// PartsDraw: the dynamic mesh bound with RT_RASTER_BIND_PARTS.  Thread i owns input triangle i: one coalesced 2-byte load of its part, then the part's
+// 64-byte entry of the call's MVP table (k_rs_part_mvp) as four 16-byte loads, then the part's packed colour when a colour table is set.
+struct PartsDraw {
+    const float *pos;
+    const uint32_t *idx;
+    uint32_t triBase, nTris;
+    uint32_t rgba;                 // the draw's own colour (partRGBA == null)
+    const uint16_t *partOf;        // [input triangle] -> part
+    const float4 *partMvp;         // [part] -> MVP, four float4 columns
+    const uint32_t *partRGBA;      // [part] -> packed colour, or null
+    __device__ __forceinline__ const float *mvp(uint32_t i, float *tmp) const {
+        const float4 *M = partMvp + (size_t)partOf[i] * 4;
+        const float4 c0 = M[0], c1 = M[1], c2 = M[2], c3 = M[3];
+        tmp[0] = c0.x; tmp[1] = c0.y; tmp[2] = c0.z; tmp[3] = c0.w; tmp[4] = c1.x; tmp[5] = c1.y; tmp[6] = c1.z; tmp[7] = c1.w;
+        tmp[8] = c2.x; tmp[9] = c2.y; tmp[10] = c2.z; tmp[11] = c2.w; tmp[12] = c3.x; tmp[13] = c3.y; tmp[14] = c3.z; tmp[15] = c3.w;
+        return tmp;
+    }
+    __device__ __forceinline__ uint32_t color(uint32_t i) const { return partRGBA ? partRGBA[partOf[i]] : rgba; }
+};
+
+struct Mat16 { float m[16]; };
+// rt_mat4_mul (mat_mul of rt_host.cpp): column-major, the same association and operation order, contraction off
+__device__ __forceinline__ void mat_mul_dev(const float *a, const float *b, float *out) {
+    for (int col = 0; col < 4; ++col)
+        for (int row = 0; row < 4; ++row)
+            out[col * 4 + row] = a[0 * 4 + row] * b[col * 4 + 0] + a[1 * 4 + row] * b[col * 4 + 1] + a[2 * 4 + row] * b[col * 4 + 2] + a[3 * 4 + row] * b[col * 4 + 3];
+}
+// One lane per part: mvp[p] = mat_mul(vp, mat_mul(model, table[p])) with the matrix table as it stands on the stream (it may have been written on
+// the device, so the product cannot be formed on the host).  Table entries and results are 64-byte aligned: four 16-byte loads, four 16-byte stores.
+__global__ __launch_bounds__(256) void k_rs_part_mvp(Mat16 vp, Mat16 model, const float4 *__restrict__ table, uint32_t nParts, float4 *__restrict__ mvp) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= nParts) return;
+    const float4 *T = table + (size_t)p * 4;
+    const float4 c0 = T[0], c1 = T[1], c2 = T[2], c3 = T[3];
+    const float t[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+    float mt[16], r[16];
+    mat_mul_dev(model.m, t, mt);
+    mat_mul_dev(vp.m, mt, r);
+    float4 *o = mvp + (size_t)p * 4;
+    for (int c = 0; c < 4; ++c) o[c] = make_float4(r[4 * c], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
+}
 
 struct CV { float x, y, z, w; };
 
@@ -67,7 +115,8 @@ __device__ __forceinline__ float plane_dist(const CV &v, int p, float gx, float 
 __device__ __forceinline__ uint32_t wave_add(bool pred) { return (uint32_t)__popcll(__ballot(pred)); }
 
 // stats[0] dropped, [1] clipped, [2] set up, [3] bin entries, [4] first triangle past the capacity, [5] tiles per row
-__global__ __launch_bounds__(256) void k_rs_setup(DrawArgs d, int W, int H, float gx, float gy, uint4 *__restrict__ hdr, int *__restrict__ verts,
+template <class Draw>
+__global__ __launch_bounds__(256) void k_rs_setup(Draw d, int W, int H, float gx, float gy, uint4 *__restrict__ hdr, int *__restrict__ verts,
                                                   uint32_t *__restrict__ counts, unsigned long long *__restrict__ stats) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const bool live = i < d.nTris;
@@ -76,10 +125,12 @@ __global__ __launch_bounds__(256) void k_rs_setup(DrawArgs d, int W, int H, floa
         const uint32_t t = d.triBase + i;
         CV v[kMaxPoly];
         bool finite = true;
+        float mtmp[16];
+        const float *m = d.mvp(i, mtmp);
+        const uint32_t rgba = d.color(i);
         for (int k = 0; k < 3; ++k) {
             const uint32_t vi = d.idx[3u * i + (uint32_t)k];
             const float px = d.pos[3u * vi + 0], py = d.pos[3u * vi + 1], pz = d.pos[3u * vi + 2];
-            const float *m = d.m;
             v[k].x = ((m[0] * px + m[4] * py) + m[8] * pz) + m[12];
             v[k].y = ((m[1] * px + m[5] * py) + m[9] * pz) + m[13];
             v[k].z = ((m[2] * px + m[6] * py) + m[10] * pz) + m[14];
@@ -154,7 +205,7 @@ __global__ __launch_bounds__(256) void k_rs_setup(DrawArgs d, int W, int H, floa
                 vo[3 * k + 0] = xs[k]; vo[3 * k + 1] = ys[k]; vo[3 * k + 2] = __float_as_int(zs[k]);
             }
         }
-        hdr[t] = make_uint4(any ? (uint32_t)n : 0u, d.rgba, rx, ry);
+        hdr[t] = make_uint4(any ? (uint32_t)n : 0u, rgba, rx, ry);
         counts[t] = cnt;
     }
     const uint32_t nd = wave_add(live && dropped), nc = wave_add(live && clipped), ns = wave_add(live && !dropped);
@@ -342,10 +393,17 @@ uint32_t pack_rgba(const float *c) { return unorm8(c[0]) | (unorm8(c[1]) << 8) |
 
 struct RtRaster {
     std::string err;
-    struct Mesh { float *pos = nullptr; uint32_t *idx = nullptr; int nVerts = 0, nIdx = 0; } mesh[RT_MAX_RASTER_MESHES];
+    // a slot holds an uploaded mesh (pos != null), or is bound to the context's dynamic mesh (bind = RT_RASTER_BIND_*), or is empty
+    struct Mesh {
+        float *pos = nullptr; uint32_t *idx = nullptr; int nVerts = 0, nIdx = 0;
+        int bind = -1;
+        uint32_t *partRGBA = nullptr; int nPartColors = 0;   // parts mode: packed colour per part on the device (null: the draw's colour)
+    } mesh[RT_MAX_RASTER_MESHES];
+    float4 *dPartMvp = nullptr; size_t nMvpCap = 0;          // per-call MVP table of the bound parts draws: 64 bytes per part
     hipStream_t last = nullptr;          // stream of the last rt_render_raster
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool rendered = false;
+    bool boundPending = false;           // a call that read the dynamic mesh may still be running (ev1 behind it has not been seen complete)
     // frame buffers (W x H)
     int W = 0, H = 0;
     uint32_t *dRGBA = nullptr, *dPrim = nullptr, *dDepth = nullptr;
@@ -378,7 +436,8 @@ const char *rt_raster_error(const RtRaster *r) { return r ? r->err.c_str() : "";
 void rt_raster_destroy(RtRaster *r) {
     if (!r) return;
     if (r->last) (void)hipStreamSynchronize(r->last);
-    for (auto &m : r->mesh) { rs_free(m.pos); rs_free(m.idx); }
+    for (auto &m : r->mesh) { rs_free(m.pos); rs_free(m.idx); rs_free(m.partRGBA); }
+    rs_free(r->dPartMvp);
     rs_free(r->dRGBA); rs_free(r->dPrim); rs_free(r->dDepth);
     rs_free(r->dHdr); rs_free(r->dVerts); rs_free(r->dCounts); rs_free(r->dOffs);
     for (int i = 0; i < 2; ++i) { rs_free(r->dKeys[i]); rs_free(r->dVals[i]); }
@@ -403,14 +462,62 @@ int rt_raster_set_mesh(RtRaster *r, int slot, const float *pos, int nVerts, cons
     }
     if (r->last) RS_TRY(r, hipStreamSynchronize(r->last));   // a raster call in flight may still read the slot
     RtRaster::Mesh &m = r->mesh[slot];
-    rs_free(m.pos); rs_free(m.idx);
-    m.nVerts = m.nIdx = 0;
+    rs_free(m.pos); rs_free(m.idx); rs_free(m.partRGBA);
+    m.nVerts = m.nIdx = m.nPartColors = 0;
+    m.bind = -1;   // an upload replaces a binding, nVerts == 0 unbinds
     if (nVerts == 0) return RT_OK;
     RS_TRY(r, hipMalloc(&m.pos, (size_t)nVerts * 12));
     RS_TRY(r, hipMalloc(&m.idx, std::max<size_t>((size_t)nIdx * 4, 4)));
     RS_TRY(r, hipMemcpy(m.pos, pos, (size_t)nVerts * 12, hipMemcpyHostToDevice));
     if (nIdx > 0) RS_TRY(r, hipMemcpy(m.idx, idx, (size_t)nIdx * 4, hipMemcpyHostToDevice));
     m.nVerts = nVerts; m.nIdx = nIdx;
+    return RT_OK;
+}
+
+int rt_raster_bind_dynamic(RtRaster *r, int slot, int mode) {
+    if (slot < 0 || slot >= RT_MAX_RASTER_MESHES) { r->err = "rt_raster_mesh_dynamic: slot " + std::to_string(slot) + " outside 0.." + std::to_string(RT_MAX_RASTER_MESHES - 1); return RT_ERR_INVALID; }
+    if (mode != RT_RASTER_BIND_SINGLE && mode != RT_RASTER_BIND_PARTS) { r->err = "rt_raster_mesh_dynamic: mode = " + std::to_string(mode); return RT_ERR_INVALID; }
+    RtRaster::Mesh &m = r->mesh[slot];
+    if (m.pos || m.partRGBA) {
+        if (r->last) RS_TRY(r, hipStreamSynchronize(r->last));   // a raster call in flight may still read what the slot holds
+        rs_free(m.pos); rs_free(m.idx); rs_free(m.partRGBA);
+    }
+    m.nVerts = m.nIdx = m.nPartColors = 0;
+    m.bind = mode;
+    return RT_OK;
+}
+
+int rt_raster_set_part_colors(RtRaster *r, int slot, const float *rgb, int nParts) {
+    if (slot < 0 || slot >= RT_MAX_RASTER_MESHES) { r->err = "rt_raster_part_colors: slot " + std::to_string(slot) + " outside 0.." + std::to_string(RT_MAX_RASTER_MESHES - 1); return RT_ERR_INVALID; }
+    RtRaster::Mesh &m = r->mesh[slot];
+    if (m.bind != RT_RASTER_BIND_PARTS) { r->err = "rt_raster_part_colors: slot " + std::to_string(slot) + " is not bound with RT_RASTER_BIND_PARTS"; return RT_ERR_INVALID; }
+    if (nParts < 0) { r->err = "rt_raster_part_colors: nParts = " + std::to_string(nParts); return RT_ERR_INVALID; }
+    if (nParts > RT_MAX_MESH_PARTS) { r->err = "rt_raster_part_colors: " + std::to_string(nParts) + " parts (a mesh has at most " + std::to_string(RT_MAX_MESH_PARTS) + ")"; return RT_ERR_INVALID; }
+    if (!rgb) nParts = 0;
+    if (m.partRGBA || nParts) {
+        if (r->last) RS_TRY(r, hipStreamSynchronize(r->last));   // a raster call in flight may still read the table
+    }
+    if (nParts != m.nPartColors) { rs_free(m.partRGBA); m.nPartColors = 0; }
+    if (nParts == 0) return RT_OK;
+    std::vector<uint32_t> packed((size_t)nParts);
+    for (int p = 0; p < nParts; ++p) packed[(size_t)p] = pack_rgba(rgb + 3 * (size_t)p);
+    if (!m.partRGBA) RS_TRY(r, hipMalloc(&m.partRGBA, (size_t)nParts * 4));
+    m.nPartColors = nParts;
+    RS_TRY(r, hipMemcpy(m.partRGBA, packed.data(), (size_t)nParts * 4, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// The second half of the event scheme: `s` is about to carry writes to the dynamic mesh -- rt_mesh_set_positions /
+// rt_mesh_set_part_matrices on it, or it has just become rt_stream()'s stream, on which the caller orders device writes of their own.  If a raster
+// call that read the mesh may still be running on another stream, `s` waits for the event behind that call.  The wait is enqueued here, when a
+// writer on another stream exists, and not on every lane by the raster call itself: a wait enqueued for the event of a call costs that call's own
+// stream time on this runtime (measured: 0.06 ms per waiting lane and call), and an application in raster mode never changes streams.
+int rt_raster_order_after(RtRaster *r, hipStream_t s) {
+    if (!r->boundPending || s == r->last) return RT_OK;
+    const hipError_t q = hipEventQuery(r->ev1);
+    if (q == hipSuccess) { r->boundPending = false; return RT_OK; }
+    if (q == hipErrorNotReady) (void)hipGetLastError();
+    RS_TRY(r, hipStreamWaitEvent(s, r->ev1, 0));
     return RT_OK;
 }
 
@@ -423,14 +530,35 @@ template <class T> static int rs_grow(RtRaster *r, T *&p, size_t have, size_t wa
 }
 #define RS_GROW(p, have, want, eb) do { int rc_ = rs_grow(r, p, have, want, eb); if (rc_ != RT_OK) return rc_; } while (0)
 
-int rt_raster_render(RtRaster *r, hipStream_t st, int W, int H, const RtRasterDraw *draws, int nDraws, const float *view, const float *proj) {
+int rt_raster_render(RtRaster *r, hipStream_t st, int W, int H, const RtRasterDraw *draws, int nDraws, const float *view, const float *proj,
+                     const RtRasterDynamic *dyn) {
     // validate the draw list first: nothing is enqueued for a bad one
     uint64_t nTris = 0;
+    bool anyBound = false;     // some draw names a bound slot: the call reads the dynamic mesh
+    size_t mvpEntries = 0;     // the largest part count of the bound parts draws
     for (int i = 0; i < nDraws; ++i) {
         const int s = draws[i].mesh;
         if (s < 0 || s >= RT_MAX_RASTER_MESHES) { r->err = "rt_render_raster: draw " + std::to_string(i) + " names slot " + std::to_string(s); return RT_ERR_INVALID; }
-        if (!r->mesh[s].pos) { r->err = "rt_render_raster: draw " + std::to_string(i) + " names empty mesh slot " + std::to_string(s); return RT_ERR_STATE; }
-        nTris += (uint64_t)r->mesh[s].nIdx / 3;
+        const RtRaster::Mesh &m = r->mesh[s];
+        if (m.bind >= 0) {
+            if (!dyn) {
+                r->err = "rt_render_raster: draw " + std::to_string(i) + " names slot " + std::to_string(s) + ", bound to the dynamic mesh, and there is no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)";
+                return RT_ERR_STATE;
+            }
+            if (m.bind == RT_RASTER_BIND_PARTS) {
+                if (m.partRGBA && m.nPartColors != dyn->nParts) {
+                    r->err = "rt_render_raster: draw " + std::to_string(i) + ": the colour table of slot " + std::to_string(s) + " has " + std::to_string(m.nPartColors) + " entries, the mesh has " +
+                             std::to_string(dyn->nParts) + " parts (rt_raster_part_colors again)";
+                    return RT_ERR_STATE;
+                }
+                mvpEntries = std::max(mvpEntries, (size_t)dyn->nParts);
+            }
+            anyBound = true;
+            nTris += (uint64_t)dyn->nTris;
+            continue;
+        }
+        if (!m.pos) { r->err = "rt_render_raster: draw " + std::to_string(i) + " names empty mesh slot " + std::to_string(s); return RT_ERR_STATE; }
+        nTris += (uint64_t)m.nIdx / 3;
     }
     if (nTris >= 0x7fffffffull) { r->err = "rt_render_raster: more than 2^31 triangles"; return RT_ERR_UNSUPPORTED; }
     if (W > 65536 || H > 65536) { r->err = "rt_render_raster: framebuffer above 65536 pixels a side (guard band, DESIGN.md 11)"; return RT_ERR_UNSUPPORTED; }
@@ -464,6 +592,10 @@ int rt_raster_render(RtRaster *r, hipStream_t st, int W, int H, const RtRasterDr
         RS_GROW(r->dCounts, r->nTriCap, nt, 4); RS_GROW(r->dOffs, r->nTriCap, nt, 8);
         r->nTriCap = std::max<size_t>(nt, 1);
     }
+    if (mvpEntries && (!r->dPartMvp || r->nMvpCap < mvpEntries)) {
+        RS_GROW(r->dPartMvp, r->nMvpCap, mvpEntries, 64);
+        r->nMvpCap = mvpEntries;
+    }
     if (!r->dBegin || r->nTileCap < nTiles) {
         RS_GROW(r->dBegin, r->nTileCap, nTiles, 4); RS_GROW(r->dEnd, r->nTileCap, nTiles, 4);
         r->nTileCap = nTiles;
@@ -496,18 +628,42 @@ int rt_raster_render(RtRaster *r, hipStream_t st, int W, int H, const RtRasterDr
     const float gx = 1.0f + kGuardPixels2 / (float)W, gy = 1.0f + kGuardPixels2 / (float)H;
     float bgc[3] = {0.1f, 0.0f, 0.2f};
     const uint32_t bg = pack_rgba(bgc);
-    // launches
+    // launches.  A call that names a bound slot reads the mesh where the caller's writes and the mesh updates put it, and those were ordered on
+    // rt_stream()'s stream as it was then: the setup work waits for every other lane (the first half of 14.4's scheme)
+    if (anyBound)
+        for (int i = 0; i < dyn->nOthers; ++i) {
+            RS_TRY(r, hipEventRecord(dyn->evOther[i], dyn->others[i]));
+            RS_TRY(r, hipStreamWaitEvent(st, dyn->evOther[i], 0));
+        }
     RS_TRY(r, hipEventRecord(r->ev0, st));
     hipLaunchKernelGGL(k_rs_init, dim3(1), dim3(64), 0, st, r->dStats, (unsigned long long)nTris, (unsigned long long)tilesX);
     uint32_t base = 0;
     for (int i = 0; i < nDraws; ++i) {
         const RtRaster::Mesh &m = r->mesh[draws[i].mesh];
-        DrawArgs a;
-        rt_mat4_mul(vp, draws[i].model, mvp);
-        std::memcpy(a.m, mvp, 64);
-        a.pos = m.pos; a.idx = m.idx; a.triBase = base; a.nTris = (uint32_t)(m.nIdx / 3); a.rgba = pack_rgba(draws[i].color);
-        if (a.nTris) hipLaunchKernelGGL(k_rs_setup, dim3((a.nTris + 255) / 256), dim3(256), 0, st, a, W, H, gx, gy, r->dHdr, r->dVerts, r->dCounts, r->dStats);
-        base += a.nTris;
+        if (m.bind == RT_RASTER_BIND_PARTS) {
+            // the parts' MVPs on the device, then one setup launch over all index triples: parts are contiguous and in order, so input triangle t is
+            // primitive base + t.  The table is reused by the next bound draw of the call: the stream orders its launches
+            PartsDraw a;
+            Mat16 mvpM, modelM;
+            std::memcpy(mvpM.m, vp, 64); std::memcpy(modelM.m, draws[i].model, 64);
+            a.pos = dyn->pos; a.idx = dyn->idx; a.triBase = base; a.nTris = (uint32_t)dyn->nTris; a.rgba = pack_rgba(draws[i].color);
+            a.partOf = dyn->partOf; a.partMvp = r->dPartMvp; a.partRGBA = m.partRGBA;
+            if (a.nTris) {
+                hipLaunchKernelGGL(k_rs_part_mvp, dim3(((unsigned)dyn->nParts + 255) / 256), dim3(256), 0, st, mvpM, modelM, reinterpret_cast<const float4 *>(dyn->partM),
+                                   (uint32_t)dyn->nParts, r->dPartMvp);
+                hipLaunchKernelGGL(k_rs_setup<PartsDraw>, dim3((a.nTris + 255) / 256), dim3(256), 0, st, a, W, H, gx, gy, r->dHdr, r->dVerts, r->dCounts, r->dStats);
+            }
+            base += a.nTris;
+        } else {
+            StaticDraw a;
+            rt_mat4_mul(vp, draws[i].model, mvp);
+            std::memcpy(a.m, mvp, 64);
+            if (m.bind == RT_RASTER_BIND_SINGLE) { a.pos = dyn->pos; a.idx = dyn->idx; a.nTris = (uint32_t)dyn->nTris; }
+            else { a.pos = m.pos; a.idx = m.idx; a.nTris = (uint32_t)(m.nIdx / 3); }
+            a.triBase = base; a.rgba = pack_rgba(draws[i].color);
+            if (a.nTris) hipLaunchKernelGGL(k_rs_setup<StaticDraw>, dim3((a.nTris + 255) / 256), dim3(256), 0, st, a, W, H, gx, gy, r->dHdr, r->dVerts, r->dCounts, r->dStats);
+            base += a.nTris;
+        }
     }
     RS_TRY(r, hipGetLastError());
     RS_TRY(r, hipMemsetAsync(r->dKeys[0], 0xFF, r->binCap * 4, st));
@@ -533,6 +689,8 @@ int rt_raster_render(RtRaster *r, hipStream_t st, int W, int H, const RtRasterDr
                        (uint32_t)nt, bg, r->dRGBA, r->dPrim, r->dDepth);
     RS_TRY(r, hipGetLastError());
     RS_TRY(r, hipEventRecord(r->ev1, st));
+    // ... and whatever writes the mesh after this call on another stream than this one waits for ev1 first (the second half): rt_raster_order_after
+    if (anyBound) r->boundPending = true;
     r->last = st;
     r->rendered = true;
     r->lastTris = nTris;
@@ -555,11 +713,28 @@ int rt_raster_read(RtRaster *r, int W, int H, uint8_t *rgba, uint32_t *prim, uin
     return RT_OK;
 }
 
+int rt_raster_buffers(RtRaster *r, int W, int H, void **rgba, void **prim, void **depth, size_t *bytesEach) {
+    if (!r->rendered) { r->err = "rt_raster_targets before rt_render_raster"; return RT_ERR_STATE; }
+    if (W != r->W || H != r->H) {
+        r->err = "rt_raster_targets: the framebuffer is " + std::to_string(W) + "x" + std::to_string(H) + " but the last raster frame is " + std::to_string(r->W) + "x" +
+                 std::to_string(r->H) + " (rt_resize since rt_render_raster): render it again";
+        return RT_ERR_STATE;
+    }
+    if (rgba) *rgba = r->dRGBA;
+    if (prim) *prim = r->dPrim;
+    if (depth) *depth = r->dDepth;
+    if (bytesEach) *bytesEach = (size_t)r->W * r->H * 4;
+    return RT_OK;
+}
+
 int rt_raster_stats(RtRaster *r, RtRasterStats *out) {
     std::memset(out, 0, sizeof *out);
     if (!r) return RT_OK;
     out->rasterBytes = r->bytes;
-    for (auto &m : r->mesh) if (m.pos) out->rasterBytes += (uint64_t)m.nVerts * 12 + (uint64_t)m.nIdx * 4;
+    for (auto &m : r->mesh) {
+        if (m.pos) out->rasterBytes += (uint64_t)m.nVerts * 12 + (uint64_t)m.nIdx * 4;
+        if (m.partRGBA) out->rasterBytes += (uint64_t)m.nPartColors * 4;
+    }
     if (!r->rendered) return RT_OK;
     RS_TRY(r, hipStreamSynchronize(r->last));
     unsigned long long s[8];

@@ -112,7 +112,23 @@ void rt_raster_destroy(RtRaster *r);
 const char *rt_raster_error(const RtRaster *r);
 void rt_raster_force_bin_capacity(RtRaster *r, size_t pairs);   // 0: automatic
 int rt_raster_set_mesh(RtRaster *r, int slot, const float *positions, int nVerts, const uint32_t *indices, int nIdx);
-int rt_raster_render(RtRaster *r, hipStream_t stream, int W, int H, const RtRasterDraw *draws, int nDraws, const float *view16, const float *proj16);
+// Slots bound to the context's dynamic mesh.  What a raster call needs of the mesh, resolved by rt_api.hip at every call: the device
+// arrays where they lie and, for the first half of the event scheme of DESIGN.md 14.4, the context's other lanes with one event each: the call
+// records it on the lane and waits for it before its setup launches.  Used only by a call that names a bound slot.  The second half is
+// rt_raster_order_after: a stream that is about to carry writes to the mesh waits for the event behind a raster call that read it on another stream.
+struct RtRasterDynamic {
+    const float *pos; const uint32_t *idx; const uint16_t *partOf; const float *partM;   // positions, index triples, [triangle] -> part, [part] -> 16 floats
+    int nTris, nParts;
+    int nOthers; hipStream_t others[8]; hipEvent_t evOther[8];
+};
+int rt_raster_bind_dynamic(RtRaster *r, int slot, int mode);
+int rt_raster_order_after(RtRaster *r, hipStream_t s);
+int rt_raster_set_part_colors(RtRaster *r, int slot, const float *rgb, int nParts);
+// dyn: null when the context has no dynamic mesh (a draw naming a bound slot is then RT_ERR_STATE)
+int rt_raster_render(RtRaster *r, hipStream_t stream, int W, int H, const RtRasterDraw *draws, int nDraws, const float *view16, const float *proj16,
+                     const RtRasterDynamic *dyn);
+// the device buffers of the last raster frame; RT_ERR_STATE as rt_raster_read
+int rt_raster_buffers(RtRaster *r, int W, int H, void **rgba8, void **primId, void **depth24, size_t *bytesEach);
 // W x H: the context's framebuffer; RT_ERR_STATE when the last raster frame has another size
 int rt_raster_read(RtRaster *r, int W, int H, uint8_t *rgba8, uint32_t *primId, uint32_t *depth24);
 int rt_raster_stats(RtRaster *r, RtRasterStats *out);

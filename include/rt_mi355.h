@@ -664,8 +664,35 @@ int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
  * alike; it is what makes the contract above checkable.  *bytes = size of the array (0: absent); dst == NULL only asks for the size; a capacity below
  * it: RT_ERR_INVALID. */
 enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 = 2, RT_SCENE_ARRAY_NODES2W = 3, RT_SCENE_ARRAY_NODES4 = 4,
-       RT_SCENE_ARRAY_QNODES4 = 5, RT_SCENE_ARRAY_LEAFBOX = 6 };
+       RT_SCENE_ARRAY_QNODES4 = 5, RT_SCENE_ARRAY_LEAFBOX = 6,
+       /* the optional record forms of rt_upload_bvh (RT_FUSED, RT_IMPLICIT): fused hubs; implicit two-child records, pair records, four-wide records,
+        * quantised four-wide records and leaf boxes */
+       RT_SCENE_ARRAY_FUSED = 7, RT_SCENE_ARRAY_IMPL_NODES2 = 8, RT_SCENE_ARRAY_IMPL_PAIRS = 9, RT_SCENE_ARRAY_IMPL_NODES4 = 10,
+       RT_SCENE_ARRAY_IMPL_QNODES4 = 11, RT_SCENE_ARRAY_IMPL_LEAFBOX = 12 };
 int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
+/* Diagnostics, host side (no GPU needed, no context): what rt_upload_bvh would put on the device for these arrays -- the packers of
+ * csrc/rt_scene_pack.cpp run and one array handed out, with rt_debug_read_scene's `which` values and size-query convention.
+ * which = RT_SCENE_ARRAY_PACK_INFO: an RtPackInfo, the scalars the context takes from the packers.  opt == NULL: the options from the environment
+ * (RT_QNODES, RT_FUSED, RT_IMPLICIT, RT_ANYHIT_TREE, RT_QNODES_SPARSE_BOXES), as an upload reads them.  Returns rt_upload_bvh's codes for a tree it
+ * would refuse (message: rt_last_error(NULL)); RT_ERR_INVALID for null arrays or counts <= 0. */
+typedef struct RtPackOptions {
+    int32_t qnodes;            /* quantised any-hit nodes: -1 by the size of the tree, 0 never, > 0 always */
+    int32_t fused, implicit, anyhitSah, sparseLeafBoxes;   /* booleans */
+    int32_t reserved[3];
+} RtPackOptions;
+typedef struct RtPackInfo {
+    int32_t nNodes, nTris, nInner, treeDepth, nWide4, nPairs, nFused, flags;   /* as RtSceneInfo */
+    int32_t implicitDepth, implicitRecords;                                     /* implicit records: depth of the leaves, pair records per leaf slot */
+    int32_t rootRef, rootRefW, rootRef4, anyStack;
+    uint32_t leafBoxMagic;
+    int32_t nLeafBoxes;
+    int32_t collapsed4;        /* the four-wide tree is the binary tree collapsed (0: the RT_ANYHIT_TREE=sah tree) */
+    float rootMin[3], rootMax[3];
+    int32_t reserved;
+} RtPackInfo;
+enum { RT_SCENE_ARRAY_PACK_INFO = 100 };
+int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, int nTris, const RtPackOptions *opt, int which, void *dst, size_t capacity,
+                        size_t *bytes);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 from pathlib import Path
 
 import numpy as np
@@ -183,6 +184,10 @@ RT_MESH_DID_REFIT, RT_MESH_DID_REBUILD = 0, 1
 # rt_debug_read_scene: the device scene arrays
 RT_SCENE_ARRAY_TRIS, RT_SCENE_ARRAY_PAIRS, RT_SCENE_ARRAY_NODES2, RT_SCENE_ARRAY_NODES2W, RT_SCENE_ARRAY_NODES4, RT_SCENE_ARRAY_QNODES4, RT_SCENE_ARRAY_LEAFBOX = range(7)
 SCENE_ARRAYS = {"tris": 0, "pairs": 1, "nodes2": 2, "nodes2w": 3, "nodes4": 4, "qnodes4": 5, "leafbox": 6}
+# ... and the optional record forms (RT_FUSED, RT_IMPLICIT), which rt_debug_read_scene and rt_debug_pack_scene know as well
+SCENE_ARRAYS_OPTIONAL = {"fused": 7, "impl_nodes2": 8, "impl_pairs": 9, "impl_nodes4": 10, "impl_qnodes4": 11, "impl_leafbox": 12}
+RT_SCENE_ARRAY_PACK_INFO = 100
+
 
 
 class RtMemoryInfo(_Struct):
@@ -354,6 +359,7 @@ SIGNATURES = {
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
     "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
+    "rt_debug_pack_scene": (C.c_int, [_FP, C.c_int, _FP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -617,6 +623,41 @@ def bvh_cost(nodes12) -> RtBvhCost:
     rc = lib().rt_bvh_cost(_fp(n) if n.shape[0] else None, n.shape[0], C.byref(out))
     if rc != RT_OK:
         raise RtError(rc, "rt_bvh_cost: no nodes, a negative count, a non-finite bound or a max below its min")
+    return out
+
+
+def pack_scene(nodes12, tris12, **options) -> dict:
+    """What upload_bvh would put on the device, without one (rt_debug_pack_scene): name -> bytes (uint8, padding included; empty: no such array) for
+    every name of SCENE_ARRAYS and SCENE_ARRAYS_OPTIONAL, and "info" -> the scalars of RtPackInfo as a namespace (nNodes .. rootMax).  options: qnodes
+    (-1 by size, 0 never, > 0 always), fused, implicit, anyhit_sah, sparse_leaf_boxes; with none given the options come from the environment, as an
+    upload reads them."""
+    n, t = _f32(nodes12).reshape(-1, 12), _f32(tris12).reshape(-1, 12)
+    opt = None
+    if options:     # RtPackOptions: qnodes, fused, implicit, anyhitSah, sparseLeafBoxes, reserved[3]
+        opt = np.array([options.pop("qnodes", -1), options.pop("fused", False), options.pop("implicit", False), options.pop("anyhit_sah", False),
+                        options.pop("sparse_leaf_boxes", False), 0, 0, 0], np.int32)
+        if options:
+            raise TypeError(f"pack_scene: unknown options {sorted(options)}")
+
+    def read(which):
+        size = C.c_size_t()
+        args = (_fp(n), n.shape[0], _fp(t), t.shape[0], None if opt is None else C.c_void_p(opt.ctypes.data), which)
+        rc = lib().rt_debug_pack_scene(*args, None, 0, C.byref(size))
+        out = np.zeros(size.value, np.uint8)
+        if rc == RT_OK and size.value:
+            rc = lib().rt_debug_pack_scene(*args, C.c_void_p(out.ctypes.data), out.size, C.byref(size))
+        if rc != RT_OK:
+            raise RtError(rc, (lib().rt_last_error(None) or b"").decode())
+        return out
+
+    out = {name: read(which) for name, which in {**SCENE_ARRAYS, **SCENE_ARRAYS_OPTIONAL}.items()}
+    raw = read(RT_SCENE_ARRAY_PACK_INFO)      # RtPackInfo: seventeen 32-bit words, two float[3], one reserved word
+    names = ("nNodes", "nTris", "nInner", "treeDepth", "nWide4", "nPairs", "nFused", "flags", "implicitDepth", "implicitRecords", "rootRef", "rootRefW",
+             "rootRef4", "anyStack", "leafBoxMagic", "nLeafBoxes", "collapsed4")
+    info = dict(zip(names, raw.view(np.int32)[:17].tolist()))
+    info["leafBoxMagic"] = int(raw.view(np.uint32)[14])
+    info["rootMin"], info["rootMax"] = raw.view(np.float32)[17:20].copy(), raw.view(np.float32)[20:23].copy()
+    out["info"] = types.SimpleNamespace(**info)
     return out
 
 
@@ -962,7 +1003,7 @@ class Renderer:
 
     def debug_read_scene(self, which) -> np.ndarray:
         """One device scene array as bytes (uint8), padding included; empty when the scene has no such array.  which: RT_SCENE_ARRAY_* or its name."""
-        which = SCENE_ARRAYS[which] if isinstance(which, str) else int(which)
+        which = {**SCENE_ARRAYS, **SCENE_ARRAYS_OPTIONAL}[which] if isinstance(which, str) else int(which)
         n = C.c_size_t()
         self._check(lib().rt_debug_read_scene(self._h, which, None, 0, C.byref(n)))
         out = np.zeros(n.value, np.uint8)

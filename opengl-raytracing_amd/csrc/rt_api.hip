@@ -20,6 +20,7 @@
 #include "rt_frame.hpp"
 #include "rt_bvh_cost.hpp"
 #include "rt_mesh.hpp"
+#include "rt_scene_pack.hpp"
 #include "rt_wave.hpp"
 
 using namespace rtd;
@@ -27,7 +28,6 @@ using namespace rtd;
 static thread_local std::string g_createError;
 
 #define RT_MAX_LANES 8
-constexpr size_t kQNodesAbove = (size_t)4 << 20;   // bytes of 112-byte any-hit nodes beyond which the quantised nodes are built and walked
 constexpr int kDefaultArenas = 2;   // ray-queue arenas shared by the frame lanes (rt_wave.hpp RtArenaPool; measured in profiles/r04_experiments.txt)
 struct StageEvent { int stage; hipEvent_t a, b; };
 
@@ -338,11 +338,33 @@ int ensure_staging(RtContext *c, size_t bytes) {
     return RT_OK;
 }
 
+// The one list of what makes up the BVH scene: afterwards the context describes the empty scene.  owned: the arrays are the context's and are freed
+// (false: they alias the dynamic mesh's and are only forgotten).  Callers have synchronised.
+void clear_scene(RtContext *c, bool owned) {
+    float4 **arrays[] = {&c->dWNodes, &c->dWNodesW, &c->dW4, &c->dQ4, &c->dLeafBox, &c->dWF, &c->dIN2, &c->dIPairs, &c->dIN4, &c->dIQ4, &c->dILeafBox, &c->dPairs, &c->dTris};
+    for (float4 **p : arrays) { if (owned && *p) (void)hipFree(*p); *p = nullptr; }
+    c->nNodes = c->nTris = c->nInner = c->treeDepth = 0;
+    c->nWide4 = c->nPairs = c->nFused = c->nLeafBoxes = c->leafBoxBytes = 0;
+    c->rootRef = c->rootRefW = c->rootRef4 = c->anyStack = 0;
+    c->implD = c->implR = 0;
+    c->leafBoxMagic = 0;
+    c->sceneFlags = 0;
+    for (int a = 0; a < 3; ++a) c->rootMin[a] = c->rootMax[a] = 0.0f;
+}
+void free_scene(RtContext *c) { clear_scene(c, true); }
+
+// One scene array to the device (an empty one stays null)
+template <class T> int upload(RtContext *c, float4 **dst, const std::vector<T> &v) {
+    if (v.empty()) return RT_OK;
+    HIP_TRY(c, hipMalloc(dst, v.size() * sizeof(T)));
+    HIP_TRY(c, hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
 // Lets go of the dynamic mesh; a scene its rebuild installed goes with it (the scene pointers alias the mesh's arrays).  Callers have synchronised.
 void release_mesh(RtContext *c) {
     if (c->sceneFromMesh) {
-        c->dWNodes = c->dW4 = c->dTris = c->dWNodesW = c->dPairs = c->dQ4 = c->dLeafBox = nullptr;
-        c->nNodes = c->nTris = c->nInner = 0;
+        clear_scene(c, false);
         c->sceneFromMesh = false;
         c->dRootBox = nullptr;
     }
@@ -486,19 +508,7 @@ void rt_destroy(RtContext *c) {
     if (c->queryDone) (void)hipEventDestroy(c->queryDone);
     rt_arena_pool_destroy(c->arenaPool);
     for (int i = 0; i < RT_MAX_LANES; ++i) if (c->lanes[i]) (void)hipStreamDestroy(c->lanes[i]);   // c->stream is lanes[0]
-    if (c->dWNodes) (void)hipFree(c->dWNodes);
-    if (c->dW4) (void)hipFree(c->dW4);
-    if (c->dQ4) (void)hipFree(c->dQ4);
-    if (c->dLeafBox) (void)hipFree(c->dLeafBox);
-    if (c->dWNodesW) (void)hipFree(c->dWNodesW);
-    if (c->dWF) (void)hipFree(c->dWF);
-    if (c->dIN2) (void)hipFree(c->dIN2);
-    if (c->dIPairs) (void)hipFree(c->dIPairs);
-    if (c->dIN4) (void)hipFree(c->dIN4);
-    if (c->dIQ4) (void)hipFree(c->dIQ4);
-    if (c->dILeafBox) (void)hipFree(c->dILeafBox);
-    if (c->dPairs) (void)hipFree(c->dPairs);
-    if (c->dTris) (void)hipFree(c->dTris);
+    free_scene(c);
     if (c->dEnv) (void)hipFree(c->dEnv);
     if (c->dCounters) (void)hipFree(c->dCounters);
     if (c->dStaging) (void)hipFree(c->dStaging);
@@ -507,643 +517,46 @@ void rt_destroy(RtContext *c) {
     delete c;
 }
 
+// The record forms are packed on the host (rt_scene_pack.cpp); this uploads them and, after the last upload has succeeded, commits the
+// context's fields in one block.  A failed upload leaves the empty scene behind.
 int rt_upload_bvh(RtContext *c, const float *nodes12, int nNodes, const float *tris12, int nTris) {
     if (!c) return RT_ERR_INVALID;
     if (nNodes < 0 || nTris < 0 || (nNodes > 0 && !nodes12) || (nTris > 0 && !tris12)) return fail(c, RT_ERR_INVALID, "rt_upload_bvh: bad arguments");
     return guarded(c, "rt_upload_bvh", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    HIP_TRY(c, sync_all(c));
-    release_mesh(c);   // an upload takes the scene over from the dynamic mesh
-    if (c->dWNodes) (void)hipFree(c->dWNodes);
-    if (c->dW4) (void)hipFree(c->dW4);
-    if (c->dQ4) (void)hipFree(c->dQ4);
-    if (c->dLeafBox) (void)hipFree(c->dLeafBox);
-    if (c->dWNodesW) (void)hipFree(c->dWNodesW);
-    if (c->dWF) (void)hipFree(c->dWF);
-    if (c->dIN2) (void)hipFree(c->dIN2);
-    if (c->dIPairs) (void)hipFree(c->dIPairs);
-    if (c->dIN4) (void)hipFree(c->dIN4);
-    if (c->dIQ4) (void)hipFree(c->dIQ4);
-    if (c->dILeafBox) (void)hipFree(c->dILeafBox);
-    c->dIN2 = c->dIPairs = c->dIN4 = c->dIQ4 = c->dILeafBox = nullptr; c->implD = c->implR = 0;
-    if (c->dPairs) (void)hipFree(c->dPairs);
-    if (c->dTris) (void)hipFree(c->dTris);
-    c->dWNodes = c->dW4 = c->dTris = c->dWNodesW = c->dPairs = c->dQ4 = c->dLeafBox = c->dWF = nullptr;
-    c->nNodes = c->nTris = c->nInner = 0;
-    c->treeDepth = 0;
-    c->nWide4 = c->nPairs = c->nFused = 0;
-    c->sceneFlags = 0;
-    c->anyStack = 0;
-    for (int i = 0; i < RT_MAX_LANES; ++i) { rt_wave_forget_share(c->wave[i]); rt_wave_set_probe_tree(c->wave[i], true); }   // a new scene: its share of bounce hits is not known
-    if (nNodes == 0 || nTris == 0) return RT_OK;
-    if (nTris >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "rt_upload_bvh: %d triangles exceed the 2^28 leaf encoding", nTris);
-
-    // Decode the reference's float-encoded links exactly as nodeFetch does (rt_bvh.glsl:97-100).
-    struct N { int left, right, first, count; };
-    std::vector<N> nd((size_t)nNodes);
-    std::vector<int> innerIdx((size_t)nNodes, -1);
-    int nInner = 0;
-    for (int i = 0; i < nNodes; ++i) {
-        const float *p = nodes12 + (size_t)i * 12;
-        nd[(size_t)i] = {(int)(p[3] + 0.5f), (int)(p[7] + 0.5f), (int)(p[8] + 0.5f), (int)(p[9] + 0.5f)};
-        const N &n = nd[(size_t)i];
-        if (n.count > 0) {
-            if (n.count > 8 || n.first < 0 || n.first + n.count > nTris)
-                return fail(c, RT_ERR_UNSUPPORTED, "rt_upload_bvh: leaf %d has first=%d count=%d (leaves hold 1..8 triangles)", i, n.first, n.count);
-        } else {
-            if (n.left <= 0 || n.right <= 0 || n.left >= nNodes || n.right >= nNodes)
-                return fail(c, RT_ERR_INVALID, "rt_upload_bvh: inner node %d has children %d,%d", i, n.left, n.right);
-            innerIdx[(size_t)i] = nInner++;
-        }
-    }
-    auto refOf = [&](int node) {
-        const N &n = nd[(size_t)node];
-        return (n.count > 0) ? -(((n.first << 3) | (n.count - 1)) + 1) : innerIdx[(size_t)node];
-    };
-    // Triangle PAIR records for the wavefront pipeline's traversal kernels: what bounds them is the number of 16-byte gather
-    // loads per ray, and a 48-byte triangle record carries only 36 bytes of payload.  Two triangles of a leaf are
-    // packed into 80 bytes = 5 loads instead of 6: floats [0..8] = v0,e1,e2 of the first, [9..17] of the second, [18] = index of the
-    // first in the reference's triangle array (closest-hit results name triangles by it), [19] unused.  A leaf owns
-    // ceil(count/2) consecutive records; its reference in the wavefront node arrays addresses the first of them.
-    std::vector<float> pairs;
-    std::vector<int> pairRefOf((size_t)nNodes, 0);
-    for (int i = 0; i < nNodes; ++i) {
-        const N &n = nd[(size_t)i];
-        if (n.count <= 0) continue;
-        const size_t rec = pairs.size() / 20;
-        if (rec + 8 >= ((size_t)1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "rt_upload_bvh: pair records exceed the 2^28 leaf encoding");
-        pairRefOf[(size_t)i] = -((int)((rec << 3) | (size_t)(n.count - 1)) + 1);
-        for (int t = 0; t < n.count; t += 2) {
-            float r[20] = {0};
-            for (int h = 0; h < 2 && t + h < n.count; ++h) {
-                const float *q = tris12 + (size_t)(n.first + t + h) * 12;
-                const float nine[9] = {q[0], q[1], q[2], q[4], q[5], q[6], q[8], q[9], q[10]};
-                std::memcpy(&r[9 * h], nine, sizeof nine);
-            }
-            const uint32_t orig = (uint32_t)(n.first + t);
-            std::memcpy(&r[18], &orig, 4);
-            if (t + 1 >= n.count) std::memcpy(&r[9], &orig, 4);   // a record with one triangle: the index again in the unused tenth float (3-load fetch)
-            pairs.insert(pairs.end(), r, r + 20);
-        }
-    }
-    pairs.resize(pairs.size() + 8 * 20, 0.0f);   // groups are fetched without a bounds branch
-    auto refOfW = [&](int node) { return (nd[(size_t)node].count > 0) ? pairRefOf[(size_t)node] : innerIdx[(size_t)node]; };
-    std::vector<float> wn((size_t)std::max(nInner, 1) * 16, 0.0f);
-    for (int i = 0; i < nNodes; ++i) {
-        if (innerIdx[(size_t)i] < 0) continue;
-        const float *L = nodes12 + (size_t)nd[(size_t)i].left * 12, *R = nodes12 + (size_t)nd[(size_t)i].right * 12;
-        float *o = &wn[(size_t)innerIdx[(size_t)i] * 16];
-        int rl = refOf(nd[(size_t)i].left), rr = refOf(nd[(size_t)i].right);
-        o[0] = L[0]; o[1] = L[1]; o[2] = L[2]; std::memcpy(&o[3], &rl, 4);
-        o[4] = L[4]; o[5] = L[5]; o[6] = L[6]; std::memcpy(&o[7], &rr, 4);
-        o[8] = R[0]; o[9] = R[1]; o[10] = R[2];
-        o[12] = R[4]; o[13] = R[5]; o[14] = R[6];
-    }
-    std::vector<float> wnW = wn;   // the same records with pair-record leaf references (wavefront closest-hit kernels)
-    for (int i = 0; i < nNodes; ++i) {
-        if (innerIdx[(size_t)i] < 0) continue;
-        float *o = &wnW[(size_t)innerIdx[(size_t)i] * 16];
-        int rl = refOfW(nd[(size_t)i].left), rr = refOfW(nd[(size_t)i].right);
-        std::memcpy(&o[3], &rl, 4);
-        std::memcpy(&o[7], &rr, 4);
-    }
-    // depth of the tree (iterative), bounds the traversal stack: one deferred sibling per level
-    int depth = 0;
-    {
-        std::vector<std::pair<int, int>> st{{0, 1}};
-        size_t visited = 0;
-        while (!st.empty()) {
-            auto [n, d] = st.back();
-            st.pop_back();
-            if (++visited > (size_t)nNodes) return fail(c, RT_ERR_INVALID, "rt_upload_bvh: node links form a cycle");
-            depth = std::max(depth, d);
-            if (nd[(size_t)n].count <= 0) { st.push_back({nd[(size_t)n].left, d + 1}); st.push_back({nd[(size_t)n].right, d + 1}); }
-        }
-    }
-    // 4-wide nodes for any-hit rays: every binary inner node at an even level absorbs its inner children, so one
-    // 128-byte record holds up to four grandchild boxes -- stored component-wise, so that the 28 payload floats take 7 of the
-    // record's 8 sixteen-byte pieces and a visit costs 7 gather loads.  A child box is only skipped (never tested) when it is an
-    // intermediate node; by monotonicity of the slab arithmetic a grandchild that passes its own test also passes
-    // its parent's, so the set of triangles tested -- and hence every any-hit answer -- is unchanged.
-    std::vector<float> w4;
-    int rootRef4 = refOfW(0);
-    if (nd[0].count <= 0) {
-        struct Job { int bin; size_t at; };   // fill node `at` (index into w4 / 32) from binary node `bin`
-        std::vector<Job> jobs;
-        w4.resize(32, 0.0f);
-        jobs.push_back({0, 0});
-        rootRef4 = 0;
-        while (!jobs.empty()) {
-            Job jb = jobs.back();
-            jobs.pop_back();
-            int kids[4], nk = 0;
-            for (int ch : {nd[(size_t)jb.bin].left, nd[(size_t)jb.bin].right}) {
-                if (nd[(size_t)ch].count > 0) kids[nk++] = ch;
-                else { kids[nk++] = nd[(size_t)ch].left; kids[nk++] = nd[(size_t)ch].right; }
-            }
-            for (int i = 0; i < 4; ++i) {
-                int ref = RT_NO_CHILD;
-                if (i < nk) {
-                    const float *b = nodes12 + (size_t)kids[i] * 12;
-                    if (nd[(size_t)kids[i]].count > 0) ref = refOfW(kids[i]);
-                    else {
-                        ref = (int)(w4.size() / 32);
-                        w4.resize(w4.size() + 32, 0.0f);
-                        jobs.push_back({kids[i], (size_t)ref});
-                    }
-                    float *o = &w4[jb.at * 32];     // SoA: [min.x x4][min.y x4][min.z x4][max.x x4][max.y x4][max.z x4][ref x4][-]
-                    o[0 + i] = b[0]; o[4 + i] = b[1]; o[8 + i] = b[2];
-                    o[12 + i] = b[4]; o[16 + i] = b[5]; o[20 + i] = b[6];
-                } else {
-                    // absent child: NaN box -- (NaN - ro) * rdInv = NaN, v_min/v_max drop NaN operands, tmax = NaN, and
-                    // "tmax >= tmin" is false, so the traversal kernel needs no child-present branch
-                    float *o = &w4[jb.at * 32];
-                    const float qnan = std::nanf("");
-                    o[0 + i] = o[4 + i] = o[8 + i] = o[12 + i] = o[16 + i] = o[20 + i] = qnan;
-                }
-                std::memcpy(&w4[jb.at * 32 + 24 + (size_t)i], &ref, 4);
-            }
-        }
-    } else w4.resize(32, 0.0f);
-    // EXPERIMENT (RT_ANYHIT_TREE=sah): any-hit answers do not depend on the tree, only on which reference leaves pass their own
-    // exact box test -- so the 4-wide tree may be ANY tree over the reference's leaves whose inner boxes contain their leaves' boxes.  Binned SAH
-    // (16 bins, cost = area x triangles) over the leaves, collapsed to four children by pulling up the child of largest area.  Off by default: it
-    // needs more node visits than the collapse of the balanced median-split tree on the bench mesh.
-    int anyStack = 0;
-    if (const char *e = getenv("RT_ANYHIT_TREE")) if (std::string(e) == "sah" && nd[0].count <= 0) {
-        struct Leaf { float lo[3], hi[3], cen[3]; int ref; float w; };
-        std::vector<Leaf> leaves;
-        for (int i = 0; i < nNodes; ++i) if (nd[(size_t)i].count > 0) {
-            Leaf L;
-            const float *b = nodes12 + (size_t)i * 12;
-            for (int a = 0; a < 3; ++a) { L.lo[a] = b[a]; L.hi[a] = b[4 + a]; L.cen[a] = 0.5f * (b[a] + b[4 + a]); }
-            L.ref = refOfW(i); L.w = (float)nd[(size_t)i].count;
-            leaves.push_back(L);
-        }
-        struct BNode { float lo[3], hi[3]; int left, right, leaf; };
-        std::vector<BNode> B;
-        std::vector<int> ids(leaves.size());
-        for (size_t i = 0; i < ids.size(); ++i) ids[i] = (int)i;
-        auto area = [](const float *lo, const float *hi) { float ex = std::max(hi[0] - lo[0], 0.0f), ey = std::max(hi[1] - lo[1], 0.0f), ez = std::max(hi[2] - lo[2], 0.0f); return 2.0f * (ex * ey + ey * ez + ez * ex); };
-        struct Job { int begin, end, node, depth; };
-        std::vector<Job> todo;
-        B.push_back(BNode{});
-        todo.push_back({0, (int)ids.size(), 0, 0});
-        constexpr int NB = 16;
-        while (!todo.empty()) {
-            const Job jb = todo.back();
-            todo.pop_back();
-            BNode bn{};
-            for (int a = 0; a < 3; ++a) { bn.lo[a] = 3.0e38f; bn.hi[a] = -3.0e38f; }
-            float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-            for (int i = jb.begin; i < jb.end; ++i) {
-                const Leaf &L = leaves[(size_t)ids[(size_t)i]];
-                for (int a = 0; a < 3; ++a) { bn.lo[a] = std::min(bn.lo[a], L.lo[a]); bn.hi[a] = std::max(bn.hi[a], L.hi[a]); clo[a] = std::min(clo[a], L.cen[a]); chi[a] = std::max(chi[a], L.cen[a]); }
-            }
-            bn.left = bn.right = -1; bn.leaf = -1;
-            if (jb.end - jb.begin == 1) { bn.leaf = ids[(size_t)jb.begin]; B[(size_t)jb.node] = bn; continue; }
-            int bestAxis = -1, bestSplit = -1;
-            float bestCost = 3.0e38f;
-            for (int a = 0; a < 3 && jb.depth < 40; ++a) {
-                const float ext = chi[a] - clo[a];
-                if (!(ext > 0.0f)) continue;
-                float blo[NB][3], bhi[NB][3], bw[NB];
-                for (int k = 0; k < NB; ++k) { bw[k] = 0.0f; for (int q = 0; q < 3; ++q) { blo[k][q] = 3.0e38f; bhi[k][q] = -3.0e38f; } }
-                for (int i = jb.begin; i < jb.end; ++i) {
-                    const Leaf &L = leaves[(size_t)ids[(size_t)i]];
-                    const int k = std::min(NB - 1, (int)((L.cen[a] - clo[a]) / ext * NB));
-                    bw[k] += L.w;
-                    for (int q = 0; q < 3; ++q) { blo[k][q] = std::min(blo[k][q], L.lo[q]); bhi[k][q] = std::max(bhi[k][q], L.hi[q]); }
-                }
-                float rlo[NB][3], rhi[NB][3], rw[NB];
-                float alo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, ahi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, aw = 0.0f;
-                for (int k = NB - 1; k >= 0; --k) {
-                    aw += bw[k];
-                    for (int q = 0; q < 3; ++q) { alo[q] = std::min(alo[q], blo[k][q]); ahi[q] = std::max(ahi[q], bhi[k][q]); rlo[k][q] = alo[q]; rhi[k][q] = ahi[q]; }
-                    rw[k] = aw;
-                }
-                float llo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, lhi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, lw = 0.0f;
-                for (int k = 0; k + 1 < NB; ++k) {
-                    lw += bw[k];
-                    for (int q = 0; q < 3; ++q) { llo[q] = std::min(llo[q], blo[k][q]); lhi[q] = std::max(lhi[q], bhi[k][q]); }
-                    if (lw == 0.0f || rw[k + 1] == 0.0f) continue;
-                    const float cost = area(llo, lhi) * lw + area(rlo[k + 1], rhi[k + 1]) * rw[k + 1];
-                    if (cost < bestCost) { bestCost = cost; bestAxis = a; bestSplit = k; }
-                }
-            }
-            int mid;
-            if (bestAxis < 0) {   // degenerate centroids or the depth cap: median by index
-                mid = (jb.begin + jb.end) / 2;
-            } else {
-                const float ext = chi[bestAxis] - clo[bestAxis];
-                auto it = std::partition(ids.begin() + jb.begin, ids.begin() + jb.end, [&](int id) {
-                    return std::min(NB - 1, (int)((leaves[(size_t)id].cen[bestAxis] - clo[bestAxis]) / ext * NB)) <= bestSplit; });
-                mid = (int)(it - ids.begin());
-                if (mid == jb.begin || mid == jb.end) mid = (jb.begin + jb.end) / 2;
-            }
-            bn.left = (int)B.size(); B.push_back(BNode{});
-            bn.right = (int)B.size(); B.push_back(BNode{});
-            B[(size_t)jb.node] = bn;
-            todo.push_back({jb.begin, mid, bn.left, jb.depth + 1});
-            todo.push_back({mid, jb.end, bn.right, jb.depth + 1});
-        }
-        // collapse to four children
-        std::vector<float> s4(32, 0.0f);
-        struct J4 { int bin; size_t at; int depth; };
-        std::vector<J4> jobs4{{0, 0, 1}};
-        int depth4 = 1;
-        while (!jobs4.empty()) {
-            const J4 jb = jobs4.back();
-            jobs4.pop_back();
-            depth4 = std::max(depth4, jb.depth);
-            std::vector<int> kids{B[(size_t)jb.bin].left, B[(size_t)jb.bin].right};
-            while (kids.size() < 4) {
-                int pick = -1;
-                float best = -1.0f;
-                for (size_t i = 0; i < kids.size(); ++i) if (B[(size_t)kids[i]].leaf < 0) { const float ar = area(B[(size_t)kids[i]].lo, B[(size_t)kids[i]].hi); if (ar > best) { best = ar; pick = (int)i; } }
-                if (pick < 0) break;
-                const int k = kids[(size_t)pick];
-                kids.erase(kids.begin() + pick);
-                kids.push_back(B[(size_t)k].left); kids.push_back(B[(size_t)k].right);
-            }
-            for (int i = 0; i < 4; ++i) {
-                int ref = RT_NO_CHILD;
-                float *o = &s4[jb.at * 32];
-                if (i < (int)kids.size()) {
-                    const BNode &kb = B[(size_t)kids[(size_t)i]];
-                    if (kb.leaf >= 0) ref = leaves[(size_t)kb.leaf].ref;
-                    else { ref = (int)(s4.size() / 32); s4.resize(s4.size() + 32, 0.0f); jobs4.push_back({kids[(size_t)i], (size_t)ref, jb.depth + 1}); o = &s4[jb.at * 32]; }
-                    // a leaf child carries the reference's exact leaf box (the test that decides which triangles are tested); an inner child the union of its leaves' boxes
-                    const float *lo = kb.leaf >= 0 ? leaves[(size_t)kb.leaf].lo : kb.lo, *hi = kb.leaf >= 0 ? leaves[(size_t)kb.leaf].hi : kb.hi;
-                    o[0 + i] = lo[0]; o[4 + i] = lo[1]; o[8 + i] = lo[2]; o[12 + i] = hi[0]; o[16 + i] = hi[1]; o[20 + i] = hi[2];
-                } else {
-                    const float qnan = std::nanf("");
-                    o[0 + i] = o[4 + i] = o[8 + i] = o[12 + i] = o[16 + i] = o[20 + i] = qnan;
-                }
-                std::memcpy(&s4[jb.at * 32 + 24 + (size_t)i], &ref, 4);
-            }
-        }
-        if (3 * depth4 <= 60) {
-            w4.swap(s4); rootRef4 = 0; anyStack = 3 * depth4;
-            for (int i = 0; i < RT_MAX_LANES; ++i) rt_wave_set_probe_tree(c->wave[i], false);   // not the binary tree collapsed: no bounce probe
-        }
-    }
-    // Exact stack need of the any-hit walk (round 4): a visit of a node with nc children pushes at most nc - 1 entries (one child is gone on with),
-    // so S(node) = nc - 1 + max over its inner children S(child).  Round 3 sized the stack as 3 per two binary levels INCLUDING the leaf level: 24 entries
-    // for the bench mesh, where 21 are enough -- and 21 x 4 B x 256 threads let seven workgroups share a CU's 160 KB of LDS instead of six.
-    if (rootRef4 == 0 && w4.size() >= 32) {
-        const size_t n4 = w4.size() / 32;
-        std::vector<int> need(n4, -1);
-        std::vector<std::pair<size_t, int>> st{{0, 0}};   // (node, next child to look at)
-        while (!st.empty()) {
-            auto &[nn, ci] = st.back();
-            if (ci < 4) {
-                int ref;
-                std::memcpy(&ref, &w4[nn * 32 + 24 + (size_t)ci], 4);
-                ++ci;
-                if (ref >= 0 && ref != RT_NO_CHILD && (size_t)ref < n4 && need[(size_t)ref] < 0) st.push_back({(size_t)ref, 0});
-                continue;
-            }
-            int nc = 0, deepest = 0;
-            for (int i = 0; i < 4; ++i) {
-                int ref;
-                std::memcpy(&ref, &w4[nn * 32 + 24 + (size_t)i], 4);
-                if (ref == RT_NO_CHILD) continue;
-                ++nc;
-                if (ref >= 0 && (size_t)ref < n4) deepest = std::max(deepest, need[(size_t)ref]);
-            }
-            need[nn] = std::max(nc - 1, 0) + deepest;
-            st.pop_back();
-        }
-        anyStack = std::max(need[0], 1);
-    }
-    // Round 4: the any-hit tree once more with QUANTISED child boxes -- 64 bytes per 4-wide node instead of 112, four gather loads per
-    // visit instead of seven.  Only the reference's LEAVES need their exact boxes (an any-hit answer is the OR over the leaves that pass their own box test);
-    // an inner box may be any box that contains them, and the slab arithmetic is monotonic in the box, so a decoded box that is checked HERE, in the very
-    // float expression the kernel decodes with (fmaf(q, 2^e, origin)), to contain the child's box passes whenever the child's does.  A leaf child passes
-    // the quantised test first and its exact box -- kept in `leafBox`, indexed from the leaf's first pair record (below) -- in the leaf phase.
-    // Built (and walked, rt_wave.hip launch_trace) when the 112-byte nodes outgrow one XCD's 4 MB L2 (kQNodesAbove): the decode costs 48 VALU operations per
-    // visit and a wave per SIMD, which a cache-resident tree does not earn back -- any-hit launch per frame, exact / quantised nodes, one launch set in flight:
-    // 20 k triangles 0.57 / 0.63-0.66 ms, 82 k (bench mesh, 0.6 MB of nodes) 0.66 / 0.74, 328 k (2.4 MB) 0.81 / 0.83-0.84, 1 M (9.8 MB) 15.9 / 13.6
-    // (profiles/r04_experiments.txt 19).  RT_QNODES=0 / 2 forces either.
-    //   piece 0: origin.xyz (float), biased exponents ex | ey << 8 | ez << 16       piece 1: lo.x lo.y lo.z hi.x, one byte per child
-    //   piece 2: hi.y hi.z - -                                                       piece 3: the four child references of the 112-byte node
-    std::vector<uint32_t> q4;
-    std::vector<float> leafBox;
-    const int qmode = getenv("RT_QNODES") ? atoi(getenv("RT_QNODES")) : -1;
-    if (rootRef4 == 0 && (qmode > 0 || (qmode < 0 && (w4.size() / 32) * 112 > kQNodesAbove))) {
-        const size_t n4 = w4.size() / 32;
-        q4.assign(n4 * 16, 0u);
-        bool okQ = true;
-        for (size_t nn = 0; nn < n4 && okQ; ++nn) {
-            const float *o = &w4[nn * 32];
-            int refs[4];
-            std::memcpy(refs, o + 24, 16);
-            uint32_t *q = &q4[nn * 16];
-            float org[3], scale[3];
-            uint32_t exps = 0;
-            for (int a = 0; a < 3; ++a) {
-                float lo = INFINITY, hi = -INFINITY;
-                for (int i = 0; i < 4; ++i) if (refs[i] != RT_NO_CHILD) { lo = std::min(lo, o[4 * a + i]); hi = std::max(hi, o[12 + 4 * a + i]); }
-                if (!(lo <= hi)) { lo = hi = 0.0f; }
-                int eb = 1;
-                const double ext = ((double)hi - (double)lo) / 255.0;
-                if (ext > 0.0) { int e2; (void)std::frexp(ext, &e2); eb = std::max(1, e2 - 1 + 127); }
-                while (eb <= 254 && std::fmaf(255.0f, std::ldexp(1.0f, eb - 127), lo) < hi) ++eb;
-                if (eb > 254) { okQ = false; break; }
-                org[a] = lo; scale[a] = std::ldexp(1.0f, eb - 127);
-                exps |= (uint32_t)eb << (8 * a);
-                std::memcpy(&q[a], &lo, 4);
-            }
-            if (!okQ) break;
-            q[3] = exps;
-            for (int i = 0; i < 4; ++i) {
-                q[12 + i] = (uint32_t)refs[i];
-                if (refs[i] == RT_NO_CHILD) continue;
-                for (int a = 0; a < 3; ++a) {
-                    const float lo = o[4 * a + i], hi = o[12 + 4 * a + i];
-                    int ql = (int)std::floor(((double)lo - (double)org[a]) / (double)scale[a]);
-                    ql = std::max(0, std::min(255, ql));
-                    while (ql > 0 && std::fmaf((float)ql, scale[a], org[a]) > lo) --ql;
-                    int qh = (int)std::ceil(((double)hi - (double)org[a]) / (double)scale[a]);
-                    qh = std::max(0, std::min(255, qh));
-                    while (qh < 255 && std::fmaf((float)qh, scale[a], org[a]) < hi) ++qh;
-                    if (std::fmaf((float)ql, scale[a], org[a]) > lo || std::fmaf((float)qh, scale[a], org[a]) < hi) okQ = false;
-                    const int wl = 4 + a, wh = a == 0 ? 7 : 7 + a;      // words: lo.x lo.y lo.z hi.x | hi.y hi.z
-                    q[wl] |= (uint32_t)ql << (8 * i);
-                    q[wh] |= (uint32_t)qh << (8 * i);
-                }
-            }
-        }
-        if (okQ) {
-            // A leaf's box sits at index first / R, R = the smallest number of pair records any leaf owns: consecutive leaves are at least R records apart,
-            // so the quotient is distinct per leaf, and the array is dense when the leaves are alike (a median-split tree: record counts differ by at most one).
-            // The kernel divides by multiplying with ceil(2^32 / R) (exact for first < 2^28, R <= 8); R = 1: the identity (magic 0).
-            int rmin = 8;
-            for (int i = 0; i < nNodes; ++i) if (nd[(size_t)i].count > 0) rmin = std::min(rmin, (nd[(size_t)i].count + 1) / 2);
-            if (getenv("RT_QNODES_SPARSE_BOXES")) rmin = 1;      // EXPERIMENT: one slot per pair record, as first built
-            c->leafBoxMagic = rmin <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + (uint64_t)rmin - 1) / (uint64_t)rmin);
-            leafBox.assign(((pairs.size() / 20) / (size_t)std::max(rmin, 1) + 1) * 8, 0.0f);
-            std::vector<char> taken(leafBox.size() / 8, 0);   // (host only: nothing but boxes is uploaded)
-            c->nLeafBoxes = 0;
-            for (int i = 0; i < nNodes; ++i) if (nd[(size_t)i].count > 0) {
-                ++c->nLeafBoxes;
-                const size_t first = (size_t)(-pairRefOf[(size_t)i] - 1) >> 3;
-                const size_t at = c->leafBoxMagic ? (size_t)(((uint64_t)first * c->leafBoxMagic) >> 32) : first;
-                const float *b = nodes12 + (size_t)i * 12;
-                const float box[8] = {b[0], b[1], b[2], b[4], b[5], b[6], 0.0f, 0.0f};
-                if (at * 8 + 8 > leafBox.size() || taken[at]) { okQ = false; break; }   // (cannot happen: distinct quotients)
-                std::memcpy(&leafBox[at * 8], box, sizeof box);
-                taken[at] = 1;
-            }
-            if (!okQ) { q4.clear(); leafBox.clear(); }
-        } else q4.clear();
-        if (!okQ) {   // asked for and not built: say so instead of falling back silently
-            c->sceneFlags |= RT_SCENE_QNODES_REJECTED;
-            if (getenv("RT_VERBOSE")) fprintf(stderr, "[rt_upload_bvh] quantised any-hit nodes rejected (exponent range or leaf-box index collision): walking the exact 112-byte nodes\n");
-        }
-    }
-    // Round 5 -- fused closest-hit records.  The closest-hit walk must keep the reference's visiting order (rt_bvh.glsl:205-241: near child first, far
-    // child behind the pop-time cull; ties and triangles a rounding in front of their leaf box make the answer depend on it), but nothing says it
-    // must spend one dependent memory round trip per binary node.  Whenever the walk enters a child X of a node N it visits X next, and X's record (the
-    // boxes of X's children) is known as soon as N's index is -- so the records of N's two children are stored TOGETHER under N's index, 128 bytes = one
-    // cache line per even-level inner node N ("hub"):
-    //     pieces 0-3: [A1.min, ref A1] [A1.max, ref A2] [A2.min, -] [A2.max, -]      A = N.left,  A1 / A2 = A's children
-    //     pieces 4-7: the same for B = N.right
-    // A leaf child X is stored as a half with ONE box: [X.min, leaf ref] [X.max, RT_NO_CHILD] [NaN box].  References are hub indices (>= 0) or the pair-record
-    // leaf codes of wnodesW (< 0).  The kernel (k_trace<.., FUSE>) fetches the eight pieces in one round trip and makes the reference's two steps from them:
-    // the step at N needs the boxes of A and B themselves, which are not stored -- they are the unions of their children's boxes, and the slab values of a
-    // union follow from the children's by min / max (per axis: tsm = min(tsm1, tsm2), tbg = max(tbg1, tbg2); tests/test_fused_nodes.py pins that identity
-    // against the slab test of the union box, signed zeros, infinities and the NaN of 0 * inf included).  That needs every inner box to BE the union of its children's, bit for bit --
-    // true of the reference's builder (bounds over a range = the union of the bounds over its halves, bvh.cpp:41-60) and of rt_build_bvh_gpu, checked
-    // here for whatever was uploaded; a tree that fails the check keeps the 64-byte records (RT_SCENE_NOT_FUSED in RtSceneInfo.flags).
-    std::vector<float> wF;
-    {
-        // built only where the option is on (both forms are measured options, off by default: no second and third copy of the tree in device memory otherwise)
-        const bool wantF = getenv("RT_FUSED") && atoi(getenv("RT_FUSED")) != 0;
-        bool okF = wantF && nd[0].count <= 0;
-        for (int i = 0; i < nNodes && okF; ++i) {
-            if (nd[(size_t)i].count > 0) continue;
-            const float *P = nodes12 + (size_t)i * 12, *L = nodes12 + (size_t)nd[(size_t)i].left * 12, *R = nodes12 + (size_t)nd[(size_t)i].right * 12;
-            for (int a = 0; a < 3; ++a)
-                if (!(P[a] == std::min(L[a], R[a])) || !(P[4 + a] == std::max(L[4 + a], R[4 + a]))) okF = false;
-        }
-        if (okF) {
-            struct Job { int bin; size_t at; };
-            std::vector<Job> jobs{{0, 0}};
-            wF.resize(32, 0.0f);
-            const float qnan = std::nanf("");
-            while (!jobs.empty()) {
-                const Job jb = jobs.back();
-                jobs.pop_back();
-                for (int h = 0; h < 2; ++h) {
-                    const int X = h == 0 ? nd[(size_t)jb.bin].left : nd[(size_t)jb.bin].right;
-                    int kids[2] = {X, -1};
-                    if (nd[(size_t)X].count <= 0) { kids[0] = nd[(size_t)X].left; kids[1] = nd[(size_t)X].right; }
-                    int refs[2] = {RT_NO_CHILD, RT_NO_CHILD};
-                    for (int k = 0; k < 2; ++k) {
-                        float box[6] = {qnan, qnan, qnan, qnan, qnan, qnan};
-                        if (kids[k] >= 0) {
-                            const float *b = nodes12 + (size_t)kids[k] * 12;
-                            box[0] = b[0]; box[1] = b[1]; box[2] = b[2]; box[3] = b[4]; box[4] = b[5]; box[5] = b[6];
-                            if (nd[(size_t)kids[k]].count > 0) refs[k] = refOfW(kids[k]);
-                            else {
-                                refs[k] = (int)(wF.size() / 32);
-                                if ((size_t)refs[k] >= ((size_t)1 << 29)) { okF = false; break; }
-                                wF.resize(wF.size() + 32, 0.0f);
-                                jobs.push_back({kids[k], (size_t)refs[k]});
-                            }
-                        }
-                        float *o = &wF[jb.at * 32 + (size_t)h * 16 + (size_t)k * 8];
-                        o[0] = box[0]; o[1] = box[1]; o[2] = box[2]; o[4] = box[3]; o[5] = box[4]; o[6] = box[5];
-                    }
-                    if (!okF) break;
-                    float *o = &wF[jb.at * 32 + (size_t)h * 16];
-                    std::memcpy(&o[3], &refs[0], 4);
-                    std::memcpy(&o[7], &refs[1], 4);
-                }
-                if (!okF) break;
-            }
-        }
-        if (!okF) { wF.clear(); if (wantF && nd[0].count <= 0) c->sceneFlags |= RT_SCENE_NOT_FUSED; }
-    }
-    // Round 5 -- implicit records.  What the traversal launches cost is their 16-byte lane-loads (one vector-L1 lookup each), and a 64-byte
-    // two-child record spends one of its four on two child references.  The reference's builder splits every range at its middle and stops at <= 8 triangles
-    // (bvh.cpp:62-76), so whenever n / 2^D falls into [4.5, 8] for some D every leaf sits at depth D and the tree is a perfect binary tree: a node is named by
-    // (depth d, path p = the left / right turns from the root as a binary number), its children are (d + 1, 2p) and (d + 1, 2p + 1), the leaves are p = 0 ..
-    // 2^D - 1 at depth D -- no reference needs to be stored.  Records: 48 bytes = the two child boxes = THREE loads, at the node's pre-order position
-    // d - popcount(p) + (p << (D - d)) (a left child sits next to its parent, as in the reference's own numbering); a leaf's triangle-pair records at
-    // p * R (R = the most records any leaf owns), the leaf's triangle count in the spare word of its first record.  Visiting order, boxes and triangle tests
-    // are those of the 64-byte records.  Checked here for whatever tree was uploaded (all leaves at one depth <= 23); others keep the explicit records.
-    std::vector<float> iN2, iPairs, iN4, iLeafBox;
-    std::vector<uint32_t> iQ4;
-    int implD = 0, implR = 0;
-    if (nd[0].count <= 0 && getenv("RT_IMPLICIT") && atoi(getenv("RT_IMPLICIT")) != 0) {
-        struct E { int node; int d; uint32_t p; };
-        std::vector<E> st{{0, 0, 0u}};
-        std::vector<int> nodeD((size_t)nNodes, -1);
-        std::vector<uint32_t> nodeP((size_t)nNodes, 0u);
-        int leafDepth = -1, maxRec = 0;
-        bool uniform = true;
-        while (!st.empty() && uniform) {
-            const E e = st.back();
-            st.pop_back();
-            nodeD[(size_t)e.node] = e.d; nodeP[(size_t)e.node] = e.p;
-            const N &n = nd[(size_t)e.node];
-            if (n.count > 0) {
-                if (leafDepth < 0) leafDepth = e.d;
-                if (e.d != leafDepth) uniform = false;
-                maxRec = std::max(maxRec, (n.count + 1) / 2);
-            } else {
-                if (e.d >= 23) { uniform = false; break; }
-                st.push_back({n.left, e.d + 1, e.p * 2u});
-                st.push_back({n.right, e.d + 1, e.p * 2u + 1u});
-            }
-        }
-        if (uniform && leafDepth >= 1) {
-            const int D = leafDepth;
-            iN2.assign((((size_t)1 << D) - 1) * 12, 0.0f);
-            iPairs.assign((((size_t)1 << D) * (size_t)maxRec + 8) * 20, 0.0f);
-            for (int i = 0; i < nNodes; ++i) {
-                if (nodeD[(size_t)i] < 0) continue;             // (unreachable nodes: none in a valid tree)
-                const N &n = nd[(size_t)i];
-                const int d = nodeD[(size_t)i];
-                const uint32_t pth = nodeP[(size_t)i];
-                if (n.count <= 0) {
-                    const size_t at = (size_t)d - (size_t)__builtin_popcount(pth) + ((size_t)pth << (D - d));
-                    const float *L = nodes12 + (size_t)n.left * 12, *R = nodes12 + (size_t)n.right * 12;
-                    const float rec[12] = {L[0], L[1], L[2], L[4], L[5], L[6], R[0], R[1], R[2], R[4], R[5], R[6]};
-                    std::memcpy(&iN2[at * 12], rec, sizeof rec);
-                } else {
-                    // the leaf's records as `pairs` holds them, at p * R; the count in the spare word of the first
-                    const size_t src = (size_t)(-pairRefOf[(size_t)i] - 1) >> 3, nrec = (size_t)(n.count + 1) / 2;
-                    float *o = &iPairs[(size_t)pth * (size_t)maxRec * 20];
-                    std::memcpy(o, &pairs[src * 20], nrec * 20 * sizeof(float));
-                    const uint32_t cnt = (uint32_t)n.count;
-                    std::memcpy(&o[19], &cnt, 4);
-                }
-            }
-            implD = D; implR = maxRec;
-            // ... and the any-hit walk's four-wide records in the same naming: an even-depth node (d, p) has the children (d + 2, 4p + j), j = 0..3 (or, when d + 1 == D,
-            // the two leaves 2p, 2p + 1), so the record is the four child boxes alone, component-wise: 96 bytes, SIX loads instead of seven, at the node's own
-            // pre-order position (odd-depth slots of the array stay empty and are never touched).  Where the quantised form is walked (trees beyond the L2) the same
-            // record in bytes: [origin.xyz, exponents] [lo.x lo.y lo.z hi.x] [hi.y hi.z - -] = 48 bytes, THREE loads instead of four, and the leaves' exact boxes at
-            // their ordinal p.
-            const bool wantQ = !q4.empty();
-            const float qnan = std::nanf("");
-            iN4.assign((((size_t)1 << D) - 1) * 24, 0.0f);
-            if (wantQ) { iQ4.assign((((size_t)1 << D) - 1) * 12, 0u); iLeafBox.assign(((size_t)1 << D) * 8, 0.0f); }
-            bool okI = true;
-            for (int i = 0; i < nNodes && okI; ++i) {
-                const int d = nodeD[(size_t)i];
-                if (d < 0) continue;
-                const N &n = nd[(size_t)i];
-                const uint32_t pth = nodeP[(size_t)i];
-                if (n.count > 0) {
-                    if (wantQ) { const float *b = nodes12 + (size_t)i * 12; const float box[8] = {b[0], b[1], b[2], b[4], b[5], b[6], 0.0f, 0.0f}; std::memcpy(&iLeafBox[(size_t)pth * 8], box, sizeof box); }
-                    continue;
-                }
-                if (d & 1) continue;
-                int kids[4] = {-1, -1, -1, -1};
-                if (d + 1 == D) { kids[0] = n.left; kids[1] = n.right; }
-                else { kids[0] = nd[(size_t)n.left].left; kids[1] = nd[(size_t)n.left].right; kids[2] = nd[(size_t)n.right].left; kids[3] = nd[(size_t)n.right].right; }
-                const size_t at = (size_t)d - (size_t)__builtin_popcount(pth) + ((size_t)pth << (D - d));
-                float *o = &iN4[at * 24];
-                for (int k = 0; k < 4; ++k) {
-                    const float *b = kids[k] >= 0 ? nodes12 + (size_t)kids[k] * 12 : nullptr;
-                    o[0 + k] = b ? b[0] : qnan; o[4 + k] = b ? b[1] : qnan; o[8 + k] = b ? b[2] : qnan;
-                    o[12 + k] = b ? b[4] : qnan; o[16 + k] = b ? b[5] : qnan; o[20 + k] = b ? b[6] : qnan;
-                }
-                if (!wantQ) continue;
-                // quantise as the explicit form does (above): origin = the children's common minimum, one power-of-two step per axis, bytes moved outward until the decoded
-                // box -- in the kernel's own expression fmaf(byte, 2^e, origin) -- contains the child's
-                uint32_t *q = &iQ4[at * 12];
-                float org[3], scale[3];
-                uint32_t exps = 0;
-                for (int a = 0; a < 3 && okI; ++a) {
-                    float lo = INFINITY, hi = -INFINITY;
-                    for (int k = 0; k < 4; ++k) if (kids[k] >= 0) { lo = std::min(lo, o[4 * a + k]); hi = std::max(hi, o[12 + 4 * a + k]); }
-                    if (!(lo <= hi)) { lo = hi = 0.0f; }
-                    int eb = 1;
-                    const double ext = ((double)hi - (double)lo) / 255.0;
-                    if (ext > 0.0) { int e2; (void)std::frexp(ext, &e2); eb = std::max(1, e2 - 1 + 127); }
-                    while (eb <= 254 && std::fmaf(255.0f, std::ldexp(1.0f, eb - 127), lo) < hi) ++eb;
-                    if (eb > 254) { okI = false; break; }
-                    org[a] = lo; scale[a] = std::ldexp(1.0f, eb - 127);
-                    exps |= (uint32_t)eb << (8 * a);
-                    std::memcpy(&q[a], &lo, 4);
-                }
-                if (!okI) break;
-                q[3] = exps;
-                for (int k = 0; k < 4; ++k) {
-                    if (kids[k] < 0) continue;
-                    for (int a = 0; a < 3; ++a) {
-                        const float lo = o[4 * a + k], hi = o[12 + 4 * a + k];
-                        int ql = (int)std::floor(((double)lo - (double)org[a]) / (double)scale[a]);
-                        ql = std::max(0, std::min(255, ql));
-                        while (ql > 0 && std::fmaf((float)ql, scale[a], org[a]) > lo) --ql;
-                        int qh = (int)std::ceil(((double)hi - (double)org[a]) / (double)scale[a]);
-                        qh = std::max(0, std::min(255, qh));
-                        while (qh < 255 && std::fmaf((float)qh, scale[a], org[a]) < hi) ++qh;
-                        if (std::fmaf((float)ql, scale[a], org[a]) > lo || std::fmaf((float)qh, scale[a], org[a]) < hi) okI = false;
-                        const int wl = 4 + a, wh = a == 0 ? 7 : 7 + a;      // words: lo.x lo.y lo.z hi.x | hi.y hi.z
-                        q[wl] |= (uint32_t)ql << (8 * k);
-                        q[wh] |= (uint32_t)qh << (8 * k);
-                    }
-                }
-            }
-            if (!okI) { iQ4.clear(); iLeafBox.clear(); }      // (the explicit quantised form passed the same checks, so this does not happen)
-        }
-    }
-    if (depth > 32) return fail(c, RT_ERR_UNSUPPORTED, "rt_upload_bvh: tree depth %d exceeds the 32-entry traversal stack", depth);
-    if (!q4.empty()) {
-        HIP_TRY(c, hipMalloc(&c->dQ4, q4.size() * 4));
-        HIP_TRY(c, hipMemcpy(c->dQ4, q4.data(), q4.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMalloc(&c->dLeafBox, leafBox.size() * 4));
-        HIP_TRY(c, hipMemcpy(c->dLeafBox, leafBox.data(), leafBox.size() * 4, hipMemcpyHostToDevice));
-        c->leafBoxBytes = leafBox.size() * 4;
-    }
-    if (!iN2.empty()) {
-        HIP_TRY(c, hipMalloc(&c->dIN2, iN2.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(c->dIN2, iN2.data(), iN2.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMalloc(&c->dIPairs, iPairs.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(c->dIPairs, iPairs.data(), iPairs.size() * sizeof(float), hipMemcpyHostToDevice));
-        c->implD = implD; c->implR = implR;
-        HIP_TRY(c, hipMalloc(&c->dIN4, iN4.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(c->dIN4, iN4.data(), iN4.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (!iQ4.empty()) {
-            HIP_TRY(c, hipMalloc(&c->dIQ4, iQ4.size() * 4));
-            HIP_TRY(c, hipMemcpy(c->dIQ4, iQ4.data(), iQ4.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMalloc(&c->dILeafBox, iLeafBox.size() * 4));
-            HIP_TRY(c, hipMemcpy(c->dILeafBox, iLeafBox.data(), iLeafBox.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
-    if (!wF.empty()) {
-        HIP_TRY(c, hipMalloc(&c->dWF, wF.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(c->dWF, wF.data(), wF.size() * sizeof(float), hipMemcpyHostToDevice));
-        c->nFused = wF.size() / 32;
-    }
-    HIP_TRY(c, hipMalloc(&c->dWNodes, wn.size() * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->dW4, w4.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(c->dW4, w4.data(), w4.size() * sizeof(float), hipMemcpyHostToDevice));
-    c->rootRef4 = rootRef4;
-    c->anyStack = anyStack;
-    c->rootRefW = refOfW(0);
-    HIP_TRY(c, hipMalloc(&c->dWNodesW, wnW.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(c->dWNodesW, wnW.data(), wnW.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc(&c->dPairs, pairs.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(c->dPairs, pairs.data(), pairs.size() * sizeof(float), hipMemcpyHostToDevice));
-    // 8 triangles of zero padding: the traversal kernels load triangle records in groups without a bounds branch
-    HIP_TRY(c, hipMalloc(&c->dTris, (size_t)(nTris + 8) * 12 * sizeof(float)));
-    HIP_TRY(c, hipMemset(c->dTris, 0, (size_t)(nTris + 8) * 12 * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(c->dWNodes, wn.data(), wn.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->dTris, tris12, (size_t)nTris * 12 * sizeof(float), hipMemcpyHostToDevice));
-    c->nNodes = nNodes; c->nTris = nTris; c->nInner = nInner; c->treeDepth = depth;
-    c->nWide4 = w4.size() / 32; c->nPairs = pairs.size() / 20 - 8;
-    c->rootRef = refOf(0);
-    std::memcpy(c->rootMin, nodes12, 12);
-    std::memcpy(c->rootMax, nodes12 + 4, 12);
-    return RT_OK;
+        (void)hipSetDevice(c->cfg.device);
+        HIP_TRY(c, sync_all(c));
+        release_mesh(c);   // an upload takes the scene over from the dynamic mesh
+        free_scene(c);
+        for (int i = 0; i < RT_MAX_LANES; ++i) { rt_wave_forget_share(c->wave[i]); rt_wave_set_probe_tree(c->wave[i], true); }   // a new scene: its share of bounce hits is not known
+        if (nNodes == 0 || nTris == 0) return RT_OK;
+        rtl::PackedScene s;
+        std::string err;
+        int rc = rtl::pack_scene(nodes12, nNodes, tris12, nTris, rtl::pack_options_from_env(), s, err);
+        if (rc != RT_OK) return fail(c, rc, "%s", err.c_str());
+        auto up = [&](float4 **dst, const auto &v) { if (rc == RT_OK) rc = upload(c, dst, v); };
+        // (the optional arrays first, then nodes, pairs and triangles: the order of allocation the upload has always had)
+        up(&c->dQ4, s.q4); up(&c->dLeafBox, s.leafBox);
+        up(&c->dIN2, s.iN2); up(&c->dIPairs, s.iPairs); up(&c->dIN4, s.iN4); up(&c->dIQ4, s.iQ4); up(&c->dILeafBox, s.iLeafBox);
+        up(&c->dWF, s.wF);
+        up(&c->dWNodes, s.wn); up(&c->dW4, s.w4); up(&c->dWNodesW, s.wnW); up(&c->dPairs, s.pairs);
+        if (rc == RT_OK) rc = [&]() -> int {
+            // 8 triangles of zero padding: the traversal kernels load triangle records in groups without a bounds branch
+            HIP_TRY(c, hipMalloc(&c->dTris, (size_t)(nTris + 8) * 12 * sizeof(float)));
+            HIP_TRY(c, hipMemset(c->dTris, 0, (size_t)(nTris + 8) * 12 * sizeof(float)));
+            HIP_TRY(c, hipMemcpy(c->dTris, tris12, (size_t)nTris * 12 * sizeof(float), hipMemcpyHostToDevice));
+            return RT_OK;
+        }();
+        if (rc != RT_OK) { free_scene(c); return rc; }
+        c->nNodes = nNodes; c->nTris = nTris; c->nInner = s.nInner; c->treeDepth = s.depth;
+        c->nWide4 = s.w4.size() / 32; c->nPairs = s.pairs.size() / 20 - 8; c->nFused = s.wF.size() / 32;
+        c->rootRef = s.rootRef; c->rootRefW = s.rootRefW; c->rootRef4 = s.rootRef4; c->anyStack = s.anyStack;
+        c->leafBoxMagic = s.leafBoxMagic; c->nLeafBoxes = s.nLeafBoxes; c->leafBoxBytes = s.leafBox.size() * 4;
+        c->implD = s.implD; c->implR = s.implR;
+        c->sceneFlags = s.flags;
+        std::memcpy(c->rootMin, s.rootMin, 12);
+        std::memcpy(c->rootMax, s.rootMax, 12);
+        if (!s.collapsed4) for (int i = 0; i < RT_MAX_LANES; ++i) rt_wave_set_probe_tree(c->wave[i], false);
+        return RT_OK;
     });
 }
 
@@ -1156,11 +569,6 @@ int rt_build_bvh_gpu(RtContext *c, const float *tris9, int nTris, float *nodes12
 }
 
 // ---- dynamic mesh: rt_mesh.hip builds, this file orders the rebuild against the lanes and installs its arrays
-static bool want_quantised(size_t nWide4, int rootRef4) {   // rt_upload_bvh's rule
-    const int qmode = getenv("RT_QNODES") ? atoi(getenv("RT_QNODES")) : -1;
-    return rootRef4 == 0 && (qmode > 0 || (qmode < 0 && nWide4 * 112 > kQNodesAbove));
-}
-
 int rt_bvh_layout(int nTris, RtBvhLayout *out) {
     if (!out) return RT_ERR_INVALID;
     std::memset(out, 0, sizeof *out);
@@ -1171,7 +579,7 @@ int rt_bvh_layout(int nTris, RtBvhLayout *out) {
         if (rc != RT_OK) return fail(nullptr, rc, "rt_bvh_layout: %d triangles exceed the 2^28 leaf encoding or the 32-entry traversal stack", nTris);
         out->nTris = L.nTris; out->nNodes = L.nNodes; out->nInner = L.nInner; out->treeDepth = L.treeDepth;
         out->nWide4 = (int32_t)L.nWide4; out->nPairs = (int32_t)L.nPairs; out->anyStack = L.anyStack;
-        out->quantised = want_quantised(L.nWide4, L.rootRef4) ? 1 : 0;
+        out->quantised = rtl::want_quantised(rtl::pack_options_from_env(), L.nWide4, L.rootRef4) ? 1 : 0;
         out->bytesNodes2 = (uint64_t)std::max(L.nInner, 1) * 64;
         out->bytesNodes4 = out->quantised ? (uint64_t)L.nWide4 * 64 + (uint64_t)L.nLeaves * 32 : (uint64_t)L.nWide4 * 128;
         out->bytesPairs = (uint64_t)L.nPairs * 80;
@@ -1203,10 +611,11 @@ static int mesh_upload(RtContext *c, const char *who, const float *positions, in
         return fail(c, RT_ERR_INVALID, "%s: partFirst runs from %d to %d, the mesh from 0 to %d triangles", who, partFirst[0], partFirst[nParts], nIdx / 3);
     for (int p = 0; p < nParts; ++p)
         if (partFirst[p + 1] < partFirst[p]) return fail(c, RT_ERR_INVALID, "%s: partFirst decreases at part %d (%d after %d)", who, p, partFirst[p + 1], partFirst[p]);
+    const rtl::PackOptions opt = rtl::pack_options_from_env();
     if (nIdx > 0) {
-        if (getenv("RT_FUSED") && atoi(getenv("RT_FUSED")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_FUSED records are not rebuilt on the device", who);
-        if (getenv("RT_IMPLICIT") && atoi(getenv("RT_IMPLICIT")) != 0) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_IMPLICIT records are not rebuilt on the device", who);
-        if (getenv("RT_ANYHIT_TREE") && std::string(getenv("RT_ANYHIT_TREE")) == "sah") return fail(c, RT_ERR_UNSUPPORTED, "%s: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device", who);
+        if (opt.fused) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_FUSED records are not rebuilt on the device", who);
+        if (opt.implicit) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_IMPLICIT records are not rebuilt on the device", who);
+        if (opt.anyhitSah) return fail(c, RT_ERR_UNSUPPORTED, "%s: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device", who);
         if (nIdx / 3 >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "%s: %d triangles exceed the 2^28 leaf encoding", who, nIdx / 3);
     }
     const int rc = rt_upload_bvh(c, nullptr, 0, nullptr, 0);   // waits for the lanes, removes the scene and the previous mesh, forgets the bounce share
@@ -1216,7 +625,7 @@ static int mesh_upload(RtContext *c, const char *who, const float *positions, in
         const int lr = rtl::bvh_layout(nIdx / 3, L);
         if (lr != RT_OK) return fail(c, lr, "%s: %d triangles cannot be laid out", who, nIdx / 3);
         const char *err = nullptr;
-        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, partFirst, nParts, want_quantised(L.nWide4, L.rootRef4), &c->mesh, &err);
+        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, partFirst, nParts, rtl::want_quantised(opt, L.nWide4, L.rootRef4), opt.sparseLeafBoxes, &c->mesh, &err);
         if (mr != RT_OK) { c->mesh = nullptr; return fail(c, mr, "%s: %s", who, err ? err : "layout failed"); }
         bool ok = hipEventCreateWithFlags(&c->evMeshDone, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&c->evMeshOrder, hipEventDisableTiming) == hipSuccess;
@@ -1327,7 +736,7 @@ static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = 
     c->dQ4 = okQ ? sc.q4 : nullptr; c->dLeafBox = okQ ? sc.leafBox : nullptr;
     c->leafBoxBytes = sc.leafBoxBytes; c->leafBoxMagic = sc.leafBoxMagic; c->nLeafBoxes = L.nLeaves;
     c->sceneFlags = (sc.q4 && !okQ) ? RT_SCENE_QNODES_REJECTED : 0;
-    if (sc.q4 && !okQ && getenv("RT_VERBOSE")) fprintf(stderr, "[%s] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n", who);
+    if (sc.q4 && !okQ && rtl::pack_options_from_env().verbose) fprintf(stderr, "[%s] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n", who);
     c->nNodes = L.nNodes; c->nTris = L.nTris; c->nInner = L.nInner; c->treeDepth = L.treeDepth;
     c->nWide4 = L.nWide4; c->nPairs = L.nPairs; c->nFused = 0;
     c->rootRef = L.rootRef; c->rootRefW = L.rootRefW; c->rootRef4 = L.rootRef4; c->anyStack = L.anyStack;
@@ -1542,6 +951,7 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
     const void *src = nullptr;
     size_t n = 0;
     const bool have = c->nNodes > 0 && c->nTris > 0;
+    const size_t implNodes = ((size_t)1 << c->implD) - 1;   // slots of the implicit node arrays; the leaves are one more
     switch (which) {
         case RT_SCENE_ARRAY_TRIS: src = c->dTris; n = (size_t)(c->nTris + 8) * 48; break;
         case RT_SCENE_ARRAY_PAIRS: src = c->dPairs; n = (c->nPairs + 8) * 80; break;
@@ -1550,6 +960,12 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
         case RT_SCENE_ARRAY_NODES4: src = c->dW4; n = c->nWide4 * 128; break;
         case RT_SCENE_ARRAY_QNODES4: src = c->dQ4; n = c->nWide4 * 64; break;
         case RT_SCENE_ARRAY_LEAFBOX: src = c->dLeafBox; n = c->leafBoxBytes; break;
+        case RT_SCENE_ARRAY_FUSED: src = c->dWF; n = c->nFused * 128; break;
+        case RT_SCENE_ARRAY_IMPL_NODES2: src = c->dIN2; n = implNodes * 48; break;
+        case RT_SCENE_ARRAY_IMPL_PAIRS: src = c->dIPairs; n = ((implNodes + 1) * (size_t)c->implR + 8) * 80; break;
+        case RT_SCENE_ARRAY_IMPL_NODES4: src = c->dIN4; n = implNodes * 96; break;
+        case RT_SCENE_ARRAY_IMPL_QNODES4: src = c->dIQ4; n = implNodes * 48; break;
+        case RT_SCENE_ARRAY_IMPL_LEAFBOX: src = c->dILeafBox; n = (implNodes + 1) * 32; break;
         default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
     }
     if (!have || !src) return RT_OK;
@@ -1560,6 +976,59 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
     HIP_TRY(c, sync_all(c));
     HIP_TRY(c, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
     return RT_OK;
+}
+
+int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, int nTris, const RtPackOptions *opt, int which, void *dst, size_t capacity,
+                        size_t *bytes) {
+    if (!bytes || !nodes12 || !tris12 || nNodes <= 0 || nTris <= 0) return RT_ERR_INVALID;
+    *bytes = 0;
+    return guarded(nullptr, "rt_debug_pack_scene", [&]() -> int {
+        rtl::PackOptions o = rtl::pack_options_from_env();
+        if (opt) { o.qnodes = opt->qnodes; o.fused = opt->fused != 0; o.implicit = opt->implicit != 0; o.anyhitSah = opt->anyhitSah != 0; o.sparseLeafBoxes = opt->sparseLeafBoxes != 0; }
+        rtl::PackedScene s;
+        std::string err;
+        const int rc = rtl::pack_scene(nodes12, nNodes, tris12, nTris, o, s, err);
+        if (rc != RT_OK) return fail(nullptr, rc, "%s", err.c_str());
+        std::vector<float> tris;
+        const void *src = nullptr;
+        size_t n = 0;
+        auto of = [&](const auto &v) { src = v.data(); n = v.size() * 4; };
+        switch (which) {
+            case RT_SCENE_ARRAY_TRIS: tris.assign(tris12, tris12 + (size_t)nTris * 12); tris.resize((size_t)(nTris + 8) * 12, 0.0f); of(tris); break;
+            case RT_SCENE_ARRAY_PAIRS: of(s.pairs); break;
+            case RT_SCENE_ARRAY_NODES2: of(s.wn); break;
+            case RT_SCENE_ARRAY_NODES2W: of(s.wnW); break;
+            case RT_SCENE_ARRAY_NODES4: of(s.w4); break;
+            case RT_SCENE_ARRAY_QNODES4: of(s.q4); break;
+            case RT_SCENE_ARRAY_LEAFBOX: of(s.leafBox); break;
+            case RT_SCENE_ARRAY_FUSED: of(s.wF); break;
+            case RT_SCENE_ARRAY_IMPL_NODES2: of(s.iN2); break;
+            case RT_SCENE_ARRAY_IMPL_PAIRS: of(s.iPairs); break;
+            case RT_SCENE_ARRAY_IMPL_NODES4: of(s.iN4); break;
+            case RT_SCENE_ARRAY_IMPL_QNODES4: of(s.iQ4); break;
+            case RT_SCENE_ARRAY_IMPL_LEAFBOX: of(s.iLeafBox); break;
+            case RT_SCENE_ARRAY_PACK_INFO: {
+                static_assert(sizeof(RtPackInfo) % 4 == 0, "RtPackInfo is handed out as words");
+                RtPackInfo info = {};
+                info.nNodes = nNodes; info.nTris = nTris; info.nInner = s.nInner; info.treeDepth = s.depth;
+                info.nWide4 = (int32_t)(s.w4.size() / 32); info.nPairs = (int32_t)(s.pairs.size() / 20 - 8); info.nFused = (int32_t)(s.wF.size() / 32);
+                info.flags = s.flags | (s.iN2.empty() ? 0 : RT_SCENE_IMPLICIT); info.implicitDepth = s.implD; info.implicitRecords = s.implR;
+                info.rootRef = s.rootRef; info.rootRefW = s.rootRefW; info.rootRef4 = s.rootRef4; info.anyStack = s.anyStack;
+                info.leafBoxMagic = s.leafBoxMagic; info.nLeafBoxes = (int32_t)s.nLeafBoxes; info.collapsed4 = s.collapsed4 ? 1 : 0;
+                std::memcpy(info.rootMin, s.rootMin, 12); std::memcpy(info.rootMax, s.rootMax, 12);
+                tris.resize(sizeof info / 4);
+                std::memcpy(tris.data(), &info, sizeof info);
+                of(tris);
+                break;
+            }
+            default: return fail(nullptr, RT_ERR_INVALID, "rt_debug_pack_scene: array %d", which);
+        }
+        *bytes = n;
+        if (!dst) return RT_OK;
+        if (capacity < n) return fail(nullptr, RT_ERR_INVALID, "rt_debug_pack_scene: array %d has %zu bytes, room for %zu", which, n, capacity);
+        if (n) std::memcpy(dst, src, n);
+        return RT_OK;
+    });
 }
 
 int rt_upload_env(RtContext *c, const uint8_t *faces, int faceSize, int channels) {

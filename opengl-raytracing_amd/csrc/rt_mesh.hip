@@ -3,7 +3,7 @@
 //
 // The reference's builder splits every range at its middle and stops at <= 8 triangles (bvh.cpp:62-76), so node numbering, links, leaf ranges and with
 // them every reference, record slot, stack need and array size of every device record form depend on the triangle count alone.  mesh_create lays that
-// out once on the host (the derivations of rt_upload_bvh, applied to the skeleton instead of to decoded nodes) and keeps it on the device as index
+// out once on the host (the derivations of rt_scene_pack, applied to the skeleton instead of to decoded nodes) and keeps it on the device as index
 // tables; what depends on the geometry -- node boxes and the order of the triangles -- is computed by the level kernels of rt_bvh_build.hpp, and one
 // emission kernel per record form then writes whole records through the tables.  Every array ends up byte for byte as rt_upload_bvh would have left it.
 #include <algorithm>
@@ -21,10 +21,11 @@
 #include "../../include/rt_mi355.h"
 #include "rt_bvh_build.hpp"
 #include "rt_mesh.hpp"
+#include "rt_qnode.hpp"
+#include "rt_scene_pack.hpp"
 
 #pragma clang fp contract(off)
 
-#define RT_NO_CHILD 0x7fffffff   // rt_device_shade.hpp
 
 namespace {
 
@@ -97,9 +98,9 @@ __global__ void k_mesh_nodes2(const uint32_t *__restrict__ bounds, const Wn2Tab 
     w[0] = make_float4(lx, ly, lz, __int_as_float(t.refLW)); w[1] = make_float4(Lx, Ly, Lz, __int_as_float(t.refRW)); w[2] = q2; w[3] = q3;
 }
 
-// 128-byte four-child any-hit records, component-wise with NaN boxes for absent children, and (q4 != null) the same node quantised exactly as
-// rt_upload_bvh quantises it: the same double-precision start values and the same fmaf(q, 2^e, origin) correction loops.  A node that cannot be
-// quantised sets *status; the host then walks the exact records, as after an upload.
+// 128-byte four-child any-hit records, component-wise with NaN boxes for absent children, and (q4 != null) the same node quantised by the function
+// rt_upload_bvh quantises it with (rt_qnode.hpp).  A node that cannot be quantised sets *status; the host then walks the exact records, as after an
+// upload.
 __global__ void k_mesh_nodes4(const uint32_t *__restrict__ bounds, const W4Tab *__restrict__ tab, int n4, float4 *__restrict__ w4, uint4 *__restrict__ q4,
                               uint32_t *__restrict__ status) {
     const int nn = blockIdx.x * blockDim.x + threadIdx.x;
@@ -115,44 +116,8 @@ __global__ void k_mesh_nodes4(const uint32_t *__restrict__ bounds, const W4Tab *
     w[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (!q4) return;
     uint32_t q[16];
-    for (int k = 0; k < 16; ++k) q[k] = 0u;
-    float org[3], scale[3];
-    uint32_t exps = 0;
-    bool okQ = true;
-    for (int a = 0; a < 3; ++a) {
-        float lo = INFINITY, hi = -INFINITY;
-        for (int i = 0; i < 4; ++i)
-            if (t.ref[i] != RT_NO_CHILD) { const float l = o[4 * a + i], h = o[12 + 4 * a + i]; lo = l < lo ? l : lo; hi = hi < h ? h : hi; }   // std::min / std::max
-        if (!(lo <= hi)) { lo = hi = 0.0f; }
-        int eb = 1;
-        const double ext = ((double)hi - (double)lo) / 255.0;
-        if (ext > 0.0) { const int e2 = (int)((__double_as_longlong(ext) >> 52) & 0x7ff) - 1022; eb = e2 - 1 + 127 > 1 ? e2 - 1 + 127 : 1; }   // frexp's exponent of a normal double
-        while (eb <= 254 && __builtin_fmaf(255.0f, __uint_as_float((uint32_t)eb << 23), lo) < hi) ++eb;
-        if (eb > 254) { okQ = false; break; }
-        org[a] = lo; scale[a] = __uint_as_float((uint32_t)eb << 23);
-        exps |= (uint32_t)eb << (8 * a);
-        q[a] = __float_as_uint(lo);
-    }
-    if (okQ) {
-        q[3] = exps;
-        for (int i = 0; i < 4; ++i) {
-            q[12 + i] = (uint32_t)t.ref[i];
-            if (t.ref[i] == RT_NO_CHILD) continue;
-            for (int a = 0; a < 3; ++a) {
-                const float lo = o[4 * a + i], hi = o[12 + 4 * a + i];
-                int ql = (int)floor(((double)lo - (double)org[a]) / (double)scale[a]);
-                ql = ql < 255 ? ql : 255; ql = ql > 0 ? ql : 0;
-                while (ql > 0 && __builtin_fmaf((float)ql, scale[a], org[a]) > lo) --ql;
-                int qh = (int)ceil(((double)hi - (double)org[a]) / (double)scale[a]);
-                qh = qh < 255 ? qh : 255; qh = qh > 0 ? qh : 0;
-                while (qh < 255 && __builtin_fmaf((float)qh, scale[a], org[a]) < hi) ++qh;
-                if (__builtin_fmaf((float)ql, scale[a], org[a]) > lo || __builtin_fmaf((float)qh, scale[a], org[a]) < hi) okQ = false;
-                const int wl = 4 + a, wh = a == 0 ? 7 : 7 + a;      // words: lo.x lo.y lo.z hi.x | hi.y hi.z
-                q[wl] |= (uint32_t)ql << (8 * i);
-                q[wh] |= (uint32_t)qh << (8 * i);
-            }
-        }
-    }
+    const bool okQ = rt_quantise_node4(o, t.ref, q);
+    for (int i = 0; i < 4; ++i) q[12 + i] = (uint32_t)t.ref[i];
     if (!okQ) atomicOr(status, 1u);
     uint4 *d = q4 + (size_t)nn * 4;
     for (int k = 0; k < 4; ++k) d[k] = make_uint4(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]);
@@ -283,8 +248,8 @@ template <class T> hipError_t dev_upload(Mesh *m, T **p, const std::vector<T> &v
 
 #define MESH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); mesh_destroy(m); return RT_ERR_HIP; } } while (0)
 
-int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, Mesh **out,
-                const char **err) {
+int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, bool sparseLeafBoxes,
+                Mesh **out, const char **err) {
     *out = nullptr;
     const int n = nIdx / 3;
     Mesh *m = new Mesh();
@@ -349,50 +314,12 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
     std::vector<W4Tab> w4;
     int anyStack = 0;
     if (countOf(0) <= 0) {
-        struct Job { int bin; size_t at; };
-        std::vector<Job> jobs{{0, 0}};
-        w4.push_back(W4Tab{});
-        while (!jobs.empty()) {
-            const Job jb = jobs.back();
-            jobs.pop_back();
-            int kids[4], nk = 0;
-            for (int ch : {sk[(size_t)jb.bin].left, sk[(size_t)jb.bin].right}) {
-                if (countOf(ch) > 0) kids[nk++] = ch;
-                else { kids[nk++] = sk[(size_t)ch].left; kids[nk++] = sk[(size_t)ch].right; }
-            }
-            for (int i = 0; i < 4; ++i) {
-                int ref = RT_NO_CHILD, slot = -1;
-                if (i < nk) {
-                    slot = slotOf[(size_t)kids[i]];
-                    if (countOf(kids[i]) > 0) ref = refOfW(kids[i]);
-                    else { ref = (int)w4.size(); w4.push_back(W4Tab{}); jobs.push_back({kids[i], (size_t)ref}); }
-                }
-                w4[jb.at].slot[i] = slot; w4[jb.at].ref[i] = ref;
-            }
+        for (const Wide4 &w : collapse_to_four([&](int i) { return sk[(size_t)i].left; }, [&](int i) { return sk[(size_t)i].right; }, countOf, refOfW)) {
+            W4Tab t;
+            for (int i = 0; i < 4; ++i) { t.slot[i] = w.kid[i] >= 0 ? slotOf[(size_t)w.kid[i]] : -1; t.ref[i] = w.ref[i]; }
+            w4.push_back(t);
         }
-        // exact stack need of the any-hit walk (rt_upload_bvh): S(node) = children - 1 + max over its inner children
-        const size_t n4 = w4.size();
-        std::vector<int> need(n4, -1);
-        std::vector<std::pair<size_t, int>> st{{0, 0}};
-        while (!st.empty()) {
-            auto &[nn, ci] = st.back();
-            if (ci < 4) {
-                const int ref = w4[nn].ref[ci];
-                ++ci;
-                if (ref >= 0 && ref != RT_NO_CHILD && (size_t)ref < n4 && need[(size_t)ref] < 0) st.push_back({(size_t)ref, 0});
-                continue;
-            }
-            int nc = 0, deepest = 0;
-            for (int i = 0; i < 4; ++i) {
-                const int ref = w4[nn].ref[i];
-                if (ref == RT_NO_CHILD) continue;
-                ++nc;
-                if (ref >= 0 && (size_t)ref < n4) deepest = std::max(deepest, need[(size_t)ref]);
-            }
-            need[nn] = std::max(nc - 1, 0) + deepest;
-            st.pop_back();
-        }
-        anyStack = std::max(need[0], 1);
+        anyStack = any_stack_need(w4.size(), [&](size_t nn, int i) { return w4[nn].ref[i]; });
     }
     const BvhLayout &L = m->lay;
     if (nNodes != L.nNodes || nInner != L.nInner || maxDepth + 1 != L.treeDepth || pairTab.size() != L.nPairs || std::max<size_t>(w4.size(), 1) != L.nWide4 ||
@@ -404,13 +331,12 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
     std::vector<LeafTab> leafTab;
     size_t leafBoxFloats = 0;
     if (quantised) {
-        if (getenv("RT_QNODES_SPARSE_BOXES")) rmin = 1;
-        m->sc.leafBoxMagic = rmin <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + (uint64_t)rmin - 1) / (uint64_t)rmin);
-        leafBoxFloats = ((L.nPairs + 8) / (size_t)std::max(rmin, 1) + 1) * 8;
+        const LeafBoxRule rule(rmin, sparseLeafBoxes);
+        m->sc.leafBoxMagic = rule.magic;
+        leafBoxFloats = rule.floats(L.nPairs + 8);
         for (int i = 0; i < nNodes; ++i) {
             if (countOf(i) <= 0) continue;
-            const size_t first = (size_t)(-pairRefOf[(size_t)i] - 1) >> 3;
-            const size_t at = m->sc.leafBoxMagic ? (size_t)(((uint64_t)first * m->sc.leafBoxMagic) >> 32) : first;
+            const size_t at = rule.index((size_t)(-pairRefOf[(size_t)i] - 1) >> 3);
             if (at * 8 + 8 > leafBoxFloats) { if (err) *err = "internal: leaf-box index out of range"; delete m; return RT_ERR_STATE; }
             leafTab.push_back({slotOf[(size_t)i], (uint32_t)at});
         }

@@ -29,10 +29,10 @@ struct MeshScene {
 
 struct Mesh;
 // positions / indices: validated host arrays.  partFirst: nParts + 1 validated part boundaries in triangle units; the parts table, the
-// per-triangle part lookup and the matrix table (identities) go to the device here.  quantised: build the quantised any-hit form as well.  May allocate
-// and synchronise.
-int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, Mesh **out,
-                const char **err);
+// per-triangle part lookup and the matrix table (identities) go to the device here.  quantised: build the quantised any-hit form as well; sparseLeafBoxes: its leaf
+// boxes one slot per pair record (PackOptions).  May allocate and synchronise.
+int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, bool quantised, bool sparseLeafBoxes,
+                Mesh **out, const char **err);
 void mesh_destroy(Mesh *m);
 const BvhLayout &mesh_layout(const Mesh *m);
 const MeshScene &mesh_scene(const Mesh *m);

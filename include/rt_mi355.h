@@ -693,6 +693,42 @@ typedef struct RtPackInfo {
 enum { RT_SCENE_ARRAY_PACK_INFO = 100 };
 int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, int nTris, const RtPackOptions *opt, int which, void *dst, size_t capacity,
                         size_t *bytes);
+/* Diagnostics, host side (no GPU needed, no context): the ray-queue plan of one launch set of the wavefront pipeline (csrc/rt_wave_plan.cpp,
+ * DESIGN.md 16) -- the arithmetic rt_render_frame(s) follows, for checks.  RtWaveOptions: every environment variable of frame rendering as a lane reads it
+ * when the context is created; a "...Set" field says whether the variable was set at all where unset has a meaning of its own. */
+typedef struct RtWaveOptions {
+    uint64_t budgetBytes;      /* RT_QUEUE_BUDGET_MB << 20 */
+    uint64_t q2Cap;            /* RT_Q2_CAP (tests: force the overflow path), used when q2CapSet */
+    int32_t q2CapSet;
+    int32_t q2Predict;         /* RT_Q2_PREDICT: 0 = shadow queue 2 always sized for the worst case */
+    int32_t binGi, packetAO, chunksFromSlots;   /* RT_BIN_GI, RT_PACKET_AO, RT_CHUNKS_FROM_SLOTS: booleans */
+    int32_t probeMode;         /* RT_BOUNCE_PROBE: 0 never, 1 always, -1 auto */
+    int32_t cuSplit;           /* RT_CU_SPLIT: eighths of the CUs for the shading stream, 1..7; 0 = unset */
+    int32_t shadePrioritySet, shadePriority;    /* RT_SHADE_PRIORITY */
+    int32_t skipTraversalSet, skipTraversal;    /* RT_DEBUG_SKIP_TRAVERSAL */
+    int32_t gridPct, gridPctPrimary;            /* RT_GRID_PCT, RT_GRID_PCT_PRIMARY: >= 1; 0 = unset (by the scene and the rank count) */
+    int32_t chunkPrimarySet, chunkPrimary;      /* RT_CHUNK_PRIMARY */
+    int32_t traceStatsSet, traceStats;          /* RT_TRACE_STATS */
+    int32_t traceTimingSet, traceTiming;        /* RT_TRACE_TIMING */
+    int32_t reserved;
+} RtWaveOptions;
+typedef struct RtWavePlanArray { char name[16]; uint64_t offset, bytes; } RtWavePlanArray;   /* name: the WaveBuf member; offset 2^64-1: reserved, not handed out */
+typedef struct RtWavePlanArena { uint64_t bytes, allocBytes; int32_t nArrays, reserved; RtWavePlanArray arrays[9]; } RtWavePlanArena;
+typedef struct RtWavePlan {
+    RtWaveOptions options;     /* as used */
+    uint64_t slots, perHit, chBudget;
+    uint64_t ch, room;         /* hits per chunk, hits a growing arena is sized for (hits < 0: both chBudget) */
+    uint64_t q2Entries;        /* entries per slot of shadow queue 2 at `ch` */
+    int32_t spp, ao, S1, S2, L1, deferred;
+    int32_t nChunks;           /* hits < 0: the upper bound, every pixel slot a hit */
+    int32_t reserved;
+    /* frame: per pixel slot.  rays / results: laid out for `ch` hits (bytes), allocated for `room` hits when they grow (allocBytes). */
+    RtWavePlanArena frame, rays, results;
+} RtWavePlan;
+/* slots: pixel slots of the launch set, a multiple of 256.  aoRays: 0 = AO off.  opt == NULL: the options of the environment.  hits < 0: the plan before
+ * the hit count is known; else the plan behind its read-back (ignored under RT_CHUNKS_FROM_SLOTS).  share: the share of (hit, sample) pairs whose bounce
+ * ray hit in earlier launch sets, 0 = nothing known.  RT_ERR_UNSUPPORTED (message: rt_last_error(NULL)) for a chunk of 2^31 queue entries or more. */
+int rt_debug_wave_plan(uint64_t slots, int spp, int aoRays, const RtWaveOptions *opt, int64_t hits, double share, RtWavePlan *out);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

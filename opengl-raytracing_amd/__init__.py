@@ -9,6 +9,7 @@ src/render/render.cpp:55-243).  It never renders on the CPU: every frame goes th
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import types
 from pathlib import Path
@@ -359,6 +360,7 @@ SIGNATURES = {
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
     "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
+    "rt_debug_wave_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),   # RtWaveOptions, RtWavePlan: _wave_plan_types
     "rt_debug_pack_scene": (C.c_int, [_FP, C.c_int, _FP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -659,6 +661,65 @@ def pack_scene(nodes12, tris12, **options) -> dict:
     info["rootMin"], info["rootMax"] = raw.view(np.float32)[17:20].copy(), raw.view(np.float32)[20:23].copy()
     out["info"] = types.SimpleNamespace(**info)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _wave_plan_types():
+    """RtWaveOptions and RtWavePlan, declared at the first rt.wave_plan call and not at import: bench.py's short run is sensitive to what importing the
+    package allocates (profiles/r14_scene_pack.txt 3)."""
+    class RtWaveOptions(_Struct):
+        _fields_ = [("budgetBytes", C.c_uint64), ("q2Cap", C.c_uint64)] + \
+                   [(n, i32) for n in ("q2CapSet", "q2Predict", "binGi", "packetAO", "chunksFromSlots", "probeMode", "cuSplit", "shadePrioritySet",
+                                       "shadePriority", "skipTraversalSet", "skipTraversal", "gridPct", "gridPctPrimary", "chunkPrimarySet", "chunkPrimary",
+                                       "traceStatsSet", "traceStats", "traceTimingSet", "traceTiming", "reserved")]
+
+    class RtWavePlanArray(_Struct):
+        _fields_ = [("name", C.c_char * 16), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+    class RtWavePlanArena(_Struct):
+        _fields_ = [("bytes", C.c_uint64), ("allocBytes", C.c_uint64), ("nArrays", i32), ("reserved", i32), ("arrays", RtWavePlanArray * 9)]
+
+    class RtWavePlan(_Struct):
+        _fields_ = [("options", RtWaveOptions)] + [(n, C.c_uint64) for n in ("slots", "perHit", "chBudget", "ch", "room", "q2Entries")] + \
+                   [(n, i32) for n in ("spp", "ao", "S1", "S2", "L1", "deferred", "nChunks", "reserved")] + \
+                   [(n, RtWavePlanArena) for n in ("frame", "rays", "results")]
+
+    return RtWaveOptions, RtWavePlan
+
+
+def wave_plan(slots, spp, ao_rays=0, *, hits=None, share=0.0, **options):
+    """The ray-queue plan of one launch set of the wavefront pipeline, without a context or a GPU (rt_debug_wave_plan).  slots: pixel slots
+    (tiles x 256 x frames of the batch); ao_rays: AO rays per hit, 0 = AO off; hits: the hit count once it is known (None: before); share: the share of
+    (hit, sample) pairs whose bounce ray hit in earlier launch sets.  options: fields of RtWaveOptions by name (budget_mb for budgetBytes; q2_cap sets
+    q2Cap and q2CapSet) over the defaults; with none given the options come from the environment, as a lane reads them when the context is created.
+    -> namespace of the plan's scalars, `options` (dict) and, per arena (frame, rays, results), bytes, allocBytes and arrays = [(name, offset, bytes)]
+    with offset None for a span that is reserved but not handed out.  RtError(RT_ERR_UNSUPPORTED) for a chunk of 2^31 queue entries or more."""
+    RtWaveOptions, RtWavePlan = _wave_plan_types()
+    opt = None
+    if options:
+        opt = RtWaveOptions(budgetBytes=16 << 30, q2Predict=1, probeMode=-1)
+        if "budget_mb" in options:
+            opt.budgetBytes = int(options.pop("budget_mb")) << 20
+        if "q2_cap" in options:
+            opt.q2CapSet, opt.q2Cap = 1, int(options.pop("q2_cap"))
+        names = {n for n, _ in RtWaveOptions._fields_} - {"reserved"}
+        for k, v in options.items():
+            if k not in names:
+                raise TypeError(f"wave_plan: unknown option {k}")
+            setattr(opt, k, int(v))
+    out = RtWavePlan()
+    rc = lib().rt_debug_wave_plan(int(slots), int(spp), int(ao_rays), None if opt is None else C.byref(opt), -1 if hits is None else int(hits), float(share),
+                                  C.byref(out))
+    if rc != RT_OK:
+        raise RtError(rc, (lib().rt_last_error(None) or b"").decode() or "rt_debug_wave_plan")
+
+    def arena(a):
+        arrays = [(x.name.decode(), None if x.offset == 2**64 - 1 else int(x.offset), int(x.bytes)) for x in a.arrays[:a.nArrays]]
+        return types.SimpleNamespace(bytes=int(a.bytes), allocBytes=int(a.allocBytes), arrays=arrays)
+
+    scalars = {n: int(getattr(out, n)) for n in ("slots", "perHit", "chBudget", "ch", "room", "q2Entries", "spp", "ao", "S1", "S2", "L1", "nChunks")}
+    return types.SimpleNamespace(**scalars, deferred=bool(out.deferred), options={n: int(getattr(out.options, n)) for n, _ in RtWaveOptions._fields_ if n != "reserved"},
+                                 frame=arena(out.frame), rays=arena(out.rays), results=arena(out.results))
 
 
 def load_obj(path):

@@ -21,6 +21,7 @@
 #include "rt_bvh_cost.hpp"
 #include "rt_mesh.hpp"
 #include "rt_scene_pack.hpp"
+#include "rt_wave_plan.hpp"
 #include "rt_wave.hpp"
 
 using namespace rtd;
@@ -1027,6 +1028,16 @@ int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, i
         if (!dst) return RT_OK;
         if (capacity < n) return fail(nullptr, RT_ERR_INVALID, "rt_debug_pack_scene: array %d has %zu bytes, room for %zu", which, n, capacity);
         if (n) std::memcpy(dst, src, n);
+        return RT_OK;
+    });
+}
+
+int rt_debug_wave_plan(uint64_t slots, int spp, int aoRays, const RtWaveOptions *opt, int64_t hits, double share, RtWavePlan *out) {
+    if (!out || slots == 0 || slots % 256 != 0 || spp < 1 || aoRays < 0 || !(share >= 0.0)) return RT_ERR_INVALID;
+    return guarded(nullptr, "rt_debug_wave_plan", [&]() -> int {
+        const rtl::WavePlan p = rtl::wave_plan((size_t)slots, spp, aoRays, opt ? *opt : rtl::wave_options_from_env());
+        if (p.tooLarge) return fail(nullptr, RT_ERR_UNSUPPORTED, "%s", rtl::kTooLargeMessage);
+        rtl::wave_plan_describe(p, hits, share, *out);
         return RT_OK;
     });
 }

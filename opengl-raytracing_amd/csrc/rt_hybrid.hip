@@ -33,6 +33,7 @@
 #endif
 #include "rt_device_analytic.hpp"
 #include "rt_wave.hpp"
+#include "rt_wave_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -344,8 +345,6 @@ __global__ __launch_bounds__(256) void k_hybrid_resolve(const DevFrame *__restri
     tg.gnrm[slot] = pack_half4(mk4(gn.x, gn.y, gn.z, gn.w));
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
 struct RtHybrid {
@@ -440,10 +439,21 @@ int rt_hybrid_render(RtHybrid *h, RtContext *ctx, hipStream_t st, const DevFrame
     if (h->evFree) H_TRY(hipStreamWaitEvent(st, h->evFree, 0));   // the previous frame's kernels (on another lane's stream) still use the arena
     bool waited = false;
 
-    auto bytes_for = [&](size_t nS, size_t capQ, size_t capL) {
+    // the arena of a chunk of nS pixel slots, once: walked by a cursor that counts (bytes_for) or hands out the addresses
+    auto lay_out = [&](rtl::ArenaCursor c, HybridBuf &hb, size_t nS, size_t capQ, size_t capL) {
         const size_t T = nS * (size_t)SPP;
-        return align_up(capQ * 16, 256) * 2 + align_up(capQ * 4, 256) + align_up(capL * 4, 256) * 3 + align_up(T * 4, 256) * 4 + align_up(T * 16, 256) +
-               align_up(nS * 8, 256) + align_up(nS * 16, 256) * 2 + 4096;
+        hb.qO = c.take_n<float4>(capQ); hb.qD = c.take_n<float4>(capQ); hb.qDst = c.take_n<uint32_t>(capQ);
+        hb.logT = c.take_n<float>(capL); hb.logTri = c.take_n<int>(capL); hb.logLim = c.take_n<float>(capL);
+        hb.state = c.take_n<uint32_t>(T); hb.logBase = c.take_n<uint32_t>(T); hb.todo = c.take_n<uint32_t>(T); hb.recd = c.take_n<uint32_t>(T);
+        hb.rad = c.take_n<float4>(T);
+        hb.sMotion = c.take_n<float2>(nS); hb.sPos = c.take_n<float4>(nS); hb.sNrm = c.take_n<float4>(nS);
+        return c.off + 4096;
+    };
+    auto bytes_for = [&](size_t nS, size_t capQ, size_t capL) { HybridBuf counted; return lay_out(rtl::ArenaCursor{}, counted, nS, capQ, capL); };
+    // queue and log capacities of T (pixel, sample) pairs at the current estimates
+    auto capacities = [&](size_t T, size_t &capQ, size_t &capL) {
+        capQ = std::min(std::max<size_t>((size_t)((double)T * h->ratioQ) + 4096, 4096), T * (size_t)qmax);
+        capL = std::min<size_t>(std::min(std::max<size_t>((size_t)((double)T * h->ratioL) + 4096, 4096), T * (size_t)qmax * 4), 0xfffffff0u);
     };
     size_t slot0 = 0;
     int attempts = 0;
@@ -456,9 +466,8 @@ int rt_hybrid_render(RtHybrid *h, RtContext *ctx, hipStream_t st, const DevFrame
         nS = std::min(nS, nSlots - slot0);      // nSlots is a multiple of 256
         size_t T = nS * (size_t)SPP;
         while (T >= ((size_t)1 << 32) / 4) { nS = std::max<size_t>(nS / 2 / 256 * 256, 256); T = nS * (size_t)SPP; }   // 32-bit thread ids and log addresses
-        size_t capQ = std::max<size_t>((size_t)((double)T * h->ratioQ) + 4096, 4096), capL = std::max<size_t>((size_t)((double)T * h->ratioL) + 4096, 4096);
-        capQ = std::min(capQ, T * (size_t)qmax);
-        capL = std::min<size_t>(std::min(capL, T * (size_t)qmax * 4), 0xfffffff0u);
+        size_t capQ, capL;
+        capacities(T, capQ, capL);
         size_t need = bytes_for(nS, capQ, capL);
         if (h->arenaBytes < need) {
             // the arena grows on demand; when the device cannot give that much (other contexts, the wavefront pipeline's arenas), the chunk is halved
@@ -475,23 +484,14 @@ int rt_hybrid_render(RtHybrid *h, RtContext *ctx, hipStream_t st, const DevFrame
                 nS = std::max<size_t>(nS / 2 / 256 * 256, 256);
                 h->okSlots = nS;                // remembered: the next chunk and the next frame start here instead of failing the same allocations again
                 T = nS * (size_t)SPP;
-                capQ = std::min(std::max<size_t>((size_t)((double)T * h->ratioQ) + 4096, 4096), T * (size_t)qmax);
-                capL = std::min<size_t>(std::min(std::max<size_t>((size_t)((double)T * h->ratioL) + 4096, 4096), T * (size_t)qmax * 4), 0xfffffff0u);
+                capacities(T, capQ, capL);
                 need = bytes_for(nS, capQ, capL);
             }
             h->arenaBytes = need;
         }
         HybridBuf hb;
-        {
-            char *q = (char *)h->arena;
-            auto take = [&](size_t bytes) { char *r = q; q += align_up(bytes, 256); return r; };
-            hb.qO = (float4 *)take(capQ * 16); hb.qD = (float4 *)take(capQ * 16); hb.qDst = (uint32_t *)take(capQ * 4);
-            hb.logT = (float *)take(capL * 4); hb.logTri = (int *)take(capL * 4); hb.logLim = (float *)take(capL * 4);
-            hb.state = (uint32_t *)take(T * 4); hb.logBase = (uint32_t *)take(T * 4); hb.todo = (uint32_t *)take(T * 4); hb.recd = (uint32_t *)take(T * 4);
-            hb.rad = (float4 *)take(T * 16);
-            hb.sMotion = (float2 *)take(nS * 8); hb.sPos = (float4 *)take(nS * 16); hb.sNrm = (float4 *)take(nS * 16);
-            hb.stgO = (float4 *)h->staging; hb.stgD = (float4 *)((char *)h->staging + stgEach);
-        }
+        (void)lay_out(rtl::ArenaCursor{(char *)h->arena}, hb, nS, capQ, capL);
+        hb.stgO = (float4 *)h->staging; hb.stgD = (float4 *)((char *)h->staging + stgEach);
         hb.cnt = h->cnt; hb.qmax = qmax; hb.SPP = SPP; hb.check = h->check ? 1 : 0;
         hb.capQ = (uint32_t)std::min<size_t>(capQ, 0xfffffff0u); hb.capL = (uint32_t)capL;
         hb.slot0 = (uint32_t)slot0; hb.nS = (uint32_t)nS; hb.T = (uint32_t)T;

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/rt_mi355.h"
+#include "rt_wave_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1951,6 +1952,21 @@ __global__ void k_accum_tally(const uint32_t *counts, unsigned long long *acc, i
     if (i == 6) acc[6] += (unsigned long long)frames;
 }
 
+// Workgroups of a persistent traversal grid: the resident 256-thread workgroups per CU (8 at most) times the CUs, gridPct per cent of that, 8 at least.
+// The runtime's answer is kept per (device, kernel, LDS bytes): a process may hold contexts on devices of different shapes
+template <class Kernel>
+unsigned persistent_grid(Kernel kernel, size_t ldsBytes, int cus, int gridPct) {
+    thread_local std::map<std::tuple<int, const void *, size_t>, int> occ;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int &perCU = occ[std::make_tuple(dev, (const void *)kernel, ldsBytes)];
+    if (perCU == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
+        perCU = std::min(perCU, 8);
+    }
+    return (unsigned)std::max(8, cus * perCU * gridPct / 100);
+}
+
 template <class Src, bool ANY>
 uint32_t launch_trace(hipStream_t st, int cus, int gridPct, int depth, const DevFrame *fr, const DevScene &hs, Src src, uint32_t *head, unsigned long long *tally,
                   unsigned long long *gatherLoads, TraceTune tune, unsigned long long *stats = nullptr, unsigned maxBlocks = 0) {
@@ -1970,16 +1986,7 @@ uint32_t launch_trace(hipStream_t st, int cus, int gridPct, int depth, const Dev
     auto go = [&](auto k) {
         const auto kernel = decltype(k)::fn;
         built = decltype(k)::bits;
-        // the runtime's answer per (device, kernel, LDS bytes): a process may hold contexts on devices of different shapes
-        thread_local std::map<std::tuple<int, const void *, size_t>, int> occ;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        int &perCU = occ[std::make_tuple(dev, (const void *)kernel, ldsBytes)];
-        if (perCU == 0) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
-            perCU = std::min(perCU, 8);
-        }
-        unsigned blocks = (unsigned)std::max(8, cus * perCU * gridPct / 100);
+        unsigned blocks = persistent_grid(kernel, ldsBytes, cus, gridPct);
         if (maxBlocks) blocks = std::min(blocks, maxBlocks);   // (ray queries: no more waves than the rays can occupy)
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), ldsBytes, st, fr, nodes, pairRecords, src, head, tally, gatherLoads, tune, stack, stats, leafBoxes);
     };
@@ -2012,15 +2019,7 @@ uint32_t launch_packets(hipStream_t st, int cus, int gridPct, int depth, const D
                     unsigned long long *gatherLoads, TraceTune tune) {
     const int stack = std::max(4, hs.anyStack > 0 ? hs.anyStack : 3 * ((depth + 1) / 2));
     const size_t ldsBytes = (size_t)256 * stack * 4;
-    thread_local std::map<std::pair<int, size_t>, int> occ;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int &perCU = occ[{dev, ldsBytes}];
-    if (perCU == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_packets, 256, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
-        perCU = std::min(perCU, 8);
-    }
-    const unsigned blocks = (unsigned)std::max(8, cus * perCU * gridPct / 100);
+    const unsigned blocks = persistent_grid(k_trace_packets, ldsBytes, cus, gridPct);
     hipLaunchKernelGGL(k_trace_packets, dim3(blocks), dim3(256), ldsBytes, st, fr, hs.w4, hs.pairs, src, head, tally, gatherLoads, tune, stack);
     return (uint32_t)RT_BUILD_PACKETS << RT_BUILD_ANY_SHIFT;
 }
@@ -2060,35 +2059,25 @@ size_t rt_arena_pool_bytes(const RtArenaPool *p) { size_t b = 0; for (int i = 0;
 
 struct RtWave {
     std::string err;
-    RtArenaPool *pool = nullptr;   // null: this lane owns its arena (chunkArena below)
-    int arena = 0;                 // index into pool: lane % n for a launch set of one chunk, the lane itself for a set of several (see rt_wave_render)
+    RtArenaPool *pool = nullptr;   // the context's ray arenas (rt_api.hip)
+    int arena = 0;                 // index into pool: lane % n for a launch set of one chunk, the lane itself for a set of several (wave_settle_chunks)
     int lane = 0;
     int cus = 256;
-    // ray-queue budget per frame lane; 288 GB of HBM make this cheap.  16 GB hold the queues of a whole batch of eight 1080p / 4 spp frames (7.4 M hits x
-    // 2.1 KB) in ONE chunk: no hit-count read-back, half the launches (1.76-1.80 -> 1.68-1.72 ms per frame against 8 GB; profiles/r03_experiments.txt)
-    size_t budgetBytes = (size_t)16 << 30;
+    rtl::WaveOptions opt = rtl::wave_default_options();   // the options of the environment, read ONCE: at rt_wave_create (rt_wave_plan.cpp)
     TraceTune tune = tune_from_env();   // chunk 0 = run length chosen in the kernel from the queue size
     // allocations
     size_t slotsCap = 0;      // per-frame arrays sized for this many pixel slots
-    size_t chunkBytes = 0;    // bytes of the per-chunk arena
     int prevChunks = 0, prevSPP = 1;   // chunks / spp of this lane's previous launch set: its hit count and bounce-hit counts are copied to hostHits[1], [2..] before the counters are cleared
-    double q2FracOwn = 0.0;   // (no pool)
-    int q2SPPOwn = 0;
-    void *frameArena = nullptr, *chunkArena = nullptr, *resultArena = nullptr;
+    void *frameArena = nullptr, *chunkArena = nullptr, *resultArena = nullptr;   // chunkArena: the pool's arena this launch set uses
     size_t resultBytes = 0;   // per-lane traversal results (what k_combine reads)
     uint32_t *counts = nullptr, *heads = nullptr;
     int launchCap = 0, chunkCap = 0;     // trace launches `heads` holds cursors for / chunks `counts` holds bounce counters for
     unsigned long long *acc = nullptr;   // traced-ray tallies accumulated over frames
     unsigned long long *stats = nullptr; // RT_TRACE_STATS=1: 4 stages x 8 diagnostic sums
     uint32_t *hostHits = nullptr;        // pinned: the hit count of a batch that needs more than one chunk (read back once per batch)
-    bool packetAO = false;               // RT_PACKET_AO=1 (measured option, round 4): the AO rays of a hit traced as one packet (k_trace_packets) instead of one by one in the any-hit launch
     hipStream_t shadeStream = nullptr;   // RT_CU_SPLIT: the shading kernels' stream (a CU-masked one), else null
     hipEvent_t hopEv = nullptr;
-    bool binGi = false;                  // RT_BIN_GI=1: bounce rays sorted by direction inside each workgroup of k_gen_direct (experiment)
-    bool chunksFromSlots = false;        // RT_CHUNKS_FROM_SLOTS=1 (tests): launch the chunk loop for every pixel slot, as rounds 1-2 did
     uint32_t builds = 0;                 // RT_BUILD_* bits of the traversal builds launched since the last rt_wave_builds reset
-    // RT_BOUNCE_PROBE: 0 never, 1 always, -1 (auto) while the bounce-hit share of earlier launch sets is below kProbeShareMax
-    int probeMode = -1;
     bool probeTree = true;               // the any-hit tree is the collapse of the binary one (rt_upload_bvh): false under RT_ANYHIT_TREE=sah
     unsigned long long *probeAcc = nullptr;   // device, monotonic: [0] bounce rays the probe walked [1] rays it re-traced closest-hit
     unsigned long long probeLaunches = 0, closestLaunches = 0;   // bounce launches (chunks) with / without the probe
@@ -2106,25 +2095,21 @@ RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
     w->cus = cus > 0 ? cus : 256;
     w->pool = pool;
     w->lane = lane;
-    w->arena = pool ? lane % pool->n : 0;
-    if (const char *e = getenv("RT_QUEUE_BUDGET_MB")) w->budgetBytes = (size_t)atoll(e) << 20;
-    if (const char *e = getenv("RT_DEBUG_SKIP_TRAVERSAL")) w->tune.skipTraversal = atoi(e);
-    if (const char *e = getenv("RT_CHUNKS_FROM_SLOTS")) w->chunksFromSlots = atoi(e) != 0;
-    if (const char *e = getenv("RT_BIN_GI")) w->binGi = atoi(e) != 0;
-    if (const char *e = getenv("RT_PACKET_AO")) w->packetAO = atoi(e) != 0;
-    if (const char *e = getenv("RT_BOUNCE_PROBE")) w->probeMode = std::string(e) == "auto" ? -1 : (atoi(e) != 0 ? 1 : 0);
+    w->arena = lane % pool->n;
+    w->opt = rtl::wave_options_from_env();
+    if (w->opt.skipTraversalSet) w->tune.skipTraversal = w->opt.skipTraversal;
     (void)hipEventCreateWithFlags(&w->hopEv, hipEventDisableTiming);
-    if (const char *e = getenv("RT_CU_SPLIT")) {
-        const int k = std::max(1, std::min(7, atoi(e)));
+    if (w->opt.cuSplit) {
+        const int k = w->opt.cuSplit;
         uint32_t mask[8];
         for (int i = 0; i < 8; ++i) { uint32_t m = 0; for (int b = 0; b < 32; ++b) if (((i * 32 + b) & 7) < k) m |= 1u << b; mask[i] = m; }
         if (hipExtStreamCreateWithCUMask(&w->shadeStream, 8, mask) != hipSuccess) w->shadeStream = nullptr;
     }
     // EXPERIMENT RT_SHADE_PRIORITY=p: the shading kernels on a second stream of queue priority p (-1 high, 1 low; no CU mask), the traversal launches on the lane's own
-    else if (const char *e = getenv("RT_SHADE_PRIORITY")) {
+    else if (w->opt.shadePrioritySet) {
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const int p = std::max(greatest, std::min(least, atoi(e)));
+        const int p = std::max(greatest, std::min(least, (int)w->opt.shadePriority));
         if (hipStreamCreateWithPriority(&w->shadeStream, hipStreamNonBlocking, p) != hipSuccess) w->shadeStream = nullptr;
     }
     return w;
@@ -2134,7 +2119,6 @@ void rt_wave_destroy(RtWave *w) {
     if (w->shadeStream) (void)hipStreamDestroy(w->shadeStream);
     if (w->hopEv) (void)hipEventDestroy(w->hopEv);
     if (w->frameArena) (void)hipFree(w->frameArena);
-    if (w->chunkArena && !w->pool) (void)hipFree(w->chunkArena);
     if (w->resultArena) (void)hipFree(w->resultArena);
     if (w->counts) (void)hipFree(w->counts);
     if (w->heads) (void)hipFree(w->heads);
@@ -2147,166 +2131,149 @@ void rt_wave_destroy(RtWave *w) {
     delete w;
 }
 const char *rt_wave_error(const RtWave *w) { return w->err.c_str(); }
-size_t rt_wave_frame_bytes(const RtWave *w) { return w ? w->slotsCap * (4 + 4 + 4 + sizeof(HitRec) + 16 + 4 + 8 + 8) + (w->pool ? 0 : w->chunkBytes) + w->resultBytes : 0; }
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+size_t rt_wave_frame_bytes(const RtWave *w) { return w ? rtl::arena_bytes(rtl::frame_arena(w->slotsCap)) + w->resultBytes : 0; }
 
 #define W_TRY(expr)                                                                   \
     do {                                                                              \
         hipError_t e_ = (expr);                                                       \
         if (e_ != hipSuccess) { w->err = std::string(#expr) + ": " + hipGetErrorString(e_); return RT_ERR_HIP; } \
     } while (0)
+#define W_STEP(expr)                      \
+    do {                                  \
+        const int rc_ = (expr);           \
+        if (rc_ != RT_OK) return rc_;     \
+    } while (0)
 
-int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dFrame, const DevFrame &host, Targets tg,
-                   unsigned long long *, bool count, int treeDepth, hipEvent_t evPrevDone, bool cacheResident) {
-    if (count) { w->err = "work counters are produced by the megakernel pipeline (RT_PIPELINE_MEGAKERNEL)"; return RT_ERR_UNSUPPORTED; }
-    const RtUniforms &u = host.u;
-    const int batch = std::max(host.g.batch, 1);
-    const size_t nSlots = (size_t)std::max(host.g.nLocalTiles, 1) * 256 * (size_t)batch;   // pixel slots of all frames of the batch
-    const int SPP = std::max(u.spp, 1);
-    const int A = (u.enableAO == 1) ? std::max(u.aoSamples, 0) : 0;
-    const int S1 = A + 4 * SPP + 2, S2 = 6 * SPP;   // WaveBuf::sh1_slot
+// ---- one launch set (a frame, or a batch of frames) on its way through the steps of rt_wave_render
+struct LaunchSet {
+    RtWave *w;
+    RtContext *ctx;
+    hipStream_t st, ss;        // the lane's stream: traversal launches; the shading kernels' stream (== st unless RT_CU_SPLIT / RT_SHADE_PRIORITY)
+    const DevFrame *dFrame;
+    const DevFrame *host;      // host copy of *dFrame
+    Targets tg;
+    int treeDepth;
+    rtl::WavePlan plan;
+    WaveBuf wb;
+    size_t CH;                 // hits per chunk
+    int nChunks;
+    int giCopied;              // bounce-hit counters of the lane's previous launch set on their way to hostHits[2..]
+    int gridPct, gridPctPrimary;
+    unsigned long long *S;     // RT_TRACE_STATS / RT_TRACE_TIMING sums, or null
+    bool probe;                // this set's bounce rays are walked any-hit first
+    unsigned retraceBlocks, listedBlocks;
+};
 
-    if (!w->acc) { W_TRY(hipMalloc(&w->acc, 16 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->acc, 0, 16 * sizeof(unsigned long long), st)); }
-    if (!w->probeAcc) { W_TRY(hipMalloc(&w->probeAcc, 2 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->probeAcc, 0, 2 * sizeof(unsigned long long), st)); }
-    {   // the share of bounce hits belongs to one spp (rt_upload_bvh / rt_resize forget it too)
-        double &share = w->pool ? w->pool->q2Frac : w->q2FracOwn;
-        int &shareSPP = w->pool ? w->pool->q2SPP : w->q2SPPOwn;
-        if (shareSPP != SPP) { share = 0.0; shareSPP = SPP; }
-        if (w->prevSPP != SPP) w->prevChunks = 0;   // this lane's previous launch set ran at another spp: its bounce counts are not read
-    }
-    // per-frame arena: cand, primT, primTri, hits
-    if (w->slotsCap < nSlots) {
+static_assert(sizeof(HitRec) == rtl::kHitRecBytes, "the planner's frame arena holds HitRec records");
+
+static double &wave_share(RtWave *w) { return w->pool->q2Frac; }   // (live: updated behind a set's hit-count read-back, before a large set sizes its arena)
+
+static hipError_t wave_hop(RtWave *w, hipStream_t from, hipStream_t to) {
+    if (from == to) return hipSuccess;
+    hipError_t e = hipEventRecord(w->hopEv, from);
+    return e != hipSuccess ? e : hipStreamWaitEvent(to, w->hopEv, 0);
+}
+// One timed stage on `on` -- the shading stream L.ss or the traversal stream L.st: `on` waits for what the lane's stream holds, and the lane's stream for the stage.
+// EXPERIMENT (RT_CU_SPLIT=k): the shading kernels run on a second stream restricted to k eighths of the CUs, the traversal
+// launches -- the lane's own stream, created with the complementary mask in rt_api.hip -- on the rest.  ss == st when the experiment is off.
+template <class Launch>
+static int wave_stage(LaunchSet &L, int stage, hipStream_t on, Launch launch) {
+    RtWave *w = L.w;
+    W_TRY(wave_hop(w, L.st, on));
+    rt_stage_begin(L.ctx, stage, on);
+    launch();
+    rt_stage_end(L.ctx, stage, 1, on);
+    W_TRY(wave_hop(w, on, L.st));
+    return RT_OK;
+}
+// the sharded cursors of trace launch k of chunk c -- 0: the any-hit launch, 1: the bounce rays, 2: the probe's re-trace, 3: the AO packets ([0] of the table: the primary rays)
+static uint32_t *wave_cursor(const WaveBuf &wb, int c, int k) { return &wb.heads[(size_t)(1 + c * 4 + k) * kHeadWords]; }
+
+// step 1 -- lane bookkeeping: the tallies, the share of bounce hits (it belongs to one spp; rt_upload_bvh / rt_resize forget it too), the per-frame arena
+static int wave_begin(LaunchSet &L) {
+    RtWave *w = L.w;
+    const int SPP = L.plan.spp;
+    if (!w->acc) { W_TRY(hipMalloc(&w->acc, 16 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->acc, 0, 16 * sizeof(unsigned long long), L.st)); }
+    if (!w->probeAcc) { W_TRY(hipMalloc(&w->probeAcc, 2 * sizeof(unsigned long long))); W_TRY(hipMemsetAsync(w->probeAcc, 0, 2 * sizeof(unsigned long long), L.st)); }
+    if (w->pool->q2SPP != SPP) { w->pool->q2Frac = 0.0; w->pool->q2SPP = SPP; }
+    if (w->prevSPP != SPP) w->prevChunks = 0;   // this lane's previous launch set ran at another spp: its bounce counts are not read
+    if (w->slotsCap < L.plan.slots) {
         if (w->frameArena) (void)hipFree(w->frameArena);
         w->frameArena = nullptr;
-        W_TRY(hipMalloc(&w->frameArena, nSlots * (4 + 4 + 4 + sizeof(HitRec) + 16 + 4 + 8 + 8)));
-        w->slotsCap = nSlots;
+        W_TRY(hipMalloc(&w->frameArena, rtl::arena_bytes(rtl::frame_arena(L.plan.slots))));
+        w->slotsCap = L.plan.slots;
     }
-    // chunk capacity from the budget
-    // bytes per hit: 36 per light ray (origin, direction, tMax word), 16 per dense ray (AO, bounce) + 16 per hit and dense group for its origin; results as before
-    const int L1 = S1 - A;                                     // light slots of shadow queue 1
-    const size_t giOrgs = w->binGi ? (size_t)SPP : 1;          // bounce origins per hit (RT_BIN_GI: one per record)
-    const size_t perHit = (size_t)(L1 + S2) * 36 + (size_t)(A + SPP) * 16 + (size_t)((A > 0 ? 1 : 0) + giOrgs) * 16 + (size_t)S1 + (size_t)SPP * 12 + (size_t)S2;
-    const size_t CHbudget = align_up(std::min(nSlots, std::max<size_t>(w->budgetBytes / perHit, 4096)), 256);
-    // ray records + liveness words (read by the traversal launches only: a SHARED arena can be handed on as soon as the last of them is done) ...
-    // (shadow queue 2 -- six slots per bounce HIT -- is an allocation of its own since round 5: q2_bytes(entries per slot))
-    auto rays_bytes = [&](size_t ch) {
-        return align_up(ch * (size_t)L1 * 16, 256) + align_up(ch * (size_t)S1 * 16, 256) + align_up(ch * (size_t)L1 * 4, 256) + align_up(ch * 16, 256) +
-               align_up(ch * (size_t)SPP * 16, 256) + align_up(ch * giOrgs * 16, 256) + 4096;
-    };
-    auto q2_bytes = [&](size_t n) { return align_up(n * 6 * 16, 256) * 2 + align_up(n * 6 * 4, 256) + 4096; };
-    // ... and the results k_combine reads (1 byte per any-hit ray, 8 per bounce ray, 4 per (hit, sample)) + the bounce probe's hit list (4 per bounce ray): the lane's own
-    auto result_bytes = [&](size_t ch) {
-        return align_up(ch * (size_t)S1, 256) + align_up(ch * (size_t)SPP * 8, 256) + align_up(ch * (size_t)S2, 256) * 2 + align_up(ch * (size_t)SPP * 4, 256) * 3 + 4096;
-    };
-    // arrays that hold `ch` hits (grown, never shrunk; `room`: allocate for that many when growing, so that a batch with a few more hits fits too)
-    // Shadow queue 2 (round 5): six ray records per bounce HIT, behind queue 1 in the same allocation.  Sized for the worst case -- every bounce ray
-    // hits -- it was 48 % of the ray arenas; on the bench view 1 % of that is used.  A LARGE launch set (sized from its hit count anyway) sizes it from what earlier
-    // launch sets needed: twice the largest share of (hit, sample) pairs that bounced so far + slack, the worst case while nothing is known; pairs beyond the capacity -- a
-    // view whose bounce hits more than doubled -- are traced in place by k_gen_gi_overflow instead of queued (an order of magnitude slower per ray: 1 M-triangle scene, 20 ms
-    // per frame with half the pairs overflowing -- hence never a guess below the worst case).  Small launch sets take the worst case, no question asked of the device.
-    const double &q2Share = w->pool ? w->pool->q2Frac : w->q2FracOwn;   // (live: updated behind this set's hit-count read-back, before a large set sizes its arena)
-    bool predictQ2 = false;          // set for deferred sets below
-    const bool predictOn = !(getenv("RT_Q2_PREDICT") && atoi(getenv("RT_Q2_PREDICT")) == 0);   // RT_Q2_PREDICT=0: always the worst case, as in rounds 1-4 (A/B)
-    auto n2_of = [&](size_t ch) -> size_t {
-        const size_t worst = ch * (size_t)SPP;
-        size_t n2 = (predictOn && predictQ2 && q2Share > 0.0) ? std::max<size_t>((size_t)(2.0 * q2Share * (double)worst) + 65536, worst / 32) : worst;
-        if (const char *e = getenv("RT_Q2_CAP")) n2 = std::max<size_t>((size_t)atoll(e), 64);   // tests: force the overflow path
-        return align_up(std::min(n2, worst), 64);
-    };
-    auto arena_bytes = [&](size_t ch) { return rays_bytes(ch) + q2_bytes(n2_of(ch)); };
-    auto ensure = [&](size_t ch, size_t room) -> int {
-        room = std::max(room, ch);
-        if (w->resultBytes < result_bytes(ch)) {
-            if (w->resultArena) { W_TRY(hipStreamSynchronize(st)); (void)hipFree(w->resultArena); }
-            w->resultArena = nullptr;
-            w->resultBytes = 0;
-            W_TRY(hipMalloc(&w->resultArena, result_bytes(room)));
-            w->resultBytes = result_bytes(room);
-        }
-        if (w->pool) {
-            // a shared arena: grown once its current user is done with it
-            RtArenaPool &P = *w->pool;
-            const int a = w->arena;
-            // (grown when too small; given back ONCE it is more than 1.6 x what a launch set asks for now that the share of bounce hits is known: the worst-case
-            // allocation of the first launch sets.  Either way behind the arena's current user.)
-            // The new size is for the LARGEST launch set the arena has held, not for this one: bench.py's five-frame warm-up batch once shrank an arena that the
-            // seven-frame batches of the timed region then had to grow again (a device-wide synchronisation and a multi-gigabyte hipMalloc inside a 34 ms region:
-            // 1.65 -> 1.81 ms per step).
-            room = std::max(room, P.maxCh[a]);
-            if (P.bytes[a] < arena_bytes(ch) || (predictOn && predictQ2 && q2Share > 0.0 && P.bytes[a] > arena_bytes(room) + arena_bytes(room) / 2 + arena_bytes(room) / 10)) {
-                if (P.lastUser[a]) W_TRY(hipEventSynchronize(P.freeEv[a]));
-                if (P.mem[a]) (void)hipFree(P.mem[a]);
-                P.mem[a] = nullptr; P.bytes[a] = 0;
-                W_TRY(hipMalloc(&P.mem[a], arena_bytes(room)));
-                P.bytes[a] = arena_bytes(room);
-            }
-            P.maxCh[a] = room;
-            w->chunkArena = P.mem[a];
-        } else if (w->chunkBytes < arena_bytes(ch)) {
-            if (w->chunkArena) { W_TRY(hipStreamSynchronize(st)); (void)hipFree(w->chunkArena); }
-            w->chunkArena = nullptr;
-            w->chunkBytes = 0;
-            W_TRY(hipMalloc(&w->chunkArena, arena_bytes(room)));
-            w->chunkBytes = arena_bytes(room);
-        }
-        return RT_OK;
-    };
-    // Round 4: a launch set whose queues would be large if every pixel slot were a hit (a batch of eight 1080p frames: 30 GB) is sized from its HIT count --
-    // read back once, behind k_post_primary, on this lane's stream only (the other lanes keep the GPU busy: 1.726 vs 1.719 ms per frame with and without
-    // that read-back, profiles/r04_experiments.txt) -- instead of from the budget.  Small launch sets (and RT_CHUNKS_FROM_SLOTS) are sized from their pixel
-    // slots as before and never wait for the host.
-    constexpr size_t kComfortBytes = (size_t)4 << 30;
-    const bool deferred = !w->chunksFromSlots && rays_bytes(CHbudget) + q2_bytes(CHbudget * (size_t)SPP) > kComfortBytes;
-    size_t CH = CHbudget;
-    WaveBuf wb;
-    auto carve = [&](size_t ch) {
-        char *q = (char *)w->chunkArena;
-        auto take = [&](size_t bytes) { char *r = q; q += align_up(bytes, 256); return r; };
-        wb.shO = (float4 *)take(ch * (size_t)L1 * 16); wb.shD = (float4 *)take(ch * (size_t)S1 * 16);
-        wb.shT = (float *)take(ch * (size_t)L1 * 4); wb.aoOrg = (float4 *)take(ch * 16);
-        wb.giD = (float4 *)take(ch * (size_t)SPP * 16); wb.giOrg = (float4 *)take(ch * giOrgs * 16);
-        const size_t n2 = n2_of(ch);
-        wb.sh2O = (float4 *)take(n2 * 6 * 16); wb.sh2D = (float4 *)take(n2 * 6 * 16); wb.sh2T = (float *)take(n2 * 6 * 4);
-        wb.q2Stride = (uint32_t)n2;
-        q = (char *)w->resultArena;
-        wb.occ1 = (uint8_t *)take(ch * (size_t)S1);
-        wb.giT = (float *)take(ch * (size_t)SPP * 4); wb.giTri = (int *)take(ch * (size_t)SPP * 4);
-        wb.occ2 = (uint8_t *)take(ch * (size_t)S2);
-        wb.occOvf = (uint8_t *)take(ch * (size_t)S2);
-        wb.giPos = (int *)take(ch * (size_t)SPP * 4);
-        wb.giPerm = w->binGi ? (int *)take(ch * (size_t)SPP * 4) : nullptr;
-        wb.giHit = (uint32_t *)take(ch * (size_t)SPP * 4);
-        wb.CH = (uint32_t)ch;
-    };
-    if (CHbudget * (size_t)std::max(S1, S2) >= ((size_t)1 << 31)) { w->err = "ray queue chunk exceeds 2^31 entries; lower RT_QUEUE_BUDGET_MB"; return RT_ERR_UNSUPPORTED; }
-    {
-        char *p = (char *)w->frameArena;
-        wb.cand = (uint32_t *)p; p += nSlots * 4;
-        wb.primT = (float *)p; p += nSlots * 4;
-        wb.primTri = (int *)p; p += nSlots * 4;
-        wb.hits = (HitRec *)p; p += nSlots * sizeof(HitRec);
-        wb.pendC = (float4 *)p; p += nSlots * 16;     // nSlots is a multiple of 256: every sub-array stays 16-byte aligned
-        wb.pendPos = (uint2 *)p; p += nSlots * 8;
-        wb.pendNrm = (uint2 *)p; p += nSlots * 8;
-        wb.pendMy = (float *)p;
+    return RT_OK;
+}
+
+// step 3 -- arrays that hold `ch` hits (grown, never shrunk; `room`: allocate for that many when growing, so that a batch with a few more hits fits too).
+// predict: shadow queue 2 from the share of bounce hits (a deferred set behind its read-back), else the worst case.
+static int wave_grow_arenas(LaunchSet &L, size_t ch, size_t room, bool predict) {
+    RtWave *w = L.w;
+    const rtl::WavePlan &plan = L.plan;
+    room = std::max(room, ch);
+    if (w->resultBytes < plan.result_bytes(ch)) {
+        if (w->resultArena) { W_TRY(hipStreamSynchronize(L.st)); (void)hipFree(w->resultArena); }
+        w->resultArena = nullptr;
+        w->resultBytes = 0;
+        W_TRY(hipMalloc(&w->resultArena, plan.result_bytes(room)));
+        w->resultBytes = plan.result_bytes(room);
     }
-    wb.shO = wb.shD = wb.aoOrg = wb.giD = wb.giOrg = wb.sh2O = wb.sh2D = nullptr; wb.shT = wb.sh2T = nullptr;   // (deferred: carved behind k_post_primary)
-    wb.occ1 = wb.occ2 = wb.occOvf = nullptr; wb.giT = nullptr; wb.giTri = wb.giPos = wb.giPerm = nullptr; wb.giHit = nullptr;
-    wb.q2Stride = 0;
-    if (!deferred) {
-        if (w->pool) w->arena = (nSlots + CH - 1) / CH > 1 ? w->lane : w->lane % w->pool->n;
-        int rc = ensure(CH, CH);
-        if (rc != RT_OK) return rc;
-        carve(CH);
+    // a shared arena: grown once its current user is done with it
+    RtArenaPool &P = *w->pool;
+    const int a = w->arena;
+    const double share = wave_share(w);
+    auto arena_bytes = [&](size_t n) { return plan.ray_bytes(n, predict, share); };
+    // (grown when too small; given back ONCE it is more than 1.6 x what a launch set asks for now that the share of bounce hits is known: the worst-case
+    // allocation of the first launch sets.  Either way behind the arena's current user.)
+    // The new size is for the LARGEST launch set the arena has held, not for this one: bench.py's five-frame warm-up batch once shrank an arena that the
+    // seven-frame batches of the timed region then had to grow again (a device-wide synchronisation and a multi-gigabyte hipMalloc inside a 34 ms region:
+    // 1.65 -> 1.81 ms per step).
+    room = std::max(room, P.maxCh[a]);
+    if (P.bytes[a] < arena_bytes(ch) || (plan.opt.q2Predict && predict && share > 0.0 && P.bytes[a] > arena_bytes(room) + arena_bytes(room) / 2 + arena_bytes(room) / 10)) {
+        if (P.lastUser[a]) W_TRY(hipEventSynchronize(P.freeEv[a]));
+        if (P.mem[a]) (void)hipFree(P.mem[a]);
+        P.mem[a] = nullptr; P.bytes[a] = 0;
+        W_TRY(hipMalloc(&P.mem[a], arena_bytes(room)));
+        P.bytes[a] = arena_bytes(room);
     }
-    wb.CH = (uint32_t)CH; wb.A = A; wb.SPP = SPP;
-    int nChunks = (int)((nSlots + CH - 1) / CH);   // upper bound (every pixel slot a hit); cut down to the hit count below
-    // cursor table (one set of sharded cursors per trace launch) and per-chunk bounce counters: grown when a small queue budget
-    // cuts the frame into more chunks than seen so far (4K / 16 spp at RT_QUEUE_BUDGET_MB=128 is 491 chunks).  Both arrays are
-    // only touched by this lane's stream, which is drained first.
+    P.maxCh[a] = room;
+    w->chunkArena = P.mem[a];
+    return RT_OK;
+}
+
+// the WaveBuf pointers of an arena, from the list its bytes came from
+static void wave_point_frame_arrays(LaunchSet &L) {
+    void *p[rtl::WA_COUNT] = {};
+    rtl::arena_carve(rtl::frame_arena(L.plan.slots), L.w->frameArena, p);
+    WaveBuf &wb = L.wb;
+    wb.cand = (uint32_t *)p[rtl::WA_CAND]; wb.primT = (float *)p[rtl::WA_PRIMT]; wb.primTri = (int *)p[rtl::WA_PRIMTRI]; wb.hits = (HitRec *)p[rtl::WA_HITS];
+    wb.pendC = (float4 *)p[rtl::WA_PENDC]; wb.pendPos = (uint2 *)p[rtl::WA_PENDPOS]; wb.pendNrm = (uint2 *)p[rtl::WA_PENDNRM]; wb.pendMy = (float *)p[rtl::WA_PENDMY];
+}
+static void wave_point_chunk_arrays(LaunchSet &L, size_t ch, bool predict) {
+    const size_t n2 = L.plan.q2_entries(ch, predict, wave_share(L.w));
+    void *p[rtl::WA_COUNT] = {};
+    rtl::arena_carve(L.plan.ray_arena(ch, n2), L.w->chunkArena, p);
+    rtl::arena_carve(L.plan.result_arena(ch), L.w->resultArena, p);
+    WaveBuf &wb = L.wb;
+    wb.shO = (float4 *)p[rtl::WA_SHO]; wb.shD = (float4 *)p[rtl::WA_SHD]; wb.shT = (float *)p[rtl::WA_SHT]; wb.aoOrg = (float4 *)p[rtl::WA_AOORG];
+    wb.giD = (float4 *)p[rtl::WA_GID]; wb.giOrg = (float4 *)p[rtl::WA_GIORG];
+    wb.sh2O = (float4 *)p[rtl::WA_SH2O]; wb.sh2D = (float4 *)p[rtl::WA_SH2D]; wb.sh2T = (float *)p[rtl::WA_SH2T];
+    wb.q2Stride = (uint32_t)n2;
+    wb.occ1 = (uint8_t *)p[rtl::WA_OCC1]; wb.giT = (float *)p[rtl::WA_GIT]; wb.giTri = (int *)p[rtl::WA_GITRI];
+    wb.occ2 = (uint8_t *)p[rtl::WA_OCC2]; wb.occOvf = (uint8_t *)p[rtl::WA_OCCOVF];
+    wb.giPos = (int *)p[rtl::WA_GIPOS]; wb.giPerm = (int *)p[rtl::WA_GIPERM]; wb.giHit = (uint32_t *)p[rtl::WA_GIHIT];   // (giPerm: null unless RT_BIN_GI)
+    wb.CH = (uint32_t)ch;
+}
+
+// step 4 -- cursor table (one set of sharded cursors per trace launch) and per-chunk bounce counters: grown when a small queue budget
+// cuts the frame into more chunks than seen so far (4K / 16 spp at RT_QUEUE_BUDGET_MB=128 is 491 chunks).  Both arrays are
+// only touched by this lane's stream, which is drained first.
+static int wave_cursor_table(LaunchSet &L) {
+    RtWave *w = L.w;
+    const int nChunks = L.nChunks;
     if (1 + nChunks * 4 > w->launchCap || nChunks > w->chunkCap) {
-        W_TRY(hipStreamSynchronize(st));
+        W_TRY(hipStreamSynchronize(L.st));
         if (w->counts) (void)hipFree(w->counts);
         if (w->heads) (void)hipFree(w->heads);
         w->counts = w->heads = nullptr;
@@ -2317,18 +2284,187 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         W_TRY(hipMalloc(&w->heads, (size_t)lc * kHeadWords * sizeof(uint32_t)));
         w->launchCap = lc; w->chunkCap = cc;
     }
-    wb.counts = w->counts; wb.heads = w->heads;
+    L.wb.counts = w->counts; L.wb.heads = w->heads;
 
     // the bounce-hit counts of this lane's PREVIOUS launch set, before they are cleared: read on the host behind this set's own hit-count read-back (no extra
     // synchronisation) -- what the capacity of shadow queue 2 is predicted from
     if (!w->hostHits) W_TRY(hipHostMalloc((void **)&w->hostHits, 64 * sizeof(uint32_t)));
-    const int giCopied = std::min(w->prevChunks, 60);
-    if (giCopied > 0) {
-        W_TRY(hipMemcpyAsync(w->hostHits + 1, w->counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        W_TRY(hipMemcpyAsync(w->hostHits + 2, w->counts + 64, (size_t)giCopied * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    L.giCopied = std::min(w->prevChunks, 60);
+    if (L.giCopied > 0) {
+        W_TRY(hipMemcpyAsync(w->hostHits + 1, w->counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, L.st));
+        W_TRY(hipMemcpyAsync(w->hostHits + 2, w->counts + 64, (size_t)L.giCopied * sizeof(uint32_t), hipMemcpyDeviceToHost, L.st));
     }
-    W_TRY(hipMemsetAsync(w->counts, 0, (size_t)(64 + w->chunkCap + nChunks) * sizeof(uint32_t), st));
-    W_TRY(hipMemsetAsync(w->heads, 0, (size_t)(1 + nChunks * 4) * kHeadWords * sizeof(uint32_t), st));
+    W_TRY(hipMemsetAsync(w->counts, 0, (size_t)(64 + w->chunkCap + nChunks) * sizeof(uint32_t), L.st));
+    W_TRY(hipMemsetAsync(w->heads, 0, (size_t)(1 + nChunks * 4) * kHeadWords * sizeof(uint32_t), L.st));
+    return RT_OK;
+}
+
+// step 5 -- the primary stages: candidates, their closest hits, the hit list
+static int wave_primary(LaunchSet &L, unsigned tiles) {
+    RtWave *w = L.w;
+    const WaveBuf &wb = L.wb;
+    W_STEP(wave_stage(L, ST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
+    W_STEP(wave_stage(L, ST_TRACE_PRIMARY, L.st, [&] {
+        PrimarySrc ps;
+        ps.fr = L.dFrame; ps.cand = wb.cand; ps.count = &wb.counts[0]; ps.outT = wb.primT; ps.outTri = wb.primTri;
+        TraceTune tuneP = w->tune;   // primary rays: their cost varies strongly across the screen, so shorter runs than the queue launches (128 - 256, see k_trace)
+        tuneP.chunkMax = 256;
+        if (w->opt.chunkPrimarySet) tuneP.chunk = w->opt.chunkPrimary;
+        w->builds |= launch_trace<PrimarySrc, false>(L.st, w->cus, L.gridPctPrimary, L.treeDepth, L.dFrame, L.host->sc, ps, &wb.heads[0], w->acc + 2, w->acc + 8, tuneP, L.S ? L.S + 0 : nullptr);
+    }));
+    W_STEP(wave_stage(L, ST_POST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(k_post_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
+    return RT_OK;
+}
+
+// step 6 -- More than one chunk: the number of chunks that hold hits is known only on the device.  Launching the chunk loop for the upper
+// bound (rounds 1-2) costs little time -- the kernels of an empty chunk return at once -- but fills the launch statistics with
+// empty launches (bench.py's batches of eight 1080p frames: 5 launch sets, 2 of them with rays).  Such a batch is tens of
+// milliseconds of work, so the hit count is read back once (this lane's stream only; the other lanes keep the GPU busy) and
+// the hits are dealt over equal chunks.  A single-chunk frame -- every frame-by-frame BASELINE configuration -- never syncs.
+static int wave_settle_chunks(LaunchSet &L) {
+    RtWave *w = L.w;
+    const rtl::WavePlan &plan = L.plan;
+    if (!(plan.deferred || L.nChunks > 1) || w->opt.chunksFromSlots) return RT_OK;
+    W_TRY(hipMemcpyAsync(w->hostHits, &w->counts[1], sizeof(uint32_t), hipMemcpyDeviceToHost, L.st));
+    W_TRY(hipStreamSynchronize(L.st));
+    const size_t hits = *w->hostHits;
+    if (L.giCopied > 0 && w->hostHits[1] > 0) {     // the previous launch set of this lane: what share of its (hit, sample) pairs had a bounce hit
+        unsigned long long bounced = 0;
+        for (int i = 0; i < L.giCopied; ++i) bounced += w->hostHits[2 + i];
+        double &frac = wave_share(w);
+        frac = std::max(frac, std::max(1e-9, (double)bounced / ((double)w->hostHits[1] * (double)std::max(w->prevSPP, 1))));
+    }
+    const rtl::ChunkSplit split = plan.split(hits);
+    L.nChunks = split.nChunks;
+    L.CH = split.ch;
+    // a set of several chunks keeps its arena for the whole chunk loop -- shared by two lanes that would serialise the lanes (4 spp -> 16 spp, 4K and
+    // the 1 M-triangle scene lost 3 % that way) -- so it takes the lane's OWN arena; one-chunk sets (every frame-by-frame configuration, bench.py's
+    // batches) share lane % n
+    if (plan.deferred) w->arena = L.nChunks > 1 ? w->lane : w->lane % w->pool->n;   // (not deferred: chosen and allocated before k_primary)
+    if (plan.deferred && L.nChunks > 0) W_STEP(wave_grow_arenas(L, L.CH, split.room, true));
+    if (L.nChunks > 0) wave_point_chunk_arrays(L, L.CH, plan.deferred);
+    return RT_OK;
+}
+
+// step 7a -- shade the hits of chunk c: the light and AO rays into shadow queue 1, the bounce rays into theirs; with RT_PACKET_AO the AO rays are traced here,
+// one packet per hit (k_trace_packets), and the any-hit launch then starts behind the A AO slots of queue 1.  -> queue 1 as the any-hit launch reads it.
+static int wave_chunk_direct(LaunchSet &L, int c, uint32_t c0, QueueSrc &q1) {
+    RtWave *w = L.w;
+    const WaveBuf &wb = L.wb;
+    const int A = L.plan.ao;
+    const unsigned gridHS = (unsigned)((L.CH * (size_t)L.plan.spp + 255) / 256);
+    W_STEP(wave_stage(L, ST_GEN_DIRECT, L.ss, [&] { hipLaunchKernelGGL(k_gen_direct, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr); }));
+    const bool pkAO = w->opt.packetAO && A > 0;
+    if (pkAO) W_STEP(wave_stage(L, ST_TRACE_AO, L.st, [&] {
+        PacketSrc pk;
+        pk.o = nullptr; pk.d = wb.shD; pk.tm = nullptr; pk.org = wb.aoOrg; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = A; pk.nLive = 0;
+        w->builds |= launch_packets(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, L.host->sc, pk, wave_cursor(wb, c, 3), w->acc + 7, w->acc + 14, w->tune);
+    }));
+    const size_t skip = pkAO ? (size_t)A * L.CH : 0;
+    q1.o = wb.shO; q1.d = wb.shD + skip; q1.tm = wb.shT; q1.org = wb.aoOrg; q1.orgStride = 0; q1.liveCount = &wb.counts[1]; q1.c0 = c0; q1.cap = wb.CH; q1.stride = wb.CH;
+    q1.slots = (uint32_t)(L.plan.S1 - (pkAO ? A : 0));
+    q1.denseSlots = pkAO ? 0u : (uint32_t)A;
+    q1.outT = nullptr; q1.outTri = nullptr; q1.outOcc = wb.occ1 + skip;
+    return RT_OK;
+}
+
+// step 7b -- the bounce rays of chunk c: traced (any-hit first behind a probe), then shaded where they hit -- six shadow rays per bounce hit into queue 2
+static int wave_chunk_bounce(LaunchSet &L, int c, uint32_t c0) {
+    RtWave *w = L.w;
+    const WaveBuf &wb = L.wb;
+    const int SPP = L.plan.spp;
+    const DevScene &sc = L.host->sc;
+    const unsigned gridHS = (unsigned)((L.CH * (size_t)SPP + 255) / 256);
+    uint32_t *const listCount = &wb.counts[64 + w->chunkCap + c];
+    QueueSrc qg;
+    qg.o = nullptr; qg.d = wb.giD; qg.tm = nullptr; qg.org = wb.giOrg; qg.orgStride = wb.giPerm ? wb.CH : 0u; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
+    qg.outT = wb.giT; qg.outTri = wb.giTri; qg.outOcc = nullptr;
+    W_STEP(wave_stage(L, ST_TRACE_GI, L.st, [&] {
+        if (L.probe) {
+            // any-hit walk of every bounce ray (misses answered in place, hits listed), then the closest-hit walk of the listed ones
+            BounceProbeSrc pb;
+            pb.q = qg; pb.hitters = wb.giHit; pb.hitCount = listCount; pb.inf = L.host->u.inf;
+            w->builds |= launch_trace<BounceProbeSrc, true>(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, sc, pb, wave_cursor(wb, c, 1), w->probeAcc + 0, w->acc + 10, w->tune, L.S ? L.S + 32 : nullptr)
+                         | ((uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT);
+            IndexedDenseSrc rq;
+            rq.idx = wb.giHit; rq.count = pb.hitCount; rq.org = wb.giOrg; rq.d = wb.giD; rq.stride = wb.CH; rq.orgStride = qg.orgStride; rq.outT = wb.giT; rq.outTri = wb.giTri; rq.n = 0;
+            w->builds |= launch_trace<IndexedDenseSrc, false>(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, sc, rq, wave_cursor(wb, c, 2), w->probeAcc + 1, w->acc + 10, w->tune, nullptr, L.retraceBlocks);
+            w->probeLaunches++;
+        } else {
+            w->builds |= launch_trace<QueueSrc, false>(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, sc, qg, wave_cursor(wb, c, 1), w->acc + 4, w->acc + 10, w->tune, L.S ? L.S + 32 : nullptr);
+            w->closestLaunches++;
+        }
+    }));
+    return wave_stage(L, ST_GEN_GI, L.ss, [&] {
+        // behind a probe the generator walks the probe's hit list (k_gen_gi_listed); RT_BIN_GI's permuted queue and sets without a probe visit every pair
+        const bool listed = L.probe && !wb.giPerm;
+        const uint32_t *hitList = listed ? wb.giHit : nullptr, *hitCount = listed ? listCount : nullptr;
+        unsigned long long *listStat = w->giListOn ? w->giListAcc : nullptr;
+        if (listed) {
+            hipLaunchKernelGGL(k_gen_gi_listed, dim3(L.listedBlocks), dim3(256), 0, L.ss, L.dFrame, wb, c0, hitList, hitCount, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+            w->listedLaunches++;
+        } else {
+            hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+            w->pairLaunches++;
+        }
+        if (wb.q2Stride < wb.CH * (uint32_t)SPP)   // a predicted capacity: the pairs beyond it (normally none) trace their rays in place
+            hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(L.treeDepth, 4) * 8, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], std::max(L.treeDepth, 4), hitList, hitCount);
+    });
+}
+
+// step 7 -- one chunk: generate, bounce, shadows, combine
+static int wave_chunk(LaunchSet &L, int c) {
+    RtWave *w = L.w;
+    const WaveBuf &wb = L.wb;
+    const DevScene &sc = L.host->sc;
+    const uint32_t c0 = (uint32_t)((size_t)c * L.CH);
+    QueueSrc q1;
+    W_STEP(wave_chunk_direct(L, c, c0, q1));
+    if (L.host->u.enableGI == 1) {
+        // bounce rays first, then ONE any-hit launch over both shadow queues
+        W_STEP(wave_chunk_bounce(L, c, c0));
+        DualQueueSrc qq;
+        qq.a = q1;
+        qq.b.o = wb.sh2O; qq.b.d = wb.sh2D; qq.b.tm = wb.sh2T; qq.b.liveCount = &wb.counts[64 + c]; qq.b.c0 = 0; qq.b.cap = wb.q2Stride;
+        qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.denseSlots = 0u; qq.b.org = nullptr; qq.b.orgStride = 0;
+        qq.b.outT = nullptr; qq.b.outTri = nullptr; qq.b.outOcc = wb.occ2;
+        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] {
+            w->builds |= launch_trace<DualQueueSrc, true>(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, sc, qq, wave_cursor(wb, c, 0), w->acc + 3, w->acc + 9, w->tune, L.S ? L.S + 16 : nullptr);
+        }));
+    } else {
+        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] {
+            w->builds |= launch_trace<QueueSrc, true>(L.st, w->cus, L.gridPct, L.treeDepth, L.dFrame, sc, q1, wave_cursor(wb, c, 0), w->acc + 3, w->acc + 9, w->tune, L.S ? L.S + 16 : nullptr);
+        }));
+    }
+    // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
+    if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
+    const unsigned gridH = (unsigned)((L.CH + 255) / 256);
+    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(k_combine, dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
+}
+
+// The steps of a launch set: lane bookkeeping, plan, arenas, cursor table, primary stages, chunks settled, chunk by chunk, tally and resolve.
+int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dFrame, const DevFrame &host, Targets tg,
+                   unsigned long long *, bool count, int treeDepth, hipEvent_t evPrevDone, bool cacheResident) {
+    if (count) { w->err = "work counters are produced by the megakernel pipeline (RT_PIPELINE_MEGAKERNEL)"; return RT_ERR_UNSUPPORTED; }
+    const RtUniforms &u = host.u;
+    const int batch = std::max(host.g.batch, 1);
+    const size_t nSlots = (size_t)std::max(host.g.nLocalTiles, 1) * 256 * (size_t)batch;   // pixel slots of all frames of the batch
+    LaunchSet L{};
+    L.w = w; L.ctx = ctx; L.st = st; L.ss = w->shadeStream ? w->shadeStream : st; L.dFrame = dFrame; L.host = &host; L.tg = tg; L.treeDepth = treeDepth;
+    const rtl::WavePlan &plan = L.plan = rtl::wave_plan(nSlots, u.spp, u.enableAO == 1 ? u.aoSamples : 0, w->opt);
+    const int SPP = plan.spp;
+    W_STEP(wave_begin(L));
+    if (plan.tooLarge) { w->err = rtl::kTooLargeMessage; return RT_ERR_UNSUPPORTED; }
+    L.CH = plan.chBudget;
+    L.nChunks = plan.chunks_upper_bound();   // upper bound (every pixel slot a hit); cut down to the hit count by wave_settle_chunks
+    wave_point_frame_arrays(L);
+    if (!plan.deferred) {   // (deferred: the chunk arrays stay null until they are carved behind k_post_primary)
+        w->arena = L.nChunks > 1 ? w->lane : w->lane % w->pool->n;
+        W_STEP(wave_grow_arenas(L, L.CH, L.CH, false));
+        wave_point_chunk_arrays(L, L.CH, false);
+    }
+    L.wb.CH = (uint32_t)L.CH; L.wb.A = plan.ao; L.wb.SPP = SPP;
+    W_STEP(wave_cursor_table(L));
     // Persistent grids smaller than what fits, for the two queue launches of a cache-resident scene: they run near the vector L1's access
     // rate (0.81 accesses per clock and CU, PMC), which four and a half workgroups per CU sustain as well as six, and the
     // registers left free let the shading kernels of the other frame lanes run beside them instead of waiting for a persistent grid to
@@ -2336,181 +2472,31 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
     // eight frames: 1.83 -> 1.76 ms per frame.  Not for the primary launch (latency-bound: 0.24 -> 0.27 ms at 75 %) and not for a
     // scene that misses L2 (1 M triangles: any-hit launch 15.2 -> 16.1 ms at 75 % -- it needs every wave to cover the fabric's latency).
     // A tile-parallel rank traces 1/n of the rays and overlaps four batches: half-size grids (one rank of 8: 0.47 -> 0.43 ms/frame).
-    int gridPct = host.g.world > 1 ? 50 : (cacheResident ? 75 : 100);
-    if (const char *e = getenv("RT_GRID_PCT")) gridPct = std::max(1, atoi(e));
-    int gridPctPrimary = host.g.world > 1 ? gridPct : 100;
-    if (const char *e = getenv("RT_GRID_PCT_PRIMARY")) gridPctPrimary = std::max(1, atoi(e));
-    if ((getenv("RT_TRACE_STATS") || getenv("RT_TRACE_TIMING")) && !w->stats) { W_TRY(hipMalloc(&w->stats, 64 * sizeof(unsigned long long))); W_TRY(hipMemset(w->stats, 0, 64 * sizeof(unsigned long long))); }
-    unsigned long long *S = w->stats;
-    const TraceTune tune = w->tune;
+    L.gridPct = w->opt.gridPct ? w->opt.gridPct : (host.g.world > 1 ? 50 : (cacheResident ? 75 : 100));
+    L.gridPctPrimary = w->opt.gridPctPrimary ? w->opt.gridPctPrimary : (host.g.world > 1 ? L.gridPct : 100);
+    if ((w->opt.traceStatsSet || w->opt.traceTimingSet) && !w->stats) { W_TRY(hipMalloc(&w->stats, 64 * sizeof(unsigned long long))); W_TRY(hipMemset(w->stats, 0, 64 * sizeof(unsigned long long))); }
+    L.S = w->stats;
     const unsigned tilesFrame = (unsigned)std::max(host.g.nLocalTiles, 0);
     const unsigned tiles = tilesFrame * (unsigned)batch;
     if (tiles == 0) return RT_OK;
-    // EXPERIMENT (RT_CU_SPLIT=k): the shading kernels run on a second stream restricted to k eighths of the CUs, the traversal
-    // launches -- the lane's own stream, created with the complementary mask in rt_api.hip -- on the rest.  ss == st when the experiment is off.
-    hipStream_t ss = w->shadeStream ? w->shadeStream : st;
-    auto hop = [&](hipStream_t from, hipStream_t to) -> hipError_t {
-        if (from == to) return hipSuccess;
-        hipError_t e = hipEventRecord(w->hopEv, from);
-        return e != hipSuccess ? e : hipStreamWaitEvent(to, w->hopEv, 0);
-    };
-    W_TRY(hop(st, ss));
-
-    rt_stage_begin(ctx, ST_PRIMARY, ss);
-    hipLaunchKernelGGL(k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, ss, dFrame, tg, wb);
-    rt_stage_end(ctx, ST_PRIMARY, 1, ss);
-    W_TRY(hop(ss, st));
-
-    rt_stage_begin(ctx, ST_TRACE_PRIMARY, st);
-    PrimarySrc ps;
-    ps.fr = dFrame; ps.cand = wb.cand; ps.count = &wb.counts[0]; ps.outT = wb.primT; ps.outTri = wb.primTri;
-    TraceTune tuneP = tune;   // primary rays: their cost varies strongly across the screen, so shorter runs than the queue launches (128 - 256, see k_trace)
-    tuneP.chunkMax = 256;
-    if (const char *e = getenv("RT_CHUNK_PRIMARY")) tuneP.chunk = atoi(e);
-    w->builds |= launch_trace<PrimarySrc, false>(st, w->cus, gridPctPrimary, treeDepth, dFrame, host.sc, ps, &wb.heads[0], w->acc + 2, w->acc + 8, tuneP, S ? S + 0 : nullptr);
-    rt_stage_end(ctx, ST_TRACE_PRIMARY, 1, st);
-
-    W_TRY(hop(st, ss));
-    rt_stage_begin(ctx, ST_POST_PRIMARY, ss);
-    hipLaunchKernelGGL(k_post_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, ss, dFrame, tg, wb);
-    rt_stage_end(ctx, ST_POST_PRIMARY, 1, ss);
-    W_TRY(hop(ss, st));
-
-    // More than one chunk: the number of chunks that hold hits is known only on the device.  Launching the chunk loop for the upper
-    // bound (rounds 1-2) costs little time -- the kernels of an empty chunk return at once -- but fills the launch statistics with
-    // empty launches (bench.py's batches of eight 1080p frames: 5 launch sets, 2 of them with rays).  Such a batch is tens of
-    // milliseconds of work, so the hit count is read back once (this lane's stream only; the other lanes keep the GPU busy) and
-    // the hits are dealt over equal chunks.  A single-chunk frame -- every frame-by-frame BASELINE configuration -- never syncs.
-    if ((deferred || nChunks > 1) && !w->chunksFromSlots) {
-        W_TRY(hipMemcpyAsync(w->hostHits, &w->counts[1], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        W_TRY(hipStreamSynchronize(st));
-        const size_t hits = *w->hostHits;
-        if (giCopied > 0 && w->hostHits[1] > 0) {     // the previous launch set of this lane: what share of its (hit, sample) pairs had a bounce hit
-            unsigned long long bounced = 0;
-            for (int i = 0; i < giCopied; ++i) bounced += w->hostHits[2 + i];
-            double &frac = w->pool ? w->pool->q2Frac : w->q2FracOwn;
-            frac = std::max(frac, std::max(1e-9, (double)bounced / ((double)w->hostHits[1] * (double)std::max(w->prevSPP, 1))));
-        }
-        nChunks = (int)((hits + CHbudget - 1) / CHbudget);
-        if (nChunks > 0) CH = align_up((hits + (size_t)nChunks - 1) / (size_t)nChunks, 256);
-        // a set of several chunks keeps its arena for the whole chunk loop -- shared by two lanes that would serialise the lanes (4 spp -> 16 spp, 4K and
-        // the 1 M-triangle scene lost 3 % that way) -- so it takes the lane's OWN arena; one-chunk sets (every frame-by-frame configuration, bench.py's
-        // batches) share lane % n
-        if (w->pool && deferred) w->arena = nChunks > 1 ? w->lane : w->lane % w->pool->n;   // (not deferred: chosen and allocated before k_primary)
-        predictQ2 = deferred;
-        if (deferred && nChunks > 0) {
-            // the arenas hold this launch set's hits (+ 6 % when they have to grow); a set of several chunks gets the whole budget at once: its chunk size
-            // changes with the number of frames in the batch (20 M hits = 3 x 6.7 M, 17 M = 2 x 8.6 M), and growing a 16 GB arena in the middle of a run
-            // is a device-wide synchronisation plus a large allocation (the 1 M-triangle scene at --steps 20: 47.6 instead of 18.7 ms per frame)
-            int rc = ensure(CH, nChunks > 1 ? CHbudget : std::min(CHbudget, align_up(CH + CH / 16, 256)));
-            if (rc != RT_OK) return rc;
-        }
-        if (nChunks > 0) carve(CH);
-    }
-    // RT_BOUNCE_PROBE (auto): the bounce rays are walked any-hit first while the share of them that hit, in earlier launch sets, is below kProbeShareMax.  The
-    // any-hit walk proves a miss at 0.72 of the closest-hit walk's cost on the bench view (profiles/r06_bounce_probe.txt); a hit pays both walks, so the probe
-    // pays while share < 1 - 0.72, less the second launch -- kProbeShareMax keeps a margin.  Nothing known (share 0): the closest-hit launch alone.  Both
-    // paths are exact, so a wrong guess costs time, never bits.
-    constexpr double kProbeShareMax = 0.15;
-    const bool probe = u.enableGI == 1 && w->probeTree && (w->probeMode == 1 || (w->probeMode < 0 && q2Share > 0.0 && q2Share < kProbeShareMax));
+    W_STEP(wave_primary(L, tiles));
+    W_STEP(wave_settle_chunks(L));
+    const double share = wave_share(w);
+    L.probe = u.enableGI == 1 && w->probeTree && rtl::wave_probe_on(w->opt, share);
     // the re-trace launch: a grid for about twice the expected hits (a persistent grid for ~1 % of the rays would mostly ramp up and drain)
-    const unsigned retraceBlocks = q2Share > 0.0 ? (unsigned)std::max(32.0, std::min(1e6, 2.0 * q2Share * (double)CH * SPP / 2048.0)) : 0u;
+    L.retraceBlocks = share > 0.0 ? (unsigned)std::max(32.0, std::min(1e6, 2.0 * share * (double)L.CH * SPP / 2048.0)) : 0u;
     // k_gen_gi_listed: one thread per listed hit for about twice the expected hits, between 32 workgroups and eight per CU; the grid strides over whatever the list holds
-    const unsigned listedBlocks = (unsigned)std::max(32.0, std::min((double)w->cus * 8.0, q2Share > 0.0 ? 2.0 * q2Share * (double)CH * SPP / 256.0 : (double)w->cus * 4.0));
+    L.listedBlocks = (unsigned)std::max(32.0, std::min((double)w->cus * 8.0, share > 0.0 ? 2.0 * share * (double)L.CH * SPP / 256.0 : (double)w->cus * 4.0));
     // shared arena: everything from here to the last combine reads or writes it
-    if (w->pool && nChunks > 0 && w->pool->lastUser[w->arena] && w->pool->lastUser[w->arena] != st) W_TRY(hipStreamWaitEvent(st, w->pool->freeEv[w->arena], 0));
-    for (int c = 0; c < nChunks; ++c) {
-        const uint32_t c0 = (uint32_t)((size_t)c * CH);
-        const unsigned gridHS = (unsigned)((CH * (size_t)SPP + 255) / 256), gridH = (unsigned)((CH + 255) / 256);
-        W_TRY(hop(st, ss));
-        rt_stage_begin(ctx, ST_GEN_DIRECT, ss);
-        hipLaunchKernelGGL(k_gen_direct, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr);
-        rt_stage_end(ctx, ST_GEN_DIRECT, 1, ss);
-        W_TRY(hop(ss, st));
-
-        // AO rays: one packet per hit (k_trace_packets); the any-hit launch below then starts behind the A AO slots of queue 1
-        const bool pkAO = w->packetAO && A > 0;
-        if (pkAO) {
-            PacketSrc pk;
-            pk.o = nullptr; pk.d = wb.shD; pk.tm = nullptr; pk.org = wb.aoOrg; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = A; pk.nLive = 0;
-            rt_stage_begin(ctx, ST_TRACE_AO, st);
-            w->builds |= launch_packets(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pk, &wb.heads[(size_t)(1 + c * 4 + 3) * kHeadWords], w->acc + 7, w->acc + 14, tune);
-            rt_stage_end(ctx, ST_TRACE_AO, 1, st);
-        }
-        const size_t skip = pkAO ? (size_t)A * CH : 0;
-        QueueSrc q1;
-        q1.o = wb.shO; q1.d = wb.shD + skip; q1.tm = wb.shT; q1.org = wb.aoOrg; q1.orgStride = 0; q1.liveCount = &wb.counts[1]; q1.c0 = c0; q1.cap = wb.CH; q1.stride = wb.CH;
-        q1.slots = (uint32_t)(S1 - (pkAO ? A : 0));
-        q1.denseSlots = pkAO ? 0u : (uint32_t)A;
-        q1.outT = nullptr; q1.outTri = nullptr; q1.outOcc = wb.occ1 + skip;
-        if (u.enableGI == 1) {
-            // bounce rays first, then ONE any-hit launch over both shadow queues
-            QueueSrc qg;
-            qg.o = nullptr; qg.d = wb.giD; qg.tm = nullptr; qg.org = wb.giOrg; qg.orgStride = wb.giPerm ? wb.CH : 0u; qg.liveCount = &wb.counts[1]; qg.c0 = c0; qg.cap = wb.CH; qg.stride = wb.CH; qg.slots = (uint32_t)SPP; qg.denseSlots = (uint32_t)SPP;
-            qg.outT = wb.giT; qg.outTri = wb.giTri; qg.outOcc = nullptr;
-            rt_stage_begin(ctx, ST_TRACE_GI, st);
-            if (probe) {
-                // any-hit walk of every bounce ray (misses answered in place, hits listed), then the closest-hit walk of the listed ones
-                BounceProbeSrc pb;
-                pb.q = qg; pb.hitters = wb.giHit; pb.hitCount = &wb.counts[64 + w->chunkCap + c]; pb.inf = u.inf;
-                w->builds |= launch_trace<BounceProbeSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, pb, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->probeAcc + 0, w->acc + 10, tune, S ? S + 32 : nullptr)
-                             | ((uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT);
-                IndexedDenseSrc rq;
-                rq.idx = wb.giHit; rq.count = pb.hitCount; rq.org = wb.giOrg; rq.d = wb.giD; rq.stride = wb.CH; rq.orgStride = qg.orgStride; rq.outT = wb.giT; rq.outTri = wb.giTri; rq.n = 0;
-                w->builds |= launch_trace<IndexedDenseSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, rq, &wb.heads[(size_t)(1 + c * 4 + 2) * kHeadWords], w->probeAcc + 1, w->acc + 10, tune, nullptr, retraceBlocks);
-                w->probeLaunches++;
-            } else {
-                w->builds |= launch_trace<QueueSrc, false>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qg, &wb.heads[(size_t)(1 + c * 4 + 1) * kHeadWords], w->acc + 4, w->acc + 10, tune, S ? S + 32 : nullptr);
-                w->closestLaunches++;
-            }
-            rt_stage_end(ctx, ST_TRACE_GI, 1, st);
-
-            W_TRY(hop(st, ss));
-            rt_stage_begin(ctx, ST_GEN_GI, ss);
-            // behind a probe the generator walks the probe's hit list (k_gen_gi_listed); RT_BIN_GI's permuted queue and sets without a probe visit every pair
-            const bool listed = probe && !wb.giPerm;
-            const uint32_t *hitList = listed ? wb.giHit : nullptr, *hitCount = listed ? &wb.counts[64 + w->chunkCap + c] : nullptr;
-            unsigned long long *listStat = w->giListOn ? w->giListAcc : nullptr;
-            if (listed) {
-                hipLaunchKernelGGL(k_gen_gi_listed, dim3(listedBlocks), dim3(256), 0, ss, dFrame, wb, c0, hitList, hitCount, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
-                w->listedLaunches++;
-            } else {
-                hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, ss, dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
-                w->pairLaunches++;
-            }
-            if (wb.q2Stride < wb.CH * (uint32_t)SPP)   // a predicted capacity: the pairs beyond it (normally none) trace their rays in place
-                hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(treeDepth, 4) * 8, ss, dFrame, wb, c0, &wb.counts[64 + c], std::max(treeDepth, 4), hitList, hitCount);
-            rt_stage_end(ctx, ST_GEN_GI, 1, ss);
-            W_TRY(hop(ss, st));
-
-            DualQueueSrc qq;
-            qq.a = q1;
-            qq.b.o = wb.sh2O; qq.b.d = wb.sh2D; qq.b.tm = wb.sh2T; qq.b.liveCount = &wb.counts[64 + c]; qq.b.c0 = 0; qq.b.cap = wb.q2Stride;
-            qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.denseSlots = 0u; qq.b.org = nullptr; qq.b.orgStride = 0;
-            qq.b.outT = nullptr; qq.b.outTri = nullptr; qq.b.outOcc = wb.occ2;
-            rt_stage_begin(ctx, ST_TRACE_SHADOW, st);
-            w->builds |= launch_trace<DualQueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, qq, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
-            rt_stage_end(ctx, ST_TRACE_SHADOW, 1, st);
-        } else {
-            rt_stage_begin(ctx, ST_TRACE_SHADOW, st);
-            w->builds |= launch_trace<QueueSrc, true>(st, w->cus, gridPct, treeDepth, dFrame, host.sc, q1, &wb.heads[(size_t)(1 + c * 4 + 0) * kHeadWords], w->acc + 3, w->acc + 9, tune, S ? S + 16 : nullptr);
-            rt_stage_end(ctx, ST_TRACE_SHADOW, 1, st);
-        }
-        // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
-        if (w->pool && c == nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], st)); w->pool->lastUser[w->arena] = st; }
-        W_TRY(hop(st, ss));
-        rt_stage_begin(ctx, ST_COMBINE, ss);
-        hipLaunchKernelGGL(k_combine, dim3(gridH), dim3(256), 0, ss, dFrame, tg, wb, c0);
-        rt_stage_end(ctx, ST_COMBINE, 1, ss);
-        W_TRY(hop(ss, st));
-    }
-    w->prevChunks = (u.enableGI == 1) ? nChunks : 0;
+    if (L.nChunks > 0 && w->pool->lastUser[w->arena] && w->pool->lastUser[w->arena] != st) W_TRY(hipStreamWaitEvent(st, w->pool->freeEv[w->arena], 0));
+    for (int c = 0; c < L.nChunks; ++c) W_STEP(wave_chunk(L, c));
+    // step 8 -- tally, and the temporal resolve: the one stage that needs the previous frame's COLOR0 (and must not overtake its target stores)
+    w->prevChunks = (u.enableGI == 1) ? L.nChunks : 0;
     w->prevSPP = SPP;
     hipLaunchKernelGGL(k_accum_tally, dim3(1), dim3(64), 0, st, w->counts, w->acc, batch);
-    // temporal resolve: the one stage that needs the previous frame's COLOR0 (and must not overtake its target stores)
     if (evPrevDone) W_TRY(hipStreamWaitEvent(st, evPrevDone, 0));
     rt_stage_begin(ctx, ST_RESOLVE, st);
-    hipLaunchKernelGGL(k_resolve, dim3(tilesFrame), dim3(256), 0, st, dFrame, tg, wb);
+    hipLaunchKernelGGL(k_resolve, dim3(tilesFrame), dim3(256), 0, st, dFrame, tg, L.wb);
     rt_stage_end(ctx, ST_RESOLVE, 1, st);
     W_TRY(hipGetLastError());
     return RT_OK;
@@ -2599,7 +2585,7 @@ int rt_wave_traced(RtWave *w, hipStream_t st, unsigned long long *out8, bool res
         unsigned long long v[64];
         W_TRY(hipMemcpy(v, w->stats, sizeof v, hipMemcpyDeviceToHost));
         static const char *nm[4] = {"primary", "shadow", "bounce", "bounce_shadow"};
-        if (getenv("RT_TRACE_TIMING") && atoi(getenv("RT_TRACE_TIMING"))) {
+        if (w->opt.traceTimingSet && w->opt.traceTiming) {
             // RT_TRACE_TIMING=1 (k_trace<.., TIMING>): sums over all waves of the launches since the last reset
             for (int k = 0; k < 3; ++k) {
                 const unsigned long long *q = v + k * 16;
@@ -2615,8 +2601,7 @@ int rt_wave_traced(RtWave *w, hipStream_t st, unsigned long long *out8, bool res
             if (reset) W_TRY(hipMemset(w->acc, 0, 16 * sizeof(unsigned long long)));
             return RT_OK;
         }
-        const char *mode = getenv("RT_TRACE_STATS");
-        const bool quiet = mode && atoi(mode) >= 2;   // RT_TRACE_STATS=2: collect (rt_get_traced_rays' mergedLoads*), do not print
+        const bool quiet = w->opt.traceStatsSet && w->opt.traceStats >= 2;   // RT_TRACE_STATS=2: collect (rt_get_traced_rays' mergedLoads*), do not print
         for (int k = 0; k < 4; ++k) {
             const unsigned long long *q = v + k * 16;
             double rays = (double)std::max<unsigned long long>(out8[2 + k], 1);
@@ -2671,7 +2656,7 @@ int rt_wave_gi_list(RtWave *w, hipStream_t st, unsigned long long *out4, bool re
 
 void rt_wave_forget_share(RtWave *w) {
     if (!w) return;
-    if (w->pool) w->pool->q2Frac = 0.0; else w->q2FracOwn = 0.0;
+    w->pool->q2Frac = 0.0;
     w->prevChunks = 0;   // the bounce counts of the launch set in flight belong to the old scene / frame size: not read
 }
 

@@ -18,7 +18,7 @@ int rt_arena_pool_count(const RtArenaPool *p);
 size_t rt_wave_frame_bytes(const RtWave *w);   // per-lane frame arrays (candidates, hits, pre-resolve stash)
 size_t rt_hybrid_arena_bytes(const RtHybrid *h);
 
-RtWave *rt_wave_create(int computeUnits, RtArenaPool *pool = nullptr, int lane = 0);
+RtWave *rt_wave_create(int computeUnits, RtArenaPool *pool, int lane);   // pool: the context's ray arenas; the lane reads its options (rtl::wave_options_from_env) here, once
 void rt_wave_destroy(RtWave *w);
 const char *rt_wave_error(const RtWave *w);
 // Renders one frame of a BVH scene into `tg` on `stream`.  `host` is the host copy of *dFrame.  Only the final temporal

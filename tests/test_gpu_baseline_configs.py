@@ -260,7 +260,7 @@ def test_1080p_batches_of_eight_equal_frame_by_frame_and_the_oracle(orc, monkeyp
     for the worst case instead of from the bounce hits of earlier batches (only launch sets this large predict)."""
     monkeypatch.delenv("RT_Q2_PREDICT", raising=False)
     if budget_mb == "q2_predict_0":
-        monkeypatch.setenv("RT_Q2_PREDICT", "0")                     # read per launch set
+        monkeypatch.setenv("RT_Q2_PREDICT", "0")                     # read when the renderer is created, like every option of frame rendering
         budget_mb = None
     if budget_mb:
         monkeypatch.setenv("RT_QUEUE_BUDGET_MB", str(budget_mb))     # read when the renderer is created

@@ -657,7 +657,40 @@ int rt_mesh_quality(RtContext *ctx, int which, int wait, RtMeshQuality *out);
 enum { RT_MESH_UPDATE_SINGLE = 0, RT_MESH_UPDATE_PARTS = 1 };
 enum { RT_MESH_DID_REFIT = 0, RT_MESH_DID_REBUILD = 1 };
 int rt_mesh_update(RtContext *ctx, int mode, const float *M16, float rebuildAbove, int *action);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- skinning: the positions of the dynamic mesh rewritten on the device from rest positions and a table of bone matrices, so that
+ * a host that links only this library animates an articulated model without a kernel of its own and without a host round trip per step.
+ * Linear-blend skinning with RT_SKIN_INFLUENCES influences per vertex: boneIdx4 / weights4 hold nVerts x 4 bone indices / weights, and
+ *   position[v] = sum over k of weights4[4v+k] * (table[boneIdx4[4v+k]] * rest[v]),
+ * evaluated exactly as rt_skin_positions (host side, below) defines it, bit for bit.  Weights need not sum to one and may be negative; an influence of
+ * weight +-0 is skipped, and a vertex all of whose influences are skipped keeps its rest position.  1 <= nBones <= RT_MAX_MESH_BONES.
+ * Skinning writes rt_mesh_positions() and nothing else: follow it with rt_mesh_refit / rt_mesh_rebuild / rt_mesh_update (or their _parts forms, which
+ * apply the part matrices on top), and bound raster draws read the skinned positions where they lie.  Normals are derived from the geometry, as
+ * everywhere in the library. */
+#define RT_SKIN_INFLUENCES 4
+#define RT_MAX_MESH_BONES 65536
+/* The skin of the current mesh: rest positions (nVerts x 3 floats; NULL: a device-to-device snapshot of rt_mesh_positions() as it stands on
+ * rt_stream()'s stream), bone indices and weights (nVerts x 4 each, nVerts of the current mesh), validated as rt_skin_positions validates them: an
+ * index >= nBones (whatever its weight), a non-finite weight, a null table or nBones outside 1 .. RT_MAX_MESH_BONES is RT_ERR_INVALID, with a message.
+ * Allocates the rest array, the two tables and the bone table (nBones x 16 floats, 64-byte aligned entries, every matrix the identity) and uploads
+ * them; RtMeshInfo.allocations counts them.  May synchronise and allocate; the only call of this group that may.  nBones == 0 releases the skin (the
+ * arrays may then be NULL).  A second upload replaces the first.  RT_ERR_INVALID without a mesh; rt_mesh_upload, rt_mesh_upload_parts and
+ * rt_upload_bvh release the skin with the mesh.  No tree is needed: skinning before the first rebuild is legal. */
+int rt_mesh_skin_upload(RtContext *ctx, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones);
+/* The bone table: nBones x 16 float32 on the device, column-major, for a caller that writes matrices on the device; writes must be ordered on
+ * rt_stream()'s stream, exactly as for rt_mesh_part_matrices.  rt_mesh_set_bones: `count` matrices from host memory into entries first .., copied on
+ * that stream, ordered after the work already enqueued on every frame lane and before whatever a lane is given next; a range outside the table:
+ * RT_ERR_INVALID.  Bone matrices are not inspected, as the part matrices are not.  RT_ERR_INVALID without a skin. */
+int rt_mesh_bones(RtContext *ctx, void **devPtr, size_t *bytes);
+int rt_mesh_set_bones(RtContext *ctx, int first, int count, const float *M16s);
+/* The device array of rest positions (nVerts x 3 floats): a caller applies morph targets by writing it, ordered on rt_stream()'s stream, before a
+ * skin.  RT_ERR_INVALID without a skin. */
+int rt_mesh_rest_positions(RtContext *ctx, void **devPtr, size_t *bytes);
+/* Enqueues positions := skin(rest, tables, bone table) on rt_stream()'s stream, reading the bone table as it stands when the kernel runs.  Ordered as
+ * the update calls are: after the frames, queries and bound raster draws already enqueued on any lane, before whatever is enqueued next, by events --
+ * so rt_mesh_set_bones, rt_mesh_skin, the update calls, frames and queries take effect in call order wherever frames have moved rt_stream().  No
+ * allocation, no host wait (RtMeshInfo.hostSyncs does not move).  RT_ERR_INVALID without a mesh or without a skin. */
+int rt_mesh_skin(RtContext *ctx);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload and rt_mesh_skin_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -759,6 +792,15 @@ int rt_gather_triangles_checked(const float *positions, int nVerts, const uint32
  * causes, nIdx % 3 != 0, a null or broken partFirst or nParts outside 1 .. RT_MAX_MESH_PARTS.  Returns the triangle count. */
 int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts, const float *M16s,
                               float *outTris9);
+
+/* Linear-blend skinning on host arrays, and the definition rt_mesh_skin is tested against (see rt_mesh_skin_upload for the arrays; bones16 holds
+ * nBones column-major matrices).  For vertex v with rest position p = (x, y, z) the influences k = 0 .. 3 are visited in order: one whose weight is
+ * +0 or -0 is skipped; otherwise q = B * p with B = bones16 + 16 * boneIdx4[4v+k] in rt_gather_triangles' expression, per component c
+ * (B[c]*x + B[4+c]*y) + (B[8+c]*z + B[12+c]*1), and term = w * q; the first term initialises the sum, later ones are added in order.  A vertex with no
+ * unskipped influence keeps its rest position bit for bit.  fp32 throughout, nothing fused: one influence of weight 1 is exactly the gather's
+ * transform of the point.  out (nVerts x 3 floats) may be rest.  RT_ERR_INVALID: a null array, nVerts <= 0, nBones outside 1 .. RT_MAX_MESH_BONES, any
+ * of the four indices of a vertex >= nBones whatever its weight, a non-finite weight.  Bone matrices are not inspected. */
+int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, const float *weights4, const float *bones16, int nBones, float *out);
 
 /* build_bvh (include/scene/bvh.h:102, src/scene/bvh.cpp:94-137) + the packing half of upload_bvh_tbo
  * (:147-204).  nodes12 needs room for 2*nTris*12 floats, tris12 for nTris*12.  Returns the node count. */

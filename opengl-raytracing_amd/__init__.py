@@ -216,6 +216,7 @@ class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
 
 RT_MAX_RASTER_MESHES = 8
 RT_MAX_MESH_PARTS = 65535   # rt_mesh_upload_parts
+RT_SKIN_INFLUENCES, RT_MAX_MESH_BONES = 4, 65536   # rt_mesh_skin_upload
 RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
 RT_RASTER_BIND_SINGLE, RT_RASTER_BIND_PARTS = 0, 1   # rt_raster_mesh_dynamic
 
@@ -342,6 +343,11 @@ SIGNATURES = {
     "rt_mesh_measure": (C.c_int, [C.c_void_p]),
     "rt_mesh_quality": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(RtMeshQuality)]),
     "rt_mesh_update": (C.c_int, [C.c_void_p, C.c_int, _FP, C.c_float, C.POINTER(C.c_int)]),
+    "rt_mesh_skin_upload": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_uint16), _FP, C.c_int]),
+    "rt_mesh_bones": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_bones": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _FP]),
+    "rt_mesh_rest_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_skin": (C.c_int, [C.c_void_p]),
     "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
     "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
@@ -356,6 +362,7 @@ SIGNATURES = {
     "rt_gather_triangles": (C.c_int, [_FP, _U32P, C.c_int, _FP, _FP]),
     "rt_gather_triangles_checked": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, _FP, _FP]),
     "rt_gather_triangles_parts": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, C.POINTER(C.c_int32), C.c_int, _FP, _FP]),
+    "rt_skin_positions": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_uint16), _FP, _FP, C.c_int, _FP]),
     "rt_build_bvh": (C.c_int, [_FP, C.c_int, _FP, _FP]),
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
@@ -564,6 +571,33 @@ def gather_triangles_parts(positions, indices, part_first, models=None) -> np.nd
     if n < 0:
         raise RtError(n, "rt_gather_triangles_parts: an index out of range, indices that are no triangle list or a broken part table")
     return out[:n]
+
+
+def _skin_tables(who, n_verts, bone_idx, weights):
+    """bone_idx / weights as contiguous uint16 / float32 [n_verts,4]; an index that does not fit 16 bits is refused here, before the cast hides it."""
+    bi = np.asarray(bone_idx)
+    if bi.size != 4 * n_verts or np.asarray(weights).size != 4 * n_verts:
+        raise RtError(RT_ERR_INVALID, f"{who}: {n_verts} vertices need {4 * n_verts} bone indices and weights, got {bi.size} and {np.asarray(weights).size}")
+    if bi.size and (bi.min() < 0 or bi.max() > 65535):
+        raise RtError(RT_ERR_INVALID, f"{who}: bone indices must lie in 0 .. 65535")
+    return np.ascontiguousarray(bi, dtype=np.uint16).reshape(-1, 4), _f32(weights).reshape(-1, 4)
+
+
+def skin_positions(rest, bone_idx, weights, bones) -> np.ndarray:
+    """Linear-blend skinning on the host (rt_skin_positions), the definition Renderer.mesh_skin is tested against: rest [V,3], bone_idx / weights [V,4],
+    bones [nBones,16] column-major (or [nBones,4,4] as default_bvh_transform lays one out) -> positions [V,3] float32.  An influence of weight +-0 is
+    skipped; a vertex without any other keeps its rest position."""
+    p = _f32(rest).reshape(-1, 3)
+    b = _f32(bones)
+    if b.size % 16:
+        raise RtError(RT_ERR_INVALID, "skin_positions: bones must hold 16 floats per matrix")
+    b = b.reshape(-1, 16)
+    bi, w = _skin_tables("skin_positions", p.shape[0], bone_idx, weights)
+    out = np.zeros_like(p)
+    rc = lib().rt_skin_positions(_fp(p), p.shape[0], bi.ctypes.data_as(C.POINTER(C.c_uint16)), _fp(w), _fp(b), b.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_skin_positions: no vertices, a bone count outside 1 .. 65536, a bone index out of range or a weight that is not finite")
+    return out
 
 
 def bvh_layout(n_tris: int) -> RtBvhLayout:
@@ -1056,6 +1090,66 @@ class Renderer:
         self._check(lib().rt_mesh_hit_parts(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(parts.data_ptr()), C.c_void_p(tris.data_ptr())))
         cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
         return parts, tris
+
+    # ---- skinning: the positions rewritten on the device from rest positions and a bone table
+    def _device_view(self, ptr, nbytes, cols, as_torch):
+        """A float32 [nbytes / (4 * cols), cols] tensor that aliases library memory, zero-copy (as_torch=None: when torch imports), else (pointer, bytes)."""
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        if not as_torch:
+            return ptr, nbytes
+        import torch
+        rows = nbytes // (4 * cols)
+
+        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+            __cuda_array_interface__ = {"shape": (rows, cols), "typestr": "<f4", "data": (ptr, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    def mesh_skin_upload(self, bone_idx, weights, n_bones, rest=None):
+        """The skin of the current mesh (rt_mesh_skin_upload): bone_idx / weights [V,4], four influences per vertex; rest [V,3] rest positions, None: a
+        device-to-device snapshot of mesh_positions() as it stands.  Allocates the bone table with every matrix the identity.  May synchronise;
+        n_bones=0 releases the skin."""
+        nv = getattr(self, "_mesh_verts", 0)
+        if int(n_bones) == 0:
+            self._check(lib().rt_mesh_skin_upload(self._h, None, None, None, 0))
+            return
+        bi, w = _skin_tables("mesh_skin_upload", nv, bone_idx, weights)
+        r = None if rest is None else _f32(rest).reshape(-1, 3)
+        if r is not None and r.shape[0] != nv:
+            raise RtError(RT_ERR_INVALID, f"mesh_skin_upload: {r.shape[0]} rest positions, the mesh has {nv} vertices")
+        self._check(lib().rt_mesh_skin_upload(self._h, None if r is None else _fp(r), bi.ctypes.data_as(C.POINTER(C.c_uint16)), _fp(w), int(n_bones)))
+
+    def mesh_bones(self, as_torch=None):
+        """The device table of bone matrices, column-major.  With torch (as_torch=None: when it imports) a float32 [nBones,16] tensor that aliases it,
+        zero-copy; writes to it must be ordered on stream(), as for mesh_part_matrices.  Else (pointer, bytes)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_bones(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 16, as_torch)
+
+    def mesh_set_bones(self, models, first=0):
+        """Matrices [count,16] (or [count,4,4], column-major) from host memory into entries first .. of the bone table, copied on stream() in call
+        order with skins, updates, frames and queries (rt_mesh_set_bones)."""
+        m = _f32(models)
+        if m.size % 16:
+            raise RtError(RT_ERR_INVALID, "mesh_set_bones: models must hold 16 floats per matrix")
+        m = m.reshape(-1, 16)
+        self._check(lib().rt_mesh_set_bones(self._h, int(first), m.shape[0], _fp(m)))   # pageable memory: staged before the call returns
+
+    def mesh_rest_positions(self, as_torch=None):
+        """The device array of rest positions the skin reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes).  A
+        caller applies morph targets by writing it on stream() before mesh_skin."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_rest_positions(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 3, as_torch)
+
+    def mesh_skin(self):
+        """Enqueue positions := skin(rest, tables, bone table) on stream() (rt_mesh_skin): what skin_positions computes, bit for bit, under the bone
+        table as it stands when the kernel runs.  No host wait, no allocation; follow it with mesh_refit / mesh_rebuild / mesh_update."""
+        self._check(lib().rt_mesh_skin(self._h))
 
     def mesh_info(self) -> RtMeshInfo:
         i = RtMeshInfo()

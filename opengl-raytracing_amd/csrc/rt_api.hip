@@ -699,6 +699,24 @@ int rt_mesh_set_positions(RtContext *c, const float *positions) {
     return RT_OK;
 }
 
+// The two halves of the mesh path's event scheme around work enqueued on `st`, rt_stream()'s stream: what follows on `st` waits for
+// everything already enqueued on every other lane ...
+static int mesh_after_lanes(RtContext *c, hipStream_t st) {
+    for (int i = 0; i < c->nLanes; ++i) {
+        if (c->lanes[i] == st) continue;
+        HIP_TRY(c, hipEventRecord(c->evMeshLane[i], c->lanes[i]));
+        HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
+    }
+    return RT_OK;
+}
+// ... and whatever another lane is given next waits for what has been enqueued on `st` so far.
+static int mesh_before_lanes(RtContext *c, hipStream_t st) {
+    HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
+    for (int i = 0; i < c->nLanes; ++i)
+        if (c->lanes[i] != st) HIP_TRY(c, hipStreamWaitEvent(c->lanes[i], c->evMeshDone, 0));
+    return RT_OK;
+}
+
 // A rebuild or a refit: the device work of rt_mesh.hip between the two halves of the event scheme, then the scene installed (the same pointers and
 // counts every time; what a refit can change is whether the quantised nodes could be built).
 // parts: gather under the device matrix table instead of under M16.
@@ -711,19 +729,15 @@ static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = 
     static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
     // every lane's frames and queries read the arrays that are about to be rewritten: the update waits for them ...
-    for (int i = 0; i < c->nLanes; ++i) {
-        if (c->lanes[i] == st) continue;
-        HIP_TRY(c, hipEventRecord(c->evMeshLane[i], c->lanes[i]));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
-    }
+    int rc = mesh_after_lanes(c, st);
+    if (rc != RT_OK) return rc;
     const char *err = nullptr;
     const float *gatherM = parts ? nullptr : (M16 ? M16 : kIdentity);   // null: the part-aware gather
-    int rc = refit ? rtl::mesh_refit(c->mesh, st, gatherM, &err) : rtl::mesh_rebuild(c->mesh, st, gatherM, &err);
+    rc = refit ? rtl::mesh_refit(c->mesh, st, gatherM, &err) : rtl::mesh_rebuild(c->mesh, st, gatherM, &err);
     if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
     // ... and whatever a lane is given next waits for it
-    HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
-    for (int i = 0; i < c->nLanes; ++i)
-        if (c->lanes[i] != st) HIP_TRY(c, hipStreamWaitEvent(c->lanes[i], c->evMeshDone, 0));
+    rc = mesh_before_lanes(c, st);
+    if (rc != RT_OK) return rc;
     const rtl::BvhLayout &L = rtl::mesh_layout(c->mesh);
     const rtl::MeshScene &sc = rtl::mesh_scene(c->mesh);
     bool okQ = sc.q4 != nullptr;
@@ -752,6 +766,82 @@ int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16,
 int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
 int rt_mesh_rebuild_parts(RtContext *c) { return mesh_update(c, nullptr, false, true); }
 int rt_mesh_refit_parts(RtContext *c) { return mesh_update(c, nullptr, true, true); }
+
+// ---- skinning: rt_mesh_skin.hip rewrites the positions; this file validates the tables and orders the writes against every lane
+int rt_mesh_skin_upload(RtContext *c, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    if (nBones == 0) {
+        HIP_TRY(c, sync_all(c));
+        rtl::mesh_skin_release(c->mesh);
+        return RT_OK;
+    }
+    if (nBones < 1 || nBones > RT_MAX_MESH_BONES) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: %d bones (1 .. %d)", nBones, RT_MAX_MESH_BONES);
+    if (!boneIdx4 || !weights4) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: null %s", !boneIdx4 ? "boneIdx4" : "weights4");
+    const size_t n = (size_t)rtl::mesh_verts(c->mesh) * RT_SKIN_INFLUENCES;
+    for (size_t k = 0; k < n; ++k) {
+        if ((int)boneIdx4[k] >= nBones)
+            return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: influence %zu of vertex %zu names bone %u of %d", k % RT_SKIN_INFLUENCES, k / RT_SKIN_INFLUENCES, (unsigned)boneIdx4[k], nBones);
+        if (!std::isfinite(weights4[k]))
+            return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: weight %zu of vertex %zu is not finite", k % RT_SKIN_INFLUENCES, k / RT_SKIN_INFLUENCES);
+    }
+    return guarded(c, "rt_mesh_skin_upload", [&]() -> int {
+        HIP_TRY(c, sync_all(c));   // a skin in flight reads the arrays that are replaced; the snapshot reads the positions as they stand
+        const char *err = nullptr;
+        const int rc = rtl::mesh_skin_create(c->mesh, rest, boneIdx4, weights4, nBones, &err);
+        return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_skin_upload: %s", err ? err : "allocation failed");
+    });
+}
+
+int rt_mesh_bones(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_bones: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
+    *devPtr = rtl::mesh_bones(c->mesh);
+    *bytes = (size_t)rtl::mesh_bone_count(c->mesh) * 64;
+    return RT_OK;
+}
+
+int rt_mesh_rest_positions(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_rest_positions: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
+    *devPtr = rtl::mesh_rest_positions(c->mesh);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
+    return RT_OK;
+}
+
+int rt_mesh_set_bones(RtContext *c, int first, int count, const float *M16s) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
+    const int n = rtl::mesh_bone_count(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: entries %d .. %d of a table of %d", first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!M16s) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: null matrices");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    int rc = mesh_after_lanes(c, st);   // a skin enqueued on another lane reads the table
+    if (rc != RT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_bones(c->mesh) + (size_t)first * 16, M16s, (size_t)count * 64, hipMemcpyHostToDevice, st));
+    return mesh_before_lanes(c, st);
+}
+
+int rt_mesh_skin(RtContext *c) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_skin: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_skin: no skin (rt_mesh_skin_upload first; rt_mesh_upload releases the skin)");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    // a position write: gathers, bone and rest writes and bound raster draws already enqueued on any lane come first ...
+    int rc = mesh_after_lanes(c, st);
+    if (rc != RT_OK) return rc;
+    if (c->raster && rt_raster_order_after(c->raster, st) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_skin: %s", rt_raster_error(c->raster));
+    const char *err = nullptr;
+    rc = rtl::mesh_skin(c->mesh, st, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_skin: %s", err ? err : "launch failed");
+    return mesh_before_lanes(c, st);   // ... and updates, draws and table writes a lane is given next see the new positions
+}
 
 // ---- tree quality
 static inline float key2f(uint32_t s) { const uint32_t u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s; float f; std::memcpy(&f, &u, 4); return f; }

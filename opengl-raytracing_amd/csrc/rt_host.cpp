@@ -415,6 +415,32 @@ int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t
     return nIdx / 3;
 }
 
+// Linear-blend skinning, and the definition rt_mesh_skin is held to: per vertex the influences in order, one of weight +-0 skipped,
+// q = B * p in rt_gather_triangles' expression, the first w * q starts the sum and the later ones are added to it; no influence: the rest position's bits.
+int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, const float *weights4, const float *bones16, int nBones, float *out) {
+    if (!rest || !boneIdx4 || !weights4 || !bones16 || !out || nVerts <= 0 || nBones < 1 || nBones > RT_MAX_MESH_BONES) return RT_ERR_INVALID;
+    for (size_t k = 0; k < (size_t)nVerts * RT_SKIN_INFLUENCES; ++k)
+        if ((int)boneIdx4[k] >= nBones || !std::isfinite(weights4[k])) return RT_ERR_INVALID;
+    for (int v = 0; v < nVerts; ++v) {
+        float p[3], acc[3] = {0.0f, 0.0f, 0.0f};
+        std::memcpy(p, rest + (size_t)v * 3, sizeof p);   // out may be rest
+        bool any = false;
+        for (int k = 0; k < RT_SKIN_INFLUENCES; ++k) {
+            const float w = weights4[(size_t)v * RT_SKIN_INFLUENCES + k];
+            if (w == 0.0f) continue;
+            const float *B = bones16 + (size_t)boneIdx4[(size_t)v * RT_SKIN_INFLUENCES + k] * 16;
+            for (int c = 0; c < 3; ++c) {
+                const float q = (B[c] * p[0] + B[4 + c] * p[1]) + (B[8 + c] * p[2] + B[12 + c] * 1.0f);
+                const float term = w * q;
+                acc[c] = any ? acc[c] + term : term;
+            }
+            any = true;
+        }
+        std::memcpy(out + (size_t)v * 3, any ? acc : p, sizeof p);
+    }
+    return RT_OK;
+}
+
 int rt_build_bvh_order(const float *tris9, int nTris, float *nodes12, float *tris12, int32_t *orderOut) {
     if (nTris < 0 || (nTris > 0 && (!tris9 || !nodes12 || !tris12))) return RT_ERR_INVALID;
     if (nTris == 0) return 0;

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -214,6 +215,11 @@ struct Mesh {
     int32_t *dPartFirst = nullptr;
     uint16_t *dPartOf = nullptr;
     float *dPartM = nullptr;
+    // skin: rest positions, four bone indices and weights per vertex, one matrix per bone; allocated by mesh_skin_create, not in `owned`
+    float *dRest = nullptr, *dSkinW = nullptr, *dBones = nullptr;
+    uint16_t *dSkinIdx = nullptr;
+    int nBones = 0;
+    size_t skinBytes = 0;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -400,6 +406,7 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
 
 void mesh_destroy(Mesh *m) {
     if (!m) return;
+    mesh_skin_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -522,6 +529,49 @@ int mesh_measure(Mesh *m, hipStream_t st, int slot, const char **err) {
 
 hipEvent_t mesh_quality_event(const Mesh *m, int slot) { return m->evQ[slot]; }
 const QualityRecord *mesh_quality_record(const Mesh *m, int slot) { return reinterpret_cast<const QualityRecord *>(m->hQRec + (size_t)slot * kQualityRecordBytes); }
+
+void mesh_skin_release(Mesh *m) {
+    for (void *p : {(void *)m->dRest, (void *)m->dSkinIdx, (void *)m->dSkinW, (void *)m->dBones}) if (p) (void)hipFree(p);
+    m->dRest = m->dSkinW = m->dBones = nullptr; m->dSkinIdx = nullptr;
+    m->scratchBytes -= m->skinBytes;
+    m->skinBytes = 0; m->nBones = 0;
+}
+
+int mesh_skin_create(Mesh *m, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones, const char **err) {
+    mesh_skin_release(m);
+    const size_t nv = (size_t)m->nVerts;
+    std::vector<float> ident((size_t)nBones * 16, 0.0f);
+    for (int b = 0; b < nBones; ++b)
+        for (int k = 0; k < 4; ++k) ident[(size_t)b * 16 + 5 * k] = 1.0f;
+    auto make = [&](auto **p, const void *src, size_t bytes, hipMemcpyKind kind) -> hipError_t {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e != hipSuccess) return e;
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+        ++m->allocations;
+        m->skinBytes += bytes; m->scratchBytes += bytes;
+        return hipMemcpy(q, src, bytes, kind);
+    };
+    hipError_t e = rest ? make(&m->dRest, rest, nv * 12, hipMemcpyHostToDevice) : make(&m->dRest, m->dPos, nv * 12, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = make(&m->dSkinIdx, boneIdx4, nv * RT_SKIN_INFLUENCES * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = make(&m->dSkinW, weights4, nv * RT_SKIN_INFLUENCES * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = make(&m->dBones, ident.data(), ident.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_skin_release(m); return RT_ERR_HIP; }
+    m->nBones = nBones;
+    return RT_OK;
+}
+
+int mesh_bone_count(const Mesh *m) { return m->nBones; }
+float *mesh_bones(Mesh *m) { return m->dBones; }
+float *mesh_rest_positions(Mesh *m) { return m->dRest; }
+
+int mesh_skin(Mesh *m, hipStream_t st, const char **err) {
+    if (m->nBones <= 0) return RT_ERR_INVALID;
+    skin_launch(st, m->dRest, m->dSkinIdx, m->dSkinW, m->dBones, m->nVerts, m->dPos);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
 
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err) {
     REB_TRY(hipMemcpyAsync(m->hStatus, m->dStatus, 4, hipMemcpyDeviceToHost, st));

@@ -90,6 +90,19 @@ int mesh_measure(Mesh *m, hipStream_t st, int slot, const char **err);
 hipEvent_t mesh_quality_event(const Mesh *m, int slot);
 const QualityRecord *mesh_quality_record(const Mesh *m, int slot);
 
+// Skinning.  mesh_skin_create: validated host tables for the mesh's vertices; rest == nullptr snapshots the device positions.  Replaces
+// a skin the mesh already has.  Allocates, copies and waits for the device; the caller has waited for every lane.  mesh_skin_release: the four arrays
+// freed (callers have synchronised).  mesh_skin enqueues positions := skin(rest, tables, bone table) on `st`: no allocation, no host wait;
+// RT_ERR_INVALID without a skin.
+int mesh_skin_create(Mesh *m, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones, const char **err);
+void mesh_skin_release(Mesh *m);
+int mesh_bone_count(const Mesh *m);          // 0: no skin
+float *mesh_bones(Mesh *m);                  // device, nBones x 16 floats, column-major
+float *mesh_rest_positions(Mesh *m);         // device, nVerts x 3 floats
+int mesh_skin(Mesh *m, hipStream_t st, const char **err);
+// rt_mesh_skin.hip: the kernel behind a plain launch function (raw device pointers; idx4 / w4: four influences per vertex)
+void skin_launch(hipStream_t st, const float *rest, const uint16_t *idx4, const float *w4, const float *bones, int nVerts, float *pos);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

@@ -344,7 +344,7 @@ int rt_debug_eval(RtContext *ctx, int op, const float *a, const float *b, const 
  * hit point xyz, then normal xyz; t = inf on miss), kind 1 = any hit within tMax (out[0] = 1/0).
  * kinds 2 / 3: the same two questions put to the wavefront pipeline's own traversal kernels (persistent launch, refill scheduler, the
  * any-hit node form rt_upload_bvh chose, the kernel build the environment selects for frames) -- kind 2: out[0] = t (inf on miss), out[1] = index of the
- * triangle hit; kind 3: out[0] = 1/0.
+ * triangle hit, -1 on a miss; kind 3: out[0] = 1/0, a ray with tMax < 0 is an empty slot (out[0] = 0).
  * kind 4: any-hit rays through the packet kernel of RT_PACKET_AO (k_trace_packets), out[0] = 1/0 as kind 3.  n must be a multiple of four: rays 4 p .. 4 p + 3
  * form packet p, which leaves from the origin of its first ray (the caller guarantees that all four share it, as the AO rays of one hit do); a ray with
  * tMax < 0 is an empty slot (out[0] = 0), so packets of one to three live rays can be expressed. */

@@ -1742,7 +1742,7 @@ static int debug_trace_wave(RtContext *c, int kind, const float *origins, const 
     const uint32_t un = (uint32_t)n, live = packets ? (uint32_t)P : un;   // queue entries: rays, or packets
     ok = ok && hipMemcpy(dO, o4.data(), (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dD, d4.data(), (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(dT, tm.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dCnt, &live, 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(dHeads, 0, rt_wave_head_words() * 4) == hipSuccess && hipMemset(dOcc, 0, (size_t)n) == hipSuccess && hipMemset(dTri, 0xff, (size_t)n * 4) == hipSuccess &&
+         hipMemset(dHeads, 0, rt_wave_head_words() * 4) == hipSuccess &&   // (dOcc: cleared by the wave entries on the launch's stream; dTri: every ray stores one)
          hipMemcpy(dF, host, sizeof(DevFrame), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { freeAll(); return fail(c, RT_ERR_HIP, "rt_debug_trace: allocation / upload failed"); }
     if (host->sc.rootBox) hipLaunchKernelGGL(k_frame_root_box, dim3(1), dim3(64), 0, c->stream, dF);

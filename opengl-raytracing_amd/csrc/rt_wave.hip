@@ -256,12 +256,17 @@ __global__ __launch_bounds__(256) void k_primary(const DevFrame *__restrict__ fr
     ap.commit(&wb.counts[0]);
     for (int k = 0; k < kAppendBatch; ++k) {
         const uint32_t idx = ap.index(k);
-        if (ap.mine(k)) wb.cand[idx] = (uint32_t)((blockIdx.x * kAppendBatch + k) * 256 + threadIdx.x);
+        if (ap.mine(k)) { wb.cand[idx] = (uint32_t)((blockIdx.x * kAppendBatch + k) * 256 + threadIdx.x); wb.primTri[idx] = -1; }   // the miss answer: PrimarySrc stores hits only
     }
 }
 
 // ---- persistent traversal ----------------------------------------------------------------------
 // Ray sources.
+// Sparse answers (round 17): for the frame's own primary and any-hit sources -- PrimarySrc, QueueSrc::store_any, DualQueueSrc -- an answer array holds the MISS answer
+// before the launch starts (primTri = -1, occ = 0: written coalesced by whoever writes the ray at the same index: k_primary, GenDirectTracer, GenGiTracer), and the launch
+// overwrites it only for a hit or an occlusion: a retiring miss stores nothing.  Everything else stores every answer: the bounce queue's launches (BounceProbeSrc,
+// QueueSrc::store_closest -- pre-filling giTri was measured and gained nothing) and the sources over the caller's memory or a dense list (IndexedSrc,
+// IndexedDenseSrc, CompactSrc, QuerySrc, SceneSrc).
 struct PrimarySrc {   // ray i = primary ray of candidate i
     const DevFrame *fr;
     const uint32_t *cand;
@@ -281,7 +286,7 @@ struct PrimarySrc {   // ray i = primary ray of candidate i
         ro = ld3(fr->u.camPos);
         rd = primaryDirK(fr, sub_frame_of_slot(fr->g, p.slot), px, py);
     }
-    RT_DEV void store_closest(uint32_t i, float t, int tri) const { outT[i] = t; outTri[i] = tri; }
+    RT_DEV void store_closest(uint32_t i, float t, int tri) const { if (tri >= 0) { outT[i] = t; outTri[i] = tri; } }   // misses are pre-filled, see above
     RT_DEV void store_any(uint32_t, bool) const {}
     RT_DEV bool dense(uint32_t, uint32_t) const { return false; }
     RT_DEV float probe_take(uint32_t, V3 &, V3 &, uint32_t &) const { return -1.0f; }
@@ -318,7 +323,7 @@ struct QueueSrc {     // slot-major queue: ray r -> (slot = r / n, j = r % n) at
         ro = f4xyz(oo); rd = f4xyz(dd);
     }
     RT_DEV void store_closest(uint32_t a, float t, int tri) const { outT[a] = t; outTri[a] = tri; }
-    RT_DEV void store_any(uint32_t a, bool occ) const { outOcc[a] = occ ? 1 : 0; }
+    RT_DEV void store_any(uint32_t a, bool occ) const { if (occ) outOcc[a] = 1; }   // "not occluded" is pre-filled, see above
     // Dense slots (round 4): where (nearly) every entry is a ray the liveness probe is a wasted round trip -- the i-th idle lane takes the i-th entry
     // left and reads liveness word and record together; an entry that is dead after all (AO radius 0, GI switched off) just leaves its lane idle.
     RT_DEV bool dense(uint32_t r0, uint32_t r1) const { return r1 > r0 && (r1 - 1u) / nLive < denseSlots; }
@@ -354,8 +359,9 @@ struct DualQueueSrc {
     }
     RT_DEV void store_closest(uint32_t, float, int) const {}
     RT_DEV void store_any(uint32_t token, bool occ) const {
-        if (token & 0x80000000u) b.outOcc[token & 0x7fffffffu] = occ ? 1 : 0;
-        else a.outOcc[token] = occ ? 1 : 0;
+        if (!occ) return;
+        if (token & 0x80000000u) b.outOcc[token & 0x7fffffffu] = 1;
+        else a.outOcc[token] = 1;
     }
     RT_DEV bool dense(uint32_t r0, uint32_t r1) const { return r1 <= na && a.dense(r0, r1); }
     RT_DEV float probe_take(uint32_t r, V3 &ro, V3 &rd, uint32_t &token) const { return a.probe_take(r, ro, rd, token); }
@@ -1644,6 +1650,7 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         wb.shT[al] = fmaxr(tMax, 0.0f);
         wb.shO[al] = mkf4(ro, 0.0f);
         wb.shD[a] = mkf4(rd, 0.0f);
+        wb.occ1[a] = 0;                  // "not occluded": the any-hit launch stores occlusions only
         return false;
     }
     V3 giRo, giRd;   // RT_BIN_GI: the bounce ray is kept here and written by the workgroup's sort (k_gen_direct)
@@ -1658,6 +1665,7 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         uint32_t a = (uint32_t)i * wb.CH + j;
         if (i == 0) wb.aoOrg[j] = mkf4(org, 0.0f);   // one origin for the hit's AO rays (only sample 0's thread gets here)
         wb.shD[a] = mkf4(dir, below(radius));         // closest t < radius  <=>  any hit with t <= pred(radius)
+        wb.occ1[a] = 0;
         return false;
     }
 };
@@ -1681,6 +1689,7 @@ struct GenGiTracer {       // reads the bounce result, records the shadow rays a
         wb.sh2T[a] = fmaxr(tMax, 0.0f);
         wb.sh2O[a] = mkf4(ro, 0.0f);
         wb.sh2D[a] = mkf4(rd, 0.0f);
+        wb.occ2[a] = 0;
         return false;
     }
     RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn) {
@@ -2526,15 +2535,18 @@ uint32_t rt_wave_debug_trace(hipStream_t st, int cus, int treeDepth, const DevFr
     QueueSrc q;
     q.o = o; q.d = d; q.tm = tm; q.liveCount = liveCount; q.c0 = 0; q.cap = n; q.stride = n; q.slots = 1; q.denseSlots = 0; q.org = nullptr; q.orgStride = 0;
     q.outT = outT; q.outTri = outTri; q.outOcc = outOcc; q.nLive = 0;
+    // QueueSrc stores occlusions only: "not occluded" goes in first, on the launch's stream (an empty slot, tm < 0, keeps it)
+    if (any) (void)hipMemsetAsync(outOcc, 0, n, st);
     const TraceTune tune = tune_from_env();
     if (any) return launch_trace<QueueSrc, true>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
     return launch_trace<QueueSrc, false>(st, cus, 100, treeDepth, dFrame, hostScene, q, heads, nullptr, nullptr, tune, nullptr);
 }
 // rt_debug_trace kind 4: nPackets packets of four any-hit rays through k_trace_packets, in the layout of PacketSrc with A = 4 AO slots: ray r of packet p at
-// [r * nPackets + p] (*liveCount = nPackets).  A packet leaves from the origin of its ray 0; tm < 0 marks an empty slot (its occ entry is not written).
+// [r * nPackets + p] (*liveCount = nPackets).  A packet leaves from the origin of its ray 0; tm < 0 marks an empty slot (its occ entry keeps the 0 written here first).
 uint32_t rt_wave_debug_packets(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const float4 *o, const float4 *d,
                                const float *tm, const uint32_t *liveCount, uint32_t nPackets, uint8_t *outOcc, uint32_t *heads) {
     PacketSrc pk;
+    (void)hipMemsetAsync(outOcc, 0, (size_t)nPackets * 4, st);   // what an empty slot reads
     pk.o = o; pk.d = d; pk.tm = tm; pk.org = nullptr; pk.occ = outOcc; pk.liveCount = liveCount; pk.c0 = 0; pk.cap = nPackets; pk.stride = nPackets; pk.A = 4; pk.nLive = 0;
     return launch_packets(st, cus, 100, treeDepth, dFrame, hostScene, pk, heads, nullptr, nullptr, tune_from_env());
 }

@@ -338,7 +338,8 @@ const char *rt_stage_name(int stage);
 
 /* Diagnostics used by the parity tests: evaluate one device function of the float model on arrays
  * (op: 0 sin, 1 cos, 2 exp2, 3 log2, 4 pow(a,b), 5 f32->f16 bits, 6 rand(a,b,frame=c) bits,
- * 7 a/b, 8 sqrt(a), 9 1/sqrt(a)).  Arrays are host memory of n floats (out: n uint32 bit patterns). */
+ * 7 a/b, 8 sqrt(a), 9 1/sqrt(a), 10 the cube-map texel decode of code a (0..255), 11 halton(a, b) of rt_common.glsl:106-116,
+ * 12 / 13 the sample / the hit a generator thread works on: a, b, c carry uint32 bit patterns -- thread index, live hits of the chunk, spp).  Arrays are host memory of n floats (out: n uint32 bit patterns). */
 int rt_debug_eval(RtContext *ctx, int op, const float *a, const float *b, const float *c, uint32_t *out, int n);
 /* Trace n rays against the uploaded BVH with the device traversal: kind 0 = closest hit (out: t, then
  * hit point xyz, then normal xyz; t = inf on miss), kind 1 = any hit within tMax (out[0] = 1/0).
@@ -762,6 +763,22 @@ typedef struct RtWavePlan {
  * the hit count is known; else the plan behind its read-back (ignored under RT_CHUNKS_FROM_SLOTS).  share: the share of (hit, sample) pairs whose bounce
  * ray hit in earlier launch sets, 0 = nothing known.  RT_ERR_UNSUPPORTED (message: rt_last_error(NULL)) for a chunk of 2^31 queue entries or more. */
 int rt_debug_wave_plan(uint64_t slots, int spp, int aoRays, const RtWaveOptions *opt, int64_t hits, double share, RtWavePlan *out);
+/* Diagnostics, host side (no GPU needed, no context): the arithmetic the shading stages do without a division, as the host compiles it.
+ * rt_debug_eval ops 10 (texel decode of code a) and 11 (halton(a, b)) evaluate the same functions on the device.
+ *   rt_debug_texel_unorm8: out256[c] = the value the cube-map lookup gives texel code c (c / 255.0f, computed without the division).
+ *   rt_debug_halton_pairs: out[2 i], out[2 i + 1] = (halton(f + 1, 2), halton(f + 1, 3)) for f = frame0 + i: what rt_render_frame(s) writes into the frame
+ *     descriptor for uFrameIndex = f, and cpOffset (rt_lighting.glsl:280-289) otherwise evaluates per fragment.
+ *   rt_debug_div_reciprocal: the word the host stores for divisor d when the largest dividend is nMax: floor(2^32 / d) + 1 when d >= 2 and nMax * d < 2^32,
+ *     else 0 = "divide".  rt_debug_div_by: q[i] = n[i] / d and r[i] = n[i] % d as the kernels compute them from (d, rcp).
+ *   rt_debug_frame_geom: the tile geometry of a w x h frame on `rank` of `world` for batches of `batch` frames with its three reciprocals (useReciprocals == 0:
+ *     all zero, the dividing form); xy != NULL: for every pixel slot of the batch (nLocalTiles * batch * 256) the pixel and sub-frame (x, y, k) that slot maps
+ *     to, or (-1, -1, -1) for padding. */
+typedef struct RtFrameGeomInfo { int32_t tilesX, tilesY, nTiles, nLocalTiles; uint32_t rcpLocalTiles, rcpTilesX, rcpWorld; } RtFrameGeomInfo;
+int rt_debug_texel_unorm8(float *out256);
+int rt_debug_halton_pairs(int frame0, int count, float *out);
+uint32_t rt_debug_div_reciprocal(uint32_t d, uint64_t nMax);
+int rt_debug_div_by(uint32_t d, uint32_t rcp, const uint32_t *n, size_t count, uint32_t *q, uint32_t *r);
+int rt_debug_frame_geom(int w, int h, int rank, int world, int batch, int useReciprocals, RtFrameGeomInfo *out, int32_t *xy);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

@@ -369,6 +369,11 @@ SIGNATURES = {
     "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
     "rt_debug_wave_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),   # RtWaveOptions, RtWavePlan: _wave_plan_types
     "rt_debug_pack_scene": (C.c_int, [_FP, C.c_int, _FP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rt_debug_texel_unorm8": (C.c_int, [_FP]),
+    "rt_debug_halton_pairs": (C.c_int, [C.c_int, C.c_int, _FP]),
+    "rt_debug_div_reciprocal": (C.c_uint32, [C.c_uint32, C.c_uint64]),
+    "rt_debug_div_by": (C.c_int, [C.c_uint32, C.c_uint32, _U32P, C.c_size_t, _U32P, _U32P]),
+    "rt_debug_frame_geom": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),   # RtFrameGeomInfo
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -754,6 +759,63 @@ def wave_plan(slots, spp, ao_rays=0, *, hits=None, share=0.0, **options):
     scalars = {n: int(getattr(out, n)) for n in ("slots", "perHit", "chBudget", "ch", "room", "q2Entries", "spp", "ao", "S1", "S2", "L1", "nChunks")}
     return types.SimpleNamespace(**scalars, deferred=bool(out.deferred), options={n: int(getattr(out.options, n)) for n, _ in RtWaveOptions._fields_ if n != "reserved"},
                                  frame=arena(out.frame), rays=arena(out.rays), results=arena(out.results))
+
+
+# ---- the shading stages' division-free arithmetic, as the host compiles it (no context, no GPU) ----
+
+class RtFrameGeomInfo(_Struct):   # rt_debug_frame_geom
+    _fields_ = [("tilesX", C.c_int32), ("tilesY", C.c_int32), ("nTiles", C.c_int32), ("nLocalTiles", C.c_int32),
+                ("rcpLocalTiles", C.c_uint32), ("rcpTilesX", C.c_uint32), ("rcpWorld", C.c_uint32)]
+
+
+def texel_unorm8() -> np.ndarray:
+    """The cube-map lookup's value for each of the 256 texel codes (rt_debug_texel_unorm8)."""
+    out = np.zeros(256, np.float32)
+    rc = lib().rt_debug_texel_unorm8(_fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_texel_unorm8")
+    return out
+
+
+def halton_pairs(frame0, count) -> np.ndarray:
+    """[count, 2] float32: the (halton(f + 1, 2), halton(f + 1, 3)) the host writes into the frame descriptor for uFrameIndex f = frame0 + i."""
+    out = np.zeros((int(count), 2), np.float32)
+    rc = lib().rt_debug_halton_pairs(int(frame0), int(count), _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_halton_pairs")
+    return out
+
+
+def div_reciprocal(d, n_max) -> int:
+    """The reciprocal word the host stores for divisor d and largest dividend n_max; 0 = the kernels divide (rt_debug_div_reciprocal)."""
+    return int(lib().rt_debug_div_reciprocal(int(d), int(n_max)))
+
+
+def div_by(d, rcp, n):
+    """(n // d, n % d) as the kernels compute them from the divisor and its reciprocal word (rt_debug_div_by); n: uint32 array."""
+    n = np.ascontiguousarray(n, np.uint32).reshape(-1)
+    q, r = np.zeros_like(n), np.zeros_like(n)
+    rc = lib().rt_debug_div_by(int(d), int(rcp), n.ctypes.data_as(_U32P), n.size, q.ctypes.data_as(_U32P), r.ctypes.data_as(_U32P))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_div_by")
+    return q, r
+
+
+def frame_geom(w, h, rank=0, world=1, batch=1, reciprocals=True, slots=False):
+    """rt_debug_frame_geom: (RtFrameGeomInfo, xy) -- the tile geometry rt_resize sets up, with its reciprocal words for batches of `batch` frames, and with
+    slots=True an int32 [nLocalTiles * batch * 256, 3] array of (x, y, sub-frame) per pixel slot, -1 for padding (else None)."""
+    info = RtFrameGeomInfo()
+    rc = lib().rt_debug_frame_geom(int(w), int(h), int(rank), int(world), int(batch), int(bool(reciprocals)), C.byref(info), None)
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_frame_geom")
+    xy = None
+    if slots:
+        xy = np.zeros((info.nLocalTiles * int(batch) * 256, 3), np.int32)
+        rc = lib().rt_debug_frame_geom(int(w), int(h), int(rank), int(world), int(batch), int(bool(reciprocals)), C.byref(info),
+                                       xy.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != RT_OK:
+            raise RtError(rc, "rt_debug_frame_geom")
+    return info, xy
 
 
 def load_obj(path):

@@ -216,6 +216,14 @@ __global__ void k_debug_eval(int op, const float *a, const float *b, const float
         case 7: r = f2u(x / y); break;
         case 8: r = f2u(__builtin_sqrtf(x)); break;
         case 9: r = f2u(1.0f / __builtin_sqrtf(x)); break;
+        case 10: r = f2u(texel_unorm8((uint8_t)(int)x)); break;
+        case 11: r = f2u(halton((int)x, (int)y)); break;
+        case 12: case 13: {   // a, b, c hold integers as bit patterns here: thread index, live hits, spp
+            int sm; uint32_t j;
+            sample_and_hit(f2u(x), f2u(y), (int)f2u(z), sm, j);
+            r = op == 12 ? (uint32_t)sm : j;
+            break;
+        }
         default: break;
     }
     out[i] = r;
@@ -1132,6 +1140,56 @@ int rt_debug_wave_plan(uint64_t slots, int spp, int aoRays, const RtWaveOptions 
     });
 }
 
+// The frame geometry of a w x h framebuffer on rank `rank` of `world` (rt_resize), for a batch of one.
+static FrameGeom make_frame_geom(int w, int h, int rank, int world) {
+    FrameGeom g;
+    g.W = w; g.H = h;
+    g.tilesX = (w + RT_TILE_DIM - 1) / RT_TILE_DIM;
+    g.tilesY = (h + RT_TILE_DIM - 1) / RT_TILE_DIM;
+    g.nTiles = g.tilesX * g.tilesY;
+    g.rank = rank; g.world = world;
+    g.nLocalTiles = (g.nTiles - g.rank + g.world - 1) / g.world;
+    if (g.nLocalTiles < 0) g.nLocalTiles = 0;
+    g.batch = 1;
+    frame_geom_set_reciprocals(g);
+    return g;
+}
+
+int rt_debug_texel_unorm8(float *out256) {
+    if (!out256) return RT_ERR_INVALID;
+    for (int c = 0; c < 256; ++c) out256[c] = texel_unorm8((uint8_t)c);
+    return RT_OK;
+}
+int rt_debug_halton_pairs(int frame0, int count, float *out) {
+    if (!out || count < 0 || frame0 < 0) return RT_ERR_INVALID;
+    for (int i = 0; i < count; ++i) { out[2 * i] = halton(frame0 + i + 1, 2); out[2 * i + 1] = halton(frame0 + i + 1, 3); }
+    return RT_OK;
+}
+uint32_t rt_debug_div_reciprocal(uint32_t d, uint64_t nMax) { return div_reciprocal(d, nMax); }
+int rt_debug_div_by(uint32_t d, uint32_t rcp, const uint32_t *n, size_t count, uint32_t *q, uint32_t *r) {
+    if (d == 0 || !n || !q || !r) return RT_ERR_INVALID;
+    for (size_t i = 0; i < count; ++i) { q[i] = div_by(n[i], d, rcp); r[i] = n[i] - q[i] * d; }
+    return RT_OK;
+}
+int rt_debug_frame_geom(int w, int h, int rank, int world, int batch, int useReciprocals, RtFrameGeomInfo *out, int32_t *xy) {
+    if (!out || w <= 0 || h <= 0 || world < 1 || rank < 0 || rank >= world || batch < 1 || batch > RT_MAX_BATCH) return RT_ERR_INVALID;
+    FrameGeom g = make_frame_geom(w, h, rank, world);
+    g.batch = batch;
+    frame_geom_set_reciprocals(g);
+    if (!useReciprocals) g.rcpLocalTiles = g.rcpTilesX = g.rcpWorld = 0;
+    out->tilesX = g.tilesX; out->tilesY = g.tilesY; out->nTiles = g.nTiles; out->nLocalTiles = g.nLocalTiles;
+    out->rcpLocalTiles = g.rcpLocalTiles; out->rcpTilesX = g.rcpTilesX; out->rcpWorld = g.rcpWorld;
+    if (xy)
+        for (int lt = 0; lt < g.nLocalTiles * batch; ++lt)
+            for (int tid = 0; tid < 256; ++tid) {
+                int x, y;
+                int32_t *o = xy + ((size_t)lt * 256 + tid) * 3;
+                if (pixel_of_slot(g, lt, tid, x, y)) { o[0] = x; o[1] = y; o[2] = sub_frame_of_tile(g, lt); }
+                else o[0] = o[1] = o[2] = -1;
+            }
+    return RT_OK;
+}
+
 int rt_upload_env(RtContext *c, const uint8_t *faces, int faceSize, int channels) {
     if (!c) return RT_ERR_INVALID;
     (void)hipSetDevice(c->cfg.device);
@@ -1164,15 +1222,7 @@ int rt_resize(RtContext *c, int w, int h) {
     (void)hipSetDevice(c->cfg.device);
     HIP_TRY(c, sync_all(c));
     free_targets(c);
-    FrameGeom g;
-    g.W = w; g.H = h;
-    g.tilesX = (w + RT_TILE_DIM - 1) / RT_TILE_DIM;
-    g.tilesY = (h + RT_TILE_DIM - 1) / RT_TILE_DIM;
-    g.nTiles = g.tilesX * g.tilesY;
-    g.rank = c->cfg.rank; g.world = c->cfg.worldSize;
-    g.nLocalTiles = (g.nTiles - g.rank + g.world - 1) / g.world;
-    if (g.nLocalTiles < 0) g.nLocalTiles = 0;
-    g.batch = 1;
+    const FrameGeom g = make_frame_geom(w, h, c->cfg.rank, c->cfg.worldSize);
     c->g = g;
     // every rank allocates the padded size so gather blocks are equal
     const size_t maxLocal = (size_t)(g.nTiles + g.world - 1) / g.world;
@@ -1232,6 +1282,11 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     if (!(fr.u.nodeCount > 0 && fr.u.triCount > 0)) fr.sc.hasBVH = 0;
     fr.g = c->g;
     fr.g.batch = batch;
+    frame_geom_set_reciprocals(fr.g);   // (the largest local tile index grows with the batch)
+    for (int k = 0; k < RT_MAX_BATCH; ++k) {   // cpOffset's ld2(uFrameIndex) of the batch's frames: the device's own function, evaluated here once per frame
+        const int fi = c->frameIndex + (k < batch ? k : 0);
+        fr.ld2K[k][0] = halton(fi + 1, 2); fr.ld2K[k][1] = halton(fi + 1, 3);
+    }
     for (int k = 0; k < RT_MAX_BATCH; ++k) { fr.jitterK[k][0] = jitterK ? jitterK[k < batch ? k : 0][0] : fr.u.jitter[0]; fr.jitterK[k][1] = jitterK ? jitterK[k < batch ? k : 0][1] : fr.u.jitter[1]; }
     fr.giBounces = c->giBounces;
     // Lane = frame index mod nLanes = index of the COLOR0 buffer this frame writes: consecutive frames rotate over the lanes'

@@ -15,6 +15,7 @@
 namespace rtd {
 
 #define RT_DEV __device__ __forceinline__
+#define RT_HOST_DEV __host__ __device__ __forceinline__   // the few functions the host evaluates too (frame set-up, the host-side debug entries)
 
 struct V2 { float x, y; };
 struct V3 { float x, y, z; };

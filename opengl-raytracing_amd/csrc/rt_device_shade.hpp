@@ -89,7 +89,8 @@ RT_DEV uint32_t rand_bits(float px, float py, int frame) {
 }
 RT_DEV float randr(float px, float py, int frame) { return (float)rand_bits(px, py, frame) / 4294967296.0f; }   // :75-77
 RT_DEV float epsForDist(float d) { return fmaxr(1e-4f, 1e-3f * d); }   // :88-90
-RT_DEV float halton(int i, int b) {   // :106-116
+// (host + device: render_frames_impl evaluates it once per sub-frame for DevFrame::ld2K -- the same IEEE operations, no contraction on either side)
+RT_HOST_DEV float halton(int i, int b) {   // :106-116
     float f = 1.0f, r = 0.0f;
     int n = i;
     while (n > 0) {
@@ -313,7 +314,21 @@ struct Frag {
     // uFrameIndex of THIS fragment's frame.  The reference's value for a single frame; with frame batching (rt_render_frames: K frames of
     // a static camera in one set of launches) the frames of a batch differ in it -- and in the jitter, see primaryDirJ -- and in nothing else.
     int frameIndex = 0;
+    // ld2(frameIndex) = (halton(frameIndex + 1, 2), halton(frameIndex + 1, 3)), the same for every fragment of a frame: filled from the frame descriptor
+    // (DevFrame::ld2K) for the tracers that declare kFrameLd2 (directLightBVH); nobody else reads it, and cpOffset evaluates it in place as the reference does.
+    float ld2x = 0.0f, ld2y = 0.0f;
 };
+
+// An RGBA8 texel component as texture() returns it: c / 255.0f, without the division.  With r = fl(1 / 255) the product c * r is within an ulp of the
+// quotient; one Newton step on the residual e = c - 255 q (exact in the fused multiply-add) lands on the correctly rounded quotient for every code
+// 0 .. 255 (all 256 checked against the division: tests/test_shading_divisions_host.py, tests/test_gpu_shading_divisions.py).  The plain product differs for 126 codes.
+RT_HOST_DEV float texel_unorm8(uint8_t code) {
+    const float c = (float)code, r = 1.0f / 255.0f;
+    float q = c * r;
+    const float e = __builtin_fmaf(-255.0f, q, c);
+    return __builtin_fmaf(e, r, q);
+}
+RT_DEV V3 texel_unorm8x3(uchar4 c) { return mk3(texel_unorm8(c.x), texel_unorm8(c.y), texel_unorm8(c.z)); }
 
 // texture(uEnvMap, dir): face selection per the GL cube-map table, LINEAR, CLAMP_TO_EDGE, not seamless.
 template <bool COUNT>
@@ -341,10 +356,7 @@ RT_DEV V3 texture_cube(const DevScene &sc, V3 d, Work &w) {
     j0 = min(max(j0, 0), N - 1); j1 = min(max(j1, 0), N - 1);
     const uchar4 *F = sc.env + (size_t)face * N * N;
     uchar4 c00 = F[(size_t)j0 * N + i0], c10 = F[(size_t)j0 * N + i1], c01 = F[(size_t)j1 * N + i0], c11 = F[(size_t)j1 * N + i1];
-    V3 t00 = mk3((float)c00.x / 255.0f, (float)c00.y / 255.0f, (float)c00.z / 255.0f);
-    V3 t10 = mk3((float)c10.x / 255.0f, (float)c10.y / 255.0f, (float)c10.z / 255.0f);
-    V3 t01 = mk3((float)c01.x / 255.0f, (float)c01.y / 255.0f, (float)c01.z / 255.0f);
-    V3 t11 = mk3((float)c11.x / 255.0f, (float)c11.y / 255.0f, (float)c11.z / 255.0f);
+    V3 t00 = texel_unorm8x3(c00), t10 = texel_unorm8x3(c10), t01 = texel_unorm8x3(c01), t11 = texel_unorm8x3(c11);
     float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
     return t00 * w00 + t10 * w10 + t01 * w01 + t11 * w11;
 }
@@ -404,6 +416,15 @@ RT_DEV V2 cpOffset(float px, float py, int frame) {   // :280-289
     float lx = halton(frame + 1, 2), ly = halton(frame + 1, 3);   // ld2(frame), rt_common.glsl:127-129
     return mk2(fractr(hx + lx), fractr(hy + ly));
 }
+RT_DEV V2 cpOffsetLd2(const Frag &F) {   // the same with ld2(frame) from the fragment (Frag::ld2x, ld2y)
+    float hx = randr(F.fcx, F.fcy, (int)((uint32_t)F.frameIndex * 911u));
+    float hy = randr(F.fcy, F.fcx, (int)((uint32_t)F.frameIndex * 577u));
+    return mk2(fractr(hx + F.ld2x), fractr(hy + F.ld2y));
+}
+// A tracer policy whose fragments carry ld2 says so with  static constexpr bool kFrameLd2 = true  (the wavefront stages: load_hit fills it from the frame
+// descriptor); for every other tracer directLightBVH evaluates the halton pair in place.
+template <class T, class = void> struct tracer_has_ld2 { static constexpr bool value = false; };
+template <class T> struct tracer_has_ld2<T, decltype((void)T::kFrameLd2)> { static constexpr bool value = T::kFrameLd2; };
 RT_DEV V3 kLightN() { return normalize(mk3(0.0f, -1.0f, 0.2f)); }   // :30
 RT_DEV void lightFrame(V3 &t, V3 &b) {   // :355-357
     V3 n = kLightN();
@@ -483,7 +504,9 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
     } else {
         V3 lt, lb;
         lightFrame(lt, lb);
-        V2 rot = cpOffset(F.fcx, F.fcy, F.frameIndex);
+        V2 rot;
+        if constexpr (tracer_has_ld2<T>::value) rot = cpOffsetLd2(F);
+        else rot = cpOffset(F.fcx, F.fcy, F.frameIndex);
         for (int i = 0; i < 4; ++i) {   // SOFT_SHADOW_SAMPLES
             DiskSample s = diskSample(F, hp, N, frame, i, rot, lt, lb);
             float vis = tr.shadow(seg, i, s.ro, s.rd, s.tMax, s.geom != 0.0f) ? 0.0f : 1.0f;

@@ -20,13 +20,42 @@
 namespace rtd {
 
 #define RT_MAX_BATCH 16
+constexpr int kTileRowShift = 11;   // the tile deal's row shift, see the header comment
 struct FrameGeom {
     int W, H, tilesX, tilesY, nTiles, rank, world, nLocalTiles;
     // Frame batching (rt_render_frames): `batch` consecutive frames of a static camera share one set of launches.  The kernels see
     // batch x nLocalTiles "local tiles": local tile index lt' = k * nLocalTiles + lt is tile lt of the batch's k-th frame, and pixel
     // slots follow (slot' = lt' * 256 + tid).  batch == 1 is the plain single frame.
     int batch;
+    // Reciprocals of the three run-time divisors of the slot <-> pixel arithmetic below (frame_geom_set_reciprocals): max(nLocalTiles, 1), tilesX, world.
+    // 0 = "divide as before": what a zero-filled descriptor and any FrameGeom nobody prepared carry.
+    uint32_t rcpLocalTiles = 0, rcpTilesX = 0, rcpWorld = 0;
 };
+
+// n / d as one multiply-high (the style of DevScene::leafBoxMagic).  M = floor(2^32 / d) + 1 gives M d = 2^32 + e with 0 < e <= d, so
+//     n M / 2^32 = n / d + n e / (d 2^32),
+// and the second term cannot carry the quotient to the next integer while n e < 2^32 (the fractional part of n / d is at most (d - 1) / d).  Hence
+// umulhi(n, M) == n / d for every n <= nMax when  d >= 2  and  nMax * d < 2^32.  (d == 1 would need M = 2^32 + 1.)  Otherwise the host stores 0 and
+// the device divides.
+RT_HOST_DEV uint32_t div_reciprocal(uint32_t d, uint64_t nMax) {
+    return (d >= 2u && nMax * (uint64_t)d < (1ull << 32)) ? (uint32_t)((1ull << 32) / d) + 1u : 0u;
+}
+RT_HOST_DEV uint32_t div_by(uint32_t n, uint32_t d, uint32_t rcp) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return rcp ? __umulhi(n, rcp) : n / d;
+#else
+    return rcp ? (uint32_t)(((uint64_t)n * rcp) >> 32) : n / d;
+#endif
+}
+// The largest dividends the kernels form:  a local tile index of a batch, lt' < nLocalTiles * batch (pixel_of_slot checks that bound before it divides, the
+// other callers pass slots of live pixels);  a global tile index t < nTiles, or 11 * ty with ty < tilesY (tile_row_shift), for tilesX;  t < nTiles for world.
+inline void frame_geom_set_reciprocals(FrameGeom &g) {
+    const uint32_t nl = (uint32_t)(g.nLocalTiles > 1 ? g.nLocalTiles : 1), b = (uint32_t)(g.batch > 1 ? g.batch : 1);
+    const uint64_t tMax = (uint64_t)(g.nTiles > 0 ? g.nTiles - 1 : 0), sMax = (uint64_t)kTileRowShift * (uint64_t)(g.tilesY > 0 ? g.tilesY - 1 : 0);
+    g.rcpLocalTiles = div_reciprocal(nl, (uint64_t)nl * b - 1u);
+    g.rcpTilesX = div_reciprocal((uint32_t)g.tilesX, tMax > sMax ? tMax : sMax);
+    g.rcpWorld = div_reciprocal((uint32_t)g.world, tMax);
+}
 
 struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it through scalar loads
     RtUniforms u;
@@ -34,6 +63,7 @@ struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it thr
     FrameGeom g;
     int giBounces;  // EXTENSION (rt_set_extension): bounces of the analytic / hybrid GI path, 1 = the reference
     float jitterK[RT_MAX_BATCH][2];   // uJitter of the batch's frames (frame k has uFrameIndex = u.frameIndex + k); [0] == u.jitter
+    float ld2K[RT_MAX_BATCH][2];      // ld2(u.frameIndex + k) = (halton(u.frameIndex + k + 1, 2), halton(.., 3)) of the batch's frames: cpOffset's frame-wide term (Frag::ld2x)
 };
 
 struct Targets {
@@ -46,20 +76,32 @@ struct Targets {
     uint2 *gnrm;         // COLOR3 RGBA16F
 };
 
-RT_DEV int sub_frame_of_tile(const FrameGeom &g, int localTile) { return g.batch > 1 ? localTile / max(g.nLocalTiles, 1) : 0; }
-RT_DEV int sub_frame_of_slot(const FrameGeom &g, uint32_t slot) { return sub_frame_of_tile(g, (int)(slot >> 8)); }
-// the tile deal: global tile index of tile (tx, ty) and back.  Row ty's tiles are numbered from column rowShift on (see the header comment).
-constexpr int kTileRowShift = 11;
-__host__ __device__ inline int tile_row_shift(const FrameGeom &g, int ty) { return g.world > 1 ? (ty * kTileRowShift) % g.tilesX : 0; }
-__host__ __device__ inline int tile_index(const FrameGeom &g, int tx, int ty) { return ty * g.tilesX + (tx + tile_row_shift(g, ty)) % g.tilesX; }
-__host__ __device__ inline void tile_xy(const FrameGeom &g, int t, int &tx, int &ty) {
-    ty = t / g.tilesX;
-    tx = (t % g.tilesX + g.tilesX - tile_row_shift(g, ty)) % g.tilesX;
+RT_HOST_DEV int sub_frame_of_tile(const FrameGeom &g, int localTile) {
+    return g.batch > 1 ? (int)div_by((uint32_t)localTile, (uint32_t)(g.nLocalTiles > 1 ? g.nLocalTiles : 1), g.rcpLocalTiles) : 0;
 }
-RT_DEV bool pixel_of_slot(const FrameGeom &g, int localTile, int tid, int &x, int &y) {
+RT_HOST_DEV int sub_frame_of_slot(const FrameGeom &g, uint32_t slot) { return sub_frame_of_tile(g, (int)(slot >> 8)); }
+// the tile deal: global tile index of tile (tx, ty) and back.  Row ty's tiles are numbered from column rowShift on (see the header comment).
+// (a sum of two column numbers below tilesX is reduced by one conditional subtraction: the value of the reference's "% tilesX")
+RT_HOST_DEV int tile_row_shift(const FrameGeom &g, int ty) {
+    if (!(g.world > 1)) return 0;
+    const uint32_t n = (uint32_t)(ty * kTileRowShift);
+    return (int)(n - div_by(n, (uint32_t)g.tilesX, g.rcpTilesX) * (uint32_t)g.tilesX);
+}
+RT_HOST_DEV int tile_index(const FrameGeom &g, int tx, int ty) {   // 0 <= tx < tilesX, 0 <= ty < tilesY: a tile of the frame
+    const int c = tx + tile_row_shift(g, ty);
+    return ty * g.tilesX + (c >= g.tilesX ? c - g.tilesX : c);
+}
+RT_HOST_DEV void tile_xy(const FrameGeom &g, int t, int &tx, int &ty) {
+    ty = (int)div_by((uint32_t)t, (uint32_t)g.tilesX, g.rcpTilesX);
+    const int c = t - ty * g.tilesX;                        // t % tilesX
+    if (!(g.world > 1)) { tx = c; return; }                 // rowShift == 0
+    const int v = c + g.tilesX - tile_row_shift(g, ty);     // in [1, 2 tilesX)
+    tx = v >= g.tilesX ? v - g.tilesX : v;
+}
+RT_HOST_DEV bool pixel_of_slot(const FrameGeom &g, int localTile, int tid, int &x, int &y) {
     if (g.batch > 1) {
         if (localTile >= g.nLocalTiles * g.batch) { x = y = 0; return false; }
-        localTile %= max(g.nLocalTiles, 1);
+        localTile -= sub_frame_of_tile(g, localTile) * (g.nLocalTiles > 1 ? g.nLocalTiles : 1);   // localTile % max(nLocalTiles, 1)
     }
     int t = localTile * g.world + g.rank;
     if (t >= g.nTiles) { x = y = 0; return false; }   // padding of the last local tile row of this rank
@@ -70,14 +112,46 @@ RT_DEV bool pixel_of_slot(const FrameGeom &g, int localTile, int tid, int &x, in
     y = ty * 16 + (q >> 1) * 8 + (lane >> 3);
     return t < g.nTiles && x < g.W && y < g.H;
 }
+// The same two functions as they were before the reciprocals, for the ray sources of the traversal kernels (PrimarySrc::take): those kernels sit at a
+// balance point that seventeen rounds of measurements found and keep their code.
+RT_DEV int sub_frame_of_slot_div(const FrameGeom &g, uint32_t slot) { return g.batch > 1 ? (int)(slot >> 8) / max(g.nLocalTiles, 1) : 0; }
+RT_DEV bool pixel_of_slot_div(const FrameGeom &g, int localTile, int tid, int &x, int &y) {
+    if (g.batch > 1) {
+        if (localTile >= g.nLocalTiles * g.batch) { x = y = 0; return false; }
+        localTile %= max(g.nLocalTiles, 1);
+    }
+    int t = localTile * g.world + g.rank;
+    if (t >= g.nTiles) { x = y = 0; return false; }
+    int ty = t / g.tilesX;
+    int shift = g.world > 1 ? (ty * kTileRowShift) % g.tilesX : 0;
+    int tx = (t % g.tilesX + g.tilesX - shift) % g.tilesX;
+    int q = tid >> 6, lane = tid & 63;
+    x = tx * 16 + (q & 1) * 8 + (lane & 7);
+    y = ty * 16 + (q >> 1) * 8 + (lane >> 3);
+    return t < g.nTiles && x < g.W && y < g.H;
+}
 // slot of pixel (x,y) if this rank owns it, else -1
 RT_DEV int slot_of_pixel(const FrameGeom &g, int x, int y) {
     int tx = x >> 4, ty = y >> 4;
     int t = tile_index(g, tx, ty);
-    if (t % g.world != g.rank) return -1;
+    const int local = (int)div_by((uint32_t)t, (uint32_t)g.world, g.rcpWorld);
+    if (t - local * g.world != g.rank) return -1;   // t % world
     int lx = x & 15, ly = y & 15;
     int q = (lx >> 3) | ((ly >> 3) << 1);
-    return (t / g.world) * 256 + q * 64 + (ly & 7) * 8 + (lx & 7);
+    return local * 256 + q * 64 + (ly & 7) * 8 + (lx & 7);
+}
+
+// thread index -> (sample s, hit j) of the generators, s-major: s = tid / live, j = tid % live for tid < live * SPP, without the two integer divisions.
+// s < SPP is small, so the quotient is taken from a one-instruction reciprocal estimate and corrected: tid and live are below 2^31 (rt_wave_render refuses
+// chunks of 2^31 queue entries), every step (two conversions, v_rcp_f32 at 1 ulp, one product) is within 2^-22 of exact, so the estimate misses tid / live
+// by less than SPP * 2^-21 and its floor by at most one either way while SPP <= 4096.  A larger SPP divides.
+RT_DEV void sample_and_hit(uint32_t tid, uint32_t live, int spp, int &s, uint32_t &j) {
+    if (spp > 4096) { s = (int)(tid / live); j = tid % live; return; }
+    uint32_t q = (uint32_t)((float)tid * __builtin_amdgcn_rcpf((float)live));
+    if (q * live > tid) q -= 1u;          // ((q + 1) * live < 2^32: no wrap)
+    uint32_t r = tid - q * live;
+    if (r >= live) { q += 1u; r -= live; }
+    s = (int)q; j = r;
 }
 
 RT_DEV uint2 pack_half4(V4 v) {
@@ -98,7 +172,8 @@ RT_DEV int slot_in_gathered(const FrameGeom &g, int x, int y, int blockSlots) {
     int t = tile_index(g, tx, ty);
     int lx = x & 15, ly = y & 15;
     int q = (lx >> 3) | ((ly >> 3) << 1);
-    return (t % g.world) * blockSlots + (t / g.world) * 256 + q * 64 + (ly & 7) * 8 + (lx & 7);
+    const int local = (int)div_by((uint32_t)t, (uint32_t)g.world, g.rcpWorld);
+    return (t - local * g.world) * blockSlots + local * 256 + q * 64 + (ly & 7) * 8 + (lx & 7);
 }
 
 // History access for resolveTAA (rt_taa.glsl:87,128): NEAREST, CLAMP_TO_EDGE.

@@ -282,9 +282,9 @@ struct PrimarySrc {   // ray i = primary ray of candidate i
     RT_DEV void take(uint32_t i, const Payload &p, V3 &ro, V3 &rd, uint32_t &token) const {
         token = i;
         int px, py;
-        slot_to_pixel(fr->g, p.slot, px, py);
+        pixel_of_slot_div(fr->g, (int)(p.slot >> 8), (int)(p.slot & 255u), px, py);   // (the traversal kernels keep the dividing form, rt_frame.hpp)
         ro = ld3(fr->u.camPos);
-        rd = primaryDirK(fr, sub_frame_of_slot(fr->g, p.slot), px, py);
+        rd = primaryDirK(fr, sub_frame_of_slot_div(fr->g, p.slot), px, py);
     }
     RT_DEV void store_closest(uint32_t i, float t, int tri) const { if (tri >= 0) { outT[i] = t; outTri[i] = tri; } }   // misses are pre-filled, see above
     RT_DEV void store_any(uint32_t, bool) const {}
@@ -1632,6 +1632,7 @@ RT_DEV void disk_stat_add(unsigned long long *stat, bool unlit, bool skipped) {
 
 struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
     static constexpr bool kSkipUnlitDisk = true;
+    static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     unsigned long long *stat;
     RT_DEV void disk_stat(int, bool unlit, bool skipped) { if (stat) disk_stat_add(stat, unlit, skipped); }
     WaveBuf wb;
@@ -1671,6 +1672,7 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
 };
 struct GenGiTracer {       // reads the bounce result, records the shadow rays at the bounce hit
     static constexpr bool kSkipUnlitDisk = true;
+    static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     unsigned long long *stat;
     RT_DEV void disk_stat(int, bool unlit, bool skipped) { if (stat) disk_stat_add(stat + 5, unlit, skipped); }
     WaveBuf wb;
@@ -1704,6 +1706,7 @@ struct GenGiTracer {       // reads the bounce result, records the shadow rays a
 };
 struct CombineTracer {     // reads everything
     static constexpr bool kSkipUnlitDisk = true;
+    static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
@@ -1734,6 +1737,7 @@ RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
     c.F.u = &fr->u; c.F.sc = &fr->sc; c.F.fcx = (float)c.px + 0.5f; c.F.fcy = (float)c.py + 0.5f;
     const int k = sub_frame_of_slot(fr->g, h.slot);
     c.F.frameIndex = fr->u.frameIndex + k;
+    c.F.ld2x = fr->ld2K[k][0]; c.F.ld2y = fr->ld2K[k][1];   // cpOffset's halton pair, once per sub-frame on the host
     c.dir = primaryDirK(fr, k, c.px, c.py);
     c.hp = ld3(fr->u.camPos) + c.dir * h.t;
     c.hn = tri_normal(fr->sc, h.tri);
@@ -1750,8 +1754,9 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
     const bool mine = live != 0 && tid < live * (uint32_t)wb.SPP;
     if (!mine && (!wb.giPerm || live == 0 || blockIdx.x * 256u >= live * (uint32_t)wb.SPP)) return;   // (the sort below needs whole workgroups)
-    const int s = mine ? (int)(tid / live) : 0;
-    const uint32_t j = mine ? tid % live : 0;
+    int s = 0;
+    uint32_t j = 0;
+    if (mine) sample_and_hit(tid, live, wb.SPP, s, j);
     GenDirectTracer tr;
     tr.wb = wb; tr.j = j; tr.s = s; tr.shadowMask = 0; tr.giCast = false; tr.stat = diskStat;
     tr.giRo = mk3(0.0f); tr.giRd = mk3(0.0f);
@@ -1813,8 +1818,9 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
     const bool mine = live != 0 && tid < live * (uint32_t)wb.SPP;
-    const int s = mine ? (int)(tid / live) : 0;
-    const uint32_t j = mine ? tid % live : 0;
+    int s = 0;
+    uint32_t j = 0;
+    if (mine) sample_and_hit(tid, live, wb.SPP, s, j);
     const uint32_t a = (uint32_t)s * wb.CH + j;
     const uint32_t ae = mine ? wb.gi_entry(s, j) : 0u;   // where this (hit, sample)'s bounce ray and its answer are
     const bool bounced = mine && wb.giD[ae].w >= 0.0f && wb.giTri[ae] >= 0;
@@ -1875,6 +1881,7 @@ __global__ __launch_bounds__(256) void k_gen_gi_listed(const DevFrame *__restric
 // there and may hold an earlier launch set's value.
 struct GenGiOverflowTracer {
     static constexpr bool kSkipUnlitDisk = true;
+    static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;

@@ -683,15 +683,55 @@ int rt_mesh_skin_upload(RtContext *ctx, const float *rest, const uint16_t *boneI
  * RT_ERR_INVALID.  Bone matrices are not inspected, as the part matrices are not.  RT_ERR_INVALID without a skin. */
 int rt_mesh_bones(RtContext *ctx, void **devPtr, size_t *bytes);
 int rt_mesh_set_bones(RtContext *ctx, int first, int count, const float *M16s);
-/* The device array of rest positions (nVerts x 3 floats): a caller applies morph targets by writing it, ordered on rt_stream()'s stream, before a
- * skin.  RT_ERR_INVALID without a skin. */
+/* The device array of rest positions (nVerts x 3 floats) the skin reads.  rt_mesh_morph(ctx, RT_MORPH_TO_REST) blends morph targets into it (below);
+ * a caller with a deformer of its own writes it, ordered on rt_stream()'s stream, before a skin.  RT_ERR_INVALID without a skin. */
 int rt_mesh_rest_positions(RtContext *ctx, void **devPtr, size_t *bytes);
 /* Enqueues positions := skin(rest, tables, bone table) on rt_stream()'s stream, reading the bone table as it stands when the kernel runs.  Ordered as
  * the update calls are: after the frames, queries and bound raster draws already enqueued on any lane, before whatever is enqueued next, by events --
  * so rt_mesh_set_bones, rt_mesh_skin, the update calls, frames and queries take effect in call order wherever frames have moved rt_stream().  No
  * allocation, no host wait (RtMeshInfo.hostSyncs does not move).  RT_ERR_INVALID without a mesh or without a skin. */
 int rt_mesh_skin(RtContext *ctx);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload and rt_mesh_skin_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- morph targets: sparse per-vertex deltas blended on the device under a table of weights, the first stage of
+ * weights -> morph -> bones -> skin -> rt_mesh_update -> frame, raster preview, picking; a face rig or a corrective-shape rig needs no kernel of the
+ * host's own and no host round trip per step.
+ * Targets are given the way parts are: targetFirst holds nTargets + 1 non-decreasing entry numbers from 0 to nEntries; entry e of target t
+ * (targetFirst[t] <= e < targetFirst[t+1]) moves vertex vertIdx[e] by deltas[3e .. 3e+2].  Empty targets are legal, and a target may name a vertex more
+ * than once.  The result is
+ *   dst[v] = base[v] + the terms weight[t] * delta of the entries that name v, added one by one in input order,
+ * evaluated exactly as rt_morph_positions (host side, below) defines it, bit for bit; an entry whose weight is +-0 is skipped, and a vertex without
+ * any other keeps its base position.  1 <= nTargets <= RT_MAX_MORPH_TARGETS.  The device reads the entries in a packed form, slices of 64 vertices
+ * padded to their longest entry list (rt_debug_morph_pack, below); RtMorphInfo says what it costs. */
+#define RT_MAX_MORPH_TARGETS 65536
+/* nSlices: slices of 64 vertices; maxPerVertex: the longest entry list of a vertex; entries: as given; paddedEntries: 16-byte records on the device;
+ * bytes: device bytes of the morph's four arrays (records, slice table, base, weight table). */
+typedef struct RtMorphInfo { int32_t nVerts, nTargets, nSlices, maxPerVertex; uint64_t entries, paddedEntries, bytes; } RtMorphInfo;
+/* The morph targets of the current mesh: base positions (nVerts x 3 floats of the current mesh; NULL: a device-to-device snapshot, as it stands after
+ * everything enqueued, of the rest array when the mesh has a skin, else of rt_mesh_positions()) and the targets, validated as rt_morph_positions
+ * validates them: a null array, nTargets outside 1 .. RT_MAX_MORPH_TARGETS, a broken targetFirst, a vertIdx >= nVerts or a non-finite delta is
+ * RT_ERR_INVALID, with a message; RT_ERR_UNSUPPORTED when the packed form would reach 2^31 records.  Waits for every lane, packs on the host,
+ * allocates the base array, the slice table, the records and the weight table (nTargets floats, all zero) and uploads them; RtMeshInfo.allocations and
+ * scratchBytes count them.  May synchronise and allocate; the only call of this group that may.  nTargets == 0 releases the morph (the arrays may
+ * then be NULL).  A second upload replaces the first.  RT_ERR_INVALID without a mesh; rt_mesh_upload, rt_mesh_upload_parts and rt_upload_bvh
+ * release the morph with the mesh; uploading or releasing a skin does not touch it.  No tree is needed. */
+int rt_mesh_morph_upload(RtContext *ctx, const float *base, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets);
+/* The base array (nVerts x 3 floats) and the weight table (nTargets floats, zero after the upload) on the device, for a caller that writes them
+ * there; writes must be ordered on rt_stream()'s stream, exactly as for rt_mesh_bones.  rt_mesh_set_morph_weights: `count` weights from host memory
+ * into entries first .., copied on that stream, ordered after the work already enqueued on every frame lane and before whatever a lane is given
+ * next; a range outside the table: RT_ERR_INVALID.  Weights are not inspected, as bone matrices are not.  RT_ERR_INVALID without a morph. */
+int rt_mesh_morph_base(RtContext *ctx, void **devPtr, size_t *bytes);
+int rt_mesh_morph_weights(RtContext *ctx, void **devPtr, size_t *bytes);
+int rt_mesh_set_morph_weights(RtContext *ctx, int first, int count, const float *weights);
+/* Enqueues dst := morph(base, targets, weight table) on rt_stream()'s stream, reading the weight table as it stands when the kernel runs.  Ordered as
+ * rt_mesh_skin is, by events, so rt_mesh_set_morph_weights, rt_mesh_morph, rt_mesh_set_bones, rt_mesh_skin, the update calls, frames and queries
+ * take effect in call order wherever frames have moved rt_stream(); a morph to the positions also waits for the bound raster draws already
+ * enqueued.  No allocation, no host wait (RtMeshInfo.hostSyncs does not move).  RT_ERR_INVALID without a mesh, without a morph, for an unknown dst or
+ * for RT_MORPH_TO_REST without a skin. */
+#define RT_MORPH_TO_POSITIONS 0   /* writes rt_mesh_positions() */
+#define RT_MORPH_TO_REST      1   /* writes rt_mesh_rest_positions(): follow with rt_mesh_skin; RT_ERR_INVALID without a skin */
+int rt_mesh_morph(RtContext *ctx, int dst);
+/* What the current morph holds.  RT_ERR_INVALID without a morph. */
+int rt_mesh_morph_info(RtContext *ctx, RtMorphInfo *out);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload and rt_mesh_morph_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -726,6 +766,15 @@ typedef struct RtPackInfo {
 } RtPackInfo;
 enum { RT_SCENE_ARRAY_PACK_INFO = 100 };
 int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, int nTris, const RtPackOptions *opt, int which, void *dst, size_t capacity,
+                        size_t *bytes);
+/* Diagnostics, host side (no GPU needed, no context): what rt_mesh_morph_upload would put on the device for these targets -- the packer of
+ * csrc/rt_morph_pack.cpp run and one array handed out, with rt_debug_pack_scene's size-query convention.  Slice s holds vertices
+ * 64s .. 64s+63 and as many rows as the longest entry list among them; RT_MORPH_ARRAY_SLICE_FIRST: nSlices + 1 uint32 prefix sums of the rows;
+ * RT_MORPH_ARRAY_ENTRIES: sliceFirst[nSlices] * 64 records of 16 bytes {dx, dy, dz (float bits), target (uint32)}, record (sliceFirst[s] + k) * 64 + l
+ * the k-th entry of vertex 64s + l in input order, or the pad record {+0, +0, +0, 0xFFFFFFFF} where that vertex has no k-th entry or does not exist;
+ * RT_MORPH_ARRAY_INFO: an RtMorphInfo.  Returns rt_mesh_morph_upload's codes for targets it would refuse. */
+enum { RT_MORPH_ARRAY_SLICE_FIRST = 0, RT_MORPH_ARRAY_ENTRIES = 1, RT_MORPH_ARRAY_INFO = 100 };
+int rt_debug_morph_pack(int nVerts, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets, int which, void *dst, size_t capacity,
                         size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): the ray-queue plan of one launch set of the wavefront pipeline (csrc/rt_wave_plan.cpp,
  * DESIGN.md 16) -- the arithmetic rt_render_frame(s) follows, for checks.  RtWaveOptions: every environment variable of frame rendering as a lane reads it
@@ -818,6 +867,15 @@ int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t
  * transform of the point.  out (nVerts x 3 floats) may be rest.  RT_ERR_INVALID: a null array, nVerts <= 0, nBones outside 1 .. RT_MAX_MESH_BONES, any
  * of the four indices of a vertex >= nBones whatever its weight, a non-finite weight.  Bone matrices are not inspected. */
 int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, const float *weights4, const float *bones16, int nBones, float *out);
+
+/* Morph-target blending on host arrays, and the definition rt_mesh_morph is tested against (see rt_mesh_morph_upload for the arrays; weights holds
+ * nTargets floats).  For vertex v, acc = base[v]; the entries that name v are visited in input order (ascending target, then position within the
+ * target); with w = weights[t], an entry whose w is +0 or -0 is skipped, otherwise per component acc = acc + w * d: fp32, a rounded product and a
+ * rounded sum, nothing fused.  A vertex with no unskipped entry keeps its base bits (-0 stays -0).  out (nVerts x 3 floats) may be base.
+ * RT_ERR_INVALID: a null array, nVerts <= 0, nTargets outside 1 .. RT_MAX_MORPH_TARGETS, a targetFirst that does not start at 0 or decreases, a
+ * vertIdx >= nVerts, a non-finite delta.  base and weights are not inspected. */
+int rt_morph_positions(const float *base, int nVerts, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets, const float *weights,
+                       float *out);
 
 /* build_bvh (include/scene/bvh.h:102, src/scene/bvh.cpp:94-137) + the packing half of upload_bvh_tbo
  * (:147-204).  nodes12 needs room for 2*nTris*12 floats, tris12 for nTris*12.  Returns the node count. */

@@ -167,6 +167,10 @@ class RtMeshInfo(_Struct):   # rt_get_mesh_info: the dynamic mesh and what its r
     _fields_ = [("nVerts", i32), ("nTris", i32)] + [(n, C.c_uint64) for n in ("rebuilds", "allocations", "hostSyncs", "scratchBytes", "sceneBytes")]
 
 
+class RtMorphInfo(_Struct):   # rt_mesh_morph_info / rt_debug_morph_pack: the morph targets in their packed form
+    _fields_ = [(n, i32) for n in ("nVerts", "nTargets", "nSlices", "maxPerVertex")] + [(n, C.c_uint64) for n in ("entries", "paddedEntries", "bytes")]
+
+
 class RtBvhCost(_Struct):   # rt_bvh_cost: the quality metric of a tree
     _fields_ = [("innerQ", C.c_uint64), ("leafQ", C.c_uint64)] + [(n, C.c_double) for n in ("rootArea", "inner", "leaf", "cost")] + \
                [(n, i32) for n in ("rootExp", "degenerate", "nInner", "nLeaves")]
@@ -217,6 +221,10 @@ class RtPresentParams(_Struct):  # uniforms of shaders/rt/rt_present.frag:38-50
 RT_MAX_RASTER_MESHES = 8
 RT_MAX_MESH_PARTS = 65535   # rt_mesh_upload_parts
 RT_SKIN_INFLUENCES, RT_MAX_MESH_BONES = 4, 65536   # rt_mesh_skin_upload
+RT_MAX_MORPH_TARGETS = 65536   # rt_mesh_morph_upload
+RT_MORPH_TO_POSITIONS, RT_MORPH_TO_REST = 0, 1   # rt_mesh_morph
+RT_MORPH_ARRAY_SLICE_FIRST, RT_MORPH_ARRAY_ENTRIES, RT_MORPH_ARRAY_INFO = 0, 1, 100   # rt_debug_morph_pack
+MORPH_PAD_TARGET = 0xFFFFFFFF   # target of a pad record of the packed entries
 RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
 RT_RASTER_BIND_SINGLE, RT_RASTER_BIND_PARTS = 0, 1   # rt_raster_mesh_dynamic
 
@@ -348,6 +356,12 @@ SIGNATURES = {
     "rt_mesh_set_bones": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _FP]),
     "rt_mesh_rest_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_mesh_skin": (C.c_int, [C.c_void_p]),
+    "rt_mesh_morph_upload": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32), _U32P, _FP, C.c_int]),
+    "rt_mesh_morph_base": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_morph_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_morph_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _FP]),
+    "rt_mesh_morph": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_mesh_morph_info": (C.c_int, [C.c_void_p, C.POINTER(RtMorphInfo)]),
     "rt_get_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(RtMeshInfo)]),
     "rt_debug_read_scene": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_default_render_params": (None, [C.POINTER(RtRenderParams)]),
@@ -363,12 +377,14 @@ SIGNATURES = {
     "rt_gather_triangles_checked": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, _FP, _FP]),
     "rt_gather_triangles_parts": (C.c_int, [_FP, C.c_int, _U32P, C.c_int, C.POINTER(C.c_int32), C.c_int, _FP, _FP]),
     "rt_skin_positions": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_uint16), _FP, _FP, C.c_int, _FP]),
+    "rt_morph_positions": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, _FP, _FP]),
     "rt_build_bvh": (C.c_int, [_FP, C.c_int, _FP, _FP]),
     "rt_build_bvh_order": (C.c_int, [_FP, C.c_int, _FP, _FP, C.POINTER(C.c_int32)]),
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
     "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
     "rt_debug_wave_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),   # RtWaveOptions, RtWavePlan: _wave_plan_types
     "rt_debug_pack_scene": (C.c_int, [_FP, C.c_int, _FP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rt_debug_morph_pack": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_debug_texel_unorm8": (C.c_int, [_FP]),
     "rt_debug_halton_pairs": (C.c_int, [C.c_int, C.c_int, _FP]),
     "rt_debug_div_reciprocal": (C.c_uint32, [C.c_uint32, C.c_uint64]),
@@ -603,6 +619,73 @@ def skin_positions(rest, bone_idx, weights, bones) -> np.ndarray:
     if rc != RT_OK:
         raise RtError(rc, "rt_skin_positions: no vertices, a bone count outside 1 .. 65536, a bone index out of range or a weight that is not finite")
     return out
+
+
+def _morph_targets(who, target_first, vert_idx, deltas):
+    """target_first / vert_idx / deltas as contiguous int32 [T+1] / uint32 [E] / float32 [E,3]; what a cast would hide is refused here, and so is a
+    table whose last entry is not the number of entries given, which the library could only take on trust."""
+    tf, vi = np.asarray(target_first), np.asarray(vert_idx)
+    if tf.ndim != 1 or tf.size < 1 or tf.size - 1 > RT_MAX_MORPH_TARGETS:
+        raise RtError(RT_ERR_INVALID, f"{who}: target_first must hold 1 .. {RT_MAX_MORPH_TARGETS} targets' boundaries and the end")
+    if tf.min() < 0 or tf.max() >= 2 ** 31 or (vi.size and (vi.min() < 0 or vi.max() >= 2 ** 32)):
+        raise RtError(RT_ERR_INVALID, f"{who}: target_first must fit int32 and vert_idx uint32")
+    d = _f32(deltas).reshape(-1, 3)
+    if int(tf[-1]) != vi.size or d.shape[0] != vi.size:
+        raise RtError(RT_ERR_INVALID, f"{who}: target_first ends at {int(tf[-1])}, with {vi.size} vertex indices and {d.shape[0]} deltas")
+    return np.ascontiguousarray(tf, dtype=np.int32), np.ascontiguousarray(vi, dtype=np.uint32).reshape(-1), d
+
+
+_I32P = C.POINTER(C.c_int32)
+
+
+def morph_positions(base, target_first, vert_idx, deltas, weights) -> np.ndarray:
+    """Morph-target blending on the host (rt_morph_positions), the definition Renderer.mesh_morph is tested against: base [V,3]; target t owns entries
+    target_first[t] .. target_first[t+1], entry e moves vertex vert_idx[e] by weights[t] * deltas[e]; the terms are added to the base one by one in
+    input order -> positions [V,3] float32.  An entry of weight +-0 is skipped; a vertex without any other keeps its base position."""
+    p = _f32(base).reshape(-1, 3)
+    tf, vi, d = _morph_targets("morph_positions", target_first, vert_idx, deltas)
+    w = _f32(weights).reshape(-1)
+    if w.size != tf.size - 1:
+        raise RtError(RT_ERR_INVALID, f"morph_positions: {tf.size - 1} targets, {w.size} weights")
+    out = np.zeros_like(p)
+    rc = lib().rt_morph_positions(_fp(p), p.shape[0], tf.ctypes.data_as(_I32P), vi.ctypes.data_as(_U32P), _fp(d), tf.size - 1, _fp(w), _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_morph_positions: no vertices, no targets, a broken target_first, a vertex index out of range or a delta that is not finite")
+    return out
+
+
+def morph_targets_from_dense(deltas):
+    """Dense targets [T,V,3] -> (target_first int32 [T+1], vert_idx uint32 [E], deltas float32 [E,3]), the sparse form morph_positions and
+    Renderer.mesh_morph_upload take: per target its vertices in ascending order, without the rows whose three components are all +-0."""
+    d = _f32(deltas)
+    if d.ndim != 3 or d.shape[2] != 3:
+        raise RtError(RT_ERR_INVALID, "morph_targets_from_dense: deltas must be [targets, vertices, 3]")
+    keep = (d != 0).any(axis=2)
+    t, v = np.nonzero(keep)   # row-major: ascending target, then ascending vertex
+    first = np.zeros(d.shape[0] + 1, dtype=np.int32)
+    np.cumsum(keep.sum(axis=1), out=first[1:])
+    return first, v.astype(np.uint32), np.ascontiguousarray(d[t, v])
+
+
+def debug_morph_pack(n_verts, target_first, vert_idx, deltas) -> dict:
+    """What Renderer.mesh_morph_upload would put on the device, without one (rt_debug_morph_pack): "slice_first" uint32 [nSlices+1], "entries" uint32
+    [paddedEntries,4] (the delta's float bits and the target; MORPH_PAD_TARGET marks a pad record) and "info", an RtMorphInfo."""
+    tf, vi, d = _morph_targets("debug_morph_pack", target_first, vert_idx, deltas)
+    args = (int(n_verts), tf.ctypes.data_as(_I32P), vi.ctypes.data_as(_U32P), _fp(d), tf.size - 1)
+
+    def read(which):
+        size = C.c_size_t()
+        rc = lib().rt_debug_morph_pack(*args, which, None, 0, C.byref(size))
+        out = np.zeros(size.value, dtype=np.uint8)
+        if rc == RT_OK and size.value:
+            rc = lib().rt_debug_morph_pack(*args, which, C.c_void_p(out.ctypes.data), out.size, C.byref(size))
+        if rc != RT_OK:
+            raise RtError(rc, "rt_debug_morph_pack: targets rt_mesh_morph_upload would refuse" if rc == RT_ERR_INVALID else
+                          "rt_debug_morph_pack: the padded entry records reach 2^31")
+        return out
+
+    info = RtMorphInfo.from_buffer_copy(read(RT_MORPH_ARRAY_INFO).tobytes())
+    return {"info": info, "slice_first": read(RT_MORPH_ARRAY_SLICE_FIRST).view(np.uint32), "entries": read(RT_MORPH_ARRAY_ENTRIES).view(np.uint32).reshape(-1, 4)}
 
 
 def bvh_layout(n_tris: int) -> RtBvhLayout:
@@ -1202,8 +1285,8 @@ class Renderer:
         self._check(lib().rt_mesh_set_bones(self._h, int(first), m.shape[0], _fp(m)))   # pageable memory: staged before the call returns
 
     def mesh_rest_positions(self, as_torch=None):
-        """The device array of rest positions the skin reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes).  A
-        caller applies morph targets by writing it on stream() before mesh_skin."""
+        """The device array of rest positions the skin reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes).
+        mesh_morph(to="rest") blends morph targets into it; a caller with a deformer of its own writes it on stream() before mesh_skin."""
         ptr, n = C.c_void_p(), C.c_size_t()
         self._check(lib().rt_mesh_rest_positions(self._h, C.byref(ptr), C.byref(n)))
         return self._device_view(ptr.value, n.value, 3, as_torch)
@@ -1212,6 +1295,54 @@ class Renderer:
         """Enqueue positions := skin(rest, tables, bone table) on stream() (rt_mesh_skin): what skin_positions computes, bit for bit, under the bone
         table as it stands when the kernel runs.  No host wait, no allocation; follow it with mesh_refit / mesh_rebuild / mesh_update."""
         self._check(lib().rt_mesh_skin(self._h))
+
+    # ---- morph targets (DESIGN.md 14.11): sparse deltas blended on the device under a weight table, before the skin or straight into the positions
+    def mesh_morph_upload(self, target_first, vert_idx, deltas, base=None):
+        """The morph targets of the current mesh (rt_mesh_morph_upload), in morph_positions' sparse form (morph_targets_from_dense makes it from dense
+        deltas); base [V,3] base positions, None: a device-to-device snapshot of the rest array when the mesh has a skin, else of mesh_positions(),
+        as it stands.  Allocates the weight table, all zero.  May synchronise; target_first=None releases the morph."""
+        if target_first is None:
+            self._check(lib().rt_mesh_morph_upload(self._h, None, None, None, None, 0))
+            return
+        nv = getattr(self, "_mesh_verts", 0)
+        tf, vi, d = _morph_targets("mesh_morph_upload", target_first, vert_idx, deltas)
+        b = None if base is None else _f32(base).reshape(-1, 3)
+        if b is not None and b.shape[0] != nv:
+            raise RtError(RT_ERR_INVALID, f"mesh_morph_upload: {b.shape[0]} base positions, the mesh has {nv} vertices")
+        self._check(lib().rt_mesh_morph_upload(self._h, None if b is None else _fp(b), tf.ctypes.data_as(_I32P), vi.ctypes.data_as(_U32P), _fp(d), tf.size - 1))
+
+    def mesh_morph_base(self, as_torch=None):
+        """The device array of base positions the morph reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_morph_base(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 3, as_torch)
+
+    def mesh_morph_weights(self, as_torch=None):
+        """The device table of target weights, zero after the upload.  With torch (as_torch=None: when it imports) a float32 [nTargets,1] tensor that
+        aliases it, zero-copy; writes to it must be ordered on stream(), as for mesh_bones.  Else (pointer, bytes)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_morph_weights(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 1, as_torch)
+
+    def mesh_set_morph_weights(self, weights, first=0):
+        """Weights [count] from host memory into entries first .. of the weight table, copied on stream() in call order with morphs, skins, updates,
+        frames and queries (rt_mesh_set_morph_weights)."""
+        w = _f32(weights).reshape(-1)
+        self._check(lib().rt_mesh_set_morph_weights(self._h, int(first), w.size, _fp(w)))   # pageable memory: staged before the call returns
+
+    def mesh_morph(self, to="positions"):
+        """Enqueue dst := morph(base, targets, weight table) on stream() (rt_mesh_morph): what morph_positions computes, bit for bit, under the weight
+        table as it stands when the kernel runs.  to="positions" writes mesh_positions(): follow it with mesh_refit / mesh_rebuild / mesh_update;
+        to="rest" writes mesh_rest_positions(): follow it with mesh_skin.  No host wait, no allocation."""
+        dst = {"positions": RT_MORPH_TO_POSITIONS, "rest": RT_MORPH_TO_REST}.get(to, to)
+        if not isinstance(dst, int):
+            raise RtError(RT_ERR_INVALID, f"mesh_morph: to={to!r} (\"positions\" or \"rest\")")
+        self._check(lib().rt_mesh_morph(self._h, dst))
+
+    def mesh_morph_info(self) -> RtMorphInfo:
+        i = RtMorphInfo()
+        self._check(lib().rt_mesh_morph_info(self._h, C.byref(i)))
+        return i
 
     def mesh_info(self) -> RtMeshInfo:
         i = RtMeshInfo()

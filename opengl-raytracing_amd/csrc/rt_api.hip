@@ -20,6 +20,7 @@
 #include "rt_frame.hpp"
 #include "rt_bvh_cost.hpp"
 #include "rt_mesh.hpp"
+#include "rt_morph_pack.hpp"
 #include "rt_scene_pack.hpp"
 #include "rt_wave_plan.hpp"
 #include "rt_wave.hpp"
@@ -849,6 +850,92 @@ int rt_mesh_skin(RtContext *c) {
     rc = rtl::mesh_skin(c->mesh, st, &err);
     if (rc != RT_OK) return fail(c, rc, "rt_mesh_skin: %s", err ? err : "launch failed");
     return mesh_before_lanes(c, st);   // ... and updates, draws and table writes a lane is given next see the new positions
+}
+
+// ---- morph targets: rt_morph_pack.cpp checks and packs the targets, rt_mesh_morph.hip blends them; this file orders the writes
+int rt_mesh_morph_upload(RtContext *c, const float *base, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_upload: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    if (nTargets == 0) {
+        HIP_TRY(c, sync_all(c));
+        rtl::mesh_morph_release(c->mesh);
+        return RT_OK;
+    }
+    return guarded(c, "rt_mesh_morph_upload", [&]() -> int {
+        const int nVerts = rtl::mesh_verts(c->mesh);
+        std::string msg;
+        int rc = rtl::morph_validate(nVerts, targetFirst, vertIdx, deltas, nTargets, msg);
+        if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph_upload: %s", msg.c_str());
+        rtl::MorphPlan plan;
+        rc = rtl::morph_plan(nVerts, targetFirst, vertIdx, nTargets, plan, msg);
+        if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph_upload: %s", msg.c_str());
+        std::vector<rtl::MorphRecord> records;
+        rtl::morph_fill(plan, targetFirst, vertIdx, deltas, records);
+        HIP_TRY(c, sync_all(c));   // a morph in flight reads the arrays that are replaced; the snapshot reads its source as it stands
+        const char *err = nullptr;
+        rc = rtl::mesh_morph_create(c->mesh, base, plan.sliceFirst.data(), records.data(), plan.info, &err);
+        return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_morph_upload: %s", err ? err : "allocation failed");
+    });
+}
+
+int rt_mesh_morph_base(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_base: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
+    *devPtr = rtl::mesh_morph_base(c->mesh);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
+    return RT_OK;
+}
+
+int rt_mesh_morph_weights(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_weights: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
+    *devPtr = rtl::mesh_morph_weights(c->mesh);
+    *bytes = (size_t)rtl::mesh_morph_target_count(c->mesh) * 4;
+    return RT_OK;
+}
+
+int rt_mesh_set_morph_weights(RtContext *c, int first, int count, const float *weights) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
+    const int n = rtl::mesh_morph_target_count(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: entries %d .. %d of a table of %d", first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!weights) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: null weights");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    int rc = mesh_after_lanes(c, st);   // a morph enqueued on another lane reads the table
+    if (rc != RT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_morph_weights(c->mesh) + first, weights, (size_t)count * 4, hipMemcpyHostToDevice, st));
+    return mesh_before_lanes(c, st);
+}
+
+int rt_mesh_morph(RtContext *c, int dst) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no morph (rt_mesh_morph_upload first; rt_mesh_upload releases the morph)");
+    if (dst != RT_MORPH_TO_POSITIONS && dst != RT_MORPH_TO_REST) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: destination %d", dst);
+    if (dst == RT_MORPH_TO_REST && !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no rest array to write (rt_mesh_skin_upload first)");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    // gathers, skins, weight and base writes already enqueued on any lane come first, and for a position write the bound raster draws as well ...
+    int rc = mesh_after_lanes(c, st);
+    if (rc != RT_OK) return rc;
+    if (dst == RT_MORPH_TO_POSITIONS && c->raster && rt_raster_order_after(c->raster, st) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_morph: %s", rt_raster_error(c->raster));
+    const char *err = nullptr;
+    rc = rtl::mesh_morph(c->mesh, st, dst == RT_MORPH_TO_REST, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph: %s", err ? err : "launch failed");
+    return mesh_before_lanes(c, st);   // ... and skins, updates, draws and table writes a lane is given next see what was written
+}
+
+int rt_mesh_morph_info(RtContext *c, RtMorphInfo *out) {
+    if (!c || !out) return RT_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_info: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
+    *out = rtl::mesh_morph_info(c->mesh);
+    return RT_OK;
 }
 
 // ---- tree quality

@@ -220,6 +220,13 @@ struct Mesh {
     uint16_t *dSkinIdx = nullptr;
     int nBones = 0;
     size_t skinBytes = 0;
+    // morph targets: base positions, the packed records with their slice table, one weight per target; allocated by
+    // mesh_morph_create, not in `owned`
+    float *dMorphBase = nullptr, *dMorphW = nullptr;
+    uint32_t *dMorphSliceFirst = nullptr;
+    void *dMorphEntries = nullptr;
+    RtMorphInfo morph = {};   // nTargets == 0: no morph
+    size_t morphBytes = 0;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -407,6 +414,7 @@ int mesh_create(const float *positions, int nVerts, const uint32_t *indices, int
 void mesh_destroy(Mesh *m) {
     if (!m) return;
     mesh_skin_release(m);
+    mesh_morph_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -569,6 +577,49 @@ float *mesh_rest_positions(Mesh *m) { return m->dRest; }
 int mesh_skin(Mesh *m, hipStream_t st, const char **err) {
     if (m->nBones <= 0) return RT_ERR_INVALID;
     skin_launch(st, m->dRest, m->dSkinIdx, m->dSkinW, m->dBones, m->nVerts, m->dPos);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_morph_release(Mesh *m) {
+    for (void *p : {(void *)m->dMorphBase, (void *)m->dMorphSliceFirst, m->dMorphEntries, (void *)m->dMorphW}) if (p) (void)hipFree(p);
+    m->dMorphBase = m->dMorphW = nullptr; m->dMorphSliceFirst = nullptr; m->dMorphEntries = nullptr;
+    m->scratchBytes -= m->morphBytes;
+    m->morphBytes = 0; m->morph = RtMorphInfo{};
+}
+
+int mesh_morph_create(Mesh *m, const float *base, const uint32_t *sliceFirst, const void *records, const RtMorphInfo &info, const char **err) {
+    mesh_morph_release(m);
+    const size_t nv = (size_t)m->nVerts;
+    auto make = [&](auto **p, const void *src, size_t bytes, hipMemcpyKind kind) -> hipError_t {   // src == nullptr: zeros
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e != hipSuccess) return e;
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+        ++m->allocations;
+        m->morphBytes += bytes; m->scratchBytes += bytes;
+        if (!src) return hipMemset(q, 0, std::max<size_t>(bytes, 16));
+        return bytes ? hipMemcpy(q, src, bytes, kind) : hipSuccess;
+    };
+    hipError_t e = base ? make(&m->dMorphBase, base, nv * 12, hipMemcpyHostToDevice)
+                        : make(&m->dMorphBase, m->nBones > 0 ? m->dRest : m->dPos, nv * 12, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = make(&m->dMorphSliceFirst, sliceFirst, ((size_t)info.nSlices + 1) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = make(&m->dMorphEntries, records, (size_t)info.paddedEntries * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = make(&m->dMorphW, nullptr, (size_t)info.nTargets * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_morph_release(m); return RT_ERR_HIP; }
+    m->morph = info;
+    return RT_OK;
+}
+
+int mesh_morph_target_count(const Mesh *m) { return m->morph.nTargets; }
+const RtMorphInfo &mesh_morph_info(const Mesh *m) { return m->morph; }
+float *mesh_morph_base(Mesh *m) { return m->dMorphBase; }
+float *mesh_morph_weights(Mesh *m) { return m->dMorphW; }
+
+int mesh_morph(Mesh *m, hipStream_t st, bool toRest, const char **err) {
+    if (m->morph.nTargets <= 0 || (toRest && m->nBones <= 0)) return RT_ERR_INVALID;
+    morph_launch(st, m->dMorphBase, m->dMorphSliceFirst, m->dMorphEntries, m->dMorphW, m->nVerts, toRest ? m->dRest : m->dPos);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

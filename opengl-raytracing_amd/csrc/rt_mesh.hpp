@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/rt_mi355.h"
+
 namespace rtl {
 
 // What the triangle count alone determines (the builder splits every range at its middle and stops at <= 8 triangles).
@@ -102,6 +104,22 @@ float *mesh_rest_positions(Mesh *m);         // device, nVerts x 3 floats
 int mesh_skin(Mesh *m, hipStream_t st, const char **err);
 // rt_mesh_skin.hip: the kernel behind a plain launch function (raw device pointers; idx4 / w4: four influences per vertex)
 void skin_launch(hipStream_t st, const float *rest, const uint16_t *idx4, const float *w4, const float *bones, int nVerts, float *pos);
+
+// Morph targets.  mesh_morph_create: the packed form rt_morph_pack.cpp made of validated targets for the mesh's vertices (sliceFirst:
+// info.nSlices + 1 words; records: info.paddedEntries 16-byte records); base == nullptr snapshots the rest array when the mesh has a skin, else the
+// positions.  The weight table starts all zero.  Replaces a morph the mesh already has.  Allocates, copies and waits for the device; the caller has
+// waited for every lane.  mesh_morph_release: the four arrays freed (callers have synchronised).  mesh_morph enqueues dst := morph(base, records,
+// weight table) on `st`, dst the rest array (toRest) or the positions: no allocation, no host wait; RT_ERR_INVALID without a morph, or toRest
+// without a skin.
+int mesh_morph_create(Mesh *m, const float *base, const uint32_t *sliceFirst, const void *records, const RtMorphInfo &info, const char **err);
+void mesh_morph_release(Mesh *m);
+int mesh_morph_target_count(const Mesh *m);  // 0: no morph
+const RtMorphInfo &mesh_morph_info(const Mesh *m);
+float *mesh_morph_base(Mesh *m);             // device, nVerts x 3 floats
+float *mesh_morph_weights(Mesh *m);          // device, nTargets floats
+int mesh_morph(Mesh *m, hipStream_t st, bool toRest, const char **err);
+// rt_mesh_morph.hip: the kernel behind a plain launch function (raw device pointers; entries: the packed records)
+void morph_launch(hipStream_t st, const float *base, const uint32_t *sliceFirst, const void *entries, const float *weights, int nVerts, float *dst);
 
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);

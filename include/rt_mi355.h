@@ -731,7 +731,44 @@ int rt_mesh_set_morph_weights(RtContext *ctx, int first, int count, const float 
 int rt_mesh_morph(RtContext *ctx, int dst);
 /* What the current morph holds.  RT_ERR_INVALID without a morph. */
 int rt_mesh_morph_info(RtContext *ctx, RtMorphInfo *out);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload and rt_mesh_morph_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- previous pose and object motion: EXTENSION, not in the reference, whose motion target and reprojection offset are
+ * ndcFromWorld(hp, currViewProj) - ndcFromWorld(hp, prevViewProj) with one world point hp (rt.frag, rt_taa.glsl:175-179) -- exact while nothing but the
+ * camera moves, and wrong at every pixel a skinned, morphed or re-placed mesh covers.  With motion enabled the mesh keeps its previous pose as rows:
+ * prevTris, nTris rows of 48 bytes in the tris12 layout [v0 -][e1 -][e2 -], row i belonging to the same input triangle (rt_mesh_order's order[i]) as row
+ * i of the device triangle array and holding, byte for byte, the row that input triangle had in the triangle array before the most recent update.  Rows
+ * are copied and permuted, never recomputed, so the previous pose is right however the positions were produced: one matrix, part matrices, skin, morph,
+ * or the caller's own kernel.  Off until asked for; while it is off every kernel's output is what it was.
+ *   Every update -- rt_mesh_rebuild, rt_mesh_refit, their _parts forms, rt_mesh_update in both modes -- moves the previous pose while motion is enabled:
+ * the rows it is about to replace become the previous pose, row i afterwards the old row of input triangle order_new[i] (a refit keeps the order; a
+ * rebuild carries the old rows across its reordering).  The mesh's first rebuild has no old rows: the previous pose is then the new rows, zero motion.
+ * All of it is part of the update's own ordered work on rt_stream()'s stream: no allocation, no host wait (RtMeshInfo.hostSyncs moves only by the
+ * quantised form's status read, as before); frames and queries already enqueued keep the pose they were enqueued with.  rt_mesh_set_positions,
+ * rt_mesh_skin and rt_mesh_morph touch neither the triangle array nor the previous pose.
+ *   Frames: while the installed scene is the dynamic mesh's, motion is enabled and u->useBVH == 1, a primary hit on row tri with barycentrics (a, b) --
+ * the u, v rt_pick_pixels returns for that pixel -- takes prevNDC = ndcFromWorld(prevHp, prevViewProj) with prevHp as rt_hit_motion (below) defines it,
+ * on both pipelines; hp, RT_TARGET_GPOS, RT_TARGET_GNRM, the miss rule ((4, 4) under cameraMoved), resolveTAA, the batching rule of rt_render_frames
+ * and the tile-parallel exchange are unchanged, and a frame changes no mesh state.  The hybrid scene (RT_SCENE_HYBRID) keeps the reference's motion.
+ * rt_render_frame(s) take cameraMoved from the caller and never latch: render the frame after an update with cameraMoved = 1, so that the resolve
+ * reprojects, and call rt_mesh_motion_latch when the mesh comes to rest.  rt_render_ray / rt_render_ray_frames keep their FrameState inside the
+ * context and do it themselves: the context remembers "an update since the last latch"; a frame rendered in that state gets cameraMoved = 1 (and with
+ * it the moving jitter scale) even under an unchanged camera, and behind that frame the call latches; rt_render_ray_frames renders its first frame
+ * that way and batches the rest.  With motion disabled none of these entry points changes. */
+/* on != 0: allocates prevTris and the scratch a rebuild carries old rows across in (nTris rows each; RtMeshInfo.allocations and scratchBytes count
+ * them) and, if the mesh has a tree, latches.  on == 0 releases both.  May synchronise and allocate; the only call of this group that may.  No tree is
+ * needed to enable.  RT_ERR_INVALID without a mesh; rt_mesh_upload, rt_mesh_upload_parts and rt_upload_bvh release it with the mesh. */
+int rt_mesh_motion_enable(RtContext *ctx, int on);
+/* previous pose := current pose.  Enqueued on rt_stream()'s stream and ordered exactly as the update calls are: after the frames and queries already
+ * enqueued on every lane, before whatever is enqueued next, by events.  No allocation, no host wait.  RT_ERR_INVALID without a mesh, without motion
+ * enabled, or before the mesh's first rebuild. */
+int rt_mesh_motion_latch(RtContext *ctx);
+/* Where each hit point was in the previous pose: for the RtHit and points outputs of rt_trace_rays (points = origin + dir * t), rt_trace_scene_rays or
+ * rt_pick_pixels, prevPoints (3 floats per hit) equals rt_hit_motion's prevPoints bit for bit under the device's two triangle arrays as they stand when
+ * the kernel runs; zeros for a prim outside [0, nTris) -- a miss, an analytic hit, a stale value -- with nothing read out of bounds.  Device pointers,
+ * hits 16-byte aligned; enqueued on rt_stream()'s stream like rt_mesh_hit_parts: no allocation, no host wait.  RT_ERR_INVALID without a mesh, without
+ * motion enabled, or before the first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
+int rt_mesh_hit_prev_points(RtContext *ctx, const RtHit *hits, const float *points, int n, float *prevPoints);
+int rt_mesh_hit_prev_points_host(RtContext *ctx, const RtHit *hits, const float *points, int n, float *prevPoints);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload and rt_mesh_motion_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -742,7 +779,9 @@ enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 
        /* the optional record forms of rt_upload_bvh (RT_FUSED, RT_IMPLICIT): fused hubs; implicit two-child records, pair records, four-wide records,
         * quantised four-wide records and leaf boxes */
        RT_SCENE_ARRAY_FUSED = 7, RT_SCENE_ARRAY_IMPL_NODES2 = 8, RT_SCENE_ARRAY_IMPL_PAIRS = 9, RT_SCENE_ARRAY_IMPL_NODES4 = 10,
-       RT_SCENE_ARRAY_IMPL_QNODES4 = 11, RT_SCENE_ARRAY_IMPL_LEAFBOX = 12 };
+       RT_SCENE_ARRAY_IMPL_QNODES4 = 11, RT_SCENE_ARRAY_IMPL_LEAFBOX = 12,
+       /* the dynamic mesh's previous pose (rt_mesh_motion_enable): nTris rows of 48 bytes, no padding; size 0 while motion is not enabled */
+       RT_SCENE_ARRAY_PREV_TRIS = 13 };
 int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): what rt_upload_bvh would put on the device for these arrays -- the packers of
  * csrc/rt_scene_pack.cpp run and one array handed out, with rt_debug_read_scene's `which` values and size-query convention.
@@ -867,6 +906,19 @@ int rt_gather_triangles_parts(const float *positions, int nVerts, const uint32_t
  * transform of the point.  out (nVerts x 3 floats) may be rest.  RT_ERR_INVALID: a null array, nVerts <= 0, nBones outside 1 .. RT_MAX_MESH_BONES, any
  * of the four indices of a vertex >= nBones whatever its weight, a non-finite weight.  Bone matrices are not inspected. */
 int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, const float *weights4, const float *bones16, int nBones, float *out);
+
+/* Object motion of hits on the dynamic mesh on host arrays, and the definition rt_mesh_hit_prev_points and the frames' motion target are tested
+ * against (see rt_mesh_motion_enable for prevTris12; tris12: the current rows, nTris of 12 floats each; points: 3 floats per hit).  For hit i with
+ * p = hits[i].prim in [0, nTris), T = tris12 + 12 p, P = prevTris12 + 12 p, (a, b) = (hits[i].u, hits[i].v) and x = points + 3 i: if the nine geometry
+ * floats of P (words 0-2, 4-6, 8-10) are bit-equal to those of T, prev = x bit for bit; otherwise per component c
+ *   d = ((P.v0[c] - T.v0[c]) + (P.e1[c] - T.e1[c]) * a) + (P.e2[c] - T.e2[c]) * b,   prev = x + d,
+ * fp32 with rounded products and sums, nothing fused.  motion = ndcFromWorld(x, u->currViewProj) - ndcFromWorld(prev, u->prevViewProj) with ndcFromWorld
+ * as the frames evaluate it (rt_taa.glsl:175-179): per clip component fma(VP[8+k], z, fma(VP[4+k], y, VP[k] * x)) + VP[12+k], w = max(cw, 1e-6), two
+ * divisions.  So a pose that did not change yields exactly the reference's motion, and the delta form keeps precision where the displacement is small
+ * against the coordinates.  A prim outside [0, nTris) gives zeros in both outputs and reads nothing.  prevPoints (3 floats per hit) and motion2 (2 per
+ * hit): either may be NULL, not both; u may be NULL when motion2 is.  RT_ERR_INVALID: a null required array, nTris <= 0, n < 0.  Needs no GPU. */
+int rt_hit_motion(const RtUniforms *u, const float *tris12, const float *prevTris12, int nTris, const RtHit *hits, const float *points, int n, float *prevPoints,
+                  float *motion2);
 
 /* Morph-target blending on host arrays, and the definition rt_mesh_morph is tested against (see rt_mesh_morph_upload for the arrays; weights holds
  * nTargets floats).  For vertex v, acc = base[v]; the entries that name v are visited in input order (ascending target, then position within the

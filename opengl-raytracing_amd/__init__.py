@@ -191,6 +191,8 @@ RT_SCENE_ARRAY_TRIS, RT_SCENE_ARRAY_PAIRS, RT_SCENE_ARRAY_NODES2, RT_SCENE_ARRAY
 SCENE_ARRAYS = {"tris": 0, "pairs": 1, "nodes2": 2, "nodes2w": 3, "nodes4": 4, "qnodes4": 5, "leafbox": 6}
 # ... and the optional record forms (RT_FUSED, RT_IMPLICIT), which rt_debug_read_scene and rt_debug_pack_scene know as well
 SCENE_ARRAYS_OPTIONAL = {"fused": 7, "impl_nodes2": 8, "impl_pairs": 9, "impl_nodes4": 10, "impl_qnodes4": 11, "impl_leafbox": 12}
+# ... and the dynamic mesh's previous pose (rt_mesh_motion_enable): nTris rows of 48 bytes, empty while motion is not enabled
+RT_SCENE_ARRAY_PREV_TRIS = 13
 RT_SCENE_ARRAY_PACK_INFO = 100
 
 
@@ -356,6 +358,11 @@ SIGNATURES = {
     "rt_mesh_set_bones": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _FP]),
     "rt_mesh_rest_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_mesh_skin": (C.c_int, [C.c_void_p]),
+    "rt_mesh_motion_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_mesh_motion_latch": (C.c_int, [C.c_void_p]),
+    "rt_mesh_hit_prev_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_prev_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_hit_motion": (C.c_int, [C.c_void_p, _FP, _FP, C.c_int, C.c_void_p, _FP, C.c_int, _FP, _FP]),
     "rt_mesh_morph_upload": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32), _U32P, _FP, C.c_int]),
     "rt_mesh_morph_base": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_mesh_morph_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -619,6 +626,28 @@ def skin_positions(rest, bone_idx, weights, bones) -> np.ndarray:
     if rc != RT_OK:
         raise RtError(rc, "rt_skin_positions: no vertices, a bone count outside 1 .. 65536, a bone index out of range or a weight that is not finite")
     return out
+
+
+def hit_motion(u, tris12, prev_tris12, hits, points, want=("prev", "motion")):
+    """Object motion of hits on the dynamic mesh on the host (rt_hit_motion), the definition Renderer.mesh_hit_prev_points and the frames' MOTION
+    target are tested against: tris12 / prev_tris12 [T,12] the current and the previous rows, hits a RayHits / SceneHits or its [N,4] float32 record
+    array, points [N,3] -> (prev_points [N,3], motion [N,2]) float32.  want names the outputs to compute; the other is None.  u (RtUniforms) may be
+    None when motion is not wanted."""
+    rec = np.ascontiguousarray(hits.record if isinstance(hits, RayHits) else hits)
+    if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+        raise RtError(RT_ERR_INVALID, f"hit_motion: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+    t, p = _f32(tris12).reshape(-1, 12), _f32(prev_tris12).reshape(-1, 12)
+    x = _f32(points).reshape(-1, 3)
+    n = rec.shape[0]
+    if p.shape != t.shape or x.shape[0] != n:
+        raise RtError(RT_ERR_INVALID, f"hit_motion: {t.shape[0]} current and {p.shape[0]} previous rows, {n} hits and {x.shape[0]} points")
+    prev = np.zeros((n, 3), np.float32) if "prev" in want else None
+    mo = np.zeros((n, 2), np.float32) if "motion" in want else None
+    rc = lib().rt_hit_motion(None if u is None else C.addressof(u), _fp(t), _fp(p), t.shape[0], C.c_void_p(rec.ctypes.data), _fp(x), n,
+                             None if prev is None else _fp(prev), None if mo is None else _fp(mo))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_hit_motion: a null array, no triangles, no output asked for, or motion without uniforms")
+    return prev, mo
 
 
 def _morph_targets(who, target_first, vert_idx, deltas):
@@ -1295,6 +1324,56 @@ class Renderer:
         """Enqueue positions := skin(rest, tables, bone table) on stream() (rt_mesh_skin): what skin_positions computes, bit for bit, under the bone
         table as it stands when the kernel runs.  No host wait, no allocation; follow it with mesh_refit / mesh_rebuild / mesh_update."""
         self._check(lib().rt_mesh_skin(self._h))
+
+    # ---- previous pose and object motion (DESIGN.md 14.12): the rows before the most recent update, kept on the device beside the current ones
+    def mesh_motion_enable(self, on=True):
+        """Keep the previous pose of the dynamic mesh (rt_mesh_motion_enable): every update then moves it, and frames of the mesh's scene with
+        useBVH == 1 write object motion at primary hits.  Allocates two arrays of nTris rows and latches if there is a tree; may synchronise.
+        on=False releases them.  Off until asked for."""
+        self._check(lib().rt_mesh_motion_enable(self._h, 1 if on else 0))
+
+    def mesh_motion_latch(self):
+        """previous pose := current pose, enqueued in call order with updates, frames and queries (rt_mesh_motion_latch): no host wait."""
+        self._check(lib().rt_mesh_motion_latch(self._h))
+
+    def mesh_prev_tris(self) -> np.ndarray:
+        """The previous pose as float32 [nTris,12] rows of the tris12 layout (rt_debug_read_scene: synchronises); empty while motion is not enabled
+        or before the first rebuild.  Row i belongs to input triangle mesh_order()[i], as row i of debug_read_scene("tris")."""
+        return self.debug_read_scene(RT_SCENE_ARRAY_PREV_TRIS).view(np.float32).reshape(-1, 12)
+
+    def mesh_hit_prev_points(self, hits, points):
+        """Where each hit point was in the previous pose: float32 [N,3], hit_motion's prev_points bit for bit; zeros for a miss, an analytic hit or
+        a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array; points [N,3] the hit points (SceneHits.points, or
+        origin + dir * t).  numpy in, numpy out (rt_mesh_hit_prev_points_host: synchronises); torch tensors on this context's device take the
+        zero-copy path of mesh_hit_parts: enqueued on the library stream, ordered against torch's current stream, no host wait."""
+        rec = hits.record if isinstance(hits, RayHits) else hits
+        if isinstance(rec, np.ndarray):
+            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+                raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+            rec = np.ascontiguousarray(rec)
+            n = rec.shape[0]
+            x = _f32(points).reshape(-1, 3)
+            if x.shape[0] != n:
+                raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: {n} hits and {x.shape[0]} points")
+            out = np.zeros((n, 3), np.float32)
+            self._check(lib().rt_mesh_hit_prev_points_host(self._h, C.c_void_p(rec.ctypes.data), C.c_void_p(x.ctypes.data), n, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+            raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+        n = rec.shape[0]
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.numel() != 3 * n or points.device != dev:
+            raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: points must be a float32 [N,3] tensor on {dev}")
+        rec = rec.contiguous()
+        x = points.contiguous()
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
+        self._check(lib().rt_mesh_hit_prev_points(self._h, C.c_void_p(rec.data_ptr()), C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        return out
 
     # ---- morph targets (DESIGN.md 14.11): sparse deltas blended on the device under a weight table, before the skin or straight into the positions
     def mesh_morph_upload(self, target_first, vert_idx, deltas, base=None):

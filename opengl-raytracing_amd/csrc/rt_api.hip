@@ -74,6 +74,7 @@ struct RtContext {
     hipEvent_t evMeshOrder = nullptr;      // the order array of the current tree has been written, on meshOrderStream
     hipStream_t meshOrderStream = nullptr;
     uint64_t meshRebuilds = 0, meshHostSyncs = 0, meshRefits = 0, meshRefitsSinceRebuild = 0;
+    bool meshMotionDirty = false;          // previous pose: an update since the last latch, for rt_render_ray's own frame state
     // tree quality: which result slots of the mesh are in flight and what they measure; the arrived records the policy reads
     struct MeshQSlot { bool inFlight = false; uint64_t update = 0, tree = 0; int32_t refits = 0; } meshQSlot[rtl::kQualityRing];
     RtMeshQuality meshQLatest = {}, meshQBaseline = {};
@@ -380,6 +381,7 @@ void release_mesh(RtContext *c) {
     }
     rtl::mesh_destroy(c->mesh);
     c->mesh = nullptr;
+    c->meshMotionDirty = false;
     for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->evMeshLane[i]) (void)hipEventDestroy(c->evMeshLane[i]); c->evMeshLane[i] = nullptr; }
     if (c->evMeshDone) (void)hipEventDestroy(c->evMeshDone);
     c->evMeshDone = nullptr;
@@ -768,6 +770,7 @@ static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = 
     c->sceneFromMesh = true;
     if (refit) { ++c->meshRefits; ++c->meshRefitsSinceRebuild; }
     else { ++c->meshRebuilds; c->meshRefitsSinceRebuild = 0; }
+    if (rtl::mesh_prev_tris(c->mesh)) c->meshMotionDirty = true;
     return RT_OK;
 }
 
@@ -775,6 +778,80 @@ int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16,
 int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
 int rt_mesh_rebuild_parts(RtContext *c) { return mesh_update(c, nullptr, false, true); }
 int rt_mesh_refit_parts(RtContext *c) { return mesh_update(c, nullptr, true, true); }
+
+// ---- previous pose: rt_mesh.hip moves it inside every update; this file owns enabling, the latch's ordering and the hit query
+int rt_mesh_motion_enable(RtContext *c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
+    c->meshMotionDirty = false;
+    if (!on) { rtl::mesh_motion_release(c->mesh); return RT_OK; }
+    const char *err = nullptr;
+    const int rc = rtl::mesh_motion_create(c->mesh, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_motion_enable: %s", err ? err : "allocation failed");
+    return RT_OK;
+}
+
+int rt_mesh_motion_latch(RtContext *c) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_prev_tris(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: motion is not enabled (rt_mesh_motion_enable first)");
+    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: no pose to keep (rt_mesh_rebuild first)");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    int rc = mesh_after_lanes(c, st);   // frames and queries on every lane read the previous pose they were enqueued with ...
+    if (rc != RT_OK) return rc;
+    const char *err = nullptr;
+    rc = rtl::mesh_motion_latch(c->mesh, st, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_motion_latch: %s", err ? err : "copy failed");
+    c->meshMotionDirty = false;
+    return mesh_before_lanes(c, st);    // ... and whatever a lane is given next sees the latched one
+}
+
+static int hit_prev_points_args(RtContext *c, const char *who, const RtHit *hits, const float *points, int n, const float *prevPoints) {
+    if (n < 0 || (n > 0 && (!hits || !points)) || !prevPoints) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits, points and prevPoints are needed)", who, n);
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
+    if (!rtl::mesh_prev_tris(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: motion is not enabled (rt_mesh_motion_enable first)", who);
+    return RT_OK;
+}
+
+int rt_mesh_hit_prev_points(RtContext *c, const RtHit *hits, const float *points, int n, float *prevPoints) {
+    if (!c) return RT_ERR_INVALID;
+    int rc = hit_prev_points_args(c, "rt_mesh_hit_prev_points", hits, points, n, prevPoints);
+    if (rc != RT_OK) return rc;
+    if (((uintptr_t)hits & 15u) || (((uintptr_t)points | (uintptr_t)prevPoints) & 3u))
+        return fail(c, RT_ERR_INVALID, "rt_mesh_hit_prev_points: hits must be 16-byte aligned, points and prevPoints 4-byte aligned");
+    if (n == 0) return RT_OK;
+    (void)hipSetDevice(c->cfg.device);
+    const char *err = nullptr;
+    rc = rtl::mesh_hit_prev_points(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, points, n, prevPoints, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_prev_points: %s", err ? err : "launch failed");
+    return RT_OK;
+}
+
+int rt_mesh_hit_prev_points_host(RtContext *c, const RtHit *hits, const float *points, int n, float *prevPoints) {
+    if (!c) return RT_ERR_INVALID;
+    const int ar = hit_prev_points_args(c, "rt_mesh_hit_prev_points_host", hits, points, n, prevPoints);
+    if (ar != RT_OK) return ar;
+    if (n == 0) return RT_OK;
+    return guarded(c, "rt_mesh_hit_prev_points_host", [&]() -> int {
+    (void)hipSetDevice(c->cfg.device);
+    const size_t N = (size_t)n, hB = N * sizeof(RtHit), pB = (N * 12 + 15) / 16 * 16, total = hB + 2 * pB;   // hits | points | prevPoints
+    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
+    const int sr = ensure_staging(c, total);
+    if (sr != RT_OK) return sr;
+    char *base = (char *)c->dStaging;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(base + hB, points, N * 12, hipMemcpyHostToDevice, st));
+    const int qr = rt_mesh_hit_prev_points(c, (const RtHit *)base, (const float *)(base + hB), n, (float *)(base + hB + pB));
+    if (qr != RT_OK) { (void)sync_all(c); return qr; }
+    HIP_TRY(c, hipMemcpyAsync(prevPoints, base + hB + pB, N * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return RT_OK;
+    });
+}
 
 // ---- skinning: rt_mesh_skin.hip rewrites the positions; this file validates the tables and orders the writes against every lane
 int rt_mesh_skin_upload(RtContext *c, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones) {
@@ -1152,6 +1229,7 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
         case RT_SCENE_ARRAY_IMPL_NODES4: src = c->dIN4; n = implNodes * 96; break;
         case RT_SCENE_ARRAY_IMPL_QNODES4: src = c->dIQ4; n = implNodes * 48; break;
         case RT_SCENE_ARRAY_IMPL_LEAFBOX: src = c->dILeafBox; n = (implNodes + 1) * 32; break;
+        case RT_SCENE_ARRAY_PREV_TRIS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_prev_tris(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
     }
     if (!have || !src) return RT_OK;
@@ -1376,6 +1454,8 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     }
     for (int k = 0; k < RT_MAX_BATCH; ++k) { fr.jitterK[k][0] = jitterK ? jitterK[k < batch ? k : 0][0] : fr.u.jitter[0]; fr.jitterK[k][1] = jitterK ? jitterK[k < batch ? k : 0][1] : fr.u.jitter[1]; }
     fr.giBounces = c->giBounces;
+    // object motion: primary hits of the dynamic mesh's own scene; the hybrid scene keeps the reference's motion
+    fr.prevTris = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_prev_tris(c->mesh) : nullptr;
     // Lane = frame index mod nLanes = index of the COLOR0 buffer this frame writes: consecutive frames rotate over the lanes'
     // streams and overlap everywhere except at the temporal resolve (the only read of the previous frame), and every later
     // reader of a COLOR0 buffer (gather, assemble) is stream-ordered before the next writer of the same buffer.
@@ -1473,14 +1553,16 @@ int rt_render_ray(RtContext *c, const RtRenderParams *params, const RtCamera *ca
     if (currProj) std::memcpy(P, currProj, 64); else rt_camera_proj(cam, P);
     rt_mat4_mul(P, V, VP);                                   // FrameState::beginFrame, frame_state.h:68-73
     if (!c->haveFrameState) { std::memcpy(c->prevVP, VP, 64); c->haveFrameState = true; }   // application.cpp:316-319
-    const int moved = rt_camera_moved(VP, c->prevVP);        // application.cpp:387-395
+    // previous pose: the mesh moved since the last latch -- the frame is a moved one whatever the camera did, and takes the pose with it
+    const bool meshMoved = c->mesh && c->meshMotionDirty && rtl::mesh_prev_tris(c->mesh);
+    const int moved = (rt_camera_moved(VP, c->prevVP) || meshMoved) ? 1 : 0;        // application.cpp:387-395
     RtUniforms u;
     rt_make_uniforms(params, cam, V, VP, c->prevVP, c->g.W, c->g.H, c->frameIndex, moved, useBVH, showMotion, c->nNodes, c->nTris,
                      c->dEnv != nullptr, &u);
     int rc = rt_render_frame(c, &u);
     if (rc != RT_OK) return rc;
     std::memcpy(c->prevVP, VP, 64);                          // FrameState::endFrame, frame_state.h:81-84
-    return RT_OK;
+    return meshMoved ? rt_mesh_motion_latch(c) : RT_OK;
 }
 
 int rt_set_extension(RtContext *c, const RtExtension *ext) {
@@ -1506,14 +1588,21 @@ int rt_render_ray_frames(RtContext *c, const RtRenderParams *params, const RtCam
         std::vector<RtUniforms> us((size_t)count);
         float prev[16];
         std::memcpy(prev, c->prevVP, 64);
+        // previous pose: as rt_render_ray -- the first frame is a moved one and latches, the rest are batched behind it
+        const bool meshMoved = c->mesh && c->meshMotionDirty && rtl::mesh_prev_tris(c->mesh);
         for (int i = 0; i < count; ++i) {
-            const int moved = rt_camera_moved(VP, prev);
+            const int moved = (rt_camera_moved(VP, prev) || (meshMoved && i == 0)) ? 1 : 0;
             rt_make_uniforms(params, cam, V, VP, prev, c->g.W, c->g.H, c->frameIndex + i, moved, useBVH, showMotion, c->nNodes, c->nTris, c->dEnv != nullptr,
                              &us[(size_t)i]);
             std::memcpy(prev, VP, 64);
         }
         const int first = c->frameIndex;
-        int rc = rt_render_frames(c, us.data(), count);
+        int rc = RT_OK;
+        if (meshMoved) {
+            rc = rt_render_frame(c, &us[0]);
+            if (rc == RT_OK) rc = rt_mesh_motion_latch(c);
+            if (rc == RT_OK && count > 1) rc = rt_render_frames(c, us.data() + 1, count - 1);
+        } else rc = rt_render_frames(c, us.data(), count);
         // FrameState::endFrame (frame_state.h:81-84) runs after every rendered frame: if the sequence failed part-way, the frames
         // that did render have advanced frameIndex and the camera state must follow them, exactly as with rt_render_ray per frame
         if (rc == RT_OK || c->frameIndex != first) std::memcpy(c->prevVP, VP, 64);

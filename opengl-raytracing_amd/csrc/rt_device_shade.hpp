@@ -11,6 +11,7 @@
 #pragma once
 #include "../../include/rt_mi355.h"
 #include "rt_device_math.hpp"
+#include "rt_mesh_motion.hpp"
 
 #pragma clang fp contract(off)
 
@@ -279,6 +280,27 @@ RT_DEV bool bvh_anyhit(const DevScene &sc, V3 ro, V3 rd, float eps, float tMax, 
 RT_DEV V3 tri_normal(const DevScene &sc, int tri) {
     const float4 *t = sc.tris + (size_t)tri * 3;
     return normalize(cross(f4xyz(t[1]), f4xyz(t[2])));
+}
+
+// Object motion: where the primary hit `hp` = ro + rd * t on row `tri` was in the dynamic mesh's previous pose.  (a, b) are the hit's
+// barycentrics on the row as it is now, with QuerySrc::store_closest's operations in its order -- the u, v rt_pick_pixels returns for the pixel -- and the
+// rest is rt_hit_motion's.  prevTris == null (no dynamic mesh, or motion not enabled): hp itself, the reference's rule.
+RT_DEV V3 prevHitPoint(const float4 *tris, const float4 *prevTris, int tri, V3 ro, V3 rd, V3 hp) {
+    if (!prevTris) return hp;
+    const float4 *T = tris + (size_t)tri * 3, *P = prevTris + (size_t)tri * 3;
+    const float4 t0 = T[0], t1 = T[1], t2 = T[2], p0 = P[0], p1 = P[1], p2 = P[2];
+    const V3 v0 = f4xyz(t0), e1 = f4xyz(t1), e2 = f4xyz(t2);
+    const V3 pvec = cross(rd, e2);
+    const float invDet = 1.0f / dot(e1, pvec);
+    const V3 tvec = ro - v0;
+    const float a = dot(tvec, pvec) * invDet;
+    const float b = dot(rd, cross(tvec, e1)) * invDet;
+    const float Tf[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+    const float Pf[12] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, p2.w};
+    const float x[3] = {hp.x, hp.y, hp.z};
+    float prev[3];
+    rtmotion::prev_point(Tf, Pf, a, b, x, prev);
+    return mk3(prev[0], prev[1], prev[2]);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@
 
 #include "../../include/rt_mi355.h"
 #include "rt_bvh_cost.hpp"
+#include "rt_mesh_motion.hpp"
 
 namespace rthost {
 
@@ -437,6 +438,40 @@ int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, c
             any = true;
         }
         std::memcpy(out + (size_t)v * 3, any ? acc : p, sizeof p);
+    }
+    return RT_OK;
+}
+
+// ndcFromWorld (rt_device_shade.hpp, rt_taa.glsl:175-179) as the device evaluates it: the two-fmaf chain plus the translation term, w clamped, two divisions
+static inline void ndc_from_world(const float *p, const float *VP, float *out2) {
+    const float cx = std::fmaf(VP[8], p[2], std::fmaf(VP[4], p[1], VP[0] * p[0])) + VP[12];
+    const float cy = std::fmaf(VP[9], p[2], std::fmaf(VP[5], p[1], VP[1] * p[0])) + VP[13];
+    const float cw = std::fmaf(VP[11], p[2], std::fmaf(VP[7], p[1], VP[3] * p[0])) + VP[15];
+    const float w = std::fmax(cw, 1e-6f);
+    out2[0] = cx / w; out2[1] = cy / w;
+}
+
+// Object motion of hits on the dynamic mesh, and the definition rt_mesh_hit_prev_points and the frames are held to: the hit point moved
+// by the difference between the previous and the current row of its triangle at the hit's barycentrics (rt_mesh_motion.hpp), then the reference's
+// motion with the previous point under the previous view-projection.  A prim outside [0, nTris): zeros, nothing read.
+int rt_hit_motion(const RtUniforms *u, const float *tris12, const float *prevTris12, int nTris, const RtHit *hits, const float *points, int n, float *prevPoints,
+                  float *motion2) {
+    if (!tris12 || !prevTris12 || nTris <= 0 || n < 0 || (!prevPoints && !motion2) || (motion2 && !u) || (n > 0 && (!hits || !points))) return RT_ERR_INVALID;
+    for (int i = 0; i < n; ++i) {
+        float prev[3] = {0.0f, 0.0f, 0.0f}, mo[2] = {0.0f, 0.0f};
+        const int p = hits[i].prim;
+        if (p >= 0 && p < nTris) {
+            const float *x = points + (size_t)i * 3;
+            rtmotion::prev_point(tris12 + (size_t)p * 12, prevTris12 + (size_t)p * 12, hits[i].u, hits[i].v, x, prev);
+            if (motion2) {
+                float c2[2], p2[2];
+                ndc_from_world(x, u->currViewProj, c2);
+                ndc_from_world(prev, u->prevViewProj, p2);
+                mo[0] = c2[0] - p2[0]; mo[1] = c2[1] - p2[1];
+            }
+        }
+        if (prevPoints) std::memcpy(prevPoints + (size_t)i * 3, prev, sizeof prev);
+        if (motion2) std::memcpy(motion2 + (size_t)i * 2, mo, sizeof mo);
     }
     return RT_OK;
 }

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr
                 const V3 hp = camPos + dir * tHit;
                 const V3 hn = tri_normal(fr->sc, triHit);
                 if (COUNT) w.hitPixels++;
-                V2 prevNDC = ndcFromWorld(hp, u.prevViewProj), currNDC = ndcFromWorld(hp, u.currViewProj);
+                V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, triHit, camPos, dir, hp), u.prevViewProj), currNDC = ndcFromWorld(hp, u.currViewProj);
                 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
                 gpos = mk4(hp.x, hp.y, hp.z, 1.0f);
                 V3 nn = normalize(hn);

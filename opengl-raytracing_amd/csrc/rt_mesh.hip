@@ -227,6 +227,10 @@ struct Mesh {
     void *dMorphEntries = nullptr;
     RtMorphInfo morph = {};   // nTargets == 0: no morph
     size_t morphBytes = 0;
+    // previous pose: the rows before the most recent update, in the current order, and the old rows by input triangle a rebuild
+    // carries them across in; allocated by mesh_motion_create, not in `owned`
+    float4 *dPrevTris = nullptr, *dPrevByInput = nullptr;
+    size_t motionBytes = 0;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -415,6 +419,7 @@ void mesh_destroy(Mesh *m) {
     if (!m) return;
     mesh_skin_release(m);
     mesh_morph_release(m);
+    mesh_motion_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -457,6 +462,9 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     const BvhLayout &L = m->lay;
     const int n = L.nTris;
     const unsigned gN = blocks_for((size_t)n);
+    // previous pose: the rows that are about to be replaced, filed by input triangle while the old permutation still stands
+    const bool carry = m->dPrevTris && m->permCur >= 0;
+    if (carry) motion_launch_scatter(st, m->sc.tris, m->dPerm[m->permCur], m->dOut, n, m->dPrevByInput);
     m->permCur = -1; m->orderValid = false;   // the sorts below use both permutation buffers
     if (M16) {
         Mat16 M;
@@ -482,6 +490,10 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     hipLaunchKernelGGL(k_emit_tris, dim3(gN), dim3(256), 0, st, m->dT9, m->dPerm[cur], m->dOut, n, reinterpret_cast<float *>(m->sc.tris));
     emit_records(m, st);
     REB_TRY(hipGetLastError());
+    if (m->dPrevTris) {   // ... and handed out in the new order; the first rebuild has no old rows: the new ones, zero motion
+        if (carry) { motion_launch_gather(st, m->dPrevByInput, m->dPerm[cur], m->dOut, n, m->dPrevTris); REB_TRY(hipGetLastError()); }
+        else REB_TRY(hipMemcpyAsync(m->dPrevTris, m->sc.tris, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+    }
     m->permCur = cur;
     return RT_OK;
 }
@@ -492,6 +504,8 @@ int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     if (m->permCur < 0) return RT_ERR_INVALID;
     const BvhLayout &L = m->lay;
     const int n = L.nTris;
+    // previous pose: a refit keeps every input triangle in its row, so the rows that are about to be rewritten are copied as they lie
+    if (m->dPrevTris) REB_TRY(hipMemcpyAsync(m->dPrevTris, m->sc.tris, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     if (M16) refit_launch_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, n, M16, m->sc.tris);
     else parts_launch_refit_tris(st, m->dPos, m->dIdx, m->dPerm[m->permCur], m->dOut, m->dPartOf, m->dPartM, n, m->sc.tris);
     refit_launch_leaves(st, m->sc.tris, m->dRefitLeaf, (int)L.nLeaves, m->dBounds, m->dStatus);
@@ -620,6 +634,48 @@ float *mesh_morph_weights(Mesh *m) { return m->dMorphW; }
 int mesh_morph(Mesh *m, hipStream_t st, bool toRest, const char **err) {
     if (m->morph.nTargets <= 0 || (toRest && m->nBones <= 0)) return RT_ERR_INVALID;
     morph_launch(st, m->dMorphBase, m->dMorphSliceFirst, m->dMorphEntries, m->dMorphW, m->nVerts, toRest ? m->dRest : m->dPos);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_motion_release(Mesh *m) {
+    for (void *p : {(void *)m->dPrevTris, (void *)m->dPrevByInput}) if (p) (void)hipFree(p);
+    m->dPrevTris = m->dPrevByInput = nullptr;
+    m->scratchBytes -= m->motionBytes;
+    m->motionBytes = 0;
+}
+
+int mesh_motion_create(Mesh *m, const char **err) {
+    mesh_motion_release(m);
+    const size_t bytes = (size_t)m->lay.nTris * 48;
+    auto make = [&](float4 **p) -> hipError_t {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return e;
+        *p = reinterpret_cast<float4 *>(q);
+        ++m->allocations;
+        m->motionBytes += bytes; m->scratchBytes += bytes;
+        return hipMemset(q, 0, bytes);
+    };
+    hipError_t e = make(&m->dPrevTris);
+    if (e == hipSuccess) e = make(&m->dPrevByInput);
+    if (e == hipSuccess && m->permCur >= 0) e = hipMemcpy(m->dPrevTris, m->sc.tris, bytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_motion_release(m); return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+const float4 *mesh_prev_tris(const Mesh *m) { return m->dPrevTris; }
+
+int mesh_motion_latch(Mesh *m, hipStream_t st, const char **err) {
+    if (!m->dPrevTris || m->permCur < 0) return RT_ERR_INVALID;
+    REB_TRY(hipMemcpyAsync(m->dPrevTris, m->sc.tris, (size_t)m->lay.nTris * 48, hipMemcpyDeviceToDevice, st));
+    return RT_OK;
+}
+
+int mesh_hit_prev_points(Mesh *m, hipStream_t st, const void *hits, const float *points, int n, float *prevPoints, const char **err) {
+    if (!m->dPrevTris || m->permCur < 0) return RT_ERR_INVALID;
+    motion_launch_hit_prev_points(st, hits, points, n, m->sc.tris, m->dPrevTris, m->lay.nTris, prevPoints);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

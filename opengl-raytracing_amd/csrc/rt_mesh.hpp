@@ -121,6 +121,24 @@ int mesh_morph(Mesh *m, hipStream_t st, bool toRest, const char **err);
 // rt_mesh_morph.hip: the kernel behind a plain launch function (raw device pointers; entries: the packed records)
 void morph_launch(hipStream_t st, const float *base, const uint32_t *sliceFirst, const void *entries, const float *weights, int nVerts, float *dst);
 
+// The previous pose: prevTris, nTris rows of the triangle array's layout, row i = the row input triangle order[i] had before the most
+// recent update.  mesh_motion_create allocates it and the remap scratch (old rows by input triangle) and, when there is a tree, latches; allocates and
+// waits for the device; the caller has waited for every lane.  mesh_motion_release: both arrays freed (callers have synchronised).  While the arrays
+// exist mesh_rebuild and mesh_refit move the previous pose on their stream, inside their own sequence of launches.  mesh_motion_latch enqueues
+// previous pose := current pose on `st`: no allocation, no host wait; RT_ERR_INVALID without the arrays or without a tree.
+int mesh_motion_create(Mesh *m, const char **err);
+void mesh_motion_release(Mesh *m);
+const float4 *mesh_prev_tris(const Mesh *m);   // device; null: motion is not enabled
+int mesh_motion_latch(Mesh *m, hipStream_t st, const char **err);
+// Enqueues prevPoints[i] = where hit i's point was in the previous pose (rt_hit_motion's prevPoints) on `st` for n RtHit records and their points (device
+// pointers).  RT_ERR_INVALID without the arrays or without a tree.
+int mesh_hit_prev_points(Mesh *m, hipStream_t st, const void *hits, const float *points, int n, float *prevPoints, const char **err);
+// rt_mesh_motion.hip: the kernels behind plain launch functions (raw device pointers; perm / outOfPos: the tables refit_launch_order composes)
+void motion_launch_scatter(hipStream_t st, const float4 *tris, const int *perm, const int *outOfPos, int nTris, float4 *byInput);
+void motion_launch_gather(hipStream_t st, const float4 *byInput, const int *perm, const int *outOfPos, int nTris, float4 *prev);
+void motion_launch_hit_prev_points(hipStream_t st, const void *hits, const float *points, int n, const float4 *tris, const float4 *prevTris, int nTris,
+                                   float *prevPoints);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

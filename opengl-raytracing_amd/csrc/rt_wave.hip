@@ -1946,7 +1946,7 @@ __global__ __launch_bounds__(256) void k_combine(const DevFrame *__restrict__ fr
     CombineTracer tr;
     tr.wb = wb; tr.sc = &fr->sc; tr.j = j; tr.s = 0;
     Work w;
-    V2 prevNDC = ndcFromWorld(c.hp, u.prevViewProj), currNDC = ndcFromWorld(c.hp, u.currViewProj);
+    V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir, c.hp), u.prevViewProj), currNDC = ndcFromWorld(c.hp, u.currViewProj);
     V2 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
     V3 nn = normalize(c.hn);
     float ao = 1.0f;

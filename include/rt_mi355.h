@@ -768,7 +768,45 @@ int rt_mesh_motion_latch(RtContext *ctx);
  * motion enabled, or before the first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
 int rt_mesh_hit_prev_points(RtContext *ctx, const RtHit *hits, const float *points, int n, float *prevPoints);
 int rt_mesh_hit_prev_points_host(RtContext *ctx, const RtHit *hits, const float *points, int n, float *prevPoints);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload and rt_mesh_motion_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- smooth vertex normals: EXTENSION, not in the reference, which shades every mesh hit with the triangle's own normal
+ * normalize(cross(e1, e2)) (triHit, rt_bvh.glsl:168) -- right for a static scan, faceted on an articulated model, with facets that crawl as it deforms.
+ * With normals enabled the mesh keeps, on the device, one area-weighted normal per vertex and the three corner normals of every row of the triangle
+ * array (nrmRows: nTris rows of 48 bytes, three float4 (nx, ny, nz, 0), row i beside row i of the triangle array, its corners those of input triangle
+ * rt_mesh_order's order[i]), both exactly as rt_vertex_normals (below) defines them, bit for bit.  They are computed from the rows, so they are
+ * world-space normals and right however the positions were produced: one matrix, part matrices, skin, morph, or the caller's own kernel.  Off until
+ * asked for; while it is off every kernel's output is what it was.  Hard edges are the caller's to make, by duplicating vertices.
+ *   Every update -- rt_mesh_rebuild, rt_mesh_refit, their _parts forms, rt_mesh_update in both modes -- recomputes them behind its new rows while normals
+ * are enabled, as part of its own ordered work on rt_stream()'s stream (a rebuild derives the order array for itself first): no allocation, no host
+ * wait (RtMeshInfo.hostSyncs moves only by the quantised form's status read, as before); frames and queries already enqueued keep the normals they were
+ * enqueued with.  rt_mesh_set_positions, rt_mesh_skin, rt_mesh_morph and rt_mesh_motion_latch do not touch them.
+ *   Frames: while the installed scene is the dynamic mesh's, normals are enabled and u->useBVH == 1, the normal of a mesh hit -- the primary hit and the
+ * bounce hit, on both pipelines -- is the smooth one: with (a, b) the hit's barycentrics on its row, computed with the operations of rt_pick_pixels' u, v
+ * in their order, it is what rt_hit_normals (below) defines from the row's three corner normals.  So RT_TARGET_GNRM, direct light, AO, the bounce and
+ * its direct light use it wherever the reference uses h.n, and rt_mesh_hit_normals on a pixel's pick is that pixel's GNRM: the target holds the
+ * halves of exactly those floats (the reference's second normalize(h.n) in front of the store is not applied to a normal that is already the definition's).  A flat region -- three bit-equal corner normals -- shades with exactly the reference's bits.  Traversal, hp, RT_TARGET_GPOS, RT_TARGET_MOTION,
+ * resolveTAA and the miss rule are unchanged.  The face normal stays in: rt_trace_rays' and rt_pick_pixels' optional normal outputs, the hybrid scene
+ * (RT_SCENE_HYBRID) and the analytic scene, and the raster preview.  Known, not solved: ray origins are offset along the smooth normal, as the
+ * reference offsets along h.n; at a grazing silhouette that can start a ray under a neighbouring facet. */
+/* incidences: index-buffer entries (3 nTris); paddedEntries: 4-byte entries of the packed adjacency on the device; bytes: device bytes of the five arrays
+ * (adjacency, its slice table, face vectors, vertex normals, nrmRows). */
+typedef struct RtNormalInfo { int32_t nVerts, nTris, nSlices, maxPerVertex; uint64_t incidences, paddedEntries, bytes; } RtNormalInfo;
+/* on != 0: waits for every lane, reads the mesh's index buffer back, packs the vertex -> triangle adjacency on the host (rt_debug_normal_pack, below),
+ * allocates it, the face vectors, the vertex normals and nrmRows (RtMeshInfo.allocations and scratchBytes count them) and, if the mesh has a tree,
+ * computes the normals at once.  on == 0 releases everything.  May synchronise and allocate; the only call of this group that may.  No tree is needed
+ * to enable.  RT_ERR_INVALID without a mesh; RT_ERR_UNSUPPORTED when the packed adjacency would reach 2^31 entries; rt_mesh_upload,
+ * rt_mesh_upload_parts and rt_upload_bvh release it with the mesh. */
+int rt_mesh_normals_enable(RtContext *ctx, int on);
+/* The device array of vertex normals: nVerts x 4 floats (nx, ny, nz, 0), written on rt_stream()'s stream by the update calls: order reads of it there.
+ * RT_ERR_INVALID without a mesh or without normals enabled. */
+int rt_mesh_vertex_normals(RtContext *ctx, void **devPtr, size_t *bytes);
+/* The shading normal of each hit: for the RtHit outputs of rt_trace_rays, rt_trace_scene_rays or rt_pick_pixels, normals (3 floats per hit) equals
+ * rt_hit_normals' out3 bit for bit under the device's triangle array and normals as they stand when the kernel runs; zeros for a prim outside
+ * [0, nTris) -- a miss, an analytic hit, a stale value -- with nothing read out of bounds.  Device pointers, hits 16-byte aligned; enqueued on
+ * rt_stream()'s stream like rt_mesh_hit_prev_points: no allocation, no host wait.  RT_ERR_INVALID without a mesh, without normals enabled, or before
+ * the first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
+int rt_mesh_hit_normals(RtContext *ctx, const RtHit *hits, int n, float *normals);
+int rt_mesh_hit_normals_host(RtContext *ctx, const RtHit *hits, int n, float *normals);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload, rt_mesh_motion_enable and rt_mesh_normals_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -781,7 +819,9 @@ enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 
        RT_SCENE_ARRAY_FUSED = 7, RT_SCENE_ARRAY_IMPL_NODES2 = 8, RT_SCENE_ARRAY_IMPL_PAIRS = 9, RT_SCENE_ARRAY_IMPL_NODES4 = 10,
        RT_SCENE_ARRAY_IMPL_QNODES4 = 11, RT_SCENE_ARRAY_IMPL_LEAFBOX = 12,
        /* the dynamic mesh's previous pose (rt_mesh_motion_enable): nTris rows of 48 bytes, no padding; size 0 while motion is not enabled */
-       RT_SCENE_ARRAY_PREV_TRIS = 13 };
+       RT_SCENE_ARRAY_PREV_TRIS = 13,
+       /* the dynamic mesh's corner normals (rt_mesh_normals_enable): nTris rows of 48 bytes, no padding; size 0 while normals are not enabled */
+       RT_SCENE_ARRAY_NORMAL_ROWS = 14 };
 int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): what rt_upload_bvh would put on the device for these arrays -- the packers of
  * csrc/rt_scene_pack.cpp run and one array handed out, with rt_debug_read_scene's `which` values and size-query convention.
@@ -815,6 +855,15 @@ int rt_debug_pack_scene(const float *nodes12, int nNodes, const float *tris12, i
 enum { RT_MORPH_ARRAY_SLICE_FIRST = 0, RT_MORPH_ARRAY_ENTRIES = 1, RT_MORPH_ARRAY_INFO = 100 };
 int rt_debug_morph_pack(int nVerts, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets, int which, void *dst, size_t capacity,
                         size_t *bytes);
+/* Diagnostics, host side (no GPU needed, no context): what rt_mesh_normals_enable would put on the device for this index buffer -- the packer of
+ * csrc/rt_normal_pack.cpp run and one array handed out, with rt_debug_pack_scene's size-query convention.  An incidence of vertex v is
+ * a pair (k, c) with indices[3k + c] == v, ordered by k, then c.  Slice s holds vertices 64s .. 64s+63 and is as wide as the longest incidence list
+ * among them; RT_NORMAL_ARRAY_SLICE_FIRST: nSlices + 1 uint32 prefix sums of width * 64, in entries; RT_NORMAL_ARRAY_ENTRIES: sliceFirst[nSlices] int32,
+ * entry sliceFirst[s] + j * 64 + l the input triangle of the j-th incidence of vertex 64s + l, or -1 where that vertex has no j-th incidence or does
+ * not exist; RT_NORMAL_ARRAY_INFO: an RtNormalInfo.  RT_ERR_INVALID: null indices, nIdx <= 0 or no multiple of 3, nVerts <= 0, an index >= nVerts, an
+ * unknown array; RT_ERR_UNSUPPORTED when the padded entries would reach 2^31. */
+enum { RT_NORMAL_ARRAY_SLICE_FIRST = 0, RT_NORMAL_ARRAY_ENTRIES = 1, RT_NORMAL_ARRAY_INFO = 100 };
+int rt_debug_normal_pack(const uint32_t *indices, int nIdx, int nVerts, int which, void *dst, size_t capacity, size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): the ray-queue plan of one launch set of the wavefront pipeline (csrc/rt_wave_plan.cpp,
  * DESIGN.md 16) -- the arithmetic rt_render_frame(s) follows, for checks.  RtWaveOptions: every environment variable of frame rendering as a lane reads it
  * when the context is created; a "...Set" field says whether the variable was set at all where unset has a meaning of its own. */
@@ -919,6 +968,24 @@ int rt_skin_positions(const float *rest, int nVerts, const uint16_t *boneIdx4, c
  * hit): either may be NULL, not both; u may be NULL when motion2 is.  RT_ERR_INVALID: a null required array, nTris <= 0, n < 0.  Needs no GPU. */
 int rt_hit_motion(const RtUniforms *u, const float *tris12, const float *prevTris12, int nTris, const RtHit *hits, const float *points, int n, float *prevPoints,
                   float *motion2);
+
+/* Smooth vertex normals on host arrays, and the definitions the device's normals, rt_mesh_hit_normals and the frames' normals are tested against
+ * (tris12: the rows of the triangle array, nTris of 12 floats [v0 -][e1 -][e2 -]; order: row -> input triangle, rt_mesh_order's array; indices: the
+ * 3 nTris indices of the input triangles).  fp32 in the device's float model: rounded products and sums, fused only where cross and dot write an fmaf.
+ *   rt_vertex_normals: the face vector of input triangle k is cross(e1, e2) of the row r with order[r] == k, per component fmaf(a.y, b.z, -(a.z * b.y)),
+ * not normalised, so the weighting is by area.  S[v] is the sum of the face vectors of every incidence (k, c) with indices[3k + c] == v, taken with k
+ * ascending, then c; the first term initialises the sum; a triangle that names v twice contributes twice.  n[v] = S * (1 / sqrt(dot(S, S))) with
+ * dot = fmaf(z, z, fmaf(y, y, x * x)) when dot(S, S) > 0 and finite, else three +0 (an isolated vertex, a zero or non-finite sum).  normals3: 3 floats
+ * per vertex.  RT_ERR_INVALID: a null array, nTris <= 0, nVerts <= 0, an index >= nVerts, an order entry outside [0, nTris).
+ *   rt_hit_normals: for hit i on row p = hits[i].prim in [0, nTris) with (a, b) = (hits[i].u, hits[i].v), the corner normals n0, n1, n2 are those of
+ * vertices indices[3 order[p] + c].  If their nine floats are bit-equal corner to corner the answer is n0 bit for bit, unless n0 is all zero.  Otherwise
+ * m = (n0 * ((1 - a) - b) + n1 * a) + n2 * b per component, and the answer is m * (1 / sqrt(dot(m, m))) when dot(m, m) > 0 and finite.  In every
+ * remaining case (a zero n0 among bit-equal corners, a zero or non-finite m, NaN barycentrics) it is the row's face normal normalize(cross(e1, e2)),
+ * the reference's.  A prim outside [0, nTris) gives zeros and reads nothing.  out3: 3 floats per hit.  RT_ERR_INVALID: a null array, nTris <= 0,
+ * nVerts <= 0, n < 0, or a hit row whose order entry or indices are out of range.  Neither needs a GPU. */
+int rt_vertex_normals(const float *tris12, const int32_t *order, int nTris, const uint32_t *indices, int nVerts, float *normals3);
+int rt_hit_normals(const float *tris12, const int32_t *order, int nTris, const uint32_t *indices, const float *normals3, int nVerts, const RtHit *hits, int n,
+                   float *out3);
 
 /* Morph-target blending on host arrays, and the definition rt_mesh_morph is tested against (see rt_mesh_morph_upload for the arrays; weights holds
  * nTargets floats).  For vertex v, acc = base[v]; the entries that name v are visited in input order (ascending target, then position within the

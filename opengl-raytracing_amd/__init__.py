@@ -171,6 +171,10 @@ class RtMorphInfo(_Struct):   # rt_mesh_morph_info / rt_debug_morph_pack: the mo
     _fields_ = [(n, i32) for n in ("nVerts", "nTargets", "nSlices", "maxPerVertex")] + [(n, C.c_uint64) for n in ("entries", "paddedEntries", "bytes")]
 
 
+class RtNormalInfo(_Struct):   # rt_debug_normal_pack: the vertex -> triangle adjacency in its packed form
+    _fields_ = [(n, i32) for n in ("nVerts", "nTris", "nSlices", "maxPerVertex")] + [(n, C.c_uint64) for n in ("incidences", "paddedEntries", "bytes")]
+
+
 class RtBvhCost(_Struct):   # rt_bvh_cost: the quality metric of a tree
     _fields_ = [("innerQ", C.c_uint64), ("leafQ", C.c_uint64)] + [(n, C.c_double) for n in ("rootArea", "inner", "leaf", "cost")] + \
                [(n, i32) for n in ("rootExp", "degenerate", "nInner", "nLeaves")]
@@ -193,6 +197,9 @@ SCENE_ARRAYS = {"tris": 0, "pairs": 1, "nodes2": 2, "nodes2w": 3, "nodes4": 4, "
 SCENE_ARRAYS_OPTIONAL = {"fused": 7, "impl_nodes2": 8, "impl_pairs": 9, "impl_nodes4": 10, "impl_qnodes4": 11, "impl_leafbox": 12}
 # ... and the dynamic mesh's previous pose (rt_mesh_motion_enable): nTris rows of 48 bytes, empty while motion is not enabled
 RT_SCENE_ARRAY_PREV_TRIS = 13
+# ... and its corner normals (rt_mesh_normals_enable): nTris rows of 48 bytes, empty while normals are not enabled
+RT_SCENE_ARRAY_NORMAL_ROWS = 14
+SCENE_ARRAYS_MESH = {"prev tris": 13, "normal rows": 14}
 RT_SCENE_ARRAY_PACK_INFO = 100
 
 
@@ -226,6 +233,8 @@ RT_SKIN_INFLUENCES, RT_MAX_MESH_BONES = 4, 65536   # rt_mesh_skin_upload
 RT_MAX_MORPH_TARGETS = 65536   # rt_mesh_morph_upload
 RT_MORPH_TO_POSITIONS, RT_MORPH_TO_REST = 0, 1   # rt_mesh_morph
 RT_MORPH_ARRAY_SLICE_FIRST, RT_MORPH_ARRAY_ENTRIES, RT_MORPH_ARRAY_INFO = 0, 1, 100   # rt_debug_morph_pack
+RT_NORMAL_ARRAY_SLICE_FIRST, RT_NORMAL_ARRAY_ENTRIES, RT_NORMAL_ARRAY_INFO = 0, 1, 100   # rt_debug_normal_pack
+NORMAL_PAD_ENTRY = -1   # an entry of the packed adjacency that stands for no incidence
 MORPH_PAD_TARGET = 0xFFFFFFFF   # target of a pad record of the packed entries
 RASTER_BACKGROUND = 0xFFFFFFFF   # rt_read_raster primId of a pixel no triangle covers (depth24 0xFFFFFF)
 RT_RASTER_BIND_SINGLE, RT_RASTER_BIND_PARTS = 0, 1   # rt_raster_mesh_dynamic
@@ -362,6 +371,13 @@ SIGNATURES = {
     "rt_mesh_motion_latch": (C.c_int, [C.c_void_p]),
     "rt_mesh_hit_prev_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rt_mesh_hit_prev_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_normals_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_mesh_vertex_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_hit_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_normals_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_vertex_normals": (C.c_int, [_FP, C.POINTER(C.c_int32), C.c_int, _U32P, C.c_int, _FP]),
+    "rt_hit_normals": (C.c_int, [_FP, C.POINTER(C.c_int32), C.c_int, _U32P, _FP, C.c_int, C.c_void_p, C.c_int, _FP]),
+    "rt_debug_normal_pack": (C.c_int, [_U32P, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_hit_motion": (C.c_int, [C.c_void_p, _FP, _FP, C.c_int, C.c_void_p, _FP, C.c_int, _FP, _FP]),
     "rt_mesh_morph_upload": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32), _U32P, _FP, C.c_int]),
     "rt_mesh_morph_base": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -715,6 +731,73 @@ def debug_morph_pack(n_verts, target_first, vert_idx, deltas) -> dict:
 
     info = RtMorphInfo.from_buffer_copy(read(RT_MORPH_ARRAY_INFO).tobytes())
     return {"info": info, "slice_first": read(RT_MORPH_ARRAY_SLICE_FIRST).view(np.uint32), "entries": read(RT_MORPH_ARRAY_ENTRIES).view(np.uint32).reshape(-1, 4)}
+
+
+def _normal_mesh(who, tris12, order, indices):
+    """tris12 / order / indices as contiguous float32 [T,12] / int32 [T] / uint32 [3T]; what a cast would hide is refused here."""
+    t = _f32(tris12).reshape(-1, 12)
+    o, ix = np.asarray(order).reshape(-1), np.asarray(indices).reshape(-1)
+    if o.size != t.shape[0] or ix.size != 3 * t.shape[0]:
+        raise RtError(RT_ERR_INVALID, f"{who}: {t.shape[0]} rows, {o.size} order entries and {ix.size} indices")
+    if (o.size and (o.min() < -2 ** 31 or o.max() >= 2 ** 31)) or (ix.size and (ix.min() < 0 or ix.max() >= 2 ** 32)):
+        raise RtError(RT_ERR_INVALID, f"{who}: order must fit int32 and indices uint32")
+    return t, np.ascontiguousarray(o, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.uint32)
+
+
+def vertex_normals(tris12, order, indices, n_verts) -> np.ndarray:
+    """Area-weighted vertex normals on the host (rt_vertex_normals), the definition Renderer.mesh_vertex_normals is tested against: tris12 [T,12] the
+    rows of the triangle array, order [T] row -> input triangle (Renderer.mesh_order), indices the 3T indices of the input triangles -> normals
+    [n_verts,3] float32; three +0 for a vertex whose face vectors have no sum with a direction."""
+    t, o, ix = _normal_mesh("vertex_normals", tris12, order, indices)
+    out = np.zeros((max(int(n_verts), 0), 3), np.float32)
+    rc = lib().rt_vertex_normals(_fp(t), o.ctypes.data_as(_I32P), t.shape[0], ix.ctypes.data_as(_U32P), int(n_verts), _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_vertex_normals: no triangles, no vertices, an index out of range or an order entry outside the triangles")
+    return out
+
+
+def hit_normals(tris12, order, indices, normals, hits) -> np.ndarray:
+    """Shading normals of hits on the dynamic mesh on the host (rt_hit_normals), the definition Renderer.mesh_hit_normals and the frames' GNRM target
+    are tested against: tris12 / order / indices as for vertex_normals, normals [V,3] (or [V,4], the device layout) the vertex normals, hits a
+    RayHits / SceneHits or its [N,4] float32 record array -> [N,3] float32; zeros for a prim outside the triangles."""
+    rec = np.ascontiguousarray(hits.record if isinstance(hits, RayHits) else hits)
+    if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+        raise RtError(RT_ERR_INVALID, f"hit_normals: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+    t, o, ix = _normal_mesh("hit_normals", tris12, order, indices)
+    nv = _f32(normals)
+    if nv.ndim != 2 or nv.shape[1] not in (3, 4):
+        raise RtError(RT_ERR_INVALID, f"hit_normals: normals must be [V,3] or [V,4], got {nv.shape}")
+    nv = np.ascontiguousarray(nv[:, :3])
+    out = np.zeros((rec.shape[0], 3), np.float32)
+    rc = lib().rt_hit_normals(_fp(t), o.ctypes.data_as(_I32P), t.shape[0], ix.ctypes.data_as(_U32P), _fp(nv), nv.shape[0], C.c_void_p(rec.ctypes.data),
+                              rec.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_hit_normals: no triangles, no vertices, or a hit row whose order entry or indices are out of range")
+    return out
+
+
+def debug_normal_pack(indices, n_verts) -> dict:
+    """What Renderer.mesh_normals_enable would put on the device for this index buffer, without one (rt_debug_normal_pack): "slice_first" uint32
+    [nSlices+1] in entries, "entries" int32 [paddedEntries] (NORMAL_PAD_ENTRY marks no incidence) and "info", an RtNormalInfo."""
+    ix = np.asarray(indices).reshape(-1)
+    if ix.size and (ix.min() < 0 or ix.max() >= 2 ** 32):
+        raise RtError(RT_ERR_INVALID, "debug_normal_pack: indices must fit uint32")
+    ix = np.ascontiguousarray(ix, dtype=np.uint32)
+    args = (ix.ctypes.data_as(_U32P), ix.size, int(n_verts))
+
+    def read(which):
+        size = C.c_size_t()
+        rc = lib().rt_debug_normal_pack(*args, which, None, 0, C.byref(size))
+        out = np.zeros(size.value, dtype=np.uint8)
+        if rc == RT_OK and size.value:
+            rc = lib().rt_debug_normal_pack(*args, which, C.c_void_p(out.ctypes.data), out.size, C.byref(size))
+        if rc != RT_OK:
+            raise RtError(rc, "rt_debug_normal_pack: an index buffer rt_mesh_normals_enable would refuse" if rc == RT_ERR_INVALID else
+                          "rt_debug_normal_pack: the padded adjacency reaches 2^31 entries")
+        return out
+
+    info = RtNormalInfo.from_buffer_copy(read(RT_NORMAL_ARRAY_INFO).tobytes())
+    return {"info": info, "slice_first": read(RT_NORMAL_ARRAY_SLICE_FIRST).view(np.uint32), "entries": read(RT_NORMAL_ARRAY_ENTRIES).view(np.int32)}
 
 
 def bvh_layout(n_tris: int) -> RtBvhLayout:
@@ -1375,6 +1458,53 @@ class Renderer:
         cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
         return out
 
+    # ---- smooth vertex normals: recomputed on the device behind every update, blended at mesh hits by frames and by mesh_hit_normals
+    def mesh_normals_enable(self, on=True):
+        """Keep area-weighted vertex normals of the dynamic mesh (rt_mesh_normals_enable): every update then recomputes them from its new rows, and
+        frames of the mesh's scene with useBVH == 1 shade mesh hits with the smooth normal.  Packs the adjacency on the host, allocates five arrays and
+        computes the normals if there is a tree; may synchronise.  on=False releases them.  Off until asked for."""
+        self._check(lib().rt_mesh_normals_enable(self._h, 1 if on else 0))
+
+    def mesh_vertex_normals(self, as_torch=None):
+        """The device array of vertex normals: a float32 [V,4] tensor (nx, ny, nz, 0) that aliases it (as mesh_positions; written on stream() by the
+        update calls), else (pointer, bytes).  vertex_normals of debug_read_scene("tris"), mesh_order() and the indices, bit for bit."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_vertex_normals(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 4, as_torch)
+
+    def mesh_normal_rows(self) -> np.ndarray:
+        """The corner normals as float32 [nTris,12] rows, three (nx, ny, nz, 0) per row (rt_debug_read_scene: synchronises); empty while normals are
+        not enabled or before the first rebuild.  Row i belongs to input triangle mesh_order()[i], as row i of debug_read_scene("tris")."""
+        return self.debug_read_scene(RT_SCENE_ARRAY_NORMAL_ROWS).view(np.float32).reshape(-1, 12)
+
+    def mesh_hit_normals(self, hits):
+        """The shading normal of each hit: float32 [N,3], hit_normals bit for bit -- on a pixel's pick, that pixel's GNRM before the conversion to half;
+        zeros for a miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in, numpy
+        out (rt_mesh_hit_normals_host: synchronises); a torch tensor on this context's device takes the zero-copy path of mesh_hit_parts: enqueued
+        on the library stream, ordered against torch's current stream, no host wait."""
+        rec = hits.record if isinstance(hits, RayHits) else hits
+        if isinstance(rec, np.ndarray):
+            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+                raise RtError(RT_ERR_INVALID, f"mesh_hit_normals: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+            rec = np.ascontiguousarray(rec)
+            n = rec.shape[0]
+            out = np.zeros((n, 3), np.float32)
+            self._check(lib().rt_mesh_hit_normals_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+            raise RtError(RT_ERR_INVALID, f"mesh_hit_normals: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+        rec = rec.contiguous()
+        n = rec.shape[0]
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
+        self._check(lib().rt_mesh_hit_normals(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        return out
+
     # ---- morph targets (DESIGN.md 14.11): sparse deltas blended on the device under a weight table, before the skin or straight into the positions
     def mesh_morph_upload(self, target_first, vert_idx, deltas, base=None):
         """The morph targets of the current mesh (rt_mesh_morph_upload), in morph_positions' sparse form (morph_targets_from_dense makes it from dense
@@ -1430,7 +1560,7 @@ class Renderer:
 
     def debug_read_scene(self, which) -> np.ndarray:
         """One device scene array as bytes (uint8), padding included; empty when the scene has no such array.  which: RT_SCENE_ARRAY_* or its name."""
-        which = {**SCENE_ARRAYS, **SCENE_ARRAYS_OPTIONAL}[which] if isinstance(which, str) else int(which)
+        which = {**SCENE_ARRAYS, **SCENE_ARRAYS_OPTIONAL, **SCENE_ARRAYS_MESH}[which] if isinstance(which, str) else int(which)
         n = C.c_size_t()
         self._check(lib().rt_debug_read_scene(self._h, which, None, 0, C.byref(n)))
         out = np.zeros(n.value, np.uint8)

@@ -21,6 +21,7 @@
 #include "rt_bvh_cost.hpp"
 #include "rt_mesh.hpp"
 #include "rt_morph_pack.hpp"
+#include "rt_normal_pack.hpp"
 #include "rt_scene_pack.hpp"
 #include "rt_wave_plan.hpp"
 #include "rt_wave.hpp"
@@ -744,8 +745,11 @@ static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = 
     if (rc != RT_OK) return rc;
     const char *err = nullptr;
     const float *gatherM = parts ? nullptr : (M16 ? M16 : kIdentity);   // null: the part-aware gather
+    const bool orderWas = refit && rtl::mesh_order_written(c->mesh);
     rc = refit ? rtl::mesh_refit(c->mesh, st, gatherM, &err) : rtl::mesh_rebuild(c->mesh, st, gatherM, &err);
     if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
+    // smooth normals: the update derived the order array for itself, on `st`
+    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
     // ... and whatever a lane is given next waits for it
     rc = mesh_before_lanes(c, st);
     if (rc != RT_OK) return rc;
@@ -848,6 +852,87 @@ int rt_mesh_hit_prev_points_host(RtContext *c, const RtHit *hits, const float *p
     const int qr = rt_mesh_hit_prev_points(c, (const RtHit *)base, (const float *)(base + hB), n, (float *)(base + hB + pB));
     if (qr != RT_OK) { (void)sync_all(c); return qr; }
     HIP_TRY(c, hipMemcpyAsync(prevPoints, base + hB + pB, N * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return RT_OK;
+    });
+}
+
+// ---- smooth vertex normals: rt_normal_pack.cpp packs the adjacency, rt_mesh.hip recomputes the normals inside every update; this file
+// owns enabling and the hit query
+int rt_mesh_normals_enable(RtContext *c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_normals_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    return guarded(c, "rt_mesh_normals_enable", [&]() -> int {
+        (void)hipSetDevice(c->cfg.device);
+        HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
+        if (!on) { rtl::mesh_normals_release(c->mesh); return RT_OK; }
+        const int nIdx = rtl::mesh_layout(c->mesh).nTris * 3, nVerts = rtl::mesh_verts(c->mesh);
+        std::vector<uint32_t> idx((size_t)nIdx);
+        HIP_TRY(c, hipMemcpy(idx.data(), rtl::mesh_indices(c->mesh), (size_t)nIdx * 4, hipMemcpyDeviceToHost));
+        std::string perr;
+        int rc = rtl::normal_validate(idx.data(), nIdx, nVerts, perr);
+        rtl::NormalPlan plan;
+        if (rc == RT_OK) rc = rtl::normal_plan(idx.data(), nIdx, nVerts, plan, perr);
+        if (rc != RT_OK) return fail(c, rc, "rt_mesh_normals_enable: %s", perr.c_str());
+        std::vector<int32_t> entries;
+        rtl::normal_fill(plan, idx.data(), nIdx, entries);
+        const bool orderWas = rtl::mesh_order_written(c->mesh);
+        hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+        const char *err = nullptr;
+        rc = rtl::mesh_normals_create(c->mesh, st, plan.sliceFirst.data(), entries.data(), plan.info, &err);
+        if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
+        if (rc != RT_OK) return fail(c, rc, "rt_mesh_normals_enable: %s", err ? err : "allocation failed");
+        return RT_OK;
+    });
+}
+
+int rt_mesh_vertex_normals(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_vertex_normals: no mesh (rt_mesh_upload first)");
+    if (!rtl::mesh_vertex_normals(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_vertex_normals: normals are not enabled (rt_mesh_normals_enable first)");
+    *devPtr = const_cast<float4 *>(rtl::mesh_vertex_normals(c->mesh));
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 16;
+    return RT_OK;
+}
+
+static int hit_normals_args(RtContext *c, const char *who, const RtHit *hits, int n, const float *normals) {
+    if (n < 0 || (n > 0 && !hits) || !normals) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits and normals are needed)", who, n);
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
+    if (!rtl::mesh_normal_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: normals are not enabled (rt_mesh_normals_enable first)", who);
+    return RT_OK;
+}
+
+int rt_mesh_hit_normals(RtContext *c, const RtHit *hits, int n, float *normals) {
+    if (!c) return RT_ERR_INVALID;
+    int rc = hit_normals_args(c, "rt_mesh_hit_normals", hits, n, normals);
+    if (rc != RT_OK) return rc;
+    if (((uintptr_t)hits & 15u) || ((uintptr_t)normals & 3u)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_normals: hits must be 16-byte aligned, normals 4-byte aligned");
+    if (n == 0) return RT_OK;
+    (void)hipSetDevice(c->cfg.device);
+    const char *err = nullptr;
+    rc = rtl::mesh_hit_normals(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, n, normals, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_normals: %s", err ? err : "launch failed");
+    return RT_OK;
+}
+
+int rt_mesh_hit_normals_host(RtContext *c, const RtHit *hits, int n, float *normals) {
+    if (!c) return RT_ERR_INVALID;
+    const int ar = hit_normals_args(c, "rt_mesh_hit_normals_host", hits, n, normals);
+    if (ar != RT_OK) return ar;
+    if (n == 0) return RT_OK;
+    return guarded(c, "rt_mesh_hit_normals_host", [&]() -> int {
+    (void)hipSetDevice(c->cfg.device);
+    const size_t N = (size_t)n, hB = N * sizeof(RtHit), total = hB + N * 12;   // hits | normals
+    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
+    const int sr = ensure_staging(c, total);
+    if (sr != RT_OK) return sr;
+    char *base = (char *)c->dStaging;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
+    const int qr = rt_mesh_hit_normals(c, (const RtHit *)base, n, (float *)(base + hB));
+    if (qr != RT_OK) { (void)sync_all(c); return qr; }
+    HIP_TRY(c, hipMemcpyAsync(normals, base + hB, N * 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return RT_OK;
     });
@@ -1230,6 +1315,7 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
         case RT_SCENE_ARRAY_IMPL_QNODES4: src = c->dIQ4; n = implNodes * 48; break;
         case RT_SCENE_ARRAY_IMPL_LEAFBOX: src = c->dILeafBox; n = (implNodes + 1) * 32; break;
         case RT_SCENE_ARRAY_PREV_TRIS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_prev_tris(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
+        case RT_SCENE_ARRAY_NORMAL_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_normal_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
     }
     if (!have || !src) return RT_OK;
@@ -1456,6 +1542,8 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     fr.giBounces = c->giBounces;
     // object motion: primary hits of the dynamic mesh's own scene; the hybrid scene keeps the reference's motion
     fr.prevTris = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_prev_tris(c->mesh) : nullptr;
+    // smooth normals: mesh hits of the dynamic mesh's own scene; the hybrid scene keeps the face normal
+    fr.nrmRows = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_normal_rows(c->mesh) : nullptr;
     // Lane = frame index mod nLanes = index of the COLOR0 buffer this frame writes: consecutive frames rotate over the lanes'
     // streams and overlap everywhere except at the temporal resolve (the only read of the previous frame), and every later
     // reader of a COLOR0 buffer (gather, assemble) is stream-ordered before the next writer of the same buffer.

@@ -12,6 +12,7 @@
 #include "../../include/rt_mi355.h"
 #include "rt_device_math.hpp"
 #include "rt_mesh_motion.hpp"
+#include "rt_mesh_normals.hpp"
 
 #pragma clang fp contract(off)
 
@@ -301,6 +302,38 @@ RT_DEV V3 prevHitPoint(const float4 *tris, const float4 *prevTris, int tri, V3 r
     float prev[3];
     rtmotion::prev_point(Tf, Pf, a, b, x, prev);
     return mk3(prev[0], prev[1], prev[2]);
+}
+
+// Smooth normals: the shading normal of the hit of the ray (ro, rd) on row `tri`.  nrmRows == null (no dynamic mesh, or normals not
+// enabled): tri_normal, the reference's rule.  Otherwise (a, b) are the hit's barycentrics with prevHitPoint's operations in their order -- the u, v
+// rt_pick_pixels returns for the pixel -- and the rest is rt_hit_normals' rule on the row's three corner normals (rt_mesh_normals.hpp).
+// The steps are taken one after the other -- the row for (a, b), then the corner normals, and the row again only where the blend has no answer -- so that
+// the shading kernels hold one of them at a time and keep the registers they had.
+RT_DEV V3 hitNormal(const float4 *tris, const float4 *nrmRows, int tri, V3 ro, V3 rd) {
+    const float4 *T = tris + (size_t)tri * 3;
+    if (!nrmRows) return normalize(cross(f4xyz(T[1]), f4xyz(T[2])));
+    float a, b;
+    {
+        const V3 v0 = f4xyz(T[0]), e1 = f4xyz(T[1]), e2 = f4xyz(T[2]);
+        const V3 pvec = cross(rd, e2);
+        const float invDet = 1.0f / dot(e1, pvec);
+        const V3 tvec = ro - v0;
+        a = dot(tvec, pvec) * invDet;
+        b = dot(rd, cross(tvec, e1)) * invDet;
+    }
+    const float4 *N = nrmRows + (size_t)tri * 3;
+    const float4 c0 = N[0], c1 = N[1], c2 = N[2];
+    const float n0[3] = {c0.x, c0.y, c0.z}, n1[3] = {c1.x, c1.y, c1.z}, n2[3] = {c2.x, c2.y, c2.z};
+    float out[3];
+    if (!rtnormal::blend_normals(n0, n1, n2, a, b, out)) {
+        int again = tri;
+        asm volatile("" : "+v"(again));   // a second read of the row, not the first one kept alive across the blend
+        const float4 *R = tris + (size_t)again * 3;
+        const float4 r1 = R[1], r2 = R[2];
+        const float e1[3] = {r1.x, r1.y, r1.z}, e2[3] = {r2.x, r2.y, r2.z};
+        rtnormal::face_normal(e1, e2, out);
+    }
+    return mk3(out[0], out[1], out[2]);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -66,6 +66,8 @@ struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it thr
     float ld2K[RT_MAX_BATCH][2];      // ld2(u.frameIndex + k) = (halton(u.frameIndex + k + 1, 2), halton(.., 3)) of the batch's frames: cpOffset's frame-wide term (Frag::ld2x)
     const float4 *prevTris = nullptr; // object motion: the dynamic mesh's previous pose, row for row beside sc.tris; null = off.  Last, so that every
                                       // offset above, and DevScene as a kernel argument, stay what they were
+    const float4 *nrmRows = nullptr;  // smooth normals: the dynamic mesh's corner normals, row for row beside sc.tris; null = off, the face normal.
+                                      // Behind prevTris for the same reason
 };
 
 struct Targets {

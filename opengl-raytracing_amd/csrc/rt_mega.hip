@@ -16,6 +16,7 @@ namespace {
 template <bool COUNT>
 struct InlineTracer {
     const DevScene *sc;
+    const float4 *nrm;   // DevFrame::nrmRows: the bounce hit's smooth normal (null: the face normal)
     float eps, inf;
     StackEntry *stk;
     Work *w;
@@ -33,7 +34,7 @@ struct InlineTracer {
         int tri;
         if (!closest(ro, rd, t, tri)) return 0;
         hp = ro + rd * t;
-        hn = tri_normal(*sc, tri);
+        hn = hitNormal(sc->tris, nrm, tri, ro, rd);
         return 1;
     }
     RT_DEV bool ao(int, V3 org, V3 dir, float radius) {
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr
 
         if (u.useBVH == 1) {
             InlineTracer<COUNT> tr;
-            tr.sc = &fr->sc; tr.eps = u.eps; tr.inf = u.inf; tr.w = &w;
+            tr.sc = &fr->sc; tr.nrm = fr->nrmRows; tr.eps = u.eps; tr.inf = u.inf; tr.w = &w;
             tr.stk = &lds_stack[(tid >> 6) * STACK * 64 + (tid & 63)];
             const bool bvhOn = (u.nodeCount > 0 && u.triCount > 0);
             // The SPP primary rays of rt.frag:79-86 are identical (only the seed changes): trace once,
@@ -90,12 +91,12 @@ __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr
             }
             if (hitAny) {
                 const V3 hp = camPos + dir * tHit;
-                const V3 hn = tri_normal(fr->sc, triHit);
+                const V3 hn = hitNormal(fr->sc.tris, fr->nrmRows, triHit, camPos, dir);
                 if (COUNT) w.hitPixels++;
                 V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, triHit, camPos, dir, hp), u.prevViewProj), currNDC = ndcFromWorld(hp, u.currViewProj);
                 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
                 gpos = mk4(hp.x, hp.y, hp.z, 1.0f);
-                V3 nn = normalize(hn);
+                V3 nn = fr->nrmRows ? hn : normalize(hn);   // the smooth normal is rt_hit_normals' to the bit: GNRM is f16 of it, not of a second normalisation
                 gnrm = mk4(nn.x, nn.y, nn.z, 0.0f);
                 float ao = 1.0f;
                 if (u.enableAO == 1) {

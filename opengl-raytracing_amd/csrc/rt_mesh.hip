@@ -231,6 +231,12 @@ struct Mesh {
     // carries them across in; allocated by mesh_motion_create, not in `owned`
     float4 *dPrevTris = nullptr, *dPrevByInput = nullptr;
     size_t motionBytes = 0;
+    // smooth normals: the packed vertex -> triangle adjacency, the face vectors by input triangle, one normal per vertex and the
+    // corner normals row for row beside the triangle array; allocated by mesh_normals_create, not in `owned`
+    uint32_t *dNrmSliceFirst = nullptr;
+    int32_t *dNrmEntries = nullptr;
+    float4 *dFaceByInput = nullptr, *dVertNrm = nullptr, *dNrmRows = nullptr;
+    size_t normalBytes = 0;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -420,6 +426,7 @@ void mesh_destroy(Mesh *m) {
     mesh_skin_release(m);
     mesh_morph_release(m);
     mesh_motion_release(m);
+    mesh_normals_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -443,6 +450,15 @@ size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }
 #define REB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); return RT_ERR_HIP; } } while (0)
 
 namespace {
+// smooth normals behind the new rows of an update: the order array first -- a rebuild has just invalidated it -- then the three kernels
+int normals_update(Mesh *m, hipStream_t st, const char **err) {
+    const int *order = nullptr;
+    const int rc = mesh_order(m, st, &order, err);
+    if (rc != RT_OK) return rc;
+    normals_launch_update(st, m->sc.tris, order, m->dIdx, m->lay.nTris, m->dNrmSliceFirst, m->dNrmEntries, m->nVerts, m->dFaceByInput, m->dVertNrm, m->dNrmRows);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
 // every record form from the bounds and the triangle array, through the tables: the tail of a rebuild and of a refit
 void emit_records(Mesh *m, hipStream_t st) {
     const BvhLayout &L = m->lay;
@@ -495,6 +511,7 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
         else REB_TRY(hipMemcpyAsync(m->dPrevTris, m->sc.tris, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     }
     m->permCur = cur;
+    if (m->dNrmRows) return normals_update(m, st, err);
     return RT_OK;
 }
 
@@ -516,6 +533,7 @@ int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     }
     emit_records(m, st);
     REB_TRY(hipGetLastError());
+    if (m->dNrmRows) return normals_update(m, st, err);
     return RT_OK;
 }
 
@@ -676,6 +694,51 @@ int mesh_motion_latch(Mesh *m, hipStream_t st, const char **err) {
 int mesh_hit_prev_points(Mesh *m, hipStream_t st, const void *hits, const float *points, int n, float *prevPoints, const char **err) {
     if (!m->dPrevTris || m->permCur < 0) return RT_ERR_INVALID;
     motion_launch_hit_prev_points(st, hits, points, n, m->sc.tris, m->dPrevTris, m->lay.nTris, prevPoints);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_normals_release(Mesh *m) {
+    for (void *p : {(void *)m->dNrmSliceFirst, (void *)m->dNrmEntries, (void *)m->dFaceByInput, (void *)m->dVertNrm, (void *)m->dNrmRows}) if (p) (void)hipFree(p);
+    m->dNrmSliceFirst = nullptr; m->dNrmEntries = nullptr; m->dFaceByInput = m->dVertNrm = m->dNrmRows = nullptr;
+    m->scratchBytes -= m->normalBytes;
+    m->normalBytes = 0;
+}
+
+int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err) {
+    mesh_normals_release(m);
+    const size_t nt = (size_t)m->lay.nTris, nv = (size_t)m->nVerts;
+    auto make = [&](auto **p, const void *src, size_t bytes) -> hipError_t {   // src == nullptr: zeros
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e != hipSuccess) return e;
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+        ++m->allocations;
+        m->normalBytes += bytes; m->scratchBytes += bytes;
+        if (!src) return hipMemset(q, 0, std::max<size_t>(bytes, 16));
+        return bytes ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    };
+    hipError_t e = make(&m->dNrmSliceFirst, sliceFirst, ((size_t)info.nSlices + 1) * 4);
+    if (e == hipSuccess) e = make(&m->dNrmEntries, entries, (size_t)info.paddedEntries * 4);
+    if (e == hipSuccess) e = make(&m->dFaceByInput, nullptr, nt * 16);
+    if (e == hipSuccess) e = make(&m->dVertNrm, nullptr, nv * 16);
+    if (e == hipSuccess) e = make(&m->dNrmRows, nullptr, nt * 48);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_normals_release(m); return RT_ERR_HIP; }
+    if (m->permCur >= 0) {
+        const int rc = normals_update(m, st, err);
+        if (rc == RT_OK) e = hipDeviceSynchronize();
+        if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_normals_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
+    }
+    return RT_OK;
+}
+
+const float4 *mesh_vertex_normals(const Mesh *m) { return m->dVertNrm; }
+const float4 *mesh_normal_rows(const Mesh *m) { return m->dNrmRows; }
+
+int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *normals, const char **err) {
+    if (!m->dNrmRows || m->permCur < 0) return RT_ERR_INVALID;
+    normals_launch_hit_normals(st, hits, n, m->sc.tris, m->dNrmRows, m->lay.nTris, normals);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

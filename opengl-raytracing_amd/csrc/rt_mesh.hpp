@@ -139,6 +139,24 @@ void motion_launch_gather(hipStream_t st, const float4 *byInput, const int *perm
 void motion_launch_hit_prev_points(hipStream_t st, const void *hits, const float *points, int n, const float4 *tris, const float4 *prevTris, int nTris,
                                    float *prevPoints);
 
+// Smooth vertex normals.  mesh_normals_create: the packed adjacency rt_normal_pack.cpp made of the mesh's own index buffer
+// (sliceFirst: info.nSlices + 1 words; entries: info.paddedEntries words); allocates it, the face vectors by input triangle, the vertex normals
+// (nVerts float4) and nrmRows (nTris rows of three float4, row i beside row i of the triangle array) and, when there is a tree, computes the normals on
+// `st`; allocates, copies and waits for the device; the caller has waited for every lane.  mesh_normals_release: the five arrays freed (callers have
+// synchronised).  While the arrays exist mesh_rebuild and mesh_refit recompute the normals behind their new rows on their stream, inside their own
+// sequence of launches: no allocation, no host wait.
+int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err);
+void mesh_normals_release(Mesh *m);
+const float4 *mesh_vertex_normals(const Mesh *m);   // device, nVerts float4 (xyz, w = 0); null: normals are not enabled
+const float4 *mesh_normal_rows(const Mesh *m);      // device, nTris x 3 float4; null: normals are not enabled
+// Enqueues normals[i] = the shading normal of hit i (rt_hit_normals' out3) on `st` for n RtHit records (device pointers).  RT_ERR_INVALID without the
+// arrays or without a tree.
+int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *normals, const char **err);
+// rt_mesh_normals.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
+void normals_launch_update(hipStream_t st, const float4 *tris, const int *order, const uint32_t *idx, int nTris, const uint32_t *sliceFirst, const int32_t *entries,
+                           int nVerts, float4 *faceByInput, float4 *vertNrm, float4 *nrmRows);
+void normals_launch_hit_normals(hipStream_t st, const void *hits, int n, const float4 *tris, const float4 *nrmRows, int nTris, float *normals);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

@@ -1670,13 +1670,14 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         return false;
     }
 };
-struct GenGiTracer {       // reads the bounce result, records the shadow rays at the bounce hit
+template <bool SMOOTH> struct GenGiTracer {       // reads the bounce result, records the shadow rays at the bounce hit
     static constexpr bool kSkipUnlitDisk = true;
     static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     unsigned long long *stat;
     RT_DEV void disk_stat(int, bool unlit, bool skipped) { if (stat) disk_stat_add(stat + 5, unlit, skipped); }
     WaveBuf wb;
     const DevScene *sc;
+    const float4 *nrm;   // SMOOTH: DevFrame::nrmRows, the bounce hit's corner normals
     float inf;
     uint32_t j;
     int s;
@@ -1699,17 +1700,18 @@ struct GenGiTracer {       // reads the bounce result, records the shadow rays a
         int tri = wb.giTri[a];
         if (tri < 0) return 0;
         hp = ro + rd * wb.giT[a];
-        hn = tri_normal(*sc, tri);
+        hn = SMOOTH ? hitNormal(sc->tris, nrm, tri, ro, rd) : tri_normal(*sc, tri);
         return 1;
     }
     RT_DEV bool ao(int, V3, V3, float) { return false; }
 };
-struct CombineTracer {     // reads everything
+template <bool SMOOTH> struct CombineTracer {     // reads everything
     static constexpr bool kSkipUnlitDisk = true;
     static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
+    const float4 *nrm;   // SMOOTH: DevFrame::nrmRows, the bounce hit's corner normals
     uint32_t j;
     int s;
     RT_DEV bool shadow(int seg, int k, V3, V3, float, bool matters) {
@@ -1723,14 +1725,14 @@ struct CombineTracer {     // reads everything
         int tri = wb.giTri[a];
         if (tri < 0) return 0;
         hp = ro + rd * wb.giT[a];
-        hn = tri_normal(*sc, tri);
+        hn = SMOOTH ? hitNormal(sc->tris, nrm, tri, ro, rd) : tri_normal(*sc, tri);
         return 1;
     }
     RT_DEV bool ao(int i, V3, V3, float radius) { return radius > 0.0f && wb.occ1[(uint32_t)i * wb.CH + j] != 0; }
 };
 
 struct HitCtx { Frag F; V3 dir, hp, hn; int px, py; uint32_t slot; };
-RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
+template <bool SMOOTH> RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
     HitCtx c;
     c.slot = h.slot;
     slot_to_pixel(fr->g, h.slot, c.px, c.py);
@@ -1740,7 +1742,7 @@ RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
     c.F.ld2x = fr->ld2K[k][0]; c.F.ld2y = fr->ld2K[k][1];   // cpOffset's halton pair, once per sub-frame on the host
     c.dir = primaryDirK(fr, k, c.px, c.py);
     c.hp = ld3(fr->u.camPos) + c.dir * h.t;
-    c.hn = tri_normal(fr->sc, h.tri);
+    c.hn = SMOOTH ? hitNormal(fr->sc.tris, fr->nrmRows, h.tri, ld3(fr->u.camPos), c.dir) : tri_normal(fr->sc, h.tri);
     return c;
 }
 // live hits of the chunk starting at c0: |[c0, c0+CH) ∩ [0, hits)|, written without a wrapping subtraction (hipcc -O3 was
@@ -1748,7 +1750,7 @@ RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
 RT_DEV uint32_t chunk_live(const WaveBuf &wb, uint32_t c0) { uint32_t h = wb.counts[1]; return min(h, c0 + wb.CH) - min(h, c0); }
 
 // ---- stage: gen_direct  (thread = (hit j, sample s), s-major so a wave shares s) -----------------
-__global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, unsigned long long *diskStat) {
+template <bool SMOOTH> RT_DEV void gen_direct_body(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, unsigned long long *diskStat) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
@@ -1761,7 +1763,7 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
     tr.wb = wb; tr.j = j; tr.s = s; tr.shadowMask = 0; tr.giCast = false; tr.stat = diskStat;
     tr.giRo = mk3(0.0f); tr.giRd = mk3(0.0f);
     if (mine) {
-        HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+        HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
         const int SPP = max(u.spp, 1);
         const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
         (void)directLightBVH(tr, c.F, SEG_DIRECT, c.hp, c.hn, seed, -c.dir);
@@ -1804,6 +1806,9 @@ __global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__
         }
     }
 }
+// the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
+__global__ __launch_bounds__(256) void k_gen_direct(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, unsigned long long *diskStat) { gen_direct_body<false>(fr, wb, c0, diskStat); }
+__global__ __launch_bounds__(256) void k_gen_direct_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, unsigned long long *diskStat) { gen_direct_body<true>(fr, wb, c0, diskStat); }
 
 // ---- stage: gen_gi -------------------------------------------------------------------------------
 // rt_debug_gi_list: two sums over the bounce-hit generators -- (hit, sample) pairs visited, pairs shaded.  One lane per wave adds, once the entry switched counting on.
@@ -1813,7 +1818,7 @@ RT_DEV void gi_list_stat_add(unsigned long long *stat, bool visited, bool shaded
     if (vi) atomicAdd(&stat[0], (unsigned long long)__popcll(vi));
     if (sh) atomicAdd(&stat[1], (unsigned long long)__popcll(sh));
 }
-__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
+template <bool SMOOTH> RT_DEV void gen_gi_body(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
@@ -1829,25 +1834,27 @@ __global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr,
     if (!mine) return;
     wb.giPos[a] = bounced ? (int)pos : -1;
     if (!bounced) return;
-    GenGiTracer tr;
-    tr.wb = wb; tr.sc = &fr->sc; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
-    HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+    GenGiTracer<SMOOTH> tr;
+    tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
+    HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
     const int SPP = max(u.spp, 1);
     const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
     Work w;
-    (void)oneBounceGIBVH<GenGiTracer, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
+    (void)oneBounceGIBVH<GenGiTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
     if (pos < wb.q2Stride)
         for (int k = 0; k < 6; ++k)
             if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
 }
+// the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
+__global__ __launch_bounds__(256) void k_gen_gi(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) { gen_gi_body<false>(fr, wb, c0, giCount, diskStat, listStat); }
+__global__ __launch_bounds__(256) void k_gen_gi_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) { gen_gi_body<true>(fr, wb, c0, giCount, diskStat, listStat); }
 
 // The same stage behind a bounce probe (RT_BOUNCE_PROBE, giPerm == null): the probe left the queue addresses of the bounce rays that hit in a dense list
 // (BounceProbeSrc::hitters, re-traced closest-hit since), so only those are visited -- on the bench view 54 419 of 29.6 M (hit, sample) pairs per launch set --
 // instead of every pair.  A fixed grid strides over the list, whose length only the device knows.  giPos is written for the pairs that bounced and for no other:
 // CombineTracer reads it behind gi() == 1 alone, k_gen_gi_overflow walks the same list.  Queue 2 positions are dealt in list order instead of pair order; an
 // entry's position is only ever reached through giPos, so frames do not change.
-__global__ __launch_bounds__(256) void k_gen_gi_listed(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *hitList, const uint32_t *hitCount,
-                                                       uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
+template <bool SMOOTH> RT_DEV void gen_gi_listed_body(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *hitList, const uint32_t *hitCount, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) {
     const RtUniforms &u = fr->u;
     const uint32_t n = min(*hitCount, wb.CH * (uint32_t)wb.SPP);
     for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {   // whole workgroups: block_append
@@ -1861,30 +1868,34 @@ __global__ __launch_bounds__(256) void k_gen_gi_listed(const DevFrame *__restric
         const int s = (int)(a / wb.CH);
         const uint32_t j = a % wb.CH;
         wb.giPos[a] = (int)pos;
-        GenGiTracer tr;
-        tr.wb = wb; tr.sc = &fr->sc; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
-        HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+        GenGiTracer<SMOOTH> tr;
+        tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.inf = u.inf; tr.j = j; tr.s = s; tr.pos = pos; tr.shadowMask = 0; tr.stat = diskStat;
+        HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
         const int SPP = max(u.spp, 1);
         const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
         Work w;
-        (void)oneBounceGIBVH<GenGiTracer, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
+        (void)oneBounceGIBVH<GenGiTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
         if (pos < wb.q2Stride)
             for (int k = 0; k < 6; ++k)
                 if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
     }
 }
+// the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
+__global__ __launch_bounds__(256) void k_gen_gi_listed(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *hitList, const uint32_t *hitCount, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) { gen_gi_listed_body<false>(fr, wb, c0, hitList, hitCount, giCount, diskStat, listStat); }
+__global__ __launch_bounds__(256) void k_gen_gi_listed_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *hitList, const uint32_t *hitCount, uint32_t *giCount, unsigned long long *diskStat, unsigned long long *listStat) { gen_gi_listed_body<true>(fr, wb, c0, hitList, hitCount, giCount, diskStat, listStat); }
 
 // Shadow queue 2 of a large launch set holds a PREDICTED number of bounce hits (rt_wave_render).  The (hit, sample) pairs beyond it -- none, unless the view changed so
 // that more than twice as many bounce rays hit as in any batch before -- get their six shadow rays traced right here, one thread per pair, with the megakernel's any-hit
 // walk (bvh_anyhit: the same answers as the any-hit launch, tests/test_gpu_parity.py), into occOvf.  Launched behind every k_gen_gi of such a set; returns at once when
 // nothing overflowed.  Behind k_gen_gi_listed it walks the probe's hit list (hitList != null) as that kernel did: giPos of a pair outside the list is not written
 // there and may hold an earlier launch set's value.
-struct GenGiOverflowTracer {
+template <bool SMOOTH> struct GenGiOverflowTracer {
     static constexpr bool kSkipUnlitDisk = true;
     static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
+    const float4 *nrm;   // SMOOTH: DevFrame::nrmRows, the bounce hit's corner normals
     float eps;
     StackEntry *stk;
     uint32_t j;
@@ -1902,13 +1913,12 @@ struct GenGiOverflowTracer {
         int tri = wb.giTri[a];
         if (tri < 0) return 0;
         hp = ro + rd * wb.giT[a];
-        hn = tri_normal(*sc, tri);
+        hn = SMOOTH ? hitNormal(sc->tris, nrm, tri, ro, rd) : tri_normal(*sc, tri);
         return 1;
     }
     RT_DEV bool ao(int, V3, V3, float) { return false; }
 };
-__global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries,
-                                                         const uint32_t *hitList, const uint32_t *hitCount) {
+template <bool SMOOTH> RT_DEV void gen_gi_overflow_body(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries, const uint32_t *hitList, const uint32_t *hitCount) {
     if (*giCount <= wb.q2Stride) return;      // the normal case: a small fixed grid that leaves at once (a grid of one thread per pair -- 29 000 workgroups for a batch of eight
                                               // 1080p frames -- cost 2 % of a frame just to be dispatched and return)
     const uint32_t live = chunk_live(wb, c0);
@@ -1924,41 +1934,47 @@ __global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restr
         }
         const int gp = wb.giPos[(uint32_t)s * wb.CH + j];
         if (gp < 0 || (uint32_t)gp < wb.q2Stride) continue;
-        GenGiOverflowTracer tr;
-        tr.wb = wb; tr.sc = &fr->sc; tr.eps = fr->u.eps; tr.j = j; tr.s = s; tr.pos = (uint32_t)gp;
+        GenGiOverflowTracer<SMOOTH> tr;
+        tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.eps = fr->u.eps; tr.j = j; tr.s = s; tr.pos = (uint32_t)gp;
         tr.stk = reinterpret_cast<StackEntry *>(rt_dyn_lds) + (threadIdx.x >> 6) * stackEntries * 64 + (threadIdx.x & 63);
-        HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+        HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
         const int SPP = max(fr->u.spp, 1);
         const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
         Work w;
-        (void)oneBounceGIBVH<GenGiOverflowTracer, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
+        (void)oneBounceGIBVH<GenGiOverflowTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
     }
 }
+// the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
+__global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries, const uint32_t *hitList, const uint32_t *hitCount) { gen_gi_overflow_body<false>(fr, wb, c0, giCount, stackEntries, hitList, hitCount); }
+__global__ __launch_bounds__(256) void k_gen_gi_overflow_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries, const uint32_t *hitList, const uint32_t *hitCount) { gen_gi_overflow_body<true>(fr, wb, c0, giCount, stackEntries, hitList, hitCount); }
 
 // ---- stage: combine (thread = hit) ---------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_combine(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
+template <bool SMOOTH> RT_DEV void combine_body(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= live) return;
-    HitCtx c = load_hit(fr, wb.hits[c0 + j]);
+    HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
     const int SPP = max(u.spp, 1);
-    CombineTracer tr;
-    tr.wb = wb; tr.sc = &fr->sc; tr.j = j; tr.s = 0;
+    CombineTracer<SMOOTH> tr;
+    tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.j = j; tr.s = 0;
     Work w;
     V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir, c.hp), u.prevViewProj), currNDC = ndcFromWorld(c.hp, u.currViewProj);
     V2 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
-    V3 nn = normalize(c.hn);
+    V3 nn = SMOOTH ? c.hn : normalize(c.hn);   // the smooth normal is rt_hit_normals' to the bit: GNRM is f16 of it, not of a second normalisation
     float ao = 1.0f;
     if (u.enableAO == 1) ao = computeAO_BVH(tr, c.F, c.hp, c.hn, c.F.frameIndex);
     V3 frameSum = mk3(0.0f);
     for (int s = 0; s < SPP; ++s) {
         tr.s = s;
         int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
-        frameSum = frameSum + shadeSampleBVH<CombineTracer, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
+        frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
     }
     finish_pixel(fr, wb, (int)c.slot, frameSum, motionOut, mk4(c.hp.x, c.hp.y, c.hp.z, 1.0f), mk4(nn.x, nn.y, nn.z, 0.0f));
 }
+// the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
+__global__ __launch_bounds__(256) void k_combine(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false>(fr, tg, wb, c0); }
+__global__ __launch_bounds__(256) void k_combine_smooth(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true>(fr, tg, wb, c0); }
 
 __global__ void k_accum_tally(const uint32_t *counts, unsigned long long *acc, int frames) {
     // acc: [0] candidates [1] hits [2] primary rays traced [3] shadow [4] bounce [5] bounce-shadow (the traversal kernels add to
@@ -2369,7 +2385,7 @@ static int wave_chunk_direct(LaunchSet &L, int c, uint32_t c0, QueueSrc &q1) {
     const WaveBuf &wb = L.wb;
     const int A = L.plan.ao;
     const unsigned gridHS = (unsigned)((L.CH * (size_t)L.plan.spp + 255) / 256);
-    W_STEP(wave_stage(L, ST_GEN_DIRECT, L.ss, [&] { hipLaunchKernelGGL(k_gen_direct, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr); }));
+    W_STEP(wave_stage(L, ST_GEN_DIRECT, L.ss, [&] { hipLaunchKernelGGL(L.host->nrmRows ? k_gen_direct_smooth : k_gen_direct, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr); }));
     const bool pkAO = w->opt.packetAO && A > 0;
     if (pkAO) W_STEP(wave_stage(L, ST_TRACE_AO, L.st, [&] {
         PacketSrc pk;
@@ -2417,14 +2433,14 @@ static int wave_chunk_bounce(LaunchSet &L, int c, uint32_t c0) {
         const uint32_t *hitList = listed ? wb.giHit : nullptr, *hitCount = listed ? listCount : nullptr;
         unsigned long long *listStat = w->giListOn ? w->giListAcc : nullptr;
         if (listed) {
-            hipLaunchKernelGGL(k_gen_gi_listed, dim3(L.listedBlocks), dim3(256), 0, L.ss, L.dFrame, wb, c0, hitList, hitCount, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+            hipLaunchKernelGGL(L.host->nrmRows ? k_gen_gi_listed_smooth : k_gen_gi_listed, dim3(L.listedBlocks), dim3(256), 0, L.ss, L.dFrame, wb, c0, hitList, hitCount, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
             w->listedLaunches++;
         } else {
-            hipLaunchKernelGGL(k_gen_gi, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
+            hipLaunchKernelGGL(L.host->nrmRows ? k_gen_gi_smooth : k_gen_gi, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], w->diskStatOn ? w->diskAcc : nullptr, listStat);
             w->pairLaunches++;
         }
         if (wb.q2Stride < wb.CH * (uint32_t)SPP)   // a predicted capacity: the pairs beyond it (normally none) trace their rays in place
-            hipLaunchKernelGGL(k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(L.treeDepth, 4) * 8, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], std::max(L.treeDepth, 4), hitList, hitCount);
+            hipLaunchKernelGGL(L.host->nrmRows ? k_gen_gi_overflow_smooth : k_gen_gi_overflow, dim3(std::min<unsigned>(gridHS, (unsigned)w->cus * 4u)), dim3(256), (size_t)256 * std::max(L.treeDepth, 4) * 8, L.ss, L.dFrame, wb, c0, &wb.counts[64 + c], std::max(L.treeDepth, 4), hitList, hitCount);
     });
 }
 
@@ -2455,7 +2471,7 @@ static int wave_chunk(LaunchSet &L, int c) {
     // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
     if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
     const unsigned gridH = (unsigned)((L.CH + 255) / 256);
-    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(k_combine, dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
+    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(L.host->nrmRows ? k_combine_smooth : k_combine, dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
 }
 
 // The steps of a launch set: lane bookkeeping, plan, arenas, cursor table, primary stages, chunks settled, chunk by chunk, tally and resolve.

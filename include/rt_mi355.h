@@ -806,7 +806,47 @@ int rt_mesh_vertex_normals(RtContext *ctx, void **devPtr, size_t *bytes);
  * the first rebuild.  _host: the same with host pointers, staged through the context's buffer; synchronises. */
 int rt_mesh_hit_normals(RtContext *ctx, const RtHit *hits, int n, float *normals);
 int rt_mesh_hit_normals_host(RtContext *ctx, const RtHit *hits, int n, float *normals);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload, rt_mesh_motion_enable and rt_mesh_normals_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- per-vertex colours: EXTENSION, not in the reference, which shades every mesh hit with the constant albedo 0.85 (directLightBVH,
+ * rt_lighting.glsl) -- right for its one grey model, wrong for several parts in one scene.  With colours enabled the mesh keeps, on the device, one colour
+ * per vertex (nVerts float4 (r, g, b, 0): linear RGB albedo, initialised to 0.85) and the three corner colours of every row of the triangle array
+ * (colRows: nTris rows of 48 bytes, three float4 (r, g, b, 0), row i beside row i of the triangle array, its corners those of input triangle
+ * rt_mesh_order's order[i]), exactly as rt_color_rows (below) defines them.  Off until asked for; while it is off every kernel's output is what it was.
+ *   Every update -- rt_mesh_rebuild, rt_mesh_refit, their _parts forms, rt_mesh_update in both modes -- gathers the rows again behind its new rows while
+ * colours are enabled, as part of its own ordered work on rt_stream()'s stream (a rebuild derives the order array for itself first): no allocation, no
+ * host wait; frames and queries already enqueued keep the colours they were enqueued with.  Writing colours does not touch the rows: an update or
+ * rt_mesh_colors_refresh does.
+ *   Frames: while the installed scene is the dynamic mesh's, colours are enabled and u->useBVH == 1, the albedo of a mesh hit is what rt_hit_colors
+ * (below) defines at the hit's barycentrics (those of rt_pick_pixels' u, v): the primary hit's colour is the albedo of its direct light (diffuse term and
+ * sky term) and the factor of its bounce; the bounce hit's colour is the albedo of the bounce hit's direct light -- a red wall tints the floor beside it.
+ * specStrength 0.25 and gloss 32 stay constants.  No ray, no geometry, no normal, RT_TARGET_GPOS / GNRM / MOTION, resolveTAA and the miss rule change.
+ * A mesh whose colours are all 0.85 renders bit for bit as with colours disabled.  Out of scope: per-vertex specular and gloss, textures and UVs,
+ * colours in the hybrid scene (RT_SCENE_HYBRID), the analytic scene and the raster preview (which keeps its draw and part colours), colours read from
+ * .obj files. */
+/* on != 0: waits for every lane, allocates the vertex colours (every vertex (0.85, 0.85, 0.85, 0)) and colRows (RtMeshInfo.allocations and scratchBytes
+ * count both) and, if the mesh has a tree, fills the rows at once.  on == 0 releases both.  May synchronise and allocate; the only call of this group
+ * that may.  No tree is needed to enable.  on != 0 while colours are enabled changes nothing: the colours and the rows stay, nothing is allocated (disable
+ * first to start again from 0.85).  RT_ERR_INVALID without a mesh; rt_mesh_upload, rt_mesh_upload_parts and rt_upload_bvh release them with the
+ * mesh. */
+int rt_mesh_colors_enable(RtContext *ctx, int on);
+/* The device array of vertex colours: nVerts x 4 floats (r, g, b, 0).  The caller may write it on rt_stream()'s stream; device-written colours are taken
+ * as they are.  RT_ERR_INVALID without a mesh or without colours enabled. */
+int rt_mesh_colors(RtContext *ctx, void **devPtr, size_t *bytes);
+/* Colours first .. first + count - 1 from rgb3 (3 floats per vertex, host memory, copied before the call returns), written and ordered like
+ * rt_mesh_set_bones: behind everything enqueued on any lane, before whatever a lane is given next; as there, the copy leaves pageable memory, so the
+ * host may spend the copy's time in the call.  RT_ERR_INVALID without a mesh or colours, for a
+ * range outside [0, nVerts], a null rgb3 with count > 0, or a component that is non-finite or negative.  Does not touch the rows. */
+int rt_mesh_set_colors(RtContext *ctx, const float *rgb3, int first, int count);
+/* The row gather alone (k_color_rows), for a caller who changed colours and not positions; enqueued and ordered exactly as rt_mesh_motion_latch is: no
+ * allocation, no host wait.  RT_ERR_INVALID without a mesh, without colours enabled, or before the first rebuild. */
+int rt_mesh_colors_refresh(RtContext *ctx);
+/* The colour of each hit: for the RtHit outputs of rt_trace_rays, rt_trace_scene_rays or rt_pick_pixels, colors (3 floats per hit) equals rt_hit_colors'
+ * out3 bit for bit under the device's colRows as they stand when the kernel runs; zeros for a prim outside [0, nTris) -- a miss, an analytic hit, a stale
+ * value -- with nothing read out of bounds.  Device pointers, hits 16-byte aligned; enqueued on rt_stream()'s stream like rt_mesh_hit_normals: no
+ * allocation, no host wait.  RT_ERR_INVALID without a mesh, without colours enabled, or before the first rebuild.  _host: the same with host pointers,
+ * staged through the context's buffer; synchronises. */
+int rt_mesh_hit_colors(RtContext *ctx, const RtHit *hits, int n, float *colors);
+int rt_mesh_hit_colors_host(RtContext *ctx, const RtHit *hits, int n, float *colors);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload, rt_mesh_motion_enable, rt_mesh_normals_enable and rt_mesh_colors_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -821,7 +861,9 @@ enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 
        /* the dynamic mesh's previous pose (rt_mesh_motion_enable): nTris rows of 48 bytes, no padding; size 0 while motion is not enabled */
        RT_SCENE_ARRAY_PREV_TRIS = 13,
        /* the dynamic mesh's corner normals (rt_mesh_normals_enable): nTris rows of 48 bytes, no padding; size 0 while normals are not enabled */
-       RT_SCENE_ARRAY_NORMAL_ROWS = 14 };
+       RT_SCENE_ARRAY_NORMAL_ROWS = 14,
+       /* the dynamic mesh's corner colours (rt_mesh_colors_enable): nTris rows of 48 bytes, no padding; size 0 while colours are not enabled */
+       RT_SCENE_ARRAY_COLOR_ROWS = 15 };
 int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): what rt_upload_bvh would put on the device for these arrays -- the packers of
  * csrc/rt_scene_pack.cpp run and one array handed out, with rt_debug_read_scene's `which` values and size-query convention.
@@ -986,6 +1028,22 @@ int rt_hit_motion(const RtUniforms *u, const float *tris12, const float *prevTri
 int rt_vertex_normals(const float *tris12, const int32_t *order, int nTris, const uint32_t *indices, int nVerts, float *normals3);
 int rt_hit_normals(const float *tris12, const int32_t *order, int nTris, const uint32_t *indices, const float *normals3, int nVerts, const RtHit *hits, int n,
                    float *out3);
+
+/* Per-vertex colours on host arrays, and the definitions the device's colRows, rt_mesh_hit_colors and the frames' albedo are tested against (order:
+ * row -> input triangle, rt_mesh_order's array; indices: the 3 nTris indices of the input triangles; colors: 3 floats per vertex).  fp32 in the device's
+ * float model: every product and sum rounded on its own, no fmaf.
+ *   rt_hit_colors: for hit i on row p = hits[i].prim in [0, nTris) with (a, b) = (hits[i].u, hits[i].v), the corner colours c0, c1, c2 are those of
+ * vertices indices[3 order[p] + c].  If a or b is not finite the answer is c0 bit for bit.  Otherwise, per channel: c0's value bit for bit where the
+ * three corner values of the channel are bit-equal -- so nine floats that are bit-equal corner to corner give c0 bit for bit, and a channel that is
+ * constant over the mesh is not disturbed by the others -- and (c0 * ((1 - a) - b) + c1 * a) + c2 * b elsewhere.  Not clamped, not validated: the barycentrics of a real hit give a convex
+ * combination up to rounding.  A prim outside [0, nTris) gives zeros and reads nothing.  tris12 (the rows of the triangle array) is not read -- the
+ * barycentrics come with the hit -- and may be null.  out3: 3 floats per hit.  RT_ERR_INVALID: a null array, nTris <= 0, nVerts <= 0, n < 0, or a hit
+ * row whose order entry or indices are out of range.
+ *   rt_color_rows: rows12 gets nTris rows of 12 floats, three (r, g, b, 0); row i holds the corner colours of input triangle order[i].
+ * RT_ERR_INVALID: a null array, nTris <= 0, nVerts <= 0, an order entry outside [0, nTris), an index >= nVerts.  Neither needs a GPU. */
+int rt_hit_colors(const float *tris12, int nTris, const int32_t *order, const uint32_t *indices, const float *colors, int nVerts, const RtHit *hits, int n,
+                  float *out3);
+int rt_color_rows(const int32_t *order, const uint32_t *indices, const float *colors, int nTris, int nVerts, float *rows12);
 
 /* Morph-target blending on host arrays, and the definition rt_mesh_morph is tested against (see rt_mesh_morph_upload for the arrays; weights holds
  * nTargets floats).  For vertex v, acc = base[v]; the entries that name v are visited in input order (ascending target, then position within the

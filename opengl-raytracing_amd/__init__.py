@@ -199,7 +199,10 @@ SCENE_ARRAYS_OPTIONAL = {"fused": 7, "impl_nodes2": 8, "impl_pairs": 9, "impl_no
 RT_SCENE_ARRAY_PREV_TRIS = 13
 # ... and its corner normals (rt_mesh_normals_enable): nTris rows of 48 bytes, empty while normals are not enabled
 RT_SCENE_ARRAY_NORMAL_ROWS = 14
-SCENE_ARRAYS_MESH = {"prev tris": 13, "normal rows": 14}
+# ... and its corner colours (rt_mesh_colors_enable): nTris rows of 48 bytes, empty while colours are not enabled
+RT_SCENE_ARRAY_COLOR_ROWS = 15
+SCENE_ARRAYS_MESH = {"prev tris": 13, "normal rows": 14, "color rows": 15}
+MESH_GREY = 0.85   # the albedo of a mesh hit without colours, and of every vertex when colours are enabled
 RT_SCENE_ARRAY_PACK_INFO = 100
 
 
@@ -378,6 +381,14 @@ SIGNATURES = {
     "rt_vertex_normals": (C.c_int, [_FP, C.POINTER(C.c_int32), C.c_int, _U32P, C.c_int, _FP]),
     "rt_hit_normals": (C.c_int, [_FP, C.POINTER(C.c_int32), C.c_int, _U32P, _FP, C.c_int, C.c_void_p, C.c_int, _FP]),
     "rt_debug_normal_pack": (C.c_int, [_U32P, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rt_mesh_colors_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_mesh_colors": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_colors": (C.c_int, [C.c_void_p, _FP, C.c_int, C.c_int]),
+    "rt_mesh_colors_refresh": (C.c_int, [C.c_void_p]),
+    "rt_mesh_hit_colors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_colors_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_hit_colors": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_void_p, C.c_int, _FP]),
+    "rt_color_rows": (C.c_int, [C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, _FP]),
     "rt_hit_motion": (C.c_int, [C.c_void_p, _FP, _FP, C.c_int, C.c_void_p, _FP, C.c_int, _FP, _FP]),
     "rt_mesh_morph_upload": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32), _U32P, _FP, C.c_int]),
     "rt_mesh_morph_base": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -798,6 +809,68 @@ def debug_normal_pack(indices, n_verts) -> dict:
 
     info = RtNormalInfo.from_buffer_copy(read(RT_NORMAL_ARRAY_INFO).tobytes())
     return {"info": info, "slice_first": read(RT_NORMAL_ARRAY_SLICE_FIRST).view(np.uint32), "entries": read(RT_NORMAL_ARRAY_ENTRIES).view(np.int32)}
+
+
+def _color_mesh(who, order, indices, colors):
+    """order / indices / colors as contiguous int32 [T] / uint32 [3T] / float32 [V,3] ([V,4], the device layout, is cut); what a cast would hide is
+    refused here."""
+    o, ix = np.asarray(order).reshape(-1), np.asarray(indices).reshape(-1)
+    if ix.size != 3 * o.size:
+        raise RtError(RT_ERR_INVALID, f"{who}: {o.size} order entries and {ix.size} indices")
+    if (o.size and (o.min() < -2 ** 31 or o.max() >= 2 ** 31)) or (ix.size and (ix.min() < 0 or ix.max() >= 2 ** 32)):
+        raise RtError(RT_ERR_INVALID, f"{who}: order must fit int32 and indices uint32")
+    cv = _f32(colors)
+    if cv.ndim != 2 or cv.shape[1] not in (3, 4):
+        raise RtError(RT_ERR_INVALID, f"{who}: colors must be [V,3] or [V,4], got {cv.shape}")
+    return np.ascontiguousarray(o, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.uint32), np.ascontiguousarray(cv[:, :3])
+
+
+def hit_colors(tris12, order, indices, colors, hits) -> np.ndarray:
+    """Colours of hits on the dynamic mesh on the host (rt_hit_colors), the definition Renderer.mesh_hit_colors and the frames' albedo are tested
+    against: order [T] row -> input triangle (Renderer.mesh_order), indices the 3T indices of the input triangles, colors [V,3] (or [V,4], the device
+    layout) the vertex colours, hits a RayHits / SceneHits or its [N,4] float32 record array -> [N,3] float32; zeros for a prim outside the
+    triangles.  tris12 (the rows of the triangle array) is not read -- the barycentrics come with the hits -- and may be None."""
+    rec = np.ascontiguousarray(hits.record if isinstance(hits, RayHits) else hits)
+    if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+        raise RtError(RT_ERR_INVALID, f"hit_colors: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+    o, ix, cv = _color_mesh("hit_colors", order, indices, colors)
+    t = None if tris12 is None else _f32(tris12).reshape(-1, 12)
+    if t is not None and t.shape[0] != o.size:
+        raise RtError(RT_ERR_INVALID, f"hit_colors: {t.shape[0]} rows and {o.size} order entries")
+    out = np.zeros((rec.shape[0], 3), np.float32)
+    rc = lib().rt_hit_colors(None if t is None else _fp(t), o.size, o.ctypes.data_as(_I32P), ix.ctypes.data_as(_U32P), _fp(cv), cv.shape[0],
+                             C.c_void_p(rec.ctypes.data), rec.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_hit_colors: no triangles, no vertices, or a hit row whose order entry or indices are out of range")
+    return out
+
+
+def color_rows(order, indices, colors) -> np.ndarray:
+    """The device row array of the vertex colours on the host (rt_color_rows), the definition Renderer.mesh_color_rows is tested against -> float32
+    [T,12], three (r, g, b, 0) per row; row i holds the corner colours of input triangle order[i]."""
+    o, ix, cv = _color_mesh("color_rows", order, indices, colors)
+    out = np.zeros((o.size, 12), np.float32)
+    rc = lib().rt_color_rows(o.ctypes.data_as(_I32P), ix.ctypes.data_as(_U32P), _fp(cv), o.size, cv.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_color_rows: no triangles, no vertices, an index out of range or an order entry outside the triangles")
+    return out
+
+
+def vertex_colors_from_parts(indices, part_first, rgb, n_verts) -> np.ndarray:
+    """Vertex colours [n_verts,3] float32 from one colour per part (pure numpy), the bridge from rt_raster_part_colors' table: part p owns input
+    triangles part_first[p] .. part_first[p+1] (Renderer.mesh_upload_parts' table) and every vertex they name gets rgb[p]; on a vertex that parts
+    share the later part wins; a vertex no triangle names keeps MESH_GREY."""
+    ix = np.asarray(indices).reshape(-1, 3)
+    pf = np.asarray(part_first).reshape(-1)
+    col = _f32(rgb).reshape(-1, 3)
+    if pf.size != col.shape[0] + 1 or pf[0] != 0 or pf[-1] != ix.shape[0] or np.any(np.diff(pf) < 0):
+        raise RtError(RT_ERR_INVALID, f"vertex_colors_from_parts: {col.shape[0]} colours, a part table of {pf.size} entries over {ix.shape[0]} triangles")
+    if ix.size and (ix.min() < 0 or ix.max() >= int(n_verts)):
+        raise RtError(RT_ERR_INVALID, "vertex_colors_from_parts: an index outside the vertices")
+    out = np.full((int(n_verts), 3), MESH_GREY, np.float32)
+    for p in range(col.shape[0]):
+        out[ix[int(pf[p]):int(pf[p + 1])].reshape(-1)] = col[p]
+    return out
 
 
 def bvh_layout(n_tris: int) -> RtBvhLayout:
@@ -1502,6 +1575,67 @@ class Renderer:
         cur = torch.cuda.current_stream(dev)
         ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
         self._check(lib().rt_mesh_hit_normals(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        return out
+
+    # ---- per-vertex colours: kept on the device beside the triangle array, the albedo of mesh hits in frames and in mesh_hit_colors
+    def mesh_colors_enable(self, on=True):
+        """Keep one colour per vertex of the dynamic mesh (rt_mesh_colors_enable), every one MESH_GREY at first: every update then gathers the corner
+        colours beside its new rows, and frames of the mesh's scene with useBVH == 1 shade mesh hits with them.  Allocates two arrays and fills the
+        rows if there is a tree; may synchronise.  on=False releases them.  Off until asked for."""
+        self._check(lib().rt_mesh_colors_enable(self._h, 1 if on else 0))
+
+    def mesh_colors(self, as_torch=None):
+        """The device array of vertex colours: a float32 [V,4] tensor (r, g, b, 0) that aliases it (as mesh_positions; the caller may write it on
+        stream()), else (pointer, bytes).  The rows follow at the next update or mesh_colors_refresh."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().rt_mesh_colors(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, 4, as_torch)
+
+    def mesh_set_colors(self, rgb, first=0):
+        """Colours [count,3] from host memory for vertices first .., copied on stream() in call order with updates, frames and queries
+        (rt_mesh_set_colors); a non-finite or negative component is refused.  The rows follow at the next update or mesh_colors_refresh."""
+        c = _f32(rgb)
+        if c.size % 3:
+            raise RtError(RT_ERR_INVALID, "mesh_set_colors: rgb must hold 3 floats per vertex")
+        c = c.reshape(-1, 3)
+        self._check(lib().rt_mesh_set_colors(self._h, _fp(c), int(first), c.shape[0]))   # pageable memory: staged before the call returns
+
+    def mesh_colors_refresh(self):
+        """The corner colours gathered again from the vertex colours, for colours that changed under positions that did not; enqueued in call order
+        with updates, frames and queries (rt_mesh_colors_refresh): no host wait."""
+        self._check(lib().rt_mesh_colors_refresh(self._h))
+
+    def mesh_color_rows(self) -> np.ndarray:
+        """The corner colours as float32 [nTris,12] rows, three (r, g, b, 0) per row (rt_debug_read_scene: synchronises); empty while colours are not
+        enabled or before the first rebuild.  Row i belongs to input triangle mesh_order()[i], as row i of debug_read_scene("tris")."""
+        return self.debug_read_scene(RT_SCENE_ARRAY_COLOR_ROWS).view(np.float32).reshape(-1, 12)
+
+    def mesh_hit_colors(self, hits):
+        """The colour of each hit: float32 [N,3], hit_colors bit for bit -- on a pixel's pick, the albedo that pixel's frame shades with; zeros for a
+        miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in, numpy out
+        (rt_mesh_hit_colors_host: synchronises); a torch tensor on this context's device takes the zero-copy path of mesh_hit_normals: enqueued on
+        the library stream, ordered against torch's current stream, no host wait."""
+        rec = hits.record if isinstance(hits, RayHits) else hits
+        if isinstance(rec, np.ndarray):
+            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+                raise RtError(RT_ERR_INVALID, f"mesh_hit_colors: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+            rec = np.ascontiguousarray(rec)
+            n = rec.shape[0]
+            out = np.zeros((n, 3), np.float32)
+            self._check(lib().rt_mesh_hit_colors_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+            raise RtError(RT_ERR_INVALID, f"mesh_hit_colors: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+        rec = rec.contiguous()
+        n = rec.shape[0]
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
+        self._check(lib().rt_mesh_hit_colors(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(out.data_ptr())))
         cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
         return out
 

@@ -938,6 +938,117 @@ int rt_mesh_hit_normals_host(RtContext *c, const RtHit *hits, int n, float *norm
     });
 }
 
+// ---- per-vertex colours: rt_mesh.hip gathers the rows inside every update; this file owns enabling, the ordering of colour writes and
+// of the gather alone, and the hit query
+int rt_mesh_colors_enable(RtContext *c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
+    if (!on) { rtl::mesh_colors_release(c->mesh); return RT_OK; }
+    if (rtl::mesh_vertex_colors(c->mesh)) return RT_OK;   // already enabled: the colours and the rows stay as they are, nothing is allocated
+    const bool orderWas = rtl::mesh_order_written(c->mesh);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    const char *err = nullptr;
+    const int rc = rtl::mesh_colors_create(c->mesh, st, &err);
+    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_colors_enable: %s", err ? err : "allocation failed");
+    return RT_OK;
+}
+
+int rt_mesh_colors(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: no mesh (rt_mesh_upload first)");
+    if (!rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: colours are not enabled (rt_mesh_colors_enable first)");
+    *devPtr = rtl::mesh_vertex_colors(c->mesh);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 16;
+    return RT_OK;
+}
+
+int rt_mesh_set_colors(RtContext *c, const float *rgb3, int first, int count) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh || !rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: no colours (rt_mesh_upload and rt_mesh_colors_enable first)");
+    const int n = rtl::mesh_verts(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: vertices %d .. %d of %d", first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!rgb3) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: null colours");
+    for (size_t i = 0; i < (size_t)count * 3; ++i)
+        if (!(rgb3[i] >= 0.0f) || !(rgb3[i] < INFINITY)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: component %zu of vertex %zu is %g (finite and >= 0 is needed)", i % 3, (size_t)first + i / 3, (double)rgb3[i]);
+    return guarded(c, "rt_mesh_set_colors", [&]() -> int {
+        (void)hipSetDevice(c->cfg.device);
+        hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+        // (r, g, b, 0) per vertex as the device holds them, in a buffer of the call's own.  It may go when the call returns only because the HIP runtime
+        // finishes with pageable host memory -- stages it, or completes the copy -- before hipMemcpyAsync returns; rt_mesh_set_bones leans on the same
+        // for the caller's array.  So the call is ordered on the stream like rt_mesh_set_bones, and like it may spend the copy's time on the host.
+        std::vector<float> v4((size_t)count * 4);
+        for (size_t i = 0; i < (size_t)count; ++i) { v4[4 * i] = rgb3[3 * i]; v4[4 * i + 1] = rgb3[3 * i + 1]; v4[4 * i + 2] = rgb3[3 * i + 2]; v4[4 * i + 3] = 0.0f; }
+        int rc = mesh_after_lanes(c, st);   // a gather enqueued on another lane reads the colours
+        if (rc != RT_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(rtl::mesh_vertex_colors(c->mesh) + (size_t)first, v4.data(), (size_t)count * 16, hipMemcpyHostToDevice, st));
+        return mesh_before_lanes(c, st);
+    });
+}
+
+int rt_mesh_colors_refresh(RtContext *c) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_color_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: colours are not enabled (rt_mesh_colors_enable first)");
+    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no rows to fill (rt_mesh_rebuild first)");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    int rc = mesh_after_lanes(c, st);   // frames and queries on every lane read the rows they were enqueued with ...
+    if (rc != RT_OK) return rc;
+    const char *err = nullptr;
+    const bool orderWas = rtl::mesh_order_written(c->mesh);
+    rc = rtl::mesh_colors_refresh(c->mesh, st, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_colors_refresh: %s", err ? err : "launch failed");
+    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
+    return mesh_before_lanes(c, st);    // ... and whatever a lane is given next sees the new ones
+}
+
+static int hit_colors_args(RtContext *c, const char *who, const RtHit *hits, int n, const float *colors) {
+    if (n < 0 || (n > 0 && !hits) || !colors) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits and colors are needed)", who, n);
+    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
+    if (!rtl::mesh_color_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: colours are not enabled (rt_mesh_colors_enable first)", who);
+    return RT_OK;
+}
+
+int rt_mesh_hit_colors(RtContext *c, const RtHit *hits, int n, float *colors) {
+    if (!c) return RT_ERR_INVALID;
+    int rc = hit_colors_args(c, "rt_mesh_hit_colors", hits, n, colors);
+    if (rc != RT_OK) return rc;
+    if (((uintptr_t)hits & 15u) || ((uintptr_t)colors & 3u)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_colors: hits must be 16-byte aligned, colors 4-byte aligned");
+    if (n == 0) return RT_OK;
+    (void)hipSetDevice(c->cfg.device);
+    const char *err = nullptr;
+    rc = rtl::mesh_hit_colors(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, n, colors, &err);
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_colors: %s", err ? err : "launch failed");
+    return RT_OK;
+}
+
+int rt_mesh_hit_colors_host(RtContext *c, const RtHit *hits, int n, float *colors) {
+    if (!c) return RT_ERR_INVALID;
+    const int ar = hit_colors_args(c, "rt_mesh_hit_colors_host", hits, n, colors);
+    if (ar != RT_OK) return ar;
+    if (n == 0) return RT_OK;
+    return guarded(c, "rt_mesh_hit_colors_host", [&]() -> int {
+    (void)hipSetDevice(c->cfg.device);
+    const size_t N = (size_t)n, hB = N * sizeof(RtHit), total = hB + N * 12;   // hits | colors
+    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
+    const int sr = ensure_staging(c, total);
+    if (sr != RT_OK) return sr;
+    char *base = (char *)c->dStaging;
+    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
+    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
+    const int qr = rt_mesh_hit_colors(c, (const RtHit *)base, n, (float *)(base + hB));
+    if (qr != RT_OK) { (void)sync_all(c); return qr; }
+    HIP_TRY(c, hipMemcpyAsync(colors, base + hB, N * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return RT_OK;
+    });
+}
+
 // ---- skinning: rt_mesh_skin.hip rewrites the positions; this file validates the tables and orders the writes against every lane
 int rt_mesh_skin_upload(RtContext *c, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones) {
     if (!c) return RT_ERR_INVALID;
@@ -1316,6 +1427,7 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
         case RT_SCENE_ARRAY_IMPL_LEAFBOX: src = c->dILeafBox; n = (implNodes + 1) * 32; break;
         case RT_SCENE_ARRAY_PREV_TRIS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_prev_tris(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         case RT_SCENE_ARRAY_NORMAL_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_normal_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
+        case RT_SCENE_ARRAY_COLOR_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_color_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
     }
     if (!have || !src) return RT_OK;
@@ -1544,6 +1656,8 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     fr.prevTris = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_prev_tris(c->mesh) : nullptr;
     // smooth normals: mesh hits of the dynamic mesh's own scene; the hybrid scene keeps the face normal
     fr.nrmRows = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_normal_rows(c->mesh) : nullptr;
+    // per-vertex colours: mesh hits of the dynamic mesh's own scene; the hybrid scene keeps the constant albedo
+    fr.colRows = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_color_rows(c->mesh) : nullptr;
     // Lane = frame index mod nLanes = index of the COLOR0 buffer this frame writes: consecutive frames rotate over the lanes'
     // streams and overlap everywhere except at the temporal resolve (the only read of the previous frame), and every later
     // reader of a COLOR0 buffer (gather, assemble) is stream-ordered before the next writer of the same buffer.

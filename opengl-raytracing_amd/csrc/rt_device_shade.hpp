@@ -13,6 +13,7 @@
 #include "rt_device_math.hpp"
 #include "rt_mesh_motion.hpp"
 #include "rt_mesh_normals.hpp"
+#include "rt_mesh_colors.hpp"
 
 #pragma clang fp contract(off)
 
@@ -336,6 +337,30 @@ RT_DEV V3 hitNormal(const float4 *tris, const float4 *nrmRows, int tri, V3 ro, V
     return mk3(out[0], out[1], out[2]);
 }
 
+// Per-vertex colours: the albedo of the hit of the ray (ro, rd) on row `tri`.  colRows == null (no dynamic mesh, or colours not
+// enabled): the reference's constant.  Otherwise (a, b) are the hit's barycentrics with hitNormal's operations in their order -- the u, v rt_pick_pixels
+// returns for the pixel -- and the rest is rt_hit_colors' rule on the row's three corner colours (rt_mesh_colors.hpp).  The steps are taken one after
+// the other, as in hitNormal: the row for (a, b), then the corner colours.
+RT_DEV V3 hitColor(const float4 *tris, const float4 *colRows, int tri, V3 ro, V3 rd) {
+    if (!colRows) return mk3(0.85f);
+    float a, b;
+    {
+        const float4 *T = tris + (size_t)tri * 3;
+        const V3 v0 = f4xyz(T[0]), e1 = f4xyz(T[1]), e2 = f4xyz(T[2]);
+        const V3 pvec = cross(rd, e2);
+        const float invDet = 1.0f / dot(e1, pvec);
+        const V3 tvec = ro - v0;
+        a = dot(tvec, pvec) * invDet;
+        b = dot(rd, cross(tvec, e1)) * invDet;
+    }
+    const float4 *R = colRows + (size_t)tri * 3;
+    const float4 r0 = R[0], r1 = R[1], r2 = R[2];
+    const float c0[3] = {r0.x, r0.y, r0.z}, c1[3] = {r1.x, r1.y, r1.z}, c2[3] = {r2.x, r2.y, r2.z};
+    float out[3];
+    rtcolor::blend_colors(c0, c1, c2, a, b, out);
+    return mk3(out[0], out[1], out[2]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // EXTENSION (hybrid scene, staged): replay state of one (pixel, sample) thread of rt_hybrid.hip.  The analytic shading code asks for mesh
 // hits through ONE function (traceScene); staged, that function answers from a log of earlier passes and records what it cannot answer yet
@@ -540,12 +565,23 @@ enum { SEG_DIRECT = 0, SEG_GI_DIRECT = 1 };
 //   static constexpr bool T::kSkipUnlitDisk: a wave all of whose lanes satisfy diskUnlit does not evaluate the disk loop: it reports
 // the four samples as dead rays (matters == false) and leaves sum at mk3(0.0f) -- what the loop computes for such a hit, bit for bit.
 // The tracer is then told through T::disk_stat(seg, unlit, skipped).  Tracers that count the rays the REFERENCE casts do not opt in.
-template <class T>
-RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame, V3 Vdir) {
+// Where a hit's colour is kept while it is shaded.  The shading asks for it with get() at every use, not once: HeldAlbedo answers from
+// registers (the wavefront's k_combine, which calls nothing), LdsAlbedo reads it again from LDS (the megakernel, whose traversal is a call: a value kept
+// across a call is kept in scratch, a value read again behind it is not).
+struct HeldAlbedo { V3 c; RT_DEV V3 get() const { return c; } };
+struct LdsAlbedo {   // three floats of one lane, 256 floats apart
+    float *p;
+    RT_DEV V3 get() const { return mk3(p[0], p[256], p[512]); }
+    RT_DEV void set(V3 c) const { p[0] = c.x; p[256] = c.y; p[512] = c.z; }
+};
+// COLOR: hitAlbedo->get() is the hit's colour; without it the albedo is the reference's constant, and the instantiation the code it always was.
+template <class T, bool COLOR = false, class A = HeldAlbedo>
+RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame, V3 Vdir, const A *hitAlbedo = nullptr) {
     const RtUniforms &u = *F.u;
     V3 N = normalize(hn);
     V3 sum = mk3(0.0f);
-    const V3 albedo = mk3(0.85f);
+    const V3 grey = mk3(0.85f);
+    auto albedo = [&]() -> V3 { if constexpr (COLOR) return hitAlbedo->get(); else return grey; };
     const float specStrength = 0.25f, gloss = 32.0f;
     V3 V = normalize(Vdir);
     bool skip = false;
@@ -566,12 +602,12 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
             DiskSample s = diskSample(F, hp, N, frame, i, rot, lt, lb);
             float vis = tr.shadow(seg, i, s.ro, s.rd, s.tMax, s.geom != 0.0f) ? 0.0f : 1.0f;
             V3 Li = mk3(18.0f) * s.geom * vis;
-            sum = sum + shadeLambertPhong(u.pi, N, V, s.L, Li, albedo, specStrength, gloss);
+            sum = sum + shadeLambertPhong(u.pi, N, V, s.L, Li, albedo(), specStrength, gloss);
         }
     }
     sum = sum / 4.0f;
     MaterialProps fakeMat;
-    fakeMat.albedo = albedo; fakeMat.specStrength = specStrength; fakeMat.gloss = gloss; fakeMat.type = 0; fakeMat.ior = 1.0f;
+    fakeMat.albedo = albedo(); fakeMat.specStrength = specStrength; fakeMat.gloss = gloss; fakeMat.type = 0; fakeMat.ior = 1.0f;
     // sunDirect :114-144
     V3 sun = mk3(0.0f);
     if (u.sunEnabled != 0) {
@@ -583,7 +619,7 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
             float e = epsForDist(maxT);
             V3 origin = hp + N * e;
             bool blocked = tr.shadow(seg, 4, origin, L, maxT - e, true);
-            if (!blocked) sun = shadeLambertPhong(u.pi, N, Vs, L, ld3(u.sunColor) * u.sunIntensity, albedo, specStrength, gloss);
+            if (!blocked) sun = shadeLambertPhong(u.pi, N, Vs, L, ld3(u.sunColor) * u.sunIntensity, albedo(), specStrength, gloss);
         }
     }
     sum = sum + sun;
@@ -604,7 +640,7 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
                 bool blocked = tr.shadow(seg, 5, origin, L, dist - e, true);
                 if (!blocked) {
                     V3 Li = ld3(u.pointLightColor) * (u.pointLightIntensity / fmaxr(dist2, 1e-4f));
-                    pt = shadeLambertPhong(u.pi, N, Vp, L, Li, albedo, specStrength, gloss);
+                    pt = shadeLambertPhong(u.pi, N, Vp, L, Li, albedo(), specStrength, gloss);
                 }
             }
         }
@@ -616,10 +652,13 @@ RT_DEV V3 directLightBVH(T &tr, const Frag &F, int seg, V3 hp, V3 hn, int frame,
 // where the bounce ray of a hit starts (:531): the same point for every sample of the hit.  N0 = normalize(hn0).
 RT_DEV V3 bounce_origin(V3 hp0, V3 N0, float eps) { return hp0 + N0 * eps; }
 // oneBounceGIBVH (:515-561):  int T::gi(V3 ro, V3 rd, V3 &hp, V3 &hn)  -> 1 hit, 0 miss, -1 "not known yet"
-template <class T, bool COUNT>
-RT_DEV V3 oneBounceGIBVH(T &tr, const Frag &F, V3 hp0, V3 hn0, int frame, int seed, Work &w) {
+// COLOR: hitAlbedo->get() is the primary hit's colour, and the tracer hands the bounce hit's back in a T::BounceAlbedo through gi's
+// sixth argument (the fifth is the primary's, for a tracer that keeps its colours where that one says).  Without it
+// both are the reference's constant -- the generators, whose rays no colour reaches, are instantiated so -- and the code is what it always was.
+template <class T, bool COUNT, bool COLOR = false, class A = HeldAlbedo>
+RT_DEV V3 oneBounceGIBVH(T &tr, const Frag &F, V3 hp0, V3 hn0, int frame, int seed, Work &w, const A *hitAlbedo = nullptr) {
     const RtUniforms &u = *F.u;
-    const V3 albedo0 = mk3(0.85f);
+    const V3 grey0 = mk3(0.85f);
     const float MAX_GI_LUM = 8.0f, MIN_COS_THETA = 0.1f;
     float o19 = (float)(int)((uint32_t)seed * 19u), o41 = (float)(int)((uint32_t)seed * 41u);
     V2 uu = mk2(randr(F.fcx + o19, F.fcy + o19, frame), randr(F.fcy + o41, F.fcx + o41, frame));
@@ -629,9 +668,19 @@ RT_DEV V3 oneBounceGIBVH(T &tr, const Frag &F, V3 hp0, V3 hn0, int frame, int se
     if (cosTheta <= MIN_COS_THETA) return mk3(0.0f);
     V3 origin = bounce_origin(hp0, N0, u.eps);
     V3 hp1, hn1;
-    int hit1 = tr.gi(origin, wi, hp1, hn1);
-    if (hit1 < 0) return mk3(0.0f);
-    V3 Li = (hit1 > 0) ? directLightBVH(tr, F, SEG_GI_DIRECT, hp1, hn1, frame, -wi) : sky<COUNT>(F, wi, w);
+    V3 Li;
+    if constexpr (COLOR) {
+        typename T::BounceAlbedo albedo1;
+        int hit1 = tr.gi(origin, wi, hp1, hn1, *hitAlbedo, albedo1);
+        if (hit1 < 0) return mk3(0.0f);
+        Li = (hit1 > 0) ? directLightBVH<T, true, typename T::BounceAlbedo>(tr, F, SEG_GI_DIRECT, hp1, hn1, frame, -wi, &albedo1) : sky<COUNT>(F, wi, w);
+    } else {
+        int hit1 = tr.gi(origin, wi, hp1, hn1);
+        if (hit1 < 0) return mk3(0.0f);
+        Li = (hit1 > 0) ? directLightBVH(tr, F, SEG_GI_DIRECT, hp1, hn1, frame, -wi) : sky<COUNT>(F, wi, w);
+    }
+    V3 albedo0;
+    if constexpr (COLOR) albedo0 = hitAlbedo->get(); else albedo0 = grey0;
     V3 contrib = albedo0 * (cosTheta / u.pi) * Li;
     float lum = dot(contrib, mk3(0.299f, 0.587f, 0.114f));
     if (lum > MAX_GI_LUM) {
@@ -660,11 +709,12 @@ RT_DEV float computeAO_BVH(T &tr, const Frag &F, V3 hp, V3 hn, int frame) {
 }
 
 // One BVH-mode sample of rt.frag:105-117 on a primary hit.
-template <class T, bool COUNT>
-RT_DEV V3 shadeSampleBVH(T &tr, const Frag &F, V3 hp, V3 hn, V3 V, int seed, float ao, Work &w) {
+// COLOR: hitAlbedo->get() is the primary hit's colour.
+template <class T, bool COUNT, bool COLOR = false, class A = HeldAlbedo>
+RT_DEV V3 shadeSampleBVH(T &tr, const Frag &F, V3 hp, V3 hn, V3 V, int seed, float ao, Work &w, const A *hitAlbedo = nullptr) {
     const RtUniforms &u = *F.u;
-    V3 radiance = directLightBVH(tr, F, SEG_DIRECT, hp, hn, seed, V);
-    if (u.enableGI == 1) radiance = radiance + u.giScaleBVH * oneBounceGIBVH<T, COUNT>(tr, F, hp, hn, F.frameIndex, seed, w);
+    V3 radiance = directLightBVH<T, COLOR, A>(tr, F, SEG_DIRECT, hp, hn, seed, V, hitAlbedo);
+    if (u.enableGI == 1) radiance = radiance + u.giScaleBVH * oneBounceGIBVH<T, COUNT, COLOR, A>(tr, F, hp, hn, F.frameIndex, seed, w, hitAlbedo);
     if (u.enableAO == 1) radiance = radiance * ao;
     return radiance;
 }

@@ -68,6 +68,8 @@ struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it thr
                                       // offset above, and DevScene as a kernel argument, stay what they were
     const float4 *nrmRows = nullptr;  // smooth normals: the dynamic mesh's corner normals, row for row beside sc.tris; null = off, the face normal.
                                       // Behind prevTris for the same reason
+    const float4 *colRows = nullptr;  // per-vertex colours: the dynamic mesh's corner colours, row for row beside sc.tris; null = off, the constant
+                                      // albedo.  Last, behind nrmRows, for the same reason
 };
 
 struct Targets {

@@ -13,6 +13,9 @@ using namespace rtd;
 namespace {
 
 // Rays are traced where the shading code asks for them.
+// The primary hit's colour of one lane, in LDS (p: three floats 256 apart; the bounce hit's follow 768 floats behind), and DevFrame::colRows for the bounce hit
+struct MegaAlbedo : LdsAlbedo { const float4 *colRows; };
+
 template <bool COUNT>
 struct InlineTracer {
     const DevScene *sc;
@@ -29,6 +32,18 @@ struct InlineTracer {
         return r;
     }
     __device__ __noinline__ bool closest(V3 ro, V3 rd, float &t, int &tri) { return bvh_closest<COUNT>(*sc, ro, rd, eps, inf, stk, t, tri, *w); }
+    // per-vertex colours: the bounce hit's colour goes where the primary's keeper says -- LDS, not a member: nothing of it lives across the calls
+    using BounceAlbedo = LdsAlbedo;
+    RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn, const MegaAlbedo &primary, LdsAlbedo &albedo) {
+        float t;
+        int tri;
+        if (!closest(ro, rd, t, tri)) return 0;
+        hp = ro + rd * t;
+        hn = hitNormal(sc->tris, nrm, tri, ro, rd);
+        albedo.p = primary.p + 768;
+        albedo.set(hitColor(sc->tris, primary.colRows, tri, ro, rd));
+        return 1;
+    }
     RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn) {
         float t;
         int tri;
@@ -49,6 +64,7 @@ struct InlineTracer {
 template <bool COUNT, int STACK>
 __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr, Targets tg, unsigned long long *counters) {
     __shared__ StackEntry lds_stack[4 * STACK * 64];
+    __shared__ float lds_albedo[2 * 3 * 256];   // per-vertex colours: the primary and the bounce hit's colour of every lane, kept here across the traversal calls
     const RtUniforms &u = fr->u;
     const FrameGeom &g = fr->g;
     const int tid = threadIdx.x;
@@ -109,9 +125,12 @@ __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr
                         w.fetchAO += w.fetches() - w1.fetches();
                     }
                 }
+                MegaAlbedo albedo;   // per-vertex colours: fetched once per hit, behind the AO rays; null colRows: the constant
+                albedo.p = &lds_albedo[tid]; albedo.colRows = fr->colRows;
+                albedo.set(hitColor(fr->sc.tris, fr->colRows, triHit, camPos, dir));
                 for (int s = 0; s < SPP; ++s) {
                     int seed = (int)((uint32_t)u.frameIndex * (uint32_t)SPP + (uint32_t)s);
-                    frameSum = frameSum + shadeSampleBVH<InlineTracer<COUNT>, COUNT>(tr, F, hp, hn, V, seed, ao, w);
+                    frameSum = frameSum + shadeSampleBVH<InlineTracer<COUNT>, COUNT, true, MegaAlbedo>(tr, F, hp, hn, V, seed, ao, w, &albedo);
                 }
             } else {
                 V3 r = sky<COUNT>(F, dir, w);

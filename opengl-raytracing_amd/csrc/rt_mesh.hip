@@ -237,6 +237,10 @@ struct Mesh {
     int32_t *dNrmEntries = nullptr;
     float4 *dFaceByInput = nullptr, *dVertNrm = nullptr, *dNrmRows = nullptr;
     size_t normalBytes = 0;
+    // per-vertex colours: one colour per vertex and the corner colours row for row beside the triangle array; allocated by
+    // mesh_colors_create, not in `owned`
+    float4 *dVertCol = nullptr, *dColRows = nullptr;
+    size_t colorBytes = 0;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -427,6 +431,7 @@ void mesh_destroy(Mesh *m) {
     mesh_morph_release(m);
     mesh_motion_release(m);
     mesh_normals_release(m);
+    mesh_colors_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -457,6 +462,16 @@ int normals_update(Mesh *m, hipStream_t st, const char **err) {
     if (rc != RT_OK) return rc;
     normals_launch_update(st, m->sc.tris, order, m->dIdx, m->lay.nTris, m->dNrmSliceFirst, m->dNrmEntries, m->nVerts, m->dFaceByInput, m->dVertNrm, m->dNrmRows);
     REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+// the tail of an update behind its new rows: smooth normals, then the colour rows under the same order array -- a
+// rebuild moved every input triangle to another row; a refit's gather rewrites what it finds, which is what a caller who also changed colours wants
+int attributes_update(Mesh *m, hipStream_t st, const char **err) {
+    if (m->dNrmRows) {
+        const int rc = normals_update(m, st, err);
+        if (rc != RT_OK) return rc;
+    }
+    if (m->dColRows) return mesh_colors_refresh(m, st, err);
     return RT_OK;
 }
 // every record form from the bounds and the triangle array, through the tables: the tail of a rebuild and of a refit
@@ -511,8 +526,7 @@ int mesh_rebuild(Mesh *m, hipStream_t st, const float *M16, const char **err) {
         else REB_TRY(hipMemcpyAsync(m->dPrevTris, m->sc.tris, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     }
     m->permCur = cur;
-    if (m->dNrmRows) return normals_update(m, st, err);
-    return RT_OK;
+    return attributes_update(m, st, err);
 }
 
 bool mesh_has_tree(const Mesh *m) { return m->permCur >= 0; }
@@ -533,8 +547,7 @@ int mesh_refit(Mesh *m, hipStream_t st, const float *M16, const char **err) {
     }
     emit_records(m, st);
     REB_TRY(hipGetLastError());
-    if (m->dNrmRows) return normals_update(m, st, err);
-    return RT_OK;
+    return attributes_update(m, st, err);
 }
 
 int mesh_order(Mesh *m, hipStream_t st, const int **order, const char **err) {
@@ -739,6 +752,56 @@ const float4 *mesh_normal_rows(const Mesh *m) { return m->dNrmRows; }
 int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *normals, const char **err) {
     if (!m->dNrmRows || m->permCur < 0) return RT_ERR_INVALID;
     normals_launch_hit_normals(st, hits, n, m->sc.tris, m->dNrmRows, m->lay.nTris, normals);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_colors_release(Mesh *m) {
+    for (void *p : {(void *)m->dVertCol, (void *)m->dColRows}) if (p) (void)hipFree(p);
+    m->dVertCol = m->dColRows = nullptr;
+    m->scratchBytes -= m->colorBytes;
+    m->colorBytes = 0;
+}
+
+int mesh_colors_create(Mesh *m, hipStream_t st, const char **err) {
+    mesh_colors_release(m);
+    const size_t nt = (size_t)m->lay.nTris, nv = (size_t)m->nVerts;
+    auto make = [&](float4 **p, size_t bytes) -> hipError_t {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e != hipSuccess) return e;
+        *p = static_cast<float4 *>(q);
+        ++m->allocations;
+        m->colorBytes += bytes; m->scratchBytes += bytes;
+        return hipMemset(q, 0, std::max<size_t>(bytes, 16));
+    };
+    hipError_t e = make(&m->dVertCol, nv * 16);
+    if (e == hipSuccess) e = make(&m->dColRows, nt * 48);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) { colors_launch_fill(st, m->dVertCol, m->nVerts); e = hipGetLastError(); }
+    int rc = RT_OK;
+    if (e == hipSuccess && m->permCur >= 0) rc = mesh_colors_refresh(m, st, err);
+    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
+    if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_colors_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
+    return RT_OK;
+}
+
+float4 *mesh_vertex_colors(const Mesh *m) { return m->dVertCol; }
+const float4 *mesh_color_rows(const Mesh *m) { return m->dColRows; }
+
+int mesh_colors_refresh(Mesh *m, hipStream_t st, const char **err) {
+    if (!m->dColRows || m->permCur < 0) return RT_ERR_INVALID;
+    const int *order = nullptr;
+    const int rc = mesh_order(m, st, &order, err);
+    if (rc != RT_OK) return rc;
+    colors_launch_rows(st, order, m->dIdx, m->dVertCol, m->lay.nTris, m->nVerts, m->dColRows);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *colors, const char **err) {
+    if (!m->dColRows || m->permCur < 0) return RT_ERR_INVALID;
+    colors_launch_hit_colors(st, hits, n, m->dColRows, m->lay.nTris, colors);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

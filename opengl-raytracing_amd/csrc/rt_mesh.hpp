@@ -157,6 +157,25 @@ void normals_launch_update(hipStream_t st, const float4 *tris, const int *order,
                            int nVerts, float4 *faceByInput, float4 *vertNrm, float4 *nrmRows);
 void normals_launch_hit_normals(hipStream_t st, const void *hits, int n, const float4 *tris, const float4 *nrmRows, int nTris, float *normals);
 
+// Per-vertex colours.  mesh_colors_create: allocates the vertex colours (nVerts float4, every one (0.85, 0.85, 0.85, 0)) and colRows
+// (nTris rows of three float4, row i beside row i of the triangle array) and, when there is a tree, gathers the rows on `st`; allocates and waits for
+// the device; the caller has waited for every lane.  mesh_colors_release: both arrays freed (callers have synchronised).  While the arrays exist
+// mesh_rebuild and mesh_refit gather the rows again behind their new rows on their stream, inside their own sequence of launches: no allocation, no
+// host wait.
+int mesh_colors_create(Mesh *m, hipStream_t st, const char **err);
+void mesh_colors_release(Mesh *m);
+float4 *mesh_vertex_colors(const Mesh *m);        // device, nVerts float4 (rgb, w = 0); null: colours are not enabled
+const float4 *mesh_color_rows(const Mesh *m);     // device, nTris x 3 float4; null: colours are not enabled
+// Enqueues the row gather alone on `st` (deriving the order array first where the tree has none yet).  RT_ERR_INVALID without the arrays or a tree.
+int mesh_colors_refresh(Mesh *m, hipStream_t st, const char **err);
+// Enqueues colors[i] = the colour of hit i (rt_hit_colors' out3) on `st` for n RtHit records (device pointers).  RT_ERR_INVALID without the arrays or
+// without a tree.
+int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *colors, const char **err);
+// rt_mesh_colors.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
+void colors_launch_fill(hipStream_t st, float4 *vertCol, int nVerts);
+void colors_launch_rows(hipStream_t st, const int *order, const uint32_t *idx, const float4 *vertCol, int nTris, int nVerts, float4 *colRows);
+void colors_launch_hit_colors(hipStream_t st, const void *hits, int n, const float4 *colRows, int nTris, float *colors);
+
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);
 

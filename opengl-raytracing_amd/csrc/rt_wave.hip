@@ -1705,13 +1705,14 @@ template <bool SMOOTH> struct GenGiTracer {       // reads the bounce result, re
     }
     RT_DEV bool ao(int, V3, V3, float) { return false; }
 };
-template <bool SMOOTH> struct CombineTracer {     // reads everything
+template <bool SMOOTH, bool COLOR> struct CombineTracer {     // reads everything
     static constexpr bool kSkipUnlitDisk = true;
     static constexpr bool kFrameLd2 = true;   // load_hit fills Frag::ld2x / ld2y
     RT_DEV void disk_stat(int, bool, bool) {}
     WaveBuf wb;
     const DevScene *sc;
     const float4 *nrm;   // SMOOTH: DevFrame::nrmRows, the bounce hit's corner normals
+    const float4 *col;   // COLOR: DevFrame::colRows, the bounce hit's corner colours
     uint32_t j;
     int s;
     RT_DEV bool shadow(int seg, int k, V3, V3, float, bool matters) {
@@ -1726,6 +1727,12 @@ template <bool SMOOTH> struct CombineTracer {     // reads everything
         if (tri < 0) return 0;
         hp = ro + rd * wb.giT[a];
         hn = SMOOTH ? hitNormal(sc->tris, nrm, tri, ro, rd) : tri_normal(*sc, tri);
+        return 1;
+    }
+    using BounceAlbedo = HeldAlbedo;
+    RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn, const HeldAlbedo &, HeldAlbedo &albedo) {   // COLOR builds: the normal first, then the colour, one row at a time
+        if (gi(ro, rd, hp, hn) == 0) return 0;
+        albedo.c = hitColor(sc->tris, col, wb.giTri[wb.gi_entry(s, j)], ro, rd);
         return 1;
     }
     RT_DEV bool ao(int i, V3, V3, float radius) { return radius > 0.0f && wb.occ1[(uint32_t)i * wb.CH + j] != 0; }
@@ -1949,15 +1956,15 @@ __global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restr
 __global__ __launch_bounds__(256) void k_gen_gi_overflow_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries, const uint32_t *hitList, const uint32_t *hitCount) { gen_gi_overflow_body<true>(fr, wb, c0, giCount, stackEntries, hitList, hitCount); }
 
 // ---- stage: combine (thread = hit) ---------------------------------------------------------------
-template <bool SMOOTH> RT_DEV void combine_body(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
+template <bool SMOOTH, bool COLOR> RT_DEV void combine_body(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= live) return;
     HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
     const int SPP = max(u.spp, 1);
-    CombineTracer<SMOOTH> tr;
-    tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.j = j; tr.s = 0;
+    CombineTracer<SMOOTH, COLOR> tr;
+    tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.col = COLOR ? fr->colRows : nullptr; tr.j = j; tr.s = 0;
     Work w;
     V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir, c.hp), u.prevViewProj), currNDC = ndcFromWorld(c.hp, u.currViewProj);
     V2 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
@@ -1965,16 +1972,29 @@ template <bool SMOOTH> RT_DEV void combine_body(const DevFrame *__restrict__ fr,
     float ao = 1.0f;
     if (u.enableAO == 1) ao = computeAO_BVH(tr, c.F, c.hp, c.hn, c.F.frameIndex);
     V3 frameSum = mk3(0.0f);
-    for (int s = 0; s < SPP; ++s) {
-        tr.s = s;
-        int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
-        frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
+    if constexpr (COLOR) {   // per-vertex colours: the primary hit's colour once per hit, in front of the sample loop
+        HeldAlbedo albedo;
+        albedo.c = hitColor(fr->sc.tris, fr->colRows, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir);
+        for (int s = 0; s < SPP; ++s) {
+            tr.s = s;
+            int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
+            frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH, COLOR>, false, true>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w, &albedo);
+        }
+    } else {
+        for (int s = 0; s < SPP; ++s) {
+            tr.s = s;
+            int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
+            frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH, COLOR>, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
+        }
     }
     finish_pixel(fr, wb, (int)c.slot, frameSum, motionOut, mk4(c.hp.x, c.hp.y, c.hp.z, 1.0f), mk4(nn.x, nn.y, nn.z, 0.0f));
 }
 // the stage as it always was, and with the smooth normals of DESIGN.md 14.13 (DevFrame::nrmRows != null): a build of its own, so that the first keeps its code
-__global__ __launch_bounds__(256) void k_combine(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false>(fr, tg, wb, c0); }
-__global__ __launch_bounds__(256) void k_combine_smooth(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true>(fr, tg, wb, c0); }
+__global__ __launch_bounds__(256) void k_combine(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false, false>(fr, tg, wb, c0); }
+__global__ __launch_bounds__(256) void k_combine_smooth(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true, false>(fr, tg, wb, c0); }
+// ... and with the per-vertex colours of DESIGN.md 14.14 (DevFrame::colRows != null): the only stage that evaluates the shading, so the only one built again
+__global__ __launch_bounds__(256) void k_combine_color(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false, true>(fr, tg, wb, c0); }
+__global__ __launch_bounds__(256) void k_combine_smooth_color(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true, true>(fr, tg, wb, c0); }
 
 __global__ void k_accum_tally(const uint32_t *counts, unsigned long long *acc, int frames) {
     // acc: [0] candidates [1] hits [2] primary rays traced [3] shadow [4] bounce [5] bounce-shadow (the traversal kernels add to
@@ -2471,7 +2491,7 @@ static int wave_chunk(LaunchSet &L, int c) {
     // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
     if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
     const unsigned gridH = (unsigned)((L.CH + 255) / 256);
-    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(L.host->nrmRows ? k_combine_smooth : k_combine, dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
+    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(L.host->colRows ? (L.host->nrmRows ? k_combine_smooth_color : k_combine_color) : (L.host->nrmRows ? k_combine_smooth : k_combine), dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
 }
 
 // The steps of a launch set: lane bookkeeping, plan, arenas, cursor table, primary stages, chunks settled, chunk by chunk, tally and resolve.

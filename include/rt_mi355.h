@@ -553,7 +553,8 @@ int rt_bvh_layout(int nTris, RtBvhLayout *out);
  * build scratch.  May synchronise and allocate; the only call of the group that may.  nIdx == 0 releases the mesh (and the scene it installed). */
 int rt_mesh_upload(RtContext *ctx, const float *positions, int nVerts, const uint32_t *indices, int nIdx);
 /* The device array of object-space positions (nVerts x 3 floats) for a caller that deforms the mesh on the device; writes must be ordered on
- * rt_stream()'s stream, as the rays of rt_trace_rays.  rt_mesh_set_positions: the same from host memory (nVerts x 3 floats), copied on that stream. */
+ * rt_stream()'s stream, as the rays of rt_trace_rays.  Refused (no mesh), it leaves *devPtr NULL and *bytes 0, as every accessor of this group does.
+ * rt_mesh_set_positions: the same from host memory (nVerts x 3 floats), copied on that stream. */
 int rt_mesh_positions(RtContext *ctx, void **devPtr, size_t *bytes);
 int rt_mesh_set_positions(RtContext *ctx, const float *positions);
 /* Gather with the model matrix M16 (column-major; NULL: identity), build, emit every record form, install.  Enqueued on rt_stream()'s stream, ordered

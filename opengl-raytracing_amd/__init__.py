@@ -1229,22 +1229,7 @@ class Renderer:
     def mesh_positions(self, as_torch=None):
         """The device array of object-space positions.  With torch (as_torch=None: when it imports) a float32 [V,3] tensor that aliases it, zero-copy;
         writes to it must be ordered on stream() (run them under torch.cuda.stream(torch.cuda.ExternalStream(ren.stream()))).  Else (pointer, bytes)."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_positions(self._h, C.byref(ptr), C.byref(n)))
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
-        if not as_torch:
-            return ptr.value, n.value
-        import torch
-        nv = n.value // 12
-
-        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-            __cuda_array_interface__ = {"shape": (nv, 3), "typestr": "<f4", "data": (ptr.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        return self._device_array("rt_mesh_positions", 3, as_torch)
 
     def mesh_set_positions(self, positions):
         v = _f32(positions).reshape(-1, 3)
@@ -1356,22 +1341,7 @@ class Renderer:
     def mesh_part_matrices(self, as_torch=None):
         """The device table of model matrices, one per part, column-major.  With torch (as_torch=None: when it imports) a float32 [nParts,16] tensor
         that aliases it, zero-copy; writes to it must be ordered on stream(), as for mesh_positions.  Else (pointer, bytes)."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_part_matrices(self._h, C.byref(ptr), C.byref(n)))
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
-        if not as_torch:
-            return ptr.value, n.value
-        import torch
-        nparts = n.value // 64
-
-        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-            __cuda_array_interface__ = {"shape": (nparts, 16), "typestr": "<f4", "data": (ptr.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        return self._device_array("rt_mesh_part_matrices", 16, as_torch)
 
     def mesh_set_part_matrices(self, models, first=0):
         """Matrices [count,16] (or [count,4,4] as default_bvh_transform lays one out: column-major) from host memory into entries first .. of the
@@ -1397,29 +1367,7 @@ class Renderer:
         (-1, -1) for a miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in,
         numpy out (rt_mesh_hit_parts_host: synchronises); a torch tensor on this context's device takes the zero-copy path of trace_rays: enqueued
         on the library stream, ordered against torch's current stream, no host wait."""
-        rec = hits.record if isinstance(hits, RayHits) else hits
-        if isinstance(rec, np.ndarray):
-            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
-                raise RtError(RT_ERR_INVALID, f"mesh_hit_parts: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
-            rec = np.ascontiguousarray(rec)
-            n = rec.shape[0]
-            parts, tris = np.zeros(n, np.int32), np.zeros(n, np.int32)
-            self._check(lib().rt_mesh_hit_parts_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(parts.ctypes.data), C.c_void_p(tris.ctypes.data)))
-            return parts, tris
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
-            raise RtError(RT_ERR_INVALID, f"mesh_hit_parts: records must be a numpy array or a float32 [N,4] tensor on {dev}")
-        rec = rec.contiguous()
-        n = rec.shape[0]
-        parts = torch.empty(n, dtype=torch.int32, device=dev)
-        tris = torch.empty(n, dtype=torch.int32, device=dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the records (and the outputs' allocation) are ready before the map starts
-        self._check(lib().rt_mesh_hit_parts(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(parts.data_ptr()), C.c_void_p(tris.data_ptr())))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
-        return parts, tris
+        return tuple(self._mesh_hit_query("mesh_hit_parts", hits, None, [(0, np.int32), (0, np.int32)]))
 
     # ---- skinning (DESIGN.md 14.10): the positions rewritten on the device from rest positions and a bone table
     def _device_view(self, ptr, nbytes, cols, as_torch):
@@ -1439,6 +1387,51 @@ class Renderer:
             __cuda_array_interface__ = {"shape": (rows, cols), "typestr": "<f4", "data": (ptr, False), "version": 2, "strides": None}
         return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
 
+    def _device_array(self, entry, cols, as_torch):
+        """_device_view of what the (context, void **devPtr, size_t *bytes) accessor `entry` names."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._check(getattr(lib(), entry)(self._h, C.byref(ptr), C.byref(n)))
+        return self._device_view(ptr.value, n.value, cols, as_torch)
+
+    def _mesh_hit_query(self, name, hits, extra, outputs):
+        """The four mesh_hit_* methods: hits a RayHits / SceneHits or its [N,4] float32 record array; extra None or (name, [N,3] array), a second
+        input; outputs (columns, dtype) per answer, columns 0: [N].  numpy in, numpy out through rt_<name>_host, which synchronises; torch tensors on
+        this context's device through rt_<name>: zero-copy, enqueued on the library stream, ordered against torch's current stream, no host wait.
+        -> the list of answers."""
+        rec = hits.record if isinstance(hits, RayHits) else hits
+        if isinstance(rec, np.ndarray):
+            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+                raise RtError(RT_ERR_INVALID, f"{name}: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+            rec = np.ascontiguousarray(rec)
+            n = rec.shape[0]
+            ins = [rec]
+            if extra is not None:
+                x = _f32(extra[1]).reshape(-1, 3)
+                if x.shape[0] != n:
+                    raise RtError(RT_ERR_INVALID, f"{name}: {n} hits and {x.shape[0]} {extra[0]}")
+                ins.append(x)
+            outs = [np.zeros((n, cols) if cols else n, dt) for cols, dt in outputs]
+            self._check(getattr(lib(), f"rt_{name}_host")(self._h, *(C.c_void_p(a.ctypes.data) for a in ins), n, *(C.c_void_p(o.ctypes.data) for o in outs)))
+            return outs
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+            raise RtError(RT_ERR_INVALID, f"{name}: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+        n = rec.shape[0]
+        ins = [rec.contiguous()]
+        if extra is not None:
+            x = extra[1]
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != 3 * n or x.device != dev:
+                raise RtError(RT_ERR_INVALID, f"{name}: {extra[0]} must be a float32 [N,3] tensor on {dev}")
+            ins.append(x.contiguous())
+        outs = [torch.empty((n, cols) if cols else n, dtype=getattr(torch, np.dtype(dt).name), device=dev) for cols, dt in outputs]
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the inputs (and the outputs' allocation) are ready before the kernel starts
+        self._check(getattr(lib(), f"rt_{name}")(self._h, *(C.c_void_p(a.data_ptr()) for a in ins), n, *(C.c_void_p(o.data_ptr()) for o in outs)))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        return outs
+
     def mesh_skin_upload(self, bone_idx, weights, n_bones, rest=None):
         """The skin of the current mesh (rt_mesh_skin_upload): bone_idx / weights [V,4], four influences per vertex; rest [V,3] rest positions, None: a
         device-to-device snapshot of mesh_positions() as it stands.  Allocates the bone table with every matrix the identity.  May synchronise;
@@ -1456,9 +1449,7 @@ class Renderer:
     def mesh_bones(self, as_torch=None):
         """The device table of bone matrices, column-major.  With torch (as_torch=None: when it imports) a float32 [nBones,16] tensor that aliases it,
         zero-copy; writes to it must be ordered on stream(), as for mesh_part_matrices.  Else (pointer, bytes)."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_bones(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 16, as_torch)
+        return self._device_array("rt_mesh_bones", 16, as_torch)
 
     def mesh_set_bones(self, models, first=0):
         """Matrices [count,16] (or [count,4,4], column-major) from host memory into entries first .. of the bone table, copied on stream() in call
@@ -1472,9 +1463,7 @@ class Renderer:
     def mesh_rest_positions(self, as_torch=None):
         """The device array of rest positions the skin reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes).
         mesh_morph(to="rest") blends morph targets into it; a caller with a deformer of its own writes it on stream() before mesh_skin."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_rest_positions(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 3, as_torch)
+        return self._device_array("rt_mesh_rest_positions", 3, as_torch)
 
     def mesh_skin(self):
         """Enqueue positions := skin(rest, tables, bone table) on stream() (rt_mesh_skin): what skin_positions computes, bit for bit, under the bone
@@ -1502,34 +1491,7 @@ class Renderer:
         a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array; points [N,3] the hit points (SceneHits.points, or
         origin + dir * t).  numpy in, numpy out (rt_mesh_hit_prev_points_host: synchronises); torch tensors on this context's device take the
         zero-copy path of mesh_hit_parts: enqueued on the library stream, ordered against torch's current stream, no host wait."""
-        rec = hits.record if isinstance(hits, RayHits) else hits
-        if isinstance(rec, np.ndarray):
-            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
-                raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
-            rec = np.ascontiguousarray(rec)
-            n = rec.shape[0]
-            x = _f32(points).reshape(-1, 3)
-            if x.shape[0] != n:
-                raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: {n} hits and {x.shape[0]} points")
-            out = np.zeros((n, 3), np.float32)
-            self._check(lib().rt_mesh_hit_prev_points_host(self._h, C.c_void_p(rec.ctypes.data), C.c_void_p(x.ctypes.data), n, C.c_void_p(out.ctypes.data)))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
-            raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: records must be a numpy array or a float32 [N,4] tensor on {dev}")
-        n = rec.shape[0]
-        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.numel() != 3 * n or points.device != dev:
-            raise RtError(RT_ERR_INVALID, f"mesh_hit_prev_points: points must be a float32 [N,3] tensor on {dev}")
-        rec = rec.contiguous()
-        x = points.contiguous()
-        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
-        self._check(lib().rt_mesh_hit_prev_points(self._h, C.c_void_p(rec.data_ptr()), C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr())))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
-        return out
+        return self._mesh_hit_query("mesh_hit_prev_points", hits, ("points", points), [(3, np.float32)])[0]
 
     # ---- smooth vertex normals (DESIGN.md 14.13): recomputed on the device behind every update, blended at mesh hits by frames and by mesh_hit_normals
     def mesh_normals_enable(self, on=True):
@@ -1541,9 +1503,7 @@ class Renderer:
     def mesh_vertex_normals(self, as_torch=None):
         """The device array of vertex normals: a float32 [V,4] tensor (nx, ny, nz, 0) that aliases it (as mesh_positions; written on stream() by the
         update calls), else (pointer, bytes).  vertex_normals of debug_read_scene("tris"), mesh_order() and the indices, bit for bit."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_vertex_normals(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 4, as_torch)
+        return self._device_array("rt_mesh_vertex_normals", 4, as_torch)
 
     def mesh_normal_rows(self) -> np.ndarray:
         """The corner normals as float32 [nTris,12] rows, three (nx, ny, nz, 0) per row (rt_debug_read_scene: synchronises); empty while normals are
@@ -1555,28 +1515,7 @@ class Renderer:
         zeros for a miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in, numpy
         out (rt_mesh_hit_normals_host: synchronises); a torch tensor on this context's device takes the zero-copy path of mesh_hit_parts: enqueued
         on the library stream, ordered against torch's current stream, no host wait."""
-        rec = hits.record if isinstance(hits, RayHits) else hits
-        if isinstance(rec, np.ndarray):
-            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
-                raise RtError(RT_ERR_INVALID, f"mesh_hit_normals: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
-            rec = np.ascontiguousarray(rec)
-            n = rec.shape[0]
-            out = np.zeros((n, 3), np.float32)
-            self._check(lib().rt_mesh_hit_normals_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(out.ctypes.data)))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
-            raise RtError(RT_ERR_INVALID, f"mesh_hit_normals: records must be a numpy array or a float32 [N,4] tensor on {dev}")
-        rec = rec.contiguous()
-        n = rec.shape[0]
-        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
-        self._check(lib().rt_mesh_hit_normals(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(out.data_ptr())))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
-        return out
+        return self._mesh_hit_query("mesh_hit_normals", hits, None, [(3, np.float32)])[0]
 
     # ---- per-vertex colours (DESIGN.md 14.14): kept on the device beside the triangle array, the albedo of mesh hits in frames and in mesh_hit_colors
     def mesh_colors_enable(self, on=True):
@@ -1588,9 +1527,7 @@ class Renderer:
     def mesh_colors(self, as_torch=None):
         """The device array of vertex colours: a float32 [V,4] tensor (r, g, b, 0) that aliases it (as mesh_positions; the caller may write it on
         stream()), else (pointer, bytes).  The rows follow at the next update or mesh_colors_refresh."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_colors(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 4, as_torch)
+        return self._device_array("rt_mesh_colors", 4, as_torch)
 
     def mesh_set_colors(self, rgb, first=0):
         """Colours [count,3] from host memory for vertices first .., copied on stream() in call order with updates, frames and queries
@@ -1616,28 +1553,7 @@ class Renderer:
         miss, an analytic hit or a prim outside the mesh.  hits: a RayHits / SceneHits or its [N,4] float32 record array.  numpy in, numpy out
         (rt_mesh_hit_colors_host: synchronises); a torch tensor on this context's device takes the zero-copy path of mesh_hit_normals: enqueued on
         the library stream, ordered against torch's current stream, no host wait."""
-        rec = hits.record if isinstance(hits, RayHits) else hits
-        if isinstance(rec, np.ndarray):
-            if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
-                raise RtError(RT_ERR_INVALID, f"mesh_hit_colors: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
-            rec = np.ascontiguousarray(rec)
-            n = rec.shape[0]
-            out = np.zeros((n, 3), np.float32)
-            self._check(lib().rt_mesh_hit_colors_host(self._h, C.c_void_p(rec.ctypes.data), n, C.c_void_p(out.ctypes.data)))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
-            raise RtError(RT_ERR_INVALID, f"mesh_hit_colors: records must be a numpy array or a float32 [N,4] tensor on {dev}")
-        rec = rec.contiguous()
-        n = rec.shape[0]
-        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the records (and the output's allocation) are ready before the kernel starts
-        self._check(lib().rt_mesh_hit_colors(self._h, C.c_void_p(rec.data_ptr()), n, C.c_void_p(out.data_ptr())))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
-        return out
+        return self._mesh_hit_query("mesh_hit_colors", hits, None, [(3, np.float32)])[0]
 
     # ---- morph targets (DESIGN.md 14.11): sparse deltas blended on the device under a weight table, before the skin or straight into the positions
     def mesh_morph_upload(self, target_first, vert_idx, deltas, base=None):
@@ -1656,16 +1572,12 @@ class Renderer:
 
     def mesh_morph_base(self, as_torch=None):
         """The device array of base positions the morph reads: a float32 [V,3] tensor that aliases it (as mesh_positions), else (pointer, bytes)."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_morph_base(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 3, as_torch)
+        return self._device_array("rt_mesh_morph_base", 3, as_torch)
 
     def mesh_morph_weights(self, as_torch=None):
         """The device table of target weights, zero after the upload.  With torch (as_torch=None: when it imports) a float32 [nTargets,1] tensor that
         aliases it, zero-copy; writes to it must be ordered on stream(), as for mesh_bones.  Else (pointer, bytes)."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        self._check(lib().rt_mesh_morph_weights(self._h, C.byref(ptr), C.byref(n)))
-        return self._device_view(ptr.value, n.value, 1, as_torch)
+        return self._device_array("rt_mesh_morph_weights", 1, as_torch)
 
     def mesh_set_morph_weights(self, weights, first=0):
         """Weights [count] from host memory into entries first .. of the weight table, copied on stream() in call order with morphs, skins, updates,

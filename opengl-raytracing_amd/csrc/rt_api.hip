@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -16,144 +15,14 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: RCCL is bound at run time (rccl_api below), single-GPU users never load it
 
-#include "../../include/rt_mi355.h"
-#include "rt_frame.hpp"
-#include "rt_bvh_cost.hpp"
-#include "rt_mesh.hpp"
-#include "rt_morph_pack.hpp"
-#include "rt_normal_pack.hpp"
+#include "rt_context.hpp"
 #include "rt_scene_pack.hpp"
 #include "rt_wave_plan.hpp"
-#include "rt_wave.hpp"
 
 using namespace rtd;
+using namespace rtapi;
 
-static thread_local std::string g_createError;
-
-#define RT_MAX_LANES 8
 constexpr int kDefaultArenas = 2;   // ray-queue arenas shared by the frame lanes (rt_wave.hpp RtArenaPool; measured in profiles/r04_experiments.txt)
-struct StageEvent { int stage; hipEvent_t a, b; };
-
-struct RtContext {
-    RtDeviceConfig cfg{};
-    // Frames in flight: frame f runs on lane f % nLanes (own stream, frame descriptor, ray-queue arenas, COLOR0 buffer), so
-    // up to nLanes consecutive frames overlap everywhere except at the temporal resolve.  stream == lanes[0]: every
-    // non-frame operation runs there after a sync of all lanes.
-    int nLanes = 3;
-    bool serialFrames = false;          // RT_LANES=1: a frame starts when its predecessor has finished
-    hipStream_t lanes[RT_MAX_LANES] = {};
-    hipStream_t stream = nullptr;
-    hipStream_t lastStream = nullptr;    // stream of the most recent frame (gather / assemble are ordered behind it)
-    hipEvent_t evDone[RT_MAX_LANES] = {};   // the frame on lane i has written its targets
-    std::string err;
-    // scene
-    float4 *dWNodes = nullptr, *dW4 = nullptr, *dTris = nullptr, *dWNodesW = nullptr, *dPairs = nullptr;
-    float4 *dQ4 = nullptr, *dLeafBox = nullptr;   // RT_QNODES: quantised any-hit nodes + the leaves' exact boxes
-    float4 *dWF = nullptr;           // fused closest-hit records (round 5), null when the tree's boxes are not the unions of their children's
-    float4 *dIN4 = nullptr, *dIQ4 = nullptr, *dILeafBox = nullptr;   // ... and the any-hit walk's four-wide records, exact (96 B) and quantised (48 B + the leaves' exact boxes by ordinal)
-    float4 *dIN2 = nullptr, *dIPairs = nullptr;   // implicit records (round 5): 48-byte two-child records without references + the pair records in leaf order; null unless every leaf sits at depth implD
-    int implD = 0, implR = 0;
-    size_t nFused = 0;
-    int sceneFlags = 0;              // RT_SCENE_* bits of RtSceneInfo.flags
-    int rootRefW = 0;
-    void *dHistAll[RT_MAX_LANES] = {};      // tile-parallel + moving camera: every rank's COLOR0 block of the frame a lane rendered
-    bool histExchanged[RT_MAX_LANES] = {};
-    uchar4 *dEnv = nullptr;
-    int envSize = 0;
-    int nNodes = 0, nTris = 0, nInner = 0, rootRef = 0, rootRef4 = 0, treeDepth = 0;
-    size_t nWide4 = 0, nPairs = 0;   // records in dW4 / dPairs
-    size_t nLeafBoxes = 0;           // leaves with an exact box in dLeafBox (quantised any-hit nodes)
-    uint32_t leafBoxMagic = 0;       // dLeafBox index of a leaf = (first pair record * magic) >> 32 (0: = first)
-    int anyStack = 0;                // stack entries of the any-hit walk (0: from the binary depth)
-    float rootMin[3] = {0, 0, 0}, rootMax[3] = {0, 0, 0};
-    size_t leafBoxBytes = 0;         // bytes of dLeafBox
-    // dynamic mesh: its arrays belong to `mesh`; once a rebuild has installed them the scene pointers above alias them (sceneFromMesh)
-    rtl::Mesh *mesh = nullptr;
-    bool sceneFromMesh = false;
-    float *dRootBox = nullptr;       // sceneFromMesh: node 0's box on the device -- the host does not know it (rootMin / rootMax above are not used then)
-    hipEvent_t evMeshLane[RT_MAX_LANES] = {}, evMeshDone = nullptr;   // a rebuild waits for every lane / every lane waits for the rebuild
-    hipEvent_t evMeshOrder = nullptr;      // the order array of the current tree has been written, on meshOrderStream
-    hipStream_t meshOrderStream = nullptr;
-    uint64_t meshRebuilds = 0, meshHostSyncs = 0, meshRefits = 0, meshRefitsSinceRebuild = 0;
-    bool meshMotionDirty = false;          // previous pose: an update since the last latch, for rt_render_ray's own frame state
-    // tree quality: which result slots of the mesh are in flight and what they measure; the arrived records the policy reads
-    struct MeshQSlot { bool inFlight = false; uint64_t update = 0, tree = 0; int32_t refits = 0; } meshQSlot[rtl::kQualityRing];
-    RtMeshQuality meshQLatest = {}, meshQBaseline = {};
-    bool meshQHaveLatest = false, meshQHaveBaseline = false;
-    uint64_t meshQLatestTree = 0, meshQBaselineTree = 0;   // RtMeshInfo.rebuilds when the measured tree was built
-    uint64_t meshQSkipped = 0, meshQEnqueued = 0;
-    int meshQNewest = -1;                                  // slot of the newest enqueued measurement
-    // frame state
-    FrameGeom g{};
-    bool sized = false;
-    uint2 *dColor[RT_MAX_LANES] = {};   // COLOR0 ring: frame f writes [f % nLanes], reads [(f-1) % nLanes]
-    // motion / position / normal are ringed like COLOR0: a gather (or any other reader) of frame f's targets runs on lane f's
-    // stream and must not see frame f+1's stores, which run on another stream
-    uint32_t *dMotion[RT_MAX_LANES] = {};
-    uint2 *dGPos[RT_MAX_LANES] = {}, *dGNrm[RT_MAX_LANES] = {};
-    size_t nSlots = 0;
-    int frameIndex = 0, writeIdx = 0;     // include/render/accum.h:125-138
-    bool haveFrameState = false;
-    float prevVP[16];
-    DevFrame *dFrame[RT_MAX_LANES] = {};
-    unsigned long long *dCounters = nullptr;
-    void *dStaging = nullptr;
-    size_t stagingBytes = 0;
-    RtWave *wave[RT_MAX_LANES] = {};
-    RtArenaPool *arenaPool = nullptr;   // ray-queue arenas shared by the lanes' wavefront pipelines
-    RtHybrid *hybrid[RT_MAX_LANES] = {};   // EXTENSION: staged hybrid pipeline, created on first use
-    RtRaster *raster = nullptr;            // raster preview (rt_raster.hip): mesh slots + its own buffers, created on first use
-    int cus = 256;
-    uint32_t debugBuilds = 0;   // RT_BUILD_* bits of the rt_debug_trace kind 2 - 4 launches since the last rt_debug_builds reset
-    // rt_trace_rays scratch, allocated on the first query: the query's frame descriptor (uEPS / uINF / scene, written on the stream) and its
-    // cursor words.  Queries share it, so a query on another stream than the previous one waits for that one's event first.
-    DevFrame *dQueryFrame = nullptr;
-    uint32_t *dQueryHeads = nullptr;
-    hipEvent_t queryDone = nullptr;
-    hipStream_t queryStream = nullptr;   // stream of the last query (null: none yet)
-    int giBounces = 1;   // EXTENSION, rt_set_extension
-    int envFilter = 0;   // rt_set_extension: cube-map filter model (0 exact fp32 weights, 1 coordinates rounded to 1/256 texel)
-    // tile-parallel exchange owned by the library (rt_comm.cpp): RCCL communicator + per-lane gather buffers on the gathering rank
-    void *comm = nullptr;                               // ncclComm_t
-    void *dGathered[RT_MAX_LANES][4] = {};              // [lane][target]: worldSize blocks, rank-major
-    void *dAssembled[RT_MAX_LANES][4] = {};             // [lane][target]: row-major frame of halfs
-    int gatheredLane[4] = {-1, -1, -1, -1};             // lane whose frame rt_gather_frame(which) gathered last
-    // timing
-    bool timing = false;
-    std::vector<StageEvent> pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> freeEvents;
-    uint64_t gathers = 0, gatherBytes = 0, historyExchanges = 0;   // rt_comm_info
-    double stageMs[RT_MAX_STAGES] = {0};
-    uint64_t stageLaunches[RT_MAX_STAGES] = {0};
-    int timedFrames = 0;
-};
-
-static int fail(RtContext *c, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf; else g_createError = buf;
-    return code;
-}
-// No C++ exception crosses the C ABI: std::bad_alloc etc. from the host-side repacking become status codes.
-template <class F> static int guarded(RtContext *c, const char *what, F &&body) {
-    try { return body(); }
-    catch (const std::bad_alloc &) { return fail(c, RT_ERR_IO, "%s: out of host memory", what); }
-    catch (...) { return fail(c, RT_ERR_INVALID, "%s: unexpected exception", what); }
-}
-static hipError_t sync_all(RtContext *c) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < c->nLanes; ++i)
-        if (c->lanes[i]) { hipError_t ei = hipStreamSynchronize(c->lanes[i]); if (e == hipSuccess) e = ei; }
-    return e;
-}
-#define HIP_TRY(c, expr)                                                                                  \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((c), RT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 static const char *kStageNames[RT_MAX_STAGES] = {"mega",     "primary", "trace_primary",   "post_primary", "gen_direct", "trace_shadow",
                                                  "trace_gi", "gen_gi",  "resolve",         "combine",      "assemble",   "present",
@@ -291,33 +160,6 @@ __global__ __launch_bounds__(256) void k_debug_trace(DevScene sc, int kind, cons
     }
 }
 
-DevScene make_dev_scene(const RtContext *c) {
-    DevScene s;
-    s.wnodes = c->dWNodes;
-    s.w4 = c->dW4;
-    s.q4 = c->dQ4;
-    s.leafBox = c->dLeafBox;
-    s.leafBoxMagic = c->leafBoxMagic;
-    s.wnodesW = c->dWNodesW;
-    s.wF = c->dWF;
-    s.iN2 = c->dIN2; s.iPairs = c->dIPairs; s.implD = c->implD; s.implR = c->implR;
-    s.iN4 = c->dIN4; s.iQ4 = c->dIQ4; s.iLeafBox = c->dILeafBox;
-    s.pairs = c->dPairs;
-    s.rootRefW = c->rootRefW;
-    s.tris = c->dTris;
-    s.env = c->dEnv;
-    s.envSize = c->envSize;
-    s.envFilter = c->envFilter;
-    s.rootRef = c->rootRef;
-    s.rootRef4 = c->rootRef4;
-    s.hasBVH = (c->nNodes > 0 && c->nTris > 0) ? 1 : 0;
-    s.anyStack = c->anyStack;
-    std::memcpy(s.rootMin, c->rootMin, 12);
-    std::memcpy(s.rootMax, c->rootMax, 12);
-    s.rootBox = c->sceneFromMesh ? c->dRootBox : nullptr;
-    return s;
-}
-
 void free_gather_buffers(RtContext *c) {
     for (int l = 0; l < RT_MAX_LANES; ++l)
         for (int w = 0; w < 4; ++w) {
@@ -341,28 +183,6 @@ void free_targets(RtContext *c) {
     c->sized = false;
 }
 
-int ensure_staging(RtContext *c, size_t bytes) {
-    if (c->stagingBytes >= bytes) return RT_OK;
-    if (c->dStaging) (void)hipFree(c->dStaging);
-    c->dStaging = nullptr; c->stagingBytes = 0;
-    HIP_TRY(c, hipMalloc(&c->dStaging, bytes));
-    c->stagingBytes = bytes;
-    return RT_OK;
-}
-
-// The one list of what makes up the BVH scene: afterwards the context describes the empty scene.  owned: the arrays are the context's and are freed
-// (false: they alias the dynamic mesh's and are only forgotten).  Callers have synchronised.
-void clear_scene(RtContext *c, bool owned) {
-    float4 **arrays[] = {&c->dWNodes, &c->dWNodesW, &c->dW4, &c->dQ4, &c->dLeafBox, &c->dWF, &c->dIN2, &c->dIPairs, &c->dIN4, &c->dIQ4, &c->dILeafBox, &c->dPairs, &c->dTris};
-    for (float4 **p : arrays) { if (owned && *p) (void)hipFree(*p); *p = nullptr; }
-    c->nNodes = c->nTris = c->nInner = c->treeDepth = 0;
-    c->nWide4 = c->nPairs = c->nFused = c->nLeafBoxes = c->leafBoxBytes = 0;
-    c->rootRef = c->rootRefW = c->rootRef4 = c->anyStack = 0;
-    c->implD = c->implR = 0;
-    c->leafBoxMagic = 0;
-    c->sceneFlags = 0;
-    for (int a = 0; a < 3; ++a) c->rootMin[a] = c->rootMax[a] = 0.0f;
-}
 void free_scene(RtContext *c) { clear_scene(c, true); }
 
 // One scene array to the device (an empty one stays null)
@@ -371,23 +191,6 @@ template <class T> int upload(RtContext *c, float4 **dst, const std::vector<T> &
     HIP_TRY(c, hipMalloc(dst, v.size() * sizeof(T)));
     HIP_TRY(c, hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return RT_OK;
-}
-
-// Lets go of the dynamic mesh; a scene its rebuild installed goes with it (the scene pointers alias the mesh's arrays).  Callers have synchronised.
-void release_mesh(RtContext *c) {
-    if (c->sceneFromMesh) {
-        clear_scene(c, false);
-        c->sceneFromMesh = false;
-        c->dRootBox = nullptr;
-    }
-    rtl::mesh_destroy(c->mesh);
-    c->mesh = nullptr;
-    c->meshMotionDirty = false;
-    for (int i = 0; i < RT_MAX_LANES; ++i) { if (c->evMeshLane[i]) (void)hipEventDestroy(c->evMeshLane[i]); c->evMeshLane[i] = nullptr; }
-    if (c->evMeshDone) (void)hipEventDestroy(c->evMeshDone);
-    c->evMeshDone = nullptr;
-    if (c->evMeshOrder) (void)hipEventDestroy(c->evMeshOrder);
-    c->evMeshOrder = nullptr; c->meshOrderStream = nullptr;
 }
 
 int last_lane(const RtContext *c) { return (c->writeIdx + c->nLanes - 1) % c->nLanes; }   // lane of the frame rendered last
@@ -579,829 +382,6 @@ int rt_build_bvh_gpu(RtContext *c, const float *tris9, int nTris, float *nodes12
     const int rc = rtl::build_bvh_gpu(c->cfg.device, tris9, nTris, nodes12, tris12, &err);
     if (rc < 0) return fail(c, rc, "rt_build_bvh_gpu: %s", err ? err : "bad arguments");
     return rc;
-}
-
-// ---- dynamic mesh: rt_mesh.hip builds, this file orders the rebuild against the lanes and installs its arrays
-int rt_bvh_layout(int nTris, RtBvhLayout *out) {
-    if (!out) return RT_ERR_INVALID;
-    std::memset(out, 0, sizeof *out);
-    return guarded(nullptr, "rt_bvh_layout", [&]() -> int {
-        rtl::BvhLayout L;
-        const int rc = rtl::bvh_layout(nTris, L);
-        if (rc == RT_ERR_INVALID) return fail(nullptr, rc, "rt_bvh_layout: nTris = %d", nTris);
-        if (rc != RT_OK) return fail(nullptr, rc, "rt_bvh_layout: %d triangles exceed the 2^28 leaf encoding or the 32-entry traversal stack", nTris);
-        out->nTris = L.nTris; out->nNodes = L.nNodes; out->nInner = L.nInner; out->treeDepth = L.treeDepth;
-        out->nWide4 = (int32_t)L.nWide4; out->nPairs = (int32_t)L.nPairs; out->anyStack = L.anyStack;
-        out->quantised = rtl::want_quantised(rtl::pack_options_from_env(), L.nWide4, L.rootRef4) ? 1 : 0;
-        out->bytesNodes2 = (uint64_t)std::max(L.nInner, 1) * 64;
-        out->bytesNodes4 = out->quantised ? (uint64_t)L.nWide4 * 64 + (uint64_t)L.nLeaves * 32 : (uint64_t)L.nWide4 * 128;
-        out->bytesPairs = (uint64_t)L.nPairs * 80;
-        out->bytesTris = (uint64_t)L.nTris * 48;
-        return RT_OK;
-    });
-}
-
-static void mesh_quality_reset(RtContext *c) {
-    for (auto &sl : c->meshQSlot) sl = RtContext::MeshQSlot{};
-    c->meshQLatest = c->meshQBaseline = RtMeshQuality{};
-    c->meshQHaveLatest = c->meshQHaveBaseline = false;
-    c->meshQLatestTree = c->meshQBaselineTree = 0;
-    c->meshQSkipped = c->meshQEnqueued = 0;
-    c->meshQNewest = -1;
-}
-
-// rt_mesh_upload (partFirst == null: one part holding everything) and rt_mesh_upload_parts
-static int mesh_upload(RtContext *c, const char *who, const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts) {
-    if (!c) return RT_ERR_INVALID;
-    if (nIdx < 0 || nVerts < 0 || (nIdx > 0 && (!positions || !indices || nVerts == 0))) return fail(c, RT_ERR_INVALID, "%s: bad arguments", who);
-    if (nIdx % 3 != 0) return fail(c, RT_ERR_INVALID, "%s: %d indices are not a list of triangles", who, nIdx);
-    for (int k = 0; k < nIdx; ++k)
-        if (indices[k] >= (uint32_t)nVerts) return fail(c, RT_ERR_INVALID, "%s: index %d names vertex %u of %d", who, k, indices[k], nVerts);
-    const int32_t one[2] = {0, nIdx / 3};
-    if (!partFirst) { partFirst = one; nParts = 1; }
-    if (nParts < 1 || nParts > RT_MAX_MESH_PARTS) return fail(c, RT_ERR_INVALID, "%s: %d parts (1 .. %d)", who, nParts, RT_MAX_MESH_PARTS);
-    if (partFirst[0] != 0 || partFirst[nParts] != nIdx / 3)
-        return fail(c, RT_ERR_INVALID, "%s: partFirst runs from %d to %d, the mesh from 0 to %d triangles", who, partFirst[0], partFirst[nParts], nIdx / 3);
-    for (int p = 0; p < nParts; ++p)
-        if (partFirst[p + 1] < partFirst[p]) return fail(c, RT_ERR_INVALID, "%s: partFirst decreases at part %d (%d after %d)", who, p, partFirst[p + 1], partFirst[p]);
-    const rtl::PackOptions opt = rtl::pack_options_from_env();
-    if (nIdx > 0) {
-        if (opt.fused) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_FUSED records are not rebuilt on the device", who);
-        if (opt.implicit) return fail(c, RT_ERR_UNSUPPORTED, "%s: RT_IMPLICIT records are not rebuilt on the device", who);
-        if (opt.anyhitSah) return fail(c, RT_ERR_UNSUPPORTED, "%s: the RT_ANYHIT_TREE=sah tree is not rebuilt on the device", who);
-        if (nIdx / 3 >= (1 << 28)) return fail(c, RT_ERR_UNSUPPORTED, "%s: %d triangles exceed the 2^28 leaf encoding", who, nIdx / 3);
-    }
-    const int rc = rt_upload_bvh(c, nullptr, 0, nullptr, 0);   // waits for the lanes, removes the scene and the previous mesh, forgets the bounce share
-    if (rc != RT_OK || nIdx == 0) return rc;
-    return guarded(c, who, [&]() -> int {
-        rtl::BvhLayout L;
-        const int lr = rtl::bvh_layout(nIdx / 3, L);
-        if (lr != RT_OK) return fail(c, lr, "%s: %d triangles cannot be laid out", who, nIdx / 3);
-        const char *err = nullptr;
-        const int mr = rtl::mesh_create(positions, nVerts, indices, nIdx, partFirst, nParts, rtl::want_quantised(opt, L.nWide4, L.rootRef4), opt.sparseLeafBoxes, &c->mesh, &err);
-        if (mr != RT_OK) { c->mesh = nullptr; return fail(c, mr, "%s: %s", who, err ? err : "layout failed"); }
-        bool ok = hipEventCreateWithFlags(&c->evMeshDone, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&c->evMeshOrder, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < c->nLanes; ++i) ok = hipEventCreateWithFlags(&c->evMeshLane[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { release_mesh(c); return fail(c, RT_ERR_HIP, "%s: event creation failed", who); }
-        c->meshRebuilds = c->meshHostSyncs = c->meshRefits = c->meshRefitsSinceRebuild = 0;
-        mesh_quality_reset(c);
-        return RT_OK;
-    });
-}
-
-int rt_mesh_upload(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx) {
-    return mesh_upload(c, "rt_mesh_upload", positions, nVerts, indices, nIdx, nullptr, 1);
-}
-
-int rt_mesh_upload_parts(RtContext *c, const float *positions, int nVerts, const uint32_t *indices, int nIdx, const int32_t *partFirst, int nParts) {
-    if (!c) return RT_ERR_INVALID;
-    if (!partFirst) return fail(c, RT_ERR_INVALID, "rt_mesh_upload_parts: null partFirst");
-    return mesh_upload(c, "rt_mesh_upload_parts", positions, nVerts, indices, nIdx, partFirst, nParts);
-}
-
-int rt_mesh_parts(RtContext *c, int32_t *partFirst, int capacity, int *nParts) {
-    if (!c || !nParts) return RT_ERR_INVALID;
-    *nParts = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_parts: no mesh (rt_mesh_upload first)");
-    const int n = rtl::mesh_part_count(c->mesh);
-    *nParts = n;
-    if (!partFirst) return RT_OK;
-    if (capacity < n + 1) return fail(c, RT_ERR_INVALID, "rt_mesh_parts: room for %d entries, the table has %d", capacity, n + 1);
-    std::memcpy(partFirst, rtl::mesh_part_first(c->mesh), (size_t)(n + 1) * sizeof(int32_t));
-    return RT_OK;
-}
-
-int rt_mesh_part_matrices(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_part_matrices: no mesh (rt_mesh_upload first)");
-    *devPtr = rtl::mesh_part_matrices(c->mesh);
-    *bytes = (size_t)rtl::mesh_part_count(c->mesh) * 64;
-    return RT_OK;
-}
-
-int rt_mesh_set_part_matrices(RtContext *c, int first, int count, const float *M16s) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: no mesh (rt_mesh_upload first)");
-    const int n = rtl::mesh_part_count(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: entries %d .. %d of a table of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!M16s) return fail(c, RT_ERR_INVALID, "rt_mesh_set_part_matrices: null matrices");
-    (void)hipSetDevice(c->cfg.device);
-    if (c->raster && rt_raster_order_after(c->raster, c->lastStream ? c->lastStream : c->stream) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_set_part_matrices: %s", rt_raster_error(c->raster));
-    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_part_matrices(c->mesh) + (size_t)first * 16, M16s, (size_t)count * 64, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
-    return RT_OK;
-}
-
-int rt_mesh_positions(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_positions: no mesh (rt_mesh_upload first)");
-    *devPtr = rtl::mesh_positions(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
-    return RT_OK;
-}
-
-int rt_mesh_set_positions(RtContext *c, const float *positions) {
-    if (!c || !positions) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_set_positions: no mesh (rt_mesh_upload first)");
-    (void)hipSetDevice(c->cfg.device);
-    if (c->raster && rt_raster_order_after(c->raster, c->lastStream ? c->lastStream : c->stream) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_set_positions: %s", rt_raster_error(c->raster));
-    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_positions(c->mesh), positions, (size_t)rtl::mesh_verts(c->mesh) * 12, hipMemcpyHostToDevice, c->lastStream ? c->lastStream : c->stream));
-    return RT_OK;
-}
-
-// The two halves of the mesh path's event scheme around work enqueued on `st`, rt_stream()'s stream: what follows on `st` waits for
-// everything already enqueued on every other lane ...
-static int mesh_after_lanes(RtContext *c, hipStream_t st) {
-    for (int i = 0; i < c->nLanes; ++i) {
-        if (c->lanes[i] == st) continue;
-        HIP_TRY(c, hipEventRecord(c->evMeshLane[i], c->lanes[i]));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshLane[i], 0));
-    }
-    return RT_OK;
-}
-// ... and whatever another lane is given next waits for what has been enqueued on `st` so far.
-static int mesh_before_lanes(RtContext *c, hipStream_t st) {
-    HIP_TRY(c, hipEventRecord(c->evMeshDone, st));
-    for (int i = 0; i < c->nLanes; ++i)
-        if (c->lanes[i] != st) HIP_TRY(c, hipStreamWaitEvent(c->lanes[i], c->evMeshDone, 0));
-    return RT_OK;
-}
-
-// A rebuild or a refit: the device work of rt_mesh.hip between the two halves of the event scheme, then the scene installed (the same pointers and
-// counts every time; what a refit can change is whether the quantised nodes could be built).
-// parts: gather under the device matrix table instead of under M16.
-static int mesh_update(RtContext *c, const float *M16, bool refit, bool parts = false, const char *caller = nullptr) {
-    const char *who = caller ? caller : parts ? (refit ? "rt_mesh_refit_parts" : "rt_mesh_rebuild_parts") : (refit ? "rt_mesh_refit" : "rt_mesh_rebuild");
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", who);
-    if (refit && !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree to keep (rt_mesh_rebuild first)", who);
-    (void)hipSetDevice(c->cfg.device);
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    // every lane's frames and queries read the arrays that are about to be rewritten: the update waits for them ...
-    int rc = mesh_after_lanes(c, st);
-    if (rc != RT_OK) return rc;
-    const char *err = nullptr;
-    const float *gatherM = parts ? nullptr : (M16 ? M16 : kIdentity);   // null: the part-aware gather
-    const bool orderWas = refit && rtl::mesh_order_written(c->mesh);
-    rc = refit ? rtl::mesh_refit(c->mesh, st, gatherM, &err) : rtl::mesh_rebuild(c->mesh, st, gatherM, &err);
-    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
-    // smooth normals: the update derived the order array for itself, on `st`
-    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
-    // ... and whatever a lane is given next waits for it
-    rc = mesh_before_lanes(c, st);
-    if (rc != RT_OK) return rc;
-    const rtl::BvhLayout &L = rtl::mesh_layout(c->mesh);
-    const rtl::MeshScene &sc = rtl::mesh_scene(c->mesh);
-    bool okQ = sc.q4 != nullptr;
-    if (sc.q4) {   // the host picks the any-hit kernel by whether the quantised nodes exist: the one allowed wait
-        rc = rtl::mesh_quantised_ok(c->mesh, st, okQ, &err);
-        ++c->meshHostSyncs;
-        if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "status read failed");
-    }
-    // install: pointers and counts are those of the mesh, the same at every rebuild
-    c->dWNodes = sc.wnodes; c->dWNodesW = sc.wnodesW; c->dW4 = sc.w4; c->dPairs = sc.pairs; c->dTris = sc.tris;
-    c->dQ4 = okQ ? sc.q4 : nullptr; c->dLeafBox = okQ ? sc.leafBox : nullptr;
-    c->leafBoxBytes = sc.leafBoxBytes; c->leafBoxMagic = sc.leafBoxMagic; c->nLeafBoxes = L.nLeaves;
-    c->sceneFlags = (sc.q4 && !okQ) ? RT_SCENE_QNODES_REJECTED : 0;
-    if (sc.q4 && !okQ && rtl::pack_options_from_env().verbose) fprintf(stderr, "[%s] quantised any-hit nodes rejected (exponent range): walking the exact 112-byte nodes\n", who);
-    c->nNodes = L.nNodes; c->nTris = L.nTris; c->nInner = L.nInner; c->treeDepth = L.treeDepth;
-    c->nWide4 = L.nWide4; c->nPairs = L.nPairs; c->nFused = 0;
-    c->rootRef = L.rootRef; c->rootRefW = L.rootRefW; c->rootRef4 = L.rootRef4; c->anyStack = L.anyStack;
-    c->dRootBox = sc.rootBox;
-    c->sceneFromMesh = true;
-    if (refit) { ++c->meshRefits; ++c->meshRefitsSinceRebuild; }
-    else { ++c->meshRebuilds; c->meshRefitsSinceRebuild = 0; }
-    if (rtl::mesh_prev_tris(c->mesh)) c->meshMotionDirty = true;
-    return RT_OK;
-}
-
-int rt_mesh_rebuild(RtContext *c, const float *M16) { return mesh_update(c, M16, false); }
-int rt_mesh_refit(RtContext *c, const float *M16) { return mesh_update(c, M16, true); }
-int rt_mesh_rebuild_parts(RtContext *c) { return mesh_update(c, nullptr, false, true); }
-int rt_mesh_refit_parts(RtContext *c) { return mesh_update(c, nullptr, true, true); }
-
-// ---- previous pose: rt_mesh.hip moves it inside every update; this file owns enabling, the latch's ordering and the hit query
-int rt_mesh_motion_enable(RtContext *c, int on) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-    c->meshMotionDirty = false;
-    if (!on) { rtl::mesh_motion_release(c->mesh); return RT_OK; }
-    const char *err = nullptr;
-    const int rc = rtl::mesh_motion_create(c->mesh, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_motion_enable: %s", err ? err : "allocation failed");
-    return RT_OK;
-}
-
-int rt_mesh_motion_latch(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_prev_tris(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: motion is not enabled (rt_mesh_motion_enable first)");
-    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_motion_latch: no pose to keep (rt_mesh_rebuild first)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    int rc = mesh_after_lanes(c, st);   // frames and queries on every lane read the previous pose they were enqueued with ...
-    if (rc != RT_OK) return rc;
-    const char *err = nullptr;
-    rc = rtl::mesh_motion_latch(c->mesh, st, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_motion_latch: %s", err ? err : "copy failed");
-    c->meshMotionDirty = false;
-    return mesh_before_lanes(c, st);    // ... and whatever a lane is given next sees the latched one
-}
-
-static int hit_prev_points_args(RtContext *c, const char *who, const RtHit *hits, const float *points, int n, const float *prevPoints) {
-    if (n < 0 || (n > 0 && (!hits || !points)) || !prevPoints) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits, points and prevPoints are needed)", who, n);
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
-    if (!rtl::mesh_prev_tris(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: motion is not enabled (rt_mesh_motion_enable first)", who);
-    return RT_OK;
-}
-
-int rt_mesh_hit_prev_points(RtContext *c, const RtHit *hits, const float *points, int n, float *prevPoints) {
-    if (!c) return RT_ERR_INVALID;
-    int rc = hit_prev_points_args(c, "rt_mesh_hit_prev_points", hits, points, n, prevPoints);
-    if (rc != RT_OK) return rc;
-    if (((uintptr_t)hits & 15u) || (((uintptr_t)points | (uintptr_t)prevPoints) & 3u))
-        return fail(c, RT_ERR_INVALID, "rt_mesh_hit_prev_points: hits must be 16-byte aligned, points and prevPoints 4-byte aligned");
-    if (n == 0) return RT_OK;
-    (void)hipSetDevice(c->cfg.device);
-    const char *err = nullptr;
-    rc = rtl::mesh_hit_prev_points(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, points, n, prevPoints, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_prev_points: %s", err ? err : "launch failed");
-    return RT_OK;
-}
-
-int rt_mesh_hit_prev_points_host(RtContext *c, const RtHit *hits, const float *points, int n, float *prevPoints) {
-    if (!c) return RT_ERR_INVALID;
-    const int ar = hit_prev_points_args(c, "rt_mesh_hit_prev_points_host", hits, points, n, prevPoints);
-    if (ar != RT_OK) return ar;
-    if (n == 0) return RT_OK;
-    return guarded(c, "rt_mesh_hit_prev_points_host", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    const size_t N = (size_t)n, hB = N * sizeof(RtHit), pB = (N * 12 + 15) / 16 * 16, total = hB + 2 * pB;   // hits | points | prevPoints
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(base + hB, points, N * 12, hipMemcpyHostToDevice, st));
-    const int qr = rt_mesh_hit_prev_points(c, (const RtHit *)base, (const float *)(base + hB), n, (float *)(base + hB + pB));
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    HIP_TRY(c, hipMemcpyAsync(prevPoints, base + hB + pB, N * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
-    });
-}
-
-// ---- smooth vertex normals: rt_normal_pack.cpp packs the adjacency, rt_mesh.hip recomputes the normals inside every update; this file
-// owns enabling and the hit query
-int rt_mesh_normals_enable(RtContext *c, int on) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_normals_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    return guarded(c, "rt_mesh_normals_enable", [&]() -> int {
-        (void)hipSetDevice(c->cfg.device);
-        HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-        if (!on) { rtl::mesh_normals_release(c->mesh); return RT_OK; }
-        const int nIdx = rtl::mesh_layout(c->mesh).nTris * 3, nVerts = rtl::mesh_verts(c->mesh);
-        std::vector<uint32_t> idx((size_t)nIdx);
-        HIP_TRY(c, hipMemcpy(idx.data(), rtl::mesh_indices(c->mesh), (size_t)nIdx * 4, hipMemcpyDeviceToHost));
-        std::string perr;
-        int rc = rtl::normal_validate(idx.data(), nIdx, nVerts, perr);
-        rtl::NormalPlan plan;
-        if (rc == RT_OK) rc = rtl::normal_plan(idx.data(), nIdx, nVerts, plan, perr);
-        if (rc != RT_OK) return fail(c, rc, "rt_mesh_normals_enable: %s", perr.c_str());
-        std::vector<int32_t> entries;
-        rtl::normal_fill(plan, idx.data(), nIdx, entries);
-        const bool orderWas = rtl::mesh_order_written(c->mesh);
-        hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-        const char *err = nullptr;
-        rc = rtl::mesh_normals_create(c->mesh, st, plan.sliceFirst.data(), entries.data(), plan.info, &err);
-        if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
-        if (rc != RT_OK) return fail(c, rc, "rt_mesh_normals_enable: %s", err ? err : "allocation failed");
-        return RT_OK;
-    });
-}
-
-int rt_mesh_vertex_normals(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_vertex_normals: no mesh (rt_mesh_upload first)");
-    if (!rtl::mesh_vertex_normals(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_vertex_normals: normals are not enabled (rt_mesh_normals_enable first)");
-    *devPtr = const_cast<float4 *>(rtl::mesh_vertex_normals(c->mesh));
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 16;
-    return RT_OK;
-}
-
-static int hit_normals_args(RtContext *c, const char *who, const RtHit *hits, int n, const float *normals) {
-    if (n < 0 || (n > 0 && !hits) || !normals) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits and normals are needed)", who, n);
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
-    if (!rtl::mesh_normal_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: normals are not enabled (rt_mesh_normals_enable first)", who);
-    return RT_OK;
-}
-
-int rt_mesh_hit_normals(RtContext *c, const RtHit *hits, int n, float *normals) {
-    if (!c) return RT_ERR_INVALID;
-    int rc = hit_normals_args(c, "rt_mesh_hit_normals", hits, n, normals);
-    if (rc != RT_OK) return rc;
-    if (((uintptr_t)hits & 15u) || ((uintptr_t)normals & 3u)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_normals: hits must be 16-byte aligned, normals 4-byte aligned");
-    if (n == 0) return RT_OK;
-    (void)hipSetDevice(c->cfg.device);
-    const char *err = nullptr;
-    rc = rtl::mesh_hit_normals(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, n, normals, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_normals: %s", err ? err : "launch failed");
-    return RT_OK;
-}
-
-int rt_mesh_hit_normals_host(RtContext *c, const RtHit *hits, int n, float *normals) {
-    if (!c) return RT_ERR_INVALID;
-    const int ar = hit_normals_args(c, "rt_mesh_hit_normals_host", hits, n, normals);
-    if (ar != RT_OK) return ar;
-    if (n == 0) return RT_OK;
-    return guarded(c, "rt_mesh_hit_normals_host", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    const size_t N = (size_t)n, hB = N * sizeof(RtHit), total = hB + N * 12;   // hits | normals
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
-    const int qr = rt_mesh_hit_normals(c, (const RtHit *)base, n, (float *)(base + hB));
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    HIP_TRY(c, hipMemcpyAsync(normals, base + hB, N * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
-    });
-}
-
-// ---- per-vertex colours: rt_mesh.hip gathers the rows inside every update; this file owns enabling, the ordering of colour writes and
-// of the gather alone, and the hit query
-int rt_mesh_colors_enable(RtContext *c, int on) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-    if (!on) { rtl::mesh_colors_release(c->mesh); return RT_OK; }
-    if (rtl::mesh_vertex_colors(c->mesh)) return RT_OK;   // already enabled: the colours and the rows stay as they are, nothing is allocated
-    const bool orderWas = rtl::mesh_order_written(c->mesh);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    const char *err = nullptr;
-    const int rc = rtl::mesh_colors_create(c->mesh, st, &err);
-    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_colors_enable: %s", err ? err : "allocation failed");
-    return RT_OK;
-}
-
-int rt_mesh_colors(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: no mesh (rt_mesh_upload first)");
-    if (!rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: colours are not enabled (rt_mesh_colors_enable first)");
-    *devPtr = rtl::mesh_vertex_colors(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 16;
-    return RT_OK;
-}
-
-int rt_mesh_set_colors(RtContext *c, const float *rgb3, int first, int count) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh || !rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: no colours (rt_mesh_upload and rt_mesh_colors_enable first)");
-    const int n = rtl::mesh_verts(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: vertices %d .. %d of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!rgb3) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: null colours");
-    for (size_t i = 0; i < (size_t)count * 3; ++i)
-        if (!(rgb3[i] >= 0.0f) || !(rgb3[i] < INFINITY)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: component %zu of vertex %zu is %g (finite and >= 0 is needed)", i % 3, (size_t)first + i / 3, (double)rgb3[i]);
-    return guarded(c, "rt_mesh_set_colors", [&]() -> int {
-        (void)hipSetDevice(c->cfg.device);
-        hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-        // (r, g, b, 0) per vertex as the device holds them, in a buffer of the call's own.  It may go when the call returns only because the HIP runtime
-        // finishes with pageable host memory -- stages it, or completes the copy -- before hipMemcpyAsync returns; rt_mesh_set_bones leans on the same
-        // for the caller's array.  So the call is ordered on the stream like rt_mesh_set_bones, and like it may spend the copy's time on the host.
-        std::vector<float> v4((size_t)count * 4);
-        for (size_t i = 0; i < (size_t)count; ++i) { v4[4 * i] = rgb3[3 * i]; v4[4 * i + 1] = rgb3[3 * i + 1]; v4[4 * i + 2] = rgb3[3 * i + 2]; v4[4 * i + 3] = 0.0f; }
-        int rc = mesh_after_lanes(c, st);   // a gather enqueued on another lane reads the colours
-        if (rc != RT_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(rtl::mesh_vertex_colors(c->mesh) + (size_t)first, v4.data(), (size_t)count * 16, hipMemcpyHostToDevice, st));
-        return mesh_before_lanes(c, st);
-    });
-}
-
-int rt_mesh_colors_refresh(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_color_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: colours are not enabled (rt_mesh_colors_enable first)");
-    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no rows to fill (rt_mesh_rebuild first)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    int rc = mesh_after_lanes(c, st);   // frames and queries on every lane read the rows they were enqueued with ...
-    if (rc != RT_OK) return rc;
-    const char *err = nullptr;
-    const bool orderWas = rtl::mesh_order_written(c->mesh);
-    rc = rtl::mesh_colors_refresh(c->mesh, st, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_colors_refresh: %s", err ? err : "launch failed");
-    if (!orderWas && rtl::mesh_order_written(c->mesh)) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
-    return mesh_before_lanes(c, st);    // ... and whatever a lane is given next sees the new ones
-}
-
-static int hit_colors_args(RtContext *c, const char *who, const RtHit *hits, int n, const float *colors) {
-    if (n < 0 || (n > 0 && !hits) || !colors) return fail(c, RT_ERR_INVALID, "%s: bad arguments (n = %d; hits and colors are needed)", who, n);
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no tree (rt_mesh_upload and rt_mesh_rebuild first)", who);
-    if (!rtl::mesh_color_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: colours are not enabled (rt_mesh_colors_enable first)", who);
-    return RT_OK;
-}
-
-int rt_mesh_hit_colors(RtContext *c, const RtHit *hits, int n, float *colors) {
-    if (!c) return RT_ERR_INVALID;
-    int rc = hit_colors_args(c, "rt_mesh_hit_colors", hits, n, colors);
-    if (rc != RT_OK) return rc;
-    if (((uintptr_t)hits & 15u) || ((uintptr_t)colors & 3u)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_colors: hits must be 16-byte aligned, colors 4-byte aligned");
-    if (n == 0) return RT_OK;
-    (void)hipSetDevice(c->cfg.device);
-    const char *err = nullptr;
-    rc = rtl::mesh_hit_colors(c->mesh, c->lastStream ? c->lastStream : c->stream, hits, n, colors, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_colors: %s", err ? err : "launch failed");
-    return RT_OK;
-}
-
-int rt_mesh_hit_colors_host(RtContext *c, const RtHit *hits, int n, float *colors) {
-    if (!c) return RT_ERR_INVALID;
-    const int ar = hit_colors_args(c, "rt_mesh_hit_colors_host", hits, n, colors);
-    if (ar != RT_OK) return ar;
-    if (n == 0) return RT_OK;
-    return guarded(c, "rt_mesh_hit_colors_host", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    const size_t N = (size_t)n, hB = N * sizeof(RtHit), total = hB + N * 12;   // hits | colors
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
-    const int qr = rt_mesh_hit_colors(c, (const RtHit *)base, n, (float *)(base + hB));
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    HIP_TRY(c, hipMemcpyAsync(colors, base + hB, N * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
-    });
-}
-
-// ---- skinning: rt_mesh_skin.hip rewrites the positions; this file validates the tables and orders the writes against every lane
-int rt_mesh_skin_upload(RtContext *c, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    if (nBones == 0) {
-        HIP_TRY(c, sync_all(c));
-        rtl::mesh_skin_release(c->mesh);
-        return RT_OK;
-    }
-    if (nBones < 1 || nBones > RT_MAX_MESH_BONES) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: %d bones (1 .. %d)", nBones, RT_MAX_MESH_BONES);
-    if (!boneIdx4 || !weights4) return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: null %s", !boneIdx4 ? "boneIdx4" : "weights4");
-    const size_t n = (size_t)rtl::mesh_verts(c->mesh) * RT_SKIN_INFLUENCES;
-    for (size_t k = 0; k < n; ++k) {
-        if ((int)boneIdx4[k] >= nBones)
-            return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: influence %zu of vertex %zu names bone %u of %d", k % RT_SKIN_INFLUENCES, k / RT_SKIN_INFLUENCES, (unsigned)boneIdx4[k], nBones);
-        if (!std::isfinite(weights4[k]))
-            return fail(c, RT_ERR_INVALID, "rt_mesh_skin_upload: weight %zu of vertex %zu is not finite", k % RT_SKIN_INFLUENCES, k / RT_SKIN_INFLUENCES);
-    }
-    return guarded(c, "rt_mesh_skin_upload", [&]() -> int {
-        HIP_TRY(c, sync_all(c));   // a skin in flight reads the arrays that are replaced; the snapshot reads the positions as they stand
-        const char *err = nullptr;
-        const int rc = rtl::mesh_skin_create(c->mesh, rest, boneIdx4, weights4, nBones, &err);
-        return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_skin_upload: %s", err ? err : "allocation failed");
-    });
-}
-
-int rt_mesh_bones(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_bones: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
-    *devPtr = rtl::mesh_bones(c->mesh);
-    *bytes = (size_t)rtl::mesh_bone_count(c->mesh) * 64;
-    return RT_OK;
-}
-
-int rt_mesh_rest_positions(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_rest_positions: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
-    *devPtr = rtl::mesh_rest_positions(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
-    return RT_OK;
-}
-
-int rt_mesh_set_bones(RtContext *c, int first, int count, const float *M16s) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh || !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: no skin (rt_mesh_upload and rt_mesh_skin_upload first)");
-    const int n = rtl::mesh_bone_count(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: entries %d .. %d of a table of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!M16s) return fail(c, RT_ERR_INVALID, "rt_mesh_set_bones: null matrices");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    int rc = mesh_after_lanes(c, st);   // a skin enqueued on another lane reads the table
-    if (rc != RT_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_bones(c->mesh) + (size_t)first * 16, M16s, (size_t)count * 64, hipMemcpyHostToDevice, st));
-    return mesh_before_lanes(c, st);
-}
-
-int rt_mesh_skin(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_skin: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_skin: no skin (rt_mesh_skin_upload first; rt_mesh_upload releases the skin)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    // a position write: gathers, bone and rest writes and bound raster draws already enqueued on any lane come first ...
-    int rc = mesh_after_lanes(c, st);
-    if (rc != RT_OK) return rc;
-    if (c->raster && rt_raster_order_after(c->raster, st) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_skin: %s", rt_raster_error(c->raster));
-    const char *err = nullptr;
-    rc = rtl::mesh_skin(c->mesh, st, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_skin: %s", err ? err : "launch failed");
-    return mesh_before_lanes(c, st);   // ... and updates, draws and table writes a lane is given next see the new positions
-}
-
-// ---- morph targets: rt_morph_pack.cpp checks and packs the targets, rt_mesh_morph.hip blends them; this file orders the writes
-int rt_mesh_morph_upload(RtContext *c, const float *base, const int32_t *targetFirst, const uint32_t *vertIdx, const float *deltas, int nTargets) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_upload: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    if (nTargets == 0) {
-        HIP_TRY(c, sync_all(c));
-        rtl::mesh_morph_release(c->mesh);
-        return RT_OK;
-    }
-    return guarded(c, "rt_mesh_morph_upload", [&]() -> int {
-        const int nVerts = rtl::mesh_verts(c->mesh);
-        std::string msg;
-        int rc = rtl::morph_validate(nVerts, targetFirst, vertIdx, deltas, nTargets, msg);
-        if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph_upload: %s", msg.c_str());
-        rtl::MorphPlan plan;
-        rc = rtl::morph_plan(nVerts, targetFirst, vertIdx, nTargets, plan, msg);
-        if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph_upload: %s", msg.c_str());
-        std::vector<rtl::MorphRecord> records;
-        rtl::morph_fill(plan, targetFirst, vertIdx, deltas, records);
-        HIP_TRY(c, sync_all(c));   // a morph in flight reads the arrays that are replaced; the snapshot reads its source as it stands
-        const char *err = nullptr;
-        rc = rtl::mesh_morph_create(c->mesh, base, plan.sliceFirst.data(), records.data(), plan.info, &err);
-        return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_morph_upload: %s", err ? err : "allocation failed");
-    });
-}
-
-int rt_mesh_morph_base(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_base: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
-    *devPtr = rtl::mesh_morph_base(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 12;
-    return RT_OK;
-}
-
-int rt_mesh_morph_weights(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_weights: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
-    *devPtr = rtl::mesh_morph_weights(c->mesh);
-    *bytes = (size_t)rtl::mesh_morph_target_count(c->mesh) * 4;
-    return RT_OK;
-}
-
-int rt_mesh_set_morph_weights(RtContext *c, int first, int count, const float *weights) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
-    const int n = rtl::mesh_morph_target_count(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: entries %d .. %d of a table of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!weights) return fail(c, RT_ERR_INVALID, "rt_mesh_set_morph_weights: null weights");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    int rc = mesh_after_lanes(c, st);   // a morph enqueued on another lane reads the table
-    if (rc != RT_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rtl::mesh_morph_weights(c->mesh) + first, weights, (size_t)count * 4, hipMemcpyHostToDevice, st));
-    return mesh_before_lanes(c, st);
-}
-
-int rt_mesh_morph(RtContext *c, int dst) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no morph (rt_mesh_morph_upload first; rt_mesh_upload releases the morph)");
-    if (dst != RT_MORPH_TO_POSITIONS && dst != RT_MORPH_TO_REST) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: destination %d", dst);
-    if (dst == RT_MORPH_TO_REST && !rtl::mesh_bone_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph: no rest array to write (rt_mesh_skin_upload first)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    // gathers, skins, weight and base writes already enqueued on any lane come first, and for a position write the bound raster draws as well ...
-    int rc = mesh_after_lanes(c, st);
-    if (rc != RT_OK) return rc;
-    if (dst == RT_MORPH_TO_POSITIONS && c->raster && rt_raster_order_after(c->raster, st) != RT_OK) return fail(c, RT_ERR_HIP, "rt_mesh_morph: %s", rt_raster_error(c->raster));
-    const char *err = nullptr;
-    rc = rtl::mesh_morph(c->mesh, st, dst == RT_MORPH_TO_REST, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_morph: %s", err ? err : "launch failed");
-    return mesh_before_lanes(c, st);   // ... and skins, updates, draws and table writes a lane is given next see what was written
-}
-
-int rt_mesh_morph_info(RtContext *c, RtMorphInfo *out) {
-    if (!c || !out) return RT_ERR_INVALID;
-    std::memset(out, 0, sizeof *out);
-    if (!c->mesh || !rtl::mesh_morph_target_count(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_morph_info: no morph (rt_mesh_upload and rt_mesh_morph_upload first)");
-    *out = rtl::mesh_morph_info(c->mesh);
-    return RT_OK;
-}
-
-// ---- tree quality
-static inline float key2f(uint32_t s) { const uint32_t u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s; float f; std::memcpy(&f, &u, 4); return f; }
-
-// Collects what has arrived, without waiting: an arrived slot's integers become a record (rt_bvh_cost's own expressions) and the slot is free again.
-static void mesh_quality_harvest(RtContext *c) {
-    const rtl::BvhLayout &L = rtl::mesh_layout(c->mesh);
-    for (int i = 0; i < rtl::kQualityRing; ++i) {
-        RtContext::MeshQSlot &sl = c->meshQSlot[i];
-        if (!sl.inFlight || hipEventQuery(rtl::mesh_quality_event(c->mesh, i)) != hipSuccess) continue;
-        sl.inFlight = false;
-        const rtl::QualityRecord r = *rtl::mesh_quality_record(c->mesh, i);
-        RtMeshQuality q = {};
-        RtBvhCost &k = q.cost;
-        k.nInner = L.nInner; k.nLeaves = (int32_t)L.nLeaves;
-        const double A = rtcost::half_area(key2f(r.rootKeys[3]) - key2f(r.rootKeys[0]), key2f(r.rootKeys[4]) - key2f(r.rootKeys[1]), key2f(r.rootKeys[5]) - key2f(r.rootKeys[2]));
-        k.rootArea = A;
-        if (A == 0.0) k.degenerate = 1;
-        else {
-            k.rootExp = rtcost::root_exp(A);
-            k.innerQ = r.innerQ; k.leafQ = r.leafQ;
-            k.inner = rtcost::from_sum(k.innerQ, k.rootExp, A);
-            k.leaf = rtcost::from_sum(k.leafQ, k.rootExp, A);
-            k.cost = k.inner + k.leaf;
-        }
-        q.update = sl.update; q.refitsSinceRebuild = sl.refits;
-        if (!c->meshQHaveLatest || q.update >= c->meshQLatest.update) { c->meshQLatest = q; c->meshQLatestTree = sl.tree; c->meshQHaveLatest = true; }
-        if (sl.refits == 0 && (!c->meshQHaveBaseline || sl.tree >= c->meshQBaselineTree)) { c->meshQBaseline = q; c->meshQBaselineTree = sl.tree; c->meshQHaveBaseline = true; }
-    }
-}
-
-static int mesh_measure(RtContext *c, const char *who) {
-    (void)hipSetDevice(c->cfg.device);
-    mesh_quality_harvest(c);
-    int slot = -1;
-    for (int i = 0; i < rtl::kQualityRing && slot < 0; ++i) if (!c->meshQSlot[i].inFlight) slot = i;
-    if (slot < 0) { ++c->meshQSkipped; return RT_OK; }
-    const char *err = nullptr;
-    const int rc = rtl::mesh_measure(c->mesh, c->lastStream ? c->lastStream : c->stream, slot, &err);
-    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
-    RtContext::MeshQSlot &sl = c->meshQSlot[slot];
-    sl.inFlight = true; sl.update = c->meshRebuilds + c->meshRefits; sl.tree = c->meshRebuilds; sl.refits = (int32_t)c->meshRefitsSinceRebuild;
-    c->meshQNewest = slot;
-    ++c->meshQEnqueued;
-    return RT_OK;
-}
-
-int rt_mesh_measure(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_measure: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_measure: no tree to measure (rt_mesh_rebuild first)");
-    return mesh_measure(c, "rt_mesh_measure");
-}
-
-int rt_mesh_quality(RtContext *c, int which, int wait, RtMeshQuality *out) {
-    if (!c || !out) return RT_ERR_INVALID;
-    std::memset(out, 0, sizeof *out);
-    if (which != RT_MESH_QUALITY_LATEST && which != RT_MESH_QUALITY_BASELINE) return fail(c, RT_ERR_INVALID, "rt_mesh_quality: which = %d", which);
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_quality: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    if (wait && c->meshQNewest >= 0 && c->meshQSlot[c->meshQNewest].inFlight) HIP_TRY(c, hipEventSynchronize(rtl::mesh_quality_event(c->mesh, c->meshQNewest)));
-    mesh_quality_harvest(c);
-    if (which == RT_MESH_QUALITY_LATEST) {
-        if (!c->meshQHaveLatest) return fail(c, RT_ERR_STATE, "rt_mesh_quality: no measurement has arrived yet");
-        *out = c->meshQLatest;
-    } else {
-        if (!c->meshQHaveBaseline || c->meshQBaselineTree != c->meshRebuilds)
-            return fail(c, RT_ERR_STATE, "rt_mesh_quality: no measurement of the current tree as its rebuild left it has arrived");
-        *out = c->meshQBaseline;
-    }
-    out->skipped = (int32_t)c->meshQSkipped;
-    return RT_OK;
-}
-
-int rt_mesh_update(RtContext *c, int mode, const float *M16, float rebuildAbove, int *action) {
-    if (!c) return RT_ERR_INVALID;
-    if (mode != RT_MESH_UPDATE_SINGLE && mode != RT_MESH_UPDATE_PARTS) return fail(c, RT_ERR_INVALID, "rt_mesh_update: mode = %d", mode);
-    if (mode == RT_MESH_UPDATE_PARTS && M16) return fail(c, RT_ERR_INVALID, "rt_mesh_update: RT_MESH_UPDATE_PARTS gathers under the matrix table, M16 must be NULL");
-    if (!(rebuildAbove >= 1.0f)) return fail(c, RT_ERR_INVALID, "rt_mesh_update: rebuildAbove = %g (a ratio of costs, at least 1)", (double)rebuildAbove);
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_update: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    bool rebuild = true;
-    if (rtl::mesh_has_tree(c->mesh)) {
-        mesh_quality_harvest(c);
-        const bool haveBase = c->meshQHaveBaseline && c->meshQBaselineTree == c->meshRebuilds;
-        bool baseInFlight = false;
-        for (const auto &sl : c->meshQSlot) baseInFlight = baseInFlight || (sl.inFlight && sl.tree == c->meshRebuilds && sl.refits == 0);
-        if (haveBase) {
-            // a record of the current tree is at least as new as its baseline; one of an older tree cannot be newer
-            const RtMeshQuality &latest = (c->meshQHaveLatest && c->meshQLatestTree == c->meshRebuilds) ? c->meshQLatest : c->meshQBaseline;
-            if (c->meshQBaseline.cost.degenerate || latest.cost.degenerate) rebuild = false;
-            else rebuild = latest.cost.cost > (double)rebuildAbove * c->meshQBaseline.cost.cost;
-        } else rebuild = !baseInFlight;
-    }
-    const int rc = mesh_update(c, M16, !rebuild, mode == RT_MESH_UPDATE_PARTS, "rt_mesh_update");
-    if (rc != RT_OK) return rc;
-    if (action) *action = rebuild ? RT_MESH_DID_REBUILD : RT_MESH_DID_REFIT;
-    return mesh_measure(c, "rt_mesh_update");
-}
-
-int rt_mesh_refit_count(RtContext *c, uint64_t *total, uint64_t *sinceRebuild) {
-    if (!c || (!total && !sinceRebuild)) return RT_ERR_INVALID;
-    if (total) *total = c->mesh ? c->meshRefits : 0;
-    if (sinceRebuild) *sinceRebuild = c->mesh ? c->meshRefitsSinceRebuild : 0;
-    return RT_OK;
-}
-
-// The order array of the current tree, readable on `st`: derived there at the first call after a rebuild; a later reader on another stream (frames rotate
-// rt_stream() through the lanes) waits for that launch by an event.
-static int mesh_order_on(RtContext *c, hipStream_t st, const char *who, const int **order) {
-    const char *err = nullptr;
-    const bool written = rtl::mesh_order_written(c->mesh);
-    const int rc = rtl::mesh_order(c->mesh, st, order, &err);
-    if (rc != RT_OK) return fail(c, rc, "%s: %s", who, err ? err : "launch failed");
-    if (!written) { HIP_TRY(c, hipEventRecord(c->evMeshOrder, st)); c->meshOrderStream = st; }
-    else if (c->meshOrderStream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshOrder, 0));
-    return RT_OK;
-}
-
-int rt_mesh_order_device(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_order: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
-    (void)hipSetDevice(c->cfg.device);
-    const int *order = nullptr;
-    const int rc = mesh_order_on(c, c->lastStream ? c->lastStream : c->stream, "rt_mesh_order", &order);
-    if (rc != RT_OK) return rc;
-    *devPtr = const_cast<int *>(order);
-    *bytes = (size_t)rtl::mesh_layout(c->mesh).nTris * 4;
-    return RT_OK;
-}
-
-int rt_mesh_hit_parts(RtContext *c, const RtHit *hits, int n, int32_t *parts, int32_t *tris) {
-    if (!c) return RT_ERR_INVALID;
-    if (n < 0 || (n > 0 && !hits) || (!parts && !tris)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: bad arguments (n = %d; hits and one of parts / tris are needed)", n);
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
-    if (((uintptr_t)hits | (uintptr_t)parts | (uintptr_t)tris) & 3u) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts: arrays must be 4-byte aligned");
-    if (n == 0) return RT_OK;
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
-    const int *order = nullptr;
-    int rc = mesh_order_on(c, st, "rt_mesh_hit_parts", &order);
-    if (rc != RT_OK) return rc;
-    const char *err = nullptr;
-    rc = rtl::mesh_hit_parts(c->mesh, st, order, hits, n, parts, tris, &err);
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_hit_parts: %s", err ? err : "launch failed");
-    return RT_OK;
-}
-
-int rt_mesh_hit_parts_host(RtContext *c, const RtHit *hits, int n, int32_t *parts, int32_t *tris) {
-    if (!c) return RT_ERR_INVALID;
-    if (n < 0 || (n > 0 && !hits) || (!parts && !tris)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts_host: bad arguments (n = %d; hits and one of parts / tris are needed)", n);
-    if (!c->mesh || !rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_hit_parts_host: no tree (rt_mesh_upload and rt_mesh_rebuild first)");
-    if (n == 0) return RT_OK;
-    return guarded(c, "rt_mesh_hit_parts_host", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    const size_t N = (size_t)n, hB = N * sizeof(RtHit), offP = hB, offT = offP + (N * 4 + 15) / 16 * 16, total = offT + N * 4;   // hits | parts | tris
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, hits, hB, hipMemcpyHostToDevice, st));
-    const int qr = rt_mesh_hit_parts(c, (const RtHit *)base, n, (int32_t *)(base + offP), (int32_t *)(base + offT));
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    if (parts) HIP_TRY(c, hipMemcpyAsync(parts, base + offP, N * 4, hipMemcpyDeviceToHost, st));
-    if (tris) HIP_TRY(c, hipMemcpyAsync(tris, base + offT, N * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
-    });
-}
-
-int rt_mesh_order(RtContext *c, int32_t *order) {
-    if (!c || !order) return RT_ERR_INVALID;
-    void *d = nullptr;
-    size_t bytes = 0;
-    const int rc = rt_mesh_order_device(c, &d, &bytes);
-    if (rc != RT_OK) return rc;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(order, d, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
-}
-
-int rt_get_mesh_info(RtContext *c, RtMeshInfo *out) {
-    if (!c || !out) return RT_ERR_INVALID;
-    std::memset(out, 0, sizeof *out);
-    if (!c->mesh) return RT_OK;
-    out->nVerts = rtl::mesh_verts(c->mesh); out->nTris = rtl::mesh_layout(c->mesh).nTris;
-    out->rebuilds = c->meshRebuilds; out->allocations = rtl::mesh_allocations(c->mesh); out->hostSyncs = c->meshHostSyncs;
-    out->scratchBytes = rtl::mesh_scratch_bytes(c->mesh); out->sceneBytes = rtl::mesh_scene_bytes(c->mesh);
-    return RT_OK;
 }
 
 int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, size_t *bytes) {
@@ -1937,7 +917,7 @@ int rt_assemble_gathered(RtContext *c, int which, const void *gatheredDev, void 
     (void)hipSetDevice(c->cfg.device);
     const int ch = (which == RT_TARGET_MOTION) ? 2 : 4;
     const size_t n = (size_t)c->g.W * c->g.H;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // behind the gather the caller enqueued on rt_stream()
+    hipStream_t st = api_stream(c);   // behind the gather the caller enqueued on rt_stream()
     rt_stage_begin(c, 10, st);
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gatheredDev, dstDev, c->g, ch, c->nSlots * ch * 2);
     rt_stage_end(c, 10, 1, st);
@@ -1960,7 +940,7 @@ int rt_render_raster(RtContext *c, const RtRasterDraw *draws, int nDraws, const 
     if (c->g.world > 1) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_raster: tile-parallel contexts (worldSize %d) do not rasterise; use a single-rank context", c->g.world);
     (void)hipSetDevice(c->cfg.device);
     if (!c->raster) c->raster = rt_raster_create();
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    hipStream_t st = api_stream(c);   // rt_stream()
     // the dynamic mesh as it is now (a binding follows a later rt_mesh_upload): its arrays, and mesh_update's per-lane events for the other lanes.  Whoever
     // releases the mesh has waited for every lane, and this call runs on one, so no array is freed under it.
     RtRasterDynamic dyn = {};
@@ -2028,7 +1008,7 @@ int rt_get_raster_stats(RtContext *c, RtRasterStats *out) {
 
 int rt_stream(RtContext *c, void **s) {
     if (!c || !s) return RT_ERR_INVALID;
-    *s = (void *)(c->lastStream ? c->lastStream : c->stream);   // the stream the most recent frame was enqueued on
+    *s = (void *)api_stream(c);   // the stream the most recent frame was enqueued on
     return RT_OK;
 }
 
@@ -2237,7 +1217,7 @@ static int query_args(RtContext *c, const char *what, int kind, const float *ori
 // The query scratch (allocated on the first query) and rt_stream()'s stream, which first waits for the previous query if that ran on another stream
 static int query_begin(RtContext *c, hipStream_t &st) {
     (void)hipSetDevice(c->cfg.device);
-    st = c->lastStream ? c->lastStream : c->stream;   // rt_stream()
+    st = api_stream(c);   // rt_stream()
     if (!c->dQueryFrame) {
         HIP_TRY(c, hipMalloc(&c->dQueryFrame, sizeof(DevFrame)));
         HIP_TRY(c, hipMalloc(&c->dQueryHeads, rt_wave_head_words() * sizeof(uint32_t)));
@@ -2277,30 +1257,14 @@ int rt_trace_rays_host(RtContext *c, int kind, const float *origins, int originS
     if (!c) return RT_ERR_INVALID;
     const int rc = query_args(c, "rt_trace_rays_host", kind, origins, originStride, dirs, dirStride, tMax, n, hits, occluded);
     if (rc != RT_OK || n == 0) return rc;
-    return guarded(c, "rt_trace_rays_host", [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
-    // staging layout: origins | dirs | tMax | hits / occluded | normals, each 16-byte aligned; the ray arrays keep their strides
+    // staging layout: origins | dirs | tMax | hits / occluded | normals; the ray arrays keep their strides
+    const bool any = kind == RT_QUERY_ANY;
     const size_t N = (size_t)n;
-    const size_t oB = ((N - 1) * originStride + 3) * 4, dB = ((N - 1) * dirStride + 3) * 4, tB = tMax ? N * 4 : 0;
-    const size_t hB = kind == RT_QUERY_CLOSEST ? N * sizeof(RtHit) : N, nB = (kind == RT_QUERY_CLOSEST && normals) ? N * 12 : 0;
-    auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t offD = al(oB), offT = offD + al(dB), offH = offT + al(tB), offN = offH + al(hB), total = offN + al(nB);
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, origins, oB, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(base + offD, dirs, dB, hipMemcpyHostToDevice, st));
-    if (tMax) HIP_TRY(c, hipMemcpyAsync(base + offT, tMax, tB, hipMemcpyHostToDevice, st));
-    const int qr = rt_trace_rays(c, kind, (const float *)base, originStride, (const float *)(base + offD), dirStride, tMax ? (const float *)(base + offT) : nullptr,
-                                 eps, inf, n, kind == RT_QUERY_CLOSEST ? (RtHit *)(base + offH) : nullptr, nB ? (float *)(base + offN) : nullptr,
-                                 kind == RT_QUERY_ANY ? (uint8_t *)(base + offH) : nullptr);
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    HIP_TRY(c, hipMemcpyAsync(kind == RT_QUERY_CLOSEST ? (void *)hits : (void *)occluded, base + offH, hB, hipMemcpyDeviceToHost, st));
-    if (nB) HIP_TRY(c, hipMemcpyAsync(normals, base + offN, nB, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
+    const StageSeg segs[] = {{origins, ((N - 1) * originStride + 3) * 4, false}, {dirs, ((N - 1) * dirStride + 3) * 4, false}, {tMax, tMax ? N * 4 : 0, false},
+                             {any ? (void *)occluded : (void *)hits, any ? N : N * sizeof(RtHit), true}, {normals, (!any && normals) ? N * 12 : 0, true}};
+    return staged(c, "rt_trace_rays_host", segs, [&](void *const *d) {
+        return rt_trace_rays(c, kind, (const float *)d[0], originStride, (const float *)d[1], dirStride, (const float *)d[2], eps, inf, n,
+                             any ? nullptr : (RtHit *)d[3], (float *)d[4], any ? (uint8_t *)d[3] : nullptr);
     });
 }
 
@@ -2367,41 +1331,22 @@ int rt_pick_pixels(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, 
     return scene_query(c, "rt_pick_pixels", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals, points, nullptr);
 }
 
-// host arrays: staged through the context's buffer (inputs | outputs, each 16-byte aligned; the ray arrays keep their strides), then synchronised
+// host arrays: staged through the context's buffer (origins | dirs | xy | tMax | hits / occluded | objects | normals | points; the ray arrays keep their
+// strides), then synchronised
 static int scene_query_host(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs,
                             int dirStride, const int32_t *xy, const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
     bool mesh = false;
     const int rc = scene_query_args(c, what, u, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, mesh);
     if (rc != RT_OK || n == 0) return rc;
-    return guarded(c, what, [&]() -> int {
-    (void)hipSetDevice(c->cfg.device);
     const bool any = kind == RT_QUERY_ANY;
     const size_t N = (size_t)n;
-    const size_t oB = xy ? 0 : ((N - 1) * originStride + 3) * 4, dB = xy ? 0 : ((N - 1) * dirStride + 3) * 4, xB = xy ? N * 8 : 0, tB = tMax ? N * 4 : 0;
-    const size_t hB = any ? N : N * sizeof(RtHit), bB = (!any && objects) ? N * 4 : 0, nB = (!any && normals) ? N * 12 : 0, pB = (!any && points) ? N * 12 : 0;
-    auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t offD = al(oB), offX = offD + al(dB), offT = offX + al(xB), offH = offT + al(tB), offB = offH + al(hB), offN = offB + al(bB), offP = offN + al(nB),
-                 total = offP + al(pB);
-    HIP_TRY(c, sync_all(c));   // the staging buffer may be replaced below
-    const int sr = ensure_staging(c, total);
-    if (sr != RT_OK) return sr;
-    char *base = (char *)c->dStaging;
-    hipStream_t st = c->lastStream ? c->lastStream : c->stream;
-    if (oB) HIP_TRY(c, hipMemcpyAsync(base, origins, oB, hipMemcpyHostToDevice, st));
-    if (dB) HIP_TRY(c, hipMemcpyAsync(base + offD, dirs, dB, hipMemcpyHostToDevice, st));
-    if (xB) HIP_TRY(c, hipMemcpyAsync(base + offX, xy, xB, hipMemcpyHostToDevice, st));
-    if (tB) HIP_TRY(c, hipMemcpyAsync(base + offT, tMax, tB, hipMemcpyHostToDevice, st));
-    const int qr = scene_query(c, what, u, kind, flags, oB ? (const float *)base : nullptr, originStride, dB ? (const float *)(base + offD) : nullptr, dirStride,
-                               xB ? (const int32_t *)(base + offX) : nullptr, tB ? (const float *)(base + offT) : nullptr, n, any ? nullptr : (RtHit *)(base + offH),
-                               bB ? (int32_t *)(base + offB) : nullptr, nB ? (float *)(base + offN) : nullptr, pB ? (float *)(base + offP) : nullptr,
-                               any ? (uint8_t *)(base + offH) : nullptr);
-    if (qr != RT_OK) { (void)sync_all(c); return qr; }
-    HIP_TRY(c, hipMemcpyAsync(any ? (void *)occluded : (void *)hits, base + offH, hB, hipMemcpyDeviceToHost, st));
-    if (bB) HIP_TRY(c, hipMemcpyAsync(objects, base + offB, bB, hipMemcpyDeviceToHost, st));
-    if (nB) HIP_TRY(c, hipMemcpyAsync(normals, base + offN, nB, hipMemcpyDeviceToHost, st));
-    if (pB) HIP_TRY(c, hipMemcpyAsync(points, base + offP, pB, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return RT_OK;
+    const StageSeg segs[] = {{origins, xy ? 0 : ((N - 1) * originStride + 3) * 4, false}, {dirs, xy ? 0 : ((N - 1) * dirStride + 3) * 4, false},
+                             {xy, xy ? N * 8 : 0, false}, {tMax, tMax ? N * 4 : 0, false},
+                             {any ? (void *)occluded : (void *)hits, any ? N : N * sizeof(RtHit), true}, {objects, (!any && objects) ? N * 4 : 0, true},
+                             {normals, (!any && normals) ? N * 12 : 0, true}, {points, (!any && points) ? N * 12 : 0, true}};
+    return staged(c, what, segs, [&](void *const *d) {
+        return scene_query(c, what, u, kind, flags, (const float *)d[0], originStride, (const float *)d[1], dirStride, (const int32_t *)d[2], (const float *)d[3], n,
+                           any ? nullptr : (RtHit *)d[4], (int32_t *)d[5], (float *)d[6], (float *)d[7], any ? (uint8_t *)d[4] : nullptr);
     });
 }
 

@@ -13,7 +13,6 @@
 #include <cstring>
 #include <map>
 #include <new>
-#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -189,6 +188,15 @@ int bvh_layout(int nTris, BvhLayout &out) {
     return RT_OK;
 }
 
+// The device memory of one optional feature (skin, morph, motion, normals, colours): the blocks its create call allocated beyond `owned`, each with the
+// member that points at it, and their byte count.  attach / detach below are the only code that allocates, counts and frees them.
+struct Attachment {
+    struct Block { void *mem; void *member; void (*forget)(void *member); };
+    Block blocks[5] = {};
+    int n = 0;
+    size_t bytes = 0;
+};
+
 struct Mesh {
     BvhLayout lay;
     MeshScene sc;
@@ -219,28 +227,28 @@ struct Mesh {
     float *dRest = nullptr, *dSkinW = nullptr, *dBones = nullptr;
     uint16_t *dSkinIdx = nullptr;
     int nBones = 0;
-    size_t skinBytes = 0;
+    Attachment skin;
     // morph targets: base positions, the packed records with their slice table, one weight per target; allocated by
     // mesh_morph_create, not in `owned`
     float *dMorphBase = nullptr, *dMorphW = nullptr;
     uint32_t *dMorphSliceFirst = nullptr;
     void *dMorphEntries = nullptr;
     RtMorphInfo morph = {};   // nTargets == 0: no morph
-    size_t morphBytes = 0;
+    Attachment morphMem;
     // previous pose: the rows before the most recent update, in the current order, and the old rows by input triangle a rebuild
     // carries them across in; allocated by mesh_motion_create, not in `owned`
     float4 *dPrevTris = nullptr, *dPrevByInput = nullptr;
-    size_t motionBytes = 0;
+    Attachment motion;
     // smooth normals: the packed vertex -> triangle adjacency, the face vectors by input triangle, one normal per vertex and the
     // corner normals row for row beside the triangle array; allocated by mesh_normals_create, not in `owned`
     uint32_t *dNrmSliceFirst = nullptr;
     int32_t *dNrmEntries = nullptr;
     float4 *dFaceByInput = nullptr, *dVertNrm = nullptr, *dNrmRows = nullptr;
-    size_t normalBytes = 0;
+    Attachment normals;
     // per-vertex colours: one colour per vertex and the corner colours row for row beside the triangle array; allocated by
     // mesh_colors_create, not in `owned`
     float4 *dVertCol = nullptr, *dColRows = nullptr;
-    size_t colorBytes = 0;
+    Attachment colors;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -270,6 +278,28 @@ template <class T> hipError_t dev_upload(Mesh *m, T **p, const std::vector<T> &v
     hipError_t e = dev_alloc(m, p, v.size() * sizeof(T), false, false);
     if (e != hipSuccess || v.empty()) return e;
     return hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// One block of an attachment behind *p: at least 16 bytes, counted as one allocation and with the bytes asked for in scratchBytes; filled from host or
+// device memory (nothing to copy when bytes == 0) or with zeros (all of the block; also what a null source means).  Synchronous: the create calls end
+// with hipDeviceSynchronize.
+enum class Fill { host, device, zeros };
+template <class T> hipError_t attach(Mesh *m, Attachment &a, T **p, size_t bytes, Fill fill, const void *src = nullptr) {
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) return e;
+    a.blocks[a.n++] = {q, p, [](void *member) { *static_cast<T **>(member) = nullptr; }};
+    *p = static_cast<T *>(q);
+    ++m->allocations;
+    a.bytes += bytes; m->scratchBytes += bytes;
+    if (fill == Fill::zeros || !src) return hipMemset(q, 0, std::max<size_t>(bytes, 16));   // (no source: an empty table, its 16 bytes zero)
+    return bytes ? hipMemcpy(q, src, bytes, fill == Fill::host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) : hipSuccess;
+}
+// ... and all of them freed, their members null, their bytes out of scratchBytes (allocations counts what was ever allocated)
+void detach(Mesh *m, Attachment &a) {
+    for (int i = 0; i < a.n; ++i) { (void)hipFree(a.blocks[i].mem); a.blocks[i].forget(a.blocks[i].member); }
+    m->scratchBytes -= a.bytes;
+    a = Attachment{};
 }
 }  // namespace
 
@@ -584,10 +614,8 @@ hipEvent_t mesh_quality_event(const Mesh *m, int slot) { return m->evQ[slot]; }
 const QualityRecord *mesh_quality_record(const Mesh *m, int slot) { return reinterpret_cast<const QualityRecord *>(m->hQRec + (size_t)slot * kQualityRecordBytes); }
 
 void mesh_skin_release(Mesh *m) {
-    for (void *p : {(void *)m->dRest, (void *)m->dSkinIdx, (void *)m->dSkinW, (void *)m->dBones}) if (p) (void)hipFree(p);
-    m->dRest = m->dSkinW = m->dBones = nullptr; m->dSkinIdx = nullptr;
-    m->scratchBytes -= m->skinBytes;
-    m->skinBytes = 0; m->nBones = 0;
+    detach(m, m->skin);
+    m->nBones = 0;
 }
 
 int mesh_skin_create(Mesh *m, const float *rest, const uint16_t *boneIdx4, const float *weights4, int nBones, const char **err) {
@@ -596,19 +624,11 @@ int mesh_skin_create(Mesh *m, const float *rest, const uint16_t *boneIdx4, const
     std::vector<float> ident((size_t)nBones * 16, 0.0f);
     for (int b = 0; b < nBones; ++b)
         for (int k = 0; k < 4; ++k) ident[(size_t)b * 16 + 5 * k] = 1.0f;
-    auto make = [&](auto **p, const void *src, size_t bytes, hipMemcpyKind kind) -> hipError_t {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
-        ++m->allocations;
-        m->skinBytes += bytes; m->scratchBytes += bytes;
-        return hipMemcpy(q, src, bytes, kind);
-    };
-    hipError_t e = rest ? make(&m->dRest, rest, nv * 12, hipMemcpyHostToDevice) : make(&m->dRest, m->dPos, nv * 12, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = make(&m->dSkinIdx, boneIdx4, nv * RT_SKIN_INFLUENCES * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = make(&m->dSkinW, weights4, nv * RT_SKIN_INFLUENCES * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = make(&m->dBones, ident.data(), ident.size() * sizeof(float), hipMemcpyHostToDevice);
+    Attachment &a = m->skin;
+    hipError_t e = rest ? attach(m, a, &m->dRest, nv * 12, Fill::host, rest) : attach(m, a, &m->dRest, nv * 12, Fill::device, m->dPos);
+    if (e == hipSuccess) e = attach(m, a, &m->dSkinIdx, nv * RT_SKIN_INFLUENCES * sizeof(uint16_t), Fill::host, boneIdx4);
+    if (e == hipSuccess) e = attach(m, a, &m->dSkinW, nv * RT_SKIN_INFLUENCES * sizeof(float), Fill::host, weights4);
+    if (e == hipSuccess) e = attach(m, a, &m->dBones, ident.size() * sizeof(float), Fill::host, ident.data());
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_skin_release(m); return RT_ERR_HIP; }
     m->nBones = nBones;
@@ -627,30 +647,19 @@ int mesh_skin(Mesh *m, hipStream_t st, const char **err) {
 }
 
 void mesh_morph_release(Mesh *m) {
-    for (void *p : {(void *)m->dMorphBase, (void *)m->dMorphSliceFirst, m->dMorphEntries, (void *)m->dMorphW}) if (p) (void)hipFree(p);
-    m->dMorphBase = m->dMorphW = nullptr; m->dMorphSliceFirst = nullptr; m->dMorphEntries = nullptr;
-    m->scratchBytes -= m->morphBytes;
-    m->morphBytes = 0; m->morph = RtMorphInfo{};
+    detach(m, m->morphMem);
+    m->morph = RtMorphInfo{};
 }
 
 int mesh_morph_create(Mesh *m, const float *base, const uint32_t *sliceFirst, const void *records, const RtMorphInfo &info, const char **err) {
     mesh_morph_release(m);
     const size_t nv = (size_t)m->nVerts;
-    auto make = [&](auto **p, const void *src, size_t bytes, hipMemcpyKind kind) -> hipError_t {   // src == nullptr: zeros
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
-        ++m->allocations;
-        m->morphBytes += bytes; m->scratchBytes += bytes;
-        if (!src) return hipMemset(q, 0, std::max<size_t>(bytes, 16));
-        return bytes ? hipMemcpy(q, src, bytes, kind) : hipSuccess;
-    };
-    hipError_t e = base ? make(&m->dMorphBase, base, nv * 12, hipMemcpyHostToDevice)
-                        : make(&m->dMorphBase, m->nBones > 0 ? m->dRest : m->dPos, nv * 12, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = make(&m->dMorphSliceFirst, sliceFirst, ((size_t)info.nSlices + 1) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = make(&m->dMorphEntries, records, (size_t)info.paddedEntries * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = make(&m->dMorphW, nullptr, (size_t)info.nTargets * 4, hipMemcpyHostToDevice);
+    Attachment &a = m->morphMem;
+    hipError_t e = base ? attach(m, a, &m->dMorphBase, nv * 12, Fill::host, base)
+                        : attach(m, a, &m->dMorphBase, nv * 12, Fill::device, m->nBones > 0 ? m->dRest : m->dPos);
+    if (e == hipSuccess) e = attach(m, a, &m->dMorphSliceFirst, ((size_t)info.nSlices + 1) * 4, Fill::host, sliceFirst);
+    if (e == hipSuccess) e = attach(m, a, &m->dMorphEntries, (size_t)info.paddedEntries * 16, Fill::host, records);
+    if (e == hipSuccess) e = attach(m, a, &m->dMorphW, (size_t)info.nTargets * 4, Fill::zeros);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_morph_release(m); return RT_ERR_HIP; }
     m->morph = info;
@@ -669,27 +678,13 @@ int mesh_morph(Mesh *m, hipStream_t st, bool toRest, const char **err) {
     return RT_OK;
 }
 
-void mesh_motion_release(Mesh *m) {
-    for (void *p : {(void *)m->dPrevTris, (void *)m->dPrevByInput}) if (p) (void)hipFree(p);
-    m->dPrevTris = m->dPrevByInput = nullptr;
-    m->scratchBytes -= m->motionBytes;
-    m->motionBytes = 0;
-}
+void mesh_motion_release(Mesh *m) { detach(m, m->motion); }
 
 int mesh_motion_create(Mesh *m, const char **err) {
     mesh_motion_release(m);
     const size_t bytes = (size_t)m->lay.nTris * 48;
-    auto make = [&](float4 **p) -> hipError_t {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e != hipSuccess) return e;
-        *p = reinterpret_cast<float4 *>(q);
-        ++m->allocations;
-        m->motionBytes += bytes; m->scratchBytes += bytes;
-        return hipMemset(q, 0, bytes);
-    };
-    hipError_t e = make(&m->dPrevTris);
-    if (e == hipSuccess) e = make(&m->dPrevByInput);
+    hipError_t e = attach(m, m->motion, &m->dPrevTris, bytes, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, m->motion, &m->dPrevByInput, bytes, Fill::zeros);
     if (e == hipSuccess && m->permCur >= 0) e = hipMemcpy(m->dPrevTris, m->sc.tris, bytes, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_motion_release(m); return RT_ERR_HIP; }
@@ -711,31 +706,17 @@ int mesh_hit_prev_points(Mesh *m, hipStream_t st, const void *hits, const float 
     return RT_OK;
 }
 
-void mesh_normals_release(Mesh *m) {
-    for (void *p : {(void *)m->dNrmSliceFirst, (void *)m->dNrmEntries, (void *)m->dFaceByInput, (void *)m->dVertNrm, (void *)m->dNrmRows}) if (p) (void)hipFree(p);
-    m->dNrmSliceFirst = nullptr; m->dNrmEntries = nullptr; m->dFaceByInput = m->dVertNrm = m->dNrmRows = nullptr;
-    m->scratchBytes -= m->normalBytes;
-    m->normalBytes = 0;
-}
+void mesh_normals_release(Mesh *m) { detach(m, m->normals); }
 
 int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err) {
     mesh_normals_release(m);
     const size_t nt = (size_t)m->lay.nTris, nv = (size_t)m->nVerts;
-    auto make = [&](auto **p, const void *src, size_t bytes) -> hipError_t {   // src == nullptr: zeros
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
-        ++m->allocations;
-        m->normalBytes += bytes; m->scratchBytes += bytes;
-        if (!src) return hipMemset(q, 0, std::max<size_t>(bytes, 16));
-        return bytes ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    hipError_t e = make(&m->dNrmSliceFirst, sliceFirst, ((size_t)info.nSlices + 1) * 4);
-    if (e == hipSuccess) e = make(&m->dNrmEntries, entries, (size_t)info.paddedEntries * 4);
-    if (e == hipSuccess) e = make(&m->dFaceByInput, nullptr, nt * 16);
-    if (e == hipSuccess) e = make(&m->dVertNrm, nullptr, nv * 16);
-    if (e == hipSuccess) e = make(&m->dNrmRows, nullptr, nt * 48);
+    Attachment &a = m->normals;
+    hipError_t e = attach(m, a, &m->dNrmSliceFirst, ((size_t)info.nSlices + 1) * 4, Fill::host, sliceFirst);
+    if (e == hipSuccess) e = attach(m, a, &m->dNrmEntries, (size_t)info.paddedEntries * 4, Fill::host, entries);
+    if (e == hipSuccess) e = attach(m, a, &m->dFaceByInput, nt * 16, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, a, &m->dVertNrm, nv * 16, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, a, &m->dNrmRows, nt * 48, Fill::zeros);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_normals_release(m); return RT_ERR_HIP; }
     if (m->permCur >= 0) {
@@ -756,27 +737,12 @@ int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *no
     return RT_OK;
 }
 
-void mesh_colors_release(Mesh *m) {
-    for (void *p : {(void *)m->dVertCol, (void *)m->dColRows}) if (p) (void)hipFree(p);
-    m->dVertCol = m->dColRows = nullptr;
-    m->scratchBytes -= m->colorBytes;
-    m->colorBytes = 0;
-}
+void mesh_colors_release(Mesh *m) { detach(m, m->colors); }
 
 int mesh_colors_create(Mesh *m, hipStream_t st, const char **err) {
     mesh_colors_release(m);
-    const size_t nt = (size_t)m->lay.nTris, nv = (size_t)m->nVerts;
-    auto make = [&](float4 **p, size_t bytes) -> hipError_t {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        *p = static_cast<float4 *>(q);
-        ++m->allocations;
-        m->colorBytes += bytes; m->scratchBytes += bytes;
-        return hipMemset(q, 0, std::max<size_t>(bytes, 16));
-    };
-    hipError_t e = make(&m->dVertCol, nv * 16);
-    if (e == hipSuccess) e = make(&m->dColRows, nt * 48);
+    hipError_t e = attach(m, m->colors, &m->dVertCol, (size_t)m->nVerts * 16, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, m->colors, &m->dColRows, (size_t)m->lay.nTris * 48, Fill::zeros);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) { colors_launch_fill(st, m->dVertCol, m->nVerts); e = hipGetLastError(); }
     int rc = RT_OK;

@@ -1,0 +1,99 @@
+// rt_wave_buf.hpp -- the records every part of the wavefront pipeline shares: stage ids, the hit record, the frame's arrays (WaveBuf), the batched list append and
+// the cursor constants of the trace launches.
+// Part of the rt_wave.hip translation unit: included by it alone, behind its `#pragma clang fp contract(off)` and `using namespace rtd;`.
+#pragma once
+#include "rt_wave.hpp"
+
+// stage ids (rt_stage_name in rt_api.hip)
+enum { ST_PRIMARY = 1, ST_TRACE_PRIMARY, ST_POST_PRIMARY, ST_GEN_DIRECT, ST_TRACE_SHADOW, ST_TRACE_GI, ST_GEN_GI, ST_RESOLVE, ST_COMBINE, ST_TRACE_AO = 13 };
+
+struct HitRec { uint32_t slot; float t; int tri; };
+
+struct WaveBuf {
+    // per frame
+    uint32_t *cand;          // candidate pixel slots
+    uint32_t *counts;        // [0] candidates, [1] hits, [2..] traced-ray tallies
+    uint32_t *heads;         // ray cursors, one per trace launch
+    float *primT;            // per candidate
+    int *primTri;
+    HitRec *hits;
+    // per chunk of CH hits
+    // Shadow queue 1: (A + 4*SPP + 2) slots x CH.  Every slot has a direction record in shD.  The A AO slots are DENSE slots: the record is {dir, limit} -- limit =
+    // tMax, < 0 = no ray -- and the origin, one for all AO rays of the hit (computeAO_BVH), is aoOrg[j].  The light slots behind them keep an origin record and a
+    // tMax / liveness word of their own (hp + L*e differs from ray to ray): shO / shT, indexed by the slot's address LESS the A * CH dense ones.
+    float4 *shO, *shD;
+    float *shT, *sh2T;       // per-slot tMax (any-hit); < 0 = no ray in this slot (4 B instead of a 32-B record)
+    float4 *aoOrg;           // per hit: hp + N * aoBias, written once (AO ray 0)
+    uint8_t *occ1;
+    // Bounce queue: SPP dense slots x CH, record {dir, 1.0 = a ray was cast | < 0 = none}; the origin hp + N * eps (bounce_origin) belongs to the hit: giOrg[j],
+    // written once by sample 0 whether or not that sample casts.  (RT_BIN_GI permutes the records of a workgroup: there giOrg holds one origin per RECORD.)
+    float4 *giD, *giOrg;
+    float *giT;
+    int *giTri;
+    float4 *sh2O, *sh2D;     // shadow queue 2: 6 slots x q2Stride, entries compacted over the (hit, sample) pairs whose bounce hit
+    uint32_t q2Stride;       // entries per slot of queue 2: CH * SPP (every bounce ray may hit) for small launch sets; for large ones (round 5) a capacity PREDICTED from the bounce
+                             // hits of earlier batches -- a (hit, sample) pair whose entry lies beyond it is not queued: k_gen_gi_overflow traces its six rays in place
+    uint8_t *occOvf;         // answers of those rays, [6][CH * SPP] (per lane, like occ2)
+    uint8_t *occ2;
+    int *giPos;              // per (sample, hit): entry in queue 2, -1 when the bounce ray missed or was not cast
+    int *giPerm;             // RT_BIN_GI=1 (experiment, round 4): per (sample, hit) the bounce queue entry its ray was sorted to; null = entry (sample, hit) itself
+    uint32_t *giHit;         // RT_BOUNCE_PROBE: bounce queue addresses whose any-hit probe found a triangle (dense, CH * SPP entries at most; per lane, like giT)
+    // per frame, per pixel slot: everything the frame produced BEFORE the temporal resolve (the only history-dependent step)
+    float4 *pendC;           // curr.rgb (frame average, fp32), motion.x
+    float *pendMy;           // motion.y
+    uint2 *pendPos, *pendNrm;
+    uint32_t CH;             // chunk capacity (hits)
+    int A;                   // AO rays per hit (0 when AO is off)
+    int SPP;
+    // slot of shadow queue 1 for ray k of sample s: A AO slots, then the four disk-light rays of every sample, then ONE sun and ONE point-light
+    // slot per hit -- those two rays do not depend on the sample (rt_lighting.glsl:114-214), sample 0 traces them and the others reuse its answer,
+    // so samples > 0 own no slot for them (round 4: 22 instead of 28 slots per hit at 4 spp)
+    __device__ __forceinline__ uint32_t gi_entry(int s, uint32_t j) const { const uint32_t a = (uint32_t)s * CH + j; return giPerm ? (uint32_t)giPerm[a] : a; }
+    __device__ __forceinline__ uint32_t sh1_light(uint32_t a) const { return a - (uint32_t)A * CH; }   // address of a light slot -> entry of shO / shT
+    __device__ __forceinline__ uint32_t sh1_slot(int s, int k) const { return (uint32_t)(k < 4 ? A + s * 4 + k : A + 4 * SPP + (k - 4)); }
+};
+
+namespace {
+// block_append (rt_wave_stages.hpp) for kAppendBatch sub-blocks of 256 items handled by one workgroup: still ONE atomic, for 2048 items.  (With one
+// atomic per 256 items k_primary spent 0.10 ms of a 1080p frame queueing 8100 atomics on one word; now 0.025 ms.)
+//   note(k, pred) for every sub-block k, commit(counter), then index(k) -> position of this thread's item of sub-block k.
+// All 256 threads call every method, with the same k.
+constexpr int kAppendBatch = 8;
+struct BatchAppend {
+    uint32_t bits = 0;
+    uint32_t (*cnt)[4];
+    uint32_t *base;
+    RT_DEV void note(int k, bool pred) {
+        unsigned long long m = __ballot(pred);
+        if (pred) bits |= 1u << k;
+        if ((threadIdx.x & 63) == 0) cnt[k][threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    }
+    RT_DEV void commit(uint32_t *counter) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t tot = 0;
+            for (int k = 0; k < kAppendBatch; ++k) tot += cnt[k][0] + cnt[k][1] + cnt[k][2] + cnt[k][3];
+            *base = tot ? atomicAdd(counter, tot) : 0u;
+        }
+        __syncthreads();
+    }
+    RT_DEV bool mine(int k) const { return (bits >> k) & 1u; }
+    RT_DEV uint32_t index(int k) const {
+        const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        uint32_t off = *base;
+        for (int kk = 0; kk < k; ++kk) off += cnt[kk][0] + cnt[kk][1] + cnt[kk][2] + cnt[kk][3];
+        for (uint32_t i = 0; i < wv; ++i) off += cnt[k][i];
+        const unsigned long long m = __ballot(mine(k));
+        return off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    }
+};
+#define RT_BATCH_APPEND(name) __shared__ uint32_t name##_cnt[kAppendBatch][4]; __shared__ uint32_t name##_base; BatchAppend name; name.cnt = name##_cnt; name.base = &name##_base
+
+// The ray cursors of one trace launch (WaveBuf::heads, k_trace's scheduler): sharded, each shard on a line of its own.
+constexpr uint32_t kShards = 64, kShardStride = 32;   // cursor shards per trace launch, uint32 words between them (128 B)
+constexpr uint32_t kHeadWords = kShards * kShardStride;
+
+// live hits of the chunk starting at c0: |[c0, c0+CH) ∩ [0, hits)|, written without a wrapping subtraction (hipcc -O3 was
+// seen to drop the `h > c0 ? ... : 0` guard of the obvious form, turning empty chunks into full ones)
+RT_DEV uint32_t chunk_live(const WaveBuf &wb, uint32_t c0) { uint32_t h = wb.counts[1]; return min(h, c0 + wb.CH) - min(h, c0); }
+}  // namespace

@@ -820,7 +820,7 @@ int rt_mesh_hit_normals_host(RtContext *ctx, const RtHit *hits, int n, float *no
  * (below) defines at the hit's barycentrics (those of rt_pick_pixels' u, v): the primary hit's colour is the albedo of its direct light (diffuse term and
  * sky term) and the factor of its bounce; the bounce hit's colour is the albedo of the bounce hit's direct light -- a red wall tints the floor beside it.
  * specStrength 0.25 and gloss 32 stay constants.  No ray, no geometry, no normal, RT_TARGET_GPOS / GNRM / MOTION, resolveTAA and the miss rule change.
- * A mesh whose colours are all 0.85 renders bit for bit as with colours disabled.  Out of scope: per-vertex specular and gloss, textures and UVs,
+ * A mesh whose colours are all 0.85 renders bit for bit as with colours disabled.  Out of scope: per-vertex specular and gloss (textures and UVs: below),
  * colours in the hybrid scene (RT_SCENE_HYBRID), the analytic scene and the raster preview (which keeps its draw and part colours), colours read from
  * .obj files. */
 /* on != 0: waits for every lane, allocates the vertex colours (every vertex (0.85, 0.85, 0.85, 0)) and colRows (RtMeshInfo.allocations and scratchBytes
@@ -847,7 +847,54 @@ int rt_mesh_colors_refresh(RtContext *ctx);
  * staged through the context's buffer; synchronises. */
 int rt_mesh_hit_colors(RtContext *ctx, const RtHit *hits, int n, float *colors);
 int rt_mesh_hit_colors_host(RtContext *ctx, const RtHit *hits, int n, float *colors);
-/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload, rt_mesh_motion_enable, rt_mesh_normals_enable and rt_mesh_colors_enable); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
+/* ---- UVs and an albedo texture: EXTENSION, not in the reference.  With UVs enabled the mesh keeps, on the device, one UV per vertex
+ * (nVerts float2, zeros at first) and the three corner UVs of every row of the triangle array (uvRows: nTris rows of 32 bytes, (u0, v0, u1, v1),
+ * (u2, v2, 0, 0), row i beside row i of the triangle array, its corners those of input triangle rt_mesh_order's order[i]), exactly as rt_uv_rows (below)
+ * defines them.  A texture is W x H RGBA8 texels (1 <= W, H <= 16384), row 0 at v = 0 (GL upload order), alpha stored and ignored, decoded through a
+ * 256-entry table and sampled as rt_sample_texture (below) defines.  Off until asked for; while it is off every kernel's output is what it was.
+ *   Every update -- rt_mesh_rebuild, rt_mesh_refit, their _parts forms, rt_mesh_update in both modes -- gathers the UV rows again behind the colours'
+ * gather while UVs are enabled, inside its own ordered work on rt_stream()'s stream: no allocation, no host wait.  Writing UVs does not touch the rows:
+ * an update or rt_mesh_uvs_refresh does.
+ *   Frames: while the installed scene is the dynamic mesh's, UVs are enabled, a texture is present and u->useBVH == 1, the albedo of a mesh hit is
+ * base * texel per channel, one rounded product: base is what the hit's albedo was (rt_hit_colors' blend, or 0.85 with colours off), texel is
+ * rt_sample_texture at rt_hit_uvs' UV, both at the hit's barycentrics (those of rt_pick_pixels' u, v).  It applies where the colours apply: the primary
+ * hit's albedo and bounce factor, and the bounce hit's albedo.  A caller who wants the texture alone enables colours and sets them to 1.  specStrength
+ * and gloss stay constants; no ray, normal, RT_TARGET_GPOS / GNRM / MOTION or resolveTAA changes.  An all-255 texture renders bit for bit as no texture.
+ * Out of scope: mipmaps and ray differentials, more than one texture (parts share an atlas), alpha and cut-outs, normal / specular / gloss maps,
+ * textures in the hybrid scene, the analytic scene and the raster preview. */
+enum { RT_TEX_LINEAR = 0, RT_TEX_NEAREST = 1, RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 2, RT_TEX_UNORM = 0, RT_TEX_SRGB = 4 };
+#define RT_TEX_MAX_SIZE 16384
+/* on != 0: waits for every lane, allocates the vertex UVs (zeros) and uvRows (RtMeshInfo.allocations and scratchBytes count both) and, if the mesh has
+ * a tree, fills the rows at once.  on == 0 releases both.  May synchronise and allocate; the only call of the UV group that may.  on != 0 while UVs are
+ * enabled changes nothing.  RT_ERR_INVALID without a mesh; rt_mesh_upload, rt_mesh_upload_parts and rt_upload_bvh release them with the mesh. */
+int rt_mesh_uvs_enable(RtContext *ctx, int on);
+/* The device array of vertex UVs: nVerts x 2 floats.  The caller may write it on rt_stream()'s stream.  RT_ERR_INVALID (outputs cleared) without a
+ * mesh or without UVs enabled. */
+int rt_mesh_uvs(RtContext *ctx, void **devPtr, size_t *bytes);
+/* UVs first .. first + count - 1 from uv2 (2 floats per vertex, host memory, copied before the call returns), ordered like rt_mesh_set_colors.
+ * RT_ERR_INVALID without a mesh or UVs, for a range outside [0, nVerts], a null uv2 with count > 0, or a non-finite component (negative values are
+ * fine).  Does not touch the rows. */
+int rt_mesh_set_uvs(RtContext *ctx, const float *uv2, int first, int count);
+/* The row gather alone (k_uv_rows), ordered exactly as rt_mesh_colors_refresh: no allocation, no host wait.  RT_ERR_INVALID without a mesh, without
+ * UVs enabled, or before the first rebuild. */
+int rt_mesh_uvs_refresh(RtContext *ctx);
+/* The mesh's texture: rgba8 holds W x H texels of 4 bytes, row 0 at v = 0; flags: RT_TEX_* or'ed.  An attachment of its own (the texels and the 1 KB
+ * decode table; RtMeshInfo counts them): waits for every lane, may allocate; a second upload of the same size reuses the block.  rgba8 == NULL with
+ * W == H == 0 releases it.  RT_ERR_INVALID without a mesh, for a size outside 1 .. RT_TEX_MAX_SIZE, unknown flag bits or a null rgba8 with a size.
+ * Released with the mesh. */
+int rt_mesh_texture_upload(RtContext *ctx, const uint8_t *rgba8, int W, int H, int flags);
+/* The device texels (W * H * 4 bytes), so that a caller can write them on rt_stream()'s stream (video textures): frames and queries read the texels as
+ * they stand in stream order, no refresh call is needed.  RT_ERR_INVALID (outputs cleared) without a mesh or a texture. */
+int rt_mesh_texture(RtContext *ctx, void **devPtr, size_t *bytes, int *W, int *H);
+/* The UV of each hit (uvs: 2 floats per hit, rt_hit_uvs' out2 bit for bit under the device's uvRows) and the texture sample there (texels: 3 floats
+ * per hit, rt_sample_texture at that UV, not multiplied by the colour); zeros for a prim outside [0, nTris), nothing read out of bounds.  Pointers,
+ * alignment and ordering as rt_mesh_hit_colors.  RT_ERR_INVALID without a mesh, without UVs enabled, before the first rebuild, and for
+ * rt_mesh_hit_texels without a texture.  _host: host pointers, staged; synchronises. */
+int rt_mesh_hit_uvs(RtContext *ctx, const RtHit *hits, int n, float *uvs);
+int rt_mesh_hit_uvs_host(RtContext *ctx, const RtHit *hits, int n, float *uvs);
+int rt_mesh_hit_texels(RtContext *ctx, const RtHit *hits, int n, float *texels);
+int rt_mesh_hit_texels_host(RtContext *ctx, const RtHit *hits, int n, float *texels);
+/* allocations: device / pinned allocations made by the mesh path so far (all of them in rt_mesh_upload, rt_mesh_skin_upload, rt_mesh_morph_upload, rt_mesh_motion_enable, rt_mesh_normals_enable, rt_mesh_colors_enable, rt_mesh_uvs_enable and rt_mesh_texture_upload); hostSyncs: host waits made by rt_mesh_rebuild and rt_mesh_refit. */
 typedef struct RtMeshInfo { int32_t nVerts, nTris; uint64_t rebuilds, allocations, hostSyncs, scratchBytes, sceneBytes; } RtMeshInfo;
 int rt_get_mesh_info(RtContext *ctx, RtMeshInfo *out);
 /* Diagnostics: one device scene array, padding included, copied to the host (synchronises) -- for scenes installed by rt_upload_bvh or rt_mesh_rebuild
@@ -864,7 +911,9 @@ enum { RT_SCENE_ARRAY_TRIS = 0, RT_SCENE_ARRAY_PAIRS = 1, RT_SCENE_ARRAY_NODES2 
        /* the dynamic mesh's corner normals (rt_mesh_normals_enable): nTris rows of 48 bytes, no padding; size 0 while normals are not enabled */
        RT_SCENE_ARRAY_NORMAL_ROWS = 14,
        /* the dynamic mesh's corner colours (rt_mesh_colors_enable): nTris rows of 48 bytes, no padding; size 0 while colours are not enabled */
-       RT_SCENE_ARRAY_COLOR_ROWS = 15 };
+       RT_SCENE_ARRAY_COLOR_ROWS = 15,
+       /* the dynamic mesh's corner UVs (rt_mesh_uvs_enable): nTris rows of 32 bytes, no padding; size 0 while UVs are not enabled */
+       RT_SCENE_ARRAY_UV_ROWS = 16 };
 int rt_debug_read_scene(RtContext *ctx, int which, void *dst, size_t capacity, size_t *bytes);
 /* Diagnostics, host side (no GPU needed, no context): what rt_upload_bvh would put on the device for these arrays -- the packers of
  * csrc/rt_scene_pack.cpp run and one array handed out, with rt_debug_read_scene's `which` values and size-query convention.
@@ -1046,6 +1095,26 @@ int rt_hit_colors(const float *tris12, int nTris, const int32_t *order, const ui
                   float *out3);
 int rt_color_rows(const int32_t *order, const uint32_t *indices, const float *colors, int nTris, int nVerts, float *rows12);
 
+/* UVs and textures on host arrays, and the definitions the device's uvRows, rt_mesh_hit_uvs, rt_mesh_hit_texels and the frames' texel are tested
+ * against (order, indices as for rt_hit_colors; uvs: 2 floats per vertex).  fp32 in the device's float model: every product and sum rounded on its own.
+ *   rt_uv_rows: out gets nTris rows of 8 floats, (u0, v0, u1, v1), (u2, v2, 0, 0); row i holds the corner UVs of input triangle order[i].
+ *   rt_hit_uvs: per component rt_hit_colors' rule on the corner UVs: the first corner when a or b is not finite, the corner value bit for bit where the
+ * three are bit-equal, (c0 * ((1 - a) - b) + c1 * a) + c2 * b elsewhere.  A prim outside [0, nTris) gives zeros and reads nothing.  out2: 2 floats per hit.
+ *   rt_srgb_table: out[c] for texel code c, with x = c / 255.0: x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4), in double, rounded to float;
+ * out[0] == 0 and out[255] == 1 exactly.
+ *   rt_sample_texture: out3[i] = the decoded RGB of the texture at uv2[i].  The decode table is texel code c -> c / 255 (RT_TEX_UNORM) or rt_srgb_table's
+ * (RT_TEX_SRGB).  Per axis (u and W shown): a non-finite coordinate counts as 0; s = u - floorf(u) (REPEAT) or min(max(u, 0), 1) (CLAMP); LINEAR:
+ * x = s * W - 0.5f, fl = floorf(x), f = x - fl, i0 = (int)fl, i1 = i0 + 1; NEAREST: i = (int)floorf(s * W); indices wrapped ((i % W) + W) % W under
+ * REPEAT, clamped to [0, W - 1] under CLAMP.  NEAREST answers that texel; LINEAR per channel the decoded value bit for bit where the four decoded values
+ * are bit-equal, ((t00 * w00 + t10 * w10) + t01 * w01) + t11 * w11 elsewhere, w00 = (1 - a)(1 - b), w10 = a (1 - b), w01 = (1 - a) b, w11 = a b with
+ * (a, b) the two f.  Row 0 of the texels is v = 0.
+ * RT_ERR_INVALID: a null array, a negative count, nTris <= 0, nVerts <= 0, an order entry or index out of range, W or H outside 1 .. RT_TEX_MAX_SIZE,
+ * unknown flag bits.  None needs a GPU. */
+int rt_uv_rows(const int32_t *order, const uint32_t *indices, const float *uvs, int nTris, int nVerts, float *out);
+int rt_hit_uvs(const RtHit *hits, int n, const int32_t *order, const uint32_t *indices, const float *uvs, int nTris, int nVerts, float *out2);
+int rt_srgb_table(float *out256);
+int rt_sample_texture(const uint8_t *texels, int W, int H, int flags, const float *uv2, int n, float *out3);
+
 /* Morph-target blending on host arrays, and the definition rt_mesh_morph is tested against (see rt_mesh_morph_upload for the arrays; weights holds
  * nTargets floats).  For vertex v, acc = base[v]; the entries that name v are visited in input order (ascending target, then position within the
  * target); with w = weights[t], an entry whose w is +0 or -0 is skipped, otherwise per component acc = acc + w * d: fp32, a rounded product and a
@@ -1081,6 +1150,9 @@ int rt_bvh_cost(const float *nodes12, int nNodes, RtBvhCost *out);
 /* Stand-in for Model/Mesh + Assimp (include/scene/model.h:105-228) for plain .obj files: v / f records,
  * fan triangulation, negative indices.  Buffers are malloc'ed; release with rt_free. */
 int rt_load_obj(const char *path, float **positions, int *nVerts, uint32_t **indices, int *nIdx);
+/* rt_load_obj with texture coordinates: v, vt and f v/vt[/vn] records, the same fan triangulation and negative indices.  Vertex k is the k-th distinct
+ * (v, vt) pair in order of first use by the faces; a corner without vt gets (0, 0) and pairs as vt = none.  positions: 3 floats per vertex, uvs: 2. */
+int rt_load_obj_uv(const char *path, float **positions, float **uvs, int *nVerts, uint32_t **indices, int *nIdx);
 /* PNG decode (8-bit RGB / RGBA / grey, non-interlaced; zlib) standing in for stbi_load at cubemap.cpp:40 */
 int rt_load_png(const char *path, uint8_t **pixels, int *width, int *height, int *channels);
 /* 8-bit PNG writer (zlib), rows top-to-bottom as stored; flipY != 0 writes the last row first, i.e. turns a

@@ -201,7 +201,14 @@ RT_SCENE_ARRAY_PREV_TRIS = 13
 RT_SCENE_ARRAY_NORMAL_ROWS = 14
 # ... and its corner colours (rt_mesh_colors_enable): nTris rows of 48 bytes, empty while colours are not enabled
 RT_SCENE_ARRAY_COLOR_ROWS = 15
-SCENE_ARRAYS_MESH = {"prev tris": 13, "normal rows": 14, "color rows": 15}
+# ... and its corner UVs (rt_mesh_uvs_enable): nTris rows of 32 bytes, empty while UVs are not enabled
+RT_SCENE_ARRAY_UV_ROWS = 16
+# texture flags (rt_mesh_texture_upload, rt_sample_texture): filter | wrap | encoding
+TEX_LINEAR, TEX_NEAREST = 0, 1
+TEX_REPEAT, TEX_CLAMP = 0, 2
+TEX_UNORM, TEX_SRGB = 0, 4
+TEX_MAX_SIZE = 16384
+SCENE_ARRAYS_MESH = {"prev tris": 13, "normal rows": 14, "color rows": 15, "uv rows": 16}
 MESH_GREY = 0.85   # the albedo of a mesh hit without colours, and of every vertex when colours are enabled
 RT_SCENE_ARRAY_PACK_INFO = 100
 
@@ -387,6 +394,21 @@ SIGNATURES = {
     "rt_mesh_colors_refresh": (C.c_int, [C.c_void_p]),
     "rt_mesh_hit_colors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rt_mesh_hit_colors_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_uvs_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_mesh_uvs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_mesh_set_uvs": (C.c_int, [C.c_void_p, _FP, C.c_int, C.c_int]),
+    "rt_mesh_uvs_refresh": (C.c_int, [C.c_void_p]),
+    "rt_mesh_texture_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "rt_mesh_texture": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rt_mesh_hit_uvs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_uvs_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_texels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_mesh_hit_texels_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_uv_rows": (C.c_int, [C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, _FP]),
+    "rt_hit_uvs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, _FP]),
+    "rt_srgb_table": (C.c_int, [_FP]),
+    "rt_sample_texture": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _FP]),
+    "rt_load_obj_uv": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_hit_colors": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_void_p, C.c_int, _FP]),
     "rt_color_rows": (C.c_int, [C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, _FP]),
     "rt_hit_motion": (C.c_int, [C.c_void_p, _FP, _FP, C.c_int, C.c_void_p, _FP, C.c_int, _FP, _FP]),
@@ -856,6 +878,77 @@ def color_rows(order, indices, colors) -> np.ndarray:
     return out
 
 
+def _uv_mesh(who, order, indices, uvs):
+    """order / indices / uvs as contiguous int32 [T] / uint32 [3T] / float32 [V,2]; what a cast would hide is refused here."""
+    o, ix = np.asarray(order).reshape(-1), np.asarray(indices).reshape(-1)
+    if ix.size != 3 * o.size:
+        raise RtError(RT_ERR_INVALID, f"{who}: {o.size} order entries and {ix.size} indices")
+    if (o.size and (o.min() < -2 ** 31 or o.max() >= 2 ** 31)) or (ix.size and (ix.min() < 0 or ix.max() >= 2 ** 32)):
+        raise RtError(RT_ERR_INVALID, f"{who}: order must fit int32 and indices uint32")
+    uv = _f32(uvs)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise RtError(RT_ERR_INVALID, f"{who}: uvs must be [V,2], got {uv.shape}")
+    return np.ascontiguousarray(o, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.uint32), np.ascontiguousarray(uv)
+
+
+def uv_rows(order, indices, uvs) -> np.ndarray:
+    """The device row array of the vertex UVs on the host (rt_uv_rows), the definition Renderer.mesh_uv_rows is tested against -> float32 [T,8],
+    (u0, v0, u1, v1), (u2, v2, 0, 0) per row; row i holds the corner UVs of input triangle order[i]."""
+    o, ix, uv = _uv_mesh("uv_rows", order, indices, uvs)
+    out = np.zeros((o.size, 8), np.float32)
+    rc = lib().rt_uv_rows(o.ctypes.data_as(_I32P), ix.ctypes.data_as(_U32P), _fp(uv), o.size, uv.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_uv_rows: no triangles, no vertices, an index out of range or an order entry outside the triangles")
+    return out
+
+
+def hit_uvs(order, indices, uvs, hits) -> np.ndarray:
+    """UVs of hits on the dynamic mesh on the host (rt_hit_uvs), the definition Renderer.mesh_hit_uvs is tested against: order [T] row -> input
+    triangle (Renderer.mesh_order), indices the 3T indices of the input triangles, uvs [V,2], hits a RayHits / SceneHits or its [N,4] float32 record
+    array -> [N,2] float32; zeros for a prim outside the triangles."""
+    rec = np.ascontiguousarray(hits.record if isinstance(hits, RayHits) else hits)
+    if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
+        raise RtError(RT_ERR_INVALID, f"hit_uvs: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
+    o, ix, uv = _uv_mesh("hit_uvs", order, indices, uvs)
+    out = np.zeros((rec.shape[0], 2), np.float32)
+    rc = lib().rt_hit_uvs(C.c_void_p(rec.ctypes.data), rec.shape[0], o.ctypes.data_as(_I32P), ix.ctypes.data_as(_U32P), _fp(uv), o.size, uv.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_hit_uvs: no triangles, no vertices, or a hit row whose order entry or indices are out of range")
+    return out
+
+
+def srgb_table() -> np.ndarray:
+    """The sRGB decode of the 256 texel codes (rt_srgb_table): the table of an RT_TEX_SRGB texture."""
+    out = np.zeros(256, np.float32)
+    rc = lib().rt_srgb_table(_fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_srgb_table")
+    return out
+
+
+def _texels(who, texels):
+    """texels as a contiguous uint8 [H,W,4] array; what a cast would hide is refused here."""
+    t = np.asarray(texels)
+    if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 4:
+        raise RtError(RT_ERR_INVALID, f"{who}: texels must be uint8 [H,W,4] (row 0 at v = 0), got {t.dtype} {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def sample_texture(texels, flags, uvs) -> np.ndarray:
+    """The texture sample on the host (rt_sample_texture), the definition Renderer.mesh_hit_texels and the frames' texel are tested against: texels
+    uint8 [H,W,4] with row 0 at v = 0, flags TEX_* or'ed, uvs [N,2] -> float32 [N,3], the decoded RGB."""
+    t = _texels("sample_texture", texels)
+    uv = _f32(uvs)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise RtError(RT_ERR_INVALID, f"sample_texture: uvs must be [N,2], got {uv.shape}")
+    uv = np.ascontiguousarray(uv)
+    out = np.zeros((uv.shape[0], 3), np.float32)
+    rc = lib().rt_sample_texture(C.c_void_p(t.ctypes.data), t.shape[1], t.shape[0], int(flags), _fp(uv), uv.shape[0], _fp(out))
+    if rc != RT_OK:
+        raise RtError(rc, f"rt_sample_texture: a size outside 1 .. {TEX_MAX_SIZE} or unknown flag bits")
+    return out
+
+
 def vertex_colors_from_parts(indices, part_first, rgb, n_verts) -> np.ndarray:
     """Vertex colours [n_verts,3] float32 from one colour per part (pure numpy), the bridge from rt_raster_part_colors' table: part p owns input
     triangles part_first[p] .. part_first[p+1] (Renderer.mesh_upload_parts' table) and every vertex they name gets rgb[p]; on a vertex that parts
@@ -1097,6 +1190,23 @@ def load_obj(path):
     lib().rt_free(pos)
     lib().rt_free(idx)
     return p, i
+
+
+def load_obj_uv(path):
+    """rt_load_obj_uv: positions [V,3], uvs [V,2], indices [3T] of a .obj with vt records -- one vertex per distinct (v, vt) pair, in order of first
+    use by the faces; a corner without vt gets (0, 0)."""
+    pos, uv, idx = _FP(), _FP(), _U32P()
+    nv, ni = C.c_int(), C.c_int()
+    rc = lib().rt_load_obj_uv(str(path).encode(), C.byref(pos), C.byref(uv), C.byref(nv), C.byref(idx), C.byref(ni))
+    if rc != RT_OK:
+        raise RtError(rc, f"rt_load_obj_uv({path})")
+    p = np.ctypeslib.as_array(pos, shape=(max(nv.value * 3, 1),))[: nv.value * 3].copy().reshape(-1, 3)
+    t = np.ctypeslib.as_array(uv, shape=(max(nv.value * 2, 1),))[: nv.value * 2].copy().reshape(-1, 2)
+    i = np.ctypeslib.as_array(idx, shape=(max(ni.value, 1),))[: ni.value].copy()
+    lib().rt_free(pos)
+    lib().rt_free(uv)
+    lib().rt_free(idx)
+    return p, t, i
 
 
 def load_png(path) -> np.ndarray:
@@ -1394,7 +1504,7 @@ class Renderer:
         return self._device_view(ptr.value, n.value, cols, as_torch)
 
     def _mesh_hit_query(self, name, hits, extra, outputs):
-        """The four mesh_hit_* methods: hits a RayHits / SceneHits or its [N,4] float32 record array; extra None or (name, [N,3] array), a second
+        """The mesh_hit_* methods: hits a RayHits / SceneHits or its [N,4] float32 record array; extra None or (name, [N,3] array), a second
         input; outputs (columns, dtype) per answer, columns 0: [N].  numpy in, numpy out through rt_<name>_host, which synchronises; torch tensors on
         this context's device through rt_<name>: zero-copy, enqueued on the library stream, ordered against torch's current stream, no host wait.
         -> the list of answers."""
@@ -1554,6 +1664,74 @@ class Renderer:
         (rt_mesh_hit_colors_host: synchronises); a torch tensor on this context's device takes the zero-copy path of mesh_hit_normals: enqueued on
         the library stream, ordered against torch's current stream, no host wait."""
         return self._mesh_hit_query("mesh_hit_colors", hits, None, [(3, np.float32)])[0]
+
+    # ---- UVs and the albedo texture (DESIGN.md 14.15): corner UVs beside the triangle array, a texture the albedo of mesh hits is multiplied by
+    def mesh_uvs_enable(self, on=True):
+        """Keep one UV per vertex of the dynamic mesh (rt_mesh_uvs_enable), zeros at first: every update then gathers the corner UVs beside its new
+        rows.  Allocates two arrays and fills the rows if there is a tree; may synchronise.  on=False releases them.  Off until asked for."""
+        self._check(lib().rt_mesh_uvs_enable(self._h, 1 if on else 0))
+
+    def mesh_uvs(self, as_torch=None):
+        """The device array of vertex UVs: a float32 [V,2] tensor that aliases it (the caller may write it on stream()), else (pointer, bytes).  The
+        rows follow at the next update or mesh_uvs_refresh."""
+        return self._device_array("rt_mesh_uvs", 2, as_torch)
+
+    def mesh_set_uvs(self, uv, first=0):
+        """UVs [count,2] from host memory for vertices first .., copied on stream() in call order with updates, frames and queries (rt_mesh_set_uvs);
+        a non-finite component is refused.  The rows follow at the next update or mesh_uvs_refresh."""
+        c = _f32(uv)
+        if c.size % 2:
+            raise RtError(RT_ERR_INVALID, "mesh_set_uvs: uv must hold 2 floats per vertex")
+        c = np.ascontiguousarray(c.reshape(-1, 2))
+        self._check(lib().rt_mesh_set_uvs(self._h, _fp(c), int(first), c.shape[0]))   # pageable memory: staged before the call returns
+
+    def mesh_uvs_refresh(self):
+        """The corner UVs gathered again from the vertex UVs; enqueued in call order with updates, frames and queries (rt_mesh_uvs_refresh): no host
+        wait."""
+        self._check(lib().rt_mesh_uvs_refresh(self._h))
+
+    def mesh_uv_rows(self) -> np.ndarray:
+        """The corner UVs as float32 [nTris,8] rows, (u0, v0, u1, v1), (u2, v2, 0, 0) (rt_debug_read_scene: synchronises); empty while UVs are not
+        enabled or before the first rebuild.  Row i belongs to input triangle mesh_order()[i]."""
+        return self.debug_read_scene(RT_SCENE_ARRAY_UV_ROWS).view(np.float32).reshape(-1, 8)
+
+    def mesh_texture_upload(self, texels, flags=0):
+        """The mesh's albedo texture (rt_mesh_texture_upload): texels uint8 [H,W,4] with row 0 at v = 0, flags TEX_* or'ed; None releases it.  With
+        UVs enabled, frames of the mesh's scene with useBVH == 1 multiply the albedo of mesh hits by its sample.  May allocate and synchronise."""
+        if texels is None:
+            self._check(lib().rt_mesh_texture_upload(self._h, None, 0, 0, 0))
+            return
+        t = _texels("mesh_texture_upload", texels)
+        self._check(lib().rt_mesh_texture_upload(self._h, C.c_void_p(t.ctypes.data), t.shape[1], t.shape[0], int(flags)))
+
+    def mesh_texture(self, as_torch=None):
+        """The device texels: a uint8 [H,W,4] tensor that aliases them (the caller may write it on stream(); frames and queries read the texels as
+        they stand in stream order), else (pointer, bytes, W, H)."""
+        ptr, n, w, h = C.c_void_p(), C.c_size_t(), C.c_int(), C.c_int()
+        self._check(lib().rt_mesh_texture(self._h, C.byref(ptr), C.byref(n), C.byref(w), C.byref(h)))
+        if as_torch is None:
+            try:
+                import torch  # noqa: F401
+                as_torch = True
+            except ImportError:
+                as_torch = False
+        if not as_torch:
+            return ptr.value, n.value, w.value, h.value
+        import torch
+
+        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
+            __cuda_array_interface__ = {"shape": (h.value, w.value, 4), "typestr": "|u1", "data": (ptr.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    def mesh_hit_uvs(self, hits):
+        """The UV of each hit: float32 [N,2], hit_uvs bit for bit; zeros for a miss, an analytic hit or a prim outside the mesh.  Arguments and
+        paths as mesh_hit_colors."""
+        return self._mesh_hit_query("mesh_hit_uvs", hits, None, [(2, np.float32)])[0]
+
+    def mesh_hit_texels(self, hits):
+        """The texture's sample at each hit's UV: float32 [N,3], sample_texture(hit_uvs) bit for bit, not multiplied by the colour; zeros for a prim
+        outside the mesh.  Arguments and paths as mesh_hit_colors."""
+        return self._mesh_hit_query("mesh_hit_texels", hits, None, [(3, np.float32)])[0]
 
     # ---- morph targets (DESIGN.md 14.11): sparse deltas blended on the device under a weight table, before the skin or straight into the positions
     def mesh_morph_upload(self, target_first, vert_idx, deltas, base=None):

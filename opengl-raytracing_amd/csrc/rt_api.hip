@@ -408,6 +408,7 @@ int rt_debug_read_scene(RtContext *c, int which, void *dst, size_t capacity, siz
         case RT_SCENE_ARRAY_PREV_TRIS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_prev_tris(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         case RT_SCENE_ARRAY_NORMAL_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_normal_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
         case RT_SCENE_ARRAY_COLOR_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_color_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 48; break;
+        case RT_SCENE_ARRAY_UV_ROWS: src = (c->mesh && c->sceneFromMesh) ? rtl::mesh_uv_rows(c->mesh) : nullptr; n = (size_t)c->nTris * 32; break;
         default: return fail(c, RT_ERR_INVALID, "rt_debug_read_scene: array %d", which);
     }
     if (!have || !src) return RT_OK;
@@ -638,12 +639,23 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     fr.nrmRows = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_normal_rows(c->mesh) : nullptr;
     // per-vertex colours: mesh hits of the dynamic mesh's own scene; the hybrid scene keeps the constant albedo
     fr.colRows = (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1) ? rtl::mesh_color_rows(c->mesh) : nullptr;
+    // UVs and the albedo texture: mesh hits of the dynamic mesh's own scene, and only with both the UVs and a texture
+    if (c->mesh && c->sceneFromMesh && fr.u.useBVH == 1 && rtl::mesh_uv_rows(c->mesh) && rtl::mesh_texture(c->mesh)) {
+        fr.uvRows = rtl::mesh_uv_rows(c->mesh);
+        fr.tex = *rtl::mesh_texture(c->mesh);
+    }
     // Lane = frame index mod nLanes = index of the COLOR0 buffer this frame writes: consecutive frames rotate over the lanes'
     // streams and overlap everywhere except at the temporal resolve (the only read of the previous frame), and every later
     // reader of a COLOR0 buffer (gather, assemble) is stream-ordered before the next writer of the same buffer.
     const int lane = c->writeIdx, prevLane = (c->writeIdx + c->nLanes - 1) % c->nLanes;
     hipStream_t st = c->lanes[lane];
     if (c->serialFrames) HIP_TRY(c, hipStreamWaitEvent(st, c->evDone[prevLane], 0));
+    // the albedo texture: the caller may have written the texels on rt_stream()'s stream, the previous frame's lane; this frame reads
+    // them as they stand behind that write
+    if (fr.uvRows && api_stream(c) != st) {
+        HIP_TRY(c, hipEventRecord(c->evMeshDone, api_stream(c)));
+        HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshDone, 0));
+    }
     HIP_TRY(c, hipMemcpyAsync(c->dFrame[lane], &fr, sizeof(fr), hipMemcpyHostToDevice, st));
     if (fr.sc.rootBox) hipLaunchKernelGGL(k_frame_root_box, dim3(1), dim3(64), 0, st, c->dFrame[lane]);
     Targets tg;

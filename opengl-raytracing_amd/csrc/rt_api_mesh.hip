@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rt_context.hpp"
+#include "rt_mesh_uvs.hpp"
 #include "rt_bvh_cost.hpp"
 #include "rt_morph_pack.hpp"
 #include "rt_normal_pack.hpp"
@@ -64,7 +65,7 @@ int mesh_order_on(RtContext *c, hipStream_t st, const char *who, const int **ord
     });
 }
 
-// ---- the hit queries: per hit record of a closest-hit answer, an attribute of the mesh.  One routine serves the four
+// ---- the hit queries: per hit record of a closest-hit answer, an attribute of the mesh.  One routine serves the six
 // device entry points and their *_host twins; a HitQuery is what tells them apart.
 struct HitQuery {
     const char *entry;        // the device entry point: the name in a failed launch, also under the twin
@@ -101,6 +102,20 @@ const HitQuery kHitColors = {
     [](const rtl::Mesh *m) -> const void * { return rtl::mesh_color_rows(m); }, "colours are not enabled (rt_mesh_colors_enable first)", false,
     [](rtl::Mesh *m, hipStream_t st, const int *, const void *hits, const float *, int n, void *colors, void *, const char **err) {
         return rtl::mesh_hit_colors(m, st, hits, n, (float *)colors, err);
+    }};
+
+const HitQuery kHitUvs = {
+    "rt_mesh_hit_uvs", "hits and uvs", false, 1, 8, 15u, "hits must be 16-byte aligned, uvs 4-byte aligned",
+    [](const rtl::Mesh *m) -> const void * { return rtl::mesh_uv_rows(m); }, "UVs are not enabled (rt_mesh_uvs_enable first)", false,
+    [](rtl::Mesh *m, hipStream_t st, const int *, const void *hits, const float *, int n, void *uvs, void *, const char **err) {
+        return rtl::mesh_hit_uvs(m, st, hits, n, (float *)uvs, err);
+    }};
+const HitQuery kHitTexels = {
+    "rt_mesh_hit_texels", "hits and texels", false, 1, 12, 15u, "hits must be 16-byte aligned, texels 4-byte aligned",
+    [](const rtl::Mesh *m) -> const void * { return rtl::mesh_uv_rows(m) ? (const void *)rtl::mesh_texture(m) : nullptr; },
+    "UVs and a texture are needed (rt_mesh_uvs_enable and rt_mesh_texture_upload first)", false,
+    [](rtl::Mesh *m, hipStream_t st, const int *, const void *hits, const float *, int n, void *texels, void *, const char **err) {
+        return rtl::mesh_hit_texels(m, st, hits, n, (float *)texels, err);
     }};
 
 // who: the entry point called.  host: its arrays are host memory, staged as hits | points | outputs around the device path (an output the caller
@@ -476,6 +491,119 @@ int rt_mesh_hit_colors(RtContext *c, const RtHit *hits, int n, float *colors) {
 }
 int rt_mesh_hit_colors_host(RtContext *c, const RtHit *hits, int n, float *colors) {
     return mesh_hit_query(c, kHitColors, "rt_mesh_hit_colors_host", true, hits, nullptr, n, colors, nullptr);
+}
+
+// ---- UVs and the albedo texture: rt_mesh.hip gathers the UV rows inside every update, behind the colours'; this file owns enabling,
+// the ordering of UV writes and of the gather alone, the texture's upload and the two hit queries
+int rt_mesh_uvs_enable(RtContext *c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
+    if (!on) { rtl::mesh_uvs_release(c->mesh); return RT_OK; }
+    if (rtl::mesh_vertex_uvs(c->mesh)) return RT_OK;   // already enabled: the UVs and the rows stay as they are, nothing is allocated
+    hipStream_t st = api_stream(c);   // rt_stream()
+    const char *err = nullptr;
+    int rc = RT_OK;
+    // (a create that fails behind the order array's launch leaves the array written: the event is recorded either way)
+    const int er = with_order_event(c, st, false, false, [&] { rc = rtl::mesh_uvs_create(c->mesh, st, &err); return RT_OK; });
+    if (er != RT_OK) return er;
+    if (rc != RT_OK) return fail(c, rc, "rt_mesh_uvs_enable: %s", err ? err : "allocation failed");
+    return RT_OK;
+}
+
+int rt_mesh_uvs(RtContext *c, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs: no mesh (rt_mesh_upload first)");
+    if (!rtl::mesh_vertex_uvs(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs: UVs are not enabled (rt_mesh_uvs_enable first)");
+    *devPtr = rtl::mesh_vertex_uvs(c->mesh);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 8;
+    return RT_OK;
+}
+
+int rt_mesh_set_uvs(RtContext *c, const float *uv2, int first, int count) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh || !rtl::mesh_vertex_uvs(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: no UVs (rt_mesh_upload and rt_mesh_uvs_enable first)");
+    const int n = rtl::mesh_verts(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: vertices %d .. %d of %d", first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!uv2) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: null UVs");
+    for (size_t i = 0; i < (size_t)count * 2; ++i)
+        if (!std::isfinite(uv2[i])) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: component %zu of vertex %zu is %g (a finite value is needed)", i % 2, (size_t)first + i / 2, (double)uv2[i]);
+    return guarded(c, "rt_mesh_set_uvs", [&]() -> int {
+        (void)hipSetDevice(c->cfg.device);
+        hipStream_t st = api_stream(c);   // rt_stream()
+        // the caller's array, pageable memory: staged or copied before hipMemcpyAsync returns, as in rt_mesh_set_bones; ordered like rt_mesh_set_colors
+        return between_lanes(c, st, [&]() -> int {   // a gather enqueued on another lane reads the UVs
+            HIP_TRY(c, hipMemcpyAsync(rtl::mesh_vertex_uvs(c->mesh) + (size_t)first, uv2, (size_t)count * 8, hipMemcpyHostToDevice, st));
+            return RT_OK;
+        });
+    });
+}
+
+int rt_mesh_uvs_refresh(RtContext *c) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    if (!rtl::mesh_uv_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: UVs are not enabled (rt_mesh_uvs_enable first)");
+    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: no rows to fill (rt_mesh_rebuild first)");
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = api_stream(c);   // rt_stream()
+    // frames and queries on every lane read the rows they were enqueued with, and whatever a lane is given next sees the new ones
+    return between_lanes(c, st, [&] {
+        return with_order_event(c, st, false, false, [&]() -> int {
+            const char *err = nullptr;
+            const int rc = rtl::mesh_uvs_refresh(c->mesh, st, &err);
+            return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_uvs_refresh: %s", err ? err : "launch failed");
+        });
+    });
+}
+
+int rt_mesh_texture_upload(RtContext *c, const uint8_t *rgba8, int W, int H, int flags) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_texture_upload: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
+    const bool release = !rgba8 && W == 0 && H == 0;
+    if (!release) {
+        if (W < 1 || H < 1 || W > RT_TEX_MAX_SIZE || H > RT_TEX_MAX_SIZE) return fail(c, RT_ERR_INVALID, "rt_mesh_texture_upload: %d x %d texels (1 .. %d each)", W, H, RT_TEX_MAX_SIZE);
+        if ((uint32_t)flags & ~rtuv::kAllFlags) return fail(c, RT_ERR_INVALID, "rt_mesh_texture_upload: unknown flag bits 0x%x", (unsigned)flags & ~rtuv::kAllFlags);
+        if (!rgba8) return fail(c, RT_ERR_INVALID, "rt_mesh_texture_upload: null texels");
+    }
+    return guarded(c, "rt_mesh_texture_upload", [&]() -> int {
+        (void)hipSetDevice(c->cfg.device);
+        HIP_TRY(c, sync_all(c));   // frames and queries in flight read the texels that are about to be replaced or go
+        if (release) { rtl::mesh_texture_release(c->mesh); return RT_OK; }
+        float table[256];
+        if ((uint32_t)flags & rtuv::kSrgb) (void)rt_srgb_table(table);
+        else for (int k = 0; k < 256; ++k) table[k] = rtuv::unorm8((uint8_t)k);
+        const char *err = nullptr;
+        const int rc = rtl::mesh_texture_create(c->mesh, rgba8, W, H, (uint32_t)flags, table, &err);
+        return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_texture_upload: %s", err ? err : "allocation failed");
+    });
+}
+
+int rt_mesh_texture(RtContext *c, void **devPtr, size_t *bytes, int *W, int *H) {
+    if (!c || !devPtr || !bytes || !W || !H) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0; *W = 0; *H = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_texture: no mesh (rt_mesh_upload first)");
+    const rtuv::Texture *t = rtl::mesh_texture(c->mesh);
+    if (!t) return fail(c, RT_ERR_INVALID, "rt_mesh_texture: no texture (rt_mesh_texture_upload first)");
+    *devPtr = const_cast<void *>(t->texels);
+    *bytes = (size_t)t->W * (size_t)t->H * 4;
+    *W = t->W; *H = t->H;
+    return RT_OK;
+}
+
+int rt_mesh_hit_uvs(RtContext *c, const RtHit *hits, int n, float *uvs) {
+    return mesh_hit_query(c, kHitUvs, "rt_mesh_hit_uvs", false, hits, nullptr, n, uvs, nullptr);
+}
+int rt_mesh_hit_uvs_host(RtContext *c, const RtHit *hits, int n, float *uvs) {
+    return mesh_hit_query(c, kHitUvs, "rt_mesh_hit_uvs_host", true, hits, nullptr, n, uvs, nullptr);
+}
+int rt_mesh_hit_texels(RtContext *c, const RtHit *hits, int n, float *texels) {
+    return mesh_hit_query(c, kHitTexels, "rt_mesh_hit_texels", false, hits, nullptr, n, texels, nullptr);
+}
+int rt_mesh_hit_texels_host(RtContext *c, const RtHit *hits, int n, float *texels) {
+    return mesh_hit_query(c, kHitTexels, "rt_mesh_hit_texels_host", true, hits, nullptr, n, texels, nullptr);
 }
 
 // ---- skinning: rt_mesh_skin.hip rewrites the positions; this file validates the tables and orders the writes against every lane

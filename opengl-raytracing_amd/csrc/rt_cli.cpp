@@ -119,10 +119,10 @@ static void die(RtContext *c, const char *what, int rc) {
 
 int main(int argc, char **argv) {
     std::vector<std::string> objs;
-    std::string env, out = "frame";
+    std::string env, out = "frame", texture;
     bool raster = false;                     // --raster: renderRaster's draw list instead of ray frames (ground / --obj / sphere meshes)
     std::string groundObj, sphereObj;
-    bool dumpTargets = false;
+    bool dumpTargets = false, textureSrgb = false;
     float dt = 1.0f / 60.0f;   // seconds per frame for the point-light orbit
     int W = 1920, H = 1080, frames = 1, device = 0, useBVH = 0, showMotion = 0;
     int giBounces = 1;
@@ -178,6 +178,8 @@ int main(int argc, char **argv) {
             }
         }
         else if (a == "--obj") { objs.push_back(next()); if (useBVH == 0) useBVH = 1; }
+        else if (a == "--texture") texture = next();                 // EXTENSION: an albedo texture for the one --obj mesh
+        else if (a == "--texture-srgb") textureSrgb = true;
         else if (a == "--dump-targets") dumpTargets = true;
         else if (a == "--raster") raster = true;
         else if (a == "--ground") groundObj = next();
@@ -212,6 +214,7 @@ int main(int argc, char **argv) {
                                     "              [--cam x,y,z,yaw,pitch] [--fov deg] [--aspect a] [--exposure e] [--no-gi --no-ao --no-taa --no-svgf --no-env] [--out prefix]\n"
                                     "              [--raster [--ground f.obj] [--sphere f.obj]]  (renderRaster's flat-colour preview of ground / --obj / sphere)\n"
                                     "              [--hybrid [--gi-bounces n]]   EXTENSION: the analytic scene with the .obj mesh added to it, n diffuse GI bounces\n"
+                                    "              [--texture f.png [--texture-srgb]]   EXTENSION: one --obj with vt records, shaded through the PNG as its albedo\n"
                                     "              [--env-filter 0|1]   cube-map filter model: exact fp32 weights (default) / texel coordinates rounded to 1/256 texel\n"
                                     "              [--ranks N [--devices d0,d1,..] [--gather-every k] [--dry-run]]   tile-parallel over N GPUs, one process each, RCCL gather to rank 0\n"
                                     "              (--obj may be repeated; --dump-targets writes prefix_{color,motion,gpos,gnrm}.pfm; --scene file.json sets any of\n"
@@ -342,7 +345,36 @@ int main(int argc, char **argv) {
         return 0;
     }
 
-    if (!objs.empty()) {
+    if (!texture.empty()) {
+        // EXTENSION: the mesh keeps its vt records and lives on the device as the dynamic mesh, placed by the default transform as the
+        // untextured path places it; colours at 1 so that the albedo is the texture alone
+        if (objs.size() != 1 || ranks > 0 || raster) { std::fprintf(stderr, "rt_cli: --texture takes one --obj, without --ranks or --raster\n"); return 2; }
+        float M[16];
+        rt_default_bvh_transform(M);
+        float *pos = nullptr, *uvs = nullptr; uint32_t *idx = nullptr; int nv = 0, ni = 0;
+        if ((rc = rt_load_obj_uv(objs[0].c_str(), &pos, &uvs, &nv, &idx, &ni)) != RT_OK) die(ctx, "rt_load_obj_uv", rc);
+        uint8_t *px = nullptr; int w = 0, h = 0, ch = 0;
+        if ((rc = rt_load_png(texture.c_str(), &px, &w, &h, &ch)) != RT_OK) die(ctx, "rt_load_png", rc);
+        std::vector<uint8_t> rgba((size_t)w * h * 4);
+        for (int y = 0; y < h; ++y)                                    // the PNG's first row is the top one: row 0 of the texture is v = 0, the bottom
+            for (int x = 0; x < w; ++x) {
+                const uint8_t *src = px + ((size_t)(h - 1 - y) * w + x) * ch;
+                uint8_t *dst = &rgba[((size_t)y * w + x) * 4];
+                dst[0] = src[0]; dst[1] = ch >= 3 ? src[1] : src[0]; dst[2] = ch >= 3 ? src[2] : src[0]; dst[3] = ch == 4 ? src[3] : 255;
+            }
+        rt_free(px);
+        if ((rc = rt_mesh_upload(ctx, pos, nv, idx, ni)) != RT_OK) die(ctx, "rt_mesh_upload", rc);
+        if ((rc = rt_mesh_colors_enable(ctx, 1)) != RT_OK) die(ctx, "rt_mesh_colors_enable", rc);
+        const std::vector<float> white((size_t)nv * 3, 1.0f);
+        if ((rc = rt_mesh_set_colors(ctx, white.data(), 0, nv)) != RT_OK) die(ctx, "rt_mesh_set_colors", rc);
+        if ((rc = rt_mesh_uvs_enable(ctx, 1)) != RT_OK) die(ctx, "rt_mesh_uvs_enable", rc);
+        if ((rc = rt_mesh_set_uvs(ctx, uvs, 0, nv)) != RT_OK) die(ctx, "rt_mesh_set_uvs", rc);
+        if ((rc = rt_mesh_texture_upload(ctx, rgba.data(), w, h, textureSrgb ? RT_TEX_SRGB : RT_TEX_UNORM)) != RT_OK) die(ctx, "rt_mesh_texture_upload", rc);
+        if ((rc = rt_mesh_rebuild(ctx, M)) != RT_OK) die(ctx, "rt_mesh_rebuild", rc);
+        RT_SAY("[OBJ] %s: %d vertices, %d triangles\n", objs[0].c_str(), nv, ni / 3);
+        RT_SAY("[TEXTURE] %s: %dx%d, %s\n", texture.c_str(), w, h, textureSrgb ? "sRGB" : "linear");
+        rt_free(pos); rt_free(uvs); rt_free(idx);
+    } else if (!objs.empty()) {
         float M[16];
         rt_default_bvh_transform(M);                                  // include/app/state.h:26-31
         std::vector<float> tris9;

@@ -14,6 +14,7 @@
 #include "rt_mesh_motion.hpp"
 #include "rt_mesh_normals.hpp"
 #include "rt_mesh_colors.hpp"
+#include "rt_mesh_uvs.hpp"
 
 #pragma clang fp contract(off)
 
@@ -359,6 +360,39 @@ RT_DEV V3 hitColor(const float4 *tris, const float4 *colRows, int tri, V3 ro, V3
     float out[3];
     rtcolor::blend_colors(c0, c1, c2, a, b, out);
     return mk3(out[0], out[1], out[2]);
+}
+
+// UVs and the albedo texture: the albedo of the hit of the ray (ro, rd) on row `tri` while the frame carries uvRows and a texture:
+// base * texel per channel, one rounded product.  base is hitColor's answer -- colRows == null: the reference's constant -- and texel is
+// rt_sample_texture's at rt_hit_uvs' UV.  (a, b) are computed once, with hitNormal's operations in their order, and the steps are taken one after the
+// other, as in hitColor: the row for (a, b), the colour row, the UV row, then the texels.
+RT_DEV V3 hitAlbedoTex(const float4 *tris, const float4 *colRows, const float4 *uvRows, const rtuv::Texture &tex, int tri, V3 ro, V3 rd) {
+    float a, b;
+    {
+        const float4 *T = tris + (size_t)tri * 3;
+        const V3 v0 = f4xyz(T[0]), e1 = f4xyz(T[1]), e2 = f4xyz(T[2]);
+        const V3 pvec = cross(rd, e2);
+        const float invDet = 1.0f / dot(e1, pvec);
+        const V3 tvec = ro - v0;
+        a = dot(tvec, pvec) * invDet;
+        b = dot(rd, cross(tvec, e1)) * invDet;
+    }
+    float base[3] = {0.85f, 0.85f, 0.85f};
+    if (colRows) {
+        const float4 *R = colRows + (size_t)tri * 3;
+        const float4 r0 = R[0], r1 = R[1], r2 = R[2];
+        const float c0[3] = {r0.x, r0.y, r0.z}, c1[3] = {r1.x, r1.y, r1.z}, c2[3] = {r2.x, r2.y, r2.z};
+        rtcolor::blend_colors(c0, c1, c2, a, b, base);
+    }
+    float uv[2], t[3];
+    {
+        const float4 *U = uvRows + (size_t)tri * 2;
+        const float4 u0 = U[0], u1 = U[1];
+        const float c0[2] = {u0.x, u0.y}, c1[2] = {u0.z, u0.w}, c2[2] = {u1.x, u1.y};
+        rtuv::blend_uvs(c0, c1, c2, a, b, uv);
+    }
+    rtuv::sample(tex, uv[0], uv[1], t);
+    return mk3(base[0] * t[0], base[1] * t[1], base[2] * t[2]);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -69,7 +69,9 @@ struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it thr
     const float4 *nrmRows = nullptr;  // smooth normals: the dynamic mesh's corner normals, row for row beside sc.tris; null = off, the face normal.
                                       // Behind prevTris for the same reason
     const float4 *colRows = nullptr;  // per-vertex colours: the dynamic mesh's corner colours, row for row beside sc.tris; null = off, the constant
-                                      // albedo.  Last, behind nrmRows, for the same reason
+                                      // albedo.  Behind nrmRows, for the same reason
+    const float4 *uvRows = nullptr;   // UVs and the albedo texture: the dynamic mesh's corner UVs, row for row beside sc.tris, and the texture the
+    rtuv::Texture tex;                // albedo of a mesh hit is multiplied by; uvRows == null = off (set only with a texture).  Last, behind colRows, for the same reason
 };
 
 struct Targets {

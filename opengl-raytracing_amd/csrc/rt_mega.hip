@@ -3,6 +3,8 @@
 // Used for the analytic scene (pure ALU, nothing to queue) and as the reference-shaped baseline
 // for BVH scenes that the wavefront pipeline (rt_wave.hip) is measured and bit-compared against.
 // A workgroup is one 16x16 tile; each wave is an 8x8 pixel block; the traversal stack lives in LDS.
+#include <cstddef>
+
 #include "rt_device_analytic.hpp"
 #include "rt_frame.hpp"
 
@@ -41,7 +43,9 @@ struct InlineTracer {
         hp = ro + rd * t;
         hn = hitNormal(sc->tris, nrm, tri, ro, rd);
         albedo.p = primary.p + 768;
-        albedo.set(hitColor(sc->tris, primary.colRows, tri, ro, rd));
+        // (the tracer's scene is the frame's: the frame is found from it, so that the keeper and the tracer hold what they held)
+        const DevFrame *fr = reinterpret_cast<const DevFrame *>(reinterpret_cast<const char *>(sc) - offsetof(DevFrame, sc));
+        albedo.set(fr->uvRows ? hitAlbedoTex(sc->tris, primary.colRows, fr->uvRows, fr->tex, tri, ro, rd) : hitColor(sc->tris, primary.colRows, tri, ro, rd));
         return 1;
     }
     RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn) {
@@ -127,7 +131,8 @@ __global__ __launch_bounds__(256, 4) void k_mega(const DevFrame *__restrict__ fr
                 }
                 MegaAlbedo albedo;   // per-vertex colours: fetched once per hit, behind the AO rays; null colRows: the constant
                 albedo.p = &lds_albedo[tid]; albedo.colRows = fr->colRows;
-                albedo.set(hitColor(fr->sc.tris, fr->colRows, triHit, camPos, dir));
+                // the albedo texture: the product is formed in front of set(): nothing new lives across a traversal call
+                albedo.set(fr->uvRows ? hitAlbedoTex(fr->sc.tris, fr->colRows, fr->uvRows, fr->tex, triHit, camPos, dir) : hitColor(fr->sc.tris, fr->colRows, triHit, camPos, dir));
                 for (int s = 0; s < SPP; ++s) {
                     int seed = (int)((uint32_t)u.frameIndex * (uint32_t)SPP + (uint32_t)s);
                     frameSum = frameSum + shadeSampleBVH<InlineTracer<COUNT>, COUNT, true, MegaAlbedo>(tr, F, hp, hn, V, seed, ao, w, &albedo);

@@ -21,6 +21,7 @@
 #include "../../include/rt_mi355.h"
 #include "rt_bvh_build.hpp"
 #include "rt_mesh.hpp"
+#include "rt_mesh_uvs.hpp"
 #include "rt_qnode.hpp"
 #include "rt_scene_pack.hpp"
 
@@ -188,7 +189,7 @@ int bvh_layout(int nTris, BvhLayout &out) {
     return RT_OK;
 }
 
-// The device memory of one optional feature (skin, morph, motion, normals, colours): the blocks its create call allocated beyond `owned`, each with the
+// The device memory of one optional feature (skin, morph, motion, normals, colours, UVs, the texture): the blocks its create call allocated beyond `owned`, each with the
 // member that points at it, and their byte count.  attach / detach below are the only code that allocates, counts and frees them.
 struct Attachment {
     struct Block { void *mem; void *member; void (*forget)(void *member); };
@@ -249,6 +250,15 @@ struct Mesh {
     // mesh_colors_create, not in `owned`
     float4 *dVertCol = nullptr, *dColRows = nullptr;
     Attachment colors;
+    // UVs and the albedo texture: one UV per vertex and the corner UVs row for row beside the triangle array (mesh_uvs_create); the
+    // texels and the decode table behind `tex` (mesh_texture_create); neither in `owned`
+    float2 *dVertUv = nullptr;
+    float4 *dUvRows = nullptr;
+    Attachment uvs;
+    uint32_t *dTexels = nullptr;
+    float *dTexTable = nullptr;
+    rtuv::Texture tex;   // texels == null: no texture
+    Attachment texture;
     // the tree a refit keeps: which of dPerm holds the last rebuild's permutation (-1: no rebuild yet); the other one is idle until the next rebuild
     // and holds, once asked for, the row -> input triangle map
     int permCur = -1;
@@ -462,6 +472,8 @@ void mesh_destroy(Mesh *m) {
     mesh_motion_release(m);
     mesh_normals_release(m);
     mesh_colors_release(m);
+    mesh_uvs_release(m);
+    mesh_texture_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
     if (m->hQRec) (void)hipHostFree(m->hQRec);
@@ -494,14 +506,19 @@ int normals_update(Mesh *m, hipStream_t st, const char **err) {
     REB_TRY(hipGetLastError());
     return RT_OK;
 }
-// the tail of an update behind its new rows: smooth normals, then the colour rows under the same order array -- a
-// rebuild moved every input triangle to another row; a refit's gather rewrites what it finds, which is what a caller who also changed colours wants
+// the tail of an update behind its new rows: smooth normals, then the colour rows, then the UV rows (DESIGN.md
+// 14.15) under the same order array -- a rebuild moved every input triangle to another row; a refit's gather rewrites what it finds, which is what a
+// caller who also changed colours or UVs wants
 int attributes_update(Mesh *m, hipStream_t st, const char **err) {
     if (m->dNrmRows) {
         const int rc = normals_update(m, st, err);
         if (rc != RT_OK) return rc;
     }
-    if (m->dColRows) return mesh_colors_refresh(m, st, err);
+    if (m->dColRows) {
+        const int rc = mesh_colors_refresh(m, st, err);
+        if (rc != RT_OK) return rc;
+    }
+    if (m->dUvRows) return mesh_uvs_refresh(m, st, err);
     return RT_OK;
 }
 // every record form from the bounds and the triangle array, through the tables: the tail of a rebuild and of a refit
@@ -768,6 +785,71 @@ int mesh_colors_refresh(Mesh *m, hipStream_t st, const char **err) {
 int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *colors, const char **err) {
     if (!m->dColRows || m->permCur < 0) return RT_ERR_INVALID;
     colors_launch_hit_colors(st, hits, n, m->dColRows, m->lay.nTris, colors);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_uvs_release(Mesh *m) { detach(m, m->uvs); }
+
+int mesh_uvs_create(Mesh *m, hipStream_t st, const char **err) {
+    mesh_uvs_release(m);
+    hipError_t e = attach(m, m->uvs, &m->dVertUv, (size_t)m->nVerts * 8, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, m->uvs, &m->dUvRows, (size_t)m->lay.nTris * 32, Fill::zeros);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    int rc = RT_OK;
+    if (e == hipSuccess && m->permCur >= 0) rc = mesh_uvs_refresh(m, st, err);
+    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
+    if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_uvs_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
+    return RT_OK;
+}
+
+float2 *mesh_vertex_uvs(const Mesh *m) { return m->dVertUv; }
+const float4 *mesh_uv_rows(const Mesh *m) { return m->dUvRows; }
+
+int mesh_uvs_refresh(Mesh *m, hipStream_t st, const char **err) {
+    if (!m->dUvRows || m->permCur < 0) return RT_ERR_INVALID;
+    const int *order = nullptr;
+    const int rc = mesh_order(m, st, &order, err);
+    if (rc != RT_OK) return rc;
+    uvs_launch_rows(st, order, m->dIdx, m->dVertUv, m->lay.nTris, m->nVerts, m->dUvRows);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int mesh_hit_uvs(Mesh *m, hipStream_t st, const void *hits, int n, float *uvs, const char **err) {
+    if (!m->dUvRows || m->permCur < 0) return RT_ERR_INVALID;
+    uvs_launch_hit_uvs(st, hits, n, m->dUvRows, m->lay.nTris, uvs);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+void mesh_texture_release(Mesh *m) {
+    detach(m, m->texture);
+    m->tex = rtuv::Texture{};
+}
+
+int mesh_texture_create(Mesh *m, const uint8_t *rgba8, int W, int H, uint32_t flags, const float *table256, const char **err) {
+    const size_t bytes = (size_t)W * (size_t)H * 4;
+    hipError_t e = hipSuccess;
+    if (m->dTexels && (size_t)m->tex.W * (size_t)m->tex.H * 4 == bytes) {   // the same size: the block is kept
+        e = hipMemcpy(m->dTexels, rgba8, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(m->dTexTable, table256, 1024, hipMemcpyHostToDevice);
+    } else {
+        mesh_texture_release(m);
+        e = attach(m, m->texture, &m->dTexels, bytes, Fill::host, rgba8);
+        if (e == hipSuccess) e = attach(m, m->texture, &m->dTexTable, 1024, Fill::host, table256);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_texture_release(m); return RT_ERR_HIP; }
+    m->tex.texels = m->dTexels; m->tex.table = m->dTexTable; m->tex.W = W; m->tex.H = H; m->tex.flags = flags;
+    return RT_OK;
+}
+
+const rtuv::Texture *mesh_texture(const Mesh *m) { return m->tex.texels ? &m->tex : nullptr; }
+
+int mesh_hit_texels(Mesh *m, hipStream_t st, const void *hits, int n, float *texels, const char **err) {
+    if (!m->dUvRows || !m->tex.texels || m->permCur < 0) return RT_ERR_INVALID;
+    uvs_launch_hit_texels(st, hits, n, m->dUvRows, m->lay.nTris, m->tex, texels);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

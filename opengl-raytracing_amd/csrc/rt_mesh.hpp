@@ -9,6 +9,8 @@
 
 #include "../../include/rt_mi355.h"
 
+namespace rtuv { struct Texture; }   // rt_mesh_uvs.hpp
+
 namespace rtl {
 
 // What the triangle count alone determines (the builder splits every range at its middle and stops at <= 8 triangles).
@@ -175,6 +177,29 @@ int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *col
 void colors_launch_fill(hipStream_t st, float4 *vertCol, int nVerts);
 void colors_launch_rows(hipStream_t st, const int *order, const uint32_t *idx, const float4 *vertCol, int nTris, int nVerts, float4 *colRows);
 void colors_launch_hit_colors(hipStream_t st, const void *hits, int n, const float4 *colRows, int nTris, float *colors);
+
+// UVs and the albedo texture.  mesh_uvs_create: allocates the vertex UVs (nVerts float2, zeros) and uvRows (nTris rows of two float4,
+// (u0, v0, u1, v1), (u2, v2, 0, 0), row i beside row i of the triangle array) and, when there is a tree, gathers the rows on `st`; allocates and waits
+// for the device; the caller has waited for every lane.  While the arrays exist mesh_rebuild and mesh_refit gather the rows again behind the colours'
+// gather, inside their own sequence of launches: no allocation, no host wait.
+int mesh_uvs_create(Mesh *m, hipStream_t st, const char **err);
+void mesh_uvs_release(Mesh *m);
+float2 *mesh_vertex_uvs(const Mesh *m);           // device, nVerts float2; null: UVs are not enabled
+const float4 *mesh_uv_rows(const Mesh *m);        // device, nTris x 2 float4; null: UVs are not enabled
+int mesh_uvs_refresh(Mesh *m, hipStream_t st, const char **err);   // the gather alone, as mesh_colors_refresh
+// The texture: an attachment of its own, the texels (W x H RGBA8) and the 256-float decode table.  mesh_texture_create allocates (a block of the same
+// size is kept), copies both from host memory and waits for the device; the caller has waited for every lane.  mesh_texture: null without one.
+int mesh_texture_create(Mesh *m, const uint8_t *rgba8, int W, int H, uint32_t flags, const float *table256, const char **err);
+void mesh_texture_release(Mesh *m);
+const rtuv::Texture *mesh_texture(const Mesh *m);
+// Enqueue uvs[i] = the UV of hit i (rt_hit_uvs' out2) / texels[i] = the texture's sample there on `st` for n RtHit records (device pointers).
+// RT_ERR_INVALID without the arrays (the texture, for the second) or without a tree.
+int mesh_hit_uvs(Mesh *m, hipStream_t st, const void *hits, int n, float *uvs, const char **err);
+int mesh_hit_texels(Mesh *m, hipStream_t st, const void *hits, int n, float *texels, const char **err);
+// rt_mesh_uvs.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
+void uvs_launch_rows(hipStream_t st, const int *order, const uint32_t *idx, const float2 *vertUv, int nTris, int nVerts, float4 *uvRows);
+void uvs_launch_hit_uvs(hipStream_t st, const void *hits, int n, const float4 *uvRows, int nTris, float *uvs);
+void uvs_launch_hit_texels(hipStream_t st, const void *hits, int n, const float4 *uvRows, int nTris, const rtuv::Texture &tex, float *texels);
 
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);

@@ -453,7 +453,7 @@ static int wave_chunk(LaunchSet &L, int c) {
     // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
     if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
     const unsigned gridH = (unsigned)((L.CH + 255) / 256);
-    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(L.host->colRows ? (L.host->nrmRows ? k_combine_smooth_color : k_combine_color) : (L.host->nrmRows ? k_combine_smooth : k_combine), dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
+    return wave_stage(L, ST_COMBINE, L.ss, [&] { hipLaunchKernelGGL(L.host->uvRows ? (L.host->nrmRows ? k_combine_smooth_tex : k_combine_tex) : L.host->colRows ? (L.host->nrmRows ? k_combine_smooth_color : k_combine_color) : (L.host->nrmRows ? k_combine_smooth : k_combine), dim3(gridH), dim3(256), 0, L.ss, L.dFrame, L.tg, wb, c0); });
 }
 
 // The steps of a launch set: lane bookkeeping, plan, arenas, cursor table, primary stages, chunks settled, chunk by chunk, tally and resolve.

@@ -2,6 +2,8 @@
 // policies through which they run the reference's shading code.
 // Part of the rt_wave.hip translation unit: included by it alone, behind its `#pragma clang fp contract(off)` and `using namespace rtd;`.
 #pragma once
+#include <type_traits>
+
 #include "rt_trace.hpp"   // rt_dyn_lds (k_gen_gi_overflow's stacks)
 
 namespace {
@@ -266,6 +268,19 @@ template <bool SMOOTH, bool COLOR> struct CombineTracer {     // reads everythin
     RT_DEV bool ao(int i, V3, V3, float radius) { return radius > 0.0f && wb.occ1[(uint32_t)i * wb.CH + j] != 0; }
 };
 
+// ... and with the albedo texture of DESIGN.md 14.15 (DevFrame::uvRows != null): the bounce hit's albedo is its colour times its texel; col may be null
+template <bool SMOOTH> struct CombineTexTracer : CombineTracer<SMOOTH, true> {
+    using Base = CombineTracer<SMOOTH, true>;
+    using Base::gi;
+    const float4 *uv;            // DevFrame::uvRows, the bounce hit's corner UVs
+    const rtuv::Texture *tex;    // DevFrame::tex
+    RT_DEV int gi(V3 ro, V3 rd, V3 &hp, V3 &hn, const HeldAlbedo &, HeldAlbedo &albedo) {   // the normal first, then the albedo, one row at a time
+        if (Base::gi(ro, rd, hp, hn) == 0) return 0;
+        albedo.c = hitAlbedoTex(this->sc->tris, this->col, uv, *tex, this->wb.giTri[this->wb.gi_entry(this->s, this->j)], ro, rd);
+        return 1;
+    }
+};
+
 struct HitCtx { Frag F; V3 dir, hp, hn; int px, py; uint32_t slot; };
 template <bool SMOOTH> RT_DEV HitCtx load_hit(const DevFrame *fr, const HitRec &h) {
     HitCtx c;
@@ -474,15 +489,17 @@ __global__ __launch_bounds__(256) void k_gen_gi_overflow(const DevFrame *__restr
 __global__ __launch_bounds__(256) void k_gen_gi_overflow_smooth(const DevFrame *__restrict__ fr, WaveBuf wb, uint32_t c0, const uint32_t *giCount, int stackEntries, const uint32_t *hitList, const uint32_t *hitCount) { gen_gi_overflow_body<true>(fr, wb, c0, giCount, stackEntries, hitList, hitCount); }
 
 // ---- stage: combine (thread = hit) ---------------------------------------------------------------
-template <bool SMOOTH, bool COLOR> RT_DEV void combine_body(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
+template <bool SMOOTH, bool COLOR, bool TEX = false> RT_DEV void combine_body(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) {
     const RtUniforms &u = fr->u;
     const uint32_t live = chunk_live(wb, c0);
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= live) return;
     HitCtx c = load_hit<SMOOTH>(fr, wb.hits[c0 + j]);
     const int SPP = max(u.spp, 1);
-    CombineTracer<SMOOTH, COLOR> tr;
+    using Tracer = typename std::conditional<TEX, CombineTexTracer<SMOOTH>, CombineTracer<SMOOTH, COLOR>>::type;
+    Tracer tr;
     tr.wb = wb; tr.sc = &fr->sc; tr.nrm = SMOOTH ? fr->nrmRows : nullptr; tr.col = COLOR ? fr->colRows : nullptr; tr.j = j; tr.s = 0;
+    if constexpr (TEX) { tr.uv = fr->uvRows; tr.tex = &fr->tex; }
     Work w;
     V2 prevNDC = ndcFromWorld(prevHitPoint(fr->sc.tris, fr->prevTris, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir, c.hp), u.prevViewProj), currNDC = ndcFromWorld(c.hp, u.currViewProj);
     V2 motionOut = mk2(currNDC.x - prevNDC.x, currNDC.y - prevNDC.y);
@@ -492,17 +509,18 @@ template <bool SMOOTH, bool COLOR> RT_DEV void combine_body(const DevFrame *__re
     V3 frameSum = mk3(0.0f);
     if constexpr (COLOR) {   // per-vertex colours: the primary hit's colour once per hit, in front of the sample loop
         HeldAlbedo albedo;
-        albedo.c = hitColor(fr->sc.tris, fr->colRows, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir);
+        if constexpr (TEX) albedo.c = hitAlbedoTex(fr->sc.tris, fr->colRows, fr->uvRows, fr->tex, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir);
+        else albedo.c = hitColor(fr->sc.tris, fr->colRows, wb.hits[c0 + j].tri, ld3(u.camPos), c.dir);
         for (int s = 0; s < SPP; ++s) {
             tr.s = s;
             int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
-            frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH, COLOR>, false, true>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w, &albedo);
+            frameSum = frameSum + shadeSampleBVH<Tracer, false, true>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w, &albedo);
         }
     } else {
         for (int s = 0; s < SPP; ++s) {
             tr.s = s;
             int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
-            frameSum = frameSum + shadeSampleBVH<CombineTracer<SMOOTH, COLOR>, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
+            frameSum = frameSum + shadeSampleBVH<Tracer, false>(tr, c.F, c.hp, c.hn, -c.dir, seed, ao, w);
         }
     }
     finish_pixel(fr, wb, (int)c.slot, frameSum, motionOut, mk4(c.hp.x, c.hp.y, c.hp.z, 1.0f), mk4(nn.x, nn.y, nn.z, 0.0f));
@@ -513,6 +531,9 @@ __global__ __launch_bounds__(256) void k_combine_smooth(const DevFrame *__restri
 // ... and with the per-vertex colours of DESIGN.md 14.14 (DevFrame::colRows != null): the only stage that evaluates the shading, so the only one built again
 __global__ __launch_bounds__(256) void k_combine_color(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false, true>(fr, tg, wb, c0); }
 __global__ __launch_bounds__(256) void k_combine_smooth_color(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true, true>(fr, tg, wb, c0); }
+// ... and with the albedo texture of DESIGN.md 14.15 (DevFrame::uvRows != null): two builds, the colours behind a run-time test of DevFrame::colRows
+__global__ __launch_bounds__(256) void k_combine_tex(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<false, true, true>(fr, tg, wb, c0); }
+__global__ __launch_bounds__(256) void k_combine_smooth_tex(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb, uint32_t c0) { combine_body<true, true, true>(fr, tg, wb, c0); }
 
 __global__ void k_accum_tally(const uint32_t *counts, unsigned long long *acc, int frames) {
     // acc: [0] candidates [1] hits [2] primary rays traced [3] shadow [4] bounce [5] bounce-shadow (the traversal kernels add to

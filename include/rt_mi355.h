@@ -837,7 +837,7 @@ int rt_mesh_colors(RtContext *ctx, void **devPtr, size_t *bytes);
  * host may spend the copy's time in the call.  RT_ERR_INVALID without a mesh or colours, for a
  * range outside [0, nVerts], a null rgb3 with count > 0, or a component that is non-finite or negative.  Does not touch the rows. */
 int rt_mesh_set_colors(RtContext *ctx, const float *rgb3, int first, int count);
-/* The row gather alone (k_color_rows), for a caller who changed colours and not positions; enqueued and ordered exactly as rt_mesh_motion_latch is: no
+/* The row gather alone (k_corner_rows<ColorAttr>), for a caller who changed colours and not positions; enqueued and ordered exactly as rt_mesh_motion_latch is: no
  * allocation, no host wait.  RT_ERR_INVALID without a mesh, without colours enabled, or before the first rebuild. */
 int rt_mesh_colors_refresh(RtContext *ctx);
 /* The colour of each hit: for the RtHit outputs of rt_trace_rays, rt_trace_scene_rays or rt_pick_pixels, colors (3 floats per hit) equals rt_hit_colors'
@@ -875,7 +875,7 @@ int rt_mesh_uvs(RtContext *ctx, void **devPtr, size_t *bytes);
  * RT_ERR_INVALID without a mesh or UVs, for a range outside [0, nVerts], a null uv2 with count > 0, or a non-finite component (negative values are
  * fine).  Does not touch the rows. */
 int rt_mesh_set_uvs(RtContext *ctx, const float *uv2, int first, int count);
-/* The row gather alone (k_uv_rows), ordered exactly as rt_mesh_colors_refresh: no allocation, no host wait.  RT_ERR_INVALID without a mesh, without
+/* The row gather alone (k_corner_rows<UvAttr>), ordered exactly as rt_mesh_colors_refresh: no allocation, no host wait.  RT_ERR_INVALID without a mesh, without
  * UVs enabled, or before the first rebuild. */
 int rt_mesh_uvs_refresh(RtContext *ctx);
 /* The mesh's texture: rgba8 holds W x H texels of 4 bytes, row 0 at v = 0; flags: RT_TEX_* or'ed.  An attachment of its own (the texels and the 1 KB

@@ -101,14 +101,13 @@ const HitQuery kHitColors = {
     "rt_mesh_hit_colors", "hits and colors", false, 1, 12, 15u, "hits must be 16-byte aligned, colors 4-byte aligned",
     [](const rtl::Mesh *m) -> const void * { return rtl::mesh_color_rows(m); }, "colours are not enabled (rt_mesh_colors_enable first)", false,
     [](rtl::Mesh *m, hipStream_t st, const int *, const void *hits, const float *, int n, void *colors, void *, const char **err) {
-        return rtl::mesh_hit_colors(m, st, hits, n, (float *)colors, err);
+        return rtl::mesh_hit_blend(m, rtl::Corner::colors, st, hits, n, (float *)colors, err);
     }};
-
 const HitQuery kHitUvs = {
     "rt_mesh_hit_uvs", "hits and uvs", false, 1, 8, 15u, "hits must be 16-byte aligned, uvs 4-byte aligned",
     [](const rtl::Mesh *m) -> const void * { return rtl::mesh_uv_rows(m); }, "UVs are not enabled (rt_mesh_uvs_enable first)", false,
     [](rtl::Mesh *m, hipStream_t st, const int *, const void *hits, const float *, int n, void *uvs, void *, const char **err) {
-        return rtl::mesh_hit_uvs(m, st, hits, n, (float *)uvs, err);
+        return rtl::mesh_hit_blend(m, rtl::Corner::uvs, st, hits, n, (float *)uvs, err);
     }};
 const HitQuery kHitTexels = {
     "rt_mesh_hit_texels", "hits and texels", false, 1, 12, 15u, "hits must be 16-byte aligned, texels 4-byte aligned",
@@ -143,6 +142,98 @@ int mesh_hit_query(RtContext *c, const HitQuery &q, const char *who, bool host, 
     const size_t N = (size_t)n;
     const StageSeg segs[] = {{hits, N * sizeof(RtHit), false}, {points, q.takesPoints ? N * 12 : 0, false}, {out0, N * q.outBytes, true}, {out1, q.outputs > 1 ? N * q.outBytes : 0, true}};
     return staged(c, who, segs, [&](void *const *d) { return onDevice(d[0], (const float *)d[1], d[2], d[3]); });
+}
+
+// ---- the corner attributes a caller writes (colours 14.14, UVs 14.15): rt_mesh.hip gathers their rows inside every update; this file owns
+// enabling, the ordering of the writes and of the gather alone.  One routine each serves rt_mesh_colors_* and rt_mesh_uvs_*; a CornerApi is what
+// tells them apart.
+struct CornerApi {
+    rtl::Corner which;
+    const char *enable, *accessor, *set, *refresh;   // the entry points
+    const char *noun;                                // in the messages
+    int floats;                                      // per vertex, as the host hands them over
+    size_t stride;                                   // bytes per vertex on the device
+    bool repack;                                     // ... where every vertex is four floats, the last one 0
+    bool (*ok)(float);                               // what a component must be
+    const char *needed;                              // ... and the message behind it
+};
+const CornerApi kColorsApi = {rtl::Corner::colors, "rt_mesh_colors_enable", "rt_mesh_colors", "rt_mesh_set_colors", "rt_mesh_colors_refresh", "colours", 3, 16, true,
+                              [](float x) { return x >= 0.0f && x < INFINITY; }, "finite and >= 0 is needed"};
+const CornerApi kUvsApi = {rtl::Corner::uvs, "rt_mesh_uvs_enable", "rt_mesh_uvs", "rt_mesh_set_uvs", "rt_mesh_uvs_refresh", "UVs", 2, 8, false,
+                           [](float x) { return std::isfinite(x); }, "a finite value is needed"};
+
+int corner_enable(RtContext *c, const CornerApi &a, int on) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", a.enable);
+    (void)hipSetDevice(c->cfg.device);
+    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
+    if (!on) { rtl::mesh_corner_release(c->mesh, a.which); return RT_OK; }
+    if (rtl::mesh_corner_vertices(c->mesh, a.which)) return RT_OK;   // already enabled: the values and the rows stay as they are, nothing is allocated
+    hipStream_t st = api_stream(c);   // rt_stream()
+    const char *err = nullptr;
+    int rc = RT_OK;
+    // (a create that fails behind the order array's launch leaves the array written: the event is recorded either way; rt_mesh_normals_enable too)
+    const int er = with_order_event(c, st, false, false, [&] { rc = rtl::mesh_corner_create(c->mesh, a.which, st, &err); return RT_OK; });
+    if (er != RT_OK) return er;
+    if (rc != RT_OK) return fail(c, rc, "%s: %s", a.enable, err ? err : "allocation failed");
+    return RT_OK;
+}
+
+int corner_accessor(RtContext *c, const CornerApi &a, void **devPtr, size_t *bytes) {
+    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
+    *devPtr = nullptr; *bytes = 0;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first)", a.accessor);
+    if (!rtl::mesh_corner_vertices(c->mesh, a.which)) return fail(c, RT_ERR_INVALID, "%s: %s are not enabled (%s first)", a.accessor, a.noun, a.enable);
+    *devPtr = rtl::mesh_corner_vertices(c->mesh, a.which);
+    *bytes = (size_t)rtl::mesh_verts(c->mesh) * a.stride;
+    return RT_OK;
+}
+
+int corner_set(RtContext *c, const CornerApi &a, const float *values, int first, int count) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh || !rtl::mesh_corner_vertices(c->mesh, a.which)) return fail(c, RT_ERR_INVALID, "%s: no %s (rt_mesh_upload and %s first)", a.set, a.noun, a.enable);
+    const int n = rtl::mesh_verts(c->mesh);
+    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "%s: vertices %d .. %d of %d", a.set, first, first + count, n);
+    if (count == 0) return RT_OK;
+    if (!values) return fail(c, RT_ERR_INVALID, "%s: null %s", a.set, a.noun);
+    const size_t F = (size_t)a.floats;
+    for (size_t i = 0; i < (size_t)count * F; ++i)
+        if (!a.ok(values[i])) return fail(c, RT_ERR_INVALID, "%s: component %zu of vertex %zu is %g (%s)", a.set, i % F, (size_t)first + i / F, (double)values[i], a.needed);
+    return guarded(c, a.set, [&]() -> int {
+        (void)hipSetDevice(c->cfg.device);
+        hipStream_t st = api_stream(c);   // rt_stream()
+        // The source is pageable host memory: the caller's array or, repacked, (r, g, b, 0) per vertex as the device holds them in a buffer of the call's
+        // own.  Either may go when the call returns only because the HIP runtime finishes with pageable host memory -- stages it, or completes the copy
+        // -- before hipMemcpyAsync returns; rt_mesh_set_bones leans on the same.  So the call is ordered on the stream like rt_mesh_set_bones, and like
+        // it may spend the copy's time on the host.
+        std::vector<float> v4;
+        if (a.repack) {
+            v4.resize((size_t)count * 4);
+            for (size_t i = 0; i < (size_t)count; ++i) { v4[4 * i] = values[3 * i]; v4[4 * i + 1] = values[3 * i + 1]; v4[4 * i + 2] = values[3 * i + 2]; v4[4 * i + 3] = 0.0f; }
+        }
+        return between_lanes(c, st, [&]() -> int {   // a gather enqueued on another lane reads the vertex array
+            char *dst = static_cast<char *>(rtl::mesh_corner_vertices(c->mesh, a.which)) + (size_t)first * a.stride;
+            HIP_TRY(c, hipMemcpyAsync(dst, a.repack ? v4.data() : values, (size_t)count * a.stride, hipMemcpyHostToDevice, st));
+            return RT_OK;
+        });
+    });
+}
+
+int corner_refresh(RtContext *c, const CornerApi &a) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->mesh) return fail(c, RT_ERR_INVALID, "%s: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)", a.refresh);
+    if (!rtl::mesh_corner_vertices(c->mesh, a.which)) return fail(c, RT_ERR_INVALID, "%s: %s are not enabled (%s first)", a.refresh, a.noun, a.enable);
+    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "%s: no rows to fill (rt_mesh_rebuild first)", a.refresh);
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t st = api_stream(c);   // rt_stream()
+    // frames and queries on every lane read the rows they were enqueued with, and whatever a lane is given next sees the new ones
+    return between_lanes(c, st, [&] {
+        return with_order_event(c, st, false, false, [&]() -> int {
+            const char *err = nullptr;
+            const int rc = rtl::mesh_corner_refresh(c->mesh, a.which, st, &err);
+            return rc == RT_OK ? RT_OK : fail(c, rc, "%s: %s", a.refresh, err ? err : "launch failed");
+        });
+    });
 }
 
 }  // namespace
@@ -378,7 +469,7 @@ int rt_mesh_normals_enable(RtContext *c, int on) {
     return guarded(c, "rt_mesh_normals_enable", [&]() -> int {
         (void)hipSetDevice(c->cfg.device);
         HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-        if (!on) { rtl::mesh_normals_release(c->mesh); return RT_OK; }
+        if (!on) { rtl::mesh_corner_release(c->mesh, rtl::Corner::normals); return RT_OK; }
         const int nIdx = rtl::mesh_layout(c->mesh).nTris * 3, nVerts = rtl::mesh_verts(c->mesh);
         std::vector<uint32_t> idx((size_t)nIdx);
         HIP_TRY(c, hipMemcpy(idx.data(), rtl::mesh_indices(c->mesh), (size_t)nIdx * 4, hipMemcpyDeviceToHost));
@@ -391,7 +482,7 @@ int rt_mesh_normals_enable(RtContext *c, int on) {
         rtl::normal_fill(plan, idx.data(), nIdx, entries);
         hipStream_t st = api_stream(c);   // rt_stream()
         const char *err = nullptr;
-        // (a create that fails behind the order array's launch leaves the array written: the event is recorded either way)
+        // (recorded behind a create that failed as well: corner_enable)
         const int er = with_order_event(c, st, false, false, [&] { rc = rtl::mesh_normals_create(c->mesh, st, plan.sliceFirst.data(), entries.data(), plan.info, &err); return RT_OK; });
         if (er != RT_OK) return er;
         if (rc != RT_OK) return fail(c, rc, "rt_mesh_normals_enable: %s", err ? err : "allocation failed");
@@ -416,76 +507,11 @@ int rt_mesh_hit_normals_host(RtContext *c, const RtHit *hits, int n, float *norm
     return mesh_hit_query(c, kHitNormals, "rt_mesh_hit_normals_host", true, hits, nullptr, n, normals, nullptr);
 }
 
-// ---- per-vertex colours: rt_mesh.hip gathers the rows inside every update; this file owns enabling, the ordering of colour writes and
-// of the gather alone, and the hit query
-int rt_mesh_colors_enable(RtContext *c, int on) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-    if (!on) { rtl::mesh_colors_release(c->mesh); return RT_OK; }
-    if (rtl::mesh_vertex_colors(c->mesh)) return RT_OK;   // already enabled: the colours and the rows stay as they are, nothing is allocated
-    hipStream_t st = api_stream(c);   // rt_stream()
-    const char *err = nullptr;
-    int rc = RT_OK;
-    // (a create that fails behind the order array's launch leaves the array written: the event is recorded either way)
-    const int er = with_order_event(c, st, false, false, [&] { rc = rtl::mesh_colors_create(c->mesh, st, &err); return RT_OK; });
-    if (er != RT_OK) return er;
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_colors_enable: %s", err ? err : "allocation failed");
-    return RT_OK;
-}
-
-int rt_mesh_colors(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: no mesh (rt_mesh_upload first)");
-    if (!rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors: colours are not enabled (rt_mesh_colors_enable first)");
-    *devPtr = rtl::mesh_vertex_colors(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 16;
-    return RT_OK;
-}
-
-int rt_mesh_set_colors(RtContext *c, const float *rgb3, int first, int count) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh || !rtl::mesh_vertex_colors(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: no colours (rt_mesh_upload and rt_mesh_colors_enable first)");
-    const int n = rtl::mesh_verts(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: vertices %d .. %d of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!rgb3) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: null colours");
-    for (size_t i = 0; i < (size_t)count * 3; ++i)
-        if (!(rgb3[i] >= 0.0f) || !(rgb3[i] < INFINITY)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_colors: component %zu of vertex %zu is %g (finite and >= 0 is needed)", i % 3, (size_t)first + i / 3, (double)rgb3[i]);
-    return guarded(c, "rt_mesh_set_colors", [&]() -> int {
-        (void)hipSetDevice(c->cfg.device);
-        hipStream_t st = api_stream(c);   // rt_stream()
-        // (r, g, b, 0) per vertex as the device holds them, in a buffer of the call's own.  It may go when the call returns only because the HIP runtime
-        // finishes with pageable host memory -- stages it, or completes the copy -- before hipMemcpyAsync returns; rt_mesh_set_bones leans on the same
-        // for the caller's array.  So the call is ordered on the stream like rt_mesh_set_bones, and like it may spend the copy's time on the host.
-        std::vector<float> v4((size_t)count * 4);
-        for (size_t i = 0; i < (size_t)count; ++i) { v4[4 * i] = rgb3[3 * i]; v4[4 * i + 1] = rgb3[3 * i + 1]; v4[4 * i + 2] = rgb3[3 * i + 2]; v4[4 * i + 3] = 0.0f; }
-        return between_lanes(c, st, [&]() -> int {   // a gather enqueued on another lane reads the colours
-            HIP_TRY(c, hipMemcpyAsync(rtl::mesh_vertex_colors(c->mesh) + (size_t)first, v4.data(), (size_t)count * 16, hipMemcpyHostToDevice, st));
-            return RT_OK;
-        });
-    });
-}
-
-int rt_mesh_colors_refresh(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_color_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: colours are not enabled (rt_mesh_colors_enable first)");
-    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_colors_refresh: no rows to fill (rt_mesh_rebuild first)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = api_stream(c);   // rt_stream()
-    // frames and queries on every lane read the rows they were enqueued with, and whatever a lane is given next sees the new ones
-    return between_lanes(c, st, [&] {
-        return with_order_event(c, st, false, false, [&]() -> int {
-            const char *err = nullptr;
-            const int rc = rtl::mesh_colors_refresh(c->mesh, st, &err);
-            return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_colors_refresh: %s", err ? err : "launch failed");
-        });
-    });
-}
-
+// ---- per-vertex colours
+int rt_mesh_colors_enable(RtContext *c, int on) { return corner_enable(c, kColorsApi, on); }
+int rt_mesh_colors(RtContext *c, void **devPtr, size_t *bytes) { return corner_accessor(c, kColorsApi, devPtr, bytes); }
+int rt_mesh_set_colors(RtContext *c, const float *rgb3, int first, int count) { return corner_set(c, kColorsApi, rgb3, first, count); }
+int rt_mesh_colors_refresh(RtContext *c) { return corner_refresh(c, kColorsApi); }
 int rt_mesh_hit_colors(RtContext *c, const RtHit *hits, int n, float *colors) {
     return mesh_hit_query(c, kHitColors, "rt_mesh_hit_colors", false, hits, nullptr, n, colors, nullptr);
 }
@@ -493,71 +519,11 @@ int rt_mesh_hit_colors_host(RtContext *c, const RtHit *hits, int n, float *color
     return mesh_hit_query(c, kHitColors, "rt_mesh_hit_colors_host", true, hits, nullptr, n, colors, nullptr);
 }
 
-// ---- UVs and the albedo texture: rt_mesh.hip gathers the UV rows inside every update, behind the colours'; this file owns enabling,
-// the ordering of UV writes and of the gather alone, the texture's upload and the two hit queries
-int rt_mesh_uvs_enable(RtContext *c, int on) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_enable: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    (void)hipSetDevice(c->cfg.device);
-    HIP_TRY(c, sync_all(c));   // frames in flight read the array that is about to appear or go
-    if (!on) { rtl::mesh_uvs_release(c->mesh); return RT_OK; }
-    if (rtl::mesh_vertex_uvs(c->mesh)) return RT_OK;   // already enabled: the UVs and the rows stay as they are, nothing is allocated
-    hipStream_t st = api_stream(c);   // rt_stream()
-    const char *err = nullptr;
-    int rc = RT_OK;
-    // (a create that fails behind the order array's launch leaves the array written: the event is recorded either way)
-    const int er = with_order_event(c, st, false, false, [&] { rc = rtl::mesh_uvs_create(c->mesh, st, &err); return RT_OK; });
-    if (er != RT_OK) return er;
-    if (rc != RT_OK) return fail(c, rc, "rt_mesh_uvs_enable: %s", err ? err : "allocation failed");
-    return RT_OK;
-}
-
-int rt_mesh_uvs(RtContext *c, void **devPtr, size_t *bytes) {
-    if (!c || !devPtr || !bytes) return RT_ERR_INVALID;
-    *devPtr = nullptr; *bytes = 0;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs: no mesh (rt_mesh_upload first)");
-    if (!rtl::mesh_vertex_uvs(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs: UVs are not enabled (rt_mesh_uvs_enable first)");
-    *devPtr = rtl::mesh_vertex_uvs(c->mesh);
-    *bytes = (size_t)rtl::mesh_verts(c->mesh) * 8;
-    return RT_OK;
-}
-
-int rt_mesh_set_uvs(RtContext *c, const float *uv2, int first, int count) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh || !rtl::mesh_vertex_uvs(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: no UVs (rt_mesh_upload and rt_mesh_uvs_enable first)");
-    const int n = rtl::mesh_verts(c->mesh);
-    if (first < 0 || count < 0 || first > n || count > n - first) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: vertices %d .. %d of %d", first, first + count, n);
-    if (count == 0) return RT_OK;
-    if (!uv2) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: null UVs");
-    for (size_t i = 0; i < (size_t)count * 2; ++i)
-        if (!std::isfinite(uv2[i])) return fail(c, RT_ERR_INVALID, "rt_mesh_set_uvs: component %zu of vertex %zu is %g (a finite value is needed)", i % 2, (size_t)first + i / 2, (double)uv2[i]);
-    return guarded(c, "rt_mesh_set_uvs", [&]() -> int {
-        (void)hipSetDevice(c->cfg.device);
-        hipStream_t st = api_stream(c);   // rt_stream()
-        // the caller's array, pageable memory: staged or copied before hipMemcpyAsync returns, as in rt_mesh_set_bones; ordered like rt_mesh_set_colors
-        return between_lanes(c, st, [&]() -> int {   // a gather enqueued on another lane reads the UVs
-            HIP_TRY(c, hipMemcpyAsync(rtl::mesh_vertex_uvs(c->mesh) + (size_t)first, uv2, (size_t)count * 8, hipMemcpyHostToDevice, st));
-            return RT_OK;
-        });
-    });
-}
-
-int rt_mesh_uvs_refresh(RtContext *c) {
-    if (!c) return RT_ERR_INVALID;
-    if (!c->mesh) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: no mesh (rt_mesh_upload first; rt_upload_bvh releases the mesh)");
-    if (!rtl::mesh_uv_rows(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: UVs are not enabled (rt_mesh_uvs_enable first)");
-    if (!rtl::mesh_has_tree(c->mesh)) return fail(c, RT_ERR_INVALID, "rt_mesh_uvs_refresh: no rows to fill (rt_mesh_rebuild first)");
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t st = api_stream(c);   // rt_stream()
-    // frames and queries on every lane read the rows they were enqueued with, and whatever a lane is given next sees the new ones
-    return between_lanes(c, st, [&] {
-        return with_order_event(c, st, false, false, [&]() -> int {
-            const char *err = nullptr;
-            const int rc = rtl::mesh_uvs_refresh(c->mesh, st, &err);
-            return rc == RT_OK ? RT_OK : fail(c, rc, "rt_mesh_uvs_refresh: %s", err ? err : "launch failed");
-        });
-    });
-}
+// ---- UVs and the albedo texture: beside the UVs' four calls this file owns the texture's upload and the two hit queries
+int rt_mesh_uvs_enable(RtContext *c, int on) { return corner_enable(c, kUvsApi, on); }
+int rt_mesh_uvs(RtContext *c, void **devPtr, size_t *bytes) { return corner_accessor(c, kUvsApi, devPtr, bytes); }
+int rt_mesh_set_uvs(RtContext *c, const float *uv2, int first, int count) { return corner_set(c, kUvsApi, uv2, first, count); }
+int rt_mesh_uvs_refresh(RtContext *c) { return corner_refresh(c, kUvsApi); }
 
 int rt_mesh_texture_upload(RtContext *c, const uint8_t *rgba8, int W, int H, int flags) {
     if (!c) return RT_ERR_INVALID;

@@ -240,21 +240,16 @@ struct Mesh {
     // carries them across in; allocated by mesh_motion_create, not in `owned`
     float4 *dPrevTris = nullptr, *dPrevByInput = nullptr;
     Attachment motion;
-    // smooth normals: the packed vertex -> triangle adjacency, the face vectors by input triangle, one normal per vertex and the
-    // corner normals row for row beside the triangle array; allocated by mesh_normals_create, not in `owned`
+    // the corner attributes, indexed by Corner -- smooth normals, colours, UVs: one value per vertex and the corner values row for row
+    // beside the triangle array, corner_kind's bytes each; allocated by mesh_normals_create and mesh_corner_create, not in `owned`
+    struct CornerArrays { void *vert = nullptr; float4 *rows = nullptr; Attachment mem; };
+    CornerArrays corner[3];
+    // what the normals are computed from: the packed vertex -> triangle adjacency and the face vectors by input triangle; with
+    // the normals' attachment
     uint32_t *dNrmSliceFirst = nullptr;
     int32_t *dNrmEntries = nullptr;
-    float4 *dFaceByInput = nullptr, *dVertNrm = nullptr, *dNrmRows = nullptr;
-    Attachment normals;
-    // per-vertex colours: one colour per vertex and the corner colours row for row beside the triangle array; allocated by
-    // mesh_colors_create, not in `owned`
-    float4 *dVertCol = nullptr, *dColRows = nullptr;
-    Attachment colors;
-    // UVs and the albedo texture: one UV per vertex and the corner UVs row for row beside the triangle array (mesh_uvs_create); the
-    // texels and the decode table behind `tex` (mesh_texture_create); neither in `owned`
-    float2 *dVertUv = nullptr;
-    float4 *dUvRows = nullptr;
-    Attachment uvs;
+    float4 *dFaceByInput = nullptr;
+    // the albedo texture: the texels and the decode table behind `tex` (mesh_texture_create), not in `owned`
     uint32_t *dTexels = nullptr;
     float *dTexTable = nullptr;
     rtuv::Texture tex;   // texels == null: no texture
@@ -470,9 +465,7 @@ void mesh_destroy(Mesh *m) {
     mesh_skin_release(m);
     mesh_morph_release(m);
     mesh_motion_release(m);
-    mesh_normals_release(m);
-    mesh_colors_release(m);
-    mesh_uvs_release(m);
+    for (Corner which : {Corner::normals, Corner::colors, Corner::uvs}) mesh_corner_release(m, which);
     mesh_texture_release(m);
     for (void *p : m->owned) (void)hipFree(p);
     if (m->hStatus) (void)hipHostFree(m->hStatus);
@@ -497,28 +490,15 @@ size_t mesh_scene_bytes(const Mesh *m) { return m->sceneBytes; }
 #define REB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (err) *err = hipGetErrorString(e_); return RT_ERR_HIP; } } while (0)
 
 namespace {
-// smooth normals behind the new rows of an update: the order array first -- a rebuild has just invalidated it -- then the three kernels
-int normals_update(Mesh *m, hipStream_t st, const char **err) {
-    const int *order = nullptr;
-    const int rc = mesh_order(m, st, &order, err);
-    if (rc != RT_OK) return rc;
-    normals_launch_update(st, m->sc.tris, order, m->dIdx, m->lay.nTris, m->dNrmSliceFirst, m->dNrmEntries, m->nVerts, m->dFaceByInput, m->dVertNrm, m->dNrmRows);
-    REB_TRY(hipGetLastError());
-    return RT_OK;
-}
-// the tail of an update behind its new rows: smooth normals, then the colour rows, then the UV rows (DESIGN.md
-// 14.15) under the same order array -- a rebuild moved every input triangle to another row; a refit's gather rewrites what it finds, which is what a
-// caller who also changed colours or UVs wants
+// the tail of an update behind its new rows: the corner attributes that are enabled, in Corner's order and under the same order array --
+// a rebuild moved every input triangle to another row; a refit's gather rewrites what it finds, which is what a caller who also changed colours or
+// UVs wants
 int attributes_update(Mesh *m, hipStream_t st, const char **err) {
-    if (m->dNrmRows) {
-        const int rc = normals_update(m, st, err);
+    for (Corner which : {Corner::normals, Corner::colors, Corner::uvs}) {
+        if (!m->corner[(int)which].rows) continue;
+        const int rc = mesh_corner_refresh(m, which, st, err);
         if (rc != RT_OK) return rc;
     }
-    if (m->dColRows) {
-        const int rc = mesh_colors_refresh(m, st, err);
-        if (rc != RT_OK) return rc;
-    }
-    if (m->dUvRows) return mesh_uvs_refresh(m, st, err);
     return RT_OK;
 }
 // every record form from the bounds and the triangle array, through the tables: the tail of a rebuild and of a refit
@@ -723,102 +703,76 @@ int mesh_hit_prev_points(Mesh *m, hipStream_t st, const void *hits, const float 
     return RT_OK;
 }
 
-void mesh_normals_release(Mesh *m) { detach(m, m->normals); }
+// ---- the corner attributes
+void mesh_corner_release(Mesh *m, Corner which) { detach(m, m->corner[(int)which].mem); }
+
+namespace {
+// The attribute's two arrays, zeroed, behind the blocks its attachment already holds (e: what allocating those gave), the colours' grey fill, the
+// rows at once when there is a tree, and the wait for the device.  A failure releases the attribute.
+int corner_create(Mesh *m, Corner which, hipStream_t st, hipError_t e, const char **err) {
+    Mesh::CornerArrays &a = m->corner[(int)which];
+    const CornerKind &k = corner_kind(which);
+    if (e == hipSuccess) e = attach(m, a.mem, &a.vert, (size_t)m->nVerts * k.vertBytes, Fill::zeros);
+    if (e == hipSuccess) e = attach(m, a.mem, &a.rows, (size_t)m->lay.nTris * k.rowBytes, Fill::zeros);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && which == Corner::colors) { corner_launch_color_fill(st, static_cast<float4 *>(a.vert), m->nVerts); e = hipGetLastError(); }
+    int rc = RT_OK;
+    if (e == hipSuccess && m->permCur >= 0) rc = mesh_corner_refresh(m, which, st, err);
+    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
+    if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_corner_release(m, which); return rc != RT_OK ? rc : RT_ERR_HIP; }
+    return RT_OK;
+}
+}  // namespace
+
+int mesh_corner_create(Mesh *m, Corner which, hipStream_t st, const char **err) {
+    if (which == Corner::normals) return RT_ERR_INVALID;   // (mesh_normals_create: they need their adjacency)
+    mesh_corner_release(m, which);
+    return corner_create(m, which, st, hipSuccess, err);
+}
 
 int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err) {
-    mesh_normals_release(m);
-    const size_t nt = (size_t)m->lay.nTris, nv = (size_t)m->nVerts;
-    Attachment &a = m->normals;
+    mesh_corner_release(m, Corner::normals);
+    Attachment &a = m->corner[(int)Corner::normals].mem;
     hipError_t e = attach(m, a, &m->dNrmSliceFirst, ((size_t)info.nSlices + 1) * 4, Fill::host, sliceFirst);
     if (e == hipSuccess) e = attach(m, a, &m->dNrmEntries, (size_t)info.paddedEntries * 4, Fill::host, entries);
-    if (e == hipSuccess) e = attach(m, a, &m->dFaceByInput, nt * 16, Fill::zeros);
-    if (e == hipSuccess) e = attach(m, a, &m->dVertNrm, nv * 16, Fill::zeros);
-    if (e == hipSuccess) e = attach(m, a, &m->dNrmRows, nt * 48, Fill::zeros);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { if (err) *err = hipGetErrorString(e); mesh_normals_release(m); return RT_ERR_HIP; }
-    if (m->permCur >= 0) {
-        const int rc = normals_update(m, st, err);
-        if (rc == RT_OK) e = hipDeviceSynchronize();
-        if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_normals_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
-    }
+    if (e == hipSuccess) e = attach(m, a, &m->dFaceByInput, (size_t)m->lay.nTris * 16, Fill::zeros);
+    return corner_create(m, Corner::normals, st, e, err);
+}
+
+void *mesh_corner_vertices(const Mesh *m, Corner which) { return m->corner[(int)which].vert; }
+const float4 *mesh_vertex_normals(const Mesh *m) { return static_cast<const float4 *>(m->corner[(int)Corner::normals].vert); }
+const float4 *mesh_normal_rows(const Mesh *m) { return m->corner[(int)Corner::normals].rows; }
+float4 *mesh_vertex_colors(const Mesh *m) { return static_cast<float4 *>(m->corner[(int)Corner::colors].vert); }
+const float4 *mesh_color_rows(const Mesh *m) { return m->corner[(int)Corner::colors].rows; }
+float2 *mesh_vertex_uvs(const Mesh *m) { return static_cast<float2 *>(m->corner[(int)Corner::uvs].vert); }
+const float4 *mesh_uv_rows(const Mesh *m) { return m->corner[(int)Corner::uvs].rows; }
+
+// the gather under the order array -- derived first where a rebuild has just invalidated it -- and, in front of it, the two kernels that recompute the
+// smooth normals from the rows of the triangle array
+int mesh_corner_refresh(Mesh *m, Corner which, hipStream_t st, const char **err) {
+    const Mesh::CornerArrays &a = m->corner[(int)which];
+    if (!a.rows || m->permCur < 0) return RT_ERR_INVALID;
+    const int *order = nullptr;
+    const int rc = mesh_order(m, st, &order, err);
+    if (rc != RT_OK) return rc;
+    if (which == Corner::normals)
+        normals_launch_update(st, m->sc.tris, order, m->lay.nTris, m->dNrmSliceFirst, m->dNrmEntries, m->nVerts, m->dFaceByInput, static_cast<float4 *>(a.vert));
+    corner_kind(which).launchRows(st, order, m->dIdx, a.vert, m->lay.nTris, m->nVerts, a.rows);
+    REB_TRY(hipGetLastError());
     return RT_OK;
 }
 
-const float4 *mesh_vertex_normals(const Mesh *m) { return m->dVertNrm; }
-const float4 *mesh_normal_rows(const Mesh *m) { return m->dNrmRows; }
+int mesh_hit_blend(Mesh *m, Corner which, hipStream_t st, const void *hits, int n, float *values, const char **err) {
+    const CornerKind &k = corner_kind(which);
+    if (!k.launchHitBlend || !m->corner[(int)which].rows || m->permCur < 0) return RT_ERR_INVALID;
+    k.launchHitBlend(st, hits, n, m->corner[(int)which].rows, m->lay.nTris, values);
+    REB_TRY(hipGetLastError());
+    return RT_OK;
+}
 
 int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *normals, const char **err) {
-    if (!m->dNrmRows || m->permCur < 0) return RT_ERR_INVALID;
-    normals_launch_hit_normals(st, hits, n, m->sc.tris, m->dNrmRows, m->lay.nTris, normals);
-    REB_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-void mesh_colors_release(Mesh *m) { detach(m, m->colors); }
-
-int mesh_colors_create(Mesh *m, hipStream_t st, const char **err) {
-    mesh_colors_release(m);
-    hipError_t e = attach(m, m->colors, &m->dVertCol, (size_t)m->nVerts * 16, Fill::zeros);
-    if (e == hipSuccess) e = attach(m, m->colors, &m->dColRows, (size_t)m->lay.nTris * 48, Fill::zeros);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) { colors_launch_fill(st, m->dVertCol, m->nVerts); e = hipGetLastError(); }
-    int rc = RT_OK;
-    if (e == hipSuccess && m->permCur >= 0) rc = mesh_colors_refresh(m, st, err);
-    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
-    if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_colors_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
-    return RT_OK;
-}
-
-float4 *mesh_vertex_colors(const Mesh *m) { return m->dVertCol; }
-const float4 *mesh_color_rows(const Mesh *m) { return m->dColRows; }
-
-int mesh_colors_refresh(Mesh *m, hipStream_t st, const char **err) {
-    if (!m->dColRows || m->permCur < 0) return RT_ERR_INVALID;
-    const int *order = nullptr;
-    const int rc = mesh_order(m, st, &order, err);
-    if (rc != RT_OK) return rc;
-    colors_launch_rows(st, order, m->dIdx, m->dVertCol, m->lay.nTris, m->nVerts, m->dColRows);
-    REB_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *colors, const char **err) {
-    if (!m->dColRows || m->permCur < 0) return RT_ERR_INVALID;
-    colors_launch_hit_colors(st, hits, n, m->dColRows, m->lay.nTris, colors);
-    REB_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-void mesh_uvs_release(Mesh *m) { detach(m, m->uvs); }
-
-int mesh_uvs_create(Mesh *m, hipStream_t st, const char **err) {
-    mesh_uvs_release(m);
-    hipError_t e = attach(m, m->uvs, &m->dVertUv, (size_t)m->nVerts * 8, Fill::zeros);
-    if (e == hipSuccess) e = attach(m, m->uvs, &m->dUvRows, (size_t)m->lay.nTris * 32, Fill::zeros);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    int rc = RT_OK;
-    if (e == hipSuccess && m->permCur >= 0) rc = mesh_uvs_refresh(m, st, err);
-    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
-    if (rc != RT_OK || e != hipSuccess) { if (rc == RT_OK && err) *err = hipGetErrorString(e); mesh_uvs_release(m); return rc != RT_OK ? rc : RT_ERR_HIP; }
-    return RT_OK;
-}
-
-float2 *mesh_vertex_uvs(const Mesh *m) { return m->dVertUv; }
-const float4 *mesh_uv_rows(const Mesh *m) { return m->dUvRows; }
-
-int mesh_uvs_refresh(Mesh *m, hipStream_t st, const char **err) {
-    if (!m->dUvRows || m->permCur < 0) return RT_ERR_INVALID;
-    const int *order = nullptr;
-    const int rc = mesh_order(m, st, &order, err);
-    if (rc != RT_OK) return rc;
-    uvs_launch_rows(st, order, m->dIdx, m->dVertUv, m->lay.nTris, m->nVerts, m->dUvRows);
-    REB_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-int mesh_hit_uvs(Mesh *m, hipStream_t st, const void *hits, int n, float *uvs, const char **err) {
-    if (!m->dUvRows || m->permCur < 0) return RT_ERR_INVALID;
-    uvs_launch_hit_uvs(st, hits, n, m->dUvRows, m->lay.nTris, uvs);
+    if (!mesh_normal_rows(m) || m->permCur < 0) return RT_ERR_INVALID;
+    normals_launch_hit_normals(st, hits, n, m->sc.tris, mesh_normal_rows(m), m->lay.nTris, normals);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -848,8 +802,8 @@ int mesh_texture_create(Mesh *m, const uint8_t *rgba8, int W, int H, uint32_t fl
 const rtuv::Texture *mesh_texture(const Mesh *m) { return m->tex.texels ? &m->tex : nullptr; }
 
 int mesh_hit_texels(Mesh *m, hipStream_t st, const void *hits, int n, float *texels, const char **err) {
-    if (!m->dUvRows || !m->tex.texels || m->permCur < 0) return RT_ERR_INVALID;
-    uvs_launch_hit_texels(st, hits, n, m->dUvRows, m->lay.nTris, m->tex, texels);
+    if (!mesh_uv_rows(m) || !m->tex.texels || m->permCur < 0) return RT_ERR_INVALID;
+    corner_launch_hit_texels(st, hits, n, mesh_uv_rows(m), m->lay.nTris, m->tex, texels);
     REB_TRY(hipGetLastError());
     return RT_OK;
 }

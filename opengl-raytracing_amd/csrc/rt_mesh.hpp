@@ -141,65 +141,63 @@ void motion_launch_gather(hipStream_t st, const float4 *byInput, const int *perm
 void motion_launch_hit_prev_points(hipStream_t st, const void *hits, const float *points, int n, const float4 *tris, const float4 *prevTris, int nTris,
                                    float *prevPoints);
 
-// Smooth vertex normals.  mesh_normals_create: the packed adjacency rt_normal_pack.cpp made of the mesh's own index buffer
-// (sliceFirst: info.nSlices + 1 words; entries: info.paddedEntries words); allocates it, the face vectors by input triangle, the vertex normals
-// (nVerts float4) and nrmRows (nTris rows of three float4, row i beside row i of the triangle array) and, when there is a tree, computes the normals on
-// `st`; allocates, copies and waits for the device; the caller has waited for every lane.  mesh_normals_release: the five arrays freed (callers have
-// synchronised).  While the arrays exist mesh_rebuild and mesh_refit recompute the normals behind their new rows on their stream, inside their own
-// sequence of launches: no allocation, no host wait.
-int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err);
-void mesh_normals_release(Mesh *m);
+// The corner attributes: smooth normals, colours and UVs are each a per-vertex array and a row array, row i beside row i of the triangle
+// array, that holds the three corner values of the row's input triangle.  A kind is what tells them apart (corner_kind: rt_mesh_corner.hip's table,
+// one row per traits type); everything else -- the arrays, the gather behind every update, the gather alone, the blend at a hit, the release -- is one path.
+enum class Corner { normals, colors, uvs };   // the order an update walks them in
+struct CornerKind {
+    size_t vertBytes, rowBytes;   // per vertex (16, 16, 8) and per row (48, 48, 32)
+    // the gather: rows[r] = the corner values of input triangle order[r] (raw device pointers; order: row -> input triangle)
+    void (*launchRows)(hipStream_t st, const int *order, const uint32_t *idx, const void *vert, int nTris, int nVerts, float4 *rows);
+    // the blend at n RtHit records, kChannels floats each; null: the attribute has a query of its own (normals: k_hit_normals)
+    void (*launchHitBlend)(hipStream_t st, const void *hits, int n, const float4 *rows, int nTris, float *values);
+};
+const CornerKind &corner_kind(Corner which);
+// mesh_corner_create (colours and UVs): allocates the vertex array (zeros; colours: every one (0.85, 0.85, 0.85, 0)) and the row array and, when there
+// is a tree, gathers the rows on `st`; allocates and waits for the device; the caller has waited for every lane.  mesh_corner_release: the attribute's
+// arrays freed (callers have synchronised).  While the arrays exist mesh_rebuild and mesh_refit gather the rows again behind their new rows on their
+// stream, inside their own sequence of launches, normals (recomputed first), then colours, then UVs: no allocation, no host wait.
+int mesh_corner_create(Mesh *m, Corner which, hipStream_t st, const char **err);
+void mesh_corner_release(Mesh *m, Corner which);
+void *mesh_corner_vertices(const Mesh *m, Corner which);   // device; null: the attribute is not enabled
+// Enqueues the row gather alone on `st` (deriving the order array first where the tree has none yet; normals: the two kernels that recompute them in
+// front of it).  RT_ERR_INVALID without the arrays or a tree.
+int mesh_corner_refresh(Mesh *m, Corner which, hipStream_t st, const char **err);
+// Enqueues values[i] = the attribute at hit i (rt_hit_colors' out3, rt_hit_uvs' out2) on `st` for n RtHit records (device pointers).  RT_ERR_INVALID
+// without the arrays, without a tree or for normals.
+int mesh_hit_blend(Mesh *m, Corner which, hipStream_t st, const void *hits, int n, float *values, const char **err);
 const float4 *mesh_vertex_normals(const Mesh *m);   // device, nVerts float4 (xyz, w = 0); null: normals are not enabled
 const float4 *mesh_normal_rows(const Mesh *m);      // device, nTris x 3 float4; null: normals are not enabled
+float4 *mesh_vertex_colors(const Mesh *m);          // device, nVerts float4 (rgb, w = 0); null: colours are not enabled
+const float4 *mesh_color_rows(const Mesh *m);       // device, nTris x 3 float4; null: colours are not enabled
+float2 *mesh_vertex_uvs(const Mesh *m);             // device, nVerts float2; null: UVs are not enabled
+const float4 *mesh_uv_rows(const Mesh *m);          // device, nTris x 2 float4, (u0, v0, u1, v1), (u2, v2, 0, 0); null: UVs are not enabled
+
+// Smooth vertex normals: the one attribute a kernel writes.  mesh_normals_create: the packed adjacency rt_normal_pack.cpp made of the
+// mesh's own index buffer (sliceFirst: info.nSlices + 1 words; entries: info.paddedEntries words); allocates it, the face vectors by input triangle and
+// the attribute's two arrays and, when there is a tree, computes the normals and gathers the rows on `st`; allocates, copies and waits for the device;
+// the caller has waited for every lane.  mesh_corner_release frees all five.
+int mesh_normals_create(Mesh *m, hipStream_t st, const uint32_t *sliceFirst, const int32_t *entries, const RtNormalInfo &info, const char **err);
 // Enqueues normals[i] = the shading normal of hit i (rt_hit_normals' out3) on `st` for n RtHit records (device pointers).  RT_ERR_INVALID without the
 // arrays or without a tree.
 int mesh_hit_normals(Mesh *m, hipStream_t st, const void *hits, int n, float *normals, const char **err);
 // rt_mesh_normals.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
-void normals_launch_update(hipStream_t st, const float4 *tris, const int *order, const uint32_t *idx, int nTris, const uint32_t *sliceFirst, const int32_t *entries,
-                           int nVerts, float4 *faceByInput, float4 *vertNrm, float4 *nrmRows);
+void normals_launch_update(hipStream_t st, const float4 *tris, const int *order, int nTris, const uint32_t *sliceFirst, const int32_t *entries, int nVerts,
+                           float4 *faceByInput, float4 *vertNrm);
 void normals_launch_hit_normals(hipStream_t st, const void *hits, int n, const float4 *tris, const float4 *nrmRows, int nTris, float *normals);
 
-// Per-vertex colours.  mesh_colors_create: allocates the vertex colours (nVerts float4, every one (0.85, 0.85, 0.85, 0)) and colRows
-// (nTris rows of three float4, row i beside row i of the triangle array) and, when there is a tree, gathers the rows on `st`; allocates and waits for
-// the device; the caller has waited for every lane.  mesh_colors_release: both arrays freed (callers have synchronised).  While the arrays exist
-// mesh_rebuild and mesh_refit gather the rows again behind their new rows on their stream, inside their own sequence of launches: no allocation, no
-// host wait.
-int mesh_colors_create(Mesh *m, hipStream_t st, const char **err);
-void mesh_colors_release(Mesh *m);
-float4 *mesh_vertex_colors(const Mesh *m);        // device, nVerts float4 (rgb, w = 0); null: colours are not enabled
-const float4 *mesh_color_rows(const Mesh *m);     // device, nTris x 3 float4; null: colours are not enabled
-// Enqueues the row gather alone on `st` (deriving the order array first where the tree has none yet).  RT_ERR_INVALID without the arrays or a tree.
-int mesh_colors_refresh(Mesh *m, hipStream_t st, const char **err);
-// Enqueues colors[i] = the colour of hit i (rt_hit_colors' out3) on `st` for n RtHit records (device pointers).  RT_ERR_INVALID without the arrays or
-// without a tree.
-int mesh_hit_colors(Mesh *m, hipStream_t st, const void *hits, int n, float *colors, const char **err);
-// rt_mesh_colors.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
-void colors_launch_fill(hipStream_t st, float4 *vertCol, int nVerts);
-void colors_launch_rows(hipStream_t st, const int *order, const uint32_t *idx, const float4 *vertCol, int nTris, int nVerts, float4 *colRows);
-void colors_launch_hit_colors(hipStream_t st, const void *hits, int n, const float4 *colRows, int nTris, float *colors);
-
-// UVs and the albedo texture.  mesh_uvs_create: allocates the vertex UVs (nVerts float2, zeros) and uvRows (nTris rows of two float4,
-// (u0, v0, u1, v1), (u2, v2, 0, 0), row i beside row i of the triangle array) and, when there is a tree, gathers the rows on `st`; allocates and waits
-// for the device; the caller has waited for every lane.  While the arrays exist mesh_rebuild and mesh_refit gather the rows again behind the colours'
-// gather, inside their own sequence of launches: no allocation, no host wait.
-int mesh_uvs_create(Mesh *m, hipStream_t st, const char **err);
-void mesh_uvs_release(Mesh *m);
-float2 *mesh_vertex_uvs(const Mesh *m);           // device, nVerts float2; null: UVs are not enabled
-const float4 *mesh_uv_rows(const Mesh *m);        // device, nTris x 2 float4; null: UVs are not enabled
-int mesh_uvs_refresh(Mesh *m, hipStream_t st, const char **err);   // the gather alone, as mesh_colors_refresh
-// The texture: an attachment of its own, the texels (W x H RGBA8) and the 256-float decode table.  mesh_texture_create allocates (a block of the same
-// size is kept), copies both from host memory and waits for the device; the caller has waited for every lane.  mesh_texture: null without one.
+// The albedo texture: an attachment of its own, the texels (W x H RGBA8) and the 256-float decode table.  mesh_texture_create
+// allocates (a block of the same size is kept), copies both from host memory and waits for the device; the caller has waited for every lane.
+// mesh_texture: null without one.
 int mesh_texture_create(Mesh *m, const uint8_t *rgba8, int W, int H, uint32_t flags, const float *table256, const char **err);
 void mesh_texture_release(Mesh *m);
 const rtuv::Texture *mesh_texture(const Mesh *m);
-// Enqueue uvs[i] = the UV of hit i (rt_hit_uvs' out2) / texels[i] = the texture's sample there on `st` for n RtHit records (device pointers).
-// RT_ERR_INVALID without the arrays (the texture, for the second) or without a tree.
-int mesh_hit_uvs(Mesh *m, hipStream_t st, const void *hits, int n, float *uvs, const char **err);
+// Enqueues texels[i] = the texture's sample at the UV of hit i on `st` for n RtHit records (device pointers).  RT_ERR_INVALID without the UVs, the
+// texture or a tree.
 int mesh_hit_texels(Mesh *m, hipStream_t st, const void *hits, int n, float *texels, const char **err);
-// rt_mesh_uvs.hip: the kernels behind plain launch functions (raw device pointers; order: row -> input triangle)
-void uvs_launch_rows(hipStream_t st, const int *order, const uint32_t *idx, const float2 *vertUv, int nTris, int nVerts, float4 *uvRows);
-void uvs_launch_hit_uvs(hipStream_t st, const void *hits, int n, const float4 *uvRows, int nTris, float *uvs);
-void uvs_launch_hit_texels(hipStream_t st, const void *hits, int n, const float4 *uvRows, int nTris, const rtuv::Texture &tex, float *texels);
+// rt_mesh_corner.hip: the two kernels beside the table's
+void corner_launch_color_fill(hipStream_t st, float4 *vertCol, int nVerts);
+void corner_launch_hit_texels(hipStream_t st, const void *hits, int n, const float4 *uvRows, int nTris, const rtuv::Texture &tex, float *texels);
 
 // Quantised form only: enqueue the read of the status word behind the rebuild, wait for `st`, and say whether every node could be quantised.
 int mesh_quantised_ok(Mesh *m, hipStream_t st, bool &ok, const char **err);

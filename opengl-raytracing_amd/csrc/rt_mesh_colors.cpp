@@ -1,5 +1,5 @@
 // rt_mesh_colors.cpp -- per-vertex colours of the dynamic mesh on host arrays: the definitions the device's colour rows
-// (k_color_rows), rt_mesh_hit_colors and the frames' albedo are held to.  Plain C++: no HIP header, links on its own (tests/colors_sanitize.cpp).
+// (k_corner_rows<ColorAttr>), rt_mesh_hit_colors and the frames' albedo are held to.  Plain C++: no HIP header, links on its own (tests/colors_sanitize.cpp).
 // The arithmetic is rt_mesh_colors.hpp's, shared with the device.
 #include <cstdint>
 #include <cstring>

@@ -8,6 +8,8 @@
 #pragma once
 #include <cstdint>
 
+#include "rt_mesh_corner.hpp"
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define RT_MOTION_HD __host__ __device__
 #else
@@ -18,16 +20,10 @@
 
 namespace rtmotion {
 
-RT_MOTION_HD inline bool same_bits(float p, float q) {
-    uint32_t u, v;
-    __builtin_memcpy(&u, &p, 4); __builtin_memcpy(&v, &q, 4);
-    return u == v;
-}
-
 RT_MOTION_HD inline void prev_point(const float *T, const float *P, float a, float b, const float *x, float *prev) {
     bool same = true;
     for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) same = same && same_bits(T[4 * r + c], P[4 * r + c]);
+        for (int c = 0; c < 3; ++c) same = same && rtcorner::same_bits(T[4 * r + c], P[4 * r + c]);
     for (int c = 0; c < 3; ++c) {
         const float d = ((P[c] - T[c]) + (P[4 + c] - T[4 + c]) * a) + (P[8 + c] - T[8 + c]) * b;
         prev[c] = same ? x[c] : x[c] + d;

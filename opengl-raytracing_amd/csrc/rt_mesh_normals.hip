@@ -1,16 +1,16 @@
 // rt_mesh_normals.hip -- smooth vertex normals of the dynamic mesh: recomputed from the rows of the triangle array behind every
-// update, kept per vertex and, row for row beside the triangle array, per corner, and the query that blends them at a hit.  A translation unit of its
-// own for the reason rt_mesh_skin.hip is one: the code objects of the other mesh files stay the machine code they were.  rt_mesh.hip owns the arrays.
+// update, and the query that blends them at a hit.  The gather of the corner rows is the one all corner attributes share (k_corner_rows<NormalAttr>,
+// rt_mesh_corner.hip).  A translation unit of its own for the reason rt_mesh_skin.hip is one: the code objects of the other mesh files stay the
+// machine code they were.  rt_mesh.hip owns the arrays.
 //
-// Three kernels run behind the new rows, a store pass and a per-destination sum pass through an inverted index, so the sums have one fixed order and
-// no atomics:
+// Two kernels run behind the new rows and in front of the gather, a store pass and a per-destination sum pass through an inverted index, so the sums
+// have one fixed order and no atomics:
 //   k_face_vectors    one thread per row: e1 and e2 as two 16-byte loads, cross(e1, e2) as one 16-byte store to faceByInput[order[row]];
 //   k_vertex_normals  one thread per vertex, one wave per slice of the packed adjacency (rt_normal_pack.hpp): the slice's entry range comes from two
 //                     scalar loads and the walk has a wave-uniform trip count; a step is 256 consecutive bytes of triangle numbers per wave and one
 //                     16-byte gather per lane from faceByInput.  The sums form a chain in entry order, but no load depends on them: four steps'
 //                     numbers are loaded, then their four face vectors, before the first is added.  A pad entry gathers face 0 and is dropped by a
-//                     select.  One float4 stored, xyz the normal and w = 0;
-//   k_corner_rows     one thread per row: order[row], three indices, three 16-byte vertex normals, three 16-byte stores to nrmRows.
+//                     select.  One float4 stored, xyz the normal and w = 0.
 // k_hit_normals: one thread per hit -- the 16-byte RtHit, the row (for the fallback) and the row's three corner normals as three 16-byte loads each,
 // issued together, 12 bytes stored.  No LDS, no atomics, no scratch.  The arithmetic is rt_mesh_normals.hpp's, operation for operation.
 #include <algorithm>
@@ -74,21 +74,6 @@ __global__ __launch_bounds__(256) void k_vertex_normals(const uint32_t *__restri
     vertNrm[i] = make_float4(n[0], n[1], n[2], 0.0f);
 }
 
-__global__ __launch_bounds__(256) void k_corner_rows(const int *__restrict__ order, const uint32_t *__restrict__ idx, const float4 *__restrict__ vertNrm, int nTris,
-                                                     int nVerts, float4 *__restrict__ nrmRows) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= nTris) return;
-    const int k = order[r];
-    float4 n0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n1 = n0, n2 = n0;
-    if (k >= 0 && k < nTris) {
-        const uint32_t *ix = idx + (size_t)k * 3;
-        const uint32_t i0 = ix[0], i1 = ix[1], i2 = ix[2];
-        if (i0 < (uint32_t)nVerts && i1 < (uint32_t)nVerts && i2 < (uint32_t)nVerts) { n0 = vertNrm[i0]; n1 = vertNrm[i1]; n2 = vertNrm[i2]; }   // (validated on upload)
-    }
-    float4 *o = nrmRows + (size_t)r * 3;
-    o[0] = n0; o[1] = n1; o[2] = n2;
-}
-
 // A prim outside [0, nTris) -- a miss, an analytic hit, a stale record -- reads neither array and answers zeros.
 __global__ __launch_bounds__(256) void k_hit_normals(const float4 *__restrict__ hits, int n, const float4 *__restrict__ tris, const float4 *__restrict__ nrmRows,
                                                      int nTris, float *__restrict__ normals) {
@@ -114,12 +99,11 @@ inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n +
 
 namespace rtl {
 
-void normals_launch_update(hipStream_t st, const float4 *tris, const int *order, const uint32_t *idx, int nTris, const uint32_t *sliceFirst, const int32_t *entries,
-                           int nVerts, float4 *faceByInput, float4 *vertNrm, float4 *nrmRows) {
+void normals_launch_update(hipStream_t st, const float4 *tris, const int *order, int nTris, const uint32_t *sliceFirst, const int32_t *entries, int nVerts,
+                           float4 *faceByInput, float4 *vertNrm) {
     const int nSlices = (nVerts + 63) / 64;
     hipLaunchKernelGGL(k_face_vectors, dim3(blocks_for((size_t)nTris)), dim3(256), 0, st, tris, order, nTris, faceByInput);
     hipLaunchKernelGGL(k_vertex_normals, dim3(blocks_for((size_t)nVerts)), dim3(256), 0, st, sliceFirst, entries, faceByInput, nTris, nVerts, nSlices, vertNrm);
-    hipLaunchKernelGGL(k_corner_rows, dim3(blocks_for((size_t)nTris)), dim3(256), 0, st, order, idx, vertNrm, nTris, nVerts, nrmRows);
 }
 
 void normals_launch_hit_normals(hipStream_t st, const void *hits, int n, const float4 *tris, const float4 *nrmRows, int nTris, float *normals) {

@@ -1,5 +1,5 @@
 // rt_mesh_normals.hpp -- smooth vertex normals of the dynamic mesh, once, for the host definitions (rt_vertex_normals and
-// rt_hit_normals, rt_normal_pack.cpp), the device kernels (rt_mesh_normals.hip) and the frames (hitNormal, rt_device_shade.hpp).
+// rt_hit_normals, rt_normal_pack.cpp), the device kernels (rt_mesh_normals.hip, rt_mesh_corner.hip) and the frames (hitNormal, rt_device_shade.hpp).
 //
 // A row of the triangle array is [v0 -][e1 -][e2 -].  Its face vector is cross(e1, e2) in rt_device_math.hpp's expression, not normalised, so a vertex
 // sum weights by area; a vertex normal is the sum under normalize's expression, or three +0 where the sum has no direction.  At a hit with barycentrics
@@ -8,6 +8,8 @@
 // products and sums, nothing fused except where cross and dot write an fmaf.
 #pragma once
 #include <cstdint>
+
+#include "rt_mesh_corner.hpp"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define RT_NORMAL_HD __host__ __device__
@@ -18,12 +20,6 @@
 #pragma clang fp contract(off)
 
 namespace rtnormal {
-
-RT_NORMAL_HD inline bool same_bits(float p, float q) {
-    uint32_t u, v;
-    __builtin_memcpy(&u, &p, 4); __builtin_memcpy(&v, &q, 4);
-    return u == v;
-}
 
 // cross and dot of rt_device_math.hpp, operation for operation
 RT_NORMAL_HD inline void cross3(const float *a, const float *b, float *o) {
@@ -56,7 +52,7 @@ RT_NORMAL_HD inline void vertex_normal(const float *S, float *n) {
 // barycentrics), out is untouched and the row's face normal is the answer
 RT_NORMAL_HD inline bool blend_normals(const float *n0, const float *n1, const float *n2, float a, float b, float *out) {
     bool same = true;
-    for (int c = 0; c < 3; ++c) same = same && same_bits(n0[c], n1[c]) && same_bits(n0[c], n2[c]);
+    for (int c = 0; c < 3; ++c) same = same && rtcorner::same_bits(n0[c], n1[c]) && rtcorner::same_bits(n0[c], n2[c]);
     if (same) {
         if (n0[0] == 0.0f && n0[1] == 0.0f && n0[2] == 0.0f) return false;
         out[0] = n0[0]; out[1] = n0[1]; out[2] = n0[2];

@@ -1,5 +1,5 @@
 // rt_mesh_uvs.cpp -- vertex UVs and the albedo texture of the dynamic mesh on host arrays: the definitions the device's UV rows
-// (k_uv_rows), rt_mesh_hit_uvs, rt_mesh_hit_texels and the frames' texel are held to, the sRGB decode table, and the .obj reader that keeps vt.
+// (k_corner_rows<UvAttr>), rt_mesh_hit_uvs, rt_mesh_hit_texels and the frames' texel are held to, the sRGB decode table, and the .obj reader that keeps vt.
 // Plain C++: no HIP header, links on its own (tests/uvs_sanitize.cpp).  The arithmetic is rt_mesh_uvs.hpp's, shared with the device.
 #include <cmath>
 #include <cstdint>

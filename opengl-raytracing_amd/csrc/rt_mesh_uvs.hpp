@@ -1,8 +1,7 @@
 // rt_mesh_uvs.hpp -- vertex UVs and the albedo texture of the dynamic mesh, once, for the host definitions (rt_uv_rows, rt_hit_uvs and
-// rt_sample_texture, rt_mesh_uvs.cpp), the device kernels (rt_mesh_uvs.hip) and the frames (hitAlbedoTex, rt_device_shade.hpp).
+// rt_sample_texture, rt_mesh_uvs.cpp), the device kernels (rt_mesh_corner.hip) and the frames (hitAlbedoTex, rt_device_shade.hpp).
 //
-// A vertex UV is two floats.  At a hit with barycentrics (a, b) the three corner UVs are blended component by component under rtcolor::blend_colors'
-// rule: a component whose three corner values are bit-equal hands that value back bit for bit, non-finite barycentrics give the first corner.
+// A vertex UV is two floats.  At a hit the three corner UVs are blended component by component under rt_mesh_corner.hpp's rule.
 // A texture is W x H RGBA8 texels, row 0 at v = 0, decoded through a 256-entry float table (c / 255, or the sRGB curve: one code path for both) and
 // sampled NEAREST or LINEAR under REPEAT or CLAMP; a LINEAR channel whose four decoded values are bit-equal hands that value back bit for bit -- the
 // four weights do not sum to 1 in float32, and a texture of one value must sample as that value.  fp32, every product and sum rounded on its own,
@@ -11,7 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "rt_mesh_colors.hpp"
+#include "rt_mesh_corner.hpp"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define RT_UV_HD __host__ __device__
@@ -44,15 +43,7 @@ RT_UV_HD inline float unorm8(uint8_t code) {
 }
 
 // the blend of a row's three corner UVs at barycentrics (a, b)
-RT_UV_HD inline void blend_uvs(const float *c0, const float *c1, const float *c2, float a, float b, float *out) {
-    const bool first = !rtcolor::finite_bits(a) || !rtcolor::finite_bits(b);
-    const float w = (1.0f - a) - b;
-    for (int c = 0; c < 2; ++c) {
-        const bool flat = rtcolor::same_bits(c0[c], c1[c]) && rtcolor::same_bits(c0[c], c2[c]);
-        const float m = (c0[c] * w + c1[c] * a) + c2[c] * b;
-        out[c] = (first || flat) ? c0[c] : m;
-    }
-}
+RT_UV_HD inline void blend_uvs(const float *c0, const float *c1, const float *c2, float a, float b, float *out) { rtcorner::blend_corners<2>(c0, c1, c2, a, b, out); }
 
 // One axis of a lookup: the coordinate u on an edge of N texels.  i0, i1: the two texels (equal under NEAREST), f: the weight of i1.
 RT_UV_HD inline int wrap_index(int i, int N, bool clamp) {
@@ -60,7 +51,7 @@ RT_UV_HD inline int wrap_index(int i, int N, bool clamp) {
     return ((i % N) + N) % N;
 }
 RT_UV_HD inline void axis(float u, int N, bool nearest, bool clamp, int &i0, int &i1, float &f) {
-    if (!rtcolor::finite_bits(u)) u = 0.0f;
+    if (!rtcorner::finite_bits(u)) u = 0.0f;
     float s;
     if (clamp) { s = u < 0.0f ? 0.0f : u; s = s > 1.0f ? 1.0f : s; }
     else s = u - __builtin_floorf(u);
@@ -105,7 +96,7 @@ RT_UV_HD inline void sample(const Texture &t, float u, float v, float *out) {
     for (int k = 0; k < 3; ++k) {
         const float t00 = t.table[(c00 >> (8 * k)) & 255u], t10 = t.table[(c10 >> (8 * k)) & 255u];
         const float t01 = t.table[(c01 >> (8 * k)) & 255u], t11 = t.table[(c11 >> (8 * k)) & 255u];
-        const bool flat = rtcolor::same_bits(t00, t10) && rtcolor::same_bits(t00, t01) && rtcolor::same_bits(t00, t11);
+        const bool flat = rtcorner::same_bits(t00, t10) && rtcorner::same_bits(t00, t01) && rtcorner::same_bits(t00, t11);
         const float m = ((t00 * w00 + t10 * w10) + t01 * w01) + t11 * w11;
         out[k] = flat ? t00 : m;
     }

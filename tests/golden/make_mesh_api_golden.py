@@ -1,8 +1,10 @@
 """Records tests/golden/mesh_api_parent.json: what every call of tests/mesh_api_cases.py returns in every state it belongs to -- the return code, the
 text of rt_last_error, what the accessors leave in their outputs.
 
-Run on a GPU against a build of the commit BEFORE the dynamic-mesh API moved to csrc/rt_api_mesh.hip (it uses the exported rt_mesh_* entry points and
-the Renderer methods of that commit only), from the root of that commit's tree with this file and tests/mesh_api_cases.py copied into it:
+Run on a GPU against a build of the commit BEFORE the one that reorganises the dynamic-mesh API (it uses the exported rt_mesh_* entry points and the
+Renderer methods of that commit only), from the root of that commit's tree with this file and tests/mesh_api_cases.py copied into it.  The record
+was made before the API moved to csrc/rt_api_mesh.hip, and again -- the UV and texture cases added, every earlier entry unchanged -- before colours
+and UVs became one corner-attribute path:
 
     python tests/golden/make_mesh_api_golden.py [out.json]
 
@@ -25,9 +27,12 @@ def main():
     record = {state: cases.run(state) for state in cases.STATES}
     for state, calls in record.items():
         for name, got in calls.items():
-            quiet = name.endswith("/n_zero") or name in cases.ACCESSORS
+            quiet = name.endswith("/n_zero") or name in cases.QUIET
             assert quiet or got["rc"] != rt.RT_OK, f"{state}: {name} was not refused"
             assert got.get("untouched", True), f"{state}: {name} wrote to an output"
+    if out.exists():                                                # what an earlier parent recorded stays as it was recorded: a later one only adds
+        for state, calls in json.loads(out.read_text()).items():
+            record.setdefault(state, {}).update(calls)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(record, indent=1, sort_keys=True) + "\n")
     print(f"{sum(len(c) for c in record.values())} records in {len(record)} states -> {out}")

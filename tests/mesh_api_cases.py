@@ -1,5 +1,6 @@
 """The refusals of the dynamic-mesh C API, as one table shared by tests/golden/make_mesh_api_golden.py, which recorded them on the commit
-before the API moved to csrc/rt_api_mesh.hip, and tests/test_gpu_mesh_api_contract.py, which holds the library to that record.
+before the API moved to csrc/rt_api_mesh.hip -- and the UV and texture cases on the commit before colours and UVs became one corner-attribute path --
+and tests/test_gpu_mesh_api_contract.py, which holds the library to that record.
 
 A case is a context state, a raw ctypes call of an exported entry point and what came back: the return code, rt_last_error's text when the call was
 refused, and for the device-pointer accessors what they left in their outputs.  Every call here is refused before any device work, or (n = 0, the
@@ -16,7 +17,7 @@ N_TRIS, PART_FIRST, N_BONES, N_TARGETS = 65, (0, 30, 65), 2, 3   # 65 triangles:
 N_REC = 8                                                         # records in every hit buffer
 SENTINEL = 0x5A
 
-STATES = ("no_mesh", "mesh_no_tree", "tree_features_off", "features_no_tree", "morph_no_skin", "all_on", "released")
+STATES = ("no_mesh", "mesh_no_tree", "tree_features_off", "features_no_tree", "morph_no_skin", "all_on", "released", "uvs_no_texture")
 ALL = STATES
 
 
@@ -46,6 +47,11 @@ def morph(nv):
     return rt.morph_targets_from_dense(d)
 
 
+def texture():
+    """3 x 5 texels, every byte its own."""
+    return np.random.default_rng(35).integers(0, 256, (5, 3, 4)).astype(np.uint8)
+
+
 def enter(r, state):
     """Brings the fresh Renderer r into `state`."""
     v, f = mesh()
@@ -61,7 +67,11 @@ def enter(r, state):
         r.mesh_motion_enable()
         r.mesh_normals_enable()
         r.mesh_colors_enable()
-    if state in ("tree_features_off", "all_on", "released"):
+        r.mesh_uvs_enable()
+        r.mesh_texture_upload(texture())
+    if state == "uvs_no_texture":                                   # a tree and UVs: what rt_mesh_hit_texels still lacks is the texture
+        r.mesh_uvs_enable()
+    if state in ("tree_features_off", "all_on", "released", "uvs_no_texture"):
         r.mesh_rebuild_parts()
     if state == "released":
         r.upload_bvh(np.zeros((0, 12), f32), np.zeros((0, 12), f32))
@@ -88,7 +98,7 @@ class Buffers:
         return all(bool((o == SENTINEL).all()) for o in self.h_out) and all(bool((o == SENTINEL).all().item()) for o in self.d_out)
 
 
-QUERIES = ("parts", "prev_points", "normals", "colors")
+QUERIES = ("parts", "prev_points", "normals", "colors", "uvs", "texels")
 HIT_VARIANTS = ("n_negative", "null_hits", "null_outputs", "null_points", "n_zero", "hits_misaligned", "output_misaligned")
 
 
@@ -123,8 +133,9 @@ def _hit_call(query, host, variant):
     return call
 
 
-ACCESSORS = ("rt_mesh_part_matrices", "rt_mesh_positions", "rt_mesh_vertex_normals", "rt_mesh_colors", "rt_mesh_bones", "rt_mesh_rest_positions",
-             "rt_mesh_morph_base", "rt_mesh_morph_weights")
+ACCESSORS = ("rt_mesh_part_matrices", "rt_mesh_positions", "rt_mesh_vertex_normals", "rt_mesh_colors", "rt_mesh_uvs", "rt_mesh_bones",
+             "rt_mesh_rest_positions", "rt_mesh_morph_base", "rt_mesh_morph_weights")
+QUIET = ACCESSORS + ("rt_mesh_texture",)                          # calls that succeed where there is something to hand out: they do no device work
 
 
 def _accessor(name):
@@ -137,12 +148,23 @@ def _accessor(name):
     return call
 
 
+def _texture(L, h, b):
+    ptr, n, w, t = C.c_void_p(0xDEAD0), C.c_size_t(12345), C.c_int(77), C.c_int(88)
+    rc = L.rt_mesh_texture(h, C.byref(ptr), C.byref(n), C.byref(w), C.byref(t))
+    if rc == rt.RT_OK:
+        return rc, {"null": not ptr.value, "bytes": n.value, "size": [w.value, t.value]}
+    return rc, {"cleared": [not ptr.value, n.value == 0, w.value == 0, t.value == 0]}
+
+
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 _M = np.tile(np.eye(4, dtype=f32).reshape(-1), 4)
 _ONES = np.ones(64, f32)
+_NEGATIVE = np.array([0.5, -0.25, 0.5], f32)                      # one colour, its green negative
+_NOT_FINITE = np.array([0.5, 0.25, 0.5, np.inf], f32)             # two UVs, the second one's v infinite
+_TEXELS = texture()
 _NOT_TREE = ("no_mesh", "mesh_no_tree", "features_no_tree", "morph_no_skin", "released")
 _NOT_ALL_ON = tuple(s for s in STATES if s != "all_on")
 
@@ -161,9 +183,16 @@ CALLS.update({
     "rt_mesh_set_bones/past_the_table": (lambda L, h, b: (L.rt_mesh_set_bones(h, 1, N_BONES, _fp(_M)), {}), ALL),
     "rt_mesh_set_morph_weights/past_the_table": (lambda L, h, b: (L.rt_mesh_set_morph_weights(h, N_TARGETS + 1, 0, _fp(_ONES)), {}), ALL),
     "rt_mesh_set_colors/past_the_table": (lambda L, h, b: (L.rt_mesh_set_colors(h, _fp(_ONES), N_TRIS + 2, 1), {}), ALL),
+    "rt_mesh_set_colors/negative": (lambda L, h, b: (L.rt_mesh_set_colors(h, _fp(_NEGATIVE), 5, 1), {}), ALL),
+    "rt_mesh_set_uvs/past_the_table": (lambda L, h, b: (L.rt_mesh_set_uvs(h, _fp(_ONES), N_TRIS + 2, 1), {}), ALL),
+    "rt_mesh_set_uvs/not_finite": (lambda L, h, b: (L.rt_mesh_set_uvs(h, _fp(_NOT_FINITE), 3, 2), {}), ALL),
     "rt_mesh_set_part_matrices/past_the_table": (lambda L, h, b: (L.rt_mesh_set_part_matrices(h, 1, len(PART_FIRST) - 1, _fp(_M)), {}), ALL),
     "rt_mesh_motion_latch": (lambda L, h, b: (L.rt_mesh_motion_latch(h), {}), _NOT_ALL_ON),
     "rt_mesh_colors_refresh": (lambda L, h, b: (L.rt_mesh_colors_refresh(h), {}), _NOT_ALL_ON),
+    "rt_mesh_uvs_refresh": (lambda L, h, b: (L.rt_mesh_uvs_refresh(h), {}), tuple(s for s in _NOT_ALL_ON if s != "uvs_no_texture")),
+    "rt_mesh_texture": (_texture, ALL),
+    "rt_mesh_texture_upload/zero_width": (lambda L, h, b: (L.rt_mesh_texture_upload(h, _TEXELS.ctypes.data, 0, 5, 0), {}), ALL),
+    "rt_mesh_texture_upload/unknown_flags": (lambda L, h, b: (L.rt_mesh_texture_upload(h, _TEXELS.ctypes.data, 3, 5, 8), {}), ALL),
     "rt_mesh_skin": (lambda L, h, b: (L.rt_mesh_skin(h), {}), ("no_mesh", "mesh_no_tree", "tree_features_off", "morph_no_skin", "released")),
     "rt_mesh_morph/destination_7": (lambda L, h, b: (L.rt_mesh_morph(h, 7), {}), ALL),
     "rt_mesh_morph/to_rest": (lambda L, h, b: (L.rt_mesh_morph(h, rt.RT_MORPH_TO_REST), {}), ("no_mesh", "mesh_no_tree", "tree_features_off", "morph_no_skin", "released")),

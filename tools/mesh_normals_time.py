@@ -4,7 +4,7 @@
 
 Per size (the bench mesh -- bunny stand-in, 81 920 triangles -- and the 1 M-triangle scene), in one process and on one context, device time between
 events recorded on the library stream around the call, the positions rewritten before every step:
-  - rt_mesh_refit and rt_mesh_rebuild with normals disabled, then enabled: the difference is k_face_vectors + k_vertex_normals + k_corner_rows (and,
+  - rt_mesh_refit and rt_mesh_rebuild with normals disabled, then enabled: the difference is k_face_vectors + k_vertex_normals + k_corner_rows<NormalAttr> (and,
     behind a rebuild, the order array the rebuild derives for itself).  Run the tool under a kernel trace (rocprofv3 --kernel-trace --stats -- python
     tools/mesh_normals_time.py --frames 0) for the three kernels one by one;
   - rt_mesh_hit_normals on the hits of a 1920 x 1080 pick, device tensors.

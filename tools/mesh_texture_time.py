@@ -4,7 +4,7 @@
 
 Per size (the bench mesh -- bunny stand-in, 81 920 triangles -- and the 1 M-triangle scene), in one process and on one context, device time between
 events recorded on the library stream around the call, the positions rewritten before every step:
-  - rt_mesh_refit and rt_mesh_rebuild with UVs disabled, then enabled (random UVs): the difference is k_uv_rows (and the order array, which a
+  - rt_mesh_refit and rt_mesh_rebuild with UVs disabled, then enabled (random UVs): the difference is k_corner_rows<UvAttr> (and the order array, which a
     rebuild, and the first refit behind one, derives for itself);
   - rt_mesh_uvs_refresh, the gather alone;
   - rt_mesh_hit_texels on the hits of a 1920 x 1080 pick under a 1024 x 1024 texture (LINEAR, REPEAT), device tensors.

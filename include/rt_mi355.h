@@ -992,6 +992,34 @@ typedef struct RtWavePlan {
  * the hit count is known; else the plan behind its read-back (ignored under RT_CHUNKS_FROM_SLOTS).  share: the share of (hit, sample) pairs whose bounce
  * ray hit in earlier launch sets, 0 = nothing known.  RT_ERR_UNSUPPORTED (message: rt_last_error(NULL)) for a chunk of 2^31 queue entries or more. */
 int rt_debug_wave_plan(uint64_t slots, int spp, int aoRays, const RtWaveOptions *opt, int64_t hits, double share, RtWavePlan *out);
+/* Diagnostics, host side (no GPU needed, no context): the k_trace build a traversal launch chooses (csrc/rt_trace_build.cpp) -- the other
+ * half of what a frame decides before it launches, for checks.  RtTraceOptions: the switches of the environment that choose a build, as tune_from_env reads
+ * them (RT_TRACE_TIMING, RT_COOP, RT_NEAR_FIRST, RT_QNODES, RT_FUSED, RT_IMPLICIT, RT_LEAFB, RT_LEAFB_CLOSEST). */
+typedef struct RtTraceOptions { int32_t timing, coop, nearFirst, qnodes, fused, impl, leafb, leafbClosest; } RtTraceOptions;
+typedef struct RtTraceCase {
+    RtTraceOptions opt;
+    int32_t any;                          /* any-hit launch (else closest-hit) */
+    int32_t stats;                        /* the launch was given sums to add to: a frame's launch under RT_TRACE_STATS / RT_TRACE_TIMING */
+    int32_t depth;                        /* of the binary tree (RtSceneInfo.treeDepth) */
+    int32_t anyStack;                     /* RtPackInfo.anyStack; 0: not known */
+    int32_t q4, wF, iN2, iN4, iQ4;        /* the scene has the record form (RT_SCENE_ARRAY_QNODES4, _FUSED, _IMPL_NODES2, _IMPL_NODES4, _IMPL_QNODES4 are not empty) */
+    int32_t reserved;
+} RtTraceCase;
+enum { RT_TRACE_NODES_WNODESW = 0, RT_TRACE_NODES_WF = 1, RT_TRACE_NODES_IN2 = 2, RT_TRACE_NODES_W4 = 3, RT_TRACE_NODES_Q4 = 4, RT_TRACE_NODES_IN4 = 5,
+       RT_TRACE_NODES_IQ4 = 6 };
+typedef struct RtTraceBuild {
+    uint32_t opt;                         /* RT_BUILD_LEAFB4 .. RT_BUILD_TIMING, unshifted, without RT_BUILD_LAUNCHED */
+    int32_t nodes;                        /* RT_TRACE_NODES_*: the node array walked */
+    int32_t implPairs, implLeafBoxes;     /* the implicit pair records / leaf boxes are read */
+    int32_t stack;                        /* stack entries per lane */
+    int32_t reserved;
+    uint64_t ldsBytes;                    /* dynamic LDS per workgroup */
+} RtTraceBuild;
+/* rt_debug_trace_options: the switches of the environment.  rt_debug_trace_build: out[i] = the choice for cases[i], i < n.  rt_debug_trace_builds: the k_trace
+ * builds the library holds for a hit kind (their `opt`), at most `capacity` of them into out (NULL: none); returns their number. */
+int rt_debug_trace_options(RtTraceOptions *out);
+int rt_debug_trace_build(const RtTraceCase *cases, int64_t n, RtTraceBuild *out);
+int rt_debug_trace_builds(int any, uint32_t *out, int capacity);
 /* Diagnostics, host side (no GPU needed, no context): the arithmetic the shading stages do without a division, as the host compiles it.
  * rt_debug_eval ops 10 (texel decode of code a) and 11 (halton(a, b)) evaluate the same functions on the device.
  *   rt_debug_texel_unorm8: out256[c] = the value the cube-map lookup gives texel code c (c / 255.0f, computed without the division).

@@ -439,6 +439,9 @@ SIGNATURES = {
     "rt_refit_bvh": (C.c_int, [_FP, C.c_int, C.POINTER(C.c_int32), _FP, C.c_int, _FP]),
     "rt_bvh_cost": (C.c_int, [_FP, C.c_int, C.POINTER(RtBvhCost)]),
     "rt_debug_wave_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),   # RtWaveOptions, RtWavePlan: _wave_plan_types
+    "rt_debug_trace_options": (C.c_int, [C.c_void_p]),                          # RtTraceOptions, RtTraceCase, RtTraceBuild: _trace_build_types
+    "rt_debug_trace_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rt_debug_trace_builds": (C.c_int, [C.c_int, _U32P, C.c_int]),
     "rt_debug_pack_scene": (C.c_int, [_FP, C.c_int, _FP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_debug_morph_pack": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _U32P, _FP, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_debug_texel_unorm8": (C.c_int, [_FP]),
@@ -1120,6 +1123,74 @@ def wave_plan(slots, spp, ao_rays=0, *, hits=None, share=0.0, **options):
     scalars = {n: int(getattr(out, n)) for n in ("slots", "perHit", "chBudget", "ch", "room", "q2Entries", "spp", "ao", "S1", "S2", "L1", "nChunks")}
     return types.SimpleNamespace(**scalars, deferred=bool(out.deferred), options={n: int(getattr(out.options, n)) for n, _ in RtWaveOptions._fields_ if n != "reserved"},
                                  frame=arena(out.frame), rays=arena(out.rays), results=arena(out.results))
+
+
+# ---- the k_trace build a traversal launch chooses (no context, no GPU; csrc/rt_trace_build.cpp) ----
+
+TRACE_OPTIONS = ("timing", "coop", "nearFirst", "qnodes", "fused", "impl", "leafb", "leafbClosest")   # RtTraceOptions
+TRACE_FORMS = ("q4", "wF", "iN2", "iN4", "iQ4")                                                        # the optional record forms of a scene (RtTraceCase)
+TRACE_NODES = ("wnodesW", "wF", "iN2", "w4", "q4", "iN4", "iQ4")                                       # RT_TRACE_NODES_*
+
+
+@functools.lru_cache(maxsize=None)
+def _trace_build_types():
+    """RtTraceCase and RtTraceBuild as numpy record types, declared at the first call and not at import (see _wave_plan_types)."""
+    case = np.dtype([(n, np.int32) for n in TRACE_OPTIONS + ("any", "stats", "depth", "anyStack") + TRACE_FORMS + ("reserved",)])
+    build = np.dtype([("opt", np.uint32), ("nodes", np.int32), ("implPairs", np.int32), ("implLeafBoxes", np.int32), ("stack", np.int32), ("reserved", np.int32),
+                      ("ldsBytes", np.uint64)])
+    assert case.itemsize == 72 and build.itemsize == 32
+    return case, build
+
+
+def trace_options() -> dict:
+    """The switches of the environment that choose a k_trace build, as a context reads them (rt_debug_trace_options)."""
+    out = np.zeros(len(TRACE_OPTIONS), np.int32)
+    rc = lib().rt_debug_trace_options(out.ctypes.data)
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_trace_options")
+    return dict(zip(TRACE_OPTIONS, (int(v) for v in out)))
+
+
+def trace_builds_kept(any_hit) -> tuple:
+    """The k_trace builds the library holds for closest-hit (any_hit false) or any-hit launches: their option bits, unshifted (rt_debug_trace_builds)."""
+    out = np.zeros(64, np.uint32)
+    n = lib().rt_debug_trace_builds(1 if any_hit else 0, out.ctypes.data_as(_U32P), out.size)
+    return tuple(int(v) for v in out[:n])
+
+
+def trace_build_cases(cases) -> np.ndarray:
+    """rt_debug_trace_build over an array of RtTraceCase records (dtype: _trace_build_types()[0]) -> the RtTraceBuild records, one per case."""
+    case, build = _trace_build_types()
+    cases = np.ascontiguousarray(cases, dtype=case)
+    out = np.zeros(cases.shape[0], build)
+    rc = lib().rt_debug_trace_build(cases.ctypes.data, cases.shape[0], out.ctypes.data)
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_trace_build")
+    return out
+
+
+def trace_build(any_hit, *, depth, stats=False, any_stack=0, forms=(), **options):
+    """The k_trace build a traversal launch chooses, without a context or a GPU (rt_debug_trace_build).  any_hit: an any-hit launch; depth: the
+    binary tree's depth; stats: the launch adds to diagnostic sums (a frame's under RT_TRACE_STATS / RT_TRACE_TIMING); any_stack: RtPackInfo.anyStack; forms:
+    the optional record forms the scene has, names of TRACE_FORMS; options: fields of RtTraceOptions by name over the defaults -- with none given the
+    options come from the environment, as a context reads them.
+    -> namespace: opt (RT_BUILD_* bits, unshifted), bits (their names, as Renderer.debug_builds spells them), nodes (the array walked, a name of
+    TRACE_NODES), implPairs, implLeafBoxes, stack, ldsBytes."""
+    case, _ = _trace_build_types()
+    c = np.zeros(1, case)
+    opt = {**dict(timing=0, coop=0, nearFirst=0, qnodes=-1, fused=0, impl=0, leafb=2, leafbClosest=2), **options} if options else trace_options()
+    if set(opt) != set(TRACE_OPTIONS):
+        raise TypeError(f"trace_build: unknown option {sorted(set(opt) - set(TRACE_OPTIONS))}")
+    if set(forms) - set(TRACE_FORMS):
+        raise TypeError(f"trace_build: unknown record form {sorted(set(forms) - set(TRACE_FORMS))}")
+    for k, v in opt.items():
+        c[k] = int(v)
+    for k in forms:
+        c[k] = 1
+    c["any"], c["stats"], c["depth"], c["anyStack"] = bool(any_hit), bool(stats), int(depth), int(any_stack)
+    b = trace_build_cases(c)[0]
+    return types.SimpleNamespace(opt=int(b["opt"]), bits=frozenset(n for n, v in RT_BUILD_BITS.items() if int(b["opt"]) & v), nodes=TRACE_NODES[int(b["nodes"])],
+                                 implPairs=bool(b["implPairs"]), implLeafBoxes=bool(b["implLeafBoxes"]), stack=int(b["stack"]), ldsBytes=int(b["ldsBytes"]))
 
 
 # ---- the shading stages' division-free arithmetic, as the host compiles it (no context, no GPU; DESIGN.md 4.2) ----

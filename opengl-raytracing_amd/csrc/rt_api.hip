@@ -1171,8 +1171,10 @@ static int debug_trace_wave(RtContext *c, int kind, const float *origins, const 
          hipMemcpy(dF, host, sizeof(DevFrame), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { freeAll(); return fail(c, RT_ERR_HIP, "rt_debug_trace: allocation / upload failed"); }
     if (host->sc.rootBox) hipLaunchKernelGGL(k_frame_root_box, dim3(1), dim3(64), 0, c->stream, dF);
-    c->debugBuilds |= packets ? rt_wave_debug_packets(c->stream, c->cus, c->treeDepth, dF, host->sc, dO, dD, dT, dCnt, (uint32_t)P, dOcc, dHeads)
-                              : rt_wave_debug_trace(c->stream, c->cus, c->treeDepth, dF, host->sc, any, dO, dD, dT, dCnt, un, dOutT, dTri, dOcc, dHeads);
+    const uint32_t built = packets ? rt_wave_debug_packets(c->stream, c->cus, c->treeDepth, dF, host->sc, dO, dD, dT, dCnt, (uint32_t)P, dOcc, dHeads)
+                                   : rt_wave_debug_trace(c->stream, c->cus, c->treeDepth, dF, host->sc, any, dO, dD, dT, dCnt, un, dOutT, dTri, dOcc, dHeads);
+    if (!built) { (void)sync_all(c); freeAll(); return fail(c, RT_ERR_UNSUPPORTED, "rt_debug_trace: the library holds no k_trace build for the chosen options"); }
+    c->debugBuilds |= built;
     std::vector<float> t((size_t)n);
     std::vector<int> tri((size_t)n);
     std::vector<uint8_t> occ((size_t)n);
@@ -1259,9 +1261,10 @@ int rt_trace_rays(RtContext *c, int kind, const float *origins, int originStride
     const int br = query_begin(c, st);
     if (br != RT_OK) return br;
     const DevScene sc = make_dev_scene(c);
-    (void)rt_wave_trace_query(st, c->cus, c->treeDepth, c->dQueryFrame, sc, kind == RT_QUERY_ANY, origins, originStride, dirs, dirStride, tMax, eps, inf, (uint32_t)n,
-                              hits, normals, occluded, c->dQueryHeads);
-    return query_end(c, st);
+    const uint32_t built = rt_wave_trace_query(st, c->cus, c->treeDepth, c->dQueryFrame, sc, kind == RT_QUERY_ANY, origins, originStride, dirs, dirStride, tMax, eps, inf,
+                                               (uint32_t)n, hits, normals, occluded, c->dQueryHeads);
+    const int end = query_end(c, st);
+    return end != RT_OK || built ? end : fail(c, RT_ERR_UNSUPPORTED, "rt_trace_rays: the library holds no k_trace build for the chosen options");
 }
 
 int rt_trace_rays_host(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
@@ -1327,8 +1330,9 @@ static int scene_query(RtContext *c, const char *what, const RtUniforms *u, int 
     r.hits = any ? nullptr : reinterpret_cast<float4 *>(hits);
     r.objects = any ? nullptr : objects; r.normals = any ? nullptr : normals; r.points = any ? nullptr : points; r.occ = any ? occluded : nullptr;
     rt_scene_query_analytic(st, *u, sc, flags, r, c->dQueryFrame, c->dQueryHeads);
-    if (mesh) (void)rt_wave_trace_scene(st, c->cus, c->treeDepth, c->dQueryFrame, sc, u->useBVH == RT_SCENE_HYBRID, r, u->inf, c->dQueryHeads);
-    return query_end(c, st);
+    const uint32_t built = mesh ? rt_wave_trace_scene(st, c->cus, c->treeDepth, c->dQueryFrame, sc, u->useBVH == RT_SCENE_HYBRID, r, u->inf, c->dQueryHeads) : 1u;
+    const int end = query_end(c, st);
+    return end != RT_OK || built ? end : fail(c, RT_ERR_UNSUPPORTED, "scene query: the library holds no k_trace build for the chosen options");
 }
 
 int rt_trace_scene_rays(RtContext *c, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,

@@ -515,8 +515,9 @@ int rt_hybrid_render(RtHybrid *h, RtContext *ctx, hipStream_t st, const DevFrame
                 rt_stage_end(ctx, ST_COMBINE, 2, st);
                 H_TRY(hipMemsetAsync(h->heads, 0, rt_wave_head_words() * sizeof(uint32_t), st));
                 rt_stage_begin(ctx, ST_TRACE_GI, st);
-                rt_wave_trace_closest_compact(st, h->cus, treeDepth, dFrame, host.sc, hb.qO, hb.qD, hb.qDst, &h->cnt[C_REC * kCnt], &h->cnt[C_FLAGS * kCnt], hb.capQ, hb.logT, hb.logTri, h->heads, h->check ? hb.capL : 0u);
+                const uint32_t built = rt_wave_trace_closest_compact(st, h->cus, treeDepth, dFrame, host.sc, hb.qO, hb.qD, hb.qDst, &h->cnt[C_REC * kCnt], &h->cnt[C_FLAGS * kCnt], hb.capQ, hb.logT, hb.logTri, h->heads, h->check ? hb.capL : 0u);
                 rt_stage_end(ctx, ST_TRACE_GI, 1, st);
+                if (!built) { h->err = "hybrid: the library holds no k_trace build for the chosen options"; return RT_ERR_UNSUPPORTED; }
                 h->launches++;
                 // the threads that recorded check their speculation; who failed is packed into the next pass's list
                 H_TRY(hipMemsetAsync(h->cnt + C_TODO * kCnt, 0, sizeof(uint32_t), st));

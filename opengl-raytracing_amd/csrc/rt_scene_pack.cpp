@@ -294,7 +294,7 @@ int ref_of4(const std::vector<float> &w4, size_t node, int i) {
 // an inner box may be any box that contains them, and the slab arithmetic is monotonic in the box, so a decoded box that is checked HERE, in the very
 // float expression the kernel decodes with (fmaf(q, 2^e, origin)), to contain the child's box passes whenever the child's does.  A leaf child passes
 // the quantised test first and its exact box -- kept in `leafBox`, indexed from the leaf's first pair record (below) -- in the leaf phase.
-// Built (and walked, rt_wave.hip launch_trace) when the 112-byte nodes outgrow one XCD's 4 MB L2 (kQNodesAbove): the decode costs 48 VALU operations per
+// Built (and walked: rt_trace_build.cpp trace_build, rt_trace.hpp launch_trace) when the 112-byte nodes outgrow one XCD's 4 MB L2 (kQNodesAbove): the decode costs 48 VALU operations per
 // visit and a wave per SIMD, which a cache-resident tree does not earn back -- any-hit launch per frame, exact / quantised nodes, one launch set in flight:
 // 20 k triangles 0.57 / 0.63-0.66 ms, 82 k (bench mesh, 0.6 MB of nodes) 0.66 / 0.74, 328 k (2.4 MB) 0.81 / 0.83-0.84, 1 M (9.8 MB) 15.9 / 13.6
 // (profiles/r04_experiments.txt 19).  RT_QNODES=0 / 2 forces either.

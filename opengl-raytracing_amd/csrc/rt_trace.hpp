@@ -5,8 +5,14 @@
 #include <algorithm>
 #include <map>
 #include <tuple>
+#include <utility>
 
+#include "rt_trace_build.hpp"
 #include "rt_trace_src.hpp"
+
+using rtl::TraceTune;   // the scheduler's tunables and the switches of the environment: plain C++ (rt_trace_build.hpp), and k_trace's argument
+using rtl::default_tune;
+using rtl::tune_from_env;
 
 namespace {
 // hipcc sinks loads into the branches that first use them (e.g. a triangle's v0 behind the determinant test), which turns
@@ -91,43 +97,6 @@ RT_DEV uint32_t quad_distinct(uint32_t key) {
 }
 
 
-// Tunables of the scheduler (overridable per context through RT_REFILL_MIN / RT_MIN_SEARCH for experiments).
-struct TraceTune { int refillMin; int minSearch; int chunk; int leafb; int skipTraversal; int quadRefill; int coop; int leafbClosest; int nearFirst; int reverse; int guided; int chunkMax; int denseTake; int qnodes; int fused; int impl; int timing; };   // skipTraversal: diagnostic (RT_DEBUG_SKIP_TRAVERSAL)
-// fused (RT_FUSED=1, measured option of round 5, off): closest-hit launches walk the fused records (DevScene::wF) when rt_upload_bvh built them -- the reference's
-// visiting order in half the dependent round trips (bounce rays: 20.6 -> 11.2 steps, primary 17.1 -> 9.7), bit-identical, and 3-4 % SLOWER in every mode (batched,
-// frame by frame, one rank of eight): the same number of 16-byte lane-loads per ray, and that number -- not the length of the dependency chain -- is what these
-// launches cost (profiles/r05_experiments.txt 1)
-static TraceTune default_tune() {
-    TraceTune t{32, 16, 0, 2, 0, 0, 0, 2, 0, 1, 0, 768, 1, -1, 0, 0, 0};
-    if (const char *e = getenv("RT_TRACE_TIMING")) t.timing = atoi(e);
-    // impl (RT_IMPLICIT=1, measured option of round 5, off): closest-hit launches walk 48-byte records WITHOUT child references (three loads per node visit instead of
-    // four) when every leaf of the tree sits at one depth (rt_upload_bvh) -- bit-identical, 25 % fewer node loads, and no faster (bounce launch 0.615 -> 0.628 ms per
-    // frame, primary 0.253 -> 0.259): together with `fused` the second half of the finding that neither the loads nor the dependent steps of these launches can be
-    // removed for time while their vector instructions stay (profiles/r05_experiments.txt 2)
-    if (const char *e = getenv("RT_IMPLICIT")) t.impl = atoi(e);
-    if (const char *e = getenv("RT_FUSED")) t.fused = atoi(e);
-    return t;
-}
-// default_tune() with the scheduler and kernel-build options of the environment: what a context's frames launch (rt_wave_create) and what rt_debug_trace
-// kinds 2 - 4 launch (rt_wave_debug_trace / rt_wave_debug_packets), so that the per-ray tests walk the build a frame walks under the same environment.
-// RT_DEBUG_SKIP_TRAVERSAL is not read here: it skips the work, and only frames take it.
-static TraceTune tune_from_env() {
-    TraceTune t = default_tune();
-    if (const char *e = getenv("RT_REFILL_MIN")) t.refillMin = std::max(1, std::min(64, atoi(e)));
-    if (const char *e = getenv("RT_CHUNK")) { int v = atoi(e); t.chunk = v <= 0 ? 0 : std::max(8, std::min(1 << 20, v)); }   // 0 = from the queue size
-    if (const char *e = getenv("RT_LEAFB")) t.leafb = t.leafbClosest = atoi(e);
-    if (const char *e = getenv("RT_LEAFB_CLOSEST")) t.leafbClosest = atoi(e);
-    if (const char *e = getenv("RT_MIN_SEARCH")) t.minSearch = std::max(0, std::min(64, atoi(e)));
-    if (const char *e = getenv("RT_QUAD_REFILL")) t.quadRefill = atoi(e) != 0;
-    if (const char *e = getenv("RT_COOP")) t.coop = atoi(e);   // quad-cooperative node fetch of the closest-hit launches (measured option)
-    if (const char *e = getenv("RT_NEAR_FIRST")) t.nearFirst = atoi(e);
-    if (const char *e = getenv("RT_REVERSE")) t.reverse = atoi(e);      // 0: any-hit queues dealt from their beginning, as in rounds 1-3
-    if (const char *e = getenv("RT_GUIDED")) t.guided = atoi(e);
-    if (const char *e = getenv("RT_DENSE_TAKE")) t.denseTake = atoi(e);   // 0: every refill probes liveness first, as in rounds 2-3
-    if (const char *e = getenv("RT_QNODES")) t.qnodes = atoi(e);          // 0: never; 1 / 2: always (seven / six waves per SIMD); default: when rt_upload_bvh built them
-    return t;
-}
-
 // The slab test of rt_bvh.glsl:124-134 in two halves, so that the per-axis values of two child boxes can be merged into their parent's (k_trace, FUSE):
 // slab_parts + slab_eval are slab() operation for operation.
 struct SlabP { float sx, sy, sz, bx, by, bz; };
@@ -168,10 +137,18 @@ extern __shared__ __align__(16) unsigned char rt_dyn_lds[];
 #ifndef RT_IMPL_ANYHIT_WAVES
 #define RT_IMPL_ANYHIT_WAVES 6   // the implicit any-hit build at six waves per SIMD: at seven (72 VGPRs) it spills 32 B per lane into its inner loop (experiment 9)
 #endif
-template <class Src, bool ANY, int LEAFB, bool STATS = false, bool COOP = false, bool NEAR = false, int QN = 0, bool FUSE = false, bool IMPL = false, bool TIMING = false>
-__global__ __launch_bounds__(256, (!STATS && !ANY) ? 5 : ((NEAR || QN == 2 || (IMPL && RT_IMPL_ANYHIT_WAVES == 6)) ? 6 : (ANY && !STATS && LEAFB == 2 ? RT_ANYHIT_WAVES : 1))) void k_trace(const DevFrame *__restrict__ fr, const float4 *__restrict__ wnodes, const float4 *__restrict__ tris, Src src,
+// A k_trace build is named by its RT_BUILD_* bits (include/rt_mi355.h), unshifted and without RT_BUILD_LAUNCHED: OPT.  The waves per SIMD a build is held to:
+constexpr int trace_waves(bool any, uint32_t opt) {
+    const bool stats = (opt & RT_BUILD_STATS) != 0, leafb2 = (opt & RT_BUILD_LEAFB4) == 0;
+    return (!stats && !any) ? 5 : (((opt & (RT_BUILD_NEAR | RT_BUILD_QN2)) != 0 || ((opt & RT_BUILD_IMPL) != 0 && RT_IMPL_ANYHIT_WAVES == 6)) ? 6 : (any && !stats && leafb2 ? RT_ANYHIT_WAVES : 1));
+}
+template <class Src, bool ANY, uint32_t OPT>
+__global__ __launch_bounds__(256, trace_waves(ANY, OPT)) void k_trace(const DevFrame *__restrict__ fr, const float4 *__restrict__ wnodes, const float4 *__restrict__ tris, Src src,
                                                 uint32_t *head, unsigned long long *tally, unsigned long long *gatherLoads, TraceTune tune,
                                                 int stackEntries, unsigned long long *stats = nullptr, const float4 *__restrict__ leafBox = nullptr) {
+    constexpr int LEAFB = (OPT & RT_BUILD_LEAFB4) ? 4 : 2, QN = (OPT & RT_BUILD_QN1) ? 1 : ((OPT & RT_BUILD_QN2) ? 2 : 0);
+    constexpr bool STATS = (OPT & RT_BUILD_STATS) != 0, COOP = (OPT & RT_BUILD_COOP) != 0, NEAR = (OPT & RT_BUILD_NEAR) != 0, FUSE = (OPT & RT_BUILD_FUSE) != 0,
+                   IMPL = (OPT & RT_BUILD_IMPL) != 0, TIMING = (OPT & RT_BUILD_TIMING) != 0;
     // STATS (diagnostic build only, RT_TRACE_STATS=1): [0] inner-node visits [1] leaf visits [2] triangle tests [3] inner-phase wave
     // iterations [4] active lanes summed over them [5] leaf-phase wave iterations [6] lanes with a leaf summed [7] refill rounds
     unsigned long long st_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [14] / [15]: the same with wave-wide merging (distinct records per wave step)   // [8] cycles in inner steps [9] in leaf phases [10] in refills [11] wave lifetime
@@ -741,15 +718,6 @@ __global__ __launch_bounds__(256, (!STATS && !ANY) ? 5 : ((NEAR || QN == 2 || (I
     }
 }
 
-// A k_trace build with its RT_BUILD_* bits (include/rt_mi355.h): launch_trace reports which build it launched (rt_debug_builds).
-template <class Src, bool ANY, int LEAFB, bool STATS = false, bool COOP = false, bool NEAR = false, int QN = 0, bool FUSE = false, bool IMPL = false, bool TIMING = false>
-struct KTrace {
-    static constexpr auto fn = &k_trace<Src, ANY, LEAFB, STATS, COOP, NEAR, QN, FUSE, IMPL, TIMING>;
-    static constexpr uint32_t bits = (uint32_t)(RT_BUILD_LAUNCHED | (LEAFB >= 4 ? RT_BUILD_LEAFB4 : 0) | (STATS ? RT_BUILD_STATS : 0) | (COOP ? RT_BUILD_COOP : 0) |
-                                                (NEAR ? RT_BUILD_NEAR : 0) | (QN == 1 ? RT_BUILD_QN1 : 0) | (QN == 2 ? RT_BUILD_QN2 : 0) | (FUSE ? RT_BUILD_FUSE : 0) |
-                                                (IMPL ? RT_BUILD_IMPL : 0) | (TIMING ? RT_BUILD_TIMING : 0)) << (ANY ? RT_BUILD_ANY_SHIFT : 0);
-};
-
 // ---- packet traversal (round 4) ----------------------------------------------------------------------
 // The AO rays of one hit leave from ONE point (computeAO: org = hp + N * aoBias, rt_lighting.glsl:721-757) and are short (aoRadius 0.8): the
 // four of them visit nearly the same part of the tree -- traced one by one they fetch 39.8 four-wide node records and 8.8 leaves per hit on the
@@ -1015,45 +983,42 @@ struct TraceLaunch {
     unsigned maxBlocks = 0;                // ray queries: no more workgroups than the rays can occupy (0: whatever fits)
 };
 
-template <class Src, bool ANY>
-uint32_t launch_trace(const TraceLaunch &t, Src src) {
-    const DevScene &hs = t.scene; const TraceTune &tune = t.tune; unsigned long long *const stats = t.stats;
-    // Stack entries: closest-hit defers one sibling per binary level (8 B each); any-hit walks 4-wide nodes and can
-    // defer three per two levels (4 B each).  Resident 256-thread workgroups per CU follow from the LDS footprint and the kernel's
-    // registers: asked from the runtime per (kernel, stack size), the persistent grid is exactly what fits.
-    const int stack = std::max(4, ANY ? (hs.anyStack > 0 ? hs.anyStack : 3 * ((t.depth + 1) / 2)) : t.depth);
-    const size_t ldsBytes = (size_t)256 * stack * (ANY ? 4 : 8);
-    const bool qn = ANY && tune.qnodes != 0 && hs.q4 != nullptr && !stats && !tune.nearFirst;   // (the diagnostic and near-first builds walk the exact nodes)   // -1: whenever rt_upload_bvh built the quantised nodes (trees beyond the L2)
-    const bool fuse = !ANY && tune.fused != 0 && hs.wF != nullptr && !tune.coop;   // closest-hit launches: the fused records when rt_upload_bvh built them
-    const bool impl = tune.impl != 0 && (!stats || tune.timing) && (ANY ? (hs.iN4 != nullptr && (!qn || hs.iQ4 != nullptr) && !tune.nearFirst && tune.leafb < 4 && !(qn && tune.qnodes == 1) && hs.anyStack > 0)
-                                                       : (!fuse && hs.iN2 != nullptr && !tune.coop));   // ... the implicit records when every leaf sits at one depth
-    const float4 *nodes = ANY ? (impl ? (qn ? hs.iQ4 : hs.iN4) : (qn ? hs.q4 : hs.w4)) : (fuse ? hs.wF : (impl ? hs.iN2 : hs.wnodesW));
-    const float4 *pairRecords = impl ? hs.iPairs : hs.pairs;
-    const float4 *leafBoxes = (ANY && impl) ? hs.iLeafBox : hs.leafBox;
-    uint32_t built = 0;   // RT_BUILD_* bits of the build launched
-    auto go = [&](auto k) {
-        const auto kernel = decltype(k)::fn;
-        built = decltype(k)::bits;
-        unsigned blocks = persistent_grid(kernel, ldsBytes, t.cus, t.gridPct);
-        if (t.maxBlocks) blocks = std::min(blocks, t.maxBlocks);   // (ray queries: no more waves than the rays can occupy)
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), ldsBytes, t.st, t.fr, nodes, pairRecords, src, t.head, t.tally, t.gatherLoads, tune, stack, stats, leafBoxes);
-    };
-    const int leafb = ANY ? tune.leafb : tune.leafbClosest;
-    if (stats && tune.timing) {   // RT_TRACE_TIMING=1: the production kernel of this launch with scalar time stamps (exact / implicit records, default leaf groups only)
-        if (impl) go(KTrace<Src, ANY, 2, false, false, false, 0, false, true, true>{}); else go(KTrace<Src, ANY, 2, false, false, false, 0, false, false, true>{});
-        return built;
+// What a scene offers a launch (rt_trace_build.hpp)
+inline rtl::TraceForms trace_forms(const DevScene &sc) { return rtl::TraceForms{sc.q4 != nullptr, sc.wF != nullptr, sc.iN2 != nullptr, sc.iN4 != nullptr, sc.iQ4 != nullptr, sc.anyStack}; }
+inline const float4 *trace_nodes(const DevScene &sc, rtl::TraceNodes which) {
+    switch (which) {
+        case rtl::TN_WF: return sc.wF;
+        case rtl::TN_IN2: return sc.iN2;
+        case rtl::TN_W4: return sc.w4;
+        case rtl::TN_Q4: return sc.q4;
+        case rtl::TN_IN4: return sc.iN4;
+        case rtl::TN_IQ4: return sc.iQ4;
+        default: return sc.wnodesW;
     }
-    if (impl && ANY) { if (qn) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 2 : 0, false, true>{}); else go(KTrace<Src, ANY, 2, false, false, false, 0, false, true>{}); }
-    else if (impl) go(KTrace<Src, ANY, 2, false, false, false, 0, false, true>{});
-    else if (stats && fuse) go(KTrace<Src, ANY, 2, true, false, false, 0, !ANY>{});
-    else if (stats) { if (leafb >= 4) go(KTrace<Src, ANY, 4, true>{}); else go(KTrace<Src, ANY, 2, true>{}); }
-    else if (fuse) go(KTrace<Src, ANY, 2, false, false, false, 0, !ANY>{});
-    else if (!ANY && tune.coop) go(KTrace<Src, ANY, 2, false, !ANY>{});
-    else if (ANY && tune.nearFirst) go(KTrace<Src, ANY, 2, false, false, ANY>{});
-    else if (qn && tune.qnodes == 1) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 1 : 0>{});   // seven waves per SIMD, 44 B of scratch: slower (measured)
-    else if (qn) go(KTrace<Src, ANY, 2, false, false, false, ANY ? 2 : 0>{});
-    else       { if (leafb >= 4) go(KTrace<Src, ANY, 4, false>{}); else go(KTrace<Src, ANY, 2, false>{}); }
-    return built;
+}
+
+// One trace launch: the build rtl::trace_build chooses (rt_trace_build.cpp: the rules, tested without a GPU), its arrays, and the kernel of that build out of the
+// kept builds of this hit kind.  Returns the RT_BUILD_* bits of the build launched (rt_debug_builds); 0 -- nothing was launched -- for a build that is not kept,
+// which trace_build never returns (tests/test_trace_build_host.py).
+template <class Src, bool ANY, size_t... I>
+uint32_t launch_trace_of(const TraceLaunch &t, const Src &src, const rtl::TraceBuild &b, std::index_sequence<I...>) {
+    constexpr const uint32_t *kept = ANY ? rtl::kAnyBuilds : rtl::kClosestBuilds;
+    const DevScene &hs = t.scene;
+    const float4 *nodes = trace_nodes(hs, b.nodes), *pairRecords = b.implPairs ? hs.iPairs : hs.pairs, *leafBoxes = b.implLeafBoxes ? hs.iLeafBox : hs.leafBox;
+    auto go = [&](auto kernel) {
+        // Resident 256-thread workgroups per CU follow from the LDS footprint and the kernel's registers: the persistent grid is exactly what fits
+        unsigned blocks = persistent_grid(kernel, b.ldsBytes, t.cus, t.gridPct);
+        if (t.maxBlocks) blocks = std::min(blocks, t.maxBlocks);   // (ray queries: no more waves than the rays can occupy)
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), b.ldsBytes, t.st, t.fr, nodes, pairRecords, src, t.head, t.tally, t.gatherLoads, t.tune, b.stack, t.stats, leafBoxes);
+        return true;
+    };
+    const bool launched = ((b.opt == kept[I] && go(&k_trace<Src, ANY, kept[I]>)) || ...);
+    return launched ? (uint32_t)(RT_BUILD_LAUNCHED | b.opt) << (ANY ? RT_BUILD_ANY_SHIFT : 0) : 0u;
+}
+template <class Src, bool ANY>
+uint32_t launch_trace(const TraceLaunch &t, const Src &src) {
+    const rtl::TraceBuild b = rtl::trace_build(ANY, t.tune, trace_forms(t.scene), t.depth, t.stats != nullptr);
+    return launch_trace_of<Src, ANY>(t, src, b, std::make_index_sequence<ANY ? rtl::kNAnyBuilds : rtl::kNClosestBuilds>{});
 }
 // ... closest- or any-hit by a run-time choice (the debug and query entries)
 template <class Src> uint32_t launch_trace_kind(bool any, const TraceLaunch &t, const Src &src) { return any ? launch_trace<Src, true>(t, src) : launch_trace<Src, false>(t, src); }
@@ -1067,10 +1032,9 @@ __global__ __launch_bounds__(256) void k_query_prep(DevFrame *fr, DevScene sc, f
 
 uint32_t launch_packets(const TraceLaunch &t, PacketSrc src) {   // (stats and maxBlocks are not for packets)
     const DevScene &hs = t.scene;
-    const int stack = std::max(4, hs.anyStack > 0 ? hs.anyStack : 3 * ((t.depth + 1) / 2));
-    const size_t ldsBytes = (size_t)256 * stack * 4;
-    const unsigned blocks = persistent_grid(k_trace_packets, ldsBytes, t.cus, t.gridPct);
-    hipLaunchKernelGGL(k_trace_packets, dim3(blocks), dim3(256), ldsBytes, t.st, t.fr, hs.w4, hs.pairs, src, t.head, t.tally, t.gatherLoads, t.tune, stack);
+    const rtl::TraceBuild b = rtl::trace_build(true, t.tune, trace_forms(hs), t.depth, false);   // the any-hit stack and its LDS bytes; the packets walk w4 whatever the build
+    const unsigned blocks = persistent_grid(k_trace_packets, b.ldsBytes, t.cus, t.gridPct);
+    hipLaunchKernelGGL(k_trace_packets, dim3(blocks), dim3(256), b.ldsBytes, t.st, t.fr, hs.w4, hs.pairs, src, t.head, t.tally, t.gatherLoads, t.tune, b.stack);
     return (uint32_t)RT_BUILD_PACKETS << RT_BUILD_ANY_SHIFT;
 }
 }  // namespace

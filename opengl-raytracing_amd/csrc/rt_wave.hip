@@ -93,6 +93,7 @@ struct RtWave {
     hipStream_t shadeStream = nullptr;   // RT_CU_SPLIT: the shading kernels' stream (a CU-masked one), else null
     hipEvent_t hopEv = nullptr;
     uint32_t builds = 0;                 // RT_BUILD_* bits of the traversal builds launched since the last rt_wave_builds reset
+    bool noKernel = false;               // a trace launch found no kernel for the build it chose and launched nothing (wave_built): the stage fails
     bool probeTree = true;               // the any-hit tree is the collapse of the binary one (rt_upload_bvh): false under RT_ANYHIT_TREE=sah
     unsigned long long *probeAcc = nullptr;   // device, monotonic: [0] bounce rays the probe walked [1] rays it re-traced closest-hit
     unsigned long long probeLaunches = 0, closestLaunches = 0;   // bounce launches (chunks) with / without the probe
@@ -176,6 +177,10 @@ static_assert(sizeof(HitRec) == rtl::kHitRecBytes, "the planner's frame arena ho
 
 static double &wave_share(RtWave *w) { return w->pool->q2Frac; }   // (live: updated behind a set's hit-count read-back, before a large set sizes its arena)
 
+// a trace launch's RT_BUILD_* bits into the lane's record; 0: launch_trace holds no kernel for the build it chose and launched nothing
+const char *const kNoKernelMessage = "traversal launch: the library holds no k_trace build for the chosen options";
+static void wave_built(RtWave *w, uint32_t built) { w->builds |= built; if (!built) w->noKernel = true; }
+
 static hipError_t wave_hop(RtWave *w, hipStream_t from, hipStream_t to) {
     if (from == to) return hipSuccess;
     hipError_t e = hipEventRecord(w->hopEv, from);
@@ -191,6 +196,7 @@ static int wave_stage(LaunchSet &L, int stage, hipStream_t on, Launch launch) {
     rt_stage_begin(L.ctx, stage, on);
     launch();
     rt_stage_end(L.ctx, stage, 1, on);
+    if (w->noKernel) { w->noKernel = false; w->err = kNoKernelMessage; return RT_ERR_UNSUPPORTED; }
     W_TRY(wave_hop(w, on, L.st));
     return RT_OK;
 }
@@ -336,7 +342,7 @@ static int wave_primary(LaunchSet &L, unsigned tiles) {
         TraceTune tuneP = w->tune;   // primary rays: their cost varies strongly across the screen, so shorter runs than the queue launches (128 - 256, see k_trace)
         tuneP.chunkMax = 256;
         if (w->opt.chunkPrimarySet) tuneP.chunk = w->opt.chunkPrimary;
-        w->builds |= launch_trace<PrimarySrc, false>(wave_trace(L, L.gridPctPrimary, &wb.heads[0], tuneP, w->acc + 2, w->acc + 8, 0), ps);
+        wave_built(w, launch_trace<PrimarySrc, false>(wave_trace(L, L.gridPctPrimary, &wb.heads[0], tuneP, w->acc + 2, w->acc + 8, 0), ps));
     }));
     W_STEP(wave_stage(L, ST_POST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(k_post_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
     return RT_OK;
@@ -382,7 +388,7 @@ static int wave_chunk_direct(LaunchSet &L, int c, uint32_t c0, bool pkAO) {
     if (pkAO) W_STEP(wave_stage(L, ST_TRACE_AO, L.st, [&] {
         PacketSrc pk{};   // the A dense AO slots in front of shadow queue 1
         pk.d = wb.shD; pk.org = wb.aoOrg; pk.occ = wb.occ1; pk.liveCount = &wb.counts[1]; pk.c0 = c0; pk.cap = wb.CH; pk.stride = wb.CH; pk.A = L.plan.ao;
-        w->builds |= launch_packets(wave_trace(L, L.gridPct, wave_cursor(wb, c, 3), w->tune, w->acc + 7, w->acc + 14), pk);
+        wave_built(w, launch_packets(wave_trace(L, L.gridPct, wave_cursor(wb, c, 3), w->tune, w->acc + 7, w->acc + 14), pk));
     }));
     return RT_OK;
 }
@@ -402,15 +408,16 @@ static int wave_chunk_bounce(LaunchSet &L, int c, uint32_t c0) {
             // any-hit walk of every bounce ray (misses answered in place, hits listed), then the closest-hit walk of the listed ones
             BounceProbeSrc pb{};
             pb.q = qg; pb.hitters = wb.giHit; pb.hitCount = listCount; pb.inf = L.host->u.inf;
-            w->builds |= launch_trace<BounceProbeSrc, true>(wave_trace(L, L.gridPct, wave_cursor(wb, c, 1), w->tune, w->probeAcc + 0, w->acc + 10, 32), pb) | ((uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT);
+            wave_built(w, launch_trace<BounceProbeSrc, true>(wave_trace(L, L.gridPct, wave_cursor(wb, c, 1), w->tune, w->probeAcc + 0, w->acc + 10, 32), pb));
+            w->builds |= (uint32_t)RT_BUILD_BOUNCE_PROBE << RT_BUILD_ANY_SHIFT;
             IndexedDenseSrc rq{};
             rq.idx = wb.giHit; rq.count = listCount; rq.org = wb.giOrg; rq.d = wb.giD; rq.stride = wb.CH; rq.orgStride = qg.orgStride; rq.outT = wb.giT; rq.outTri = wb.giTri;
             TraceLaunch retrace = wave_trace(L, L.gridPct, wave_cursor(wb, c, 2), w->tune, w->probeAcc + 1, w->acc + 10);
             retrace.maxBlocks = L.retraceBlocks;
-            w->builds |= launch_trace<IndexedDenseSrc, false>(retrace, rq);
+            wave_built(w, launch_trace<IndexedDenseSrc, false>(retrace, rq));
             w->probeLaunches++;
         } else {
-            w->builds |= launch_trace<QueueSrc, false>(wave_trace(L, L.gridPct, wave_cursor(wb, c, 1), w->tune, w->acc + 4, w->acc + 10, 32), qg);
+            wave_built(w, launch_trace<QueueSrc, false>(wave_trace(L, L.gridPct, wave_cursor(wb, c, 1), w->tune, w->acc + 4, w->acc + 10, 32), qg));
             w->closestLaunches++;
         }
     }));
@@ -446,9 +453,9 @@ static int wave_chunk(LaunchSet &L, int c) {
         DualQueueSrc qq{};
         qq.a = q1;   // b: shadow queue 2, six slots, the entries compacted over the chunk's bounce hits
         qq.b.o = wb.sh2O; qq.b.d = wb.sh2D; qq.b.tm = wb.sh2T; qq.b.liveCount = &wb.counts[64 + c]; qq.b.c0 = 0; qq.b.cap = wb.q2Stride; qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.outOcc = wb.occ2;
-        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { w->builds |= launch_trace<DualQueueSrc, true>(shadows, qq); }));
+        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { wave_built(w, launch_trace<DualQueueSrc, true>(shadows, qq)); }));
     } else {
-        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { w->builds |= launch_trace<QueueSrc, true>(shadows, q1); }));
+        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { wave_built(w, launch_trace<QueueSrc, true>(shadows, q1)); }));
     }
     // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
     if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
@@ -518,17 +525,17 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
 
 // Closest-hit traversal of the rays listed in idx[0 .. *count) (queue addresses into o / d; results to outT / outTri at the same address) with the
 // persistent kernel of this pipeline, for rt_hybrid.hip.  `heads`: kHeadWords zeroed cursor words.
-void rt_wave_trace_closest_indexed(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const uint32_t *idx,
+uint32_t rt_wave_trace_closest_indexed(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const uint32_t *idx,
                                    const uint32_t *count, const float4 *o, const float4 *d, float *outT, int *outTri, uint32_t *heads) {
     IndexedSrc q{};
     q.idx = idx; q.count = count; q.o = o; q.d = d; q.outT = outT; q.outTri = outTri;
-    launch_trace<IndexedSrc, false>(TraceLaunch{st, cus, 100, treeDepth, dFrame, hostScene, heads, default_tune()}, q);
+    return launch_trace<IndexedSrc, false>(TraceLaunch{st, cus, 100, treeDepth, dFrame, hostScene, heads, default_tune()}, q);
 }
-void rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const float4 *o, const float4 *d,
+uint32_t rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const DevFrame *dFrame, const DevScene &hostScene, const float4 *o, const float4 *d,
                                    const uint32_t *dst, const uint32_t *count, const uint32_t *flags, uint32_t cap, float *outT, int *outTri, uint32_t *heads, uint32_t capOut) {
     CompactSrc q{};
     q.o = o; q.d = d; q.dst = dst; q.count = count; q.flags = flags; q.cap = cap; q.capOut = capOut; q.outT = outT; q.outTri = outTri;
-    launch_trace<CompactSrc, false>(TraceLaunch{st, cus, 100, treeDepth, dFrame, hostScene, heads, default_tune()}, q);
+    return launch_trace<CompactSrc, false>(TraceLaunch{st, cus, 100, treeDepth, dFrame, hostScene, heads, default_tune()}, q);
 }
 // Diagnostics (rt_debug_trace kinds 2 / 3): n arbitrary rays through the PRODUCTION traversal kernels -- a one-slot queue of n entries, closest-hit or any-hit
 // launch as the frames use it (persistent grid, refill scheduler, the any-hit node form rt_upload_bvh chose, the build the environment selects: tune_from_env)

@@ -49,11 +49,12 @@ void rt_wave_set_probe_tree(RtWave *w, bool collapsed);
 
 // Closest-hit traversal of the rays listed in idx[0 .. *count) (queue addresses into o / d) with the persistent kernel of the wavefront
 // pipeline; results to outT / outTri at the same address.  heads: rt_wave_head_words() zeroed uint32 cursor words.
-void rt_wave_trace_closest_indexed(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const uint32_t *idx,
-                                   const uint32_t *count, const float4 *o, const float4 *d, float *outT, int *outTri, uint32_t *heads);
+// -> the RT_BUILD_* bits of the build launched, as every trace entry below; 0: the library holds no kernel for the chosen build and nothing was launched.
+uint32_t rt_wave_trace_closest_indexed(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const uint32_t *idx,
+                                       const uint32_t *count, const float4 *o, const float4 *d, float *outT, int *outTri, uint32_t *heads);
 // The same over a dense array of records o[r] / d[r], r < min(*count, cap); the answer of record r goes to outT / outTri at dst[r].
 // Nothing is traced when *flags has bit 2 or 4 set (rt_hybrid.hip: a pass that outgrew its arrays left the queue incomplete).
-void rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const float4 *o, const float4 *d,
+uint32_t rt_wave_trace_closest_compact(hipStream_t st, int cus, int treeDepth, const rtd::DevFrame *dFrame, const rtd::DevScene &hostScene, const float4 *o, const float4 *d,
                                    const uint32_t *dst, const uint32_t *count, const uint32_t *flags, uint32_t cap, float *outT, int *outTri, uint32_t *heads,
                                    uint32_t capOut = 0);   // capOut != 0 (RT_HYBRID_CHECK): entries of outT / outTri, checked before every store
 // rt_debug_trace kinds 2 - 4 (diagnostics): rays through the production traversal kernels with the build the environment selects; the RT_BUILD_* bits of

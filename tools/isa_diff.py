@@ -6,9 +6,11 @@
 
 Every function symbol of the OLD library's gfx950 code objects is disassembled (llvm-objdump -d) in both libraries and compared instruction
 by instruction, encodings included; only the absolute addresses llvm-objdump prints in its comments and the "..." it prints for zero
-padding behind a section's last function are dropped (a kernel that merely moved inside its code object is the same code).  Symbols only
-the NEW library has are listed as added.  Exit status 0 when no existing symbol changed or disappeared, 1 otherwise.  The code objects
-are read straight from the .hip_fatbin section (clang offload bundles, one per translation unit), so nothing beyond the ROCm LLVM tools
+padding behind a section's last function are dropped (a kernel that merely moved inside its code object is the same code).  A symbol
+that disappeared is paired with a symbol of the same code object that only the NEW library has when their instruction streams are
+identical apart from the symbol's own name in branch-target comments, one to one, and reported as renamed (a template's arguments changed, its code did not).  Symbols only the NEW library has and
+that no such pair accounts for are listed as added.  Exit status 0 when no existing symbol changed or disappeared without an identical
+partner, 1 otherwise.  The code objects are read straight from the .hip_fatbin section (clang offload bundles, one per translation unit), so nothing beyond the ROCm LLVM tools
 is needed.
 """
 import argparse
@@ -88,6 +90,25 @@ def build_rev(rev: str, work: Path) -> Path:
     return work / "opengl-raytracing_amd" / "librt_mi355.so"
 
 
+def pair_renamed(before, after, gone, added):
+    """(gone, added, renamed) with every removed symbol that has an added symbol of identical code in its code object taken out of both lists, one to one."""
+    def stream(k, body):   # (llvm-objdump names a branch's target <symbol+offset> in its comment: the symbol's own name is not part of its code)
+        return k[0], tuple(line.replace(f"<{k[1]}+", "<.+").replace(f"<{k[1]}>", "<.>") for line in body)
+
+    pool = {}
+    for k in added:
+        pool.setdefault(stream(k, after[k]), []).append(k)
+    renamed, left = [], []
+    for k in gone:
+        partners = pool.get(stream(k, before[k]))
+        if partners:
+            renamed.append((k, partners.pop(0)))
+        else:
+            left.append(k)
+    taken = {k2 for _, k2 in renamed}
+    return left, [k for k in added if k not in taken], renamed
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old", nargs="?")
@@ -107,9 +128,13 @@ def main():
         changed = [k for k in before if k in after and before[k] != after[k]]
         gone = [k for k in before if k not in after]
         added = [k for k in after if k not in before]
+        same = len(before) - len(changed) - len(gone)
+        gone, added, renamed = pair_renamed(before, after, gone, added)
         print(f"old: {old}\nnew: {a.new}")
-        print(f"symbols before: {len(before)} in {len({k[0] for k in before})} code objects; identical: {len(before) - len(changed) - len(gone)}; "
+        print(f"symbols before: {len(before)} in {len({k[0] for k in before})} code objects; identical: {same}; renamed: {len(renamed)}; "
               f"changed: {len(changed)}; removed: {len(gone)}; added: {len(added)}")
+        for k, k2 in renamed:
+            print(f"  renamed  [{k[0]}] {k[1]} -> {k2[1]}  ({len(before[k])} instructions)")
         for k in changed:
             print(f"  CHANGED  [{k[0]}] {k[1]}  ({len(before[k])} -> {len(after[k])} instructions)")
         for k in gone:

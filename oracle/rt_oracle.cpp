@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "orc_dress.h"
 #include "orc_math.h"
 #include "orc_types.h"
 
@@ -46,6 +47,7 @@ struct Scene {
     int W = 0, H = 0;
     int envFilter = 0;              // cube-map filter model: 0 exact fp32 weights, 1 texel coordinates rounded to 1/256 texel
     int giBounces = 1;              // EXTENSION (not in the reference): diffuse bounces of the analytic / hybrid GI path, see giPath
+    const OrcDress *dress = nullptr;   // EXTENSION (orc_dress.h): the dynamic mesh's normals, colours, texture and previous pose; set only while u.useBVH == 1
 };
 // EXTENSION, not in the reference (SURVEY.md 8d config 3 "run B", labelled mode=hybrid): uUseBVH == 2 renders the analytic branch of
 // rt.frag with the BVH mesh added to the analytic scene as one more object.  Everything else is the reference's analytic code.
@@ -55,7 +57,7 @@ static std::atomic<int> g_envFilter{0};
 static const int MAT_MESH = 5;      // no material of rt_materials.glsl:20-24 -> getMaterial's default branch (:123-124): 0.8 grey, spec 0.2, gloss 16, diffuse
 
 // ---------------------------------------------------------------- rt_common.glsl
-struct Hit { float t; vec3 p; vec3 n; int mat; int prim; };             // :39-44; prim (not in the shader): the row of the winning triangle, traceBVH only
+struct Hit { float t; vec3 p; vec3 n; int mat; int prim; float a, b; };  // :39-44; prim, a, b (not in the shader): the row of the winning triangle and triHit's u, v on it, traceBVH only
 
 static inline uint32_t hash2(uint32_t vx, uint32_t vy) {                // :57-63
     vx = vx * 1664525u + 1013904223u;
@@ -266,7 +268,7 @@ static inline bool aabbHit(vec3 ro, vec3 rdInv, vec3 bmin, vec3 bmax, float &tmi
     tmaxOut = tmax;
     return tmax >= tmin;
 }
-static inline bool triHit(const Scene &S, vec3 ro, vec3 rd, const TriSOA &T, float tMax, float &t, vec3 &n) {   // :154-170
+static inline bool triHit(const Scene &S, vec3 ro, vec3 rd, const TriSOA &T, float tMax, float &t, vec3 &n, float *uv = nullptr) {   // :154-170; uv (not in the shader): u, v of a hit
     vec3 pvec = cross(rd, T.e2);
     float det = dot(T.e1, pvec);
     if (std::fabs(det) < 1e-8f) return false;
@@ -281,6 +283,7 @@ static inline bool triHit(const Scene &S, vec3 ro, vec3 rd, const TriSOA &T, flo
     if (tt < S.u.eps || tt > tMax) return false;
     t = tt;
     n = normalize(cross(T.e1, T.e2));
+    if (uv) { uv[0] = u; uv[1] = v; }
     return true;
 }
 static bool traceBVH(const Scene &S, Counters &C, vec3 ro, vec3 rd, Hit &hitOut) {    // :193-243
@@ -301,8 +304,9 @@ static bool traceBVH(const Scene &S, Counters &C, vec3 ro, vec3 rd, Hit &hitOut)
         if (N.count > 0) {
             for (int i = 0; i < N.count; ++i) {
                 TriSOA T = triFetch(S, C, N.first + i);
-                float t; vec3 n;
-                if (triHit(S, ro, rd, T, hitOut.t, t, n)) {
+                float t; vec3 n; float uv[2];
+                if (triHit(S, ro, rd, T, hitOut.t, t, n, uv)) {
+                    hitOut.a = uv[0]; hitOut.b = uv[1];
                     hitOut.t = t;
                     hitOut.p = ro + rd * t;
                     hitOut.n = n;
@@ -522,9 +526,17 @@ static vec3 directLight(const Scene &S, Counters &C, const Frag &F, const Hit &h
     sum += pointDirect(S, C, h, mat, V);
     return sum;
 }
-static vec3 directLightBVH(const Scene &S, Counters &C, const Frag &F, const Hit &h, int frame, vec3 Vdir) {   // :405-460
+// EXTENSION (orc_dress.h): what a dressed mesh hit carries in place of the reference's face normal and constant albedo.  The normal goes into h.n, so
+// that everything the reference derives from h.n follows it; the albedo is handed to the three places DESIGN.md 14.14 names.
+static const vec3 kMeshAlbedo = {0.85f, 0.85f, 0.85f};                  // rt_lighting.glsl:407 and :516
+static vec3 dressHit(const Scene &S, Hit &h) {
+    if (!S.dress) return kMeshAlbedo;
+    const OrcDress &d = *S.dress;
+    if (d.nrmRows) h.n = dressNormal(S.tris + (size_t)h.prim * 12, d.nrmRows + (size_t)h.prim * 12, h.a, h.b);
+    return dressAlbedo(d, h.prim, h.a, h.b);
+}
+static vec3 directLightBVH(const Scene &S, Counters &C, const Frag &F, const Hit &h, int frame, vec3 Vdir, vec3 albedo = kMeshAlbedo) {   // :405-460
     vec3 N = normalize(h.n);
-    const vec3 albedo = v3(0.85f);
     const float specStrength = 0.25f, gloss = 32.0f;
     vec3 V = normalize(Vdir);
     vec3 sum = diskLight(S, C, F, h, N, V, frame, albedo, specStrength, gloss);
@@ -567,8 +579,7 @@ static vec3 oneBounceGIAnalytic(const Scene &S, Counters &C, const Frag &F, cons
     }
     return result;
 }
-static vec3 oneBounceGIBVH(const Scene &S, Counters &C, const Frag &F, const Hit &h0, int frame, int seed) {   // :515-561
-    const vec3 albedo0 = v3(0.85f);
+static vec3 oneBounceGIBVH(const Scene &S, Counters &C, const Frag &F, const Hit &h0, int frame, int seed, vec3 albedo0 = kMeshAlbedo) {   // :515-561
     const float MAX_GI_LUM = 8.0f, MIN_COS_THETA = 0.1f;
     float o19 = (float)(int)((uint32_t)seed * 19u), o41 = (float)(int)((uint32_t)seed * 41u);
     vec2 u = {rand_(vec2{F.fc.x + o19, F.fc.y + o19}, frame), rand_(vec2{F.fc.y + o41, F.fc.x + o41}, frame)};
@@ -579,7 +590,8 @@ static vec3 oneBounceGIBVH(const Scene &S, Counters &C, const Frag &F, const Hit
     vec3 origin = h0.p + N0 * S.u.eps;
     Hit h1;
     bool hit1 = traceBVH(S, C, origin, wi, h1);
-    vec3 Li = hit1 ? directLightBVH(S, C, F, h1, frame, -wi) : sky(S, C, wi);
+    vec3 albedo1 = hit1 ? dressHit(S, h1) : kMeshAlbedo;   // the bounce hit, at its own barycentrics
+    vec3 Li = hit1 ? directLightBVH(S, C, F, h1, frame, -wi, albedo1) : sky(S, C, wi);
     vec3 contrib = albedo0 * (cosTheta / S.u.pi) * Li;
     float lum = dot(contrib, v3(0.299f, 0.587f, 0.114f));
     if (lum > MAX_GI_LUM) {
@@ -751,20 +763,26 @@ static PixelOut shadePixel(const Scene &S, Counters &C, int px, int py) {     //
         bool hitAny = (u.useBVH == 1) ? traceBVH(S, C, camPos, dir, h) : traceAnalytic(S, C, camPos, dir, h);
         C.fetchPrimary += C.fetches() - f0;
         vec3 radiance;
+        vec3 albedo = kMeshAlbedo;
+        const bool dressed = hitAny && u.useBVH == 1 && S.dress;
+        if (dressed) albedo = dressHit(S, h);
         if (hitAny) {
             if (s == 0) {
                 C.hitPixels++;
-                vec2 prevNDC = ndcFromWorld(h.p, u.prevViewProj);
+                vec3 prevP = h.p;
+                if (dressed && S.dress->prevTris)
+                    prevP = dressPrevPoint(S.tris + (size_t)h.prim * 12, S.dress->prevTris + (size_t)h.prim * 12, h.a, h.b, h.p);
+                vec2 prevNDC = ndcFromWorld(prevP, u.prevViewProj);
                 vec2 currNDC = ndcFromWorld(h.p, u.currViewProj);
                 motionOut = {currNDC.x - prevNDC.x, currNDC.y - prevNDC.y};
                 o.gpos = {h.p.x, h.p.y, h.p.z, 1.0f};
-                vec3 nn = normalize(h.n);
+                vec3 nn = (dressed && S.dress->nrmRows) ? h.n : normalize(h.n);   // GNRM holds the smooth normal's own floats
                 o.gnrm = {nn.x, nn.y, nn.z, 0.0f};
             }
             vec3 V = -dir;
             if (u.useBVH == 1) {
-                radiance = directLightBVH(S, C, F, h, seed, V);
-                if (u.enableGI == 1) radiance += u.giScaleBVH * oneBounceGIBVH(S, C, F, h, u.frameIndex, seed);
+                radiance = directLightBVH(S, C, F, h, seed, V, albedo);
+                if (u.enableGI == 1) radiance += u.giScaleBVH * oneBounceGIBVH(S, C, F, h, u.frameIndex, seed, albedo);
                 if (u.enableAO == 1) radiance *= computeAO(S, C, F, h, u.frameIndex);
             } else {
                 MaterialProps mat = getMaterial(S, h.mat);
@@ -887,6 +905,69 @@ int orc_trace_bvh_shadow(const OrcUniforms *u, const float *nodes, const float *
 static std::atomic<int> g_giBounces{1};
 void orc_set_gi_bounces(int n) { g_giBounces = n; }
 void orc_set_env_filter(int m) { g_envFilter = m; }
+// EXTENSION (orc_dress.h): the dress of the orc_render calls that follow, read only while u->useBVH == 1 (the hybrid and the analytic branch ignore it).
+// The struct is copied, the arrays stay the caller's and are only read; null clears, and so does a dress without any array.
+static OrcDress g_dress{};
+static bool g_dressSet = false;
+void orc_set_dress(const OrcDress *d) {
+    g_dressSet = d && (d->nrmRows || d->colRows || d->prevTris || dressHasTexture(*d));
+    g_dress = g_dressSet ? *d : OrcDress{};
+}
+// The current dress applied to given hit records (rec: n x 4, RtHit's t, prim as int32 bits, u, v) on the rows tris12.  normal3 and albedo3 get three
+// floats per record; prevPoint3 holds the hit points on entry and the previous points on return.  An output whose attribute is not set is left
+// untouched (so is a null one, and so is everything while no dress is set); a prim outside [0, nTris) gives zeros.  Returns n, -1 for a null input.
+int orc_dress_hits(const float *tris12, const float *rec, int n, float *normal3, float *albedo3, float *prevPoint3) {
+    if (!tris12 || !rec || n < 0) return -1;
+    if (!g_dressSet) return n;
+    const OrcDress &d = g_dress;
+    for (int i = 0; i < n; ++i) {
+        const float *r = rec + (size_t)i * 4;
+        const int prim = (int)f2u(r[1]);
+        const float a = r[2], b = r[3];
+        const bool on = prim >= 0 && prim < d.nTris;
+        const float *T = tris12 + (size_t)(on ? prim : 0) * 12;
+        if (normal3 && d.nrmRows) {
+            vec3 v = on ? dressNormal(T, d.nrmRows + (size_t)prim * 12, a, b) : v3(0.0f);
+            normal3[i * 3 + 0] = v.x; normal3[i * 3 + 1] = v.y; normal3[i * 3 + 2] = v.z;
+        }
+        if (albedo3 && dressHasAlbedo(d)) {
+            vec3 v = on ? dressAlbedo(d, prim, a, b) : v3(0.0f);
+            albedo3[i * 3 + 0] = v.x; albedo3[i * 3 + 1] = v.y; albedo3[i * 3 + 2] = v.z;
+        }
+        if (prevPoint3 && d.prevTris) {
+            vec3 x = {prevPoint3[i * 3 + 0], prevPoint3[i * 3 + 1], prevPoint3[i * 3 + 2]};
+            vec3 v = on ? dressPrevPoint(T, d.prevTris + (size_t)prim * 12, a, b, x) : v3(0.0f);
+            prevPoint3[i * 3 + 0] = v.x; prevPoint3[i * 3 + 1] = v.y; prevPoint3[i * 3 + 2] = v.z;
+        }
+    }
+    return n;
+}
+
+// The primary hit of every pixel of a BVH frame as shadePixel finds it: rec gets W * H records (t, prim as int32 bits, triHit's u, v; t = uINF and
+// prim = -1 on a miss), points3 the hit points (zeros on a miss), row 0 = bottom row.  For the tests that restate a target from the oracle's own hits.
+int orc_primary_hits(const OrcUniforms *u, const float *nodes12, const float *tris12, float *rec, float *points3) {
+    Scene S; S.u = *u; S.nodes = nodes12; S.tris = tris12;
+    S.W = (int)u->resolution[0]; S.H = (int)u->resolution[1];
+    if (S.W <= 0 || S.H <= 0 || !nodes12 || !tris12 || !rec || !points3) return -1;
+    Counters C;
+    vec2 camJit = (u->enableJitter == 1) ? vec2{u->jitter[0], u->jitter[1]} : vec2{0.0f, 0.0f};
+    vec3 camPos = ld3(u->camPos), camRight = ld3(u->camRight), camUp = ld3(u->camUp), camFwd = ld3(u->camFwd);
+    for (int py = 0; py < S.H; ++py)
+        for (int px = 0; px < S.W; ++px) {
+            vec2 fc = {(float)px + 0.5f, (float)py + 0.5f};
+            vec2 uv = {(fc.x + camJit.x) / u->resolution[0], (fc.y + camJit.y) / u->resolution[1]};
+            vec2 ndc = {uv.x * 2.0f - 1.0f, uv.y * 2.0f - 1.0f};
+            vec3 dir = normalize(camFwd + (ndc.x * camRight) * (u->tanHalfFov * u->aspect) + (ndc.y * camUp) * u->tanHalfFov);
+            Hit h; h.p = v3(0.0f); h.prim = -1; h.a = h.b = 0.0f;
+            bool hit = traceBVH(S, C, camPos, dir, h);
+            size_t i = (size_t)py * S.W + px;
+            int prim = hit ? h.prim : -1;
+            rec[i * 4 + 0] = hit ? h.t : u->inf; rec[i * 4 + 1] = u2f((uint32_t)prim);
+            rec[i * 4 + 2] = hit ? h.a : 0.0f; rec[i * 4 + 3] = hit ? h.b : 0.0f;
+            points3[i * 3 + 0] = hit ? h.p.x : 0.0f; points3[i * 3 + 1] = hit ? h.p.y : 0.0f; points3[i * 3 + 2] = hit ? h.p.z : 0.0f;
+        }
+    return 0;
+}
 
 int orc_render(const OrcUniforms *u, const float *nodes12, const float *tris12, const uint8_t *envFaces, int envFaceSize,
                int envChannels, const uint16_t *prevAccum, uint16_t *outColor, uint16_t *outMotion, uint16_t *outGPos,
@@ -902,6 +983,11 @@ int orc_render(const OrcUniforms *u, const float *nodes12, const float *tris12, 
     if (S.W <= 0 || S.H <= 0) return -1;
     if (u->useEnvMap == 1 && (!envFaces || envFaceSize <= 0 || envChannels < 3)) return -2;
     if ((u->useBVH == 1 || u->useBVH == kSceneHybrid) && u->nodeCount > 0 && u->triCount > 0 && (!nodes12 || !tris12)) return -3;
+    const OrcDress dress = g_dress;   // this render's own copy: read only by the workers
+    if (g_dressSet && u->useBVH == 1) {
+        if (dress.nTris < u->triCount) return -4;   // rows are read at every prim traceBVH can return
+        S.dress = &dress;
+    }
     x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, S.W); y1 = std::min(y1, S.H);
     if (nthreads < 1) nthreads = 1;
     std::atomic<int> nextRow{y0};

@@ -3,6 +3,7 @@ tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg -- never by the 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import subprocess
 from pathlib import Path
 
@@ -33,6 +34,56 @@ class OrcCounters(C.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
+class OrcDress(C.Structure):
+    """oracle/orc_dress.h: the arrays of a dressed render, each optional."""
+    _fields_ = [("nTris", C.c_int), ("nrmRows", _FP), ("colRows", _FP), ("uvRows", _FP), ("texels", _U8P), ("texW", C.c_int), ("texH", C.c_int),
+                ("texFlags", C.c_int), ("table", _FP), ("prevTris", _FP)]
+
+
+@dataclasses.dataclass
+class Dress:
+    """The dress of the dynamic mesh for render() and dress_hits(): rows beside the rows of tris12, every one optional.
+    nrm_rows, col_rows, prev_tris: [T,12] float32; uv_rows: [T,8]; texels: [H,W,4] uint8, row 0 at v = 0, with flags (RT_TEX_* bits) and table,
+    the 256 decoded values (c / 255 or the sRGB curve).  The texture applies only with uv_rows."""
+    nrm_rows: np.ndarray = None
+    col_rows: np.ndarray = None
+    uv_rows: np.ndarray = None
+    texels: np.ndarray = None
+    flags: int = 0
+    table: np.ndarray = None
+    prev_tris: np.ndarray = None
+
+    def pack(self, n_tris=None):
+        """-> (OrcDress, the arrays it points into: keep them alive while the struct is in use)."""
+        rows = {}
+        for name, width in (("nrm_rows", 12), ("col_rows", 12), ("uv_rows", 8), ("prev_tris", 12)):
+            a = getattr(self, name)
+            if a is not None:
+                a = _f32(a).reshape(-1, width)
+                if n_tris is None:
+                    n_tris = a.shape[0]
+                if a.shape[0] != n_tris:
+                    raise ValueError(f"Dress.{name}: {a.shape[0]} rows for {n_tris} triangles")
+            rows[name] = a
+        tex = None if self.texels is None else np.ascontiguousarray(self.texels, np.uint8)
+        table = None if self.table is None else _f32(self.table).reshape(-1)
+        if tex is not None and (tex.ndim != 3 or tex.shape[2] != 4 or table is None or table.size != 256):
+            raise ValueError("Dress.texels is [H,W,4] uint8 and comes with a table of 256 floats")
+        d = OrcDress()
+        d.nTris = int(n_tris or 0)
+        for field, name in (("nrmRows", "nrm_rows"), ("colRows", "col_rows"), ("uvRows", "uv_rows"), ("prevTris", "prev_tris")):
+            if rows[name] is not None:
+                setattr(d, field, _fp(rows[name]))
+        if tex is not None:
+            d.texels, d.table = tex.ctypes.data_as(_U8P), _fp(table)
+            d.texH, d.texW, d.texFlags = tex.shape[0], tex.shape[1], int(self.flags)
+        return d, (rows, tex, table)
+
+
+def _as_dress(dress):
+    return dress if isinstance(dress, Dress) else Dress(**dress)
+
+
 def build():
     subprocess.run(["make", "-C", str(ORC_DIR)], check=True, capture_output=True)
 
@@ -54,6 +105,8 @@ def load(path):
                              C.c_int, C.c_int, C.c_int, C.c_int, _U8P, C.c_int, C.POINTER(OrcCounters)]
     L.orc_set_gi_bounces.argtypes = [C.c_int]
     L.orc_set_env_filter.argtypes = [C.c_int]
+    if hasattr(L, "orc_set_dress"):             # (a library built before the dressed mode renders undressed frames all the same)
+        L.orc_set_dress.restype = None; L.orc_set_dress.argtypes = [C.POINTER(OrcDress)]
     return L
 
 
@@ -85,6 +138,8 @@ def lib():
                              C.c_int, C.c_int, C.c_int, C.c_int, _U8P, C.c_int, C.POINTER(OrcCounters)]
     L.orc_set_gi_bounces.argtypes = [C.c_int]
     L.orc_set_env_filter.argtypes = [C.c_int]
+    L.orc_set_dress.restype = None; L.orc_set_dress.argtypes = [C.POINTER(OrcDress)]
+    L.orc_dress_hits.restype = C.c_int; L.orc_dress_hits.argtypes = [_FP, _FP, C.c_int, _FP, _FP, _FP]
     L.orc_default_render_params.argtypes = [C.POINTER(rt.RtRenderParams)]
     L.orc_default_camera.argtypes = [C.POINTER(rt.RtCamera)]
     L.orc_default_bvh_transform.argtypes = [_FP]
@@ -197,10 +252,12 @@ def cubemap_from_cross(img):
     return faces
 
 
-def render(u, nodes12=None, tris12=None, env_faces=None, prev=None, region=None, mask=None, nthreads=8, L=None, gi_bounces=1, env_filter=0):
+def render(u, nodes12=None, tris12=None, env_faces=None, prev=None, region=None, mask=None, nthreads=8, L=None, gi_bounces=1, env_filter=0,
+           dress=None):
     """One frame by the oracle -> ([color, motion, gpos, gnrm] uint16 arrays HxWxC, OrcCounters).  L: a library from load().
     gi_bounces: EXTENSION knob of the analytic / hybrid GI path (1 = the reference).  env_filter: cube-map filter model (0 = exact
-    fp32 weights, 1 = texel coordinates rounded to 1/256 texel)."""
+    fp32 weights, 1 = texel coordinates rounded to 1/256 texel).  dress: a Dress (or a dict of its fields), the dynamic mesh's
+    normals, colours, texture and previous pose beside tris12 -- read only while u.useBVH == 1, and cleared again before render returns."""
     (L or lib()).orc_set_gi_bounces(int(gi_bounces))
     (L or lib()).orc_set_env_filter(int(env_filter))
     W, H = int(u.resolution[0]), int(u.resolution[1])
@@ -212,13 +269,61 @@ def render(u, nodes12=None, tris12=None, env_faces=None, prev=None, region=None,
     m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
     x0, y0, x1, y1 = region if region else (0, 0, W, H)
     cnt = OrcCounters()
-    rc = (L or lib()).orc_render(C.byref(u), None if n is None else _fp(n), None if t is None else _fp(t),
-                          None if e is None else e.ctypes.data_as(_U8P), 0 if e is None else e.shape[1], 0 if e is None else e.shape[3],
-                          None if p is None else p.ctypes.data_as(_U16P), *[o.ctypes.data_as(_U16P) for o in outs],
-                          x0, y0, x1, y1, None if m is None else m.ctypes.data_as(_U8P), nthreads, C.byref(cnt))
+    keep = None
+    if dress is not None:
+        d, keep = _as_dress(dress).pack(None if t is None else t.reshape(-1, 12).shape[0])
+        (L or lib()).orc_set_dress(C.byref(d))
+    try:
+        rc = (L or lib()).orc_render(C.byref(u), None if n is None else _fp(n), None if t is None else _fp(t),
+                              None if e is None else e.ctypes.data_as(_U8P), 0 if e is None else e.shape[1], 0 if e is None else e.shape[3],
+                              None if p is None else p.ctypes.data_as(_U16P), *[o.ctypes.data_as(_U16P) for o in outs],
+                              x0, y0, x1, y1, None if m is None else m.ctypes.data_as(_U8P), nthreads, C.byref(cnt))
+    finally:
+        if dress is not None:
+            (L or lib()).orc_set_dress(None)      # no later render inherits it
+    del keep
     if rc != 0:
         raise RuntimeError(f"orc_render failed: {rc}")
     return outs, cnt
+
+
+def dress_hits(dress, tris12, rec, points=None):
+    """The dress applied to hit records (rec [N,4] float32: t, prim as int32 bits, u, v) on the rows tris12 -> (normals [N,3], albedo [N,3],
+    previous points [N,3]); an entry is None where the dress does not set the attribute (previous points need `points`, the hit points).
+    A prim outside the rows gives zeros."""
+    dress = _as_dress(dress)
+    t = _f32(tris12).reshape(-1, 12)
+    r = _f32(rec).reshape(-1, 4)
+    n = r.shape[0]
+    d, keep = dress.pack(t.shape[0])
+    has_tex = dress.uv_rows is not None and dress.texels is not None
+    normal = np.zeros((n, 3), np.float32) if dress.nrm_rows is not None else None
+    albedo = np.zeros((n, 3), np.float32) if dress.col_rows is not None or has_tex else None
+    prev = np.array(_f32(points).reshape(n, 3), copy=True) if dress.prev_tris is not None and points is not None else None
+    L = lib()
+    L.orc_set_dress(C.byref(d))
+    try:
+        rc = L.orc_dress_hits(_fp(t), _fp(r), n, *[None if a is None else _fp(a) for a in (normal, albedo, prev)])
+    finally:
+        L.orc_set_dress(None)
+    del keep
+    if rc != n:
+        raise RuntimeError(f"orc_dress_hits failed: {rc}")
+    return normal, albedo, prev
+
+
+def primary_hits(u, nodes12, tris12):
+    """The oracle's primary hit of every pixel of a BVH frame -> (rec [H*W,4] float32: t, prim as int32 bits, u, v; points [H*W,3]), row 0 = bottom
+    row; prim -1 on a miss."""
+    W, H = int(u.resolution[0]), int(u.resolution[1])
+    rec, pts = np.zeros((W * H, 4), np.float32), np.zeros((W * H, 3), np.float32)
+    f = lib().orc_primary_hits
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(rt.RtUniforms), _FP, _FP, _FP, _FP]
+    rc = f(C.byref(u), _fp(_f32(nodes12)), _fp(_f32(tris12)), _fp(rec), _fp(pts))
+    if rc != 0:
+        raise RuntimeError(f"orc_primary_hits failed: {rc}")
+    return rec, pts
 
 
 def present(pp, targets, nthreads=8):

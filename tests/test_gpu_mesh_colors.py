@@ -12,6 +12,7 @@ import torch
 
 import opengl_raytracing_amd as rt
 import scenes
+from mesh_fixtures import random_colors as _random_colors
 from test_gpu_dynamic_mesh import _mesh, _model, _ntris
 from test_gpu_mesh_motion import H, TARGETS, W, _dev, _placed_turned, _refused, _rows, _same, _skin_step, _turn, _xy
 from test_gpu_mesh_normals import _flat, _sphere, _two_bone_skin
@@ -23,10 +24,6 @@ f32 = np.float32
 IDENT = np.eye(4, dtype=f32).reshape(-1)
 GREY = f32(0.85)
 PIPELINES = [rt.RT_PIPELINE_WAVEFRONT, rt.RT_PIPELINE_MEGAKERNEL]
-
-
-def _random_colors(nv, seed):
-    return np.random.default_rng(seed).uniform(0.05, 1.0, (nv, 3)).astype(f32)
 
 
 def _device_colors(b):

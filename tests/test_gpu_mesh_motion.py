@@ -11,6 +11,7 @@ import torch
 
 import opengl_raytracing_amd as rt
 import scenes
+from mesh_fixtures import bones as _bones, placed_turned as _placed_turned, turn as _turn
 from test_gpu_dynamic_mesh import _mesh, _model, _ntris
 from test_gpu_mesh_refit import _set_qnodes
 
@@ -44,16 +45,6 @@ def _refused(call, code=rt.RT_ERR_INVALID):
 
 
 # ---------------------------------------------------------------- 1: prevTris replayed on the host
-def _turn(k):
-    """A model matrix that turns the mesh about an oblique axis and stretches it: the medians of the next rebuild fall elsewhere."""
-    a = 0.9 * k
-    c, s = np.cos(a), np.sin(a)
-    M = np.eye(4)
-    M[:3, :3] = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) @ np.array([[1, 0, 0], [0, c, -s], [0, s, c]]) @ np.diag([1.0 + 0.3 * abs(k), 1.0, 1.0 / (1.0 + 0.2 * abs(k))])
-    M[:3, 3] = [0.2 * k, -0.1 * k, 0.05]
-    return np.ascontiguousarray(M.T, f32).reshape(-1)
-
-
 class _Replay:
     """Follows the device through updates from what debug_read_scene("tris") and mesh_order() show before and after each of them."""
 
@@ -141,23 +132,6 @@ def _bend_mesh():
     for a in (v, f, bi, w):
         a.setflags(write=False)
     return v, f, bi, w
-
-
-def _bones(k):
-    """Step k of the bend: bone 1 turned about z by 0.12 rad per step -- its end of the mesh moves by a few pixels of a 64 x 48 frame."""
-    a = 0.12 * k
-    M = np.eye(4)
-    M[:3, :3] = [[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
-    return np.stack([IDENT, np.ascontiguousarray(M.T, f32).reshape(-1)]).astype(f32)
-
-
-def _placed_turned():
-    """The default placement turned about y and stretched: column-major, as the library takes it."""
-    c, s = np.cos(0.6), np.sin(0.6)
-    M = np.eye(4)
-    M[:3, :3] = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]) @ np.diag([0.55, 0.5, 0.45])
-    M[:3, 3] = [-2.0, 1.5, 0.0]
-    return np.ascontiguousarray(M.T, f32).reshape(-1)
 
 
 def _skin_step(b, k):

@@ -12,27 +12,16 @@ import torch
 
 import opengl_raytracing_amd as rt
 import scenes
+from mesh_fixtures import flat as _flat, sphere as _sphere, two_bone_skin as _two_bone_skin
 from test_gpu_dynamic_mesh import _mesh, _model, _ntris
 from test_gpu_mesh_motion import H, TARGETS, W, _bones, _dev, _placed_turned, _refused, _rows, _same, _skin_step, _turn, _xy
 from test_gpu_mesh_refit import _set_qnodes
-from test_mesh_normals_host import _fan, flat_grid
+from test_mesh_normals_host import _fan
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 IDENT = np.eye(4, dtype=f32).reshape(-1)
-
-
-def _two_bone_skin(v):
-    """Two bones blended along x: (bone_idx [V,4], weights [V,4])."""
-    x = v[:, 0]
-    span = max(float(x.max() - x.min()), 1e-6)
-    t = np.clip((x - x.min()) / f32(span) * f32(2.0) - f32(0.5), 0, 1).astype(f32)
-    w = np.zeros((v.shape[0], 4), f32)
-    w[:, 0], w[:, 1] = f32(1.0) - t, t
-    bi = np.zeros((v.shape[0], 4), np.uint16)
-    bi[:, 1] = 1
-    return bi, w
 
 
 def _device_normals(b):
@@ -107,37 +96,6 @@ def test_normals_equal_the_host_definition(monkeypatch, mesh, qnodes):
 
 
 # ---------------------------------------------------------------- the animated sphere of the frame and query tests
-@functools.lru_cache(maxsize=None)
-def _sphere():
-    """The 1 280-triangle icosphere with two bones blended along x, read only."""
-    v, f = rt.meshgen.icosphere(3)
-    v = np.ascontiguousarray(v, f32)
-    f = np.ascontiguousarray(f, np.uint32).reshape(-1)
-    bi, w = _two_bone_skin(v)
-    for a in (v, f, bi, w):
-        a.setflags(write=False)
-    return v, f, bi, w
-
-
-@functools.lru_cache(maxsize=None)
-def _flat():
-    """The flat anchor: a floor at y = 1 facing up and, two units above it, a ceiling facing down, both grids of unit right triangles at integer
-    coordinates in front of the close-up camera -> (positions, indices), read only.  Bounce and AO rays from one meet the other."""
-    nx, nz = 6, 5
-    v, f = flat_grid(nx, nz)
-    floor = (v + np.array([-5, 1, -4], f32)).astype(f32)
-    ceiling = (v + np.array([-5, 3, -4], f32)).astype(f32)
-    at = lambda i, j: v.shape[0] + i * (nz + 1) + j      # noqa: E731
-    f2 = []                                                                     # e1 = (0, 0, +-1), e2 = (-+1, 0, 0): cross(e1, e2) = (+0, -1, +0) exactly
-    for i in range(nx):
-        for j in range(nz):
-            f2 += [at(i + 1, j), at(i + 1, j + 1), at(i, j), at(i, j + 1), at(i, j), at(i + 1, j + 1)]
-    v, f = np.concatenate([floor, ceiling]), np.concatenate([f, np.array(f2, np.uint32)]).astype(np.uint32)
-    for a in (v, f):
-        a.setflags(write=False)
-    return v, f
-
-
 def _animated(b, normals, motion=False):
     v, f, bi, w = _sphere()
     b.upload_env(scenes.tiny_env(8))

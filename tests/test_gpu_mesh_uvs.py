@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import opengl_raytracing_amd as rt
+from mesh_fixtures import random_texture as _random_texture, random_uvs as _random_uvs
 from test_gpu_dynamic_mesh import _mesh, _model, _ntris
 from test_gpu_mesh_colors import PIPELINES, _animated, _flat_scene, _frame, _random_colors, _uniforms
 from test_gpu_mesh_motion import H, TARGETS, W, _dev, _placed_turned, _refused, _rows, _same, _skin_step, _turn, _xy
@@ -23,14 +24,6 @@ f32 = np.float32
 IDENT = np.eye(4, dtype=f32).reshape(-1)
 FLAGS = tuple(range(8))
 WHITE = np.full((2, 3, 4), 255, np.uint8)
-
-
-def _random_uvs(nv, seed):
-    return np.random.default_rng(seed).uniform(-1.5, 2.5, (nv, 2)).astype(f32)
-
-
-def _random_texture(w, h, seed):
-    return np.random.default_rng(seed).integers(0, 256, (h, w, 4)).astype(np.uint8)
 
 
 def _device_uvs(b):

@@ -1,0 +1,182 @@
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels and
+// their _host twins.  Host code only: rt_wave.hip and rt_scene_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "rt_context.hpp"
+
+using namespace rtd;
+using namespace rtapi;
+
+namespace {
+
+// What every query checks of its arguments, in the order the entry points have always checked it.  flags: the scene queries' (0 otherwise); xy != null: pixel
+// rays (rt_pick_pixels), else origins / dirs.  ownBVH: rt_trace_rays, which checks the ray arrays' 2^32-float bound last and needs an uploaded BVH.
+int query_args(RtContext *c, const char *what, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride, const int32_t *xy,
+               const float *tMax, int n, const RtHit *hits, const uint8_t *occluded, bool ownBVH) {
+    if (kind != RT_QUERY_CLOSEST && kind != RT_QUERY_ANY) return fail(c, RT_ERR_INVALID, "%s: kind %d (RT_QUERY_CLOSEST or RT_QUERY_ANY)", what, kind);
+    if (flags & ~(RT_QUERY_SKIP_GLASS | RT_QUERY_SKIP_MARKER)) return fail(c, RT_ERR_INVALID, "%s: flags 0x%x (RT_QUERY_SKIP_*)", what, flags);
+    if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
+    if (xy) {
+        if ((size_t)n * 2 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the pixel array exceeds 2^32 entries", what);
+    } else {
+        if (originStride < 3 || dirStride < 3) return fail(c, RT_ERR_INVALID, "%s: strides %d / %d floats (at least 3)", what, originStride, dirStride);
+        if (n > 0 && (!origins || !dirs)) return fail(c, RT_ERR_INVALID, "%s: null ray arrays", what);
+    }
+    const bool tooLong = !xy && (size_t)(n > 0 ? n - 1 : 0) * (size_t)std::max(originStride, dirStride) + 3 > ((size_t)1 << 32);
+    if (tooLong && !ownBVH) return fail(c, RT_ERR_INVALID, "%s: the ray arrays exceed 2^32 floats", what);
+    if (kind == RT_QUERY_ANY && !tMax) return fail(c, RT_ERR_INVALID, "%s: any-hit queries need tMax", what);
+    if (n > 0 && kind == RT_QUERY_CLOSEST && !hits) return fail(c, RT_ERR_INVALID, "%s: closest-hit queries need hits", what);
+    if (n > 0 && kind == RT_QUERY_ANY && !occluded) return fail(c, RT_ERR_INVALID, "%s: any-hit queries need occluded", what);
+    if (tooLong) return fail(c, RT_ERR_INVALID, "%s: the ray arrays exceed 2^32 floats", what);
+    if (ownBVH && (c->nNodes <= 0 || c->nTris <= 0)) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
+    return RT_OK;
+}
+
+// The query scratch (allocated on the first query) and rt_stream()'s stream, which first waits for the previous query if that ran on another stream
+int query_begin(RtContext *c, hipStream_t &st) {
+    (void)hipSetDevice(c->cfg.device);
+    st = api_stream(c);   // rt_stream()
+    if (!c->dQueryFrame) {
+        HIP_TRY(c, hipMalloc(&c->dQueryFrame, sizeof(DevFrame)));
+        HIP_TRY(c, hipMalloc(&c->dQueryHeads, rt_wave_head_words() * sizeof(uint32_t)));
+        // on the query's own stream: the lanes do not synchronise with the null stream, and a memset there can land after the first query's kernels
+        // have written their uniforms into the scratch
+        HIP_TRY(c, hipMemsetAsync(c->dQueryFrame, 0, sizeof(DevFrame), st));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->queryDone, hipEventDisableTiming));
+    }
+    if (c->queryStream && c->queryStream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->queryDone, 0));   // the scratch is free again
+    return RT_OK;
+}
+int query_end(RtContext *c, hipStream_t st) {
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->queryDone, st));
+    c->queryStream = st;
+    return RT_OK;
+}
+
+// ---- scene queries and pixel picking: the analytic leg (rt_scene_query.hip) into the caller's outputs, then the mesh leg through the frames'
+// persistent traversal launch (SceneSrc).  Shares rt_trace_rays' scratch; touches no frame state.
+// Checks everything before any device work; `mesh` = the scene has a mesh leg.
+int scene_query_args(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs,
+                     int dirStride, const int32_t *xy, const float *tMax, int n, const RtHit *hits, const uint8_t *occluded, bool &mesh) {
+    if (!u) return fail(c, RT_ERR_INVALID, "%s: null uniforms", what);
+    const int rc = query_args(c, what, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, false);
+    if (rc != RT_OK) return rc;
+    // the mesh as render_frames_impl sees it
+    const bool meshMode = u->useBVH == 1 || u->useBVH == RT_SCENE_HYBRID;
+    mesh = meshMode && u->nodeCount > 0 && u->triCount > 0;
+    if (mesh && (c->nNodes == 0 || u->nodeCount > c->nNodes || u->triCount > c->nTris))
+        return fail(c, RT_ERR_STATE, "%s: uniforms name %d nodes / %d tris, uploaded %d / %d", what, u->nodeCount, u->triCount, c->nNodes, c->nTris);
+    return RT_OK;
+}
+
+int scene_query(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                const int32_t *xy, const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    bool mesh = false;
+    const int rc = scene_query_args(c, what, u, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)xy | (uintptr_t)tMax | (uintptr_t)objects | (uintptr_t)normals | (uintptr_t)points) & 3u)
+        return fail(c, RT_ERR_INVALID, "%s: float and int32 arrays must be 4-byte aligned", what);
+    if (kind == RT_QUERY_CLOSEST && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "%s: hits must be 16-byte aligned (one 16-byte store per ray)", what);
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    DevScene sc = make_dev_scene(c);
+    if (!mesh) sc.hasBVH = 0;
+    const bool any = kind == RT_QUERY_ANY;
+    SceneRays r;
+    r.o = xy ? nullptr : origins; r.d = xy ? nullptr : dirs; r.os = originStride; r.ds = dirStride; r.xy = xy; r.tm = tMax; r.n = (uint32_t)n;
+    r.hits = any ? nullptr : reinterpret_cast<float4 *>(hits);
+    r.objects = any ? nullptr : objects; r.normals = any ? nullptr : normals; r.points = any ? nullptr : points; r.occ = any ? occluded : nullptr;
+    rt_scene_query_analytic(st, *u, sc, flags, r, c->dQueryFrame, c->dQueryHeads);
+    const uint32_t built = mesh ? rt_wave_trace_scene(st, c->cus, c->treeDepth, c->dQueryFrame, sc, u->useBVH == RT_SCENE_HYBRID, r, u->inf, c->dQueryHeads) : 1u;
+    const int end = query_end(c, st);
+    return end != RT_OK || built ? end : fail(c, RT_ERR_UNSUPPORTED, "scene query: the library holds no k_trace build for the chosen options");
+}
+
+// host arrays: staged through the context's buffer (origins | dirs | xy | tMax | hits / occluded | objects | normals | points; the ray arrays keep their
+// strides), then synchronised
+int scene_query_host(RtContext *c, const char *what, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs,
+                     int dirStride, const int32_t *xy, const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    bool mesh = false;
+    const int rc = scene_query_args(c, what, u, kind, flags, origins, originStride, dirs, dirStride, xy, tMax, n, hits, occluded, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    const bool any = kind == RT_QUERY_ANY;
+    const size_t N = (size_t)n;
+    const StageSeg segs[] = {{origins, xy ? 0 : ((N - 1) * originStride + 3) * 4, false}, {dirs, xy ? 0 : ((N - 1) * dirStride + 3) * 4, false},
+                             {xy, xy ? N * 8 : 0, false}, {tMax, tMax ? N * 4 : 0, false},
+                             {any ? (void *)occluded : (void *)hits, any ? N : N * sizeof(RtHit), true}, {objects, (!any && objects) ? N * 4 : 0, true},
+                             {normals, (!any && normals) ? N * 12 : 0, true}, {points, (!any && points) ? N * 12 : 0, true}};
+    return staged(c, what, segs, [&](void *const *d) {
+        return scene_query(c, what, u, kind, flags, (const float *)d[0], originStride, (const float *)d[1], dirStride, (const int32_t *)d[2], (const float *)d[3], n,
+                           any ? nullptr : (RtHit *)d[4], (int32_t *)d[5], (float *)d[6], (float *)d[7], any ? (uint8_t *)d[4] : nullptr);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- ray queries: user rays through the frames' persistent traversal launch; reads the BVH, touches no frame state
+int rt_trace_rays(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
+                  RtHit *hits, float *normals, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = query_args(c, "rt_trace_rays", kind, 0, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, occluded, true);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)tMax | (uintptr_t)normals) & 3u) return fail(c, RT_ERR_INVALID, "rt_trace_rays: float arrays must be 4-byte aligned");
+    if (kind == RT_QUERY_CLOSEST && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "rt_trace_rays: hits must be 16-byte aligned (one 16-byte store per ray)");
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    const DevScene sc = make_dev_scene(c);
+    const uint32_t built = rt_wave_trace_query(st, c->cus, c->treeDepth, c->dQueryFrame, sc, kind == RT_QUERY_ANY, origins, originStride, dirs, dirStride, tMax, eps, inf,
+                                               (uint32_t)n, hits, normals, occluded, c->dQueryHeads);
+    const int end = query_end(c, st);
+    return end != RT_OK || built ? end : fail(c, RT_ERR_UNSUPPORTED, "rt_trace_rays: the library holds no k_trace build for the chosen options");
+}
+
+int rt_trace_rays_host(RtContext *c, int kind, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
+                       RtHit *hits, float *normals, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = query_args(c, "rt_trace_rays_host", kind, 0, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, occluded, true);
+    if (rc != RT_OK || n == 0) return rc;
+    // staging layout: origins | dirs | tMax | hits / occluded | normals; the ray arrays keep their strides
+    const bool any = kind == RT_QUERY_ANY;
+    const size_t N = (size_t)n;
+    const StageSeg segs[] = {{origins, ((N - 1) * originStride + 3) * 4, false}, {dirs, ((N - 1) * dirStride + 3) * 4, false}, {tMax, tMax ? N * 4 : 0, false},
+                             {any ? (void *)occluded : (void *)hits, any ? N : N * sizeof(RtHit), true}, {normals, (!any && normals) ? N * 12 : 0, true}};
+    return staged(c, "rt_trace_rays_host", segs, [&](void *const *d) {
+        return rt_trace_rays(c, kind, (const float *)d[0], originStride, (const float *)d[1], dirStride, (const float *)d[2], eps, inf, n,
+                             any ? nullptr : (RtHit *)d[3], (float *)d[4], any ? (uint8_t *)d[3] : nullptr);
+    });
+}
+
+int rt_trace_scene_rays(RtContext *c, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                        const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    return scene_query(c, "rt_trace_scene_rays", u, kind, flags, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, objects, normals, points, occluded);
+}
+
+int rt_pick_pixels(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, RtHit *hits, int32_t *objects, float *normals, float *points) {
+    if (!c) return RT_ERR_INVALID;
+    if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels: null pixel array");
+    return scene_query(c, "rt_pick_pixels", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals, points, nullptr);
+}
+
+int rt_trace_scene_rays_host(RtContext *c, const RtUniforms *u, int kind, int flags, const float *origins, int originStride, const float *dirs, int dirStride,
+                             const float *tMax, int n, RtHit *hits, int32_t *objects, float *normals, float *points, uint8_t *occluded) {
+    if (!c) return RT_ERR_INVALID;
+    return scene_query_host(c, "rt_trace_scene_rays_host", u, kind, flags, origins, originStride, dirs, dirStride, nullptr, tMax, n, hits, objects, normals, points,
+                            occluded);
+}
+
+int rt_pick_pixels_host(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, RtHit *hits, int32_t *objects, float *normals, float *points) {
+    if (!c) return RT_ERR_INVALID;
+    if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels_host: null pixel array");
+    return scene_query_host(c, "rt_pick_pixels_host", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals,
+                            points, nullptr);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// rt_context.hpp -- private to the C ABI's translation units (rt_api.hip, rt_api_mesh.hip): the context, how a call fails, and the
-// helpers both files need.  Everything here is host code and has internal names: the exported rt_* set is include/rt_mi355.h's alone.
+// rt_context.hpp -- private to the C ABI's translation units (rt_api.hip and rt_api_*.hip): the context, how a call fails, and the
+// helpers more than one of them needs.  Everything here is host code and has internal names: the exported rt_* set is include/rt_mi355.h's alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -98,7 +98,7 @@ struct RtContext {
     hipStream_t queryStream = nullptr;   // stream of the last query (null: none yet)
     int giBounces = 1;   // EXTENSION, rt_set_extension
     int envFilter = 0;   // rt_set_extension: cube-map filter model (0 exact fp32 weights, 1 coordinates rounded to 1/256 texel)
-    // tile-parallel exchange owned by the library (rt_comm.cpp): RCCL communicator + per-lane gather buffers on the gathering rank
+    // tile-parallel exchange owned by the library (rt_api_exchange.hip): RCCL communicator + per-lane gather buffers on the gathering rank
     void *comm = nullptr;                               // ncclComm_t
     void *dGathered[RT_MAX_LANES][4] = {};              // [lane][target]: worldSize blocks, rank-major
     void *dAssembled[RT_MAX_LANES][4] = {};             // [lane][target]: row-major frame of halfs
@@ -146,6 +146,36 @@ inline hipError_t sync_all(RtContext *c) {
 
 // rt_stream()'s stream: the one the most recent frame was enqueued on
 inline hipStream_t api_stream(const RtContext *c) { return c->lastStream ? c->lastStream : c->stream; }
+
+inline int last_lane(const RtContext *c) { return (c->writeIdx + c->nLanes - 1) % c->nLanes; }   // lane of the frame rendered last
+// Target `which` (RT_TARGET_*) of the frame a lane rendered and its channels; null / 0 for an unknown target.
+inline void *lane_target(RtContext *c, int lane, int which, int &ch) {
+    switch (which) {
+        case RT_TARGET_COLOR: ch = 4; return c->dColor[lane];
+        case RT_TARGET_MOTION: ch = 2; return c->dMotion[lane];
+        case RT_TARGET_GPOS: ch = 4; return c->dGPos[lane];
+        case RT_TARGET_GNRM: ch = 4; return c->dGNrm[lane];
+        default: ch = 0; return nullptr;
+    }
+}
+inline void *target_ptr(RtContext *c, int which, int &ch) { return lane_target(c, last_lane(c), which, ch); }
+
+// rt_api.hip: the frame geometry of a w x h framebuffer on rank `rank` of `world` (rt_resize), for a batch of one ...
+rtd::FrameGeom make_frame_geom(int w, int h, int rank, int world);
+// ... and k_frame_root_box on `st`: a scene a device rebuild installed has its root box on the device only, the descriptor at `fr` takes it from there
+void launch_frame_root_box(hipStream_t st, rtd::DevFrame *fr);
+
+// The per-lane tallies of the wavefront pipelines as one sum: fn is rt_wave_traced or one of its kin (rt_wave.hpp), v the K words it hands out.
+template <int K, class F> int sum_over_lanes(RtContext *c, const char *what, F fn, int reset, unsigned long long (&v)[K]) {
+    for (int k = 0; k < K; ++k) v[k] = 0;
+    for (int i = 0; i < c->nLanes; ++i) {
+        unsigned long long t[K];
+        const int rc = fn(c->wave[i], c->lanes[i], t, reset != 0);
+        if (rc != RT_OK) return fail(c, rc, "%s: %s", what, rt_wave_error(c->wave[i]));
+        for (int k = 0; k < K; ++k) v[k] += t[k];
+    }
+    return RT_OK;
+}
 
 inline rtd::DevScene make_dev_scene(const RtContext *c) {
     rtd::DevScene s;

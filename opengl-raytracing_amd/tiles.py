@@ -6,7 +6,7 @@ the world size); rank r of n owns tiles with
 globalTile % n == r, stored densely (localTile = globalTile // n), 256 pixels per tile in four 8x8
 quadrants (slot = q*64 + ly*8 + lx).  Every rank contributes an equally sized block (padded to
 ceil(nTiles/n) tiles) so one gather moves the frame; `assemble` is the numpy statement of the
-device un-tiling kernel (k_assemble in csrc/rt_api.hip)."""
+device un-tiling kernel (k_assemble in csrc/rt_api_exchange.hip)."""
 from __future__ import annotations
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""The arithmetic identity the fused closest-hit records rest on (csrc/rt_trace.hpp `slab_union`, csrc/rt_api.hip rt_upload_bvh "fused closest-hit records").
+"""The arithmetic identity the fused closest-hit records rest on (csrc/rt_trace.hpp `slab_union`, csrc/rt_scene_pack.cpp "fused closest-hit records").
 
 The reference's step at a node N tests the boxes of N's children A and B (rt_bvh.glsl:226-239, aabbHit :124-134).  The fused record of N holds the boxes of A's
 and B's CHILDREN only; A's box is the union of its children's (checked at upload), and the kernel derives A's slab values from the children's:
@@ -113,7 +113,7 @@ def test_builder_boxes_are_unions_of_their_childrens():
 
 
 def test_implicit_records_preorder_address():
-    """The address arithmetic of the implicit records (csrc/rt_api.hip "implicit records", csrc/rt_trace.hpp k_trace<.., IMPL>): in a perfect binary tree whose leaves sit at
+    """The address arithmetic of the implicit records (csrc/rt_scene_pack.cpp "implicit records", csrc/rt_trace.hpp k_trace<.., IMPL>): in a perfect binary tree whose leaves sit at
     depth D, the inner node reached by the left / right turns p (as a binary number, d bits) at depth d has the pre-order position  d - popcount(p) + (p << (D - d))  among
     the inner nodes -- a left child sits next to its parent, a right child behind the whole left subtree -- and the positions of all inner nodes are a permutation of
     0 .. 2^D - 2.  Checked against an explicit pre-order walk."""

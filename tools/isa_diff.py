@@ -8,7 +8,9 @@ Every function symbol of the OLD library's gfx950 code objects is disassembled (
 by instruction, encodings included; only the absolute addresses llvm-objdump prints in its comments and the "..." it prints for zero
 padding behind a section's last function are dropped (a kernel that merely moved inside its code object is the same code).  A symbol
 that disappeared is paired with a symbol of the same code object that only the NEW library has when their instruction streams are
-identical apart from the symbol's own name in branch-target comments, one to one, and reported as renamed (a template's arguments changed, its code did not).  Symbols only the NEW library has and
+identical apart from the symbol's own name in branch-target comments, one to one, and reported as renamed (a template's arguments changed, its code did not).
+A symbol that left its code object and appears in another one under the same name with identical instructions is reported as moved (its
+translation unit changed, its code did not).  Symbols only the NEW library has and
 that no such pair accounts for are listed as added.  Exit status 0 when no existing symbol changed or disappeared without an identical
 partner, 1 otherwise.  The code objects are read straight from the .hip_fatbin section (clang offload bundles, one per translation unit), so nothing beyond the ROCm LLVM tools
 is needed.
@@ -109,6 +111,23 @@ def pair_renamed(before, after, gone, added):
     return left, [k for k in added if k not in taken], renamed
 
 
+def pair_moved(before, after, gone, added):
+    """(gone, added, moved) with every removed symbol that another code object now holds under the same name and with identical instructions taken
+    out of both lists, one to one: its translation unit changed, its code did not."""
+    pool = {}
+    for k in added:
+        pool.setdefault((k[1], tuple(after[k])), []).append(k)
+    moved, left = [], []
+    for k in gone:
+        partners = pool.get((k[1], tuple(before[k])))
+        if partners:
+            moved.append((k, partners.pop(0)))
+        else:
+            left.append(k)
+    taken = {k2 for _, k2 in moved}
+    return left, [k for k in added if k not in taken], moved
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old", nargs="?")
@@ -130,11 +149,14 @@ def main():
         added = [k for k in after if k not in before]
         same = len(before) - len(changed) - len(gone)
         gone, added, renamed = pair_renamed(before, after, gone, added)
+        gone, added, moved = pair_moved(before, after, gone, added)
         print(f"old: {old}\nnew: {a.new}")
         print(f"symbols before: {len(before)} in {len({k[0] for k in before})} code objects; identical: {same}; renamed: {len(renamed)}; "
-              f"changed: {len(changed)}; removed: {len(gone)}; added: {len(added)}")
+              f"moved: {len(moved)}; changed: {len(changed)}; removed: {len(gone)}; added: {len(added)}")
         for k, k2 in renamed:
             print(f"  renamed  [{k[0]}] {k[1]} -> {k2[1]}  ({len(before[k])} instructions)")
+        for k, k2 in moved:
+            print(f"  moved    [{k[0]}] -> [{k2[0]}] {k[1]}  ({len(before[k])} instructions)")
         for k in changed:
             print(f"  CHANGED  [{k[0]}] {k[1]}  ({len(before[k])} -> {len(after[k])} instructions)")
         for k in gone:

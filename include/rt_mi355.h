@@ -521,6 +521,40 @@ int rt_trace_scene_rays_host(RtContext *ctx, const RtUniforms *u, int kind, int 
 int rt_pick_pixels_host(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n,
                         RtHit *hits, int32_t *objects, float *normals, float *points);
 
+/* ---------------------------------------------------------------- multi-hit queries: the K nearest hits and the hit count per ray
+ * What lies behind the first surface: the layers under a cursor, every part a probe passes through, entry / exit pairs, the crossing count.
+ *   For ray i with the limit T = tMax ? tMax[i] : inf, S is the set of triangles traceBVHShadow's loop (shaders/rt/rt_bvh.glsl:260-304) would accept
+ * at the limit T with its `return true` removed: the root and every node on the way to the triangle's leaf pass aabbHit(...) && tmin <= T, and the
+ * triangle passes triHit(ro, rd, T_i, T) with uEPS = eps.  The order of the visit is no part of it.  Nothing is culled against a hit already found
+ * (DESIGN.md 20.2): the walk visits every box along the ray up to T, so bound the work with tMax.
+ *   counts[i] = |S|.  hits[i * maxHits + j], j < min(maxHits, |S|), are the maxHits smallest elements of S under (key(t), prim) ascending: prim is the row
+ * of tris12 as in rt_trace_rays, key(t) = bits(t) ^ (bits(t) >> 31 ? 0xFFFFFFFF : 0x80000000) -- the numeric order for every ordinary t, and an order
+ * for the NaN t a degenerate ray gets through triHit's comparisons (positive NaNs last).  A record is {t, prim, u, v} with u, v as rt_trace_rays
+ * computes them; slots j >= |S| hold the miss record {inf, -1, 0, 0}.  tMax[i] < 0 marks an empty slot: count 0, every slot a miss.  maxHits == 0 asks
+ * for the counts alone.  The records are RtHit's: the flattened array is an input of rt_mesh_hit_parts, _normals, _colors, _uvs, _texels and
+ * _prev_points as it stands (a miss answers zeros or -1 there).
+ *   counts[i] > 0 exactly when rt_trace_rays' RT_QUERY_ANY says occluded at the same tMax, and without tMax exactly when RT_QUERY_CLOSEST hits; the
+ * closest answer is an element of S, so key(hits[i * maxHits].t) <= key(closest t).
+ *   rt_multi_hits is the definition: host arrays, no context, no GPU; nodes12 / tris12 as rt_build_bvh returns them (a single leaf is a tree).  It
+ * returns RT_ERR_INVALID for the refusals below that apply to it, and for nodes that are no tree over the rows.
+ *   rt_trace_rays_multi: device pointers; enqueued on rt_stream()'s stream; no host synchronisation and, after the context's first query, no allocation.
+ * Rays and strides as rt_trace_rays.  hits: n * maxHits records, 16-byte aligned, required unless maxHits == 0; counts may be NULL unless maxHits == 0.
+ * RT_ERR_INVALID: maxHits outside 0 .. RT_MULTI_HIT_MAX, n < 0, strides below 3, null or misaligned arrays, n * maxHits beyond INT32_MAX, ray arrays
+ * beyond 2^32 floats.  RT_ERR_STATE: no BVH uploaded.  A refused call writes nothing; n == 0 is a no-op.  Frame state stays untouched as with rt_trace_rays.
+ *   rt_pick_pixels_multi: pixel (xy[2i], xy[2i + 1]) along the frame's own primary ray, built on the device exactly as rt_pick_pixels builds it (jitter
+ * included), with eps = u->eps and the limit u->inf.  The BVH scene only: u->useBVH != 1 is RT_ERR_INVALID; u->nodeCount / u->triCount are checked as
+ * rt_pick_pixels checks them (either 0: no mesh, every count 0).
+ *   The _host twins take host pointers, stage through the context's buffer and synchronise. */
+#define RT_MULTI_HIT_MAX 32
+int rt_multi_hits(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *origins, int originStride,
+                  const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n, int maxHits, RtHit *hits, int32_t *counts);
+int rt_trace_rays_multi(RtContext *ctx, const float *origins, int originStride, const float *dirs, int dirStride,
+                        const float *tMax /* may be NULL */, float eps, float inf, int n, int maxHits, RtHit *hits, int32_t *counts);
+int rt_trace_rays_multi_host(RtContext *ctx, const float *origins, int originStride, const float *dirs, int dirStride,
+                             const float *tMax, float eps, float inf, int n, int maxHits, RtHit *hits, int32_t *counts);
+int rt_pick_pixels_multi(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts);
+int rt_pick_pixels_multi_host(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

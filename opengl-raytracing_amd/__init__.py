@@ -260,6 +260,7 @@ class RtRasterStats(_Struct):
 
 
 RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1   # rt_trace_rays kinds
+RT_MULTI_HIT_MAX = 32                    # most records per ray of the multi-hit queries
 RT_QUERY_SKIP_GLASS, RT_QUERY_SKIP_MARKER = 1, 2   # rt_trace_scene_rays flags
 # rt_trace_scene_rays / rt_pick_pixels objects: the device's material ids
 RT_OBJECT_NONE, RT_OBJECT_FLOOR, RT_OBJECT_ALBEDO_SPHERE, RT_OBJECT_GLASS_SPHERE, RT_OBJECT_MIRROR_SPHERE, RT_OBJECT_POINT_LIGHT, RT_OBJECT_MESH = -1, 0, 1, 2, 3, 4, 5
@@ -352,6 +353,14 @@ SIGNATURES = {
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_pick_pixels": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_pick_pixels_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_multi_hits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
+                                C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_trace_rays_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
+    "rt_trace_rays_multi_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p]),
+    "rt_pick_pixels_multi": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_pick_pixels_multi_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1361,6 +1370,67 @@ def _query_invalid(msg):
     return RtError(RT_ERR_INVALID, f"trace_rays: {msg}")
 
 
+class MultiHits:
+    """Answers of multi_hits, Renderer.trace_rays_multi and Renderer.pick_multi: `hits` [N,K,4] float32 -- K RtHit records per ray,
+    nearest first, the miss record {inf, -1, 0, 0} past the ray's last hit -- with the views t [N,K], prim [N,K] int32 and uv [N,K,2], and `count`
+    [N] int32, the number of all the ray's hits, which may exceed K.  hits.reshape(-1, 4) is an input of the mesh_hit_* queries as it stands.
+    numpy arrays or torch tensors, as the rays were."""
+
+    def __init__(self, hits, count):
+        self.hits = hits
+        self.count = count
+        self.t = hits[:, :, 0]
+        if isinstance(hits, np.ndarray):
+            self.prim = hits.view(np.int32)[:, :, 1]
+        else:
+            import torch
+            self.prim = hits.view(torch.int32)[:, :, 1]
+        self.uv = hits[:, :, 2:4]
+
+    def __len__(self):
+        return self.hits.shape[0]
+
+
+def _multi_k(max_hits):
+    k = int(max_hits)
+    if not 0 <= k <= RT_MULTI_HIT_MAX:
+        raise _query_invalid(f"max_hits = {k} (0 .. RT_MULTI_HIT_MAX = {RT_MULTI_HIT_MAX})")
+    return k
+
+
+def _numpy_rays(origins, dirs, tmax):
+    """The checks of Renderer.trace_rays on numpy rays -> (n, origin stride, dir stride, contiguous tmax)."""
+    for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
+        if not isinstance(a, np.ndarray) and a is not None:
+            raise _query_invalid(f"{name} must be a numpy array")
+        if a is not None and a.dtype != np.float32:
+            raise _query_invalid(f"{name} must be float32, got {a.dtype}")
+    n = origins.shape[0] if origins.ndim == 2 else -1
+    os_ = Renderer._ray_rows("origins", origins, 4, origins.strides)
+    ds = Renderer._ray_rows("dirs", dirs, 4, dirs.strides, n)
+    if tmax is not None:
+        if tmax.shape != (n,):
+            raise _query_invalid(f"tmax must be [{n}], got shape {tmax.shape}")
+        tmax = np.ascontiguousarray(tmax)
+    return n, os_, ds, tmax
+
+
+def multi_hits(nodes12, tris12, origins, dirs, tmax=None, max_hits=4, eps=1e-4, inf=1e30) -> MultiHits:
+    """The definition of the multi-hit query (rt_multi_hits), on the host and without a context: per ray the max_hits nearest of
+    the triangles traceBVHShadow's walk of (nodes12, tris12) would accept up to tmax[i] (inf without tmax), ordered by (t, prim), and the count of
+    all of them.  Rays as Renderer.trace_rays takes them (numpy); tmax[i] < 0 marks an empty slot."""
+    k = _multi_k(max_hits)
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    n, os_, ds, tmax = _numpy_rays(origins, dirs, tmax)
+    hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    rc = lib().rt_multi_hits(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, p(hits), C.c_void_p(count.ctypes.data))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_multi_hits: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_multi_hits")
+    return MultiHits(hits, count)
+
+
 # ------------------------------------------------------------------------------------ device side
 class Renderer:
     """One RtContext.  Mirrors the reference's per-frame call sequence."""
@@ -2202,6 +2272,66 @@ class Renderer:
             raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
         dev = self._query_device(xy, dtype=torch.int32)
         return self._scene_query_torch(dev, u, RT_QUERY_CLOSEST, 0, None, xy, None, xy.shape[0], normals, points)
+
+    def trace_rays_multi(self, origins, dirs, tmax=None, max_hits=4, eps=1e-4, inf=1e30) -> MultiHits:
+        """The max_hits nearest hits and the hit count of every ray against the uploaded BVH (rt_trace_rays_multi) -> MultiHits, equal
+        to multi_hits on the uploaded arrays bit for bit.  Rays, tmax, eps / inf and the numpy / torch paths (stream ordering and lifetimes included)
+        as trace_rays.  The walk visits every box along the ray up to tmax: bound the work with tmax.  max_hits = 0 asks for the counts alone."""
+        k = _multi_k(max_hits)
+        arrays = [a for a in (origins, dirs, tmax) if a is not None]
+        if all(isinstance(a, np.ndarray) for a in arrays):
+            n, os_, ds, tmax = _numpy_rays(origins, dirs, tmax)
+            hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
+            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+            self._check(lib().rt_trace_rays_multi_host(self._h, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, p(hits), p(count)))
+            return MultiHits(hits, count)
+        import torch
+        if not all(isinstance(a, torch.Tensor) for a in arrays):
+            raise _query_invalid("origins, dirs and tmax must all be numpy arrays or all torch tensors")
+        dev = self._query_device(origins, dirs, tmax, dtype=torch.float32)
+        n = origins.shape[0] if origins.dim() == 2 else -1
+        os_ = self._ray_rows("origins", origins, 1, origins.stride())
+        ds = self._ray_rows("dirs", dirs, 1, dirs.stride(), n)
+        if tmax is not None and (tuple(tmax.shape) != (n,) or (n > 1 and tmax.stride(0) != 1)):
+            raise _query_invalid(f"tmax must be a contiguous [{n}] tensor, got shape {tuple(tmax.shape)}")
+        return self._multi_torch(dev, n, k, (origins, dirs, tmax),
+                                 lambda p, hits, count: lib().rt_trace_rays_multi(self._h, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, hits, count))
+
+    def pick_multi(self, u, xy, max_hits=4) -> MultiHits:
+        """The max_hits nearest hits and the hit count under pixels (x, y) (int32 [N,2], row 0 = bottom) of a BVH frame rendered with uniforms `u`
+        (rt_pick_pixels_multi): each along the frame's own primary ray, jitter included, up to u.inf -> MultiHits.  numpy or torch, as pick."""
+        k = _multi_k(max_hits)
+        if isinstance(xy, np.ndarray):
+            if xy.dtype != np.int32 or xy.ndim != 2 or xy.shape[1] != 2:
+                raise _query_invalid(f"xy must be int32 [N,2], got {xy.dtype} {xy.shape}")
+            xy = np.ascontiguousarray(xy)
+            n = xy.shape[0]
+            hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
+            p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+            self._check(lib().rt_pick_pixels_multi_host(self._h, C.byref(u), p(xy), n, k, p(hits), p(count)))
+            return MultiHits(hits, count)
+        import torch
+        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+            raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
+        dev = self._query_device(xy, dtype=torch.int32)
+        n = xy.shape[0]
+        return self._multi_torch(dev, n, k, (xy,), lambda p, hits, count: lib().rt_pick_pixels_multi(self._h, C.byref(u), p(xy), n, k, hits, count))
+
+    def _multi_torch(self, dev, n, k, inputs, call):
+        """The zero-copy path of the multi-hit queries: stream ordering and lifetimes exactly as _trace_rays_torch."""
+        import torch
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the rays (and the outputs' allocation) are ready before the query starts
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+        self._check(call(p, p(hits), p(count)))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers
+        for a in inputs:                     # (never tied to the library stream: it dies with the context)
+            if a is not None:
+                a.record_stream(cur)
+        return MultiHits(hits, count)
 
     def _query_device(self, *arrays, dtype):
         import torch

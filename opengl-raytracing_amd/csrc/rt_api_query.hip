@@ -1,10 +1,12 @@
-// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels and
-// their _host twins.  Host code only: rt_wave.hip and rt_scene_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
+// rt_trace_rays_multi, rt_pick_pixels_multi and their _host twins.  Host code only: rt_wave.hip, rt_scene_query.hip and rt_multi_hit.hip launch, this file
+// checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "rt_context.hpp"
+#include "rt_multi_hit.hpp"
 
 using namespace rtd;
 using namespace rtapi;
@@ -115,6 +117,52 @@ int scene_query_host(RtContext *c, const char *what, const RtUniforms *u, int ki
     });
 }
 
+// ---- multi-hit queries: the K nearest hits and the hit count per ray, by a traversal of their own (rt_multi_hit.hip).  Share the queries'
+// scratch and event; touch no frame state.
+// What both multi-hit entries check of their outputs and counts, before anything is enqueued or written
+int multi_args(RtContext *c, const char *what, int n, int maxHits, const RtHit *hits, const int32_t *counts) {
+    if (maxHits < 0 || maxHits > RT_MULTI_HIT_MAX) return fail(c, RT_ERR_INVALID, "%s: maxHits = %d (0 .. RT_MULTI_HIT_MAX = %d)", what, maxHits, RT_MULTI_HIT_MAX);
+    if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
+    if (n > 0 && maxHits > 0 && !hits) return fail(c, RT_ERR_INVALID, "%s: maxHits > 0 needs hits", what);
+    if (n > 0 && maxHits == 0 && !counts) return fail(c, RT_ERR_INVALID, "%s: maxHits == 0 asks for the counts alone and needs counts", what);
+    if ((uint64_t)n * (uint64_t)maxHits > (uint64_t)INT32_MAX) return fail(c, RT_ERR_INVALID, "%s: n * maxHits exceeds INT32_MAX records", what);
+    return RT_OK;
+}
+int multi_aligned(RtContext *c, const char *what, const void *a, const void *b, const void *tMax, const RtHit *hits, const int32_t *counts) {
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)tMax | (uintptr_t)counts) & 3u) return fail(c, RT_ERR_INVALID, "%s: float and int32 arrays must be 4-byte aligned", what);
+    if ((uintptr_t)hits & 15u) return fail(c, RT_ERR_INVALID, "%s: hits must be 16-byte aligned (one 16-byte store per record)", what);
+    return RT_OK;
+}
+int multi_rays_args(RtContext *c, const char *what, const float *origins, int originStride, const float *dirs, int dirStride, int n, int maxHits, const RtHit *hits,
+                    const int32_t *counts) {
+    const int rc = multi_args(c, what, n, maxHits, hits, counts);
+    if (rc != RT_OK) return rc;
+    if (originStride < 3 || dirStride < 3) return fail(c, RT_ERR_INVALID, "%s: strides %d / %d floats (at least 3)", what, originStride, dirStride);
+    if (n > 0 && (!origins || !dirs)) return fail(c, RT_ERR_INVALID, "%s: null ray arrays", what);
+    if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)std::max(originStride, dirStride) + 3 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the ray arrays exceed 2^32 floats", what);
+    if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
+    return RT_OK;
+}
+// The pixel form: the frame's BVH scene only; u->nodeCount / u->triCount as scene_query_args checks them.  `mesh` = the scene has one.
+int multi_pick_args(RtContext *c, const char *what, const RtUniforms *u, const int32_t *xy, int n, int maxHits, const RtHit *hits, const int32_t *counts, bool &mesh) {
+    if (!u) return fail(c, RT_ERR_INVALID, "%s: null uniforms", what);
+    int rc = multi_args(c, what, n, maxHits, hits, counts);
+    if (rc != RT_OK) return rc;
+    if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "%s: null pixel array", what);
+    if (u->useBVH != 1) return fail(c, RT_ERR_INVALID, "%s: useBVH = %d -- multi-hit picking answers for the BVH scene only (useBVH == 1)", what, u->useBVH);
+    mesh = u->nodeCount > 0 && u->triCount > 0;
+    if (mesh && (c->nNodes == 0 || u->nodeCount > c->nNodes || u->triCount > c->nTris))
+        return fail(c, RT_ERR_STATE, "%s: uniforms name %d nodes / %d tris, uploaded %d / %d", what, u->nodeCount, u->triCount, c->nNodes, c->nTris);
+    return RT_OK;
+}
+int multi_launch(RtContext *c, bool mesh, const MultiHitQuery &q) {
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    HIP_TRY(c, rt_multi_hit_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), mesh, q));
+    return query_end(c, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -177,6 +225,60 @@ int rt_pick_pixels_host(RtContext *c, const RtUniforms *u, const int32_t *xy, in
     if (n > 0 && !xy) return fail(c, RT_ERR_INVALID, "rt_pick_pixels_host: null pixel array");
     return scene_query_host(c, "rt_pick_pixels_host", u, RT_QUERY_CLOSEST, 0, nullptr, 3, nullptr, 3, n > 0 ? xy : nullptr, nullptr, n, hits, objects, normals,
                             points, nullptr);
+}
+
+// ---- multi-hit queries
+int rt_trace_rays_multi(RtContext *c, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
+                        int maxHits, RtHit *hits, int32_t *counts) {
+    if (!c) return RT_ERR_INVALID;
+    int rc = multi_rays_args(c, "rt_trace_rays_multi", origins, originStride, dirs, dirStride, n, maxHits, hits, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    rc = multi_aligned(c, "rt_trace_rays_multi", origins, dirs, tMax, maxHits ? hits : nullptr, counts);
+    if (rc != RT_OK) return rc;
+    MultiHitQuery q = {};
+    q.o = origins; q.d = dirs; q.os = originStride; q.ds = dirStride; q.tm = tMax; q.n = (uint32_t)n; q.K = maxHits; q.eps = eps; q.inf = inf;
+    q.hits = maxHits ? reinterpret_cast<float4 *>(hits) : nullptr; q.counts = counts;
+    return multi_launch(c, true, q);
+}
+
+int rt_trace_rays_multi_host(RtContext *c, const float *origins, int originStride, const float *dirs, int dirStride, const float *tMax, float eps, float inf, int n,
+                             int maxHits, RtHit *hits, int32_t *counts) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = multi_rays_args(c, "rt_trace_rays_multi_host", origins, originStride, dirs, dirStride, n, maxHits, hits, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    // staging layout: origins | dirs | tMax | hits | counts; the ray arrays keep their strides
+    const size_t N = (size_t)n;
+    const StageSeg segs[] = {{origins, ((N - 1) * originStride + 3) * 4, false}, {dirs, ((N - 1) * dirStride + 3) * 4, false}, {tMax, tMax ? N * 4 : 0, false},
+                             {hits, N * maxHits * sizeof(RtHit), true}, {counts, counts ? N * 4 : 0, true}};
+    return staged(c, "rt_trace_rays_multi_host", segs, [&](void *const *d) {
+        return rt_trace_rays_multi(c, (const float *)d[0], originStride, (const float *)d[1], dirStride, (const float *)d[2], eps, inf, n, maxHits, (RtHit *)d[3],
+                                   (int32_t *)d[4]);
+    });
+}
+
+int rt_pick_pixels_multi(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts) {
+    if (!c) return RT_ERR_INVALID;
+    bool mesh = false;
+    int rc = multi_pick_args(c, "rt_pick_pixels_multi", u, xy, n, maxHits, hits, counts, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    rc = multi_aligned(c, "rt_pick_pixels_multi", xy, nullptr, nullptr, maxHits ? hits : nullptr, counts);
+    if (rc != RT_OK) return rc;
+    MultiHitQuery q = {};
+    q.xy = xy; q.cam = u; q.os = q.ds = 3; q.n = (uint32_t)n; q.K = maxHits; q.eps = u->eps; q.inf = u->inf;
+    q.hits = maxHits ? reinterpret_cast<float4 *>(hits) : nullptr; q.counts = counts;
+    return multi_launch(c, mesh, q);
+}
+
+int rt_pick_pixels_multi_host(RtContext *c, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts) {
+    if (!c) return RT_ERR_INVALID;
+    bool mesh = false;
+    const int rc = multi_pick_args(c, "rt_pick_pixels_multi_host", u, xy, n, maxHits, hits, counts, mesh);
+    if (rc != RT_OK || n == 0) return rc;
+    const size_t N = (size_t)n;
+    const StageSeg segs[] = {{xy, N * 8, false}, {hits, N * maxHits * sizeof(RtHit), true}, {counts, counts ? N * 4 : 0, true}};
+    return staged(c, "rt_pick_pixels_multi_host", segs, [&](void *const *d) {
+        return rt_pick_pixels_multi(c, u, (const int32_t *)d[0], n, maxHits, (RtHit *)d[1], (int32_t *)d[2]);
+    });
 }
 
 }  // extern "C"

@@ -555,6 +555,33 @@ int rt_trace_rays_multi_host(RtContext *ctx, const float *origins, int originStr
 int rt_pick_pixels_multi(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts);
 int rt_pick_pixels_multi_host(RtContext *ctx, const RtUniforms *u, const int32_t *xy, int n, int maxHits, RtHit *hits, int32_t *counts);
 
+/* ---------------------------------------------------------------- nearest-point queries: the closest surface point of the mesh per point
+ * How far a point is from the surface and where the nearest surface point lies: proximity and contact tests, snapping, projecting points onto the
+ * mesh, taking colour, UV or normal from the nearest surface point.
+ *   Point i is points[i * stride .. i * stride + 2] (stride >= 3 floats).  Its limit is L = +inf without maxDist, else maxDist[i] * maxDist[i] rounded
+ * once in float32; maxDist[i] < 0 or a non-finite coordinate marks an empty slot.  With lb(box, p) the squared distance from p to a box and d2(t) the
+ * squared distance from p to row t by Ericson's closest-point walk over the row as stored (DESIGN.md 21.1 has every operation),
+ *     e(t) = max(d2(t), lb(box(n), p) for every node n from the root to t's leaf)          (a NaN d2 stays NaN)
+ * and the answer is the triangle least under (e(t), prim) ascending among those with e(t) <= L: prim is the row of tris12 as in rt_trace_rays.  The
+ * order of the visit is no part of it.  e(t) differs from d2(t) only where rounding made a triangle look nearer than a box around it.
+ *   hits[i] = {t = e, prim, u, v}: t is the squared distance, the nearest point is v0 + u e1 + v e2 of the row; closest (3 floats per point, may be
+ * NULL) receives it.  No triangle within L, an empty slot or no scene: {+inf, -1, 0, 0} and a zero point (the float +inf: there is no uINF here).  The
+ * records are RtHit's: an input of rt_mesh_hit_parts, _normals, _colors, _uvs and _texels as it stands -- the part, smooth normal, colour, UV or texel
+ * of the nearest surface point.
+ *   rt_nearest_points is the definition: host arrays, no context, no GPU; nodes12 / tris12 as rt_build_bvh returns them (a single leaf is a tree).  It
+ * returns RT_ERR_INVALID for the refusals below that apply to it, and for nodes that are no tree over the rows.
+ *   rt_query_nearest: device pointers; enqueued on rt_stream()'s stream; no host synchronisation and, after the context's first query, no allocation.
+ * It walks the two-child records and triangle rows every scene form has, culling against its best: an unbounded query of a point far from the mesh
+ * costs more than one near it, so give maxDist where a bound is known.  visits (may be NULL): visits[i] = the number of boxes whose lb the walk
+ * evaluated for point i, 0 for an empty slot -- a diagnostic that depends on the visit order and is no part of the definition.  hits: n records,
+ * 16-byte aligned.  RT_ERR_INVALID: n < 0, a stride below 3, null or misaligned arrays, a point array beyond 2^32 floats.  RT_ERR_STATE: no BVH
+ * uploaded.  A refused call writes nothing; n == 0 is a no-op.  Frame state stays untouched as with rt_trace_rays.
+ *   The _host twin takes host pointers, stages through the context's buffer and synchronises. */
+int rt_nearest_points(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *points, int stride,
+                      const float *maxDist /* may be NULL */, int n, RtHit *hits, float *closest /* may be NULL */);
+int rt_query_nearest(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits);
+int rt_query_nearest_host(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

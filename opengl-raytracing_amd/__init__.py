@@ -361,6 +361,9 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "rt_pick_pixels_multi": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_pick_pixels_multi_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_nearest_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_query_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_query_nearest_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1431,6 +1434,59 @@ def multi_hits(nodes12, tris12, origins, dirs, tmax=None, max_hits=4, eps=1e-4, 
     return MultiHits(hits, count)
 
 
+class NearestPoints:
+    """Answers of nearest_points and Renderer.nearest_points: `hits` [N,4] float32 -- one RtHit record {e, prim, u, v} per point, the
+    miss record {+inf, -1, 0, 0} where no triangle lies within the limit -- with the views dist2 [N] (e: the squared distance), prim [N] int32 and
+    uv [N,2]; `points` [N,3], the nearest surface point v0 + u e1 + v e2 (zeros for a miss); `visits` [N] int32 or None.  hits is an input of the
+    mesh_hit_* queries as it stands.  numpy arrays or torch tensors, as the points were."""
+
+    def __init__(self, hits, points, visits=None):
+        self.hits = hits
+        self.points = points
+        self.visits = visits
+        self.dist2 = hits[:, 0]
+        if isinstance(hits, np.ndarray):
+            self.prim = hits.view(np.int32)[:, 1]
+        else:
+            import torch
+            self.prim = hits.view(torch.int32)[:, 1]
+        self.uv = hits[:, 2:4]
+
+    def __len__(self):
+        return self.hits.shape[0]
+
+
+def _numpy_points(points, max_dist):
+    """The checks of the nearest-point queries on numpy points -> (n, stride, contiguous max_dist)."""
+    for name, a in (("points", points), ("max_dist", max_dist)):
+        if not isinstance(a, np.ndarray) and a is not None:
+            raise _query_invalid(f"{name} must be a numpy array")
+        if a is not None and a.dtype != np.float32:
+            raise _query_invalid(f"{name} must be float32, got {a.dtype}")
+    stride = Renderer._ray_rows("points", points, 4, points.strides)
+    n = points.shape[0]
+    if max_dist is not None:
+        if max_dist.shape != (n,):
+            raise _query_invalid(f"max_dist must be [{n}], got shape {max_dist.shape}")
+        max_dist = np.ascontiguousarray(max_dist)
+    return n, stride, max_dist
+
+
+def nearest_points(nodes12, tris12, points, max_dist=None) -> NearestPoints:
+    """The definition of the nearest-point query (rt_nearest_points), on the host and without a context: per point the triangle of
+    (nodes12, tris12) least under (e, prim) with e <= max_dist[i]^2 (no limit without max_dist).  points: float32 [N,k], k >= 3, rows may be
+    strided (numpy); max_dist[i] < 0 or a non-finite coordinate marks an empty slot."""
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    n, stride, max_dist = _numpy_points(points, max_dist)
+    hits, closest = np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32)
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    rc = lib().rt_nearest_points(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(points), stride, p(max_dist), n, p(hits), p(closest))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_nearest_points: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_nearest_points")
+    return NearestPoints(hits, closest)
+
+
 # ------------------------------------------------------------------------------------ device side
 class Renderer:
     """One RtContext.  Mirrors the reference's per-frame call sequence."""
@@ -2332,6 +2388,42 @@ class Renderer:
             if a is not None:
                 a.record_stream(cur)
         return MultiHits(hits, count)
+
+    def nearest_points(self, points, max_dist=None, visits=False) -> NearestPoints:
+        """The nearest surface point of the uploaded BVH or the dynamic mesh for every point (rt_query_nearest) -> NearestPoints, equal
+        to nearest_points on the same arrays bit for bit.  points: float32 [N,k], k >= 3, rows may be strided; max_dist: float32 [N] or None
+        (max_dist[i] < 0 marks an empty slot).  An unbounded query far from the mesh costs more than one near it: give max_dist where a bound is
+        known.  visits=True also returns the number of boxes tested per point (a diagnostic).  numpy / torch paths, stream ordering and lifetimes
+        as trace_rays_multi."""
+        arrays = [a for a in (points, max_dist) if a is not None]
+        if all(isinstance(a, np.ndarray) for a in arrays):
+            n, stride, max_dist = _numpy_points(points, max_dist)
+            hits, closest = np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32)
+            vis = np.zeros(n, np.int32) if visits else None
+            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+            self._check(lib().rt_query_nearest_host(self._h, p(points), stride, p(max_dist), n, p(hits), p(closest), p(vis)))
+            return NearestPoints(hits, closest, vis)
+        import torch
+        if not all(isinstance(a, torch.Tensor) for a in arrays):
+            raise _query_invalid("points and max_dist must all be numpy arrays or all torch tensors")
+        dev = self._query_device(points, max_dist, dtype=torch.float32)
+        stride = self._ray_rows("points", points, 1, points.stride())
+        n = points.shape[0]
+        if max_dist is not None and (tuple(max_dist.shape) != (n,) or (n > 1 and max_dist.stride(0) != 1)):
+            raise _query_invalid(f"max_dist must be a contiguous [{n}] tensor, got shape {tuple(max_dist.shape)}")
+        hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        vis = torch.empty(n, dtype=torch.int32, device=dev) if visits else None
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the points (and the outputs' allocation) are ready before the query starts
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+        self._check(lib().rt_query_nearest(self._h, p(points), stride, p(max_dist), n, p(hits), p(closest), p(vis)))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers
+        for a in (points, max_dist):         # (never tied to the library stream: it dies with the context)
+            if a is not None:
+                a.record_stream(cur)
+        return NearestPoints(hits, closest, vis)
 
     def _query_device(self, *arrays, dtype):
         import torch

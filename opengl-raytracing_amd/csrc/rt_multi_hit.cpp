@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rt_mi355.h"
+#include "rt_bvh_tree.hpp"
 
 namespace {
 
@@ -53,9 +54,9 @@ inline bool tri_hit(V ro, V rd, const float *tri12, float eps, float tMax, float
     return true;
 }
 
-struct Node { int left, right, first, count; };   // nodeFetch, rt_bvh.glsl:91-102
-inline int to_index(float f) { return (f >= 0.0f && f < 2147483520.0f) ? (int)(f + 0.5f) : -1; }   // int(f + 0.5) of an index; -1 for what is none (negative, huge, NaN)
-inline Node node_fetch(const float *p) { return Node{to_index(p[3]), to_index(p[7]), to_index(p[8]), to_index(p[9])}; }
+using rtbvh::Node;   // a node's links, and the tree check rt_nearest.cpp shares (rt_bvh_tree.hpp)
+using rtbvh::node_fetch;
+using rtbvh::is_tree;
 
 // The monotone map of a float's bits: ascending keys are ascending t, -0 before +0, negative NaNs first and positive NaNs last
 inline uint32_t key_of(float t) {
@@ -65,26 +66,6 @@ inline uint32_t key_of(float t) {
 }
 
 struct Found { uint32_t key; int32_t prim; float t, u, v; };
-
-// Every node is reached once from node 0, children and triangle ranges lie inside the arrays: the walk below then ends and reads nothing else
-bool is_tree(const float *nodes12, int nNodes, int nTris) {
-    std::vector<uint8_t> seen((size_t)nNodes, 0);
-    std::vector<int> stack{0};
-    while (!stack.empty()) {
-        const int ni = stack.back();
-        stack.pop_back();
-        if (ni < 0 || ni >= nNodes || seen[(size_t)ni]) return false;
-        seen[(size_t)ni] = 1;
-        const Node N = node_fetch(nodes12 + (size_t)ni * 12);
-        if (N.count > 0) {
-            if (N.first < 0 || N.count > nTris || N.first > nTris - N.count) return false;
-        } else {
-            stack.push_back(N.left);
-            stack.push_back(N.right);
-        }
-    }
-    return true;
-}
 
 }  // namespace
 

@@ -389,6 +389,14 @@ int rt_debug_disk_skip(RtContext *ctx, RtDiskSkip *out, int reset);
  * argument that is null before): call it once, with reset, first. */
 typedef struct RtGiList { uint64_t visited, shaded, listedLaunches, pairLaunches; } RtGiList;
 int rt_debug_gi_list(RtContext *ctx, RtGiList *out, int reset);
+/* The light-slot liveness masks of the wavefront frames: the ray generators mark the light slots of the two shadow queues that hold a ray in
+ * bit masks beside the queues, and the any-hit launch deals its refills from those bits.  Environment RT_LIGHT_MASKS=1 (default): shadow queue 1; 2: queue 2
+ * as well (measured option); 0: neither (a dead slot is then a tMax word < 0, as before); frames are bit-identical in all three.  Counts since the last reset, summed over the frame lanes (synchronises): bits1 / bits2 = bits
+ * set for shadow queue 1 / 2 (= the light rays cast), wordsScanned = 64-bit mask words the any-hit launches read, refillPasses = their masked refill passes,
+ * maskWords1 / maskWords2 = mask words of each lane's last chunk (0 with RT_LIGHT_MASKS=0).  The first four count only from the first call of this entry on:
+ * call it once, with reset, first. */
+typedef struct RtLightMasks { uint64_t bits1, bits2, wordsScanned, refillPasses, maskWords1, maskWords2; } RtLightMasks;
+int rt_debug_light_masks(RtContext *ctx, RtLightMasks *out, int reset);
 /* Diagnostics: the per-hit test beside the code it stands for.  For n pairs (hp, normal; 3 floats each) flags[i] bit 0 = the test holds, bit 1 = one of the
  * four disk samples of `seeds` (pixel, frame) seeds had geom != 0; maxDot[i] = the largest dot(N, L) those samples computed.  u supplies uPI. */
 int rt_debug_disk_unlit(RtContext *ctx, const RtUniforms *u, const float *hp, const float *normals, int n, int seeds, uint8_t *flags, float *maxDot);

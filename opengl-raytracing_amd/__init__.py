@@ -152,6 +152,10 @@ class RtGiList(_Struct):   # rt_debug_gi_list: what the bounce-hit generator vis
     _fields_ = [(n, C.c_uint64) for n in ("visited", "shaded", "listedLaunches", "pairLaunches")]
 
 
+class RtLightMasks(_Struct):   # rt_debug_light_masks: the light-slot liveness masks of the shadow queues (RT_LIGHT_MASKS)
+    _fields_ = [(n, C.c_uint64) for n in ("bits1", "bits2", "wordsScanned", "refillPasses", "maskWords1", "maskWords2")]
+
+
 class RtSceneInfo(_Struct):
     _fields_ = [(n, i32) for n in ("nNodes", "nTris", "nInner", "treeDepth", "nWide4", "nPairs")] + \
                [(n, C.c_uint64) for n in ("bytesNodes2", "bytesNodes4", "bytesPairs", "bytesTris")] + \
@@ -341,6 +345,7 @@ SIGNATURES = {
     "rt_debug_bounce_probe": (C.c_int, [C.c_void_p, C.POINTER(RtBounceProbe), C.c_int]),
     "rt_debug_disk_skip": (C.c_int, [C.c_void_p, C.POINTER(RtDiskSkip), C.c_int]),
     "rt_debug_gi_list": (C.c_int, [C.c_void_p, C.POINTER(RtGiList), C.c_int]),
+    "rt_debug_light_masks": (C.c_int, [C.c_void_p, C.POINTER(RtLightMasks), C.c_int]),
     "rt_debug_disk_unlit": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                       C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,
@@ -2589,6 +2594,13 @@ class Renderer:
         over every pair (rt_debug_gi_list).  The kernels count from the first call on: call once with reset first."""
         b = RtGiList()
         self._check(lib().rt_debug_gi_list(self._h, C.byref(b), int(reset)))
+        return b
+
+    def light_masks(self, reset=False) -> RtLightMasks:
+        """Counts of the light-slot liveness masks since the last reset: bits set for shadow queue 1 / 2, mask words the any-hit launches scanned, their
+        masked refill passes, mask words of the last chunk (rt_debug_light_masks).  The kernels count from the first call on: call once with reset first."""
+        b = RtLightMasks()
+        self._check(lib().rt_debug_light_masks(self._h, C.byref(b), int(reset)))
         return b
 
     def debug_disk_unlit(self, u, hp, normals, seeds=64):

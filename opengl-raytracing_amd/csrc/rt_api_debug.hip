@@ -231,6 +231,7 @@ int rt_debug_disk_unlit(RtContext *c, const RtUniforms *u, const float *hp, cons
 int rt_debug_bounce_probe(RtContext *c, RtBounceProbe *out, int reset) { return lane_sum_record(c, "rt_debug_bounce_probe", rt_wave_bounce_probe, out, reset); }
 int rt_debug_disk_skip(RtContext *c, RtDiskSkip *out, int reset) { return lane_sum_record(c, "rt_debug_disk_skip", rt_wave_disk_skip, out, reset); }
 int rt_debug_gi_list(RtContext *c, RtGiList *out, int reset) { return lane_sum_record(c, "rt_debug_gi_list", rt_wave_gi_list, out, reset); }
+int rt_debug_light_masks(RtContext *c, RtLightMasks *out, int reset) { return lane_sum_record(c, "rt_debug_light_masks", rt_wave_light_masks, out, reset); }
 
 int rt_debug_builds(RtContext *c, uint32_t *out, int reset) {
     if (!c || !out) return RT_ERR_INVALID;

@@ -317,7 +317,52 @@ __global__ __launch_bounds__(256, trace_waves(ANY, OPT)) void k_trace(const DevF
             };
             unsigned long long idleLeft = idleMask;
             while (idleLeft != 0ull && runNext < runEnd) {
-                const uint32_t window = min(64u, runEnd - runNext);
+                uint32_t window = min(64u, runEnd - runNext);
+                if constexpr (MaskedSrc<Src>::value) {
+                    // Light-slot liveness masks: behind the dense slots a slot's liveness is one bit.  The lanes read the mask words of the run's
+                    // next segment -- the slots left that share a queue slot: consecutive bits -- in one coalesced load; the i-th idle lane gets the i-th set
+                    // bit, across all words of the segment, with no further memory access; the takers then read tMax and record together.  Two round trips per
+                    // refill pass, however many dead slots lie in between, instead of two per 64-slot window.
+                    if (src.masked()) {
+                        const uint32_t dEnd = src.dense_end();
+                        if (runNext >= dEnd && runNext < src.masked_end()) {
+                            MaskSeg sg = src.segment(runNext, runEnd);
+                            const uint32_t sh = sg.bit & 63u;
+                            sg.len = min(sg.len, 4096u - sh);                         // one word per lane (RT_CHUNK allows longer runs: the rest is the next pass's)
+                            const uint32_t endBit = sh + sg.len, nW = (endBit + 63u) >> 6;
+                            unsigned long long word = 0ull;
+                            if (lane < nW) word = sg.live[(sg.bit >> 6) + lane];
+                            if (lane == 0u) word &= ~0ull << sh;                      // bits in front of the segment and behind it: other runs, the next slot
+                            if (lane == nW - 1u && (endBit & 63u) != 0u) word &= ~0ull >> (64u - (endBit & 63u));
+                            const uint32_t nIdleL = (uint32_t)__popcll(idleLeft);
+                            const uint32_t rank = (uint32_t)__popcll(idleLeft & ((1ull << lane) - 1ull));
+                            const bool idleMe = ((idleLeft >> lane) & 1ull) != 0ull;
+                            bool takes = false;
+                            unsigned long long mineW = 0ull;                          // the word this lane's slot is in, its place in the segment, the slot's rank in it
+                            uint32_t mineAt = 0u, mineN = 0u;
+                            uint32_t taken = 0u, stop = endBit;                       // live slots handed out so far; first bit of the segment that is NOT used up
+                            for (uint32_t w = 0; w < nW; ++w) {
+                                const unsigned long long mw = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(word >> 32), (int)w) << 32) |
+                                                              (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)word, (int)w);
+                                const uint32_t c = (uint32_t)__popcll(mw);
+                                if (c == 0u) continue;
+                                if (idleMe && rank >= taken && rank - taken < c) { takes = true; mineW = mw; mineAt = w * 64u; mineN = rank - taken; }
+                                if (taken + c > nIdleL) { stop = w * 64u + nth_set(mw, nIdleL - taken); break; }   // more live slots than idle lanes: the rest stays
+                                taken += c;
+                            }
+                            if (takes) {
+                                uint32_t token;
+                                const float tMax = src.take_live(sg.a + (mineAt + nth_set(mineW, mineN) - sh), ro, rd, token);
+                                start_ray(tMax, token);
+                            }
+                            if (lane == 0u) if (unsigned long long *ms = src.mask_stat()) { atomicAdd(&ms[0], (unsigned long long)nW); atomicAdd(&ms[1], 1ull); }
+                            runNext += stop - sh;
+                            idleLeft = whole_quads(__ballot(!active));               // root misses may draw again
+                            continue;
+                        }
+                        if (runNext < dEnd) window = min(window, dEnd - runNext);   // the dense slots in front are probed as ever, but not beyond them: a dead light slot has no tMax word
+                    }
+                }
                 if (tune.denseTake && src.dense(runNext, runNext + window)) {
                     // dense slots: no probe -- the i-th idle lane reads the i-th entry left, liveness word and record in ONE round trip
                     const uint32_t nIdleL = (uint32_t)__popcll(idleLeft);

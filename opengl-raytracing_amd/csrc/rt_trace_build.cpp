@@ -37,6 +37,10 @@ TraceTune tune_from_env() {
     if (const char *e = getenv("RT_QNODES")) t.qnodes = atoi(e);          // 0: never; 1 / 2: always (seven / six waves per SIMD); default: when rt_upload_bvh built them
     return t;
 }
+int light_masks_from_env() {
+    const char *e = getenv("RT_LIGHT_MASKS");
+    return e ? std::max(0, std::min(2, atoi(e))) : 1;
+}
 
 TraceBuild trace_build(bool any, const TraceTune &tune, const TraceForms &f, int depth, bool stats) {
     TraceBuild b{};

@@ -17,6 +17,10 @@ TraceTune default_tune();
 // kinds 2 - 4 launch (rt_wave_debug_trace / rt_wave_debug_packets), so that the per-ray tests walk the build a frame walks under the same environment.
 // RT_DEBUG_SKIP_TRAVERSAL is not read here: it skips the work, and only frames take it.
 TraceTune tune_from_env();
+// RT_LIGHT_MASKS: 1 (default) the light slots of shadow queue 1 are marked live in bit masks instead of by tMax words < 0; 2 (measured option)
+// those of shadow queue 2 as well; 0 neither, the A/B switch.
+// Read beside tune_from_env, not into TraceTune: that record is an argument of every k_trace build, and a member more would move the arguments behind it in all of them.
+int light_masks_from_env();
 
 // What a scene offers a launch: the optional record forms rt_upload_bvh built (DevScene's pointers, non-null) and the exact any-hit stack size (0: not known)
 struct TraceForms { bool q4, wF, iN2, iN4, iQ4; int anyStack; };

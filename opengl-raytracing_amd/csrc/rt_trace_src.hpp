@@ -94,13 +94,58 @@ struct QueueSrc : AddrSrc<QueueSrc> {     // slot-major queue: ray r -> (slot = 
     }
 };
 
+// Light-slot liveness masks: the frames' shadow queues.  Behind the dense slots, bit [address - denseSlots * stride] of `live` says whether
+// the slot holds a ray -- the index of o / tm --, and tm of a dead slot is not written at all.  A source with the MaskedSrc trait adds to the protocol:
+//   masked()                        the launch has masks; false (live == null, RT_LIGHT_MASKS=0): the source is the unmasked one, dead slots carry tm < 0
+//   dense_end(), masked_end()       the slots r in between are the masked ones; those in front are dense slots, those behind an unmasked queue: probed and taken as ever
+//   segment(r, rEnd)                the slots from r on that share a queue and a slot (consecutive addresses, consecutive bits), at most up to rEnd
+//   take_live(a, ro, rd, token)     tMax and record of the live slot with payload address a, in ONE round trip
+// QueueSrc itself stays as it is, for the bounce queue and the debug entries: a member more would move the kernel arguments of their builds.
+struct MaskSeg { const unsigned long long *live; uint32_t bit, a, len; };   // the mask array, the bit and the payload address of slot r, slots in the segment
+struct MaskedQueueSrc : QueueSrc {
+    const unsigned long long *live;
+    unsigned long long *maskStat;   // rt_debug_light_masks: [0] mask words scanned [1] masked refill passes; null until the entry was called
+    RT_DEV bool masked() const { return live != nullptr; }
+    RT_DEV unsigned long long *mask_stat() const { return maskStat; }
+    RT_DEV uint32_t dense_end() const { return denseSlots * nLive; }
+    RT_DEV uint32_t masked_end() const { return size(); }
+    RT_DEV MaskSeg segment(uint32_t r, uint32_t rEnd) const {
+        const uint32_t sl = r / nLive, j = r - sl * nLive;
+        MaskSeg s;
+        s.live = live; s.a = sl * stride + j; s.bit = s.a - nDense(); s.len = min(rEnd - r, nLive - j);
+        return s;
+    }
+    RT_DEV float take_live(uint32_t a, V3 &ro, V3 &rd, uint32_t &token) const {
+        token = a;
+        const float t = tm[a - nDense()];
+        const float4 oo = o[a - nDense()], dd = d[a];
+        ro = f4xyz(oo); rd = f4xyz(dd);
+        return t;
+    }
+};
+
 // Two any-hit queues traced by ONE persistent launch (direct shadows + AO, then the shadows at the bounce hits): a second
 // launch would pay the ~0.15 ms ramp-up / drain latency of a persistent grid again for a few thousand rays.
 struct DualQueueSrc {
-    QueueSrc a, b;
+    MaskedQueueSrc a, b;
     uint32_t na;
     RT_DEV void prepare() { a.prepare(); b.prepare(); na = a.size(); }
     RT_DEV uint32_t size() const { return na + b.size(); }
+    RT_DEV bool masked() const { return a.masked(); }                  // (queue 1, or both: RT_LIGHT_MASKS=2)
+    RT_DEV uint32_t masked_end() const { return b.masked() ? size() : na; }
+    RT_DEV unsigned long long *mask_stat() const { return a.maskStat; }
+    RT_DEV uint32_t dense_end() const { return a.dense_end(); }       // (queue 2 has no dense slots)
+    RT_DEV MaskSeg segment(uint32_t r, uint32_t rEnd) const {
+        if (r < na) return a.segment(r, min(rEnd, na));
+        MaskSeg s = b.segment(r - na, rEnd - na);
+        s.a |= 0x80000000u;
+        return s;
+    }
+    RT_DEV float take_live(uint32_t pa, V3 &ro, V3 &rd, uint32_t &token) const {
+        const float t = (pa & 0x80000000u) ? b.take_live(pa & 0x7fffffffu, ro, rd, token) : a.take_live(pa, ro, rd, token);
+        token = pa;
+        return t;
+    }
     typedef QueueSrc::Payload Payload;
     RT_DEV float probe(uint32_t r, Payload &p) const {
         if (r < na) return a.probe(r, p);
@@ -340,4 +385,8 @@ struct SceneSrc : AddrSrc<SceneSrc> {
 template <class Src> struct QueryTMax { static constexpr bool value = false; };
 template <> struct QueryTMax<QuerySrc> { static constexpr bool value = true; };
 template <> struct QueryTMax<SceneSrc> { static constexpr bool value = true; };
+// The sources with light-slot liveness masks (MaskedQueueSrc above): k_trace builds its masked refill for them alone, every other build keeps its instructions.
+template <class Src> struct MaskedSrc { static constexpr bool value = false; };
+template <> struct MaskedSrc<MaskedQueueSrc> { static constexpr bool value = true; };
+template <> struct MaskedSrc<DualQueueSrc> { static constexpr bool value = true; };
 }  // namespace

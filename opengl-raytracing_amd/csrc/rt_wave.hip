@@ -104,6 +104,13 @@ struct RtWave {
     bool giListOn = false;
     unsigned long long listedLaunches = 0, pairLaunches = 0, giListBase[2] = {0, 0};   // host: bounce-hit generator launches over the hit list / over every pair
     unsigned long long tracedProbeBase = 0;   // rt_wave_traced's reset: probeAcc[0] at that time (probed rays count as bounce rays there)
+    // light-slot liveness masks: the lane's own words, grown with the chunk arrays; queue 1's first, queue 2's behind them
+    int lightMasks = rtl::light_masks_from_env();   // 0 none, 1 queue 1, 2 both queues
+    unsigned long long *liveMem = nullptr;
+    size_t liveWords = 0;
+    unsigned long long *maskAcc = nullptr;    // device: rt_wave_light_masks' sums -- [0] set bits of queue 1 [1] of queue 2 (k_count_live) [2] mask words scanned [3] masked
+    bool maskStatOn = false;                  // refill passes (k_trace); counted only once the entry was called
+    unsigned long long maskWordsLast[2] = {0, 0};   // mask words of the last chunk: queue 1, queue 2
 };
 
 RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
@@ -134,13 +141,13 @@ void rt_wave_destroy(RtWave *w) {
     if (!w) return;
     if (w->shadeStream) (void)hipStreamDestroy(w->shadeStream);
     if (w->hopEv) (void)hipEventDestroy(w->hopEv);
-    for (void *p : std::initializer_list<void *>{w->frameArena, w->resultArena, w->counts, w->heads, w->acc, w->probeAcc, w->diskAcc, w->giListAcc, w->stats})
+    for (void *p : std::initializer_list<void *>{w->frameArena, w->resultArena, w->counts, w->heads, w->acc, w->probeAcc, w->diskAcc, w->giListAcc, w->stats, w->liveMem, w->maskAcc})
         if (p) (void)hipFree(p);
     if (w->hostHits) (void)hipHostFree(w->hostHits);
     delete w;
 }
 const char *rt_wave_error(const RtWave *w) { return w->err.c_str(); }
-size_t rt_wave_frame_bytes(const RtWave *w) { return w ? rtl::arena_bytes(rtl::frame_arena(w->slotsCap)) + w->resultBytes : 0; }
+size_t rt_wave_frame_bytes(const RtWave *w) { return w ? rtl::arena_bytes(rtl::frame_arena(w->slotsCap)) + w->resultBytes : 0; }   // (the planner's totals, tests/test_gpu_wave_plan.py; the liveness words, 8 B each: rt_wave_light_masks)
 
 #define W_TRY(expr)                                                                   \
     do {                                                                              \
@@ -210,11 +217,12 @@ static TraceLaunch wave_trace(const LaunchSet &L, int gridPct, uint32_t *head, c
 // Ray sources, here and where a launch builds its own in place, start from a value-initialised object (`QueueSrc q{};`): a field that is not named is zero -- nLive / n
 // among them, which prepare() fills on the device -- and none reaches a launch indeterminate.
 // shadow queue 1 as the any-hit launch reads it: whole, or -- the AO rays went as packets -- from behind its A AO slots
-static QueueSrc wave_shadow_queue1(const LaunchSet &L, uint32_t c0, bool pkAO) {
+static MaskedQueueSrc wave_shadow_queue1(const LaunchSet &L, uint32_t c0, bool pkAO) {
     const WaveBuf &wb = L.wb;
     const int A = L.plan.ao;
     const size_t skip = pkAO ? (size_t)A * L.CH : 0;   // (packets: the A AO slots are answered already)
-    QueueSrc q{};
+    MaskedQueueSrc q{};
+    q.live = wb.shLive; q.maskStat = (wb.shLive && L.w->maskStatOn) ? L.w->maskAcc + 2 : nullptr;
     q.o = wb.shO; q.d = wb.shD + skip; q.tm = wb.shT; q.org = wb.aoOrg; q.orgStride = 0; q.liveCount = &wb.counts[1]; q.c0 = c0; q.cap = wb.CH; q.stride = wb.CH; q.outOcc = wb.occ1 + skip;
     q.slots = (uint32_t)(L.plan.S1 - (pkAO ? A : 0));
     q.denseSlots = pkAO ? 0u : (uint32_t)A;
@@ -298,6 +306,36 @@ static void wave_point_chunk_arrays(LaunchSet &L, size_t ch, bool predict) {
     wb.CH = (uint32_t)ch;
 }
 
+// The liveness words of the chunk arrays just pointed: L1 * CH bits for the light slots of queue 1 and -- RT_LIGHT_MASKS=2 -- 6 * q2Stride for
+// queue 2, one word more each.
+// The lane's own allocation (grown, never shrunk, behind the lane's stream), beside the planned arenas and outside their layout.  RT_LIGHT_MASKS=0: none.
+static int wave_light_masks(LaunchSet &L) {
+    RtWave *w = L.w;
+    if (!w->lightMasks) return RT_OK;
+    const size_t w1 = rtl::align_up(((size_t)L.plan.L1 * L.wb.CH + 63) / 64 + 1, 32), w2 = w->lightMasks >= 2 ? rtl::align_up(((size_t)6 * L.wb.q2Stride + 63) / 64 + 1, 32) : 0;
+    if (w->liveWords < w1 + w2) {
+        if (w->liveMem) { W_TRY(hipStreamSynchronize(L.st)); (void)hipFree(w->liveMem); }
+        w->liveMem = nullptr;
+        w->liveWords = 0;
+        W_TRY(hipMalloc(&w->liveMem, (w1 + w2) * sizeof(unsigned long long)));
+        w->liveWords = w1 + w2;
+    }
+    L.wb.shLive = w->liveMem;
+    L.wb.sh2Live = w2 ? w->liveMem + w1 : nullptr;
+    w->maskWordsLast[0] = w1; w->maskWordsLast[1] = w2;
+    return RT_OK;
+}
+// rt_debug_light_masks: the set bits of both mask arrays, counted behind the chunk's generators
+static __global__ __launch_bounds__(256) void k_count_live(const unsigned long long *live, size_t words1, size_t words2, unsigned long long *sums) {
+    unsigned long long n1 = 0, n2 = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words1 + words2; i += (size_t)gridDim.x * 256) {
+        const unsigned long long c = (unsigned long long)__popcll(live[i]);
+        if (i < words1) n1 += c; else n2 += c;
+    }
+    for (int off = 32; off > 0; off >>= 1) { n1 += __shfl_down(n1, off, 64); n2 += __shfl_down(n2, off, 64); }
+    if ((threadIdx.x & 63) == 0) { if (n1) atomicAdd(&sums[0], n1); if (n2) atomicAdd(&sums[1], n2); }
+}
+
 // step 4 -- cursor table (one set of sharded cursors per trace launch) and per-chunk bounce counters: grown when a small queue budget
 // cuts the frame into more chunks than seen so far (4K / 16 spp at RT_QUEUE_BUDGET_MB=128 is 491 chunks).  Both arrays are
 // only touched by this lane's stream, which is drained first.
@@ -374,7 +412,7 @@ static int wave_settle_chunks(LaunchSet &L) {
     // batches) share lane % n
     if (plan.deferred) w->arena = L.nChunks > 1 ? w->lane : w->lane % w->pool->n;   // (not deferred: chosen and allocated before k_primary)
     if (plan.deferred && L.nChunks > 0) W_STEP(wave_grow_arenas(L, L.CH, split.room, true));
-    if (L.nChunks > 0) wave_point_chunk_arrays(L, L.CH, plan.deferred);
+    if (L.nChunks > 0) { wave_point_chunk_arrays(L, L.CH, plan.deferred); W_STEP(wave_light_masks(L)); }
     return RT_OK;
 }
 
@@ -384,6 +422,8 @@ static int wave_chunk_direct(LaunchSet &L, int c, uint32_t c0, bool pkAO) {
     RtWave *w = L.w;
     const WaveBuf &wb = L.wb;
     const unsigned gridHS = (unsigned)((L.CH * (size_t)L.plan.spp + 255) / 256);
+    // the chunk's liveness bits start clear: on the lane's stream, behind the any-hit launch of the chunk before and of the lane's previous launch set
+    if (wb.shLive) W_TRY(hipMemsetAsync(wb.shLive, 0, (size_t)(w->maskWordsLast[0] + w->maskWordsLast[1]) * sizeof(unsigned long long), L.st));
     W_STEP(wave_stage(L, ST_GEN_DIRECT, L.ss, [&] { hipLaunchKernelGGL(L.host->nrmRows ? k_gen_direct_smooth : k_gen_direct, dim3(gridHS), dim3(256), 0, L.ss, L.dFrame, wb, c0, w->diskStatOn ? w->diskAcc : nullptr); }));
     if (pkAO) W_STEP(wave_stage(L, ST_TRACE_AO, L.st, [&] {
         PacketSrc pk{};   // the A dense AO slots in front of shadow queue 1
@@ -445,17 +485,22 @@ static int wave_chunk(LaunchSet &L, int c) {
     const uint32_t c0 = (uint32_t)((size_t)c * L.CH);
     const bool pkAO = w->opt.packetAO && L.plan.ao > 0;
     W_STEP(wave_chunk_direct(L, c, c0, pkAO));
-    const QueueSrc q1 = wave_shadow_queue1(L, c0, pkAO);
+    const MaskedQueueSrc q1 = wave_shadow_queue1(L, c0, pkAO);
     const TraceLaunch shadows = wave_trace(L, L.gridPct, wave_cursor(wb, c, 0), w->tune, w->acc + 3, w->acc + 9, 16);
+    // rt_debug_light_masks: the bits the generators set, counted before the launch that reads them
+    auto count_live = [&] { if (wb.shLive && w->maskStatOn) hipLaunchKernelGGL(k_count_live, dim3(256), dim3(256), 0, L.st, wb.shLive, (size_t)w->maskWordsLast[0], (size_t)w->maskWordsLast[1], w->maskAcc); };
     if (L.host->u.enableGI == 1) {
         // bounce rays first, then ONE any-hit launch over both shadow queues
         W_STEP(wave_chunk_bounce(L, c, c0));
+        count_live();
         DualQueueSrc qq{};
         qq.a = q1;   // b: shadow queue 2, six slots, the entries compacted over the chunk's bounce hits
+        qq.b.live = wb.sh2Live; qq.b.maskStat = q1.maskStat;
         qq.b.o = wb.sh2O; qq.b.d = wb.sh2D; qq.b.tm = wb.sh2T; qq.b.liveCount = &wb.counts[64 + c]; qq.b.c0 = 0; qq.b.cap = wb.q2Stride; qq.b.stride = wb.q2Stride; qq.b.slots = 6u; qq.b.outOcc = wb.occ2;
         W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { wave_built(w, launch_trace<DualQueueSrc, true>(shadows, qq)); }));
     } else {
-        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { wave_built(w, launch_trace<QueueSrc, true>(shadows, q1)); }));
+        count_live();
+        W_STEP(wave_stage(L, ST_TRACE_SHADOW, L.st, [&] { wave_built(w, launch_trace<MaskedQueueSrc, true>(shadows, q1)); }));
     }
     // the last traversal launch of the batch is queued: the shared ray arena may go to the next batch (k_combine reads the lane's own result arrays)
     if (c == L.nChunks - 1) { W_TRY(hipEventRecord(w->pool->freeEv[w->arena], L.st)); w->pool->lastUser[w->arena] = L.st; }
@@ -483,6 +528,7 @@ int rt_wave_render(RtWave *w, RtContext *ctx, hipStream_t st, const DevFrame *dF
         w->arena = L.nChunks > 1 ? w->lane : w->lane % w->pool->n;
         W_STEP(wave_grow_arenas(L, L.CH, L.CH, false));
         wave_point_chunk_arrays(L, L.CH, false);
+        W_STEP(wave_light_masks(L));
     }
     L.wb.CH = (uint32_t)L.CH; L.wb.A = plan.ao; L.wb.SPP = SPP;
     W_STEP(wave_cursor_table(L));
@@ -671,6 +717,15 @@ int rt_wave_gi_list(RtWave *w, hipStream_t st, unsigned long long *out4, bool re
     const unsigned long long l[2] = {w->listedLaunches, w->pairLaunches};
     for (int i = 0; i < 2; ++i) { out4[2 + i] = l[i] - w->giListBase[i]; if (reset) w->giListBase[i] = l[i]; }
     w->giListOn = true;
+    return RT_OK;
+}
+
+int rt_wave_light_masks(RtWave *w, hipStream_t st, unsigned long long *out6, bool reset) {
+    for (int i = 0; i < 6; ++i) out6[i] = 0;
+    if (!w) return RT_OK;
+    W_STEP(wave_read_sums(w, st, w->maskAcc, 4, out6, reset));
+    if (w->lightMasks) { out6[4] = w->maskWordsLast[0]; out6[5] = w->maskWordsLast[1]; }
+    w->maskStatOn = true;
     return RT_OK;
 }
 

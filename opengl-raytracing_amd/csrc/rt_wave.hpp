@@ -41,6 +41,10 @@ int rt_wave_disk_skip(RtWave *w, hipStream_t stream, unsigned long long *out10, 
 // The bounce-hit generator (k_gen_gi / k_gen_gi_listed) since the last reset, 4 words: [0] (hit, sample) pairs it visited [1] pairs it shaded (their bounce ray hit)
 // [2] launches over the bounce probe's hit list [3] launches over every pair.  [0] and [1] count from the first call on.
 int rt_wave_gi_list(RtWave *w, hipStream_t stream, unsigned long long *out4, bool reset);
+// The light-slot liveness masks since the last reset, 6 words: [0] bits the generators set for shadow queue 1 [1] for queue 2 [2] mask words the
+// any-hit launches scanned [3] their masked refill passes [4] [5] mask words of the lane's last chunk, queue 1 / queue 2 (0: RT_LIGHT_MASKS=0).  [0] - [3] count
+// from the first call on.
+int rt_wave_light_masks(RtWave *w, hipStream_t stream, unsigned long long *out6, bool reset);
 // The share of bounce hits of earlier launch sets (what shadow queue 2 is sized from and the bounce probe is chosen by) belongs to a scene and a frame size:
 // rt_upload_bvh and rt_resize forget it (an spp change does so in rt_wave_render)
 void rt_wave_forget_share(RtWave *w);

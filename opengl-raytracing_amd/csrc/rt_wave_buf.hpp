@@ -23,6 +23,10 @@ struct WaveBuf {
     // tMax / liveness word of their own (hp + L*e differs from ray to ray): shO / shT, indexed by the slot's address LESS the A * CH dense ones.
     float4 *shO, *shD;
     float *shT, *sh2T;       // per-slot tMax (any-hit); < 0 = no ray in this slot (4 B instead of a 32-B record)
+    // Light-slot liveness masks: bit b of shLive = light-slot entry b of queue 1 (the index of shO / shT) holds a ray, bit a of sh2Live = entry a of
+    // queue 2 does.  Cleared before the chunk's k_gen_direct, set by the generators (live_set); shT / sh2T of a dead slot are then not written at all.
+    // Null (RT_LIGHT_MASKS=0): a dead slot is marked by shT / sh2T < 0, as before.  The lane's own memory, not the planned ray arena.
+    unsigned long long *shLive, *sh2Live;
     float4 *aoOrg;           // per hit: hp + N * aoBias, written once (AO ray 0)
     uint8_t *occ1;
     // Bounce queue: SPP dense slots x CH, record {dir, 1.0 = a ray was cast | < 0 = none}; the origin hp + N * eps (bounce_origin) belongs to the hit: giOrg[j],
@@ -88,6 +92,46 @@ struct BatchAppend {
     }
 };
 #define RT_BATCH_APPEND(name) __shared__ uint32_t name##_cnt[kAppendBatch][4]; __shared__ uint32_t name##_base; BatchAppend name; name.cnt = name##_cnt; name.base = &name##_base
+
+// Light-slot liveness (WaveBuf::shLive / sh2Live): the lanes that call this together set bit `bit` of `live` where `on`.  A wave with no live lane issues no
+// memory operation.  Where the live lanes stand on consecutive bits in lane order (k_gen_direct: one sample, consecutive hits) ONE lane ORs the wave's ballot,
+// shifted, into the one or two words it straddles; where they stand in two neighbouring words otherwise (queue 2's compacted entries) one lane ORs the two
+// words, put together in a scalar loop; else (a wave across a sample boundary) every live lane ORs its own bit.  The words are shared with neighbouring waves:
+// atomics, whose value is not read (no return: they do not wait for memory).
+RT_DEV void live_set(unsigned long long *live, uint32_t bit, bool on) {
+    const unsigned long long m = __ballot(on);
+    if (m == 0ull) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int first = __ffsll((long long)m) - 1;
+    const uint32_t b0 = (uint32_t)__shfl((int)bit, first, 64);                             // the first live lane's bit: the row starts there
+    const bool row = __ballot(on && bit - b0 != lane - (uint32_t)first) == 0ull;
+    if (row) {
+        if ((int)lane == first) {
+            const unsigned long long mm = m >> first;
+            const uint32_t sh = b0 & 63u;
+            (void)__hip_atomic_fetch_or(&live[b0 >> 6], mm << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (sh != 0u && (mm >> (64u - sh)) != 0ull) (void)__hip_atomic_fetch_or(&live[(b0 >> 6) + 1u], mm >> (64u - sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
+    // Not a row, but all in the first live lane's word or the next (queue 2: an entry is the pair's rank among the workgroup's bounce hits, so the bits are
+    // consecutive over the CALLING lanes and skip the others): the two words are put together bit by bit from the live lanes' values -- a wave-uniform loop of
+    // scalar instructions, at most 64 rounds -- and one lane ORs them in.  (One atomic per live lane made k_gen_gi 20 % longer on the 1 M-triangle scene, where
+    // most bounce rays hit: profiles/r19_light_masks.txt 4.)
+    const uint32_t w0 = b0 >> 6;
+    if (__ballot(on && (bit >> 6) - w0 > 1u) == 0ull) {
+        unsigned long long lo = 0ull, hi = 0ull;
+        for (unsigned long long rem = m; rem != 0ull; rem &= rem - 1ull) {
+            const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)bit, __ffsll((long long)rem) - 1);
+            if ((b >> 6) == w0) lo |= 1ull << (b & 63u);
+            else hi |= 1ull << (b & 63u);
+        }
+        if ((int)lane == first) {
+            (void)__hip_atomic_fetch_or(&live[w0], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (hi != 0ull) (void)__hip_atomic_fetch_or(&live[w0 + 1u], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else if (on) (void)__hip_atomic_fetch_or(&live[bit >> 6], 1ull << (bit & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // The ray cursors of one trace launch (WaveBuf::heads, k_trace's scheduler): sharded, each shard on a line of its own.
 constexpr uint32_t kShards = 64, kShardStride = 32;   // cursor shards per trace launch, uint32 words between them (128 B)

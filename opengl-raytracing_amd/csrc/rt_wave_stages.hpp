@@ -182,7 +182,10 @@ struct GenDirectTracer {   // records first-generation rays of (hit j, sample s)
         if (k >= 4 && s > 0) return false;
         uint32_t a = wb.sh1_slot(s, k) * wb.CH + j;
         const uint32_t al = wb.sh1_light(a);
-        if (!matters) { wb.shT[al] = -1.0f; return false; }   // dead ray: its answer is multiplied by zero
+        // dead ray (its answer is multiplied by zero): its liveness bit stays clear and nothing is stored; without masks its tMax word says so
+        if (wb.shLive) live_set(wb.shLive, al, matters);
+        else if (!matters) wb.shT[al] = -1.0f;
+        if (!matters) return false;
         wb.shT[al] = fmaxr(tMax, 0.0f);
         wb.shO[al] = mkf4(ro, 0.0f);
         wb.shD[a] = mkf4(rd, 0.0f);
@@ -232,7 +235,9 @@ template <bool SMOOTH> struct GenGiTracer {       // reads the bounce result, re
         if (pos >= wb.q2Stride) return false;          // beyond the queue's capacity: k_gen_gi_overflow traces this pair's rays itself
         uint32_t a = (uint32_t)k * wb.q2Stride + pos;
         shadowMask |= 1u << k;
-        if (!matters) { wb.sh2T[a] = -1.0f; return false; }
+        if (wb.sh2Live) live_set(wb.sh2Live, a, matters);
+        else if (!matters) wb.sh2T[a] = -1.0f;
+        if (!matters) return false;
         wb.sh2T[a] = fmaxr(tMax, 0.0f);
         wb.sh2O[a] = mkf4(ro, 0.0f);
         wb.sh2D[a] = mkf4(rd, 0.0f);
@@ -314,7 +319,7 @@ template <bool SMOOTH> RT_DEV void gen_direct_body(const DevFrame *__restrict__ 
         const int SPP = max(u.spp, 1);
         const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
         (void)directLightBVH(tr, c.F, SEG_DIRECT, c.hp, c.hn, seed, -c.dir);
-        if (s == 0)
+        if (s == 0 && !wb.shLive)         // (with liveness masks the bit of a slot that was not set is clear already)
             for (int k = 4; k < 6; ++k)   // sun / point rays are conditional (rt_lighting.glsl:123,194)
                 if (!(tr.shadowMask & (1u << k))) wb.shT[wb.sh1_light(wb.sh1_slot(0, k) * wb.CH + j)] = -1.0f;
         Work w;
@@ -388,7 +393,7 @@ template <bool SMOOTH> RT_DEV void gen_gi_body(const DevFrame *__restrict__ fr, 
     const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
     Work w;
     (void)oneBounceGIBVH<GenGiTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
-    if (pos < wb.q2Stride)
+    if (pos < wb.q2Stride && !wb.sh2Live)   // (with liveness masks the bit of a slot that was not set is clear already)
         for (int k = 0; k < 6; ++k)
             if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
 }
@@ -422,7 +427,7 @@ template <bool SMOOTH> RT_DEV void gen_gi_listed_body(const DevFrame *__restrict
         const int seed = (int)((uint32_t)c.F.frameIndex * (uint32_t)SPP + (uint32_t)s);
         Work w;
         (void)oneBounceGIBVH<GenGiTracer<SMOOTH>, false>(tr, c.F, c.hp, c.hn, c.F.frameIndex, seed, w);
-        if (pos < wb.q2Stride)
+        if (pos < wb.q2Stride && !wb.sh2Live)
             for (int k = 0; k < 6; ++k)
                 if (!(tr.shadowMask & (1u << k))) wb.sh2T[(uint32_t)k * wb.q2Stride + pos] = -1.0f;
     }

@@ -1105,6 +1105,15 @@ int rt_debug_halton_pairs(int frame0, int count, float *out);
 uint32_t rt_debug_div_reciprocal(uint32_t d, uint64_t nMax);
 int rt_debug_div_by(uint32_t d, uint32_t rcp, const uint32_t *n, size_t count, uint32_t *q, uint32_t *r);
 int rt_debug_frame_geom(int w, int h, int rank, int world, int batch, int useReciprocals, RtFrameGeomInfo *out, int32_t *xy);
+/* Diagnostics, host side (no GPU needed, no context): the candidate order of a batch of frames (csrc/rt_batch_order.hpp, DESIGN.md 4.2 "Frame batching"), as
+ * the host compiles the arithmetic of k_primary_interleaved.
+ *   rt_debug_batch_tiles: out[v] = the local tile index lt' = k * nLocalTiles + lt that iteration v of that kernel's grid handles, v < batch * nLocalTiles:
+ *     the frames k of spatial tile lt follow each other (v = lt * batch + k).
+ *   rt_debug_batch_order: a workgroup of `waves` waves noted ballots[k * waves + w] in iteration k < n (bit l: lane l has a candidate).  out[(k * waves + w) *
+ *     64 + l] = the position of that candidate relative to the workgroup's first, 0xffffffff where there is none: wave by wave, inside a wave lane by lane,
+ *     and a lane's candidates by iteration. */
+int rt_debug_batch_tiles(int batch, int nLocalTiles, int32_t *out);
+int rt_debug_batch_order(const uint64_t *ballots, int n, int waves, uint32_t *out);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

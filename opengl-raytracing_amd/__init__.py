@@ -466,6 +466,8 @@ SIGNATURES = {
     "rt_debug_div_reciprocal": (C.c_uint32, [C.c_uint32, C.c_uint64]),
     "rt_debug_div_by": (C.c_int, [C.c_uint32, C.c_uint32, _U32P, C.c_size_t, _U32P, _U32P]),
     "rt_debug_frame_geom": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),   # RtFrameGeomInfo
+    "rt_debug_batch_tiles": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "rt_debug_batch_order": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int, _U32P]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -1265,6 +1267,28 @@ def frame_geom(w, h, rank=0, world=1, batch=1, reciprocals=True, slots=False):
         if rc != RT_OK:
             raise RtError(rc, "rt_debug_frame_geom")
     return info, xy
+
+
+def batch_tiles(batch, n_local_tiles) -> np.ndarray:
+    """rt_debug_batch_tiles: int32 [batch * n_local_tiles], the local tile index (k * n_local_tiles + lt) each iteration of k_primary_interleaved's grid handles in a
+    batch of frames: the frames of a spatial tile follow each other."""
+    out = np.zeros(int(batch) * int(n_local_tiles), np.int32)
+    rc = lib().rt_debug_batch_tiles(int(batch), int(n_local_tiles), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_batch_tiles")
+    return out
+
+
+def batch_order(ballots) -> np.ndarray:
+    """rt_debug_batch_order: ballots uint64 [n, waves] (bit l of [k, w]: lane l of wave w has a candidate in iteration k) -> uint32 [n, waves, 64], each
+    candidate's position relative to the workgroup's first (0xffffffff: none) in k_primary_interleaved's order for a batch of frames."""
+    b = np.ascontiguousarray(ballots, dtype=np.uint64)
+    n, waves = b.shape
+    out = np.zeros((n, waves, 64), np.uint32)
+    rc = lib().rt_debug_batch_order(b.ctypes.data_as(C.POINTER(C.c_uint64)), n, waves, out.ctypes.data_as(_U32P))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_batch_order")
+    return out
 
 
 def load_obj(path):

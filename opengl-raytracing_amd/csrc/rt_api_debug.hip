@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_batch_order.hpp"
 #include "rt_context.hpp"
 #include "rt_scene_pack.hpp"
 #include "rt_wave_plan.hpp"
@@ -386,4 +387,22 @@ int rt_debug_frame_geom(int w, int h, int rank, int world, int batch, int useRec
     return RT_OK;
 }
 
+int rt_debug_batch_tiles(int batch, int nLocalTiles, int32_t *out) {
+    if (!out || batch < 1 || batch > RT_MAX_BATCH || nLocalTiles < 0) return RT_ERR_INVALID;
+    for (int v = 0; v < batch * nLocalTiles; ++v) out[v] = batch_tile_of_virtual(v, batch, nLocalTiles);
+    return RT_OK;
+}
+int rt_debug_batch_order(const uint64_t *ballots, int n, int waves, uint32_t *out) {
+    if (!ballots || !out || n < 1 || n > 32 || waves < 1) return RT_ERR_INVALID;
+    const unsigned long long *m = reinterpret_cast<const unsigned long long *>(ballots);
+    uint32_t waveBase = 0;   // the items of lower waves (InterleavedAppend::commit)
+    for (int w = 0; w < waves; ++w) {
+        for (uint32_t lane = 0; lane < 64; ++lane) {
+            const uint32_t start = waveBase + interleaved_lane_start(m + w, waves, n, lane), bits = interleaved_lane_bits(m + w, waves, n, lane);
+            for (int k = 0; k < n; ++k) out[((size_t)k * waves + w) * 64 + lane] = (bits >> k) & 1u ? interleaved_index(start, bits, k) : 0xffffffffu;
+        }
+        for (int k = 0; k < n; ++k) waveBase += (uint32_t)__builtin_popcountll(m[(size_t)k * waves + w]);
+    }
+    return RT_OK;
+}
 }  // extern "C"

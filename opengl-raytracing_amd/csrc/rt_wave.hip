@@ -106,6 +106,7 @@ struct RtWave {
     unsigned long long tracedProbeBase = 0;   // rt_wave_traced's reset: probeAcc[0] at that time (probed rays count as bounce rays there)
     // light-slot liveness masks: the lane's own words, grown with the chunk arrays; queue 1's first, queue 2's behind them
     int lightMasks = rtl::light_masks_from_env();   // 0 none, 1 queue 1, 2 both queues
+    int batchInterleave = rtl::batch_interleave_from_env();   // RT_BATCH_INTERLEAVE: a batch's candidates pixel-major, the frames of a pixel side by side (k_primary_interleaved); 0: frame-major (k_primary)
     unsigned long long *liveMem = nullptr;
     size_t liveWords = 0;
     unsigned long long *maskAcc = nullptr;    // device: rt_wave_light_masks' sums -- [0] set bits of queue 1 [1] of queue 2 (k_count_live) [2] mask words scanned [3] masked
@@ -373,7 +374,8 @@ static int wave_cursor_table(LaunchSet &L) {
 static int wave_primary(LaunchSet &L, unsigned tiles) {
     RtWave *w = L.w;
     const WaveBuf &wb = L.wb;
-    W_STEP(wave_stage(L, ST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
+    const bool interleave = w->batchInterleave && L.host->g.batch > 1;   // a single frame keeps k_primary: nothing to put side by side
+    W_STEP(wave_stage(L, ST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(interleave ? k_primary_interleaved : k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
     W_STEP(wave_stage(L, ST_TRACE_PRIMARY, L.st, [&] {
         PrimarySrc ps{};
         ps.fr = L.dFrame; ps.cand = wb.cand; ps.count = &wb.counts[0]; ps.outT = wb.primT; ps.outTri = wb.primTri;

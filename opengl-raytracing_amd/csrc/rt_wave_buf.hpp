@@ -2,6 +2,7 @@
 // the cursor constants of the trace launches.
 // Part of the rt_wave.hip translation unit: included by it alone, behind its `#pragma clang fp contract(off)` and `using namespace rtd;`.
 #pragma once
+#include "rt_batch_order.hpp"
 #include "rt_wave.hpp"
 
 // stage ids (rt_stage_name in rt_api.hip)
@@ -92,6 +93,36 @@ struct BatchAppend {
     }
 };
 #define RT_BATCH_APPEND(name) __shared__ uint32_t name##_cnt[kAppendBatch][4]; __shared__ uint32_t name##_base; BatchAppend name; name.cnt = name##_cnt; name.base = &name##_base
+
+// The same append with a wave's items laid out lane by lane, and a lane's kAppendBatch items side by side (rt_batch_order.hpp): k_primary_interleaved's order for a batch
+// of frames, whose iterations are the frames of one spatial tile.  Still ONE atomic per workgroup; the waves keep their ballots instead of their counts.
+//   note(k, pred) for every sub-block k, commit(counter), then index(k) -> position of this thread's item of sub-block k.
+struct InterleavedAppend {
+    uint32_t bits = 0, first = 0;
+    unsigned long long (*bal)[4];
+    uint32_t *base;
+    RT_DEV void note(int k, bool pred) {
+        const unsigned long long m = __ballot(pred);
+        if (pred) bits |= 1u << k;
+        if ((threadIdx.x & 63) == 0) bal[k][threadIdx.x >> 6] = m;
+    }
+    RT_DEV void commit(uint32_t *counter) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t tot = 0;
+            for (int k = 0; k < kAppendBatch; ++k) for (int i = 0; i < 4; ++i) tot += (uint32_t)__popcll(bal[k][i]);
+            *base = tot ? atomicAdd(counter, tot) : 0u;
+        }
+        __syncthreads();
+        const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        first = *base;
+        for (uint32_t i = 0; i < wv; ++i) for (int k = 0; k < kAppendBatch; ++k) first += (uint32_t)__popcll(bal[k][i]);
+        first += interleaved_lane_start(&bal[0][wv], 4, kAppendBatch, lane);
+    }
+    RT_DEV bool mine(int k) const { return (bits >> k) & 1u; }
+    RT_DEV uint32_t index(int k) const { return interleaved_index(first, bits, k); }
+};
+#define RT_INTERLEAVED_APPEND(name) __shared__ unsigned long long name##_bal[kAppendBatch][4]; __shared__ uint32_t name##_base; InterleavedAppend name; name.bal = name##_bal; name.base = &name##_base
 
 // Light-slot liveness (WaveBuf::shLive / sh2Live): the lanes that call this together set bit `bit` of `live` where `on`.  A wave with no live lane issues no
 // memory operation.  Where the live lanes stand on consecutive bits in lane order (k_gen_direct: one sample, consecutive hits) ONE lane ORs the wave's ballot,

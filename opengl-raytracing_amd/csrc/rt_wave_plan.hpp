@@ -19,6 +19,9 @@ using WaveOptions = RtWaveOptions;
 WaveOptions wave_default_options();
 // The one getenv reader of frame rendering in rt_wave.hip (the traversal builds' switches are tune_from_env's: a kernel argument, shared with the debug entries).
 WaveOptions wave_options_from_env();
+// RT_BATCH_INTERLEAVE (default 1): a batch's candidate list pixel-major, the frames of a pixel side by side (k_primary_interleaved, rt_batch_order.hpp); 0: frame-major, as the
+// slots are.  Read beside wave_options_from_env, once per lane; an order of the lists, not a term of the plan.
+int batch_interleave_from_env();
 
 // RT_BOUNCE_PROBE (auto): the bounce rays are walked any-hit first while the share of them that hit, in earlier launch sets, is below kProbeShareMax.  The
 // any-hit walk proves a miss at 0.72 of the closest-hit walk's cost on the bench view (profiles/r06_bounce_probe.txt); a hit pays both walks, so the probe

@@ -119,6 +119,42 @@ __global__ __launch_bounds__(256) void k_primary(const DevFrame *__restrict__ fr
         if (ap.mine(k)) { wb.cand[idx] = (uint32_t)((blockIdx.x * kAppendBatch + k) * 256 + threadIdx.x); wb.primTri[idx] = -1; }   // the miss answer: PrimarySrc stores hits only
     }
 }
+// k_primary's pixel body for local tile `tile`: the primary ray against the root box.  A pixel that misses it is finished here; the others are candidates.
+// (k_primary keeps its own copy, so that a single frame runs the code it always ran.)
+RT_DEV bool primary_pixel(const DevFrame *__restrict__ fr, const WaveBuf &wb, int tile) {
+    const RtUniforms &u = fr->u;
+    int px, py;
+    const bool live = tile < fr->g.nLocalTiles * max(fr->g.batch, 1) && pixel_of_slot(fr->g, tile, threadIdx.x, px, py);
+    const int slot = tile * 256 + threadIdx.x;
+    bool cand = false;
+    if (live) {
+        V3 dir = primaryDirK(fr, sub_frame_of_tile(fr->g, tile), px, py);
+        V3 rdInv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+        float tmin;
+        cand = fr->sc.hasBVH && slab(ld3(u.camPos), rdInv, ld3(fr->sc.rootMin), ld3(fr->sc.rootMax), tmin) && !(tmin > u.inf);
+        if (!cand) finish_miss(fr, wb, slot, px, py, dir);
+    }
+    return cand;
+}
+// The same stage for a batch of frames (RT_BATCH_INTERLEAVE; a kernel of its own, so that k_primary keeps its code): the workgroup's kAppendBatch iterations walk
+// the frames of a spatial tile before the next tile (batch_tile_of_virtual) and a wave appends pixel by pixel, each pixel's frames side by side
+// (InterleavedAppend) -- the same candidates in the same slots, in another order of the list, and with it of every later list and queue: the frames of a pixel,
+// nearly the same rays, share a wave.
+__global__ __launch_bounds__(256) void k_primary_interleaved(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb) {
+    const int batch = max(fr->g.batch, 1), nl = fr->g.nLocalTiles, total = nl * batch;
+    RT_INTERLEAVED_APPEND(ap);
+    for (int k = 0; k < kAppendBatch; ++k) {
+        const int v = blockIdx.x * kAppendBatch + k;
+        ap.note(k, primary_pixel(fr, wb, v < total ? batch_tile_of_virtual(v, batch, nl) : total));   // (total: no tile, nothing live)
+    }
+    ap.commit(&wb.counts[0]);
+    for (int k = 0; k < kAppendBatch; ++k) {
+        if (!ap.mine(k)) continue;
+        const uint32_t idx = ap.index(k);
+        wb.cand[idx] = (uint32_t)(batch_tile_of_virtual(blockIdx.x * kAppendBatch + k, batch, nl) * 256 + threadIdx.x);
+        wb.primTri[idx] = -1;
+    }
+}
 
 // ---- stage: post_primary -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_post_primary(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb) {   // workgroup = kAppendBatch x 256 candidates

@@ -590,6 +590,38 @@ int rt_nearest_points(const float *nodes12, int nNodes, const float *tris12, int
 int rt_query_nearest(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits);
 int rt_query_nearest_host(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits);
 
+/* ---------------------------------------------------------------- proximity queries: the K nearest triangles and the count within a radius
+ * Which triangles lie within r of a probe, how many, and the K nearest features where one nearest point is ambiguous: a contact manifold instead of
+ * one contact, a brush or selection sphere, a trigger volume against a skinned or refitted mesh, density.
+ *   Points, stride, maxDist, the limit L, empty slots and e(t) exactly as for the nearest-point queries above.  For point i, S is the set of rows t of
+ * tris12 with e(t) <= L true (a NaN e or a NaN L accepts nothing).  The order of the visit is no part of it.
+ *   counts[i] = |S| (counts may be NULL unless maxHits == 0).  hits[i * maxHits + j], j < min(maxHits, |S|), are the maxHits least elements of S under
+ * (e(t), prim) ascending, each {t = e, prim, u, v} with u, v as rt_nearest_points computes them; slots j >= |S| hold the miss record {+inf, -1, 0, 0}.
+ * closest (3 floats per record, n * maxHits * 3 in all, may be NULL) receives the point v0 + u e1 + v e2 of each record, zeros for a miss slot.
+ * maxHits == 0 asks for the counts alone.  The records are RtHit's: the flattened array is an input of rt_mesh_hit_parts, _normals, _colors, _uvs and
+ * _texels as it stands.
+ *   With maxHits == 1, hits and closest equal rt_nearest_points' / rt_query_nearest's on the same arguments bit for bit; counts[i] > 0 exactly when
+ * the nearest-point query answers point i at the same maxDist.
+ *   rt_nearest_points_multi is the definition: host arrays, no context, no GPU; nodes12 / tris12 as rt_build_bvh returns them (a single leaf is a tree).
+ * It returns RT_ERR_INVALID for the refusals below that apply to it, and for nodes that are no tree over the rows.
+ *   rt_query_nearest_multi: device pointers; enqueued on rt_stream()'s stream; no host synchronisation and, after the context's first query, no allocation.
+ * Without counts the walk culls against its maxHits-th best; with counts (or maxHits == 0) every row within L matters and it culls against L alone:
+ * an unbounded count visits the whole tree, so give maxDist with counts.  visits (may be NULL) as rt_query_nearest's: a diagnostic.  hits: n * maxHits
+ * records, 16-byte aligned, required unless maxHits == 0.  RT_ERR_INVALID: maxHits outside 0 .. RT_NEAREST_MULTI_MAX, maxHits == 0 without counts,
+ * n * maxHits beyond INT32_MAX, n < 0, a stride below 3, null or misaligned arrays, a point array beyond 2^32 floats.  RT_ERR_STATE: no BVH uploaded.
+ * A refused call writes nothing; n == 0 is a no-op.  Frame state stays untouched as with rt_trace_rays.
+ *   The _host twin takes host pointers, stages through the context's buffer and synchronises. */
+#define RT_NEAREST_MULTI_MAX 32
+int rt_nearest_points_multi(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *points, int stride,
+                            const float *maxDist /* may be NULL */, int n, int maxHits, RtHit *hits, int32_t *counts /* may be NULL */,
+                            float *closest /* may be NULL */);
+int rt_query_nearest_multi(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, int maxHits, RtHit *hits, int32_t *counts,
+                           float *closest, int32_t *visits);
+int rt_query_nearest_multi_host(RtContext *ctx, const float *points, int stride, const float *maxDist, int n, int maxHits, RtHit *hits, int32_t *counts,
+                                float *closest, int32_t *visits);
+/* (tests) The launch of rt_query_nearest_multi for a stack of stackEntries (1 .. 64) per lane and maxHits records: threads per block and its LDS bytes. */
+int rt_debug_nearest_multi_block(int stackEntries, int maxHits, int *threads, int64_t *ldsBytes);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

@@ -265,6 +265,7 @@ class RtRasterStats(_Struct):
 
 RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1   # rt_trace_rays kinds
 RT_MULTI_HIT_MAX = 32                    # most records per ray of the multi-hit queries
+RT_NEAREST_MULTI_MAX = 32                # most records per point of the proximity queries
 RT_QUERY_SKIP_GLASS, RT_QUERY_SKIP_MARKER = 1, 2   # rt_trace_scene_rays flags
 # rt_trace_scene_rays / rt_pick_pixels objects: the device's material ids
 RT_OBJECT_NONE, RT_OBJECT_FLOOR, RT_OBJECT_ALBEDO_SPHERE, RT_OBJECT_GLASS_SPHERE, RT_OBJECT_MIRROR_SPHERE, RT_OBJECT_POINT_LIGHT, RT_OBJECT_MESH = -1, 0, 1, 2, 3, 4, 5
@@ -369,6 +370,11 @@ SIGNATURES = {
     "rt_nearest_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_query_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_query_nearest_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_nearest_points_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "rt_query_nearest_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_query_nearest_multi_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_debug_nearest_multi_block": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1516,6 +1522,66 @@ def nearest_points(nodes12, tris12, points, max_dist=None) -> NearestPoints:
     return NearestPoints(hits, closest)
 
 
+class NearestMulti:
+    """Answers of nearest_points_multi and Renderer.nearest_points_multi: `hits` [N,K,4] float32 -- K RtHit records {e, prim, u, v} per
+    point, nearest first under (e, prim), the miss record {+inf, -1, 0, 0} past the point's last row within its limit -- with the views dist2 [N,K],
+    prim [N,K] int32 and uv [N,K,2]; `points` [N,K,3], the surface point of each record (zeros for a miss); `count` [N] int32 or None, the number of
+    all the rows within the limit, which may exceed K; `visits` [N] int32 or None.  hits.reshape(-1, 4) is an input of the mesh_hit_* queries as it
+    stands.  numpy arrays or torch tensors, as the points were."""
+
+    def __init__(self, hits, points, count=None, visits=None):
+        self.hits = hits
+        self.points = points
+        self.count = count
+        self.visits = visits
+        self.dist2 = hits[:, :, 0]
+        if isinstance(hits, np.ndarray):
+            self.prim = hits.view(np.int32)[:, :, 1]
+        else:
+            import torch
+            self.prim = hits.view(torch.int32)[:, :, 1]
+        self.uv = hits[:, :, 2:4]
+
+    def __len__(self):
+        return self.hits.shape[0]
+
+
+def _nearest_multi_k(max_hits, counts):
+    k = int(max_hits)
+    if not 0 <= k <= RT_NEAREST_MULTI_MAX:
+        raise _query_invalid(f"max_hits = {k} (0 .. RT_NEAREST_MULTI_MAX = {RT_NEAREST_MULTI_MAX})")
+    if k == 0 and not counts:
+        raise _query_invalid("max_hits = 0 asks for the counts alone and needs counts")
+    return k
+
+
+def nearest_points_multi(nodes12, tris12, points, max_hits, max_dist=None) -> NearestMulti:
+    """The definition of the proximity query (rt_nearest_points_multi), on the host and without a context: per point the max_hits rows of
+    (nodes12, tris12) least under (e, prim) among those with e <= max_dist[i]^2 (no limit without max_dist), and the count of all of them.  Points and
+    max_dist as nearest_points takes them; max_hits = 0 asks for the counts alone."""
+    k = _nearest_multi_k(max_hits, True)
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    n, stride, max_dist = _numpy_points(points, max_dist)
+    hits, closest, count = np.zeros((n, k, 4), np.float32), np.zeros((n, k, 3), np.float32), np.zeros(n, np.int32)
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    rc = lib().rt_nearest_points_multi(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(points), stride, p(max_dist), n, k, p(hits),
+                                       C.c_void_p(count.ctypes.data), p(closest))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_nearest_points_multi: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_nearest_points_multi")
+    return NearestMulti(hits, closest, count)
+
+
+def nearest_multi_block(stack_entries, max_hits):
+    """(threads per block, LDS bytes per block) of rt_query_nearest_multi's launch for a stack of stack_entries per lane and max_hits records
+    (rt_debug_nearest_multi_block).  No GPU."""
+    threads, lds = C.c_int(0), C.c_int64(0)
+    rc = lib().rt_debug_nearest_multi_block(int(stack_entries), int(max_hits), C.byref(threads), C.byref(lds))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_nearest_multi_block")
+    return threads.value, lds.value
+
+
 # ------------------------------------------------------------------------------------ device side
 class Renderer:
     """One RtContext.  Mirrors the reference's per-frame call sequence."""
@@ -2453,6 +2519,44 @@ class Renderer:
             if a is not None:
                 a.record_stream(cur)
         return NearestPoints(hits, closest, vis)
+
+    def nearest_points_multi(self, points, max_hits, max_dist=None, counts=True, visits=False) -> NearestMulti:
+        """The max_hits nearest rows of the uploaded BVH or the dynamic mesh for every point, and the count of all the rows within its limit
+        (rt_query_nearest_multi) -> NearestMulti, equal to nearest_points_multi on the same arrays bit for bit.  Points, max_dist,
+        visits, the numpy / torch paths, stream ordering and lifetimes as nearest_points.  counts=False leaves the count out and lets the walk cull
+        against its max_hits-th best; with counts it visits every box within max_dist, so give max_dist.  max_hits = 0 asks for the counts alone."""
+        k = _nearest_multi_k(max_hits, counts)
+        arrays = [a for a in (points, max_dist) if a is not None]
+        if all(isinstance(a, np.ndarray) for a in arrays):
+            n, stride, max_dist = _numpy_points(points, max_dist)
+            hits, closest = np.zeros((n, k, 4), np.float32), np.zeros((n, k, 3), np.float32)
+            count = np.zeros(n, np.int32) if counts else None
+            vis = np.zeros(n, np.int32) if visits else None
+            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+            self._check(lib().rt_query_nearest_multi_host(self._h, p(points), stride, p(max_dist), n, k, p(hits), p(count), p(closest), p(vis)))
+            return NearestMulti(hits, closest, count, vis)
+        import torch
+        if not all(isinstance(a, torch.Tensor) for a in arrays):
+            raise _query_invalid("points and max_dist must all be numpy arrays or all torch tensors")
+        dev = self._query_device(points, max_dist, dtype=torch.float32)
+        stride = self._ray_rows("points", points, 1, points.stride())
+        n = points.shape[0]
+        if max_dist is not None and (tuple(max_dist.shape) != (n,) or (n > 1 and max_dist.stride(0) != 1)):
+            raise _query_invalid(f"max_dist must be a contiguous [{n}] tensor, got shape {tuple(max_dist.shape)}")
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        closest = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+        vis = torch.empty(n, dtype=torch.int32, device=dev) if visits else None
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                 # the points (and the outputs' allocation) are ready before the query starts
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+        self._check(lib().rt_query_nearest_multi(self._h, p(points), stride, p(max_dist), n, k, p(hits), p(count), p(closest), p(vis)))
+        cur.wait_stream(ext)                 # torch's work after this call sees the answers
+        for a in (points, max_dist):         # (never tied to the library stream: it dies with the context)
+            if a is not None:
+                a.record_stream(cur)
+        return NearestMulti(hits, closest, count, vis)
 
     def _query_device(self, *arrays, dtype):
         import torch

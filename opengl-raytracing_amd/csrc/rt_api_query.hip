@@ -1,6 +1,6 @@
-// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20 and 21): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
-// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest and their _host twins.  Host code only: rt_wave.hip, rt_scene_query.hip, rt_multi_hit.hip and
-// rt_nearest.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21 and 22): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
+// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi and their _host twins.  Host code only: rt_wave.hip, rt_scene_query.hip,
+// rt_multi_hit.hip, rt_nearest.hip and rt_nearest_multi.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include "rt_context.hpp"
 #include "rt_multi_hit.hpp"
 #include "rt_nearest.hpp"
+#include "rt_nearest_multi.hpp"
 
 using namespace rtd;
 using namespace rtapi;
@@ -167,15 +168,26 @@ int multi_launch(RtContext *c, bool mesh, const MultiHitQuery &q) {
 
 // ---- nearest-point queries: the closest surface point per point, by a traversal of their own (rt_nearest.hip).  Share the queries' scratch
 // and event; touch no frame state.
-// What both entries check, before anything is enqueued or written
-int nearest_args(RtContext *c, const char *what, const float *points, int stride, int n, const RtHit *hits) {
+// What the entries check, before anything is enqueued or written.  needHits: the call writes records (not so the proximity query's counts alone)
+int nearest_args(RtContext *c, const char *what, const float *points, int stride, int n, const RtHit *hits, bool needHits) {
     if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
     if (stride < 3) return fail(c, RT_ERR_INVALID, "%s: stride %d floats (at least 3)", what, stride);
     if (n > 0 && !points) return fail(c, RT_ERR_INVALID, "%s: null point array", what);
-    if (n > 0 && !hits) return fail(c, RT_ERR_INVALID, "%s: the query needs hits", what);
+    if (n > 0 && needHits && !hits) return fail(c, RT_ERR_INVALID, "%s: the query needs hits", what);
     if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + 3 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the point array exceeds 2^32 floats", what);
     if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
     return RT_OK;
+}
+
+// ---- proximity queries: the K nearest rows and the count within the limit per point, by a traversal of their own (rt_nearest_multi.hip).
+// Share the queries' scratch and event; touch no frame state.
+// What both entries check, before anything is enqueued or written: the records and counts first, then what nearest_args checks
+int nearest_multi_args(RtContext *c, const char *what, const float *points, int stride, int n, int maxHits, const RtHit *hits, const int32_t *counts) {
+    if (maxHits < 0 || maxHits > RT_NEAREST_MULTI_MAX)
+        return fail(c, RT_ERR_INVALID, "%s: maxHits = %d (0 .. RT_NEAREST_MULTI_MAX = %d)", what, maxHits, RT_NEAREST_MULTI_MAX);
+    if (n > 0 && maxHits == 0 && !counts) return fail(c, RT_ERR_INVALID, "%s: maxHits == 0 asks for the counts alone and needs counts", what);
+    if (n > 0 && (uint64_t)n * (uint64_t)maxHits > (uint64_t)INT32_MAX) return fail(c, RT_ERR_INVALID, "%s: n * maxHits exceeds INT32_MAX records", what);
+    return nearest_args(c, what, points, stride, n, hits, maxHits > 0);
 }
 
 }  // namespace
@@ -299,7 +311,7 @@ int rt_pick_pixels_multi_host(RtContext *c, const RtUniforms *u, const int32_t *
 // ---- nearest-point queries
 int rt_query_nearest(RtContext *c, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits) {
     if (!c) return RT_ERR_INVALID;
-    const int rc = nearest_args(c, "rt_query_nearest", points, stride, n, hits);
+    const int rc = nearest_args(c, "rt_query_nearest", points, stride, n, hits, true);
     if (rc != RT_OK || n == 0) return rc;
     if (((uintptr_t)points | (uintptr_t)maxDist | (uintptr_t)closest | (uintptr_t)visits) & 3u)
         return fail(c, RT_ERR_INVALID, "rt_query_nearest: float and int32 arrays must be 4-byte aligned");
@@ -316,7 +328,7 @@ int rt_query_nearest(RtContext *c, const float *points, int stride, const float 
 
 int rt_query_nearest_host(RtContext *c, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits) {
     if (!c) return RT_ERR_INVALID;
-    const int rc = nearest_args(c, "rt_query_nearest_host", points, stride, n, hits);
+    const int rc = nearest_args(c, "rt_query_nearest_host", points, stride, n, hits, true);
     if (rc != RT_OK || n == 0) return rc;
     // staging layout: points | maxDist | hits | closest | visits; the point array keeps its stride
     const size_t N = (size_t)n;
@@ -324,6 +336,40 @@ int rt_query_nearest_host(RtContext *c, const float *points, int stride, const f
                              {closest, closest ? N * 12 : 0, true}, {visits, visits ? N * 4 : 0, true}};
     return staged(c, "rt_query_nearest_host", segs, [&](void *const *d) {
         return rt_query_nearest(c, (const float *)d[0], stride, (const float *)d[1], n, (RtHit *)d[2], (float *)d[3], (int32_t *)d[4]);
+    });
+}
+
+// ---- proximity queries
+int rt_query_nearest_multi(RtContext *c, const float *points, int stride, const float *maxDist, int n, int maxHits, RtHit *hits, int32_t *counts, float *closest,
+                           int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = nearest_multi_args(c, "rt_query_nearest_multi", points, stride, n, maxHits, hits, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)points | (uintptr_t)maxDist | (uintptr_t)counts | (uintptr_t)closest | (uintptr_t)visits) & 3u)
+        return fail(c, RT_ERR_INVALID, "rt_query_nearest_multi: float and int32 arrays must be 4-byte aligned");
+    if (maxHits > 0 && ((uintptr_t)hits & 15u)) return fail(c, RT_ERR_INVALID, "rt_query_nearest_multi: hits must be 16-byte aligned (one 16-byte store per record)");
+    NearestMultiQuery q = {};
+    q.p = points; q.ps = stride; q.md = maxDist; q.n = (uint32_t)n; q.K = maxHits; q.hits = maxHits ? reinterpret_cast<float4 *>(hits) : nullptr; q.counts = counts;
+    q.closest = maxHits ? closest : nullptr; q.visits = visits;
+    const char *e = getenv("RT_NEAREST_FAR_FIRST");   // (tests) the farther child first: the same answer by another visit order
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    HIP_TRY(c, rt_nearest_multi_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), e && atoi(e) != 0, q));
+    return query_end(c, st);
+}
+
+int rt_query_nearest_multi_host(RtContext *c, const float *points, int stride, const float *maxDist, int n, int maxHits, RtHit *hits, int32_t *counts,
+                                float *closest, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = nearest_multi_args(c, "rt_query_nearest_multi_host", points, stride, n, maxHits, hits, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    // staging layout: points | maxDist | hits | counts | closest | visits; the point array keeps its stride
+    const size_t N = (size_t)n, R = N * (size_t)maxHits;
+    const StageSeg segs[] = {{points, ((N - 1) * stride + 3) * 4, false}, {maxDist, maxDist ? N * 4 : 0, false}, {hits, R * sizeof(RtHit), true},
+                             {counts, counts ? N * 4 : 0, true}, {closest, closest ? R * 12 : 0, true}, {visits, visits ? N * 4 : 0, true}};
+    return staged(c, "rt_query_nearest_multi_host", segs, [&](void *const *d) {
+        return rt_query_nearest_multi(c, (const float *)d[0], stride, (const float *)d[1], n, maxHits, (RtHit *)d[2], (int32_t *)d[3], (float *)d[4], (int32_t *)d[5]);
     });
 }
 

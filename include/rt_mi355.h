@@ -1146,6 +1146,26 @@ int rt_debug_frame_geom(int w, int h, int rank, int world, int batch, int useRec
  *     and a lane's candidates by iteration. */
 int rt_debug_batch_tiles(int batch, int nLocalTiles, int32_t *out);
 int rt_debug_batch_order(const uint64_t *ballots, int n, int waves, uint32_t *out);
+/* Diagnostics, host side (no GPU needed, no context): the beam cull of a batch's primary stage (csrc/rt_beam.hpp, csrc/rt_beam.cpp, DESIGN.md 4.2 "Beam cull"),
+ * the functions k_beam_cull runs as the host compiles them.
+ *   rt_debug_beam_cull: dead[lt] = 1 where every primary ray of local tile lt, in every one of the `batch` frames (jitters: batch pairs; NULL with batch 1 =
+ *     u->jitter), surely misses the tree `records` (nInner two-child records of 16 floats, RT_SCENE_ARRAY_NODES2W; rootRef, rootMin, rootMax from RtPackInfo) --
+ *     0 wherever the argument does not apply.  nLocalTiles must be the frame's (rt_debug_frame_geom).  stats, rdInvOut may be NULL; rdInvOut[((k H + y) W + x) 3 ..]
+ *     = the reciprocal direction of pixel (x, y) in frame k, the floats the cull and the traversal see.
+ *   rt_debug_beam_slab: n boxes (lo, hi) seen from n origins against n intervals [L, H] of reciprocal directions, three floats each: fails[i] = 1 when the slab
+ *     test fails for every ray of the interval; bounds[4 i ..] = {tminLo, tminHi, tmaxLo, tmaxHi}, or four NaN where the argument does not apply.
+ *   rt_debug_beam_cull_stats: the same four sums over the launch sets the context has culled on the device since the call before (reset != 0 clears them). */
+typedef struct RtBeamCullStats { uint64_t tiles, deadTiles, overflowTiles, levels; } RtBeamCullStats;
+int rt_debug_beam_cull(const RtUniforms *u, const float *jitters, int batch, int rank, int world, const float *records, int nInner, int rootRef,
+                       const float *rootMin, const float *rootMax, uint8_t *dead, int nLocalTiles, RtBeamCullStats *stats, float *rdInvOut);
+int rt_debug_beam_slab(int n, const float *ro, const float *lo, const float *hi, const float *L, const float *H, uint8_t *fails, float *bounds);
+/*   rt_debug_beam_walk: n beams from the one origin ro against the tree: verdict[i] of the interval (L + 3 i, H + 3 i) = 0 dead, 1 alive, 2 kept because a level
+ *     of the walk held more than 64 inner nodes; levels[i] (may be NULL) the levels walked. */
+int rt_debug_beam_walk(int n, const float *ro, const float *L, const float *H, const float *records, int nInner, int rootRef, const float *rootMin,
+                       const float *rootMax, uint8_t *verdict, int32_t *levels);
+int rt_debug_beam_cull_stats(RtContext *ctx, RtBeamCullStats *out, int reset);
+/* The dead flags of the launch set the context rendered last, copied to the host: out[nLocalTiles] (synchronises); RT_ERR_STATE when that set was not culled. */
+int rt_debug_beam_cull_flags(RtContext *ctx, uint8_t *out, int nLocalTiles);
 
 /* ---------------------------------------------------------------- host side (no GPU needed) */
 

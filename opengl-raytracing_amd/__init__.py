@@ -474,6 +474,11 @@ SIGNATURES = {
     "rt_debug_frame_geom": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),   # RtFrameGeomInfo
     "rt_debug_batch_tiles": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "rt_debug_batch_order": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int, _U32P]),
+    "rt_debug_beam_cull": (C.c_int, [C.POINTER(RtUniforms), _FP, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.c_int, _FP, _FP, _U8P, C.c_int, C.c_void_p, _FP]),   # RtBeamCullStats
+    "rt_debug_beam_slab": (C.c_int, [C.c_int, _FP, _FP, _FP, _FP, _FP, _U8P, _FP]),
+    "rt_debug_beam_walk": (C.c_int, [C.c_int, _FP, _FP, _FP, _FP, C.c_int, C.c_int, _FP, _FP, _U8P, C.POINTER(C.c_int32)]),
+    "rt_debug_beam_cull_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "rt_debug_beam_cull_flags": (C.c_int, [C.c_void_p, _U8P, C.c_int]),
     "rt_load_obj": (C.c_int, [C.c_char_p, C.POINTER(_FP), C.POINTER(C.c_int), C.POINTER(_U32P), C.POINTER(C.c_int)]),
     "rt_load_png": (C.c_int, [C.c_char_p, C.POINTER(_U8P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_save_png": (C.c_int, [C.c_char_p, _U8P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -1295,6 +1300,64 @@ def batch_order(ballots) -> np.ndarray:
     if rc != RT_OK:
         raise RtError(rc, "rt_debug_batch_order")
     return out
+
+
+class RtBeamCullStats(_Struct):   # rt_debug_beam_cull / rt_debug_beam_cull_stats: the beam cull of a batch's primary stage (RT_BEAM_CULL)
+    _fields_ = [("tiles", C.c_uint64), ("deadTiles", C.c_uint64), ("overflowTiles", C.c_uint64), ("levels", C.c_uint64)]
+
+
+def beam_cull(u, nodes12, tris12, jitters=None, rank=0, world=1, rays=False, packed=None):
+    """rt_debug_beam_cull: the dead flags of the frame shape of `u` on the host -> (dead uint8 [nLocalTiles], RtBeamCullStats[, rd_inv float32 [K, H, W, 3]
+    with rays=True]).  dead[lt] = 1: every primary ray of local tile lt, in each of the K frames whose jitters are `jitters` ([K, 2]; None: the one frame of
+    u.jitter), surely misses the mesh.  packed: a pack_scene result for (nodes12, tris12) to use instead of packing them here."""
+    jit = None if jitters is None else _f32(jitters).reshape(-1, 2)
+    K = 1 if jit is None else jit.shape[0]
+    W, H = int(u.resolution[0]), int(u.resolution[1])
+    info, _ = frame_geom(W, H, rank, world)
+    p = packed if packed is not None else pack_scene(nodes12, tris12)
+    rec = np.ascontiguousarray(p["nodes2w"]).view(np.float32)
+    n_inner = int(p["info"].nInner)
+    lo, hi = _f32(p["info"].rootMin), _f32(p["info"].rootMax)
+    dead = np.zeros(info.nLocalTiles, np.uint8)
+    stats = RtBeamCullStats()
+    rd = np.zeros((K, H, W, 3), np.float32) if rays else None
+    rc = lib().rt_debug_beam_cull(C.byref(u), None if jit is None else _fp(jit), K, int(rank), int(world), _fp(rec) if rec.size else None, n_inner,
+                                  int(p["info"].rootRefW), _fp(lo), _fp(hi), dead.ctypes.data_as(_U8P), info.nLocalTiles, C.byref(stats),
+                                  None if rd is None else _fp(rd))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_beam_cull")
+    return (dead, stats, rd) if rays else (dead, stats)
+
+
+def beam_walk(ro, L, H, nodes12=None, tris12=None, packed=None):
+    """rt_debug_beam_walk: beams [n, 3] float32 (L, H: per axis the least and largest reciprocal direction) from the one origin ro against the tree ->
+    (verdict uint8 [n]: 0 dead, 1 alive, 2 kept because a level of the walk overflowed; levels int32 [n])."""
+    p = packed if packed is not None else pack_scene(nodes12, tris12)
+    rec = np.ascontiguousarray(p["nodes2w"]).view(np.float32)
+    lo, hi, o = _f32(p["info"].rootMin), _f32(p["info"].rootMax), _f32(ro).reshape(3)
+    l, h = _f32(L).reshape(-1, 3), _f32(H).reshape(-1, 3)
+    if l.shape != h.shape:
+        raise ValueError("beam_walk: L and H of different shapes")
+    verdict, levels = np.zeros(l.shape[0], np.uint8), np.zeros(l.shape[0], np.int32)
+    rc = lib().rt_debug_beam_walk(l.shape[0], _fp(o), _fp(l), _fp(h), _fp(rec) if rec.size else None, int(p["info"].nInner), int(p["info"].rootRefW),
+                                  _fp(lo), _fp(hi), verdict.ctypes.data_as(_U8P), levels.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_beam_walk")
+    return verdict, levels
+
+
+def beam_slab(ro, lo, hi, L, H):
+    """rt_debug_beam_slab over [n, 3] float32 arrays -> (fails uint8 [n], bounds float32 [n, 4] = tminLo, tminHi, tmaxLo, tmaxHi; NaN where the argument does
+    not apply)."""
+    a = [_f32(x).reshape(-1, 3) for x in (ro, lo, hi, L, H)]
+    n = a[0].shape[0]
+    if any(x.shape[0] != n for x in a):
+        raise ValueError("beam_slab: arrays of different lengths")
+    fails, bounds = np.zeros(n, np.uint8), np.zeros((n, 4), np.float32)
+    rc = lib().rt_debug_beam_slab(n, *[_fp(x) for x in a], fails.ctypes.data_as(_U8P), _fp(bounds))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_debug_beam_slab")
+    return fails, bounds
 
 
 def load_obj(path):
@@ -2730,6 +2793,20 @@ class Renderer:
         b = RtLightMasks()
         self._check(lib().rt_debug_light_masks(self._h, C.byref(b), int(reset)))
         return b
+
+    def beam_cull_stats(self, reset=False) -> RtBeamCullStats:
+        """Counts of the beam cull since the last reset: tiles walked, dead tiles, tiles kept because a level of the walk overflowed, levels walked
+        (rt_debug_beam_cull_stats).  The kernel counts from the first call on: call once with reset first."""
+        b = RtBeamCullStats()
+        self._check(lib().rt_debug_beam_cull_stats(self._h, C.byref(b), int(reset)))
+        return b
+
+    def beam_cull_flags(self, n_local_tiles) -> np.ndarray:
+        """uint8 [n_local_tiles] (frame_geom(...).nLocalTiles of this rank): the dead flags of the launch set rendered last (rt_debug_beam_cull_flags:
+        synchronises); RtError(RT_ERR_STATE) when that set was not culled."""
+        out = np.zeros(int(n_local_tiles), np.uint8)
+        self._check(lib().rt_debug_beam_cull_flags(self._h, out.ctypes.data_as(_U8P), out.size))
+        return out
 
     def debug_disk_unlit(self, u, hp, normals, seeds=64):
         """rt_debug_disk_unlit: (unlit, lit, maxDot) arrays for n (hp, normal) pairs -- the per-hit test, whether any of the four disk samples of `seeds`

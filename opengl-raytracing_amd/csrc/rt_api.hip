@@ -420,6 +420,13 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
         HIP_TRY(c, hipEventRecord(c->evMeshDone, api_stream(c)));
         HIP_TRY(c, hipStreamWaitEvent(st, c->evMeshDone, 0));
     }
+    const bool count = c->cfg.countWork != 0;
+    int pipeline = c->cfg.pipeline;
+    if (pipeline == RT_PIPELINE_AUTO) pipeline = (fr.u.useBVH == 1 && fr.sc.hasBVH && !count) ? RT_PIPELINE_WAVEFRONT : RT_PIPELINE_MEGAKERNEL;
+    if (pipeline == RT_PIPELINE_WAVEFRONT && !(fr.u.useBVH == 1)) pipeline = RT_PIPELINE_MEGAKERNEL;   // analytic scene: pure ALU, megakernel only
+    // beam cull: BVH frames of the wavefront pipeline; the lane says whether this launch set is culled and where its flags lie
+    const bool cacheResident = (size_t)c->nInner * 64 + c->nWide4 * 128 + c->nPairs * 80 < ((size_t)32 << 20);   // the BVH arrays fit the 32 MB of L2
+    if (pipeline == RT_PIPELINE_WAVEFRONT && !count) fr.tileDead = rt_wave_beam_flags(c->wave[lane], st, fr, std::max(c->treeDepth, 1), cacheResident);
     HIP_TRY(c, hipMemcpyAsync(c->dFrame[lane], &fr, sizeof(fr), hipMemcpyHostToDevice, st));
     if (fr.sc.rootBox) launch_frame_root_box(st, c->dFrame[lane]);
     Targets tg;
@@ -429,10 +436,6 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
     tg.blockSlots = (int)c->nSlots;
     c->histExchanged[lane] = false;   // this lane's exchange buffer belongs to the frame that is about to be rendered
     tg.motion = c->dMotion[lane]; tg.gpos = c->dGPos[lane]; tg.gnrm = c->dGNrm[lane];
-    const bool count = c->cfg.countWork != 0;
-    int pipeline = c->cfg.pipeline;
-    if (pipeline == RT_PIPELINE_AUTO) pipeline = (fr.u.useBVH == 1 && fr.sc.hasBVH && !count) ? RT_PIPELINE_WAVEFRONT : RT_PIPELINE_MEGAKERNEL;
-    if (pipeline == RT_PIPELINE_WAVEFRONT && !(fr.u.useBVH == 1)) pipeline = RT_PIPELINE_MEGAKERNEL;   // analytic scene: pure ALU, megakernel only
     if (batch > 1 && pipeline != RT_PIPELINE_WAVEFRONT) return fail(c, RT_ERR_STATE, "internal: a frame batch reached the megakernel");
     // EXTENSION: the hybrid scene in stages (rt_hybrid.hip) unless the megakernel was asked for; same frames bit for bit
     const bool staged = c->cfg.pipeline != RT_PIPELINE_MEGAKERNEL && fr.u.useBVH == RT_SCENE_HYBRID && fr.sc.hasBVH && !count;
@@ -442,7 +445,7 @@ static int render_frames_impl(RtContext *c, const RtUniforms *uIn, int batch, co
         if (rc != RT_OK) return fail(c, rc, "staged hybrid pipeline: %s", rt_hybrid_error(c->hybrid[0]));
     } else if (pipeline == RT_PIPELINE_WAVEFRONT) {
         int rc = rt_wave_render(c->wave[lane], c, st, c->dFrame[lane], fr, tg, c->dCounters, count, std::max(c->treeDepth, 1), c->nLanes > 1 ? c->evDone[prevLane] : nullptr,
-                                (size_t)c->nInner * 64 + c->nWide4 * 128 + c->nPairs * 80 < ((size_t)32 << 20));
+                                cacheResident);
         if (rc != RT_OK) return fail(c, rc, "wavefront pipeline: %s", rt_wave_error(c->wave[lane]));
     } else {
         if (c->nLanes > 1) HIP_TRY(c, hipStreamWaitEvent(st, c->evDone[prevLane], 0));   // the megakernel reads the history from its first instruction on

@@ -233,6 +233,15 @@ int rt_debug_bounce_probe(RtContext *c, RtBounceProbe *out, int reset) { return 
 int rt_debug_disk_skip(RtContext *c, RtDiskSkip *out, int reset) { return lane_sum_record(c, "rt_debug_disk_skip", rt_wave_disk_skip, out, reset); }
 int rt_debug_gi_list(RtContext *c, RtGiList *out, int reset) { return lane_sum_record(c, "rt_debug_gi_list", rt_wave_gi_list, out, reset); }
 int rt_debug_light_masks(RtContext *c, RtLightMasks *out, int reset) { return lane_sum_record(c, "rt_debug_light_masks", rt_wave_light_masks, out, reset); }
+int rt_debug_beam_cull_stats(RtContext *c, RtBeamCullStats *out, int reset) { return lane_sum_record(c, "rt_debug_beam_cull_stats", rt_wave_beam_cull, out, reset); }
+// the flags of the lane that rendered last
+int rt_debug_beam_cull_flags(RtContext *c, uint8_t *out, int nLocalTiles) {
+    if (!c || !out || nLocalTiles <= 0) return RT_ERR_INVALID;
+    (void)hipSetDevice(c->cfg.device);
+    const int lane = last_lane(c);
+    const int rc = rt_wave_beam_read(c->wave[lane], c->lanes[lane], out, (size_t)nLocalTiles);
+    return rc == RT_OK ? RT_OK : fail(c, rc, "rt_debug_beam_cull_flags: %s", rt_wave_error(c->wave[lane]));
+}
 
 int rt_debug_builds(RtContext *c, uint32_t *out, int reset) {
     if (!c || !out) return RT_ERR_INVALID;

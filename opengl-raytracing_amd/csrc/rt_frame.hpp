@@ -72,6 +72,8 @@ struct DevFrame {   // one copy in HBM, refreshed per frame; kernels read it thr
                                       // albedo.  Behind nrmRows, for the same reason
     const float4 *uvRows = nullptr;   // UVs and the albedo texture: the dynamic mesh's corner UVs, row for row beside sc.tris, and the texture the
     rtuv::Texture tex;                // albedo of a mesh hit is multiplied by; uvRows == null = off (set only with a texture).  Last, behind colRows, for the same reason
+    const uint8_t *tileDead = nullptr;   // beam cull: [local spatial tile] != 0 -- every primary ray of the tile, in every frame of the launch set, misses the
+                                      // mesh (k_beam_cull): the primary stage finishes its pixels at once.  null = no cull.  Last, for the same reason
 };
 
 struct Targets {

@@ -112,6 +112,12 @@ struct RtWave {
     unsigned long long *maskAcc = nullptr;    // device: rt_wave_light_masks' sums -- [0] set bits of queue 1 [1] of queue 2 (k_count_live) [2] mask words scanned [3] masked
     bool maskStatOn = false;                  // refill passes (k_trace); counted only once the entry was called
     unsigned long long maskWordsLast[2] = {0, 0};   // mask words of the last chunk: queue 1, queue 2
+    // beam cull: the lane's own flags, one byte per local spatial tile, grown with the frame
+    int beamCull = rtl::beam_cull_from_env();   // RT_BEAM_CULL: -1 auto (launch sets of two or more frames), 1 single frames too, 0 never
+    uint8_t *beamDead = nullptr;
+    size_t beamCap = 0, beamLast = 0;           // tiles the flags hold room for / tiles of the last culled launch set (0: none yet)
+    unsigned long long *beamAcc = nullptr;      // device: rt_wave_beam_cull's four sums (k_beam_cull); counted only once the entry was called
+    bool beamStatOn = false;
 };
 
 RtWave *rt_wave_create(int cus, RtArenaPool *pool, int lane) {
@@ -142,7 +148,7 @@ void rt_wave_destroy(RtWave *w) {
     if (!w) return;
     if (w->shadeStream) (void)hipStreamDestroy(w->shadeStream);
     if (w->hopEv) (void)hipEventDestroy(w->hopEv);
-    for (void *p : std::initializer_list<void *>{w->frameArena, w->resultArena, w->counts, w->heads, w->acc, w->probeAcc, w->diskAcc, w->giListAcc, w->stats, w->liveMem, w->maskAcc})
+    for (void *p : std::initializer_list<void *>{w->frameArena, w->resultArena, w->counts, w->heads, w->acc, w->probeAcc, w->diskAcc, w->giListAcc, w->stats, w->liveMem, w->maskAcc, w->beamDead, w->beamAcc})
         if (p) (void)hipFree(p);
     if (w->hostHits) (void)hipHostFree(w->hostHits);
     delete w;
@@ -375,7 +381,11 @@ static int wave_primary(LaunchSet &L, unsigned tiles) {
     RtWave *w = L.w;
     const WaveBuf &wb = L.wb;
     const bool interleave = w->batchInterleave && L.host->g.batch > 1;   // a single frame keeps k_primary: nothing to put side by side
-    W_STEP(wave_stage(L, ST_PRIMARY, L.ss, [&] { hipLaunchKernelGGL(interleave ? k_primary_interleaved : k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb); }));
+    W_STEP(wave_stage(L, ST_PRIMARY, L.ss, [&] {
+        // the beam cull (rt_wave_beam_flags chose it for this set): the tiles' flags in front of the kernel that reads them, one wave per local spatial tile
+        if (L.host->tileDead) hipLaunchKernelGGL(k_beam_cull, dim3(((unsigned)std::max(L.host->g.nLocalTiles, 0) + 3u) / 4u), dim3(256), 0, L.ss, L.dFrame, const_cast<uint8_t *>(L.host->tileDead), w->beamStatOn ? w->beamAcc : nullptr);
+        hipLaunchKernelGGL(interleave ? k_primary_interleaved : k_primary, dim3((tiles + kAppendBatch - 1) / kAppendBatch), dim3(256), 0, L.ss, L.dFrame, L.tg, wb);
+    }));
     W_STEP(wave_stage(L, ST_TRACE_PRIMARY, L.st, [&] {
         PrimarySrc ps{};
         ps.fr = L.dFrame; ps.cand = wb.cand; ps.count = &wb.counts[0]; ps.outT = wb.primT; ps.outTri = wb.primTri;
@@ -728,6 +738,42 @@ int rt_wave_light_masks(RtWave *w, hipStream_t st, unsigned long long *out6, boo
     W_STEP(wave_read_sums(w, st, w->maskAcc, 4, out6, reset));
     if (w->lightMasks) { out6[4] = w->maskWordsLast[0]; out6[5] = w->maskWordsLast[1]; }
     w->maskStatOn = true;
+    return RT_OK;
+}
+
+// The beam cull: whether the launch set `host` describes is culled, and where its flags go.  Culled: a BVH frame whose primary launch walks the
+// two-child records k_beam_cull walks (not the fused or implicit forms: their tests are the same floats, but nothing has checked the cull against them), in a launch
+// set of two or more frames over a scene that fits L2 (cacheResident, as rt_wave_render takes it), or any launch set under RT_BEAM_CULL=1.  The flags are the lane's own, grown behind the lane's stream.  null: no cull, or no memory for it.
+const uint8_t *rt_wave_beam_flags(RtWave *w, hipStream_t st, const DevFrame &host, int treeDepth, bool cacheResident) {
+    if (!w) return nullptr;
+    w->beamLast = 0;   // (rt_wave_beam_read: the flags of an earlier set are not this set's)
+    // auto: not for a tree that misses L2 -- the walk's record loads then cost what the (cheap) culled rays saved and more: 1 M triangles 16.955 -> 16.990 ms per frame
+    if (w->beamCull == 0 || (w->beamCull < 0 && (host.g.batch < 2 || !cacheResident))) return nullptr;
+    if (!host.sc.hasBVH || !host.sc.wnodesW || host.g.nLocalTiles <= 0) return nullptr;
+    for (bool stats : {false, true})
+        if (rtl::trace_build(false, w->tune, trace_forms(host.sc), treeDepth, stats).nodes != rtl::TN_WNODESW) return nullptr;
+    const size_t need = (size_t)host.g.nLocalTiles;
+    if (w->beamCap < need) {
+        if (w->beamDead) { if (hipStreamSynchronize(st) != hipSuccess) return nullptr; (void)hipFree(w->beamDead); }
+        w->beamDead = nullptr;
+        w->beamCap = 0;
+        if (hipMalloc(&w->beamDead, need) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        w->beamCap = need;
+    }
+    w->beamLast = need;
+    return w->beamDead;
+}
+int rt_wave_beam_cull(RtWave *w, hipStream_t st, unsigned long long *out4, bool reset) {
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (!w) return RT_OK;
+    W_STEP(wave_read_sums(w, st, w->beamAcc, 4, out4, reset));
+    w->beamStatOn = true;
+    return RT_OK;
+}
+int rt_wave_beam_read(RtWave *w, hipStream_t st, uint8_t *out, size_t n) {
+    if (!w || !w->beamDead || w->beamLast == 0 || n != w->beamLast) { if (w) w->err = "no culled launch set of that many tiles"; return RT_ERR_STATE; }
+    W_TRY(hipStreamSynchronize(st));
+    W_TRY(hipMemcpy(out, w->beamDead, n, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

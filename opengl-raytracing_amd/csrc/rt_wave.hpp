@@ -45,6 +45,13 @@ int rt_wave_gi_list(RtWave *w, hipStream_t stream, unsigned long long *out4, boo
 // any-hit launches scanned [3] their masked refill passes [4] [5] mask words of the lane's last chunk, queue 1 / queue 2 (0: RT_LIGHT_MASKS=0).  [0] - [3] count
 // from the first call on.
 int rt_wave_light_masks(RtWave *w, hipStream_t stream, unsigned long long *out6, bool reset);
+// The beam cull (RT_BEAM_CULL).  rt_wave_beam_flags: called by rt_render_frame(s) BEFORE the frame descriptor `host` goes to the device -- the
+// lane's flags for this launch set (DevFrame::tileDead; k_beam_cull fills them in front of the primary stage), or null when the set is not culled.
+// rt_wave_beam_cull: since the last reset, 4 words: [0] tiles walked [1] dead tiles [2] tiles kept because a level of the walk overflowed [3] levels walked;
+// counted from the first call on.  rt_wave_beam_read: the n flags of the lane's last culled launch set (RT_ERR_STATE: none, or not n tiles).
+const uint8_t *rt_wave_beam_flags(RtWave *w, hipStream_t stream, const rtd::DevFrame &host, int treeDepth, bool cacheResident);
+int rt_wave_beam_cull(RtWave *w, hipStream_t stream, unsigned long long *out4, bool reset);
+int rt_wave_beam_read(RtWave *w, hipStream_t stream, uint8_t *out, size_t n);
 // The share of bounce hits of earlier launch sets (what shadow queue 2 is sized from and the bounce probe is chosen by) belongs to a scene and a frame size:
 // rt_upload_bvh and rt_resize forget it (an spp change does so in rt_wave_render)
 void rt_wave_forget_share(RtWave *w);

@@ -45,6 +45,12 @@ int batch_interleave_from_env() {
     return e ? (atoi(e) != 0 ? 1 : 0) : 1;
 }
 
+int beam_cull_from_env() {
+    const char *e = getenv("RT_BEAM_CULL");
+    if (!e || !*e || !strcmp(e, "auto")) return -1;
+    return atoi(e) != 0 ? 1 : 0;
+}
+
 const char *wave_array_name(int id) {
     static const char *const names[WA_COUNT] = {"cand", "primT", "primTri", "hits", "pendC", "pendPos", "pendNrm", "pendMy", "shO", "shD", "shT", "aoOrg", "giD",
                                                 "giOrg", "sh2O", "sh2D", "sh2T", "occ1", "giT", "giTri", "occ2", "occOvf", "giPos", "giPerm", "giHit"};

@@ -22,6 +22,9 @@ WaveOptions wave_options_from_env();
 // RT_BATCH_INTERLEAVE (default 1): a batch's candidate list pixel-major, the frames of a pixel side by side (k_primary_interleaved, rt_batch_order.hpp); 0: frame-major, as the
 // slots are.  Read beside wave_options_from_env, once per lane; an order of the lists, not a term of the plan.
 int batch_interleave_from_env();
+// RT_BEAM_CULL (DESIGN.md 4.2 "Beam cull"): finish the tiles whose every primary ray surely misses the mesh in front of the primary launch (k_beam_cull).
+// -1 (default, "auto"): launch sets of two or more frames over a scene that fits L2; 1: every launch set, single frames as well; 0: never, the A/B switch.  Read beside batch_interleave_from_env, once per lane.
+int beam_cull_from_env();
 
 // RT_BOUNCE_PROBE (auto): the bounce rays are walked any-hit first while the share of them that hit, in earlier launch sets, is below kProbeShareMax.  The
 // any-hit walk proves a miss at 0.72 of the closest-hit walk's cost on the bench view (profiles/r06_bounce_probe.txt); a hit pays both walks, so the probe

@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "rt_beam.hpp"    // the beam cull's interval arithmetic (k_beam_cull)
 #include "rt_trace.hpp"   // rt_dyn_lds (k_gen_gi_overflow's stacks)
 
 namespace {
@@ -94,6 +95,91 @@ RT_DEV uint32_t block_append(bool pred, uint32_t *counter) {
     return r;
 }
 
+// ---- stage: beam cull (RT_BEAM_CULL) -------------------------------------------------
+// One wave per local spatial tile, in front of the primary stage: tileDead[lt] = 1 when every primary ray of the tile, in every frame of the launch set, surely
+// misses the mesh (rt_beam.hpp has the argument; rt_debug_beam_cull is the same verdict on the host).  The lanes share the tile's 256 x batch rays and reduce their
+// rdInv components to [L, H] per axis; then lane i stands on frontier node i of the interval walk: a level is one record load per lane, two ballots and a
+// compaction by rank (the order of a level's nodes does not matter to the verdict).  stat (rt_debug_beam_cull_stats, null until the entry was called): tiles, dead
+// tiles, tiles kept because a level overflowed, levels walked.
+RT_DEV int nth_set_bit(unsigned long long m, int j) {   // position of the j-th set bit of m, j < popcount(m)
+    int pos = 0;
+    for (int w = 32; w >= 1; w >>= 1) {
+        const int c = __popcll((m >> pos) & ((1ull << w) - 1ull));
+        if (j >= c) { j -= c; pos += w; }
+    }
+    return pos;
+}
+__global__ __launch_bounds__(256) void k_beam_cull(const DevFrame *__restrict__ fr, uint8_t *__restrict__ tileDead, unsigned long long *__restrict__ stat) {
+    const int lane = (int)(threadIdx.x & 63u), lt = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const int nl = fr->g.nLocalTiles, batch = max(fr->g.batch, 1);
+    if (lt >= nl) return;   // (whole waves)
+    rtbeam::Interval I;
+    rtbeam::interval_clear(I);
+    bool bad = false;
+    for (int k = 0; k < batch; ++k)
+        for (int q = 0; q < 4; ++q) {
+            int px, py;
+            if (!pixel_of_slot(fr->g, k * nl + lt, q * 64 + lane, px, py)) continue;
+            const V3 dir = primaryDirK(fr, k, px, py);
+            const V3 rdInv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);   // primary_pixel's three divisions
+            const float r[3] = {rdInv.x, rdInv.y, rdInv.z};
+            for (int a = 0; a < 3; ++a) {
+                if (!rtbeam::usable(r[a])) bad = true;
+                else { I.L[a] = fminr(I.L[a], r[a]); I.H[a] = fmaxr(I.H[a], r[a]); }
+            }
+        }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int a = 0; a < 3; ++a) { I.L[a] = fminr(I.L[a], __shfl_xor(I.L[a], off, 64)); I.H[a] = fmaxr(I.H[a], __shfl_xor(I.H[a], off, 64)); }
+    const float ro[3] = {fr->u.camPos[0], fr->u.camPos[1], fr->u.camPos[2]};
+    int verdict = rtbeam::kAlive, levels = 0;
+    if (fr->sc.hasBVH && __ballot(bad) == 0ull && rtbeam::interval_ok(I.L, I.H)) {
+        if (rtbeam::slab_fails_ok(ro, fr->sc.rootMin, fr->sc.rootMax, I.L, I.H)) verdict = rtbeam::kDead;
+        else if (fr->sc.rootRefW >= 0) {
+            const float4 *nodes = fr->sc.wnodesW;
+            int node = fr->sc.rootRefW, n = 1;   // lane i < n stands on frontier node `node`
+            verdict = rtbeam::kDead;
+            while (n > 0) {
+                ++levels;
+                bool in0 = false, in1 = false, leaf = false;
+                int r0 = 0, r1 = 0;
+                if (lane < n) {
+                    const float4 *rec = nodes + (size_t)node * 4;
+                    const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+                    const float lo0[3] = {a.x, a.y, a.z}, hi0[3] = {b.x, b.y, b.z}, lo1[3] = {c.x, c.y, c.z}, hi1[3] = {d.x, d.y, d.z};
+                    r0 = (int)f2u(a.w); r1 = (int)f2u(b.w);
+                    const bool s0 = !rtbeam::slab_fails_ok(ro, lo0, hi0, I.L, I.H), s1 = !rtbeam::slab_fails_ok(ro, lo1, hi1, I.L, I.H);
+                    leaf = (s0 && r0 < 0) || (s1 && r1 < 0);
+                    in0 = s0 && r0 >= 0; in1 = s1 && r1 >= 0;
+                }
+                if (__ballot(leaf) != 0ull) { verdict = rtbeam::kAlive; break; }
+                const unsigned long long m0 = __ballot(in0), m1 = __ballot(in1);
+                const int p0 = __popcll(m0), total = p0 + __popcll(m1);
+                if (total > rtbeam::kFrontier) { verdict = rtbeam::kOverflow; break; }
+                // the next frontier: the surviving left children in lane order, then the right ones
+                const bool fromLeft = lane < p0;
+                const int src = lane < total ? nth_set_bit(fromLeft ? m0 : m1, fromLeft ? lane : lane - p0) : 0;
+                const int fromL = __shfl(r0, src, 64), fromR = __shfl(r1, src, 64);
+                node = fromLeft ? fromL : fromR;
+                n = total;
+            }
+        }
+    }
+    if (lane == 0) {
+        tileDead[lt] = verdict == rtbeam::kDead ? 1 : 0;
+        if (stat) {
+            atomicAdd(&stat[0], 1ull);
+            if (verdict == rtbeam::kDead) atomicAdd(&stat[1], 1ull);
+            if (verdict == rtbeam::kOverflow) atomicAdd(&stat[2], 1ull);
+            if (levels) atomicAdd(&stat[3], (unsigned long long)levels);
+        }
+    }
+}
+// the primary stage's reading of those flags: local tile `tile` of the batch (< nLocalTiles * batch) lies in a dead spatial tile
+RT_DEV bool tile_is_dead(const DevFrame *__restrict__ fr, int tile) {
+    const uint8_t *dead = fr->tileDead;
+    return dead && dead[tile - sub_frame_of_tile(fr->g, tile) * max(fr->g.nLocalTiles, 1)] != 0;
+}
+
 // ---- stage: primary ----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_primary(const DevFrame *__restrict__ fr, Targets tg, WaveBuf wb) {   // workgroup = kAppendBatch tiles
     const RtUniforms &u = fr->u;
@@ -106,10 +192,13 @@ __global__ __launch_bounds__(256) void k_primary(const DevFrame *__restrict__ fr
         bool cand = false;
         if (live) {
             V3 dir = primaryDirK(fr, sub_frame_of_tile(fr->g, tile), px, py);
-            V3 rdInv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-            float tmin;
-            cand = fr->sc.hasBVH && slab(ld3(u.camPos), rdInv, ld3(fr->sc.rootMin), ld3(fr->sc.rootMax), tmin) && !(tmin > u.inf);
-            if (!cand) finish_miss(fr, wb, slot, px, py, dir);
+            if (tile_is_dead(fr, tile)) finish_miss(fr, wb, slot, px, py, dir);   // the beam cull: what k_post_primary would have called, with the same arguments
+            else {
+                V3 rdInv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+                float tmin;
+                cand = fr->sc.hasBVH && slab(ld3(u.camPos), rdInv, ld3(fr->sc.rootMin), ld3(fr->sc.rootMax), tmin) && !(tmin > u.inf);
+                if (!cand) finish_miss(fr, wb, slot, px, py, dir);
+            }
         }
         ap.note(k, cand);
     }
@@ -129,6 +218,7 @@ RT_DEV bool primary_pixel(const DevFrame *__restrict__ fr, const WaveBuf &wb, in
     bool cand = false;
     if (live) {
         V3 dir = primaryDirK(fr, sub_frame_of_tile(fr->g, tile), px, py);
+        if (tile_is_dead(fr, tile)) { finish_miss(fr, wb, slot, px, py, dir); return false; }   // the beam cull, as in k_primary
         V3 rdInv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
         float tmin;
         cand = fr->sc.hasBVH && slab(ld3(u.camPos), rdInv, ld3(fr->sc.rootMin), ld3(fr->sc.rootMax), tmin) && !(tmin > u.inf);

@@ -10,7 +10,11 @@ pushed through slab() at its two ends, and a walk over the two-child records fin
   origin on a box plane are inside the argument (c = 0 gives t = +-0 at both ends, c0 == c1 gives t0 == t1; rt_beam.hpp): their keep-cases are the boxes a ray of
   the interval passes -- slab() holds there with tmax == tmin or at t = 0 -- and those must be kept;
 * the walk, per view: no ray of any sub-frame of a dead tile reaches a leaf in a brute-force per-ray walk of the same records, and the oracle's primary hits show
-  every such pixel as a miss; the non-vacuity conditions on the 160x96 close-up; a beam that covers the whole mesh is kept by frontier overflow.
+  every such pixel as a miss; the non-vacuity conditions on the 160x96 close-up; a beam that covers the whole mesh is kept by frontier overflow;
+* the walk against a restatement that shares no line with rt_beam.hpp (beam_cull_cases.walk): per tile of every view the same verdict and the same count of
+  levels, over all tiles the sums rt.beam_cull reports; the comb scenes reach the widths they were built for -- dead behind a level of 32, of 33 .. 63 and of 64
+  nodes, a level of 64 behind a level of 64, overflow at exactly 65 survivors and at 128 -- and their hit variants are alive through one node of the widest level;
+* a ray with a zero direction component (the sliver scenes): the tile that holds it is kept by that rule alone and holds the only hits of the frame.
 """
 import numpy as np
 import pytest
@@ -180,6 +184,107 @@ def test_dead_tiles_hold_no_ray_that_reaches_a_leaf(orc, case):
         assert dead.all() and stats.levels == 0                              # culled at the root box
     if case in ("one_leaf_64x48", "inside_root_box_64x48"):
         assert not dead.all()                                                # somebody sees the mesh
+
+
+def _widest(entry):
+    return max(entry[2]) if entry[2] else 0
+
+
+@pytest.mark.parametrize("case", list(bc.CASES))
+def test_the_header_walk_equals_an_independent_walk(case):
+    """bc.walk restates the root-box test, the breadth-first frontier, the overflow rule and the count of levels in numpy, and shares no line with rt_beam.hpp:
+    per tile rt.beam_walk gives its verdict and its levels, and rt.beam_cull's flags and sums are those of the tiles."""
+    m, w, h, _, _ = bc.CASES[case]
+    dead, stats, rd = bc.host_cull(case)
+    ro = np.array(list(bc.uniforms(case)[0].camPos), f32)
+    mine = bc.independent_cull(case)
+    assert len(mine) == dead.size
+    for t, ((L, H, ok), (verdict, levels, _)) in enumerate(zip(bc.tile_intervals(rd, w, h), mine)):
+        if not ok or ((L > 0) != (H > 0)).any():                            # an unusable component, or an axis of both signs: kept, nothing walked
+            assert (verdict, levels) == (bc.ALIVE, 0), (case, t)
+        v, lv = rt.beam_walk(ro, L, H, packed=bc.packed(m))
+        assert (int(v[0]), int(lv[0])) == (verdict, levels), (case, t)
+        assert dead[t] == (verdict == bc.DEAD), (case, t)
+    verdicts = [e[0] for e in mine]
+    assert (stats.tiles, stats.deadTiles, stats.overflowTiles, stats.levels) == (len(mine), verdicts.count(bc.DEAD), verdicts.count(bc.OVERFLOW), sum(e[1] for e in mine))
+
+
+def test_the_comb_scenes_reach_the_wide_levels():
+    """The widths the comb scenes exist for, by the independent walk -- conditions, not measurements: a dead verdict behind a level of 32 inner nodes, of 33 .. 63
+    and of exactly 64; a level of 64 that follows a level of more than 32 (a compaction out of the upper half of the lanes); overflow at exactly 65 survivors and
+    at 128 or more.  At this builder: tile (2, 1) of comb32 32, comb64s33 33, comb64s40 40, comb64 64, comb128s64 64, comb128alt 64 behind 64, all dead;
+    comb128s65 65 and comb128 128, both kept by overflow.  The hit scenes (comb128alt_h*, comb64_h*): the same widths, and the tile alive through one node of
+    the widest level -- the verdict that shows a node lost on the way."""
+    dead_widths, overflow_widths, full_steps = set(), set(), []
+    for case in bc.COMB_CASES:
+        mine = bc.independent_cull(case)
+        t = bc.COMB_TILE[1] * 10 + bc.COMB_TILE[0]
+        for verdict, levels, widths in mine:
+            if verdict == bc.DEAD and levels:
+                dead_widths.add(max(widths))
+                full_steps += [case for a, b in zip(widths, widths[1:]) if a > 32 and b == 64]
+            if verdict == bc.OVERFLOW:
+                assert max(widths[:-1]) <= 64 < widths[-1]
+                overflow_widths.add(widths[-1])
+        # the scene's own tile carries the scene's width
+        slabs, straddle, hit = bc.COMBS[bc.CASES[case][0]]
+        want = slabs if straddle is None else slabs // 2 if straddle == "alternate" else straddle
+        assert _widest(mine[t]) == want and mine[t][0] == (bc.ALIVE if hit is not None else bc.DEAD if want <= 64 else bc.OVERFLOW), (case, mine[t])
+        if hit is not None:
+            # alive through one node of the 64: the same scene without the hit is dead, and the leaf shows at the level that stands on the 64 slabs
+            assert not bc.comb_moved(hit, straddle) and mine[t][2][-1] == 64 and mine[t][1] == len(mine[t][2])
+            assert bc.independent_cull(f"comb{slabs}{'alt' if straddle else ''}_160x96")[t][0] == bc.DEAD
+            if straddle == "alternate":
+                assert mine[t][2][-2:] == [64, 64]                           # ... behind a compaction of 64 nodes into 64
+        verdicts = [e[0] for e in mine]
+        assert verdicts.count(bc.ALIVE) > 0 and sum(1 for e in mine if e[0] == bc.DEAD and e[1] == 0) > 0      # tiles that see a leaf, tiles dead at the root box
+    assert 32 in dead_widths, f"no dead tile behind a level of 32: {sorted(dead_widths)}"
+    assert any(33 <= x <= 63 for x in dead_widths), f"no dead tile behind a level of 33 .. 63: {sorted(dead_widths)}"
+    assert 64 in dead_widths, f"no dead tile behind a level of 64: {sorted(dead_widths)}"
+    assert full_steps, "no dead tile with a level of 64 behind a level of more than 32"
+    assert 65 in overflow_widths, f"no overflow at exactly 65 survivors: {sorted(overflow_widths)}"
+    assert any(x >= 128 for x in overflow_widths), f"no overflow at 128 or more survivors: {sorted(overflow_widths)}"
+
+
+@pytest.mark.parametrize("tris", [2, 16])
+def test_a_zero_direction_component_keeps_the_tile(orc, tris):
+    """The sliver scenes: with a jitter of -0.5 pixel column 32 has dir.x == 0 and rdInv.x == inf, and only those rays meet the strip.  Tile 2 is alive by the
+    unusable-component rule alone -- the interval of its other rays fails the root box -- and holds the strip's hits; with a jitter of -0.25 nothing is infinite,
+    no ray of the tile passes the box and the tile is dead."""
+    zero, ctrl = f"sliver{tris}_zero_64x48", f"sliver{tris}_ctrl_64x48"
+    m, w, h, _, _ = bc.CASES[zero]
+    p = bc.packed(m)
+    assert (p["info"].rootRefW < 0) == (tris == 2) and bc.mesh(m)[1].shape[0] == tris         # the root a leaf / a walk below the root
+    lo, hi = f32(p["info"].rootMin), f32(p["info"].rootMax)
+    ro = np.array(bc.SLIVER_POS, f32)
+    tile = bc.tile_of_pixels(w, h) == bc.SLIVER_TILE
+    # jitter -0.5
+    dead, _, rd = bc.host_cull(zero)
+    inf_cols = np.unique(np.nonzero(np.isinf(rd[..., 0]))[2])
+    assert inf_cols.tolist() == [32] and np.isinf(rd[:, :, 32, 0]).all() and bc.usable(rd[..., 1:]).all()
+    assert dead[bc.SLIVER_TILE] == 0 and bc.independent_cull(zero)[bc.SLIVER_TILE] == (bc.ALIVE, 0, [])
+    rays = rd[:, tile]                                                       # [K, 256, 3]
+    good = rays[bc.usable(rays).all(-1)]
+    assert good.shape[0] == bc.HAND_K * 240
+    L, H = good.min(0), good.max(0)
+    assert bc.interval_ok(L, H) and bc.slab_fails(ro, lo, hi, L, H) and rt.beam_slab(ro, lo, hi, L, H)[0][0] == 1
+    assert rt.beam_walk(ro, L, H, packed=p)[0][0] == bc.DEAD
+    passing = bc.slab(ro, rays.reshape(-1, 3), lo, hi)[0].reshape(bc.HAND_K, 16, 16)
+    assert passing.sum() == 48 and passing[:, :, 1:].sum() == 0 and (passing[:, :, 0].sum(1) == 12).all()     # 12 pixels x 4 frames, all in column 32
+    hits = 0
+    for u in bc.uniforms(zero):
+        prim = orc.primary_hits(u, *bc.mesh(m))[0][:, 1].copy().view(np.int32).reshape(h, w)
+        assert (prim[~tile] < 0).all() and (prim[:, 33:] < 0).all()
+        hits += int((prim[:, 32] >= 0).sum())
+    assert hits > 0
+    # jitter -0.25
+    dead, _, rd = bc.host_cull(ctrl)
+    assert bc.usable(rd).all()
+    assert dead[bc.SLIVER_TILE] == 1 and bc.independent_cull(ctrl)[bc.SLIVER_TILE] == (bc.DEAD, 0, [])
+    assert not bc.slab(ro, rd[:, tile].reshape(-1, 3), lo, hi)[0].any()
+    for u in bc.uniforms(ctrl):
+        prim = orc.primary_hits(u, *bc.mesh(m))[0][:, 1].copy().view(np.int32).reshape(h, w)
+        assert (prim[tile] < 0).all()
 
 
 def test_non_vacuity_of_the_closeup(orc):

@@ -622,6 +622,44 @@ int rt_query_nearest_multi_host(RtContext *ctx, const float *points, int stride,
 /* (tests) The launch of rt_query_nearest_multi for a stack of stackEntries (1 .. 64) per lane and maxHits records: threads per block and its LDS bytes. */
 int rt_debug_nearest_multi_block(int stackEntries, int maxHits, int *threads, int64_t *ldsBytes);
 
+/* ---------------------------------------------------------------- box queries: the triangles overlapping an axis-aligned box, per box
+ * Which triangles touch a volume: trigger volumes, brush and marquee selection through hidden layers, broad-phase pairs for a narrow phase of the
+ * caller's own, conservative voxelisation -- against the uploaded BVH or the dynamic mesh after any rebuild, refit or update.
+ *   Box i is boxes[i * stride .. i * stride + 5] = lo.xyz, hi.xyz (stride >= 6 floats), the closed box Q = [lo, hi]: touching counts.  A NaN component
+ * or lo > hi on any axis marks an empty slot (count 0, nothing listed); +-inf components are legal, a box that spans everything lists everything.  A
+ * box [bmin, bmax] overlaps Q when on all three axes !(bmax < lo) && !(hi < bmin): comparisons only.
+ *   Row t of tris12 is accepted when (a) the box of every node from the root to t's leaf overlaps Q and (b) the 13-axis separating-axis test finds no
+ * separating axis between Q and the triangle a = v0, b = fl(v0 + e1), c = fl(v0 + e2) -- the three points rt_build_bvh and the refit take the boxes
+ * from.  The test forms no centre and no half-extent: the box axes by the overlap test above on the componentwise min / max of a, b, c; the normal
+ * cross(e1, e2), on which the triangle projects to dot(n, a); the nine axes cross(unit_k, f), f = e1, fl(e2 - e1), e2, on which it projects to the min
+ * and max of its vertices' projections.  On these ten the box projects to [sum_k min(n_k lo_k, n_k hi_k), sum_k max(n_k lo_k, n_k hi_k)], and an axis
+ * separates only when tmax < bmin || bmax < tmin is true: a NaN (0 * inf, inf - inf, an overflowed product) never separates, so infinite and huge
+ * boxes err towards overlap.  DESIGN.md 23.1 has every operation.  For trees whose node boxes are the float min / max of a, b, c of their rows --
+ * every tree this library builds -- (b) implies (a).
+ *   The list of box i is its accepted rows in the order of a depth-first walk that takes the RIGHT child before the left and the rows of a leaf
+ * ascending: a function of the tree and the box alone.  For the trees rt_build_bvh and the device builders make, that walk meets the rows in
+ * ascending order, so the list is ascending in prim; for other trees it is the walk order.
+ *   counts[i] = the number of accepted rows (counts may be NULL when prims is given).  prims (may be NULL: the counts alone): slot i starts at
+ * offsets[i] and holds offsets[i + 1] - offsets[i] entries (none if that is negative, or the start is) -- offsets has n + 1 entries -- or, with offsets
+ * NULL, starts at i * cap and holds cap entries.  The first min(capacity, counts[i]) rows of the list are written there; entries past them are NOT
+ * written.  Two patterns follow: count, exclusive scan, list -- the exact list in two calls; or one call with a fixed cap, where counts[i] > cap
+ * says that slot i overflowed.  {0, prim, 1/3, 1/3} is an RtHit for the rt_mesh_hit_* queries (the part, colour or normal of a listed triangle).
+ *   rt_box_overlaps is the definition: host arrays, no context, no GPU; nodes12 / tris12 as rt_build_bvh returns them (a single leaf is a tree).  It
+ * returns RT_ERR_INVALID for the refusals below that apply to it, and for nodes that are no tree over the rows.
+ *   rt_query_boxes: device pointers (offsets included: it is not inspected on the host); enqueued on rt_stream()'s stream; no host synchronisation
+ * and, after the context's first query, no allocation.  One lane walks one box: a single box that lists tens of thousands of rows is serial in its
+ * lane.  visits (may be NULL): visits[i] = the number of boxes tested for box i -- 1 + twice the inner nodes entered, 0 for an empty slot -- which
+ * here is a function of the tree and the box.  RT_ERR_INVALID: n < 0, a stride below 6, null boxes, prims and counts both NULL, prims without offsets
+ * and cap < 0 or n * cap beyond INT32_MAX, misaligned arrays, a box array beyond 2^32 floats.  RT_ERR_STATE: no BVH uploaded.  A refused call writes
+ * nothing; n == 0 is a no-op.  Frame state stays untouched as with rt_trace_rays.
+ *   The _host twin takes host pointers, stages through the context's buffer and synchronises; its prims array holds offsets[n] entries (offsets must
+ * then be ascending from 0), or n * cap. */
+int rt_box_overlaps(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *boxes, int stride /* >= 6: lo.xyz, hi.xyz */, int n,
+                    const int32_t *offsets /* n + 1 entries, or NULL */, int cap, int32_t *prims /* may be NULL */, int32_t *counts /* may be NULL, not both */);
+int rt_query_boxes(RtContext *ctx, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits);
+int rt_query_boxes_host(RtContext *ctx, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts,
+                        int32_t *visits);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

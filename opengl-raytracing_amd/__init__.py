@@ -375,6 +375,9 @@ SIGNATURES = {
     "rt_query_nearest_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_query_nearest_multi_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_nearest_multi_block": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "rt_box_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_query_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_query_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1645,6 +1648,109 @@ def nearest_multi_block(stack_entries, max_hits):
     return threads.value, lds.value
 
 
+class BoxOverlaps:
+    """Answers of box_overlaps and Renderer.box_overlaps: `count` [N] int32, the number of rows overlapping each box; `offsets` [N+1]
+    int32 and `prims` flat int32 -- the list of box i is prims[offsets[i] : offsets[i] + min(count[i], offsets[i+1] - offsets[i])], in walk order
+    (ascending for the trees the library builds).  With cap=None the slots are exact; with cap=k every slot holds k entries, those past the list are
+    -1, and count[i] > k says that box i overflowed.  `visits` [N] int32 or None.  numpy arrays or torch tensors, as the boxes were."""
+
+    def __init__(self, count, offsets, prims, visits=None):
+        self.count = count
+        self.offsets = offsets
+        self.prims = prims
+        self.visits = visits
+
+    def hits(self):
+        """The flat list as RtHit records {0, prim, 1/3, 1/3} [len(prims),4] float32 (prim -1: the miss record's prim): an input of the mesh_hit_*
+        queries as it stands -- the part, colour or normal at the centroid of every listed triangle."""
+        third = np.float32(1.0) / np.float32(3.0)
+        if isinstance(self.prims, np.ndarray):
+            rec = np.zeros((self.prims.shape[0], 4), np.float32)
+            rec.view(np.int32)[:, 1] = self.prims
+            rec[:, 2:4] = third
+            return rec
+        import torch
+        rec = torch.zeros((self.prims.shape[0], 4), dtype=torch.float32, device=self.prims.device)
+        rec.view(torch.int32)[:, 1] = self.prims
+        rec[:, 2:4] = float(third)
+        return rec
+
+    def __len__(self):
+        return self.count.shape[0]
+
+
+def _box_rows(a, itemsize, strides):
+    """The checks of the box queries on a [N,k] box array, k >= 6 -> the row stride in floats."""
+    if a.ndim != 2 or a.shape[1] < 6:
+        raise _query_invalid(f"boxes must be [N,k] with k >= 6 (lo.xyz, hi.xyz), got shape {tuple(a.shape)}")
+    row, col = strides
+    if col != itemsize or row % itemsize or (a.shape[0] > 1 and row // itemsize < 6):
+        raise _query_invalid("boxes must have unit stride along its last dimension and rows at least 6 floats apart")
+    return max(row // itemsize, 6) if a.shape[0] > 1 else max(a.shape[1], 6)
+
+
+def _box_cap(cap):
+    if cap is None:
+        return None
+    k = int(cap)
+    if k < 0:
+        raise _query_invalid(f"cap = {k}")
+    return k
+
+
+def _numpy_boxes(boxes):
+    if not isinstance(boxes, np.ndarray):
+        raise _query_invalid("boxes must be a numpy array")
+    if boxes.dtype != np.float32:
+        raise _query_invalid(f"boxes must be float32, got {boxes.dtype}")
+    return boxes.shape[0] if boxes.ndim == 2 else -1, _box_rows(boxes, 4, boxes.strides)
+
+
+def _numpy_box_query(call, boxes, cap, visits):
+    """Both forms on host arrays: call(boxes, stride, n, offsets, cap, prims, counts, visits) -> rc, checked by the caller's wrapper."""
+    n, stride = _numpy_boxes(boxes)
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    count = np.zeros(n, np.int32)
+    vis = np.zeros(n, np.int32) if visits else None
+    if cap is not None:
+        if n * cap > 2 ** 31 - 1:
+            raise _query_invalid(f"{n} boxes x cap {cap} exceed INT32_MAX entries")
+        offsets = (np.arange(n + 1, dtype=np.int64) * cap).astype(np.int32)
+        prims = np.full(n * cap, -1, np.int32)
+        if n:
+            call(p(boxes), stride, n, None, cap, p(prims), p(count), p(vis))
+        return BoxOverlaps(count, offsets, prims, vis)
+    offsets = np.zeros(n + 1, np.int32)
+    if n:
+        call(p(boxes), stride, n, None, 0, None, p(count), p(vis))
+        total = np.cumsum(count, dtype=np.int64)
+        if total[-1] > 2 ** 31 - 1:
+            raise _query_invalid(f"the lists hold {int(total[-1])} entries, beyond INT32_MAX")
+        offsets[1:] = total
+    prims = np.full(int(offsets[-1]), -1, np.int32)
+    if prims.size:
+        call(p(boxes), stride, n, p(offsets), 0, p(prims), None, None)
+    return BoxOverlaps(count, offsets, prims, vis)
+
+
+def box_overlaps(nodes12, tris12, boxes, cap=None) -> BoxOverlaps:
+    """The definition of the box query (rt_box_overlaps), on the host and without a context: per closed box [lo, hi] the rows of
+    (nodes12, tris12) that lie under overlapping node boxes and that the 13-axis separating-axis test cannot part from it, in walk order, and their
+    count.  boxes: float32 [N,k], k >= 6 (lo.xyz, hi.xyz), rows may be strided (numpy); a NaN component or lo > hi marks an empty slot.  cap=None:
+    the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per box."""
+    cap = _box_cap(cap)
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+
+    def call(b, stride, n, offsets, cap_, prims, counts, _visits):
+        rc = lib().rt_box_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], b, stride, n, offsets, cap_, prims, counts)
+        if rc != RT_OK:
+            raise RtError(rc, "rt_box_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_box_overlaps")
+
+    return _numpy_box_query(call, boxes, cap, False)
+
+
 # ------------------------------------------------------------------------------------ device side
 class Renderer:
     """One RtContext.  Mirrors the reference's per-frame call sequence."""
@@ -2620,6 +2726,57 @@ class Renderer:
             if a is not None:
                 a.record_stream(cur)
         return NearestMulti(hits, closest, count, vis)
+
+    def box_overlaps(self, boxes, cap=None, visits=False) -> BoxOverlaps:
+        """The rows of the uploaded BVH or the dynamic mesh that overlap each axis-aligned box (rt_query_boxes) -> BoxOverlaps, equal to
+        box_overlaps on the same arrays bit for bit.  boxes: float32 [N,k], k >= 6 (lo.xyz, hi.xyz), rows may be strided; a NaN component or lo > hi
+        marks an empty slot.  cap=None: the exact lists in two passes -- count, an exclusive scan (torch.cumsum on the device), allocate, list: the
+        allocation waits for the total.  cap=k: one call into k entries per box, no host wait; count[i] > k says that box i overflowed.  visits=True
+        also returns the number of boxes tested per box.  One lane walks one box: few boxes that each list very many rows run serially.  numpy /
+        torch paths, stream ordering and lifetimes as nearest_points."""
+        cap = _box_cap(cap)
+        if isinstance(boxes, np.ndarray):
+            call = lambda *a: self._check(lib().rt_query_boxes_host(self._h, *a))
+            return _numpy_box_query(call, boxes, cap, visits)
+        import torch
+        if not isinstance(boxes, torch.Tensor):
+            raise _query_invalid("boxes must be a numpy array or a torch tensor")
+        dev = self._query_device(boxes, dtype=torch.float32)
+        stride = _box_rows(boxes, 1, boxes.stride() if boxes.dim() == 2 else (0, 0))
+        n = boxes.shape[0]
+        if cap is not None and n * cap > 2 ** 31 - 1:
+            raise _query_invalid(f"{n} boxes x cap {cap} exceed INT32_MAX entries")
+        count = torch.zeros(n, dtype=torch.int32, device=dev)
+        vis = torch.zeros(n, dtype=torch.int32, device=dev) if visits else None
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+
+        def query(offsets, cap_, prims, counts, vis_):
+            ext.wait_stream(cur)             # the boxes (and the outputs' allocation and fill) are ready before the query starts
+            self._check(lib().rt_query_boxes(self._h, p(boxes), stride, n, p(offsets), cap_, p(prims), p(counts), p(vis_)))
+            cur.wait_stream(ext)             # torch's work after this call sees the answers
+
+        if cap is not None:
+            offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * cap).to(torch.int32)
+            prims = torch.full((n * cap,), -1, dtype=torch.int32, device=dev)
+            if n:
+                query(None, cap, prims, count, vis)          # (cap = 0: no prims, the counts alone)
+        else:
+            offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+            total = 0
+            if n:
+                query(None, 0, None, count, vis)
+                scan = torch.cumsum(count, 0, dtype=torch.int64)
+                total = int(scan[-1])        # (the one host wait of the exact form: the list's allocation needs the total)
+                if total > 2 ** 31 - 1:
+                    raise _query_invalid(f"the lists hold {total} entries, beyond INT32_MAX")
+                offsets[1:] = scan.to(torch.int32)
+            prims = torch.full((total,), -1, dtype=torch.int32, device=dev)
+            if total:
+                query(offsets, 0, prims, None, None)
+        boxes.record_stream(cur)             # (never tied to the library stream: it dies with the context)
+        return BoxOverlaps(count, offsets, prims, vis)
 
     def _query_device(self, *arrays, dtype):
         import torch

@@ -1,11 +1,12 @@
-// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21 and 22): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
-// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi and their _host twins.  Host code only: rt_wave.hip, rt_scene_query.hip,
-// rt_multi_hit.hip, rt_nearest.hip and rt_nearest_multi.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21, 22 and 23): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
+// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes and their _host twins.  Host code only: rt_wave.hip,
+// rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip and rt_box_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 
+#include "rt_box_query.hpp"
 #include "rt_context.hpp"
 #include "rt_multi_hit.hpp"
 #include "rt_nearest.hpp"
@@ -190,6 +191,21 @@ int nearest_multi_args(RtContext *c, const char *what, const float *points, int 
     return nearest_args(c, what, points, stride, n, hits, maxHits > 0);
 }
 
+// ---- box queries: the rows overlapping an axis-aligned box per box, by a traversal of their own (rt_box_query.hip).  Share the queries'
+// scratch and event; touch no frame state.
+// What both entries check, before anything is enqueued or written.  offsets is the caller's to get right: device memory for rt_query_boxes
+int box_args(RtContext *c, const char *what, const float *boxes, int stride, int n, const int32_t *offsets, int cap, const int32_t *prims, const int32_t *counts) {
+    if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
+    if (stride < 6) return fail(c, RT_ERR_INVALID, "%s: stride %d floats (at least 6: lo.xyz, hi.xyz)", what, stride);
+    if (n > 0 && !boxes) return fail(c, RT_ERR_INVALID, "%s: null box array", what);
+    if (n > 0 && !prims && !counts) return fail(c, RT_ERR_INVALID, "%s: the query needs prims or counts", what);
+    if (prims && !offsets && cap < 0) return fail(c, RT_ERR_INVALID, "%s: cap = %d without offsets", what, cap);
+    if (prims && !offsets && (uint64_t)n * (uint64_t)cap > (uint64_t)INT32_MAX) return fail(c, RT_ERR_INVALID, "%s: n * cap exceeds INT32_MAX entries", what);
+    if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + 6 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the box array exceeds 2^32 floats", what);
+    if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -370,6 +386,46 @@ int rt_query_nearest_multi_host(RtContext *c, const float *points, int stride, c
                              {counts, counts ? N * 4 : 0, true}, {closest, closest ? R * 12 : 0, true}, {visits, visits ? N * 4 : 0, true}};
     return staged(c, "rt_query_nearest_multi_host", segs, [&](void *const *d) {
         return rt_query_nearest_multi(c, (const float *)d[0], stride, (const float *)d[1], n, maxHits, (RtHit *)d[2], (int32_t *)d[3], (float *)d[4], (int32_t *)d[5]);
+    });
+}
+
+// ---- box queries
+int rt_query_boxes(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = box_args(c, "rt_query_boxes", boxes, stride, n, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)boxes | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
+        return fail(c, RT_ERR_INVALID, "rt_query_boxes: float and int32 arrays must be 4-byte aligned");
+    BoxQuery q = {};
+    q.b = boxes; q.bs = stride; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    HIP_TRY(c, rt_box_query_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
+    return query_end(c, st);
+}
+
+int rt_query_boxes_host(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = box_args(c, "rt_query_boxes_host", boxes, stride, n, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    // host offsets can be, and are, inspected: the staged prims array holds offsets[n] entries
+    size_t entries = prims ? (size_t)n * (size_t)cap : 0;
+    if (prims && offsets) {
+        if (offsets[0] < 0) return fail(c, RT_ERR_INVALID, "rt_query_boxes_host: offsets[0] = %d", offsets[0]);
+        for (int i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) return fail(c, RT_ERR_INVALID, "rt_query_boxes_host: offsets descend at %d", i);
+        entries = (size_t)offsets[n];
+    }
+    // staging layout: boxes | offsets | prims | counts | visits | one spare word; the box array keeps its stride; prims goes in as well, for the entries no
+    // list reaches.  An empty prims array has no staged address: the spare word stands in for it, and no list reaches that either
+    const size_t N = (size_t)n;
+    const int32_t spare = 0;
+    const StageSeg segs[] = {{boxes, ((N - 1) * stride + 6) * 4, false}, {offsets, prims && offsets ? (N + 1) * 4 : 0, false}, {prims, entries * 4, true, true},
+                             {counts, counts ? N * 4 : 0, true}, {visits, visits ? N * 4 : 0, true}, {&spare, 4, false}};
+    return staged(c, "rt_query_boxes_host", segs, [&](void *const *d) {
+        return rt_query_boxes(c, (const float *)d[0], stride, n, (const int32_t *)d[1], cap, prims ? (int32_t *)(d[2] ? d[2] : d[5]) : nullptr, (int32_t *)d[3],
+                              (int32_t *)d[4]);
     });
 }
 

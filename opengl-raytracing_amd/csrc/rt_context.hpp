@@ -248,7 +248,7 @@ inline int ensure_staging(RtContext *c, size_t bytes) {
 // A segment is one array of the call: `bytes` of it lie at a 16-byte-aligned offset of the buffer, in the order given (bytes == 0: the array is not
 // part of this call and its device address is null).  Inputs are copied in from `host`; outputs are copied out to it, unless it is null -- the
 // device entry still gets the room.
-struct StageSeg { const void *host; size_t bytes; bool out; };
+struct StageSeg { const void *host; size_t bytes; bool out; bool in = false; };   // in: an output the device writes in part -- copied in first, so the rest survives
 
 // sync_all and ensure_staging (the buffer may be replaced: nothing may be in flight), copies in on rt_stream()'s stream, body(device addresses) -- the
 // device entry point --, copies out, one wait.  A refused body leaves nothing in flight either.
@@ -265,7 +265,7 @@ template <size_t K, class F> int staged(RtContext *c, const char *what, const St
         void *dev[K];
         for (size_t k = 0; k < K; ++k) {
             dev[k] = segs[k].bytes ? base + off[k] : nullptr;
-            if (segs[k].bytes && !segs[k].out) HIP_TRY(c, hipMemcpyAsync(dev[k], segs[k].host, segs[k].bytes, hipMemcpyHostToDevice, st));
+            if (segs[k].bytes && (!segs[k].out || segs[k].in)) HIP_TRY(c, hipMemcpyAsync(dev[k], segs[k].host, segs[k].bytes, hipMemcpyHostToDevice, st));
         }
         const int qr = body(dev);
         if (qr != RT_OK) { (void)sync_all(c); return qr; }

@@ -660,6 +660,35 @@ int rt_query_boxes(RtContext *ctx, const float *boxes, int stride, int n, const 
 int rt_query_boxes_host(RtContext *ctx, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts,
                         int32_t *visits);
 
+/* ---------------------------------------------------------------- triangle queries: the mesh triangles a query triangle intersects
+ * The narrow phase after the box query's broad phase: a tool, a collider, a cutting plane, cloth or another pose of the same model tested against the
+ * uploaded BVH or the dynamic mesh after any rebuild, refit or update.
+ *   Query i is qtris[i * stride .. i * stride + 8] = p0.xyz, p1.xyz, p2.xyz (stride >= 9 floats).  A NaN in any of the nine components marks an empty
+ * slot (count 0, nothing listed, visits 0); +-inf and huge coordinates are legal and err towards overlap.  [qlo, qhi] is the componentwise fmin / fmax
+ * of the three points.
+ *   Row t of tris12 is accepted when (a) the box of every node from the root to t's leaf overlaps [qlo, qhi] -- rt_box_overlaps' comparisons, so the
+ * walk, its order and visits are those of the box query for that box -- and (b) none of 20 axes separates the query from the triangle a = v0,
+ * b = fl(v0 + e1), c = fl(v0 + e2): the three box axes by comparisons of [min3, max3](a, b, c) with [qlo, qhi]; then, with f = e1, fl(e2 - e1), e2
+ * and g = fl(p1 - p0), fl(p2 - p1), fl(p2 - p0), the normals n = cross(e1, e2) and m = cross(g1, g3), the nine cross(f_i, g_j), the three cross(n, f_i)
+ * and the three cross(m, g_j).  On such an axis both triangles project to the min / max of dot(axis, point) over their three points (a NaN operand
+ * ignored), and the axis separates only when Tmax < Qmin || Qmax < Tmin is true: a NaN never separates.  The six in-plane axes decide coplanar pairs.
+ * Degenerate triangles (a segment, a point, a zero-area row) lose axes and err towards overlap.  A pair that shares a point in all three floats is
+ * accepted; a query made of a row's own a, b, c lists that row.  DESIGN.md 24.1 has every operation.  For the trees this library builds (b) implies
+ * (a).
+ *   List order, counts, prims, offsets and cap: word for word as rt_box_overlaps above -- right child first, the rows of a leaf ascending (ascending
+ * in prim for the library's trees); the first min(capacity, counts[i]) rows are written, entries past them are NOT written.
+ *   rt_tri_overlaps is the definition: host arrays, no context, no GPU.  rt_query_tris: device pointers, enqueued on rt_stream()'s stream, no host
+ * synchronisation and, after the context's first query, no allocation; one lane walks one query.  visits (may be NULL): 1 + twice the inner nodes
+ * entered, 0 for an empty slot.  RT_ERR_INVALID: n < 0, a stride below 9, null qtris, prims and counts both NULL, prims without offsets and cap < 0 or
+ * n * cap beyond INT32_MAX, misaligned arrays, a triangle array beyond 2^32 floats.  RT_ERR_STATE: no BVH uploaded.  A refused call writes nothing;
+ * n == 0 is a no-op.  Frame state stays untouched.  The _host twin takes host pointers, stages through the context's buffer and synchronises; its
+ * prims array holds offsets[n] entries (offsets must then be ascending from 0), or n * cap. */
+int rt_tri_overlaps(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *qtris, int stride /* >= 9: p0.xyz, p1.xyz, p2.xyz */, int n,
+                    const int32_t *offsets /* n + 1 entries, or NULL */, int cap, int32_t *prims /* may be NULL */, int32_t *counts /* may be NULL, not both */);
+int rt_query_tris(RtContext *ctx, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits);
+int rt_query_tris_host(RtContext *ctx, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts,
+                       int32_t *visits);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

@@ -378,6 +378,9 @@ SIGNATURES = {
     "rt_box_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_query_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_query_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_tri_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_query_tris": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_query_tris_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1706,9 +1709,10 @@ def _numpy_boxes(boxes):
     return boxes.shape[0] if boxes.ndim == 2 else -1, _box_rows(boxes, 4, boxes.strides)
 
 
-def _numpy_box_query(call, boxes, cap, visits):
-    """Both forms on host arrays: call(boxes, stride, n, offsets, cap, prims, counts, visits) -> rc, checked by the caller's wrapper."""
-    n, stride = _numpy_boxes(boxes)
+def _numpy_box_query(call, boxes, cap, visits, rows=_numpy_boxes, result=BoxOverlaps):
+    """Both forms on host arrays: call(boxes, stride, n, offsets, cap, prims, counts, visits) -> rc, checked by the caller's wrapper.  rows: the
+    checks of the query array -> (n, stride); result: the answers' class (the triangle queries pass their own)."""
+    n, stride = rows(boxes)
     p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
     count = np.zeros(n, np.int32)
     vis = np.zeros(n, np.int32) if visits else None
@@ -1719,7 +1723,7 @@ def _numpy_box_query(call, boxes, cap, visits):
         prims = np.full(n * cap, -1, np.int32)
         if n:
             call(p(boxes), stride, n, None, cap, p(prims), p(count), p(vis))
-        return BoxOverlaps(count, offsets, prims, vis)
+        return result(count, offsets, prims, vis)
     offsets = np.zeros(n + 1, np.int32)
     if n:
         call(p(boxes), stride, n, None, 0, None, p(count), p(vis))
@@ -1730,7 +1734,7 @@ def _numpy_box_query(call, boxes, cap, visits):
     prims = np.full(int(offsets[-1]), -1, np.int32)
     if prims.size:
         call(p(boxes), stride, n, p(offsets), 0, p(prims), None, None)
-    return BoxOverlaps(count, offsets, prims, vis)
+    return result(count, offsets, prims, vis)
 
 
 def box_overlaps(nodes12, tris12, boxes, cap=None) -> BoxOverlaps:
@@ -1749,6 +1753,80 @@ def box_overlaps(nodes12, tris12, boxes, cap=None) -> BoxOverlaps:
             raise RtError(rc, "rt_box_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_box_overlaps")
 
     return _numpy_box_query(call, boxes, cap, False)
+
+
+class TriOverlaps(BoxOverlaps):
+    """Answers of tri_overlaps and Renderer.tri_overlaps: `count`, `offsets`, `prims`, `visits` and `.hits()` as BoxOverlaps, per query
+    triangle; `.pairs()` is the list as (query, prim) rows."""
+
+    def pairs(self):
+        """[M,2] int32: one row (query, prim) per written list entry, queries ascending and each query's prims in list order -- the form a collision
+        response wants.  Entries no list reaches (cap form: the -1 entries) are left out."""
+        if isinstance(self.prims, np.ndarray):
+            start = self.offsets[:-1].astype(np.int64)
+            k = np.clip(np.minimum(self.count.astype(np.int64), self.offsets[1:].astype(np.int64) - start), 0, None)
+            query = np.repeat(np.arange(k.size, dtype=np.int64), k)
+            within = np.arange(query.size, dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
+            return np.stack([query.astype(np.int32), self.prims[np.repeat(start, k) + within]], 1) if query.size else np.zeros((0, 2), np.int32)
+        import torch
+        start = self.offsets[:-1].to(torch.int64)
+        k = torch.clamp(torch.minimum(self.count.to(torch.int64), self.offsets[1:].to(torch.int64) - start), min=0)
+        query = torch.repeat_interleave(torch.arange(k.numel(), dtype=torch.int64, device=k.device), k)
+        within = torch.arange(query.numel(), dtype=torch.int64, device=k.device) - torch.repeat_interleave(torch.cumsum(k, 0) - k, k)
+        return torch.stack([query.to(torch.int32), self.prims[torch.repeat_interleave(start, k) + within]], 1)
+
+
+def _tri_rows(shape, itemsize, strides):
+    """The checks of the triangle queries on a [N,k] (k >= 9) or [N,3,3] array -> the row stride in floats."""
+    if len(shape) == 3 and tuple(shape[1:]) == (3, 3):
+        if strides[1] != 3 * itemsize or strides[2] != itemsize:
+            raise _query_invalid("qtris [N,3,3]: the nine floats of a triangle must be contiguous")
+        shape, strides = (shape[0], 9), (strides[0], itemsize)
+    if len(shape) != 2 or shape[1] < 9:
+        raise _query_invalid(f"qtris must be [N,k] with k >= 9 (p0.xyz, p1.xyz, p2.xyz) or [N,3,3], got shape {tuple(shape)}")
+    row, col = strides
+    if col != itemsize or row % itemsize or (shape[0] > 1 and row // itemsize < 9):
+        raise _query_invalid("qtris must have unit stride along its last dimension and rows at least 9 floats apart")
+    return max(row // itemsize, 9) if shape[0] > 1 else max(shape[1], 9)
+
+
+def _numpy_tris(qtris):
+    if not isinstance(qtris, np.ndarray):
+        raise _query_invalid("qtris must be a numpy array")
+    if qtris.dtype != np.float32:
+        raise _query_invalid(f"qtris must be float32, got {qtris.dtype}")
+    stride = _tri_rows(qtris.shape, 4, qtris.strides)
+    return qtris.shape[0], stride
+
+
+def tri_overlaps(nodes12, tris12, qtris, cap=None) -> TriOverlaps:
+    """The definition of the triangle query (rt_tri_overlaps), on the host and without a context: per query triangle (p0, p1, p2) the
+    rows of (nodes12, tris12) that lie under node boxes overlapping the box of its points and that the 20-axis separating-axis test cannot part from
+    it, in walk order, and their count.  qtris: float32 [N,9], [N,3,3] or [N,k], k >= 9, rows may be strided (numpy); a NaN component marks an empty
+    slot.  cap=None: the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per query."""
+    cap = _box_cap(cap)
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+
+    def call(q, stride, n, offsets, cap_, prims, counts, _visits):
+        rc = lib().rt_tri_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], q, stride, n, offsets, cap_, prims, counts)
+        if rc != RT_OK:
+            raise RtError(rc, "rt_tri_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_tri_overlaps")
+
+    return _numpy_box_query(call, qtris, cap, False, rows=_numpy_tris, result=TriOverlaps)
+
+
+def rows_as_tris(tris12):
+    """The points of each row of tris12 as query triangles [N,9] float32: a = v0, b = v0 + e1, c = v0 + e2 by the definition's float32 adds (DESIGN.md
+    24.1) -- the very floats the triangle test forms, so a query made of them shares its points with the row bit for bit.  numpy or torch."""
+    if isinstance(tris12, np.ndarray):
+        t = _f32(tris12).reshape(-1, 12)
+        with np.errstate(all="ignore"):
+            return np.concatenate([t[:, 0:3], t[:, 0:3] + t[:, 4:7], t[:, 0:3] + t[:, 8:11]], 1)
+    import torch
+    t = tris12.reshape(-1, 12)
+    return torch.cat([t[:, 0:3], t[:, 0:3] + t[:, 4:7], t[:, 0:3] + t[:, 8:11]], 1)
 
 
 # ------------------------------------------------------------------------------------ device side
@@ -2743,6 +2821,12 @@ class Renderer:
             raise _query_invalid("boxes must be a numpy array or a torch tensor")
         dev = self._query_device(boxes, dtype=torch.float32)
         stride = _box_rows(boxes, 1, boxes.stride() if boxes.dim() == 2 else (0, 0))
+        return self._device_overlaps(lib().rt_query_boxes, BoxOverlaps, boxes, stride, dev, cap, visits)
+
+    def _device_overlaps(self, entry, result, boxes, stride, dev, cap, visits):
+        """Both forms of a box or triangle query on a torch device tensor of queries (`boxes`, rows `stride` floats apart), through the C entry
+        `entry` -> result(count, offsets, prims, visits)."""
+        import torch
         n = boxes.shape[0]
         if cap is not None and n * cap > 2 ** 31 - 1:
             raise _query_invalid(f"{n} boxes x cap {cap} exceed INT32_MAX entries")
@@ -2754,7 +2838,7 @@ class Renderer:
 
         def query(offsets, cap_, prims, counts, vis_):
             ext.wait_stream(cur)             # the boxes (and the outputs' allocation and fill) are ready before the query starts
-            self._check(lib().rt_query_boxes(self._h, p(boxes), stride, n, p(offsets), cap_, p(prims), p(counts), p(vis_)))
+            self._check(entry(self._h, p(boxes), stride, n, p(offsets), cap_, p(prims), p(counts), p(vis_)))
             cur.wait_stream(ext)             # torch's work after this call sees the answers
 
         if cap is not None:
@@ -2776,7 +2860,24 @@ class Renderer:
             if total:
                 query(offsets, 0, prims, None, None)
         boxes.record_stream(cur)             # (never tied to the library stream: it dies with the context)
-        return BoxOverlaps(count, offsets, prims, vis)
+        return result(count, offsets, prims, vis)
+
+    def tri_overlaps(self, qtris, cap=None, visits=False) -> TriOverlaps:
+        """The rows of the uploaded BVH or the dynamic mesh that each query triangle intersects (rt_query_tris) -> TriOverlaps, equal to
+        tri_overlaps on the same arrays bit for bit.  qtris: float32 [N,9], [N,3,3] or [N,k], k >= 9 (p0.xyz, p1.xyz, p2.xyz), rows may be strided; a
+        NaN component marks an empty slot.  cap, visits, the numpy / torch paths, stream ordering and lifetimes as box_overlaps; visits equals
+        box_overlaps' for the boxes of the queries' points.  A self query lists every neighbour that shares a vertex: filter `.pairs()` by the index
+        buffer.  One lane walks one query."""
+        cap = _box_cap(cap)
+        if isinstance(qtris, np.ndarray):
+            call = lambda *a: self._check(lib().rt_query_tris_host(self._h, *a))
+            return _numpy_box_query(call, qtris, cap, visits, rows=_numpy_tris, result=TriOverlaps)
+        import torch
+        if not isinstance(qtris, torch.Tensor):
+            raise _query_invalid("qtris must be a numpy array or a torch tensor")
+        dev = self._query_device(qtris, dtype=torch.float32)
+        stride = _tri_rows(tuple(qtris.shape), 1, qtris.stride())
+        return self._device_overlaps(lib().rt_query_tris, TriOverlaps, qtris, stride, dev, cap, visits)
 
     def _query_device(self, *arrays, dtype):
         import torch

@@ -1,6 +1,6 @@
-// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21, 22 and 23): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
-// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes and their _host twins.  Host code only: rt_wave.hip,
-// rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip and rt_box_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21, 22, 23 and 24): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
+// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes, rt_query_tris and their _host twins.  Host code only: rt_wave.hip,
+// rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip, rt_box_query.hip and rt_tri_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "rt_multi_hit.hpp"
 #include "rt_nearest.hpp"
 #include "rt_nearest_multi.hpp"
+#include "rt_tri_query.hpp"
 
 using namespace rtd;
 using namespace rtapi;
@@ -191,19 +192,50 @@ int nearest_multi_args(RtContext *c, const char *what, const float *points, int 
     return nearest_args(c, what, points, stride, n, hits, maxHits > 0);
 }
 
-// ---- box queries: the rows overlapping an axis-aligned box per box, by a traversal of their own (rt_box_query.hip).  Share the queries'
-// scratch and event; touch no frame state.
-// What both entries check, before anything is enqueued or written.  offsets is the caller's to get right: device memory for rt_query_boxes
-int box_args(RtContext *c, const char *what, const float *boxes, int stride, int n, const int32_t *offsets, int cap, const int32_t *prims, const int32_t *counts) {
+// ---- box queries and triangle queries: the rows overlapping an axis-aligned box, or intersected by a query triangle, per
+// query, each by a traversal of its own (rt_box_query.hip, rt_tri_query.hip).  Share the queries' scratch and event; touch no frame state.
+// What tells the two apart in the checks and in the staging: the floats of one query, and the words of the messages
+struct OverlapKind { int floats; const char *layout, *noun; };
+constexpr OverlapKind kBoxes = {6, "lo.xyz, hi.xyz", "box"}, kTris = {9, "p0.xyz, p1.xyz, p2.xyz", "triangle"};
+
+// What all four entries check, before anything is enqueued or written.  offsets is the caller's to get right: device memory for the device entries
+int overlap_args(RtContext *c, const char *what, const OverlapKind &k, const float *queries, int stride, int n, const int32_t *offsets, int cap, const int32_t *prims,
+                 const int32_t *counts) {
     if (n < 0) return fail(c, RT_ERR_INVALID, "%s: n = %d", what, n);
-    if (stride < 6) return fail(c, RT_ERR_INVALID, "%s: stride %d floats (at least 6: lo.xyz, hi.xyz)", what, stride);
-    if (n > 0 && !boxes) return fail(c, RT_ERR_INVALID, "%s: null box array", what);
+    if (stride < k.floats) return fail(c, RT_ERR_INVALID, "%s: stride %d floats (at least %d: %s)", what, stride, k.floats, k.layout);
+    if (n > 0 && !queries) return fail(c, RT_ERR_INVALID, "%s: null %s array", what, k.noun);
     if (n > 0 && !prims && !counts) return fail(c, RT_ERR_INVALID, "%s: the query needs prims or counts", what);
     if (prims && !offsets && cap < 0) return fail(c, RT_ERR_INVALID, "%s: cap = %d without offsets", what, cap);
     if (prims && !offsets && (uint64_t)n * (uint64_t)cap > (uint64_t)INT32_MAX) return fail(c, RT_ERR_INVALID, "%s: n * cap exceeds INT32_MAX entries", what);
-    if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + 6 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the box array exceeds 2^32 floats", what);
+    if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + (size_t)k.floats > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the %s array exceeds 2^32 floats", what, k.noun);
     if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
     return RT_OK;
+}
+
+// The _host twin of `entry` (rt_query_boxes or rt_query_tris): host pointers staged through the context's buffer
+using OverlapEntry = int (*)(RtContext *, const float *, int, int, const int32_t *, int, int32_t *, int32_t *, int32_t *);
+int overlap_host(RtContext *c, const char *what, const OverlapKind &k, OverlapEntry entry, const float *queries, int stride, int n, const int32_t *offsets, int cap,
+                 int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = overlap_args(c, what, k, queries, stride, n, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    // host offsets can be, and are, inspected: the staged prims array holds offsets[n] entries
+    size_t entries = prims ? (size_t)n * (size_t)cap : 0;
+    if (prims && offsets) {
+        if (offsets[0] < 0) return fail(c, RT_ERR_INVALID, "%s: offsets[0] = %d", what, offsets[0]);
+        for (int i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) return fail(c, RT_ERR_INVALID, "%s: offsets descend at %d", what, i);
+        entries = (size_t)offsets[n];
+    }
+    // staging layout: queries | offsets | prims | counts | visits | one spare word; the query array keeps its stride; prims goes in as well, for the entries
+    // no list reaches.  An empty prims array has no staged address: the spare word stands in for it, and no list reaches that either
+    const size_t N = (size_t)n;
+    const int32_t spare = 0;
+    const StageSeg segs[] = {{queries, ((N - 1) * stride + k.floats) * 4, false}, {offsets, prims && offsets ? (N + 1) * 4 : 0, false}, {prims, entries * 4, true, true},
+                             {counts, counts ? N * 4 : 0, true}, {visits, visits ? N * 4 : 0, true}, {&spare, 4, false}};
+    return staged(c, what, segs, [&](void *const *d) {
+        return entry(c, (const float *)d[0], stride, n, (const int32_t *)d[1], cap, prims ? (int32_t *)(d[2] ? d[2] : d[5]) : nullptr, (int32_t *)d[3], (int32_t *)d[4]);
+    });
 }
 
 }  // namespace
@@ -392,7 +424,7 @@ int rt_query_nearest_multi_host(RtContext *c, const float *points, int stride, c
 // ---- box queries
 int rt_query_boxes(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
     if (!c) return RT_ERR_INVALID;
-    const int rc = box_args(c, "rt_query_boxes", boxes, stride, n, offsets, cap, prims, counts);
+    const int rc = overlap_args(c, "rt_query_boxes", kBoxes, boxes, stride, n, offsets, cap, prims, counts);
     if (rc != RT_OK || n == 0) return rc;
     if (((uintptr_t)boxes | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
         return fail(c, RT_ERR_INVALID, "rt_query_boxes: float and int32 arrays must be 4-byte aligned");
@@ -406,27 +438,27 @@ int rt_query_boxes(RtContext *c, const float *boxes, int stride, int n, const in
 }
 
 int rt_query_boxes_host(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    return overlap_host(c, "rt_query_boxes_host", kBoxes, rt_query_boxes, boxes, stride, n, offsets, cap, prims, counts, visits);
+}
+
+// ---- triangle queries
+int rt_query_tris(RtContext *c, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
     if (!c) return RT_ERR_INVALID;
-    const int rc = box_args(c, "rt_query_boxes_host", boxes, stride, n, offsets, cap, prims, counts);
+    const int rc = overlap_args(c, "rt_query_tris", kTris, qtris, stride, n, offsets, cap, prims, counts);
     if (rc != RT_OK || n == 0) return rc;
-    // host offsets can be, and are, inspected: the staged prims array holds offsets[n] entries
-    size_t entries = prims ? (size_t)n * (size_t)cap : 0;
-    if (prims && offsets) {
-        if (offsets[0] < 0) return fail(c, RT_ERR_INVALID, "rt_query_boxes_host: offsets[0] = %d", offsets[0]);
-        for (int i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) return fail(c, RT_ERR_INVALID, "rt_query_boxes_host: offsets descend at %d", i);
-        entries = (size_t)offsets[n];
-    }
-    // staging layout: boxes | offsets | prims | counts | visits | one spare word; the box array keeps its stride; prims goes in as well, for the entries no
-    // list reaches.  An empty prims array has no staged address: the spare word stands in for it, and no list reaches that either
-    const size_t N = (size_t)n;
-    const int32_t spare = 0;
-    const StageSeg segs[] = {{boxes, ((N - 1) * stride + 6) * 4, false}, {offsets, prims && offsets ? (N + 1) * 4 : 0, false}, {prims, entries * 4, true, true},
-                             {counts, counts ? N * 4 : 0, true}, {visits, visits ? N * 4 : 0, true}, {&spare, 4, false}};
-    return staged(c, "rt_query_boxes_host", segs, [&](void *const *d) {
-        return rt_query_boxes(c, (const float *)d[0], stride, n, (const int32_t *)d[1], cap, prims ? (int32_t *)(d[2] ? d[2] : d[5]) : nullptr, (int32_t *)d[3],
-                              (int32_t *)d[4]);
-    });
+    if (((uintptr_t)qtris | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
+        return fail(c, RT_ERR_INVALID, "rt_query_tris: float and int32 arrays must be 4-byte aligned");
+    TriQuery q = {};
+    q.t = qtris; q.ts = stride; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    HIP_TRY(c, rt_tri_query_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
+    return query_end(c, st);
+}
+
+int rt_query_tris_host(RtContext *c, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    return overlap_host(c, "rt_query_tris_host", kTris, rt_query_tris, qtris, stride, n, offsets, cap, prims, counts, visits);
 }
 
 }  // extern "C"

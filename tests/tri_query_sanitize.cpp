@@ -1,0 +1,227 @@
+// The triangle query's definition (csrc/rt_tri_query.cpp: rt_tri_overlaps) driven over its edge cases under AddressSanitizer + UBSan on the CPU
+// (tests/test_tri_query_host_sanitizers.py).  Linked with rt_tri_query.cpp alone.  Every array is exactly as long as the call may read or write: a
+// strided query array ends with its last triangle's ninth float, offsets hold n + 1 entries, prims offsets[n] or n * cap entries (none at all for
+// cap = 0), counts n.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "rt_mi355.h"
+
+static int g_fail = 0;
+#define CHECK(x) do { if (!(x)) { std::printf("FAILED line %d: %s\n", __LINE__, #x); ++g_fail; } } while (0)
+
+struct Tree { std::vector<float> nodes, tris; int nNodes = 0, nTris = 0; };
+
+// rows of tris12 from tris9 (v0, e1, e2), and a median split by index over them with leaves of at most 8: any tree over the rows serves here
+static void grow(Tree &T, int first, int count) {
+    const int me = T.nNodes++;
+    T.nodes.resize((size_t)T.nNodes * 12, 0.0f);
+    float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
+    for (int i = first; i < first + count; ++i) {
+        const float *t = &T.tris[(size_t)i * 12];
+        for (int a = 0; a < 3; ++a)
+            for (float v : {t[a], t[a] + t[4 + a], t[a] + t[8 + a]}) { lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
+    }
+    for (int a = 0; a < 3; ++a) { T.nodes[(size_t)me * 12 + a] = lo[a]; T.nodes[(size_t)me * 12 + 4 + a] = hi[a]; }
+    if (count <= 8) { T.nodes[(size_t)me * 12 + 8] = (float)first; T.nodes[(size_t)me * 12 + 9] = (float)count; return; }
+    const int half = count / 2;
+    const int l = T.nNodes;
+    grow(T, first, half);
+    const int r = T.nNodes;
+    grow(T, first + half, count - half);
+    T.nodes[(size_t)me * 12 + 3] = (float)l; T.nodes[(size_t)me * 12 + 7] = (float)r;
+}
+static Tree tree_of(const std::vector<float> &tris9) {
+    Tree T;
+    T.nTris = (int)tris9.size() / 9;
+    T.tris.assign((size_t)T.nTris * 12, 0.0f);
+    for (int i = 0; i < T.nTris; ++i)
+        for (int k = 0; k < 3; ++k) std::memcpy(&T.tris[(size_t)i * 12 + 4 * k], &tris9[(size_t)i * 9 + 3 * k], 12);
+    grow(T, 0, T.nTris);
+    return T;
+}
+
+// n query triangles with the given stride in an array that ends with the last triangle's ninth float; every seventh an empty slot (a NaN that
+// rotates through the nine components)
+struct Queries { std::vector<float> q; int n, stride; };
+static Queries queries_about(int n, int stride, unsigned seed) {
+    Queries Q;
+    Q.n = n; Q.stride = stride;
+    Q.q.assign((size_t)(n - 1) * stride + 9, 0.0f);
+    std::mt19937 r(seed);
+    for (int i = 0; i < n; ++i) {
+        float *q = &Q.q[(size_t)i * stride];
+        float c[3];
+        for (int a = 0; a < 3; ++a) c[a] = (float)((int)(r() % 640u) - 320) / 8.0f * (a == 1 ? 0.05f : 1.0f);
+        const float h = (float)(r() % 200u) / 8.0f;
+        for (int p = 0; p < 3; ++p)
+            for (int a = 0; a < 3; ++a) q[3 * p + a] = c[a] + h * ((float)(r() % 65u) / 32.0f - 1.0f);
+        if (i % 7 == 3) q[(i / 7) % 9] = std::numeric_limits<float>::quiet_NaN();
+    }
+    return Q;
+}
+
+// What one call leaves of a slot: the count within [0, nTris]; the first min(room, count) entries distinct rows of the tree; the rest untouched
+static void check_slot(const Tree &T, const int32_t *slot, int64_t room, int32_t count, int32_t mark) {
+    CHECK(count >= 0 && count <= T.nTris);
+    const int64_t kept = std::min<int64_t>(std::max<int64_t>(room, 0), count);
+    for (int64_t j = 0; j < kept; ++j) {
+        CHECK(slot[j] >= 0 && slot[j] < T.nTris);
+        for (int64_t k = 0; k < j; ++k) CHECK(slot[k] != slot[j]);
+    }
+    for (int64_t j = kept; j < room; ++j) CHECK(slot[j] == mark);
+}
+
+int main() {
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    const int32_t mark = -77;
+    // ---- one leaf: two triangles, no inner node
+    Tree one = tree_of({-0.75f, 0.25f, -0.75f, 2, 0, 0, 1, 1.5f, -0.2f, -0.75f, 0.25f, 1.25f, 2, 0, 0, 1, 1.5f, -0.5f});
+    CHECK(one.nNodes == 1 && one.nTris == 2);
+    // ---- the layer stack: six layers of three coincident copies of a quad, 36 triangles
+    std::vector<float> t9;
+    for (int k = 0; k < 6; ++k)
+        for (int c = 0; c < 3; ++c) {
+            const float y = (float)(0.25 * k + 0.1);
+            const float edges[2][6] = {{60, 0, 0, 60, 0, 60}, {60, 0, 60, 0, 0, 60}};
+            for (const auto &e : edges) {
+                t9.insert(t9.end(), {-30.0f, y, -30.0f});
+                t9.insert(t9.end(), e, e + 6);
+            }
+        }
+    Tree stack = tree_of(t9);
+    CHECK(stack.nTris == 36 && stack.nNodes > 1);
+    for (const Tree *T : {&one, &stack})
+        for (int stride : {9, 10, 12})
+            for (int n : {1, 2, 65}) {
+                Queries Q = queries_about(n, stride, 7u + (unsigned)(stride + n));
+                std::vector<int32_t> counts((size_t)n, mark);
+                // the counts alone
+                CHECK(rt_tri_overlaps(T->nodes.data(), T->nNodes, T->tris.data(), T->nTris, Q.q.data(), stride, n, nullptr, 0, nullptr, counts.data()) == RT_OK);
+                for (int i = 0; i < n; ++i) {
+                    CHECK(counts[(size_t)i] >= 0 && counts[(size_t)i] <= T->nTris);
+                    if (i % 7 == 3) CHECK(counts[(size_t)i] == 0);
+                }
+                // the exact list: count, scan, list -- with and without the counts again
+                std::vector<int32_t> offsets((size_t)n + 1, 0);
+                for (int i = 0; i < n; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + counts[(size_t)i];
+                for (int withCounts = 0; withCounts < 2; ++withCounts) {
+                    std::vector<int32_t> prims((size_t)offsets[(size_t)n], mark), again((size_t)n, mark);
+                    // (a vector without elements may hand out any pointer: an empty list array is passed as one spare word no slot reaches)
+                    int32_t spare = mark;
+                    CHECK(rt_tri_overlaps(T->nodes.data(), T->nNodes, T->tris.data(), T->nTris, Q.q.data(), stride, n, offsets.data(), 0,
+                                          prims.empty() ? &spare : prims.data(), withCounts ? again.data() : nullptr) == RT_OK);
+                    CHECK(spare == mark);
+                    for (int i = 0; i < n; ++i) {
+                        check_slot(*T, prims.data() + offsets[(size_t)i], counts[(size_t)i], counts[(size_t)i], mark);
+                        if (withCounts) CHECK(again[(size_t)i] == counts[(size_t)i]);
+                    }
+                }
+                // fixed capacities
+                for (int cap : {0, 1, 3, 8}) {
+                    std::vector<int32_t> prims((size_t)n * cap, mark), again((size_t)n, mark);
+                    int32_t spare = mark;
+                    CHECK(rt_tri_overlaps(T->nodes.data(), T->nNodes, T->tris.data(), T->nTris, Q.q.data(), stride, n, nullptr, cap, cap ? prims.data() : &spare,
+                                          again.data()) == RT_OK);
+                    CHECK(spare == mark);
+                    for (int i = 0; i < n; ++i) {
+                        CHECK(again[(size_t)i] == counts[(size_t)i]);
+                        check_slot(*T, prims.data() + (size_t)i * cap, cap, counts[(size_t)i], mark);
+                    }
+                }
+            }
+    // ---- degenerate queries: NaN and infinite components, denormals, huge values, segments and points; zero-area rows among the rows
+    {
+        Tree flat = tree_of({0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1});
+        const float sp[] = {nan, inf, -inf, 0.0f, -0.0f, 1e-41f, 3.0f, 3e38f, -3e38f};
+        std::vector<float> b;
+        for (float a : sp) for (float c : sp) for (float d : sp) for (float e : sp) b.insert(b.end(), {a, c, -1.0f, d, e, d, e, 0.25f, a});
+        for (float a : sp) for (float c : sp) b.insert(b.end(), {a, c, a, a, c, a, a, c, a});           // points
+        for (float a : sp) for (float c : sp) b.insert(b.end(), {a, 0.25f, c, c, 0.5f, a, c, 0.5f, a});    // segments
+        const int n = (int)b.size() / 9, cap = 3;
+        std::vector<int32_t> prims((size_t)n * cap), counts((size_t)n);
+        for (const Tree *T : {&one, &stack, &flat}) {
+            std::fill(prims.begin(), prims.end(), mark);
+            std::fill(counts.begin(), counts.end(), mark);
+            CHECK(rt_tri_overlaps(T->nodes.data(), T->nNodes, T->tris.data(), T->nTris, b.data(), 9, n, nullptr, cap, prims.data(), counts.data()) == RT_OK);
+            for (int i = 0; i < n; ++i) {
+                const float *q = &b[(size_t)i * 9];
+                bool live = true;
+                for (int k = 0; k < 9; ++k) live = live && q[k] == q[k];
+                if (!live) CHECK(counts[(size_t)i] == 0);
+                check_slot(*T, prims.data() + (size_t)i * cap, cap, counts[(size_t)i], mark);
+            }
+        }
+        // a query made of a row's own points lists that row, a zero-area row and a point row included
+        for (int t = 0; t < flat.nTris; ++t) {
+            const float *r = &flat.tris[(size_t)t * 12];
+            const float own[9] = {r[0], r[1], r[2], r[0] + r[4], r[1] + r[5], r[2] + r[6], r[0] + r[8], r[1] + r[9], r[2] + r[10]};
+            int32_t list[3] = {mark, mark, mark}, count = mark;
+            CHECK(rt_tri_overlaps(flat.nodes.data(), flat.nNodes, flat.tris.data(), flat.nTris, own, 9, 1, nullptr, 3, list, &count) == RT_OK);
+            CHECK(count >= 1 && std::find(list, list + std::min(count, 3), t) != list + std::min(count, 3));
+        }
+        // a triangle in the plane x = 0 that cuts every layer lists everything, in walk order: the split by index and the right child first give
+        // descending leaves
+        const float all[9] = {0, -100, -100, 0, 100, -100, 0, 0, 100};
+        std::vector<int32_t> list((size_t)stack.nTris, mark);
+        int32_t count = mark;
+        CHECK(rt_tri_overlaps(stack.nodes.data(), stack.nNodes, stack.tris.data(), stack.nTris, all, 9, 1, nullptr, stack.nTris, list.data(), &count) == RT_OK);
+        CHECK(count == stack.nTris);
+        std::vector<int32_t> sorted = list;
+        std::sort(sorted.begin(), sorted.end());
+        for (int i = 0; i < stack.nTris; ++i) CHECK(sorted[(size_t)i] == i);
+        CHECK(list[0] > list[(size_t)stack.nTris - 1]);
+    }
+    // ---- slots of negative length or with a negative start hold nothing
+    {
+        Queries Q = queries_about(5, 9, 3u);
+        const int32_t odd[6] = {3, 1, 1, -5, 2, 2};
+        int32_t prims[4] = {mark, mark, mark, mark}, counts[5];
+        CHECK(rt_tri_overlaps(stack.nodes.data(), stack.nNodes, stack.tris.data(), stack.nTris, Q.q.data(), 9, 5, odd, 0, prims, counts) == RT_OK);
+        CHECK(prims[0] == mark && prims[1] == mark && prims[2] == mark && prims[3] == mark);
+    }
+    // ---- refusals: nothing is read or written
+    {
+        Queries Q = queries_about(2, 9, 1u);
+        int32_t prims[8], cnt[2] = {mark, mark};
+        const int32_t off[3] = {0, 4, 8};
+        std::fill(prims, prims + 8, mark);
+        auto call = [&](const Tree &T, int n, int stride, const float *b, const int32_t *o, int cap, int32_t *p, int32_t *c) {
+            return rt_tri_overlaps(T.nodes.data(), T.nNodes, T.tris.data(), T.nTris, b, stride, n, o, cap, p, c);
+        };
+        CHECK(call(stack, -1, 9, Q.q.data(), off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(call(stack, 2, 8, Q.q.data(), off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(call(stack, 2, 9, nullptr, off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(call(stack, 2, 9, Q.q.data(), off, 0, nullptr, nullptr) == RT_ERR_INVALID);          // prims and counts both NULL
+        CHECK(call(stack, 2, 9, Q.q.data(), nullptr, -1, prims, cnt) == RT_ERR_INVALID);            // prims without offsets, cap < 0
+        CHECK(call(stack, INT_MAX / 4 + 1, 9, Q.q.data(), nullptr, 4, prims, cnt) == RT_ERR_INVALID);   // n * cap beyond INT32_MAX
+        CHECK(call(stack, 0, 9, nullptr, nullptr, 0, nullptr, nullptr) == RT_OK);                   // n == 0: a no-op
+        CHECK(rt_tri_overlaps(nullptr, stack.nNodes, stack.tris.data(), stack.nTris, Q.q.data(), 9, 2, off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(rt_tri_overlaps(stack.nodes.data(), stack.nNodes, nullptr, stack.nTris, Q.q.data(), 9, 2, off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(rt_tri_overlaps(stack.nodes.data(), -1, stack.tris.data(), stack.nTris, Q.q.data(), 9, 2, off, 0, prims, cnt) == RT_ERR_INVALID);
+        // nodes that are no tree over the rows: a child off the array, a cycle, a range beyond the rows, huge and NaN links
+        for (float link : {-1.0f, 1e9f, nan, (float)stack.nNodes, 0.0f}) {
+            Tree bad = stack;
+            bad.nodes[3] = link;
+            CHECK(call(bad, 2, 9, Q.q.data(), off, 0, prims, cnt) == RT_ERR_INVALID);
+        }
+        Tree bad = one;
+        bad.nodes[9] = 3.0f;
+        CHECK(call(bad, 2, 9, Q.q.data(), off, 0, prims, cnt) == RT_ERR_INVALID);
+        bad.nodes[8] = 2e9f; bad.nodes[9] = 1.0f;
+        CHECK(call(bad, 2, 9, Q.q.data(), off, 0, prims, cnt) == RT_ERR_INVALID);
+        CHECK(cnt[0] == mark && cnt[1] == mark && std::all_of(prims, prims + 8, [&](int32_t v) { return v == mark; }));
+        // an empty scene intersects nothing
+        CHECK(rt_tri_overlaps(nullptr, 0, nullptr, 0, Q.q.data(), 9, 2, off, 0, prims, cnt) == RT_OK && cnt[0] == 0 && cnt[1] == 0 && prims[0] == mark);
+    }
+    if (g_fail) { std::printf("tri query host: %d checks FAILED\n", g_fail); return 1; }
+    std::printf("tri query host: all checks passed\n");
+    return 0;
+}

@@ -1,17 +1,16 @@
 // rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
 // rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes, rt_query_tris and their _host twins.  Host code only: rt_wave.hip,
-// rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip, rt_box_query.hip and rt_tri_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
+// rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip and rt_overlap_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 
-#include "rt_box_query.hpp"
 #include "rt_context.hpp"
 #include "rt_multi_hit.hpp"
 #include "rt_nearest.hpp"
 #include "rt_nearest_multi.hpp"
-#include "rt_tri_query.hpp"
+#include "rt_overlap_query.hpp"
 
 using namespace rtd;
 using namespace rtapi;
@@ -62,6 +61,17 @@ int query_end(RtContext *c, hipStream_t st) {
     c->queryStream = st;
     return RT_OK;
 }
+// One query by a traversal of its own: `call` enqueues it on `st` between query_begin and query_end and returns its hipError_t
+template <class Launch>
+int query_run(RtContext *c, const char *expr, Launch launch) {
+    hipStream_t st = nullptr;
+    const int br = query_begin(c, st);
+    if (br != RT_OK) return br;
+    const hipError_t e = launch(st);
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "%s failed: %s", expr, hipGetErrorString(e));   // (HIP_TRY's words)
+    return query_end(c, st);
+}
+#define QUERY_RUN(c, call) query_run(c, #call, [&](hipStream_t st) { return call; })
 
 // ---- scene queries and pixel picking: the analytic leg (rt_scene_query.hip) into the caller's outputs, then the mesh leg through the frames'
 // persistent traversal launch (SceneSrc).  Shares rt_trace_rays' scratch; touches no frame state.
@@ -161,11 +171,7 @@ int multi_pick_args(RtContext *c, const char *what, const RtUniforms *u, const i
     return RT_OK;
 }
 int multi_launch(RtContext *c, bool mesh, const MultiHitQuery &q) {
-    hipStream_t st = nullptr;
-    const int br = query_begin(c, st);
-    if (br != RT_OK) return br;
-    HIP_TRY(c, rt_multi_hit_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), mesh, q));
-    return query_end(c, st);
+    return QUERY_RUN(c, rt_multi_hit_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), mesh, q));
 }
 
 // ---- nearest-point queries: the closest surface point per point, by a traversal of their own (rt_nearest.hip).  Share the queries' scratch
@@ -193,10 +199,10 @@ int nearest_multi_args(RtContext *c, const char *what, const float *points, int 
 }
 
 // ---- box queries and triangle queries: the rows overlapping an axis-aligned box, or intersected by a query triangle, per
-// query, each by a traversal of its own (rt_box_query.hip, rt_tri_query.hip).  Share the queries' scratch and event; touch no frame state.
-// What tells the two apart in the checks and in the staging: the floats of one query, and the words of the messages
-struct OverlapKind { int floats; const char *layout, *noun; };
-constexpr OverlapKind kBoxes = {6, "lo.xyz, hi.xyz", "box"}, kTris = {9, "p0.xyz, p1.xyz, p2.xyz", "triangle"};
+// query, by one traversal over two shapes (rt_overlap_query.hip).  Share the queries' scratch and event; touch no frame state.
+// What tells the two apart in the checks, in the staging and in the launch: the floats of one query, the words of the messages, and the shape
+struct OverlapKind { int floats; const char *layout, *noun; OverlapShape shape; };
+constexpr OverlapKind kBoxes = {6, "lo.xyz, hi.xyz", "box", RT_OVERLAP_BOX}, kTris = {9, "p0.xyz, p1.xyz, p2.xyz", "triangle", RT_OVERLAP_TRI};
 
 // What all four entries check, before anything is enqueued or written.  offsets is the caller's to get right: device memory for the device entries
 int overlap_args(RtContext *c, const char *what, const OverlapKind &k, const float *queries, int stride, int n, const int32_t *offsets, int cap, const int32_t *prims,
@@ -210,6 +216,19 @@ int overlap_args(RtContext *c, const char *what, const OverlapKind &k, const flo
     if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + (size_t)k.floats > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the %s array exceeds 2^32 floats", what, k.noun);
     if (c->nNodes <= 0 || c->nTris <= 0) return fail(c, RT_ERR_STATE, "%s: no BVH uploaded", what);
     return RT_OK;
+}
+
+// The device entry (rt_query_boxes or rt_query_tris)
+int overlap_query(RtContext *c, const char *what, const OverlapKind &k, const float *queries, int stride, int n, const int32_t *offsets, int cap, int32_t *prims,
+                  int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = overlap_args(c, what, k, queries, stride, n, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)queries | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
+        return fail(c, RT_ERR_INVALID, "%s: float and int32 arrays must be 4-byte aligned", what);
+    OverlapQuery q = {};
+    q.q = queries; q.qs = stride; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
+    return QUERY_RUN(c, rt_overlap_launch(k.shape, st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
 }
 
 // The _host twin of `entry` (rt_query_boxes or rt_query_tris): host pointers staged through the context's buffer
@@ -367,11 +386,7 @@ int rt_query_nearest(RtContext *c, const float *points, int stride, const float 
     NearestQuery q = {};
     q.p = points; q.ps = stride; q.md = maxDist; q.n = (uint32_t)n; q.hits = reinterpret_cast<float4 *>(hits); q.closest = closest; q.visits = visits;
     const char *e = getenv("RT_NEAREST_FAR_FIRST");   // (tests) the farther child first: the same answer by another visit order
-    hipStream_t st = nullptr;
-    const int br = query_begin(c, st);
-    if (br != RT_OK) return br;
-    HIP_TRY(c, rt_nearest_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), e && atoi(e) != 0, q));
-    return query_end(c, st);
+    return QUERY_RUN(c, rt_nearest_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), e && atoi(e) != 0, q));
 }
 
 int rt_query_nearest_host(RtContext *c, const float *points, int stride, const float *maxDist, int n, RtHit *hits, float *closest, int32_t *visits) {
@@ -400,11 +415,7 @@ int rt_query_nearest_multi(RtContext *c, const float *points, int stride, const 
     q.p = points; q.ps = stride; q.md = maxDist; q.n = (uint32_t)n; q.K = maxHits; q.hits = maxHits ? reinterpret_cast<float4 *>(hits) : nullptr; q.counts = counts;
     q.closest = maxHits ? closest : nullptr; q.visits = visits;
     const char *e = getenv("RT_NEAREST_FAR_FIRST");   // (tests) the farther child first: the same answer by another visit order
-    hipStream_t st = nullptr;
-    const int br = query_begin(c, st);
-    if (br != RT_OK) return br;
-    HIP_TRY(c, rt_nearest_multi_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), e && atoi(e) != 0, q));
-    return query_end(c, st);
+    return QUERY_RUN(c, rt_nearest_multi_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), e && atoi(e) != 0, q));
 }
 
 int rt_query_nearest_multi_host(RtContext *c, const float *points, int stride, const float *maxDist, int n, int maxHits, RtHit *hits, int32_t *counts,
@@ -423,18 +434,7 @@ int rt_query_nearest_multi_host(RtContext *c, const float *points, int stride, c
 
 // ---- box queries
 int rt_query_boxes(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
-    if (!c) return RT_ERR_INVALID;
-    const int rc = overlap_args(c, "rt_query_boxes", kBoxes, boxes, stride, n, offsets, cap, prims, counts);
-    if (rc != RT_OK || n == 0) return rc;
-    if (((uintptr_t)boxes | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
-        return fail(c, RT_ERR_INVALID, "rt_query_boxes: float and int32 arrays must be 4-byte aligned");
-    BoxQuery q = {};
-    q.b = boxes; q.bs = stride; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
-    hipStream_t st = nullptr;
-    const int br = query_begin(c, st);
-    if (br != RT_OK) return br;
-    HIP_TRY(c, rt_box_query_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
-    return query_end(c, st);
+    return overlap_query(c, "rt_query_boxes", kBoxes, boxes, stride, n, offsets, cap, prims, counts, visits);
 }
 
 int rt_query_boxes_host(RtContext *c, const float *boxes, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
@@ -443,18 +443,7 @@ int rt_query_boxes_host(RtContext *c, const float *boxes, int stride, int n, con
 
 // ---- triangle queries
 int rt_query_tris(RtContext *c, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
-    if (!c) return RT_ERR_INVALID;
-    const int rc = overlap_args(c, "rt_query_tris", kTris, qtris, stride, n, offsets, cap, prims, counts);
-    if (rc != RT_OK || n == 0) return rc;
-    if (((uintptr_t)qtris | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
-        return fail(c, RT_ERR_INVALID, "rt_query_tris: float and int32 arrays must be 4-byte aligned");
-    TriQuery q = {};
-    q.t = qtris; q.ts = stride; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
-    hipStream_t st = nullptr;
-    const int br = query_begin(c, st);
-    if (br != RT_OK) return br;
-    HIP_TRY(c, rt_tri_query_launch(st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
-    return query_end(c, st);
+    return overlap_query(c, "rt_query_tris", kTris, qtris, stride, n, offsets, cap, prims, counts, visits);
 }
 
 int rt_query_tris_host(RtContext *c, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {

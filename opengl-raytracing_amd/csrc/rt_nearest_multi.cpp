@@ -3,9 +3,10 @@
 //
 // For one point p, S is the set of rows t with e(t) <= L, e(t) exactly rt_nearest_points' (rt_nearest.cpp): the row's squared distance
 // d2(t) raised to the largest box bound on the way from the root to its leaf.  The count is |S|; the records are the maxHits least elements of S under
-// (e(t), prim).  e(t) is a function of the row and the point alone, so this walk visits every node, carries the running maximum, culls nothing, collects
-// S and sorts it.  The device walk (rt_nearest_multi.hip) culls against its K-th best and is held to this answer bit for bit; DESIGN.md 22.2 has the
-// proof that it may.  The float operations are rt_nearest.cpp's, shared through rt_nearest_math.hpp.
+// (e(t), prim).  e(t) is a function of the row and the point alone, so the walk (rt_nearest_rows.hpp, shared with rt_nearest.cpp) visits every node,
+// carries the running maximum and culls nothing; this file collects S and sorts it.  The device walk (rt_nearest_multi.hip) culls against its K-th
+// best and is held to this answer bit for bit; DESIGN.md 22.2 has the proof that it may.  The float operations are rt_nearest_math.hpp's, the text
+// the device compiles too.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -15,9 +16,8 @@
 #include <vector>
 
 #include "../../include/rt_mi355.h"
-#include "rt_bvh_tree.hpp"
-#include "rt_nearest_math.hpp"
 #include "rt_nearest_multi_block.hpp"
+#include "rt_nearest_rows.hpp"
 
 using namespace rtnear;
 
@@ -33,40 +33,17 @@ extern "C" int rt_nearest_points_multi(const float *nodes12, int nNodes, const f
         const bool scene = nNodes > 0 && nTris > 0;
         if (scene && !rtbvh::is_tree(nodes12, nNodes, nTris)) return RT_ERR_INVALID;
         const size_t K = (size_t)maxHits;
-        std::vector<std::pair<int, float>> stack;   // (node, the largest lb above it)
+        std::vector<std::pair<int, float>> stack;
         std::vector<std::pair<float, int>> S;       // (e, prim) of the accepted rows: std::pair orders as (e, prim), no e is NaN
         for (int i = 0; i < n; ++i) {
             const V p = ld(points + (size_t)i * stride);
             const float md = maxDist ? maxDist[i] : 0.0f;
             const float L = maxDist ? md * md : INFINITY;
             S.clear();
-            if (scene && !(maxDist && md < 0.0f) && finite3(p)) {   // maxDist[i] < 0 or a non-finite coordinate: an empty slot
-                stack.assign(1, {0, 0.0f});
-                while (!stack.empty()) {
-                    const int ni = stack.back().first;
-                    const float above = stack.back().second;
-                    stack.pop_back();
-                    const float *q = nodes12 + (size_t)ni * 12;
-                    const float pathLB = fmaxr(above, box_lb(ld(q), ld(q + 4), p));
-                    const rtbvh::Node N = rtbvh::node_fetch(q);
-                    if (N.count > 0) {
-                        for (int k = 0; k < N.count; ++k) {
-                            const int prim = N.first + k;
-                            const float *t = tris12 + (size_t)prim * 12;
-                            const V v0 = ld(t), e1 = ld(t + 4), e2 = ld(t + 8);
-                            float u, v;
-                            closest_uv(p, v0, e1, e2, u, v);
-                            const V diff = sub(p, point_at(v0, e1, e2, u, v));
-                            const float d2 = dot(diff, diff);
-                            const float e = (d2 < pathLB) ? pathLB : d2;   // a NaN d2 stays NaN
-                            if (e <= L) S.push_back({e, prim});
-                        }
-                    } else {
-                        stack.push_back({N.right, pathLB});
-                        stack.push_back({N.left, pathLB});
-                    }
-                }
-            }
+            if (scene && !(maxDist && md < 0.0f) && finite3(p))   // maxDist[i] < 0 or a non-finite coordinate: an empty slot
+                for_each_row(nodes12, tris12, p, stack, [&](int prim, float e) {
+                    if (e <= L) S.push_back({e, prim});
+                });
             if (counts) counts[i] = (int32_t)S.size();
             const size_t kept = std::min(K, S.size());
             std::partial_sort(S.begin(), S.begin() + (ptrdiff_t)kept, S.end());

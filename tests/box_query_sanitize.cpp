@@ -1,5 +1,5 @@
-// The box query's definition (csrc/rt_box_query.cpp: rt_box_overlaps) driven over its edge cases under AddressSanitizer + UBSan on the CPU
-// (tests/test_box_query_host_sanitizers.py).  Linked with rt_box_query.cpp alone.  Every array is exactly as long as the call may read or write: a
+// The box query's definition (csrc/rt_overlap_query.cpp: rt_box_overlaps) driven over its edge cases under AddressSanitizer + UBSan on the CPU
+// (tests/test_box_query_host_sanitizers.py).  Linked with rt_overlap_query.cpp alone.  Every array is exactly as long as the call may read or write: a
 // strided box array ends with its last box's sixth float, offsets hold n + 1 entries, prims offsets[n] or n * cap entries (none at all for cap = 0),
 // counts n.
 #include <algorithm>

@@ -1,5 +1,5 @@
-// The triangle query's definition (csrc/rt_tri_query.cpp: rt_tri_overlaps) driven over its edge cases under AddressSanitizer + UBSan on the CPU
-// (tests/test_tri_query_host_sanitizers.py).  Linked with rt_tri_query.cpp alone.  Every array is exactly as long as the call may read or write: a
+// The triangle query's definition (csrc/rt_overlap_query.cpp: rt_tri_overlaps) driven over its edge cases under AddressSanitizer + UBSan on the CPU
+// (tests/test_tri_query_host_sanitizers.py).  Linked with rt_overlap_query.cpp alone.  Every array is exactly as long as the call may read or write: a
 // strided query array ends with its last triangle's ninth float, offsets hold n + 1 entries, prims offsets[n] or n * cap entries (none at all for
 // cap = 0), counts n.
 #include <algorithm>

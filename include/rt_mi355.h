@@ -689,6 +689,77 @@ int rt_query_tris(RtContext *ctx, const float *qtris, int stride, int n, const i
 int rt_query_tris_host(RtContext *ctx, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts,
                        int32_t *visits);
 
+/* ---------------------------------------------------------------- hull queries: the triangles in a frustum or an oriented box; marquee picking
+ * The volumes an axis-aligned box does not fit: the frustum behind a rectangle of a perspective view (marquee selection through hidden layers), a
+ * trigger volume that moves with a part (a box under the part's model matrix), a sheared box.  All are one shape, a convex hexahedron given by its
+ * eight corners -- the image of a box under an affine or projective map.
+ *   Query i is hulls[i * stride .. i * stride + 23] = c0.xyz .. c7.xyz (stride >= 24 floats).  Corner k has bit 0 for the low or high end along the
+ * shape's first parameter, bit 1 along the second, bit 2 along the third (for a frustum: x, y and depth).  A NaN in any of the 24 floats marks an empty
+ * slot (count 0, nothing listed, visits 0); +-inf and huge coordinates are legal and err towards overlap.  The solid is the convex hull of the eight
+ * points.  The caller supplies planar, convex faces; where they are not planar the test still never misses a real overlap -- every axis it tries
+ * projects all eight points -- and errs towards overlap.  [lo, hi] is the componentwise fmin / fmax of the corners.
+ *   Formed once per query: the six face normals -- for the faces {0,2,4,6}, {1,3,5,7}, {0,1,4,5}, {2,3,6,7}, {0,1,2,3}, {4,5,6,7}, written (a, b, c, d),
+ * cross(fl(c_d - c_a), fl(c_c - c_b)), the cross product of the face's diagonals, so that a face collapsed to a point (the apex of a pyramid) leaves its
+ * neighbours' normals intact and has the zero normal itself, which never separates -- and the hull's interval on each, the min / max of dot(normal, c_k)
+ * over the eight corners, a NaN operand ignored.
+ *   Row t of tris12 is accepted when (a) every node from the root to t's leaf passes the node test -- its box overlaps [lo, hi] by rt_box_overlaps'
+ * comparisons, and none of the six face normals parts the box from the hull: the box projects to its corners through dot's own three steps, the least
+ * and the greatest kept at each, and a normal separates only when bmax < hmin || hmax < bmin is true -- and (b) none of 46 axes separates the hull from
+ * the triangle a = v0, b = fl(v0 + e1), c = fl(v0 + e2), tried in this order: the three box axes by comparisons of [min3, max3](a, b, c) with [lo, hi];
+ * the six face normals against the kept intervals; n = cross(e1, e2); the 36 axes cross(f_i, d_e) with f = e1, fl(e2 - e1), e2 and d_e = fl(c_j - c_i)
+ * for the edges (0,1), (2,3), (4,5), (6,7), (0,2), (1,3), (4,6), (5,7), (0,4), (1,5), (2,6), (3,7), the edge loop outside.  On a projected axis the hull is
+ * the min / max of dot(axis, c_k) and the triangle that of dot(axis, point); the axis separates only when Tmax < Hmin || Hmax < Tmin is true: a NaN
+ * never separates.  On the 43 projected axes, and in the node test, only finite projections separate: a hull some 1e19 across that is not
+ * axis-aligned has normals and edge products that overflow, dot then gives inf for some points and NaN for others, and an interval of the points that
+ * happened to stay finite would be no interval of the hull.  So each side's interval counts only when the float sum of its projections (the eight
+ * corners' ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), the row's (ta + tb) + tc) is finite -- an inf or a NaN among them stays in the sum --,
+ * and a node's box only when it and its interval on the normal lie within +-1e38 (comparisons, which a NaN fails).  That is how infinite and huge hulls err towards overlap.  Degenerate hulls (a point, a segment, a quad) and rows lose axes and err towards overlap; a pair that shares a point in all three
+ * floats is accepted.  DESIGN.md 26.1 has every operation.  For the trees this library builds, node boxes are the float min / max of a, b, c of their
+ * rows and the box's interval on a normal contains the dot of every point inside the box, so (b) implies (a): the list is the set of rows the row test
+ * accepts, whatever the walk.
+ *   List order, counts, prims, offsets and cap: word for word as rt_box_overlaps above -- right child first, the rows of a leaf ascending; the first
+ * min(capacity, counts[i]) rows are written, entries past them are NOT written.
+ *   rt_hull_overlaps is the definition: host arrays, no context, no GPU.  rt_query_hulls: device pointers, enqueued on rt_stream()'s stream, no host
+ * synchronisation and, after the context's first query, no allocation; one lane walks one query.  visits (may be NULL): the node boxes tested, 1 + twice
+ * the inner nodes entered, 0 for an empty slot -- never more than rt_query_boxes' on [lo, hi].  RT_ERR_INVALID: n < 0, a stride below 24, null hulls,
+ * prims and counts both NULL, prims without offsets and cap < 0 or n * cap beyond INT32_MAX, misaligned arrays, a hull array beyond 2^32 floats.
+ * RT_ERR_STATE: no BVH uploaded.  A refused call writes nothing; n == 0 is a no-op.  Frame state stays untouched.  The _host twin takes host pointers,
+ * stages through the context's buffer and synchronises; its prims array holds offsets[n] entries (offsets must then be ascending from 0), or n * cap.
+ *
+ *   The corner makers, host only, no context, no GPU.  rt_box_corners: corner k of box i (boxes[i * stride ..] = lo.xyz, hi.xyz, stride >= 6) is
+ * M * (k&1 ? hi.x : lo.x, k&2 ? hi.y : lo.y, k&4 ? hi.z : lo.z, 1) in rt_gather_triangles' expression, into corners24[i * 24 ..].  M16s NULL is the
+ * identity, which copies; else matrix i is M16s[i * matStride ..], matStride 0 (one matrix for all boxes) or 16 (one per box, as the part matrices
+ * lie in rt_mesh_part_matrices' table).  A NaN component or lo > hi writes 24 NaNs, an empty slot.  RT_ERR_INVALID: n < 0, a stride below 6, another
+ * matStride, null arrays with n > 0.
+ *   rt_rect_frusta: rect i is rects[i * stride ..] = (x0, y0, x1, y1) (stride >= 4) in pixel-corner coordinates of the frame u describes, row 0 at the
+ * bottom as rt_pick_pixels counts rows: pixel (x, y) covers [x, x + 1] x [y, y + 1].  Any floats are legal, outside the frame too; a NaN, x1 < x0 or
+ * y1 < y0 writes 24 NaNs.  The direction through the frame point (fx, fy) is primaryDirJ's before its normalize, jitter honoured as there:
+ * D(fx, fy)[a] = (camFwd[a] + (nx * camRight[a]) * sx) + (ny * camUp[a]) * sy with nx = ((fx + jx) / resolution[0]) * 2 - 1, ny likewise, sx = tanHalfFov *
+ * aspect, sy = tanHalfFov.  Its depth along camFwd is 1, so the near and far faces are planes of constant depth, and corner k is
+ * fma(D(k&1 ? x1 : x0, k&2 ? y1 : y0)[a], k&4 ? far : tNear, camPos[a]).  tNear >= 0; 0 gives the pyramid from the eye.  far = max(tFar, tNear) when
+ * tFar >= 0; tFar < 0 is "to the far side of the scene": with s the greatest dot(camFwd, fl(rootCorner_k - camPos)) over the eight corners of
+ * [rootMin, rootMax], far = fmax(fma(|s|, 2^-10, s), tNear) -- widened so that rounding cannot cut off the farthest vertex.  Only the camera fields of u
+ * are read: camPos, camRight, camUp, camFwd, tanHalfFov, aspect, resolution, jitter, enableJitter.  RT_ERR_INVALID: null u, rootMin or rootMax, a
+ * resolution <= 0, a negative or NaN tNear, a NaN tFar, a stride below 4, n < 0, null arrays with n > 0.
+ *   rt_pick_rects: marquee picking.  A kernel writes rt_rect_frusta's 24 floats per rect into corners -- a required device array of n * 24 floats, an
+ * output the caller can draw -- with the root box of the uploaded BVH or the dynamic mesh as it stands on the device; then the hull query runs on
+ * corners, on the same stream and with no host wait.  Everything else -- offsets, cap, prims, counts, visits, the refusals, "a refused call writes
+ * nothing" and "no allocation after the context's first query" -- as rt_query_hulls, plus rt_rect_frusta's refusals.  The _host twin as above; its
+ * corners array is host memory. */
+int rt_hull_overlaps(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *hulls, int stride /* >= 24: c0.xyz .. c7.xyz */, int n,
+                     const int32_t *offsets /* n + 1 entries, or NULL */, int cap, int32_t *prims /* may be NULL */, int32_t *counts /* may be NULL, not both */);
+int rt_query_hulls(RtContext *ctx, const float *hulls, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits);
+int rt_query_hulls_host(RtContext *ctx, const float *hulls, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts,
+                        int32_t *visits);
+int rt_box_corners(const float *boxes, int stride /* >= 6 */, int n, const float *M16s /* NULL: the identity */, int matStride /* 0 or 16 */,
+                   float *corners24);
+int rt_rect_frusta(const RtUniforms *u, const float *rootMin, const float *rootMax, const float *rects, int stride /* >= 4: x0, y0, x1, y1 */, int n,
+                   float tNear, float tFar /* < 0: to the far side of the scene */, float *corners24);
+int rt_pick_rects(RtContext *ctx, const RtUniforms *u, const float *rects, int stride, int n, float tNear, float tFar, float *corners /* n * 24 floats */,
+                  const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits);
+int rt_pick_rects_host(RtContext *ctx, const RtUniforms *u, const float *rects, int stride, int n, float tNear, float tFar, float *corners,
+                       const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits);
+
 /* ---------------------------------------------------------------- dynamic mesh: the BVH scene rebuilt on the device
  * Replaces rebuild_bvh_from_model_path / a change of AppState::bvhTransform (gather_model_triangles + build_bvh + upload_bvh_tbo on every change of
  * the model or its transform).  Contract: after rt_mesh_rebuild(ctx, M) the context's scene is, byte for byte in every device array, what

@@ -381,6 +381,15 @@ SIGNATURES = {
     "rt_tri_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_query_tris": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_query_tris_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hull_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_query_hulls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_query_hulls_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_box_corners": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_rect_frusta": (C.c_int, [C.POINTER(RtUniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "rt_pick_rects": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    "rt_pick_rects_host": (C.c_int, [C.c_void_p, C.POINTER(RtUniforms), C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "rt_bvh_layout": (C.c_int, [C.c_int, C.POINTER(RtBvhLayout)]),
     "rt_mesh_upload": (C.c_int, [C.c_void_p, _FP, C.c_int, _U32P, C.c_int]),
     "rt_mesh_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -1817,6 +1826,113 @@ def tri_overlaps(nodes12, tris12, qtris, cap=None) -> TriOverlaps:
     return _numpy_box_query(call, qtris, cap, False, rows=_numpy_tris, result=TriOverlaps)
 
 
+class HullOverlaps(TriOverlaps):
+    """Answers of hull_overlaps, Renderer.hull_overlaps and Renderer.pick_rects: `count`, `offsets`, `prims`, `visits`, `.hits()` and
+    `.pairs()` as TriOverlaps, per hull; `corners` [N,24] float32 -- the hulls pick_rects made of its rects, eight corners each, ready to draw -- or
+    None where the caller brought the hulls."""
+
+    def __init__(self, count, offsets, prims, visits=None, corners=None):
+        super().__init__(count, offsets, prims, visits)
+        self.corners = corners
+
+
+def _hull_rows(shape, itemsize, strides):
+    """The checks of the hull queries on a [N,k] (k >= 24) or [N,8,3] array -> the row stride in floats."""
+    if len(shape) == 3 and tuple(shape[1:]) == (8, 3):
+        if strides[1] != 3 * itemsize or strides[2] != itemsize:
+            raise _query_invalid("hulls [N,8,3]: the 24 floats of a hull must be contiguous")
+        shape, strides = (shape[0], 24), (strides[0], itemsize)
+    if len(shape) != 2 or shape[1] < 24:
+        raise _query_invalid(f"hulls must be [N,k] with k >= 24 (c0.xyz .. c7.xyz) or [N,8,3], got shape {tuple(shape)}")
+    row, col = strides
+    if col != itemsize or row % itemsize or (shape[0] > 1 and row // itemsize < 24):
+        raise _query_invalid("hulls must have unit stride along its last dimension and rows at least 24 floats apart")
+    return max(row // itemsize, 24) if shape[0] > 1 else max(shape[1], 24)
+
+
+def _numpy_hulls(hulls):
+    if not isinstance(hulls, np.ndarray):
+        raise _query_invalid("hulls must be a numpy array")
+    if hulls.dtype != np.float32:
+        raise _query_invalid(f"hulls must be float32, got {hulls.dtype}")
+    stride = _hull_rows(hulls.shape, 4, hulls.strides)
+    return hulls.shape[0], stride
+
+
+def hull_overlaps(nodes12, tris12, hulls, cap=None) -> HullOverlaps:
+    """The definition of the hull query (rt_hull_overlaps), on the host and without a context: per convex hexahedron (eight corners, corner
+    k with bit 0 / 1 / 2 for the high end along the shape's first / second / third parameter) the rows of (nodes12, tris12) that lie under nodes that
+    its box and its six face normals cannot part from it and that the 46-axis separating-axis test cannot part from it, in walk order, and their
+    count.  hulls: float32 [N,24], [N,8,3] or [N,k], k >= 24, rows may be strided (numpy); a NaN among the 24 floats marks an empty slot.  cap=None:
+    the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per hull."""
+    cap = _box_cap(cap)
+    nodes = _f32(nodes12).reshape(-1, 12)
+    tris = _f32(tris12).reshape(-1, 12)
+    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+
+    def call(q, stride, n, offsets, cap_, prims, counts, _visits):
+        rc = lib().rt_hull_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], q, stride, n, offsets, cap_, prims, counts)
+        if rc != RT_OK:
+            raise RtError(rc, "rt_hull_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_hull_overlaps")
+
+    return _numpy_box_query(call, hulls, cap, False, rows=_numpy_hulls, result=HullOverlaps)
+
+
+def box_corners(boxes, M=None):
+    """The hulls [N,24] float32 of the boxes [N,k], k >= 6 (lo.xyz, hi.xyz; numpy float32, rows may be strided) under M (rt_box_corners, DESIGN.md
+    26.2): None, the identity, which copies; 16 floats, one column-major matrix for all boxes; or [N,16], one per box -- rows of
+    mesh_part_matrices().  A NaN component or lo > hi gives 24 NaNs, an empty slot of the hull query."""
+    n, stride = _numpy_boxes(boxes)
+    m, mat_stride = None, 0
+    if M is not None:
+        m = _f32(M).reshape(-1, 16)
+        if m.shape[0] not in (1, n):
+            raise _query_invalid(f"M must hold one matrix or one per box, got {m.shape[0]} for {n} boxes")
+        mat_stride = 16 if m.shape[0] == n and n > 1 else 0
+    out = np.zeros((n, 24), np.float32)
+    if n:
+        rc = lib().rt_box_corners(C.c_void_p(boxes.ctypes.data), stride, n, C.c_void_p(m.ctypes.data) if m is not None else None, mat_stride,
+                                  C.c_void_p(out.ctypes.data))
+        if rc != RT_OK:
+            raise RtError(rc, "rt_box_corners")
+    return out
+
+
+def _rect_rows(a, itemsize, strides):
+    """The checks of a [N,k] rect array, k >= 4 -> the row stride in floats."""
+    if a.ndim != 2 or a.shape[1] < 4:
+        raise _query_invalid(f"rects must be [N,k] with k >= 4 (x0, y0, x1, y1), got shape {tuple(a.shape)}")
+    row, col = strides
+    if col != itemsize or row % itemsize or (a.shape[0] > 1 and row // itemsize < 4):
+        raise _query_invalid("rects must have unit stride along its last dimension and rows at least 4 floats apart")
+    return max(row // itemsize, 4) if a.shape[0] > 1 else max(a.shape[1], 4)
+
+
+def _numpy_rects(rects):
+    if not isinstance(rects, np.ndarray):
+        raise _query_invalid("rects must be a numpy array")
+    if rects.dtype != np.float32:
+        raise _query_invalid(f"rects must be float32, got {rects.dtype}")
+    if rects.ndim != 2:
+        raise _query_invalid("rects must be [N,k]")
+    return rects.shape[0], _rect_rows(rects, 4, rects.strides)
+
+
+def rect_frusta(u, root_min, root_max, rects, t_near=0.0, t_far=None):
+    """The hulls [N,24] float32 behind the rects [N,k], k >= 4 (x0, y0, x1, y1 in pixel-corner coordinates of u's frame, row 0 at the bottom; numpy
+    float32) between the depths t_near and t_far along the view direction (rt_rect_frusta).  t_near=0: the pyramid from the eye.
+    t_far=None: to the far side of the box [root_min, root_max] -- node 0's box of the scene.  A NaN, x1 < x0 or y1 < y0 gives 24 NaNs."""
+    n, stride = _numpy_rects(rects)
+    lo, hi = _f32(root_min).reshape(3), _f32(root_max).reshape(3)
+    out = np.zeros((n, 24), np.float32)
+    rc = lib().rt_rect_frusta(C.byref(u) if u is not None else None, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data),
+                              C.c_void_p(rects.ctypes.data) if n else None, stride, n, float(t_near), -1.0 if t_far is None else float(t_far),
+                              C.c_void_p(out.ctypes.data) if n else None)
+    if rc != RT_OK:
+        raise RtError(rc, "rt_rect_frusta")
+    return out
+
+
 def rows_as_tris(tris12):
     """The points of each row of tris12 as query triangles [N,9] float32: a = v0, b = v0 + e1, c = v0 + e2 by the definition's float32 adds (DESIGN.md
     24.1) -- the very floats the triangle test forms, so a query made of them shares its points with the row bit for bit.  numpy or torch."""
@@ -2878,6 +2994,53 @@ class Renderer:
         dev = self._query_device(qtris, dtype=torch.float32)
         stride = _tri_rows(tuple(qtris.shape), 1, qtris.stride())
         return self._device_overlaps(lib().rt_query_tris, TriOverlaps, qtris, stride, dev, cap, visits)
+
+    def hull_overlaps(self, hulls, cap=None, visits=False) -> HullOverlaps:
+        """The rows of the uploaded BVH or the dynamic mesh that overlap each convex hexahedron (rt_query_hulls) -> HullOverlaps, equal
+        to hull_overlaps on the same arrays bit for bit.  hulls: float32 [N,24], [N,8,3] or [N,k], k >= 24 (c0.xyz .. c7.xyz), rows may be strided; a
+        NaN among the 24 floats marks an empty slot.  box_corners and rect_frusta make hulls of boxes under matrices and of rects of the frame.  cap,
+        visits, the numpy / torch paths, stream ordering and lifetimes as box_overlaps; visits never exceeds box_overlaps' for the boxes of the
+        hulls' corners.  One lane walks one hull."""
+        cap = _box_cap(cap)
+        if isinstance(hulls, np.ndarray):
+            call = lambda *a: self._check(lib().rt_query_hulls_host(self._h, *a))
+            return _numpy_box_query(call, hulls, cap, visits, rows=_numpy_hulls, result=HullOverlaps)
+        import torch
+        if not isinstance(hulls, torch.Tensor):
+            raise _query_invalid("hulls must be a numpy array or a torch tensor")
+        dev = self._query_device(hulls, dtype=torch.float32)
+        stride = _hull_rows(tuple(hulls.shape), 1, hulls.stride())
+        return self._device_overlaps(lib().rt_query_hulls, HullOverlaps, hulls, stride, dev, cap, visits)
+
+    def pick_rects(self, u, rects, t_near=0.0, t_far=None, cap=None, visits=False) -> HullOverlaps:
+        """Marquee picking (rt_pick_rects): the rows of the uploaded BVH or the dynamic mesh inside the frustum behind each rect of u's
+        frame, hidden ones included -> HullOverlaps whose `corners` [N,24] are the frusta, equal to rect_frusta bit for bit, and whose lists equal
+        hull_overlaps on them.  rects: float32 [N,k], k >= 4 (x0, y0, x1, y1 in pixel-corner coordinates, row 0 at the bottom: pixel (x, y) covers
+        [x, x+1] x [y, y+1]); t_near, t_far as rect_frusta, the root box the scene's own as it stands on the device.  cap, visits, the numpy / torch
+        paths, stream ordering and lifetimes as box_overlaps."""
+        cap = _box_cap(cap)
+        if not isinstance(u, RtUniforms):
+            raise _query_invalid("u must be an RtUniforms")
+        tn, tf = float(t_near), -1.0 if t_far is None else float(t_far)
+        if isinstance(rects, np.ndarray):
+            n, stride = _numpy_rects(rects)
+            corners = np.zeros((n, 24), np.float32)
+            pc = C.c_void_p(corners.ctypes.data) if n else None
+            call = lambda r, _stride, n_, *a: self._check(lib().rt_pick_rects_host(self._h, C.byref(u), r, stride, n_, tn, tf, pc, *a))
+            ans = _numpy_box_query(call, rects, cap, visits, rows=lambda _r: (n, stride), result=HullOverlaps)
+            ans.corners = corners
+            return ans
+        import torch
+        if not isinstance(rects, torch.Tensor):
+            raise _query_invalid("rects must be a numpy array or a torch tensor")
+        dev = self._query_device(rects, dtype=torch.float32)
+        stride = _rect_rows(rects, 1, rects.stride() if rects.dim() == 2 else (0, 0))
+        corners = torch.zeros((rects.shape[0], 24), dtype=torch.float32, device=dev)
+        pc = C.c_void_p(corners.data_ptr()) if corners.numel() else None
+        entry = lambda h, r, stride_, n_, *a: lib().rt_pick_rects(h, C.byref(u), r, stride_, n_, tn, tf, pc, *a)
+        ans = self._device_overlaps(entry, HullOverlaps, rects, stride, dev, cap, visits)
+        ans.corners = corners
+        return ans
 
     def _query_device(self, *arrays, dtype):
         import torch

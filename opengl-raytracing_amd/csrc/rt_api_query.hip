@@ -1,5 +1,5 @@
-// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21, 22, 23 and 24): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
-// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes, rt_query_tris and their _host twins.  Host code only: rt_wave.hip,
+// rt_api_query.hip -- the query part of the C ABI (include/rt_mi355.h; DESIGN.md 12, 13, 19, 20, 21, 22, 23, 24 and 26): rt_trace_rays, rt_trace_scene_rays, rt_pick_pixels,
+// rt_trace_rays_multi, rt_pick_pixels_multi, rt_query_nearest, rt_query_nearest_multi, rt_query_boxes, rt_query_tris, rt_query_hulls, rt_pick_rects and their _host twins.  Host code only: rt_wave.hip,
 // rt_scene_query.hip, rt_multi_hit.hip, rt_nearest.hip, rt_nearest_multi.hip and rt_overlap_query.hip launch, this file checks arguments and orders the queries on rt_stream()'s stream.
 #include <hip/hip_runtime.h>
 
@@ -198,11 +198,12 @@ int nearest_multi_args(RtContext *c, const char *what, const float *points, int 
     return nearest_args(c, what, points, stride, n, hits, maxHits > 0);
 }
 
-// ---- box queries and triangle queries: the rows overlapping an axis-aligned box, or intersected by a query triangle, per
-// query, by one traversal over two shapes (rt_overlap_query.hip).  Share the queries' scratch and event; touch no frame state.
+// ---- box queries, triangle queries and hull queries: the rows overlapping an axis-aligned box, intersected
+// by a query triangle, or overlapping a convex hexahedron, per query, by one traversal over three shapes (rt_overlap_query.hip).  Share the queries' scratch and event; touch no frame state.
 // What tells the two apart in the checks, in the staging and in the launch: the floats of one query, the words of the messages, and the shape
 struct OverlapKind { int floats; const char *layout, *noun; OverlapShape shape; };
-constexpr OverlapKind kBoxes = {6, "lo.xyz, hi.xyz", "box", RT_OVERLAP_BOX}, kTris = {9, "p0.xyz, p1.xyz, p2.xyz", "triangle", RT_OVERLAP_TRI};
+constexpr OverlapKind kBoxes = {6, "lo.xyz, hi.xyz", "box", RT_OVERLAP_BOX}, kTris = {9, "p0.xyz, p1.xyz, p2.xyz", "triangle", RT_OVERLAP_TRI},
+                      kHulls = {24, "c0.xyz .. c7.xyz", "hull", RT_OVERLAP_HULL};
 
 // What all four entries check, before anything is enqueued or written.  offsets is the caller's to get right: device memory for the device entries
 int overlap_args(RtContext *c, const char *what, const OverlapKind &k, const float *queries, int stride, int n, const int32_t *offsets, int cap, const int32_t *prims,
@@ -218,7 +219,7 @@ int overlap_args(RtContext *c, const char *what, const OverlapKind &k, const flo
     return RT_OK;
 }
 
-// The device entry (rt_query_boxes or rt_query_tris)
+// The device entry (rt_query_boxes, rt_query_tris or rt_query_hulls)
 int overlap_query(RtContext *c, const char *what, const OverlapKind &k, const float *queries, int stride, int n, const int32_t *offsets, int cap, int32_t *prims,
                   int32_t *counts, int32_t *visits) {
     if (!c) return RT_ERR_INVALID;
@@ -231,21 +232,28 @@ int overlap_query(RtContext *c, const char *what, const OverlapKind &k, const fl
     return QUERY_RUN(c, rt_overlap_launch(k.shape, st, c->treeDepth, c->dQueryFrame, make_dev_scene(c), q));
 }
 
-// The _host twin of `entry` (rt_query_boxes or rt_query_tris): host pointers staged through the context's buffer
-using OverlapEntry = int (*)(RtContext *, const float *, int, int, const int32_t *, int, int32_t *, int32_t *, int32_t *);
-int overlap_host(RtContext *c, const char *what, const OverlapKind &k, OverlapEntry entry, const float *queries, int stride, int n, const int32_t *offsets, int cap,
-                 int32_t *prims, int32_t *counts, int32_t *visits) {
-    if (!c) return RT_ERR_INVALID;
-    const int rc = overlap_args(c, what, k, queries, stride, n, offsets, cap, prims, counts);
-    if (rc != RT_OK || n == 0) return rc;
-    // host offsets can be, and are, inspected: the staged prims array holds offsets[n] entries
-    size_t entries = prims ? (size_t)n * (size_t)cap : 0;
+// Host offsets can be, and are, inspected: the staged prims array holds offsets[n] entries, or n * cap
+int host_entries(RtContext *c, const char *what, int n, const int32_t *offsets, int cap, const int32_t *prims, size_t &entries) {
+    entries = prims ? (size_t)n * (size_t)cap : 0;
     if (prims && offsets) {
         if (offsets[0] < 0) return fail(c, RT_ERR_INVALID, "%s: offsets[0] = %d", what, offsets[0]);
         for (int i = 0; i < n; ++i)
             if (offsets[i + 1] < offsets[i]) return fail(c, RT_ERR_INVALID, "%s: offsets descend at %d", what, i);
         entries = (size_t)offsets[n];
     }
+    return RT_OK;
+}
+
+// The _host twin of `entry` (rt_query_boxes, rt_query_tris or rt_query_hulls): host pointers staged through the context's buffer
+using OverlapEntry = int (*)(RtContext *, const float *, int, int, const int32_t *, int, int32_t *, int32_t *, int32_t *);
+int overlap_host(RtContext *c, const char *what, const OverlapKind &k, OverlapEntry entry, const float *queries, int stride, int n, const int32_t *offsets, int cap,
+                 int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = overlap_args(c, what, k, queries, stride, n, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    size_t entries = 0;
+    const int er = host_entries(c, what, n, offsets, cap, prims, entries);
+    if (er != RT_OK) return er;
     // staging layout: queries | offsets | prims | counts | visits | one spare word; the query array keeps its stride; prims goes in as well, for the entries
     // no list reaches.  An empty prims array has no staged address: the spare word stands in for it, and no list reaches that either
     const size_t N = (size_t)n;
@@ -255,6 +263,21 @@ int overlap_host(RtContext *c, const char *what, const OverlapKind &k, OverlapEn
     return staged(c, what, segs, [&](void *const *d) {
         return entry(c, (const float *)d[0], stride, n, (const int32_t *)d[1], cap, prims ? (int32_t *)(d[2] ? d[2] : d[5]) : nullptr, (int32_t *)d[3], (int32_t *)d[4]);
     });
+}
+
+// ---- marquee picking: the frusta behind rects of the frame, written into the caller's corners array by a kernel of their own, then
+// the hull query on them, on the same stream and with no host wait
+// What both entries check, before anything is enqueued or written: the camera, the depths and the rects, then what overlap_args checks of a hull query
+// on `corners`
+int pick_rects_args(RtContext *c, const char *what, const RtUniforms *u, const float *rects, int stride, int n, float tNear, float tFar, const float *corners,
+                    const int32_t *offsets, int cap, const int32_t *prims, const int32_t *counts) {
+    if (!u) return fail(c, RT_ERR_INVALID, "%s: null uniforms", what);
+    if (!rthull::rect_args_ok(u, stride, tNear, tFar))
+        return fail(c, RT_ERR_INVALID, "%s: resolution %g x %g, tNear %g, tFar %g, stride %d floats (a resolution above 0, tNear >= 0, tFar no NaN, at least 4: x0, y0, x1, y1)", what,
+                    (double)u->resolution[0], (double)u->resolution[1], (double)tNear, (double)tFar, stride);
+    if (n > 0 && (!rects || !corners)) return fail(c, RT_ERR_INVALID, "%s: null rect or corner array", what);
+    if ((size_t)(n > 0 ? n - 1 : 0) * (size_t)stride + 4 > ((size_t)1 << 32)) return fail(c, RT_ERR_INVALID, "%s: the rect array exceeds 2^32 floats", what);
+    return overlap_args(c, what, kHulls, corners, 24, n, offsets, cap, prims, counts);
 }
 
 }  // namespace
@@ -448,6 +471,51 @@ int rt_query_tris(RtContext *c, const float *qtris, int stride, int n, const int
 
 int rt_query_tris_host(RtContext *c, const float *qtris, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
     return overlap_host(c, "rt_query_tris_host", kTris, rt_query_tris, qtris, stride, n, offsets, cap, prims, counts, visits);
+}
+
+// ---- hull queries
+int rt_query_hulls(RtContext *c, const float *hulls, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    return overlap_query(c, "rt_query_hulls", kHulls, hulls, stride, n, offsets, cap, prims, counts, visits);
+}
+
+int rt_query_hulls_host(RtContext *c, const float *hulls, int stride, int n, const int32_t *offsets, int cap, int32_t *prims, int32_t *counts, int32_t *visits) {
+    return overlap_host(c, "rt_query_hulls_host", kHulls, rt_query_hulls, hulls, stride, n, offsets, cap, prims, counts, visits);
+}
+
+int rt_pick_rects(RtContext *c, const RtUniforms *u, const float *rects, int stride, int n, float tNear, float tFar, float *corners, const int32_t *offsets, int cap,
+                  int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = pick_rects_args(c, "rt_pick_rects", u, rects, stride, n, tNear, tFar, corners, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    if (((uintptr_t)rects | (uintptr_t)corners | (uintptr_t)offsets | (uintptr_t)prims | (uintptr_t)counts | (uintptr_t)visits) & 3u)
+        return fail(c, RT_ERR_INVALID, "rt_pick_rects: float and int32 arrays must be 4-byte aligned");
+    const rthull::RectCam cam = rthull::rect_cam(*u);
+    OverlapQuery q = {};
+    q.q = corners; q.qs = 24; q.n = (uint32_t)n; q.offsets = prims ? offsets : nullptr; q.cap = cap; q.prims = prims; q.counts = counts; q.visits = visits;
+    return query_run(c, "rt_pick_rects", [&](hipStream_t st) {
+        const DevScene sc = make_dev_scene(c);
+        const hipError_t e = rt_rect_frusta_launch(st, c->dQueryFrame, sc, cam, rects, stride, (uint32_t)n, tNear, tFar, corners);
+        return e != hipSuccess ? e : rt_overlap_launch(RT_OVERLAP_HULL, st, c->treeDepth, c->dQueryFrame, sc, q, true);   // (one prep launch per call)
+    });
+}
+
+int rt_pick_rects_host(RtContext *c, const RtUniforms *u, const float *rects, int stride, int n, float tNear, float tFar, float *corners, const int32_t *offsets, int cap,
+                       int32_t *prims, int32_t *counts, int32_t *visits) {
+    if (!c) return RT_ERR_INVALID;
+    const int rc = pick_rects_args(c, "rt_pick_rects_host", u, rects, stride, n, tNear, tFar, corners, offsets, cap, prims, counts);
+    if (rc != RT_OK || n == 0) return rc;
+    size_t entries = 0;
+    const int er = host_entries(c, "rt_pick_rects_host", n, offsets, cap, prims, entries);
+    if (er != RT_OK) return er;
+    // staging layout: rects | corners | offsets | prims | counts | visits | one spare word, as overlap_host
+    const size_t N = (size_t)n;
+    const int32_t spare = 0;
+    const StageSeg segs[] = {{rects, ((N - 1) * stride + 4) * 4, false}, {corners, N * 96, true}, {offsets, prims && offsets ? (N + 1) * 4 : 0, false},
+                             {prims, entries * 4, true, true}, {counts, counts ? N * 4 : 0, true}, {visits, visits ? N * 4 : 0, true}, {&spare, 4, false}};
+    return staged(c, "rt_pick_rects_host", segs, [&](void *const *d) {
+        return rt_pick_rects(c, u, (const float *)d[0], stride, n, tNear, tFar, (float *)d[1], (const int32_t *)d[2], cap, prims ? (int32_t *)(d[3] ? d[3] : d[6]) : nullptr,
+                             (int32_t *)d[4], (int32_t *)d[5]);
+    });
 }
 
 }  // extern "C"

@@ -1,10 +1,11 @@
-// rt_overlap_query.cpp -- rt_box_overlaps and rt_tri_overlaps (include/rt_mi355.h): the definitions of the box query and of the
-// triangle query.  Host only, no context, no GPU.
+// rt_overlap_query.cpp -- rt_box_overlaps, rt_tri_overlaps and rt_hull_overlaps (include/rt_mi355.h): the definitions of the box
+// query, of the triangle query and of the hull query.  Host only, no context, no GPU.
 //
-// For one query with the closed box [lo, hi] -- the box itself, or the box of a query triangle's three points -- the list is the rows t that lie under
-// nodes whose boxes overlap [lo, hi] all the way from the root and that the shape's separating-axis test cannot part from the query (13 axes for a
-// box; 20 for a triangle), in the order of a depth-first walk that takes the right child before the left and the rows
-// of a leaf ascending.  Nothing culls, so list and count are functions of the tree and the query alone; the device walk (rt_overlap_query.hip) makes
+// For one query with the closed box [lo, hi] -- the box itself, or the box of a query triangle's three points or of a hull's eight corners -- the list
+// is the rows t that lie under nodes that pass the shape's node test all the way from the root -- their boxes overlap [lo, hi] and, for a hull, none of
+// its six face normals parts them from it -- and that the shape's separating-axis test cannot part from the query (13 axes for a box, DESIGN.md 23.1;
+// 20 for a triangle; 46 for a hull), in the order of a depth-first walk that takes the right child before the left
+// and the rows of a leaf ascending.  Nothing culls by what was found, so list and count are functions of the tree and the query alone; the device walk (rt_overlap_query.hip) makes
 // the same tests in the same order and is held to this answer bit for bit.  The shapes and every float operation are rt_overlap_math.hpp's, the text
 // the device compiles too.
 #include <climits>
@@ -46,13 +47,12 @@ int overlaps(int minFloats, const float *nodes12, int nNodes, const float *tris1
             Shape S;
             if (scene && S.load(queries + (size_t)i * stride)) {   // else an empty slot
                 S.prepare();
-                const V lo = S.lo(), hi = S.hi();
                 stack.assign(1, 0);
                 while (!stack.empty()) {
                     const int ni = stack.back();
                     stack.pop_back();
                     const float *nd = nodes12 + (size_t)ni * 12;
-                    if (!boxes_overlap(ld(nd), ld(nd + 4), lo, hi)) continue;
+                    if (!S.node(ld(nd), ld(nd + 4))) continue;
                     const rtbvh::Node N = rtbvh::node_fetch(nd);
                     if (N.count > 0) {
                         for (int k = 0; k < N.count; ++k) {
@@ -85,4 +85,9 @@ extern "C" int rt_box_overlaps(const float *nodes12, int nNodes, const float *tr
 extern "C" int rt_tri_overlaps(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *qtris, int stride, int n, const int32_t *offsets,
                                int cap, int32_t *prims, int32_t *counts) {
     return overlaps<TriShape>(9, nodes12, nNodes, tris12, nTris, qtris, stride, n, offsets, cap, prims, counts);
+}
+
+extern "C" int rt_hull_overlaps(const float *nodes12, int nNodes, const float *tris12, int nTris, const float *hulls, int stride, int n, const int32_t *offsets,
+                                int cap, int32_t *prims, int32_t *counts) {
+    return overlaps<HullShape>(24, nodes12, nNodes, tris12, nTris, hulls, stride, n, offsets, cap, prims, counts);
 }

@@ -1,10 +1,13 @@
-// rt_overlap_query.hip -- the box query (rt_query_boxes) and the triangle query (rt_query_tris): per query the rows of the
-// triangle array that overlap the box, or that the query triangle intersects, as rt_box_overlaps and rt_tri_overlaps (rt_overlap_query.cpp) define
+// rt_overlap_query.hip -- the box query (rt_query_boxes), the triangle query (rt_query_tris) and the hull query
+// (rt_query_hulls, rt_pick_rects): per query the rows of the triangle array that overlap the box, that the query triangle intersects, or
+// that overlap the convex hull of the query's eight corners, as rt_box_overlaps, rt_tri_overlaps and rt_hull_overlaps (rt_overlap_query.cpp) define
 // them, in walk order.  One lane per query walks the two arrays every scene has -- the 64-byte two-child records with exact boxes (sc.wnodes) and the
-// 48-byte triangle rows (sc.tris) -- depth first, the right child before the left.  The query's box never shrinks, so nothing culls: the walk enters
-// exactly the nodes whose boxes overlap it, tests both children of each, and pushes the left one only when it overlaps too.  What a query is -- its
-// floats, its box, what it keeps across the walk and its test of a row -- is the shape's (rt_overlap_math.hpp), the same text the
-// definitions run.  A triangle forms its edges, its normal, the three in-plane axes and its intervals on those four once, after the root box test.
+// 48-byte triangle rows (sc.tris) -- depth first, the right child before the left.  The query never shrinks, so nothing culls by what was found: the
+// walk enters exactly the nodes that pass the shape's node test -- their boxes overlap the query's and, for a hull, none of its six face normals parts
+// them from it --, tests both children of each, and pushes the left one only when both pass.  What a query is -- its floats, its box, its node test,
+// what it keeps across the walk and its test of a row -- is the shape's (rt_overlap_math.hpp), the same text the definitions run.
+// A triangle forms its edges, its normal, the three in-plane axes and its intervals on those four once, after the root box test; a hull forms its six
+// face normals and its intervals on them once, before it, and its twelve edges again for every row that reaches them.
 //   LDS, sized by the launch: the stack, one 4-byte ref per entry laid out [entry][lane] per wave -- one wave's push or pop is one conflict-free 4-byte
 // write or read.  The shape, the write cursor and the count live in registers; a listing lane issues one 4-byte store per listed row and one for its
 // count.  No dynamically indexed register array, no scratch, no atomics.
@@ -17,8 +20,6 @@
 
 namespace rtd {
 namespace {
-
-using rtoverlap::boxes_overlap;
 
 // stackEntries: entries per lane of the stack (the tree's depth: depth first, at most one deferred sibling per level).  LIST = false: the counts alone
 template <class Shape, bool LIST>
@@ -44,16 +45,16 @@ __global__ __launch_bounds__(256) void k_overlap_query(const DevFrame *fr, Overl
     int found = 0, visits = 0;
     if (live) {
         visits = 1;
-        const V3 lo = S.lo(), hi = S.hi();
-        if (boxes_overlap(ld3(sc.rootMin), ld3(sc.rootMax), lo, hi)) {
-            S.prepare();
+        if constexpr (Shape::kPrepareFirst) S.prepare();   // (a hull's node test reads its face normals)
+        if (S.node(ld3(sc.rootMin), ld3(sc.rootMax))) {
+            if constexpr (!Shape::kPrepareFirst) S.prepare();
             int ref = sc.rootRef;
             int sp = 0;
             for (;;) {
                 if (ref >= 0) {
                     const float4 *nd = sc.wnodes + (size_t)ref * 4;
                     const float4 a = nd[0], bb = nd[1], c = nd[2], d = nd[3];
-                    const bool goL = boxes_overlap(f4xyz(a), f4xyz(bb), lo, hi), goR = boxes_overlap(f4xyz(c), f4xyz(d), lo, hi);
+                    const bool goL = S.node(f4xyz(a), f4xyz(bb)), goR = S.node(f4xyz(c), f4xyz(d));
                     visits += 2;
                     const int refL = (int)f2u(a.w), refR = (int)f2u(bb.w);
                     if (goL && goR && sp < stackEntries) {   // (the depth bounds the deferred siblings: one per level)
@@ -86,6 +87,15 @@ __global__ __launch_bounds__(256) void k_overlap_query(const DevFrame *fr, Overl
     if (r.visits) r.visits[i] = visits;
 }
 
+// rt_rect_frusta's 24 floats per rect (rt_hull_corners.hpp), the root box from the frame descriptor
+__global__ __launch_bounds__(256) void k_rect_frusta(const DevFrame *fr, rthull::RectCam cam, const float *rects, int stride, uint32_t n, float tNear, float tFar,
+                                                     float *corners) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float far = rthull::rect_far(cam, ld3(fr->sc.rootMin), ld3(fr->sc.rootMax), tNear, tFar);
+    rthull::rect_frustum(cam, rects + (size_t)i * stride, tNear, far, corners + (size_t)i * 24);
+}
+
 template <class Shape>
 void launch(hipStream_t st, int treeDepth, DevFrame *dFrame, const OverlapQuery &q) {
     const int stackEntries = rt_query_stack_entries(treeDepth);
@@ -99,9 +109,17 @@ void launch(hipStream_t st, int treeDepth, DevFrame *dFrame, const OverlapQuery 
 
 using namespace rtd;
 
-hipError_t rt_overlap_launch(OverlapShape shape, hipStream_t st, int treeDepth, DevFrame *dFrame, const DevScene &sc, const OverlapQuery &q) {
-    rt_query_prep(st, dFrame, sc);
-    if (shape == RT_OVERLAP_TRI) launch<rtoverlap::TriShape>(st, treeDepth, dFrame, q);
+hipError_t rt_overlap_launch(OverlapShape shape, hipStream_t st, int treeDepth, DevFrame *dFrame, const DevScene &sc, const OverlapQuery &q, bool prepared) {
+    if (!prepared) rt_query_prep(st, dFrame, sc);
+    if (shape == RT_OVERLAP_HULL) launch<rtoverlap::HullShape>(st, treeDepth, dFrame, q);
+    else if (shape == RT_OVERLAP_TRI) launch<rtoverlap::TriShape>(st, treeDepth, dFrame, q);
     else launch<rtoverlap::BoxShape>(st, treeDepth, dFrame, q);
+    return hipGetLastError();
+}
+
+hipError_t rt_rect_frusta_launch(hipStream_t st, DevFrame *dFrame, const DevScene &sc, const rthull::RectCam &cam, const float *rects, int stride, uint32_t n,
+                                 float tNear, float tFar, float *corners) {
+    rt_query_prep(st, dFrame, sc);
+    hipLaunchKernelGGL(k_rect_frusta, dim3((n + 255u) / 256u), dim3(256), 0, st, (const DevFrame *)dFrame, cam, rects, stride, n, tNear, tFar, corners);
     return hipGetLastError();
 }

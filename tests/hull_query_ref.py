@@ -1,0 +1,615 @@
+"""The hull query's definition restated in numpy float32, independent of the library's C++: the 46-axis separating-axis test with every
+fmaf of 26.1 through analytic_ref.fma32, over all (query, row) pairs and each axis's verdict kept apart (the 43 projected axes are evaluated on the
+pairs the three box axes do not part: the others are rejected whatever they say, and their rows of `sep` stay False); the node test (box overlap and
+the six face normals) and an explicit right-first walk for order and `visits`; the path mask, computed separately.  Also a float64 43-axis test, a
+float64 clipping test that knows nothing of axes (the triangle clipped by the six inward half-spaces), the corner makers in numpy float32, and the
+query sets the hull tests share (meshes: nearest_ref.MESHES)."""
+import functools
+
+import numpy as np
+
+import analytic_ref as ar
+import nearest_ref
+import opengl_raytracing_amd as rt
+
+f32 = np.float32
+MESHES = nearest_ref.MESHES
+mesh = nearest_ref.mesh
+_idx = nearest_ref._idx
+FACES = ((0, 2, 4, 6), (1, 3, 5, 7), (0, 1, 4, 5), (2, 3, 6, 7), (0, 1, 2, 3), (4, 5, 6, 7))
+EDGES = ((0, 1), (2, 3), (4, 5), (6, 7), (0, 2), (1, 3), (4, 6), (5, 7), (0, 4), (1, 5), (2, 6), (3, 7))
+# the 43 projected axes, in the order of Sat.sep[3:]
+AXES = tuple(f"face {''.join(map(str, f))}" for f in FACES) + ("n",) + tuple(f"f{i + 1} x d{a}{b}" for (a, b) in EDGES for i in range(3))
+
+
+def _sub(a, b):
+    with np.errstate(all="ignore"):
+        return (a - b).astype(f32)
+
+
+def _mul(a, b):
+    with np.errstate(all="ignore"):
+        return (a * b).astype(f32)
+
+
+def _add(a, b):
+    with np.errstate(all="ignore"):
+        return (a + b).astype(f32)
+
+
+def _min3(a, b, c):
+    return np.fmin(np.fmin(a, b), c)                       # a NaN operand is ignored
+
+
+def _max3(a, b, c):
+    return np.fmax(np.fmax(a, b), c)
+
+
+def corners(q24):
+    """[N,8,3] float32 of queries [N,k], k >= 24."""
+    return np.ascontiguousarray(np.asarray(q24)[:, :24], f32).reshape(-1, 8, 3)
+
+
+def live(q24):
+    """[N] bool: none of the 24 floats is a NaN."""
+    return ~np.isnan(np.asarray(q24)[:, :24]).any(1)
+
+
+def aabb(q24):
+    """[N,6] float32: lo, hi -- the fmin / fmax of the eight corners per component."""
+    c = corners(q24)
+    return np.concatenate([np.fmin.reduce(c, 1), np.fmax.reduce(c, 1)], 1)
+
+
+def row_points(tris12):
+    """a, b, c of every row: one rounded add per component."""
+    t = np.asarray(tris12, f32)
+    return t[:, 0:3], _add(t[:, 0:3], t[:, 4:7]), _add(t[:, 0:3], t[:, 8:11])
+
+
+def boxes_overlap(bmin, bmax, lo, hi):
+    """Closed boxes [M,3] against queries [N,3] -> [N,M]: comparisons only."""
+    with np.errstate(all="ignore"):
+        return (~(bmax[None] < lo[:, None]) & ~(hi[:, None] < bmin[None])).all(-1)
+
+
+def normals(c):
+    """The six face normals [N,6,3] of corners [N,8,3]: the cross product of each face's diagonals."""
+    with np.errstate(all="ignore"):
+        return np.stack([ar.cross(_sub(c[:, d], c[:, a]), _sub(c[:, cc], c[:, b])) for (a, b, cc, d) in FACES], 1)
+
+
+def hull_interval(ax, c):
+    """ax [...,3] against corners [...,8,3] -> (hmin, hmax): all eight through dot; NaN -- an interval that never separates -- unless the float32
+    sum ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)) is finite: an inf or a NaN among the projections stays in it."""
+    with np.errstate(all="ignore"):
+        p = np.stack([ar.dot(ax, c[..., k, :]) for k in range(8)], -1)
+        ok = np.isfinite(_add(_add(_add(p[..., 0], p[..., 1]), _add(p[..., 2], p[..., 3])), _add(_add(p[..., 4], p[..., 5]), _add(p[..., 6], p[..., 7]))))
+    return np.where(ok, np.fmin.reduce(p, -1), f32(np.nan)), np.where(ok, np.fmax.reduce(p, -1), f32(np.nan))
+
+
+def box_interval(n, lo, hi):
+    """The box's corners through dot's own three steps, the least and the greatest kept at each."""
+    with np.errstate(all="ignore"):
+        lx, hx = _mul(n[..., 0], lo[..., 0]), _mul(n[..., 0], hi[..., 0])
+        mx, Mx = np.fmin(lx, hx), np.fmax(lx, hx)
+        my = np.fmin(ar.fma32(n[..., 1], lo[..., 1], mx), ar.fma32(n[..., 1], hi[..., 1], mx))
+        My = np.fmax(ar.fma32(n[..., 1], lo[..., 1], Mx), ar.fma32(n[..., 1], hi[..., 1], Mx))
+        return (np.fmin(ar.fma32(n[..., 2], lo[..., 2], my), ar.fma32(n[..., 2], hi[..., 2], my)),
+                np.fmax(ar.fma32(n[..., 2], lo[..., 2], My), ar.fma32(n[..., 2], hi[..., 2], My)))
+
+
+def node_test(bmin, bmax, q24):
+    """[N,M] bool: node boxes [M,3] that query i enters -- the box overlaps [lo, hi] and none of the six face normals parts it from the hull -- and
+    [N,M] bool: the boxes a face normal parts although they overlap [lo, hi]."""
+    c = corners(q24)
+    box = aabb(q24)
+    ov = boxes_overlap(bmin, bmax, box[:, 0:3], box[:, 3:6])
+    nrm = normals(c)
+    sep = np.zeros_like(ov)
+    with np.errstate(all="ignore"):
+        for k in range(6):
+            hmin, hmax = hull_interval(nrm[:, k], c)
+            lo, hi = box_interval(nrm[:, None, k], bmin[None], bmax[None])
+            finite = (lo >= -LIMIT) & (hi <= LIMIT) & (bmin >= -LIMIT).all(-1)[None] & (bmax <= LIMIT).all(-1)[None]       # (a NaN fails these)
+            sep |= ((hi < hmin[:, None]) | (hmax[:, None] < lo)) & finite
+    alive = live(q24)[:, None]
+    return ov & ~sep & alive, ov & sep & alive
+
+
+def pair_axes(tris12, q24):
+    """The 43 projected axes of pairs: rows [P,12] against hulls [P,24] -> [43,P] bool, whether each axis separates.  A NaN never does."""
+    t = np.asarray(tris12, f32)
+    c = corners(q24)
+    e1, e2 = t[:, 4:7], t[:, 8:11]
+    T = row_points(t)
+    out = []
+
+    def sep(ax, hmin=None, hmax=None):
+        with np.errstate(all="ignore"):
+            if hmin is None:
+                hmin, hmax = hull_interval(ax, c)
+            p = [ar.dot(ax, v) for v in T]
+            finite = np.isfinite(_add(_add(p[0], p[1]), p[2]))                                  # only projections with a finite sum separate
+            return ((_max3(*p) < hmin) | (hmax < _min3(*p))) & finite
+
+    with np.errstate(all="ignore"):
+        nrm = normals(c)
+        for k in range(6):
+            out.append(sep(nrm[:, k], *hull_interval(nrm[:, k], c)))
+        out.append(sep(ar.cross(e1, e2)))
+        f = (e1, _sub(e2, e1), e2)
+        for (i, j) in EDGES:
+            d = _sub(c[:, j], c[:, i])
+            for fi in f:
+                out.append(sep(ar.cross(fi, d)))
+    return np.stack(out)
+
+
+class Sat:
+    """The row test of 26.1 for queries [N,24] against every row [T,12]: sep [46,N,T] bool -- whether the box axes x, y, z and the 43 projected axes
+    (AXES) separate, the latter evaluated where no box axis does and the query is live, False elsewhere -- and accept [N,T], no axis separating and
+    the query live."""
+
+    def __init__(self, tris12, q24):
+        tris12, q24 = np.asarray(tris12, f32), np.ascontiguousarray(np.asarray(q24)[:, :24], f32)
+        a, b, c = row_points(tris12)
+        box = aabb(q24)
+        lo, hi = box[:, 0:3], box[:, 3:6]
+        N, Tn = q24.shape[0], tris12.shape[0]
+        self.live = live(q24)
+        self.sep = np.zeros((46, N, Tn), bool)
+        with np.errstate(all="ignore"):
+            tmin, tmax = _min3(a, b, c), _max3(a, b, c)
+            for k in range(3):
+                self.sep[k] = (tmax[None, :, k] < lo[:, None, k]) | (hi[:, None, k] < tmin[None, :, k])
+        self.box_ok = ~self.sep[:3].any(0) & self.live[:, None]
+        qi, ti = np.nonzero(self.box_ok)
+        for s in range(0, qi.size, 1 << 17):
+            sl = slice(s, s + (1 << 17))
+            self.sep[3:, qi[sl], ti[sl]] = pair_axes(tris12[ti[sl]], q24[qi[sl]])
+        self.accept = self.box_ok & ~self.sep[3:].any(0)
+
+
+class Walk:
+    """An explicit depth-first walk of nodes12 for all queries at once, the right child before the left: `order` [T], the rows in the order the walk
+    of a query that enters everything meets them; path [N,T] bool, every node from the root to the row's leaf passes the node test; visits [N], the
+    boxes tested: 1 + twice the inner nodes entered, 0 for an empty slot; culled [N,M], the nodes a face normal rejected although their boxes overlap
+    [lo, hi] and the walk reached them."""
+
+    def __init__(self, nodes12, n_tris, q24):
+        nodes12 = np.asarray(nodes12, f32)
+        N = np.asarray(q24).shape[0]
+        alive = live(q24)
+        enter, by_normal = node_test(nodes12[:, 0:3], nodes12[:, 4:7], q24)
+        self.path = np.zeros((N, n_tris), bool)
+        self.visits = alive.astype(np.int32)               # the root box
+        self.culled = np.zeros_like(by_normal)
+        self.culled[:, 0] = by_normal[:, 0]
+        order = []
+        stack = [(0, enter[:, 0])]
+        while stack:
+            ni, entered = stack.pop()
+            count = _idx(nodes12[ni, 9])
+            if count > 0:
+                first = _idx(nodes12[ni, 8])
+                order.extend(range(first, first + count))
+                self.path[:, first:first + count] = entered[:, None]
+            else:
+                self.visits += 2 * entered.astype(np.int32)
+                l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
+                self.culled[:, l] = entered & by_normal[:, l]
+                self.culled[:, r] = entered & by_normal[:, r]
+                stack.append((l, entered & enter[:, l]))
+                stack.append((r, entered & enter[:, r]))      # popped first
+        self.order = np.array(order, np.int64)
+
+
+class Answer:
+    """The definition's answer for queries against (nodes12, tris12): sat, walk, accepted = sat.accept & walk.path [N,T], count [N] int32, and lists --
+    lists[i] the accepted rows of query i in walk order (int32 arrays)."""
+
+    def __init__(self, nodes12, tris12, q24):
+        self.sat = Sat(tris12, q24)
+        self.walk = Walk(nodes12, tris12.shape[0], q24)
+        self.accepted = self.sat.accept & self.walk.path
+        self.count = self.accepted.sum(1).astype(np.int32)
+        in_order = self.accepted[:, self.walk.order]
+        self.lists = [self.walk.order[in_order[i]].astype(np.int32) for i in range(np.asarray(q24).shape[0])]
+        self.visits = self.walk.visits
+
+    def offsets(self):
+        return np.concatenate([[0], np.cumsum(self.count)]).astype(np.int32)
+
+    def filled(self, offsets=None, cap=None, sentinel=-77):
+        """What a call leaves of a prims array pre-filled with `sentinel`: slot i (offsets, or i * cap) holds the first min(capacity, count) rows."""
+        n = len(self.lists)
+        if offsets is None:
+            offsets = (np.arange(n + 1, dtype=np.int64) * cap)
+        out = np.full(int(max(offsets[-1], 0)), sentinel, np.int32)
+        for i, rows in enumerate(self.lists):
+            room = max(int(offsets[i + 1]) - int(offsets[i]), 0)
+            k = min(room, rows.size)
+            out[int(offsets[i]):int(offsets[i]) + k] = rows[:k]
+        return out
+
+    def pairs(self):
+        return np.array([(i, t) for i, rows in enumerate(self.lists) for t in rows], np.int32).reshape(-1, 2)
+
+
+def box_visits(nodes12, q24):
+    """[N] int32: the visits of the box query on the hulls' [lo, hi] -- the walk without the six normals."""
+    nodes12 = np.asarray(nodes12, f32)
+    box = aabb(q24)
+    alive = live(q24)
+    ov = boxes_overlap(nodes12[:, 0:3], nodes12[:, 4:7], box[:, 0:3], box[:, 3:6]) & alive[:, None]
+    visits = alive.astype(np.int32)
+    stack = [(0, ov[:, 0])]
+    while stack:
+        ni, entered = stack.pop()
+        if _idx(nodes12[ni, 9]) > 0:
+            continue
+        visits += 2 * entered.astype(np.int32)
+        l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
+        stack.append((l, entered & ov[:, l]))
+        stack.append((r, entered & ov[:, r]))
+    return visits
+
+
+# ---------------------------------------------------------------- float64: the 43 axes, and clipping
+
+def pair_sat64(tris12, q24):
+    """[P] bool for pairs: the box axes and the 43 projected axes in float64 on the float64 points; edges and normals from float64 differences.  A NaN
+    never separates; dead queries accept nothing."""
+    t, c = np.asarray(tris12, np.float64), corners(q24).astype(np.float64)
+    a = t[:, 0:3]
+    b, cc = a + t[:, 4:7], a + t[:, 8:11]
+    with np.errstate(all="ignore"):
+        lo, hi = np.fmin.reduce(c, 1), np.fmax.reduce(c, 1)
+        sep = ((_max3(a, b, cc) < lo) | (hi < _min3(a, b, cc))).any(-1)
+        f = (b - a, cc - b, cc - a)
+        axes = [np.cross(c[:, d] - c[:, p], c[:, r] - c[:, q]) for (p, q, r, d) in FACES] + [np.cross(f[0], f[2])]
+        axes += [np.cross(fi, c[:, j] - c[:, i]) for (i, j) in EDGES for fi in f]
+        for ax in axes:
+            tp = [(ax * v).sum(-1) for v in (a, b, cc)]
+            hp = (ax[:, None, :] * c).sum(-1)
+            sep = sep | (_max3(*tp) < np.fmin.reduce(hp, 1)) | (np.fmax.reduce(hp, 1) < _min3(*tp))
+    return ~sep & live(q24)
+
+
+def pair_clip64(tris12, q24):
+    """[P] bool for pairs of finite hulls and rows: the float64 triangle a, a + e1, a + e2 clipped (Sutherland-Hodgman) by the six closed half-spaces
+    of the hull's faces is not empty.  A face's plane has the normal of its diagonals and passes through the mean of its four corners; the inside is
+    the side of the mean of all eight; a collapsed face (zero normal) bounds nothing.  No axis table enters."""
+    t, c = np.asarray(tris12, np.float64), corners(q24).astype(np.float64)
+    out = np.zeros(t.shape[0], bool)
+    for p in range(t.shape[0]):
+        poly = [t[p, 0:3], t[p, 0:3] + t[p, 4:7], t[p, 0:3] + t[p, 8:11]]
+        centre = c[p].mean(0)
+        for (i, j, k, l) in FACES:
+            n = np.cross(c[p, l] - c[p, i], c[p, k] - c[p, j])
+            if not n.any():
+                continue
+            off = n @ (c[p, i] + c[p, j] + c[p, k] + c[p, l]) / 4
+            if n @ centre < off:
+                n, off = -n, -off
+            d = [n @ v - off for v in poly]
+            nxt = []
+            for m in range(len(poly)):
+                v0, v1, d0, d1 = poly[m], poly[(m + 1) % len(poly)], d[m], d[(m + 1) % len(poly)]
+                if d0 >= 0:
+                    nxt.append(v0)
+                if (d0 < 0) != (d1 < 0) and d0 != d1:
+                    nxt.append(v0 + (v1 - v0) * (d0 / (d0 - d1)))
+            poly = nxt
+            if not poly:
+                break
+        out[p] = bool(poly)
+    return out
+
+
+# ---------------------------------------------------------------- the corner makers in numpy float32
+
+def box_corners(boxes, M=None):
+    """rt_box_corners: [N,24] float32.  M: None, [16] or [N,16], column-major."""
+    b = np.asarray(boxes, f32)[:, :6]
+    n = b.shape[0]
+    out = np.zeros((n, 8, 3), f32)
+    m = None if M is None else np.broadcast_to(np.asarray(M, f32).reshape(-1, 16), (n, 16))
+    with np.errstate(all="ignore"):
+        for k in range(8):
+            p = [b[:, 3 + a] if k >> a & 1 else b[:, a] for a in range(3)]
+            for a in range(3):
+                out[:, k, a] = p[a] if m is None else _add(_add(_mul(m[:, a], p[0]), _mul(m[:, 4 + a], p[1])), _add(_mul(m[:, 8 + a], p[2]), _mul(m[:, 12 + a], f32(1))))
+        empty = ~((b[:, 0] <= b[:, 3]) & (b[:, 1] <= b[:, 4]) & (b[:, 2] <= b[:, 5]))
+    out[empty] = np.nan
+    return out.reshape(n, 24)
+
+
+def scene_far(u, root_min, root_max, t_near):
+    lo, hi = np.asarray(root_min, f32), np.asarray(root_max, f32)
+    fwd, pos = np.array(list(u.camFwd), f32), np.array(list(u.camPos), f32)
+    pts = np.array([[hi[a] if k >> a & 1 else lo[a] for a in range(3)] for k in range(8)], f32)
+    with np.errstate(all="ignore"):
+        s = np.fmax.reduce(ar.dot(np.broadcast_to(fwd, pts.shape), _sub(pts, pos)))
+        return np.fmax(ar.fma32(np.abs(s), f32(2.0 ** -10), s), f32(t_near)).astype(f32)
+
+
+def rect_frusta(u, root_min, root_max, rects, t_near=0.0, t_far=None):
+    """rt_rect_frusta: [N,24] float32."""
+    r = np.asarray(rects, f32)[:, :4]
+    n = r.shape[0]
+    tn = f32(t_near)
+    far = scene_far(u, root_min, root_max, tn) if t_far is None or t_far < 0 else np.fmax(f32(t_far), tn)
+    jit = u.enableJitter == 1
+    jx, jy = (f32(u.jitter[0]), f32(u.jitter[1])) if jit else (f32(0), f32(0))
+    sx, sy = _mul(f32(u.tanHalfFov), f32(u.aspect)), f32(u.tanHalfFov)
+    right, up, fwd, pos = (np.array(list(v), f32) for v in (u.camRight, u.camUp, u.camFwd, u.camPos))
+    out = np.zeros((n, 8, 3), f32)
+    with np.errstate(all="ignore"):
+        for k in range(8):
+            fx, fy = r[:, 2] if k & 1 else r[:, 0], r[:, 3] if k & 2 else r[:, 1]
+            t = far if k & 4 else tn
+            nx = _sub(_mul((_add(fx, jx) / f32(u.resolution[0])).astype(f32), f32(2)), f32(1))
+            ny = _sub(_mul((_add(fy, jy) / f32(u.resolution[1])).astype(f32), f32(2)), f32(1))
+            for a in range(3):
+                d = _add(_add(fwd[a], _mul(_mul(nx, right[a]), sx)), _mul(_mul(ny, up[a]), sy))
+                out[:, k, a] = ar.fma32(d, np.broadcast_to(f32(t), d.shape), np.broadcast_to(pos[a], d.shape))
+        empty = ~((r[:, 0] <= r[:, 2]) & (r[:, 1] <= r[:, 3]))
+    out[empty] = np.nan
+    return out.reshape(n, 24)
+
+
+def camera(eye, target, w, h, tan_half_fov=0.5, jitter=None, up=(0.0, 1.0, 0.0)):
+    """An RtUniforms with the camera fields alone: at `eye`, looking at `target`."""
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, np.asarray(up, np.float64))
+    right /= np.linalg.norm(right)
+    upv = np.cross(right, fwd)
+    u = rt.RtUniforms()
+    for name, v in (("camPos", eye), ("camRight", right), ("camUp", upv), ("camFwd", fwd)):
+        for a in range(3):
+            getattr(u, name)[a] = float(f32(v[a]))
+    u.tanHalfFov, u.aspect = float(tan_half_fov), float(f32(w / h))
+    u.resolution[0], u.resolution[1] = float(w), float(h)
+    if jitter is not None:
+        u.enableJitter, u.jitter[0], u.jitter[1] = 1, float(jitter[0]), float(jitter[1])
+    return u
+
+
+# ---------------------------------------------------------------- the query sets the tests share
+
+def _leaves(nodes):
+    return np.array([k for k in range(nodes.shape[0]) if _idx(nodes[k, 9]) > 0])
+
+
+def _rotation(rng):
+    q = rng.normal(size=4)
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+CUBE = np.array([[1.0 if k >> a & 1 else -1.0 for a in range(3)] for k in range(8)])
+
+
+def generic_hexahedra(rng, centre, size):
+    """[M,24] float64: projective images of the cube [-1, 1]^3 about `centre` [M,3] of about `size` [M]: x = (A s + t) / (1 + w . s) with a random
+    well-conditioned A and |w|_1 <= 0.6, so that the image is a convex hexahedron with planar faces and no two edges parallel."""
+    m = centre.shape[0]
+    out = np.zeros((m, 8, 3))
+    for i in range(m):
+        A = _rotation(rng) @ np.diag(rng.uniform(0.4, 1.0, 3)) @ (np.eye(3) + 0.4 * rng.uniform(-1, 1, (3, 3)))
+        w = rng.uniform(-1, 1, 3)
+        w *= rng.uniform(0.1, 0.6) / np.abs(w).sum()
+        out[i] = centre[i] + size[i] * (CUBE @ A.T) / (1 + CUBE @ w)[:, None]
+    return out.reshape(m, 24)
+
+
+LIMIT = f32(1e38)                                      # a node's box and its interval on a normal count within +-LIMIT only
+HUGE = 1e19                                            # an extent from which the cross product of two diagonals overflows float32
+
+
+def huge_turned(rng, mid, m):
+    """[m,24] float64: boxes of half-extent S = 2^61 .. 2^95 under a rotation, placed so that the point `mid` lies deep inside (the centre at mid, or
+    0.875 S or nearly S off it), or outside.  Their face normals are of the order S^2 and overflow float32, so dot() gives inf for some points and
+    NaN (inf - inf, inf * 0) for others; every third is turned about z alone by a matrix exact in float32, which leaves zeros in the axes."""
+    out = np.zeros((m, 8, 3))
+    for i in range(m):
+        S = 2.0 ** rng.integers(61, 96)
+        R = _rotation(rng)
+        if i % 3 == 0:
+            R = np.array([[0.5, -0.75, 0.0], [0.75, 0.5, 0.0], [0.0, 0.0, 1.0]])           # (not normalised: a scaled box is a hull too)
+        off = (0.0, -1.0 + 2.0 ** -20, -0.875, 0.5, -1.5, 1.0 - 2.0 ** -20)[i % 6]
+        out[i] = mid + R[:, 0] * S * off + (CUBE * S) @ R.T
+    return out.reshape(m, 24)
+
+
+def _matrix(rng, kind, centre):
+    """A column-major model matrix [16] that takes a box about the origin to an oriented (kind 0), sheared (1) or axis-aligned (2) box about centre."""
+    L = np.eye(3) if kind == 2 else _rotation(rng)
+    if kind == 1:
+        L = L @ (np.eye(3) + 0.5 * np.triu(rng.uniform(-1, 1, (3, 3)), 1))
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = L, centre
+    return M.T.reshape(16)
+
+
+def _directed(tris12, rng, rows, per_row, keep, ext):
+    """Hulls that ONE projected axis alone parts from one row, their boxes overlapping: generic hexahedra and sheared boxes of about the row's size at a
+    small gap from it, judged by the definition above on the (candidate, row) pair alone, at most `keep` kept per axis."""
+    T = tris12.shape[0]
+    kept = [[] for _ in AXES]
+    a, b, c = (v.astype(np.float64) for v in row_points(tris12))
+    for t in rng.integers(0, T, rows):
+        size = max(np.linalg.norm(b[t] - a[t]), np.linalg.norm(c[t] - a[t]), np.linalg.norm(c[t] - b[t]), 1e-3 * ext)
+        wts = rng.dirichlet((1, 1, 1), per_row)
+        at = wts[:, 0:1] * a[t] + wts[:, 1:2] * b[t] + wts[:, 2:3] * c[t]
+        d = rng.normal(size=(per_row, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        sz = size * rng.uniform(0.2, 1.5, per_row)
+        cand = generic_hexahedra(rng, at + d * (sz * rng.uniform(0.6, 1.6, per_row))[:, None], sz).astype(f32)
+        rows12 = np.repeat(tris12[t:t + 1], per_row, 0)
+        box = aabb(cand)
+        ta, tb, tc = row_points(rows12)
+        with np.errstate(all="ignore"):
+            box_ok = ~((_max3(ta, tb, tc) < box[:, 0:3]) | (box[:, 3:6] < _min3(ta, tb, tc))).any(1)
+        s = pair_axes(rows12, cand)
+        alone = box_ok & (s.sum(0) == 1)
+        for k in range(len(AXES)):
+            for j in np.flatnonzero(alone & s[k]):
+                if len(kept[k]) < keep:
+                    kept[k].append(cand[j])
+    return np.array([q for axis in kept for q in axis], f32).reshape(-1, 24), [len(k) for k in kept]
+
+
+def view(name, w=48, h=36, jitter=None):
+    """An RtUniforms (camera fields alone) looking at the mesh from outside its root box."""
+    nodes, _ = mesh(name)
+    lo, hi = nodes[0, 0:3].astype(np.float64), nodes[0, 4:7].astype(np.float64)
+    mid, ext = (lo + hi) / 2, float(max((hi - lo).max(), 1e-3))
+    return camera(mid + np.array([0.9, 0.7, 1.6]) * ext, mid + np.array([0.05, -0.02, 0.0]) * ext, w, h, 0.45, jitter)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(nodes12, tris12, hulls [N,24]) with N >= 2 049, seeded: rect frusta of view(name) -- rects of a pixel, a tile, the frame and off the frame --;
+    pyramids with tNear = 0; oriented, sheared and axis-aligned boxes about and inside the mesh (box_corners under a matrix, and under none); generic
+    hexahedra; hulls that share one corner bit for bit with a row point a, b or c; hulls collapsed to a point, a segment and a quad; hulls whose
+    [lo, hi] is flush with a leaf box; +-inf, 3e38 and far-away hulls; turned boxes 2^62 to 2^96 across, whose normals and edge products overflow
+    (huge_turned); hulls one axis alone parts from a row (_directed); every 97th query an empty
+    slot, the NaN rotating through the 24 floats."""
+    nodes, tris = mesh(name)
+    rng = np.random.default_rng(26 + len(name))
+    a, b, c = row_points(tris)
+    T = tris.shape[0]
+    lo, hi = nodes[0, 0:3].astype(np.float64), nodes[0, 4:7].astype(np.float64)
+    ext = np.maximum(hi - lo, 1e-3 * float((hi - lo).max()))
+    big, mid = float(ext.max()), (lo + hi) * 0.5
+    Qs = []
+
+    def surface(m):
+        k = rng.integers(0, T, m)
+        w = rng.dirichlet((1, 1, 1), m)
+        return a[k] * w[:, 0:1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:3], k
+
+    # rect frusta and pyramids
+    W, H = 48, 36
+    for jitter, t_near, t_far, m in ((None, 0.05 * big, None, 160), ((0.31, -0.22), 0.3 * big, 2.5 * big, 120), (None, 0.0, None, 160)):
+        u = view(name, W, H, jitter)
+        x0, y0 = rng.uniform(-4, W + 2, m), rng.uniform(-4, H + 2, m)
+        side = np.where(rng.random(m) < 0.5, 1.0, rng.choice([4.0, 8.0, 16.0], m))
+        rects = np.stack([x0, y0, x0 + side, y0 + side * rng.uniform(0.5, 1.5, m)], 1)
+        rects[:m // 4, :2] = np.floor(rects[:m // 4, :2])                      # whole pixels
+        rects[:m // 4, 2:] = rects[:m // 4, :2] + 1
+        rects[-6:] = [[0, 0, W, H], [-W, 0, 0, H], [2 * W, 0, 3 * W, H], [0, -H, W, 0], [5, 7, 5, 7], [10, 3, 10, 20]]
+        Qs.append(rect_frusta(u, nodes[0, 0:3], nodes[0, 4:7], rects.astype(f32), t_near, t_far))
+    # oriented, sheared and axis-aligned boxes about surface points and inside the root box
+    m = 420
+    at, _ = surface(m)
+    at = np.where(rng.random((m, 1)) < 0.3, rng.uniform(lo, hi, (m, 3)), at)
+    half = ext * 2.0 ** -rng.integers(1, 9, (m, 1)) * rng.uniform(0.3, 1.0, (m, 3))
+    Ms = np.stack([_matrix(rng, int(k), at[i]) for i, k in enumerate(rng.integers(0, 3, m))]).astype(f32)
+    obj = np.concatenate([-half, half], 1).astype(f32)
+    Qs.append(box_corners(obj, Ms))
+    world = np.concatenate([at - half, at + half], 1).astype(f32)[:80]
+    Qs.append(box_corners(world))                                               # under no matrix: copies
+    # generic hexahedra
+    m = 320
+    at, _ = surface(m)
+    Qs.append(generic_hexahedra(rng, at + rng.normal(size=(m, 3)) * ext * 0.05, big * 2.0 ** -rng.uniform(0.5, 8, m)))
+    # one corner shared bit for bit with a row point: a sheared box grown from that corner
+    m = 160
+    k = rng.integers(0, T, m)
+    shared = np.stack([a, b, c], 1)[k, rng.integers(0, 3, m)]
+    hull = np.zeros((m, 8, 3), f32)
+    for i in range(m):
+        vec = (_rotation(rng) @ (np.eye(3) + 0.3 * rng.uniform(-1, 1, (3, 3)))).T * (big * 2.0 ** -rng.uniform(2, 9, (3, 1)))
+        kk = int(rng.integers(0, 8))
+        for j in range(8):
+            hull[i, j] = (shared[i].astype(np.float64) + sum(vec[bit] for bit in range(3) if (j ^ kk) >> bit & 1)).astype(f32) if j != kk else shared[i]
+    Qs.append(hull.reshape(m, 24))
+    # collapsed: a point (at a vertex, on a face as rounded, elsewhere), a segment (bit 2 picks the end), a quad (bit 2 ignored)
+    k = rng.integers(0, T, 50)
+    Qs.append(np.tile(np.stack([a, b, c], 1)[k, rng.integers(0, 3, 50)], (1, 8)))
+    at, _ = surface(40)
+    Qs.append(np.tile(at.astype(f32), (1, 8)))
+    Qs.append(np.tile(rng.uniform(lo, hi, (20, 3)), (1, 8)))
+    at, k = surface(50)
+    nrm = np.cross((b[k] - a[k]).astype(np.float64), (c[k] - a[k]).astype(np.float64))
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
+    h = big * 2.0 ** -rng.integers(2, 10, (50, 1))
+    Qs.append(np.concatenate([np.tile(at + nrm * h, (1, 4)), np.tile(at - nrm * h, (1, 4))], 1))      # a segment piercing a face
+    quad = generic_hexahedra(rng, surface(50)[0] + rng.normal(size=(50, 3)) * ext * 0.02, big * 2.0 ** -rng.uniform(1, 7, 50)).reshape(50, 8, 3)
+    quad[:, 4:] = quad[:, :4]
+    Qs.append(quad.reshape(50, 24))
+    # [lo, hi] flush with a leaf box: an axis-aligned hull that ends exactly where the leaf box begins, or begins where it ends
+    leaves = _leaves(nodes)
+    kl = leaves[rng.integers(0, leaves.size, 160)]
+    llo, lhi = nodes[kl, 0:3].astype(np.float64), nodes[kl, 4:7].astype(np.float64)
+    span = np.maximum(lhi - llo, 0.02 * ext)
+    blo = rng.uniform(llo - 0.3 * span, lhi, (160, 3)).astype(f32)
+    bhi = (blo + rng.uniform(0.05, 1.0, (160, 3)) * span).astype(f32)
+    ax, below, rows = rng.integers(0, 3, 160), rng.random(160) < 0.5, np.arange(160)
+    face = np.where(below, nodes[kl, ax], nodes[kl, 4 + ax]).astype(f32)
+    blo[rows, ax] = np.where(below, face - span[rows, ax].astype(f32) * f32(0.25), face)
+    bhi[rows, ax] = np.where(below, face, face + span[rows, ax].astype(f32) * f32(0.25))
+    Qs.append(box_corners(np.concatenate([blo, bhi], 1)))
+    inf = np.inf
+    everything = box_corners(np.array([[-inf] * 3 + [inf] * 3, [-3e38] * 3 + [3e38] * 3, [-1e30] * 3 + [1e30] * 3, [lo[0], lo[1], lo[2], inf, inf, inf],
+                                       [-inf, mid[1], mid[2], inf, mid[1], mid[2]], [3e38] * 6, [inf] * 6, [-inf] * 6, [-1e20, lo[1], mid[2], 1e20, mid[1], 1e20]], f32))
+    Qs.append(everything)
+    odd = generic_hexahedra(rng, np.tile(mid, (4, 1)), np.full(4, big))
+    odd[0, 0], odd[1, 13], odd[2, 23], odd[3, 5] = inf, -inf, 3e38, -3e38
+    Qs.append(odd)
+    Qs.append(huge_turned(rng, mid, 48))
+    dirs = rng.normal(size=(100, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    Qs.append(generic_hexahedra(rng, mid + dirs * big * 10.0 ** rng.uniform(0.5, 3.0, (100, 1)), np.full(100, 0.2 * big)))          # far away
+    Qs.append(_directed(tris, rng, rows=24, per_row=400, keep=3, ext=big)[0])
+    q = np.concatenate([np.asarray(x, np.float64).reshape(-1, 24) for x in Qs]).astype(f32)
+    if q.shape[0] < 2049:
+        extra = 2049 - q.shape[0]
+        at, _ = surface(extra)
+        q = np.concatenate([q, generic_hexahedra(rng, at, big * 2.0 ** -rng.uniform(1, 9, extra)).astype(f32)])
+    q = np.ascontiguousarray(q[rng.permutation(q.shape[0])])
+    empty = np.arange(0, q.shape[0], 97)
+    q[empty, np.arange(empty.size) % 24] = np.nan                     # every 97th query an empty slot, the NaN rotating through the 24 floats
+    q.setflags(write=False)
+    return nodes, tris, q
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """The numpy definition's Answer on case(name).  Computed once; leave it unchanged."""
+    nodes, tris, q = case(name)
+    return Answer(nodes, tris, q)
+
+
+@functools.lru_cache(maxsize=None)
+def walk(name):
+    """The reference Walk alone on case(name): order, path and visits without the row test.  Computed once; leave it unchanged."""
+    nodes, tris, q = case(name)
+    return Walk(nodes, tris.shape[0], q)
+
+
+GENERIC_SEED = 2605
+
+
+@functools.lru_cache(maxsize=None)
+def generic_pairs(seed=GENERIC_SEED, m=6000):
+    """(rows [m,12], hulls [m,24]) float32: the generic set -- random generic hexahedra, frusta-like pyramids and sheared boxes against random
+    triangles in the unit cube, nothing placed to touch."""
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((m, 12), f32)
+    rows[:, 0:3] = rng.uniform(-1, 1, (m, 3))
+    rows[:, 4:7], rows[:, 8:11] = rng.normal(size=(m, 3)) * 0.5, rng.normal(size=(m, 3)) * 0.5
+    centre = rows[:, 0:3].astype(np.float64) + rng.normal(size=(m, 3)) * 0.6
+    hulls = generic_hexahedra(rng, centre, rng.uniform(0.2, 0.8, m)).reshape(m, 8, 3)
+    third = m // 3
+    apex = hulls[:third, :4].mean(1, keepdims=True)                       # pyramids: the near face collapsed to a point
+    hulls[:third, :4] = apex
+    for i in range(third, 2 * third):                                      # sheared boxes
+        hulls[i] = centre[i] + (CUBE * rng.uniform(0.1, 0.6, 3)) @ (_rotation(rng) @ (np.eye(3) + 0.5 * np.triu(rng.uniform(-1, 1, (3, 3)), 1))).T
+    return rows, hulls.reshape(m, 24).astype(f32)

@@ -8,6 +8,7 @@ src/render/render.cpp:55-243).  It never renders on the CPU: every frame goes th
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -1445,6 +1446,14 @@ ASSET_DIR = _PKG_DIR.parent / "assets"
 
 
 # ------------------------------------------------------------------------------------ device side
+def _prim_view(record):
+    """The prim column of RtHit records [...,4] float32 as int32, a view: numpy or torch, as the records are."""
+    if isinstance(record, np.ndarray):
+        return record.view(np.int32)[..., 1]
+    import torch
+    return record.view(torch.int32)[..., 1]
+
+
 class RayHits:
     """Closest-hit answers of Renderer.trace_rays: `record` [N,4] float32 (one RtHit per ray) and views of it -- t [N], prim [N] int32 (row of
     the uploaded tris12, -1 on a miss), uv [N,2] -- plus normal [N,3] when asked for.  numpy arrays or torch tensors, as the rays were."""
@@ -1452,11 +1461,7 @@ class RayHits:
     def __init__(self, record, normal=None):
         self.record = record
         self.t = record[:, 0]
-        if isinstance(record, np.ndarray):
-            self.prim = record.view(np.int32)[:, 1]
-        else:
-            import torch
-            self.prim = record.view(torch.int32)[:, 1]
+        self.prim = _prim_view(record)
         self.uv = record[:, 2:4]
         self.normal = normal
 
@@ -1486,6 +1491,144 @@ def _query_invalid(msg):
     return RtError(RT_ERR_INVALID, f"trace_rays: {msg}")
 
 
+# ---- the checks every query shares: what kind of arrays, their rows, their limits; and the two ways of handing them to C
+def _device_of(index, named, dtype, own=False):
+    """The tensors `named` = ((name, tensor or None), ...) are of `dtype` and on cuda:index -> that device.  own: trace_rays names the argument
+    in its refusals, every later query does not."""
+    import torch
+    dev = torch.device("cuda", index)
+    for name, a in named:
+        if a is None:
+            continue
+        if a.dtype != dtype:
+            raise _query_invalid(f"{name} must be float32, got {a.dtype}" if own else f"expected {dtype}, got {a.dtype}")
+        if a.device != dev:
+            raise _query_invalid(f"{name} is on {a.device}, the context on {dev}" if own else f"a tensor is on {a.device}, the context on {dev}")
+    return dev
+
+
+def _query_arrays(named, ren=None, own=False):
+    """The kind of the float32 arrays of a query, `named` = ((name, array or None), ...) -> None: numpy arrays; a torch device: tensors on it.
+    ren None is a host definition, which takes numpy alone; else the Renderer asked, and the arrays may all be numpy or all torch on its device
+    (read only then: numpy arguments are refused without a context)."""
+    given = [(name, a) for name, a in named if a is not None]
+    if ren is not None and not all(isinstance(a, np.ndarray) for _, a in given):
+        import torch
+        if not all(isinstance(a, torch.Tensor) for _, a in given):
+            names = [name for name, _ in named]
+            raise _query_invalid(f"{', '.join(names[:-1])} and {names[-1]} must all be numpy arrays or all torch tensors" if len(names) > 1 else
+                                 f"{names[0]} must be a numpy array or a torch tensor")
+        return _device_of(ren.device, given, torch.float32, own)
+    for name, a in given:
+        if not isinstance(a, np.ndarray):
+            raise _query_invalid(f"{name} must be a numpy array")
+        if a.dtype != np.float32:
+            raise _query_invalid(f"{name} must be float32, got {a.dtype}")
+    return None
+
+
+def _layout(a):
+    """(shape, itemsize, strides) as _rows takes them: of a numpy array in bytes, of a tensor in elements."""
+    return (a.shape, a.itemsize, a.strides) if isinstance(a, np.ndarray) else (tuple(a.shape), 1, a.stride())
+
+
+# the arrays of query rows: noun, least k, layout words, and the [N,a,b] form: ((a, b), what its a * b floats are) or None
+_BOXES = ("boxes", 6, " (lo.xyz, hi.xyz)", None)
+_QTRIS = ("qtris", 9, " (p0.xyz, p1.xyz, p2.xyz) or [N,3,3]", ((3, 3), "nine floats of a triangle"))
+_HULLS = ("hulls", 24, " (c0.xyz .. c7.xyz) or [N,8,3]", ((8, 3), "24 floats of a hull"))
+_RECTS = ("rects", 4, " (x0, y0, x1, y1)", None)
+
+
+def _rows(noun, k, layout, cell, shape, itemsize, strides, n=None):
+    """The one row check: an array of query rows is [N,j] with j >= k -- or [N,a,b], cell = ((a, b), words), with the a * b floats of a row
+    contiguous --, its floats adjacent within a row and its rows at least k floats apart; n: the row count it must have (dirs) -> the row
+    stride in floats.  A single row has no stride to go by: its length stands in."""
+    shape = tuple(shape)
+    if cell and len(shape) == 3 and shape[1:] == cell[0]:
+        (a, b), words = cell
+        if strides[1] != b * itemsize or strides[2] != itemsize:
+            raise _query_invalid(f"{noun} [N,{a},{b}]: the {words} must be contiguous")
+        shape, strides = (shape[0], a * b), (strides[0], itemsize)
+    if len(shape) != 2 or shape[1] < k:
+        raise _query_invalid(f"{noun} must be [N,k] with k >= {k}{layout}, got shape {shape}")
+    if n is not None and shape[0] != n:
+        raise _query_invalid(f"{noun} has {shape[0]} rows, origins {n}")
+    row, col = strides
+    if col != itemsize or row % itemsize or (shape[0] > 1 and row // itemsize < k):
+        raise _query_invalid(f"{noun} must have unit stride along its last dimension and rows at least {k} floats apart")
+    return max(row // itemsize, k) if shape[0] > 1 else max(shape[1], k)
+
+
+def _row_array(family, a, ren=None):
+    """One array of query rows, family one of _BOXES .. _RECTS: its kind (_query_arrays), then its rows -> (torch device or None, n, row stride)."""
+    dev = _query_arrays(((family[0], a),), ren)
+    if family is _RECTS and dev is None and a.ndim != 2:
+        raise _query_invalid("rects must be [N,k]")          # (numpy rects have words of their own here)
+    return dev, a.shape[0], _rows(*family, *_layout(a))
+
+
+def _limit(name, a, n, dev):
+    """tmax / max_dist: [n]; a numpy array is made contiguous, a tensor must be -> the array to pass, or None."""
+    if a is None:
+        return None
+    if dev is None:
+        if a.shape != (n,):
+            raise _query_invalid(f"{name} must be [{n}], got shape {a.shape}")
+        return np.ascontiguousarray(a)
+    if tuple(a.shape) != (n,) or (n > 1 and a.stride(0) != 1):
+        raise _query_invalid(f"{name} must be a contiguous [{n}] tensor, got shape {tuple(a.shape)}")
+    return a
+
+
+def _ray_check(origins, dirs, tmax, ren=None, own=False):
+    """The checks of Renderer.trace_rays on its rays -> (torch device or None for numpy, n, origin stride, dir stride, tmax to pass)."""
+    dev = _query_arrays((("origins", origins), ("dirs", dirs), ("tmax", tmax)), ren, own)
+    n = origins.shape[0] if len(origins.shape) == 2 else -1
+    os_ = _rows("origins", 3, "", None, *_layout(origins))
+    ds = _rows("dirs", 3, "", None, *_layout(dirs), n)
+    return dev, n, os_, ds, _limit("tmax", tmax, n, dev)
+
+
+def _point_check(points, max_dist, ren=None):
+    """The checks of the nearest-point queries on their points -> (torch device or None for numpy, n, stride, max_dist to pass)."""
+    dev = _query_arrays((("points", points), ("max_dist", max_dist)), ren)
+    stride = _rows("points", 3, "", None, *_layout(points))
+    n = points.shape[0]
+    return dev, n, stride, _limit("max_dist", max_dist, n, dev)
+
+
+def _ptr(a, null_if_empty=False):
+    """A numpy array or a tensor as a void * argument; None stays None.  null_if_empty: an empty array goes as NULL, which the multi-hit, nearest
+    and overlap queries do on both paths.  rt_trace_rays and rt_trace_scene_rays get the address as it is -- an empty numpy array has one, an
+    empty tensor has none -- and that is observable: they refuse an any-hit query with a NULL tMax before they look at n."""
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        return C.c_void_p(a.ctypes.data) if a.size or not null_if_empty else None
+    return C.c_void_p(a.data_ptr()) if a.numel() or not null_if_empty else None
+
+
+def _ptr0(a):
+    return _ptr(a, True)
+
+
+def _new(dev, shape, dtype=np.float32, zero=False):
+    """An output of a query: a zero-filled numpy array for dev None, else a tensor on dev -- torch.empty unless `zero` says that the fill is
+    counted on (the any-hit `occluded` flags, the marquee's corners)."""
+    if dev is None:
+        return np.zeros(shape, dtype)
+    import torch
+    return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+
+
+def _as_bool(occluded):
+    """The uint8 flags of an any-hit query as the bool array the caller gets, a view."""
+    if isinstance(occluded, np.ndarray):
+        return occluded.view(bool)
+    import torch
+    return occluded.view(torch.bool)
+
+
 class MultiHits:
     """Answers of multi_hits, Renderer.trace_rays_multi and Renderer.pick_multi: `hits` [N,K,4] float32 -- K RtHit records per ray,
     nearest first, the miss record {inf, -1, 0, 0} past the ray's last hit -- with the views t [N,K], prim [N,K] int32 and uv [N,K,2], and `count`
@@ -1496,11 +1639,7 @@ class MultiHits:
         self.hits = hits
         self.count = count
         self.t = hits[:, :, 0]
-        if isinstance(hits, np.ndarray):
-            self.prim = hits.view(np.int32)[:, :, 1]
-        else:
-            import torch
-            self.prim = hits.view(torch.int32)[:, :, 1]
+        self.prim = _prim_view(hits)
         self.uv = hits[:, :, 2:4]
 
     def __len__(self):
@@ -1514,23 +1653,6 @@ def _multi_k(max_hits):
     return k
 
 
-def _numpy_rays(origins, dirs, tmax):
-    """The checks of Renderer.trace_rays on numpy rays -> (n, origin stride, dir stride, contiguous tmax)."""
-    for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
-        if not isinstance(a, np.ndarray) and a is not None:
-            raise _query_invalid(f"{name} must be a numpy array")
-        if a is not None and a.dtype != np.float32:
-            raise _query_invalid(f"{name} must be float32, got {a.dtype}")
-    n = origins.shape[0] if origins.ndim == 2 else -1
-    os_ = Renderer._ray_rows("origins", origins, 4, origins.strides)
-    ds = Renderer._ray_rows("dirs", dirs, 4, dirs.strides, n)
-    if tmax is not None:
-        if tmax.shape != (n,):
-            raise _query_invalid(f"tmax must be [{n}], got shape {tmax.shape}")
-        tmax = np.ascontiguousarray(tmax)
-    return n, os_, ds, tmax
-
-
 def multi_hits(nodes12, tris12, origins, dirs, tmax=None, max_hits=4, eps=1e-4, inf=1e30) -> MultiHits:
     """The definition of the multi-hit query (rt_multi_hits), on the host and without a context: per ray the max_hits nearest of
     the triangles traceBVHShadow's walk of (nodes12, tris12) would accept up to tmax[i] (inf without tmax), ordered by (t, prim), and the count of
@@ -1538,10 +1660,10 @@ def multi_hits(nodes12, tris12, origins, dirs, tmax=None, max_hits=4, eps=1e-4, 
     k = _multi_k(max_hits)
     nodes = _f32(nodes12).reshape(-1, 12)
     tris = _f32(tris12).reshape(-1, 12)
-    n, os_, ds, tmax = _numpy_rays(origins, dirs, tmax)
+    _, n, os_, ds, tmax = _ray_check(origins, dirs, tmax)
     hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
-    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-    rc = lib().rt_multi_hits(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, p(hits), C.c_void_p(count.ctypes.data))
+    p = _ptr0
+    rc = lib().rt_multi_hits(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, p(hits), _ptr(count))
     if rc != RT_OK:
         raise RtError(rc, "rt_multi_hits: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_multi_hits")
     return MultiHits(hits, count)
@@ -1558,31 +1680,11 @@ class NearestPoints:
         self.points = points
         self.visits = visits
         self.dist2 = hits[:, 0]
-        if isinstance(hits, np.ndarray):
-            self.prim = hits.view(np.int32)[:, 1]
-        else:
-            import torch
-            self.prim = hits.view(torch.int32)[:, 1]
+        self.prim = _prim_view(hits)
         self.uv = hits[:, 2:4]
 
     def __len__(self):
         return self.hits.shape[0]
-
-
-def _numpy_points(points, max_dist):
-    """The checks of the nearest-point queries on numpy points -> (n, stride, contiguous max_dist)."""
-    for name, a in (("points", points), ("max_dist", max_dist)):
-        if not isinstance(a, np.ndarray) and a is not None:
-            raise _query_invalid(f"{name} must be a numpy array")
-        if a is not None and a.dtype != np.float32:
-            raise _query_invalid(f"{name} must be float32, got {a.dtype}")
-    stride = Renderer._ray_rows("points", points, 4, points.strides)
-    n = points.shape[0]
-    if max_dist is not None:
-        if max_dist.shape != (n,):
-            raise _query_invalid(f"max_dist must be [{n}], got shape {max_dist.shape}")
-        max_dist = np.ascontiguousarray(max_dist)
-    return n, stride, max_dist
 
 
 def nearest_points(nodes12, tris12, points, max_dist=None) -> NearestPoints:
@@ -1591,9 +1693,9 @@ def nearest_points(nodes12, tris12, points, max_dist=None) -> NearestPoints:
     strided (numpy); max_dist[i] < 0 or a non-finite coordinate marks an empty slot."""
     nodes = _f32(nodes12).reshape(-1, 12)
     tris = _f32(tris12).reshape(-1, 12)
-    n, stride, max_dist = _numpy_points(points, max_dist)
+    _, n, stride, max_dist = _point_check(points, max_dist)
     hits, closest = np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32)
-    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    p = _ptr0
     rc = lib().rt_nearest_points(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(points), stride, p(max_dist), n, p(hits), p(closest))
     if rc != RT_OK:
         raise RtError(rc, "rt_nearest_points: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_nearest_points")
@@ -1613,11 +1715,7 @@ class NearestMulti:
         self.count = count
         self.visits = visits
         self.dist2 = hits[:, :, 0]
-        if isinstance(hits, np.ndarray):
-            self.prim = hits.view(np.int32)[:, :, 1]
-        else:
-            import torch
-            self.prim = hits.view(torch.int32)[:, :, 1]
+        self.prim = _prim_view(hits)
         self.uv = hits[:, :, 2:4]
 
     def __len__(self):
@@ -1640,11 +1738,11 @@ def nearest_points_multi(nodes12, tris12, points, max_hits, max_dist=None) -> Ne
     k = _nearest_multi_k(max_hits, True)
     nodes = _f32(nodes12).reshape(-1, 12)
     tris = _f32(tris12).reshape(-1, 12)
-    n, stride, max_dist = _numpy_points(points, max_dist)
+    _, n, stride, max_dist = _point_check(points, max_dist)
     hits, closest, count = np.zeros((n, k, 4), np.float32), np.zeros((n, k, 3), np.float32), np.zeros(n, np.int32)
-    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    p = _ptr0
     rc = lib().rt_nearest_points_multi(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(points), stride, p(max_dist), n, k, p(hits),
-                                       C.c_void_p(count.ctypes.data), p(closest))
+                                       _ptr(count), p(closest))
     if rc != RT_OK:
         raise RtError(rc, "rt_nearest_points_multi: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_nearest_points_multi")
     return NearestMulti(hits, closest, count)
@@ -1678,27 +1776,15 @@ class BoxOverlaps:
         third = np.float32(1.0) / np.float32(3.0)
         if isinstance(self.prims, np.ndarray):
             rec = np.zeros((self.prims.shape[0], 4), np.float32)
-            rec.view(np.int32)[:, 1] = self.prims
-            rec[:, 2:4] = third
-            return rec
-        import torch
-        rec = torch.zeros((self.prims.shape[0], 4), dtype=torch.float32, device=self.prims.device)
-        rec.view(torch.int32)[:, 1] = self.prims
+        else:
+            import torch
+            rec = torch.zeros((self.prims.shape[0], 4), dtype=torch.float32, device=self.prims.device)
+        _prim_view(rec)[:] = self.prims
         rec[:, 2:4] = float(third)
         return rec
 
     def __len__(self):
         return self.count.shape[0]
-
-
-def _box_rows(a, itemsize, strides):
-    """The checks of the box queries on a [N,k] box array, k >= 6 -> the row stride in floats."""
-    if a.ndim != 2 or a.shape[1] < 6:
-        raise _query_invalid(f"boxes must be [N,k] with k >= 6 (lo.xyz, hi.xyz), got shape {tuple(a.shape)}")
-    row, col = strides
-    if col != itemsize or row % itemsize or (a.shape[0] > 1 and row // itemsize < 6):
-        raise _query_invalid("boxes must have unit stride along its last dimension and rows at least 6 floats apart")
-    return max(row // itemsize, 6) if a.shape[0] > 1 else max(a.shape[1], 6)
 
 
 def _box_cap(cap):
@@ -1710,19 +1796,10 @@ def _box_cap(cap):
     return k
 
 
-def _numpy_boxes(boxes):
-    if not isinstance(boxes, np.ndarray):
-        raise _query_invalid("boxes must be a numpy array")
-    if boxes.dtype != np.float32:
-        raise _query_invalid(f"boxes must be float32, got {boxes.dtype}")
-    return boxes.shape[0] if boxes.ndim == 2 else -1, _box_rows(boxes, 4, boxes.strides)
-
-
-def _numpy_box_query(call, boxes, cap, visits, rows=_numpy_boxes, result=BoxOverlaps):
-    """Both forms on host arrays: call(boxes, stride, n, offsets, cap, prims, counts, visits) -> rc, checked by the caller's wrapper.  rows: the
-    checks of the query array -> (n, stride); result: the answers' class (the triangle queries pass their own)."""
-    n, stride = rows(boxes)
-    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+def _numpy_box_query(call, result, boxes, n, stride, cap, visits):
+    """Both forms on host arrays, for the n checked query rows `boxes`, `stride` floats apart: call(boxes, stride, n, offsets, cap, prims, counts,
+    visits) -> rc, checked by the caller's wrapper.  result: the answers' class."""
+    p = _ptr0
     count = np.zeros(n, np.int32)
     vis = np.zeros(n, np.int32) if visits else None
     if cap is not None:
@@ -1751,17 +1828,22 @@ def box_overlaps(nodes12, tris12, boxes, cap=None) -> BoxOverlaps:
     (nodes12, tris12) that lie under overlapping node boxes and that the 13-axis separating-axis test cannot part from it, in walk order, and their
     count.  boxes: float32 [N,k], k >= 6 (lo.xyz, hi.xyz), rows may be strided (numpy); a NaN component or lo > hi marks an empty slot.  cap=None:
     the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per box."""
+    return _host_overlaps("rt_box_overlaps", BoxOverlaps, _BOXES, nodes12, tris12, boxes, cap)
+
+
+def _host_overlaps(entry, result, family, nodes12, tris12, queries, cap):
+    """box_overlaps, tri_overlaps and hull_overlaps: the C definition `entry` over the checked arrays -> result."""
     cap = _box_cap(cap)
     nodes = _f32(nodes12).reshape(-1, 12)
     tris = _f32(tris12).reshape(-1, 12)
-    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+    _, n, stride = _row_array(family, queries)
 
-    def call(b, stride, n, offsets, cap_, prims, counts, _visits):
-        rc = lib().rt_box_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], b, stride, n, offsets, cap_, prims, counts)
+    def call(q, stride_, n_, offsets, cap_, prims, counts, _visits):
+        rc = getattr(lib(), entry)(_ptr0(nodes), nodes.shape[0], _ptr0(tris), tris.shape[0], q, stride_, n_, offsets, cap_, prims, counts)
         if rc != RT_OK:
-            raise RtError(rc, "rt_box_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_box_overlaps")
+            raise RtError(rc, f"{entry}: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else entry)
 
-    return _numpy_box_query(call, boxes, cap, False)
+    return _numpy_box_query(call, result, queries, n, stride, cap, False)
 
 
 class TriOverlaps(BoxOverlaps):
@@ -1785,45 +1867,12 @@ class TriOverlaps(BoxOverlaps):
         return torch.stack([query.to(torch.int32), self.prims[torch.repeat_interleave(start, k) + within]], 1)
 
 
-def _tri_rows(shape, itemsize, strides):
-    """The checks of the triangle queries on a [N,k] (k >= 9) or [N,3,3] array -> the row stride in floats."""
-    if len(shape) == 3 and tuple(shape[1:]) == (3, 3):
-        if strides[1] != 3 * itemsize or strides[2] != itemsize:
-            raise _query_invalid("qtris [N,3,3]: the nine floats of a triangle must be contiguous")
-        shape, strides = (shape[0], 9), (strides[0], itemsize)
-    if len(shape) != 2 or shape[1] < 9:
-        raise _query_invalid(f"qtris must be [N,k] with k >= 9 (p0.xyz, p1.xyz, p2.xyz) or [N,3,3], got shape {tuple(shape)}")
-    row, col = strides
-    if col != itemsize or row % itemsize or (shape[0] > 1 and row // itemsize < 9):
-        raise _query_invalid("qtris must have unit stride along its last dimension and rows at least 9 floats apart")
-    return max(row // itemsize, 9) if shape[0] > 1 else max(shape[1], 9)
-
-
-def _numpy_tris(qtris):
-    if not isinstance(qtris, np.ndarray):
-        raise _query_invalid("qtris must be a numpy array")
-    if qtris.dtype != np.float32:
-        raise _query_invalid(f"qtris must be float32, got {qtris.dtype}")
-    stride = _tri_rows(qtris.shape, 4, qtris.strides)
-    return qtris.shape[0], stride
-
-
 def tri_overlaps(nodes12, tris12, qtris, cap=None) -> TriOverlaps:
     """The definition of the triangle query (rt_tri_overlaps), on the host and without a context: per query triangle (p0, p1, p2) the
     rows of (nodes12, tris12) that lie under node boxes overlapping the box of its points and that the 20-axis separating-axis test cannot part from
     it, in walk order, and their count.  qtris: float32 [N,9], [N,3,3] or [N,k], k >= 9, rows may be strided (numpy); a NaN component marks an empty
     slot.  cap=None: the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per query."""
-    cap = _box_cap(cap)
-    nodes = _f32(nodes12).reshape(-1, 12)
-    tris = _f32(tris12).reshape(-1, 12)
-    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
-
-    def call(q, stride, n, offsets, cap_, prims, counts, _visits):
-        rc = lib().rt_tri_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], q, stride, n, offsets, cap_, prims, counts)
-        if rc != RT_OK:
-            raise RtError(rc, "rt_tri_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_tri_overlaps")
-
-    return _numpy_box_query(call, qtris, cap, False, rows=_numpy_tris, result=TriOverlaps)
+    return _host_overlaps("rt_tri_overlaps", TriOverlaps, _QTRIS, nodes12, tris12, qtris, cap)
 
 
 class HullOverlaps(TriOverlaps):
@@ -1836,53 +1885,20 @@ class HullOverlaps(TriOverlaps):
         self.corners = corners
 
 
-def _hull_rows(shape, itemsize, strides):
-    """The checks of the hull queries on a [N,k] (k >= 24) or [N,8,3] array -> the row stride in floats."""
-    if len(shape) == 3 and tuple(shape[1:]) == (8, 3):
-        if strides[1] != 3 * itemsize or strides[2] != itemsize:
-            raise _query_invalid("hulls [N,8,3]: the 24 floats of a hull must be contiguous")
-        shape, strides = (shape[0], 24), (strides[0], itemsize)
-    if len(shape) != 2 or shape[1] < 24:
-        raise _query_invalid(f"hulls must be [N,k] with k >= 24 (c0.xyz .. c7.xyz) or [N,8,3], got shape {tuple(shape)}")
-    row, col = strides
-    if col != itemsize or row % itemsize or (shape[0] > 1 and row // itemsize < 24):
-        raise _query_invalid("hulls must have unit stride along its last dimension and rows at least 24 floats apart")
-    return max(row // itemsize, 24) if shape[0] > 1 else max(shape[1], 24)
-
-
-def _numpy_hulls(hulls):
-    if not isinstance(hulls, np.ndarray):
-        raise _query_invalid("hulls must be a numpy array")
-    if hulls.dtype != np.float32:
-        raise _query_invalid(f"hulls must be float32, got {hulls.dtype}")
-    stride = _hull_rows(hulls.shape, 4, hulls.strides)
-    return hulls.shape[0], stride
-
-
 def hull_overlaps(nodes12, tris12, hulls, cap=None) -> HullOverlaps:
     """The definition of the hull query (rt_hull_overlaps), on the host and without a context: per convex hexahedron (eight corners, corner
     k with bit 0 / 1 / 2 for the high end along the shape's first / second / third parameter) the rows of (nodes12, tris12) that lie under nodes that
     its box and its six face normals cannot part from it and that the 46-axis separating-axis test cannot part from it, in walk order, and their
     count.  hulls: float32 [N,24], [N,8,3] or [N,k], k >= 24, rows may be strided (numpy); a NaN among the 24 floats marks an empty slot.  cap=None:
     the exact lists in two passes (count, scan, list); cap=k: one pass into k entries per hull."""
-    cap = _box_cap(cap)
-    nodes = _f32(nodes12).reshape(-1, 12)
-    tris = _f32(tris12).reshape(-1, 12)
-    pa = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
-
-    def call(q, stride, n, offsets, cap_, prims, counts, _visits):
-        rc = lib().rt_hull_overlaps(pa(nodes), nodes.shape[0], pa(tris), tris.shape[0], q, stride, n, offsets, cap_, prims, counts)
-        if rc != RT_OK:
-            raise RtError(rc, "rt_hull_overlaps: the nodes are not a tree over the rows of tris12" if rc == RT_ERR_INVALID else "rt_hull_overlaps")
-
-    return _numpy_box_query(call, hulls, cap, False, rows=_numpy_hulls, result=HullOverlaps)
+    return _host_overlaps("rt_hull_overlaps", HullOverlaps, _HULLS, nodes12, tris12, hulls, cap)
 
 
 def box_corners(boxes, M=None):
     """The hulls [N,24] float32 of the boxes [N,k], k >= 6 (lo.xyz, hi.xyz; numpy float32, rows may be strided) under M (rt_box_corners, DESIGN.md
     26.2): None, the identity, which copies; 16 floats, one column-major matrix for all boxes; or [N,16], one per box -- rows of
     mesh_part_matrices().  A NaN component or lo > hi gives 24 NaNs, an empty slot of the hull query."""
-    n, stride = _numpy_boxes(boxes)
+    _, n, stride = _row_array(_BOXES, boxes)
     m, mat_stride = None, 0
     if M is not None:
         m = _f32(M).reshape(-1, 16)
@@ -1898,31 +1914,11 @@ def box_corners(boxes, M=None):
     return out
 
 
-def _rect_rows(a, itemsize, strides):
-    """The checks of a [N,k] rect array, k >= 4 -> the row stride in floats."""
-    if a.ndim != 2 or a.shape[1] < 4:
-        raise _query_invalid(f"rects must be [N,k] with k >= 4 (x0, y0, x1, y1), got shape {tuple(a.shape)}")
-    row, col = strides
-    if col != itemsize or row % itemsize or (a.shape[0] > 1 and row // itemsize < 4):
-        raise _query_invalid("rects must have unit stride along its last dimension and rows at least 4 floats apart")
-    return max(row // itemsize, 4) if a.shape[0] > 1 else max(a.shape[1], 4)
-
-
-def _numpy_rects(rects):
-    if not isinstance(rects, np.ndarray):
-        raise _query_invalid("rects must be a numpy array")
-    if rects.dtype != np.float32:
-        raise _query_invalid(f"rects must be float32, got {rects.dtype}")
-    if rects.ndim != 2:
-        raise _query_invalid("rects must be [N,k]")
-    return rects.shape[0], _rect_rows(rects, 4, rects.strides)
-
-
 def rect_frusta(u, root_min, root_max, rects, t_near=0.0, t_far=None):
     """The hulls [N,24] float32 behind the rects [N,k], k >= 4 (x0, y0, x1, y1 in pixel-corner coordinates of u's frame, row 0 at the bottom; numpy
     float32) between the depths t_near and t_far along the view direction (rt_rect_frusta).  t_near=0: the pyramid from the eye.
     t_far=None: to the far side of the box [root_min, root_max] -- node 0's box of the scene.  A NaN, x1 < x0 or y1 < y0 gives 24 NaNs."""
-    n, stride = _numpy_rects(rects)
+    _, n, stride = _row_array(_RECTS, rects)
     lo, hi = _f32(root_min).reshape(3), _f32(root_max).reshape(3)
     out = np.zeros((n, 24), np.float32)
     rc = lib().rt_rect_frusta(C.byref(u) if u is not None else None, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data),
@@ -1943,6 +1939,25 @@ def rows_as_tris(tris12):
     import torch
     t = tris12.reshape(-1, 12)
     return torch.cat([t[:, 0:3], t[:, 0:3] + t[:, 4:7], t[:, 0:3] + t[:, 8:11]], 1)
+
+
+def _model16(who, model):
+    """A model matrix argument: None, or 16 floats (column-major, or a 4x4 array as default_bvh_transform returns it) -> None or float32 [16]."""
+    m = None if model is None else _f32(model).reshape(-1)
+    if m is not None and m.size != 16:
+        raise RtError(RT_ERR_INVALID, f"{who}: model must have 16 floats")
+    return m
+
+
+def _wants_torch(as_torch):
+    """as_torch of the device-array accessors: None stands for "when torch imports"."""
+    if as_torch is None:
+        try:
+            import torch  # noqa: F401
+            return True
+        except ImportError:
+            return False
+    return as_torch
 
 
 # ------------------------------------------------------------------------------------ device side
@@ -2002,24 +2017,23 @@ class Renderer:
             raise RtError(RT_ERR_INVALID, f"mesh_set_positions: {v.shape[0]} vertices, the mesh has {getattr(self, '_mesh_verts', 0)}")
         self._check(lib().rt_mesh_set_positions(self._h, _fp(v)))   # pageable memory: staged before the call returns, as a frame's uniforms are
 
+    def _sync_scene_counts(self):
+        i = self.scene_info()
+        self.n_nodes, self.n_tris = i.nNodes, i.nTris
+
     def mesh_rebuild(self, model=None):
         """Gather with the model matrix (column-major 16 floats or a 4x4 array as default_bvh_transform returns it; None: identity), build the BVH and
         every device record form on the device, install (rt_mesh_rebuild).  Asynchronous; no host wait unless the quantised any-hit form is in use."""
-        m = None if model is None else _f32(model).reshape(-1)
-        if m is not None and m.size != 16:
-            raise RtError(RT_ERR_INVALID, "mesh_rebuild: model must have 16 floats")
+        m = _model16("mesh_rebuild", model)
         self._check(lib().rt_mesh_rebuild(self._h, None if m is None else _fp(m)))
-        i = self.scene_info()
-        self.n_nodes, self.n_tris = i.nNodes, i.nTris
+        self._sync_scene_counts()
 
     def mesh_refit(self, model=None):
         """Keep the tree of the last mesh_rebuild and recompute what depends on coordinates -- triangles, every box, every record form -- from the
         current device positions and the model matrix (None: identity) (rt_mesh_refit).  Asynchronous like mesh_rebuild, at a fraction of its cost.
         Exact for any deformation; the tree gets slower to walk as triangles move apart: mesh_measure / mesh_quality measure that, and mesh_update
         refits or rebuilds by it."""
-        m = None if model is None else _f32(model).reshape(-1)
-        if m is not None and m.size != 16:
-            raise RtError(RT_ERR_INVALID, "mesh_refit: model must have 16 floats")
+        m = _model16("mesh_refit", model)
         self._check(lib().rt_mesh_refit(self._h, None if m is None else _fp(m)))
 
     def mesh_measure(self):
@@ -2043,15 +2057,12 @@ class Renderer:
         times what the tree cost as its rebuild left it; then enqueue a measurement of the result.  parts=True gathers under the device matrix table
         (model must be None).  Never waits, so the decision rests on the previous step's tree at the latest.  rebuild_above has no default: what ratio
         is worth a rebuild depends on the scene.  -> "refit" or "rebuild"."""
-        m = None if model is None else _f32(model).reshape(-1)
-        if m is not None and m.size != 16:
-            raise RtError(RT_ERR_INVALID, "mesh_update: model must have 16 floats")
+        m = _model16("mesh_update", model)
         action = C.c_int(-1)
         self._check(lib().rt_mesh_update(self._h, RT_MESH_UPDATE_PARTS if parts else RT_MESH_UPDATE_SINGLE, None if m is None else _fp(m), float(rebuild_above),
                                          C.byref(action)))
         if action.value == RT_MESH_DID_REBUILD:
-            i = self.scene_info()
-            self.n_nodes, self.n_tris = i.nNodes, i.nTris
+            self._sync_scene_counts()
         return "rebuild" if action.value == RT_MESH_DID_REBUILD else "refit"
 
     def mesh_refit_count(self):
@@ -2064,24 +2075,13 @@ class Renderer:
         """order[i] = the input triangle that is row i of the device triangle array since the last mesh_rebuild, so order[prim] maps a hit back to the
         index buffer.  With torch (as_torch=None: when it imports) an int32 [nTris] tensor that aliases the device array, zero-copy, valid until the
         next mesh_rebuild and written on stream(): read it there.  Else a numpy array (rt_mesh_order: copies and synchronises)."""
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
-        if not as_torch:
+        if not _wants_torch(as_torch):
             out = np.zeros(max(self.mesh_info().nTris, 1), np.int32)
             self._check(lib().rt_mesh_order(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
             return out[:self.mesh_info().nTris]
-        import torch
         ptr, n = C.c_void_p(), C.c_size_t()
         self._check(lib().rt_mesh_order_device(self._h, C.byref(ptr), C.byref(n)))
-        nt = n.value // 4
-
-        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-            __cuda_array_interface__ = {"shape": (nt,), "typestr": "<i4", "data": (ptr.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        return self._alias(ptr.value, (n.value // 4,), "<i4")
 
     # ---- parts (DESIGN.md 14.8): one model matrix per part, on the device, and hit -> (part, triangle of the part)
     def mesh_upload_parts(self, positions, indices, part_first):
@@ -2120,8 +2120,7 @@ class Renderer:
     def mesh_rebuild_parts(self):
         """mesh_rebuild with every part gathered under its own matrix of the device table (rt_mesh_rebuild_parts)."""
         self._check(lib().rt_mesh_rebuild_parts(self._h))
-        i = self.scene_info()
-        self.n_nodes, self.n_tris = i.nNodes, i.nTris
+        self._sync_scene_counts()
 
     def mesh_refit_parts(self):
         """mesh_refit with every part gathered under its own matrix of the device table (rt_mesh_refit_parts)."""
@@ -2137,19 +2136,14 @@ class Renderer:
     # ---- skinning: the positions rewritten on the device from rest positions and a bone table
     def _device_view(self, ptr, nbytes, cols, as_torch):
         """A float32 [nbytes / (4 * cols), cols] tensor that aliases library memory, zero-copy (as_torch=None: when torch imports), else (pointer, bytes)."""
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
-        if not as_torch:
-            return ptr, nbytes
+        return self._alias(ptr, (nbytes // (4 * cols), cols), "<f4") if _wants_torch(as_torch) else (ptr, nbytes)
+
+    def _alias(self, ptr, shape, typestr):
+        """A tensor of `shape` and `typestr` over device memory at `ptr` that the library owns, zero-copy."""
         import torch
-        rows = nbytes // (4 * cols)
 
         class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-            __cuda_array_interface__ = {"shape": (rows, cols), "typestr": "<f4", "data": (ptr, False), "version": 2, "strides": None}
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
         return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
 
     def _device_array(self, entry, cols, as_torch):
@@ -2165,36 +2159,30 @@ class Renderer:
         -> the list of answers."""
         rec = hits.record if isinstance(hits, RayHits) else hits
         if isinstance(rec, np.ndarray):
+            dev = None
             if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] != 4:
                 raise RtError(RT_ERR_INVALID, f"{name}: records must be float32 [N,4], got {rec.dtype} {rec.shape}")
-            rec = np.ascontiguousarray(rec)
             n = rec.shape[0]
-            ins = [rec]
+            ins = [np.ascontiguousarray(rec)]
             if extra is not None:
                 x = _f32(extra[1]).reshape(-1, 3)
                 if x.shape[0] != n:
                     raise RtError(RT_ERR_INVALID, f"{name}: {n} hits and {x.shape[0]} {extra[0]}")
                 ins.append(x)
-            outs = [np.zeros((n, cols) if cols else n, dt) for cols, dt in outputs]
-            self._check(getattr(lib(), f"rt_{name}_host")(self._h, *(C.c_void_p(a.ctypes.data) for a in ins), n, *(C.c_void_p(o.ctypes.data) for o in outs)))
-            return outs
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
-            raise RtError(RT_ERR_INVALID, f"{name}: records must be a numpy array or a float32 [N,4] tensor on {dev}")
-        n = rec.shape[0]
-        ins = [rec.contiguous()]
-        if extra is not None:
-            x = extra[1]
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != 3 * n or x.device != dev:
-                raise RtError(RT_ERR_INVALID, f"{name}: {extra[0]} must be a float32 [N,3] tensor on {dev}")
-            ins.append(x.contiguous())
-        outs = [torch.empty((n, cols) if cols else n, dtype=getattr(torch, np.dtype(dt).name), device=dev) for cols, dt in outputs]
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the inputs (and the outputs' allocation) are ready before the kernel starts
-        self._check(getattr(lib(), f"rt_{name}")(self._h, *(C.c_void_p(a.data_ptr()) for a in ins), n, *(C.c_void_p(o.data_ptr()) for o in outs)))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers; lifetimes as in _trace_rays_torch
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not isinstance(rec, torch.Tensor) or rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 4 or rec.device != dev:
+                raise RtError(RT_ERR_INVALID, f"{name}: records must be a numpy array or a float32 [N,4] tensor on {dev}")
+            n = rec.shape[0]
+            ins = [rec.contiguous()]
+            if extra is not None:
+                x = extra[1]
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != 3 * n or x.device != dev:
+                    raise RtError(RT_ERR_INVALID, f"{name}: {extra[0]} must be a float32 [N,3] tensor on {dev}")
+                ins.append(x.contiguous())
+        outs = [_new(dev, (n, cols) if cols else n, dt) for cols, dt in outputs]
+        self._query(dev, f"rt_{name}", ins, *(_ptr(a) for a in ins), n, *(_ptr(o) for o in outs))
         return outs
 
     def mesh_skin_upload(self, bone_idx, weights, n_bones, rest=None):
@@ -2364,19 +2352,9 @@ class Renderer:
         they stand in stream order), else (pointer, bytes, W, H)."""
         ptr, n, w, h = C.c_void_p(), C.c_size_t(), C.c_int(), C.c_int()
         self._check(lib().rt_mesh_texture(self._h, C.byref(ptr), C.byref(n), C.byref(w), C.byref(h)))
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
-        if not as_torch:
+        if not _wants_torch(as_torch):
             return ptr.value, n.value, w.value, h.value
-        import torch
-
-        class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-            __cuda_array_interface__ = {"shape": (h.value, w.value, 4), "typestr": "|u1", "data": (ptr.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        return self._alias(ptr.value, (h.value, w.value, 4), "|u1")
 
     def mesh_hit_uvs(self, hits):
         """The UV of each hit: float32 [N,2], hit_uvs bit for bit; zeros for a miss, an analytic hit or a prim outside the mesh.  Arguments and
@@ -2664,82 +2642,51 @@ class Renderer:
         kind = RT_QUERY_ANY if any_hit else RT_QUERY_CLOSEST
         if any_hit and tmax is None:
             raise _query_invalid("any-hit queries need tmax")
-        arrays = [a for a in (origins, dirs, tmax) if a is not None]
-        if all(isinstance(a, np.ndarray) for a in arrays):
-            return self._trace_rays_numpy(kind, origins, dirs, tmax, eps, inf, normals)
-        import torch
-        if not all(isinstance(a, torch.Tensor) for a in arrays):
-            raise _query_invalid("origins, dirs and tmax must all be numpy arrays or all torch tensors")
-        return self._trace_rays_torch(kind, origins, dirs, tmax, eps, inf, normals)
-
-    @staticmethod
-    def _ray_rows(name, a, itemsize, strides, n=None):
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise _query_invalid(f"{name} must be [N,k] with k >= 3, got shape {tuple(a.shape)}")
-        if n is not None and a.shape[0] != n:
-            raise _query_invalid(f"{name} has {a.shape[0]} rows, origins {n}")
-        row, col = strides
-        if col != itemsize or row % itemsize or (a.shape[0] > 1 and row // itemsize < 3):
-            raise _query_invalid(f"{name} must have unit stride along its last dimension and rows at least 3 floats apart")
-        return max(row // itemsize, 3) if a.shape[0] > 1 else max(a.shape[1], 3)
-
-    def _trace_rays_numpy(self, kind, origins, dirs, tmax, eps, inf, normals):
-        for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
-            if a is not None and a.dtype != np.float32:
-                raise _query_invalid(f"{name} must be float32, got {a.dtype}")
-        n = origins.shape[0] if origins.ndim == 2 else -1
-        os_ = self._ray_rows("origins", origins, 4, origins.strides)
-        ds = self._ray_rows("dirs", dirs, 4, dirs.strides, n)
-        if tmax is not None:
-            if tmax.shape != (n,):
-                raise _query_invalid(f"tmax must be [{n}], got shape {tmax.shape}")
-            tmax = np.ascontiguousarray(tmax)
-        p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-        if kind == RT_QUERY_ANY:
-            occ = np.zeros(n, np.uint8)
-            self._check(lib().rt_trace_rays_host(self._h, kind, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, None, None, p(occ)))
-            return occ.view(bool)
-        rec = np.zeros((n, 4), np.float32)
-        nrm = np.zeros((n, 3), np.float32) if normals else None
-        self._check(lib().rt_trace_rays_host(self._h, kind, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, p(rec), p(nrm), None))
+        dev, n, os_, ds, tmax_ = _ray_check(origins, dirs, tmax, self, own=True)
+        rays = (_ptr(origins), os_, _ptr(dirs), ds, _ptr(tmax_), eps, inf, n)
+        if any_hit:
+            occ = _new(dev, n, np.uint8, zero=True)
+            self._query(dev, "rt_trace_rays", (origins, dirs, tmax), kind, *rays, None, None, _ptr(occ))
+            return _as_bool(occ)
+        rec = _new(dev, (n, 4))
+        nrm = _new(dev, (n, 3)) if normals else None
+        self._query(dev, "rt_trace_rays", (origins, dirs, tmax), kind, *rays, _ptr(rec), _ptr(nrm), None)
         return RayHits(rec, nrm)
 
-    def _trace_rays_torch(self, kind, origins, dirs, tmax, eps, inf, normals):
+    @contextlib.contextmanager
+    def _library_stream(self, dev, inputs):
+        """The stream protocol of every zero-copy torch path, here and nowhere else: `with ... as run`, and each run(entry, *args)
+        is one pass -- the library stream waits for torch's current stream, so the inputs and the outputs, allocated and filled before the first
+        pass, are ready; the C call entry(context, *args), checked; torch's current stream waits for the library stream, so the work behind it
+        sees the answers.  At the end the input tensors are recorded on torch's current stream.
+        Lifetimes: a block freed on torch's current stream is reused only by work queued behind the second wait, i.e. behind the query; input
+        tensors of other streams are tied to the current stream by the record.  Never to the library stream: it dies with the context, before
+        the tensors may, and the allocator would record an event on it when they are freed -- so nothing is recorded where the caller runs the
+        query under torch.cuda.stream(ExternalStream(self.stream()))."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
-            if a is None:
-                continue
-            if a.dtype != torch.float32:
-                raise _query_invalid(f"{name} must be float32, got {a.dtype}")
-            if a.device != dev:
-                raise _query_invalid(f"{name} is on {a.device}, the context on {dev}")
-        n = origins.shape[0] if origins.dim() == 2 else -1
-        os_ = self._ray_rows("origins", origins, 1, origins.stride())
-        ds = self._ray_rows("dirs", dirs, 1, dirs.stride(), n)
-        if tmax is not None and (tuple(tmax.shape) != (n,) or (n > 1 and tmax.stride(0) != 1)):
-            raise _query_invalid(f"tmax must be a contiguous [{n}] tensor, got shape {tuple(tmax.shape)}")
-        if kind == RT_QUERY_ANY:
-            out, nrm = torch.zeros(n, dtype=torch.uint8, device=dev), None
-        else:
-            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
         ext = torch.cuda.ExternalStream(self.stream(), device=dev)
         cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the rays (and the outputs' allocation) are ready before the query starts
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        self._check(lib().rt_trace_rays(self._h, kind, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n,
-                                        p(out) if kind == RT_QUERY_CLOSEST else None, p(nrm), p(out) if kind == RT_QUERY_ANY else None))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers
-        # Lifetimes: a block freed on torch's current stream is reused only by work queued behind the wait above, i.e. behind the query; input
-        # tensors of other streams are tied to the current stream too.  (Never to the library stream: it dies with the context, before the
-        # tensors may.)
-        for a in (origins, dirs, tmax):
+
+        def run(entry, *args):
+            ext.wait_stream(cur)
+            self._check(entry(self._h, *args))
+            cur.wait_stream(ext)
+
+        yield run
+        if cur.cuda_stream == ext.cuda_stream:      # the caller made the library stream torch's current one: a record would tie the tensors to it
+            return
+        for a in inputs:
             if a is not None:
                 a.record_stream(cur)
-        if kind == RT_QUERY_ANY:
-            return out.view(torch.bool)
-        return RayHits(out, nrm)
+
+    def _query(self, dev, name, inputs, *args):
+        """One query call on the arrays `inputs`: the C entry `name`_host for numpy arrays (dev None), which synchronises; `name` on the library
+        stream for tensors on dev, ordered against torch's current stream and without a host wait."""
+        if dev is None:
+            self._check(getattr(lib(), name + "_host")(self._h, *args))
+            return
+        with self._library_stream(dev, inputs) as run:
+            run(getattr(lib(), name), *args)
 
     def trace_scene_rays(self, u, origins, dirs, tmax=None, any_hit=False, skip_glass=False, skip_marker=False, normals=False, points=False):
         """Ray queries against the scene a frame rendered with uniforms `u` shows (rt_trace_scene_rays): u.useBVH picks the analytic
@@ -2750,101 +2697,58 @@ class Renderer:
         flags = (RT_QUERY_SKIP_GLASS if skip_glass else 0) | (RT_QUERY_SKIP_MARKER if skip_marker else 0)
         if any_hit and tmax is None:
             raise _query_invalid("any-hit queries need tmax")
-        arrays = [a for a in (origins, dirs, tmax) if a is not None]
-        if all(isinstance(a, np.ndarray) for a in arrays):
-            for name, a in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
-                if a is not None and a.dtype != np.float32:
-                    raise _query_invalid(f"{name} must be float32, got {a.dtype}")
-            n = origins.shape[0] if origins.ndim == 2 else -1
-            os_ = self._ray_rows("origins", origins, 4, origins.strides)
-            ds = self._ray_rows("dirs", dirs, 4, dirs.strides, n)
-            if tmax is not None:
-                if tmax.shape != (n,):
-                    raise _query_invalid(f"tmax must be [{n}], got shape {tmax.shape}")
-                tmax = np.ascontiguousarray(tmax)
-            return self._scene_query_numpy(u, kind, flags, (origins, os_, dirs, ds), None, tmax, n, normals, points)
+        dev, n, os_, ds, tmax_ = _ray_check(origins, dirs, tmax, self)
+        rays = (C.byref(u), kind, flags, _ptr(origins), os_, _ptr(dirs), ds, _ptr(tmax_), n)
+        if any_hit:
+            occ = _new(dev, n, np.uint8, zero=True)
+            self._query(dev, "rt_trace_scene_rays", (origins, dirs, tmax), *rays, None, None, None, None, _ptr(occ))
+            return _as_bool(occ)
+        ans = self._scene_hits(dev, n, normals, points)
+        self._query(dev, "rt_trace_scene_rays", (origins, dirs, tmax), *rays, *(_ptr(a) for a in ans), None)
+        return SceneHits(*ans)
+
+    def _scene_hits(self, dev, n, normals, points):
+        """The outputs of a closest-hit scene query: (record, object, normal or None, point or None), as SceneHits takes them."""
+        return _new(dev, (n, 4)), _new(dev, n, np.int32), _new(dev, (n, 3)) if normals else None, _new(dev, (n, 3)) if points else None
+
+    def _pixels(self, xy):
+        """The pixel check of pick and pick_multi: int32 [N,2]; a numpy array is made contiguous, a tensor must be -> (torch device or None for
+        numpy, n, xy to pass)."""
+        if isinstance(xy, np.ndarray):
+            if xy.dtype != np.int32 or xy.ndim != 2 or xy.shape[1] != 2:
+                raise _query_invalid(f"xy must be int32 [N,2], got {xy.dtype} {xy.shape}")
+            return None, xy.shape[0], np.ascontiguousarray(xy)
         import torch
-        if not all(isinstance(a, torch.Tensor) for a in arrays):
-            raise _query_invalid("origins, dirs and tmax must all be numpy arrays or all torch tensors")
-        dev = self._query_device(origins, dirs, tmax, dtype=torch.float32)
-        n = origins.shape[0] if origins.dim() == 2 else -1
-        os_ = self._ray_rows("origins", origins, 1, origins.stride())
-        ds = self._ray_rows("dirs", dirs, 1, dirs.stride(), n)
-        if tmax is not None and (tuple(tmax.shape) != (n,) or (n > 1 and tmax.stride(0) != 1)):
-            raise _query_invalid(f"tmax must be a contiguous [{n}] tensor, got shape {tuple(tmax.shape)}")
-        return self._scene_query_torch(dev, u, kind, flags, (origins, os_, dirs, ds), None, tmax, n, normals, points)
+        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+            raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
+        return _device_of(self.device, (("xy", xy),), torch.int32), xy.shape[0], xy
 
     def pick(self, u, xy, normals=True, points=True):
         """What pixels (x, y) (int32 [N,2], row 0 = bottom) of a frame rendered with uniforms `u` show (rt_pick_pixels): each is traced
         along the frame's own primary ray (jitter included) through the frame's scene -> SceneHits.  numpy or torch, as trace_scene_rays."""
-        if isinstance(xy, np.ndarray):
-            if xy.dtype != np.int32 or xy.ndim != 2 or xy.shape[1] != 2:
-                raise _query_invalid(f"xy must be int32 [N,2], got {xy.dtype} {xy.shape}")
-            return self._scene_query_numpy(u, RT_QUERY_CLOSEST, 0, None, np.ascontiguousarray(xy), None, xy.shape[0], normals, points)
-        import torch
-        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
-            raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
-        dev = self._query_device(xy, dtype=torch.int32)
-        return self._scene_query_torch(dev, u, RT_QUERY_CLOSEST, 0, None, xy, None, xy.shape[0], normals, points)
+        dev, n, xy = self._pixels(xy)
+        ans = self._scene_hits(dev, n, normals, points)
+        self._query(dev, "rt_pick_pixels", (xy,), C.byref(u), _ptr(xy), n, *(_ptr(a) for a in ans))
+        return SceneHits(*ans)
 
     def trace_rays_multi(self, origins, dirs, tmax=None, max_hits=4, eps=1e-4, inf=1e30) -> MultiHits:
         """The max_hits nearest hits and the hit count of every ray against the uploaded BVH (rt_trace_rays_multi) -> MultiHits, equal
         to multi_hits on the uploaded arrays bit for bit.  Rays, tmax, eps / inf and the numpy / torch paths (stream ordering and lifetimes included)
         as trace_rays.  The walk visits every box along the ray up to tmax: bound the work with tmax.  max_hits = 0 asks for the counts alone."""
         k = _multi_k(max_hits)
-        arrays = [a for a in (origins, dirs, tmax) if a is not None]
-        if all(isinstance(a, np.ndarray) for a in arrays):
-            n, os_, ds, tmax = _numpy_rays(origins, dirs, tmax)
-            hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
-            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-            self._check(lib().rt_trace_rays_multi_host(self._h, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, p(hits), p(count)))
-            return MultiHits(hits, count)
-        import torch
-        if not all(isinstance(a, torch.Tensor) for a in arrays):
-            raise _query_invalid("origins, dirs and tmax must all be numpy arrays or all torch tensors")
-        dev = self._query_device(origins, dirs, tmax, dtype=torch.float32)
-        n = origins.shape[0] if origins.dim() == 2 else -1
-        os_ = self._ray_rows("origins", origins, 1, origins.stride())
-        ds = self._ray_rows("dirs", dirs, 1, dirs.stride(), n)
-        if tmax is not None and (tuple(tmax.shape) != (n,) or (n > 1 and tmax.stride(0) != 1)):
-            raise _query_invalid(f"tmax must be a contiguous [{n}] tensor, got shape {tuple(tmax.shape)}")
-        return self._multi_torch(dev, n, k, (origins, dirs, tmax),
-                                 lambda p, hits, count: lib().rt_trace_rays_multi(self._h, p(origins), os_, p(dirs), ds, p(tmax), eps, inf, n, k, hits, count))
+        dev, n, os_, ds, tmax_ = _ray_check(origins, dirs, tmax, self)
+        hits, count = _new(dev, (n, k, 4)), _new(dev, n, np.int32)
+        p = _ptr0
+        self._query(dev, "rt_trace_rays_multi", (origins, dirs, tmax), p(origins), os_, p(dirs), ds, p(tmax_), eps, inf, n, k, p(hits), p(count))
+        return MultiHits(hits, count)
 
     def pick_multi(self, u, xy, max_hits=4) -> MultiHits:
         """The max_hits nearest hits and the hit count under pixels (x, y) (int32 [N,2], row 0 = bottom) of a BVH frame rendered with uniforms `u`
         (rt_pick_pixels_multi): each along the frame's own primary ray, jitter included, up to u.inf -> MultiHits.  numpy or torch, as pick."""
         k = _multi_k(max_hits)
-        if isinstance(xy, np.ndarray):
-            if xy.dtype != np.int32 or xy.ndim != 2 or xy.shape[1] != 2:
-                raise _query_invalid(f"xy must be int32 [N,2], got {xy.dtype} {xy.shape}")
-            xy = np.ascontiguousarray(xy)
-            n = xy.shape[0]
-            hits, count = np.zeros((n, k, 4), np.float32), np.zeros(n, np.int32)
-            p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
-            self._check(lib().rt_pick_pixels_multi_host(self._h, C.byref(u), p(xy), n, k, p(hits), p(count)))
-            return MultiHits(hits, count)
-        import torch
-        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
-            raise _query_invalid("xy must be an int32 [N,2] numpy array or contiguous torch tensor")
-        dev = self._query_device(xy, dtype=torch.int32)
-        n = xy.shape[0]
-        return self._multi_torch(dev, n, k, (xy,), lambda p, hits, count: lib().rt_pick_pixels_multi(self._h, C.byref(u), p(xy), n, k, hits, count))
-
-    def _multi_torch(self, dev, n, k, inputs, call):
-        """The zero-copy path of the multi-hit queries: stream ordering and lifetimes exactly as _trace_rays_torch."""
-        import torch
-        hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
-        count = torch.empty(n, dtype=torch.int32, device=dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the rays (and the outputs' allocation) are ready before the query starts
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-        self._check(call(p, p(hits), p(count)))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers
-        for a in inputs:                     # (never tied to the library stream: it dies with the context)
-            if a is not None:
-                a.record_stream(cur)
+        dev, n, xy = self._pixels(xy)
+        hits, count = _new(dev, (n, k, 4)), _new(dev, n, np.int32)
+        self._query(dev, "rt_pick_pixels_multi", (xy,), C.byref(u), _ptr0(xy), n, k, _ptr0(hits), _ptr0(count))
         return MultiHits(hits, count)
 
     def nearest_points(self, points, max_dist=None, visits=False) -> NearestPoints:
@@ -2853,34 +2757,11 @@ class Renderer:
         (max_dist[i] < 0 marks an empty slot).  An unbounded query far from the mesh costs more than one near it: give max_dist where a bound is
         known.  visits=True also returns the number of boxes tested per point (a diagnostic).  numpy / torch paths, stream ordering and lifetimes
         as trace_rays_multi."""
-        arrays = [a for a in (points, max_dist) if a is not None]
-        if all(isinstance(a, np.ndarray) for a in arrays):
-            n, stride, max_dist = _numpy_points(points, max_dist)
-            hits, closest = np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32)
-            vis = np.zeros(n, np.int32) if visits else None
-            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-            self._check(lib().rt_query_nearest_host(self._h, p(points), stride, p(max_dist), n, p(hits), p(closest), p(vis)))
-            return NearestPoints(hits, closest, vis)
-        import torch
-        if not all(isinstance(a, torch.Tensor) for a in arrays):
-            raise _query_invalid("points and max_dist must all be numpy arrays or all torch tensors")
-        dev = self._query_device(points, max_dist, dtype=torch.float32)
-        stride = self._ray_rows("points", points, 1, points.stride())
-        n = points.shape[0]
-        if max_dist is not None and (tuple(max_dist.shape) != (n,) or (n > 1 and max_dist.stride(0) != 1)):
-            raise _query_invalid(f"max_dist must be a contiguous [{n}] tensor, got shape {tuple(max_dist.shape)}")
-        hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        vis = torch.empty(n, dtype=torch.int32, device=dev) if visits else None
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the points (and the outputs' allocation) are ready before the query starts
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-        self._check(lib().rt_query_nearest(self._h, p(points), stride, p(max_dist), n, p(hits), p(closest), p(vis)))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers
-        for a in (points, max_dist):         # (never tied to the library stream: it dies with the context)
-            if a is not None:
-                a.record_stream(cur)
+        dev, n, stride, limit = _point_check(points, max_dist, self)
+        hits, closest = _new(dev, (n, 4)), _new(dev, (n, 3))
+        vis = _new(dev, n, np.int32) if visits else None
+        p = _ptr0
+        self._query(dev, "rt_query_nearest", (points, max_dist), p(points), stride, p(limit), n, p(hits), p(closest), p(vis))
         return NearestPoints(hits, closest, vis)
 
     def nearest_points_multi(self, points, max_hits, max_dist=None, counts=True, visits=False) -> NearestMulti:
@@ -2889,36 +2770,12 @@ class Renderer:
         visits, the numpy / torch paths, stream ordering and lifetimes as nearest_points.  counts=False leaves the count out and lets the walk cull
         against its max_hits-th best; with counts it visits every box within max_dist, so give max_dist.  max_hits = 0 asks for the counts alone."""
         k = _nearest_multi_k(max_hits, counts)
-        arrays = [a for a in (points, max_dist) if a is not None]
-        if all(isinstance(a, np.ndarray) for a in arrays):
-            n, stride, max_dist = _numpy_points(points, max_dist)
-            hits, closest = np.zeros((n, k, 4), np.float32), np.zeros((n, k, 3), np.float32)
-            count = np.zeros(n, np.int32) if counts else None
-            vis = np.zeros(n, np.int32) if visits else None
-            p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-            self._check(lib().rt_query_nearest_multi_host(self._h, p(points), stride, p(max_dist), n, k, p(hits), p(count), p(closest), p(vis)))
-            return NearestMulti(hits, closest, count, vis)
-        import torch
-        if not all(isinstance(a, torch.Tensor) for a in arrays):
-            raise _query_invalid("points and max_dist must all be numpy arrays or all torch tensors")
-        dev = self._query_device(points, max_dist, dtype=torch.float32)
-        stride = self._ray_rows("points", points, 1, points.stride())
-        n = points.shape[0]
-        if max_dist is not None and (tuple(max_dist.shape) != (n,) or (n > 1 and max_dist.stride(0) != 1)):
-            raise _query_invalid(f"max_dist must be a contiguous [{n}] tensor, got shape {tuple(max_dist.shape)}")
-        hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
-        closest = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
-        count = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
-        vis = torch.empty(n, dtype=torch.int32, device=dev) if visits else None
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the points (and the outputs' allocation) are ready before the query starts
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-        self._check(lib().rt_query_nearest_multi(self._h, p(points), stride, p(max_dist), n, k, p(hits), p(count), p(closest), p(vis)))
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers
-        for a in (points, max_dist):         # (never tied to the library stream: it dies with the context)
-            if a is not None:
-                a.record_stream(cur)
+        dev, n, stride, limit = _point_check(points, max_dist, self)
+        hits, closest = _new(dev, (n, k, 4)), _new(dev, (n, k, 3))
+        count = _new(dev, n, np.int32) if counts else None
+        vis = _new(dev, n, np.int32) if visits else None
+        p = _ptr0
+        self._query(dev, "rt_query_nearest_multi", (points, max_dist), p(points), stride, p(limit), n, k, p(hits), p(count), p(closest), p(vis))
         return NearestMulti(hits, closest, count, vis)
 
     def box_overlaps(self, boxes, cap=None, visits=False) -> BoxOverlaps:
@@ -2928,54 +2785,52 @@ class Renderer:
         allocation waits for the total.  cap=k: one call into k entries per box, no host wait; count[i] > k says that box i overflowed.  visits=True
         also returns the number of boxes tested per box.  One lane walks one box: few boxes that each list very many rows run serially.  numpy /
         torch paths, stream ordering and lifetimes as nearest_points."""
+        return self._overlap_query("rt_query_boxes", BoxOverlaps, _BOXES, boxes, cap, visits)
+
+    def _overlap_query(self, name, result, family, queries, cap, visits):
+        """box_overlaps, tri_overlaps and hull_overlaps: the checks, then _overlaps."""
         cap = _box_cap(cap)
-        if isinstance(boxes, np.ndarray):
-            call = lambda *a: self._check(lib().rt_query_boxes_host(self._h, *a))
-            return _numpy_box_query(call, boxes, cap, visits)
-        import torch
-        if not isinstance(boxes, torch.Tensor):
-            raise _query_invalid("boxes must be a numpy array or a torch tensor")
-        dev = self._query_device(boxes, dtype=torch.float32)
-        stride = _box_rows(boxes, 1, boxes.stride() if boxes.dim() == 2 else (0, 0))
-        return self._device_overlaps(lib().rt_query_boxes, BoxOverlaps, boxes, stride, dev, cap, visits)
+        dev, n, stride = _row_array(family, queries, self)
+        return self._overlaps(name, result, dev, n, stride, queries, cap, visits)
+
+    def _overlaps(self, name, result, dev, n, stride, queries, cap, visits, adapt=lambda entry: entry):
+        """Both forms of an overlap query over n checked query rows through the C entry `name` (numpy, dev None: `name`_host) -> result(count,
+        offsets, prims, visits).  adapt wraps the entry where its arguments are not (context, queries, stride, n, offsets, cap, prims, counts,
+        visits) as they stand."""
+        if dev is None:
+            entry = adapt(getattr(lib(), name + "_host"))
+            return _numpy_box_query(lambda *a: self._check(entry(self._h, *a)), result, queries, n, stride, cap, visits)
+        return self._device_overlaps(adapt(getattr(lib(), name)), result, queries, stride, dev, cap, visits)
 
     def _device_overlaps(self, entry, result, boxes, stride, dev, cap, visits):
-        """Both forms of a box or triangle query on a torch device tensor of queries (`boxes`, rows `stride` floats apart), through the C entry
-        `entry` -> result(count, offsets, prims, visits)."""
+        """Both forms of an overlap query on a torch device tensor of queries (`boxes`, rows `stride` floats apart), through the C entry `entry`
+        -> result(count, offsets, prims, visits).  One pass of the stream protocol per call, the queries recorded once."""
         import torch
         n = boxes.shape[0]
         if cap is not None and n * cap > 2 ** 31 - 1:
             raise _query_invalid(f"{n} boxes x cap {cap} exceed INT32_MAX entries")
         count = torch.zeros(n, dtype=torch.int32, device=dev)
         vis = torch.zeros(n, dtype=torch.int32, device=dev) if visits else None
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-
-        def query(offsets, cap_, prims, counts, vis_):
-            ext.wait_stream(cur)             # the boxes (and the outputs' allocation and fill) are ready before the query starts
-            self._check(entry(self._h, p(boxes), stride, n, p(offsets), cap_, p(prims), p(counts), p(vis_)))
-            cur.wait_stream(ext)             # torch's work after this call sees the answers
-
-        if cap is not None:
-            offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * cap).to(torch.int32)
-            prims = torch.full((n * cap,), -1, dtype=torch.int32, device=dev)
-            if n:
-                query(None, cap, prims, count, vis)          # (cap = 0: no prims, the counts alone)
-        else:
-            offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
-            total = 0
-            if n:
-                query(None, 0, None, count, vis)
-                scan = torch.cumsum(count, 0, dtype=torch.int64)
-                total = int(scan[-1])        # (the one host wait of the exact form: the list's allocation needs the total)
-                if total > 2 ** 31 - 1:
-                    raise _query_invalid(f"the lists hold {total} entries, beyond INT32_MAX")
-                offsets[1:] = scan.to(torch.int32)
-            prims = torch.full((total,), -1, dtype=torch.int32, device=dev)
-            if total:
-                query(offsets, 0, prims, None, None)
-        boxes.record_stream(cur)             # (never tied to the library stream: it dies with the context)
+        p = _ptr0
+        with self._library_stream(dev, (boxes,)) as run:
+            if cap is not None:
+                offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * cap).to(torch.int32)
+                prims = torch.full((n * cap,), -1, dtype=torch.int32, device=dev)
+                if n:
+                    run(entry, p(boxes), stride, n, None, cap, p(prims), p(count), p(vis))          # (cap = 0: no prims, the counts alone)
+            else:
+                offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+                total = 0
+                if n:
+                    run(entry, p(boxes), stride, n, None, 0, None, p(count), p(vis))
+                    scan = torch.cumsum(count, 0, dtype=torch.int64)
+                    total = int(scan[-1])        # (the one host wait of the exact form: the list's allocation needs the total)
+                    if total > 2 ** 31 - 1:
+                        raise _query_invalid(f"the lists hold {total} entries, beyond INT32_MAX")
+                    offsets[1:] = scan.to(torch.int32)
+                prims = torch.full((total,), -1, dtype=torch.int32, device=dev)
+                if total:
+                    run(entry, p(boxes), stride, n, p(offsets), 0, p(prims), None, None)
         return result(count, offsets, prims, vis)
 
     def tri_overlaps(self, qtris, cap=None, visits=False) -> TriOverlaps:
@@ -2984,16 +2839,7 @@ class Renderer:
         NaN component marks an empty slot.  cap, visits, the numpy / torch paths, stream ordering and lifetimes as box_overlaps; visits equals
         box_overlaps' for the boxes of the queries' points.  A self query lists every neighbour that shares a vertex: filter `.pairs()` by the index
         buffer.  One lane walks one query."""
-        cap = _box_cap(cap)
-        if isinstance(qtris, np.ndarray):
-            call = lambda *a: self._check(lib().rt_query_tris_host(self._h, *a))
-            return _numpy_box_query(call, qtris, cap, visits, rows=_numpy_tris, result=TriOverlaps)
-        import torch
-        if not isinstance(qtris, torch.Tensor):
-            raise _query_invalid("qtris must be a numpy array or a torch tensor")
-        dev = self._query_device(qtris, dtype=torch.float32)
-        stride = _tri_rows(tuple(qtris.shape), 1, qtris.stride())
-        return self._device_overlaps(lib().rt_query_tris, TriOverlaps, qtris, stride, dev, cap, visits)
+        return self._overlap_query("rt_query_tris", TriOverlaps, _QTRIS, qtris, cap, visits)
 
     def hull_overlaps(self, hulls, cap=None, visits=False) -> HullOverlaps:
         """The rows of the uploaded BVH or the dynamic mesh that overlap each convex hexahedron (rt_query_hulls) -> HullOverlaps, equal
@@ -3001,16 +2847,7 @@ class Renderer:
         NaN among the 24 floats marks an empty slot.  box_corners and rect_frusta make hulls of boxes under matrices and of rects of the frame.  cap,
         visits, the numpy / torch paths, stream ordering and lifetimes as box_overlaps; visits never exceeds box_overlaps' for the boxes of the
         hulls' corners.  One lane walks one hull."""
-        cap = _box_cap(cap)
-        if isinstance(hulls, np.ndarray):
-            call = lambda *a: self._check(lib().rt_query_hulls_host(self._h, *a))
-            return _numpy_box_query(call, hulls, cap, visits, rows=_numpy_hulls, result=HullOverlaps)
-        import torch
-        if not isinstance(hulls, torch.Tensor):
-            raise _query_invalid("hulls must be a numpy array or a torch tensor")
-        dev = self._query_device(hulls, dtype=torch.float32)
-        stride = _hull_rows(tuple(hulls.shape), 1, hulls.stride())
-        return self._device_overlaps(lib().rt_query_hulls, HullOverlaps, hulls, stride, dev, cap, visits)
+        return self._overlap_query("rt_query_hulls", HullOverlaps, _HULLS, hulls, cap, visits)
 
     def pick_rects(self, u, rects, t_near=0.0, t_far=None, cap=None, visits=False) -> HullOverlaps:
         """Marquee picking (rt_pick_rects): the rows of the uploaded BVH or the dynamic mesh inside the frustum behind each rect of u's
@@ -3022,85 +2859,13 @@ class Renderer:
         if not isinstance(u, RtUniforms):
             raise _query_invalid("u must be an RtUniforms")
         tn, tf = float(t_near), -1.0 if t_far is None else float(t_far)
-        if isinstance(rects, np.ndarray):
-            n, stride = _numpy_rects(rects)
-            corners = np.zeros((n, 24), np.float32)
-            pc = C.c_void_p(corners.ctypes.data) if n else None
-            call = lambda r, _stride, n_, *a: self._check(lib().rt_pick_rects_host(self._h, C.byref(u), r, stride, n_, tn, tf, pc, *a))
-            ans = _numpy_box_query(call, rects, cap, visits, rows=lambda _r: (n, stride), result=HullOverlaps)
-            ans.corners = corners
-            return ans
-        import torch
-        if not isinstance(rects, torch.Tensor):
-            raise _query_invalid("rects must be a numpy array or a torch tensor")
-        dev = self._query_device(rects, dtype=torch.float32)
-        stride = _rect_rows(rects, 1, rects.stride() if rects.dim() == 2 else (0, 0))
-        corners = torch.zeros((rects.shape[0], 24), dtype=torch.float32, device=dev)
-        pc = C.c_void_p(corners.data_ptr()) if corners.numel() else None
-        entry = lambda h, r, stride_, n_, *a: lib().rt_pick_rects(h, C.byref(u), r, stride_, n_, tn, tf, pc, *a)
-        ans = self._device_overlaps(entry, HullOverlaps, rects, stride, dev, cap, visits)
+        dev, n, stride = _row_array(_RECTS, rects, self)
+        corners = _new(dev, (n, 24), zero=True)
+        pc = _ptr0(corners)
+        adapt = lambda entry: lambda h, r, stride_, n_, *a: entry(h, C.byref(u), r, stride_, n_, tn, tf, pc, *a)
+        ans = self._overlaps("rt_pick_rects", HullOverlaps, dev, n, stride, rects, cap, visits, adapt)
         ans.corners = corners
         return ans
-
-    def _query_device(self, *arrays, dtype):
-        import torch
-        dev = torch.device("cuda", self.device)
-        for a in arrays:
-            if a is None:
-                continue
-            if a.dtype != dtype:
-                raise _query_invalid(f"expected {dtype}, got {a.dtype}")
-            if a.device != dev:
-                raise _query_invalid(f"a tensor is on {a.device}, the context on {dev}")
-        return dev
-
-    def _scene_query_numpy(self, u, kind, flags, rays, xy, tmax, n, normals, points):
-        p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-        if kind == RT_QUERY_ANY:
-            o, os_, d, ds = rays
-            occ = np.zeros(n, np.uint8)
-            self._check(lib().rt_trace_scene_rays_host(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n, None, None, None, None, p(occ)))
-            return occ.view(bool)
-        rec, obj = np.zeros((n, 4), np.float32), np.zeros(n, np.int32)
-        nrm = np.zeros((n, 3), np.float32) if normals else None
-        pts = np.zeros((n, 3), np.float32) if points else None
-        if xy is not None:
-            self._check(lib().rt_pick_pixels_host(self._h, C.byref(u), p(xy), n, p(rec), p(obj), p(nrm), p(pts)))
-        else:
-            o, os_, d, ds = rays
-            self._check(lib().rt_trace_scene_rays_host(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n, p(rec), p(obj), p(nrm), p(pts), None))
-        return SceneHits(rec, obj, nrm, pts)
-
-    def _scene_query_torch(self, dev, u, kind, flags, rays, xy, tmax, n, normals, points):
-        """The zero-copy path: stream ordering and lifetimes exactly as _trace_rays_torch."""
-        import torch
-        if kind == RT_QUERY_ANY:
-            out, obj, nrm, pts = torch.zeros(n, dtype=torch.uint8, device=dev), None, None, None
-        else:
-            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            obj = torch.empty(n, dtype=torch.int32, device=dev)
-            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
-            pts = torch.empty((n, 3), dtype=torch.float32, device=dev) if points else None
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                 # the rays (and the outputs' allocation) are ready before the query starts
-        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        if xy is not None:
-            self._check(lib().rt_pick_pixels(self._h, C.byref(u), p(xy), n, p(out), p(obj), p(nrm), p(pts)))
-            inputs = (xy,)
-        else:
-            o, os_, d, ds = rays
-            self._check(lib().rt_trace_scene_rays(self._h, C.byref(u), kind, flags, p(o), os_, p(d), ds, p(tmax), n,
-                                                  p(out) if kind == RT_QUERY_CLOSEST else None, p(obj), p(nrm), p(pts),
-                                                  p(out) if kind == RT_QUERY_ANY else None))
-            inputs = (o, d, tmax)
-        cur.wait_stream(ext)                 # torch's work after this call sees the answers
-        for a in inputs:                     # (never tied to the library stream: it dies with the context)
-            if a is not None:
-                a.record_stream(cur)
-        if kind == RT_QUERY_ANY:
-            return out.view(torch.bool)
-        return SceneHits(out, obj, nrm, pts)
 
     def raster_mesh(self, slot, positions, indices=None):
         """Upload one mesh for the raster preview (Mesh::setupMesh); positions [N,3] float32, indices uint32 triples.  None frees the slot."""
@@ -3137,26 +2902,14 @@ class Renderer:
         (as_torch=None: when it imports) tensors that alias the device buffers, zero-copy and without a host wait: torch's current stream is made to
         wait for the library stream, as trace_rays does it; prim_id and depth24 are int32 views of the uint32 words (the background id reads -1).
         They are valid until a raster call grows the buffers or resize().  Else numpy copies (read_raster)."""
-        if as_torch is None:
-            try:
-                import torch  # noqa: F401
-                as_torch = True
-            except ImportError:
-                as_torch = False
         a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
         self._check(lib().rt_raster_targets(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
-        if not as_torch:
+        if not _wants_torch(as_torch):
             return self.read_raster()
         import torch
         dev = torch.device("cuda", self.device)
         h, w = self.height, self.width
-
-        def view(ptr, shape, typestr):
-            class _View:   # __cuda_array_interface__: the library owns the memory, the tensor only views it
-                __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
-            return torch.as_tensor(_View(), device=dev)
-
-        out = view(a.value, (h, w, 4), "|u1"), view(b.value, (h, w), "<i4"), view(c.value, (h, w), "<i4")
+        out = self._alias(a.value, (h, w, 4), "|u1"), self._alias(b.value, (h, w), "<i4"), self._alias(c.value, (h, w), "<i4")
         torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(self.stream(), device=dev))   # torch's reads see the raster frame
         return out
 

@@ -8,33 +8,21 @@ import numpy as np
 
 import analytic_ref as ar
 import nearest_ref
+import overlap_ref as orf
 
 f32 = np.float32
 MESHES = nearest_ref.MESHES
 mesh = nearest_ref.mesh
 _idx = nearest_ref._idx
+_min3, _max3, boxes_overlap, _leaves = orf.min3, orf.max3, orf.boxes_overlap, orf.leaves
 # the ten axes that are not box axes, in the order of Sat.sep[3:]
 AXES = ("normal", "e1 x X", "e1 x Y", "e1 x Z", "(e2-e1) x X", "(e2-e1) x Y", "(e2-e1) x Z", "e2 x X", "e2 x Y", "e2 x Z")
-
-
-def _min3(a, b, c):
-    return np.fmin(np.fmin(a, b), c)                       # a NaN operand is ignored
-
-
-def _max3(a, b, c):
-    return np.fmax(np.fmax(a, b), c)
 
 
 def live(boxes):
     """[N] bool: neither a NaN component nor lo > hi on any axis."""
     with np.errstate(all="ignore"):
         return (boxes[:, 0:3] <= boxes[:, 3:6]).all(1)
-
-
-def boxes_overlap(bmin, bmax, lo, hi):
-    """Closed boxes [M,3] against queries [N,3] -> [N,M]: comparisons only."""
-    with np.errstate(all="ignore"):
-        return (~(bmax[None] < lo[:, None]) & ~(hi[:, None] < bmin[None])).all(-1)
 
 
 def _edge_axis(n1, n2, v1, v2, l1, h1, l2, h2):
@@ -80,62 +68,16 @@ class Sat:
         self.accept = ~self.sep.any(0) & self.live[:, None]
 
 
-class Walk:
-    """An explicit depth-first walk of nodes12 for all boxes at once, the right child before the left: `order` [T], the rows in the order the walk of a
-    box that overlaps everything meets them (any box's walk meets a subsequence of it); path [N,T] bool, every node box from the root to the row's
-    leaf overlaps the box; visits [N], the boxes tested: 1 + twice the inner nodes entered, 0 for an empty slot."""
-
-    def __init__(self, nodes12, n_tris, boxes):
-        nodes12, boxes = np.asarray(nodes12, f32), np.ascontiguousarray(boxes[:, :6], f32)
-        N = boxes.shape[0]
-        alive = live(boxes)
-        ov = boxes_overlap(nodes12[:, 0:3], nodes12[:, 4:7], boxes[:, 0:3], boxes[:, 3:6]) & alive[:, None]
-        self.path = np.zeros((N, n_tris), bool)
-        self.visits = alive.astype(np.int32)               # the root box
-        order = []
-        stack = [(0, ov[:, 0])]
-        while stack:
-            ni, entered = stack.pop()
-            count = _idx(nodes12[ni, 9])
-            if count > 0:
-                first = _idx(nodes12[ni, 8])
-                order.extend(range(first, first + count))
-                self.path[:, first:first + count] = entered[:, None]
-            else:
-                self.visits += 2 * entered.astype(np.int32)
-                l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
-                stack.append((l, entered & ov[:, l]))
-                stack.append((r, entered & ov[:, r]))      # popped first
-        self.order = np.array(order, np.int64)
+def Walk(nodes12, n_tris, boxes):
+    """overlap_ref.Walk for boxes [N,6]: a node is entered where its box overlaps the query box."""
+    boxes = np.ascontiguousarray(boxes[:, :6], f32)
+    alive = live(boxes)
+    return orf.Walk(nodes12, n_tris, orf.box_enter(nodes12, boxes, alive), alive)
 
 
-class Answer:
-    """The definition's answer for boxes against (nodes12, tris12): sat, walk, accepted = sat.accept & walk.path [N,T], count [N] int32, and lists --
-    lists[i] the accepted rows of box i in walk order (int32 arrays)."""
-
-    def __init__(self, nodes12, tris12, boxes):
-        self.sat = Sat(tris12, boxes)
-        self.walk = Walk(nodes12, tris12.shape[0], boxes)
-        self.accepted = self.sat.accept & self.walk.path
-        self.count = self.accepted.sum(1).astype(np.int32)
-        in_order = self.accepted[:, self.walk.order]
-        self.lists = [self.walk.order[in_order[i]].astype(np.int32) for i in range(boxes.shape[0])]
-        self.visits = self.walk.visits
-
-    def offsets(self):
-        return np.concatenate([[0], np.cumsum(self.count)]).astype(np.int32)
-
-    def filled(self, offsets=None, cap=None, sentinel=-77):
-        """What a call leaves of a prims array pre-filled with `sentinel`: slot i (offsets, or i * cap) holds the first min(capacity, count) rows."""
-        n = len(self.lists)
-        if offsets is None:
-            offsets = (np.arange(n + 1, dtype=np.int64) * cap)
-        out = np.full(int(max(offsets[-1], 0)), sentinel, np.int32)
-        for i, rows in enumerate(self.lists):
-            room = max(int(offsets[i + 1]) - int(offsets[i]), 0)
-            k = min(room, rows.size)
-            out[int(offsets[i]):int(offsets[i]) + k] = rows[:k]
-        return out
+def Answer(nodes12, tris12, boxes):
+    """overlap_ref.Answer of Sat and Walk for boxes against (nodes12, tris12)."""
+    return orf.Answer(Sat(tris12, boxes), Walk(nodes12, tris12.shape[0], boxes))
 
 
 def sat64(tris12, boxes):
@@ -160,10 +102,6 @@ def sat64(tris12, boxes):
 
 
 # ---------------------------------------------------------------- the box sets the tests share
-
-def _leaves(nodes):
-    return np.array([k for k in range(nodes.shape[0]) if _idx(nodes[k, 9]) > 0])
-
 
 def _directed(a, b, c, rng, per_axis):
     """Boxes placed to be parted from one row by one of the ten non-box axes alone.  Edge axis cross(unit_k, f): the box spans the row generously along

@@ -11,20 +11,17 @@ import numpy as np
 import analytic_ref as ar
 import nearest_ref
 import opengl_raytracing_amd as rt
+import overlap_ref as orf
 
 f32 = np.float32
 MESHES = nearest_ref.MESHES
 mesh = nearest_ref.mesh
 _idx = nearest_ref._idx
+_min3, _max3, _sub, row_points, boxes_overlap, _leaves, _rotation = orf.min3, orf.max3, orf.sub, orf.row_points, orf.boxes_overlap, orf.leaves, orf.rotation
 FACES = ((0, 2, 4, 6), (1, 3, 5, 7), (0, 1, 4, 5), (2, 3, 6, 7), (0, 1, 2, 3), (4, 5, 6, 7))
 EDGES = ((0, 1), (2, 3), (4, 5), (6, 7), (0, 2), (1, 3), (4, 6), (5, 7), (0, 4), (1, 5), (2, 6), (3, 7))
 # the 43 projected axes, in the order of Sat.sep[3:]
 AXES = tuple(f"face {''.join(map(str, f))}" for f in FACES) + ("n",) + tuple(f"f{i + 1} x d{a}{b}" for (a, b) in EDGES for i in range(3))
-
-
-def _sub(a, b):
-    with np.errstate(all="ignore"):
-        return (a - b).astype(f32)
 
 
 def _mul(a, b):
@@ -35,14 +32,6 @@ def _mul(a, b):
 def _add(a, b):
     with np.errstate(all="ignore"):
         return (a + b).astype(f32)
-
-
-def _min3(a, b, c):
-    return np.fmin(np.fmin(a, b), c)                       # a NaN operand is ignored
-
-
-def _max3(a, b, c):
-    return np.fmax(np.fmax(a, b), c)
 
 
 def corners(q24):
@@ -59,18 +48,6 @@ def aabb(q24):
     """[N,6] float32: lo, hi -- the fmin / fmax of the eight corners per component."""
     c = corners(q24)
     return np.concatenate([np.fmin.reduce(c, 1), np.fmax.reduce(c, 1)], 1)
-
-
-def row_points(tris12):
-    """a, b, c of every row: one rounded add per component."""
-    t = np.asarray(tris12, f32)
-    return t[:, 0:3], _add(t[:, 0:3], t[:, 4:7]), _add(t[:, 0:3], t[:, 8:11])
-
-
-def boxes_overlap(bmin, bmax, lo, hi):
-    """Closed boxes [M,3] against queries [N,3] -> [N,M]: comparisons only."""
-    with np.errstate(all="ignore"):
-        return (~(bmax[None] < lo[:, None]) & ~(hi[:, None] < bmin[None])).all(-1)
 
 
 def normals(c):
@@ -171,89 +148,23 @@ class Sat:
         self.accept = self.box_ok & ~self.sep[3:].any(0)
 
 
-class Walk:
-    """An explicit depth-first walk of nodes12 for all queries at once, the right child before the left: `order` [T], the rows in the order the walk
-    of a query that enters everything meets them; path [N,T] bool, every node from the root to the row's leaf passes the node test; visits [N], the
-    boxes tested: 1 + twice the inner nodes entered, 0 for an empty slot; culled [N,M], the nodes a face normal rejected although their boxes overlap
-    [lo, hi] and the walk reached them."""
-
-    def __init__(self, nodes12, n_tris, q24):
-        nodes12 = np.asarray(nodes12, f32)
-        N = np.asarray(q24).shape[0]
-        alive = live(q24)
-        enter, by_normal = node_test(nodes12[:, 0:3], nodes12[:, 4:7], q24)
-        self.path = np.zeros((N, n_tris), bool)
-        self.visits = alive.astype(np.int32)               # the root box
-        self.culled = np.zeros_like(by_normal)
-        self.culled[:, 0] = by_normal[:, 0]
-        order = []
-        stack = [(0, enter[:, 0])]
-        while stack:
-            ni, entered = stack.pop()
-            count = _idx(nodes12[ni, 9])
-            if count > 0:
-                first = _idx(nodes12[ni, 8])
-                order.extend(range(first, first + count))
-                self.path[:, first:first + count] = entered[:, None]
-            else:
-                self.visits += 2 * entered.astype(np.int32)
-                l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
-                self.culled[:, l] = entered & by_normal[:, l]
-                self.culled[:, r] = entered & by_normal[:, r]
-                stack.append((l, entered & enter[:, l]))
-                stack.append((r, entered & enter[:, r]))      # popped first
-        self.order = np.array(order, np.int64)
+def Walk(nodes12, n_tris, q24):
+    """overlap_ref.Walk for hulls [N,24] under node_test: with `culled`, the nodes a face normal rejected although their boxes overlap [lo, hi] and
+    the walk reached them."""
+    nodes12 = np.asarray(nodes12, f32)
+    enter, by_normal = node_test(nodes12[:, 0:3], nodes12[:, 4:7], q24)
+    return orf.Walk(nodes12, n_tris, enter, live(q24), by_normal)
 
 
-class Answer:
-    """The definition's answer for queries against (nodes12, tris12): sat, walk, accepted = sat.accept & walk.path [N,T], count [N] int32, and lists --
-    lists[i] the accepted rows of query i in walk order (int32 arrays)."""
-
-    def __init__(self, nodes12, tris12, q24):
-        self.sat = Sat(tris12, q24)
-        self.walk = Walk(nodes12, tris12.shape[0], q24)
-        self.accepted = self.sat.accept & self.walk.path
-        self.count = self.accepted.sum(1).astype(np.int32)
-        in_order = self.accepted[:, self.walk.order]
-        self.lists = [self.walk.order[in_order[i]].astype(np.int32) for i in range(np.asarray(q24).shape[0])]
-        self.visits = self.walk.visits
-
-    def offsets(self):
-        return np.concatenate([[0], np.cumsum(self.count)]).astype(np.int32)
-
-    def filled(self, offsets=None, cap=None, sentinel=-77):
-        """What a call leaves of a prims array pre-filled with `sentinel`: slot i (offsets, or i * cap) holds the first min(capacity, count) rows."""
-        n = len(self.lists)
-        if offsets is None:
-            offsets = (np.arange(n + 1, dtype=np.int64) * cap)
-        out = np.full(int(max(offsets[-1], 0)), sentinel, np.int32)
-        for i, rows in enumerate(self.lists):
-            room = max(int(offsets[i + 1]) - int(offsets[i]), 0)
-            k = min(room, rows.size)
-            out[int(offsets[i]):int(offsets[i]) + k] = rows[:k]
-        return out
-
-    def pairs(self):
-        return np.array([(i, t) for i, rows in enumerate(self.lists) for t in rows], np.int32).reshape(-1, 2)
+def Answer(nodes12, tris12, q24):
+    """overlap_ref.Answer of Sat and Walk for queries against (nodes12, tris12)."""
+    return orf.Answer(Sat(tris12, q24), Walk(nodes12, tris12.shape[0], q24))
 
 
 def box_visits(nodes12, q24):
     """[N] int32: the visits of the box query on the hulls' [lo, hi] -- the walk without the six normals."""
-    nodes12 = np.asarray(nodes12, f32)
-    box = aabb(q24)
     alive = live(q24)
-    ov = boxes_overlap(nodes12[:, 0:3], nodes12[:, 4:7], box[:, 0:3], box[:, 3:6]) & alive[:, None]
-    visits = alive.astype(np.int32)
-    stack = [(0, ov[:, 0])]
-    while stack:
-        ni, entered = stack.pop()
-        if _idx(nodes12[ni, 9]) > 0:
-            continue
-        visits += 2 * entered.astype(np.int32)
-        l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
-        stack.append((l, entered & ov[:, l]))
-        stack.append((r, entered & ov[:, r]))
-    return visits
+    return orf.Walk(nodes12, 0, orf.box_enter(nodes12, aabb(q24), alive), alive).visits
 
 
 # ---------------------------------------------------------------- float64: the 43 axes, and clipping
@@ -379,17 +290,6 @@ def camera(eye, target, w, h, tan_half_fov=0.5, jitter=None, up=(0.0, 1.0, 0.0))
 
 
 # ---------------------------------------------------------------- the query sets the tests share
-
-def _leaves(nodes):
-    return np.array([k for k in range(nodes.shape[0]) if _idx(nodes[k, 9]) > 0])
-
-
-def _rotation(rng):
-    q = rng.normal(size=4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
 
 CUBE = np.array([[1.0 if k >> a & 1 else -1.0 for a in range(3)] for k in range(8)])
 

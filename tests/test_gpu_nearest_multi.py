@@ -18,6 +18,7 @@ import nearest_multi_ref as mref
 import nearest_ref as ref
 import opengl_raytracing_amd as rt
 import scenes
+from query_gpu import PIPELINES, _clean_env, dev as _dev, np_of as _np, to as _to  # noqa: F401  (_clean_env: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,30 +26,6 @@ f32 = np.float32
 bits = ref.bits
 NS = (1, 63, 64, 65, 257, 2049)
 KS = (0, 1, 2, 4, 8, 32)
-OPTION_VARS = ("RT_COOP", "RT_FUSED", "RT_IMPLICIT", "RT_NEAR_FIRST", "RT_QNODES", "RT_QNODES_SPARSE_BOXES", "RT_ANYHIT_TREE", "RT_LEAFB",
-               "RT_LEAFB_CLOSEST", "RT_QUAD_REFILL", "RT_REFILL_MIN", "RT_GUIDED", "RT_CHUNK", "RT_MIN_SEARCH", "RT_REVERSE", "RT_DENSE_TAKE",
-               "RT_TRACE_STATS", "RT_TRACE_TIMING", "RT_DEBUG_SKIP_TRAVERSAL", "RT_NEAREST_FAR_FIRST")
-PIPELINES = {"megakernel": rt.RT_PIPELINE_MEGAKERNEL, "wavefront": rt.RT_PIPELINE_WAVEFRONT}
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for v in OPTION_VARS:
-        monkeypatch.delenv(v, raising=False)
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _to(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.array(a, copy=True, order="C")).to(_dev())      # (the shared fixtures are read-only)
-
-
-def _np(a):
-    return a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
 
 
 def _same(got, want, what, pick=None):

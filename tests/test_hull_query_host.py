@@ -4,7 +4,8 @@ the entries no list reaches left as they were, every refusal writing nothing, th
 although the node test culls by six normals as well, every list ascends), the shared-point property, walk order on a hand-made tree, what the fixtures
 must hold for a wrong test to show, the float64 tests, and the corner makers rt.box_corners and rt.rect_frusta against their numpy definitions.
 Three of these -- the path mask and ascending lists, the telling cases, the generic set's numpy half -- assert properties of the definition and of the
-fixtures as hull_query_ref.py states them, not of the library: they say that the other tests compare the library with something worth comparing with."""
+fixtures as hull_query_ref.py states them, not of the library: they say that the other tests compare the library with something worth comparing with.
+The bodies the three overlap queries share are overlap_cases.py's."""
 import ctypes as C
 
 import numpy as np
@@ -12,19 +13,10 @@ import pytest
 
 import hull_query_ref as ref
 import opengl_raytracing_amd as rt
+import overlap_cases as oc
+from overlap_cases import SENTINEL, _lists_of
 
 f32 = np.float32
-SENTINEL = -77
-CAPS = (0, 1, 3, 8)
-
-
-def _raw(nodes, tris, hulls, stride, n, offsets, cap, prims, counts):
-    p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    return rt.lib().rt_hull_overlaps(p(nodes), nodes.shape[0], p(tris), tris.shape[0], p(hulls), stride, n, p(offsets), cap, p(prims), p(counts))
-
-
-def _lists_of(got):
-    return [got.prims[got.offsets[i]:got.offsets[i] + min(got.count[i], got.offsets[i + 1] - got.offsets[i])] for i in range(len(got))]
 
 
 def _same_bits(a, b):
@@ -35,99 +27,16 @@ def _same_bits(a, b):
 
 @pytest.mark.parametrize("mesh", ref.MESHES)
 def test_counts_and_lists_equal_the_numpy_definition(mesh):
-    nodes, tris, q = ref.case(mesh)
-    want = ref.reference(mesh)
-    assert q.shape[0] >= 2049
-    got = rt.hull_overlaps(nodes, tris, q)
-    bad = np.flatnonzero(got.count != want.count)
-    assert bad.size == 0, (mesh, bad[:8], got.count[bad[:8]], want.count[bad[:8]], q[bad[:2]])
-    assert isinstance(got, rt.HullOverlaps) and isinstance(got, rt.TriOverlaps) and got.corners is None
-    assert np.array_equal(got.offsets, want.offsets()) and got.prims.dtype == np.int32
-    assert np.array_equal(got.prims, want.filled(want.offsets())), mesh
-    pairs = got.pairs()
-    assert pairs.dtype == np.int32 and np.array_equal(pairs, want.pairs())
-    for cap in CAPS:
-        got = rt.hull_overlaps(nodes, tris, q, cap=cap)
-        assert np.array_equal(got.count, want.count) and np.array_equal(got.offsets, np.arange(q.shape[0] + 1) * cap)
-        assert np.array_equal(got.prims, want.filled(cap=cap, sentinel=-1)), (mesh, cap)
-        kept = got.pairs()                                             # the written entries alone: the first min(cap, count) of every list
-        assert np.array_equal(kept, np.array([(i, t) for i, rows in enumerate(want.lists) for t in rows[:cap]], np.int32).reshape(-1, 2))
-    hits = rt.hull_overlaps(nodes, tris, q[:65], cap=3).hits()
-    assert hits.shape == (195, 4) and np.array_equal(hits.view(np.int32)[:, 1], want.filled(cap=3, sentinel=-1)[:195])
+    oc.counts_and_lists_equal_the_numpy_definition(oc.HULL, mesh)
 
 
 @pytest.mark.parametrize("stride", [24, 25, 32])
 def test_strided_queries_counts_alone_lists_alone_and_sentinels(stride):
-    nodes, tris, q = ref.case("bunny")
-    want = ref.reference("bunny")
-    N = q.shape[0]
-    wide = np.full((N, stride), np.nan, f32)
-    wide[:, :24] = q
-    flat = np.ascontiguousarray(wide.reshape(-1)[:(N - 1) * stride + 24])         # exactly as long as a call may read
-    view = np.lib.stride_tricks.as_strided(flat, (N, 24), (4 * stride, 4))
-    got = rt.hull_overlaps(nodes, tris, view)
-    assert np.array_equal(got.count, want.count) and np.array_equal(got.prims, want.filled(want.offsets()))
-    if stride == 24:
-        got = rt.hull_overlaps(nodes, tris, flat.reshape(N, 8, 3))                # [N,8,3]
-    else:
-        got = rt.hull_overlaps(nodes, tris, np.lib.stride_tricks.as_strided(flat, (N, 8, 3), (4 * stride, 12, 4)))
-    assert np.array_equal(got.count, want.count) and np.array_equal(got.prims, want.filled(want.offsets()))
-    # counts alone
-    counts = np.full(N, SENTINEL, np.int32)
-    assert _raw(nodes, tris, flat, stride, N, None, 0, None, counts) == rt.RT_OK and np.array_equal(counts, want.count)
-    # lists alone: exact slots with a guard word behind the last, slots one short, and fixed capacities
-    off = want.offsets()
-    prims = np.full(off[-1] + 1, SENTINEL, np.int32)
-    assert _raw(nodes, tris, flat, stride, N, off, 0, prims, None) == rt.RT_OK
-    assert np.array_equal(prims[:-1], want.filled(off)) and prims[-1] == SENTINEL
-    short = np.concatenate([[0], np.cumsum(np.maximum(want.count - 1, 0))]).astype(np.int32)
-    prims = np.full(short[-1], SENTINEL, np.int32)
-    counts[:] = SENTINEL
-    assert _raw(nodes, tris, flat, stride, N, short, 0, prims, counts) == rt.RT_OK
-    assert np.array_equal(prims, want.filled(short)) and np.array_equal(counts, want.count)
-    for cap in CAPS:
-        prims = np.full(N * cap, SENTINEL, np.int32)
-        assert _raw(nodes, tris, flat, stride, N, None, cap, prims if cap else np.zeros(1, np.int32), None) == rt.RT_OK
-        filled = want.filled(cap=cap, sentinel=SENTINEL)
-        assert np.array_equal(prims, filled), cap
-        if cap:
-            assert (filled == SENTINEL).any() and ((prims == SENTINEL) == (np.arange(N * cap) % cap >= np.repeat(want.count, cap))).all()
-    # a slot of negative length, and one with a negative start, hold nothing
-    odd = np.array([3, 1, 1, -5, 2, 2], np.int32)
-    prims = np.full(8, SENTINEL, np.int32)
-    counts = np.full(5, SENTINEL, np.int32)
-    assert _raw(nodes, tris, flat, stride, 5, odd, 0, prims, counts) == rt.RT_OK
-    assert np.array_equal(counts, want.count[:5]) and (prims == SENTINEL).all()
+    oc.strided_counts_alone_lists_alone_and_sentinels(oc.HULL, stride)
 
 
 def test_every_refusal_writes_nothing():
-    nodes, tris, q = ref.case("layers")
-    q = np.array(q[1:5])
-    prims, counts = np.full(32, SENTINEL, np.int32), np.full(4, SENTINEL, np.int32)
-    off = np.array([0, 8, 16, 24, 32], np.int32)
-    ok = dict(nodes=nodes, tris=tris, hulls=q, stride=24, n=4, offsets=off, cap=0, prims=prims, counts=counts)
-    call = lambda **kw: _raw(**dict(ok, **kw))
-    assert call(n=-1) == rt.RT_ERR_INVALID
-    assert call(stride=23) == rt.RT_ERR_INVALID
-    assert call(hulls=None) == rt.RT_ERR_INVALID
-    assert call(prims=None, counts=None) == rt.RT_ERR_INVALID
-    assert call(offsets=None, cap=-1) == rt.RT_ERR_INVALID
-    assert call(offsets=None, cap=(1 << 31) // 4 + 1) == rt.RT_ERR_INVALID                   # n * cap beyond INT32_MAX
-    for link in (-1.0, 1e9, np.nan, float(nodes.shape[0]), 0.0):                             # nodes that are no tree over the rows
-        bad = nodes.copy()
-        bad[0, 3] = link
-        assert call(nodes=bad) == rt.RT_ERR_INVALID, link
-    assert (prims == SENTINEL).all() and (counts == SENTINEL).all()
-    assert _raw(nodes, tris, None, 24, 0, None, 0, None, None) == rt.RT_OK                    # n == 0: a no-op
-    assert call() == rt.RT_OK and (counts != SENTINEL).all()
-    for bad_call in (lambda: rt.hull_overlaps(nodes, tris, q[:, :23]), lambda: rt.hull_overlaps(nodes, tris, q.astype(np.float64)),
-                     lambda: rt.hull_overlaps(nodes, tris, q, cap=-1), lambda: rt.hull_overlaps(nodes, tris, list(q)),
-                     lambda: rt.hull_overlaps(nodes, tris, q.reshape(4, 8, 3).transpose(0, 2, 1)), lambda: rt.hull_overlaps(nodes, tris, q.reshape(2, 2, 24))):
-        with pytest.raises(rt.RtError) as e:
-            bad_call()
-        assert e.value.code == rt.RT_ERR_INVALID
-    empty = rt.hull_overlaps(nodes, tris, q[:0])
-    assert len(empty) == 0 and empty.prims.size == 0 and np.array_equal(empty.offsets, [0]) and empty.pairs().shape == (0, 2)
+    oc.every_refusal_writes_nothing(oc.HULL)
 
 
 # ---------------------------------------------------------------- 2: the properties of library-built trees, the shared point, and walk order
@@ -138,10 +47,7 @@ def test_the_path_mask_removes_nothing_and_every_list_ascends(mesh):
     through dot's own three steps, the least and the greatest kept at each -- contains dot(normal, p) of every point p inside the box, each step being
     monotone.  So a normal that parts a node from the hull's interval parts every row under it from the same interval, on the same axis of the row
     test: a row the row test accepts lies under entered nodes all the way up, whatever the node test culls."""
-    want = ref.reference(mesh)
-    assert not (want.sat.accept & ~want.walk.path).any()
-    assert np.array_equal(want.walk.order, np.arange(want.walk.order.size))
-    assert all((np.diff(rows) > 0).all() for rows in want.lists)
+    oc.the_path_mask_removes_nothing_and_every_list_ascends(oc.HULL, mesh)
 
 
 @pytest.mark.parametrize("mesh", ref.MESHES)
@@ -173,38 +79,7 @@ def test_a_tree_with_swapped_children_lists_in_walk_order():
     """23.5's three nodes by hand: the root's LEFT child holds rows 0, 1, its RIGHT child rows 2, 3.  The walk takes the right child first: 2, 3, 0, 1.
     With the children swapped in the root's links it is 0, 1, 2, 3.  Row x spans (x, 0, 0), (x + 0.5, 0, 0), (x, 0.5, 0.25).  The hulls: a slab about
     the plane y = 0.1 over all four rows; a thin box turned 20 degrees about z that crosses rows 1 and 2; a point inside the right child's box."""
-    t9 = np.array([[x, 0, 0, 0.5, 0, 0, 0, 0.5, 0.25] for x in (0.0, 1.0, 2.0, 3.0)], f32)
-    tris = np.zeros((4, 12), f32)
-    tris[:, 0:3], tris[:, 4:7], tris[:, 8:11] = t9[:, 0:3], t9[:, 3:6], t9[:, 6:9]
-
-    def box(rows):
-        v = np.concatenate([tris[rows, 0:3], tris[rows, 0:3] + tris[rows, 4:7], tris[rows, 0:3] + tris[rows, 8:11]])
-        return v.min(0), v.max(0)
-
-    nodes = np.zeros((3, 12), f32)
-    for k, rows in enumerate(([0, 1, 2, 3], [0, 1], [2, 3])):
-        nodes[k, 0:3], nodes[k, 4:7] = box(rows)
-    nodes[0, 3], nodes[0, 7] = 1, 2
-    nodes[1, 8], nodes[1, 9] = 0, 2
-    nodes[2, 8], nodes[2, 9] = 2, 2
-    co, si = np.cos(np.radians(20.0)), np.sin(np.radians(20.0))
-    turn = np.array([co, si, 0, 0, -si, co, 0, 0, 0, 0, 1, 0, 1.75, 0.2, 0.1, 1], f32)       # column-major: 20 degrees about z, to (1.75, 0.2, 0.1)
-    q = np.concatenate([rt.box_corners(np.array([[-1, 0.05, -1, 5, 0.15, 1]], f32)),
-                        rt.box_corners(np.array([[-0.9, -0.05, -0.5, 0.9, 0.05, 0.5]], f32), turn), np.tile(np.array([[2.6, 0.3, 0]], f32), (1, 8))])
-    got = rt.hull_overlaps(nodes, tris, q)
-    want = ref.Answer(nodes, tris, q)
-    assert [list(r) for r in _lists_of(got)] == [[2, 3, 0, 1], [2, 1], []] and [list(r) for r in want.lists] == [[2, 3, 0, 1], [2, 1], []]
-    assert list(want.visits) == [3, 3, 3]
-    assert np.array_equal(got.pairs(), [[0, 2], [0, 3], [0, 0], [0, 1], [1, 2], [1, 1]])
-    nodes[0, 3], nodes[0, 7] = 2, 1
-    got = rt.hull_overlaps(nodes, tris, q)
-    assert [list(r) for r in _lists_of(got)] == [[0, 1, 2, 3], [1, 2], []]
-    assert [list(r) for r in ref.Answer(nodes, tris, q).lists] == [[0, 1, 2, 3], [1, 2], []]
-    # condition (a) is part of the definition: shrink the right child's box off its rows, and the walk no longer reaches rows 2 and 3
-    nodes[2, 0] = 10.0
-    got = rt.hull_overlaps(nodes, tris, q)
-    assert [list(r) for r in _lists_of(got)] == [[0, 1], [1], []]
-    assert [list(r) for r in ref.Answer(nodes, tris, q).lists] == [[0, 1], [1], []]
+    oc.a_tree_with_swapped_children_lists_in_walk_order(oc.HULL)
 
 
 # ---------------------------------------------------------------- 3: the fixtures hold the cases where a wrong test shows

@@ -9,28 +9,18 @@ import numpy as np
 
 import analytic_ref as ar
 import nearest_ref
+import overlap_ref as orf
 
 f32 = np.float32
 MESHES = nearest_ref.MESHES
 mesh = nearest_ref.mesh
 _idx = nearest_ref._idx
+_min3, _max3, _sub, row_points, rows_as_tris, boxes_overlap = orf.min3, orf.max3, orf.sub, orf.row_points, orf.rows_as_tris, orf.boxes_overlap
+_leaves, _rotation = orf.leaves, orf.rotation
 # the seventeen projected axes, in the order of Sat.sep[3:]
 AXES = ("n", "m", "f1 x g1", "f1 x g2", "f1 x g3", "f2 x g1", "f2 x g2", "f2 x g3", "f3 x g1", "f3 x g2", "f3 x g3", "n x f1", "n x f2", "n x f3",
         "m x g1", "m x g2", "m x g3")
 IN_PLANE = slice(3 + 11, 3 + 17)                           # Sat.sep rows of the six in-plane axes
-
-
-def _min3(a, b, c):
-    return np.fmin(np.fmin(a, b), c)                       # a NaN operand is ignored
-
-
-def _max3(a, b, c):
-    return np.fmax(np.fmax(a, b), c)
-
-
-def _sub(a, b):
-    with np.errstate(all="ignore"):
-        return (a - b).astype(f32)
 
 
 def live(q9):
@@ -42,23 +32,6 @@ def aabb(q9):
     """[N,6] float32: qlo, qhi -- the fmin / fmax of the three points per component."""
     q = np.asarray(q9[:, :9], f32)
     return np.concatenate([_min3(q[:, 0:3], q[:, 3:6], q[:, 6:9]), _max3(q[:, 0:3], q[:, 3:6], q[:, 6:9])], 1)
-
-
-def row_points(tris12):
-    """a, b, c of every row: one rounded add per component."""
-    t = np.asarray(tris12, f32)
-    with np.errstate(all="ignore"):
-        return t[:, 0:3], (t[:, 0:3] + t[:, 4:7]).astype(f32), (t[:, 0:3] + t[:, 8:11]).astype(f32)
-
-
-def rows_as_tris(tris12):
-    return np.concatenate(row_points(tris12), 1)
-
-
-def boxes_overlap(bmin, bmax, lo, hi):
-    """Closed boxes [M,3] against queries [N,3] -> [N,M]: comparisons only."""
-    with np.errstate(all="ignore"):
-        return (~(bmax[None] < lo[:, None]) & ~(hi[:, None] < bmin[None])).all(-1)
 
 
 def _axis_sep(ax, T, Q):
@@ -103,66 +76,15 @@ class Sat:
         self.accept = ~self.sep.any(0) & self.live[:, None]
 
 
-class Walk:
-    """An explicit depth-first walk of nodes12 for all queries at once, the right child before the left: `order` [T], the rows in the order the walk
-    of a query that overlaps everything meets them; path [N,T] bool, every node box from the root to the row's leaf overlaps [qlo, qhi]; visits [N],
-    the boxes tested: 1 + twice the inner nodes entered, 0 for an empty slot."""
-
-    def __init__(self, nodes12, n_tris, q9):
-        nodes12 = np.asarray(nodes12, f32)
-        box = aabb(q9)
-        N = box.shape[0]
-        alive = live(q9)
-        ov = boxes_overlap(nodes12[:, 0:3], nodes12[:, 4:7], box[:, 0:3], box[:, 3:6]) & alive[:, None]
-        self.path = np.zeros((N, n_tris), bool)
-        self.visits = alive.astype(np.int32)               # the root box
-        order = []
-        stack = [(0, ov[:, 0])]
-        while stack:
-            ni, entered = stack.pop()
-            count = _idx(nodes12[ni, 9])
-            if count > 0:
-                first = _idx(nodes12[ni, 8])
-                order.extend(range(first, first + count))
-                self.path[:, first:first + count] = entered[:, None]
-            else:
-                self.visits += 2 * entered.astype(np.int32)
-                l, r = _idx(nodes12[ni, 3]), _idx(nodes12[ni, 7])
-                stack.append((l, entered & ov[:, l]))
-                stack.append((r, entered & ov[:, r]))      # popped first
-        self.order = np.array(order, np.int64)
+def Walk(nodes12, n_tris, q9):
+    """overlap_ref.Walk for query triangles [N,9]: a node is entered where its box overlaps [qlo, qhi]."""
+    alive = live(q9)
+    return orf.Walk(nodes12, n_tris, orf.box_enter(nodes12, aabb(q9), alive), alive)
 
 
-class Answer:
-    """The definition's answer for queries against (nodes12, tris12): sat, walk, accepted = sat.accept & walk.path [N,T], count [N] int32, and lists --
-    lists[i] the accepted rows of query i in walk order (int32 arrays)."""
-
-    def __init__(self, nodes12, tris12, q9):
-        self.sat = Sat(tris12, q9)
-        self.walk = Walk(nodes12, tris12.shape[0], q9)
-        self.accepted = self.sat.accept & self.walk.path
-        self.count = self.accepted.sum(1).astype(np.int32)
-        in_order = self.accepted[:, self.walk.order]
-        self.lists = [self.walk.order[in_order[i]].astype(np.int32) for i in range(q9.shape[0])]
-        self.visits = self.walk.visits
-
-    def offsets(self):
-        return np.concatenate([[0], np.cumsum(self.count)]).astype(np.int32)
-
-    def filled(self, offsets=None, cap=None, sentinel=-77):
-        """What a call leaves of a prims array pre-filled with `sentinel`: slot i (offsets, or i * cap) holds the first min(capacity, count) rows."""
-        n = len(self.lists)
-        if offsets is None:
-            offsets = (np.arange(n + 1, dtype=np.int64) * cap)
-        out = np.full(int(max(offsets[-1], 0)), sentinel, np.int32)
-        for i, rows in enumerate(self.lists):
-            room = max(int(offsets[i + 1]) - int(offsets[i]), 0)
-            k = min(room, rows.size)
-            out[int(offsets[i]):int(offsets[i]) + k] = rows[:k]
-        return out
-
-    def pairs(self):
-        return np.array([(i, t) for i, rows in enumerate(self.lists) for t in rows], np.int32).reshape(-1, 2)
+def Answer(nodes12, tris12, q9):
+    """overlap_ref.Answer of Sat and Walk for queries against (nodes12, tris12)."""
+    return orf.Answer(Sat(tris12, q9), Walk(nodes12, tris12.shape[0], q9))
 
 
 def sat64(tris12, q9):
@@ -187,17 +109,6 @@ def sat64(tris12, q9):
 
 
 # ---------------------------------------------------------------- the query sets the tests share
-
-def _leaves(nodes):
-    return np.array([k for k in range(nodes.shape[0]) if _idx(nodes[k, 9]) > 0])
-
-
-def _rotation(rng):
-    q = rng.normal(size=4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
 
 def _frame(P):
     """An orthonormal frame (u, v, w) of the triangle P [3,3] in float64: u along P1 - P0, w the normal.  None for a zero-area triangle."""
